@@ -23,6 +23,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with these extra
   cpu_baseline     the CPU oracle (a port; the reference cannot be built here) on the same job, on rank 0's host cores
   scaling_bounds   what N GPUs can do to a blocking frame (the build is replicated): strong and weak
 A failed parity gate makes the run exit non-zero.
+
+--dump-outputs DIR writes the match records of the last timed step (rank 0's, i.e. the gathered list at N > 1) as
+DIR/tmpl_idx.npy (float64), DIR/score.npy and DIR/transform.npy (float32, one row of 6 per match): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -31,10 +35,6 @@ import os
 import subprocess
 import sys
 import time
-
-# One HIP stream per pipeline slot (plus torch's): ask the runtime for enough hardware queues that
-# they do not share one (read at HIP initialisation, i.e. before torch is imported).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -153,6 +153,33 @@ def cpu_baseline(cfg, scene, tmpls, sample_templates, reps, warmup=True):
     }, m
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, records):
+    """The match records of one frame as float arrays: tmpl_idx (float64, exact for any index), score and transform
+    (float32, as computed).  Above DUMP_LIMIT_BYTES a fixed, seeded sample of the rows is written, in their original
+    order, with their positions as row.npy.  Returns the JSON object that describes what was written."""
+    records = np.asarray(records)
+    n = len(records)
+    rows = np.arange(n)
+    row_bytes = 8 + 4 + 6 * 4
+    sampled = n * row_bytes > DUMP_LIMIT_BYTES
+    if sampled:
+        keep = DUMP_LIMIT_BYTES // (row_bytes + 8)  # (+ row.npy)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    arrays = {"tmpl_idx": records["tmpl_idx"][rows].astype(np.float64),
+              "score": records["score"][rows].astype(np.float32),
+              "transform": records["transform"][rows].astype(np.float32).reshape(len(rows), 6)}
+    if sampled:
+        arrays["row"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in arrays), "matches": n, "rows_written": int(len(rows)),
+            "sampled": bool(sampled)}
+
+
 def relaunch_under_torchrun(args):
     """--gpus N without a launcher: start the N ranks as children (before anything touches the GPU) and exit with
     their code, so that a plain `python bench.py --gpus 8` reports an 8-GPU number instead of a 1-GPU one."""
@@ -195,7 +222,11 @@ def main():
                          "penalize -> sort_matches through `import openfdcm_amd as openfdcm` only) timed after the run (0 = skip)")
     ap.add_argument("--cpu-reps", type=int, default=5, help="CPU baseline runs (median)")
     ap.add_argument("--cpu-warmup", type=int, default=1, help="0: no warm-up build of the CPU baseline (the large configs: a build takes a minute)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the match records of the last timed step to DIR/<field>.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args)
 
@@ -316,6 +347,11 @@ def main():
         frame_digests = fshards.gather_digests(kept, below_template=sample_n)
     n_matches = total_matches / max(1, args.steps * (world if by_frames else 1))
     gpu_last = None if acc["last"] is None else np.array(acc["last"], copy=True)
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        if gpu_last is None:
+            raise SystemExit("--dump-outputs: the last timed step returned no matches on rank 0")
+        dumped = dump_outputs(args.dump_outputs, gpu_last)
 
     # untimed extra: blocking frames (one in flight, the GPU to itself) for the roofline objects.  The frames cycle the
     # same scenes as the timed region, so every build is a NEW scene for its handle (the launch order and the priority
@@ -455,6 +491,8 @@ def main():
                                 "dt3_build_span_ms": avg["total_ms"], "search_span_ms": acc["search_total_ms"] / K,
                                 "search_kernel_ms": acc["search_kernel_ms"] / K},
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if single:
             s_ms = single["stage_ms"]
             stage_sum = sum(s_ms[k] for k in ("seeds_ms", "pass1_ms", "pass2_ms", "propagate_ms", "integral_ms"))

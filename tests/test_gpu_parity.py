@@ -1028,22 +1028,35 @@ def test_sharded_engine_rejects_bad_devices(amd):
         ShardedEngine(tmpls, devices=[0, 0])
 
 
-def test_bench_force_dist_runs_the_rccl_gather_and_passes_its_parity_gate(amd):
+def test_bench_force_dist_runs_the_rccl_gather_and_passes_its_parity_gate(amd, tmp_path):
     """bench.py --force-dist: the multi-process path (torch.distributed backend nccl = RCCL, per-frame gather with the
     count in a trailing record, slot buffers guarded by events) with world size 1, frames in flight, checked by the
-    bench's own parity gate against the oracle."""
+    bench's own parity gate against the oracle.  --dump-outputs: the last timed frame's records are the oracle's."""
     import json
     import os
     import subprocess
     import sys
+    from openfdcm_amd import synthetic
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29571", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
+    dump = tmp_path / "dump"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "8", "--warmup", "2",
-                          "--templates", "120", "--cpu-sample", "40", "--cpu-reps", "1", "--single-frames", "3"],
+                          "--templates", "120", "--cpu-sample", "40", "--cpu-reps", "1", "--single-frames", "3",
+                          "--dump-outputs", str(dump)],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
     doc = json.loads(out.stdout.strip().splitlines()[-1])
     assert doc["parity_gate"] == "ok" and doc["n_gpus"] == 1 and doc["config"]["matches_per_step"] > 1000
+    assert doc["steps"] == 8 and doc["ms_per_step"] > 0 and doc["dump_outputs"]["files"] == ["score.npy", "tmpl_idx.npy", "transform.npy"]
+    # the last timed frame is frame 4 x 4 (set-up) + 2 (warm-up) + 7 of the stream: scene seed 1 + 25 % 4
+    cfg = synthetic.CONFIGS["2p"]
+    sc = synthetic.scene(cfg["S"], cfg["scene_lines"], 1 + 25 % 4)
+    ofm = O.build(sc, depth=cfg["depth"], coeff=5.0, padding=1.0, distance=cfg["distance"], nthreads=8)
+    want = O.search(ofm, synthetic.templates(120, cfg["n"], cfg["S"], 2), sc, 4, 4, kind=O.BATCH_OPTIMIZE, batch=10, nthreads=8)
+    idx, score, tr = (np.load(str(dump / f"{k}.npy")) for k in ("tmpl_idx", "score", "transform"))
+    assert idx.dtype == np.float64 and score.dtype == np.float32 and tr.dtype == np.float32 and tr.shape == (len(want), 6)
+    assert np.array_equal(idx, want["tmpl_idx"].astype(np.float64)) and score.tobytes() == np.ascontiguousarray(want["score"]).tobytes()
+    assert tr.tobytes() == np.ascontiguousarray(want["transform"]).tobytes()
     assert doc["roofline"]["frac"] > 0 and doc["roofline_search"]["achieved"] > 0 and doc["cpu_baseline"]["cores"] >= 1
     assert doc["config"]["distinct_scenes"] == 4 and "all 8 timed frames" in doc["parity_gate_detail"]
     assert doc["roofline"]["same_scene_ms"] > 0 and doc["dt3_build_ms"] >= doc["dt3_build_kernels_ms"] > 0

@@ -1,12 +1,10 @@
 #!/bin/bash
 # Collect the round's judged measurements on the GPU box into gpurun_out/<tag>/ (copy into profiles/ afterwards).
 # usage (inside gpurun): bash tools/collect_profiles.sh <out dir under gpurun_out> [profiles/ prefix, default r06]
-# The program goes directly after `--` (no env / bash -c hop under rocprofv3); the queue count bench.py asks for is
-# exported here because under rocprofv3 the GPU is initialised before python starts.
+# The program goes directly after `--` (no env / bash -c hop under rocprofv3).
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/${1:-prof}
 mkdir -p $OUT
-export GPU_MAX_HW_QUEUES=8
 export TMPDIR=/tmp
 cd /tmp
 stats() {  # stats <name> <program args...>: rocprofv3 --kernel-trace --stats summary of a command

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel durations with the frame pipeline running (4 frames in flight); run through gpurun
 cd "$(dirname "$0")/.."
-export GPU_MAX_HW_QUEUES=8 TMPDIR=/tmp
+export TMPDIR=/tmp
 rm -rf gpurun_out/pprof; mkdir -p gpurun_out/pprof
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pprof/r -- python3 bench.py --cpu-sample 0 --single-frames 0 --steps 200 --warmup 20 > gpurun_out/pprof/r.log 2>&1
 f=$(find gpurun_out/pprof/r -name "*kernel_stats.csv" | head -1)

@@ -4,7 +4,6 @@
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/${1:-pmc_sq}
 mkdir -p $OUT
-export GPU_MAX_HW_QUEUES=8
 export TMPDIR=/tmp
 cd /tmp
 pass() {  # pass <name> <counters...> : one rocprofv3 --pmc pass of the one-frame bench

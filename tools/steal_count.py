@@ -1,5 +1,5 @@
-import sys, ctypes, json
-sys.path.insert(0, "/root/repo")
+import os, sys, ctypes, json
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from openfdcm_amd import synthetic, _capi
 from openfdcm_amd.engine import DeviceFeatureMap

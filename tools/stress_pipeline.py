@@ -1,6 +1,5 @@
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from openfdcm_amd import synthetic, _capi
 from openfdcm_amd.engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, search_raw
