@@ -74,7 +74,11 @@ __global__ void __launch_bounds__(256) k_evaluate(const float* __restrict__ vol,
             inside = inside && x >= 0 && x < W && y >= 0 && y < H;
         }
     }
-    inside = inside && __shfl_xor((int)inside, 32) != 0;
+    // every lane takes part in the exchange: behind `inside &&` only the lanes still inside would, all passing 1, and the
+    // compiler folds that to 1 -- each half then judged only its own lines (an end point outside on the other half's
+    // lines scored a number and read outside the volume)
+    const int other_inside = __shfl_xor((int)inside, 32);
+    inside = inside && other_inside != 0;
     // (64-bit addresses: the seam serves volumes of any size and is not the hot path; L[5 i + 4] holds the bin)
     const VolRef V = make_volref(vol, ivol_slice_floats(W, H), 0, false);
     const float s = pair_score<false>(V, L, n, offx, offy, (unsigned)H, h, act && inside);

@@ -1,0 +1,497 @@
+"""Every DT3 build stage and every match score against definitions that come from neither restatement of the reference.
+
+The parity tests compare the HIP path with oracle/ bit for bit, so an error the two share goes unnoticed.  Here both are
+held to plain numpy statements of what each stage computes, in integers or float64, which use nothing from oracle/ but
+its build and search entry points (the CPU side) and none of its rasterisation:
+
+  stage 1, L2^2   per column, the squared 1-D distance along y to the nearest seed (FLT_MAX without one); then the
+                  exact-owner statement of the row pass (tests/test_exact_owner.py) over every row -- bit for bit.
+                  L2 is the float32 sqrt of that, bit for bit.  The seeds are the volume's zeros; their geometry is
+                  checked on its own against the scene (every distance).
+  stage 2         P_i = min_j (D_j + coeff * path_ij), path_ij the shortest circular chain of key steps from slice j to
+                  i, in float64; tolerance from the float32 roundings on the chain.
+  stage 3         the chain of each slice's rasterised step: I = D at the chain's first pixel, I(p) = f32(I(prev p) +
+                  D(p)) everywhere else (exact), and a float64 prefix sum within the summation bound.
+  scores          sum over the template's lines of |I(p1) - I(p2)| in the slice of the nearest key, the end points
+                  translated in float64 and truncated, re-evaluated from the stage-3 volume.
+
+Each check runs on the oracle (CPU) and on DeviceFeatureMap (`gpu`) from one parametrisation, over the square synthetic
+scenes and the scenes of helpers.edge_scenes() (tiny maps, far-off coordinates, axis-parallel lines, one slice only,
+depths 1, 2 and 180, coefficients 0 and 50, padding 1.0 and 3.7).
+"""
+import numpy as np
+import pytest
+
+from helpers import EDGE_SCENES, FMAX, exact_pass, exact_pass_rows
+from oracle import oracle as O
+
+U = 2.0 ** -24          # unit roundoff of float32
+
+BACKENDS = [pytest.param("oracle", id="oracle"), pytest.param("device", id="device", marks=pytest.mark.gpu)]
+DISTS = [pytest.param(O.L2_SQUARED, id="l2sq"), pytest.param(O.L2, id="l2"), pytest.param(O.L1, id="l1")]
+
+# (S, lines, depth, coeff, padding, seed): the square synthetic scenes (bounding box [0, S-1]^2)
+SQUARE = {"s33": (33, 8, 5, 5.0, 1.0, 11), "s64": (64, 12, 4, 5.0, 1.0, 3), "s97": (97, 25, 7, 50.0, 1.37, 4),
+          "s150": (150, 30, 12, 0.0, 1.0, 6), "s300": (300, 60, 7, 5.0, 2.2, 8), "s640": (640, 120, 30, 5.0, 1.0, 9),
+          "s1024": (1024, 200, 30, 5.0, 1.0, 1)}
+EXHAUSTIVE = ["s33", "s64", "s97", "s150", "s300"] + list(EDGE_SCENES)   # whole volumes at every size <= 300
+ALL_CASES = EXHAUSTIVE + ["s640", "s1024"]
+
+
+def case(name):
+    """-> scene, depth, coeff, padding"""
+    if name in SQUARE:
+        from openfdcm_amd import synthetic
+        S, n, depth, coeff, pad, seed = SQUARE[name]
+        return synthetic.scene(S, n, seed), depth, coeff, pad
+    return EDGE_SCENES[name]
+
+
+class Built:
+    """What a build hands over: keys, scene translation, size and the (depth, W, H) volume."""
+    def __init__(self, backend, name, dist, stop_after):
+        scene, depth, coeff, pad = case(name)
+        self.scene, self.coeff, self.padding = scene, coeff, pad
+        if backend == "oracle":
+            self.h = O.build(scene, depth=depth, coeff=coeff, padding=pad, distance=dist, nthreads=4, stop_after=stop_after)
+            self.W, self.H, self.translation = self.h.W, self.h.H, self.h.translation
+        else:
+            from openfdcm_amd.engine import DeviceFeatureMap
+            self.h = DeviceFeatureMap.build(scene, depth=depth, coeff=coeff, padding=pad, distance=dist, stop_after=stop_after)
+            self.W, self.H, self.translation = self.h.width, self.h.height, self.h.scene_translation
+        self.backend, self.keys = backend, np.array(self.h.keys, dtype=np.float32)
+        self.vol = self.h.volume()
+        assert self.vol.shape == (len(self.keys), self.W, self.H)
+
+    def evaluate(self, tmpl, translations):
+        if self.backend == "oracle":
+            return O.evaluate(self.h, tmpl, translations)
+        return self.h.evaluate([tmpl], [translations])[0]
+
+    def search(self, templates, kind, batch):
+        if self.backend == "oracle":
+            return O.search(self.h, templates, self.scene, 4, 4, kind=kind, batch=batch, nthreads=4)
+        from openfdcm_amd.engine import DeviceTemplates, search_raw
+        return search_raw(self.h, DeviceTemplates(templates), self.scene, 4, 4, kind, batch)
+
+
+def ulp32(x):
+    return np.spacing(np.float32(np.max(np.abs(x)) if np.size(x) else 0.0)).astype(np.float64)
+
+
+# ------------------------------------------------------------------------------------------------ definitions
+def definition_keys(m):
+    return np.arange(m) * np.pi / m - np.pi / 2
+
+
+def nearest_bins(lines64, m, margin):
+    """(4, N) float64 lines -> (bin, ambiguous) with bin the nearest of the m keys k pi / m - pi / 2 (circularly: an angle
+    near pi/2 belongs to key 0) by a float64 arctan, ambiguous where the angle is within `margin` (per line) of the
+    boundary between two keys or the line has no direction."""
+    dx, dy = lines64[2] - lines64[0], lines64[3] - lines64[1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = np.arctan(dy / dx)
+    pos = (a + np.pi / 2) * m / np.pi                      # key units
+    b = np.floor(pos + 0.5)
+    frac = pos + 0.5 - b                                   # a boundary lies at frac 0 (and 1)
+    amb = np.minimum(frac, 1 - frac) * np.pi / m < margin if m > 1 else np.zeros(len(pos), dtype=bool)
+    amb |= ~np.isfinite(pos) | (np.hypot(dx, dy) < 1e-6)
+    b = np.where(np.isfinite(b), b, 0).astype(np.int64) % m
+    return b, amb
+
+
+def scene_geometry(scene, padding):
+    """getSceneCenteredTranslation in float64: (translation, size) of the square map around the scene."""
+    s = scene.astype(np.float64)
+    xs, ys = np.concatenate([s[0], s[2]]), np.concatenate([s[1], s[3]])
+    rm = max(1.0, float(np.float32(padding))) * max(xs.max() - xs.min(), ys.max() - ys.min())
+    t = np.array([rm / 2 - (xs.max() + xs.min()) / 2, rm / 2 - (ys.max() + ys.min()) / 2])
+    return t, rm + 1
+
+
+def column_distances_sq(seeds):
+    """seeds (W, H) bool -> squared distance along y to the nearest seed of the same column (FLT_MAX if none)."""
+    W, H = seeds.shape
+    y = np.arange(H)
+    big = 1 << 40
+    prev = np.maximum.accumulate(np.where(seeds, y, -big), axis=1)
+    nxt = np.minimum.accumulate(np.where(seeds, y, big)[:, ::-1], axis=1)[:, ::-1]
+    d = np.minimum(y - prev, nxt - y)
+    return np.where(seeds.any(axis=1)[:, None], (d.astype(np.int64) ** 2).astype(np.float32), FMAX)
+
+
+def stage1_l2sq(vol, rows=None):
+    """The stage-1 L2^2 definition from the volume's zeros -> (depth, W, H), or only the given rows y of each slice."""
+    m, W, H = vol.shape
+    ys = np.arange(H) if rows is None else np.asarray(rows)
+    out = np.empty((m, W, len(ys)), dtype=np.float32)
+    for k in range(m):
+        F = column_distances_sq(vol[k] == 0)[:, ys]        # (W, rows)
+        out[k] = exact_pass_rows(F.T).T
+    return out
+
+
+def chebyshev_to_segments(px, py, seg):
+    """Chebyshev distance of points (P,) to segments (4, L) -> (P, L): min over t of max(|x(t) - px|, |y(t) - py|),
+    attained at an end, where one coordinate difference vanishes, or where the two are equal in size."""
+    ax, ay = seg[0][None, :] - px[:, None], seg[1][None, :] - py[:, None]
+    dx, dy = (seg[2] - seg[0])[None, :], (seg[3] - seg[1])[None, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cands = [np.zeros_like(ax), np.ones_like(ax), -ax / dx, -ay / dy, (ay - ax) / (dx - dy), -(ax + ay) / (dx + dy)]
+    best = np.full(ax.shape, np.inf)
+    for t in cands:
+        t = np.clip(np.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0), 0.0, 1.0)
+        best = np.minimum(best, np.maximum(np.abs(ax + t * dx), np.abs(ay + t * dy)))
+    return best
+
+
+def clip_to_box(seg, xmax, ymax, eps):
+    """Liang-Barsky clip of (4, L) float64 segments to [-eps, xmax + eps] x [-eps, ymax + eps] -> (segments, kept)."""
+    x1, y1, x2, y2 = seg
+    dx, dy = x2 - x1, y2 - y1
+    t0, t1 = np.zeros(len(x1)), np.ones(len(x1))
+    keep = np.ones(len(x1), dtype=bool)
+    for p, q in ((-dx, x1 + eps), (dx, xmax + eps - x1), (-dy, y1 + eps), (dy, ymax + eps - y1)):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = q / p
+        par = p == 0
+        keep &= ~(par & (q < 0))
+        t0 = np.where(~par & (p < 0), np.maximum(t0, r), t0)
+        t1 = np.where(~par & (p > 0), np.minimum(t1, r), t1)
+    keep &= t0 <= t1
+    return np.array([x1 + t0 * dx, y1 + t0 * dy, x1 + t1 * dx, y1 + t1 * dy]), keep
+
+
+def round_half_away(x):
+    return np.sign(x) * np.floor(np.abs(x) + 0.5)
+
+
+def step_shifts(key, n):
+    """The rasterised step of a key (rasterizeVector(cos, sin)): major axis (0 = x, 1 = y), its direction, and per step
+    i = 1 .. n-1 the candidate minor-axis shifts round(i v) - round((i - 1) v) (two where i v or (i - 1) v lies so close
+    to a half that float32 may round it either way)."""
+    c, s = np.cos(float(key)), np.sin(float(key))
+    major = 0 if abs(s) < abs(c) else 1
+    d = int(np.sign(c if major == 0 else s))
+    v = (s / abs(c)) if major == 0 else (c / abs(s))
+    i = np.arange(n, dtype=np.float64)
+    iv = i * v
+    lo = round_half_away(iv)
+    # float32 v carries 2^-24 |v| of error, the float32 product i v another half ulp of |i v|
+    near = np.abs(np.abs(iv - np.trunc(iv)) - 0.5) < (i * abs(v) + 1) * 2.0 ** -22
+    alt = np.where(near, 2 * np.floor(iv) + 1 - lo, lo)        # the other neighbour of the half
+    shifts = []
+    for j in range(1, n):
+        cand = {int(a - b) for a in (lo[j], alt[j]) for b in (lo[j - 1], alt[j - 1])}
+        shifts.append(sorted(cand, key=lambda t: t != int(lo[j] - lo[j - 1])))
+    return major, d, shifts
+
+
+# ------------------------------------------------------------------------------------------------ 1. stage 1, L2^2 / L2
+def _assert_bits(got, want, what):
+    same = got.view(np.uint32) == want.view(np.uint32)
+    if not same.all():
+        k, x, y = np.argwhere(~same)[0]
+        raise AssertionError(f"{what}: {int((~same).sum())} of {same.size} differ; first slice {k} x {x} y {y}: "
+                             f"got {got[k, x, y]!r} definition {want[k, x, y]!r}")
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("dist", DISTS[:2])
+@pytest.mark.parametrize("name", ALL_CASES)
+def test_stage1_l2_is_the_exact_owner_transform(backend, dist, name):
+    b = Built(backend, name, dist, 1)
+    assert (b.vol == 0).any()
+    rows = None
+    if b.H > 300:   # a fixed, seeded sample of rows in every slice
+        rows = np.sort(np.random.default_rng(b.H).choice(b.H, size=6, replace=False))
+    want = stage1_l2sq(b.vol, rows)
+    if dist == O.L2:
+        want = np.sqrt(want)
+    got = b.vol if rows is None else b.vol[:, :, rows]
+    _assert_bits(got, want, f"{backend} {name} dist {dist}")
+
+
+def test_batched_exact_pass_is_the_row_statement():
+    """exact_pass_rows is exact_pass, vectorised: the same rows through both."""
+    rng = np.random.default_rng(3)
+    for n in (1, 2, 7, 64, 301):
+        F = np.where(rng.uniform(size=(40, n)) < rng.uniform(0.02, 0.9, size=(40, 1)),
+                     (rng.integers(0, 300, size=(40, n)) ** 2).astype(np.float32), FMAX).astype(np.float32)
+        F[0] = FMAX
+        want = np.stack([exact_pass(f) for f in F])
+        assert np.array_equal(exact_pass_rows(F).view(np.uint32), want.view(np.uint32)), n
+
+
+# ------------------------------------------------------------------------------------------------ 2. seed geometry
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("dist", DISTS)
+@pytest.mark.parametrize("name", ALL_CASES)
+def test_stage1_seeds_lie_on_the_scene_lines(backend, dist, name):
+    """Every zero of slice k lies within Chebyshev distance 0.5 (+ rounding) of the translated, clipped segment of a
+    scene line whose float64 orientation is nearest key k; every end point of such a line inside the map rounds to a
+    zero of slice k.  Also: the size and the translation are the float64 scene-centred ones, the keys k pi/m - pi/2."""
+    b = Built(backend, name, dist, 1)
+    scene, m = b.scene.astype(np.float64), len(b.keys)
+    t64, size = scene_geometry(b.scene, b.padding)
+    assert b.W == b.H and int(np.ceil(size - 1e-4)) <= b.W <= int(np.ceil(size + 1e-4)), (b.W, size)
+    assert np.all(np.abs(b.translation - t64) <= 4 * ulp32(np.concatenate([t64, scene.ravel()]))), (b.translation, t64)
+    assert np.all(np.abs(b.keys - definition_keys(m)) <= 2 * np.spacing(np.float32(np.pi / 2)))
+    tr = scene + np.array([b.translation[0], b.translation[1]] * 2, dtype=np.float64)[:, None]
+    # float32 rounding of the translated coordinates (the implementation translates in float32)
+    err = 2 * max(ulp32(scene), ulp32(tr), ulp32(b.translation))
+    length = np.hypot(tr[2] - tr[0], tr[3] - tr[1])
+    bins, amb = nearest_bins(tr, m, 1e-5 + 4 * err / np.maximum(length, 1e-30))
+    seg, kept = clip_to_box(tr, b.W - 1, b.H - 1, err)
+    tol = 0.5 + 1e-3 + 4 * err
+    for k in range(m):
+        xs, ys = np.nonzero(b.vol[k] == 0)
+        if len(xs) == 0:
+            continue
+        mine = kept & ((bins == k) | amb)
+        assert mine.any(), f"slice {k} has {len(xs)} zeros and no scene line"
+        dmin = chebyshev_to_segments(xs.astype(np.float64), ys.astype(np.float64), seg[:, mine]).min(axis=1)
+        bad = dmin > tol
+        assert not bad.any(), f"{backend} {name} slice {k}: zero at {(xs[bad][0], ys[bad][0])} is {dmin[bad][0]} from its lines"
+    # end points.  A line of extent below one pixel along its major axis is a single raster point: its second end point
+    # (LinSpaced of one element is the upper end), or its first where both coincide (drawing.h:78-81).
+    major = np.maximum(np.abs(tr[2] - tr[0]), np.abs(tr[3] - tr[1]))
+    checked = 0
+    for i in range(tr.shape[1]):
+        ends = [(tr[0, i], tr[1, i]), (tr[2, i], tr[3, i])]
+        if major[i] < 1:
+            ends = ends[:1] if major[i] <= 1e-5 else ends[1:]
+        for x, y in ends:
+            # an end point just outside the box is clipped onto it (drawing.cpp:29-112), not dropped
+            if not (-err < x < b.W - 1 + err and -err < y < b.H - 1 + err):
+                continue
+            x, y = min(max(x, 0.0), b.W - 1.0), min(max(y, 0.0), b.H - 1.0)
+            if any(abs(abs(c - np.trunc(c)) - 0.5) <= err + 1e-6 for c in (x, y)):
+                continue                                   # rounds either way within float32 reach
+            px, py = int(round_half_away(x)), int(round_half_away(y))
+            slices = range(m) if amb[i] else [bins[i]]
+            assert any(b.vol[k, px, py] == 0 for k in slices), (backend, name, i, tr[:, i], (px, py))
+            checked += 1
+    assert checked > 0
+
+
+# ------------------------------------------------------------------------------------------------ 3. stage 2
+def stage2_definition(D, keys, coeff):
+    """float64 min-plus over the circular chain of keys: -> (P, k_best) with k_best the number of steps of the cheapest
+    chain (the fewest on a tie).  Edge weights coeff * min(h, pi - h), h = |key_a - key_b| from the handle's float32 keys
+    (their spacing differs from pi/m by about an ulp, more than this check resolves)."""
+    m = len(keys)
+    D = D.astype(np.float64)
+    if m == 1:
+        return D.copy(), np.zeros(D.shape, dtype=np.int64)
+    kk = keys.astype(np.float64)
+    h = np.abs(kk - np.roll(kk, 1))                      # edge (c-1 -> c)
+    w = coeff * np.minimum(h, np.abs(h - np.pi))
+    P = np.full(D.shape, np.inf)
+    K = np.zeros(D.shape, dtype=np.int64)
+    for i in range(m):
+        for j in range(m):
+            fwd = sum(w[(j + s) % m] for s in range(1, (i - j) % m + 1))          # j -> j+1 -> ... -> i
+            bwd = sum(w[(j - s + 1) % m] for s in range(1, (j - i) % m + 1))      # j -> j-1 -> ... -> i
+            kf, kb = (i - j) % m, (j - i) % m
+            cost, k = (fwd, kf) if (fwd, kf) <= (bwd, kb) else (bwd, kb)
+            v = D[j] + cost
+            better = (v < P[i]) | ((v == P[i]) & (k < K[i]))
+            P[i] = np.where(better, v, P[i])
+            K[i] = np.where(better, k, K[i])
+    return P, K
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("dist", DISTS)
+@pytest.mark.parametrize("name", ALL_CASES)
+def test_stage2_is_the_min_plus_over_orientations(backend, dist, name):
+    """Against the float64 definition, from the same backend's stage-1 volume.  Tolerance from the roundings on a chain
+    of k steps: each weight coeff * min(h, pi_f - h) in float32 is off by at most coeff (2^-24 pi (h) + |pi_f - pi| (<
+    2^-23) + 2^-24 pi/2 (product)) < coeff 2^-21, each addition by 2^-24 of the chain's value, at most |P|.  The result
+    is at most the float32 value of the cheapest chain (taken along it by one of the two sweeps; min and float32
+    addition are monotone): P32 <= P64 + k (coeff 2^-21 + 2^-24 |P|), k that chain's steps.  It is the float32 value of
+    some walk of the two sweeps, at most 3 m steps, whose float64 value is >= P64: P32 >= P64 - 3 m (...)."""
+    D = Built(backend, name, dist, 1).vol
+    b = Built(backend, name, dist, 2)
+    got = b.vol.astype(np.float64)
+    if b.H > 300:
+        rows = np.sort(np.random.default_rng(b.H + 1).choice(b.H, size=64, replace=False))
+        D, got = D[:, :, rows], got[:, :, rows]
+    P, K = stage2_definition(D, b.keys, b.coeff)
+    m = len(b.keys)
+    e = b.coeff * 2.0 ** -21 + U * np.abs(P)
+    above = got - P > K * e
+    below = P - got > 3 * m * e
+    for bad, what in ((above, "above"), (below, "below")):
+        if bad.any():
+            k, x, y = np.argwhere(bad)[0]
+            raise AssertionError(f"{backend} {name} dist {dist}: {int(bad.sum())} voxels {what} the definition; first "
+                                 f"slice {k} x {x} y {y}: got {got[k, x, y]!r} definition {P[k, x, y]!r} k {K[k, x, y]}")
+    all_max = (D == FMAX).all(axis=0)
+    assert (got[:, all_max] == FMAX).all()
+
+
+# ------------------------------------------------------------------------------------------------ 4. stage 3
+def check_chains(D, I, d, shifts):
+    """D, I: (n_major, n_minor) float32 of one slice, major axis first.  Exact recurrence and the float64 bound; returns
+    the number of chain links checked."""
+    n, L = D.shape
+    order = list(range(n)) if d > 0 else list(range(n - 1, -1, -1))
+    first = order[0]
+    assert np.array_equal(I[first].view(np.uint32), D[first].view(np.uint32)), "chain start: I != D"
+    S = D[first].astype(np.float64)
+    A = np.abs(S)
+    cnt = np.ones(L)
+    links = 0
+    y = np.arange(L)
+    for step, col in enumerate(order[1:], start=1):
+        prev = order[step - 1]
+        ok = False
+        for s in shifts[step - 1]:
+            src = y - s
+            valid = (src >= 0) & (src < L)
+            srcc = np.clip(src, 0, L - 1)
+            want = np.where(valid, (I[prev][srcc] + D[col]).astype(np.float32), D[col])   # float32 addition
+            if np.array_equal(want.view(np.uint32), I[col].view(np.uint32)):
+                ok = True
+                break
+        assert ok, f"major index {col}: I != f32(I(prev) + D) for every rounding of the step ({shifts[step - 1]})"
+        S = np.where(valid, S[srcc] + D[col], D[col].astype(np.float64))
+        A = np.where(valid, A[srcc] + np.abs(D[col]), np.abs(D[col].astype(np.float64)))
+        cnt = np.where(valid, cnt[srcc] + 1, 1)
+        bad = np.abs(I[col] - S) > cnt * U * A
+        assert not bad.any(), f"major index {col}: {I[col][bad][0]!r} vs float64 prefix sum {S[bad][0]!r}"
+        links += int(valid.sum())
+    return links
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("dist", DISTS)
+@pytest.mark.parametrize("name", ALL_CASES)
+def test_stage3_is_the_line_integral_along_each_keys_step(backend, dist, name):
+    """Per slice, the chains of its key's rasterised step (major axis +-1, minor round(i v) - round((i-1) v)): the first
+    pixel keeps D, every other I(p) == f32(I(prev p) + D(p)) exactly, and I is within n 2^-24 sum|D| of the float64
+    prefix sum of its n-pixel chain."""
+    D = Built(backend, name, dist, 2).vol
+    b = Built(backend, name, dist, 3)
+    links = 0
+    for k in range(len(b.keys)):
+        major, d, shifts = step_shifts(b.keys[k], b.W)             # (square maps: W == H)
+        if major == 0:
+            links += check_chains(D[k], b.vol[k], d, shifts)
+        else:
+            links += check_chains(D[k].T, b.vol[k].T, d, shifts)
+    assert links > 0 or b.W == 1
+
+
+# ------------------------------------------------------------------------------------------------ 5. scores
+def rescore(vol, keys, lines64, W, H, err, aerr):
+    """float64 score of a template whose (4, n) end points are already translated into the map: (score, bound, status)
+    with status 'ok', 'outside' or 'ambiguous' (an end point within err of a pixel edge, or a line within 1e-5 rad plus
+    the angle error of end points off by aerr of a bin boundary)."""
+    m = len(keys)
+    n = lines64.shape[1]
+    if n == 0:
+        return 0.0, 0.0, "ok"
+    length = np.hypot(lines64[2] - lines64[0], lines64[3] - lines64[1])
+    bins, amb = nearest_bins(lines64, m, 1e-5 + 2 * aerr / np.maximum(length, 1e-30))
+    lim = np.array([W, H, W, H])[:, None]
+    if ((lines64 <= -1 - err) | (lines64 >= lim + err)).any():     # truncates to a pixel outside the map
+        return None, None, "outside"
+    near = (np.abs(lines64 - np.round(lines64)) < err) & (np.round(lines64) != 0)  # cast<int>() truncates: 0 from both sides
+    if near.any() or amb.any():
+        return None, None, "ambiguous"
+    ix = np.trunc(lines64).astype(np.int64)
+    assert ((ix >= 0) & (ix < lim)).all()
+    a = vol[bins, ix[0], ix[1]].astype(np.float64)
+    c = vol[bins, ix[2], ix[3]].astype(np.float64)
+    terms = np.abs(a - c)
+    return float(terms.sum()), float(n * U * terms.sum()), "ok"
+
+
+def _random_templates(rng, W, count):
+    out = []
+    for _ in range(count):
+        n = int(rng.integers(1, 13))
+        c = rng.uniform(0, W, size=2)
+        p = c[:, None] + rng.uniform(-0.3, 0.3, size=(2, 2 * n)) * W
+        t = p.reshape(4, n, order="F")
+        t[2:] += (np.abs(t[2:] - t[:2]) < 1e-3) * 1.0                # no zero-length lines
+        out.append(t.astype(np.float32))
+    return out
+
+
+SCORE_CASES = ["s33", "s97", "s300", "s640", "w2", "w8", "w17", "w24", "point", "offset", "offset-pad", "axis",
+               "one-slice", "depth180", "depth1"]
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("dist", DISTS)
+@pytest.mark.parametrize("name", SCORE_CASES)
+def test_evaluate_is_the_sum_of_line_differences(backend, dist, name):
+    """FeatureMap::evaluate on random templates and translations, some putting an end point outside the map, against
+    the float64 re-evaluation from the stage-3 volume within n_lines 2^-24 sum|terms|.  Outside the map the device
+    scores NaN; the reference reads such pixels unchecked, so the oracle is only given translations clearly inside."""
+    b = Built(backend, name, dist, 3)
+    rng = np.random.default_rng(len(name) * 7 + dist)
+    st = b.translation.astype(np.float64)
+    counts = {"ok": 0, "outside": 0, "ambiguous": 0}
+    for t in _random_templates(rng, b.W, 60):
+        trs = rng.uniform(-0.5, 0.5, size=(12, 2)) * b.W - (t[:2].mean(axis=1) + st - 0.5 * b.W)
+        trs[:3] += rng.uniform(-1.5, 1.5, size=(3, 2)) * b.W      # mostly outside
+        trs = trs.astype(np.float32)
+        want = []
+        for tr in trs:
+            off = np.array([st[0] + tr[0], st[1] + tr[1]] * 2)[:, None]
+            lines = t.astype(np.float64) + off
+            # float32: offset = translation + scene translation, end point + offset (half an ulp each); the bins come
+            # from the untranslated template
+            err = max(1e-3, 2 * max(ulp32(st), ulp32(tr), ulp32(t), ulp32(lines)))
+            want.append(rescore(b.vol, b.keys, lines, b.W, b.H, err, ulp32(t)))
+        use = np.array([w[2] == "ok" for w in want]) if backend == "oracle" else np.ones(len(trs), dtype=bool)
+        if not use.any():
+            continue
+        got = b.evaluate(t, trs[use])
+        for g, (s, bound, status) in zip(got, [w for w, u in zip(want, use) if u]):
+            counts[status] += 1
+            if status == "outside":
+                assert np.isnan(g), (name, g)
+            elif status == "ok":
+                assert abs(float(g) - s) <= bound, (backend, name, float(g), s, bound)
+    assert counts["ok"] > 60, counts
+    assert counts["ambiguous"] < 0.25 * sum(counts.values()), counts
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("kind", [pytest.param(O.BATCH_OPTIMIZE, id="batch"), pytest.param(O.DEFAULT_OPTIMIZE, id="default")])
+@pytest.mark.parametrize("dist", DISTS)
+@pytest.mark.parametrize("name", ["s64", "s300", "s1024", "w17", "offset", "axis", "one-slice", "depth180"])
+def test_search_records_score_their_own_transform(backend, kind, dist, name):
+    """Every record of the search, re-scored from its own transform (R p + t + scene translation, in float64) on the
+    stage-3 volume.  Records with an end point within float32 reach of a pixel edge (or a line of a bin boundary) are
+    skipped; fewer than a quarter may be."""
+    from openfdcm_amd import synthetic
+    b = Built(backend, name, dist, 3)
+    n_lines = 4 if name.startswith("offset") else 12
+    tmpls = synthetic.templates(24, n_lines, max(b.W, 16), 5 + dist)
+    rec = b.search(tmpls, kind, 10)
+    assert len(rec) > 20
+    st = b.translation.astype(np.float64)
+    skipped = 0
+    for r in rec:
+        T = r["transform"].astype(np.float64).reshape(2, 3)
+        t = tmpls[r["tmpl_idx"]].astype(np.float64)
+        pts = t.reshape(2, -1, order="F")
+        moved = (T[:, :2] @ pts + T[:, 2:3] + st[:, None]).reshape(4, -1, order="F")
+        # float32 on the device / oracle side: R p + t (three roundings), the record's t + translation, translation +
+        # scene translation and the end point + offset (one each): at most 3 ulps of the largest intermediate.  The bins
+        # come from the aligned template R p + t (1.5 ulps per coordinate).
+        big = max(ulp32(moved), ulp32(T[:, 2]), ulp32(st), ulp32(T[:, :2] @ pts))
+        aligned = max(ulp32(T[:, :2] @ pts + T[:, 2:3]), ulp32(T[:, :2] @ pts))
+        s, bound, status = rescore(b.vol, b.keys, moved, b.W, b.H, max(1e-3, 4 * big), 2 * aligned)
+        if status != "ok":
+            skipped += 1
+            continue
+        assert abs(float(r["score"]) - s) <= bound, (backend, name, int(r["tmpl_idx"]), float(r["score"]), s, bound)
+    assert skipped < 0.25 * len(rec), (skipped, len(rec))

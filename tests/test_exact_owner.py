@@ -12,30 +12,8 @@ gaps (where two quotients round to the same float), few seeds, values at the 2^2
 import numpy as np
 import pytest
 
+from helpers import FMAX, exact_pass  # noqa: F401  (the statement above, shared with test_definitions_dt3)
 from oracle import oracle as O
-
-FMAX = np.float32(np.finfo(np.float32).max)
-
-
-def exact_pass(f):
-    """f: float32 vector (squares of integers or FLT_MAX) -> the statement above, in integers."""
-    n = len(f)
-    cols = np.flatnonzero(f != FMAX)
-    if len(cols) == 0:
-        return f.copy()
-    fi = f[cols].astype(np.int64)
-    q = np.arange(n, dtype=np.int64)
-    cost = fi[None, :] + (q[:, None] - cols[None, :]) ** 2       # [pixel][seeded column]
-    owner = cols[np.argmin(cost, axis=1)]                          # argmin takes the first (smallest) column on a tie
-    out = np.zeros(n, dtype=np.int64)
-    fint = np.zeros(n, dtype=np.int64)
-    fint[cols] = fi
-    for p in range(n):
-        o = owner[p]
-        out[p] = (out[o] if o < p else fint[o]) + (p - o) ** 2
-    assert out.max() < 2 ** 24 + 2 ** 23
-    return out.astype(np.float32)
-
 
 def literal_pass(f):
     # oracle.column_pass_l2 takes an (H, W) image and runs the pass down every column: one column of length n

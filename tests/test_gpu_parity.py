@@ -7,7 +7,7 @@ bit-identical too; the tests report when they are not.
 import numpy as np
 import pytest
 
-from helpers import apply_transform, create_lines
+from helpers import EDGE_SCENES, apply_transform, create_lines
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -55,14 +55,21 @@ def assert_matches_close(got, want, what):
 
 @pytest.mark.parametrize("dist", [O.L2_SQUARED, O.L2, O.L1])
 @pytest.mark.parametrize("stage", [1, 2, 3])
-@pytest.mark.parametrize("S,n,depth,seed", [(64, 12, 4, 3), (97, 25, 7, 4), (200, 40, 30, 5)])
+@pytest.mark.parametrize("S,n,depth,seed", [(64, 12, 4, 3), (97, 25, 7, 4), (200, 40, 30, 5)] +
+                         [pytest.param(name, 0, 0, 0, id=f"edge-{name}") for name in EDGE_SCENES])
 def test_staged_build_bit_exact(amd, dist, stage, S, n, depth, seed):
+    """Synthetic scenes, and the scenes of helpers.edge_scenes(): tiny maps (W = 1 ... 32), coordinates far from the
+    origin, axis-parallel lines, lines of one slice, depths 1, 2 and 180, coefficients 0 and 50, padding 3.7."""
     from openfdcm_amd.engine import DeviceFeatureMap
-    scene = small_scene(S, n, seed)
-    # non-trivial padding on the odd size: exercises scene translation and out-of-box clipping
-    padding = 1.0 if S != 97 else 1.37
-    dev = DeviceFeatureMap.build(scene, depth=depth, coeff=5.0, padding=padding, distance=dist, stop_after=stage)
-    orc = O.build(scene, depth=depth, coeff=5.0, padding=padding, distance=dist, nthreads=4, stop_after=stage)
+    coeff = 5.0
+    if isinstance(S, str):
+        scene, depth, coeff, padding = EDGE_SCENES[S]
+    else:
+        scene = small_scene(S, n, seed)
+        # non-trivial padding on the odd size: exercises scene translation and out-of-box clipping
+        padding = 1.0 if S != 97 else 1.37
+    dev = DeviceFeatureMap.build(scene, depth=depth, coeff=coeff, padding=padding, distance=dist, stop_after=stage)
+    orc = O.build(scene, depth=depth, coeff=coeff, padding=padding, distance=dist, nthreads=4, stop_after=stage)
     assert (dev.width, dev.height, dev.depth) == (orc.W, orc.H, orc.depth)
     assert np.array_equal(dev.scene_translation, orc.translation)
     assert np.array_equal(dev.keys, orc.keys)
