@@ -293,6 +293,33 @@ int fdcm_partial_sort_matches(fdcm_match* matches, int64_t n, int64_t max_num_ca
 int fdcm_topk(fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches_device, int64_t n,
               int32_t tmpl_index_base, int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);
 
+/* ---- exhaustive translation search: every template scored at every point of a translation grid (the
+ *      sliding-window form of FDCM; the reference's search only walks scene lines, defaultmatch.cpp:32-89).
+ *      Not in the reference: the definitions are this project's (README.md, "Exhaustive search"). ----
+ * A grid is {x0, y0, nx, ny, sx, sy}: nx, ny >= 1, sx, sy >= 1, nx * ny < 2^31, every point inside |t| < 2^24.  Point (i, j)
+ * is the translation t = (x0 + i sx, y0 + j sy), row-major index g = j nx + i.  score(template, t) is evaluate<Dt3Cpu>
+ * (dt3cpu.cpp:126-179) at t: exactly the bits fdcm_featuremap_evaluate returns for that template and translation.  t is
+ * admissible for a template when fdcm_featuremap_evaluate does not return NaN there (every end point + T + t inside
+ * (-1, W) x (-1, H)): a product of two integer intervals per template.  A template without lines scores 0 everywhere.
+ * Concurrent callers of one feature map take turns, as for the seam. */
+typedef struct fdcm_grid {
+    int32_t x0, y0, nx, ny, sx, sy;
+} fdcm_grid;
+/* The smallest grid with strides (sx, sy) and x0, y0 multiples of them that holds every admissible integer translation of
+ * every template with lines; nx = ny = 0 when there is none. */
+int fdcm_exhaustive_window(const fdcm_featuremap* fm, const fdcm_templates* templates, int32_t sx, int32_t sy, fdcm_grid* grid);
+/* Per template with lines, in ascending index: its admissible grid points ordered by (score, g), the first min(k, count)
+ * of them as records {index + tmpl_index_base, score, {1, 0, t.x, 0, 1, t.y}} (combine(t, identity): penalize,
+ * sort_matches and the device tail take them as they are).  1 <= k <= 64.  An empty feature map or template list gives
+ * zero records.  Release with fdcm_matches_free. */
+int fdcm_search_exhaustive(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, int32_t k,
+                           int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out);
+/* The score map: out[template][j][i] = score at grid point (i, j) where admissible, NaN elsewhere (n_templates * ny * nx
+ * floats). */
+int fdcm_score_map(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, float* out_host);
+/* Same into device memory; returns when the map is complete (as fdcm_search_device). */
+int fdcm_score_map_device(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, float* out_device);
+
 /* ---- the reference's line files (.lines / .scene / .tmpl): read / write of core/serialization.h:99-132 (Python: openfdcm.read
  *      / openfdcm.write, python/src/core.cpp:41-42).  Host only.  fdcm_lines_read hands out n lines as 4 floats each
  *      (x1 y1 x2 y2 = the 4 x N column-major LineArray), to be released with fdcm_lines_free; a missing file, a file that is

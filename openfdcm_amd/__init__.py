@@ -436,4 +436,58 @@ def sort_matches(matches, max_num_candidates=None):
     return MatchList(rec)
 
 
+# ---------------------------------------------------------------- exhaustive translation search (extension)
+def _strides(stride):
+    sx, sy = (stride, stride) if _np.ndim(stride) == 0 else tuple(stride)
+    return int(sx), int(sy)
+
+
+def _device_map(featuremap):
+    dt3 = featuremap._dt3 if isinstance(featuremap, FeatureMap) else featuremap
+    if isinstance(dt3, Dt3Cpu):
+        return dt3._fm
+    if isinstance(dt3, DeviceFeatureMap):
+        return dt3
+    raise TypeError("featuremap must be a Dt3Cpu, FeatureMap or DeviceFeatureMap")
+
+
+def exhaustive_window(featuremap, templates, stride=1):
+    """The default window of exhaustive_search / score_map: the smallest grid with the given stride (an int or (sx, sy)),
+    origin a multiple of it, that holds every admissible integer translation of every template with lines.  Returns
+    (x0, y0, nx, ny, sx, sy); nx = ny = 0 when no template fits anywhere."""
+    sx, sy = _strides(stride)
+    return _device_map(featuremap).exhaustive_window(_template_cache.get(templates), sx, sy).as_tuple()
+
+
+def _window(fm, tset, stride, window):
+    if window is not None:
+        return tuple(int(v) for v in window)
+    sx, sy = _strides(stride)
+    return fm.exhaustive_window(tset, sx, sy).as_tuple()
+
+
+def exhaustive_search(featuremap, templates, stride=1, k=1, window=None):
+    """Score every template at every translation of a grid and keep the k best of each (1 <= k <= 64), ordered by
+    (score, grid index); templates without lines give nothing.  window: (x0, y0, nx, ny, sx, sy), by default
+    exhaustive_window(featuremap, templates, stride).  Returns a MatchList whose transforms are the pure translations
+    [[1, 0, tx], [0, 1, ty]], ready for penalize / sort_matches."""
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates)
+    g = _window(fm, tset, stride, window)
+    if g[2] == 0 or g[3] == 0:
+        return MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
+    return MatchList(fm.exhaustive_search(tset, g, k=k))
+
+
+def score_map(featuremap, templates, stride=1, window=None):
+    """The dense chamfer score map: (float32 array [T, ny, nx] of the scores, NaN where a translation puts the template
+    outside the feature map; grid (x0, y0, nx, ny, sx, sy)).  Point (i, j) is the translation (x0 + i sx, y0 + j sy)."""
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates)
+    g = _window(fm, tset, stride, window)
+    if g[2] == 0 or g[3] == 0:
+        return _np.zeros((tset.count, g[3], g[2]), dtype=_np.float32), g
+    return fm.score_map(tset, g), g
+
+
 from .lineio import read, write  # noqa: E402  (.lines/.scene/.tmpl files, serialization.h)

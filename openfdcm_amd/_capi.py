@@ -39,6 +39,18 @@ class SearchTiming(C.Structure):
                 ("evaluations", C.c_int64)]
 
 
+class Grid(C.Structure):
+    """fdcm_grid: translations (x0 + i * sx, y0 + j * sy) for 0 <= i < nx, 0 <= j < ny."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("sx", C.c_int32),
+                ("sy", C.c_int32)]
+
+    def as_tuple(self):
+        return (self.x0, self.y0, self.nx, self.ny, self.sx, self.sy)
+
+    def __repr__(self):
+        return "Grid(x0={}, y0={}, nx={}, ny={}, sx={}, sy={})".format(*self.as_tuple())
+
+
 # every symbol include/fdcm.h declares: (name, restype, argtypes)
 _fp, _i64p, _vp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_void_p
 SYMBOLS = [
@@ -101,6 +113,10 @@ SYMBOLS = [
     ("fdcm_penalize", C.c_int, [C.c_int, C.c_float, _vp, C.c_int64, _fp, C.c_int64]),
     ("fdcm_sort_matches", C.c_int, [_vp, C.c_int64]),
     ("fdcm_partial_sort_matches", C.c_int, [_vp, C.c_int64, C.c_int64]),
+    ("fdcm_exhaustive_window", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.POINTER(Grid)]),
+    ("fdcm_search_exhaustive", C.c_int, [_vp, _vp, C.POINTER(Grid), C.c_int32, C.c_int32, C.POINTER(_vp), _i64p]),
+    ("fdcm_score_map", C.c_int, [_vp, _vp, C.POINTER(Grid), _fp]),
+    ("fdcm_score_map_device", C.c_int, [_vp, _vp, C.POINTER(Grid), _vp]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),
     ("fdcm_lines_free", None, [C.POINTER(C.c_float)]),

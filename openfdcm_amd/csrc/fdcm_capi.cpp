@@ -460,6 +460,59 @@ int fdcm_topk(fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_m
     });
 }
 
+// ------------------------------------------------------------------------------------------ exhaustive search
+// Definitions: include/fdcm.h, "exhaustive translation search" (the grid, score, admissible set, window and top-k order).
+static void check_exhaustive_args(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid* grid) {
+    require(grid != nullptr, "grid is null");
+    require(grid->nx >= 1 && grid->ny >= 1, "grid: nx and ny must be >= 1");
+    require(grid->sx >= 1 && grid->sy >= 1, "grid: strides sx and sy must be >= 1");
+    require((int64_t)grid->nx * grid->ny < ((int64_t)1 << 31), "grid: nx * ny must be below 2^31");
+    require(fm && t, "null featuremap/templates");
+    require(fm->device == t->device, "featuremap and templates live on different devices");
+}
+
+int fdcm_exhaustive_window(const fdcm_featuremap* fm, const fdcm_templates* templates, int32_t sx, int32_t sy, fdcm_grid* grid) {
+    return guarded([&] {
+        require(sx >= 1 && sy >= 1, "strides sx and sy must be >= 1");
+        require(fm && templates && grid, "null featuremap/templates/grid");
+        exhaustive_window(const_cast<fdcm_featuremap*>(fm), templates, sx, sy, grid);
+    });
+}
+
+int fdcm_search_exhaustive(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, int32_t k,
+                           int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out) {
+    return guarded([&] {
+        require(k >= 1 && k <= 64, "k must be in [1, 64]");
+        check_exhaustive_args(fm, templates, grid);
+        require(out && n_out, "null output");
+        *out = nullptr;
+        try {
+            run_search_exhaustive(const_cast<fdcm_featuremap*>(fm), templates, *grid, k, tmpl_index_base, out, n_out);
+        } catch (...) {
+            result_release(*out);
+            *out = nullptr;
+            throw;
+        }
+        if (!*out) *out = result_acquire(sizeof(fdcm_match));  // no records: an empty (non-null) array
+    });
+}
+
+int fdcm_score_map(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, float* out_host) {
+    return guarded([&] {
+        check_exhaustive_args(fm, templates, grid);
+        require(out_host != nullptr || templates->T == 0, "out_host is null");
+        run_score_map(const_cast<fdcm_featuremap*>(fm), templates, *grid, out_host, nullptr);
+    });
+}
+
+int fdcm_score_map_device(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, float* out_device) {
+    return guarded([&] {
+        check_exhaustive_args(fm, templates, grid);
+        require(out_device != nullptr || templates->T == 0, "out_device is null");
+        run_score_map(const_cast<fdcm_featuremap*>(fm), templates, *grid, nullptr, out_device);
+    });
+}
+
 int fdcm_search_last_timing(const fdcm_featuremap* fm, fdcm_search_timing* t) {
     return guarded([&] {
         require(fm && t, "null argument");

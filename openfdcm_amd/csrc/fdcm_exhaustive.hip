@@ -1,0 +1,503 @@
+// fdcm_exhaustive.hip -- exhaustive translation search: the score of every template at every point of a translation
+// grid (a dense chamfer score map) and the k best grid points of every template (include/fdcm.h, "exhaustive search").
+// A score is evaluate<Dt3Cpu> (dt3cpu.cpp:126-179) at one translation: the bits fdcm_featuremap_evaluate returns there.
+//
+//   k_exhaustive<BUF32, TOPK>  a workgroup takes a contiguous run of 16 x 64 sub-tiles of the grid (a portion) and a
+//                              chunk of kChunk templates; for every sub-tile it scores every template of the chunk (a lane per 4
+//                              translations), then writes the scores (map) or offers them to a running k-best list
+//                              per wave and template kept in LDS (top-k)
+//   k_exhaustive_merge         one wave per template merges the per-wave lists into the template's k best
+//
+// Keys of the top-k are (score bits << 32) | grid index: scores are >= +0, so the key order is the (score, g) order,
+// which is total -- the result does not depend on which wave saw which point first.  No atomics.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "fdcm_internal.h"
+#include "fdcm_score.h"
+
+namespace fdcm {
+
+namespace {
+
+constexpr int kChunk = 8;                 // templates per workgroup
+constexpr int kTileX = 16, kTileY = 64;   // a sub-tile: 4 waves x 4 columns (i) by 16 lanes x 4 rows (j) per wave
+constexpr int kRows = kTileY / 16;        // translations per lane
+constexpr int kMaxK = 64;
+constexpr unsigned long long kNoKey = ~0ull;
+constexpr int kMaxCoord = (1 << 24) - 1;  // valid translations: |t| < 2^24
+
+struct ExLine {  // one template line: end points, and the line's slice (bin * floats per slice, or the bin: see VolRef)
+    float x1, y1, x2, y2;
+    int se, pad0, pad1, pad2;
+};
+struct ExTmpl {    // one template of a launch
+    int line0, n;  // its lines in the line array
+    int i0, i1, j0, j1;  // grid indices of its admissible translations: [i0, i1] x [j0, j1] (empty when i0 > i1 or j0 > j1)
+    int slot, pad;       // where its output goes: map plane / candidate lists / merged list
+};
+
+// One read of the interleaved volume (ivol_index) at column x, row y of the line's slice.  xw: the column's part of the
+// element index (with the slice) from ex_column.  The 64-bit form clamps to the slice: its translations are admissible,
+// so the clamp never changes a value -- it only keeps a wrong interval from reading outside the volume (the 32-bit
+// form's buffer descriptor returns 0 outside it).
+template <bool BUF32>
+__device__ __forceinline__ size_t ex_column(int x, int se, int W, unsigned H, size_t SL) {
+    if (BUF32) return (size_t)((((__umul24((unsigned)x >> 2, H)) << 2) | ((unsigned)x & 3u)) + (unsigned)se);
+    x = min(max(x, 0), W - 1);
+    return (size_t)se * SL + (size_t)((unsigned)x >> 2) * H * 4 + (unsigned)(x & 3);
+}
+template <bool BUF32>
+__device__ __forceinline__ float ex_read(const VolRef& V, size_t xw, int y, unsigned H) {
+    if (BUF32) return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(V.rs, ((unsigned)xw + ((unsigned)y << 2)) << 2, 0, 0));
+    y = min(max(y, 0), (int)H - 1);
+    return V.vol[xw + (size_t)y * 4];
+}
+
+// The wave's sorted list of its k best keys, lane l holding entry l; insert key K (< entry k - 1).
+__device__ __forceinline__ unsigned long long list_insert(unsigned long long e, unsigned long long K, int lane) {
+    const int pos = __popcll(__ballot(e < K));
+    const unsigned long long up = __shfl_up(e, 1);
+    return lane > pos ? up : (lane == pos ? K : e);
+}
+__device__ __forceinline__ unsigned long long read_lane64(unsigned long long v, int src) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// Offers one key per lane (kNoKey: none) to the list e with threshold thr = entry k - 1; returns the new threshold.
+__device__ __forceinline__ unsigned long long list_offer(unsigned long long& e, unsigned long long key, unsigned long long thr,
+                                                         int k, int lane) {
+    unsigned long long mask = __ballot(key < thr);
+    while (mask) {  // wave-uniform
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        const unsigned long long K = read_lane64(key, src);
+        if (K < thr) {
+            e = list_insert(e, K, lane);
+            thr = read_lane64(e, k - 1);
+        }
+    }
+    return thr;
+}
+
+template <bool BUF32, bool TOPK>
+__global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
+                                                    float ty, const ExLine* __restrict__ lines, const ExTmpl* __restrict__ tm,
+                                                    int T, int x0, int y0, int nx, int ny, int sx, int sy, int tiles_x,
+                                                    int n_subtiles, int portions, int k, float* __restrict__ map,
+                                                    long long plane, unsigned long long* __restrict__ cand) {
+    __shared__ unsigned long long lists[TOPK ? 4 * kChunk * kMaxK : 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // Workgroup b -> (portion, template chunk).  Workgroups are observed to be dealt round-robin over the 8 XCDs (b and
+    // b + 8 share one): all chunks of portion p go to one XCD, next to each other in dispatch order, so they walk the same
+    // sub-tiles together and read one window of the volume through that XCD's L2.  Placement only affects speed.
+    const int n_chunks = (T + kChunk - 1) / kChunk;
+    const int r = (int)blockIdx.x / 8;
+    const int chunk = r % n_chunks, portion = (r / n_chunks) * 8 + (int)blockIdx.x % 8;
+    const int t_first = chunk * kChunk, t_end = min(T, t_first + kChunk);
+    const VolRef V = make_volref(vol, SL, m, BUF32);
+    const unsigned uH = (unsigned)H;
+    unsigned long long* L = lists + (TOPK ? wave * kChunk * kMaxK : 0);
+    if (TOPK)
+        for (int c = 0; c < kChunk; ++c) L[c * kMaxK + lane] = kNoKey;  // each wave owns its lists: no barrier
+
+    // a portion is a contiguous run of sub-tiles (row-major): the next sub-tile's window overlaps the last one's
+    const int s_begin = (int)((long long)n_subtiles * portion / portions);
+    const int s_end = (int)((long long)n_subtiles * (portion + 1) / portions);
+    for (int s = s_begin; s < s_end; ++s) {
+        const int ti = s % tiles_x, tj = s / tiles_x;
+        const int i = ti * kTileX + wave * 4 + (lane & 3);
+        const int jb = tj * kTileY + (lane >> 2);
+        const int tile_i0 = ti * kTileX, tile_j0 = tj * kTileY;
+        for (int t = t_first; t < t_end; ++t) {
+            const ExTmpl P = tm[t];
+            // the sub-tile against the template's admissible box (all wave-uniform)
+            const bool meets = P.i0 <= P.i1 && P.j0 <= P.j1 && P.i0 < tile_i0 + kTileX && P.i1 >= tile_i0 &&
+                               P.j0 < tile_j0 + kTileY && P.j1 >= tile_j0;
+            if (TOPK && !meets) continue;
+            bool act[kRows];
+            float offy[kRows];
+            // translate(tmpl, sceneTranslation + translation), dt3cpu.cpp:153.  A translation outside the box is
+            // replaced by the box's first corner, which is admissible: every read stays inside the volume
+            const bool act_i = i >= P.i0 && i <= P.i1;
+            const float offx = tx + (float)(x0 + (act_i ? i : P.i0) * sx);
+#pragma unroll
+            for (int r = 0; r < kRows; ++r) {
+                const int j = jb + 16 * r;
+                act[r] = act_i && j >= P.j0 && j <= P.j1;
+                offy[r] = ty + (float)(y0 + (act[r] ? j : P.j0) * sy);
+            }
+            float res[kRows] = {0.f, 0.f, 0.f, 0.f};
+            if (meets) {
+                // score_per_line.sum(), dt3cpu.cpp:175, in Eigen 3.4.0's order (as pair_score, fdcm_score.h): packets
+                // p0 = lines 8b..8b+3 and p1 = 8b+4..8b+7 summed over the blocks of 8, p0 += p1, the trailing packet,
+                // predux (p0[0] + p0[2]) + (p0[1] + p0[3]), then the scalar tail.  Zero-initialised accumulators give the
+                // same bits (0 + v == v for v >= +0), so one code path serves every n.
+                const ExLine* Lt = lines + P.line0;
+                const int n = P.n, aligned2 = (n / 8) * 8, aligned = (n / 4) * 4;
+                float p0[kRows][4], p1[kRows][4];
+#pragma unroll
+                for (int r = 0; r < kRows; ++r)
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) p0[r][l] = p1[r][l] = 0.f;
+                for (int b = 0; b < aligned2; b += 8) {
+                    float va[8][kRows], vb[8][kRows];
+#pragma unroll
+                    for (int l = 0; l < 8; ++l) {
+                        const ExLine ln = Lt[b + l];
+                        const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
+                        const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
+#pragma unroll
+                        for (int r = 0; r < kRows; ++r) {  // translate then cast<int>()
+                            va[l][r] = ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH);
+                            vb[l][r] = ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < kRows; ++r)
+#pragma unroll
+                        for (int l = 0; l < 4; ++l) {
+                            p0[r][l] = p0[r][l] + f_abs(va[l][r] - vb[l][r]);
+                            p1[r][l] = p1[r][l] + f_abs(va[l + 4][r] - vb[l + 4][r]);
+                        }
+                }
+#pragma unroll
+                for (int r = 0; r < kRows; ++r)
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + p1[r][l];
+                if (aligned > aligned2) {  // the trailing packet
+                    float va[4][kRows], vb[4][kRows];
+#pragma unroll
+                    for (int l = 0; l < 4; ++l) {
+                        const ExLine ln = Lt[aligned2 + l];
+                        const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
+                        const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
+#pragma unroll
+                        for (int r = 0; r < kRows; ++r) {
+                            va[l][r] = ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH);
+                            vb[l][r] = ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < kRows; ++r)
+#pragma unroll
+                        for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + f_abs(va[l][r] - vb[l][r]);
+                }
+                if (aligned)
+#pragma unroll
+                    for (int r = 0; r < kRows; ++r) res[r] = (p0[r][0] + p0[r][2]) + (p0[r][1] + p0[r][3]);
+                for (int idx = aligned; idx < n; ++idx) {  // the scalar tail, in order
+                    const ExLine ln = Lt[idx];
+                    const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
+                    const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
+#pragma unroll
+                    for (int r = 0; r < kRows; ++r)
+                        res[r] = res[r] + f_abs(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH) -
+                                                ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH));
+                }
+            }
+            if (!TOPK) {
+                if (i < nx) {
+                    float* out = map + (long long)P.slot * plane;
+#pragma unroll
+                    for (int r = 0; r < kRows; ++r) {
+                        const int j = jb + 16 * r;
+                        if (j < ny) out[(long long)j * nx + i] = act[r] ? res[r] : f_nan();
+                    }
+                }
+            } else {
+                unsigned long long* Lc = L + (t - t_first) * kMaxK;
+                unsigned long long thr = Lc[k - 1];
+                unsigned long long key[kRows];
+                bool any = false;
+#pragma unroll
+                for (int r = 0; r < kRows; ++r) {
+                    key[r] = act[r] ? ((unsigned long long)__float_as_uint(res[r]) << 32) | (unsigned)((jb + 16 * r) * nx + i)
+                                    : kNoKey;
+                    any = any || key[r] < thr;
+                }
+                if (__ballot(any)) {  // rare once the list has filled: the k-th best only falls
+                    unsigned long long e = Lc[lane];
+#pragma unroll
+                    for (int r = 0; r < kRows; ++r) thr = list_offer(e, key[r], thr, k, lane);
+                    Lc[lane] = e;
+                }
+            }
+        }
+    }
+    if (TOPK) {
+        // candidate lists: [slot][blockIdx.x * 4 + wave][k]
+        const long long n_lists = (long long)portions * 4;
+        for (int t = t_first; t < t_end; ++t) {
+            const unsigned long long v = L[(t - t_first) * kMaxK + lane];
+            if (lane < k) cand[((long long)tm[t].slot * n_lists + portion * 4 + wave) * k + lane] = v;
+        }
+    }
+}
+
+// One wave per template: the k best of its n_lists sorted lists of k keys.
+__global__ void __launch_bounds__(256) k_exhaustive_merge(const unsigned long long* __restrict__ cand, int T, int n_lists,
+                                                          int k, unsigned long long* __restrict__ best) {
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= T) return;  // wave-uniform
+    unsigned long long e = kNoKey, thr = kNoKey;
+    const unsigned long long* c = cand + (long long)t * n_lists * k;
+    for (int q = 0; q < n_lists; ++q) {
+        const unsigned long long v = lane < k ? c[(long long)q * k + lane] : kNoKey;
+        thr = list_offer(e, v, thr, k, lane);
+    }
+    if (lane < k) best[(long long)t * k + lane] = e;
+}
+
+long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+// The integer translations t in [-kMaxCoord, kMaxCoord] with lo < fl(p + fl(off + t)) < hi for p = pmin and p = pmax, i.e.
+// for every end point coordinate p of the template: the seam's rule (fdcm_seam.hip, k_evaluate) along one axis, with
+// lo = -1 and hi = the feature size.  Float addition is monotone, so the set is an interval; found by bisection on the
+// same float operations the kernels do.  Returns false when it is empty.
+bool axis_interval(float pmin, float pmax, float off, float size, int& a0, int& a1) {
+    auto above = [&](int t) { return pmin + (off + (float)t) > -1.f; };  // rises with t
+    auto below = [&](int t) { return pmax + (off + (float)t) < size; };  // falls with t
+    if (!above(kMaxCoord) || !below(-kMaxCoord)) return false;
+    int lo = -kMaxCoord, hi = kMaxCoord;  // the first t that is above
+    while (lo < hi) {
+        const int mid = (int)floor_div((long long)lo + hi, 2);
+        if (above(mid)) hi = mid; else lo = mid + 1;
+    }
+    a0 = lo;
+    lo = -kMaxCoord; hi = kMaxCoord;  // the last t that is below
+    while (lo < hi) {
+        const int mid = (int)floor_div((long long)lo + hi + 1, 2);
+        if (below(mid)) lo = mid; else hi = mid - 1;
+    }
+    a1 = lo;
+    return a0 <= a1;
+}
+
+struct Box { bool any; int x0, x1, y0, y1; };
+
+// The admissible translations of a template (lines [l0, l0 + n) of t): a box, or none.  A template without lines is
+// admissible everywhere.
+Box admissible_box(const fdcm_featuremap* fm, const fdcm_templates* t, int64_t l0, int64_t n) {
+    Box b{true, -kMaxCoord, kMaxCoord, -kMaxCoord, kMaxCoord};
+    if (n == 0) return b;
+    if (fm->W == 0 || fm->H == 0 || fm->m == 0) { b.any = false; return b; }
+    float mnx = f_inf(), mxx = -f_inf(), mny = f_inf(), mxy = -f_inf();
+    for (int64_t q = l0; q < l0 + n; ++q) {
+        const float* p = &t->lines[(size_t)q * 4];
+        for (int c = 0; c < 2; ++c) {
+            if (std::isnan(p[2 * c]) || std::isnan(p[2 * c + 1])) { b.any = false; return b; }
+            mnx = std::min(mnx, p[2 * c]); mxx = std::max(mxx, p[2 * c]);
+            mny = std::min(mny, p[2 * c + 1]); mxy = std::max(mxy, p[2 * c + 1]);
+        }
+    }
+    b.any = axis_interval(mnx, mxx, fm->tx, (float)fm->W, b.x0, b.x1) && axis_interval(mny, mxy, fm->ty, (float)fm->H, b.y0, b.y1);
+    return b;
+}
+
+// grid indices [i0, i1] of the points x0 + i * s inside [a0, a1]
+void grid_range(int a0, int a1, int x0, int n, int s, int& i0, int& i1) {
+    i0 = (int)std::max<long long>(0, -floor_div((long long)x0 - a0, s));  // ceil((a0 - x0) / s)
+    i1 = (int)std::min<long long>(n - 1, floor_div((long long)a1 - x0, s));
+}
+
+void check_grid(const fdcm_grid& g) {
+    if (g.nx < 1 || g.ny < 1) throw std::string("grid: nx and ny must be >= 1");
+    if (g.sx < 1 || g.sy < 1) throw std::string("grid: strides sx and sy must be >= 1");
+    if ((long long)g.nx * g.ny >= (1ll << 31)) throw std::string("grid: nx * ny must be below 2^31");
+    const long long xe = (long long)g.x0 + (long long)(g.nx - 1) * g.sx, ye = (long long)g.y0 + (long long)(g.ny - 1) * g.sy;
+    if (g.x0 < -kMaxCoord || xe > kMaxCoord || g.y0 < -kMaxCoord || ye > kMaxCoord)
+        throw std::string("grid: every translation must satisfy |t| < 2^24");
+}
+
+struct Prepared {
+    std::vector<ExLine> lines;
+    std::vector<ExTmpl> tm;  // every template of the set, slot = its index
+    bool buf32 = true;
+    size_t SL = 0;
+};
+
+// closestOrientation of every template line with the host libm (dt3cpu.cpp:144-148, as fdcm_seam.hip's run_evaluate) and
+// the admissible box of every template in grid indices.
+void prepare(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, Prepared& P) {
+    P.SL = ivol_slice_floats(fm->W, fm->H);
+    P.buf32 = (size_t)fm->m * P.SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
+    P.lines.resize((size_t)std::max<int64_t>(1, t->n_lines));
+    if (t->n_lines > 0x7fffffffll) throw std::string("too many template lines for one exhaustive search");
+    for (int64_t q = 0; q < t->n_lines && fm->m > 0; ++q) {
+        const float* p = &t->lines[(size_t)q * 4];
+        const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
+        const int bin = closest_orientation(fm->keys.data(), (int)fm->m, angle);
+        P.lines[(size_t)q] = ExLine{p[0], p[1], p[2], p[3], P.buf32 ? (int)((unsigned)bin * (unsigned)P.SL) : bin, 0, 0, 0};
+    }
+    P.tm.resize((size_t)t->T);
+    for (int64_t i = 0; i < t->T; ++i) {
+        const int64_t l0 = t->offsets[(size_t)i], n = t->offsets[(size_t)i + 1] - l0;
+        const Box b = admissible_box(fm, t, l0, n);
+        ExTmpl& e = P.tm[(size_t)i];
+        e = ExTmpl{(int)l0, (int)n, 0, -1, 0, -1, (int)i, 0};
+        if (b.any) {
+            grid_range(b.x0, b.x1, g.x0, g.nx, g.sx, e.i0, e.i1);
+            grid_range(b.y0, b.y1, g.y0, g.ny, g.sy, e.j0, e.j1);
+        }
+    }
+}
+
+void begin(fdcm_featuremap* fm) {
+    if (fm->vol_stage != 3) throw std::string("the feature map holds a partial build (no line integral): nothing to search");
+    finish_build(fm);
+    FDCM_HIP(hipSetDevice(fm->device));
+    if (!fm->stream) FDCM_HIP(hipStreamCreateWithFlags(&fm->stream, hipStreamNonBlocking));
+}
+
+size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Launches k_exhaustive over the templates tm (already on the device at d_tm) with the lines at d_lines.
+template <bool TOPK>
+void launch(fdcm_featuremap* fm, const Prepared& P, const fdcm_grid& g, const ExLine* d_lines, const ExTmpl* d_tm, int T, int k,
+            int portions, float* map, unsigned long long* cand) {
+    const int tiles_x = (g.nx + kTileX - 1) / kTileX, tiles_y = (g.ny + kTileY - 1) / kTileY;
+    const int n_subtiles = tiles_x * tiles_y;
+    const float* vol = fm->vol.as<float>();
+    const long long plane = (long long)g.nx * g.ny;
+    const int per_launch = (1 << 20) * kChunk;  // keeps portions x chunks in range; outputs go by slot
+    for (int t0 = 0; t0 < T; t0 += per_launch) {
+        const int nt = std::min(per_launch, T - t0);
+        const dim3 grid((unsigned)(portions * ((nt + kChunk - 1) / kChunk)));  // portions: a multiple of 8
+        if (P.buf32)
+            hipLaunchKernelGGL((k_exhaustive<true, TOPK>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+                               fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
+                               map, plane, cand);
+        else
+            hipLaunchKernelGGL((k_exhaustive<false, TOPK>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+                               fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
+                               map, plane, cand);
+        FDCM_HIP(hipGetLastError());
+    }
+}
+
+// Workgroups along the grid (a multiple of 8, one group per XCD): about as many workgroups of all template chunks as are
+// resident at once (4 per compute unit: 128 VGPRs), no more groups than sub-tiles.
+int portions_for(const fdcm_featuremap* fm, const fdcm_grid& g, int T) {
+    const long long n_subtiles = (long long)((g.nx + kTileX - 1) / kTileX) * ((g.ny + kTileY - 1) / kTileY);
+    const long long chunks = (std::min(T, (1 << 20) * kChunk) + kChunk - 1) / kChunk;
+    const long long per_xcd = std::max<long long>(1, (4ll * device_cus(fm->device) / 8) / chunks);
+    return 8 * (int)std::max<long long>(1, std::min<long long>(per_xcd, (n_subtiles + 7) / 8));
+}
+
+}  // namespace
+
+void exhaustive_window(fdcm_featuremap* fm, const fdcm_templates* t, int32_t sx, int32_t sy, fdcm_grid* out) {
+    if (sx < 1 || sy < 1) throw std::string("strides sx and sy must be >= 1");
+    long long X0 = 0, X1 = -1, Y0 = 0, Y1 = -1;
+    bool any = false;
+    for (int64_t i = 0; i < t->T; ++i) {
+        const int64_t l0 = t->offsets[(size_t)i], n = t->offsets[(size_t)i + 1] - l0;
+        if (n == 0) continue;  // a template without lines emits nothing: it does not widen the window
+        const Box b = admissible_box(fm, t, l0, n);
+        if (!b.any) continue;
+        X0 = any ? std::min<long long>(X0, b.x0) : b.x0; X1 = any ? std::max<long long>(X1, b.x1) : b.x1;
+        Y0 = any ? std::min<long long>(Y0, b.y0) : b.y0; Y1 = any ? std::max<long long>(Y1, b.y1) : b.y1;
+        any = true;
+    }
+    fdcm_grid g{0, 0, 0, 0, sx, sy};
+    if (any) {
+        const long long x0 = floor_div(X0, sx) * sx, y0 = floor_div(Y0, sy) * sy;
+        g.x0 = (int32_t)x0; g.y0 = (int32_t)y0;
+        g.nx = (int32_t)(floor_div(X1 - x0, sx) + 1);
+        g.ny = (int32_t)(floor_div(Y1 - y0, sy) + 1);
+    }
+    *out = g;
+}
+
+void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, float* out_host, float* out_device) {
+    check_grid(g);
+    if (t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);  // concurrent callers of one feature map take turns (shared s_eval)
+    begin(fm);
+    Prepared P;
+    prepare(fm, t, g, P);
+    const int64_t T = t->T;
+    const size_t plane_bytes = (size_t)g.nx * g.ny * sizeof(float);
+    // host output: templates in batches whose maps fit a 256 MB workspace; device output: one launch
+    const int64_t batch = out_device ? T : std::max<int64_t>(1, std::min<int64_t>(T, ((size_t)256 << 20) / plane_bytes));
+    const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_map = o_tm + al256(P.tm.size() * sizeof(ExTmpl));
+    fm->s_eval.reserve(o_map + (out_device ? 0 : (size_t)batch * plane_bytes));
+    char* d = (char*)fm->s_eval.p;
+    hipStream_t st = fm->stream;
+    for (int64_t b0 = 0; b0 < T; b0 += batch) {
+        const int nb = (int)std::min<int64_t>(batch, T - b0);
+        for (int q = 0; q < nb; ++q) P.tm[(size_t)(b0 + q)].slot = out_device ? (int)(b0 + q) : q;
+    }
+    FDCM_HIP(hipMemcpyAsync(d + o_lines, P.lines.data(), P.lines.size() * sizeof(ExLine), hipMemcpyHostToDevice, st));
+    FDCM_HIP(hipMemcpyAsync(d + o_tm, P.tm.data(), P.tm.size() * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
+    for (int64_t b0 = 0; b0 < T; b0 += batch) {
+        const int nb = (int)std::min<int64_t>(batch, T - b0);
+        float* map = out_device ? out_device : (float*)(d + o_map);
+        launch<false>(fm, P, g, (const ExLine*)(d + o_lines), (const ExTmpl*)(d + o_tm) + b0, nb, 0, portions_for(fm, g, nb), map,
+                      nullptr);
+        if (!out_device)
+            FDCM_HIP(hipMemcpyAsync(out_host + (size_t)b0 * g.nx * g.ny, map, (size_t)nb * plane_bytes, hipMemcpyDeviceToHost, st));
+    }
+    FDCM_HIP(hipStreamSynchronize(st));  // (P stays alive until here)
+}
+
+void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int32_t base,
+                           fdcm_match** out, int64_t* n_out) {
+    check_grid(g);
+    if (k < 1 || k > kMaxK) throw std::string("k must be in [1, 64]");
+    *n_out = 0;
+    if (t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    Prepared P;
+    prepare(fm, t, g, P);
+    // the templates that can emit: lines, and admissible points in the grid (search() skips templates without lines)
+    std::vector<ExTmpl> act;
+    std::vector<int32_t> index;  // the set's index of every template in `act`
+    for (const ExTmpl& e : P.tm)
+        if (e.n > 0 && e.i0 <= e.i1 && e.j0 <= e.j1) { act.push_back(e); index.push_back(e.slot); }
+    if (act.empty()) return;
+    const int T = (int)act.size();
+    for (int q = 0; q < T; ++q) act[(size_t)q].slot = q;
+    const int portions = portions_for(fm, g, T), n_lists = portions * 4;
+    const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_cand = o_tm + al256(act.size() * sizeof(ExTmpl)),
+                 o_best = o_cand + al256((size_t)T * n_lists * k * 8), total = o_best + al256((size_t)T * k * 8);
+    fm->s_eval.reserve(total);
+    char* d = (char*)fm->s_eval.p;
+    hipStream_t st = fm->stream;
+    FDCM_HIP(hipMemcpyAsync(d + o_lines, P.lines.data(), P.lines.size() * sizeof(ExLine), hipMemcpyHostToDevice, st));
+    FDCM_HIP(hipMemcpyAsync(d + o_tm, act.data(), act.size() * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
+    launch<true>(fm, P, g, (const ExLine*)(d + o_lines), (const ExTmpl*)(d + o_tm), T, k, portions, nullptr,
+                 (unsigned long long*)(d + o_cand));
+    hipLaunchKernelGGL(k_exhaustive_merge, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, (const unsigned long long*)(d + o_cand), T,
+                       n_lists, k, (unsigned long long*)(d + o_best));
+    FDCM_HIP(hipGetLastError());
+    std::vector<unsigned long long> best((size_t)T * k);
+    FDCM_HIP(hipMemcpyAsync(best.data(), d + o_best, best.size() * 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    int64_t n = 0;
+    for (unsigned long long v : best) n += v != kNoKey;
+    fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, n) * sizeof(fdcm_match));
+    int64_t w = 0;
+    for (int q = 0; q < T; ++q)  // ascending template index: `act` keeps the set's order
+        for (int r = 0; r < k; ++r) {
+            const unsigned long long v = best[(size_t)q * k + r];
+            if (v == kNoKey) break;
+            const unsigned gi = (unsigned)(v & 0xffffffffu);
+            const int i = (int)(gi % (unsigned)g.nx), j = (int)(gi / (unsigned)g.nx);
+            fdcm_match& rec = m[w++];
+            rec.tmpl_idx = base + index[(size_t)q];
+            rec.score = f_from_bits((uint32_t)(v >> 32));
+            // combine(t, identity): the transform of a pure translation (Match.transform)
+            rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = (float)(g.x0 + i * g.sx);
+            rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = (float)(g.y0 + j * g.sy);
+        }
+    *out = m;
+    *n_out = n;
+}
+
+}  // namespace fdcm

@@ -208,6 +208,11 @@ bool orientation_bins_on_host();
 void run_minmax(fdcm_featuremap* fm, const float* lines, const int64_t* offsets, int64_t T, const float* align, float* out);
 void run_evaluate(fdcm_featuremap* fm, const float* lines, const int64_t* offsets, int64_t T, const float* translations,
                   const int64_t* tr_offsets, float* scores);
+// implemented in fdcm_exhaustive.hip: the exhaustive translation search (include/fdcm.h)
+void exhaustive_window(fdcm_featuremap* fm, const fdcm_templates* t, int32_t sx, int32_t sy, fdcm_grid* out);
+void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, float* out_host, float* out_device);
+void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int32_t base,
+                           fdcm_match** out, int64_t* n_out);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

@@ -20,6 +20,16 @@ def _adopt_matches(ptr, n):
     return res
 
 
+def as_grid(grid):
+    """capi.Grid from a capi.Grid or an (x0, y0, nx, ny, sx, sy) sequence."""
+    if isinstance(grid, capi.Grid):
+        return grid
+    vals = [int(v) for v in grid]
+    if len(vals) != 6:
+        raise ValueError("a grid is (x0, y0, nx, ny, sx, sy)")
+    return capi.Grid(*vals)
+
+
 class DeviceFeatureMap:
     """Owns an fdcm_featuremap handle (DT3 volume resident in HBM)."""
 
@@ -130,6 +140,35 @@ class DeviceFeatureMap:
             self._h, capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)), len(offsets) - 1, capi.fptr(tflat),
             toff.ctypes.data_as(C.POINTER(C.c_int64)), capi.fptr(scores)))
         return [scores[toff[i]:toff[i + 1]].copy() for i in range(len(trs))]
+
+    # ---- exhaustive translation search (include/fdcm.h): grids are capi.Grid or (x0, y0, nx, ny, sx, sy)
+    def exhaustive_window(self, templates, sx=1, sy=1):
+        """The smallest grid with strides (sx, sy), origin a multiple of them, that holds every admissible integer
+        translation of every template with lines (nx = ny = 0: none).  templates: DeviceTemplates."""
+        g = capi.Grid()
+        capi.check(capi.lib().fdcm_exhaustive_window(self._h, templates._h, int(sx), int(sy), C.byref(g)))
+        return g
+
+    def exhaustive_search(self, templates, grid, k=1, tmpl_index_base=0):
+        """Per template with lines: its k best admissible grid points by (score, grid index), as raw match records
+        (capi.MATCH_DTYPE) with transform [1, 0, tx, 0, 1, ty]."""
+        g = as_grid(grid)
+        out, n = C.c_void_p(), C.c_int64()
+        capi.check(capi.lib().fdcm_search_exhaustive(self._h, templates._h, C.byref(g), int(k), int(tmpl_index_base),
+                                                     C.byref(out), C.byref(n)))
+        return _adopt_matches(out, n.value)
+
+    def score_map(self, templates, grid):
+        """(T, ny, nx) float32: the score of every template at every grid point, NaN where not admissible."""
+        g = as_grid(grid)
+        out = np.empty((templates.count, g.ny, g.nx), dtype=np.float32)
+        capi.check(capi.lib().fdcm_score_map(self._h, templates._h, C.byref(g), capi.fptr(out)))
+        return out
+
+    def score_map_into(self, templates, grid, device_ptr):
+        """The score map into a device buffer of T * ny * nx floats."""
+        g = as_grid(grid)
+        capi.check(capi.lib().fdcm_score_map_device(self._h, templates._h, C.byref(g), C.c_void_p(device_ptr)))
 
     def stage_timing(self, on):
         """Device-side times cost an event between the kernels: True / 1 per-stage times (default), 2 the build's and the

@@ -1,0 +1,110 @@
+"""Times the exhaustive translation search (include/fdcm.h, "exhaustive translation search") on config 2': the feature map
+and the 1000 x 32-line synthetic templates bench.py uses, every template over its default window (exhaustive_window), at
+stride 1, 2 and 4 with k = 1 and 8.
+
+For every case it prints the wall time of one blocking fdcm_search_exhaustive call (median of --reps after a warm-up),
+the admissible translations scored (the sum over templates of the window's points inside each template's admissible
+box), and the lookup rate: 2 lookups per template line and admissible translation.  The CPU figure is the oracle's
+evaluate<Dt3Cpu> (the reference's code, one host thread) on a random sample of admissible translations, the same
+lookups per translation.
+
+    python tools/exhaustive_bench.py [--reps 5] [--cpu-sample 20000] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def boxes(dev, tmpls):
+    """Per template its admissible box (x0, y0, x1, y1), from the stride-1 window of the template alone."""
+    from openfdcm_amd.engine import DeviceTemplates
+    out = []
+    for t in tmpls:
+        ts = DeviceTemplates([t])
+        x0, y0, nx, ny, _, _ = dev.exhaustive_window(ts, 1, 1).as_tuple()
+        ts.close()
+        out.append((x0, y0, x0 + nx - 1, y0 + ny - 1) if nx else None)
+    return out
+
+
+def points_in(lo, hi, g0, n, s):
+    """Grid points g0 + i s (0 <= i < n) inside [lo, hi]."""
+    i0 = max(0, -((g0 - lo) // s))
+    i1 = min(n - 1, (hi - g0) // s)
+    return max(0, i1 - i0 + 1)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cpu-sample", type=int, default=20000, help="translations the oracle scores on the host")
+    ap.add_argument("--strides", default="1,2,4")
+    ap.add_argument("--ks", default="1,8")
+    ap.add_argument("--json", default=None, help="also write the results here")
+    args = ap.parse_args()
+
+    from openfdcm_amd import synthetic
+    from openfdcm_amd.engine import DeviceFeatureMap, DeviceTemplates
+    from oracle import oracle as O
+
+    cfg, scene, tmpls = synthetic.make_config("2p")
+    dev = DeviceFeatureMap.build(scene, depth=cfg["depth"], coeff=5.0, padding=1.0, distance=cfg["distance"])
+    tset = DeviceTemplates(tmpls)
+    n_lines = int(sum(t.shape[1] for t in tmpls))
+    bx = boxes(dev, tmpls)
+    rows = []
+    for s in [int(v) for v in args.strides.split(",")]:
+        grid = dev.exhaustive_window(tset, s, s).as_tuple()
+        x0, y0, nx, ny, sx, sy = grid
+        adm = [0 if b is None else points_in(b[0], b[2], x0, nx, sx) * points_in(b[1], b[3], y0, ny, sy) for b in bx]
+        lookups = 2 * sum(a * t.shape[1] for a, t in zip(adm, tmpls))
+        for k in [int(v) for v in args.ks.split(",")]:
+            dev.exhaustive_search(tset, grid, k=k)  # warm-up: workspaces, code objects
+            times = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                recs = dev.exhaustive_search(tset, grid, k=k)
+                times.append(time.perf_counter() - t0)
+            ms = float(np.median(times)) * 1e3
+            rows.append({"stride": s, "k": k, "grid": list(grid), "grid_points": nx * ny, "admissible": int(sum(adm)),
+                         "lookups": int(lookups), "ms_per_call": round(ms, 3), "ms_min": round(min(times) * 1e3, 3),
+                         "lookups_per_s": float(f"{lookups / (ms * 1e-3):.4g}"), "records": int(len(recs))})
+            print(f"stride {s} k {k}: grid {nx}x{ny}, {sum(adm)} admissible translations, {lookups:.3g} lookups, "
+                  f"{ms:.2f} ms/call (min {min(times) * 1e3:.2f}), {lookups / (ms * 1e-3):.3g} lookups/s", flush=True)
+
+    # the same work on the host: the oracle's evaluate (one thread) on random admissible translations of random templates
+    orc = O.build(scene, depth=cfg["depth"], coeff=5.0, padding=1.0, distance=cfg["distance"], nthreads=16)
+    rng = np.random.default_rng(7)
+    per = 500
+    picks = [t for t in rng.permutation(len(tmpls)) if bx[t] is not None][: max(1, args.cpu_sample // per)]
+    cpu_s, cpu_lookups = 0.0, 0
+    for t in picks:
+        b = bx[t]
+        tr = np.stack([rng.integers(b[0], b[2] + 1, per), rng.integers(b[1], b[3] + 1, per)], axis=1).astype(np.float32)
+        t0 = time.perf_counter()
+        O.evaluate(orc, tmpls[t], tr)
+        cpu_s += time.perf_counter() - t0
+        cpu_lookups += 2 * tmpls[t].shape[1] * per
+    cpu = {"threads": 1, "translations": per * len(picks), "lookups": cpu_lookups, "seconds": round(cpu_s, 4),
+           "lookups_per_s": float(f"{cpu_lookups / cpu_s:.4g}")}
+    print(f"CPU (oracle evaluate<Dt3Cpu>, 1 thread): {cpu['translations']} translations, {cpu_lookups:.3g} lookups in "
+          f"{cpu_s * 1e3:.1f} ms: {cpu['lookups_per_s']:.3g} lookups/s", flush=True)
+    for r in rows:
+        r["speedup_vs_cpu_1thread"] = round(r["lookups_per_s"] / cpu["lookups_per_s"], 1)
+    res = {"workload": "config 2': 1024x1024 scene (200 lines, seed 1), depth 30, L2, padding 1.0; 1000 templates x 32 lines "
+                       "(seed 2), default window per stride", "template_lines": n_lines, "gpu": rows, "cpu": cpu}
+    print(json.dumps(res))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
