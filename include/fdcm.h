@@ -314,6 +314,17 @@ int fdcm_exhaustive_window(const fdcm_featuremap* fm, const fdcm_templates* temp
  * zero records.  Release with fdcm_matches_free. */
 int fdcm_search_exhaustive(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, int32_t k,
                            int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out);
+/* Peaks: key(p) = (score bits << 32) | g for an admissible point p (a total order; points that are not admissible have no
+ * key).  For radii 0 <= rx, ry <= 32 in grid steps, an admissible point p = (i, j) is a peak of its template when
+ * key(p) < key(q) for every other admissible point q = (i', j') of the grid with |i' - i| <= rx and |j' - j| <= ry:
+ * key(p) is the minimum of the keys in its (2 rx + 1) x (2 ry + 1) window, neighbours outside the grid or not admissible
+ * ignored.  Two peaks are never within (rx, ry) of each other; on a plateau of equal scores the lowest grid index wins.
+ * Per template with lines, in ascending index: its peaks ordered by key, the first min(k, count) of them (1 <= k <= 64),
+ * as the records of fdcm_search_exhaustive.  Templates without lines or without admissible points in the grid give
+ * nothing; an empty feature map or template list gives zero records.  rx = ry = 0 is exactly fdcm_search_exhaustive.
+ * Device memory stays below 1 GB whatever the templates and the grid.  Release with fdcm_matches_free. */
+int fdcm_search_exhaustive_peaks(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, int32_t k,
+                                 int32_t rx, int32_t ry, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out);
 /* The score map: out[template][j][i] = score at grid point (i, j) where admissible, NaN elsewhere (n_templates * ny * nx
  * floats). */
 int fdcm_score_map(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, float* out_host);

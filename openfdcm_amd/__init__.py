@@ -479,6 +479,20 @@ def exhaustive_search(featuremap, templates, stride=1, k=1, window=None):
     return MatchList(fm.exhaustive_search(tset, g, k=k))
 
 
+def exhaustive_peaks(featuremap, templates, radius, stride=1, k=1, window=None):
+    """exhaustive_search for detection: per template its k best peaks of the score map, ordered by (score, grid index).  A
+    peak is an admissible grid point whose (score, grid index) is the smallest within radius = r or (rx, ry) grid steps
+    (0 <= rx, ry <= 32) on either axis, so two peaks of one template are never that close; radius 0 is exhaustive_search.
+    Returns a MatchList of pure translations, ready for penalize / sort_matches."""
+    rx, ry = _strides(radius)
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates)
+    g = _window(fm, tset, stride, window)
+    if g[2] == 0 or g[3] == 0:
+        return MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
+    return MatchList(fm.exhaustive_peaks(tset, g, k=k, rx=rx, ry=ry))
+
+
 def score_map(featuremap, templates, stride=1, window=None):
     """The dense chamfer score map: (float32 array [T, ny, nx] of the scores, NaN where a translation puts the template
     outside the feature map; grid (x0, y0, nx, ny, sx, sy)).  Point (i, j) is the translation (x0 + i sx, y0 + j sy)."""

@@ -115,6 +115,8 @@ SYMBOLS = [
     ("fdcm_partial_sort_matches", C.c_int, [_vp, C.c_int64, C.c_int64]),
     ("fdcm_exhaustive_window", C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.POINTER(Grid)]),
     ("fdcm_search_exhaustive", C.c_int, [_vp, _vp, C.POINTER(Grid), C.c_int32, C.c_int32, C.POINTER(_vp), _i64p]),
+    ("fdcm_search_exhaustive_peaks", C.c_int, [_vp, _vp, C.POINTER(Grid), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(_vp), _i64p]),
     ("fdcm_score_map", C.c_int, [_vp, _vp, C.POINTER(Grid), _fp]),
     ("fdcm_score_map_device", C.c_int, [_vp, _vp, C.POINTER(Grid), _vp]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),

@@ -497,6 +497,25 @@ int fdcm_search_exhaustive(const fdcm_featuremap* fm, const fdcm_templates* temp
     });
 }
 
+int fdcm_search_exhaustive_peaks(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, int32_t k,
+                                 int32_t rx, int32_t ry, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out) {
+    return guarded([&] {
+        require(k >= 1 && k <= 64, "k must be in [1, 64]");
+        require(rx >= 0 && rx <= 32 && ry >= 0 && ry <= 32, "radii rx and ry must be in [0, 32]");
+        check_exhaustive_args(fm, templates, grid);
+        require(out && n_out, "null output");
+        *out = nullptr;
+        try {
+            run_search_exhaustive_peaks(const_cast<fdcm_featuremap*>(fm), templates, *grid, k, rx, ry, tmpl_index_base, out, n_out);
+        } catch (...) {
+            result_release(*out);
+            *out = nullptr;
+            throw;
+        }
+        if (!*out) *out = result_acquire(sizeof(fdcm_match));  // no records: an empty (non-null) array
+    });
+}
+
 int fdcm_score_map(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, float* out_host) {
     return guarded([&] {
         check_exhaustive_args(fm, templates, grid);

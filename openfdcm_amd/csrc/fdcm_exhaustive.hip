@@ -7,6 +7,8 @@
 //                              translations), then writes the scores (map) or offers them to a running k-best list
 //                              per wave and template kept in LDS (top-k)
 //   k_exhaustive_merge         one wave per template merges the per-wave lists into the template's k best
+//   k_exhaustive_peaks<R>      peaks: reads the score planes k_exhaustive<., false> wrote and offers every point whose
+//                              key is the minimum of its (2rx+1) x (2ry+1) window to a per-wave k-best list
 //
 // Keys of the top-k are (score bits << 32) | grid index: scores are >= +0, so the key order is the (score, g) order,
 // which is total -- the result does not depend on which wave saw which point first.  No atomics.
@@ -252,6 +254,81 @@ __global__ void __launch_bounds__(256) k_exhaustive_merge(const unsigned long lo
     if (lane < k) best[(long long)t * k + lane] = e;
 }
 
+// Peaks (include/fdcm.h, "peaks"): a point is a peak when its key is the minimum of the keys in its (2rx+1) x (2ry+1)
+// window.  A workgroup takes tiles of kPkTX x kPkTY points of one template's score plane (written by k_exhaustive<., false>)
+// and loads each with its rx / ry halo into LDS as score bits, kPkNone for no key (outside the plane or the template's
+// box, or NaN).  Row pass: per halo row and tile column the minimum key of the row's 2rx+1 window (the smallest score
+// bits, the first column on ties: within a row the grid index rises with i).  Column pass: per tile point the minimum
+// of the 2ry+1 row minima; the point is a peak when that is its own key.  Peaks go to the wave's sorted k-best list
+// (registers, lane l holding entry l) with list_offer; k_exhaustive_merge folds the lists.  R: the largest radius the
+// LDS is sized for.
+constexpr int kPkTX = 64, kPkTY = 32;  // tile: a wave per row, kPkTY / 4 rows per wave
+constexpr unsigned kPkNone = ~0u;      // no key: above the bits of every score >= +0 (NaN included)
+constexpr int kMaxRadius = 32;
+constexpr size_t kPeakMapBytes = (size_t)768 << 20;  // the score planes of one batch
+constexpr int kPeakWorkgroups = 2048;                // peak workgroups of a launch, about: parts per template
+
+template <int R>
+__global__ void __launch_bounds__(256) k_exhaustive_peaks(const float* __restrict__ map, int w, int h, const ExTmpl* __restrict__ tm,
+                                                          int parts, int rx, int ry, int di0, int di1, int dj0, int dj1, int ia,
+                                                          int ja, int nx, int k, int n_lists,
+                                                          unsigned long long* __restrict__ cand) {
+    constexpr int kW = kPkTX + 2 * R, kH = kPkTY + 2 * R;
+    __shared__ unsigned S[kH * kW];             // score bits of the tile and its halo
+    __shared__ unsigned long long B[kH * kPkTX];  // row-window minimum keys
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = (int)blockIdx.x / parts, part = (int)blockIdx.x % parts;
+    const ExTmpl P = tm[q];
+    const float* plane = map + (long long)P.slot * w * h;
+    const int W2 = kPkTX + 2 * rx, H2 = kPkTY + 2 * ry;
+    // the points this launch decides for the template: its box (plane coordinates) within the decision rectangle
+    const int bi0 = max(P.i0, di0), bi1 = min(P.i1, di1), bj0 = max(P.j0, dj0), bj1 = min(P.j1, dj1);
+    const int ntx = bi0 <= bi1 ? (bi1 - bi0) / kPkTX + 1 : 0, nty = bj0 <= bj1 ? (bj1 - bj0) / kPkTY + 1 : 0;
+    unsigned long long e = kNoKey, thr = kNoKey;
+    for (int tile = part; tile < ntx * nty; tile += parts) {  // workgroup-uniform
+        const int li0 = bi0 + (tile % ntx) * kPkTX, lj0 = bj0 + (tile / ntx) * kPkTY;
+        for (int idx = threadIdx.x; idx < H2 * W2; idx += 256) {
+            const int hr = idx / W2, hc = idx - hr * W2;
+            const int li = li0 - rx + hc, lj = lj0 - ry + hr;
+            unsigned v = kPkNone;
+            if (li >= P.i0 && li <= P.i1 && lj >= P.j0 && lj <= P.j1) {  // the box lies inside the plane
+                const float s = plane[(long long)lj * w + li];
+                if (!(s != s)) v = __float_as_uint(s);
+            }
+            S[hr * kW + hc] = v;
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < H2 * kPkTX; idx += 256) {
+            const int hr = idx / kPkTX, c = idx % kPkTX;
+            const unsigned* row = S + hr * kW + c;
+            unsigned best = row[0];
+            int at = 0;
+            for (int d = 1; d <= 2 * rx; ++d) {
+                const unsigned v = row[d];
+                if (v < best) { best = v; at = d; }
+            }
+            const unsigned g = (unsigned)(ja + lj0 - ry + hr) * (unsigned)nx + (unsigned)(ia + li0 - rx + c + at);
+            B[hr * kPkTX + c] = best == kPkNone ? kNoKey : ((unsigned long long)best << 32) | g;
+        }
+        __syncthreads();
+        for (int r = wave; r < kPkTY; r += 4) {  // wave-uniform: every lane takes part in list_offer
+            const int li = li0 + lane, lj = lj0 + r;
+            unsigned long long m = kNoKey;
+            for (int d = 0; d <= 2 * ry; ++d) m = min(m, B[(r + d) * kPkTX + lane]);
+            const unsigned s = S[(r + ry) * kW + rx + lane];
+            unsigned long long key = kNoKey;
+            if (s != kPkNone && li <= bi1 && lj <= bj1) {
+                const unsigned long long own = ((unsigned long long)s << 32) | ((unsigned)(ja + lj) * (unsigned)nx + (unsigned)(ia + li));
+                if (own == m) key = own;
+            }
+            thr = list_offer(e, key, thr, k, lane);
+        }
+        __syncthreads();  // the next tile overwrites S and B
+    }
+    // candidate lists: [q][part * 4 + wave][k] of n_lists per template (the last list is the caller's)
+    if (lane < k) cand[((long long)q * n_lists + part * 4 + wave) * k + lane] = e;
+}
+
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // The integer translations t in [-kMaxCoord, kMaxCoord] with lo < fl(p + fl(off + t)) < hi for p = pmin and p = pmax, i.e.
@@ -388,6 +465,38 @@ int portions_for(const fdcm_featuremap* fm, const fdcm_grid& g, int T) {
     return 8 * (int)std::max<long long>(1, std::min<long long>(per_xcd, (n_subtiles + 7) / 8));
 }
 
+// The templates that can emit: lines, and admissible points in the grid (search() skips templates without lines); index:
+// the set's index of every template in `act`.
+void active_templates(const Prepared& P, std::vector<ExTmpl>& act, std::vector<int32_t>& index) {
+    for (const ExTmpl& e : P.tm)
+        if (e.n > 0 && e.i0 <= e.i1 && e.j0 <= e.j1) { act.push_back(e); index.push_back(e.slot); }
+}
+
+// The records of the merged lists best[q][k] of the templates index[q] (kNoKey ends a list).
+void emit_records(const std::vector<unsigned long long>& best, int k, const std::vector<int32_t>& index, const fdcm_grid& g,
+                  int32_t base, fdcm_match** out, int64_t* n_out) {
+    const int T = (int)index.size();
+    int64_t n = 0;
+    for (unsigned long long v : best) n += v != kNoKey;
+    fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, n) * sizeof(fdcm_match));
+    int64_t w = 0;
+    for (int q = 0; q < T; ++q)  // ascending template index: `act` keeps the set's order
+        for (int r = 0; r < k; ++r) {
+            const unsigned long long v = best[(size_t)q * k + r];
+            if (v == kNoKey) break;
+            const unsigned gi = (unsigned)(v & 0xffffffffu);
+            const int i = (int)(gi % (unsigned)g.nx), j = (int)(gi / (unsigned)g.nx);
+            fdcm_match& rec = m[w++];
+            rec.tmpl_idx = base + index[(size_t)q];
+            rec.score = f_from_bits((uint32_t)(v >> 32));
+            // combine(t, identity): the transform of a pure translation (Match.transform)
+            rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = (float)(g.x0 + i * g.sx);
+            rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = (float)(g.y0 + j * g.sy);
+        }
+    *out = m;
+    *n_out = n;
+}
+
 }  // namespace
 
 void exhaustive_window(fdcm_featuremap* fm, const fdcm_templates* t, int32_t sx, int32_t sy, fdcm_grid* out) {
@@ -455,11 +564,9 @@ void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const f
     begin(fm);
     Prepared P;
     prepare(fm, t, g, P);
-    // the templates that can emit: lines, and admissible points in the grid (search() skips templates without lines)
     std::vector<ExTmpl> act;
-    std::vector<int32_t> index;  // the set's index of every template in `act`
-    for (const ExTmpl& e : P.tm)
-        if (e.n > 0 && e.i0 <= e.i1 && e.j0 <= e.j1) { act.push_back(e); index.push_back(e.slot); }
+    std::vector<int32_t> index;
+    active_templates(P, act, index);
     if (act.empty()) return;
     const int T = (int)act.size();
     for (int q = 0; q < T; ++q) act[(size_t)q].slot = q;
@@ -479,25 +586,111 @@ void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const f
     std::vector<unsigned long long> best((size_t)T * k);
     FDCM_HIP(hipMemcpyAsync(best.data(), d + o_best, best.size() * 8, hipMemcpyDeviceToHost, st));
     FDCM_HIP(hipStreamSynchronize(st));
-    int64_t n = 0;
-    for (unsigned long long v : best) n += v != kNoKey;
-    fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, n) * sizeof(fdcm_match));
-    int64_t w = 0;
-    for (int q = 0; q < T; ++q)  // ascending template index: `act` keeps the set's order
-        for (int r = 0; r < k; ++r) {
-            const unsigned long long v = best[(size_t)q * k + r];
-            if (v == kNoKey) break;
-            const unsigned gi = (unsigned)(v & 0xffffffffu);
-            const int i = (int)(gi % (unsigned)g.nx), j = (int)(gi / (unsigned)g.nx);
-            fdcm_match& rec = m[w++];
-            rec.tmpl_idx = base + index[(size_t)q];
-            rec.score = f_from_bits((uint32_t)(v >> 32));
-            // combine(t, identity): the transform of a pure translation (Match.transform)
-            rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = (float)(g.x0 + i * g.sx);
-            rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = (float)(g.y0 + j * g.sy);
+    emit_records(best, k, index, g, base, out, n_out);
+}
+
+void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int rx, int ry,
+                                 int32_t base, fdcm_match** out, int64_t* n_out) {
+    check_grid(g);
+    if (k < 1 || k > kMaxK) throw std::string("k must be in [1, 64]");
+    if (rx < 0 || rx > kMaxRadius || ry < 0 || ry > kMaxRadius) throw std::string("radii rx and ry must be in [0, 32]");
+    *n_out = 0;
+    if (t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    Prepared P;
+    prepare(fm, t, g, P);
+    std::vector<ExTmpl> act;
+    std::vector<int32_t> index;
+    active_templates(P, act, index);
+    if (act.empty()) return;
+    const int T = (int)act.size();
+    // Decision regions: the whole grid when one plane fits the map workspace, else rectangles whose planes with their
+    // halo do.  Each region's planes cover its points and every neighbour within the radii, so region, batch and tile
+    // edges never change a result.
+    const long long pts = (long long)(kPeakMapBytes / sizeof(float));
+    int DX = g.nx, DY = g.ny;
+    if ((long long)g.nx * g.ny > pts) {
+        DY = std::min(g.ny, 8192);
+        DX = (int)std::min<long long>(g.nx, pts / (DY + 2 * ry) - 2 * rx);
+    }
+    const long long plane_max = (long long)std::min(g.nx, DX + 2 * rx) * std::min(g.ny, DY + 2 * ry);
+    const int batch = (int)std::max<long long>(1, std::min<long long>({(long long)T, pts / plane_max, 65536}));
+    struct Region { int ia, ja, w, h, di0, di1, dj0, dj1; };  // its plane [ia, ia + w) x [ja, ja + h); decisions, plane coordinates
+    std::vector<Region> regions;
+    for (int rj = 0; rj < g.ny; rj += DY)
+        for (int ri = 0; ri < g.nx; ri += DX) {
+            const int ia = std::max(0, ri - rx), ib = std::min(g.nx - 1, ri + DX - 1 + rx);
+            const int ja = std::max(0, rj - ry), jb = std::min(g.ny - 1, rj + DY - 1 + ry);
+            regions.push_back(Region{ia, ja, ib - ia + 1, jb - ja + 1, ri - ia, std::min(g.nx - 1, ri + DX - 1) - ia, rj - ja,
+                                     std::min(g.ny - 1, rj + DY - 1) - ja});
         }
-    *out = m;
-    *n_out = n;
+    // per (batch, region) the batch's templates with their boxes in the region's plane coordinates, slot = place in the batch
+    std::vector<ExTmpl> tms;
+    std::vector<int> parts;  // workgroups per template of each (batch, region)
+    for (int b0 = 0; b0 < T; b0 += batch)
+        for (const Region& R : regions) {
+            int max_tiles = 0;
+            for (int q = b0; q < std::min(T, b0 + batch); ++q) {
+                ExTmpl e = act[(size_t)q];
+                const int i0 = std::max(e.i0, R.ia) - R.ia, i1 = std::min(e.i1, R.ia + R.w - 1) - R.ia;
+                const int j0 = std::max(e.j0, R.ja) - R.ja, j1 = std::min(e.j1, R.ja + R.h - 1) - R.ja;
+                e.slot = q - b0;
+                if (i0 <= i1 && j0 <= j1) {
+                    e.i0 = i0; e.i1 = i1; e.j0 = j0; e.j1 = j1;
+                    const int ci0 = std::max(i0, R.di0), ci1 = std::min(i1, R.di1), cj0 = std::max(j0, R.dj0), cj1 = std::min(j1, R.dj1);
+                    if (ci0 <= ci1 && cj0 <= cj1)
+                        max_tiles = std::max(max_tiles, ((ci1 - ci0) / kPkTX + 1) * ((cj1 - cj0) / kPkTY + 1));
+                } else {
+                    e.i0 = 0; e.i1 = -1; e.j0 = 0; e.j1 = -1;
+                }
+                tms.push_back(e);
+            }
+            const int nb = std::min(batch, T - b0);
+            parts.push_back(std::max(1, std::min(max_tiles, (kPeakWorkgroups + nb - 1) / nb)));
+        }
+    // workspace: lines | templates | maps (batch planes) | candidate lists | merged lists; bounded whatever T and the grid
+    const size_t cand_lists = (size_t)4 * (kPeakWorkgroups + batch) + batch;  // >= nb * (4 * parts + 1) of every launch
+    const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_map = o_tm + al256(tms.size() * sizeof(ExTmpl)),
+                 o_cand = o_map + al256((size_t)batch * plane_max * sizeof(float)), o_best = o_cand + al256(cand_lists * k * 8),
+                 total = o_best + al256((size_t)batch * k * 8);
+    fm->s_eval.reserve(total);
+    char* d = (char*)fm->s_eval.p;
+    hipStream_t st = fm->stream;
+    float* map = (float*)(d + o_map);
+    unsigned long long* cand = (unsigned long long*)(d + o_cand);
+    unsigned long long* d_best = (unsigned long long*)(d + o_best);
+    FDCM_HIP(hipMemcpyAsync(d + o_lines, P.lines.data(), P.lines.size() * sizeof(ExLine), hipMemcpyHostToDevice, st));
+    FDCM_HIP(hipMemcpyAsync(d + o_tm, tms.data(), tms.size() * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
+    std::vector<unsigned long long> best((size_t)T * k);
+    size_t at = 0;  // (batch, region) launches so far
+    for (int b0 = 0; b0 < T; b0 += batch) {
+        const int nb = std::min(batch, T - b0);
+        FDCM_HIP(hipMemsetAsync(d_best, 0xff, (size_t)nb * k * 8, st));  // kNoKey
+        for (const Region& R : regions) {
+            const ExTmpl* tm = (const ExTmpl*)(d + o_tm) + (size_t)b0 * regions.size() + (size_t)(&R - regions.data()) * nb;
+            const int G = parts[at++], n_lists = 4 * G + 1;
+            // the regions before this one: their merged lists go in as each template's last list
+            FDCM_HIP(hipMemcpy2DAsync(cand + (size_t)(n_lists - 1) * k, (size_t)n_lists * k * 8, d_best, (size_t)k * 8, (size_t)k * 8,
+                                      (size_t)nb, hipMemcpyDeviceToDevice, st));
+            const fdcm_grid rg{g.x0 + R.ia * g.sx, g.y0 + R.ja * g.sy, R.w, R.h, g.sx, g.sy};
+            launch<false>(fm, P, rg, (const ExLine*)(d + o_lines), tm, nb, 0, portions_for(fm, rg, nb), map, nullptr);
+            const dim3 grid((unsigned)(nb * G));
+            if (std::max(rx, ry) <= 8)
+                hipLaunchKernelGGL(k_exhaustive_peaks<8>, grid, dim3(256), 0, st, map, R.w, R.h, tm, G, rx, ry, R.di0, R.di1, R.dj0,
+                                   R.dj1, R.ia, R.ja, g.nx, k, n_lists, cand);
+            else
+                hipLaunchKernelGGL(k_exhaustive_peaks<kMaxRadius>, grid, dim3(256), 0, st, map, R.w, R.h, tm, G, rx, ry, R.di0, R.di1,
+                                   R.dj0, R.dj1, R.ia, R.ja, g.nx, k, n_lists, cand);
+            FDCM_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_exhaustive_merge, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, (const unsigned long long*)cand, nb,
+                               n_lists, k, d_best);
+            FDCM_HIP(hipGetLastError());
+        }
+        FDCM_HIP(hipMemcpyAsync(best.data() + (size_t)b0 * k, d_best, (size_t)nb * k * 8, hipMemcpyDeviceToHost, st));
+    }
+    FDCM_HIP(hipStreamSynchronize(st));  // (P and tms stay alive until here)
+    emit_records(best, k, index, g, base, out, n_out);
 }
 
 }  // namespace fdcm

@@ -213,6 +213,8 @@ void exhaustive_window(fdcm_featuremap* fm, const fdcm_templates* t, int32_t sx,
 void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, float* out_host, float* out_device);
 void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int32_t base,
                            fdcm_match** out, int64_t* n_out);
+void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int rx, int ry,
+                                 int32_t base, fdcm_match** out, int64_t* n_out);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

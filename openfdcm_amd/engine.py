@@ -158,6 +158,16 @@ class DeviceFeatureMap:
                                                      C.byref(out), C.byref(n)))
         return _adopt_matches(out, n.value)
 
+    def exhaustive_peaks(self, templates, grid, k=1, rx=0, ry=0, tmpl_index_base=0):
+        """Per template with lines: its k best peaks by (score, grid index), a peak being an admissible grid point whose key
+        is the minimum of its (2 rx + 1) x (2 ry + 1) window (0 <= rx, ry <= 32, grid steps), as raw match records
+        (capi.MATCH_DTYPE) with transform [1, 0, tx, 0, 1, ty].  rx = ry = 0 is exhaustive_search."""
+        g = as_grid(grid)
+        out, n = C.c_void_p(), C.c_int64()
+        capi.check(capi.lib().fdcm_search_exhaustive_peaks(self._h, templates._h, C.byref(g), int(k), int(rx), int(ry),
+                                                           int(tmpl_index_base), C.byref(out), C.byref(n)))
+        return _adopt_matches(out, n.value)
+
     def score_map(self, templates, grid):
         """(T, ny, nx) float32: the score of every template at every grid point, NaN where not admissible."""
         g = as_grid(grid)

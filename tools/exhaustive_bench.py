@@ -1,6 +1,7 @@
 """Times the exhaustive translation search (include/fdcm.h, "exhaustive translation search") on config 2': the feature map
 and the 1000 x 32-line synthetic templates bench.py uses, every template over its default window (exhaustive_window), at
-stride 1, 2 and 4 with k = 1 and 8.
+stride 1, 2 and 4 with k = 1 and 8, and the peaks (fdcm_search_exhaustive_peaks) at k = 8 with radii 1, 8 and 32 on the
+same grids, each beside the top-k call of the same k.
 
 For every case it prints the wall time of one blocking fdcm_search_exhaustive call (median of --reps after a warm-up),
 the admissible translations scored (the sum over templates of the window's points inside each template's admissible
@@ -8,7 +9,7 @@ box), and the lookup rate: 2 lookups per template line and admissible translatio
 evaluate<Dt3Cpu> (the reference's code, one host thread) on a random sample of admissible translations, the same
 lookups per translation.
 
-    python tools/exhaustive_bench.py [--reps 5] [--cpu-sample 20000] [--json out.json]
+    python tools/exhaustive_bench.py [--reps 5] [--cpu-sample 20000] [--radii 1,8,32] [--json out.json]
 """
 import argparse
 import json
@@ -47,6 +48,8 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=20000, help="translations the oracle scores on the host")
     ap.add_argument("--strides", default="1,2,4")
     ap.add_argument("--ks", default="1,8")
+    ap.add_argument("--radii", default="1,8,32", help="peak radii (rx = ry); empty: no peaks cases")
+    ap.add_argument("--peak-k", type=int, default=8)
     ap.add_argument("--json", default=None, help="also write the results here")
     args = ap.parse_args()
 
@@ -79,6 +82,28 @@ def main():
             print(f"stride {s} k {k}: grid {nx}x{ny}, {sum(adm)} admissible translations, {lookups:.3g} lookups, "
                   f"{ms:.2f} ms/call (min {min(times) * 1e3:.2f}), {lookups / (ms * 1e-3):.3g} lookups/s", flush=True)
 
+    def timed(call):
+        call()  # warm-up: workspaces, code objects
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            out = call()
+            times.append(time.perf_counter() - t0)
+        return float(np.median(times)) * 1e3, min(times) * 1e3, out
+
+    peaks = []
+    radii = [int(v) for v in args.radii.split(",") if v]
+    for s in [int(v) for v in args.strides.split(",")] if radii else []:
+        grid = dev.exhaustive_window(tset, s, s).as_tuple()
+        k = args.peak_k
+        top_ms, _, _ = timed(lambda: dev.exhaustive_search(tset, grid, k=k))
+        for r in radii:
+            ms, ms_min, recs = timed(lambda: dev.exhaustive_peaks(tset, grid, k=k, rx=r, ry=r))
+            peaks.append({"stride": s, "k": k, "r": r, "grid": list(grid), "ms_per_call": round(ms, 3), "ms_min": round(ms_min, 3),
+                          "topk_ms_per_call": round(top_ms, 3), "ratio_to_topk": round(ms / top_ms, 3), "records": int(len(recs))})
+            print(f"peaks stride {s} k {k} r {r}: {ms:.2f} ms/call (min {ms_min:.2f}), top-k {top_ms:.2f} ms: "
+                  f"{ms / top_ms:.2f}x, {len(recs)} records", flush=True)
+
     # the same work on the host: the oracle's evaluate (one thread) on random admissible translations of random templates
     orc = O.build(scene, depth=cfg["depth"], coeff=5.0, padding=1.0, distance=cfg["distance"], nthreads=16)
     rng = np.random.default_rng(7)
@@ -99,7 +124,7 @@ def main():
     for r in rows:
         r["speedup_vs_cpu_1thread"] = round(r["lookups_per_s"] / cpu["lookups_per_s"], 1)
     res = {"workload": "config 2': 1024x1024 scene (200 lines, seed 1), depth 30, L2, padding 1.0; 1000 templates x 32 lines "
-                       "(seed 2), default window per stride", "template_lines": n_lines, "gpu": rows, "cpu": cpu}
+                       "(seed 2), default window per stride", "template_lines": n_lines, "gpu": rows, "peaks": peaks, "cpu": cpu}
     print(json.dumps(res))
     if args.json:
         with open(args.json, "w") as f:
