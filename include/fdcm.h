@@ -331,6 +331,39 @@ int fdcm_score_map(const fdcm_featuremap* fm, const fdcm_templates* templates, c
 /* Same into device memory; returns when the map is complete (as fdcm_search_device). */
 int fdcm_score_map_device(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, float* out_device);
 
+/* Rotations: the exhaustive search as a dense pose search over (angle, x, y).  n >= 1 rotations (c, s), float32, no unit
+ * norm required (a scale is a rotation of norm != 1), cs holding n pairs; pivots: one (px, py) per template, or NULL for
+ * the origin.  The rotated template M_a(t) is rotate(lines, R, rot_point) (math.h:372-378) with R = [[c, -s], [s, c]]:
+ * M_a = [R | m], m.x = px - (c px + (-s) py), m.y = py - (s px + c py), and every end point (x, y) goes to
+ * ((c x + (-s) y) + m.x, (s x + c y) + m.y), each product and sum rounded to float32 left to right (no fused
+ * multiply-add).  score(t, a, g) is the score above of M_a(t) at grid point g, admissible by the rule above applied to
+ * M_a(t): every (t, a) has a box of its own.  Records are {t + tmpl_index_base, score, {c, -s, m.x + t.x, s, c,
+ * m.y + t.y}} (float32 adds; combine(translation, M_a), the DefaultMatch convention), taken by penalize, sort_matches and
+ * the device tail as the alignment search's.  All values c, s and pivots must be finite. */
+typedef struct fdcm_rotations {
+    const float* cs;
+    int32_t n;
+    const float* pivots;
+} fdcm_rotations;
+/* The smallest grid with strides (sx, sy) and x0, y0 multiples of them that holds every admissible integer translation of
+ * every (template with lines, rotation); nx = ny = 0 when there is none. */
+int fdcm_exhaustive_rotations_window(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                     int32_t sx, int32_t sy, fdcm_grid* grid);
+/* Peaks across rotations.  N = nx ny; key(t, a, g) = (score bits << 32) | (a N + g), a total order per template (score,
+ * then rotation index, then grid index); n N <= 2^32 is required.  For radii 0 <= rx, ry, ra <= 32 and wrap 0 or 1, the
+ * angle distance is d(a, a') = |a - a'|, or min(|a - a'|, n - |a - a'|) with wrap = 1.  An admissible (a, i, j) is a peak
+ * when its key is below the key of every other admissible (a', i', j') of the same template with |i' - i| <= rx,
+ * |j' - j| <= ry and d(a, a') <= ra.  Per template with lines, in ascending index: its peaks ordered by key, the first
+ * min(k, count) (1 <= k <= 64).  rx = ry = ra = 0 is the top-k over all (rotation, grid point) pairs; one rotation (1, 0)
+ * gives fdcm_search_exhaustive_peaks' records (transform entry 1 is -0).  Device memory stays below 1 GB whatever the
+ * number of templates and rotations and the grid.  Release with fdcm_matches_free. */
+int fdcm_search_exhaustive_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                     const fdcm_grid* grid, int32_t k, int32_t rx, int32_t ry, int32_t ra, int32_t wrap,
+                                     int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out);
+/* The score maps of every rotated template: out[t][a][j][i], NaN where not admissible (n_templates * n * ny * nx floats). */
+int fdcm_score_map_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                             const fdcm_grid* grid, float* out_host);
+
 /* ---- the reference's line files (.lines / .scene / .tmpl): read / write of core/serialization.h:99-132 (Python: openfdcm.read
  *      / openfdcm.write, python/src/core.cpp:41-42).  Host only.  fdcm_lines_read hands out n lines as 4 floats each
  *      (x1 y1 x2 y2 = the 4 x N column-major LineArray), to be released with fdcm_lines_free; a missing file, a file that is

@@ -504,4 +504,81 @@ def score_map(featuremap, templates, stride=1, window=None):
     return fm.score_map(tset, g), g
 
 
+
+# ---------------------------------------------------------------- exhaustive search over rotations (extension)
+def _angles(angles):
+    """(n, 2) float32 (c, s) of angles in radians: float32(cos(float64)), float32(sin(float64))."""
+    a = _np.asarray(angles, dtype=_np.float64).reshape(-1)
+    return _np.stack([_np.cos(a), _np.sin(a)], axis=1).astype(_np.float32)
+
+
+def _pivots(templates, pivot, T):
+    """pivot "center": per template the centre of its end points' bounding box in float32 ((0, 0) without lines); None:
+    the origin; a (T, 2) array as it is."""
+    if pivot is None:
+        return None
+    if isinstance(pivot, str):
+        if pivot != "center":
+            raise ValueError('pivot must be "center", None or a (T, 2) array')
+        out = _np.zeros((T, 2), dtype=_np.float32)
+        for t, tm in enumerate(templates):
+            a = _np.asarray(tm, dtype=_np.float32).reshape(4, -1)
+            if a.shape[1] == 0:
+                continue
+            xs, ys = _np.concatenate([a[0], a[2]]), _np.concatenate([a[1], a[3]])
+            out[t, 0] = (xs.min() + xs.max()) / _np.float32(2)
+            out[t, 1] = (ys.min() + ys.max()) / _np.float32(2)
+        return out
+    pv = _np.ascontiguousarray(pivot, dtype=_np.float32)
+    if pv.shape != (T, 2):
+        raise ValueError("pivot array must be (T, 2)")
+    return pv
+
+
+def _rotation_args(featuremap, templates, angles, pivot):
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates)
+    return fm, tset, _angles(angles), _pivots(templates, pivot, tset.count)
+
+
+def _rotation_window(fm, tset, cs, pv, stride, window):
+    if window is not None:
+        return tuple(int(v) for v in window)
+    sx, sy = _strides(stride)
+    return fm.exhaustive_rotations_window(tset, cs, pv, sx, sy).as_tuple()
+
+
+def rotation_window(featuremap, templates, angles, stride=1, pivot="center"):
+    """The default window of exhaustive_rotation_search / rotation_score_map: the smallest grid with the given stride,
+    origin a multiple of it, that holds every admissible integer translation of every template with lines under every
+    rotation.  Returns (x0, y0, nx, ny, sx, sy); nx = ny = 0 when none fits anywhere."""
+    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot)
+    sx, sy = _strides(stride)
+    return fm.exhaustive_rotations_window(tset, cs, pv, sx, sy).as_tuple()
+
+
+def exhaustive_rotation_search(featuremap, templates, angles, stride=1, k=1, radius=0, angle_radius=0, wrap=False,
+                               pivot="center", window=None):
+    """exhaustive_peaks over rotations: every template rotated by every angle (radians) about its pivot ("center": its
+    bounding box centre, None: the origin, or a (T, 2) array) and scored at every translation of the grid.  Per template
+    its k best peaks over (angle, x, y), ordered by (score, angle index, grid index); a peak is the smallest within
+    radius = r or (rx, ry) grid steps and angle_radius angle steps (0 to 32 each), circular over the angle list with
+    wrap.  Radii 0 give the top-k over all poses.  Returns a MatchList whose transforms are [R | m + t], ready for
+    penalize / sort_matches."""
+    rx, ry = _strides(radius)
+    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot)
+    g = _rotation_window(fm, tset, cs, pv, stride, window)
+    if g[2] == 0 or g[3] == 0:
+        return MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
+    return MatchList(fm.exhaustive_rotation_search(tset, g, cs, pv, k=k, rx=rx, ry=ry, ra=int(angle_radius), wrap=wrap))
+
+
+def rotation_score_map(featuremap, templates, angles, stride=1, pivot="center", window=None):
+    """The dense score maps of the rotated templates: (float32 array [T, A, ny, nx], NaN where not admissible; grid)."""
+    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot)
+    g = _rotation_window(fm, tset, cs, pv, stride, window)
+    if g[2] == 0 or g[3] == 0:
+        return _np.zeros((tset.count, cs.shape[0], g[3], g[2]), dtype=_np.float32), g
+    return fm.rotation_score_map(tset, g, cs, pv), g
+
 from .lineio import read, write  # noqa: E402  (.lines/.scene/.tmpl files, serialization.h)

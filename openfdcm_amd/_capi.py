@@ -51,6 +51,11 @@ class Grid(C.Structure):
         return "Grid(x0={}, y0={}, nx={}, ny={}, sx={}, sy={})".format(*self.as_tuple())
 
 
+class Rotations(C.Structure):
+    """fdcm_rotations: n pairs (c, s) at cs, and one pivot (px, py) per template at pivots or NULL (the origin)."""
+    _fields_ = [("cs", C.POINTER(C.c_float)), ("n", C.c_int32), ("pivots", C.POINTER(C.c_float))]
+
+
 # every symbol include/fdcm.h declares: (name, restype, argtypes)
 _fp, _i64p, _vp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_void_p
 SYMBOLS = [
@@ -118,6 +123,10 @@ SYMBOLS = [
     ("fdcm_search_exhaustive_peaks", C.c_int, [_vp, _vp, C.POINTER(Grid), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.POINTER(_vp), _i64p]),
     ("fdcm_score_map", C.c_int, [_vp, _vp, C.POINTER(Grid), _fp]),
+    ("fdcm_exhaustive_rotations_window", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.c_int32, C.c_int32, C.POINTER(Grid)]),
+    ("fdcm_search_exhaustive_rotations", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int32, C.c_int32,
+                                                  C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp), _i64p]),
+    ("fdcm_score_map_rotations", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), _fp]),
     ("fdcm_score_map_device", C.c_int, [_vp, _vp, C.POINTER(Grid), _vp]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),

@@ -516,6 +516,70 @@ int fdcm_search_exhaustive_peaks(const fdcm_featuremap* fm, const fdcm_templates
     });
 }
 
+// Rotations: include/fdcm.h, "Rotations".  The rotations are checked before the handles; the pivots, whose count is the
+// templates', after the null checks (they read no device state).
+static void check_rotations(const fdcm_rotations* rot) {
+    require(rot != nullptr, "rotations is null");
+    require(rot->n >= 1, "rotations: n must be >= 1");
+    require(rot->cs != nullptr, "rotations: cs is null");
+    for (int32_t a = 0; a < rot->n; ++a)
+        require(std::isfinite(rot->cs[2 * a]) && std::isfinite(rot->cs[2 * a + 1]), "rotations: c and s must be finite");
+}
+static void check_pivots(const fdcm_templates* t, const fdcm_rotations* rot) {
+    if (rot->pivots)
+        for (int64_t i = 0; i < 2 * t->T; ++i) require(std::isfinite(rot->pivots[i]), "rotations: pivots must be finite");
+}
+
+int fdcm_exhaustive_rotations_window(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                     int32_t sx, int32_t sy, fdcm_grid* grid) {
+    return guarded([&] {
+        require(sx >= 1 && sy >= 1, "strides sx and sy must be >= 1");
+        check_rotations(rot);
+        require(fm && templates && grid, "null featuremap/templates/grid");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_pivots(templates, rot);
+        exhaustive_rotations_window(const_cast<fdcm_featuremap*>(fm), templates, *rot, sx, sy, grid);
+    });
+}
+
+int fdcm_search_exhaustive_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                     const fdcm_grid* grid, int32_t k, int32_t rx, int32_t ry, int32_t ra, int32_t wrap,
+                                     int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out) {
+    return guarded([&] {
+        require(k >= 1 && k <= 64, "k must be in [1, 64]");
+        require(rx >= 0 && rx <= 32 && ry >= 0 && ry <= 32 && ra >= 0 && ra <= 32, "radii rx, ry and ra must be in [0, 32]");
+        require(wrap == 0 || wrap == 1, "wrap must be 0 or 1");
+        require(grid != nullptr, "grid is null");
+        check_rotations(rot);
+        require((uint64_t)rot->n * (uint64_t)std::max(0, grid->nx) * (uint64_t)std::max(0, grid->ny) <= ((uint64_t)1 << 32),
+                "n_rot * nx * ny must be at most 2^32");
+        check_exhaustive_args(fm, templates, grid);
+        require(out && n_out, "null output");
+        check_pivots(templates, rot);
+        *out = nullptr;
+        try {
+            run_search_exhaustive_rotations(const_cast<fdcm_featuremap*>(fm), templates, *rot, *grid, k, rx, ry, ra, wrap,
+                                            tmpl_index_base, out, n_out);
+        } catch (...) {
+            result_release(*out);
+            *out = nullptr;
+            throw;
+        }
+        if (!*out) *out = result_acquire(sizeof(fdcm_match));  // no records: an empty (non-null) array
+    });
+}
+
+int fdcm_score_map_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                             const fdcm_grid* grid, float* out_host) {
+    return guarded([&] {
+        check_rotations(rot);
+        check_exhaustive_args(fm, templates, grid);
+        check_pivots(templates, rot);
+        require(out_host != nullptr || templates->T == 0, "out_host is null");
+        run_score_map_rotations(const_cast<fdcm_featuremap*>(fm), templates, *rot, *grid, out_host);
+    });
+}
+
 int fdcm_score_map(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_grid* grid, float* out_host) {
     return guarded([&] {
         check_exhaustive_args(fm, templates, grid);

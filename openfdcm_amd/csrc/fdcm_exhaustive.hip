@@ -9,12 +9,15 @@
 //   k_exhaustive_merge         one wave per template merges the per-wave lists into the template's k best
 //   k_exhaustive_peaks<R>      peaks: reads the score planes k_exhaustive<., false> wrote and offers every point whose
 //                              key is the minimum of its (2rx+1) x (2ry+1) window to a per-wave k-best list
+//   k_exhaustive_peaks3<R>     peaks across rotations: the same over (angle, row, column), keys (bits, a N + g)
+//   k_exhaustive_merge_groups  one wave per template of a batch: its merged list so far and its units' lists
 //
 // Keys of the top-k are (score bits << 32) | grid index: scores are >= +0, so the key order is the (score, g) order,
 // which is total -- the result does not depend on which wave saw which point first.  No atomics.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <thread>
 
 #include "fdcm_internal.h"
 #include "fdcm_score.h"
@@ -37,7 +40,8 @@ struct ExLine {  // one template line: end points, and the line's slice (bin * f
 struct ExTmpl {    // one template of a launch
     int line0, n;  // its lines in the line array
     int i0, i1, j0, j1;  // grid indices of its admissible translations: [i0, i1] x [j0, j1] (empty when i0 > i1 or j0 > j1)
-    int slot, pad;       // where its output goes: map plane / candidate lists / merged list
+    int slot;            // where its output goes: map plane / candidate lists / merged list
+    unsigned koff;       // added to the grid index of its top-k keys (a rotation's a * nx * ny; 0 otherwise)
 };
 
 // One read of the interleaved volume (ivol_index) at column x, row y of the line's slice.  xw: the column's part of the
@@ -216,7 +220,8 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
                 bool any = false;
 #pragma unroll
                 for (int r = 0; r < kRows; ++r) {
-                    key[r] = act[r] ? ((unsigned long long)__float_as_uint(res[r]) << 32) | (unsigned)((jb + 16 * r) * nx + i)
+                    key[r] = act[r] ? ((unsigned long long)__float_as_uint(res[r]) << 32) |
+                                          ((unsigned)((jb + 16 * r) * nx + i) + P.koff)
                                     : kNoKey;
                     any = any || key[r] < thr;
                 }
@@ -327,6 +332,105 @@ __global__ void __launch_bounds__(256) k_exhaustive_peaks(const float* __restric
     }
     // candidate lists: [q][part * 4 + wave][k] of n_lists per template (the last list is the caller's)
     if (lane < k) cand[((long long)q * n_lists + part * 4 + wave) * k + lane] = e;
+}
+
+// Peaks across rotations (include/fdcm.h, "Rotations"): keys (score bits << 32) | (a * N + g) over (angle, row, column),
+// the window a box of (2ra+1) x (2ry+1) x (2rx+1), so its minimum is separable: angle first, then rows, then columns.
+// A workgroup takes tiles of one decided (template, angle) unit and loads each tile with its rx / ry halo into LDS,
+// already reduced over the angle window: per halo point the smallest key over the planes of the angles a - ra .. a + ra
+// (circular when wrap is set; angles outside [0, n_rot) otherwise ignored), kNoKey where none is admissible (NaN).  The
+// row and column passes are k_exhaustive_peaks', on 64-bit keys; the point is a peak when the window minimum is its own
+// key.  The planes of a group (one template's angles lo, lo + 1, ... of the batch, mod n_rot) are consecutive: the plane
+// of angle a' is D.x + ((a' - lo) mod n_rot).  LDS: 8 (kH kW + kH kPkTX) bytes, 54 KiB for R = 8 and 144 KiB for R = 32.
+template <int R>
+__global__ void __launch_bounds__(256) k_exhaustive_peaks3(const float* __restrict__ map, int w, int h, const ExTmpl* __restrict__ pl,
+                                                           const int4* __restrict__ dec, int parts, int rx, int ry, int ra, int n_rot,
+                                                           int wrap, int di0, int di1, int dj0, int dj1, int ia, int ja, int nx,
+                                                           unsigned N, int k, unsigned long long* __restrict__ cand) {
+    constexpr int kW = kPkTX + 2 * R, kH = kPkTY + 2 * R;
+    __shared__ unsigned long long S[kH * kW];     // angle-window minimum keys of the tile and its halo
+    __shared__ unsigned long long B[kH * kPkTX];  // then the row-window minimum
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int u = (int)blockIdx.x / parts, part = (int)blockIdx.x % parts;
+    const int4 D = dec[u];  // x: the group's first plane, y: its first angle lo, z: its planes, w: the unit's angle
+    const long long wh = (long long)w * h;
+    auto plane_of = [&](int a2) {
+        const int o = a2 - D.y;
+        return D.x + (o < 0 ? o + n_rot : o);
+    };
+    const ExTmpl P = pl[plane_of(D.w)];
+    const float* own = map + (long long)P.slot * wh;
+    const unsigned akey = (unsigned)D.w * N;
+    const int W2 = kPkTX + 2 * rx, H2 = kPkTY + 2 * ry;
+    const int bi0 = max(P.i0, di0), bi1 = min(P.i1, di1), bj0 = max(P.j0, dj0), bj1 = min(P.j1, dj1);
+    const int ntx = bi0 <= bi1 ? (bi1 - bi0) / kPkTX + 1 : 0, nty = bj0 <= bj1 ? (bj1 - bj0) / kPkTY + 1 : 0;
+    unsigned long long e = kNoKey, thr = kNoKey;
+    for (int tile = part; tile < ntx * nty; tile += parts) {  // workgroup-uniform
+        const int li0 = bi0 + (tile % ntx) * kPkTX, lj0 = bj0 + (tile / ntx) * kPkTY;
+        for (int idx = threadIdx.x; idx < H2 * W2; idx += 256) {
+            const int hr = idx / W2, hc = idx - hr * W2;
+            const int li = li0 - rx + hc, lj = lj0 - ry + hr;
+            unsigned long long v = kNoKey;
+            if (li >= 0 && li < w && lj >= 0 && lj < h) {  // every plane of the launch covers the region's plane
+                const unsigned g = (unsigned)(ja + lj) * (unsigned)nx + (unsigned)(ia + li);
+                const long long off = (long long)lj * w + li;
+                for (int d = -ra; d <= ra; ++d) {
+                    int a2 = D.w + d;
+                    if (a2 < 0 || a2 >= n_rot) {
+                        if (!wrap) continue;
+                        a2 = (a2 % n_rot + n_rot) % n_rot;
+                    }
+                    const float s = map[(long long)plane_of(a2) * wh + off];
+                    if (!(s != s)) v = min(v, ((unsigned long long)__float_as_uint(s) << 32) | ((unsigned)a2 * N + g));
+                }
+            }
+            S[hr * kW + hc] = v;
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < H2 * kPkTX; idx += 256) {
+            const int hr = idx / kPkTX, c = idx % kPkTX;
+            const unsigned long long* row = S + hr * kW + c;
+            unsigned long long best = row[0];
+            for (int d = 1; d <= 2 * rx; ++d) best = min(best, row[d]);
+            B[hr * kPkTX + c] = best;
+        }
+        __syncthreads();
+        for (int r = wave; r < kPkTY; r += 4) {  // wave-uniform: every lane takes part in list_offer
+            const int li = li0 + lane, lj = lj0 + r;
+            unsigned long long m = kNoKey;
+            for (int d = 0; d <= 2 * ry; ++d) m = min(m, B[(r + d) * kPkTX + lane]);
+            unsigned long long key = kNoKey;
+            if (li <= bi1 && lj <= bj1) {
+                const float s = own[(long long)lj * w + li];
+                if (!(s != s)) {
+                    const unsigned long long k3 = ((unsigned long long)__float_as_uint(s) << 32) |
+                                                  (akey + (unsigned)(ja + lj) * (unsigned)nx + (unsigned)(ia + li));
+                    if (k3 == m) key = k3;
+                }
+            }
+            thr = list_offer(e, key, thr, k, lane);
+        }
+        __syncthreads();  // the next tile overwrites S and B
+    }
+    // candidate lists: [u][part * 4 + wave][k], 4 * parts per unit
+    if (lane < k) cand[((long long)u * 4 * parts + part * 4 + wave) * k + lane] = e;
+}
+
+// One wave per group (one template's units of a batch): its merged list so far best[q] and the group's units * lpu
+// candidate lists, from list unit0 * lpu on, folded into best[q].  seg: x unit0, y units, z q.
+__global__ void __launch_bounds__(256) k_exhaustive_merge_groups(const unsigned long long* __restrict__ cand, const int4* __restrict__ seg,
+                                                                 int n_groups, int lpu, int k, unsigned long long* __restrict__ best) {
+    const int lane = threadIdx.x & 63;
+    const int gi = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gi >= n_groups) return;  // wave-uniform
+    const int4 G = seg[gi];
+    unsigned long long* b = best + (long long)G.z * k;
+    unsigned long long e = kNoKey, thr = kNoKey;
+    thr = list_offer(e, lane < k ? b[lane] : kNoKey, thr, k, lane);
+    const unsigned long long* c = cand + (long long)G.x * lpu * k;
+    const long long n_lists = (long long)G.y * lpu;
+    for (long long q = 0; q < n_lists; ++q) thr = list_offer(e, lane < k ? c[q * k + lane] : kNoKey, thr, k, lane);
+    if (lane < k) b[lane] = e;
 }
 
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
@@ -496,6 +600,135 @@ void emit_records(const std::vector<unsigned long long>& best, int k, const std:
     *out = m;
     *n_out = n;
 }
+
+// ---- rotations (include/fdcm.h, "Rotations")
+// M_a = [R | m] of rotate(lines, R, rot_point), math.h:372-378, with R = [[c, -s], [s, c]] and m = p - R p: every product
+// and sum rounded to float32, left to right (the Makefile's -ffp-contract=off keeps them unfused on the host too).
+struct RotM { float c, ns, s, mx, my; };
+
+RotM rot_matrix(float c, float s, float px, float py) {
+    const float ns = -s;
+    return RotM{c, ns, s, px - (c * px + ns * py), py - (s * px + c * py)};
+}
+
+// The line sets M_a(t) of the templates [t0, t1) of t under every rotation, as one template set: (t, a) is its template
+// (t - t0) * n + a.  M: the transform of each.
+void rotated_set(const fdcm_templates* t, const fdcm_rotations& rot, int64_t t0, int64_t t1, fdcm_templates& out, RotM* M) {
+    const int n = rot.n;
+    out.device = t->device;
+    out.T = (t1 - t0) * n;
+    out.n_lines = (t->offsets[(size_t)t1] - t->offsets[(size_t)t0]) * n;
+    out.lines.resize((size_t)out.n_lines * 4);
+    out.offsets.assign((size_t)out.T + 1, 0);
+    int64_t w = 0;
+    for (int64_t i = t0; i < t1; ++i) {
+        const int64_t l0 = t->offsets[(size_t)i], l1 = t->offsets[(size_t)i + 1];
+        const float px = rot.pivots ? rot.pivots[2 * i] : 0.f, py = rot.pivots ? rot.pivots[2 * i + 1] : 0.f;
+        for (int a = 0; a < n; ++a) {
+            const RotM m = rot_matrix(rot.cs[2 * a], rot.cs[2 * a + 1], px, py);
+            M[(i - t0) * n + a] = m;
+            for (int64_t q = l0; q < l1; ++q, ++w) {
+                const float* p = &t->lines[(size_t)q * 4];
+                float* o = &out.lines[(size_t)w * 4];
+                for (int c = 0; c < 2; ++c) {  // transform, math.h:341-344
+                    const float x = p[2 * c], y = p[2 * c + 1];
+                    o[2 * c] = (m.c * x + m.ns * y) + m.mx;
+                    o[2 * c + 1] = (m.s * x + m.c * y) + m.my;
+                }
+            }
+            out.offsets[(size_t)((i - t0) * n + a) + 1] = w;
+        }
+    }
+}
+
+void check_rotated_size(const fdcm_templates* t, int n) {
+    if (t->T * (int64_t)n > 0x7fffffffll || t->n_lines * (int64_t)n > 0x7fffffffll)
+        throw std::string("too many rotated templates or template lines for one call");
+}
+
+// prepare() of the rotated set of all templates: P.tm[t * n + a] is (t, a), M its transforms.  The rotation, bins (host
+// atan) and admissible boxes run in up to 16 threads over ranges of templates, each of about 2^12 rotated lines or more.
+void prepare_rotated(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g, Prepared& P,
+                     std::vector<RotM>& M) {
+    const int n = rot.n;
+    check_rotated_size(t, n);
+    M.resize((size_t)(t->T * n));
+    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({16, t->T, (t->n_lines * n) >> 12}));
+    std::vector<int64_t> cut((size_t)nth + 1);
+    for (int c = 0; c <= nth; ++c) cut[(size_t)c] = t->T * c / nth;
+    std::vector<Prepared> part((size_t)nth);
+    std::vector<std::string> err((size_t)nth);
+    auto job = [&](int c) {
+        try {
+            fdcm_templates rt;
+            rotated_set(t, rot, cut[(size_t)c], cut[(size_t)c + 1], rt, M.data() + cut[(size_t)c] * n);
+            prepare(fm, &rt, g, part[(size_t)c]);
+        } catch (const std::string& e) {
+            err[(size_t)c] = e;
+        } catch (...) {
+            err[(size_t)c] = "host preparation of the rotated templates failed";
+        }
+    };
+    if (nth == 1) {
+        job(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (int c = 0; c < nth; ++c) pool.emplace_back(job, c);
+        for (std::thread& th : pool) th.join();
+    }
+    for (const std::string& e : err)
+        if (!e.empty()) throw e;
+    P.SL = part[0].SL;
+    P.buf32 = part[0].buf32;
+    P.lines.clear();
+    P.lines.reserve((size_t)std::max<int64_t>(1, t->n_lines * n));
+    P.tm.clear();
+    P.tm.reserve((size_t)(t->T * n));
+    for (int c = 0; c < nth; ++c) {
+        const int line0 = (int)P.lines.size(), slot0 = (int)(cut[(size_t)c] * n);
+        for (ExTmpl e : part[(size_t)c].tm) {
+            e.line0 += line0;
+            e.slot += slot0;
+            P.tm.push_back(e);
+        }
+        const size_t nl = (size_t)((t->offsets[(size_t)cut[(size_t)c + 1]] - t->offsets[(size_t)cut[(size_t)c]]) * n);
+        P.lines.insert(P.lines.end(), part[(size_t)c].lines.begin(), part[(size_t)c].lines.begin() + nl);
+    }
+    if (P.lines.empty()) P.lines.resize(1);
+}
+
+// The records of the merged lists best[q][k] of the templates index[q]: key a * N + g -> transform [R | m + (tx, ty)].
+void emit_rotation_records(const std::vector<unsigned long long>& best, int k, const std::vector<int32_t>& index,
+                           const std::vector<RotM>& M, int n, const fdcm_grid& g, int32_t base, fdcm_match** out, int64_t* n_out) {
+    const int T = (int)index.size();
+    const unsigned long long N = (unsigned long long)g.nx * g.ny;
+    int64_t cnt = 0;
+    for (unsigned long long v : best) cnt += v != kNoKey;
+    fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, cnt) * sizeof(fdcm_match));
+    int64_t w = 0;
+    for (int q = 0; q < T; ++q)
+        for (int r = 0; r < k; ++r) {
+            const unsigned long long v = best[(size_t)q * k + r];
+            if (v == kNoKey) break;
+            const unsigned long long low = v & 0xffffffffull;
+            const int a = (int)(low / N);
+            const unsigned gi = (unsigned)(low % N);
+            const int i = (int)(gi % (unsigned)g.nx), j = (int)(gi / (unsigned)g.nx);
+            const RotM& R = M[(size_t)index[(size_t)q] * n + a];
+            fdcm_match& rec = m[w++];
+            rec.tmpl_idx = base + index[(size_t)q];
+            rec.score = f_from_bits((uint32_t)(v >> 32));
+            // combine(translation, M_a), float32 adds
+            rec.transform[0] = R.c; rec.transform[1] = R.ns; rec.transform[2] = R.mx + (float)(g.x0 + i * g.sx);
+            rec.transform[3] = R.s; rec.transform[4] = R.c; rec.transform[5] = R.my + (float)(g.y0 + j * g.sy);
+        }
+    *out = m;
+    *n_out = cnt;
+}
+
+constexpr size_t kRotMapBytes = (size_t)512 << 20;   // the score planes of one batch of the rotation search
+constexpr size_t kRotLineBytes = (size_t)64 << 20;   // the rotated lines of one batch
+constexpr size_t kRotCandBytes = (size_t)128 << 20;  // the top-k candidate lists of one batch
 
 }  // namespace
 
@@ -691,6 +924,245 @@ void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, c
     }
     FDCM_HIP(hipStreamSynchronize(st));  // (P and tms stay alive until here)
     emit_records(best, k, index, g, base, out, n_out);
+}
+
+void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, int32_t sx, int32_t sy,
+                                 fdcm_grid* out) {
+    if (sx < 1 || sy < 1) throw std::string("strides sx and sy must be >= 1");
+    check_rotated_size(t, rot.n);
+    fdcm_templates rt;
+    std::vector<RotM> M((size_t)(t->T * rot.n));
+    rotated_set(t, rot, 0, t->T, rt, M.data());
+    exhaustive_window(fm, &rt, sx, sy, out);
+}
+
+void run_score_map_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
+                             float* out_host) {
+    check_grid(g);
+    check_rotated_size(t, rot.n);
+    fdcm_templates rt;
+    std::vector<RotM> M((size_t)(t->T * rot.n));
+    rotated_set(t, rot, 0, t->T, rt, M.data());
+    run_score_map(fm, &rt, g, out_host, nullptr);  // [t][a][ny][nx]: (t, a) is template t * n_rot + a
+}
+
+void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
+                                     int k, int rx, int ry, int ra, int wrap, int32_t base, fdcm_match** out, int64_t* n_out) {
+    check_grid(g);
+    if (k < 1 || k > kMaxK) throw std::string("k must be in [1, 64]");
+    if (rx < 0 || rx > kMaxRadius || ry < 0 || ry > kMaxRadius || ra < 0 || ra > kMaxRadius)
+        throw std::string("radii rx, ry and ra must be in [0, 32]");
+    if (wrap != 0 && wrap != 1) throw std::string("wrap must be 0 or 1");
+    const int n = rot.n;
+    if (n < 1) throw std::string("rotations: n must be >= 1");
+    const unsigned long long N = (unsigned long long)g.nx * g.ny;
+    if ((unsigned long long)n * N > (1ull << 32)) throw std::string("n_rot * nx * ny must be at most 2^32");
+    *n_out = 0;
+    if (t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    Prepared P;
+    std::vector<RotM> M;
+    prepare_rotated(fm, t, rot, g, P, M);
+    // the templates that can emit: lines, and an admissible grid point under some rotation
+    std::vector<int32_t> index;
+    for (int64_t i = 0; i < t->T; ++i) {
+        if (t->offsets[(size_t)i + 1] == t->offsets[(size_t)i]) continue;
+        for (int a = 0; a < n; ++a) {
+            const ExTmpl& e = P.tm[(size_t)(i * n + a)];
+            if (e.i0 <= e.i1 && e.j0 <= e.j1) { index.push_back((int32_t)i); break; }
+        }
+    }
+    if (index.empty()) return;
+    const int TA = (int)index.size();
+    const bool topk = rx == 0 && ry == 0 && ra == 0;  // every point is a peak: the fused top-k, no planes written
+
+    // Regions (peaks only): the whole grid when a batch of min(n, 2ra + 1) planes -- one decided angle and its angle
+    // halo -- fits the map workspace, else rectangles whose planes with their rx / ry halo do.
+    const long long pts = (long long)(kRotMapBytes / sizeof(float));
+    const int need = std::min(n, 2 * ra + 1);
+    int DX = g.nx, DY = g.ny;
+    if (!topk && (long long)g.nx * g.ny * need > pts) {
+        DY = std::min(g.ny, 2048);
+        DX = (int)std::max<long long>(1, std::min<long long>(g.nx, pts / need / (DY + 2 * ry) - 2 * rx));
+    }
+    struct Region { int ia, ja, w, h, di0, di1, dj0, dj1; };
+    std::vector<Region> regions;
+    if (topk) {
+        regions.push_back(Region{0, 0, g.nx, g.ny, 0, g.nx - 1, 0, g.ny - 1});
+    } else {
+        for (int rj = 0; rj < g.ny; rj += DY)
+            for (int ri = 0; ri < g.nx; ri += DX) {
+                const int ia = std::max(0, ri - rx), ib = std::min(g.nx - 1, ri + DX - 1 + rx);
+                const int ja = std::max(0, rj - ry), jb = std::min(g.ny - 1, rj + DY - 1 + ry);
+                regions.push_back(Region{ia, ja, ib - ia + 1, jb - ja + 1, ri - ia, std::min(g.nx - 1, ri + DX - 1) - ia, rj - ja,
+                                         std::min(g.ny - 1, rj + DY - 1) - ja});
+            }
+    }
+    long long plane_max = 0;
+    for (const Region& R : regions) plane_max = std::max(plane_max, (long long)R.w * R.h);
+    // planes per batch: the map workspace (peaks) or the candidate lists, (8 units + 8192) * 4 lists of k keys at most (top-k)
+    int cap;
+    if (topk)
+        cap = (int)std::max<long long>(1, std::min<long long>(65536, ((long long)(kRotCandBytes / (32ull * k)) - 8192) / 8));
+    else
+        cap = (int)std::max<long long>(need, std::min<long long>(65536, pts / plane_max));
+
+    // Batches: groups (one template's decided angles [a0, a1) and the planes of their angle halo, lo, lo + 1, ... mod n)
+    // filled in template order; a template's angles are cut across batches when they do not fit.
+    struct Group { int q, a0, a1, lo, np, plane0, unit0; };
+    struct Batch { size_t g0, g1; int planes, units; int64_t lines; };
+    auto n_planes = [&](int a0, int a1) { return wrap ? std::min(n, a1 - a0 + 2 * ra) : std::min(n, a1 + ra) - std::max(0, a0 - ra); };
+    const int64_t line_cap = (int64_t)(kRotLineBytes / sizeof(ExLine));
+    std::vector<Group> groups;
+    std::vector<Batch> batches;
+    Batch cur{0, 0, 0, 0, 0};
+    for (int q = 0; q < TA; ++q) {
+        const int64_t Lq = t->offsets[(size_t)index[(size_t)q] + 1] - t->offsets[(size_t)index[(size_t)q]];
+        int a0 = 0;
+        while (a0 < n) {
+            const int64_t room = std::max<int64_t>(0, std::min<int64_t>(cap - cur.planes, (line_cap - cur.lines) / Lq));
+            int a1 = (int)std::min<int64_t>(n, a0 + room);
+            while (a1 > a0 && n_planes(a0, a1) > room) --a1;
+            if (a1 == a0) {
+                if (cur.planes > 0) {
+                    cur.g1 = groups.size();
+                    batches.push_back(cur);
+                    cur = Batch{groups.size(), 0, 0, 0, 0};
+                    continue;
+                }
+                a1 = a0 + 1;  // one angle whose planes alone pass the line budget: a batch of its own
+            }
+            const int np = n_planes(a0, a1);
+            const int lo = wrap ? (np == n ? 0 : ((a0 - ra) % n + n) % n) : std::max(0, a0 - ra);
+            groups.push_back(Group{q, a0, a1, lo, np, cur.planes, cur.units});
+            cur.planes += np;
+            cur.units += a1 - a0;
+            cur.lines += np * Lq;
+            a0 = a1;
+        }
+    }
+    if (cur.planes > 0) {
+        cur.g1 = groups.size();
+        batches.push_back(cur);
+    }
+
+    // Host arrays of every batch: its lines, per region its planes (boxes in the region's plane coordinates, slot = the
+    // plane's place in the batch, koff = a * N), its decided units and its groups.
+    std::vector<ExLine> blines;
+    std::vector<size_t> bl0(batches.size() + 1, 0), bt0(batches.size() + 1, 0), bd0(batches.size() + 1, 0), bs0(batches.size() + 1, 0);
+    std::vector<ExTmpl> btm;
+    std::vector<int4> bdec, bseg;
+    std::vector<int> parts;  // workgroups per unit of each (batch, region)
+    size_t max_lines = 1, max_planes = 1, max_units = 1, max_groups = 1, max_cand = 1;
+    for (size_t b = 0; b < batches.size(); ++b) {
+        const Batch& B = batches[b];
+        std::vector<ExTmpl> planes;  // full-grid boxes, line0 in the batch
+        for (size_t gi = B.g0; gi < B.g1; ++gi) {
+            const Group& G = groups[gi];
+            const int64_t ti = index[(size_t)G.q];
+            for (int p = 0; p < G.np; ++p) {
+                const int a2 = (G.lo + p) % n;
+                ExTmpl e = P.tm[(size_t)(ti * n + a2)];
+                const size_t l0 = blines.size() - bl0[b];
+                blines.insert(blines.end(), P.lines.begin() + e.line0, P.lines.begin() + e.line0 + e.n);
+                e.line0 = (int)l0;
+                e.slot = G.plane0 + p;
+                e.koff = (unsigned)((unsigned long long)a2 * N);
+                planes.push_back(e);
+            }
+            bseg.push_back(make_int4(G.unit0, G.a1 - G.a0, G.q, 0));
+            for (int a = G.a0; a < G.a1; ++a) bdec.push_back(make_int4(G.plane0, G.lo, G.np, a));
+        }
+        for (const Region& R : regions) {
+            int max_tiles = 0;
+            for (ExTmpl e : planes) {
+                if (!topk) {
+                    const int i0 = std::max(e.i0, R.ia) - R.ia, i1 = std::min(e.i1, R.ia + R.w - 1) - R.ia;
+                    const int j0 = std::max(e.j0, R.ja) - R.ja, j1 = std::min(e.j1, R.ja + R.h - 1) - R.ja;
+                    if (i0 <= i1 && j0 <= j1) {
+                        e.i0 = i0; e.i1 = i1; e.j0 = j0; e.j1 = j1;
+                        const int ci0 = std::max(i0, R.di0), ci1 = std::min(i1, R.di1), cj0 = std::max(j0, R.dj0),
+                                  cj1 = std::min(j1, R.dj1);
+                        if (ci0 <= ci1 && cj0 <= cj1)
+                            max_tiles = std::max(max_tiles, ((ci1 - ci0) / kPkTX + 1) * ((cj1 - cj0) / kPkTY + 1));
+                    } else {
+                        e.i0 = 0; e.i1 = -1; e.j0 = 0; e.j1 = -1;
+                    }
+                }
+                btm.push_back(e);
+            }
+            parts.push_back(topk ? 4 * portions_for(fm, g, B.planes)  // lists per unit
+                                 : std::max(1, std::min(max_tiles, (kPeakWorkgroups + B.units - 1) / B.units)));
+            max_cand = std::max(max_cand, (size_t)B.units * (topk ? parts.back() : 4 * parts.back()));
+        }
+        bl0[b + 1] = blines.size();
+        bt0[b + 1] = btm.size();
+        bd0[b + 1] = bdec.size();
+        bs0[b + 1] = bseg.size();
+        max_lines = std::max(max_lines, bl0[b + 1] - bl0[b]);
+        max_planes = std::max(max_planes, (size_t)B.planes);
+        max_units = std::max(max_units, (size_t)B.units);
+        max_groups = std::max(max_groups, B.g1 - B.g0);
+    }
+    if (blines.empty()) blines.resize(1);
+    // workspace: lines | planes (all regions) | units | groups | maps | candidate lists | merged lists
+    const size_t tm_per_batch = max_planes * regions.size();
+    const size_t o_lines = 0, o_tm = al256(max_lines * sizeof(ExLine)), o_dec = o_tm + al256(tm_per_batch * sizeof(ExTmpl)),
+                 o_seg = o_dec + al256(max_units * sizeof(int4)), o_map = o_seg + al256(max_groups * sizeof(int4)),
+                 o_cand = o_map + (topk ? 0 : al256(max_planes * plane_max * sizeof(float))),
+                 o_best = o_cand + al256(max_cand * k * 8), total = o_best + al256((size_t)TA * k * 8);
+    fm->s_eval.reserve(total);
+    char* d = (char*)fm->s_eval.p;
+    hipStream_t st = fm->stream;
+    const ExLine* d_lines = (const ExLine*)(d + o_lines);
+    const ExTmpl* d_tm = (const ExTmpl*)(d + o_tm);
+    const int4* d_dec = (const int4*)(d + o_dec);
+    const int4* d_seg = (const int4*)(d + o_seg);
+    float* map = (float*)(d + o_map);
+    unsigned long long* cand = (unsigned long long*)(d + o_cand);
+    unsigned long long* d_best = (unsigned long long*)(d + o_best);
+    FDCM_HIP(hipMemsetAsync(d_best, 0xff, (size_t)TA * k * 8, st));  // kNoKey
+    size_t at = 0;  // (batch, region) launches so far
+    for (size_t b = 0; b < batches.size(); ++b) {
+        const Batch& B = batches[b];
+        const int n_groups = (int)(B.g1 - B.g0);
+        // stream order: these copies wait for the previous batch's kernels
+        FDCM_HIP(hipMemcpyAsync(d + o_lines, blines.data() + bl0[b], std::max<size_t>(1, bl0[b + 1] - bl0[b]) * sizeof(ExLine),
+                                hipMemcpyHostToDevice, st));
+        FDCM_HIP(hipMemcpyAsync(d + o_tm, btm.data() + bt0[b], (bt0[b + 1] - bt0[b]) * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
+        FDCM_HIP(hipMemcpyAsync(d + o_dec, bdec.data() + bd0[b], (bd0[b + 1] - bd0[b]) * sizeof(int4), hipMemcpyHostToDevice, st));
+        FDCM_HIP(hipMemcpyAsync(d + o_seg, bseg.data() + bs0[b], (bs0[b + 1] - bs0[b]) * sizeof(int4), hipMemcpyHostToDevice, st));
+        for (size_t r = 0; r < regions.size(); ++r) {
+            const Region& R = regions[r];
+            const ExTmpl* tm = d_tm + r * (size_t)B.planes;
+            const int G = parts[at++];
+            int lpu;
+            if (topk) {
+                lpu = G;
+                launch<true>(fm, P, g, d_lines, tm, B.planes, k, G / 4, nullptr, cand);
+            } else {
+                lpu = 4 * G;
+                const fdcm_grid rg{g.x0 + R.ia * g.sx, g.y0 + R.ja * g.sy, R.w, R.h, g.sx, g.sy};
+                launch<false>(fm, P, rg, d_lines, tm, B.planes, 0, portions_for(fm, rg, B.planes), map, nullptr);
+                const dim3 grid((unsigned)(B.units * G));
+                if (std::max(rx, ry) <= 8)
+                    hipLaunchKernelGGL(k_exhaustive_peaks3<8>, grid, dim3(256), 0, st, map, R.w, R.h, tm, d_dec, G, rx, ry, ra, n,
+                                       wrap, R.di0, R.di1, R.dj0, R.dj1, R.ia, R.ja, g.nx, (unsigned)N, k, cand);
+                else
+                    hipLaunchKernelGGL(k_exhaustive_peaks3<kMaxRadius>, grid, dim3(256), 0, st, map, R.w, R.h, tm, d_dec, G, rx, ry, ra,
+                                       n, wrap, R.di0, R.di1, R.dj0, R.dj1, R.ia, R.ja, g.nx, (unsigned)N, k, cand);
+                FDCM_HIP(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_exhaustive_merge_groups, dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, st,
+                               (const unsigned long long*)cand, d_seg, n_groups, lpu, k, d_best);
+            FDCM_HIP(hipGetLastError());
+        }
+    }
+    std::vector<unsigned long long> best((size_t)TA * k);
+    FDCM_HIP(hipMemcpyAsync(best.data(), d_best, best.size() * 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
+    emit_rotation_records(best, k, index, M, n, g, base, out, n_out);
 }
 
 }  // namespace fdcm

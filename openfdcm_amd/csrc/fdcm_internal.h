@@ -215,6 +215,12 @@ void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const f
                            fdcm_match** out, int64_t* n_out);
 void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int rx, int ry,
                                  int32_t base, fdcm_match** out, int64_t* n_out);
+void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, int32_t sx, int32_t sy,
+                                 fdcm_grid* out);
+void run_score_map_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
+                             float* out_host);
+void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
+                                     int k, int rx, int ry, int ra, int wrap, int32_t base, fdcm_match** out, int64_t* n_out);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

@@ -20,6 +20,20 @@ def _adopt_matches(ptr, n):
     return res
 
 
+def _rotations(cs, pivots, T):
+    """(capi.Rotations, the arrays it points to): cs (n, 2) float32, pivots (T, 2) float32 or None."""
+    cs = np.ascontiguousarray(cs, dtype=np.float32).reshape(-1, 2)
+    rot = capi.Rotations(capi.fptr(cs), cs.shape[0], None)
+    keep = [cs]
+    if pivots is not None:
+        pv = np.ascontiguousarray(pivots, dtype=np.float32).reshape(-1, 2)
+        if pv.shape[0] != T:
+            raise ValueError("one pivot per template is required")
+        rot.pivots = capi.fptr(pv)
+        keep.append(pv)
+    return rot, keep
+
+
 def as_grid(grid):
     """capi.Grid from a capi.Grid or an (x0, y0, nx, ny, sx, sy) sequence."""
     if isinstance(grid, capi.Grid):
@@ -167,6 +181,37 @@ class DeviceFeatureMap:
         capi.check(capi.lib().fdcm_search_exhaustive_peaks(self._h, templates._h, C.byref(g), int(k), int(rx), int(ry),
                                                            int(tmpl_index_base), C.byref(out), C.byref(n)))
         return _adopt_matches(out, n.value)
+
+    # ---- rotations (include/fdcm.h, "Rotations"): cs (n, 2) float32 pairs (c, s); pivots (T, 2) float32 or None (origin)
+    def exhaustive_rotations_window(self, templates, cs, pivots=None, sx=1, sy=1):
+        """The smallest grid with strides (sx, sy), origin a multiple of them, that holds every admissible integer
+        translation of every (template with lines, rotation)."""
+        rot, keep = _rotations(cs, pivots, templates.count)
+        g = capi.Grid()
+        capi.check(capi.lib().fdcm_exhaustive_rotations_window(self._h, templates._h, C.byref(rot), int(sx), int(sy),
+                                                               C.byref(g)))
+        return g
+
+    def exhaustive_rotation_search(self, templates, grid, cs, pivots=None, k=1, rx=0, ry=0, ra=0, wrap=False,
+                                   tmpl_index_base=0):
+        """Per template with lines: its k best peaks over (rotation, grid point) by (score, rotation, grid index), the
+        window (2 ra + 1) rotations (circular with wrap) x (2 ry + 1) x (2 rx + 1) grid points, as raw match records with
+        transform [c, -s, m.x + tx, s, c, m.y + ty].  rx = ry = ra = 0 is the top-k over all (rotation, point) pairs."""
+        rot, keep = _rotations(cs, pivots, templates.count)
+        g = as_grid(grid)
+        out, n = C.c_void_p(), C.c_int64()
+        capi.check(capi.lib().fdcm_search_exhaustive_rotations(self._h, templates._h, C.byref(rot), C.byref(g), int(k),
+                                                               int(rx), int(ry), int(ra), int(bool(wrap)),
+                                                               int(tmpl_index_base), C.byref(out), C.byref(n)))
+        return _adopt_matches(out, n.value)
+
+    def rotation_score_map(self, templates, grid, cs, pivots=None):
+        """(T, n, ny, nx) float32: the score of every rotated template at every grid point, NaN where not admissible."""
+        rot, keep = _rotations(cs, pivots, templates.count)
+        g = as_grid(grid)
+        out = np.empty((templates.count, rot.n, g.ny, g.nx), dtype=np.float32)
+        capi.check(capi.lib().fdcm_score_map_rotations(self._h, templates._h, C.byref(rot), C.byref(g), capi.fptr(out)))
+        return out
 
     def score_map(self, templates, grid):
         """(T, ny, nx) float32: the score of every template at every grid point, NaN where not admissible."""

@@ -1,7 +1,12 @@
 """Times the exhaustive translation search (include/fdcm.h, "exhaustive translation search") on config 2': the feature map
 and the 1000 x 32-line synthetic templates bench.py uses, every template over its default window (exhaustive_window), at
 stride 1, 2 and 4 with k = 1 and 8, and the peaks (fdcm_search_exhaustive_peaks) at k = 8 with radii 1, 8 and 32 on the
-same grids, each beside the top-k call of the same k.
+same grids, each beside the top-k call of the same k.  Rotations (fdcm_search_exhaustive_rotations): the first
+--rot-templates templates, --rot-angles angles evenly over the circle with wrap, pivot the bounding-box centre, k = --peak-k,
+(rx = ry, ra) in --rot-cases at --rot-strides, each beside fdcm_search_exhaustive (ra = rx = 0) or
+fdcm_search_exhaustive_peaks (r = rx) of the same k on the host-rotated line sets passed as one template set: the same
+scoring work without the rotation code.  The host preparation (rotation, bins, boxes) is timed alone as a call on a
+1 x 1 grid.
 
 For every case it prints the wall time of one blocking fdcm_search_exhaustive call (median of --reps after a warm-up),
 the admissible translations scored (the sum over templates of the window's points inside each template's admissible
@@ -9,7 +14,8 @@ box), and the lookup rate: 2 lookups per template line and admissible translatio
 evaluate<Dt3Cpu> (the reference's code, one host thread) on a random sample of admissible translations, the same
 lookups per translation.
 
-    python tools/exhaustive_bench.py [--reps 5] [--cpu-sample 20000] [--radii 1,8,32] [--json out.json]
+    python tools/exhaustive_bench.py [--reps 5] [--cpu-sample 20000] [--radii 1,8,32] [--rot-cases 0:0,8:1,8:2]
+                                     [--only-rotations] [--json out.json]
 """
 import argparse
 import json
@@ -42,6 +48,53 @@ def points_in(lo, hi, g0, n, s):
     return max(0, i1 - i0 + 1)
 
 
+def rotation_cases(args, dev, tmpls, timed):
+    """The rotation search against the translation-only calls on the host-rotated line sets (module docstring)."""
+    import openfdcm_amd as openfdcm
+    from openfdcm_amd.engine import DeviceTemplates
+    sub = tmpls[: args.rot_templates]
+    angles = np.arange(args.rot_angles) * (2 * np.pi / args.rot_angles)
+    cs = openfdcm._angles(angles)
+    piv = openfdcm._pivots(sub, "center", len(sub))
+    tset = DeviceTemplates(sub)
+    rs = DeviceTemplates([openfdcm_rotate(t, c, s, p) for t, p in zip(sub, piv) for c, s in cs])
+    k = args.peak_k
+    cases = [tuple(int(v) for v in c.split(":")) for c in args.rot_cases.split(",")]
+    out = {"templates": len(sub), "angles": len(cs), "k": k, "wrap": True, "rows": []}
+    prep_ms, _, _ = timed(lambda: dev.exhaustive_rotation_search(tset, (0, 0, 1, 1, 1, 1), cs, piv, k=k))
+    out["host_preparation_ms"] = round(prep_ms, 3)
+    print(f"rotations: {len(sub)} templates x {len(cs)} angles, host preparation (1 x 1 grid call) {prep_ms:.2f} ms", flush=True)
+    for s in [int(v) for v in args.rot_strides.split(",")]:
+        grid = dev.exhaustive_rotations_window(tset, cs, piv, s, s).as_tuple()
+        for r, ra in cases:
+            ms, ms_min, recs = timed(lambda: dev.exhaustive_rotation_search(tset, grid, cs, piv, k=k, rx=r, ry=r, ra=ra, wrap=True))
+            if r == 0 and ra == 0:
+                base_ms, _, _ = timed(lambda: dev.exhaustive_search(rs, grid, k=k))
+                base = "exhaustive_search"
+            else:
+                base_ms, _, _ = timed(lambda: dev.exhaustive_peaks(rs, grid, k=k, rx=r, ry=r))
+                base = f"exhaustive_peaks r {r}"
+            out["rows"].append({"stride": s, "r": r, "ra": ra, "grid": list(grid), "ms_per_call": round(ms, 3),
+                                "ms_min": round(ms_min, 3), "baseline": base, "baseline_ms_per_call": round(base_ms, 3),
+                                "ratio": round(ms / base_ms, 3), "records": int(len(recs)),
+                                "host_preparation_share": round(prep_ms / ms, 3)})
+            print(f"rotations stride {s} r {r} ra {ra}: {ms:.2f} ms/call (min {ms_min:.2f}), {base} on the host-rotated set "
+                  f"{base_ms:.2f} ms: {ms / base_ms:.3f}x, {len(recs)} records, host preparation {prep_ms / ms:.1%}", flush=True)
+    return out
+
+
+def openfdcm_rotate(tm, c, s, p):
+    """The rotated line set M_a(t) (include/fdcm.h, "Rotations"), float32 left to right."""
+    c, s, px, py = np.float32(c), np.float32(s), np.float32(p[0]), np.float32(p[1])
+    ns = -s
+    mx, my = px - (c * px + ns * py), py - (s * px + c * py)
+    out = np.empty_like(tm)
+    for r in (0, 2):
+        out[r] = (c * tm[r] + ns * tm[r + 1]) + mx
+        out[r + 1] = (s * tm[r] + c * tm[r + 1]) + my
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=5)
@@ -50,6 +103,11 @@ def main():
     ap.add_argument("--ks", default="1,8")
     ap.add_argument("--radii", default="1,8,32", help="peak radii (rx = ry); empty: no peaks cases")
     ap.add_argument("--peak-k", type=int, default=8)
+    ap.add_argument("--rot-templates", type=int, default=100)
+    ap.add_argument("--rot-angles", type=int, default=36)
+    ap.add_argument("--rot-strides", default="1,2")
+    ap.add_argument("--rot-cases", default="0:0,8:1,8:2", help="rx=ry:ra pairs; empty: no rotation cases")
+    ap.add_argument("--only-rotations", action="store_true", help="skip the translation-only cases and the CPU figure")
     ap.add_argument("--json", default=None, help="also write the results here")
     args = ap.parse_args()
 
@@ -63,7 +121,7 @@ def main():
     n_lines = int(sum(t.shape[1] for t in tmpls))
     bx = boxes(dev, tmpls)
     rows = []
-    for s in [int(v) for v in args.strides.split(",")]:
+    for s in [int(v) for v in args.strides.split(",")] if not args.only_rotations else []:
         grid = dev.exhaustive_window(tset, s, s).as_tuple()
         x0, y0, nx, ny, sx, sy = grid
         adm = [0 if b is None else points_in(b[0], b[2], x0, nx, sx) * points_in(b[1], b[3], y0, ny, sy) for b in bx]
@@ -93,7 +151,7 @@ def main():
 
     peaks = []
     radii = [int(v) for v in args.radii.split(",") if v]
-    for s in [int(v) for v in args.strides.split(",")] if radii else []:
+    for s in [int(v) for v in args.strides.split(",")] if radii and not args.only_rotations else []:
         grid = dev.exhaustive_window(tset, s, s).as_tuple()
         k = args.peak_k
         top_ms, _, _ = timed(lambda: dev.exhaustive_search(tset, grid, k=k))
@@ -103,6 +161,15 @@ def main():
                           "topk_ms_per_call": round(top_ms, 3), "ratio_to_topk": round(ms / top_ms, 3), "records": int(len(recs))})
             print(f"peaks stride {s} k {k} r {r}: {ms:.2f} ms/call (min {ms_min:.2f}), top-k {top_ms:.2f} ms: "
                   f"{ms / top_ms:.2f}x, {len(recs)} records", flush=True)
+
+    rot = rotation_cases(args, dev, tmpls, timed) if args.rot_cases else {}
+    if args.only_rotations:
+        res = {"workload": "config 2' rotations", "rotations": rot}
+        print(json.dumps(res))
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
 
     # the same work on the host: the oracle's evaluate (one thread) on random admissible translations of random templates
     orc = O.build(scene, depth=cfg["depth"], coeff=5.0, padding=1.0, distance=cfg["distance"], nthreads=16)
@@ -124,7 +191,8 @@ def main():
     for r in rows:
         r["speedup_vs_cpu_1thread"] = round(r["lookups_per_s"] / cpu["lookups_per_s"], 1)
     res = {"workload": "config 2': 1024x1024 scene (200 lines, seed 1), depth 30, L2, padding 1.0; 1000 templates x 32 lines "
-                       "(seed 2), default window per stride", "template_lines": n_lines, "gpu": rows, "peaks": peaks, "cpu": cpu}
+                       "(seed 2), default window per stride", "template_lines": n_lines, "gpu": rows, "peaks": peaks, "rotations": rot,
+           "cpu": cpu}
     print(json.dumps(res))
     if args.json:
         with open(args.json, "w") as f:
