@@ -1,16 +1,16 @@
-// fdcm_exhaustive.hip -- exhaustive translation search: the score of every template at every point of a translation
-// grid (a dense chamfer score map) and the k best grid points of every template (include/fdcm.h, "exhaustive search").
-// A score is evaluate<Dt3Cpu> (dt3cpu.cpp:126-179) at one translation: the bits fdcm_featuremap_evaluate returns there.
+// fdcm_exhaustive.hip -- exhaustive search: the score of every template at every point of a translation grid (a dense
+// chamfer score map), the k best grid points of every template, the peaks, and both over rotations (include/fdcm.h,
+// "exhaustive search").  A score is evaluate<Dt3Cpu> (dt3cpu.cpp:126-179) at one translation: the bits
+// fdcm_featuremap_evaluate returns there.
 //
-//   k_exhaustive<BUF32, TOPK>  a workgroup takes a contiguous run of 16 x 64 sub-tiles of the grid (a portion) and a
-//                              chunk of kChunk templates; for every sub-tile it scores every template of the chunk (a lane per 4
-//                              translations), then writes the scores (map) or offers them to a running k-best list
-//                              per wave and template kept in LDS (top-k)
-//   k_exhaustive_merge         one wave per template merges the per-wave lists into the template's k best
-//   k_exhaustive_peaks<R>      peaks: reads the score planes k_exhaustive<., false> wrote and offers every point whose
-//                              key is the minimum of its (2rx+1) x (2ry+1) window to a per-wave k-best list
-//   k_exhaustive_peaks3<R>     peaks across rotations: the same over (angle, row, column), keys (bits, a N + g)
-//   k_exhaustive_merge_groups  one wave per template of a batch: its merged list so far and its units' lists
+//   k_exhaustive<BUF32, TOPK>         a workgroup takes a contiguous run of 16 x 64 sub-tiles of the grid (a portion) and a
+//                                     chunk of kChunk templates; for every sub-tile it scores every template of the chunk (a
+//                                     lane per 4 translations), then writes the scores (map) or offers them to a running
+//                                     k-best list per wave and template kept in LDS (top-k)
+//   k_exhaustive_peaks<R, ANGLES>     peaks: reads the score planes k_exhaustive<., false> wrote and offers every point whose
+//                                     key is the minimum of its window to a per-wave k-best list; ANGLES: the window spans
+//                                     several angles' planes (64-bit keys in LDS), else one plane (32-bit score bits)
+//   k_exhaustive_merge_groups         one wave per template of a batch: its merged list so far and its units' lists
 //
 // Keys of the top-k are (score bits << 32) | grid index: scores are >= +0, so the key order is the (score, g) order,
 // which is total -- the result does not depend on which wave saw which point first.  No atomics.
@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstring>
 #include <thread>
+#include <type_traits>
 
 #include "fdcm_internal.h"
 #include "fdcm_score.h"
@@ -40,8 +41,8 @@ struct ExLine {  // one template line: end points, and the line's slice (bin * f
 struct ExTmpl {    // one template of a launch
     int line0, n;  // its lines in the line array
     int i0, i1, j0, j1;  // grid indices of its admissible translations: [i0, i1] x [j0, j1] (empty when i0 > i1 or j0 > j1)
-    int slot;            // where its output goes: map plane / candidate lists / merged list
-    unsigned koff;       // added to the grid index of its top-k keys (a rotation's a * nx * ny; 0 otherwise)
+    int slot;            // where its output goes: map plane / candidate lists
+    unsigned koff;       // added to the grid index of its keys (a rotation's a * nx * ny; 0 otherwise)
 };
 
 // One read of the interleaved volume (ivol_index) at column x, row y of the line's slice.  xw: the column's part of the
@@ -244,49 +245,49 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
     }
 }
 
-// One wave per template: the k best of its n_lists sorted lists of k keys.
-__global__ void __launch_bounds__(256) k_exhaustive_merge(const unsigned long long* __restrict__ cand, int T, int n_lists,
-                                                          int k, unsigned long long* __restrict__ best) {
-    const int lane = threadIdx.x & 63;
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= T) return;  // wave-uniform
-    unsigned long long e = kNoKey, thr = kNoKey;
-    const unsigned long long* c = cand + (long long)t * n_lists * k;
-    for (int q = 0; q < n_lists; ++q) {
-        const unsigned long long v = lane < k ? c[(long long)q * k + lane] : kNoKey;
-        thr = list_offer(e, v, thr, k, lane);
-    }
-    if (lane < k) best[(long long)t * k + lane] = e;
-}
-
-// Peaks (include/fdcm.h, "peaks"): a point is a peak when its key is the minimum of the keys in its (2rx+1) x (2ry+1)
-// window.  A workgroup takes tiles of kPkTX x kPkTY points of one template's score plane (written by k_exhaustive<., false>)
-// and loads each with its rx / ry halo into LDS as score bits, kPkNone for no key (outside the plane or the template's
-// box, or NaN).  Row pass: per halo row and tile column the minimum key of the row's 2rx+1 window (the smallest score
-// bits, the first column on ties: within a row the grid index rises with i).  Column pass: per tile point the minimum
-// of the 2ry+1 row minima; the point is a peak when that is its own key.  Peaks go to the wave's sorted k-best list
-// (registers, lane l holding entry l) with list_offer; k_exhaustive_merge folds the lists.  R: the largest radius the
-// LDS is sized for.
+// Peaks (include/fdcm.h, "peaks" and "Rotations"): a point is a peak when its key (score bits << 32) | (a N + g) is the
+// minimum of the keys in its window, a box of (2ra+1) x (2ry+1) x (2rx+1) over (angle, row, column), so the minimum is
+// separable: angle first, then rows, then columns.  A workgroup takes tiles of kPkTX x kPkTY points of one decided
+// (template, angle) unit and loads each with its rx / ry halo into LDS:
+//   ANGLES   already reduced over the angle window: per halo point the smallest key over the planes of the angles
+//            a - ra .. a + ra (circular when wrap is set; angles outside [0, n_rot) otherwise ignored), kNoKey where none
+//            is admissible (NaN).  The planes of a group (one template's angles lo, lo + 1, ... of the batch, mod n_rot)
+//            are consecutive: the plane of angle a' is D.x + ((a' - lo) mod n_rot).
+//   !ANGLES  the window holds the unit's own plane alone: its score bits, kPkNone for no key (outside the plane or the
+//            template's box, or NaN).  Every key of the window has the same angle term, so the score bits and the column
+//            order the row's keys: the row pass keeps the first column of the smallest bits.
+// Row pass: per halo row and tile column the minimum key of the row's 2rx+1 window.  Column pass: per tile point the
+// minimum of the 2ry+1 row minima; the point is a peak when that is its own key.  Peaks go to the wave's sorted k-best
+// list (registers, lane l holding entry l) with list_offer; k_exhaustive_merge_groups folds the lists.  R: the largest
+// radius the LDS is sized for: (4 or 8) kH kW + 8 kH kPkTX bytes.
 constexpr int kPkTX = 64, kPkTY = 32;  // tile: a wave per row, kPkTY / 4 rows per wave
 constexpr unsigned kPkNone = ~0u;      // no key: above the bits of every score >= +0 (NaN included)
 constexpr int kMaxRadius = 32;
-constexpr size_t kPeakMapBytes = (size_t)768 << 20;  // the score planes of one batch
-constexpr int kPeakWorkgroups = 2048;                // peak workgroups of a launch, about: parts per template
+constexpr int kPeakWorkgroups = 2048;  // peak workgroups of a launch, about: parts per unit
 
-template <int R>
-__global__ void __launch_bounds__(256) k_exhaustive_peaks(const float* __restrict__ map, int w, int h, const ExTmpl* __restrict__ tm,
-                                                          int parts, int rx, int ry, int di0, int di1, int dj0, int dj1, int ia,
-                                                          int ja, int nx, int k, int n_lists,
-                                                          unsigned long long* __restrict__ cand) {
+template <int R, bool ANGLES>
+__global__ void __launch_bounds__(256) k_exhaustive_peaks(const float* __restrict__ map, int w, int h, const ExTmpl* __restrict__ pl,
+                                                          const int4* __restrict__ dec, int parts, int rx, int ry, int ra, int n_rot,
+                                                          int wrap, int di0, int di1, int dj0, int dj1, int ia, int ja, int nx,
+                                                          unsigned N, int k, unsigned long long* __restrict__ cand) {
+    using Key = typename std::conditional<ANGLES, unsigned long long, unsigned>::type;
     constexpr int kW = kPkTX + 2 * R, kH = kPkTY + 2 * R;
-    __shared__ unsigned S[kH * kW];             // score bits of the tile and its halo
+    __shared__ Key S[kH * kW];                    // score bits (ANGLES: angle-window minimum keys) of the tile and halo
     __shared__ unsigned long long B[kH * kPkTX];  // row-window minimum keys
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q = (int)blockIdx.x / parts, part = (int)blockIdx.x % parts;
-    const ExTmpl P = tm[q];
-    const float* plane = map + (long long)P.slot * w * h;
+    const int u = (int)blockIdx.x / parts, part = (int)blockIdx.x % parts;
+    // x: the group's first plane, y: its first angle lo, z: its planes, w: the unit's angle
+    const int4 D = ANGLES ? dec[u] : make_int4(0, 0, 0, 0);
+    const long long wh = (long long)w * h;
+    auto plane_of = [&](int a2) {
+        const int o = a2 - D.y;
+        return D.x + (o < 0 ? o + n_rot : o);
+    };
+    const ExTmpl P = pl[ANGLES ? plane_of(D.w) : u];  // one plane per window: the batch's units are its planes
+    const float* own = map + (long long)P.slot * wh;
+    const unsigned akey = ANGLES ? (unsigned)D.w * N : P.koff;  // a N
     const int W2 = kPkTX + 2 * rx, H2 = kPkTY + 2 * ry;
-    // the points this launch decides for the template: its box (plane coordinates) within the decision rectangle
+    // the points this launch decides for the unit: its box (plane coordinates) within the decision rectangle
     const int bi0 = max(P.i0, di0), bi1 = min(P.i1, di1), bj0 = max(P.j0, dj0), bj1 = min(P.j1, dj1);
     const int ntx = bi0 <= bi1 ? (bi1 - bi0) / kPkTX + 1 : 0, nty = bj0 <= bj1 ? (bj1 - bj0) / kPkTY + 1 : 0;
     unsigned long long e = kNoKey, thr = kNoKey;
@@ -295,9 +296,23 @@ __global__ void __launch_bounds__(256) k_exhaustive_peaks(const float* __restric
         for (int idx = threadIdx.x; idx < H2 * W2; idx += 256) {
             const int hr = idx / W2, hc = idx - hr * W2;
             const int li = li0 - rx + hc, lj = lj0 - ry + hr;
-            unsigned v = kPkNone;
-            if (li >= P.i0 && li <= P.i1 && lj >= P.j0 && lj <= P.j1) {  // the box lies inside the plane
-                const float s = plane[(long long)lj * w + li];
+            Key v = (Key)kNoKey;
+            if constexpr (ANGLES) {
+                if (li >= 0 && li < w && lj >= 0 && lj < h) {  // every plane of the launch covers the region's plane
+                    const unsigned g = (unsigned)(ja + lj) * (unsigned)nx + (unsigned)(ia + li);
+                    const long long off = (long long)lj * w + li;
+                    for (int d = -ra; d <= ra; ++d) {
+                        int a2 = D.w + d;
+                        if (a2 < 0 || a2 >= n_rot) {
+                            if (!wrap) continue;
+                            a2 = (a2 % n_rot + n_rot) % n_rot;
+                        }
+                        const float s = map[(long long)plane_of(a2) * wh + off];
+                        if (!(s != s)) v = min(v, ((unsigned long long)__float_as_uint(s) << 32) | ((unsigned)a2 * N + g));
+                    }
+                }
+            } else if (li >= P.i0 && li <= P.i1 && lj >= P.j0 && lj <= P.j1) {  // the box lies inside the plane
+                const float s = own[(long long)lj * w + li];
                 if (!(s != s)) v = __float_as_uint(s);
             }
             S[hr * kW + hc] = v;
@@ -305,107 +320,43 @@ __global__ void __launch_bounds__(256) k_exhaustive_peaks(const float* __restric
         __syncthreads();
         for (int idx = threadIdx.x; idx < H2 * kPkTX; idx += 256) {
             const int hr = idx / kPkTX, c = idx % kPkTX;
-            const unsigned* row = S + hr * kW + c;
-            unsigned best = row[0];
+            const Key* row = S + hr * kW + c;
+            Key best = row[0];
             int at = 0;
             for (int d = 1; d <= 2 * rx; ++d) {
-                const unsigned v = row[d];
+                const Key v = row[d];
                 if (v < best) { best = v; at = d; }
             }
-            const unsigned g = (unsigned)(ja + lj0 - ry + hr) * (unsigned)nx + (unsigned)(ia + li0 - rx + c + at);
-            B[hr * kPkTX + c] = best == kPkNone ? kNoKey : ((unsigned long long)best << 32) | g;
+            if constexpr (ANGLES) {
+                B[hr * kPkTX + c] = best;
+            } else {
+                const unsigned g = akey + (unsigned)(ja + lj0 - ry + hr) * (unsigned)nx + (unsigned)(ia + li0 - rx + c + at);
+                B[hr * kPkTX + c] = best == kPkNone ? kNoKey : ((unsigned long long)best << 32) | g;
+            }
         }
         __syncthreads();
         for (int r = wave; r < kPkTY; r += 4) {  // wave-uniform: every lane takes part in list_offer
             const int li = li0 + lane, lj = lj0 + r;
             unsigned long long m = kNoKey;
             for (int d = 0; d <= 2 * ry; ++d) m = min(m, B[(r + d) * kPkTX + lane]);
-            const unsigned s = S[(r + ry) * kW + rx + lane];
+            // the point's own key, from its score bits
+            auto own_key = [&](unsigned s) {
+                return ((unsigned long long)s << 32) | (akey + (unsigned)(ja + lj) * (unsigned)nx + (unsigned)(ia + li));
+            };
             unsigned long long key = kNoKey;
-            if (s != kPkNone && li <= bi1 && lj <= bj1) {
-                const unsigned long long own = ((unsigned long long)s << 32) | ((unsigned)(ja + lj) * (unsigned)nx + (unsigned)(ia + li));
-                if (own == m) key = own;
-            }
-            thr = list_offer(e, key, thr, k, lane);
-        }
-        __syncthreads();  // the next tile overwrites S and B
-    }
-    // candidate lists: [q][part * 4 + wave][k] of n_lists per template (the last list is the caller's)
-    if (lane < k) cand[((long long)q * n_lists + part * 4 + wave) * k + lane] = e;
-}
-
-// Peaks across rotations (include/fdcm.h, "Rotations"): keys (score bits << 32) | (a * N + g) over (angle, row, column),
-// the window a box of (2ra+1) x (2ry+1) x (2rx+1), so its minimum is separable: angle first, then rows, then columns.
-// A workgroup takes tiles of one decided (template, angle) unit and loads each tile with its rx / ry halo into LDS,
-// already reduced over the angle window: per halo point the smallest key over the planes of the angles a - ra .. a + ra
-// (circular when wrap is set; angles outside [0, n_rot) otherwise ignored), kNoKey where none is admissible (NaN).  The
-// row and column passes are k_exhaustive_peaks', on 64-bit keys; the point is a peak when the window minimum is its own
-// key.  The planes of a group (one template's angles lo, lo + 1, ... of the batch, mod n_rot) are consecutive: the plane
-// of angle a' is D.x + ((a' - lo) mod n_rot).  LDS: 8 (kH kW + kH kPkTX) bytes, 54 KiB for R = 8 and 144 KiB for R = 32.
-template <int R>
-__global__ void __launch_bounds__(256) k_exhaustive_peaks3(const float* __restrict__ map, int w, int h, const ExTmpl* __restrict__ pl,
-                                                           const int4* __restrict__ dec, int parts, int rx, int ry, int ra, int n_rot,
-                                                           int wrap, int di0, int di1, int dj0, int dj1, int ia, int ja, int nx,
-                                                           unsigned N, int k, unsigned long long* __restrict__ cand) {
-    constexpr int kW = kPkTX + 2 * R, kH = kPkTY + 2 * R;
-    __shared__ unsigned long long S[kH * kW];     // angle-window minimum keys of the tile and its halo
-    __shared__ unsigned long long B[kH * kPkTX];  // then the row-window minimum
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int u = (int)blockIdx.x / parts, part = (int)blockIdx.x % parts;
-    const int4 D = dec[u];  // x: the group's first plane, y: its first angle lo, z: its planes, w: the unit's angle
-    const long long wh = (long long)w * h;
-    auto plane_of = [&](int a2) {
-        const int o = a2 - D.y;
-        return D.x + (o < 0 ? o + n_rot : o);
-    };
-    const ExTmpl P = pl[plane_of(D.w)];
-    const float* own = map + (long long)P.slot * wh;
-    const unsigned akey = (unsigned)D.w * N;
-    const int W2 = kPkTX + 2 * rx, H2 = kPkTY + 2 * ry;
-    const int bi0 = max(P.i0, di0), bi1 = min(P.i1, di1), bj0 = max(P.j0, dj0), bj1 = min(P.j1, dj1);
-    const int ntx = bi0 <= bi1 ? (bi1 - bi0) / kPkTX + 1 : 0, nty = bj0 <= bj1 ? (bj1 - bj0) / kPkTY + 1 : 0;
-    unsigned long long e = kNoKey, thr = kNoKey;
-    for (int tile = part; tile < ntx * nty; tile += parts) {  // workgroup-uniform
-        const int li0 = bi0 + (tile % ntx) * kPkTX, lj0 = bj0 + (tile / ntx) * kPkTY;
-        for (int idx = threadIdx.x; idx < H2 * W2; idx += 256) {
-            const int hr = idx / W2, hc = idx - hr * W2;
-            const int li = li0 - rx + hc, lj = lj0 - ry + hr;
-            unsigned long long v = kNoKey;
-            if (li >= 0 && li < w && lj >= 0 && lj < h) {  // every plane of the launch covers the region's plane
-                const unsigned g = (unsigned)(ja + lj) * (unsigned)nx + (unsigned)(ia + li);
-                const long long off = (long long)lj * w + li;
-                for (int d = -ra; d <= ra; ++d) {
-                    int a2 = D.w + d;
-                    if (a2 < 0 || a2 >= n_rot) {
-                        if (!wrap) continue;
-                        a2 = (a2 % n_rot + n_rot) % n_rot;
+            if constexpr (ANGLES) {  // the score from the unit's plane
+                if (li <= bi1 && lj <= bj1) {
+                    const float s = own[(long long)lj * w + li];
+                    if (!(s != s)) {
+                        const unsigned long long k3 = own_key(__float_as_uint(s));
+                        if (k3 == m) key = k3;
                     }
-                    const float s = map[(long long)plane_of(a2) * wh + off];
-                    if (!(s != s)) v = min(v, ((unsigned long long)__float_as_uint(s) << 32) | ((unsigned)a2 * N + g));
                 }
-            }
-            S[hr * kW + hc] = v;
-        }
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < H2 * kPkTX; idx += 256) {
-            const int hr = idx / kPkTX, c = idx % kPkTX;
-            const unsigned long long* row = S + hr * kW + c;
-            unsigned long long best = row[0];
-            for (int d = 1; d <= 2 * rx; ++d) best = min(best, row[d]);
-            B[hr * kPkTX + c] = best;
-        }
-        __syncthreads();
-        for (int r = wave; r < kPkTY; r += 4) {  // wave-uniform: every lane takes part in list_offer
-            const int li = li0 + lane, lj = lj0 + r;
-            unsigned long long m = kNoKey;
-            for (int d = 0; d <= 2 * ry; ++d) m = min(m, B[(r + d) * kPkTX + lane]);
-            unsigned long long key = kNoKey;
-            if (li <= bi1 && lj <= bj1) {
-                const float s = own[(long long)lj * w + li];
-                if (!(s != s)) {
-                    const unsigned long long k3 = ((unsigned long long)__float_as_uint(s) << 32) |
-                                                  (akey + (unsigned)(ja + lj) * (unsigned)nx + (unsigned)(ia + li));
-                    if (k3 == m) key = k3;
+            } else {  // the score bits in LDS
+                const unsigned s = S[(r + ry) * kW + rx + lane];
+                if (s != kPkNone && li <= bi1 && lj <= bj1) {
+                    const unsigned long long k2 = own_key(s);
+                    if (k2 == m) key = k2;
                 }
             }
             thr = list_offer(e, key, thr, k, lane);
@@ -569,38 +520,6 @@ int portions_for(const fdcm_featuremap* fm, const fdcm_grid& g, int T) {
     return 8 * (int)std::max<long long>(1, std::min<long long>(per_xcd, (n_subtiles + 7) / 8));
 }
 
-// The templates that can emit: lines, and admissible points in the grid (search() skips templates without lines); index:
-// the set's index of every template in `act`.
-void active_templates(const Prepared& P, std::vector<ExTmpl>& act, std::vector<int32_t>& index) {
-    for (const ExTmpl& e : P.tm)
-        if (e.n > 0 && e.i0 <= e.i1 && e.j0 <= e.j1) { act.push_back(e); index.push_back(e.slot); }
-}
-
-// The records of the merged lists best[q][k] of the templates index[q] (kNoKey ends a list).
-void emit_records(const std::vector<unsigned long long>& best, int k, const std::vector<int32_t>& index, const fdcm_grid& g,
-                  int32_t base, fdcm_match** out, int64_t* n_out) {
-    const int T = (int)index.size();
-    int64_t n = 0;
-    for (unsigned long long v : best) n += v != kNoKey;
-    fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, n) * sizeof(fdcm_match));
-    int64_t w = 0;
-    for (int q = 0; q < T; ++q)  // ascending template index: `act` keeps the set's order
-        for (int r = 0; r < k; ++r) {
-            const unsigned long long v = best[(size_t)q * k + r];
-            if (v == kNoKey) break;
-            const unsigned gi = (unsigned)(v & 0xffffffffu);
-            const int i = (int)(gi % (unsigned)g.nx), j = (int)(gi / (unsigned)g.nx);
-            fdcm_match& rec = m[w++];
-            rec.tmpl_idx = base + index[(size_t)q];
-            rec.score = f_from_bits((uint32_t)(v >> 32));
-            // combine(t, identity): the transform of a pure translation (Match.transform)
-            rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = (float)(g.x0 + i * g.sx);
-            rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = (float)(g.y0 + j * g.sy);
-        }
-    *out = m;
-    *n_out = n;
-}
-
 // ---- rotations (include/fdcm.h, "Rotations")
 // M_a = [R | m] of rotate(lines, R, rot_point), math.h:372-378, with R = [[c, -s], [s, c]] and m = p - R p: every product
 // and sum rounded to float32, left to right (the Makefile's -ffp-contract=off keeps them unfused on the host too).
@@ -697,9 +616,10 @@ void prepare_rotated(const fdcm_featuremap* fm, const fdcm_templates* t, const f
     if (P.lines.empty()) P.lines.resize(1);
 }
 
-// The records of the merged lists best[q][k] of the templates index[q]: key a * N + g -> transform [R | m + (tx, ty)].
-void emit_rotation_records(const std::vector<unsigned long long>& best, int k, const std::vector<int32_t>& index,
-                           const std::vector<RotM>& M, int n, const fdcm_grid& g, int32_t base, fdcm_match** out, int64_t* n_out) {
+// The records of the merged lists best[q][k] of the templates index[q]: key a N + g -> transform [R | m + (tx, ty)], R | m
+// the transform M[index[q] n + a] of the rotation search, or a pure translation when M is null.
+void emit_records(const std::vector<unsigned long long>& best, int k, const std::vector<int32_t>& index, int n, const fdcm_grid& g,
+                  int32_t base, const RotM* M, fdcm_match** out, int64_t* n_out) {
     const int T = (int)index.size();
     const unsigned long long N = (unsigned long long)g.nx * g.ny;
     int64_t cnt = 0;
@@ -714,21 +634,219 @@ void emit_rotation_records(const std::vector<unsigned long long>& best, int k, c
             const int a = (int)(low / N);
             const unsigned gi = (unsigned)(low % N);
             const int i = (int)(gi % (unsigned)g.nx), j = (int)(gi / (unsigned)g.nx);
-            const RotM& R = M[(size_t)index[(size_t)q] * n + a];
+            const float tx = (float)(g.x0 + i * g.sx), ty = (float)(g.y0 + j * g.sy);
             fdcm_match& rec = m[w++];
             rec.tmpl_idx = base + index[(size_t)q];
             rec.score = f_from_bits((uint32_t)(v >> 32));
-            // combine(translation, M_a), float32 adds
-            rec.transform[0] = R.c; rec.transform[1] = R.ns; rec.transform[2] = R.mx + (float)(g.x0 + i * g.sx);
-            rec.transform[3] = R.s; rec.transform[4] = R.c; rec.transform[5] = R.my + (float)(g.y0 + j * g.sy);
+            if (M) {  // combine(translation, M_a), float32 adds
+                const RotM& R = M[(size_t)index[(size_t)q] * n + a];
+                rec.transform[0] = R.c; rec.transform[1] = R.ns; rec.transform[2] = R.mx + tx;
+                rec.transform[3] = R.s; rec.transform[4] = R.c; rec.transform[5] = R.my + ty;
+            } else {  // combine(t, identity): the transform of a pure translation (Match.transform)
+                rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = tx;
+                rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = ty;
+            }
         }
     *out = m;
     *n_out = cnt;
 }
 
-constexpr size_t kRotMapBytes = (size_t)512 << 20;   // the score planes of one batch of the rotation search
-constexpr size_t kRotLineBytes = (size_t)64 << 20;   // the rotated lines of one batch
-constexpr size_t kRotCandBytes = (size_t)128 << 20;  // the top-k candidate lists of one batch
+constexpr size_t kMapBytes = (size_t)768 << 20;     // the score planes of one batch (peaks): translations
+constexpr size_t kRotMapBytes = (size_t)512 << 20;  // .. rotations (n > 1): larger batches slow their stride-2 passes
+constexpr size_t kCandBytes = (size_t)128 << 20;  // the candidate lists of one batch (top-k)
+
+// The search driver, the top-k when rx = ry = ra = 0 and the peaks otherwise.  P: T x n planes, plane t n + a being
+// template t at angle a (n = 1: the translations).  Out: index, the templates that can emit -- lines, and an admissible
+// grid point under some angle -- in ascending order, and best[q][k], the merged list of template index[q] (kNoKey ends
+// a list).
+void search(fdcm_featuremap* fm, const Prepared& P, int n, const fdcm_grid& g, int k, int rx, int ry, int ra, int wrap,
+            std::vector<unsigned long long>& best, std::vector<int32_t>& index) {
+    const int64_t T = (int64_t)P.tm.size() / n;
+    const unsigned long long N = (unsigned long long)g.nx * g.ny;
+    for (int64_t i = 0; i < T; ++i) {
+        if (P.tm[(size_t)(i * n)].n == 0) continue;
+        for (int a = 0; a < n; ++a) {
+            const ExTmpl& e = P.tm[(size_t)(i * n + a)];
+            if (e.i0 <= e.i1 && e.j0 <= e.j1) { index.push_back((int32_t)i); break; }
+        }
+    }
+    if (index.empty()) return;
+    const int TA = (int)index.size();
+    const bool topk = rx == 0 && ry == 0 && ra == 0;  // every point is a peak: the fused top-k, no planes written
+
+    // Regions (peaks only): the whole grid when a batch of min(n, 2ra + 1) planes -- one decided angle and its angle
+    // halo -- fits the map workspace, else rectangles whose planes with their rx / ry halo do.
+    const long long pts = (long long)((n == 1 ? kMapBytes : kRotMapBytes) / sizeof(float));
+    const int need = std::min(n, 2 * ra + 1);
+    int DX = g.nx, DY = g.ny;
+    if (!topk && (long long)g.nx * g.ny * need > pts) {
+        DY = std::min(g.ny, 2048);
+        DX = (int)std::max<long long>(1, std::min<long long>(g.nx, pts / need / (DY + 2 * ry) - 2 * rx));
+    }
+    struct Region { int ia, ja, w, h, di0, di1, dj0, dj1; };
+    std::vector<Region> regions;
+    if (topk) {
+        regions.push_back(Region{0, 0, g.nx, g.ny, 0, g.nx - 1, 0, g.ny - 1});
+    } else {
+        for (int rj = 0; rj < g.ny; rj += DY)
+            for (int ri = 0; ri < g.nx; ri += DX) {
+                const int ia = std::max(0, ri - rx), ib = std::min(g.nx - 1, ri + DX - 1 + rx);
+                const int ja = std::max(0, rj - ry), jb = std::min(g.ny - 1, rj + DY - 1 + ry);
+                regions.push_back(Region{ia, ja, ib - ia + 1, jb - ja + 1, ri - ia, std::min(g.nx - 1, ri + DX - 1) - ia, rj - ja,
+                                         std::min(g.ny - 1, rj + DY - 1) - ja});
+            }
+    }
+    long long plane_max = 0;
+    for (const Region& R : regions) plane_max = std::max(plane_max, (long long)R.w * R.h);
+    // planes per batch: the map workspace (peaks) or the candidate lists, (8 units + 8192) * 4 lists of k keys at most (top-k)
+    int cap;
+    if (topk)
+        cap = (int)std::max<long long>(1, std::min<long long>(65536, ((long long)(kCandBytes / (32ull * k)) - 8192) / 8));
+    else
+        cap = (int)std::max<long long>(need, std::min<long long>(65536, pts / plane_max));
+
+    // Batches: groups (one template's decided angles [a0, a1) and the planes of their angle halo, lo, lo + 1, ... mod n)
+    // filled in template order; a template's angles are cut across batches when they do not fit.
+    struct Group { int q, a0, a1, lo, np, plane0, unit0; };
+    struct Batch { size_t g0, g1; int planes, units; };
+    auto n_planes = [&](int a0, int a1) { return wrap ? std::min(n, a1 - a0 + 2 * ra) : std::min(n, a1 + ra) - std::max(0, a0 - ra); };
+    std::vector<Group> groups;
+    std::vector<Batch> batches;
+    Batch cur{0, 0, 0, 0};
+    for (int q = 0; q < TA; ++q) {
+        int a0 = 0;
+        while (a0 < n) {
+            const int room = cap - cur.planes;
+            int a1 = std::min(n, a0 + room);
+            while (a1 > a0 && n_planes(a0, a1) > room) --a1;
+            if (a1 == a0) {  // (cap >= need: an empty batch takes one angle)
+                cur.g1 = groups.size();
+                batches.push_back(cur);
+                cur = Batch{groups.size(), 0, 0, 0};
+                continue;
+            }
+            const int np = n_planes(a0, a1);
+            const int lo = wrap ? (np == n ? 0 : ((a0 - ra) % n + n) % n) : std::max(0, a0 - ra);
+            groups.push_back(Group{q, a0, a1, lo, np, cur.planes, cur.units});
+            cur.planes += np;
+            cur.units += a1 - a0;
+            a0 = a1;
+        }
+    }
+    if (cur.planes > 0) {
+        cur.g1 = groups.size();
+        batches.push_back(cur);
+    }
+
+    // Host arrays of every batch: per region its planes (boxes in the region's plane coordinates, lines in P.lines, slot =
+    // the plane's place in the batch, koff = a * N), its decided units and its groups.
+    std::vector<size_t> bt0(batches.size() + 1, 0), bd0(batches.size() + 1, 0), bs0(batches.size() + 1, 0);
+    std::vector<ExTmpl> btm;
+    std::vector<int4> bdec, bseg;
+    std::vector<int> parts;  // workgroups per unit of each (batch, region)
+    size_t max_planes = 1, max_cand = 1;
+    for (size_t b = 0; b < batches.size(); ++b) {
+        const Batch& B = batches[b];
+        std::vector<ExTmpl> planes;  // full-grid boxes
+        for (size_t gi = B.g0; gi < B.g1; ++gi) {
+            const Group& G = groups[gi];
+            const int64_t ti = index[(size_t)G.q];
+            for (int p = 0; p < G.np; ++p) {
+                const int a2 = (G.lo + p) % n;
+                ExTmpl e = P.tm[(size_t)(ti * n + a2)];
+                e.slot = G.plane0 + p;
+                e.koff = (unsigned)((unsigned long long)a2 * N);
+                planes.push_back(e);
+            }
+            bseg.push_back(make_int4(G.unit0, G.a1 - G.a0, G.q, 0));
+            for (int a = G.a0; a < G.a1; ++a) bdec.push_back(make_int4(G.plane0, G.lo, G.np, a));
+        }
+        for (const Region& R : regions) {
+            int max_tiles = 0;
+            for (ExTmpl e : planes) {
+                if (!topk) {
+                    const int i0 = std::max(e.i0, R.ia) - R.ia, i1 = std::min(e.i1, R.ia + R.w - 1) - R.ia;
+                    const int j0 = std::max(e.j0, R.ja) - R.ja, j1 = std::min(e.j1, R.ja + R.h - 1) - R.ja;
+                    if (i0 <= i1 && j0 <= j1) {
+                        e.i0 = i0; e.i1 = i1; e.j0 = j0; e.j1 = j1;
+                        const int ci0 = std::max(i0, R.di0), ci1 = std::min(i1, R.di1), cj0 = std::max(j0, R.dj0),
+                                  cj1 = std::min(j1, R.dj1);
+                        if (ci0 <= ci1 && cj0 <= cj1)
+                            max_tiles = std::max(max_tiles, ((ci1 - ci0) / kPkTX + 1) * ((cj1 - cj0) / kPkTY + 1));
+                    } else {
+                        e.i0 = 0; e.i1 = -1; e.j0 = 0; e.j1 = -1;
+                    }
+                }
+                btm.push_back(e);
+            }
+            parts.push_back(topk ? 4 * portions_for(fm, g, B.planes)  // lists per unit
+                                 : std::max(1, std::min(max_tiles, (kPeakWorkgroups + B.units - 1) / B.units)));
+            max_cand = std::max(max_cand, (size_t)B.units * (topk ? parts.back() : 4 * parts.back()));
+        }
+        bt0[b + 1] = btm.size();
+        bd0[b + 1] = bdec.size();
+        bs0[b + 1] = bseg.size();
+        max_planes = std::max(max_planes, (size_t)B.planes);
+    }
+    // Workspace: P's lines, the planes (all regions), units and groups of every batch and the merged lists, then the maps
+    // and candidate lists.  The first part goes up in one asynchronous copy from pinned memory before any kernel of the
+    // call, so no copy waits behind the call's own kernels.
+    const size_t o_tm = al256(P.lines.size() * sizeof(ExLine)), o_dec = o_tm + al256(btm.size() * sizeof(ExTmpl)),
+                 o_seg = o_dec + al256(bdec.size() * sizeof(int4)), o_best = o_seg + al256(bseg.size() * sizeof(int4)),
+                 o_map = o_best + al256((size_t)TA * k * 8),
+                 o_cand = o_map + (topk ? 0 : al256(max_planes * plane_max * sizeof(float))), total = o_cand + al256(max_cand * k * 8);
+    fm->s_eval.reserve(total);
+    fm->s_eval_stage.reserve(o_map);
+    char* d = (char*)fm->s_eval.p;
+    char* h = (char*)fm->s_eval_stage.p;
+    std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
+    std::memcpy(h + o_tm, btm.data(), btm.size() * sizeof(ExTmpl));
+    std::memcpy(h + o_dec, bdec.data(), bdec.size() * sizeof(int4));
+    std::memcpy(h + o_seg, bseg.data(), bseg.size() * sizeof(int4));
+    std::memset(h + o_best, 0xff, (size_t)TA * k * 8);  // kNoKey
+    hipStream_t st = fm->stream;
+    FDCM_HIP(hipMemcpyAsync(d, h, o_map, hipMemcpyHostToDevice, st));
+    float* map = (float*)(d + o_map);
+    unsigned long long* cand = (unsigned long long*)(d + o_cand);
+    unsigned long long* d_best = (unsigned long long*)(d + o_best);
+    size_t at = 0;  // (batch, region) launches so far
+    for (size_t b = 0; b < batches.size(); ++b) {
+        const Batch& B = batches[b];
+        const int n_groups = (int)(B.g1 - B.g0);
+        const ExTmpl* d_tm = (const ExTmpl*)(d + o_tm) + bt0[b];
+        const int4* d_dec = (const int4*)(d + o_dec) + bd0[b];
+        const int4* d_seg = (const int4*)(d + o_seg) + bs0[b];
+        for (size_t r = 0; r < regions.size(); ++r) {
+            const Region& R = regions[r];
+            const ExTmpl* tm = d_tm + r * (size_t)B.planes;
+            const int G = parts[at++];
+            int lpu;
+            if (topk) {
+                lpu = G;
+                launch<true>(fm, P, g, (const ExLine*)d, tm, B.planes, k, G / 4, nullptr, cand);
+            } else {
+                lpu = 4 * G;
+                const fdcm_grid rg{g.x0 + R.ia * g.sx, g.y0 + R.ja * g.sy, R.w, R.h, g.sx, g.sy};
+                launch<false>(fm, P, rg, (const ExLine*)d, tm, B.planes, 0, portions_for(fm, rg, B.planes), map, nullptr);
+                // 32-bit keys in LDS when the angle window holds one plane: 4 workgroups per CU at R = 8 instead of 2.
+                // That kernel reads plane u for unit u: with one plane per window every group has as many planes as units.
+                if (need == 1 && B.planes != B.units) throw std::string("exhaustive search: batch planes and units differ");
+                const bool small = std::max(rx, ry) <= 8;
+                auto peaks = need > 1 ? (small ? k_exhaustive_peaks<8, true> : k_exhaustive_peaks<kMaxRadius, true>)
+                                      : (small ? k_exhaustive_peaks<8, false> : k_exhaustive_peaks<kMaxRadius, false>);
+                hipLaunchKernelGGL(peaks, dim3((unsigned)(B.units * G)), dim3(256), 0, st, map, R.w, R.h, tm, d_dec, G, rx, ry, ra, n,
+                                   wrap, R.di0, R.di1, R.dj0, R.dj1, R.ia, R.ja, g.nx, (unsigned)N, k, cand);
+                FDCM_HIP(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_exhaustive_merge_groups, dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, st,
+                               (const unsigned long long*)cand, d_seg, n_groups, lpu, k, d_best);
+            FDCM_HIP(hipGetLastError());
+        }
+    }
+    best.resize((size_t)TA * k);
+    FDCM_HIP(hipMemcpyAsync(best.data(), d_best, best.size() * 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
+}
 
 }  // namespace
 
@@ -789,39 +907,11 @@ void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid
 
 void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int32_t base,
                            fdcm_match** out, int64_t* n_out) {
-    check_grid(g);
-    if (k < 1 || k > kMaxK) throw std::string("k must be in [1, 64]");
-    *n_out = 0;
-    if (t->T == 0) return;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    Prepared P;
-    prepare(fm, t, g, P);
-    std::vector<ExTmpl> act;
-    std::vector<int32_t> index;
-    active_templates(P, act, index);
-    if (act.empty()) return;
-    const int T = (int)act.size();
-    for (int q = 0; q < T; ++q) act[(size_t)q].slot = q;
-    const int portions = portions_for(fm, g, T), n_lists = portions * 4;
-    const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_cand = o_tm + al256(act.size() * sizeof(ExTmpl)),
-                 o_best = o_cand + al256((size_t)T * n_lists * k * 8), total = o_best + al256((size_t)T * k * 8);
-    fm->s_eval.reserve(total);
-    char* d = (char*)fm->s_eval.p;
-    hipStream_t st = fm->stream;
-    FDCM_HIP(hipMemcpyAsync(d + o_lines, P.lines.data(), P.lines.size() * sizeof(ExLine), hipMemcpyHostToDevice, st));
-    FDCM_HIP(hipMemcpyAsync(d + o_tm, act.data(), act.size() * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
-    launch<true>(fm, P, g, (const ExLine*)(d + o_lines), (const ExTmpl*)(d + o_tm), T, k, portions, nullptr,
-                 (unsigned long long*)(d + o_cand));
-    hipLaunchKernelGGL(k_exhaustive_merge, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, st, (const unsigned long long*)(d + o_cand), T,
-                       n_lists, k, (unsigned long long*)(d + o_best));
-    FDCM_HIP(hipGetLastError());
-    std::vector<unsigned long long> best((size_t)T * k);
-    FDCM_HIP(hipMemcpyAsync(best.data(), d + o_best, best.size() * 8, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipStreamSynchronize(st));
-    emit_records(best, k, index, g, base, out, n_out);
+    run_search_exhaustive_peaks(fm, t, g, k, 0, 0, base, out, n_out);  // radius 0: every point is a peak
 }
 
+// The driver on the caller's lines, not on rotated_set's identity rotation: that turns a -0 coordinate into +0, which
+// can change the sign of x2 - x1 and with it a line's orientation bin.
 void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int rx, int ry,
                                  int32_t base, fdcm_match** out, int64_t* n_out) {
     check_grid(g);
@@ -833,97 +923,10 @@ void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, c
     begin(fm);
     Prepared P;
     prepare(fm, t, g, P);
-    std::vector<ExTmpl> act;
+    std::vector<unsigned long long> best;
     std::vector<int32_t> index;
-    active_templates(P, act, index);
-    if (act.empty()) return;
-    const int T = (int)act.size();
-    // Decision regions: the whole grid when one plane fits the map workspace, else rectangles whose planes with their
-    // halo do.  Each region's planes cover its points and every neighbour within the radii, so region, batch and tile
-    // edges never change a result.
-    const long long pts = (long long)(kPeakMapBytes / sizeof(float));
-    int DX = g.nx, DY = g.ny;
-    if ((long long)g.nx * g.ny > pts) {
-        DY = std::min(g.ny, 8192);
-        DX = (int)std::min<long long>(g.nx, pts / (DY + 2 * ry) - 2 * rx);
-    }
-    const long long plane_max = (long long)std::min(g.nx, DX + 2 * rx) * std::min(g.ny, DY + 2 * ry);
-    const int batch = (int)std::max<long long>(1, std::min<long long>({(long long)T, pts / plane_max, 65536}));
-    struct Region { int ia, ja, w, h, di0, di1, dj0, dj1; };  // its plane [ia, ia + w) x [ja, ja + h); decisions, plane coordinates
-    std::vector<Region> regions;
-    for (int rj = 0; rj < g.ny; rj += DY)
-        for (int ri = 0; ri < g.nx; ri += DX) {
-            const int ia = std::max(0, ri - rx), ib = std::min(g.nx - 1, ri + DX - 1 + rx);
-            const int ja = std::max(0, rj - ry), jb = std::min(g.ny - 1, rj + DY - 1 + ry);
-            regions.push_back(Region{ia, ja, ib - ia + 1, jb - ja + 1, ri - ia, std::min(g.nx - 1, ri + DX - 1) - ia, rj - ja,
-                                     std::min(g.ny - 1, rj + DY - 1) - ja});
-        }
-    // per (batch, region) the batch's templates with their boxes in the region's plane coordinates, slot = place in the batch
-    std::vector<ExTmpl> tms;
-    std::vector<int> parts;  // workgroups per template of each (batch, region)
-    for (int b0 = 0; b0 < T; b0 += batch)
-        for (const Region& R : regions) {
-            int max_tiles = 0;
-            for (int q = b0; q < std::min(T, b0 + batch); ++q) {
-                ExTmpl e = act[(size_t)q];
-                const int i0 = std::max(e.i0, R.ia) - R.ia, i1 = std::min(e.i1, R.ia + R.w - 1) - R.ia;
-                const int j0 = std::max(e.j0, R.ja) - R.ja, j1 = std::min(e.j1, R.ja + R.h - 1) - R.ja;
-                e.slot = q - b0;
-                if (i0 <= i1 && j0 <= j1) {
-                    e.i0 = i0; e.i1 = i1; e.j0 = j0; e.j1 = j1;
-                    const int ci0 = std::max(i0, R.di0), ci1 = std::min(i1, R.di1), cj0 = std::max(j0, R.dj0), cj1 = std::min(j1, R.dj1);
-                    if (ci0 <= ci1 && cj0 <= cj1)
-                        max_tiles = std::max(max_tiles, ((ci1 - ci0) / kPkTX + 1) * ((cj1 - cj0) / kPkTY + 1));
-                } else {
-                    e.i0 = 0; e.i1 = -1; e.j0 = 0; e.j1 = -1;
-                }
-                tms.push_back(e);
-            }
-            const int nb = std::min(batch, T - b0);
-            parts.push_back(std::max(1, std::min(max_tiles, (kPeakWorkgroups + nb - 1) / nb)));
-        }
-    // workspace: lines | templates | maps (batch planes) | candidate lists | merged lists; bounded whatever T and the grid
-    const size_t cand_lists = (size_t)4 * (kPeakWorkgroups + batch) + batch;  // >= nb * (4 * parts + 1) of every launch
-    const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_map = o_tm + al256(tms.size() * sizeof(ExTmpl)),
-                 o_cand = o_map + al256((size_t)batch * plane_max * sizeof(float)), o_best = o_cand + al256(cand_lists * k * 8),
-                 total = o_best + al256((size_t)batch * k * 8);
-    fm->s_eval.reserve(total);
-    char* d = (char*)fm->s_eval.p;
-    hipStream_t st = fm->stream;
-    float* map = (float*)(d + o_map);
-    unsigned long long* cand = (unsigned long long*)(d + o_cand);
-    unsigned long long* d_best = (unsigned long long*)(d + o_best);
-    FDCM_HIP(hipMemcpyAsync(d + o_lines, P.lines.data(), P.lines.size() * sizeof(ExLine), hipMemcpyHostToDevice, st));
-    FDCM_HIP(hipMemcpyAsync(d + o_tm, tms.data(), tms.size() * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
-    std::vector<unsigned long long> best((size_t)T * k);
-    size_t at = 0;  // (batch, region) launches so far
-    for (int b0 = 0; b0 < T; b0 += batch) {
-        const int nb = std::min(batch, T - b0);
-        FDCM_HIP(hipMemsetAsync(d_best, 0xff, (size_t)nb * k * 8, st));  // kNoKey
-        for (const Region& R : regions) {
-            const ExTmpl* tm = (const ExTmpl*)(d + o_tm) + (size_t)b0 * regions.size() + (size_t)(&R - regions.data()) * nb;
-            const int G = parts[at++], n_lists = 4 * G + 1;
-            // the regions before this one: their merged lists go in as each template's last list
-            FDCM_HIP(hipMemcpy2DAsync(cand + (size_t)(n_lists - 1) * k, (size_t)n_lists * k * 8, d_best, (size_t)k * 8, (size_t)k * 8,
-                                      (size_t)nb, hipMemcpyDeviceToDevice, st));
-            const fdcm_grid rg{g.x0 + R.ia * g.sx, g.y0 + R.ja * g.sy, R.w, R.h, g.sx, g.sy};
-            launch<false>(fm, P, rg, (const ExLine*)(d + o_lines), tm, nb, 0, portions_for(fm, rg, nb), map, nullptr);
-            const dim3 grid((unsigned)(nb * G));
-            if (std::max(rx, ry) <= 8)
-                hipLaunchKernelGGL(k_exhaustive_peaks<8>, grid, dim3(256), 0, st, map, R.w, R.h, tm, G, rx, ry, R.di0, R.di1, R.dj0,
-                                   R.dj1, R.ia, R.ja, g.nx, k, n_lists, cand);
-            else
-                hipLaunchKernelGGL(k_exhaustive_peaks<kMaxRadius>, grid, dim3(256), 0, st, map, R.w, R.h, tm, G, rx, ry, R.di0, R.di1,
-                                   R.dj0, R.dj1, R.ia, R.ja, g.nx, k, n_lists, cand);
-            FDCM_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_exhaustive_merge, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, (const unsigned long long*)cand, nb,
-                               n_lists, k, d_best);
-            FDCM_HIP(hipGetLastError());
-        }
-        FDCM_HIP(hipMemcpyAsync(best.data() + (size_t)b0 * k, d_best, (size_t)nb * k * 8, hipMemcpyDeviceToHost, st));
-    }
-    FDCM_HIP(hipStreamSynchronize(st));  // (P and tms stay alive until here)
-    emit_records(best, k, index, g, base, out, n_out);
+    search(fm, P, 1, g, k, rx, ry, 0, 0, best, index);
+    emit_records(best, k, index, 1, g, base, nullptr, out, n_out);
 }
 
 void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, int32_t sx, int32_t sy,
@@ -955,8 +958,7 @@ void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* 
     if (wrap != 0 && wrap != 1) throw std::string("wrap must be 0 or 1");
     const int n = rot.n;
     if (n < 1) throw std::string("rotations: n must be >= 1");
-    const unsigned long long N = (unsigned long long)g.nx * g.ny;
-    if ((unsigned long long)n * N > (1ull << 32)) throw std::string("n_rot * nx * ny must be at most 2^32");
+    if ((unsigned long long)n * g.nx * g.ny > (1ull << 32)) throw std::string("n_rot * nx * ny must be at most 2^32");
     *n_out = 0;
     if (t->T == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
@@ -964,205 +966,10 @@ void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* 
     Prepared P;
     std::vector<RotM> M;
     prepare_rotated(fm, t, rot, g, P, M);
-    // the templates that can emit: lines, and an admissible grid point under some rotation
+    std::vector<unsigned long long> best;
     std::vector<int32_t> index;
-    for (int64_t i = 0; i < t->T; ++i) {
-        if (t->offsets[(size_t)i + 1] == t->offsets[(size_t)i]) continue;
-        for (int a = 0; a < n; ++a) {
-            const ExTmpl& e = P.tm[(size_t)(i * n + a)];
-            if (e.i0 <= e.i1 && e.j0 <= e.j1) { index.push_back((int32_t)i); break; }
-        }
-    }
-    if (index.empty()) return;
-    const int TA = (int)index.size();
-    const bool topk = rx == 0 && ry == 0 && ra == 0;  // every point is a peak: the fused top-k, no planes written
-
-    // Regions (peaks only): the whole grid when a batch of min(n, 2ra + 1) planes -- one decided angle and its angle
-    // halo -- fits the map workspace, else rectangles whose planes with their rx / ry halo do.
-    const long long pts = (long long)(kRotMapBytes / sizeof(float));
-    const int need = std::min(n, 2 * ra + 1);
-    int DX = g.nx, DY = g.ny;
-    if (!topk && (long long)g.nx * g.ny * need > pts) {
-        DY = std::min(g.ny, 2048);
-        DX = (int)std::max<long long>(1, std::min<long long>(g.nx, pts / need / (DY + 2 * ry) - 2 * rx));
-    }
-    struct Region { int ia, ja, w, h, di0, di1, dj0, dj1; };
-    std::vector<Region> regions;
-    if (topk) {
-        regions.push_back(Region{0, 0, g.nx, g.ny, 0, g.nx - 1, 0, g.ny - 1});
-    } else {
-        for (int rj = 0; rj < g.ny; rj += DY)
-            for (int ri = 0; ri < g.nx; ri += DX) {
-                const int ia = std::max(0, ri - rx), ib = std::min(g.nx - 1, ri + DX - 1 + rx);
-                const int ja = std::max(0, rj - ry), jb = std::min(g.ny - 1, rj + DY - 1 + ry);
-                regions.push_back(Region{ia, ja, ib - ia + 1, jb - ja + 1, ri - ia, std::min(g.nx - 1, ri + DX - 1) - ia, rj - ja,
-                                         std::min(g.ny - 1, rj + DY - 1) - ja});
-            }
-    }
-    long long plane_max = 0;
-    for (const Region& R : regions) plane_max = std::max(plane_max, (long long)R.w * R.h);
-    // planes per batch: the map workspace (peaks) or the candidate lists, (8 units + 8192) * 4 lists of k keys at most (top-k)
-    int cap;
-    if (topk)
-        cap = (int)std::max<long long>(1, std::min<long long>(65536, ((long long)(kRotCandBytes / (32ull * k)) - 8192) / 8));
-    else
-        cap = (int)std::max<long long>(need, std::min<long long>(65536, pts / plane_max));
-
-    // Batches: groups (one template's decided angles [a0, a1) and the planes of their angle halo, lo, lo + 1, ... mod n)
-    // filled in template order; a template's angles are cut across batches when they do not fit.
-    struct Group { int q, a0, a1, lo, np, plane0, unit0; };
-    struct Batch { size_t g0, g1; int planes, units; int64_t lines; };
-    auto n_planes = [&](int a0, int a1) { return wrap ? std::min(n, a1 - a0 + 2 * ra) : std::min(n, a1 + ra) - std::max(0, a0 - ra); };
-    const int64_t line_cap = (int64_t)(kRotLineBytes / sizeof(ExLine));
-    std::vector<Group> groups;
-    std::vector<Batch> batches;
-    Batch cur{0, 0, 0, 0, 0};
-    for (int q = 0; q < TA; ++q) {
-        const int64_t Lq = t->offsets[(size_t)index[(size_t)q] + 1] - t->offsets[(size_t)index[(size_t)q]];
-        int a0 = 0;
-        while (a0 < n) {
-            const int64_t room = std::max<int64_t>(0, std::min<int64_t>(cap - cur.planes, (line_cap - cur.lines) / Lq));
-            int a1 = (int)std::min<int64_t>(n, a0 + room);
-            while (a1 > a0 && n_planes(a0, a1) > room) --a1;
-            if (a1 == a0) {
-                if (cur.planes > 0) {
-                    cur.g1 = groups.size();
-                    batches.push_back(cur);
-                    cur = Batch{groups.size(), 0, 0, 0, 0};
-                    continue;
-                }
-                a1 = a0 + 1;  // one angle whose planes alone pass the line budget: a batch of its own
-            }
-            const int np = n_planes(a0, a1);
-            const int lo = wrap ? (np == n ? 0 : ((a0 - ra) % n + n) % n) : std::max(0, a0 - ra);
-            groups.push_back(Group{q, a0, a1, lo, np, cur.planes, cur.units});
-            cur.planes += np;
-            cur.units += a1 - a0;
-            cur.lines += np * Lq;
-            a0 = a1;
-        }
-    }
-    if (cur.planes > 0) {
-        cur.g1 = groups.size();
-        batches.push_back(cur);
-    }
-
-    // Host arrays of every batch: its lines, per region its planes (boxes in the region's plane coordinates, slot = the
-    // plane's place in the batch, koff = a * N), its decided units and its groups.
-    std::vector<ExLine> blines;
-    std::vector<size_t> bl0(batches.size() + 1, 0), bt0(batches.size() + 1, 0), bd0(batches.size() + 1, 0), bs0(batches.size() + 1, 0);
-    std::vector<ExTmpl> btm;
-    std::vector<int4> bdec, bseg;
-    std::vector<int> parts;  // workgroups per unit of each (batch, region)
-    size_t max_lines = 1, max_planes = 1, max_units = 1, max_groups = 1, max_cand = 1;
-    for (size_t b = 0; b < batches.size(); ++b) {
-        const Batch& B = batches[b];
-        std::vector<ExTmpl> planes;  // full-grid boxes, line0 in the batch
-        for (size_t gi = B.g0; gi < B.g1; ++gi) {
-            const Group& G = groups[gi];
-            const int64_t ti = index[(size_t)G.q];
-            for (int p = 0; p < G.np; ++p) {
-                const int a2 = (G.lo + p) % n;
-                ExTmpl e = P.tm[(size_t)(ti * n + a2)];
-                const size_t l0 = blines.size() - bl0[b];
-                blines.insert(blines.end(), P.lines.begin() + e.line0, P.lines.begin() + e.line0 + e.n);
-                e.line0 = (int)l0;
-                e.slot = G.plane0 + p;
-                e.koff = (unsigned)((unsigned long long)a2 * N);
-                planes.push_back(e);
-            }
-            bseg.push_back(make_int4(G.unit0, G.a1 - G.a0, G.q, 0));
-            for (int a = G.a0; a < G.a1; ++a) bdec.push_back(make_int4(G.plane0, G.lo, G.np, a));
-        }
-        for (const Region& R : regions) {
-            int max_tiles = 0;
-            for (ExTmpl e : planes) {
-                if (!topk) {
-                    const int i0 = std::max(e.i0, R.ia) - R.ia, i1 = std::min(e.i1, R.ia + R.w - 1) - R.ia;
-                    const int j0 = std::max(e.j0, R.ja) - R.ja, j1 = std::min(e.j1, R.ja + R.h - 1) - R.ja;
-                    if (i0 <= i1 && j0 <= j1) {
-                        e.i0 = i0; e.i1 = i1; e.j0 = j0; e.j1 = j1;
-                        const int ci0 = std::max(i0, R.di0), ci1 = std::min(i1, R.di1), cj0 = std::max(j0, R.dj0),
-                                  cj1 = std::min(j1, R.dj1);
-                        if (ci0 <= ci1 && cj0 <= cj1)
-                            max_tiles = std::max(max_tiles, ((ci1 - ci0) / kPkTX + 1) * ((cj1 - cj0) / kPkTY + 1));
-                    } else {
-                        e.i0 = 0; e.i1 = -1; e.j0 = 0; e.j1 = -1;
-                    }
-                }
-                btm.push_back(e);
-            }
-            parts.push_back(topk ? 4 * portions_for(fm, g, B.planes)  // lists per unit
-                                 : std::max(1, std::min(max_tiles, (kPeakWorkgroups + B.units - 1) / B.units)));
-            max_cand = std::max(max_cand, (size_t)B.units * (topk ? parts.back() : 4 * parts.back()));
-        }
-        bl0[b + 1] = blines.size();
-        bt0[b + 1] = btm.size();
-        bd0[b + 1] = bdec.size();
-        bs0[b + 1] = bseg.size();
-        max_lines = std::max(max_lines, bl0[b + 1] - bl0[b]);
-        max_planes = std::max(max_planes, (size_t)B.planes);
-        max_units = std::max(max_units, (size_t)B.units);
-        max_groups = std::max(max_groups, B.g1 - B.g0);
-    }
-    if (blines.empty()) blines.resize(1);
-    // workspace: lines | planes (all regions) | units | groups | maps | candidate lists | merged lists
-    const size_t tm_per_batch = max_planes * regions.size();
-    const size_t o_lines = 0, o_tm = al256(max_lines * sizeof(ExLine)), o_dec = o_tm + al256(tm_per_batch * sizeof(ExTmpl)),
-                 o_seg = o_dec + al256(max_units * sizeof(int4)), o_map = o_seg + al256(max_groups * sizeof(int4)),
-                 o_cand = o_map + (topk ? 0 : al256(max_planes * plane_max * sizeof(float))),
-                 o_best = o_cand + al256(max_cand * k * 8), total = o_best + al256((size_t)TA * k * 8);
-    fm->s_eval.reserve(total);
-    char* d = (char*)fm->s_eval.p;
-    hipStream_t st = fm->stream;
-    const ExLine* d_lines = (const ExLine*)(d + o_lines);
-    const ExTmpl* d_tm = (const ExTmpl*)(d + o_tm);
-    const int4* d_dec = (const int4*)(d + o_dec);
-    const int4* d_seg = (const int4*)(d + o_seg);
-    float* map = (float*)(d + o_map);
-    unsigned long long* cand = (unsigned long long*)(d + o_cand);
-    unsigned long long* d_best = (unsigned long long*)(d + o_best);
-    FDCM_HIP(hipMemsetAsync(d_best, 0xff, (size_t)TA * k * 8, st));  // kNoKey
-    size_t at = 0;  // (batch, region) launches so far
-    for (size_t b = 0; b < batches.size(); ++b) {
-        const Batch& B = batches[b];
-        const int n_groups = (int)(B.g1 - B.g0);
-        // stream order: these copies wait for the previous batch's kernels
-        FDCM_HIP(hipMemcpyAsync(d + o_lines, blines.data() + bl0[b], std::max<size_t>(1, bl0[b + 1] - bl0[b]) * sizeof(ExLine),
-                                hipMemcpyHostToDevice, st));
-        FDCM_HIP(hipMemcpyAsync(d + o_tm, btm.data() + bt0[b], (bt0[b + 1] - bt0[b]) * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
-        FDCM_HIP(hipMemcpyAsync(d + o_dec, bdec.data() + bd0[b], (bd0[b + 1] - bd0[b]) * sizeof(int4), hipMemcpyHostToDevice, st));
-        FDCM_HIP(hipMemcpyAsync(d + o_seg, bseg.data() + bs0[b], (bs0[b + 1] - bs0[b]) * sizeof(int4), hipMemcpyHostToDevice, st));
-        for (size_t r = 0; r < regions.size(); ++r) {
-            const Region& R = regions[r];
-            const ExTmpl* tm = d_tm + r * (size_t)B.planes;
-            const int G = parts[at++];
-            int lpu;
-            if (topk) {
-                lpu = G;
-                launch<true>(fm, P, g, d_lines, tm, B.planes, k, G / 4, nullptr, cand);
-            } else {
-                lpu = 4 * G;
-                const fdcm_grid rg{g.x0 + R.ia * g.sx, g.y0 + R.ja * g.sy, R.w, R.h, g.sx, g.sy};
-                launch<false>(fm, P, rg, d_lines, tm, B.planes, 0, portions_for(fm, rg, B.planes), map, nullptr);
-                const dim3 grid((unsigned)(B.units * G));
-                if (std::max(rx, ry) <= 8)
-                    hipLaunchKernelGGL(k_exhaustive_peaks3<8>, grid, dim3(256), 0, st, map, R.w, R.h, tm, d_dec, G, rx, ry, ra, n,
-                                       wrap, R.di0, R.di1, R.dj0, R.dj1, R.ia, R.ja, g.nx, (unsigned)N, k, cand);
-                else
-                    hipLaunchKernelGGL(k_exhaustive_peaks3<kMaxRadius>, grid, dim3(256), 0, st, map, R.w, R.h, tm, d_dec, G, rx, ry, ra,
-                                       n, wrap, R.di0, R.di1, R.dj0, R.dj1, R.ia, R.ja, g.nx, (unsigned)N, k, cand);
-                FDCM_HIP(hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_exhaustive_merge_groups, dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, st,
-                               (const unsigned long long*)cand, d_seg, n_groups, lpu, k, d_best);
-            FDCM_HIP(hipGetLastError());
-        }
-    }
-    std::vector<unsigned long long> best((size_t)TA * k);
-    FDCM_HIP(hipMemcpyAsync(best.data(), d_best, best.size() * 8, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
-    emit_rotation_records(best, k, index, M, n, g, base, out, n_out);
+    search(fm, P, n, g, k, rx, ry, ra, wrap, best, index);
+    emit_records(best, k, index, n, g, base, M.data(), out, n_out);
 }
 
 }  // namespace fdcm

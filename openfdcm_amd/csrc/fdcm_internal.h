@@ -163,6 +163,7 @@ struct fdcm_featuremap {
     fdcm::DevBuf s_tail;    // device tail (penalise + sort + top k) workspace
     fdcm::DevBuf s_tail_out; // the k best of the device tail before their download
     fdcm::DevBuf s_eval;    // fdcm_featuremap_evaluate / _minmax_translation: lines, translations, work items, results
+    fdcm::PinnedBuf s_eval_stage;  // host side of the exhaustive search's uploads
     std::mutex seam_mutex;  // .. which the reference's optimisers call from pool threads on one feature map (batchoptimize.cpp:102-110):
                             // the two calls share s_eval and the stream, so they take turns
     int64_t last_n_out = 0; // matches of the last host-output search, still in s_out

@@ -186,7 +186,7 @@ def test_grid_split_into_regions(built_pair, ragged):
     tset = DeviceTemplates([tmpls[5], tmpls[12], tmpls[20]])
     rx, ry = 5, 3
     ny = 4096
-    dx = (768 << 20) // 4 // (ny + 2 * ry) - 2 * rx  # region width of the library's rule
+    dx = (768 << 20) // 4 // (2048 + 2 * ry) - 2 * rx  # region width of the library's rule: strips of 2048 rows
     x0, y0 = -dx, -2000  # the cut at grid column dx is the translation x = 0, inside every box
     big = (x0, y0, dx + 200, ny, 1, 1)
     assert big[2] * big[3] > (768 << 20) // 4
