@@ -644,7 +644,8 @@ __global__ void __launch_bounds__(256) k_integral(const float* __restrict__ src,
 }
 
 // ------------------------------------------------------------------------------------------ driver
-static void ensure_timing(fdcm_featuremap* fm) {
+void ensure_stream(fdcm_featuremap* fm) {
+    if (!fm->stream) FDCM_HIP(hipStreamCreateWithFlags(&fm->stream, hipStreamNonBlocking));
     if (fm->timing.created) return;
     for (auto& e : fm->timing.ev) FDCM_HIP(hipEventCreate(&e));
     fm->timing.created = true;
@@ -657,82 +658,97 @@ void sweep_order_counts(int64_t* from_history, int64_t* from_proxy) {
     *from_proxy = g_order_from_proxy.load();
 }
 
-void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after, bool reserve_only) {
-    const auto t0 = std::chrono::steady_clock::now();
-    FDCM_HIP(hipSetDevice(fm->device));
-    if (!fm->stream) FDCM_HIP(hipStreamCreateWithFlags(&fm->stream, hipStreamNonBlocking));
-    ensure_timing(fm);
-    finish_build(fm);  // the previous build's staging and events are reused below
-    hipStream_t st = fm->stream;
-    // A reservation only grows buffers: the handle's geometry, the plan offsets of its last build and the sweep's cost
-    // history stay as they are (restored where the function returns early for it); its content survives unless a volume
-    // buffer had to grow, and the cost history unless the scratch that holds it did.
-    const long kept_cost_chunks = fm->k2_cost_chunks;
-    const int kept_cost_w = fm->k2_cost_w;
-    const void* const kept_stack = fm->stack.p;
-    const bool kept_v1 = fm->vol1_interleaved;
-    const size_t kept_off[6] = {fm->off_raster, fm->off_prop, fm->off_integral, fm->off_keys, fm->off_slice, fm->off_cost};
-    if (!reserve_only) {
-        fm->W = plan.W; fm->H = plan.H; fm->m = plan.m; fm->tx = plan.tx; fm->ty = plan.ty;
-        fm->keys = plan.keys;
-        fm->last_build = fdcm_build_timing{};
-    }
-    if (plan.m == 0 || plan.W == 0) return;
-    const int W = (int)plan.W, H = (int)plan.H, m = (int)plan.m;
-    if (plan.W > 16384 || plan.H > 16384) throw std::string("feature size above 16384 is not supported");  // 32-bit byte offsets inside a slice
-    const int HW64 = (H + 63) / 64;
-    const size_t npix = (size_t)W * H, nvox = npix * m;
-    const long ncols = (long)m * W;
-    fm->vol.reserve(std::max(nvox, (size_t)m * ivol_slice_floats(W, H)) * sizeof(float));  // the integrated volume comes back here, interleaved
-    if (HW64 > 64) fm->bitmap.reserve((size_t)ncols * HW64 * 8);  // (feature sizes above 4096 only: k_seeds + k_coldesc)
-    // every buffer of the build is reserved here, before the first kernel is queued: an allocation between two stages
-    // (a handle's first build) stalls the host for 0.5 - 1 ms while the GPU idles inside the stage events' span
-    if (stop_after >= 2) fm->ivol.reserve((size_t)m * ivol_slice_floats(W, H) * sizeof(float));
-    if (stop_after >= 3) fm->offtab.reserve((size_t)m * sh_tab_stride(W) * sizeof(int));
-    const long nchunks = (long)m * HW64;  // (slice, 64-row chunk) pairs
+BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after) {
+    const int64_t W = plan.W, H = plan.H, m = plan.m;
+    BuildLayout L;
+    L.empty = m == 0 || W == 0;
+    if (!L.empty && (W > 16384 || H > 16384)) throw std::string("feature size above 16384 is not supported");  // 32-bit byte offsets inside a slice
+    const int HW64 = L.empty ? 0 : (int)((H + 63) / 64);
+    L.HW64 = HW64; L.nchunks = (long)m * HW64;
+    // the plan blob (its proxy cost region is only uploaded when the sweep's launch order takes it)
+    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    L.off_prop = align16(plan.raster.size() * sizeof(RasterLine));
+    L.off_integral = L.off_prop + align16(plan.prop.size() * sizeof(PropStep));
+    L.off_keys = L.off_integral + align16(plan.integral.size() * sizeof(IntegralDesc));
+    L.off_slice = L.off_keys + align16(plan.keys.size() * sizeof(float));
+    L.off_cost = L.off_slice + align16(plan.slice_first.size() * sizeof(int32_t));
+    L.plan = L.off_cost + align16((size_t)L.nchunks * sizeof(int32_t));
+    if (L.empty) return L;
+    const size_t ncols = (size_t)m * W, islices = (size_t)m * ivol_slice_floats(W, H);
+    L.vol = islices * sizeof(float);  // the transforms, and later the integrated volume, interleaved (>= m W H floats)
+    if (HW64 > 64) L.bitmap = ncols * HW64 * 8;        // (feature sizes above 4096 only: k_seeds + k_coldesc)
+    if (stop_after >= 2) L.ivol = islices * sizeof(float);
+    if (stop_after >= 3) L.offtab = (size_t)m * sh_tab_stride((int)W) * sizeof(int);
+    L.coldesc = ncols * HW64 * sizeof(ColDesc);
+    L.colmask = (size_t)m * ((W + 63) / 64) * 8;
     // Which L2 / L2^2 sweep: ranges of equal column count, merged (fdcm_sweep.hip) where every value of the pass is an exact
     // integer, the literal pass one wave per chunk (fdcm_sweep_literal.hip) otherwise.  FDCM_L2_SWEEP=literal is the tests'
     // switch for the latter at every size.
     static const bool env_literal = getenv("FDCM_L2_SWEEP") != nullptr && std::strcmp(getenv("FDCM_L2_SWEEP"), "literal") == 0;
-    const bool l2 = fm->distance != FDCM_L1;
-    const bool balanced = l2 && HW64 <= 64 && sweep_balanced_applies(W, H) && !env_literal;
-    fm->vol1_interleaved = true;  // every sweep writes the transforms in the interleaved layout (ivol_index) the propagation reads
-    fm->coldesc.reserve((size_t)ncols * HW64 * sizeof(ColDesc));
-    fm->colmask.reserve((size_t)m * ((W + 63) / 64) * 8);
+    const bool l2 = distance != FDCM_L1;
+    L.balanced = l2 && HW64 <= 64 && sweep_balanced_applies(W, H) && !env_literal;
+    if (!l2) {
+        L.stack = (size_t)m * HW64 * ((W + 63) / 64) * 64 * sizeof(float2);  // the L1 pass's minima / carries
+    } else if (!L.balanced) {
+        L.stack = sweep_literal_scratch_bytes((int)W, L.nchunks);
+    } else {
+        // scratch of the balanced sweep, row-major: stack entries (W + 2 slots per row, 12 B), owner list (W + 2 entries per
+        // row, 8 B), launch order, per-chunk cost and the steal counter
+        L.slots = (int)W + 2;
+        const size_t NRr = (size_t)L.nchunks * 64;
+        auto take = [&](size_t bytes) { const size_t o = L.stack; L.stack += (bytes + 255) & ~(size_t)255; return o; };
+        L.o_ent = take(L.slots * NRr * sizeof(EnvEntry)), L.o_own = take(L.slots * NRr * sizeof(OwnEntry));
+        L.o_ord = take((size_t)L.nchunks * 4), L.o_cost = take((size_t)L.nchunks * 4), L.o_steals = take(256);
+    }
+    return L;
+}
+
+void reserve_build(fdcm_featuremap* fm, const BuildLayout& L) {
+    FDCM_HIP(hipSetDevice(fm->device));
+    ensure_stream(fm);
+    finish_build(fm);  // the previous build's staging and events are reused by the next
+    if (L.empty) return;
+    // every buffer of the build is reserved before its first kernel is queued: an allocation between two stages (a
+    // handle's first build) stalls the host for 0.5 - 1 ms while the GPU idles inside the stage events' span
+    fm->vol.reserve(L.vol); fm->bitmap.reserve(L.bitmap); fm->ivol.reserve(L.ivol); fm->offtab.reserve(L.offtab);
+    fm->coldesc.reserve(L.coldesc); fm->colmask.reserve(L.colmask);
+    const void* stack_before = fm->stack.p;
+    fm->stack.reserve(L.stack);
+    if (fm->stack.p != stack_before) { fm->k2_cost_chunks = 0; fm->steals_off = 0; }  // a new scratch: no cost table, no steal counter
+    fm->stage.reserve(L.plan); fm->plan.reserve(L.plan);
+}
+
+void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const BuildLayout L = build_layout(plan, fm->distance, stop_after);
+    reserve_build(fm, L);
+    fm->W = plan.W; fm->H = plan.H; fm->m = plan.m; fm->tx = plan.tx; fm->ty = plan.ty;
+    fm->keys = plan.keys;
+    fm->last_build = fdcm_build_timing{};
+    if (L.empty) return;
+    hipStream_t st = fm->stream;
+    const int W = (int)plan.W, H = (int)plan.H, m = (int)plan.m, HW64 = L.HW64;
+    const long ncols = (long)m * W, nchunks = L.nchunks;
     SweepBuf sb{};
     bool proxy_order = false;
     std::vector<int32_t> proxy_cost;
-    int* order_dst = nullptr;
-    if (fm->distance == FDCM_L1) {
-        fm->stack.reserve((size_t)m * HW64 * ((W + 63) / 64) * 64 * sizeof(float2));  // the L1 pass's minima / carries
-    } else if (!balanced) {
-        fm->stack.reserve(sweep_literal_scratch_bytes(W, nchunks));
-        fm->k2_cost_chunks = 0;
+    char* sp = (char*)fm->stack.p;
+    if (!L.balanced) {  // the L1 minima or the literal pass's scratch take the whole of `stack`
+        fm->k2_cost_chunks = 0; fm->steals_off = 0;
     } else {
-        // scratch of the balanced sweep, row-major: stack entries (W + 2 slots per row, 12 B), owner list (W + 2 entries per
-        // row, 8 B), launch order and per-chunk cost
-        const size_t NRr = (size_t)nchunks * 64, slots = (size_t)W + 2;
-        size_t off = 0;
-        auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-        const size_t o_ent = take(slots * NRr * sizeof(EnvEntry)), o_own = take(slots * NRr * sizeof(OwnEntry));
-        const size_t o_ord = take((size_t)nchunks * 4), o_cost = take((size_t)nchunks * 4), o_steals = take(256);
-        const void* stack_before = fm->stack.p;
-        fm->stack.reserve(off);
-        char* sp = (char*)fm->stack.p;
         // Launch order: workgroups are dispatched in index order, and when there are more of them than the GPU holds at once
         // (two per CU) the long ones must not start last.  Nothing cheap predicts a chunk's time well enough, the previous
         // build of the same shape does: scenes of a stream change little from frame to frame.  A handle's first build, and
         // every build after a change of size, takes the host's proxy per chunk (make_build_plan), which arrives with the plan.
         static const bool env_order = getenv("FDCM_SWEEP_ORDER") != nullptr;  // the tests' switch: the launch order at every size
         const bool want_order = env_order || nchunks > 2L * device_cus(fm->device);
-        const bool have_cost = want_order && fm->k2_cost_chunks == nchunks && fm->k2_cost_w == W && stack_before == fm->stack.p;
-        proxy_order = want_order && !have_cost && !reserve_only;
+        const bool have_cost = want_order && fm->k2_cost_chunks == nchunks && fm->k2_cost_w == W;
+        proxy_order = want_order && !have_cost;
         if (proxy_order) sweep_cost_proxy(plan, proxy_cost);
-        if (have_cost && !reserve_only) launch_sweep_order(st, (const int*)(sp + o_cost), (int)nchunks, (int*)(sp + o_ord));
-        order_dst = (int*)(sp + o_ord);
-        sb.ent = (EnvEntry*)(sp + o_ent); sb.own = (OwnEntry*)(sp + o_own);
-        sb.order = (have_cost || proxy_order) ? (const int*)(sp + o_ord) : nullptr;
-        sb.cost = (int*)(sp + o_cost);
+        if (have_cost) launch_sweep_order(st, (const int*)(sp + L.o_cost), (int)nchunks, (int*)(sp + L.o_ord));
+        sb.ent = (EnvEntry*)(sp + L.o_ent); sb.own = (OwnEntry*)(sp + L.o_own);
+        sb.order = (have_cost || proxy_order) ? (const int*)(sp + L.o_ord) : nullptr;
+        sb.cost = (int*)(sp + L.o_cost);
         // Dynamic cuts (a wave out of columns begins a new range in what nobody has started): they shorten the heaviest
         // workgroup's chain and add junctions, i.e. work -- worth it where the kernel lasts as long as its slowest workgroup
         // (all workgroups resident at once, the GPU to this handle), not where workgroups queue for the CUs or frames of a
@@ -740,51 +756,31 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after, bool 
         // 68.4 M matches/s; config 3: 0.76 -> 0.81 ms).  FDCM_SWEEP_STEAL=<blocks> forces a threshold (0: never) for the tests.
         sb.steal_min = -1;  // the kernel's default threshold
         sb.steal_heavy_only = (!fm->shares_gpu && nchunks <= 2L * device_cus(fm->device)) ? 0 : 1;
-        sb.steals = (int*)(sp + o_steals);
-        if (!reserve_only) {
-            if (fm->sweep_steals != sb.steals) FDCM_HIP(hipMemsetAsync(sp + o_steals, 0, 256, st));  // a new scratch (or shape): count from 0
-            fm->sweep_steals = sb.steals;
-        }
-        sb.eslots = (int)slots; sb.lslots = (int)slots;
+        sb.steals = (int*)(sp + L.o_steals);
+        if (fm->steals_off != L.o_steals) FDCM_HIP(hipMemsetAsync(sb.steals, 0, 256, st));  // a new scratch (or shape): count from 0
+        fm->steals_off = L.o_steals;
+        sb.eslots = L.slots; sb.lslots = L.slots;
         sb.colmask = (const unsigned long long*)fm->colmask.p;
         fm->k2_cost_chunks = nchunks; fm->k2_cost_w = W;
     }
 
     // ---- plan upload: one pinned blob, one async copy
-    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    fm->off_raster = 0;
-    fm->off_prop = align16(plan.raster.size() * sizeof(RasterLine));
-    fm->off_integral = fm->off_prop + align16(plan.prop.size() * sizeof(PropStep));
-    fm->off_keys = fm->off_integral + align16(plan.integral.size() * sizeof(IntegralDesc));
-    fm->off_slice = fm->off_keys + align16(plan.keys.size() * sizeof(float));
-    fm->off_cost = fm->off_slice + align16(plan.slice_first.size() * sizeof(int32_t));
-    const size_t blob = fm->off_cost + ((proxy_order || reserve_only) ? align16((size_t)nchunks * sizeof(int32_t)) : 0);
-    fm->stage.reserve(blob);
-    fm->plan.reserve(blob);
-    if (reserve_only) {  // every buffer a build of this plan's shape takes is in place; nothing was queued
-        fm->off_raster = kept_off[0]; fm->off_prop = kept_off[1]; fm->off_integral = kept_off[2];
-        fm->off_keys = kept_off[3]; fm->off_slice = kept_off[4]; fm->off_cost = kept_off[5];
-        fm->vol1_interleaved = kept_v1;
-        if (fm->stack.p == kept_stack) { fm->k2_cost_chunks = kept_cost_chunks; fm->k2_cost_w = kept_cost_w; }
-        else fm->k2_cost_chunks = 0;  // (a new scratch: its cost table holds nothing yet)
-        return;
-    }
+    fm->off_keys = L.off_keys;
     if (sb.order) (proxy_order ? g_order_from_proxy : g_order_from_history).fetch_add(1, std::memory_order_relaxed);
     char* hs = (char*)fm->stage.p;
-    if (!plan.raster.empty()) std::memcpy(hs + fm->off_raster, plan.raster.data(), plan.raster.size() * sizeof(RasterLine));
-    std::memcpy(hs + fm->off_prop, plan.prop.data(), plan.prop.size() * sizeof(PropStep));
-    std::memcpy(hs + fm->off_integral, plan.integral.data(), plan.integral.size() * sizeof(IntegralDesc));
-    std::memcpy(hs + fm->off_keys, plan.keys.data(), plan.keys.size() * sizeof(float));
-    std::memcpy(hs + fm->off_slice, plan.slice_first.data(), plan.slice_first.size() * sizeof(int32_t));
-    if (proxy_order) std::memcpy(hs + fm->off_cost, proxy_cost.data(), proxy_cost.size() * sizeof(int32_t));
-    FDCM_HIP(hipMemcpyAsync(fm->plan.p, hs, blob, hipMemcpyHostToDevice, st));
-    if (proxy_order) launch_sweep_order(st, (const int*)((const char*)fm->plan.p + fm->off_cost), (int)nchunks, order_dst);
-    fm->n_raster = (int64_t)plan.raster.size();
-    fm->n_prop = (int64_t)plan.prop.size();
+    if (!plan.raster.empty()) std::memcpy(hs + L.off_raster, plan.raster.data(), plan.raster.size() * sizeof(RasterLine));
+    std::memcpy(hs + L.off_prop, plan.prop.data(), plan.prop.size() * sizeof(PropStep));
+    std::memcpy(hs + L.off_integral, plan.integral.data(), plan.integral.size() * sizeof(IntegralDesc));
+    std::memcpy(hs + L.off_keys, plan.keys.data(), plan.keys.size() * sizeof(float));
+    std::memcpy(hs + L.off_slice, plan.slice_first.data(), plan.slice_first.size() * sizeof(int32_t));
+    if (proxy_order) std::memcpy(hs + L.off_cost, proxy_cost.data(), proxy_cost.size() * sizeof(int32_t));
+    FDCM_HIP(hipMemcpyAsync(fm->plan.p, hs, proxy_order ? L.plan : L.off_cost, hipMemcpyHostToDevice, st));
+    if (proxy_order) launch_sweep_order(st, (const int*)((const char*)fm->plan.p + L.off_cost), (int)nchunks, (int*)(sp + L.o_ord));
+    const int n_raster = (int)plan.raster.size(), n_prop = (int)plan.prop.size();
     const char* dp = (const char*)fm->plan.p;
-    const RasterLine* d_raster = (const RasterLine*)(dp + fm->off_raster);
-    const PropStep* d_prop = (const PropStep*)(dp + fm->off_prop);
-    const IntegralDesc* d_int = (const IntegralDesc*)(dp + fm->off_integral);
+    const RasterLine* d_raster = (const RasterLine*)(dp + L.off_raster);
+    const PropStep* d_prop = (const PropStep*)(dp + L.off_prop);
+    const IntegralDesc* d_int = (const IntegralDesc*)(dp + L.off_integral);
     float* vol = fm->vol.as<float>();
     hipEvent_t* ev = fm->timing.ev;
 
@@ -796,7 +792,7 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after, bool 
     if (HW64 <= 64) {
         // the tile kernel rasterises the seeds of its columns itself (LDS): no bitmap, no k_seeds, no stage of its own
         fm->seeds_fused = true;
-        const int* d_first = (const int*)(dp + fm->off_slice);
+        const int* d_first = (const int*)(dp + L.off_slice);
         const int XT = HW64 > 32 ? 32 : 64;
         const dim3 grid((unsigned)((W + XT - 1) / XT), (unsigned)m);
         const size_t lds = (size_t)HW64 * (XT + 1) * sizeof(uint4) + (size_t)HW64 * XT * 8;
@@ -808,8 +804,8 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after, bool 
         fm->seeds_fused = false;
         const long bitmap_words = ncols * HW64;
         FDCM_HIP(hipMemsetAsync(fm->bitmap.p, 0, (size_t)bitmap_words * 8, st));
-        if (fm->n_raster > 0)
-            hipLaunchKernelGGL(k_seeds, dim3((unsigned)fm->n_raster), dim3(256), 0, st, d_raster,
+        if (n_raster > 0)
+            hipLaunchKernelGGL(k_seeds, dim3((unsigned)n_raster), dim3(256), 0, st, d_raster,
                                fm->bitmap.as<unsigned long long>(), W, H, HW64);
         if (fm->stage_events) FDCM_HIP(hipEventRecord(ev[1], st));
         hipLaunchKernelGGL(k_coldesc, dim3((unsigned)((ncols + 3) / 4)), dim3(256), 0, st,
@@ -824,7 +820,7 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after, bool 
         hipLaunchKernelGGL(k_l1_word_mins, dim3((unsigned)((wwaves + 3) / 4)), dim3(256), 0, st, d_desc, mins, W, HW64, nwords, wwaves);
         hipLaunchKernelGGL(k_l1_carries, dim3((unsigned)(((long)m * HW64 * 64 + 255) / 256)), dim3(256), 0, st, mins, nwords, (long)m * HW64 * 64);
         hipLaunchKernelGGL(k_l1_word, dim3((unsigned)((wwaves + 3) / 4)), dim3(256), 0, st, d_desc, (const float2*)mins, vol, W, H, HW64, nwords, wwaves);
-    } else if (balanced) {
+    } else if (L.balanced) {
 #ifdef FDCM_LAB
         if (!lab_skip("sweep"))
 #endif
@@ -836,10 +832,9 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after, bool 
     const bool want_sqrt = fm->distance == FDCM_L2;
     if (stop_after >= 2) {
         const size_t nq = ivol_slice_floats(W, H);
-        fm->ivol.reserve((size_t)m * nq * sizeof(float));
         float* ivol = fm->ivol.as<float>();
         const unsigned pblocks = (unsigned)((nq + 255) / 256);
-        const int sq = (want_sqrt ? 1 : 0) | (fm->vol1_interleaved ? 2 : 0);
+        const int sq = (want_sqrt ? 1 : 0) | 2;  // (2: the sweeps write the transforms interleaved)
 #ifdef FDCM_LAB
         if (lab_skip("propagate")) {} else
 #endif
@@ -855,17 +850,16 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after, bool 
             if (lds > 64 * 1024)
                 FDCM_HIP(hipFuncSetAttribute((const void*)k_propagate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(k_propagate, dim3((unsigned)((nq + bd - 1) / bd)), dim3(bd), lds, st, (const float*)vol, ivol, W, H, m,
-                               d_prop, (int)fm->n_prop, sq);
+                               d_prop, n_prop, sq);
         }
     } else if (want_sqrt) {
-        const size_t nel = fm->vol1_interleaved ? (size_t)m * ivol_slice_floats(W, H) : nvox;  // (padding elements: harmless)
+        const size_t nel = (size_t)m * ivol_slice_floats(W, H);  // (padding elements: harmless)
         hipLaunchKernelGGL(k_sqrt, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, vol, nel);
     }
     if (fm->stage_events) FDCM_HIP(hipEventRecord(ev[4], st));
     if (stop_after >= 3) {
         const int chains = 2 * (W > H ? W : H);
         const int tab_stride = sh_tab_stride(W);
-        fm->offtab.reserve((size_t)m * tab_stride * sizeof(int));
         int* d_tab = fm->offtab.as<int>();
         if (!(fm->off_m == m && fm->off_steps == W)) {  // the table only depends on the keys (fixed per handle) and the size
             hipLaunchKernelGGL(k_groups, dim3((unsigned)((tab_stride + 255) / 256), (unsigned)m), dim3(256), 0, st, d_int, d_tab, W, tab_stride);

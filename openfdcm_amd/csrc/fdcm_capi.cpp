@@ -54,12 +54,14 @@ static void require(bool ok, const char* msg) {
 }
 
 static void upload_keys_only(fdcm_featuremap* fm) {
-    // feature maps adopted from caller slices carry no build plan: keep the keys where search expects them
-    fm->off_keys = 0;
-    const size_t bytes = std::max<size_t>(16, fm->keys.size() * sizeof(float));
-    fm->plan.reserve(bytes);
+    // feature maps adopted from caller slices carry no build plan: the keys go where a plan's keys would be (the search reads them there)
+    BuildPlan keys_only;
+    keys_only.W = fm->W; keys_only.H = fm->H; keys_only.m = fm->m; keys_only.keys = fm->keys;
+    const BuildLayout L = build_layout(keys_only, fm->distance, 3);
+    fm->off_keys = L.off_keys;
+    fm->plan.reserve(std::max<size_t>(16, L.plan));
     if (!fm->keys.empty())
-        FDCM_HIP(hipMemcpy(fm->plan.p, fm->keys.data(), fm->keys.size() * sizeof(float), hipMemcpyHostToDevice));
+        FDCM_HIP(hipMemcpy((char*)fm->plan.p + fm->off_keys, fm->keys.data(), fm->keys.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
 static void destroy(fdcm_featuremap* fm) {
@@ -840,11 +842,11 @@ int fdcm_selftest_sweep_steals(fdcm_featuremap* fm, int64_t* count) {
     return guarded([&] {
         require(fm && count, "null argument");
         *count = 0;
-        if (!fm->sweep_steals) return;
+        if (!fm->steal_counter()) return;
         finish_build(fm);
         FDCM_HIP(hipSetDevice(fm->device));
         int v = 0;
-        FDCM_HIP(hipMemcpy(&v, fm->sweep_steals, sizeof(int), hipMemcpyDeviceToHost));
+        FDCM_HIP(hipMemcpy(&v, fm->steal_counter(), sizeof(int), hipMemcpyDeviceToHost));
         *count = v;
     });
 }

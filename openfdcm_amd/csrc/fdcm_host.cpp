@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
+#include <stdexcept>
 #include <unordered_map>
 
 #include "fdcm_internal.h"
@@ -15,8 +16,18 @@ static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 const char* last_error_cstr() { return g_last_error.c_str(); }
 
+static thread_local bool g_no_grow = false;
+NoGrowScope::NoGrowScope() { g_no_grow = true; }
+NoGrowScope::~NoGrowScope() { g_no_grow = false; }
+static void check_growth(size_t cap, size_t bytes) {
+    if (g_no_grow)
+        throw std::logic_error("internal error: a buffer of " + std::to_string(cap) + " bytes would grow to " + std::to_string(bytes) +
+                               " bytes inside a frame whose memory was reserved before it");
+}
+
 void DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return;
+    check_growth(cap, bytes);
     release();
     FDCM_HIP(hipMalloc(&p, bytes));
     cap = bytes;
@@ -28,6 +39,7 @@ void DevBuf::release() {
 }
 void PinnedBuf::reserve(size_t bytes) {
     if (bytes <= cap) return;
+    check_growth(cap, bytes);
     release();
     FDCM_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
     cap = bytes;

@@ -36,6 +36,10 @@ struct PinnedBuf {
     void reserve(size_t bytes);
     void release();
 };
+// While a thread holds a NoGrowScope, a DevBuf / PinnedBuf reserve that would have to grow throws (std::logic_error)
+// instead of allocating.  The sharded engine's slot workers run their frames inside one: every allocation of a frame
+// happens on the caller's thread before the workers get it (fdcm_sharded.cpp, submit_frame).
+struct NoGrowScope { NoGrowScope(); ~NoGrowScope(); };
 
 // ---------------------------------------------------------------- build plan (host -> device)
 // One clipped scene line to rasterise (drawLines, drawing.h:111-125).  Each axis is either a
@@ -75,6 +79,18 @@ struct BuildPlan {
     std::vector<LineBox> boxes;       // the clipped lines' bounding boxes (what sweep_cost_proxy works from)
 };
 
+// Every size and offset (bytes) a build of one shape takes: reserve_build sizes the buffers from it, run_build takes its
+// offsets from it.  A size of 0: the build does not use that buffer.
+struct BuildLayout {
+    bool empty = true;      // no slices or no pixels: nothing to build
+    bool balanced = false;  // the L2 / L2^2 sweep of equal column ranges (fdcm_sweep.hip); the literal one otherwise (L2 builds)
+    int HW64 = 0, slots = 0;  // 64-row chunks per column; stack and owner entries per row of the balanced sweep
+    long nchunks = 0;       // (slice, 64-row chunk) pairs
+    size_t vol = 0, ivol = 0, bitmap = 0, coldesc = 0, colmask = 0, offtab = 0, stack = 0;
+    size_t o_ent = 0, o_own = 0, o_ord = 0, o_cost = 0, o_steals = 0;  // inside `stack` (balanced sweep)
+    // plan blob: RasterLine[] | PropStep[] | IntegralDesc[] | keys[] | slice_first[] | per-chunk proxy cost[]
+    size_t off_raster = 0, off_prop = 0, off_integral = 0, off_keys = 0, off_slice = 0, off_cost = 0, plan = 0;
+};
 // Host side of buildCpuFeaturemap (dt3cpu.h:174-198 + the scalar parts of :227-231).
 void make_build_plan(const float* lines, int64_t n, int64_t depth, float coeff, float padding, BuildPlan& plan);
 // per (slice, 64-row chunk): a proxy of the L2 sweep's time, for the launch order of a build without history
@@ -119,7 +135,7 @@ struct fdcm_featuremap {
     int64_t depth_param = 0;
     float coeff = 0, padding = 0;
     int distance = 0;
-    int* sweep_steals = nullptr;  // device counter inside `stack`: ranges the L2 sweep's waves took over so far (fdcm_selftest_sweep_steals)
+    size_t steals_off = 0;  // offset in `stack` of the counter of ranges the L2 sweep's waves took over so far (0: none; fdcm_selftest_sweep_steals)
     long k2_cost_chunks = 0; int k2_cost_w = 0;  // the L2 sweep's per-chunk costs in `stack` are those of a build with this shape
     int off_m = 0, off_steps = 0;  // the group table in `offtab` is valid for this depth and feature width
     bool build_pending = false;  // the last build is queued on `stream` but has not been waited for
@@ -139,20 +155,19 @@ struct fdcm_featuremap {
     // `ivol` and writes its sums back into `vol`, interleaved -- which is what the search gathers from.
     fdcm::DevBuf vol;      // max(m*W*H, m*ivol_slice_floats) floats
     fdcm::DevBuf ivol;     // m*ivol_slice_floats floats
-    bool vol1_interleaved = false;  // the transforms of the last build (stage 1) are in the interleaved layout: segmented L2 sweep
     int vol_stage = 0;     // what the handle holds: 1 = transforms (vol; staged test builds), 2 = propagated
                            // (ivol, interleaved; staged test builds), 3 = integrated (vol, interleaved): complete
     const float* current() const { return vol_stage == 2 ? ivol.as<float>() : vol.as<float>(); }
-    bool current_interleaved() const { return vol_stage >= 2 || (vol_stage == 1 && vol1_interleaved); }
+    bool current_interleaved() const { return vol_stage >= 1; }  // (every sweep writes the transforms interleaved)
     fdcm::DevBuf bitmap;   // m*W*ceil(H/64) uint64 seed bits along y
     fdcm::DevBuf coldesc;  // m*ceil(H/64)*W column-chunk descriptors (16 B)
     fdcm::DevBuf colmask;  // m*ceil(W/64) words: the seeded columns of every slice (k_coldesc_tile, for the L2 sweep)
     fdcm::DevBuf offtab;   // per slice: one word per group of 4 columns for the shallow sweeps of the line integral (k_groups)
     fdcm::DevBuf stack;    // K2 scratch: per row a (v, f, z) stack of W entries
-    fdcm::DevBuf plan;     // RasterLine[] | PropStep[] | IntegralDesc[] | keys[]
+    int* steal_counter() const { return steals_off ? (int*)((char*)stack.p + steals_off) : nullptr; }
+    fdcm::DevBuf plan;     // the last build's plan (BuildLayout), or the keys of an adopted volume
     fdcm::PinnedBuf stage; // host staging for the plan
-    size_t off_raster = 0, off_prop = 0, off_integral = 0, off_keys = 0, off_slice = 0, off_cost = 0;
-    int64_t n_raster = 0, n_prop = 0;
+    size_t off_keys = 0;   // where the keys are in `plan` (the search reads them there)
     // search workspaces
     fdcm::DevBuf s_scene;   // scene lines + sorted lengths + sorted idx
     fdcm::DevBuf s_pairs;   // (template line, scene line) per search combination
@@ -189,9 +204,12 @@ struct fdcm_templates {
 
 namespace fdcm {
 // implemented in fdcm_build.hip
-// reserve_only: size every buffer a build of this plan takes and queue nothing (the handle keeps its geometry, its plan
-// offsets and the sweep's cost history; its content too unless a volume buffer had to grow)
-void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after, bool reserve_only = false);
+void ensure_stream(fdcm_featuremap* fm);  // the handle's stream and timing events, made on first use (on fm's device)
+BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after);  // from the plan's shape and counts
+// grows the handle's buffers to the layout and queues nothing (its geometry, plan offsets and content stay; a scratch that
+// had to move drops the sweep's cost history and steal counter)
+void reserve_build(fdcm_featuremap* fm, const BuildLayout& L);
+void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after);
 // Waits for a queued build (if any) and fills fm->last_build.  run_build only queues the kernels: the search
 // that follows is ordered behind them on the same stream and its host-side preparation runs meanwhile.
 void finish_build(fdcm_featuremap* fm);
@@ -201,7 +219,7 @@ int64_t search_capacity(const fdcm_templates* t, int64_t n_scene, int64_t maxT, 
 void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene, int64_t n_scene, int64_t maxT,
                 int64_t maxS, int optimizer, int64_t batch, int32_t base, fdcm_match* out_device, fdcm_match** out_host,
                 int64_t* n_out);
-// sizes the search's workspaces for this template set and scene size, queues nothing (run_search reserves the same sizes)
+// sizes the search's workspaces for this template set and scene size, queues nothing
 void reserve_search(fdcm_featuremap* fm, const fdcm_templates* t, int64_t n_scene, int64_t maxT, int64_t maxS);
 // the searches of this process take the candidates' orientation bins from the host libm (decided once: see fdcm.h)
 bool orientation_bins_on_host();
@@ -227,6 +245,8 @@ void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* ma
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);
 void run_topk_device(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
                      int penalty, float tau, int64_t k, fdcm_match* out_device);
+// sizes run_topk_device's workspaces for T templates and n matches (at most), queues nothing
+void reserve_topk(fdcm_featuremap* fm, int64_t T, int64_t n);
 // records to the host without a copy command (a kernel writes into the mapped pinned destination); queued on st
 void records_to_host(hipStream_t st, const fdcm_match* src_device, int64_t n, fdcm_match* dst_pinned);
 // the valid records of n_blocks fixed-capacity blocks (count in the trailing record) into a pooled pinned array; waits for st

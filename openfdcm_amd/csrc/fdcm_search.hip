@@ -618,17 +618,48 @@ __global__ void __launch_bounds__(1024) k_compact(const fdcm_match* __restrict__
     }
 }
 
-int64_t search_capacity(const fdcm_templates* t, int64_t n_scene, int64_t maxT, int64_t maxS) {
-    int64_t total = 0;
+// Every limit, offset and size (bytes) of a search of this template set and scene size, in one place: search_capacity,
+// reserve_search and run_search take them from here.
+struct SearchLayout {
+    int64_t maxT = 0, maxS = 0;  // the limits as the search applies them (the scene window is maxS lines)
+    std::vector<long long> coff;  // candidate offsets per template (T + 1)
+    int64_t cpt_max = 0, ncand = 0, pairs_stride = 0;  // candidates of the largest template, of all; pair slots per template
+    int nchunks = 0;  // compaction chunks of kChunk candidates
+    size_t o_lines = 0, o_len = 0, o_idx = 0, o_coff = 0, scene = 0;  // s_scene: lines | sorted lengths | sorted idx | coff
+    size_t records = 0, flags = 0, counters = 64, pairs = 0, work_list = 0, work = 0, bins = 0, out = 0;
+};
+static SearchLayout search_layout(const fdcm_templates* t, int64_t n_scene, int64_t maxT, int64_t maxS) {
+    SearchLayout L;
     // the reference takes size_t limits and applies min(tmpl.cols(), maxTmplLines) / min(scene, maxSceneLines)
     // (defaultsearch.cpp:38, defaultsearch.h:42-46): "all lines" values such as 2^40 are legal
-    maxT = std::min<int64_t>(std::max<int64_t>(maxT, 0), std::max<int64_t>(t->max_lines, 0));
-    const int64_t window = std::min<int64_t>(std::max<int64_t>(maxS, 0), n_scene);
+    L.maxT = std::min<int64_t>(std::max<int64_t>(maxT, 0), std::max<int64_t>(t->max_lines, 0));
+    L.maxS = std::min<int64_t>(std::max<int64_t>(maxS, 0), n_scene);
+    L.coff.assign((size_t)t->T + 1, 0);
     for (int64_t i = 0; i < t->T; ++i) {
         const int64_t nt = t->offsets[i + 1] - t->offsets[i];
-        total += 2 * std::min<int64_t>(nt, maxT) * window;
+        const int64_t c = 2 * std::min<int64_t>(nt, L.maxT) * L.maxS;
+        L.coff[i + 1] = L.coff[i] + c;
+        L.cpt_max = std::max(L.cpt_max, c);
     }
-    return total;
+    L.ncand = L.coff[t->T];
+    L.nchunks = (int)((L.ncand + kChunk - 1) / kChunk);
+    L.pairs_stride = L.maxT * L.maxS;
+    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t n_s = (size_t)n_scene, ncand = (size_t)L.ncand;
+    L.o_len = align16(n_s * 16), L.o_idx = L.o_len + align16(n_s * 4), L.o_coff = L.o_idx + align16(n_s * 4);
+    L.scene = L.o_coff + align16(L.coff.size() * 8);
+    L.records = ncand * sizeof(fdcm_match);
+    L.flags = 2 * (ncand + (size_t)L.nchunks) * sizeof(int);  // valid flags, per-chunk counts and evaluation sums
+    L.pairs = std::max<size_t>(16, (size_t)t->T * (size_t)L.pairs_stride * sizeof(int2));
+    L.work_list = align16(ncand / 2 * sizeof(int2));  // the work list, then two histograms of kWorkBins
+    L.work = L.work_list + 2 * (size_t)kWorkBins * sizeof(int);
+    L.bins = ncand * (size_t)std::max<int64_t>(1, t->max_lines) * sizeof(unsigned short);
+    L.out = (ncand + 1) * sizeof(fdcm_match);  // host output: the counters ride in one record behind the candidates
+    return L;
+}
+
+int64_t search_capacity(const fdcm_templates* t, int64_t n_scene, int64_t maxT, int64_t maxS) {
+    return search_layout(t, n_scene, maxT, maxS).ncand;
 }
 
 bool orientation_bins_on_host() {
@@ -644,32 +675,21 @@ bool orientation_bins_on_host() {
     return on_host;
 }
 
-// The workspaces run_search takes, sized for (template set, scene size, window): the same expressions, nothing queued.
+// every workspace of the search but its output (s_out / s_cnt, which depend on where the matches go)
+static void reserve_workspaces(fdcm_featuremap* fm, const SearchLayout& L, bool host_bins) {
+    fm->s_stage.reserve(L.scene); fm->s_scene.reserve(L.scene);
+    fm->s_records.reserve(L.records); fm->s_flags.reserve(L.flags); fm->s_counter.reserve(L.counters);
+    fm->s_pairs.reserve(L.pairs); fm->s_work.reserve(L.work);
+    if (host_bins) { fm->s_bins_stage.reserve(L.bins); fm->s_bins.reserve(L.bins); }
+}
+
 void reserve_search(fdcm_featuremap* fm, const fdcm_templates* t, int64_t n_scene, int64_t maxT, int64_t maxS) {
     if (!t || t->T == 0 || n_scene <= 0) return;
     FDCM_HIP(hipSetDevice(fm->device));
-    maxT = std::min<int64_t>(std::max<int64_t>(maxT, 0), std::max<int64_t>(t->max_lines, 0));
-    maxS = std::min<int64_t>(std::max<int64_t>(maxS, 0), n_scene);
-    const int64_t ncand = search_capacity(t, n_scene, maxT, maxS);
-    if (ncand == 0) return;
-    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t n_s = (size_t)n_scene;
-    const size_t blob = align16(n_s * 16) + 2 * align16(n_s * 4) + align16(((size_t)t->T + 1) * 8);
-    const int nchunks = (int)((ncand + kChunk - 1) / kChunk);
-    fm->s_stage.reserve(blob);
-    fm->s_scene.reserve(blob);
-    fm->s_records.reserve((size_t)ncand * sizeof(fdcm_match));
-    fm->s_flags.reserve(2 * ((size_t)ncand + (size_t)nchunks) * sizeof(int));
-    fm->s_counter.reserve(64);
-    fm->s_cnt.reserve(64);
-    const size_t pairs_stride = (size_t)(maxT * maxS);
-    fm->s_pairs.reserve(std::max<size_t>(16, (size_t)t->T * pairs_stride * sizeof(int2)));
-    fm->s_work.reserve((((size_t)(ncand / 2) * sizeof(int2) + 15) & ~(size_t)15) + 2 * (size_t)kWorkBins * sizeof(int));
-    if (orientation_bins_on_host()) {
-        const size_t stride = (size_t)std::max<int64_t>(1, t->max_lines);
-        fm->s_bins_stage.reserve((size_t)ncand * stride * sizeof(unsigned short));
-        fm->s_bins.reserve((size_t)ncand * stride * sizeof(unsigned short));
-    }
+    const SearchLayout L = search_layout(t, n_scene, maxT, maxS);
+    if (L.ncand == 0) return;
+    reserve_workspaces(fm, L, orientation_bins_on_host());
+    fm->s_cnt.reserve(L.counters);  // (the device-output searches of the sharded engine)
 }
 
 void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene, int64_t n_scene, int64_t maxT,
@@ -687,17 +707,12 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     // parity is defined against the box's own libm, as the reference's would be.  FDCM_FORCE_HOST_BINS=1 forces it.
     const bool host_bins_needed = orientation_bins_on_host();
     FDCM_HIP(hipSetDevice(fm->device));
-    if (!fm->stream) FDCM_HIP(hipStreamCreateWithFlags(&fm->stream, hipStreamNonBlocking));
-    if (!fm->timing.created) {
-        for (auto& e : fm->timing.ev) FDCM_HIP(hipEventCreate(&e));
-        fm->timing.created = true;
-    }
+    ensure_stream(fm);
     hipStream_t st = fm->stream;
     const int n_s = (int)n_scene;
-    // Clamp the limits before any cast or sizing: the reference takes size_t and applies min() (defaultsearch.cpp:38,
-    // defaultsearch.h:42-46), so DefaultSearch(10**12, 10**12) means "all lines".
-    maxT = std::min<int64_t>(std::max<int64_t>(maxT, 0), std::max<int64_t>(t->max_lines, 0));
-    maxS = std::min<int64_t>(std::max<int64_t>(maxS, 0), n_scene);
+    // the limits are clamped before any cast: DefaultSearch(10**12, 10**12) means "all lines"
+    const SearchLayout L = search_layout(t, n_scene, maxT, maxS);
+    maxT = L.maxT; maxS = L.maxS;
     const int window = (int)maxS;
     // ---- scene side of establishSearchStrategy (defaultsearch.cpp:32-36): lengths, argsort by
     // descending length with std::sort (same comparator and index type as the reference)
@@ -709,16 +724,8 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     std::vector<long> sidx((size_t)n_s);
     std::iota(sidx.begin(), sidx.end(), 0);
     std::sort(sidx.begin(), sidx.end(), [&slen](long const i1, long const i2) { return slen[i1] > slen[i2]; });
-    // candidate offsets per template
-    std::vector<long long> coff((size_t)t->T + 1, 0);
-    int64_t cpt_max = 0;
-    for (int64_t i = 0; i < t->T; ++i) {
-        const int64_t nt = t->offsets[i + 1] - t->offsets[i];
-        const int64_t c = 2 * std::min<int64_t>(nt, maxT) * window;
-        coff[i + 1] = coff[i] + c;
-        cpt_max = std::max(cpt_max, c);
-    }
-    const long long ncand = coff[t->T];
+    const std::vector<long long>& coff = L.coff;
+    const long long ncand = L.ncand;
     fm->last_search.candidates = ncand;
     if (ncand == 0) return;
     // ---- every check that can refuse the search, before the first command is queued (a refusal must not leave an upload
@@ -732,17 +739,13 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     if (lds > 160 * 1024) throw std::string("scene/template too large for the search kernel's LDS staging");
     if (host_bins_needed && fm->m > 65535) throw std::string("host-side orientation bins need depth <= 65535");
     // ---- stage + upload: scene lines | sorted lengths | sorted idx | candidate offsets
-    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_lines = 0, o_len = align16((size_t)n_s * 16), o_idx = o_len + align16((size_t)n_s * 4),
-                 o_coff = o_idx + align16((size_t)n_s * 4), blob = o_coff + align16(coff.size() * 8);
-    fm->s_stage.reserve(blob);
-    fm->s_scene.reserve(blob);
+    reserve_workspaces(fm, L, host_bins_needed);
     char* hs = (char*)fm->s_stage.p;
-    std::memcpy(hs + o_lines, scene, (size_t)n_s * 16);
-    float* hl = (float*)(hs + o_len);
-    int* hi = (int*)(hs + o_idx);
+    std::memcpy(hs + L.o_lines, scene, (size_t)n_s * 16);
+    float* hl = (float*)(hs + L.o_len);
+    int* hi = (int*)(hs + L.o_idx);
     for (int i = 0; i < n_s; ++i) { hl[i] = slen[sidx[i]]; hi[i] = (int)sidx[i]; }
-    std::memcpy(hs + o_coff, coff.data(), coff.size() * 8);
+    std::memcpy(hs + L.o_coff, coff.data(), coff.size() * 8);
     // The search's preparation (scene upload, k_pairs, the work list) needs nothing of the volume: on a handle that has the GPU
     // to itself it goes to a second stream, beside the kernels of a build that is still running on `st` (a blocking
     // rebuild -> search spends ~25 us less); k_search waits for it through an event.  A slot of a frame pipeline keeps one
@@ -755,11 +758,8 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
         }
         sp = fm->prep_stream;
     }
-    FDCM_HIP(hipMemcpyAsync(fm->s_scene.p, hs, blob, hipMemcpyHostToDevice, sp));
-    const int nchunks = (int)((ncand + kChunk - 1) / kChunk);
-    fm->s_records.reserve((size_t)ncand * sizeof(fdcm_match));
-    fm->s_flags.reserve(2 * ((size_t)ncand + (size_t)nchunks) * sizeof(int));
-    fm->s_counter.reserve(64);
+    FDCM_HIP(hipMemcpyAsync(fm->s_scene.p, hs, L.scene, hipMemcpyHostToDevice, sp));
+    const int nchunks = L.nchunks;
     // keys live at the end of the build plan blob; for adopted volumes they are uploaded there too
     SearchParams P{};
     P.vol = fm->vol.as<float>();
@@ -771,17 +771,17 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     P.tsorted = t->d_sorted.as<int>();
     P.T = (int)t->T;
     const char* ds = (const char*)fm->s_scene.p;
-    P.slines = (const float*)(ds + o_lines);
-    P.s_sorted_len = (const float*)(ds + o_len);
-    P.s_sorted_idx = (const int*)(ds + o_idx);
+    P.slines = (const float*)(ds + L.o_lines);
+    P.s_sorted_len = (const float*)(ds + L.o_len);
+    P.s_sorted_idx = (const int*)(ds + L.o_idx);
     P.n_s = n_s;
     P.maxT = (int)maxT; P.maxS = (int)maxS; P.window = window;
     P.optimizer = optimizer;
     P.batch = (int)B;
     P.win = win;
     P.base = base;
-    P.cand_offsets = (const long long*)(ds + o_coff);
-    P.bpt = (int)((cpt_max + kWavesPerBlock - 1) / kWavesPerBlock);
+    P.cand_offsets = (const long long*)(ds + L.o_coff);
+    P.bpt = (int)((L.cpt_max + kWavesPerBlock - 1) / kWavesPerBlock);
     P.ncand = ncand;
     static const int env_xcd_parts = getenv("FDCM_SEARCH_XCD_PARTS") ? atoi(getenv("FDCM_SEARCH_XCD_PARTS")) : 0;  // tuning override, read once
     P.xcd_parts = env_xcd_parts;
@@ -790,8 +790,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     P.flags = fm->s_flags.as<int>();
     P.evals = P.flags + ncand + nchunks;
     P.counters = fm->s_counter.as<unsigned long long>();
-    P.pairs_stride = (int)(maxT * window);
-    fm->s_pairs.reserve(std::max<size_t>(16, (size_t)t->T * P.pairs_stride * sizeof(int2)));
+    P.pairs_stride = (int)L.pairs_stride;
     P.pairs = fm->s_pairs.as<int2>();
     // volumes below 4 GB (every BASELINE config but 5) are addressed through one buffer descriptor with 32-bit offsets
     static const bool env_flat = getenv("FDCM_SEARCH_FLAT") != nullptr;  // measurement: 64-bit flat addresses always
@@ -806,12 +805,10 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     const long long n_slots = (long long)t->T * P.pairs_stride;
     static const bool no_worklist = getenv("FDCM_SEARCH_TEMPLATE_MAJOR") != nullptr;  // tuning override
     if (!no_worklist && n_slots <= 0x7fffffffll) {
-        const size_t work_bytes = ((size_t)(ncand / 2) * sizeof(int2) + 15) & ~(size_t)15;
-        fm->s_work.reserve(work_bytes + 2 * (size_t)kWorkBins * sizeof(int));
         if (n_slots <= kWlSlotsPerBlock) {
             hipLaunchKernelGGL(k_worklist, dim3(1), dim3(1024), 0, sp, P, n_slots, fm->s_work.as<int2>());
         } else {
-            int* ghist = (int*)((char*)fm->s_work.p + work_bytes);
+            int* ghist = (int*)((char*)fm->s_work.p + L.work_list);
             int* cursor = ghist + kWorkBins;
             const unsigned nb = (unsigned)((n_slots + kWlSlotsPerBlock - 1) / kWlSlotsPerBlock);
             FDCM_HIP(hipMemsetAsync(ghist, 0, (size_t)kWorkBins * sizeof(int), sp));
@@ -831,8 +828,6 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     }
     if (host_bins_needed) {
         const size_t stride = (size_t)P.lds_lines;
-        fm->s_bins_stage.reserve((size_t)ncand * stride * sizeof(unsigned short));
-        fm->s_bins.reserve((size_t)ncand * stride * sizeof(unsigned short));
         unsigned short* hb = (unsigned short*)fm->s_bins_stage.p;
         const float* keys = fm->keys.data();
         const int mkeys = (int)fm->m;
@@ -911,7 +906,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     if (!dst) {
         // host output: one extra record behind the candidates' capacity carries the counters, so that the
         // matches and their count come back with a single copy
-        fm->s_out.reserve((size_t)(ncand + 1) * sizeof(fdcm_match));
+        fm->s_out.reserve(L.out);
         dst = fm->s_out.as<fdcm_match>();
         P.counters = reinterpret_cast<unsigned long long*>(dst + ncand);
     }
@@ -927,7 +922,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
         FDCM_HIP(hipHostGetDevicePointer((void**)&host_out, *out_host, 0));
         host_cnt = reinterpret_cast<unsigned long long*>(host_out + ncand);
     } else {
-        fm->s_cnt.reserve(64);
+        fm->s_cnt.reserve(L.counters);
         FDCM_HIP(hipHostGetDevicePointer((void**)&host_cnt, fm->s_cnt.p, 0));
     }
     static const bool env_two_step = getenv("FDCM_SEARCH_COMPACT2") != nullptr;  // the tests' switch: the two-kernel form at every size

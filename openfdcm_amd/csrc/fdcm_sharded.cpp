@@ -188,23 +188,20 @@ int guarded_s(F&& f) {
     }
 }
 
-// rebuild -> search on one slot of one shard; top-k mode adds the device tail.  Never throws: whatever goes wrong is
-// recorded in the slot (a worker thread has nobody to throw to).
+// rebuild -> search on one slot of one shard; top-k mode adds the device tail.  Every buffer the frame takes was reserved
+// by reserve_slot: the frame runs in a NoGrowScope.  Never throws: whatever goes wrong is recorded in the slot (a worker
+// thread has nobody to throw to).
 void run_slot_frame(fdcm_sharded* s, Shard& sh, FrameSlot& fs) {
     fs.rc = FDCM_OK; fs.n = 0; fs.send_from = nullptr; fs.error.clear();
     const Job& j = fs.job;
     const int rc = guarded_s([&] {
+        NoGrowScope no_allocations;
         auto ok = [&](int r) { if (r != FDCM_OK) throw std::string(fdcm_last_error()); };
         const float* scene = j.scene.data();
-        ok(fs.fm ? fdcm_featuremap_rebuild(fs.fm, scene, j.n_scene)
-                 : fdcm_featuremap_build(scene, j.n_scene, s->depth, s->coeff, s->padding, s->distance, &fs.fm));
+        ok(fdcm_featuremap_rebuild(fs.fm, scene, j.n_scene));  // (reserve_slot made the handle)
         fs.fm->shares_gpu = s->n_slots > 1;  // (tunes the next builds of this slot)
         const fdcm_templates* tset = j.whole ? sh.full : sh.tset;
         const int32_t base = j.whole ? 0 : (int32_t)sh.begin;
-        int64_t cap = 0;
-        ok(fdcm_search_capacity(tset, j.n_scene, j.maxT, j.maxS, &cap));
-        FDCM_HIP(hipSetDevice(sh.device));
-        fs.block.reserve(std::max<size_t>(32, (size_t)cap * sizeof(fdcm_match)));
         int64_t n = 0;
         ok(fdcm_search_device(fs.fm, tset, scene, j.n_scene, j.maxT, j.maxS, j.optimizer, j.batch, base,
                               fs.block.as<fdcm_match>(), &n));
@@ -214,7 +211,6 @@ void run_slot_frame(fdcm_sharded* s, Shard& sh, FrameSlot& fs) {
         fs.send_from = fs.block.as<fdcm_match>();
         if (j.topk) {
             const int64_t kk = std::min<int64_t>(std::max<int64_t>(j.k, 0), n);
-            fs.best.reserve(std::max<size_t>(32, (size_t)kk * sizeof(fdcm_match)));
             fdcm::run_topk_device(fs.fm, tset, fs.block.as<fdcm_match>(), n, base, j.penalty, j.tau, kk,
                                   fs.best.as<fdcm_match>());
             fs.n = kk;
@@ -289,8 +285,8 @@ void start_workers(fdcm_sharded* s, int n_slots) {
 }
 
 // Sizes the device memory of slot `si` of one shard for the frame: the record buffers take the frame's search capacity, the
-// slot's feature map every buffer its build and its search will ask for (reservations only: nothing is built or queued, and
-// a scene that cannot be built still fails where it always did -- in the frame, reported by its wait).
+// slot's feature map every buffer its build, its search and its top-k tail will ask for (reservations only: nothing is built
+// or queued, and a scene that cannot be built still fails where it always did -- in the frame, reported by its wait).
 void reserve_slot(fdcm_sharded* s, Shard& sh, size_t si, const Job& job) {
     FrameSlot& fs = *sh.slots[si];
     const fdcm_templates* tset = job.whole ? sh.full : sh.tset;
@@ -305,8 +301,9 @@ void reserve_slot(fdcm_sharded* s, Shard& sh, size_t si, const Job& job) {
     try {
         BuildPlan plan;
         make_build_plan(job.scene.data(), s->depth > 0 ? job.n_scene : 0, s->depth, s->coeff, s->padding, plan);
-        run_build(fs.fm, plan, 3, /*reserve_only=*/true);
+        reserve_build(fs.fm, build_layout(plan, fs.fm->distance, 3));
         reserve_search(fs.fm, tset, job.n_scene, job.maxT, job.maxS);
+        if (job.topk && cap > 0) reserve_topk(fs.fm, tset->T, cap);
     } catch (const std::string&) {  // e.g. a feature size the build rejects: the frame reports it
     } catch (const HipError&) {     // an allocation that failed: the frame's own build asks again and reports it
         (void)hipGetLastError();
@@ -329,8 +326,9 @@ int64_t submit_frame(fdcm_sharded* s, Job&& job) {
     if (s->slot_ticket[ei] >= 0) throw std::string("every frame slot holds a frame that has not been waited for");
     // Device memory of the slot is sized HERE, on the caller's thread, before its workers get the frame: an allocation is a
     // device-wide synchronisation, and the caller's thread is also the one that runs the exchange of earlier frames (in
-    // wait) -- so an allocation can never race a grouped send/recv in flight.  A later frame with a larger feature size or
-    // more scene lines grows the buffers here the same way.
+    // wait) -- so an allocation can never race a grouped send/recv in flight (the workers' NoGrowScope turns one that was
+    // missed here into the frame's error).  A later frame with a larger feature size or more scene lines grows the buffers
+    // here the same way.
     if (s->mode == FDCM_SHARD_FRAMES) {  // the whole frame on one device, the whole template list
         job.whole = true;
         Shard& sh = s->shards[s->shard_of(t)];

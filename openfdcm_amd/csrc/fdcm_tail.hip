@@ -95,6 +95,31 @@ void blocks_to_host(hipStream_t st, const void* blocks_device, int32_t n_blocks,
     *n_out = total;
 }
 
+// The device tail's workspaces for T templates, n matches and the k best, in one place (bytes): s_tail holds the penalty's
+// denominators, sort keys and indices (in and out), penalised scores and rocPRIM's radix-sort scratch; s_stage the
+// denominators' staging; s_tail_out the k best before their download (run_topk).
+struct TailLayout { size_t o_den = 0, o_keys, o_keys2, o_idx, o_idx2, o_ps, o_tmp, tmp_bytes = 0, tail, stage, out; };
+static TailLayout tail_layout(int64_t T, int64_t n, int64_t k) {
+    TailLayout L;
+    auto a256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t n4 = a256((size_t)n * 4);
+    L.o_keys = a256((size_t)T * 4), L.o_keys2 = L.o_keys + n4, L.o_idx = L.o_keys2 + n4, L.o_idx2 = L.o_idx + n4;
+    L.o_ps = L.o_idx2 + n4, L.o_tmp = L.o_ps + n4;
+    // (a size query: rocPRIM queues nothing without scratch; it grows with n)
+    FDCM_HIP(rocprim::radix_sort_pairs(nullptr, L.tmp_bytes, (const unsigned*)nullptr, (unsigned*)nullptr,
+                                       (const unsigned*)nullptr, (unsigned*)nullptr, (size_t)n, 0, 32));
+    L.tail = L.o_tmp + L.tmp_bytes + 256;
+    L.stage = std::max<size_t>(16, (size_t)T * 4);
+    L.out = (size_t)k * sizeof(fdcm_match);
+    return L;
+}
+
+void reserve_topk(fdcm_featuremap* fm, int64_t T, int64_t n) {
+    FDCM_HIP(hipSetDevice(fm->device));
+    const TailLayout L = tail_layout(T, n, 0);
+    fm->s_tail.reserve(L.tail); fm->s_stage.reserve(L.stage);
+}
+
 // The k best of n device-resident matches, penalised, into out_device (k <= n, both on fm's device); returns when
 // the records are complete.
 void run_topk_device(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
@@ -105,38 +130,33 @@ void run_topk_device(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_ma
     if (k <= 0) return;
     if (k > n) throw std::string("k exceeds the number of matches");
     if (n > 0x7fffffffll) throw std::string("more than 2^31 matches are not supported by the device tail");
+    const TailLayout L = tail_layout(t->T, n, k);
+    fm->s_tail.reserve(L.tail);
+    char* d = (char*)fm->s_tail.p;
     // ---- denominators on the host (getTemplateLengths + the penalty's formula), uploaded through pinned staging
     const bool pen = penalty >= 0;
-    const size_t a256 = 255;
-    const size_t o_den = 0, o_keys = ((size_t)t->T * 4 + a256) & ~a256, o_keys2 = o_keys + (((size_t)n * 4 + a256) & ~a256),
-                 o_idx = o_keys2 + (((size_t)n * 4 + a256) & ~a256), o_idx2 = o_idx + (((size_t)n * 4 + a256) & ~a256),
-                 o_ps = o_idx2 + (((size_t)n * 4 + a256) & ~a256), o_tmp = o_ps + (((size_t)n * 4 + a256) & ~a256);
-    size_t tmp_bytes = 0;
-    FDCM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (const unsigned*)nullptr, (unsigned*)nullptr,
-                                       (const unsigned*)nullptr, (unsigned*)nullptr, (size_t)n, 0, 32, st));
-    fm->s_tail.reserve(o_tmp + tmp_bytes + 256);
-    char* d = (char*)fm->s_tail.p;
     if (pen) {
         std::vector<float> len((size_t)t->T);
         if (t->T) {
             if (fdcm_templates_lengths(t, len.data()) != FDCM_OK) throw std::string(fdcm_last_error());
         }
-        fm->s_stage.reserve(std::max<size_t>(16, (size_t)t->T * 4));
+        fm->s_stage.reserve(L.stage);
         float* hd = (float*)fm->s_stage.p;
         for (int64_t i = 0; i < t->T; ++i) {
             const float l = std::max(len[(size_t)i], 1e-6f);
             hd[i] = penalty == FDCM_DEFAULT_PENALTY ? l : std::pow(l, tau);
         }
-        if (t->T) FDCM_HIP(hipMemcpyAsync(d + o_den, hd, (size_t)t->T * 4, hipMemcpyHostToDevice, st));
+        if (t->T) FDCM_HIP(hipMemcpyAsync(d + L.o_den, hd, (size_t)t->T * 4, hipMemcpyHostToDevice, st));
     }
     const unsigned nb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_tail_keys, dim3(nb), dim3(256), 0, st, matches_device, (long long)n,
-                       pen ? (const float*)(d + o_den) : nullptr, (int)base, (int)t->T, (unsigned*)(d + o_keys),
-                       (unsigned*)(d + o_idx), (float*)(d + o_ps));
-    FDCM_HIP(rocprim::radix_sort_pairs(d + o_tmp, tmp_bytes, (const unsigned*)(d + o_keys), (unsigned*)(d + o_keys2),
-                                       (const unsigned*)(d + o_idx), (unsigned*)(d + o_idx2), (size_t)n, 0, 32, st));
+                       pen ? (const float*)(d + L.o_den) : nullptr, (int)base, (int)t->T, (unsigned*)(d + L.o_keys),
+                       (unsigned*)(d + L.o_idx), (float*)(d + L.o_ps));
+    size_t tmp_bytes = L.tmp_bytes;
+    FDCM_HIP(rocprim::radix_sort_pairs(d + L.o_tmp, tmp_bytes, (const unsigned*)(d + L.o_keys), (unsigned*)(d + L.o_keys2),
+                                       (const unsigned*)(d + L.o_idx), (unsigned*)(d + L.o_idx2), (size_t)n, 0, 32, st));
     hipLaunchKernelGGL(k_tail_gather, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, matches_device,
-                       (const unsigned*)(d + o_idx2), (const float*)(d + o_ps), (long long)k, out_device);
+                       (const unsigned*)(d + L.o_idx2), (const float*)(d + L.o_ps), (long long)k, out_device);
     FDCM_HIP(hipGetLastError());
     FDCM_HIP(hipStreamSynchronize(st));
 }
@@ -150,7 +170,7 @@ void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* ma
     k = std::min<int64_t>(std::max<int64_t>(k, 0), n);
     *out = result_acquire(std::max<size_t>(1, (size_t)k) * sizeof(fdcm_match));
     if (k == 0) return;
-    fm->s_tail_out.reserve((size_t)k * sizeof(fdcm_match));
+    fm->s_tail_out.reserve(tail_layout(t->T, n, k).out);
     run_topk_device(fm, t, matches_device, n, base, penalty, tau, k, fm->s_tail_out.as<fdcm_match>());
     records_to_host(fm->stream, fm->s_tail_out.as<fdcm_match>(), k, *out);
     FDCM_HIP(hipStreamSynchronize(fm->stream));

@@ -854,6 +854,58 @@ def test_sharded_engine_slot_keeps_sweep_history_and_survives_a_failed_first_fra
     assert out.returncode == 0 and "sharded history ok" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
 
 
+def test_sharded_engine_topk_frames_that_grow(amd):
+    """Every buffer of a sharded frame is reserved on the caller's thread before the slot workers get the frame, the top-k
+    tail's included; a worker that would grow one fails the frame.  Top-k frames with more scene lines and larger feature
+    sizes than any before them equal fdcm_topk on one device."""
+    from openfdcm_amd import synthetic, _capi
+    from openfdcm_amd.engine import DeviceFeatureMap, DeviceTemplates, ShardedEngine, search_raw, topk
+    tmpls = synthetic.templates(20, 11, 128, 31)
+    eng = ShardedEngine(tmpls, n_devices=1, depth=16, coeff=5.0, padding=1.0, distance=O.L2)
+    tset = DeviceTemplates(tmpls)
+    for S, n_lines, seed in [(128, 12, 61), (128, 40, 62), (256, 60, 63), (512, 90, 64)]:
+        scene = synthetic.scene(S, n_lines, seed)
+        fm = DeviceFeatureMap.build(scene, depth=16, coeff=5.0, padding=1.0, distance=O.L2)
+        search_raw(fm, tset, scene, 4, 4, _capi.BATCH_OPTIMIZE, 10)
+        want = np.array(topk(fm, tset, 25, 1, 1.5), copy=True)
+        got = eng.search_topk(scene, 4, 4, 25, penalty=1, tau=1.5)
+        assert len(want) > 0 and got.tobytes() == want.tobytes(), (S, n_lines)
+    eng.close()
+
+
+def test_sweep_steal_counter_after_the_scratch_moves(amd):
+    """fdcm_selftest_sweep_steals after a rebuild that reallocates the sweep's scratch: a small L2 map takes the balanced
+    sweep, a 3000 x 3000 one (W^2 + H^2 > 2^24) the literal one in a larger scratch.  With FDCM_SWEEP_STEAL=0 (read once per
+    process: a process of its own) no range is ever taken over, so every read is 0."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = f"""
+import ctypes as C, sys
+sys.path.insert(0, {root!r})
+from openfdcm_amd import _capi, synthetic
+from openfdcm_amd.engine import DeviceFeatureMap
+
+def steals(fm):
+    c = C.c_int64(-1)
+    _capi.check(_capi.lib().fdcm_selftest_sweep_steals(fm._h, C.byref(c)))
+    return c.value
+
+fm = DeviceFeatureMap.build(synthetic.scene(256, 40, 5), depth=8, coeff=5.0, padding=1.0, distance=_capi.L2)
+a = steals(fm)
+fm.rebuild(synthetic.scene(3000, 40, 6))
+fm.refresh()
+assert (fm.width, fm.height) == (3000, 3000), (fm.width, fm.height)
+b = steals(fm)
+print("steals", a, b)
+"""
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600,
+                         env={**os.environ, "FDCM_SWEEP_STEAL": "0"})
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "steals 0 0" in out.stdout, out.stdout[-2000:]
+
+
 def test_sharded_engine_leaves_the_callers_device_alone(amd):
     """fdcm_sharded_* switch devices on the caller's thread for allocations and the exchange; the library's
     thread-local device and HIP's current device are what they were when a call returns."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A frame slot of the sharded engine keeps the L2 sweep's launch-order history although its buffers are reserved
-before every frame (fdcm_sharded_submit -> run_build(reserve_only)); and a slot whose first frame cannot be built
+before every frame (fdcm_sharded_submit -> reserve_build); and a slot whose first frame cannot be built
 (feature size above 16384) serves the next frame.  Run with FDCM_SWEEP_ORDER=1 so that these small builds take a launch
 order at all; prints one line per check and exits non-zero on a failure (tests/test_gpu_parity.py)."""
 import ctypes as C
