@@ -385,10 +385,7 @@ __global__ void __launch_bounds__(256) k_propagate_reg(const float* __restrict__
 // Lane rho <-> chain a + sg*(rho - 3), sg = sign(r): lanes 0..2 are the halo (the chains that reach the wave's
 // first rows during a group), lanes 3..60 the 58 chains whose rows the wave stores, lanes 61..63 would fall off
 // the 64-row window after 3 moves and are not used.
-#ifndef FDCM_SHP
-#define FDCM_SHP 12
-#endif
-static constexpr int kShP = FDCM_SHP;                 // groups (loads of 1 KB) in flight per wave
+static constexpr int kShP = 12;                       // groups (loads of 1 KB) in flight per wave
 static constexpr int kShOwn = 58, kShHalo = 3;
 // Table per slice, one word per group in sweep order: 16 * (chain offset round(i r) at the group's first step) |
 // bit j: the chains move between the group's steps j and j+1.  Steps outside the image (the padding columns of
@@ -624,16 +621,6 @@ __global__ void __launch_bounds__(256) k_integral(const float* __restrict__ src,
     // tiles against straight 1 KB streams), so mixing them over the launch overlaps them.
     const int k = (int)(((long)blockIdx.y * kstride) % (long)gridDim.y);
     const IntegralDesc d = desc[k];
-#ifdef FDCM_LAB
-    // lab builds, FDCM_INT_ONLY=shallow|steep: only that class of slices runs (PMC traffic per class: tools/int_split.sh);
-    // the flag rides in kstride's upper bits
-    const int only = kstride >> 24;
-    kstride &= 0xffffff;
-    const int k2 = (int)(((long)blockIdx.y * kstride) % (long)gridDim.y);
-    const IntegralDesc d2 = desc[k2];
-    if (only && d2.mode != only) return;
-    if (only) { if (d2.mode == 1) integral_shallow(src, dst, W, H, d2, k2, tab, shw); else integral_steep<XC>(src, dst, W, H, d2, k2, lds_tiles); return; }
-#endif
     if (d.mode == 1) integral_shallow(src, dst, W, H, d, k, tab, shw);
     else if (d.mode == 2) integral_steep<XC>(src, dst, W, H, d, k, lds_tiles);
     else {  // nothing to integrate (imgproc.h:43): the slice moves as it is
@@ -682,11 +669,9 @@ BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after) {
     L.coldesc = ncols * HW64 * sizeof(ColDesc);
     L.colmask = (size_t)m * ((W + 63) / 64) * 8;
     // Which L2 / L2^2 sweep: ranges of equal column count, merged (fdcm_sweep.hip) where every value of the pass is an exact
-    // integer, the literal pass one wave per chunk (fdcm_sweep_literal.hip) otherwise.  FDCM_L2_SWEEP=literal is the tests'
-    // switch for the latter at every size.
-    static const bool env_literal = getenv("FDCM_L2_SWEEP") != nullptr && std::strcmp(getenv("FDCM_L2_SWEEP"), "literal") == 0;
+    // integer, the literal pass one wave per chunk (fdcm_sweep_literal.hip) otherwise.
     const bool l2 = distance != FDCM_L1;
-    L.balanced = l2 && HW64 <= 64 && sweep_balanced_applies(W, H) && !env_literal;
+    L.balanced = l2 && HW64 <= 64 && sweep_balanced_applies(W, H) && !test_switches().literal_sweep;
     if (!l2) {
         L.stack = (size_t)m * HW64 * ((W + 63) / 64) * 64 * sizeof(float2);  // the L1 pass's minima / carries
     } else if (!L.balanced) {
@@ -740,8 +725,7 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
         // (two per CU) the long ones must not start last.  Nothing cheap predicts a chunk's time well enough, the previous
         // build of the same shape does: scenes of a stream change little from frame to frame.  A handle's first build, and
         // every build after a change of size, takes the host's proxy per chunk (make_build_plan), which arrives with the plan.
-        static const bool env_order = getenv("FDCM_SWEEP_ORDER") != nullptr;  // the tests' switch: the launch order at every size
-        const bool want_order = env_order || nchunks > 2L * device_cus(fm->device);
+        const bool want_order = test_switches().sweep_order || nchunks > 2L * device_cus(fm->device);
         const bool have_cost = want_order && fm->k2_cost_chunks == nchunks && fm->k2_cost_w == W;
         proxy_order = want_order && !have_cost;
         if (proxy_order) sweep_cost_proxy(plan, proxy_cost);
@@ -821,9 +805,6 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
         hipLaunchKernelGGL(k_l1_carries, dim3((unsigned)(((long)m * HW64 * 64 + 255) / 256)), dim3(256), 0, st, mins, nwords, (long)m * HW64 * 64);
         hipLaunchKernelGGL(k_l1_word, dim3((unsigned)((wwaves + 3) / 4)), dim3(256), 0, st, d_desc, (const float2*)mins, vol, W, H, HW64, nwords, wwaves);
     } else if (L.balanced) {
-#ifdef FDCM_LAB
-        if (!lab_skip("sweep"))
-#endif
         launch_sweep_balanced(st, d_desc, vol, W, H, HW64, nchunks, sb);
     } else {
         launch_sweep_literal(st, d_desc, vol, W, H, HW64, nchunks, fm->stack.p);
@@ -835,9 +816,6 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
         float* ivol = fm->ivol.as<float>();
         const unsigned pblocks = (unsigned)((nq + 255) / 256);
         const int sq = (want_sqrt ? 1 : 0) | 2;  // (2: the sweeps write the transforms interleaved)
-#ifdef FDCM_LAB
-        if (lab_skip("propagate")) {} else
-#endif
         if (m == 30) hipLaunchKernelGGL(k_propagate_reg<30>, dim3(pblocks), dim3(256), 0, st, (const float*)vol, ivol, W, H, d_prop, sq);
         else if (m == 60) hipLaunchKernelGGL(k_propagate_reg<60>, dim3(pblocks), dim3(256), 0, st, (const float*)vol, ivol, W, H, d_prop, sq);
         else if (m == 90) hipLaunchKernelGGL(k_propagate_reg<90>, dim3(pblocks), dim3(256), 0, st, (const float*)vol, ivol, W, H, d_prop, sq);
@@ -867,11 +845,9 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
         }
         int shw = (long)m * ((chains + kShOwn - 1) / kShOwn) > 8192 ? 4 : 1;  // working waves per workgroup of a shallow slice
         // steep slices: 60 own chains per block while the launch is small, 124 / 252 once such blocks would outnumber
-        // what the GPU holds several times over (fewer columns read twice; see integral_steep).  FDCM_INT_XC=64|128|256 is
-        // the tests' switch (the wide forms are only selected by large volumes).
-        static const int env_int_xc = [] { const char* e = getenv("FDCM_INT_XC"); const int v = e ? atoi(e) : 0; return (v == 64 || v == 128 || v == 256) ? v : 0; }();
+        // what the GPU holds several times over (fewer columns read twice; see integral_steep).
         const long narrow_blocks = (long)m * ((chains + 59) / 60), cus = device_cus(fm->device);
-        const int xc = env_int_xc ? env_int_xc : (narrow_blocks > 64 * cus ? 256 : (narrow_blocks > 12 * cus ? 128 : 64));
+        const int xc = test_switches().int_xc ? test_switches().int_xc : (narrow_blocks > 64 * cus ? 256 : (narrow_blocks > 12 * cus ? 128 : 64));
         const dim3 igrid((unsigned)((chains + kShOwn - 1) / kShOwn), (unsigned)m);
         int kstride = 1;
         // slices are visited in a strided order (coprime to the depth, near half of it) so that steep and shallow ones
@@ -883,10 +859,6 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
             kstride = m / 2 + 1;
             while (gcd(kstride, m) != 1) ++kstride;
         }
-#ifdef FDCM_LAB
-        static const int env_int_only = [] { const char* e = getenv("FDCM_INT_ONLY"); return !e ? 0 : (!std::strcmp(e, "shallow") ? 1 : (!std::strcmp(e, "steep") ? 2 : 0)); }();
-        kstride |= env_int_only << 24;
-#endif
 #define FDCM_INTEGRAL(XC)                                                                                                        \
         do {                                                                                                                     \
             constexpr size_t lds = integral_lds_bytes<XC>();                                                                     \
@@ -896,9 +868,6 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
             hipLaunchKernelGGL(k_integral<XC>, igrid, dim3(256), lds, st, (const float*)fm->ivol.as<float>(), vol, W, H, d_int,  \
                                d_tab, shw, kstride);                                                               \
         } while (0)
-#ifdef FDCM_LAB
-        if (lab_skip("integral")) {} else
-#endif
         if (xc == 256) FDCM_INTEGRAL(256); else if (xc == 128) FDCM_INTEGRAL(128); else FDCM_INTEGRAL(64);
 #undef FDCM_INTEGRAL
     }

@@ -850,6 +850,6 @@ int fdcm_selftest_sweep_steals(fdcm_featuremap* fm, int64_t* count) {
         *count = v;
     });
 }
-int fdcm_selftest_sweep_ranges(int n_seeded_columns) { return fdcm::sweep_ranges(n_seeded_columns, fdcm::sweep_min_cols()); }
+int fdcm_selftest_sweep_ranges(int n_seeded_columns) { return fdcm::sweep_ranges(n_seeded_columns, fdcm::test_switches().sweep_min_cols); }
 
 }  // extern "C"

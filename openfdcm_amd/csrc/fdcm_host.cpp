@@ -9,12 +9,33 @@
 #include <unordered_map>
 
 #include "fdcm_internal.h"
+#include "fdcm_sweep.h"
 
 namespace fdcm {
 
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 const char* last_error_cstr() { return g_last_error.c_str(); }
+
+const TestSwitches& test_switches() {
+    static const TestSwitches s = [] {
+        auto set = [](const char* name) { return getenv(name) != nullptr; };
+        auto num = [](const char* name, int unset) { const char* e = getenv(name); return e && *e ? atoi(e) : unset; };
+        const char* sweep = getenv("FDCM_L2_SWEEP");
+        TestSwitches r;
+        r.literal_sweep = sweep && std::strcmp(sweep, "literal") == 0;
+        r.sweep_order = set("FDCM_SWEEP_ORDER");
+        const int mc = num("FDCM_SWEEP_MINCOLS", 0), steal = num("FDCM_SWEEP_STEAL", -1), xc = num("FDCM_INT_XC", 0);
+        r.sweep_min_cols = mc >= 1 && mc <= 64 ? mc : kSweepMinCols;
+        r.sweep_steal = steal >= 0 && steal <= kSweepMaxBlocks ? steal : -1;
+        r.int_xc = xc == 64 || xc == 128 || xc == 256 ? xc : 0;
+        r.host_bins = set("FDCM_FORCE_HOST_BINS");
+        r.search_flat = set("FDCM_SEARCH_FLAT");
+        r.search_compact2 = set("FDCM_SEARCH_COMPACT2");
+        return r;
+    }();
+    return s;
+}
 
 static thread_local bool g_no_grow = false;
 NoGrowScope::NoGrowScope() { g_no_grow = true; }

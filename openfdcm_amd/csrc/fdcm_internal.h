@@ -22,6 +22,28 @@ struct HipError { hipError_t code; const char* what; int line; };
         if (e__ != hipSuccess) throw ::fdcm::HipError{e__, #call, __LINE__};        \
     } while (0)
 
+// ---------------------------------------------------------------- the tests' switches
+// Environment variables that make the library take, at the tests' small sizes, a path that only other sizes or other hosts
+// select.  test_switches() (fdcm_host.cpp) reads and checks them once per process; nothing else reads the environment.
+// An unset or invalid switch leaves the default.
+//   FDCM_L2_SWEEP=literal      the literal L2 sweep, one wave per chunk, at every size (build_layout)
+//   FDCM_SWEEP_ORDER           the L2 sweep's launch order from a cost table at every size (run_build)
+//   FDCM_SWEEP_MINCOLS=1..64   seeded columns a sweep range holds at least, instead of 16 (launch_sweep_balanced)
+//   FDCM_SWEEP_STEAL=0..128    the sweep's dynamic cuts on every workgroup, in unclaimed stretches of at least this many
+//                              blocks; 0: never (launch_sweep_balanced)
+//   FDCM_INT_XC=64|128|256     the steep line integral's chains per workgroup (run_build)
+//   FDCM_FORCE_HOST_BINS       the candidates' orientation bins from the host libm (orientation_bins_on_host)
+//   FDCM_SEARCH_FLAT           the search with 64-bit flat addresses (run_search)
+//   FDCM_SEARCH_COMPACT2       the search's two-kernel compaction at every size (run_search)
+struct TestSwitches {
+    bool literal_sweep, sweep_order;
+    int sweep_min_cols;  // 16 unless forced
+    int sweep_steal;     // -1: not forced
+    int int_xc;          // 0: not forced
+    bool host_bins, search_flat, search_compact2;
+};
+const TestSwitches& test_switches();
+
 // ---------------------------------------------------------------- device buffers (grow-only)
 struct DevBuf {
     void* p = nullptr;
@@ -112,10 +134,8 @@ FDCM_HD float lin_spaced_value(int mode, float low, float high, float step, int 
 // gathers read the same place of up to `depth` slices -- with slices a power of two apart they all fall on the same
 // memory channels (config 2': the search kernels took 0.24 - 0.36 ms depending on where the allocation landed,
 // 0.21 - 0.22 ms with the padding; 256 bytes of padding were not enough, 2 to 20 KB all the same).
-#ifndef FDCM_SLICE_PAD
-#define FDCM_SLICE_PAD 1088
-#endif
-FDCM_HD size_t ivol_slice_floats(int64_t W, int64_t H) { return (size_t)((W + 3) / 4) * (size_t)H * 4 + FDCM_SLICE_PAD; }
+static constexpr size_t kSlicePad = 1088;  // floats
+FDCM_HD size_t ivol_slice_floats(int64_t W, int64_t H) { return (size_t)((W + 3) / 4) * (size_t)H * 4 + kSlicePad; }
 FDCM_HD size_t ivol_index(int x, int y, int64_t H) { return ((size_t)(x >> 2) * (size_t)H + (size_t)y) * 4 + (size_t)(x & 3); }
 
 // ---------------------------------------------------------------- handles
@@ -265,11 +285,4 @@ int device_cus(int device);
 // pooled pinned host buffers for match arrays returned to the caller (fdcm_host.cpp)
 fdcm_match* result_acquire(size_t bytes);
 void result_release(fdcm_match* m);
-#ifdef FDCM_LAB
-// lab build: FDCM_LAB_SKIP=sweep,search,.. leaves the named kernels out of every frame (what does each cost the pipeline?)
-inline bool lab_skip(const char* what) {
-    const char* e = getenv("FDCM_LAB_SKIP");
-    return e && std::strstr(e, what) != nullptr;
-}
-#endif
 }  // namespace fdcm

@@ -64,7 +64,6 @@ struct SearchParams {
     const int2* work;               // valid pairs {template, pair slot} grouped by scene line (or null)
     long long ncand;                // candidates in total
     int nblocks;                    // k_search workgroups
-    int xcd_parts;                  // 1: every XCD takes its own contiguous part of the work list
     int lds_lines;                  // capacity (lines) of the LDS template / aligned-line areas
     const unsigned short* host_bins; // [candidate][lds_lines] orientation bins computed with the host libm, or null (see run_search)
     // outputs
@@ -72,15 +71,9 @@ struct SearchParams {
     int* flags;
     int* evals;
     unsigned long long* counters;  // [0] translations evaluated by the rule, [1] unused, [2] matches
-#ifdef FDCM_LAB
-    unsigned long long* lab;  // 8 stamps per candidate (make LAB=1, FDCM_SEARCH_LAB=1)
-#endif
 };
 
-#ifndef FDCM_SEARCH_WPB
-#define FDCM_SEARCH_WPB 4
-#endif
-static constexpr int kWavesPerBlock = FDCM_SEARCH_WPB;
+static constexpr int kWavesPerBlock = 4;
 
 struct OptState {
     VolRef V;        // the integrated volume
@@ -92,15 +85,7 @@ struct OptState {
     unsigned H;
     float tx, ty, savx, savy;
     int lim_p, lim_n;  // multiplier limits: 32 bits are enough, see k_search
-#ifdef FDCM_LAB
-    unsigned long long* lab;
-#endif
 };
-#ifdef FDCM_LAB
-#define SEARCH_STAMP(ptr, i) do { if ((ptr) && (threadIdx.x & 63) == 0) (ptr)[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SEARCH_STAMP(ptr, i) do {} while (0)
-#endif
 
 // Score multipliers k_from, k_from + dir, ... (cnt of them) into sc[dst ..]; with_zero additionally
 // scores translation (0,0) into sc[2 WIN].  32 translations per gather round.
@@ -145,7 +130,6 @@ __device__ __forceinline__ void optimise(const OptState& o, float& best, int& be
         score_range<BUF32>(o, -1, -1, have_n, WIN, false);
     }
     const float init = o.sc[2 * WIN];
-    SEARCH_STAMP(o.lab, 3);
     n_eval += 1;
     best = init;
     float back = init;  // scores.back(): NOT reset between the two directions (batchoptimize.cpp:73)
@@ -346,11 +330,9 @@ __global__ void __launch_bounds__(1024) k_wl_scatter(const SearchParams P, long 
     }
 }
 
-#ifndef FDCM_SEARCH_WPE
-#define FDCM_SEARCH_WPE 4
-#endif
+static constexpr int kSearchWavesPerEU = 4;  // waves per SIMD that k_search's registers must allow (__launch_bounds__)
 template <bool BUF32>
-__global__ void __launch_bounds__(64 * kWavesPerBlock, FDCM_SEARCH_WPE) k_search(const SearchParams P) {
+__global__ void __launch_bounds__(64 * kWavesPerBlock, kSearchWavesPerEU) k_search(const SearchParams P) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int t, local;
@@ -358,9 +340,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, FDCM_SEARCH_WPE) k_search
         // List order = launch order: workgroups go round-robin to the XCDs, so all XCDs work on the same
         // scene line at the same time.  (Giving every XCD its own contiguous part of the list was
         // measured slower: 0.32-0.39 ms against 0.27-0.29 ms.)
-        const int per_xcd = (P.nblocks + 7) >> 3;
-        const long long w = P.xcd_parts ? ((long long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * kWavesPerBlock + wave
-                                        : (long long)blockIdx.x * kWavesPerBlock + wave;
+        const long long w = (long long)blockIdx.x * kWavesPerBlock + wave;
         if (w >= P.ncand) return;  // wave-uniform; waves never synchronise with each other
         const int2 e = P.work[w >> 1];  // the two alignments of a pair run next to each other
         t = e.x;
@@ -379,10 +359,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, FDCM_SEARCH_WPE) k_search
     float* sc = L + 5 * P.lds_lines;
     for (int i = lane; i < P.m; i += 64) s_keys[i] = P.keys[i];
     const long long cand = P.cand_offsets[t] + local;
-#ifdef FDCM_LAB
-    unsigned long long* lab = P.lab ? P.lab + 8 * cand : nullptr;
-    if (lab && lane == 0) { lab[0] = __builtin_amdgcn_s_memtime(); lab[6] = wall_clock64(); }
-#endif
     const VolRef V = make_volref(P.vol, ivol_slice_floats(P.W, P.H), P.m, BUF32);
 
     // ---- which candidate: sorted template line j, window slot wi, alignment flip
@@ -393,9 +369,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, FDCM_SEARCH_WPE) k_search
 #pragma unroll
     for (int c = 0; c < 4; ++c) { tl[c] = P.tlines[(l0 + tl_local) * 4 + c]; sl[c] = P.slines[(size_t)scene_idx * 4 + c]; }
     const float* s_tl = P.tlines + l0 * 4;  // template lines straight from HBM (coalesced 16 B per lane)
-#ifdef FDCM_LAB
-    if (lab && tl[0] + sl[0] != 1.2345e-30f) SEARCH_STAMP(lab, 1);
-#endif
     // align + transform, defaultmatch.cpp:59-67
     float T1[6], T2[6], T[6];
     align_pair(tl, sl, T1, T2);
@@ -419,9 +392,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, FDCM_SEARCH_WPE) k_search
         mny = std_min(mny, std_min(y1, y2)); mxy = std_max(mxy, std_max(y1, y2));
     }
     mnx = wave_min_f(mnx); mny = wave_min_f(mny); mxx = wave_max_f(mxx); mxy = wave_max_f(mxy);
-#ifdef FDCM_LAB
-    if (lab && mnx != 1.2345e-30f) SEARCH_STAMP(lab, 2);
-#endif
 
     // ---- optimize<BatchOptimize / DefaultOptimize> for this candidate
     bool valid = true;
@@ -444,9 +414,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, FDCM_SEARCH_WPE) k_search
         OptState o;
         o.V = V; o.L = L; o.sc = sc; o.n_t = n_t; o.H = (unsigned)P.H; o.tx = P.tx; o.ty = P.ty;
         o.savx = savx; o.savy = savy; o.lane = lane;
-#ifdef FDCM_LAB
-        o.lab = lab;
-#endif
         o.B = P.optimizer == FDCM_BATCH_OPTIMIZE ? P.batch : 1; o.WIN = P.win; o.batch_rule = P.optimizer == FDCM_BATCH_OPTIMIZE;
         o.reset_back = P.optimizer == FDCM_INDULGENT_OPTIMIZE;
         // static_cast<long>(max_mul / min_mul), batchoptimize.cpp:51,74
@@ -472,9 +439,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, FDCM_SEARCH_WPE) k_search
         // translations the reference's rule evaluated (reduced by the compaction kernels: one
         // contended atomic per candidate would serialise the whole grid at ~12 ns each)
         P.evals[cand] = (int)n_eval;
-#ifdef FDCM_LAB
-        if (lab) { lab[4] = __builtin_amdgcn_s_memtime(); lab[7] = wall_clock64(); lab[5] = (unsigned long long)n_eval; }
-#endif
     }
 }
 
@@ -664,7 +628,7 @@ int64_t search_capacity(const fdcm_templates* t, int64_t n_scene, int64_t maxT, 
 
 bool orientation_bins_on_host() {
     static const bool on_host = [] {
-        const bool forced = getenv("FDCM_FORCE_HOST_BINS") != nullptr;
+        const bool forced = test_switches().host_bins;
         const bool differs = fdcm_selftest_atanf(0, 65537, (1ull << 32) / 65537) != 0;
         if (forced || differs)
             fprintf(stderr, "libfdcm_hip: orientation bins of the candidates come from this machine's libm on host threads (%s); "
@@ -783,8 +747,6 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     P.cand_offsets = (const long long*)(ds + L.o_coff);
     P.bpt = (int)((L.cpt_max + kWavesPerBlock - 1) / kWavesPerBlock);
     P.ncand = ncand;
-    static const int env_xcd_parts = getenv("FDCM_SEARCH_XCD_PARTS") ? atoi(getenv("FDCM_SEARCH_XCD_PARTS")) : 0;  // tuning override, read once
-    P.xcd_parts = env_xcd_parts;
     P.lds_lines = lds_lines;
     P.records = fm->s_records.as<fdcm_match>();
     P.flags = fm->s_flags.as<int>();
@@ -793,8 +755,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     P.pairs_stride = (int)L.pairs_stride;
     P.pairs = fm->s_pairs.as<int2>();
     // volumes below 4 GB (every BASELINE config but 5) are addressed through one buffer descriptor with 32-bit offsets
-    static const bool env_flat = getenv("FDCM_SEARCH_FLAT") != nullptr;  // measurement: 64-bit flat addresses always
-    const bool buf32 = !env_flat && (size_t)fm->m * ivol_slice_floats(fm->W, fm->H) * sizeof(float) < ((size_t)1 << 32);
+    const bool buf32 = !test_switches().search_flat && (size_t)fm->m * ivol_slice_floats(fm->W, fm->H) * sizeof(float) < ((size_t)1 << 32);
     if (lds > 64 * 1024)
         FDCM_HIP(hipFuncSetAttribute(buf32 ? (const void*)k_search<true> : (const void*)k_search<false>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -803,8 +764,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     if (timed) FDCM_HIP(hipEventRecord(ev[6], st));
     hipLaunchKernelGGL(k_pairs, dim3((unsigned)(((size_t)t->T * maxT + 255) / 256)), dim3(256), 0, sp, P);
     const long long n_slots = (long long)t->T * P.pairs_stride;
-    static const bool no_worklist = getenv("FDCM_SEARCH_TEMPLATE_MAJOR") != nullptr;  // tuning override
-    if (!no_worklist && n_slots <= 0x7fffffffll) {
+    if (n_slots <= 0x7fffffffll) {
         if (n_slots <= kWlSlotsPerBlock) {
             hipLaunchKernelGGL(k_worklist, dim3(1), dim3(1024), 0, sp, P, n_slots, fm->s_work.as<int2>());
         } else {
@@ -873,35 +833,8 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
         FDCM_HIP(hipMemcpyAsync(fm->s_bins.p, hb, (size_t)ncand * stride * sizeof(unsigned short), hipMemcpyHostToDevice, st));
         P.host_bins = fm->s_bins.as<unsigned short>();
     }
-#ifdef FDCM_LAB
-    static const bool env_lab = getenv("FDCM_SEARCH_LAB") != nullptr;
-    static DevBuf labbuf;
-    P.lab = nullptr;
-    if (env_lab) { labbuf.reserve((size_t)ncand * 64); FDCM_HIP(hipMemsetAsync(labbuf.p, 0, (size_t)ncand * 64, st)); P.lab = labbuf.as<unsigned long long>(); }
-    if (lab_skip("search")) {} else
-#endif
     if (buf32) hipLaunchKernelGGL(k_search<true>, dim3((unsigned)P.nblocks), dim3(64 * kWavesPerBlock), lds, st, P);
     else hipLaunchKernelGGL(k_search<false>, dim3((unsigned)P.nblocks), dim3(64 * kWavesPerBlock), lds, st, P);
-#ifdef FDCM_LAB
-    if (env_lab) {
-        FDCM_HIP(hipStreamSynchronize(st));
-        std::vector<unsigned long long> h((size_t)ncand * 8);
-        FDCM_HIP(hipMemcpy(h.data(), labbuf.p, h.size() * 8, hipMemcpyDeviceToHost));
-        double d[4] = {0, 0, 0, 0}, life = 0, ev = 0;
-        unsigned long long w0 = ~0ull, w1 = 0;
-        long long n = 0;
-        for (long long c = 0; c < ncand; ++c) {
-            const unsigned long long* e = &h[(size_t)c * 8];
-            if (!e[4] || !e[3]) continue;
-            d[0] += (double)(e[1] - e[0]); d[1] += (double)(e[2] - e[1]); d[2] += (double)(e[3] - e[2]); d[3] += (double)(e[4] - e[3]);
-            life += (double)(e[7] - e[6]); ev += (double)e[5];
-            w0 = std::min(w0, e[6]); w1 = std::max(w1, e[7]);
-            ++n;
-        }
-        if (n) fprintf(stderr, "[search lab] %lld waves: loads %.0f  lines+bins %.0f  round1 %.0f  rule+rounds %.0f cycles; life %.2f us (100 MHz clock), span %.1f us, evals/wave %.1f\n",
-                       n, d[0] / n, d[1] / n, d[2] / n, d[3] / n, life / n / 100.0, (double)(w1 - w0) / 100.0, ev / n);
-    }
-#endif
     fdcm_match* dst = out_device;
     if (!dst) {
         // host output: one extra record behind the candidates' capacity carries the counters, so that the
@@ -925,8 +858,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
         fm->s_cnt.reserve(L.counters);
         FDCM_HIP(hipHostGetDevicePointer((void**)&host_cnt, fm->s_cnt.p, 0));
     }
-    static const bool env_two_step = getenv("FDCM_SEARCH_COMPACT2") != nullptr;  // the tests' switch: the two-kernel form at every size
-    if (nchunks <= kCompactChunks && !env_two_step) {
+    if (nchunks <= kCompactChunks && !test_switches().search_compact2) {
         hipLaunchKernelGGL(k_compact, dim3((unsigned)nchunks), dim3(1024), 0, st, P.records, P.flags, P.evals, ncand, nchunks, dst, P.counters,
                            host_out, host_cnt);
     } else {

@@ -8,6 +8,8 @@ struct EnvEntry;
 struct OwnEntry;
 
 static constexpr int kSweepSegments = 8;  // column ranges per row = waves per workgroup
+static constexpr int kSweepMinCols = 16;  // seeded columns a range holds at least (fewer ranges on small slices)
+static constexpr int kSweepMaxBlocks = 128;  // claim blocks of columns per slice at most
 
 // Scratch of the sweep, row-major (every lane streams through its own row's records).
 struct SweepBuf {
@@ -23,19 +25,14 @@ struct SweepBuf {
     int steal_heavy_only;                 // 1: only the heaviest workgroups (launch rank / seeded columns) cut dynamically
     int steal_cols;                       // .. that holds this many columns at least
     int* steals;                          // [0]: ranges taken over so far (all launches of the handle), or null
-#ifdef FDCM_LAB
-    long long* lab;                       // lab builds (make LAB=1): 16 clock stamps / counters per (chunk, wave), or null
-#endif
 };
 
 // column ranges per row of a slice with n seeded columns: at most kSweepSegments, each with min_cols columns at least
-// (the kernel and fdcm_debug_sweep_ranges use this one function)
+// (the kernel and fdcm_selftest_sweep_ranges use this one function)
 __host__ __device__ inline int sweep_ranges(int n, int min_cols) {
     const int s = n / (min_cols > 1 ? min_cols : 1);
     return s < 1 ? 1 : (s > kSweepSegments ? kSweepSegments : s);
 }
-// seeded columns a range holds at least: 16, or FDCM_SWEEP_MINCOLS = 1..64 (the tests' switch: small images then take all 8 ranges too)
-int sweep_min_cols();
 
 // the sweep applies when every value of the pass is an exact integer (see fdcm_sweep.hip)
 inline bool sweep_balanced_applies(long W, long H) { return W * W + H * H <= (1L << 24); }

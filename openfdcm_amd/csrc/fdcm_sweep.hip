@@ -38,10 +38,6 @@
 //   owner walk  same layout: 8 stack entries of a row per step -> owner list (addend chains by pointer doubling)
 //   fill        all waves, W / kSeg pixels each, 16-byte units of the interleaved layout [k][x/4][y][x%4]
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "fdcm_build_dev.h"
 #include "fdcm_quotient.h"
@@ -53,8 +49,6 @@ static constexpr int kSeg = kSweepSegments;  // waves per block = column ranges 
 static constexpr int kNT = 64 * kSeg;
 static constexpr int kRing = 8;      // stack entries per (row, range) below the top kept in LDS
 static constexpr int kRE = 10;       // owner entries per row and round of the fill (three words each in LDS)
-[[maybe_unused]] static constexpr int kLabN = 24;     // lab builds: 64-bit words per (chunk, wave) record
-static constexpr int kMinCols = 16;  // a range holds at least this many seeded columns (fewer ranges on small slices); FDCM_SWEEP_MINCOLS
 
 // The LDS ring of stack entries, three planes of consecutive dwords: entry i of workgroup lane c is
 // (2 v, P = f + v^2, z) = plane[0..2][i & (kRing - 1)][c].  In the local run a lane reads and writes its own column c (bank = c mod 32
@@ -80,10 +74,10 @@ struct Ring {
 // (dynamic cuts: the exact-owner theorem allows any cut).  Columns are handed out in blocks: a wave claims the next block of its
 // stretch when it gets there (an atomic OR on a bit map in LDS), and stops where somebody else's range begins.
 static constexpr int kMaxR = 16;     // ranges per row at most (initial + taken over)
-static constexpr int kMaxBlk = 128;  // claim blocks per slice at most (two 64-bit words)
+static constexpr int kMaxBlk = kSweepMaxBlocks;  // claim blocks per slice at most (two 64-bit words)
 static constexpr int kStealMin = 1;   // blocks an unclaimed stretch must have for a wave out of columns to begin a new range in its middle (FDCM_SWEEP_STEAL)
                                       // (mean of config 2's four scenes: 1 block 0.196 ms, 2 blocks 0.198 -- with an occasional 0.267 on seed 4 --, 3: 0.207, 6: 0.225)
-static constexpr int kStealCols = 8;  // .. and columns  // blocks an unclaimed stretch must have for a wave out of columns to begin a new range in its middle (FDCM_SWEEP_STEAL)
+static constexpr int kStealCols = 8;  // .. and columns
 struct SweepLds {
     unsigned long long smask[64];    // the slice's seeded columns, 64 per word (W <= 4096)
     unsigned long long claim[2];     // blocks of columns that have an owner
@@ -164,15 +158,11 @@ __device__ __forceinline__ bool claim_block(SweepLds& L, int b, int lane) {
 // as it is the first to claim them: it ends where another range begins, or at the slice's last column.
 // (bend < 0: dynamic; bend >= 0: no claims at all, the run covers the blocks [b0, bend) -- ranges of equal count, FDCM_SWEEP_STEAL=0)
 __device__ __forceinline__ void local_run(const uint4* __restrict__ dp, int W, SweepLds& L, int b0, int nblk, int bend, int lane,
-                                          int y, int tid, const Ring ring, EnvEntry* __restrict__ ent_row, int& cnt_out, int& base_out, int& q0_out, long long* lab) {
+                                          int y, int tid, const Ring ring, EnvEntry* __restrict__ ent_row, int& cnt_out, int& base_out, int& q0_out) {
     const unsigned long long* smask = L.smask;
     const int q0 = __builtin_amdgcn_readfirstlane((int)L.blk_q[b0]);
     EnvEntry* __restrict__ ent = ent_row + q0;
     q0_out = q0;
-#ifdef FDCM_LAB
-    long long lab_cols = 0, lab_pop = 0, lab_evict = 0;
-    const long long lab_t0 = __builtin_amdgcn_s_memtime();
-#endif
     const float inf = f_inf();
     const uint4 db = dp[q0];
     // top entry t and the entry below it u (a register copy of ring entry cnt - 1, so that a single pop needs no LDS round trip)
@@ -277,10 +267,6 @@ __device__ __forceinline__ void local_run(const uint4* __restrict__ dp, int W, S
                 // The loop leaves with flag = 1 when a popping lane's ring ran empty above the stack's bottom (0 < cnt == base after
                 // the pop): those lanes have pend = 1, took their pop, and get their refill and u below.
                 int flag;
-#ifdef FDCM_LAB
-                ++lab_cols;
-                const long long lab_p0 = __builtin_amdgcn_s_memtime();
-#endif
                 do {
                     int pend, c1;
                     unsigned long long sx, sy;
@@ -341,10 +327,6 @@ __device__ __forceinline__ void local_run(const uint4* __restrict__ dp, int W, S
                         }
                     }
                 } while (flag);
-#ifdef FDCM_LAB
-                lab_pop += __builtin_amdgcn_s_memtime() - lab_p0;
-                if (__builtin_amdgcn_ballot_w64(cnt - base == kRing) != 0ull) ++lab_evict;
-#endif
                 if (__builtin_expect(cnt - base == kRing, 0)) evict();
                 uv = tvx2; up = tP; uz = tz;
                 ring.put(cnt, tid, tvx2, tP, tz);
@@ -355,16 +337,9 @@ __device__ __forceinline__ void local_run(const uint4* __restrict__ dp, int W, S
             }
         }
     }
-#ifdef FDCM_LAB
-    if (lab && lane == 0) { lab[16] = 0; lab[17] = lab_cols; lab[18] = lab_evict; lab[19] = lab_pop; lab[20] = 0; lab[21] = __builtin_amdgcn_s_memtime() - lab_t0; }
-#endif
     local_finish(ring, ent, tid, tvx2, tP, tz, cnt, base);
     cnt_out = cnt; base_out = base;
 }
-
-// (Round 5 built a local run with a column cursor per lane for lab builds -- FDCM_SWEEP_LOCAL=cursors: the longest wave makes 201
-// passes instead of 482 and the kernel is slower, 0.22 against 0.195 ms, because a pass with its own cursor is ~45 instructions
-// against 20; profiles/NOTES.md section 11.  It was removed in round 6 when the ranges became dynamic; git history has it.)
 
 // ---- Phase 2 lane layout: wave j works on the rows 8 j .. 8 j + 7 of the chunk, lane = 8 g + t with g the row inside
 // the wave and t = 0..7.  The 8 lanes of a row hold the row's state in copies and spend their width on 8 stack entries
@@ -382,10 +357,7 @@ __device__ __forceinline__ int first_pixel(float z, float Wf) { return (int)floo
 // behind it against the entry it landed on at once (entry c + 1 pops entry c if its local z -- its quotient on c, the very
 // test the reference makes -- is <= c's quotient on the landing entry; landing deeper only raises that quotient, so what
 // this decides the reference decides too, and what it leaves open the next round settles).
-__device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, int sh, const Ring ring, EnvEntry* __restrict__ entr, long long* lab) {
-#ifdef FDCM_LAB
-    long long n_iter = 0, n_hbm = 0, n_refill = 0;
-#endif
+__device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, int sh, const Ring ring, EnvEntry* __restrict__ entr) {
     // The first 8 incoming entries of every junction are fetched together before the first one is needed (one trip to
     // memory for all of them; the sets rotate through named registers): lane t holds entry t of the range as
     // (2 v, f + v^2, local z).  (Entries 8 .. 15 only come with a refill: rows scatter over memory, and the fetches of a
@@ -404,15 +376,7 @@ __device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, i
         }
         return c;
     };
-#ifdef FDCM_LAB
-    const long long lt0 = wall_clock64();
-    long long lt_loop = 0, lt_first = 0;
-#endif
     Cand c0 = load_cand(1, 0, false), c1 = load_cand(2, 0, false), c2 = load_cand(3, 0, false), c3 = load_cand(4, 0, false), c4 = load_cand(5, 0, false), c5 = load_cand(6, 0, false), c6 = load_cand(7, 0, false);
-#ifdef FDCM_LAB
-    asm volatile("; lab: the incoming entries have arrived" :: "v"(c0.a2v), "v"(c1.a2v), "v"(c2.a2v), "v"(c3.a2v), "v"(c4.a2v), "v"(c5.a2v), "v"(c6.a2v), "v"(c6.bz));
-    const long long lt1 = wall_clock64();
-#endif
     int ms = 0, mi = L.t_cnt[0][row] - 1, ms_lo = 0, ms_base = L.t_base[0][row], ms_slot = L.s_slot0[0];  // the top of the row's stack
     int ms_rcol = L.r_wave[0] * 64 + row;  // .. and the ring column its top entries are in
     L.t_lo[0][row] = 0;
@@ -430,16 +394,7 @@ __device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, i
         // the incoming entry and the local z of the entry behind it, in every lane of the row
         float c2v = __shfl(A2v, sh), chq = __shfl(Ahq, sh), nz = __shfl(Az, sh + 1);
         if (nw < 2) nz = f_inf();
-#ifdef FDCM_LAB
-        const long long lj0 = wall_clock64();
-        bool firstit = true;
-#endif
         for (;;) {
-#ifdef FDCM_LAB
-            ++n_iter;
-            if (!firstit && lt_first == 0) lt_first = wall_clock64() - lj0;
-            firstit = false;
-#endif
             // ---- the incoming entry cur against the 8 entries at the top of the row's stack
             // (lane t looks at entry mi - t: (2 v, P = f + v^2, z) from the LDS ring while it is still there.  The entries below
             // the ring -- the deeper lanes, after earlier pops -- are in memory: they are only fetched when the run of pops gets
@@ -456,9 +411,6 @@ __device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, i
             unsigned m8 = (unsigned)(__builtin_amdgcn_ballot_w64(pop) >> sh) & 0xffu;
             int npop = __builtin_ctz(~m8);  // leading pops, 0..8
             if (__builtin_amdgcn_ballot_w64(deep && npop == t) != 0ull) {  // some row's pops reach below its ring: one trip for all deep lanes
-#ifdef FDCM_LAB
-                ++n_hbm;
-#endif
                 const EnvEntry h = entr[ms_slot + ci];
                 float hv, hf, hz;
                 asm volatile("v_mov_b32 %0, %3\n\tv_mov_b32 %1, %4\n\tv_mov_b32 %2, %5" : "=&v"(hv), "=&v"(hf), "=&v"(hz) : "v"(h.v2), "v"(h.P), "v"(h.z));
@@ -501,9 +453,6 @@ __device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, i
                 if (moves) cur += __builtin_ctz(~a8);  // (at least one: lane 0's test is the one that said so)
                 // the window ran out (the incoming entry's successor is not held any more): the next 16 from memory
                 if (__builtin_amdgcn_ballot_w64(moves && cur - cb >= wend) != 0ull) {
-#ifdef FDCM_LAB
-                    ++n_refill;
-#endif
                     if (moves && cur - cb >= wend) cb = cur;
                     const Cand c = load_cand(w, cb, true);
                     A2v = c.a2v; Ahq = c.ahq; Az = c.az; B2v = c.b2v; Bhq = c.bhq; Bz = c.bz;
@@ -518,9 +467,6 @@ __device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, i
             }
             if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
         }
-#ifdef FDCM_LAB
-        lt_loop += wall_clock64() - lj0;
-#endif
         L.t_hi[ms][row] = mi;
         L.t_prev[w][row] = ms;
         L.t_lo[w][row] = cur;
@@ -530,9 +476,6 @@ __device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, i
         ms = w; mi = nw - 1; ms_lo = cur; ms_base = wbase; ms_slot = wslot; ms_rcol = wrcol;
     }
     L.t_hi[ms][row] = mi;
-#ifdef FDCM_LAB
-    if (lab && (threadIdx.x & 63) == 0) { lab[12] = n_iter; lab[13] = n_hbm; lab[14] = n_refill; lab[15] = ((lt1 - lt0) << 40) | (lt_loop << 20) | lt_first; }
-#endif
 }
 
 // ---- the walk over the merged stack of a row -> owner list (first pixel, column, addend).  The stack of a row is the valid
@@ -735,20 +678,6 @@ __global__ void __launch_bounds__(kNT) k_sweep_balanced(const ColDesc* __restric
     const long long t_start = wall_clock64();
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long chunk = B.order ? B.order[blockIdx.x] : (long)blockIdx.x;
-#ifdef FDCM_LAB
-    long long* lab = B.lab ? B.lab + ((size_t)chunk * kSeg + wave) * kLabN : nullptr;
-#define LAB_STAMP(i) do { if (lab && lane == 0) lab[i] = wall_clock64(); } while (0)
-#else
-#define LAB_STAMP(i) do { } while (0)
-#endif
-    LAB_STAMP(0);
-#ifdef FDCM_LAB
-    if (lab && lane == 0) {  // where the workgroup runs: HW_ID (CU, SH, SE) and the XCC
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
-        lab[22] = hw; lab[23] = xcc;
-    }
-#endif
     const long k = chunk / HW64;
     const int c = (int)(chunk - k * HW64);
     const int y = c * 64 + lane;
@@ -821,16 +750,9 @@ __global__ void __launch_bounds__(kNT) k_sweep_balanced(const ColDesc* __restric
                 run_now = false;
                 have = true;
                 int base, q0;
-#ifdef FDCM_LAB
-                local_run(dp, W, L, bstart, nblk, dyn ? -1 : (wave + 1) * kpr, lane, y, tid, ring, ent_row, cnt, base, q0, lab);
-#else
-                local_run(dp, W, L, bstart, nblk, dyn ? -1 : (wave + 1) * kpr, lane, y, tid, ring, ent_row, cnt, base, q0, nullptr);
-#endif
+                local_run(dp, W, L, bstart, nblk, dyn ? -1 : (wave + 1) * kpr, lane, y, tid, ring, ent_row, cnt, base, q0);
                 L.t_cnt[rid][lane] = (short)cnt; L.t_base[rid][lane] = (short)base;
                 if (lane == 0) { L.s_slot0[rid] = q0; L.r_wave[rid] = wave; }
-#ifdef FDCM_LAB
-                if (lab) { const int mc = wave_max(cnt); if (lane == 0) { lab[8] += 1; lab[10] = max((int)lab[10], mc); } }
-#endif
             }
             if (!dyn) break;
             // the longest stretch of unclaimed blocks (wave-uniform scalar scan; the map may change under it: the claim decides)
@@ -853,9 +775,7 @@ __global__ void __launch_bounds__(kNT) k_sweep_balanced(const ColDesc* __restric
             rid = id; bstart = bs; run_now = true;
         }
     }
-    LAB_STAMP(1);
     __syncthreads();  // every range's stack is in memory, its top entries in the rings
-    LAB_STAMP(2);
     // ---- the ranges in column order: ids beyond the first S0 were handed out as waves ran dry.  The tables are rewritten by
     // rank (the merge and the walk take the ranges from left to right) -- only when a range was taken over at all.
     int S = S0;
@@ -890,15 +810,9 @@ __global__ void __launch_bounds__(kNT) k_sweep_balanced(const ColDesc* __restric
     const int g8 = lane >> 3, t8 = lane & 7, sh8 = lane & 56, row8 = wave * 8 + g8;
     {
         EnvEntry* entr = B.ent + ((size_t)chunk * 64 + row8) * (size_t)B.eslots;
-#ifdef FDCM_LAB
-        merge_bulk(L, S, row8, t8, sh8, ring, entr, lab);
-#else
-        merge_bulk(L, S, row8, t8, sh8, ring, entr, nullptr);
-#endif
+        merge_bulk(L, S, row8, t8, sh8, ring, entr);
     }
-    LAB_STAMP(3);
     __syncthreads();  // every wave is through with the rings: their LDS becomes the walk's lists
-    LAB_STAMP(4);
     {
         unsigned* w32 = reinterpret_cast<unsigned*>(pool);
         if (S <= kSeg)
@@ -908,20 +822,13 @@ __global__ void __launch_bounds__(kNT) k_sweep_balanced(const ColDesc* __restric
             walk_batched<kMaxR>(L, W, S, part_w, B, chunk, row8, t8, sh8, reinterpret_cast<unsigned(*)[kWinStride]>(w32),
                                 reinterpret_cast<float(*)[kWinStride]>(w32 + 64 * kWinStride), reinterpret_cast<int(*)[kWinStride]>(w32 + 2 * 64 * kWinStride));
     }
-    LAB_STAMP(5);
     __syncthreads();  // the chunk's owner lists are in memory
-    LAB_STAMP(6);
     if (tid == 0) B.cost[chunk] = (int)(wall_clock64() - t_start);
     {
         unsigned* w32 = reinterpret_cast<unsigned*>(pool);
         fill_part(L, vol, W, H, k, c, chunk, part_w, B, wave, reinterpret_cast<int(*)[kNT]>(w32), reinterpret_cast<float(*)[kNT]>(w32 + kRE * kNT),
                   reinterpret_cast<float(*)[kNT]>(w32 + 2 * kRE * kNT));
     }
-    LAB_STAMP(7);
-#ifdef FDCM_LAB
-    if (lab && lane == 0) { lab[11] = L.s_lcount[wave * (64 / kSeg)]; }
-#endif
-#undef LAB_STAMP
 }
 
 // Launch order of the next build's chunks: by decreasing cost of this one (scenes of a stream change little from
@@ -945,169 +852,19 @@ __global__ void __launch_bounds__(1024) k_order(const int* __restrict__ cost, in
     for (int i = tid; i < n; i += 1024) order[atomicAdd(&cursor[255 - min(255, max(0, (int)((float)cost[i] * scale)))], 1)] = i;
 }
 
-int sweep_min_cols() {
-    static const int v = [] { const char* e = getenv("FDCM_SWEEP_MINCOLS"); const int x = e ? atoi(e) : 0; return (x >= 1 && x <= 64) ? x : kMinCols; }();
-    return v;
-}
-
 void launch_sweep_order(hipStream_t st, const int* cost, int n, int* order) { hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, cost, n, order); }
 
 void launch_sweep_balanced(hipStream_t st, const void* desc, float* vol, int W, int H, int HW64, long nchunks, const SweepBuf& B_) {
     const int part_w = (((W + kSeg - 1) / kSeg) + 3) & ~3;  // fill parts start on a group of 4 columns
     SweepBuf B = B_;
-    B.min_cols = sweep_min_cols();
-    // FDCM_SWEEP_STEAL=<blocks> (the tests' switch): a wave out of columns begins a new range in an unclaimed stretch of at least
-    // that many blocks (of 8 columns, fewer on small slices); 0 = never (ranges of equal count only); default kStealMin
-    static const int env_steal = [] { const char* e = getenv("FDCM_SWEEP_STEAL"); const int x = (e && *e) ? atoi(e) : -1; return (x >= 0 && x <= kMaxBlk) ? x : -1; }();
-    B.steal_min = env_steal >= 0 ? env_steal : (B.steal_min < 0 ? kStealMin : B.steal_min);
-    static const int env_heavy = [] { const char* e = getenv("FDCM_SWEEP_STEAL_HEAVY"); return (e && *e) ? atoi(e) : -1; }();  // measurement: 0 all workgroups, 1 the heaviest only
-    if (env_heavy >= 0) B.steal_heavy_only = env_heavy;
-    else if (env_steal >= 0) B.steal_heavy_only = 0;
-    B.steal_cols = env_steal >= 0 ? 0 : kStealCols;  // (the forced threshold counts blocks only: small test images have blocks of one column)
-#ifdef FDCM_LAB
-    if (getenv("FDCM_SWEEP_LAB")) {  // per-wave phase times (100 MHz clock) and counters of this launch, on stderr
-        static DevBuf labbuf;
-        const size_t nl = (size_t)nchunks * kSeg * kLabN;
-        labbuf.reserve(nl * 8);
-        FDCM_HIP(hipMemsetAsync(labbuf.p, 0, nl * 8, st));
-        SweepBuf B2 = B;
-        B2.lab = labbuf.as<long long>();
-        // FDCM_SWEEP_LAB=4: unused dynamic LDS on top, so that one workgroup has a CU to itself (what do co-resident waves cost?)
-        const size_t pad = atoi(getenv("FDCM_SWEEP_LAB")) == 4 ? 70000 : 0;
-        if (pad) FDCM_HIP(hipFuncSetAttribute((const void*)k_sweep_balanced, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad));
-        hipLaunchKernelGGL(k_sweep_balanced, dim3((unsigned)nchunks), dim3(kNT), pad, st, (const ColDesc*)desc, vol, W, H, HW64, part_w, B2);
-        FDCM_HIP(hipStreamSynchronize(st));
-        std::vector<long long> d(nl);
-        FDCM_HIP(hipMemcpy(d.data(), labbuf.p, nl * 8, hipMemcpyDeviceToHost));
-        long long t0 = 0x7fffffffffffffffll, t1 = 0;
-        for (long ch = 0; ch < nchunks; ++ch) for (int w = 0; w < kSeg; ++w) { const long long* e = &d[((size_t)ch * kSeg + w) * kLabN]; if (e[0]) { t0 = std::min(t0, e[0]); t1 = std::max(t1, e[7]); } }
-        auto pct = [](std::vector<double>& v, double q) { if (v.empty()) return 0.0; std::sort(v.begin(), v.end()); return v[(size_t)(q * (v.size() - 1))]; };
-        const char* names[7] = {"local run", "wait 1", "merge", "wait 2", "owner walk", "wait 3", "fill"};
-        fprintf(stderr, "[sweep lab] %ld chunks, kernel span %.1f us (first stamp to last)\n", nchunks, (t1 - t0) / 100.0);
-        for (int ph = 0; ph < 7; ++ph) {
-            std::vector<double> v;
-            for (long ch = 0; ch < nchunks; ++ch) for (int w = 0; w < kSeg; ++w) {
-                const long long* e = &d[((size_t)ch * kSeg + w) * kLabN];
-                if (!e[0]) continue;
-                v.push_back((e[ph + 1] - e[ph]) / 100.0);
-            }
-            double sum = 0; for (double x : v) sum += x;
-            fprintf(stderr, "[sweep lab] %-16s us per wave: mean %7.1f  p50 %7.1f  p90 %7.1f  p99 %7.1f  max %7.1f\n", names[ph], v.empty() ? 0.0 : sum / v.size(), pct(v, .5), pct(v, .9), pct(v, .99), pct(v, 1.0));
-        }
-        {
-            std::vector<double> life, start, cols, it, hb, lst;
-            for (long ch = 0; ch < nchunks; ++ch) {
-                const long long* e = &d[(size_t)ch * kSeg * kLabN];
-                if (!e[0]) continue;
-                long long end = 0;
-                for (int w = 0; w < kSeg; ++w) end = std::max(end, d[((size_t)ch * kSeg + w) * kLabN + 7]);
-                life.push_back((end - e[0]) / 100.0); start.push_back((e[0] - t0) / 100.0);
-                it.push_back((double)e[12]); hb.push_back((double)e[13]);
-                for (int w = 0; w < kSeg; ++w) { cols.push_back((double)d[((size_t)ch * kSeg + w) * kLabN + 9]); lst.push_back((double)d[((size_t)ch * kSeg + w) * kLabN + 10]); }
-            }
-            double ls = 0; for (double x : life) ls += x;
-            fprintf(stderr, "[sweep lab] block life us: mean %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f (sum %.0f); block start us: p50 %.1f p90 %.1f max %.1f\n", ls / life.size(), pct(life, .5), pct(life, .9),
-                    pct(life, .99), pct(life, 1.0), ls, pct(start, .5), pct(start, .9), pct(start, 1.0));
-            {  // the blocks that end last: where their time went (per phase: the longest wave)
-                std::vector<std::pair<double, long>> ends;
-                for (long ch = 0; ch < nchunks; ++ch) {
-                    long long end = 0;
-                    for (int w = 0; w < kSeg; ++w) end = std::max(end, d[((size_t)ch * kSeg + w) * kLabN + 7]);
-                    if (d[(size_t)ch * kSeg * kLabN]) ends.push_back({(end - t0) / 100.0, ch});
-                }
-                std::sort(ends.begin(), ends.end());
-                // .. and the blocks that live longest (second pass of the loop below)
-                std::vector<std::pair<double, long>> lives;
-                for (auto& en : ends) lives.push_back({en.first - (d[(size_t)en.second * kSeg * kLabN] - t0) / 100.0, en.second});
-                std::sort(lives.begin(), lives.end());
-                for (int pass = 0; pass < 2; ++pass)
-                for (size_t i = ends.size() > 6 ? ends.size() - 6 : 0; i < ends.size(); ++i) {
-                    const long ch = pass == 0 ? ends[i].second : lives[i].second;
-                    const char* what = pass == 0 ? "late" : "long";
-                    double ph[7] = {0, 0, 0, 0, 0, 0, 0}, st0 = 1e30;
-                    long long cols = 0, depth = 0, iters = 0, hbm = 0, refill = 0, owners = 0;
-                    for (int w = 0; w < kSeg; ++w) {
-                        const long long* e = &d[((size_t)ch * kSeg + w) * kLabN];
-                        st0 = std::min(st0, (e[0] - t0) / 100.0);
-                        for (int q = 0; q < 7; ++q) ph[q] = std::max(ph[q], (e[q + 1] - e[q]) / 100.0);
-                        cols = std::max(cols, e[9]); depth = std::max(depth, e[10]); iters = std::max(iters, e[12]); hbm = std::max(hbm, e[13]); refill = std::max(refill, e[14]);
-                        owners = std::max(owners, e[11]);
-                    }
-                    double endt = 0;
-                    for (auto& en : ends) if (en.second == ch) endt = en.first;
-                    fprintf(stderr, "[sweep lab] %s block %ld (slice %ld chunk %ld): %.1f -> %.1f us | local %.1f merge %.1f walk %.1f fill %.1f | columns %lld deepest %lld merge steps %lld (hbm %lld, refills %lld) owners %lld\n",
-                            what, ch, ch / HW64, ch % HW64, st0, endt, ph[0], ph[2], ph[4], ph[6], cols, depth, iters, hbm, refill, owners);
-                }
-            }
-            {
-                std::vector<double> a, b, c;
-                for (long ch = 0; ch < nchunks; ++ch) for (int w = 0; w < kSeg; ++w) { const long long v = d[((size_t)ch * kSeg + w) * kLabN + 15]; if (!d[((size_t)ch * kSeg + w) * kLabN]) continue; a.push_back((double)(v >> 40) / 100.0); b.push_back((double)((v >> 20) & 0xfffff) / 100.0); c.push_back((double)(v & 0xfffff) / 100.0); }
-                fprintf(stderr, "[sweep lab] merge: incoming entries arrive after p50 %.1f p90 %.1f us; junction loops p50 %.1f p90 %.1f us; first step of the first junction p50 %.2f p90 %.2f us\n", pct(a, .5), pct(a, .9), pct(b, .5), pct(b, .9), pct(c, .5), pct(c, .9));
-            }
-            {
-                std::vector<double> np, ns, nf, cp, cs, ct;
-                double snp = 0, scp = 0, sns = 0, scs = 0, sct = 0;
-                long long hp = 0, hcp = 0, hs = 0, hcs = 0, hct = 0, hf = 0;
-                for (long ch = 0; ch < nchunks; ++ch) for (int w = 0; w < kSeg; ++w) {
-                    const long long* e = &d[((size_t)ch * kSeg + w) * kLabN];
-                    if (!e[0] || !e[16]) continue;
-                    np.push_back((double)e[16]); ns.push_back((double)e[17]); nf.push_back((double)e[18]);
-                    cp.push_back((double)e[19] / (double)e[16]); cs.push_back(e[17] ? (double)e[20] / (double)e[17] : 0.0); ct.push_back((double)e[21]);
-                    snp += (double)e[16]; scp += (double)e[19]; sns += (double)e[17]; scs += (double)e[20]; sct += (double)e[21];
-                    if (e[21] > hct) { hct = e[21]; hp = e[16]; hcp = e[19]; hs = e[17]; hcs = e[20]; hf = e[18]; }
-                }
-                {  // the shared-cursor run: columns, ticks inside the pop loop statements, ticks of the whole local run
-                    std::vector<double> pc, oc, cols;
-                    double sp = 0, st = 0, sc = 0;
-                    for (long ch = 0; ch < nchunks; ++ch) for (int w = 0; w < kSeg; ++w) {
-                        const long long* e = &d[((size_t)ch * kSeg + w) * kLabN];
-                        if (!e[0] || e[16] || !e[17]) continue;
-                        pc.push_back((double)e[19] / (double)e[17]); oc.push_back((double)(e[21] - e[19]) / (double)e[17]); cols.push_back((double)e[17]);
-                        sp += (double)e[19]; st += (double)e[21]; sc += (double)e[17];
-                    }
-                    if (!pc.empty())
-                        fprintf(stderr, "[sweep lab] shared cursor: s_memtime ticks per column inside the pop loop: mean %.0f p50 %.0f p90 %.0f; outside it (descriptor, column value, push, eviction, the scan): mean %.0f p50 %.0f p90 %.0f; pop loop = %.0f %% of the local runs' ticks; columns per wave p50 %.0f\n",
-                                sp / sc, pct(pc, .5), pct(pc, .9), (st - sp) / sc, pct(oc, .5), pct(oc, .9), 100.0 * sp / st, pct(cols, .5));
-                }
-                if (!np.empty())
-                    fprintf(stderr, "[sweep lab] lane cursors: passes per wave p50 %.0f p90 %.0f max %.0f; stagings p50 %.0f max %.0f; slow passes p50 %.0f max %.0f; s_memtime ticks per pass: mean %.0f p50 %.0f p90 %.0f; per staging: mean %.0f; share of the local run: passes %.0f %%, stagings %.0f %%; longest wave: %lld ticks = %lld passes (%lld ticks) + %lld stagings (%lld ticks), %lld slow\n",
-                            pct(np, .5), pct(np, .9), pct(np, 1.0), pct(ns, .5), pct(ns, 1.0), pct(nf, .5), pct(nf, 1.0), scp / snp, pct(cp, .5), pct(cp, .9), scs / std::max(1.0, sns), 100.0 * scp / sct, 100.0 * scs / sct, hct, hp, hcp, hs, hcs, hf);
-            }
-            if (atoi(getenv("FDCM_SWEEP_LAB")) == 2) {  // which workgroups share a CU
-                std::vector<std::pair<unsigned long long, long>> where;
-                for (long ch = 0; ch < nchunks; ++ch) {
-                    const long long* e = &d[(size_t)ch * kSeg * kLabN];
-                    if (!e[0]) continue;
-                    const unsigned hw = (unsigned)e[22], xcc = (unsigned)e[23] & 0xf;
-                    const unsigned cu = (hw >> 8) & 0xf, shid = (hw >> 12) & 1, se = (hw >> 13) & 7;
-                    where.push_back({((unsigned long long)xcc << 24) | (se << 16) | (shid << 8) | cu, ch});
-                }
-                std::sort(where.begin(), where.end());
-                fprintf(stderr, "[sweep lab] placement (xcc.se.sh.cu: chunks in launch position order):");
-                unsigned long long last = ~0ull;
-                int shown = 0;
-                for (auto& w : where) {
-                    if (w.first != last) { if (++shown > 40) break; fprintf(stderr, "\n[sweep lab]   %llu.%llu.%llu.%llu:", w.first >> 24, (w.first >> 16) & 0xff, (w.first >> 8) & 0xff, w.first & 0xff); last = w.first; }
-                    long long end = 0;
-                    for (int w2 = 0; w2 < kSeg; ++w2) end = std::max(end, d[((size_t)w.second * kSeg + w2) * kLabN + 7]);
-                    fprintf(stderr, " %ld(%.0f-%.0f)", w.second, (d[(size_t)w.second * kSeg * kLabN] - t0) / 100.0, (end - t0) / 100.0);
-                }
-                fprintf(stderr, "\n");
-            }
-            fprintf(stderr, "[sweep lab] columns per wave p50 %.0f max %.0f; deepest local stack p50 %.0f p99 %.0f max %.0f; merge iterations per block p50 %.0f p90 %.0f max %.0f, with an HBM fetch p50 %.0f p90 %.0f max %.0f\n",
-                    pct(cols, .5), pct(cols, 1.0), pct(lst, .5), pct(lst, .99), pct(lst, 1.0), pct(it, .5), pct(it, .9), pct(it, 1.0), pct(hb, .5), pct(hb, .9), pct(hb, 1.0));
-        }
-        return;
+    const TestSwitches& sw = test_switches();
+    B.min_cols = sw.sweep_min_cols;
+    if (sw.sweep_steal >= 0) {  // a forced threshold (FDCM_SWEEP_STEAL) holds for every workgroup and counts blocks only: small test images have blocks of one column
+        B.steal_min = sw.sweep_steal; B.steal_heavy_only = 0; B.steal_cols = 0;
+    } else {
+        if (B.steal_min < 0) B.steal_min = kStealMin;
+        B.steal_cols = kStealCols;
     }
-    // FDCM_SWEEP_PAD=<bytes>: unused dynamic LDS on every workgroup, no other change (how does a pipeline of frames react to
-    // fewer sweeps per CU?)
-    static const int env_pad = getenv("FDCM_SWEEP_PAD") ? atoi(getenv("FDCM_SWEEP_PAD")) : 0;
-    if (env_pad > 0) {
-        FDCM_HIP(hipFuncSetAttribute((const void*)k_sweep_balanced, hipFuncAttributeMaxDynamicSharedMemorySize, env_pad));
-        hipLaunchKernelGGL(k_sweep_balanced, dim3((unsigned)nchunks), dim3(kNT), (size_t)env_pad, st, (const ColDesc*)desc, vol, W, H, HW64, part_w, B);
-        return;
-    }
-#endif
     hipLaunchKernelGGL(k_sweep_balanced, dim3((unsigned)nchunks), dim3(kNT), 0, st, (const ColDesc*)desc, vol, W, H, HW64, part_w, B);
 }
 

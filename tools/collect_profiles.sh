@@ -46,13 +46,12 @@ python3 $R/tools/run_config.py --config 2 --check none --reps 9 --perturb > $OUT
 bash $R/tools/fetch_calib.sh > /dev/null 2>&1 && cp $R/gpurun_out/fetch_calib.json $OUT/fetch_calib.json
 python3 $R/tools/sharded_bench.py --frames 4 --steps 200 2>> $OUT/bench.err | grep '^{' | tail -1 > $OUT/sharded_bench.json
 # round 6: bench.py cycles four scenes by default (timed region and blocking frames); the one-scene line beside it, the
-# frame-sharded schedule at N = 1, the per-stage times by scene, and the line integral's traffic by class of slice
+# frame-sharded schedule at N = 1 and the per-stage times by scene
 python3 $R/bench.py --scenes 1 --steps 200 --warmup 10 > $OUT/bench_1scene.json 2>> $OUT/bench.err
 python3 $R/bench.py --scaling strong --steps 200 --warmup 10 --cpu-sample 0 --api-frames 0 > $OUT/bench_strong_n1.json 2>> $OUT/bench.err
 python3 $R/bench.py --scaling frames --steps 200 --warmup 10 --cpu-reps 1 --api-frames 0 > $OUT/bench_frames_n1.json 2>> $OUT/bench.err
 python3 $R/tools/history_probe.py 2 > $OUT/history_probe_config2.json 2>> $OUT/bench.err
 python3 $R/tools/history_probe.py 3 > $OUT/history_probe_config3.json 2>> $OUT/bench.err
-bash $R/tools/int_split.sh 2>> $OUT/bench.err | grep "^k_integral" > $OUT/int_split_config3.txt
 bash $R/tools/pmc_sq.sh ${1:-prof}/pmc_sq > /dev/null 2>&1 && cp $OUT/pmc_sq/summary.json $OUT/pmc_sq_config2p.json
 cut -c1-300 $OUT/bench.json
 for f in $OUT/*_kernel_stats.csv; do echo $f; head -4 $f | cut -c1-110; done
