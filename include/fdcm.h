@@ -301,6 +301,9 @@ int fdcm_topk(fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_m
  * (dt3cpu.cpp:126-179) at t: exactly the bits fdcm_featuremap_evaluate returns for that template and translation.  t is
  * admissible for a template when fdcm_featuremap_evaluate does not return NaN there (every end point + T + t inside
  * (-1, W) x (-1, H)): a product of two integer intervals per template.  A template without lines scores 0 everywhere.
+ * An admissible point whose score is NaN (NaN, or +inf and -inf on one line, in the volume's data) is left out of every
+ * top-k, peak and rotation search as if it were not admissible; an infinite score is kept and orders after every finite
+ * one.  The score maps hold such points' NaN as it is.
  * Concurrent callers of one feature map take turns, as for the seam. */
 typedef struct fdcm_grid {
     int32_t x0, y0, nx, ny, sx, sy;

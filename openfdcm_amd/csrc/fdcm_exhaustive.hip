@@ -12,8 +12,9 @@
 //                                     several angles' planes (64-bit keys in LDS), else one plane (32-bit score bits)
 //   k_exhaustive_merge_groups         one wave per template of a batch: its merged list so far and its units' lists
 //
-// Keys of the top-k are (score bits << 32) | grid index: scores are >= +0, so the key order is the (score, g) order,
-// which is total -- the result does not depend on which wave saw which point first.  No atomics.
+// Keys of the top-k are (score bits << 32) | grid index: scores are >= +0 (+inf included), so the key order is the
+// (score, g) order, which is total -- the result does not depend on which wave saw which point first.  A NaN score has
+// no key.  No atomics.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -221,7 +222,8 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
                 bool any = false;
 #pragma unroll
                 for (int r = 0; r < kRows; ++r) {
-                    key[r] = act[r] ? ((unsigned long long)__float_as_uint(res[r]) << 32) |
+                    // a NaN score (NaN or inf - inf in the volume's data) has no key, as in the peaks kernel
+                    key[r] = act[r] && !(res[r] != res[r]) ? ((unsigned long long)__float_as_uint(res[r]) << 32) |
                                           ((unsigned)((jb + 16 * r) * nx + i) + P.koff)
                                     : kNoKey;
                     any = any || key[r] < thr;

@@ -155,13 +155,21 @@ __device__ __forceinline__ void optimise(const OptState& o, float& best, int& be
                     rel = 0;
                 }
                 const int take = min(nb - c0, have - rel);
-                // the piece's scores one per lane: its first minimum is a wave reduction, not a walk through LDS
+                // the piece's scores one per lane: its first minimum is a wave reduction, not a walk through LDS.
+                // std::min_element keeps its running minimum unless a later score is below it, so a NaN is never
+                // taken -- except as the batch's first score, which then stays the minimum
                 for (int e0 = 0; e0 < take; e0 += 64) {
                     const int n = min(64, take - e0);
                     const float s = o.lane < n ? o.sc[off + rel + e0 + o.lane] : f_inf();
-                    const float mn = wave_min_f(s);
-                    const int first = __ffsll((long long)__ballot(o.lane < n && s == mn)) - 1;
-                    if ((c0 == 0 && e0 == 0) || mn < bmin) { bmin = mn; bmin_k = k0 + dir * (c0 + e0 + first); }
+                    const bool is_nan = s != s;                     // lanes >= n hold +inf
+                    const unsigned long long nans = __ballot(is_nan);  // wave-uniform: no extra VGPR
+                    const float mn = wave_min_f(is_nan ? f_inf() : s);
+                    const unsigned long long at = __ballot(o.lane < n && !is_nan && s == mn);
+                    if (c0 == 0 && e0 == 0 && (nans & 1ull)) {
+                        bmin = f_nan(); bmin_k = k0;
+                    } else if (at != 0 && ((c0 == 0 && e0 == 0) || mn < bmin)) {
+                        bmin = mn; bmin_k = k0 + dir * (c0 + e0 + __ffsll((long long)at) - 1);
+                    }
                     blast = __shfl(s, n - 1);
                 }
                 c0 += take;

@@ -13,6 +13,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 f32 = np.float32
+U = 2.0 ** -24          # unit roundoff of float32
 
 
 def make_rotation(angle):
@@ -157,3 +158,54 @@ def edge_scenes():
 
 
 EDGE_SCENES = {c[0]: c[1:] for c in edge_scenes()}
+
+
+def definition_keys(m):
+    """The m orientation keys k pi / m - pi / 2 in float64."""
+    return np.arange(m) * np.pi / m - np.pi / 2
+
+
+# ---- float64 re-scoring of a template on a volume (tests/test_definitions_dt3.py, tests/test_definitions_scoring.py) ----
+def ulp32(x):
+    return np.spacing(np.float32(np.max(np.abs(x)) if np.size(x) else 0.0)).astype(np.float64)
+
+
+
+def nearest_bins(lines64, m, margin):
+    """(4, N) float64 lines -> (bin, ambiguous) with bin the nearest of the m keys k pi / m - pi / 2 (circularly: an angle
+    near pi/2 belongs to key 0) by a float64 arctan, ambiguous where the angle is within `margin` (per line) of the
+    boundary between two keys or the line has no direction."""
+    dx, dy = lines64[2] - lines64[0], lines64[3] - lines64[1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = np.arctan(dy / dx)
+    pos = (a + np.pi / 2) * m / np.pi                      # key units
+    b = np.floor(pos + 0.5)
+    frac = pos + 0.5 - b                                   # a boundary lies at frac 0 (and 1)
+    amb = np.minimum(frac, 1 - frac) * np.pi / m < margin if m > 1 else np.zeros(len(pos), dtype=bool)
+    amb |= ~np.isfinite(pos) | (np.hypot(dx, dy) < 1e-6)
+    b = np.where(np.isfinite(b), b, 0).astype(np.int64) % m
+    return b, amb
+
+
+def rescore(vol, keys, lines64, W, H, err, aerr):
+    """float64 score of a template whose (4, n) end points are already translated into the map: (score, bound, status)
+    with status 'ok', 'outside' or 'ambiguous' (an end point within err of a pixel edge, or a line within 1e-5 rad plus
+    the angle error of end points off by aerr of a bin boundary)."""
+    m = len(keys)
+    n = lines64.shape[1]
+    if n == 0:
+        return 0.0, 0.0, "ok"
+    length = np.hypot(lines64[2] - lines64[0], lines64[3] - lines64[1])
+    bins, amb = nearest_bins(lines64, m, 1e-5 + 2 * aerr / np.maximum(length, 1e-30))
+    lim = np.array([W, H, W, H])[:, None]
+    if ((lines64 <= -1 - err) | (lines64 >= lim + err)).any():     # truncates to a pixel outside the map
+        return None, None, "outside"
+    near = (np.abs(lines64 - np.round(lines64)) < err) & (np.round(lines64) != 0)  # cast<int>() truncates: 0 from both sides
+    if near.any() or amb.any():
+        return None, None, "ambiguous"
+    ix = np.trunc(lines64).astype(np.int64)
+    assert ((ix >= 0) & (ix < lim)).all()
+    a = vol[bins, ix[0], ix[1]].astype(np.float64)
+    c = vol[bins, ix[2], ix[3]].astype(np.float64)
+    terms = np.abs(a - c)
+    return float(terms.sum()), float(n * U * terms.sum()), "ok"
