@@ -677,7 +677,7 @@ BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after) {
     } else if (!L.balanced) {
         L.stack = sweep_literal_scratch_bytes((int)W, L.nchunks);
     } else {
-        // scratch of the balanced sweep, row-major: stack entries (W + 2 slots per row, 12 B), owner list (W + 2 entries per
+        // scratch of the balanced sweep, per chunk and slot-major: stack entries (W + 2 slots per row, 12 B), owner list (W + 2 entries per
         // row, 8 B), launch order, per-chunk cost and the steal counter
         L.slots = (int)W + 2;
         const size_t NRr = (size_t)L.nchunks * 64;

@@ -11,10 +11,11 @@ static constexpr int kSweepSegments = 8;  // column ranges per row = waves per w
 static constexpr int kSweepMinCols = 16;  // seeded columns a range holds at least (fewer ranges on small slices)
 static constexpr int kSweepMaxBlocks = 128;  // claim blocks of columns per slice at most
 
-// Scratch of the sweep, row-major (every lane streams through its own row's records).
+// Scratch of the sweep, per chunk and slot-major: the 64 rows of a chunk side by side in every slot (rows of a chunk stand at
+// similar depths: what a wave appends, lane = row, shares a few lines).
 struct SweepBuf {
-    EnvEntry* ent;                        // stack entries [row][slot], eslots per row (>= W)
-    OwnEntry* own;                        // owner list [row][index], lslots per row (>= W + 2)
+    EnvEntry* ent;                        // stack entries [chunk][slot][row], eslots per row (>= W)
+    OwnEntry* own;                        // owner list [chunk][index][row], lslots per row (>= W + 2)
     const int* order;                     // launch position -> chunk (longest chunks of the previous build first), or null
     int* cost;                            // per chunk: 100 MHz ticks from the block's start to the end of its owner walk
     int eslots, lslots;

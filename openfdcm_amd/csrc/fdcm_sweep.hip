@@ -33,7 +33,7 @@
 //
 // One workgroup per (slice, 64-row chunk), kSeg waves, lane = row:
 //   local run   wave w: the literal construction over its columns; stack = top entry in registers + a ring of kRing
-//               entries per row in LDS + HBM scratch behind it (row-major); everything also lands in HBM for the walk
+//               entries per row in LDS + HBM scratch behind it (slot-major: Rows); everything also lands in HBM for the walk
 //   merge       8 rows per wave, 8 lanes per row: the junctions from left to right, 8 entries per step (rings, HBM behind)
 //   owner walk  same layout: 8 stack entries of a row per step -> owner list (addend chains by pointer doubling)
 //   fill        all waves, W / kSeg pixels each, 16-byte units of the interleaved layout [k][x/4][y][x%4]
@@ -122,11 +122,21 @@ __device__ __forceinline__ int select_column_lane(const unsigned long long* smas
 // Stack entries in registers and in the ring are (float(2 v), P = f[v] + v^2, z): the numerator of imgproc.h:111,
 // ((f[q] + q^2) - f[v]) - v^2, is the exact integer P_q - P_v whatever the order (every term is an integer below 2^24), so
 // the test takes one subtraction; memory holds the same three numbers (f[v] = P - v^2 comes back exactly where the owner walk wants it).
+// The scratch of a chunk behind the LDS, slot-major: record i of row y is at [i][y], the 64 rows of a slot side by side.  Rows
+// of a chunk stand at similar depths, so what a wave appends lands in a few neighbouring lines that fill up while they are
+// still in L2 and leave it once and whole -- and the 8 rows x 8 slots of a merge or walk step, the 64 rows x kRE entries of a
+// fill round are whole sectors too.  (Row-major, every lane appended 12 bytes to a line of its own, 12 KB from its neighbour's:
+// a thousand open lines per workgroup, written back piecemeal and fetched again: profiles/NOTES.md section 13.)
+template <class T> struct Rows {
+    T* p;  // record 0 of this lane's row
+    __device__ __forceinline__ T& operator[](int i) const { return p[i * 64]; }
+    __device__ __forceinline__ Rows operator+(int i) const { return Rows{p + i * 64}; }
+};
 __device__ __forceinline__ EnvEntry to_mem(const float4& e) { return EnvEntry{e.x, e.y, e.z}; }
 __device__ __forceinline__ float4 from_mem(const EnvEntry& e) { return make_float4(e.v2, e.P, e.z, 0.f); }
 // ---- end of a local run: the top joins the entries; everything in the ring also goes to HBM (the ring keeps its content
 // for the merge)
-__device__ __forceinline__ void local_finish(const Ring ring, EnvEntry* __restrict__ ent, int tid, float tvx2, float tP, float tz, int& cnt, int& base) {
+__device__ __forceinline__ void local_finish(const Ring ring, const Rows<EnvEntry> ent, int tid, float tvx2, float tP, float tz, int& cnt, int& base) {
     if (cnt - base == kRing) { ent[base] = to_mem(ring.get(base, tid)); ++base; }
     ring.put(cnt, tid, tvx2, tP, tz);
     ++cnt;
@@ -158,10 +168,10 @@ __device__ __forceinline__ bool claim_block(SweepLds& L, int b, int lane) {
 // as it is the first to claim them: it ends where another range begins, or at the slice's last column.
 // (bend < 0: dynamic; bend >= 0: no claims at all, the run covers the blocks [b0, bend) -- ranges of equal count, FDCM_SWEEP_STEAL=0)
 __device__ __forceinline__ void local_run(const uint4* __restrict__ dp, int W, SweepLds& L, int b0, int nblk, int bend, int lane,
-                                          int y, int tid, const Ring ring, EnvEntry* __restrict__ ent_row, int& cnt_out, int& base_out, int& q0_out) {
+                                          int y, int tid, const Ring ring, const Rows<EnvEntry> ent_row, int& cnt_out, int& base_out, int& q0_out) {
     const unsigned long long* smask = L.smask;
     const int q0 = __builtin_amdgcn_readfirstlane((int)L.blk_q[b0]);
-    EnvEntry* __restrict__ ent = ent_row + q0;
+    const Rows<EnvEntry> ent = ent_row + q0;
     q0_out = q0;
     const float inf = f_inf();
     const uint4 db = dp[q0];
@@ -357,7 +367,7 @@ __device__ __forceinline__ int first_pixel(float z, float Wf) { return (int)floo
 // behind it against the entry it landed on at once (entry c + 1 pops entry c if its local z -- its quotient on c, the very
 // test the reference makes -- is <= c's quotient on the landing entry; landing deeper only raises that quotient, so what
 // this decides the reference decides too, and what it leaves open the next round settles).
-__device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, int sh, const Ring ring, EnvEntry* __restrict__ entr) {
+__device__ __forceinline__ void merge_bulk(SweepLds& L, int S, int row, int t, int sh, const Ring ring, const Rows<EnvEntry> entr) {
     // The first 8 incoming entries of every junction are fetched together before the first one is needed (one trip to
     // memory for all of them; the sets rotate through named registers): lane t holds entry t of the range as
     // (2 v, f + v^2, local z).  (Entries 8 .. 15 only come with a refill: rows scatter over memory, and the fetches of a
@@ -489,9 +499,8 @@ constexpr int kWinStride = 65;  // (odd: the lanes of a row read neighbouring li
 template <int NR>  // ranges the row's table is laid out for: 8 (no range was taken over) or kMaxR
 __device__ __forceinline__ void walk_batched(SweepLds& L, int W, int S, int part_w, const SweepBuf& B, long chunk, int row, int t, int sh,
                                              unsigned (*l_pk)[kWinStride], float (*l_b)[kWinStride], int (*l_pt)[kWinStride]) {
-    const size_t r = (size_t)chunk * 64 + row;
-    OwnEntry* own = B.own + r * (size_t)B.lslots;
-    const EnvEntry* ent = B.ent + r * (size_t)B.eslots;
+    const Rows<OwnEntry> own{B.own + (size_t)chunk * 64 * (size_t)B.lslots + row};
+    const Rows<const EnvEntry> ent{B.ent + (size_t)chunk * 64 * (size_t)B.eslots + row};
     // Range table of the row: stream index i lies in range w for i in [o_w, o_{w+1}), at slot i + K_w.
     // (K lives in LDS: the compiler turns a select chain over a register array into an indexed load from scratch memory)
     int o[NR + 1];
@@ -610,13 +619,12 @@ __device__ __forceinline__ void fill_part(SweepLds& L, float* __restrict__ vol, 
                                           int (*f_st)[kNT], float (*f_vf)[kNT], float (*f_b)[kNT]) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int y = c * 64 + lane;
-    const size_t r = (size_t)chunk * 64 + lane;
     int qcur = p * part_w;
     const int qend = min(qcur + part_w, W);
     if (qcur >= qend) return;  // (last phase of the kernel: nothing waits for this wave any more)
     int idx = p == 0 ? 0 : L.s_pi[p - 1][lane];
     const int lc = L.s_lcount[lane];
-    const OwnEntry* own = B.own + r * (size_t)B.lslots;
+    const Rows<const OwnEntry> own{B.own + (size_t)chunk * 64 * (size_t)B.lslots + lane};
     // The fill writes the interleaved layout (ivol_index: 16 bytes = 4 neighbouring columns of one row) that the
     // propagation reads: a lane computes the values of a group of 4 columns and stores them as one unit, 64 rows = 1 KB
     // contiguous per wave.  Parts start on a group (part_w is a multiple of 4) and rounds are whole groups.
@@ -681,7 +689,6 @@ __global__ void __launch_bounds__(kNT) k_sweep_balanced(const ColDesc* __restric
     const long k = chunk / HW64;
     const int c = (int)(chunk - k * HW64);
     const int y = c * 64 + lane;
-    const size_t r = (size_t)chunk * 64 + lane;
     const uint4* dp = reinterpret_cast<const uint4*>(desc + ((size_t)k * HW64 + c) * W);
     const int nwords = (W + 63) >> 6;
     for (int b = tid; b < nwords; b += kNT) L.smask[b] = B.colmask[(size_t)k * nwords + b];
@@ -741,7 +748,7 @@ __global__ void __launch_bounds__(kNT) k_sweep_balanced(const ColDesc* __restric
         // (where workgroups queue for the CUs or share them with other frames, only the heaviest ones cut dynamically: theirs are
         // the chains the kernel ends with, and the junctions a new range adds are work the others would only pay for)
         const bool dyn = B.steal_min > 0 && (B.steal_heavy_only == 0 || heavy >= 3);
-        EnvEntry* ent_row = B.ent + r * (size_t)B.eslots;
+        const Rows<EnvEntry> ent_row{B.ent + (size_t)chunk * 64 * (size_t)B.eslots + lane};
         int rid = wave, bstart = wave * kpr;
         bool have = false, run_now = wave < S0;  // have: this wave's ring columns hold a range's top entries
         int cnt = 0;
@@ -809,7 +816,7 @@ __global__ void __launch_bounds__(kNT) k_sweep_balanced(const ColDesc* __restric
     }
     const int g8 = lane >> 3, t8 = lane & 7, sh8 = lane & 56, row8 = wave * 8 + g8;
     {
-        EnvEntry* entr = B.ent + ((size_t)chunk * 64 + row8) * (size_t)B.eslots;
+        const Rows<EnvEntry> entr{B.ent + (size_t)chunk * 64 * (size_t)B.eslots + row8};
         merge_bulk(L, S, row8, t8, sh8, ring, entr);
     }
     __syncthreads();  // every wave is through with the rings: their LDS becomes the walk's lists
