@@ -1,8 +1,9 @@
 // fdcm_build.hip -- DT3 feature-map build on gfx950 (buildCpuFeaturemap<D>, dt3cpu.h:174-234).
 //
 // Volume layout in HBM, from the sweeps on: interleaved, [k][x/4][y][x%4] (ivol_index, fdcm_internal.h): 16 bytes hold 4
-// neighbouring columns of one row.  The sweeps write the transforms into `vol`, the propagation reads them and writes
-// `ivol`, the line integral reads `ivol` and writes its sums back into `vol`, which is what the search gathers from.
+// neighbouring columns of one row, and no kernel reads or writes another.  The sweeps write the transforms into `vol`, the
+// propagation reads them and writes `ivol`, the line integral reads `ivol` and writes its sums back into `vol`, which is
+// what the search gathers from.
 //
 // Kernels (W x H = feature size, m = slices, V = 4*m*W*H bytes):
 //   K0 k_seeds          clipped scene lines -> seed bitmap (1 bit per pixel, bits along y)   ~V/32
@@ -15,20 +16,15 @@
 //   K4 k_integral       directional prefix sum per slice, one sequential float chain per row / column of 16-byte
 //                       units; shallow and steep sweeps (the latter through LDS tiles) in one launch  read V, write V
 // Compiled with -ffp-contract=off; divide and sqrt are the correctly rounded forms.
-#include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 #include "fdcm_build_dev.h"
 #include "fdcm_internal.h"
-#include "fdcm_quotient.h"
 #include "fdcm_sweep.h"
 
 namespace fdcm {
-
 
 // ------------------------------------------------------------------------------------------ K0
 // drawLines (drawing.h:111-125): one block per clipped line, threads over its raster points.
@@ -281,33 +277,18 @@ __global__ void k_sqrt(float* __restrict__ vol, size_t n) {  // only for staged 
 // propagateOrientation (dt3cpu.cpp:77-107): each pixel's m-vector is loaded once into LDS
 // ([slice][thread], conflict free), the 4m steps S[c2] = min(S[c2], S[c1] + w) run there, and it
 // is stored once.  L2's final sqrt (imgproc.h:191-192) is applied on load.
-// Both variants read the y-fastest volume of the sweeps and write the interleaved volume (ivol_index) that the line
-// integral and the search work on.  A thread is a position of the interleaved slice, q = (g*H + y)*4 + c for pixel
-// (4g + c, y): 64 consecutive threads store 256 contiguous bytes and load 4 runs of 64 bytes (16 rows of 4 columns).
-struct PropPixel {
-    unsigned in_off, out_off;  // byte offsets inside a slice; 2^31: outside (columns of the last group past W)
-};
-__device__ __forceinline__ PropPixel prop_pixel(size_t q, int W, int H) {
-    const unsigned g = (unsigned)(q / ((size_t)H * 4)), r = (unsigned)(q % ((size_t)H * 4));
-    const unsigned y = r >> 2, x = 4 * g + (r & 3);
-    PropPixel pp;
-    pp.out_off = (unsigned)q * 4u;
-    pp.in_off = x < (unsigned)W ? (x * (unsigned)H + y) * 4u : 0x80000000u;
-    return pp;
-}
-
+// Both variants read the transforms and write the propagated volume in the same interleaved layout (ivol_index): a thread
+// is a position q of the slice and touches position q of every slice, 64 consecutive threads 256 contiguous bytes of each.
+// The padding (columns of the last group past W, the kSlicePad tail) is propagated like any pixel and never read as one.
 __global__ void k_propagate(const float* __restrict__ vol, float* __restrict__ ivol, int W, int H, int m,
                             const PropStep* __restrict__ steps, int nsteps, int apply_sqrt) {
     extern __shared__ float S[];
     const int bd = blockDim.x, tid = threadIdx.x;
-    const size_t q = (size_t)blockIdx.x * bd + tid, npix = (size_t)W * H, nq = ivol_slice_floats(W, H);
+    const size_t q = (size_t)blockIdx.x * bd + tid, nq = ivol_slice_floats(W, H);
     const bool ok = q < nq;
-    const PropPixel pp = prop_pixel(ok ? q : 0, W, H);
-    const bool in_il = (apply_sqrt & 2) != 0;  // the transforms are in the interleaved layout already (segmented L2 sweep)
-    const bool in = ok && (in_il || pp.in_off != 0x80000000u);
     for (int j = 0; j < m; ++j) {
-        float v = in ? (in_il ? vol[(size_t)j * nq + q] : vol[(size_t)j * npix + pp.in_off / 4]) : 0.f;
-        if (apply_sqrt & 1) v = sqrtf(v);
+        float v = ok ? vol[(size_t)j * nq + q] : 0.f;
+        if (apply_sqrt) v = sqrtf(v);
         S[j * bd + tid] = v;
     }
     for (int s = 0; s < nsteps; ++s) {
@@ -326,21 +307,21 @@ __global__ void k_propagate(const float* __restrict__ vol, float* __restrict__ i
 template <int M>
 __global__ void __launch_bounds__(256) k_propagate_reg(const float* __restrict__ vol, float* __restrict__ ivol, int W, int H,
                                                        const PropStep* __restrict__ steps, int apply_sqrt) {
-    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x, npix = (size_t)W * H, nq = ivol_slice_floats(W, H);
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nq = ivol_slice_floats(W, H);
     if (q >= nq) return;
     // One buffer descriptor per slice (scalar registers) + one 32-bit lane byte offset: addresses
     // cost no vector registers, so the M values are the kernel's whole register footprint.
-    PropPixel pp = prop_pixel(q, W, H);  // slices are < 2^30 pixels
-    const bool in_il = (apply_sqrt & 2) != 0;  // the transforms are in the interleaved layout already (segmented L2 sweep)
-    if (in_il) pp.in_off = pp.out_off;
-    apply_sqrt &= 1;
-    const size_t in_slice = in_il ? nq : npix;
-    const unsigned in_bytes = (unsigned)(in_slice * 4u), out_bytes = (unsigned)(nq * 4u);
+    const unsigned off = (unsigned)q * 4u, slice_bytes = (unsigned)(nq * 4u);  // slices are < 2^30 pixels
+    // The loads' copies of stride and offset are opaque to the compiler: knowing them equal to the stores', it keeps all M slice offsets
+    // in SGPRs from the loads to the stores (106, 30 to 270 of them spilled from M = 60 on, against 28); one alone hidden, M = 60 loses a wave.
+    size_t nq_in = nq; asm volatile("" : "+s"(nq_in));
+    unsigned off_in = off; asm volatile("" : "+v"(off_in));
+    const unsigned in_bytes = (unsigned)(nq_in * 4u);
     float S[M];
 #pragma unroll
     for (int j = 0; j < M; ++j) {
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vol) + (size_t)j * in_slice, 0, in_bytes, 0x00020000);
-        S[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, pp.in_off, 0, 0));
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(vol) + (size_t)j * nq_in, 0, in_bytes, 0x00020000);
+        S[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off_in, 0, 0));
     }
     if (apply_sqrt) {
 #pragma unroll
@@ -362,8 +343,8 @@ __global__ void __launch_bounds__(256) k_propagate_reg(const float* __restrict__
     }
 #pragma unroll
     for (int j = 0; j < M; ++j) {
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(ivol + (size_t)j * nq, 0, out_bytes, 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(S[j]), rs, pp.out_off, 0, 0);
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc(ivol + (size_t)j * nq, 0, slice_bytes, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(S[j]), rs, off, 0, 0);
     }
 }
 
@@ -695,210 +676,220 @@ void reserve_build(fdcm_featuremap* fm, const BuildLayout& L) {
     if (L.empty) return;
     // every buffer of the build is reserved before its first kernel is queued: an allocation between two stages (a
     // handle's first build) stalls the host for 0.5 - 1 ms while the GPU idles inside the stage events' span
-    fm->vol.reserve(L.vol); fm->bitmap.reserve(L.bitmap); fm->ivol.reserve(L.ivol); fm->offtab.reserve(L.offtab);
-    fm->coldesc.reserve(L.coldesc); fm->colmask.reserve(L.colmask);
-    const void* stack_before = fm->stack.p;
-    fm->stack.reserve(L.stack);
-    if (fm->stack.p != stack_before) { fm->k2_cost_chunks = 0; fm->steals_off = 0; }  // a new scratch: no cost table, no steal counter
-    fm->stage.reserve(L.plan); fm->plan.reserve(L.plan);
+    BuildBuffers& b = fm->build;
+    fm->vol.reserve(L.vol); b.bitmap.reserve(L.bitmap); fm->ivol.reserve(L.ivol);
+    b.coldesc.reserve(L.coldesc); b.colmask.reserve(L.colmask);
+    const void *stack_before = b.stack.p, *offtab_before = b.offtab.p;
+    b.stack.reserve(L.stack); b.offtab.reserve(L.offtab);
+    if (b.stack.p != stack_before) fm->sweep.reset();  // a new scratch: no cost table, no steal counter
+    if (b.offtab.p != offtab_before) fm->groups.reset();
+    b.stage.reserve(L.plan); b.plan.reserve(L.plan);
+}
+
+// ---- the stages of a build, in run_build's order: each takes the layout, the plan's device pointers and the handle, and queues on its stream
+struct PlanOnDevice {  // the uploaded blob's parts (BuildLayout::off_*)
+    const RasterLine* raster; const int* slice_first; const PropStep* prop; const IntegralDesc* integral; int n_raster, n_prop;
+};
+static void mark(fdcm_featuremap* fm, int i, bool on) { if (on) FDCM_HIP(hipEventRecord(fm->timing.ev[i], fm->stream)); }
+
+// The balanced sweep's launch order and dynamic cuts.  Queues the order from the previous build's costs and the steal counter's
+// reset, both in front of the plan's upload; fills proxy_cost when the order takes the proxy instead, which travels with the plan.
+static SweepBuf setup_balanced_sweep(fdcm_featuremap* fm, const BuildLayout& L, const BuildPlan& plan, std::vector<int32_t>& proxy_cost) {
+    SweepBuf sb{};
+    hipStream_t st = fm->stream;
+    char* sp = (char*)fm->build.stack.p;
+    const int W = (int)plan.W;
+    const long nchunks = L.nchunks, resident = 2L * device_cus(fm->device);
+    // Launch order: workgroups are dispatched in index order, and when there are more of them than the GPU holds at once
+    // (two per CU) the long ones must not start last.  Nothing cheap predicts a chunk's time well enough, the previous
+    // build of the same shape does: scenes of a stream change little from frame to frame.  A handle's first build, and
+    // every build after a change of size, takes the host's proxy per chunk (sweep_cost_proxy), which arrives with the plan.
+    const bool want_order = test_switches().sweep_order || nchunks > resident;
+    const bool have_cost = want_order && fm->sweep.cost_chunks == nchunks && fm->sweep.cost_w == W;
+    if (want_order && !have_cost) sweep_cost_proxy(plan, proxy_cost);
+    if (have_cost) launch_sweep_order(st, (const int*)(sp + L.o_cost), (int)nchunks, (int*)(sp + L.o_ord));
+    if (want_order) (have_cost ? g_order_from_history : g_order_from_proxy).fetch_add(1, std::memory_order_relaxed);
+    sb.ent = (EnvEntry*)(sp + L.o_ent); sb.own = (OwnEntry*)(sp + L.o_own); sb.cost = (int*)(sp + L.o_cost);
+    sb.order = want_order ? (const int*)(sp + L.o_ord) : nullptr;
+    // Dynamic cuts (a wave out of columns begins a new range in what nobody has started): they shorten the heaviest
+    // workgroup's chain and add junctions, i.e. work -- worth it where the kernel lasts as long as its slowest workgroup
+    // (all workgroups resident at once, the GPU to this handle), not where workgroups queue for the CUs or frames of a
+    // pipeline share them (config 2: one blocking build 0.354 -> 0.333 ms over four scenes; four frames in flight 69.7 ->
+    // 68.4 M matches/s; config 3: 0.76 -> 0.81 ms).  FDCM_SWEEP_STEAL=<blocks> forces a threshold (0: never) for the tests.
+    sb.steal_min = -1;  // the kernel's default threshold
+    sb.steal_heavy_only = (!fm->shares_gpu && nchunks <= resident) ? 0 : 1;
+    sb.steals = (int*)(sp + L.o_steals);
+    if (fm->sweep.steals_off != L.o_steals) FDCM_HIP(hipMemsetAsync(sb.steals, 0, 256, st));  // a new scratch (or shape): count from 0
+    sb.eslots = L.slots; sb.lslots = L.slots; sb.colmask = (const unsigned long long*)fm->build.colmask.p;
+    fm->sweep.steals_off = L.o_steals; fm->sweep.cost_chunks = nchunks; fm->sweep.cost_w = W;
+    return sb;
+}
+// plan upload: one pinned blob, one async copy (the proxy cost region only when the sweep's launch order takes it)
+static PlanOnDevice upload_plan(fdcm_featuremap* fm, const BuildLayout& L, const BuildPlan& plan, const std::vector<int32_t>& proxy_cost) {
+    const bool proxy_order = !proxy_cost.empty();
+    fm->off_keys = L.off_keys;
+    char* hs = (char*)fm->build.stage.p;
+    auto put = [hs](size_t off, const auto& v) { if (!v.empty()) std::memcpy(hs + off, v.data(), v.size() * sizeof(v[0])); };
+    put(L.off_raster, plan.raster); put(L.off_prop, plan.prop); put(L.off_integral, plan.integral);
+    put(L.off_keys, plan.keys); put(L.off_slice, plan.slice_first); put(L.off_cost, proxy_cost);
+    const char* dp = (const char*)fm->build.plan.p;
+    FDCM_HIP(hipMemcpyAsync(fm->build.plan.p, hs, proxy_order ? L.plan : L.off_cost, hipMemcpyHostToDevice, fm->stream));
+    if (proxy_order)
+        launch_sweep_order(fm->stream, (const int*)(dp + L.off_cost), (int)L.nchunks, (int*)((char*)fm->build.stack.p + L.o_ord));
+    return PlanOnDevice{(const RasterLine*)(dp + L.off_raster), (const int*)(dp + L.off_slice), (const PropStep*)(dp + L.off_prop),
+                        (const IntegralDesc*)(dp + L.off_integral), (int)plan.raster.size(), (int)plan.prop.size()};
+}
+// pass 1: the seeds and the column descriptors
+static void stage_pass1(fdcm_featuremap* fm, const BuildLayout& L, const PlanOnDevice& P) {
+    hipStream_t st = fm->stream;
+    const int W = (int)fm->W, H = (int)fm->H, m = (int)fm->m, HW64 = L.HW64;
+    ColDesc* d_desc = fm->build.coldesc.as<ColDesc>();
+    fm->built.seeds_fused = HW64 <= 64;
+    if (fm->built.seeds_fused) {
+        // the tile kernel rasterises the seeds of its columns itself (LDS): no bitmap, no k_seeds, no stage of its own
+        const int XT = HW64 > 32 ? 32 : 64;
+        const dim3 grid((unsigned)((W + XT - 1) / XT), (unsigned)m);
+        const size_t lds = (size_t)HW64 * (XT + 1) * sizeof(uint4) + (size_t)HW64 * XT * 8;
+        unsigned* cm = (unsigned*)fm->build.colmask.p;
+        if (HW64 <= 16) hipLaunchKernelGGL((k_coldesc_tile<16, 64>), grid, dim3(256), lds, st, P.raster, P.slice_first, d_desc, W, H, HW64, cm);
+        else if (HW64 <= 32) hipLaunchKernelGGL((k_coldesc_tile<32, 64>), grid, dim3(256), lds, st, P.raster, P.slice_first, d_desc, W, H, HW64, cm);
+        else hipLaunchKernelGGL((k_coldesc_tile<64, 32>), grid, dim3(256), lds, st, P.raster, P.slice_first, d_desc, W, H, HW64, cm);
+        return;
+    }
+    const long ncols = (long)m * W;
+    unsigned long long* bitmap = fm->build.bitmap.as<unsigned long long>();
+    FDCM_HIP(hipMemsetAsync(bitmap, 0, (size_t)ncols * HW64 * 8, st));
+    if (P.n_raster > 0) hipLaunchKernelGGL(k_seeds, dim3((unsigned)P.n_raster), dim3(256), 0, st, P.raster, bitmap, W, H, HW64);
+    mark(fm, 1, fm->built.stage_events);
+    hipLaunchKernelGGL(k_coldesc, dim3((unsigned)((ncols + 3) / 4)), dim3(256), 0, st, bitmap, d_desc, W, HW64, ncols);
+}
+// the sweep: both 1-D passes of the distance transform, from the descriptors into `vol`
+static void stage_sweep(fdcm_featuremap* fm, const BuildLayout& L, const SweepBuf& sb) {
+    hipStream_t st = fm->stream;
+    const int W = (int)fm->W, H = (int)fm->H, m = (int)fm->m, HW64 = L.HW64;
+    const ColDesc* d_desc = fm->build.coldesc.as<ColDesc>();
+    float* vol = fm->vol.as<float>();
+    if (fm->distance == FDCM_L1) {
+        // both L1 sweeps with one pass over the volume: minima per (row, word), their prefix / suffix over the row's words, then word by word
+        const int nwords = (W + 63) / 64;
+        const long wwaves = (long)m * HW64 * nwords, nrows = (long)m * HW64 * 64;
+        float2* mins = (float2*)fm->build.stack.p;
+        hipLaunchKernelGGL(k_l1_word_mins, dim3((unsigned)((wwaves + 3) / 4)), dim3(256), 0, st, d_desc, mins, W, HW64, nwords, wwaves);
+        hipLaunchKernelGGL(k_l1_carries, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, st, mins, nwords, nrows);
+        hipLaunchKernelGGL(k_l1_word, dim3((unsigned)((wwaves + 3) / 4)), dim3(256), 0, st, d_desc, (const float2*)mins, vol, W, H, HW64, nwords, wwaves);
+    } else if (L.balanced) launch_sweep_balanced(st, d_desc, vol, W, H, HW64, L.nchunks, sb);
+    else launch_sweep_literal(st, d_desc, vol, W, H, HW64, L.nchunks, fm->build.stack.p);
+}
+// orientation propagation, `vol` -> `ivol`, with L2's sqrt; a staged (test) build that stops at the transforms only takes the sqrt
+static void stage_propagate(fdcm_featuremap* fm, const PlanOnDevice& P, bool transforms_only) {
+    hipStream_t st = fm->stream;
+    const int W = (int)fm->W, H = (int)fm->H, m = (int)fm->m;
+    const size_t nq = ivol_slice_floats(W, H);
+    float *vol = fm->vol.as<float>(), *ivol = fm->ivol.as<float>();
+    const int apply_sqrt = fm->distance == FDCM_L2;
+    if (transforms_only) {
+        const size_t nel = (size_t)m * nq;  // (padding elements: harmless)
+        if (apply_sqrt) hipLaunchKernelGGL(k_sqrt, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, vol, nel);
+        return;
+    }
+    const dim3 grid((unsigned)((nq + 255) / 256));
+    switch (m) {  // the depths with a register kernel
+#define FDCM_PROPAGATE(M) \
+    case M: hipLaunchKernelGGL(k_propagate_reg<M>, grid, dim3(256), 0, st, (const float*)vol, ivol, W, H, P.prop, apply_sqrt); return;
+        FDCM_PROPAGATE(30) FDCM_PROPAGATE(60) FDCM_PROPAGATE(90) FDCM_PROPAGATE(120) FDCM_PROPAGATE(180)
+#undef FDCM_PROPAGATE
+    }
+    int bd = 256;
+    while (bd > 64 && (size_t)m * bd * sizeof(float) > 64 * 1024) bd >>= 1;
+    const size_t lds = (size_t)m * bd * sizeof(float);
+    if (lds > 64 * 1024) FDCM_HIP(hipFuncSetAttribute((const void*)k_propagate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_propagate, dim3((unsigned)((nq + bd - 1) / bd)), dim3(bd), lds, st, (const float*)vol, ivol, W, H, m, P.prop, P.n_prop, apply_sqrt);
+}
+// line integral, `ivol` -> `vol`
+static void stage_integral(fdcm_featuremap* fm, const PlanOnDevice& P) {
+    hipStream_t st = fm->stream;
+    const int W = (int)fm->W, H = (int)fm->H, m = (int)fm->m;
+    const int chains = 2 * (W > H ? W : H), tab_stride = sh_tab_stride(W);
+    int* d_tab = fm->build.offtab.as<int>();
+    if (!(fm->groups.m == m && fm->groups.steps == W)) {  // the table only depends on the keys (fixed per handle) and the size
+        hipLaunchKernelGGL(k_groups, dim3((unsigned)((tab_stride + 255) / 256), (unsigned)m), dim3(256), 0, st, P.integral, d_tab, W, tab_stride);
+        fm->groups.m = m; fm->groups.steps = W;
+    }
+    const int shw = (long)m * ((chains + kShOwn - 1) / kShOwn) > 8192 ? 4 : 1;  // working waves per workgroup of a shallow slice
+    // steep slices: 60 own chains per block while the launch is small, 124 / 252 once such blocks would outnumber
+    // what the GPU holds several times over (fewer columns read twice; see integral_steep).
+    const long narrow_blocks = (long)m * ((chains + 59) / 60), cus = device_cus(fm->device);
+    const int xc = test_switches().int_xc ? test_switches().int_xc : (narrow_blocks > 64 * cus ? 256 : (narrow_blocks > 12 * cus ? 128 : 64));
+    const dim3 igrid((unsigned)((chains + kShOwn - 1) / kShOwn), (unsigned)m);
+    int kstride = 1;
+    // slices are visited in a strided order (coprime to the depth, near half of it) so that steep and shallow ones
+    // overlap -- once the blocks queue for the CUs (config 3: 4 260 blocks, 0.45 - 0.49 against 0.50 - 0.51 ms); a small
+    // launch (config 2: 1 080 blocks, four per CU) is faster in index order (0.070 against 0.077 ms)
+    const bool small_launch = (long)m * igrid.x <= 6L * cus;
+    if (m > 2 && !small_launch) {
+        auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
+        kstride = m / 2 + 1;
+        while (gcd(kstride, m) != 1) ++kstride;
+    }
+#define FDCM_INTEGRAL(XC)                                                                                                    \
+    do {                                                                                                                     \
+        constexpr size_t lds = integral_lds_bytes<XC>();                                                                     \
+        static_assert(lds <= 160 * 1024, "tile pair must fit a CU's LDS");                                                   \
+        if (lds > 64 * 1024)                                                                                                 \
+            FDCM_HIP(hipFuncSetAttribute((const void*)k_integral<XC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        hipLaunchKernelGGL(k_integral<XC>, igrid, dim3(256), lds, st, (const float*)fm->ivol.as<float>(), fm->vol.as<float>(), \
+                           W, H, P.integral, d_tab, shw, kstride);                                                           \
+    } while (0)
+    if (xc == 256) FDCM_INTEGRAL(256); else if (xc == 128) FDCM_INTEGRAL(128); else FDCM_INTEGRAL(64);
+#undef FDCM_INTEGRAL
 }
 
 void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
     const auto t0 = std::chrono::steady_clock::now();
     const BuildLayout L = build_layout(plan, fm->distance, stop_after);
     reserve_build(fm, L);
-    fm->W = plan.W; fm->H = plan.H; fm->m = plan.m; fm->tx = plan.tx; fm->ty = plan.ty;
-    fm->keys = plan.keys;
-    fm->last_build = fdcm_build_timing{};
+    fm->W = plan.W; fm->H = plan.H; fm->m = plan.m; fm->tx = plan.tx; fm->ty = plan.ty; fm->keys = plan.keys;
+    fm->last_build = fdcm_build_timing{}; fm->built.reset(); fm->holds = VolStage::none;
     if (L.empty) return;
-    hipStream_t st = fm->stream;
-    const int W = (int)plan.W, H = (int)plan.H, m = (int)plan.m, HW64 = L.HW64;
-    const long ncols = (long)m * W, nchunks = L.nchunks;
     SweepBuf sb{};
-    bool proxy_order = false;
-    std::vector<int32_t> proxy_cost;
-    char* sp = (char*)fm->stack.p;
-    if (!L.balanced) {  // the L1 minima or the literal pass's scratch take the whole of `stack`
-        fm->k2_cost_chunks = 0; fm->steals_off = 0;
-    } else {
-        // Launch order: workgroups are dispatched in index order, and when there are more of them than the GPU holds at once
-        // (two per CU) the long ones must not start last.  Nothing cheap predicts a chunk's time well enough, the previous
-        // build of the same shape does: scenes of a stream change little from frame to frame.  A handle's first build, and
-        // every build after a change of size, takes the host's proxy per chunk (make_build_plan), which arrives with the plan.
-        const bool want_order = test_switches().sweep_order || nchunks > 2L * device_cus(fm->device);
-        const bool have_cost = want_order && fm->k2_cost_chunks == nchunks && fm->k2_cost_w == W;
-        proxy_order = want_order && !have_cost;
-        if (proxy_order) sweep_cost_proxy(plan, proxy_cost);
-        if (have_cost) launch_sweep_order(st, (const int*)(sp + L.o_cost), (int)nchunks, (int*)(sp + L.o_ord));
-        sb.ent = (EnvEntry*)(sp + L.o_ent); sb.own = (OwnEntry*)(sp + L.o_own);
-        sb.order = (have_cost || proxy_order) ? (const int*)(sp + L.o_ord) : nullptr;
-        sb.cost = (int*)(sp + L.o_cost);
-        // Dynamic cuts (a wave out of columns begins a new range in what nobody has started): they shorten the heaviest
-        // workgroup's chain and add junctions, i.e. work -- worth it where the kernel lasts as long as its slowest workgroup
-        // (all workgroups resident at once, the GPU to this handle), not where workgroups queue for the CUs or frames of a
-        // pipeline share them (config 2: one blocking build 0.354 -> 0.333 ms over four scenes; four frames in flight 69.7 ->
-        // 68.4 M matches/s; config 3: 0.76 -> 0.81 ms).  FDCM_SWEEP_STEAL=<blocks> forces a threshold (0: never) for the tests.
-        sb.steal_min = -1;  // the kernel's default threshold
-        sb.steal_heavy_only = (!fm->shares_gpu && nchunks <= 2L * device_cus(fm->device)) ? 0 : 1;
-        sb.steals = (int*)(sp + L.o_steals);
-        if (fm->steals_off != L.o_steals) FDCM_HIP(hipMemsetAsync(sb.steals, 0, 256, st));  // a new scratch (or shape): count from 0
-        fm->steals_off = L.o_steals;
-        sb.eslots = L.slots; sb.lslots = L.slots;
-        sb.colmask = (const unsigned long long*)fm->colmask.p;
-        fm->k2_cost_chunks = nchunks; fm->k2_cost_w = W;
-    }
-
-    // ---- plan upload: one pinned blob, one async copy
-    fm->off_keys = L.off_keys;
-    if (sb.order) (proxy_order ? g_order_from_proxy : g_order_from_history).fetch_add(1, std::memory_order_relaxed);
-    char* hs = (char*)fm->stage.p;
-    if (!plan.raster.empty()) std::memcpy(hs + L.off_raster, plan.raster.data(), plan.raster.size() * sizeof(RasterLine));
-    std::memcpy(hs + L.off_prop, plan.prop.data(), plan.prop.size() * sizeof(PropStep));
-    std::memcpy(hs + L.off_integral, plan.integral.data(), plan.integral.size() * sizeof(IntegralDesc));
-    std::memcpy(hs + L.off_keys, plan.keys.data(), plan.keys.size() * sizeof(float));
-    std::memcpy(hs + L.off_slice, plan.slice_first.data(), plan.slice_first.size() * sizeof(int32_t));
-    if (proxy_order) std::memcpy(hs + L.off_cost, proxy_cost.data(), proxy_cost.size() * sizeof(int32_t));
-    FDCM_HIP(hipMemcpyAsync(fm->plan.p, hs, proxy_order ? L.plan : L.off_cost, hipMemcpyHostToDevice, st));
-    if (proxy_order) launch_sweep_order(st, (const int*)((const char*)fm->plan.p + L.off_cost), (int)nchunks, (int*)(sp + L.o_ord));
-    const int n_raster = (int)plan.raster.size(), n_prop = (int)plan.prop.size();
-    const char* dp = (const char*)fm->plan.p;
-    const RasterLine* d_raster = (const RasterLine*)(dp + L.off_raster);
-    const PropStep* d_prop = (const PropStep*)(dp + L.off_prop);
-    const IntegralDesc* d_int = (const IntegralDesc*)(dp + L.off_integral);
-    float* vol = fm->vol.as<float>();
-    hipEvent_t* ev = fm->timing.ev;
-
-    fm->build_host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    fm->stage_events = fm->want_stage_events == 1;  // (an event between two kernels costs a blocking frame 3 - 5 us: fdcm_featuremap_stage_timing)
-    fm->total_events = fm->want_stage_events != 0;
-    if (fm->total_events) FDCM_HIP(hipEventRecord(ev[0], st));
-    ColDesc* d_desc = fm->coldesc.as<ColDesc>();
-    if (HW64 <= 64) {
-        // the tile kernel rasterises the seeds of its columns itself (LDS): no bitmap, no k_seeds, no stage of its own
-        fm->seeds_fused = true;
-        const int* d_first = (const int*)(dp + L.off_slice);
-        const int XT = HW64 > 32 ? 32 : 64;
-        const dim3 grid((unsigned)((W + XT - 1) / XT), (unsigned)m);
-        const size_t lds = (size_t)HW64 * (XT + 1) * sizeof(uint4) + (size_t)HW64 * XT * 8;
-        unsigned* cm = (unsigned*)fm->colmask.p;
-        if (HW64 <= 16) hipLaunchKernelGGL((k_coldesc_tile<16, 64>), grid, dim3(256), lds, st, d_raster, d_first, d_desc, W, H, HW64, cm);
-        else if (HW64 <= 32) hipLaunchKernelGGL((k_coldesc_tile<32, 64>), grid, dim3(256), lds, st, d_raster, d_first, d_desc, W, H, HW64, cm);
-        else hipLaunchKernelGGL((k_coldesc_tile<64, 32>), grid, dim3(256), lds, st, d_raster, d_first, d_desc, W, H, HW64, cm);
-    } else {
-        fm->seeds_fused = false;
-        const long bitmap_words = ncols * HW64;
-        FDCM_HIP(hipMemsetAsync(fm->bitmap.p, 0, (size_t)bitmap_words * 8, st));
-        if (n_raster > 0)
-            hipLaunchKernelGGL(k_seeds, dim3((unsigned)n_raster), dim3(256), 0, st, d_raster,
-                               fm->bitmap.as<unsigned long long>(), W, H, HW64);
-        if (fm->stage_events) FDCM_HIP(hipEventRecord(ev[1], st));
-        hipLaunchKernelGGL(k_coldesc, dim3((unsigned)((ncols + 3) / 4)), dim3(256), 0, st,
-                           fm->bitmap.as<unsigned long long>(), d_desc, W, HW64, ncols);
-    }
-    if (fm->stage_events) FDCM_HIP(hipEventRecord(ev[2], st));
-    if (fm->distance == FDCM_L1) {
-        // both L1 sweeps with one pass over the volume: minima per (row, word), their prefix / suffix over the row's words, then word by word
-        const int nwords = (W + 63) / 64;
-        const long wwaves = (long)m * HW64 * nwords;
-        float2* mins = (float2*)fm->stack.p;  // reserved above
-        hipLaunchKernelGGL(k_l1_word_mins, dim3((unsigned)((wwaves + 3) / 4)), dim3(256), 0, st, d_desc, mins, W, HW64, nwords, wwaves);
-        hipLaunchKernelGGL(k_l1_carries, dim3((unsigned)(((long)m * HW64 * 64 + 255) / 256)), dim3(256), 0, st, mins, nwords, (long)m * HW64 * 64);
-        hipLaunchKernelGGL(k_l1_word, dim3((unsigned)((wwaves + 3) / 4)), dim3(256), 0, st, d_desc, (const float2*)mins, vol, W, H, HW64, nwords, wwaves);
-    } else if (L.balanced) {
-        launch_sweep_balanced(st, d_desc, vol, W, H, HW64, nchunks, sb);
-    } else {
-        launch_sweep_literal(st, d_desc, vol, W, H, HW64, nchunks, fm->stack.p);
-    }
-    if (fm->stage_events) FDCM_HIP(hipEventRecord(ev[3], st));
-    const bool want_sqrt = fm->distance == FDCM_L2;
-    if (stop_after >= 2) {
-        const size_t nq = ivol_slice_floats(W, H);
-        float* ivol = fm->ivol.as<float>();
-        const unsigned pblocks = (unsigned)((nq + 255) / 256);
-        const int sq = (want_sqrt ? 1 : 0) | 2;  // (2: the sweeps write the transforms interleaved)
-        if (m == 30) hipLaunchKernelGGL(k_propagate_reg<30>, dim3(pblocks), dim3(256), 0, st, (const float*)vol, ivol, W, H, d_prop, sq);
-        else if (m == 60) hipLaunchKernelGGL(k_propagate_reg<60>, dim3(pblocks), dim3(256), 0, st, (const float*)vol, ivol, W, H, d_prop, sq);
-        else if (m == 90) hipLaunchKernelGGL(k_propagate_reg<90>, dim3(pblocks), dim3(256), 0, st, (const float*)vol, ivol, W, H, d_prop, sq);
-        else if (m == 120) hipLaunchKernelGGL(k_propagate_reg<120>, dim3(pblocks), dim3(256), 0, st, (const float*)vol, ivol, W, H, d_prop, sq);
-        else if (m == 180) hipLaunchKernelGGL(k_propagate_reg<180>, dim3(pblocks), dim3(256), 0, st, (const float*)vol, ivol, W, H, d_prop, sq);
-        else {
-            int bd = 256;
-            while (bd > 64 && (size_t)m * bd * sizeof(float) > 64 * 1024) bd >>= 1;
-            const size_t lds = (size_t)m * bd * sizeof(float);
-            if (lds > 64 * 1024)
-                FDCM_HIP(hipFuncSetAttribute((const void*)k_propagate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_propagate, dim3((unsigned)((nq + bd - 1) / bd)), dim3(bd), lds, st, (const float*)vol, ivol, W, H, m,
-                               d_prop, n_prop, sq);
-        }
-    } else if (want_sqrt) {
-        const size_t nel = (size_t)m * ivol_slice_floats(W, H);  // (padding elements: harmless)
-        hipLaunchKernelGGL(k_sqrt, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, vol, nel);
-    }
-    if (fm->stage_events) FDCM_HIP(hipEventRecord(ev[4], st));
-    if (stop_after >= 3) {
-        const int chains = 2 * (W > H ? W : H);
-        const int tab_stride = sh_tab_stride(W);
-        int* d_tab = fm->offtab.as<int>();
-        if (!(fm->off_m == m && fm->off_steps == W)) {  // the table only depends on the keys (fixed per handle) and the size
-            hipLaunchKernelGGL(k_groups, dim3((unsigned)((tab_stride + 255) / 256), (unsigned)m), dim3(256), 0, st, d_int, d_tab, W, tab_stride);
-            fm->off_m = m; fm->off_steps = W;
-        }
-        int shw = (long)m * ((chains + kShOwn - 1) / kShOwn) > 8192 ? 4 : 1;  // working waves per workgroup of a shallow slice
-        // steep slices: 60 own chains per block while the launch is small, 124 / 252 once such blocks would outnumber
-        // what the GPU holds several times over (fewer columns read twice; see integral_steep).
-        const long narrow_blocks = (long)m * ((chains + 59) / 60), cus = device_cus(fm->device);
-        const int xc = test_switches().int_xc ? test_switches().int_xc : (narrow_blocks > 64 * cus ? 256 : (narrow_blocks > 12 * cus ? 128 : 64));
-        const dim3 igrid((unsigned)((chains + kShOwn - 1) / kShOwn), (unsigned)m);
-        int kstride = 1;
-        // slices are visited in a strided order (coprime to the depth, near half of it) so that steep and shallow ones
-        // overlap -- once the blocks queue for the CUs (config 3: 4 260 blocks, 0.45 - 0.49 against 0.50 - 0.51 ms); a small
-        // launch (config 2: 1 080 blocks, four per CU) is faster in index order (0.070 against 0.077 ms)
-        const bool small_launch = (long)m * igrid.x <= 6L * cus;
-        if (m > 2 && !small_launch) {
-            auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
-            kstride = m / 2 + 1;
-            while (gcd(kstride, m) != 1) ++kstride;
-        }
-#define FDCM_INTEGRAL(XC)                                                                                                        \
-        do {                                                                                                                     \
-            constexpr size_t lds = integral_lds_bytes<XC>();                                                                     \
-            static_assert(lds <= 160 * 1024, "tile pair must fit a CU's LDS");                                                   \
-            if (lds > 64 * 1024)                                                                                                 \
-                FDCM_HIP(hipFuncSetAttribute((const void*)k_integral<XC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(k_integral<XC>, igrid, dim3(256), lds, st, (const float*)fm->ivol.as<float>(), vol, W, H, d_int,  \
-                               d_tab, shw, kstride);                                                               \
-        } while (0)
-        if (xc == 256) FDCM_INTEGRAL(256); else if (xc == 128) FDCM_INTEGRAL(128); else FDCM_INTEGRAL(64);
-#undef FDCM_INTEGRAL
-    }
-    fm->vol_stage = stop_after >= 3 ? 3 : (stop_after == 2 ? 2 : 1);
-    if (fm->total_events) FDCM_HIP(hipEventRecord(ev[5], st));
+    std::vector<int32_t> proxy_cost;  // (stays empty unless the sweep's launch order takes it)
+    if (L.balanced) sb = setup_balanced_sweep(fm, L, plan, proxy_cost);
+    else fm->sweep.reset();  // the L1 minima or the literal pass's scratch take the whole of `stack`
+    const PlanOnDevice P = upload_plan(fm, L, plan, proxy_cost);
+    BuildRecord& b = fm->built;
+    b.host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    b.stage_events = fm->want_stage_events == 1;  // (an event between two kernels costs a blocking frame 3 - 5 us: fdcm_featuremap_stage_timing)
+    b.total_events = fm->want_stage_events != 0;
+    mark(fm, 0, b.total_events);
+    stage_pass1(fm, L, P);  // (event 1 behind its seeds, where they are a kernel of their own)
+    mark(fm, 2, b.stage_events);
+    stage_sweep(fm, L, sb);
+    mark(fm, 3, b.stage_events);
+    stage_propagate(fm, P, stop_after < 2);
+    mark(fm, 4, b.stage_events);
+    if (stop_after >= 3) stage_integral(fm, P);
+    fm->holds = stop_after >= 3 ? VolStage::integrated : (stop_after == 2 ? VolStage::propagated : VolStage::transforms);
+    mark(fm, 5, b.total_events);
     FDCM_HIP(hipGetLastError());
-    fm->build_pending = true;  // not waited for here: see finish_build
+    b.pending = true;  // not waited for here: see finish_build
 }
 
 void finish_build(fdcm_featuremap* fm) {
-    if (!fm->build_pending) return;
-    fm->build_pending = false;
+    if (!fm->built.pending) return;
+    fm->built.pending = false;
     FDCM_HIP(hipSetDevice(fm->device));
     FDCM_HIP(hipStreamSynchronize(fm->stream));
     hipEvent_t* ev = fm->timing.ev;
     fdcm_build_timing& bt = fm->last_build;
-    if (fm->stage_events) {
-        if (fm->seeds_fused) {
-            FDCM_HIP(hipEventElapsedTime(&bt.pass1_ms, ev[0], ev[2]));  // (seeds_ms stays 0: k_coldesc_tile draws them)
-        } else {
-            FDCM_HIP(hipEventElapsedTime(&bt.seeds_ms, ev[0], ev[1]));
-            FDCM_HIP(hipEventElapsedTime(&bt.pass1_ms, ev[1], ev[2]));
-        }
+    if (fm->built.stage_events) {
+        if (!fm->built.seeds_fused) FDCM_HIP(hipEventElapsedTime(&bt.seeds_ms, ev[0], ev[1]));  // (else 0: k_coldesc_tile draws them)
+        FDCM_HIP(hipEventElapsedTime(&bt.pass1_ms, ev[fm->built.seeds_fused ? 0 : 1], ev[2]));
         FDCM_HIP(hipEventElapsedTime(&bt.pass2_ms, ev[2], ev[3]));
         FDCM_HIP(hipEventElapsedTime(&bt.propagate_ms, ev[3], ev[4]));
         FDCM_HIP(hipEventElapsedTime(&bt.integral_ms, ev[4], ev[5]));
     }
-    float span = 0.f;
-    if (fm->total_events) FDCM_HIP(hipEventElapsedTime(&span, ev[0], ev[5]));
-    bt.span_ms = span;
-    bt.total_ms = fm->build_host_ms + span;  // host preparation + the kernels' span on the device
+    if (fm->built.total_events) FDCM_HIP(hipEventElapsedTime(&bt.span_ms, ev[0], ev[5]));  // (0 without events: run_build cleared it)
+    bt.total_ms = fm->built.host_ms + bt.span_ms;  // host preparation + the kernels' span on the device
 }
 
 }  // namespace fdcm

@@ -23,9 +23,6 @@ int device_cus(int device) {
     if (c <= 0) FDCM_HIP(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, device));
     return c;
 }
-}  // namespace fdcm
-
-namespace fdcm {
 const char* last_error_cstr();
 static thread_local int g_device = 0;
 
@@ -59,9 +56,9 @@ static void upload_keys_only(fdcm_featuremap* fm) {
     keys_only.W = fm->W; keys_only.H = fm->H; keys_only.m = fm->m; keys_only.keys = fm->keys;
     const BuildLayout L = build_layout(keys_only, fm->distance, 3);
     fm->off_keys = L.off_keys;
-    fm->plan.reserve(std::max<size_t>(16, L.plan));
+    fm->build.plan.reserve(std::max<size_t>(16, L.plan));
     if (!fm->keys.empty())
-        FDCM_HIP(hipMemcpy((char*)fm->plan.p + fm->off_keys, fm->keys.data(), fm->keys.size() * sizeof(float), hipMemcpyHostToDevice));
+        FDCM_HIP(hipMemcpy((char*)fm->build.plan.p + fm->off_keys, fm->keys.data(), fm->keys.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
 static void destroy(fdcm_featuremap* fm) {
@@ -69,9 +66,7 @@ static void destroy(fdcm_featuremap* fm) {
     (void)hipSetDevice(fm->device);
     if (fm->stream) (void)hipStreamSynchronize(fm->stream);
     if (fm->prep_stream) (void)hipStreamSynchronize(fm->prep_stream);
-    fm->vol.release(); fm->ivol.release(); fm->bitmap.release(); fm->coldesc.release(); fm->colmask.release(); fm->offtab.release(); fm->stack.release(); fm->plan.release(); fm->stage.release();
-    fm->s_scene.release(); fm->s_pairs.release(); fm->s_records.release(); fm->s_flags.release(); fm->s_out.release(); fm->s_work.release(); fm->s_tail.release(); fm->s_tail_out.release(); fm->s_eval.release(); fm->s_eval_stage.release();
-    fm->s_counter.release(); fm->s_stage.release(); fm->s_cnt.release(); fm->s_bins.release(); fm->s_bins_stage.release();
+    fm->vol.release(); fm->ivol.release(); fm->build.release(); fm->search.release();
     if (fm->timing.created)
         for (auto& e : fm->timing.ev) (void)hipEventDestroy(e);
     if (fm->stream) (void)hipStreamDestroy(fm->stream);
@@ -171,16 +166,10 @@ int fdcm_featuremap_slice(const fdcm_featuremap* fm, int64_t k, float* out_host)
         require(k >= 0 && k < fm->m, "slice index out of range");
         finish_build(const_cast<fdcm_featuremap*>(fm));
         FDCM_HIP(hipSetDevice(fm->device));
-        const size_t npix = (size_t)fm->W * fm->H;
-        if (!fm->current_interleaved()) {  // a partial build (tests of the stages) that stopped before the propagation
-            FDCM_HIP(hipMemcpy(out_host, fm->vol.as<float>() + (size_t)k * npix, npix * sizeof(float), hipMemcpyDeviceToHost));
-            return;
-        }
         const size_t sl = ivol_slice_floats(fm->W, fm->H);
         std::vector<float> tmp(sl);
         FDCM_HIP(hipMemcpy(tmp.data(), fm->current() + (size_t)k * sl, sl * sizeof(float), hipMemcpyDeviceToHost));
-        for (int64_t x = 0; x < fm->W; ++x)
-            for (int64_t y = 0; y < fm->H; ++y) out_host[(size_t)x * fm->H + y] = tmp[ivol_index((int)x, (int)y, fm->H)];
+        slice_to_xy(tmp.data(), out_host, fm->W, fm->H);
     });
 }
 
@@ -195,7 +184,7 @@ int fdcm_featuremap_device_volume(const fdcm_featuremap* fm, const float** devic
 int fdcm_featuremap_device_volume_stride(const fdcm_featuremap* fm, int64_t* floats_per_slice) {
     return guarded([&] {
         require(fm && floats_per_slice, "null argument");
-        *floats_per_slice = fm->current_interleaved() ? (int64_t)ivol_slice_floats(fm->W, fm->H) : fm->W * fm->H;
+        *floats_per_slice = fm->holds == VolStage::none ? 0 : (int64_t)ivol_slice_floats(fm->W, fm->H);  // (no pixels: no slices)
     });
 }
 
@@ -235,13 +224,11 @@ int fdcm_featuremap_from_slices(const float* keys, int64_t depth, const float* v
             fm->vol.reserve((size_t)depth * sl * sizeof(float));
             std::vector<float> tmp(sl, 0.f);
             for (int64_t k = 0; k < depth; ++k) {
-                const float* src = volume_host + (size_t)k * width * height;
-                for (int64_t x = 0; x < width; ++x)
-                    for (int64_t y = 0; y < height; ++y) tmp[ivol_index((int)x, (int)y, height)] = src[(size_t)x * height + y];
+                slice_from_xy(volume_host + (size_t)k * width * height, tmp.data(), width, height);
                 FDCM_HIP(hipMemcpy(fm->vol.as<float>() + (size_t)k * sl, tmp.data(), sl * sizeof(float), hipMemcpyHostToDevice));
             }
         }
-        fm->vol_stage = 3;
+        fm->holds = VolStage::integrated;
         upload_keys_only(fm);
         *out = fm;
     });
@@ -448,7 +435,7 @@ int fdcm_topk(fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_m
         require(fm->device == templates->device, "featuremap and templates live on different devices");
         require(k >= 0, "k must be >= 0");
         if (!matches_device) {  // the matches of the last fdcm_search on this handle
-            matches_device = fm->s_out.as<fdcm_match>();
+            matches_device = fm->search.out.as<fdcm_match>();
             n = fm->last_n_out;
         }
         require(n >= 0 && (n == 0 || matches_device), "bad matches");

@@ -481,7 +481,7 @@ void prepare(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid
 }
 
 void begin(fdcm_featuremap* fm) {
-    if (fm->vol_stage != 3) throw std::string("the feature map holds a partial build (no line integral): nothing to search");
+    if (fm->holds != VolStage::integrated) throw std::string("the feature map holds a partial build (no line integral): nothing to search");
     finish_build(fm);
     FDCM_HIP(hipSetDevice(fm->device));
     if (!fm->stream) FDCM_HIP(hipStreamCreateWithFlags(&fm->stream, hipStreamNonBlocking));
@@ -797,10 +797,10 @@ void search(fdcm_featuremap* fm, const Prepared& P, int n, const fdcm_grid& g, i
                  o_seg = o_dec + al256(bdec.size() * sizeof(int4)), o_best = o_seg + al256(bseg.size() * sizeof(int4)),
                  o_map = o_best + al256((size_t)TA * k * 8),
                  o_cand = o_map + (topk ? 0 : al256(max_planes * plane_max * sizeof(float))), total = o_cand + al256(max_cand * k * 8);
-    fm->s_eval.reserve(total);
-    fm->s_eval_stage.reserve(o_map);
-    char* d = (char*)fm->s_eval.p;
-    char* h = (char*)fm->s_eval_stage.p;
+    fm->search.eval.reserve(total);
+    fm->search.eval_stage.reserve(o_map);
+    char* d = (char*)fm->search.eval.p;
+    char* h = (char*)fm->search.eval_stage.p;
     std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
     std::memcpy(h + o_tm, btm.data(), btm.size() * sizeof(ExTmpl));
     std::memcpy(h + o_dec, bdec.data(), bdec.size() * sizeof(int4));
@@ -878,7 +878,7 @@ void exhaustive_window(fdcm_featuremap* fm, const fdcm_templates* t, int32_t sx,
 void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, float* out_host, float* out_device) {
     check_grid(g);
     if (t->T == 0) return;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);  // concurrent callers of one feature map take turns (shared s_eval)
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);  // concurrent callers of one feature map take turns (shared search.eval)
     begin(fm);
     Prepared P;
     prepare(fm, t, g, P);
@@ -887,8 +887,8 @@ void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid
     // host output: templates in batches whose maps fit a 256 MB workspace; device output: one launch
     const int64_t batch = out_device ? T : std::max<int64_t>(1, std::min<int64_t>(T, ((size_t)256 << 20) / plane_bytes));
     const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_map = o_tm + al256(P.tm.size() * sizeof(ExTmpl));
-    fm->s_eval.reserve(o_map + (out_device ? 0 : (size_t)batch * plane_bytes));
-    char* d = (char*)fm->s_eval.p;
+    fm->search.eval.reserve(o_map + (out_device ? 0 : (size_t)batch * plane_bytes));
+    char* d = (char*)fm->search.eval.p;
     hipStream_t st = fm->stream;
     for (int64_t b0 = 0; b0 < T; b0 += batch) {
         const int nb = (int)std::min<int64_t>(batch, T - b0);

@@ -154,9 +154,9 @@ static RasterLine raster_descriptor(const float* l, int slice) {
 }
 
 // Proxy of the L2 sweep's time per (slice, 64-row chunk), for the launch order of a build without history (only such a
-// build asks for it: run_build): a row's chain is as long as the slice has seeded columns, and the columns whose seeds lie
-// outside the chunk's 64 rows (rows far from the line: long runs without an envelope vertex) count double
-// (tools/k2_cost_model.py: r = 0.85).
+// build asks for it: setup_balanced_sweep): a row's chain is as long as the slice has seeded columns, and the columns whose
+// seeds lie outside the chunk's 64 rows (rows far from the line: long runs without an envelope vertex) count double
+// (r = 0.85 against the measured chunk times: profiles/NOTES.md, "Launch order").
 void sweep_cost_proxy(const BuildPlan& plan, std::vector<int32_t>& cost) {
     const int HW64 = (int)((plan.H + 63) / 64);
     cost.assign((size_t)plan.m * HW64, 0);

@@ -27,11 +27,11 @@ struct HipError { hipError_t code; const char* what; int line; };
 // select.  test_switches() (fdcm_host.cpp) reads and checks them once per process; nothing else reads the environment.
 // An unset or invalid switch leaves the default.
 //   FDCM_L2_SWEEP=literal      the literal L2 sweep, one wave per chunk, at every size (build_layout)
-//   FDCM_SWEEP_ORDER           the L2 sweep's launch order from a cost table at every size (run_build)
+//   FDCM_SWEEP_ORDER           the L2 sweep's launch order from a cost table at every size (setup_balanced_sweep)
 //   FDCM_SWEEP_MINCOLS=1..64   seeded columns a sweep range holds at least, instead of 16 (launch_sweep_balanced)
 //   FDCM_SWEEP_STEAL=0..128    the sweep's dynamic cuts on every workgroup, in unclaimed stretches of at least this many
 //                              blocks; 0: never (launch_sweep_balanced)
-//   FDCM_INT_XC=64|128|256     the steep line integral's chains per workgroup (run_build)
+//   FDCM_INT_XC=64|128|256     the steep line integral's chains per workgroup (stage_integral)
 //   FDCM_FORCE_HOST_BINS       the candidates' orientation bins from the host libm (orientation_bins_on_host)
 //   FDCM_SEARCH_FLAT           the search with 64-bit flat addresses (run_search)
 //   FDCM_SEARCH_COMPACT2       the search's two-kernel compaction at every size (run_search)
@@ -126,10 +126,11 @@ FDCM_HD float lin_spaced_value(int mode, float low, float high, float step, int 
     return (i == size1) ? high : (low + (float)i * step);
 }
 
-// ---------------------------------------------------------------- the integrated volume
-// From the propagation on the volume lives in a layout whose 64-byte sectors hold 4 x by 4 y pixels:
-// [k][x/4][y][x%4] (columns of the last group past W are padding).  The search gathers single floats at positions that step by about one pixel per
-// translation, in any direction; in the y-fastest layout of the build 16 steps along x touch 16 sectors, here 4 to 8.
+// ---------------------------------------------------------------- the volume
+// The volume lives in one layout from the sweeps' first store on: interleaved, [k][x/4][y][x%4], so that a 64-byte sector
+// holds 4 x by 4 y pixels (columns of the last group past W are padding).  The search gathers single floats at positions
+// that step by about one pixel per translation, in any direction: 16 steps along x touch 4 to 8 sectors here, 16 in a volume
+// whose columns are contiguous.
 // Slices are 4352 bytes longer than their pixels: feature sizes are powers of two in practice, and a candidate's
 // gathers read the same place of up to `depth` slices -- with slices a power of two apart they all fall on the same
 // memory channels (config 2': the search kernels took 0.24 - 0.36 ms depending on where the allocation landed,
@@ -137,11 +138,60 @@ FDCM_HD float lin_spaced_value(int mode, float low, float high, float step, int 
 static constexpr size_t kSlicePad = 1088;  // floats
 FDCM_HD size_t ivol_slice_floats(int64_t W, int64_t H) { return (size_t)((W + 3) / 4) * (size_t)H * 4 + kSlicePad; }
 FDCM_HD size_t ivol_index(int x, int y, int64_t H) { return ((size_t)(x >> 2) * (size_t)H + (size_t)y) * 4 + (size_t)(x & 3); }
+// one slice between the interleaved layout and the caller's [x][y] (host side of fdcm_featuremap_slice / _from_slices)
+inline void slice_to_xy(const float* il, float* xy, int64_t W, int64_t H) {
+    for (int64_t x = 0; x < W; ++x)
+        for (int64_t y = 0; y < H; ++y) xy[(size_t)x * H + y] = il[ivol_index((int)x, (int)y, H)];
+}
+inline void slice_from_xy(const float* xy, float* il, int64_t W, int64_t H) {
+    for (int64_t x = 0; x < W; ++x)
+        for (int64_t y = 0; y < H; ++y) il[ivol_index((int)x, (int)y, H)] = xy[(size_t)x * H + y];
+}
+// what a handle holds: nothing (no pixels), or the volume after the sweeps / the propagation (staged test builds) / the line integral
+enum class VolStage { none, transforms, propagated, integrated };
 
 // ---------------------------------------------------------------- handles
-struct Timing {
-    hipEvent_t ev[9] = {};  // 0-5 build stages, 6-7 search kernels, 8 search download
-    bool created = false;
+struct Timing { hipEvent_t ev[9] = {}; bool created = false; };  // events 0-5 build stages, 6-7 search kernels, 8 search download
+
+// What the balanced L2 sweep left in `stack` for the next one, until the scratch moves or another sweep writes it: per-chunk costs of a
+// build with this shape (0 chunks: none), and at this offset the count of ranges its waves took over (0: none; fdcm_selftest_sweep_steals).
+struct SweepHistory { long cost_chunks = 0; int cost_w = 0; size_t steals_off = 0; void reset() { *this = SweepHistory{}; } };
+// The line integral's group table in `offtab` is that of this depth and feature width (the keys are fixed per handle).
+struct GroupTable { int m = 0, steps = 0; void reset() { *this = GroupTable{}; } };
+// The last build of the handle, from run_build to finish_build.
+struct BuildRecord {
+    bool pending = false;       // queued on `stream` but not waited for
+    bool seeds_fused = false;   // it drew its seeds inside k_coldesc_tile (no seeds stage, no event for it)
+    bool stage_events = false, total_events = false;  // it recorded an event between its stages (per-stage times) / its first and last one (span)
+    float host_ms = 0.f;        // host time of the call up to its first kernel launch
+    void reset() { *this = BuildRecord{}; }
+};
+struct BuildBuffers {  // what a build needs besides the volume, sized by BuildLayout
+    DevBuf bitmap;   // m*W*ceil(H/64) uint64 seed bits along y (feature sizes above 4096 only: k_seeds + k_coldesc)
+    DevBuf coldesc;  // m*ceil(H/64)*W column-chunk descriptors (16 B)
+    DevBuf colmask;  // m*ceil(W/64) words: the seeded columns of every slice (k_coldesc_tile, for the L2 sweep)
+    DevBuf offtab;   // per slice: one word per group of 4 columns for the shallow sweeps of the line integral (k_groups)
+    DevBuf stack;    // the sweep's scratch: the balanced sweep's stack and owner entries (slot-major per chunk), launch order,
+                     // per-chunk costs and steal counter; or the literal pass's scratch; or the L1 pass's minima / carries
+    DevBuf plan; PinnedBuf stage;  // the last build's plan (BuildLayout's blob) or the keys of an adopted volume; its host staging
+    void release() { for (DevBuf* b : {&bitmap, &coldesc, &colmask, &offtab, &stack, &plan}) b->release(); stage.release(); }
+};
+struct SearchBuffers {
+    DevBuf scene;     // scene lines + sorted lengths + sorted idx + candidate offsets
+    DevBuf pairs;     // (template line, scene line) per search combination
+    DevBuf records, flags;  // per candidate: result record; valid flag + scan scratch
+    DevBuf out;       // compacted matches
+    DevBuf work;      // search work list: valid pairs grouped by scene line
+    DevBuf tail, tail_out;  // device tail (penalise + sort + top k): workspace; the k best before their download
+    DevBuf eval;      // fdcm_featuremap_evaluate / _minmax_translation, exhaustive search: lines, translations, work items, results
+    DevBuf counter;   // the search's counters
+    DevBuf bins;      // orientation bins per candidate line from the host libm (only when it differs from the device's atanf)
+    PinnedBuf stage, bins_stage, eval_stage;  // host side of the uploads into scene (and the tail's denominators), bins, eval
+    PinnedBuf cnt;    // the search's counters, written by k_scatter (device-output searches)
+    void release() {
+        for (DevBuf* b : {&scene, &pairs, &records, &flags, &out, &work, &tail, &tail_out, &eval, &counter, &bins}) b->release();
+        for (PinnedBuf* b : {&stage, &bins_stage, &eval_stage, &cnt}) b->release();
+    }
 };
 
 }  // namespace fdcm
@@ -155,58 +205,29 @@ struct fdcm_featuremap {
     int64_t depth_param = 0;
     float coeff = 0, padding = 0;
     int distance = 0;
-    size_t steals_off = 0;  // offset in `stack` of the counter of ranges the L2 sweep's waves took over so far (0: none; fdcm_selftest_sweep_steals)
-    long k2_cost_chunks = 0; int k2_cost_w = 0;  // the L2 sweep's per-chunk costs in `stack` are those of a build with this shape
-    int off_m = 0, off_steps = 0;  // the group table in `offtab` is valid for this depth and feature width
-    bool build_pending = false;  // the last build is queued on `stream` but has not been waited for
-    bool seeds_fused = false;    // the last build drew its seeds inside k_coldesc_tile (no seeds stage, no event for it)
-    int want_stage_events = 1;   // fdcm_featuremap_stage_timing: 0 no events, 1 an event between the build's stages, 2 around the build and the search only
-    bool stage_events = true;    // the last build recorded its stages (fdcm_build_timing has per-stage times)
-    bool total_events = true;    // .. its first and last event (total_ms has the device span)
-    bool shares_gpu = false;     // a frame slot of a pipeline with several frames in flight: other frames' kernels run beside this handle's
-    float build_host_ms = 0.f;   // host time of that call up to its first kernel launch
+    int want_stage_events = 1;  // fdcm_featuremap_stage_timing: 0 no events, 1 an event between the build's stages, 2 around the build and the search only
+    bool shares_gpu = false;    // a frame slot of a pipeline with several frames in flight: other frames' kernels run beside this handle's
     // geometry
     int64_t W = 0, H = 0, m = 0;
     float tx = 0, ty = 0;
     std::vector<float> keys;
-    // device state
-    // The volume moves between two buffers: the sweeps write the distance transforms into `vol`, y-fastest [k][x][y];
-    // the propagation reads them and writes `ivol` in the interleaved layout (ivol_index); the line integral reads
-    // `ivol` and writes its sums back into `vol`, interleaved -- which is what the search gathers from.
-    fdcm::DevBuf vol;      // max(m*W*H, m*ivol_slice_floats) floats
-    fdcm::DevBuf ivol;     // m*ivol_slice_floats floats
-    int vol_stage = 0;     // what the handle holds: 1 = transforms (vol; staged test builds), 2 = propagated
-                           // (ivol, interleaved; staged test builds), 3 = integrated (vol, interleaved): complete
-    const float* current() const { return vol_stage == 2 ? ivol.as<float>() : vol.as<float>(); }
-    bool current_interleaved() const { return vol_stage >= 1; }  // (every sweep writes the transforms interleaved)
-    fdcm::DevBuf bitmap;   // m*W*ceil(H/64) uint64 seed bits along y
-    fdcm::DevBuf coldesc;  // m*ceil(H/64)*W column-chunk descriptors (16 B)
-    fdcm::DevBuf colmask;  // m*ceil(W/64) words: the seeded columns of every slice (k_coldesc_tile, for the L2 sweep)
-    fdcm::DevBuf offtab;   // per slice: one word per group of 4 columns for the shallow sweeps of the line integral (k_groups)
-    fdcm::DevBuf stack;    // K2 scratch: per row a (v, f, z) stack of W entries
-    int* steal_counter() const { return steals_off ? (int*)((char*)stack.p + steals_off) : nullptr; }
-    fdcm::DevBuf plan;     // the last build's plan (BuildLayout), or the keys of an adopted volume
-    fdcm::PinnedBuf stage; // host staging for the plan
-    size_t off_keys = 0;   // where the keys are in `plan` (the search reads them there)
-    // search workspaces
-    fdcm::DevBuf s_scene;   // scene lines + sorted lengths + sorted idx
-    fdcm::DevBuf s_pairs;   // (template line, scene line) per search combination
-    fdcm::DevBuf s_records; // per-candidate result records
-    fdcm::DevBuf s_flags;   // per-candidate valid flag + scan scratch
-    fdcm::DevBuf s_out;     // compacted matches
-    fdcm::DevBuf s_work;    // search work list: valid pairs grouped by scene line
-    fdcm::DevBuf s_tail;    // device tail (penalise + sort + top k) workspace
-    fdcm::DevBuf s_tail_out; // the k best of the device tail before their download
-    fdcm::DevBuf s_eval;    // fdcm_featuremap_evaluate / _minmax_translation: lines, translations, work items, results
-    fdcm::PinnedBuf s_eval_stage;  // host side of the exhaustive search's uploads
-    std::mutex seam_mutex;  // .. which the reference's optimisers call from pool threads on one feature map (batchoptimize.cpp:102-110):
-                            // the two calls share s_eval and the stream, so they take turns
-    int64_t last_n_out = 0; // matches of the last host-output search, still in s_out
-    fdcm::DevBuf s_counter;
-    fdcm::PinnedBuf s_stage;
-    fdcm::PinnedBuf s_cnt;   // the search's counters, written by k_scatter (device-output searches)
-    fdcm::DevBuf s_bins;     // orientation bins per candidate line from the host libm (only when it differs from the device's atanf)
-    fdcm::PinnedBuf s_bins_stage;
+    size_t off_keys = 0;  // where the keys are in `build.plan` (the search reads them there)
+    // The volume, interleaved (ivol_index) in either buffer: the sweeps write the distance transforms into `vol`, the
+    // propagation reads them and writes `ivol`, the line integral reads `ivol` and writes its sums back into `vol` --
+    // which is what the search gathers from.
+    fdcm::DevBuf vol;   // m*ivol_slice_floats floats
+    fdcm::DevBuf ivol;  // the same (builds that go past the sweeps)
+    fdcm::VolStage holds = fdcm::VolStage::none;
+    const float* current() const { return holds == fdcm::VolStage::propagated ? ivol.as<float>() : vol.as<float>(); }
+    fdcm::BuildBuffers build;
+    fdcm::SweepHistory sweep;
+    fdcm::GroupTable groups;
+    fdcm::BuildRecord built;
+    int* steal_counter() const { return sweep.steals_off ? (int*)((char*)build.stack.p + sweep.steals_off) : nullptr; }
+    fdcm::SearchBuffers search;
+    std::mutex seam_mutex;  // evaluate / minmax_translation (called from pool threads on one feature map, batchoptimize.cpp:102-110) and
+                            // the exhaustive search share search.eval and the stream: they take turns
+    int64_t last_n_out = 0; // matches of the last host-output search, still in search.out
     fdcm::Timing timing;
     fdcm_build_timing last_build = {};
     fdcm_search_timing last_search = {};

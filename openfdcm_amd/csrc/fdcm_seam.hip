@@ -95,8 +95,8 @@ void run_minmax(fdcm_featuremap* fm, const float* lines, const int64_t* offsets,
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t o_lines = 0, o_off = al((size_t)n_lines * 16), o_al = o_off + al((size_t)(T + 1) * 8), o_out = o_al + al((size_t)T * 8),
                  total = o_out + al((size_t)T * 8);
-    fm->s_eval.reserve(total);
-    char* d = (char*)fm->s_eval.p;
+    fm->search.eval.reserve(total);
+    char* d = (char*)fm->search.eval.p;
     if (n_lines) FDCM_HIP(hipMemcpyAsync(d + o_lines, lines, (size_t)n_lines * 16, hipMemcpyHostToDevice, st));
     FDCM_HIP(hipMemcpyAsync(d + o_off, offsets, (size_t)(T + 1) * 8, hipMemcpyHostToDevice, st));
     FDCM_HIP(hipMemcpyAsync(d + o_al, align, (size_t)T * 8, hipMemcpyHostToDevice, st));
@@ -111,7 +111,7 @@ void run_minmax(fdcm_featuremap* fm, const float* lines, const int64_t* offsets,
 void run_evaluate(fdcm_featuremap* fm, const float* lines, const int64_t* offsets, int64_t T, const float* translations,
                   const int64_t* tr_offsets, float* scores) {
     if (T == 0 || tr_offsets[T] == 0) return;
-    if (fm->vol_stage != 3) throw std::string("the feature map holds a partial build (no line integral): nothing to evaluate");
+    if (fm->holds != VolStage::integrated) throw std::string("the feature map holds a partial build (no line integral): nothing to evaluate");
     if (fm->m == 0 || fm->W == 0 || fm->H == 0) throw std::string("evaluate on an empty feature map");
     std::lock_guard<std::mutex> turn(fm->seam_mutex);  // concurrent callers of one feature map (a pool's tasks) take turns
     finish_build(fm);
@@ -142,8 +142,8 @@ void run_evaluate(fdcm_featuremap* fm, const float* lines, const int64_t* offset
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t o_l5 = 0, o_off = al(l5.size() * 4), o_tr = o_off + al((size_t)(T + 1) * 8), o_it = o_tr + al((size_t)n_tr * 8),
                  o_sc = o_it + al(items.size() * sizeof(EvalItem)), total = o_sc + al((size_t)n_tr * 4);
-    fm->s_eval.reserve(total);
-    char* d = (char*)fm->s_eval.p;
+    fm->search.eval.reserve(total);
+    char* d = (char*)fm->search.eval.p;
     if (n_lines) FDCM_HIP(hipMemcpyAsync(d + o_l5, l5.data(), l5.size() * 4, hipMemcpyHostToDevice, st));
     FDCM_HIP(hipMemcpyAsync(d + o_off, offsets, (size_t)(T + 1) * 8, hipMemcpyHostToDevice, st));
     FDCM_HIP(hipMemcpyAsync(d + o_tr, translations, (size_t)n_tr * 8, hipMemcpyHostToDevice, st));

@@ -597,7 +597,7 @@ struct SearchLayout {
     std::vector<long long> coff;  // candidate offsets per template (T + 1)
     int64_t cpt_max = 0, ncand = 0, pairs_stride = 0;  // candidates of the largest template, of all; pair slots per template
     int nchunks = 0;  // compaction chunks of kChunk candidates
-    size_t o_lines = 0, o_len = 0, o_idx = 0, o_coff = 0, scene = 0;  // s_scene: lines | sorted lengths | sorted idx | coff
+    size_t o_lines = 0, o_len = 0, o_idx = 0, o_coff = 0, scene = 0;  // search.scene: lines | sorted lengths | sorted idx | coff
     size_t records = 0, flags = 0, counters = 64, pairs = 0, work_list = 0, work = 0, bins = 0, out = 0;
 };
 static SearchLayout search_layout(const fdcm_templates* t, int64_t n_scene, int64_t maxT, int64_t maxS) {
@@ -647,12 +647,12 @@ bool orientation_bins_on_host() {
     return on_host;
 }
 
-// every workspace of the search but its output (s_out / s_cnt, which depend on where the matches go)
+// every workspace of the search but its output (search.out / search.cnt, which depend on where the matches go)
 static void reserve_workspaces(fdcm_featuremap* fm, const SearchLayout& L, bool host_bins) {
-    fm->s_stage.reserve(L.scene); fm->s_scene.reserve(L.scene);
-    fm->s_records.reserve(L.records); fm->s_flags.reserve(L.flags); fm->s_counter.reserve(L.counters);
-    fm->s_pairs.reserve(L.pairs); fm->s_work.reserve(L.work);
-    if (host_bins) { fm->s_bins_stage.reserve(L.bins); fm->s_bins.reserve(L.bins); }
+    fm->search.stage.reserve(L.scene); fm->search.scene.reserve(L.scene);
+    fm->search.records.reserve(L.records); fm->search.flags.reserve(L.flags); fm->search.counter.reserve(L.counters);
+    fm->search.pairs.reserve(L.pairs); fm->search.work.reserve(L.work);
+    if (host_bins) { fm->search.bins_stage.reserve(L.bins); fm->search.bins.reserve(L.bins); }
 }
 
 void reserve_search(fdcm_featuremap* fm, const fdcm_templates* t, int64_t n_scene, int64_t maxT, int64_t maxS) {
@@ -661,7 +661,7 @@ void reserve_search(fdcm_featuremap* fm, const fdcm_templates* t, int64_t n_scen
     const SearchLayout L = search_layout(t, n_scene, maxT, maxS);
     if (L.ncand == 0) return;
     reserve_workspaces(fm, L, orientation_bins_on_host());
-    fm->s_cnt.reserve(L.counters);  // (the device-output searches of the sharded engine)
+    fm->search.cnt.reserve(L.counters);  // (the device-output searches of the sharded engine)
 }
 
 void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene, int64_t n_scene, int64_t maxT,
@@ -702,7 +702,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     if (ncand == 0) return;
     // ---- every check that can refuse the search, before the first command is queued (a refusal must not leave an upload
     // in flight on the preparation stream that the next call's staging would overwrite)
-    if (fm->vol_stage != 3) throw std::string("the feature map holds a partial build (no line integral): nothing to search");
+    if (fm->holds != VolStage::integrated) throw std::string("the feature map holds a partial build (no line integral): nothing to search");
     const int64_t B = optimizer == FDCM_BATCH_OPTIMIZE ? std::max<int64_t>(1, batch) : 1;
     if (B > 4096) throw std::string("batch_size above 4096 is not supported");
     const int win = B <= 15 ? (int)((15 / B) * B) : (int)B;  // multipliers scored per direction and round: whole batches, 15 at most when they fit one round
@@ -712,7 +712,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     if (host_bins_needed && fm->m > 65535) throw std::string("host-side orientation bins need depth <= 65535");
     // ---- stage + upload: scene lines | sorted lengths | sorted idx | candidate offsets
     reserve_workspaces(fm, L, host_bins_needed);
-    char* hs = (char*)fm->s_stage.p;
+    char* hs = (char*)fm->search.stage.p;
     std::memcpy(hs + L.o_lines, scene, (size_t)n_s * 16);
     float* hl = (float*)(hs + L.o_len);
     int* hi = (int*)(hs + L.o_idx);
@@ -730,19 +730,19 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
         }
         sp = fm->prep_stream;
     }
-    FDCM_HIP(hipMemcpyAsync(fm->s_scene.p, hs, L.scene, hipMemcpyHostToDevice, sp));
+    FDCM_HIP(hipMemcpyAsync(fm->search.scene.p, hs, L.scene, hipMemcpyHostToDevice, sp));
     const int nchunks = L.nchunks;
     // keys live at the end of the build plan blob; for adopted volumes they are uploaded there too
     SearchParams P{};
     P.vol = fm->vol.as<float>();
-    P.keys = (const float*)((const char*)fm->plan.p + fm->off_keys);
+    P.keys = (const float*)((const char*)fm->build.plan.p + fm->off_keys);
     P.W = (int)fm->W; P.H = (int)fm->H; P.m = (int)fm->m; P.tx = fm->tx; P.ty = fm->ty;
     P.tlines = t->d_lines.as<float>();
     P.toffsets = t->d_offsets.as<long long>();
     P.tlengths = t->d_lengths.as<float>();
     P.tsorted = t->d_sorted.as<int>();
     P.T = (int)t->T;
-    const char* ds = (const char*)fm->s_scene.p;
+    const char* ds = (const char*)fm->search.scene.p;
     P.slines = (const float*)(ds + L.o_lines);
     P.s_sorted_len = (const float*)(ds + L.o_len);
     P.s_sorted_idx = (const int*)(ds + L.o_idx);
@@ -756,12 +756,12 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     P.bpt = (int)((L.cpt_max + kWavesPerBlock - 1) / kWavesPerBlock);
     P.ncand = ncand;
     P.lds_lines = lds_lines;
-    P.records = fm->s_records.as<fdcm_match>();
-    P.flags = fm->s_flags.as<int>();
+    P.records = fm->search.records.as<fdcm_match>();
+    P.flags = fm->search.flags.as<int>();
     P.evals = P.flags + ncand + nchunks;
-    P.counters = fm->s_counter.as<unsigned long long>();
+    P.counters = fm->search.counter.as<unsigned long long>();
     P.pairs_stride = (int)L.pairs_stride;
-    P.pairs = fm->s_pairs.as<int2>();
+    P.pairs = fm->search.pairs.as<int2>();
     // volumes below 4 GB (every BASELINE config but 5) are addressed through one buffer descriptor with 32-bit offsets
     const bool buf32 = !test_switches().search_flat && (size_t)fm->m * ivol_slice_floats(fm->W, fm->H) * sizeof(float) < ((size_t)1 << 32);
     if (lds > 64 * 1024)
@@ -774,17 +774,17 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     const long long n_slots = (long long)t->T * P.pairs_stride;
     if (n_slots <= 0x7fffffffll) {
         if (n_slots <= kWlSlotsPerBlock) {
-            hipLaunchKernelGGL(k_worklist, dim3(1), dim3(1024), 0, sp, P, n_slots, fm->s_work.as<int2>());
+            hipLaunchKernelGGL(k_worklist, dim3(1), dim3(1024), 0, sp, P, n_slots, fm->search.work.as<int2>());
         } else {
-            int* ghist = (int*)((char*)fm->s_work.p + L.work_list);
+            int* ghist = (int*)((char*)fm->search.work.p + L.work_list);
             int* cursor = ghist + kWorkBins;
             const unsigned nb = (unsigned)((n_slots + kWlSlotsPerBlock - 1) / kWlSlotsPerBlock);
             FDCM_HIP(hipMemsetAsync(ghist, 0, (size_t)kWorkBins * sizeof(int), sp));
             hipLaunchKernelGGL(k_wl_count, dim3(nb), dim3(1024), 0, sp, P, n_slots, ghist);
             hipLaunchKernelGGL(k_wl_starts, dim3(1), dim3(1024), 0, sp, ghist, cursor);
-            hipLaunchKernelGGL(k_wl_scatter, dim3(nb), dim3(1024), 0, sp, P, n_slots, ghist, cursor, fm->s_work.as<int2>());
+            hipLaunchKernelGGL(k_wl_scatter, dim3(nb), dim3(1024), 0, sp, P, n_slots, ghist, cursor, fm->search.work.as<int2>());
         }
-        P.work = fm->s_work.as<int2>();
+        P.work = fm->search.work.as<int2>();
         P.nblocks = (int)(((ncand + kWavesPerBlock - 1) / kWavesPerBlock + 7) / 8 * 8);
     } else {
         P.work = nullptr;
@@ -796,7 +796,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     }
     if (host_bins_needed) {
         const size_t stride = (size_t)P.lds_lines;
-        unsigned short* hb = (unsigned short*)fm->s_bins_stage.p;
+        unsigned short* hb = (unsigned short*)fm->search.bins_stage.p;
         const float* keys = fm->keys.data();
         const int mkeys = (int)fm->m;
         std::vector<float> sorted_len((size_t)n_s);
@@ -838,8 +838,8 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
                 }
             });
         for (auto& x : th) x.join();
-        FDCM_HIP(hipMemcpyAsync(fm->s_bins.p, hb, (size_t)ncand * stride * sizeof(unsigned short), hipMemcpyHostToDevice, st));
-        P.host_bins = fm->s_bins.as<unsigned short>();
+        FDCM_HIP(hipMemcpyAsync(fm->search.bins.p, hb, (size_t)ncand * stride * sizeof(unsigned short), hipMemcpyHostToDevice, st));
+        P.host_bins = fm->search.bins.as<unsigned short>();
     }
     if (buf32) hipLaunchKernelGGL(k_search<true>, dim3((unsigned)P.nblocks), dim3(64 * kWavesPerBlock), lds, st, P);
     else hipLaunchKernelGGL(k_search<false>, dim3((unsigned)P.nblocks), dim3(64 * kWavesPerBlock), lds, st, P);
@@ -847,8 +847,8 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     if (!dst) {
         // host output: one extra record behind the candidates' capacity carries the counters, so that the
         // matches and their count come back with a single copy
-        fm->s_out.reserve(L.out);
-        dst = fm->s_out.as<fdcm_match>();
+        fm->search.out.reserve(L.out);
+        dst = fm->search.out.as<fdcm_match>();
         P.counters = reinterpret_cast<unsigned long long*>(dst + ncand);
     }
     int* d_counts = P.flags + ncand;
@@ -863,8 +863,8 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
         FDCM_HIP(hipHostGetDevicePointer((void**)&host_out, *out_host, 0));
         host_cnt = reinterpret_cast<unsigned long long*>(host_out + ncand);
     } else {
-        fm->s_cnt.reserve(L.counters);
-        FDCM_HIP(hipHostGetDevicePointer((void**)&host_cnt, fm->s_cnt.p, 0));
+        fm->search.cnt.reserve(L.counters);
+        FDCM_HIP(hipHostGetDevicePointer((void**)&host_cnt, fm->search.cnt.p, 0));
     }
     if (nchunks <= kCompactChunks && !test_switches().search_compact2) {
         hipLaunchKernelGGL(k_compact, dim3((unsigned)nchunks), dim3(1024), 0, st, P.records, P.flags, P.evals, ncand, nchunks, dst, P.counters,
@@ -879,7 +879,7 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     unsigned long long hc[3] = {0, 0, 0};
     FDCM_HIP(hipStreamSynchronize(st));
     finish_build(fm);  // a build queued before this search is complete as well: collect its timings
-    std::memcpy(hc, out_host ? (const void*)(*out_host + ncand) : (const void*)fm->s_cnt.p, sizeof hc);
+    std::memcpy(hc, out_host ? (const void*)(*out_host + ncand) : (const void*)fm->search.cnt.p, sizeof hc);
     *n_out = (int64_t)hc[2];
     fm->last_search.evaluations = (int64_t)hc[0];
     if (timed) FDCM_HIP(hipEventElapsedTime(&fm->last_search.kernel_ms, ev[6], ev[7]));

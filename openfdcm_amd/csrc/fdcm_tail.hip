@@ -95,9 +95,9 @@ void blocks_to_host(hipStream_t st, const void* blocks_device, int32_t n_blocks,
     *n_out = total;
 }
 
-// The device tail's workspaces for T templates, n matches and the k best, in one place (bytes): s_tail holds the penalty's
-// denominators, sort keys and indices (in and out), penalised scores and rocPRIM's radix-sort scratch; s_stage the
-// denominators' staging; s_tail_out the k best before their download (run_topk).
+// The device tail's workspaces for T templates, n matches and the k best, in one place (bytes): search.tail holds the penalty's
+// denominators, sort keys and indices (in and out), penalised scores and rocPRIM's radix-sort scratch; search.stage the
+// denominators' staging; search.tail_out the k best before their download (run_topk).
 struct TailLayout { size_t o_den = 0, o_keys, o_keys2, o_idx, o_idx2, o_ps, o_tmp, tmp_bytes = 0, tail, stage, out; };
 static TailLayout tail_layout(int64_t T, int64_t n, int64_t k) {
     TailLayout L;
@@ -117,7 +117,7 @@ static TailLayout tail_layout(int64_t T, int64_t n, int64_t k) {
 void reserve_topk(fdcm_featuremap* fm, int64_t T, int64_t n) {
     FDCM_HIP(hipSetDevice(fm->device));
     const TailLayout L = tail_layout(T, n, 0);
-    fm->s_tail.reserve(L.tail); fm->s_stage.reserve(L.stage);
+    fm->search.tail.reserve(L.tail); fm->search.stage.reserve(L.stage);
 }
 
 // The k best of n device-resident matches, penalised, into out_device (k <= n, both on fm's device); returns when
@@ -131,8 +131,8 @@ void run_topk_device(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_ma
     if (k > n) throw std::string("k exceeds the number of matches");
     if (n > 0x7fffffffll) throw std::string("more than 2^31 matches are not supported by the device tail");
     const TailLayout L = tail_layout(t->T, n, k);
-    fm->s_tail.reserve(L.tail);
-    char* d = (char*)fm->s_tail.p;
+    fm->search.tail.reserve(L.tail);
+    char* d = (char*)fm->search.tail.p;
     // ---- denominators on the host (getTemplateLengths + the penalty's formula), uploaded through pinned staging
     const bool pen = penalty >= 0;
     if (pen) {
@@ -140,8 +140,8 @@ void run_topk_device(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_ma
         if (t->T) {
             if (fdcm_templates_lengths(t, len.data()) != FDCM_OK) throw std::string(fdcm_last_error());
         }
-        fm->s_stage.reserve(L.stage);
-        float* hd = (float*)fm->s_stage.p;
+        fm->search.stage.reserve(L.stage);
+        float* hd = (float*)fm->search.stage.p;
         for (int64_t i = 0; i < t->T; ++i) {
             const float l = std::max(len[(size_t)i], 1e-6f);
             hd[i] = penalty == FDCM_DEFAULT_PENALTY ? l : std::pow(l, tau);
@@ -170,9 +170,9 @@ void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* ma
     k = std::min<int64_t>(std::max<int64_t>(k, 0), n);
     *out = result_acquire(std::max<size_t>(1, (size_t)k) * sizeof(fdcm_match));
     if (k == 0) return;
-    fm->s_tail_out.reserve(tail_layout(t->T, n, k).out);
-    run_topk_device(fm, t, matches_device, n, base, penalty, tau, k, fm->s_tail_out.as<fdcm_match>());
-    records_to_host(fm->stream, fm->s_tail_out.as<fdcm_match>(), k, *out);
+    fm->search.tail_out.reserve(tail_layout(t->T, n, k).out);
+    run_topk_device(fm, t, matches_device, n, base, penalty, tau, k, fm->search.tail_out.as<fdcm_match>());
+    records_to_host(fm->stream, fm->search.tail_out.as<fdcm_match>(), k, *out);
     FDCM_HIP(hipStreamSynchronize(fm->stream));
     *n_out = k;
 }

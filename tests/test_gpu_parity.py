@@ -187,6 +187,37 @@ def test_search_edge_cases(amd):
     assert np.array_equal(got["score"][ok].view(np.uint32), want["score"][ok].view(np.uint32))
 
 
+def test_maps_without_pixels(amd):
+    """A map built from an empty scene and a map rebuilt from a real scene to an empty one are the same map: no size, no
+    keys, a slice stride of 0 (there is no slice to address), no matches -- and either takes a real scene afterwards."""
+    from openfdcm_amd import synthetic
+    from openfdcm_amd.engine import DeviceFeatureMap, DeviceTemplates, search_raw
+    scene = synthetic.scene(128, 30, 17)
+    tset = DeviceTemplates(synthetic.templates(6, 8, 128, 18))
+    none = np.zeros((4, 0), dtype=np.float32)
+    kw = dict(depth=12, coeff=5.0, padding=1.3, distance=O.L2)
+    built_empty = DeviceFeatureMap.build(none, **kw)
+    emptied = DeviceFeatureMap.build(scene, **kw)
+    assert emptied.width > 0 and emptied.depth == 12
+    assert emptied.device_slice_stride() >= emptied.width * emptied.height
+    emptied.rebuild(none)
+    orc = O.build(scene, nthreads=4, **kw)
+    for what, fm in (("built empty", built_empty), ("rebuilt to empty", emptied)):
+        print(f"{what}: size {fm.width} x {fm.height} x {fm.depth}, stride {fm.device_slice_stride()}")
+        assert (fm.width, fm.height, fm.depth) == (0, 0, 0), what
+        assert np.array_equal(fm.scene_translation, np.zeros(2, dtype=np.float32)), what
+        assert fm.distance == O.L2 and fm.keys.shape == (0,), what
+        assert fm.volume().shape == (0, 0, 0), what
+        assert len(search_raw(fm, tset, scene, 4, 4, O.BATCH_OPTIMIZE, 10)) == 0, what
+        assert len(search_raw(fm, tset, none, 4, 4, O.BATCH_OPTIMIZE, 10)) == 0, what
+        assert fm.device_slice_stride() == 0, what
+    for what, fm in (("built empty", built_empty), ("rebuilt to empty", emptied)):
+        fm.rebuild(scene)
+        assert np.array_equal(fm.keys, orc.keys) and np.array_equal(fm.scene_translation, orc.translation), what
+        assert fm.device_slice_stride() >= ((fm.width + 3) // 4) * fm.height * 4, what
+        assert_volume_equal(fm, orc, f"{what}, then a real scene")
+
+
 def test_refused_search_leaves_nothing_in_flight(amd):
     """a search the library refuses (batch above 4096, a partial build) throws before anything is queued on the
     preparation stream; the next search on the same handle -- whose staging buffer it rewrites -- is the oracle's."""
