@@ -55,7 +55,8 @@ typedef struct fdcm_featuremap fdcm_featuremap; /* replaces Dt3Cpu, dt3cpu.h:46-
 typedef struct fdcm_templates fdcm_templates;   /* a std::vector<LineArray> resident in HBM */
 
 typedef struct fdcm_featuremap_info {
-    int64_t width, height; /* getFeatureSize(): Size(x = W, y = H), always square (dt3cpu.cpp:113-115) */
+    int64_t width, height; /* getFeatureSize(): Size(x = W, y = H); square when built from scene lines (dt3cpu.cpp:113-115), any
+                            * shape when adopted from slices or built from an image or labels */
     int64_t depth;         /* number of orientation slices actually built (distinct keys) */
     float scene_translation[2]; /* getSceneTranslation() */
     int32_t distance;
@@ -65,7 +66,8 @@ typedef struct fdcm_featuremap_info {
 /* Per-stage device times of the last build, in milliseconds (HIP events on the build stream). */
 typedef struct fdcm_build_timing {
     float total_ms;     /* host preparation + the kernels' span on the device */
-    float seeds_ms;     /* K0: rasterise scene lines into the seed bitmap (feature sizes above 4096 only: below, K1 draws the seeds itself) */
+    float seeds_ms;     /* K0: rasterise scene lines into the seed bitmap (feature sizes above 4096 only: below, K1 draws the seeds itself);
+                         * image builds: the edge-label kernel */
     float pass1_ms;     /* K1: 1-D distance along y */
     float pass2_ms;     /* K2: in-place lower-envelope pass along x (L2/L2^2) or L1 sweeps */
     float propagate_ms; /* K3: orientation propagation (+ sqrt for L2) */
@@ -123,6 +125,51 @@ int fdcm_featuremap_from_slices(const float* keys, int64_t depth, const float* v
 /* Test hook: stop the build after stage 1 (distance transform), 2 (propagation) or 3 (all). */
 int fdcm_featuremap_build_staged(const float* scene_lines, int64_t n_lines, int64_t depth, float dt3_coeff,
                                  float padding, int distance, int stop_after, fdcm_featuremap** out);
+
+/* ---- feature maps from images: oriented edge pixels as DT3 seeds.  No counterpart in the reference, whose only seed
+ *      source is a list of scene lines; these definitions are the project's own.
+ *
+ * Image: uint8, `height` rows of `width` pixels, `row_stride` >= width bytes between rows; I(x, y) is clamped to the image
+ * (replicate border) for the gradient.
+ * Gradient (integer Sobel):  gx = [I(x+1,y-1) + 2 I(x+1,y) + I(x+1,y+1)] - [the same at x-1],
+ *                            gy = [I(x-1,y+1) + 2 I(x,y+1) + I(x+1,y+1)] - [the same at y-1],  m2 = gx^2 + gy^2 (<= 2 * 1020^2).
+ * Direction for thinning, with a = |gx|, b = |gy| (12/29 ~ tan 22.5 deg):  29 b < 12 a: d = (1, 0);  29 a < 12 b: d = (0, 1);
+ *   otherwise d = (1, 1) when (gx >= 0) == (gy >= 0), else d = (1, -1).
+ * Edge pixel p: m2(p) >= threshold^2 (1 <= threshold <= 1442), m2(p) > m2(p - d) and m2(p) >= m2(p + d); a neighbour outside
+ *   the image has m2 = 0.  (Of a two-pixel plateau one pixel wins.)  No smoothing, no hysteresis.
+ * Orientation label: the edge's tangent (-gy, gx): dx = float(-gy) (the integer is negated, so gy = 0 gives +0), dy = float(gx),
+ *   angle = atanf(dy / dx) as getAngle (math.h:295-299; IEEE division, dx = 0 gives +-pi/2), label = closestOrientation
+ *   (dt3cpu.h:93-114) over the m distinct keys that a line build of the same depth makes.
+ * Label image: one byte per pixel, rows of `width` bytes without gaps; 0 .. m-1 a slice, any value >= m (canonically 255) no
+ *   edge -- so m <= 255, and a depth above 255 is FDCM_EINVAL.
+ * Feature map of an image, with b = border >= 0: size (width + 2b, height + 2b), scene translation (b, b), padding reported as
+ *   0; pixel (x + b, y + b) of slice label(x, y) is a seed, stage 1 is the distance transform of every slice's 0 / FLT_MAX
+ *   image, stages 2 and 3 are the line build's (distanceTransform from the drawn image on, propagateOrientation, lineIntegral).
+ *   Both sides of the map are at most 4096.  A slice without seeds, or a whole image without edges, is FLT_MAX throughout
+ *   stage 1 (its square root for FDCM_L2).
+ * on_device = 1: the pointer is memory of the current device; it is read in place while the build runs, so its content must
+ *   be complete when the call is made and stay untouched until a later call on the handle has waited for the build.
+ * Argument errors (NULL pointers, size 0 or above 4096, row_stride < width, negative border, threshold outside [1, 1442],
+ * too many keys) are FDCM_EINVAL before any GPU work.  Like fdcm_featuremap_build, the builds return once queued. ---- */
+/* image -> label image; host in, host out, computed on the GPU.  depth >= 1. */
+int fdcm_edge_labels(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int64_t depth, int threshold,
+                     uint8_t* labels_out);
+int fdcm_featuremap_build_image(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                                int threshold, int64_t border, int64_t depth, float dt3_coeff, int distance,
+                                fdcm_featuremap** out);
+/* The steady-state call: any handle, whatever its last build took its seeds from (its depth, coefficient and distance stay;
+ * a handle made from an image has padding 0 for a later build from lines). */
+int fdcm_featuremap_rebuild_image(fdcm_featuremap* fm, const uint8_t* image, int64_t width, int64_t height, int64_t row_stride,
+                                  int on_device, int threshold, int64_t border);
+/* The same from a label image of the caller's own edge detector. */
+int fdcm_featuremap_build_labels(const uint8_t* labels, int64_t width, int64_t height, int on_device, int64_t border,
+                                 int64_t depth, float dt3_coeff, int distance, fdcm_featuremap** out);
+int fdcm_featuremap_rebuild_labels(fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device,
+                                   int64_t border);
+/* Test hook: stop the image build after stage 1, 2 or 3. */
+int fdcm_featuremap_build_image_staged(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                                       int threshold, int64_t border, int64_t depth, float dt3_coeff, int distance,
+                                       int stop_after, fdcm_featuremap** out);
 
 /* ---- the feature-map plug-in seam: what a FeatureMapInstance specialises besides getFeatureSize
  *      (featuremap.h:27-52; FeatureMapModel<T> forwards to them, featuremap.h:80-92) and what every optimiser of the

@@ -12,7 +12,7 @@ import numpy as _np
 
 from . import _capi
 from .matchlist import Match, MatchList, records_of  # noqa: F401
-from .engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, ShardedEngine, search_raw, topk  # noqa: F401  (extensions)
+from .engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, ShardedEngine, edge_labels, search_raw, topk  # noqa: F401  (extensions)
 
 __version__ = "0.10.0"  # API level of the reference this mirrors (openfdcm.cpp:43)
 
@@ -181,6 +181,30 @@ def build_cpu_featuremap(scene, params=None, pool=None):
     else:
         try:
             fm.rebuild(scene)
+        except Exception:
+            fm.close()
+            raise
+    out = Dt3Cpu(None, _device=fm)
+    out._pool_key = key
+    return out
+
+
+def build_image_featuremap(image, params=None, threshold=60, border=0):
+    """The DT3 feature map of a camera frame without a line extractor (extension; include/fdcm.h, "feature maps from
+    images"): the seeds are the oriented edge pixels of `image`, a 2-D uint8 numpy array or CUDA torch tensor.  Feature size
+    (W + 2 border, H + 2 border), scene translation (border, border); params.padding plays no part.  Returns a Dt3Cpu
+    that exhaustive_*, score_map, FeatureMap.evaluate and search (with the caller's scene lines) take as any other."""
+    import ctypes as C
+    params = params if params is not None else Dt3CpuParameters()
+    dev = C.c_int()
+    _capi.check(_capi.lib().fdcm_get_device(C.byref(dev)))
+    key = ("image", int(params.depth), float(params.dt3_coeff), int(params.distance), dev.value)
+    fm = _featuremap_pool.take(key)
+    if fm is None:
+        fm = DeviceFeatureMap.build_image(image, threshold, border=border, depth=key[1], coeff=key[2], distance=key[3])
+    else:
+        try:
+            fm.rebuild_image(image, threshold, border=border)
         except Exception:
             fm.close()
             raise

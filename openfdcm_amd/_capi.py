@@ -76,6 +76,15 @@ SYMBOLS = [
     ("fdcm_featuremap_from_slices", C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int64, _fp, C.POINTER(_vp)]),
     ("fdcm_featuremap_build_staged", C.c_int,
      [_fp, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(_vp)]),
+    ("fdcm_edge_labels", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, _vp]),
+    ("fdcm_featuremap_build_image", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                              C.c_float, C.c_int, C.POINTER(_vp)]),
+    ("fdcm_featuremap_rebuild_image", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64]),
+    ("fdcm_featuremap_build_labels", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_float, C.c_int,
+                                               C.POINTER(_vp)]),
+    ("fdcm_featuremap_rebuild_labels", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, C.c_int64]),
+    ("fdcm_featuremap_build_image_staged", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64,
+                                                     C.c_int64, C.c_float, C.c_int, C.c_int, C.POINTER(_vp)]),
     ("fdcm_featuremap_minmax_translation", C.c_int, [_vp, _fp, C.c_int64, _fp, _fp]),
     ("fdcm_featuremap_minmax_translation_batch", C.c_int, [_vp, _fp, _i64p, C.c_int64, _fp, _fp]),
     ("fdcm_featuremap_evaluate", C.c_int, [_vp, _fp, _i64p, C.c_int64, _fp, _i64p, _fp]),

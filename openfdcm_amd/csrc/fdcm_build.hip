@@ -95,8 +95,6 @@ __global__ void __launch_bounds__(256) k_coldesc_tile(const RasterLine* __restri
     constexpr int STR = XT + 1;
     unsigned long long* bits = reinterpret_cast<unsigned long long*>(tile + (size_t)HW64 * STR);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wi = lane & (SEG - 1), ci = lane / SEG;
-    constexpr int CPP = 64 / SEG, CPW = XT / 4;  // columns per wave pass, columns per wave
     const long k = blockIdx.y;
     const int x0 = blockIdx.x * XT;
     for (int i = threadIdx.x; i < HW64 * XT; i += 256) bits[i] = 0ull;
@@ -117,44 +115,7 @@ __global__ void __launch_bounds__(256) k_coldesc_tile(const RasterLine* __restri
         }
     }
     __syncthreads();
-    for (int pass = 0; pass < CPW / CPP; ++pass) {
-        const int xl = wave * CPW + pass * CPP + ci, x = x0 + xl;
-        const bool valid = x < W && wi < HW64;
-        const unsigned long long word = valid ? bits[wi * XT + xl] : 0ull;
-        const int last_i = word ? wi * 64 + 63 - __clzll(word) : INT_MIN;
-        const int first_i = word ? wi * 64 + (__ffsll((long long)word) - 1) : INT_MAX;
-        int pmax = last_i, smin = first_i;  // inclusive scans inside the SEG lanes of a column
-#pragma unroll
-        for (int d = 1; d < SEG; d <<= 1) {
-            const int a = __shfl_up(pmax, d), b = __shfl_down(smin, d);
-            if (wi >= d) pmax = max(pmax, a);
-            if (wi + d < SEG) smin = min(smin, b);
-        }
-        const int pe = __shfl_up(pmax, 1), se = __shfl_down(smin, 1);
-        const int pv = wi == 0 ? INT_MIN : pe, nx = wi == SEG - 1 ? INT_MAX : se;
-        if (wi < HW64)
-            tile[wi * STR + xl] = make_uint4((unsigned)(word & 0xffffffffull), (unsigned)(word >> 32),
-                                             (unsigned)(pv == INT_MIN ? -kFar : pv), (unsigned)(nx == INT_MAX ? kFar : nx));
-    }
-    __syncthreads();
-    uint4* out = reinterpret_cast<uint4*>(desc);
-    for (int idx = threadIdx.x; idx < HW64 * XT; idx += 256) {
-        const int w = idx / XT, xl = idx - w * XT;
-        if (x0 + xl < W) out[((size_t)k * HW64 + w) * W + x0 + xl] = tile[w * STR + xl];
-    }
-    // The slice's seeded columns, one bit per column ((W + 63) / 64 words of 64 bits per slice, written as 32-bit halves):
-    // the L2 sweep skips the others, and every one of its workgroups used to rebuild this mask from the descriptors.
-    if (colmask && wave == 0) {
-        const bool seeded = lane < XT && x0 + lane < W && !desc_seedless(tile[min(lane, XT - 1)]);  // chunk 0's descriptor says it for the column
-        const unsigned long long mk = __ballot(seeded);
-        unsigned* dst = colmask + ((size_t)k * ((W + 63) >> 6) + (x0 >> 6)) * 2;
-        if (XT == 64) { if (lane < 2) dst[lane] = lane ? (unsigned)(mk >> 32) : (unsigned)mk; }
-        else {
-            const int half = (x0 >> 5) & 1;
-            if (lane == 0) dst[half] = (unsigned)mk;
-            if (lane == 1 && half == 0 && x0 + 32 >= W) dst[1] = 0u;  // no block for the word's upper half
-        }
-    }
+    coldesc_from_bits<SEG, XT>(tile, bits, desc, W, HW64, colmask, k, x0, lane, wave);
 }
 
 // ---- The two L1 sweeps with ONE pass over the volume (round 3).
@@ -639,9 +600,12 @@ BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after) {
     L.off_integral = L.off_prop + align16(plan.prop.size() * sizeof(PropStep));
     L.off_keys = L.off_integral + align16(plan.integral.size() * sizeof(IntegralDesc));
     L.off_slice = L.off_keys + align16(plan.keys.size() * sizeof(float));
-    L.off_cost = L.off_slice + align16(plan.slice_first.size() * sizeof(int32_t));
+    L.off_pixels = L.off_slice + align16(plan.slice_first.size() * sizeof(int32_t));
+    L.off_cost = L.off_pixels + align16(plan.seeds.on_device ? 0 : plan.seeds.bytes());  // (pixels in front of the cost: one copy takes them)
     L.plan = L.off_cost + align16((size_t)L.nchunks * sizeof(int32_t));
     if (L.empty) return L;
+    if (plan.seeds.kind != SeedKind::lines && HW64 > 64) throw std::string("feature maps from images or labels are limited to 4096 x 4096");
+    if (plan.seeds.kind == SeedKind::image) L.labels = plan.seeds.bytes();
     const size_t ncols = (size_t)m * W, islices = (size_t)m * ivol_slice_floats(W, H);
     L.vol = islices * sizeof(float);  // the transforms, and later the integrated volume, interleaved (>= m W H floats)
     if (HW64 > 64) L.bitmap = ncols * HW64 * 8;        // (feature sizes above 4096 only: k_seeds + k_coldesc)
@@ -678,7 +642,7 @@ void reserve_build(fdcm_featuremap* fm, const BuildLayout& L) {
     // handle's first build) stalls the host for 0.5 - 1 ms while the GPU idles inside the stage events' span
     BuildBuffers& b = fm->build;
     fm->vol.reserve(L.vol); b.bitmap.reserve(L.bitmap); fm->ivol.reserve(L.ivol);
-    b.coldesc.reserve(L.coldesc); b.colmask.reserve(L.colmask);
+    b.coldesc.reserve(L.coldesc); b.colmask.reserve(L.colmask); b.labels.reserve(L.labels);
     const void *stack_before = b.stack.p, *offtab_before = b.offtab.p;
     b.stack.reserve(L.stack); b.offtab.reserve(L.offtab);
     if (b.stack.p != stack_before) fm->sweep.reset();  // a new scratch: no cost table, no steal counter
@@ -689,12 +653,16 @@ void reserve_build(fdcm_featuremap* fm, const BuildLayout& L) {
 // ---- the stages of a build, in run_build's order: each takes the layout, the plan's device pointers and the handle, and queues on its stream
 struct PlanOnDevice {  // the uploaded blob's parts (BuildLayout::off_*)
     const RasterLine* raster; const int* slice_first; const PropStep* prop; const IntegralDesc* integral; int n_raster, n_prop;
+    const float* keys; const uint8_t* pixels; int pixel_stride;  // the seed source's pixels on the device (SeedKind::labels / image)
 };
 static void mark(fdcm_featuremap* fm, int i, bool on) { if (on) FDCM_HIP(hipEventRecord(fm->timing.ev[i], fm->stream)); }
 
 // The balanced sweep's launch order and dynamic cuts.  Queues the order from the previous build's costs and the steal counter's
 // reset, both in front of the plan's upload; fills proxy_cost when the order takes the proxy instead, which travels with the plan.
-static SweepBuf setup_balanced_sweep(fdcm_featuremap* fm, const BuildLayout& L, const BuildPlan& plan, std::vector<int32_t>& proxy_cost) {
+// A build whose seeds are pixels has no line boxes for the host's proxy: pass 1 counts it on the device (device_proxy: the
+// cost region is cleared here, k_coldesc_labels adds to it, and stage_pass1 queues the order behind it -- no read-back).
+static SweepBuf setup_balanced_sweep(fdcm_featuremap* fm, const BuildLayout& L, const BuildPlan& plan, std::vector<int32_t>& proxy_cost,
+                                     bool& device_proxy) {
     SweepBuf sb{};
     hipStream_t st = fm->stream;
     char* sp = (char*)fm->build.stack.p;
@@ -706,7 +674,9 @@ static SweepBuf setup_balanced_sweep(fdcm_featuremap* fm, const BuildLayout& L, 
     // every build after a change of size, takes the host's proxy per chunk (sweep_cost_proxy), which arrives with the plan.
     const bool want_order = test_switches().sweep_order || nchunks > resident;
     const bool have_cost = want_order && fm->sweep.cost_chunks == nchunks && fm->sweep.cost_w == W;
-    if (want_order && !have_cost) sweep_cost_proxy(plan, proxy_cost);
+    device_proxy = want_order && !have_cost && plan.seeds.kind != SeedKind::lines;
+    if (device_proxy) FDCM_HIP(hipMemsetAsync(sp + L.o_cost, 0, (size_t)nchunks * 4, st));
+    else if (want_order && !have_cost) sweep_cost_proxy(plan, proxy_cost);
     if (have_cost) launch_sweep_order(st, (const int*)(sp + L.o_cost), (int)nchunks, (int*)(sp + L.o_ord));
     if (want_order) (have_cost ? g_order_from_history : g_order_from_proxy).fetch_add(1, std::memory_order_relaxed);
     sb.ent = (EnvEntry*)(sp + L.o_ent); sb.own = (OwnEntry*)(sp + L.o_own); sb.cost = (int*)(sp + L.o_cost);
@@ -732,18 +702,38 @@ static PlanOnDevice upload_plan(fdcm_featuremap* fm, const BuildLayout& L, const
     auto put = [hs](size_t off, const auto& v) { if (!v.empty()) std::memcpy(hs + off, v.data(), v.size() * sizeof(v[0])); };
     put(L.off_raster, plan.raster); put(L.off_prop, plan.prop); put(L.off_integral, plan.integral);
     put(L.off_keys, plan.keys); put(L.off_slice, plan.slice_first); put(L.off_cost, proxy_cost);
+    const SeedSource& src = plan.seeds;
+    if (src.bytes() && !src.on_device)  // rows packed: the kernels read them with a stride of `width`
+        for (int y = 0; y < src.height; ++y) std::memcpy(hs + L.off_pixels + (size_t)y * src.width, src.pixels + (size_t)y * src.row_stride, (size_t)src.width);
     const char* dp = (const char*)fm->build.plan.p;
     FDCM_HIP(hipMemcpyAsync(fm->build.plan.p, hs, proxy_order ? L.plan : L.off_cost, hipMemcpyHostToDevice, fm->stream));
     if (proxy_order)
         launch_sweep_order(fm->stream, (const int*)(dp + L.off_cost), (int)L.nchunks, (int*)((char*)fm->build.stack.p + L.o_ord));
     return PlanOnDevice{(const RasterLine*)(dp + L.off_raster), (const int*)(dp + L.off_slice), (const PropStep*)(dp + L.off_prop),
-                        (const IntegralDesc*)(dp + L.off_integral), (int)plan.raster.size(), (int)plan.prop.size()};
+                        (const IntegralDesc*)(dp + L.off_integral), (int)plan.raster.size(), (int)plan.prop.size(),
+                        (const float*)(dp + L.off_keys), src.on_device ? src.pixels : (const uint8_t*)(dp + L.off_pixels),
+                        src.on_device ? src.row_stride : src.width};
 }
 // pass 1: the seeds and the column descriptors
-static void stage_pass1(fdcm_featuremap* fm, const BuildLayout& L, const PlanOnDevice& P) {
+static void stage_pass1(fdcm_featuremap* fm, const BuildLayout& L, const PlanOnDevice& P, const SeedSource& src, bool device_proxy) {
     hipStream_t st = fm->stream;
     const int W = (int)fm->W, H = (int)fm->H, m = (int)fm->m, HW64 = L.HW64;
     ColDesc* d_desc = fm->build.coldesc.as<ColDesc>();
+    if (src.kind != SeedKind::lines) {
+        // pixels: an image becomes labels first (the seeds stage), and the tile kernel's sibling fills its bitmap tile from the labels
+        const uint8_t* labels = P.pixels;
+        fm->built.seeds_fused = src.kind == SeedKind::labels;
+        if (src.kind == SeedKind::image) {
+            launch_edge_labels(st, P.pixels, src.width, src.height, P.pixel_stride, P.keys, m, src.threshold, fm->build.labels.as<uint8_t>());
+            labels = fm->build.labels.as<uint8_t>();
+            mark(fm, 1, fm->built.stage_events);
+        }
+        char* sp = (char*)fm->build.stack.p;
+        launch_coldesc_labels(st, labels, src.width, src.height, src.border, d_desc, W, H, HW64, m, (unsigned*)fm->build.colmask.p,
+                              device_proxy ? (int*)(sp + L.o_cost) : nullptr);
+        if (device_proxy) launch_sweep_order(st, (const int*)(sp + L.o_cost), (int)L.nchunks, (int*)(sp + L.o_ord));
+        return;
+    }
     fm->built.seeds_fused = HW64 <= 64;
     if (fm->built.seeds_fused) {
         // the tile kernel rasterises the seeds of its columns itself (LDS): no bitmap, no k_seeds, no stage of its own
@@ -849,11 +839,13 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
     const BuildLayout L = build_layout(plan, fm->distance, stop_after);
     reserve_build(fm, L);
     fm->W = plan.W; fm->H = plan.H; fm->m = plan.m; fm->tx = plan.tx; fm->ty = plan.ty; fm->keys = plan.keys;
+    fm->pixel_seeded = plan.seeds.kind != SeedKind::lines;
     fm->last_build = fdcm_build_timing{}; fm->built.reset(); fm->holds = VolStage::none;
     if (L.empty) return;
     SweepBuf sb{};
     std::vector<int32_t> proxy_cost;  // (stays empty unless the sweep's launch order takes it)
-    if (L.balanced) sb = setup_balanced_sweep(fm, L, plan, proxy_cost);
+    bool device_proxy = false;        // the launch order's costs are counted by pass 1
+    if (L.balanced) sb = setup_balanced_sweep(fm, L, plan, proxy_cost, device_proxy);
     else fm->sweep.reset();  // the L1 minima or the literal pass's scratch take the whole of `stack`
     const PlanOnDevice P = upload_plan(fm, L, plan, proxy_cost);
     BuildRecord& b = fm->built;
@@ -861,7 +853,7 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
     b.stage_events = fm->want_stage_events == 1;  // (an event between two kernels costs a blocking frame 3 - 5 us: fdcm_featuremap_stage_timing)
     b.total_events = fm->want_stage_events != 0;
     mark(fm, 0, b.total_events);
-    stage_pass1(fm, L, P);  // (event 1 behind its seeds, where they are a kernel of their own)
+    stage_pass1(fm, L, P, plan.seeds, device_proxy);  // (event 1 behind its seeds, where they are a kernel of their own)
     mark(fm, 2, b.stage_events);
     stage_sweep(fm, L, sb);
     mark(fm, 3, b.stage_events);

@@ -88,6 +88,56 @@ __device__ __forceinline__ void desc_lane(const ColDesc& d, int j, unsigned long
     nc = __builtin_amdgcn_readlane(d.next, j);
 }
 
+// The descriptor step of pass 1 for H <= 4096 (k_coldesc_tile, k_coldesc_labels): a block of 256 threads holds the seed bits of
+// XT neighbouring columns of slice k in LDS (bits[word][XT]); SEG lanes (16 / 32 / 64: the words of a column) scan one column
+// each, 64 / SEG columns per wave pass, and the descriptors go through LDS (tile[word][XT + 1]) so that every store covers the
+// block's columns of one chunk.  Behind a barrier that follows the last write of `bits`.
+template <int SEG, int XT>
+__device__ __forceinline__ void coldesc_from_bits(uint4* tile, unsigned long long* bits, ColDesc* desc, int W, int HW64,
+                                                  unsigned* colmask, long k, int x0, int lane, int wave) {
+    constexpr int STR = XT + 1;
+    const int wi = lane & (SEG - 1), ci = lane / SEG;
+    constexpr int CPP = 64 / SEG, CPW = XT / 4;  // columns per wave pass, columns per wave
+    for (int pass = 0; pass < CPW / CPP; ++pass) {
+        const int xl = wave * CPW + pass * CPP + ci, x = x0 + xl;
+        const bool valid = x < W && wi < HW64;
+        const unsigned long long word = valid ? bits[wi * XT + xl] : 0ull;
+        const int last_i = word ? wi * 64 + 63 - __clzll(word) : INT_MIN;
+        const int first_i = word ? wi * 64 + (__ffsll((long long)word) - 1) : INT_MAX;
+        int pmax = last_i, smin = first_i;  // inclusive scans inside the SEG lanes of a column
+#pragma unroll
+        for (int d = 1; d < SEG; d <<= 1) {
+            const int a = __shfl_up(pmax, d), b = __shfl_down(smin, d);
+            if (wi >= d) pmax = max(pmax, a);
+            if (wi + d < SEG) smin = min(smin, b);
+        }
+        const int pe = __shfl_up(pmax, 1), se = __shfl_down(smin, 1);
+        const int pv = wi == 0 ? INT_MIN : pe, nx = wi == SEG - 1 ? INT_MAX : se;
+        if (wi < HW64)
+            tile[wi * STR + xl] = make_uint4((unsigned)(word & 0xffffffffull), (unsigned)(word >> 32),
+                                             (unsigned)(pv == INT_MIN ? -kFar : pv), (unsigned)(nx == INT_MAX ? kFar : nx));
+    }
+    __syncthreads();
+    uint4* out = reinterpret_cast<uint4*>(desc);
+    for (int idx = threadIdx.x; idx < HW64 * XT; idx += 256) {
+        const int w = idx / XT, xl = idx - w * XT;
+        if (x0 + xl < W) out[((size_t)k * HW64 + w) * W + x0 + xl] = tile[w * STR + xl];
+    }
+    // The slice's seeded columns, one bit per column ((W + 63) / 64 words of 64 bits per slice, written as 32-bit halves):
+    // the L2 sweep skips the others, and every one of its workgroups used to rebuild this mask from the descriptors.
+    if (colmask && wave == 0) {
+        const bool seeded = lane < XT && x0 + lane < W && !desc_seedless(tile[min(lane, XT - 1)]);  // chunk 0's descriptor says it for the column
+        const unsigned long long mk = __ballot(seeded);
+        unsigned* dst = colmask + ((size_t)k * ((W + 63) >> 6) + (x0 >> 6)) * 2;
+        if (XT == 64) { if (lane < 2) dst[lane] = lane ? (unsigned)(mk >> 32) : (unsigned)mk; }
+        else {
+            const int half = (x0 >> 5) & 1;
+            if (lane == 0) dst[half] = (unsigned)mk;
+            if (lane == 1 && half == 0 && x0 + 32 >= W) dst[1] = 0u;  // no block for the word's upper half
+        }
+    }
+}
+
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct EnvEntry { float v2; float P; float z; };     // one stack entry (imgproc.h: v[k], f[v[k]], z[k]) as the sweep's tests use it: 2 v, f[v] + v^2, z

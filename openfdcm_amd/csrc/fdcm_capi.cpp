@@ -139,6 +139,92 @@ int fdcm_featuremap_rebuild(fdcm_featuremap* fm, const float* scene_lines, int64
     });
 }
 
+// ------------------------------------------------------------------------------------------ feature maps from images
+// Everything an image / label build checks before it touches a device; fills the plan of the shape (no scene is made up).
+static void pixel_plan(const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device, SeedKind kind,
+                       int threshold, int64_t border, int64_t depth, float coeff, BuildPlan& plan) {
+    require(pixels != nullptr, kind == SeedKind::image ? "image is null" : "labels is null");
+    require(width >= 1 && height >= 1, "width and height must be at least 1");
+    require(border >= 0, "border must be >= 0");
+    require(width + 2 * border <= 4096 && height + 2 * border <= 4096, "feature maps from images are limited to 4096 x 4096 (border included)");
+    require(row_stride >= width, "row_stride must be >= width");
+    require(on_device == 0 || on_device == 1, "on_device must be 0 or 1");
+    if (kind == SeedKind::image) require(threshold >= 1 && threshold <= 1442, "threshold must be in [1, 1442]");
+    require(depth >= 0, "depth must be >= 0");
+    require(depth <= 255, "depth gives more than 255 orientation keys: a label is one byte");
+    plan = BuildPlan{};
+    make_shape_plan(depth, coeff, width + 2 * border, height + 2 * border, plan);
+    plan.tx = plan.ty = (float)border;
+    plan.seeds.kind = kind; plan.seeds.pixels = pixels; plan.seeds.on_device = on_device != 0;
+    plan.seeds.width = (int)width; plan.seeds.height = (int)height; plan.seeds.row_stride = (int)row_stride;
+    plan.seeds.border = (int)border; plan.seeds.threshold = threshold;
+}
+
+static int build_from_pixels(const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device, SeedKind kind,
+                             int threshold, int64_t border, int64_t depth, float coeff, int distance, int stop_after, fdcm_featuremap** out) {
+    fdcm_featuremap* fm = nullptr;
+    int rc = guarded([&] {
+        require(out != nullptr, "out is null");
+        require(distance >= FDCM_L2 && distance <= FDCM_L1, "unknown distance");
+        require(stop_after >= 1 && stop_after <= 3, "stop_after must be 1..3");
+        BuildPlan plan;
+        pixel_plan(pixels, width, height, row_stride, on_device, kind, threshold, border, depth, coeff, plan);
+        fm = new fdcm_featuremap();
+        fm->device = g_device;
+        fm->depth_param = depth; fm->coeff = coeff; fm->padding = 0.f; fm->distance = distance;
+        run_build(fm, plan, stop_after);
+        *out = fm;
+    });
+    if (rc != FDCM_OK) { destroy(fm); if (out) *out = nullptr; }
+    return rc;
+}
+
+static int rebuild_from_pixels(fdcm_featuremap* fm, const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                               SeedKind kind, int threshold, int64_t border) {
+    return guarded([&] {
+        require(fm != nullptr, "featuremap is null");
+        BuildPlan plan;
+        pixel_plan(pixels, width, height, row_stride, on_device, kind, threshold, border, fm->depth_param, fm->coeff, plan);
+        run_build(fm, plan, 3);
+    });
+}
+
+int fdcm_edge_labels(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int64_t depth, int threshold,
+                     uint8_t* labels_out) {
+    return guarded([&] {
+        require(labels_out != nullptr, "labels_out is null");
+        require(depth >= 1, "depth must be >= 1");
+        BuildPlan plan;
+        pixel_plan(image, width, height, row_stride, 0, SeedKind::image, threshold, 0, depth, 0.f, plan);
+        edge_labels_host(g_device, image, (int)width, (int)height, (int)row_stride, depth, threshold, labels_out);
+    });
+}
+
+int fdcm_featuremap_build_image(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device, int threshold,
+                                int64_t border, int64_t depth, float dt3_coeff, int distance, fdcm_featuremap** out) {
+    return build_from_pixels(image, width, height, row_stride, on_device, SeedKind::image, threshold, border, depth, dt3_coeff, distance, 3, out);
+}
+
+int fdcm_featuremap_build_image_staged(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device, int threshold,
+                                       int64_t border, int64_t depth, float dt3_coeff, int distance, int stop_after, fdcm_featuremap** out) {
+    return build_from_pixels(image, width, height, row_stride, on_device, SeedKind::image, threshold, border, depth, dt3_coeff, distance,
+                             stop_after, out);
+}
+
+int fdcm_featuremap_rebuild_image(fdcm_featuremap* fm, const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                                  int threshold, int64_t border) {
+    return rebuild_from_pixels(fm, image, width, height, row_stride, on_device, SeedKind::image, threshold, border);
+}
+
+int fdcm_featuremap_build_labels(const uint8_t* labels, int64_t width, int64_t height, int on_device, int64_t border, int64_t depth,
+                                 float dt3_coeff, int distance, fdcm_featuremap** out) {
+    return build_from_pixels(labels, width, height, width, on_device, SeedKind::labels, 0, border, depth, dt3_coeff, distance, 3, out);
+}
+
+int fdcm_featuremap_rebuild_labels(fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device, int64_t border) {
+    return rebuild_from_pixels(fm, labels, width, height, width, on_device, SeedKind::labels, 0, border);
+}
+
 int fdcm_featuremap_free(fdcm_featuremap* fm) {
     destroy(fm);
     return FDCM_OK;
@@ -149,7 +235,7 @@ int fdcm_featuremap_get_info(const fdcm_featuremap* fm, fdcm_featuremap_info* in
         require(fm && info, "null argument");
         info->width = fm->W; info->height = fm->H; info->depth = fm->m;
         info->scene_translation[0] = fm->tx; info->scene_translation[1] = fm->ty;
-        info->distance = fm->distance; info->dt3_coeff = fm->coeff; info->padding = fm->padding;
+        info->distance = fm->distance; info->dt3_coeff = fm->coeff; info->padding = fm->pixel_seeded ? 0.f : fm->padding;
     });
 }
 

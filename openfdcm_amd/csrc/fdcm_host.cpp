@@ -171,47 +171,21 @@ void sweep_cost_proxy(const BuildPlan& plan, std::vector<int32_t>& cost) {
     }
 }
 
-void make_build_plan(const float* lines, int64_t n, int64_t depth, float coeff, float padding, BuildPlan& plan) {
-    plan = BuildPlan{};
-    if (n == 0) return;
-    // getSceneCenteredTranslation, dt3cpu.cpp:109-116 (+ minmaxPoint, math.h:166-171)
-    float mnx = lines[0], mny = lines[1], mxx = mnx, mxy = mny;
-    for (int64_t i = 0; i < 2 * n; ++i) {
-        const float x = lines[2 * i], y = lines[2 * i + 1];
-        mnx = std::min(mnx, x); mxx = std::max(mxx, x);
-        mny = std::min(mny, y); mxy = std::max(mxy, y);
-    }
-    const float dx = mxx - mnx, dy = mxy - mny;
-    const float corrected_ratio = std::max(1.f, padding);
-    const float req = (corrected_ratio * std::max(dx, dy)) * 1.f;
-    plan.tx = req / 2.f - (mxx + mnx) / 2.f;
-    plan.ty = req / 2.f - (mxy + mny) / 2.f;
-    plan.W = plan.H = (int64_t)(size_t)std::ceil(req + 1.f);
+void plan_keys(int64_t depth, std::vector<float>& keys) {
     // angle keys, dt3cpu.h:188-190 (std::set<float>)
-    for (int64_t i = 0; i < depth; ++i) plan.keys.push_back(float(i) * kPif / float(depth) - kPi2f);
-    std::sort(plan.keys.begin(), plan.keys.end());
-    plan.keys.erase(std::unique(plan.keys.begin(), plan.keys.end()), plan.keys.end());
+    keys.clear();
+    for (int64_t i = 0; i < depth; ++i) keys.push_back(float(i) * kPif / float(depth) - kPi2f);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+}
+
+void make_shape_plan(int64_t depth, float coeff, int64_t W, int64_t H, BuildPlan& plan) {
+    plan.W = W; plan.H = H;
+    plan_keys(depth, plan.keys);
     plan.m = (int64_t)plan.keys.size();
     const int m = (int)plan.m;
-    // classifyLines (dt3cpu.h:123-134) + clipLines + rasterizeLine per class.  Lines are visited
-    // slice by slice in index order like the reference; the seed set is order independent.
-    const float xmax = (float)(plan.W - 1), ymax = (float)(plan.H - 1);
-    std::vector<std::vector<RasterLine>> per_slice((size_t)m);
-    for (int64_t i = 0; i < n; ++i) {
-        float l[4] = {lines[4 * i] + plan.tx, lines[4 * i + 1] + plan.ty, lines[4 * i + 2] + plan.tx,
-                      lines[4 * i + 3] + plan.ty};  // translate, math.h:352-354
-        const float angle = std::atan((l[3] - l[1]) / (l[2] - l[0]));  // getAngle, math.h:295-299
-        const int k = closest_orientation(plan.keys.data(), m, angle);
-        if (!clip_line(l, xmax, ymax)) continue;
-        per_slice[k].push_back(raster_descriptor(l, k));
-        plan.boxes.push_back(LineBox{k, std::min(l[0], l[2]), std::max(l[0], l[2]), std::min(l[1], l[3]), std::max(l[1], l[3])});
-    }
-    plan.slice_first.assign((size_t)m + 1, 0);
-    for (int k = 0; k < m; ++k) {
-        plan.slice_first[k] = (int32_t)plan.raster.size();
-        plan.raster.insert(plan.raster.end(), per_slice[k].begin(), per_slice[k].end());
-    }
-    plan.slice_first[m] = (int32_t)plan.raster.size();
+    plan.prop.clear(); plan.integral.clear();
+    if (m == 0) return;
     // propagateOrientation step table, dt3cpu.cpp:86-106
     {
         const int fwd = static_cast<int>(std::ceil(1.5 * m));
@@ -237,6 +211,45 @@ void make_build_plan(const float* lines, int64_t n, int64_t depth, float coeff, 
         else if (std::abs(ry) == 1) { d.mode = 2; d.s = (int)(long)ry; d.r = rx; }
         plan.integral.push_back(d);
     }
+}
+
+void make_build_plan(const float* lines, int64_t n, int64_t depth, float coeff, float padding, BuildPlan& plan) {
+    plan = BuildPlan{};
+    if (n == 0) return;
+    // getSceneCenteredTranslation, dt3cpu.cpp:109-116 (+ minmaxPoint, math.h:166-171)
+    float mnx = lines[0], mny = lines[1], mxx = mnx, mxy = mny;
+    for (int64_t i = 0; i < 2 * n; ++i) {
+        const float x = lines[2 * i], y = lines[2 * i + 1];
+        mnx = std::min(mnx, x); mxx = std::max(mxx, x);
+        mny = std::min(mny, y); mxy = std::max(mxy, y);
+    }
+    const float dx = mxx - mnx, dy = mxy - mny;
+    const float corrected_ratio = std::max(1.f, padding);
+    const float req = (corrected_ratio * std::max(dx, dy)) * 1.f;
+    plan.tx = req / 2.f - (mxx + mnx) / 2.f;
+    plan.ty = req / 2.f - (mxy + mny) / 2.f;
+    const int64_t S = (int64_t)(size_t)std::ceil(req + 1.f);
+    make_shape_plan(depth, coeff, S, S, plan);
+    const int m = (int)plan.m;
+    // classifyLines (dt3cpu.h:123-134) + clipLines + rasterizeLine per class.  Lines are visited
+    // slice by slice in index order like the reference; the seed set is order independent.
+    const float xmax = (float)(plan.W - 1), ymax = (float)(plan.H - 1);
+    std::vector<std::vector<RasterLine>> per_slice((size_t)m);
+    for (int64_t i = 0; i < n; ++i) {
+        float l[4] = {lines[4 * i] + plan.tx, lines[4 * i + 1] + plan.ty, lines[4 * i + 2] + plan.tx,
+                      lines[4 * i + 3] + plan.ty};  // translate, math.h:352-354
+        const float angle = std::atan((l[3] - l[1]) / (l[2] - l[0]));  // getAngle, math.h:295-299
+        const int k = closest_orientation(plan.keys.data(), m, angle);
+        if (!clip_line(l, xmax, ymax)) continue;
+        per_slice[k].push_back(raster_descriptor(l, k));
+        plan.boxes.push_back(LineBox{k, std::min(l[0], l[2]), std::max(l[0], l[2]), std::min(l[1], l[3]), std::max(l[1], l[3])});
+    }
+    plan.slice_first.assign((size_t)m + 1, 0);
+    for (int k = 0; k < m; ++k) {
+        plan.slice_first[k] = (int32_t)plan.raster.size();
+        plan.raster.insert(plan.raster.end(), per_slice[k].begin(), per_slice[k].end());
+    }
+    plan.slice_first[m] = (int32_t)plan.raster.size();
 }
 
 

@@ -90,6 +90,19 @@ struct IntegralDesc {
 
 struct LineBox { int32_t slice; float xlo, xhi, ylo, yhi; };
 
+// Where the seeds of a build come from: the plan's clipped scene lines, a label image (one byte per pixel, row-major, value k
+// < m: a seed of slice k, anything else: none), or a grey image whose oriented edge pixels become the labels first
+// (k_edge_labels).  Pixel (x, y) seeds map pixel (x + border, y + border).  The pixels are host memory, which travels in the
+// plan's blob with rows packed, or memory of the handle's device, which is read in place while the build runs.
+enum class SeedKind { lines, labels, image };
+struct SeedSource {
+    SeedKind kind = SeedKind::lines;
+    const uint8_t* pixels = nullptr;
+    bool on_device = false;
+    int width = 0, height = 0, row_stride = 0, border = 0, threshold = 0;
+    size_t bytes() const { return kind == SeedKind::lines ? 0 : (size_t)width * (size_t)height; }
+};
+
 struct BuildPlan {
     int64_t W = 0, H = 0, m = 0;
     float tx = 0, ty = 0;
@@ -99,6 +112,7 @@ struct BuildPlan {
     std::vector<PropStep> prop;
     std::vector<IntegralDesc> integral;
     std::vector<LineBox> boxes;       // the clipped lines' bounding boxes (what sweep_cost_proxy works from)
+    SeedSource seeds;                 // (lines: raster / slice_first / boxes above; else they stay empty)
 };
 
 // Every size and offset (bytes) a build of one shape takes: reserve_build sizes the buffers from it, run_build takes its
@@ -109,12 +123,17 @@ struct BuildLayout {
     int HW64 = 0, slots = 0;  // 64-row chunks per column; stack and owner entries per row of the balanced sweep
     long nchunks = 0;       // (slice, 64-row chunk) pairs
     size_t vol = 0, ivol = 0, bitmap = 0, coldesc = 0, colmask = 0, offtab = 0, stack = 0;
+    size_t labels = 0;      // the label image an image build makes of its pixels
     size_t o_ent = 0, o_own = 0, o_ord = 0, o_cost = 0, o_steals = 0;  // inside `stack` (balanced sweep)
-    // plan blob: RasterLine[] | PropStep[] | IntegralDesc[] | keys[] | slice_first[] | per-chunk proxy cost[]
-    size_t off_raster = 0, off_prop = 0, off_integral = 0, off_keys = 0, off_slice = 0, off_cost = 0, plan = 0;
+    // plan blob: RasterLine[] | PropStep[] | IntegralDesc[] | keys[] | slice_first[] | host pixels of the seed source | per-chunk proxy cost[]
+    size_t off_raster = 0, off_prop = 0, off_integral = 0, off_keys = 0, off_slice = 0, off_pixels = 0, off_cost = 0, plan = 0;
 };
 // Host side of buildCpuFeaturemap (dt3cpu.h:174-198 + the scalar parts of :227-231).
 void make_build_plan(const float* lines, int64_t n, int64_t depth, float coeff, float padding, BuildPlan& plan);
+// The parts of a plan that the shape alone decides: the distinct angle keys of `depth`, the propagation's steps and the line
+// integral's direction per slice (make_build_plan's, and all of the plan of a build whose seeds are pixels).
+void plan_keys(int64_t depth, std::vector<float>& keys);
+void make_shape_plan(int64_t depth, float coeff, int64_t W, int64_t H, BuildPlan& plan);
 // per (slice, 64-row chunk): a proxy of the L2 sweep's time, for the launch order of a build without history
 void sweep_cost_proxy(const BuildPlan& plan, std::vector<int32_t>& cost);
 
@@ -161,7 +180,7 @@ struct GroupTable { int m = 0, steps = 0; void reset() { *this = GroupTable{}; }
 // The last build of the handle, from run_build to finish_build.
 struct BuildRecord {
     bool pending = false;       // queued on `stream` but not waited for
-    bool seeds_fused = false;   // it drew its seeds inside k_coldesc_tile (no seeds stage, no event for it)
+    bool seeds_fused = false;   // it drew its seeds inside k_coldesc_tile / took them from labels (no seeds stage, no event for it)
     bool stage_events = false, total_events = false;  // it recorded an event between its stages (per-stage times) / its first and last one (span)
     float host_ms = 0.f;        // host time of the call up to its first kernel launch
     void reset() { *this = BuildRecord{}; }
@@ -170,11 +189,12 @@ struct BuildBuffers {  // what a build needs besides the volume, sized by BuildL
     DevBuf bitmap;   // m*W*ceil(H/64) uint64 seed bits along y (feature sizes above 4096 only: k_seeds + k_coldesc)
     DevBuf coldesc;  // m*ceil(H/64)*W column-chunk descriptors (16 B)
     DevBuf colmask;  // m*ceil(W/64) words: the seeded columns of every slice (k_coldesc_tile, for the L2 sweep)
+    DevBuf labels;   // image builds: the label image k_edge_labels writes and k_coldesc_labels reads
     DevBuf offtab;   // per slice: one word per group of 4 columns for the shallow sweeps of the line integral (k_groups)
     DevBuf stack;    // the sweep's scratch: the balanced sweep's stack and owner entries (slot-major per chunk), launch order,
                      // per-chunk costs and steal counter; or the literal pass's scratch; or the L1 pass's minima / carries
     DevBuf plan; PinnedBuf stage;  // the last build's plan (BuildLayout's blob) or the keys of an adopted volume; its host staging
-    void release() { for (DevBuf* b : {&bitmap, &coldesc, &colmask, &offtab, &stack, &plan}) b->release(); stage.release(); }
+    void release() { for (DevBuf* b : {&bitmap, &coldesc, &colmask, &labels, &offtab, &stack, &plan}) b->release(); stage.release(); }
 };
 struct SearchBuffers {
     DevBuf scene;     // scene lines + sorted lengths + sorted idx + candidate offsets
@@ -205,6 +225,7 @@ struct fdcm_featuremap {
     int64_t depth_param = 0;
     float coeff = 0, padding = 0;
     int distance = 0;
+    bool pixel_seeded = false;  // the last build took its seeds from an image or labels: no padding went into its geometry
     int want_stage_events = 1;  // fdcm_featuremap_stage_timing: 0 no events, 1 an event between the build's stages, 2 around the build and the search only
     bool shares_gpu = false;    // a frame slot of a pipeline with several frames in flight: other frames' kernels run beside this handle's
     // geometry
@@ -251,6 +272,14 @@ BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after);  
 // had to move drops the sweep's cost history and steal counter)
 void reserve_build(fdcm_featuremap* fm, const BuildLayout& L);
 void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after);
+// implemented in fdcm_image.hip: image -> label image (k_edge_labels), and pass 1 with its seeds from a label image
+// (k_coldesc_labels); `cost`, where given, receives the sweep's per-chunk proxy (zeroed by the caller)
+void launch_edge_labels(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
+                        int threshold, uint8_t* labels);
+void launch_coldesc_labels(hipStream_t st, const uint8_t* labels, int width, int height, int border, void* desc, int W, int H,
+                           int HW64, int m, unsigned* colmask, int* cost);
+void edge_labels_host(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth, int threshold,
+                      uint8_t* labels_out);
 // Waits for a queued build (if any) and fills fm->last_build.  run_build only queues the kernels: the search
 // that follows is ordered behind them on the same stream and its host-side preparation runs meanwhile.
 void finish_build(fdcm_featuremap* fm);

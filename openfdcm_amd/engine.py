@@ -44,6 +44,27 @@ def as_grid(grid):
     return capi.Grid(*vals)
 
 
+def _pixels(a, what):
+    """(pointer, width, height, row_stride, on_device, keep-alive) of a 2-D uint8 numpy array (copied unless its rows are
+    contiguous) or a 2-D CUDA torch.uint8 tensor (by data_ptr(), after its stream's pending work)."""
+    if isinstance(a, np.ndarray) or not hasattr(a, "data_ptr"):
+        a = np.asarray(a)
+        if a.ndim != 2 or a.dtype != np.uint8:
+            raise ValueError(f"{what} must be a 2-D uint8 array, got {a.dtype} with shape {a.shape}")
+        if a.size and (a.strides[1] != 1 or a.strides[0] < a.shape[1]):
+            a = np.ascontiguousarray(a)
+        stride = a.strides[0] if a.shape[0] > 1 and a.size else a.shape[1]
+        return C.c_void_p(a.ctypes.data), a.shape[1], a.shape[0], stride, 0, a
+    import torch
+    if a.dim() != 2 or a.dtype != torch.uint8 or not a.is_cuda:
+        raise ValueError(f"{what} must be a 2-D uint8 tensor on the GPU")
+    if a.numel() and (a.stride(1) != 1 or a.stride(0) < a.shape[1]):
+        a = a.contiguous()
+    torch.cuda.current_stream(a.device).synchronize()  # the build reads it from the handle's own stream
+    stride = a.stride(0) if a.shape[0] > 1 and a.numel() else a.shape[1]
+    return C.c_void_p(a.data_ptr()), a.shape[1], a.shape[0], stride, 1, a
+
+
 class DeviceFeatureMap:
     """Owns an fdcm_featuremap handle (DT3 volume resident in HBM)."""
 
@@ -92,6 +113,54 @@ class DeviceFeatureMap:
     def rebuild(self, scene):
         rec = capi.as_records(scene)
         capi.check(capi.lib().fdcm_featuremap_rebuild(self._h, capi.fptr(rec), rec.shape[0]))
+        self.refresh()
+
+    # ---- feature maps from images (include/fdcm.h, "feature maps from images"): image / labels are 2-D uint8, (H, W), a
+    #      numpy array or a CUDA torch tensor (read in place; kept alive here until the next build)
+    @classmethod
+    def build_image(cls, image, threshold, border=0, depth=30, coeff=5.0, distance=capi.L2, stop_after=3):
+        """The DT3 volume whose seeds are the oriented edge pixels of `image`: size (W + 2 border, H + 2 border), scene
+        translation (border, border)."""
+        p, w, h, stride, dev, keep = _pixels(image, "image")
+        out = C.c_void_p()
+        if stop_after == 3:
+            rc = capi.lib().fdcm_featuremap_build_image(p, w, h, stride, dev, int(threshold), int(border), int(depth),
+                                                        float(coeff), int(distance), C.byref(out))
+        else:
+            rc = capi.lib().fdcm_featuremap_build_image_staged(p, w, h, stride, dev, int(threshold), int(border), int(depth),
+                                                               float(coeff), int(distance), int(stop_after), C.byref(out))
+        capi.check(rc)
+        fm = cls(out)
+        fm._seed_pixels = keep
+        return fm
+
+    @classmethod
+    def build_labels(cls, labels, border=0, depth=30, coeff=5.0, distance=capi.L2):
+        """The same from a label image: value k < depth's key count seeds slice k, anything else is no edge."""
+        p, w, h, stride, dev, keep = _pixels(labels, "labels")
+        if stride != w:
+            keep = keep.contiguous() if dev else np.ascontiguousarray(keep)
+            p = C.c_void_p(keep.data_ptr() if dev else keep.ctypes.data)
+        out = C.c_void_p()
+        capi.check(capi.lib().fdcm_featuremap_build_labels(p, w, h, dev, int(border), int(depth), float(coeff), int(distance),
+                                                           C.byref(out)))
+        fm = cls(out)
+        fm._seed_pixels = keep
+        return fm
+
+    def rebuild_image(self, image, threshold, border=0):
+        p, w, h, stride, dev, keep = _pixels(image, "image")
+        capi.check(capi.lib().fdcm_featuremap_rebuild_image(self._h, p, w, h, stride, dev, int(threshold), int(border)))
+        self._seed_pixels = keep
+        self.refresh()
+
+    def rebuild_labels(self, labels, border=0):
+        p, w, h, stride, dev, keep = _pixels(labels, "labels")
+        if stride != w:
+            keep = keep.contiguous() if dev else np.ascontiguousarray(keep)
+            p = C.c_void_p(keep.data_ptr() if dev else keep.ctypes.data)
+        capi.check(capi.lib().fdcm_featuremap_rebuild_labels(self._h, p, w, h, dev, int(border)))
+        self._seed_pixels = keep
         self.refresh()
 
     def slice(self, k):
@@ -283,6 +352,18 @@ class DeviceTemplates:
             self.close()
         except Exception:
             pass
+
+
+def edge_labels(image, depth=30, threshold=60):
+    """The label image of a 2-D uint8 array (include/fdcm.h, "feature maps from images"), computed on the GPU: (H, W) uint8,
+    the orientation slice of every edge pixel and 255 elsewhere."""
+    a = np.asarray(image)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError(f"image must be a 2-D uint8 array, got {a.dtype} with shape {a.shape}")
+    p, w, h, stride, _, keep = _pixels(a, "image")
+    out = np.empty((h, w), dtype=np.uint8)
+    capi.check(capi.lib().fdcm_edge_labels(p, w, h, stride, int(depth), int(threshold), C.c_void_p(out.ctypes.data)))
+    return out
 
 
 def search_raw(fm, templates, scene, max_tmpl_lines, max_scene_lines, optimizer=capi.BATCH_OPTIMIZE, batch_size=10,
