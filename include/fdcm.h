@@ -136,7 +136,8 @@ int fdcm_featuremap_build_staged(const float* scene_lines, int64_t n_lines, int6
  * Direction for thinning, with a = |gx|, b = |gy| (12/29 ~ tan 22.5 deg):  29 b < 12 a: d = (1, 0);  29 a < 12 b: d = (0, 1);
  *   otherwise d = (1, 1) when (gx >= 0) == (gy >= 0), else d = (1, -1).
  * Edge pixel p: m2(p) >= threshold^2 (1 <= threshold <= 1442), m2(p) > m2(p - d) and m2(p) >= m2(p + d); a neighbour outside
- *   the image has m2 = 0.  (Of a two-pixel plateau one pixel wins.)  No smoothing, no hysteresis.
+ *   the image has m2 = 0.  (Of a two-pixel plateau one pixel wins.)  Smoothing, hysteresis and a minimum chain length are optional:
+ *   the _ex entry points below.
  * Orientation label: the edge's tangent (-gy, gx): dx = float(-gy) (the integer is negated, so gy = 0 gives +0), dy = float(gx),
  *   angle = atanf(dy / dx) as getAngle (math.h:295-299; IEEE division, dx = 0 gives +-pi/2), label = closestOrientation
  *   (dt3cpu.h:93-114) over the m distinct keys that a line build of the same depth makes.
@@ -166,6 +167,31 @@ int fdcm_featuremap_build_labels(const uint8_t* labels, int64_t width, int64_t h
                                  int64_t depth, float dt3_coeff, int distance, fdcm_featuremap** out);
 int fdcm_featuremap_rebuild_labels(fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device,
                                    int64_t border);
+/* ---- edges with smoothing, hysteresis and a minimum chain length.  Integer arithmetic up to the divide the label has.
+ * Smoothing: S = I for smooth = 0;  S(x,y) = (sum_ij w(i) w(j) I(x+i, y+j) + 8) >> 4 with w = [1 2 1] for smooth = 1;
+ *   S = (sum ... + 128) >> 8 with w = [1 4 6 4 1] for smooth = 2; I clamped to the image (replicate border).  S is a uint8
+ *   image of the same size, and the definitions above apply to S in place of I: the gradient reads S clamped to the image
+ *   (the smoothed pixel at the clamped coordinate, not the smoothing of an extended image).  m2 <= 2 * 1020^2 still holds.
+ * Candidate: a pixel that passes the thinning rule above (m2(p) > m2(p - d), m2(p) >= m2(p + d), m2 = 0 outside the image)
+ *   with m2 >= low^2.  Strong: a candidate with m2 >= high^2.  Component: a maximal 8-connected set of candidates.
+ * Edge pixel: a candidate whose component holds at least one strong pixel and at least min_pixels candidates.  Its label is
+ *   the one above (tangent (-gy, gx) of S's gradient, atanf, closestOrientation); everything else is 255.
+ * smooth = 0, low = high = t, min_pixels = 1 is exactly fdcm_edge_labels(threshold = t), byte for byte.  The result is a
+ *   set: it does not depend on the order in which the GPU visits or merges pixels.
+ * Argument errors besides their siblings': params NULL, smooth outside {0, 1, 2}, low < 1, high > 1442, low > high,
+ * min_pixels < 1: FDCM_EINVAL before any GPU work.  The builds return once queued: the components are resolved on the device. ---- */
+typedef struct fdcm_edge_params {
+    int32_t smooth;      /* 0, 1 or 2 */
+    int32_t low, high;   /* 1 <= low <= high <= 1442 */
+    int32_t min_pixels;  /* >= 1 */
+} fdcm_edge_params;
+int fdcm_edge_labels_ex(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int64_t depth,
+                        const fdcm_edge_params* params, uint8_t* labels_out);
+int fdcm_featuremap_build_image_ex(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                                   const fdcm_edge_params* params, int64_t border, int64_t depth, float dt3_coeff, int distance,
+                                   fdcm_featuremap** out);
+int fdcm_featuremap_rebuild_image_ex(fdcm_featuremap* fm, const uint8_t* image, int64_t width, int64_t height,
+                                     int64_t row_stride, int on_device, const fdcm_edge_params* params, int64_t border);
 /* Test hook: stop the image build after stage 1, 2 or 3. */
 int fdcm_featuremap_build_image_staged(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
                                        int threshold, int64_t border, int64_t depth, float dt3_coeff, int distance,

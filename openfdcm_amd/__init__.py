@@ -189,10 +189,11 @@ def build_cpu_featuremap(scene, params=None, pool=None):
     return out
 
 
-def build_image_featuremap(image, params=None, threshold=60, border=0):
+def build_image_featuremap(image, params=None, threshold=60, border=0, low=None, smooth=0, min_pixels=1):
     """The DT3 feature map of a camera frame without a line extractor (extension; include/fdcm.h, "feature maps from
     images"): the seeds are the oriented edge pixels of `image`, a 2-D uint8 numpy array or CUDA torch tensor.  Feature size
-    (W + 2 border, H + 2 border), scene translation (border, border); params.padding plays no part.  Returns a Dt3Cpu
+    (W + 2 border, H + 2 border), scene translation (border, border); params.padding plays no part.  `threshold` is the high
+    threshold; low (hysteresis), smooth (0, 1, 2) and min_pixels (smallest component kept) are per call, like it.  Returns a Dt3Cpu
     that exhaustive_*, score_map, FeatureMap.evaluate and search (with the caller's scene lines) take as any other."""
     import ctypes as C
     params = params if params is not None else Dt3CpuParameters()
@@ -201,10 +202,11 @@ def build_image_featuremap(image, params=None, threshold=60, border=0):
     key = ("image", int(params.depth), float(params.dt3_coeff), int(params.distance), dev.value)
     fm = _featuremap_pool.take(key)
     if fm is None:
-        fm = DeviceFeatureMap.build_image(image, threshold, border=border, depth=key[1], coeff=key[2], distance=key[3])
+        fm = DeviceFeatureMap.build_image(image, threshold, border=border, depth=key[1], coeff=key[2], distance=key[3], low=low,
+                                          smooth=smooth, min_pixels=min_pixels)
     else:
         try:
-            fm.rebuild_image(image, threshold, border=border)
+            fm.rebuild_image(image, threshold, border=border, low=low, smooth=smooth, min_pixels=min_pixels)
         except Exception:
             fm.close()
             raise

@@ -55,6 +55,11 @@ class Rotations(C.Structure):
     _fields_ = [("cs", C.POINTER(C.c_float)), ("n", C.c_int32), ("pivots", C.POINTER(C.c_float))]
 
 
+class EdgeParams(C.Structure):
+    """fdcm_edge_params: smoothing (0, 1, 2), the low and high thresholds and the smallest component kept."""
+    _fields_ = [("smooth", C.c_int32), ("low", C.c_int32), ("high", C.c_int32), ("min_pixels", C.c_int32)]
+
+
 # every symbol include/fdcm.h declares: (name, restype, argtypes)
 _fp, _i64p, _vp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_void_p
 SYMBOLS = [
@@ -85,6 +90,11 @@ SYMBOLS = [
     ("fdcm_featuremap_rebuild_labels", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, C.c_int64]),
     ("fdcm_featuremap_build_image_staged", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64,
                                                      C.c_int64, C.c_float, C.c_int, C.c_int, C.POINTER(_vp)]),
+    ("fdcm_edge_labels_ex", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(EdgeParams), _vp]),
+    ("fdcm_featuremap_build_image_ex", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(EdgeParams), C.c_int64,
+                                                 C.c_int64, C.c_float, C.c_int, C.POINTER(_vp)]),
+    ("fdcm_featuremap_rebuild_image_ex", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(EdgeParams),
+                                                   C.c_int64]),
     ("fdcm_featuremap_minmax_translation", C.c_int, [_vp, _fp, C.c_int64, _fp, _fp]),
     ("fdcm_featuremap_minmax_translation_batch", C.c_int, [_vp, _fp, _i64p, C.c_int64, _fp, _fp]),
     ("fdcm_featuremap_evaluate", C.c_int, [_vp, _fp, _i64p, C.c_int64, _fp, _i64p, _fp]),

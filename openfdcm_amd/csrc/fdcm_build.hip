@@ -606,6 +606,7 @@ BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after) {
     if (L.empty) return L;
     if (plan.seeds.kind != SeedKind::lines && HW64 > 64) throw std::string("feature maps from images or labels are limited to 4096 x 4096");
     if (plan.seeds.kind == SeedKind::image) L.labels = plan.seeds.bytes();
+    if (plan.seeds.kind == SeedKind::image && !plan.seeds.edge_plain()) L.edge_parent = L.edge_roots = plan.seeds.bytes() * 4;
     const size_t ncols = (size_t)m * W, islices = (size_t)m * ivol_slice_floats(W, H);
     L.vol = islices * sizeof(float);  // the transforms, and later the integrated volume, interleaved (>= m W H floats)
     if (HW64 > 64) L.bitmap = ncols * HW64 * 8;        // (feature sizes above 4096 only: k_seeds + k_coldesc)
@@ -643,6 +644,7 @@ void reserve_build(fdcm_featuremap* fm, const BuildLayout& L) {
     BuildBuffers& b = fm->build;
     fm->vol.reserve(L.vol); b.bitmap.reserve(L.bitmap); fm->ivol.reserve(L.ivol);
     b.coldesc.reserve(L.coldesc); b.colmask.reserve(L.colmask); b.labels.reserve(L.labels);
+    b.edge_parent.reserve(L.edge_parent); b.edge_roots.reserve(L.edge_roots);
     const void *stack_before = b.stack.p, *offtab_before = b.offtab.p;
     b.stack.reserve(L.stack); b.offtab.reserve(L.offtab);
     if (b.stack.p != stack_before) fm->sweep.reset();  // a new scratch: no cost table, no steal counter
@@ -724,7 +726,11 @@ static void stage_pass1(fdcm_featuremap* fm, const BuildLayout& L, const PlanOnD
         const uint8_t* labels = P.pixels;
         fm->built.seeds_fused = src.kind == SeedKind::labels;
         if (src.kind == SeedKind::image) {
-            launch_edge_labels(st, P.pixels, src.width, src.height, P.pixel_stride, P.keys, m, src.threshold, fm->build.labels.as<uint8_t>());
+            if (src.edge_plain())
+                launch_edge_labels(st, P.pixels, src.width, src.height, P.pixel_stride, P.keys, m, src.edge.high, fm->build.labels.as<uint8_t>());
+            else
+                launch_edge_labels_ex(st, P.pixels, src.width, src.height, P.pixel_stride, P.keys, m, src.edge, fm->build.labels.as<uint8_t>(),
+                                      fm->build.edge_parent.as<int32_t>(), fm->build.edge_roots.as<uint32_t>());
             labels = fm->build.labels.as<uint8_t>();
             mark(fm, 1, fm->built.stage_events);
         }

@@ -141,15 +141,31 @@ int fdcm_featuremap_rebuild(fdcm_featuremap* fm, const float* scene_lines, int64
 
 // ------------------------------------------------------------------------------------------ feature maps from images
 // Everything an image / label build checks before it touches a device; fills the plan of the shape (no scene is made up).
+// An image's edge parameters: `threshold` alone (the entry points without _ex), or `ex`, the caller's fdcm_edge_params.
+struct EdgeArg {
+    int threshold = 0;
+    const fdcm_edge_params* ex = nullptr;
+    bool is_ex = false;
+    static EdgeArg plain(int t) { EdgeArg a; a.threshold = t; return a; }
+    static EdgeArg params(const fdcm_edge_params* p) { EdgeArg a; a.ex = p; a.is_ex = true; return a; }
+};
 static void pixel_plan(const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device, SeedKind kind,
-                       int threshold, int64_t border, int64_t depth, float coeff, BuildPlan& plan) {
+                       const EdgeArg& edge, int64_t border, int64_t depth, float coeff, BuildPlan& plan) {
     require(pixels != nullptr, kind == SeedKind::image ? "image is null" : "labels is null");
     require(width >= 1 && height >= 1, "width and height must be at least 1");
     require(border >= 0, "border must be >= 0");
     require(width + 2 * border <= 4096 && height + 2 * border <= 4096, "feature maps from images are limited to 4096 x 4096 (border included)");
     require(row_stride >= width, "row_stride must be >= width");
     require(on_device == 0 || on_device == 1, "on_device must be 0 or 1");
-    if (kind == SeedKind::image) require(threshold >= 1 && threshold <= 1442, "threshold must be in [1, 1442]");
+    fdcm_edge_params e = {0, edge.threshold, edge.threshold, 1};
+    if (kind == SeedKind::image && !edge.is_ex) require(edge.threshold >= 1 && edge.threshold <= 1442, "threshold must be in [1, 1442]");
+    if (kind == SeedKind::image && edge.is_ex) {
+        require(edge.ex != nullptr, "params is null");
+        e = *edge.ex;
+        require(e.smooth >= 0 && e.smooth <= 2, "params: smooth must be 0, 1 or 2");
+        require(e.low >= 1 && e.high <= 1442 && e.low <= e.high, "params: low and high must satisfy 1 <= low <= high <= 1442");
+        require(e.min_pixels >= 1, "params: min_pixels must be >= 1");
+    }
     require(depth >= 0, "depth must be >= 0");
     require(depth <= 255, "depth gives more than 255 orientation keys: a label is one byte");
     plan = BuildPlan{};
@@ -157,18 +173,18 @@ static void pixel_plan(const uint8_t* pixels, int64_t width, int64_t height, int
     plan.tx = plan.ty = (float)border;
     plan.seeds.kind = kind; plan.seeds.pixels = pixels; plan.seeds.on_device = on_device != 0;
     plan.seeds.width = (int)width; plan.seeds.height = (int)height; plan.seeds.row_stride = (int)row_stride;
-    plan.seeds.border = (int)border; plan.seeds.threshold = threshold;
+    plan.seeds.border = (int)border; plan.seeds.edge = e;
 }
 
 static int build_from_pixels(const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device, SeedKind kind,
-                             int threshold, int64_t border, int64_t depth, float coeff, int distance, int stop_after, fdcm_featuremap** out) {
+                             const EdgeArg& edge, int64_t border, int64_t depth, float coeff, int distance, int stop_after, fdcm_featuremap** out) {
     fdcm_featuremap* fm = nullptr;
     int rc = guarded([&] {
         require(out != nullptr, "out is null");
         require(distance >= FDCM_L2 && distance <= FDCM_L1, "unknown distance");
         require(stop_after >= 1 && stop_after <= 3, "stop_after must be 1..3");
         BuildPlan plan;
-        pixel_plan(pixels, width, height, row_stride, on_device, kind, threshold, border, depth, coeff, plan);
+        pixel_plan(pixels, width, height, row_stride, on_device, kind, edge, border, depth, coeff, plan);
         fm = new fdcm_featuremap();
         fm->device = g_device;
         fm->depth_param = depth; fm->coeff = coeff; fm->padding = 0.f; fm->distance = distance;
@@ -180,11 +196,11 @@ static int build_from_pixels(const uint8_t* pixels, int64_t width, int64_t heigh
 }
 
 static int rebuild_from_pixels(fdcm_featuremap* fm, const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device,
-                               SeedKind kind, int threshold, int64_t border) {
+                               SeedKind kind, const EdgeArg& edge, int64_t border) {
     return guarded([&] {
         require(fm != nullptr, "featuremap is null");
         BuildPlan plan;
-        pixel_plan(pixels, width, height, row_stride, on_device, kind, threshold, border, fm->depth_param, fm->coeff, plan);
+        pixel_plan(pixels, width, height, row_stride, on_device, kind, edge, border, fm->depth_param, fm->coeff, plan);
         run_build(fm, plan, 3);
     });
 }
@@ -195,34 +211,57 @@ int fdcm_edge_labels(const uint8_t* image, int64_t width, int64_t height, int64_
         require(labels_out != nullptr, "labels_out is null");
         require(depth >= 1, "depth must be >= 1");
         BuildPlan plan;
-        pixel_plan(image, width, height, row_stride, 0, SeedKind::image, threshold, 0, depth, 0.f, plan);
+        pixel_plan(image, width, height, row_stride, 0, SeedKind::image, EdgeArg::plain(threshold), 0, depth, 0.f, plan);
         edge_labels_host(g_device, image, (int)width, (int)height, (int)row_stride, depth, threshold, labels_out);
     });
 }
 
+int fdcm_edge_labels_ex(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int64_t depth,
+                        const fdcm_edge_params* params, uint8_t* labels_out) {
+    return guarded([&] {
+        require(labels_out != nullptr, "labels_out is null");
+        require(depth >= 1, "depth must be >= 1");
+        BuildPlan plan;
+        pixel_plan(image, width, height, row_stride, 0, SeedKind::image, EdgeArg::params(params), 0, depth, 0.f, plan);
+        edge_labels_host_ex(g_device, image, (int)width, (int)height, (int)row_stride, depth, plan.seeds.edge, labels_out);
+    });
+}
+
+int fdcm_featuremap_build_image_ex(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                                   const fdcm_edge_params* params, int64_t border, int64_t depth, float dt3_coeff, int distance,
+                                   fdcm_featuremap** out) {
+    return build_from_pixels(image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::params(params), border, depth, dt3_coeff,
+                             distance, 3, out);
+}
+
+int fdcm_featuremap_rebuild_image_ex(fdcm_featuremap* fm, const uint8_t* image, int64_t width, int64_t height, int64_t row_stride,
+                                     int on_device, const fdcm_edge_params* params, int64_t border) {
+    return rebuild_from_pixels(fm, image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::params(params), border);
+}
+
 int fdcm_featuremap_build_image(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device, int threshold,
                                 int64_t border, int64_t depth, float dt3_coeff, int distance, fdcm_featuremap** out) {
-    return build_from_pixels(image, width, height, row_stride, on_device, SeedKind::image, threshold, border, depth, dt3_coeff, distance, 3, out);
+    return build_from_pixels(image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::plain(threshold), border, depth, dt3_coeff, distance, 3, out);
 }
 
 int fdcm_featuremap_build_image_staged(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device, int threshold,
                                        int64_t border, int64_t depth, float dt3_coeff, int distance, int stop_after, fdcm_featuremap** out) {
-    return build_from_pixels(image, width, height, row_stride, on_device, SeedKind::image, threshold, border, depth, dt3_coeff, distance,
+    return build_from_pixels(image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::plain(threshold), border, depth, dt3_coeff, distance,
                              stop_after, out);
 }
 
 int fdcm_featuremap_rebuild_image(fdcm_featuremap* fm, const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
                                   int threshold, int64_t border) {
-    return rebuild_from_pixels(fm, image, width, height, row_stride, on_device, SeedKind::image, threshold, border);
+    return rebuild_from_pixels(fm, image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::plain(threshold), border);
 }
 
 int fdcm_featuremap_build_labels(const uint8_t* labels, int64_t width, int64_t height, int on_device, int64_t border, int64_t depth,
                                  float dt3_coeff, int distance, fdcm_featuremap** out) {
-    return build_from_pixels(labels, width, height, width, on_device, SeedKind::labels, 0, border, depth, dt3_coeff, distance, 3, out);
+    return build_from_pixels(labels, width, height, width, on_device, SeedKind::labels, EdgeArg(), border, depth, dt3_coeff, distance, 3, out);
 }
 
 int fdcm_featuremap_rebuild_labels(fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device, int64_t border) {
-    return rebuild_from_pixels(fm, labels, width, height, width, on_device, SeedKind::labels, 0, border);
+    return rebuild_from_pixels(fm, labels, width, height, width, on_device, SeedKind::labels, EdgeArg(), border);
 }
 
 int fdcm_featuremap_free(fdcm_featuremap* fm) {

@@ -5,7 +5,11 @@
 //                      binned by closest_orientation over the build's keys               read W H, write W H
 //   k_coldesc_labels   k_coldesc_tile's sibling: the bitmap tile in LDS comes from the label image instead of RasterLines, the
 //                      descriptor step (coldesc_from_bits) is shared                     read m W H (from L2), write ~V/16
-// Both index with the caller's sizes only: every load is of a pixel inside [0, width) x [0, height), every store inside the label
+//   k_edge_candidates<S>, k_edge_union, k_edge_roots, k_edge_resolve
+//                      the same label image with smoothing, hysteresis and a minimum component size: candidates (thinned,
+//                      m2 >= low^2) with their provisional labels, their 8-connected components by union-find on one parent
+//                      per pixel, strong flag and size per root, and the candidates of the other roots back to 255
+// All index with the caller's sizes only: every load is of a pixel inside [0, width) x [0, height), every store inside the label
 // image or the descriptors of the block's own columns.
 #include <algorithm>
 
@@ -111,6 +115,193 @@ void launch_edge_labels(hipStream_t st, const uint8_t* image, int width, int hei
     hipLaunchKernelGGL(k_edge_labels, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, threshold * threshold, labels);
 }
 
+// ------------------------------------------------------------------------------------------ image -> labels, with hysteresis
+// (include/fdcm.h, "edges with smoothing, hysteresis and a minimum chain length")
+// The tile of k_edge_labels with `halo` pixels around it, from the image into LDS: rows as aligned dwords where all four bytes
+// are the row's, single bytes at the ragged ends, and the columns and rows outside the image replicated.
+template <int PH, int PW, int STR>
+__device__ __forceinline__ void load_clamped_tile(unsigned char (*px)[STR], const uint8_t* __restrict__ image, int W, int H, int stride,
+                                                  int xa, int ya, int tid) {
+    constexpr int kRowDwords = (PW + 3 + 3) / 4;
+    const int lo = max(xa, 0), hi = min(xa + PW, W);  // the held columns inside the image: [lo, hi), never empty
+    for (int idx = tid; idx < PH * kRowDwords; idx += 256) {
+        const int r = idx / kRowDwords, j = idx - r * kRowDwords;
+        const int y = min(max(ya + r, 0), H - 1);
+        const uint8_t* rp = image + (size_t)y * stride;
+        const int mis = (int)((uintptr_t)(rp + lo) & 3u);
+        const int xf = lo - mis + 4 * j;
+        if (xf >= hi) continue;
+        if (xf >= lo && xf + 4 <= hi) {
+            const unsigned v = *reinterpret_cast<const unsigned*>(rp + xf);
+            unsigned char* dst = &px[r][xf - xa];
+            dst[0] = (unsigned char)v; dst[1] = (unsigned char)(v >> 8); dst[2] = (unsigned char)(v >> 16); dst[3] = (unsigned char)(v >> 24);
+        } else {
+            for (int b = 0; b < 4; ++b) {
+                const int x = xf + b;
+                if (x >= lo && x < hi) px[r][x - xa] = rp[x];
+            }
+        }
+    }
+    for (int idx = tid; idx < PH * PW; idx += 256) {
+        const int r = idx / PW, c = idx - r * PW, x = xa + c;
+        if (x >= 0 && x < W) continue;
+        const int y = min(max(ya + r, 0), H - 1);
+        px[r][c] = image[(size_t)y * stride + (x < 0 ? 0 : W - 1)];
+    }
+}
+
+static constexpr int kNoParent = -1;            // parent of a pixel that is no candidate
+static constexpr unsigned kStrongBit = 0x80000000u;  // roots[]: bit 31 strong, bits 0-30 the component's candidates
+
+// k_edge_labels with S in place of I and low^2 for the threshold; per pixel the provisional label (255: no candidate), the
+// parent (itself for a candidate) and the root word (the pixel's own strong flag, count 0).
+template <int S>
+__global__ void __launch_bounds__(256) k_edge_candidates(const uint8_t* __restrict__ image, int W, int H, int stride, const float* __restrict__ keys,
+                                                         int m, int low2, int high2, uint8_t* __restrict__ labels, int32_t* __restrict__ parent,
+                                                         uint32_t* __restrict__ roots) {
+    constexpr int HALO = kEdgeHalo + S, RH = kEdgeTH + 2 * HALO, RW = kEdgeTW + 2 * HALO;
+    __shared__ unsigned char raw[S ? RH : 1][S ? RW + 4 : 4];  // the image around the tile (smoothing only)
+    __shared__ unsigned char px[kEdgePH][kEdgePW + 4];         // S around the tile, as k_edge_labels holds I
+    __shared__ int sm2[kEdgeMH][kEdgeMW];
+    __shared__ float skeys[256];
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * kEdgeTW, y0 = blockIdx.y * kEdgeTH;
+    if (tid < m) skeys[tid] = keys[tid];
+    if constexpr (S == 0) {
+        load_clamped_tile<kEdgePH, kEdgePW>(px, image, W, H, stride, x0 - kEdgeHalo, y0 - kEdgeHalo, tid);
+    } else {
+        load_clamped_tile<RH, RW>(raw, image, W, H, stride, x0 - HALO, y0 - HALO, tid);
+        __syncthreads();
+        // S at the clamped coordinate of every held pixel: its taps are inside `raw` (the clamped coordinate is at most
+        // kEdgeHalo outside the tile), and `raw` holds I clamped
+        for (int idx = tid; idx < kEdgePH * kEdgePW; idx += 256) {
+            const int r = idx / kEdgePW, c = idx - r * kEdgePW;
+            const int cx = min(max(x0 - kEdgeHalo + c, 0), W - 1) - (x0 - HALO), cy = min(max(y0 - kEdgeHalo + r, 0), H - 1) - (y0 - HALO);
+            int sum = 0;
+#pragma unroll
+            for (int j = -S; j <= S; ++j) {
+                int row = 0;
+#pragma unroll
+                for (int i = -S; i <= S; ++i) {
+                    const int w = S == 1 ? 2 - abs(i) : (i == 0 ? 6 : (abs(i) == 1 ? 4 : 1));
+                    row += w * raw[cy + j][cx + i];
+                }
+                sum += (S == 1 ? 2 - abs(j) : (j == 0 ? 6 : (abs(j) == 1 ? 4 : 1))) * row;
+            }
+            px[r][c] = (unsigned char)(S == 1 ? (sum + 8) >> 4 : (sum + 128) >> 8);
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < kEdgeMH * kEdgeMW; idx += 256) {
+        const int rr = idx / kEdgeMW, cc = idx - rr * kEdgeMW;
+        const int x = x0 - 1 + cc, y = y0 - 1 + rr;
+        int v = 0;
+        if (x >= 0 && x < W && y >= 0 && y < H) {
+            int gx, gy;
+            sobel_at(px, rr + 1, cc + 1, gx, gy);
+            v = gx * gx + gy * gy;
+        }
+        sm2[rr][cc] = v;
+    }
+    __syncthreads();
+    const int lx = tid & 63;
+#pragma unroll
+    for (int i = 0; i < kEdgeTH / 4; ++i) {
+        const int ly = (tid >> 6) + 4 * i;
+        const int x = x0 + lx, y = y0 + ly;
+        if (x >= W || y >= H) continue;
+        int gx, gy;
+        sobel_at(px, ly + kEdgeHalo, lx + kEdgeHalo, gx, gy);
+        const int m2 = sm2[ly + 1][lx + 1];
+        const int a = abs(gx), b = abs(gy);
+        int dx, dy;
+        if (29 * b < 12 * a) { dx = 1; dy = 0; }
+        else if (29 * a < 12 * b) { dx = 0; dy = 1; }
+        else { dx = 1; dy = ((gx >= 0) == (gy >= 0)) ? 1 : -1; }
+        const int before = sm2[ly + 1 - dy][lx + 1 - dx], after = sm2[ly + 1 + dy][lx + 1 + dx];
+        const bool cand = m2 >= low2 && m2 > before && m2 >= after;
+        unsigned char label = 255;
+        if (cand) {
+            const float tdx = (float)(-gy), tdy = (float)gx;
+            label = (unsigned char)closest_orientation(skeys, m, atanf_glibc(tdy / tdx));
+        }
+        const int p = y * W + x;  // < 2^24
+        labels[p] = label;
+        parent[p] = cand ? p : kNoParent;
+        roots[p] = cand && m2 >= high2 ? kStrongBit : 0u;
+    }
+}
+
+// Union-find on `parent` (a candidate's parent is a candidate of its component with a smaller or the same index; a root is its
+// own).  Other workgroups link roots meanwhile, so every read is an atomic load: a stale parent is still an ancestor.
+__device__ __forceinline__ int uf_load(const int32_t* parent, int p) { return __hip_atomic_load(parent + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int uf_find(const int32_t* parent, int p) {
+    for (int q = uf_load(parent, p); q != p; q = uf_load(parent, p)) p = q;
+    return p;
+}
+// Links the larger root under the smaller.  When the larger one stopped being a root meanwhile, atomicMin has either changed
+// nothing or replaced its parent, which is then merged in its turn: no link is lost, and every step lowers a parent.
+__device__ __forceinline__ void uf_union(int32_t* parent, int a, int b) {
+    for (;;) {
+        a = uf_find(parent, a); b = uf_find(parent, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }  // a > b
+        const int old = atomicMin(&parent[a], b);
+        if (old == a) return;
+        a = old;
+    }
+}
+// a candidate with each candidate among its four neighbours of the rows above and the column before: every 8-neighbour pair once
+__global__ void __launch_bounds__(256) k_edge_union(int W, int H, int32_t* parent) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= W * H || uf_load(parent, p) == kNoParent) return;
+    const int y = p / W, x = p - y * W;
+    if (x > 0 && uf_load(parent, p - 1) != kNoParent) uf_union(parent, p, p - 1);
+    if (y > 0) {
+        const int q = p - W;
+        if (x > 0 && uf_load(parent, q - 1) != kNoParent) uf_union(parent, p, q - 1);
+        if (uf_load(parent, q) != kNoParent) uf_union(parent, p, q);
+        if (x + 1 < W && uf_load(parent, q + 1) != kNoParent) uf_union(parent, p, q + 1);
+    }
+}
+// flatten, and per root the candidates' count and strong flag.  Bit 31 of roots[p] is p's own flag until this kernel adds to a
+// root's word; a root that reads its component's flag for its own ORs it into itself.
+__global__ void __launch_bounds__(256) k_edge_roots(int n, int32_t* parent, uint32_t* roots) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n || uf_load(parent, p) == kNoParent) return;
+    const int r = uf_find(parent, p);
+    if (r != p) __hip_atomic_store(parent + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned own = __hip_atomic_load(roots + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kStrongBit;
+    atomicAdd(&roots[r], 1u);
+    if (own) atomicOr(&roots[r], kStrongBit);
+}
+// the candidates of a component without a strong pixel or with fewer than min_pixels: no edge
+__global__ void __launch_bounds__(256) k_edge_resolve(int n, const int32_t* __restrict__ parent, const uint32_t* __restrict__ roots, int min_pixels,
+                                                      uint8_t* __restrict__ labels) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int r = parent[p];
+    if (r == kNoParent) return;
+    const unsigned w = roots[r];
+    if (!(w & kStrongBit) || (int)(w & ~kStrongBit) < min_pixels) labels[p] = 255;
+}
+
+void launch_edge_labels_ex(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
+                           const fdcm_edge_params& e, uint8_t* labels, int32_t* parent, uint32_t* roots) {
+    const dim3 grid((unsigned)((width + kEdgeTW - 1) / kEdgeTW), (unsigned)((height + kEdgeTH - 1) / kEdgeTH));
+    const int low2 = e.low * e.low, high2 = e.high * e.high, n = width * height;
+    switch (e.smooth) {
+    case 0: hipLaunchKernelGGL(k_edge_candidates<0>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, parent, roots); break;
+    case 1: hipLaunchKernelGGL(k_edge_candidates<1>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, parent, roots); break;
+    default: hipLaunchKernelGGL(k_edge_candidates<2>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, parent, roots); break;
+    }
+    // launch counts and grids depend on the size alone: the components are resolved without a look at them from the host
+    const dim3 flat((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(k_edge_union, flat, dim3(256), 0, st, width, height, parent);
+    hipLaunchKernelGGL(k_edge_roots, flat, dim3(256), 0, st, n, parent, roots);
+    hipLaunchKernelGGL(k_edge_resolve, flat, dim3(256), 0, st, n, (const int32_t*)parent, (const uint32_t*)roots, e.min_pixels, labels);
+}
+
 // ------------------------------------------------------------------------------------------ labels -> column descriptors
 // k_coldesc_tile (fdcm_build.hip) with another seed source: bit (y + border) of column (x + border) of slice k is set when
 // labels[y][x] == k.  A thread builds whole words (64 rows of one column; neighbouring threads take neighbouring columns, so a
@@ -174,6 +365,28 @@ void edge_labels_host(int device, const uint8_t* image, int width, int height, i
     FDCM_HIP(hipMemcpy2D(s.image.p, (size_t)width, image, (size_t)row_stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
     FDCM_HIP(hipMemcpy(s.keys.p, keys.data(), keys.size() * sizeof(float), hipMemcpyHostToDevice));
     launch_edge_labels(nullptr, s.image.as<uint8_t>(), width, height, width, s.keys.as<float>(), (int)keys.size(), threshold, s.labels.as<uint8_t>());
+    FDCM_HIP(hipGetLastError());
+    FDCM_HIP(hipDeviceSynchronize());
+    FDCM_HIP(hipMemcpy(labels_out, s.labels.p, n, hipMemcpyDeviceToHost));
+}
+
+
+void edge_labels_host_ex(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth,
+                         const fdcm_edge_params& e, uint8_t* labels_out) {
+    std::vector<float> keys;
+    plan_keys(depth, keys);
+    FDCM_HIP(hipSetDevice(device));
+    struct Scratch {
+        DevBuf image, labels, keys, parent, roots;
+        ~Scratch() { for (DevBuf* b : {&image, &labels, &keys, &parent, &roots}) b->release(); }
+    } s;
+    const size_t n = (size_t)width * height;
+    s.image.reserve(n); s.labels.reserve(n); s.keys.reserve(std::max<size_t>(1, keys.size()) * sizeof(float));
+    s.parent.reserve(n * 4); s.roots.reserve(n * 4);
+    FDCM_HIP(hipMemcpy2D(s.image.p, (size_t)width, image, (size_t)row_stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
+    FDCM_HIP(hipMemcpy(s.keys.p, keys.data(), keys.size() * sizeof(float), hipMemcpyHostToDevice));
+    launch_edge_labels_ex(nullptr, s.image.as<uint8_t>(), width, height, width, s.keys.as<float>(), (int)keys.size(), e, s.labels.as<uint8_t>(),
+                          s.parent.as<int32_t>(), s.roots.as<uint32_t>());
     FDCM_HIP(hipGetLastError());
     FDCM_HIP(hipDeviceSynchronize());
     FDCM_HIP(hipMemcpy(labels_out, s.labels.p, n, hipMemcpyDeviceToHost));

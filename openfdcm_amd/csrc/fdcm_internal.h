@@ -92,14 +92,18 @@ struct LineBox { int32_t slice; float xlo, xhi, ylo, yhi; };
 
 // Where the seeds of a build come from: the plan's clipped scene lines, a label image (one byte per pixel, row-major, value k
 // < m: a seed of slice k, anything else: none), or a grey image whose oriented edge pixels become the labels first
-// (k_edge_labels).  Pixel (x, y) seeds map pixel (x + border, y + border).  The pixels are host memory, which travels in the
-// plan's blob with rows packed, or memory of the handle's device, which is read in place while the build runs.
+// (k_edge_labels; `edge` holds the detector's parameters, and unless they are k_edge_labels' own -- edge_plain -- the
+// candidate kernel and the component kernels make the labels).  Pixel (x, y) seeds map pixel (x + border, y + border).  The
+// pixels are host memory, which travels in the plan's blob with rows packed, or memory of the handle's device, which is read
+// in place while the build runs.
 enum class SeedKind { lines, labels, image };
 struct SeedSource {
     SeedKind kind = SeedKind::lines;
     const uint8_t* pixels = nullptr;
     bool on_device = false;
-    int width = 0, height = 0, row_stride = 0, border = 0, threshold = 0;
+    int width = 0, height = 0, row_stride = 0, border = 0;
+    fdcm_edge_params edge = {0, 0, 0, 1};  // (image only; one threshold t: {0, t, t, 1})
+    bool edge_plain() const { return edge.smooth == 0 && edge.low == edge.high && edge.min_pixels == 1; }
     size_t bytes() const { return kind == SeedKind::lines ? 0 : (size_t)width * (size_t)height; }
 };
 
@@ -124,6 +128,7 @@ struct BuildLayout {
     long nchunks = 0;       // (slice, 64-row chunk) pairs
     size_t vol = 0, ivol = 0, bitmap = 0, coldesc = 0, colmask = 0, offtab = 0, stack = 0;
     size_t labels = 0;      // the label image an image build makes of its pixels
+    size_t edge_parent = 0, edge_roots = 0;  // image builds with hysteresis: a parent and a (strong flag | count) word per pixel
     size_t o_ent = 0, o_own = 0, o_ord = 0, o_cost = 0, o_steals = 0;  // inside `stack` (balanced sweep)
     // plan blob: RasterLine[] | PropStep[] | IntegralDesc[] | keys[] | slice_first[] | host pixels of the seed source | per-chunk proxy cost[]
     size_t off_raster = 0, off_prop = 0, off_integral = 0, off_keys = 0, off_slice = 0, off_pixels = 0, off_cost = 0, plan = 0;
@@ -190,11 +195,12 @@ struct BuildBuffers {  // what a build needs besides the volume, sized by BuildL
     DevBuf coldesc;  // m*ceil(H/64)*W column-chunk descriptors (16 B)
     DevBuf colmask;  // m*ceil(W/64) words: the seeded columns of every slice (k_coldesc_tile, for the L2 sweep)
     DevBuf labels;   // image builds: the label image k_edge_labels writes and k_coldesc_labels reads
+    DevBuf edge_parent, edge_roots;  // image builds with hysteresis: the union-find of the candidates (launch_edge_labels_ex)
     DevBuf offtab;   // per slice: one word per group of 4 columns for the shallow sweeps of the line integral (k_groups)
     DevBuf stack;    // the sweep's scratch: the balanced sweep's stack and owner entries (slot-major per chunk), launch order,
                      // per-chunk costs and steal counter; or the literal pass's scratch; or the L1 pass's minima / carries
     DevBuf plan; PinnedBuf stage;  // the last build's plan (BuildLayout's blob) or the keys of an adopted volume; its host staging
-    void release() { for (DevBuf* b : {&bitmap, &coldesc, &colmask, &labels, &offtab, &stack, &plan}) b->release(); stage.release(); }
+    void release() { for (DevBuf* b : {&bitmap, &coldesc, &colmask, &labels, &edge_parent, &edge_roots, &offtab, &stack, &plan}) b->release(); stage.release(); }
 };
 struct SearchBuffers {
     DevBuf scene;     // scene lines + sorted lengths + sorted idx + candidate offsets
@@ -276,10 +282,16 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after);
 // (k_coldesc_labels); `cost`, where given, receives the sweep's per-chunk proxy (zeroed by the caller)
 void launch_edge_labels(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
                         int threshold, uint8_t* labels);
+// the same by `e` (include/fdcm.h, "edges with smoothing, hysteresis and a minimum chain length"): candidates, their components
+// by union-find in `parent`, strong flag and size per root in `roots` (width * height words each), all queued on st
+void launch_edge_labels_ex(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
+                           const fdcm_edge_params& e, uint8_t* labels, int32_t* parent, uint32_t* roots);
 void launch_coldesc_labels(hipStream_t st, const uint8_t* labels, int width, int height, int border, void* desc, int W, int H,
                            int HW64, int m, unsigned* colmask, int* cost);
 void edge_labels_host(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth, int threshold,
                       uint8_t* labels_out);
+void edge_labels_host_ex(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth,
+                         const fdcm_edge_params& e, uint8_t* labels_out);
 // Waits for a queued build (if any) and fills fm->last_build.  run_build only queues the kernels: the search
 // that follows is ordered behind them on the same stream and its host-side preparation runs meanwhile.
 void finish_build(fdcm_featuremap* fm);

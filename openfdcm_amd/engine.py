@@ -65,6 +65,14 @@ def _pixels(a, what):
     return C.c_void_p(a.data_ptr()), a.shape[1], a.shape[0], stride, 1, a
 
 
+def _edge_params(threshold, low, smooth, min_pixels):
+    """None when the options are the defaults (the entry points with `threshold` alone take the call), else the
+    fdcm_edge_params of the _ex entry points: `threshold` is the high threshold, low=None means low = threshold."""
+    if low is None and int(smooth) == 0 and int(min_pixels) == 1:
+        return None
+    return capi.EdgeParams(int(smooth), int(threshold if low is None else low), int(threshold), int(min_pixels))
+
+
 class DeviceFeatureMap:
     """Owns an fdcm_featuremap handle (DT3 volume resident in HBM)."""
 
@@ -118,12 +126,20 @@ class DeviceFeatureMap:
     # ---- feature maps from images (include/fdcm.h, "feature maps from images"): image / labels are 2-D uint8, (H, W), a
     #      numpy array or a CUDA torch tensor (read in place; kept alive here until the next build)
     @classmethod
-    def build_image(cls, image, threshold, border=0, depth=30, coeff=5.0, distance=capi.L2, stop_after=3):
+    def build_image(cls, image, threshold, border=0, depth=30, coeff=5.0, distance=capi.L2, stop_after=3, low=None, smooth=0,
+                    min_pixels=1):
         """The DT3 volume whose seeds are the oriented edge pixels of `image`: size (W + 2 border, H + 2 border), scene
-        translation (border, border)."""
+        translation (border, border).  low / smooth / min_pixels: hysteresis below `threshold`, smoothing and the smallest
+        component kept (include/fdcm.h, fdcm_edge_params)."""
         p, w, h, stride, dev, keep = _pixels(image, "image")
         out = C.c_void_p()
-        if stop_after == 3:
+        ex = _edge_params(threshold, low, smooth, min_pixels)
+        if ex is not None:
+            if stop_after != 3:
+                raise ValueError("build_image: stop_after != 3 cannot be combined with low, smooth or min_pixels")
+            rc = capi.lib().fdcm_featuremap_build_image_ex(p, w, h, stride, dev, C.byref(ex), int(border), int(depth), float(coeff),
+                                                           int(distance), C.byref(out))
+        elif stop_after == 3:
             rc = capi.lib().fdcm_featuremap_build_image(p, w, h, stride, dev, int(threshold), int(border), int(depth),
                                                         float(coeff), int(distance), C.byref(out))
         else:
@@ -148,9 +164,13 @@ class DeviceFeatureMap:
         fm._seed_pixels = keep
         return fm
 
-    def rebuild_image(self, image, threshold, border=0):
+    def rebuild_image(self, image, threshold, border=0, low=None, smooth=0, min_pixels=1):
         p, w, h, stride, dev, keep = _pixels(image, "image")
-        capi.check(capi.lib().fdcm_featuremap_rebuild_image(self._h, p, w, h, stride, dev, int(threshold), int(border)))
+        ex = _edge_params(threshold, low, smooth, min_pixels)
+        if ex is not None:
+            capi.check(capi.lib().fdcm_featuremap_rebuild_image_ex(self._h, p, w, h, stride, dev, C.byref(ex), int(border)))
+        else:
+            capi.check(capi.lib().fdcm_featuremap_rebuild_image(self._h, p, w, h, stride, dev, int(threshold), int(border)))
         self._seed_pixels = keep
         self.refresh()
 
@@ -354,15 +374,19 @@ class DeviceTemplates:
             pass
 
 
-def edge_labels(image, depth=30, threshold=60):
+def edge_labels(image, depth=30, threshold=60, low=None, smooth=0, min_pixels=1):
     """The label image of a 2-D uint8 array (include/fdcm.h, "feature maps from images"), computed on the GPU: (H, W) uint8,
-    the orientation slice of every edge pixel and 255 elsewhere."""
+    the orientation slice of every edge pixel and 255 elsewhere.  low / smooth / min_pixels as DeviceFeatureMap.build_image's."""
     a = np.asarray(image)
     if a.ndim != 2 or a.dtype != np.uint8:
         raise ValueError(f"image must be a 2-D uint8 array, got {a.dtype} with shape {a.shape}")
     p, w, h, stride, _, keep = _pixels(a, "image")
     out = np.empty((h, w), dtype=np.uint8)
-    capi.check(capi.lib().fdcm_edge_labels(p, w, h, stride, int(depth), int(threshold), C.c_void_p(out.ctypes.data)))
+    ex = _edge_params(threshold, low, smooth, min_pixels)
+    if ex is not None:
+        capi.check(capi.lib().fdcm_edge_labels_ex(p, w, h, stride, int(depth), C.byref(ex), C.c_void_p(out.ctypes.data)))
+    else:
+        capi.check(capi.lib().fdcm_edge_labels(p, w, h, stride, int(depth), int(threshold), C.c_void_p(out.ctypes.data)))
     return out
 
 
