@@ -440,6 +440,53 @@ int fdcm_search_exhaustive_rotations(const fdcm_featuremap* fm, const fdcm_templ
 int fdcm_score_map_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
                              const fdcm_grid* grid, float* out_host);
 
+/* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
+ *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as
+ *      fdcm_edge_labels makes it (m = the distinct keys of `depth`, a byte < m an edge pixel of that label, labels circular)
+ *      to the segments of its straight runs, on the device.
+ * With w = bucket and h = w / 2, an edge pixel of label l has bucket l / w in partition A and ((l + h) mod m) / w in
+ * partition B.  Per partition a component is a maximal 8-connected set of edge pixels of equal bucket; n(C) is its pixel
+ * count and its root the smallest index y * width + x among its pixels.  Pixel p votes A when n(A(p)) >= n(B(p)), else B;
+ * votes(C) counts the pixels of C that voted for C's partition.  C is kept when 2 votes(C) > n(C),
+ * min_pixels <= n(C) <= 65535 and its length is at least min_length.
+ * The fit is over all pixels of C, exact in int64: Sx, Sy, Sxx, Syy, Sxy over absolute pixel coordinates,
+ * Dxx = n Sxx - Sx^2, Dyy = n Syy - Sy^2, Dxy = n Sxy - Sx Sy; C is x-major when Dxx >= Dyy.  x-major: x0 = min x,
+ * x1 = max x, s = f64(Dxy) / f64(Dxx), xb = f64(Sx) / f64(n), yb = f64(Sy) / f64(n), Y(x) = yb + s * (f64(x) - xb), every
+ * operation one unfused IEEE float64 operation; the segment is (f32(x0), f32(Y(x0)), f32(x1), f32(Y(x1))) and the length
+ * x1 - x0 + 1.  y-major: the same with x and y exchanged and s = f64(Dxy) / f64(Dyy): (f32(X(y0)), f32(y0), f32(X(y1)),
+ * f32(y1)), length y1 - y0 + 1.
+ * Output: the kept components' segments, 4 floats each (x1 y1 x2 y2, the LineArray record), in ascending
+ * 2 * root + partition (A = 0, B = 1).  Coordinates are image pixels: scene coordinates of a feature map built from the
+ * same frame, and what fdcm_templates_create takes.  The result is a function of the label image alone.  With bucket = 1
+ * the partitions coincide and the result is the same-label components.
+ * Both calls block, run on the current device and need no handle.  *lines is released with fdcm_lines_free; when nothing is
+ * kept it is NULL, *n_lines is 0 and the call returns FDCM_OK.  1 <= width, height <= 4096; depth >= 1 with at most 255
+ * keys; on_device: the pixels are host memory (0) or memory of the current device (1; labels without gaps between rows).
+ * fdcm_lines_from_image is fdcm_edge_labels_ex followed by fdcm_lines_from_labels without the label image leaving the
+ * device; edge = {0, t, t, 1} is the plain threshold t. ---- */
+typedef struct fdcm_line_params {
+    int32_t bucket;      /* labels per orientation bucket, 1 .. m */
+    int32_t min_pixels;  /* 2 .. 65535 */
+    int32_t min_length;  /* 1 .. 4096, pixels along the major axis */
+} fdcm_line_params;
+int fdcm_lines_from_labels(const uint8_t* labels, int64_t width, int64_t height, int on_device, int64_t depth,
+                           const fdcm_line_params* params, float** lines, int64_t* n_lines);
+int fdcm_lines_from_image(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                          int64_t depth, const fdcm_edge_params* edge, const fdcm_line_params* params,
+                          float** lines, int64_t* n_lines);
+/* Diagnostic, not part of the extraction: device times of the calling thread's last fdcm_lines_from_* call in milliseconds,
+ * from events the call records around its stages (eleven events per call, whether or not this is read).  Each figure is the
+ * time of that stage's kernels alone: the edge kernels (0 for labels), the union-find inside tiles, across tile borders,
+ * flatten + numbering of the roots, sums, votes, the keep rule with its scan, the fit.  The host work between stages -- the
+ * two counts read back, the buffers sized by them and their clearing -- is in none of them; total_ms spans the call's device
+ * work from its first kernel to its last with those gaps.  A stage the call did not reach (nothing to keep) and a time that
+ * could not be read are 0. */
+typedef struct fdcm_lines_timing {
+    float edges_ms, tiles_ms, borders_ms, number_ms, sums_ms, votes_ms, keep_ms, fit_ms, total_ms;
+    int64_t n_lines;
+} fdcm_lines_timing;
+int fdcm_lines_last_timing(fdcm_lines_timing* out);
+
 /* ---- the reference's line files (.lines / .scene / .tmpl): read / write of core/serialization.h:99-132 (Python: openfdcm.read
  *      / openfdcm.write, python/src/core.cpp:41-42).  Host only.  fdcm_lines_read hands out n lines as 4 floats each
  *      (x1 y1 x2 y2 = the 4 x N column-major LineArray), to be released with fdcm_lines_free; a missing file, a file that is

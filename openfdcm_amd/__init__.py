@@ -12,7 +12,7 @@ import numpy as _np
 
 from . import _capi
 from .matchlist import Match, MatchList, records_of  # noqa: F401
-from .engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, ShardedEngine, edge_labels, search_raw, topk  # noqa: F401  (extensions)
+from .engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, ShardedEngine, edge_labels, lines_from_image, lines_from_labels, search_raw, topk  # noqa: F401  (extensions)
 
 __version__ = "0.10.0"  # API level of the reference this mirrors (openfdcm.cpp:43)
 

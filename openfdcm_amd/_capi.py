@@ -60,6 +60,17 @@ class EdgeParams(C.Structure):
     _fields_ = [("smooth", C.c_int32), ("low", C.c_int32), ("high", C.c_int32), ("min_pixels", C.c_int32)]
 
 
+class LineParams(C.Structure):
+    """fdcm_line_params: labels per orientation bucket, the fewest pixels and the shortest extent of a kept component."""
+    _fields_ = [("bucket", C.c_int32), ("min_pixels", C.c_int32), ("min_length", C.c_int32)]
+
+
+class LinesTiming(C.Structure):
+    """fdcm_lines_timing: device milliseconds per stage of the thread's last fdcm_lines_from_* call."""
+    _fields_ = [(n, C.c_float) for n in ("edges_ms", "tiles_ms", "borders_ms", "number_ms", "sums_ms", "votes_ms", "keep_ms",
+                                         "fit_ms", "total_ms")] + [("n_lines", C.c_int64)]
+
+
 # every symbol include/fdcm.h declares: (name, restype, argtypes)
 _fp, _i64p, _vp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_void_p
 SYMBOLS = [
@@ -149,6 +160,11 @@ SYMBOLS = [
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),
     ("fdcm_lines_free", None, [C.POINTER(C.c_float)]),
+    ("fdcm_lines_from_labels", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(LineParams),
+                                         C.POINTER(C.POINTER(C.c_float)), _i64p]),
+    ("fdcm_lines_from_image", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(EdgeParams),
+                                        C.POINTER(LineParams), C.POINTER(C.POINTER(C.c_float)), _i64p]),
+    ("fdcm_lines_last_timing", C.c_int, [C.POINTER(LinesTiming)]),
     ("fdcm_selftest_atanf", C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint64]),
     ("fdcm_orientation_bins_mode", C.c_int, []),
     ("fdcm_selftest_sweep_ranges", C.c_int, [C.c_int]),

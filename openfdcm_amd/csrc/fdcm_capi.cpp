@@ -227,6 +227,47 @@ int fdcm_edge_labels_ex(const uint8_t* image, int64_t width, int64_t height, int
     });
 }
 
+// ------------------------------------------------------------------------------------------ line segments from images
+static void check_line_params(const fdcm_line_params* lp, int64_t m, float** lines, int64_t* n_lines) {
+    require(lp != nullptr, "line params is null");
+    require(lines != nullptr, "lines is null");
+    require(n_lines != nullptr, "n_lines is null");
+    require(lp->bucket >= 1 && lp->bucket <= m, "line params: bucket must be in [1, the number of orientation keys]");
+    require(lp->min_pixels >= 2 && lp->min_pixels <= 65535, "line params: min_pixels must be in [2, 65535]");
+    require(lp->min_length >= 1 && lp->min_length <= 4096, "line params: min_length must be in [1, 4096]");
+}
+
+int fdcm_lines_from_labels(const uint8_t* labels, int64_t width, int64_t height, int on_device, int64_t depth,
+                           const fdcm_line_params* params, float** lines, int64_t* n_lines) {
+    return guarded([&] {
+        require(depth >= 1, "depth must be >= 1");
+        BuildPlan plan;
+        pixel_plan(labels, width, height, width, on_device, SeedKind::labels, EdgeArg(), 0, depth, 0.f, plan);
+        check_line_params(params, plan.m, lines, n_lines);
+        lines_from_labels_host(g_device, labels, (int)width, (int)height, on_device != 0, (int)plan.m, *params, lines, n_lines);
+    });
+}
+
+int fdcm_lines_from_image(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                          int64_t depth, const fdcm_edge_params* edge, const fdcm_line_params* params,
+                          float** lines, int64_t* n_lines) {
+    return guarded([&] {
+        require(depth >= 1, "depth must be >= 1");
+        BuildPlan plan;
+        pixel_plan(image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::params(edge), 0, depth, 0.f, plan);
+        check_line_params(params, plan.m, lines, n_lines);
+        lines_from_image_host(g_device, image, (int)width, (int)height, (int)row_stride, on_device != 0, depth, plan.seeds.edge, *params,
+                              lines, n_lines);
+    });
+}
+
+int fdcm_lines_last_timing(fdcm_lines_timing* out) {
+    return guarded([&] {
+        require(out != nullptr, "out is null");
+        lines_last_timing(out);
+    });
+}
+
 int fdcm_featuremap_build_image_ex(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
                                    const fdcm_edge_params* params, int64_t border, int64_t depth, float dt3_coeff, int distance,
                                    fdcm_featuremap** out) {

@@ -15,6 +15,7 @@
 
 #include "fdcm_build_dev.h"
 #include "fdcm_internal.h"
+#include "fdcm_unionfind.h"
 
 namespace fdcm {
 
@@ -150,7 +151,6 @@ __device__ __forceinline__ void load_clamped_tile(unsigned char (*px)[STR], cons
     }
 }
 
-static constexpr int kNoParent = -1;            // parent of a pixel that is no candidate
 static constexpr unsigned kStrongBit = 0x80000000u;  // roots[]: bit 31 strong, bits 0-30 the component's candidates
 
 // k_edge_labels with S in place of I and low^2 for the threshold; per pixel the provisional label (255: no candidate), the
@@ -232,25 +232,6 @@ __global__ void __launch_bounds__(256) k_edge_candidates(const uint8_t* __restri
     }
 }
 
-// Union-find on `parent` (a candidate's parent is a candidate of its component with a smaller or the same index; a root is its
-// own).  Other workgroups link roots meanwhile, so every read is an atomic load: a stale parent is still an ancestor.
-__device__ __forceinline__ int uf_load(const int32_t* parent, int p) { return __hip_atomic_load(parent + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int uf_find(const int32_t* parent, int p) {
-    for (int q = uf_load(parent, p); q != p; q = uf_load(parent, p)) p = q;
-    return p;
-}
-// Links the larger root under the smaller.  When the larger one stopped being a root meanwhile, atomicMin has either changed
-// nothing or replaced its parent, which is then merged in its turn: no link is lost, and every step lowers a parent.
-__device__ __forceinline__ void uf_union(int32_t* parent, int a, int b) {
-    for (;;) {
-        a = uf_find(parent, a); b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }  // a > b
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
 // a candidate with each candidate among its four neighbours of the rows above and the column before: every 8-neighbour pair once
 __global__ void __launch_bounds__(256) k_edge_union(int W, int H, int32_t* parent) {
     const int p = blockIdx.x * 256 + threadIdx.x;

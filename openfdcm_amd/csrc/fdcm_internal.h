@@ -292,6 +292,13 @@ void edge_labels_host(int device, const uint8_t* image, int width, int height, i
                       uint8_t* labels_out);
 void edge_labels_host_ex(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth,
                          const fdcm_edge_params& e, uint8_t* labels_out);
+// implemented in fdcm_lines.hip: label image -> line segments (include/fdcm.h, "line segments from images"); blocking, on the
+// null stream of `device`; *lines is malloc'ed (fdcm_lines_free) or null when nothing is kept
+void lines_from_labels_host(int device, const uint8_t* labels, int width, int height, bool on_device, int m, const fdcm_line_params& lp,
+                            float** lines, int64_t* n_lines);
+void lines_from_image_host(int device, const uint8_t* image, int width, int height, int row_stride, bool on_device, int64_t depth,
+                           const fdcm_edge_params& e, const fdcm_line_params& lp, float** lines, int64_t* n_lines);
+void lines_last_timing(fdcm_lines_timing* out);
 // Waits for a queued build (if any) and fills fm->last_build.  run_build only queues the kernels: the search
 // that follows is ordered behind them on the same stream and its host-side preparation runs meanwhile.
 void finish_build(fdcm_featuremap* fm);

@@ -390,6 +390,54 @@ def edge_labels(image, depth=30, threshold=60, low=None, smooth=0, min_pixels=1)
     return out
 
 
+def _adopt_lines(ptr, n):
+    """A library-allocated array of n line records as a (4, n) float32 array of its own (the LineArray openfdcm.read
+    returns); the allocation is released."""
+    if not ptr or n == 0:
+        if ptr:
+            capi.lib().fdcm_lines_free(ptr)
+        return np.zeros((4, 0), dtype=np.float32)
+    try:
+        return np.ctypeslib.as_array(ptr, shape=(n, 4)).T.copy()
+    finally:
+        capi.lib().fdcm_lines_free(ptr)
+
+
+def lines_from_labels(labels, depth=30, bucket=4, line_pixels=8, line_length=8):
+    """The line segments of a label image (include/fdcm.h, "line segments from images"), computed on the GPU: (4, N) float32 in
+    image pixels, as openfdcm.read returns them.  `labels`: 2-D uint8, a numpy array or a contiguous CUDA torch tensor, as
+    edge_labels makes it for `depth`.  bucket: labels per orientation bucket; line_pixels / line_length: the fewest pixels and
+    the shortest extent along the major axis of a kept component."""
+    if hasattr(labels, "data_ptr") and not isinstance(labels, np.ndarray) and labels.dim() == 2 and not labels.is_contiguous():
+        raise ValueError("labels on the device must be contiguous")
+    p, w, h, _, dev, keep = _pixels(labels, "labels")
+    if not dev and keep.size and keep.strides[0] != w:
+        keep = np.ascontiguousarray(keep)
+        p = C.c_void_p(keep.ctypes.data)
+    lp = capi.LineParams(int(bucket), int(line_pixels), int(line_length))
+    out, n = C.POINTER(C.c_float)(), C.c_int64()
+    capi.check(capi.lib().fdcm_lines_from_labels(p, w, h, dev, int(depth), C.byref(lp), C.byref(out), C.byref(n)))
+    return _adopt_lines(out, n.value)
+
+
+def lines_from_image(image, depth=30, threshold=60, low=None, smooth=0, min_pixels=1, bucket=4, line_pixels=8, line_length=8):
+    """The line segments of a frame: edge_labels(image, depth, threshold, low, smooth, min_pixels) followed by lines_from_labels,
+    with the label image staying on the GPU.  `image`: 2-D uint8, a numpy array or a CUDA torch tensor (rows may be strided)."""
+    p, w, h, stride, dev, keep = _pixels(image, "image")
+    ex = capi.EdgeParams(int(smooth), int(threshold if low is None else low), int(threshold), int(min_pixels))
+    lp = capi.LineParams(int(bucket), int(line_pixels), int(line_length))
+    out, n = C.POINTER(C.c_float)(), C.c_int64()
+    capi.check(capi.lib().fdcm_lines_from_image(p, w, h, stride, dev, int(depth), C.byref(ex), C.byref(lp), C.byref(out), C.byref(n)))
+    return _adopt_lines(out, n.value)
+
+
+def lines_last_timing():
+    """Device milliseconds per stage of this thread's last lines_from_* call (fdcm_lines_timing) as a dict."""
+    t = capi.LinesTiming()
+    capi.check(capi.lib().fdcm_lines_last_timing(C.byref(t)))
+    return {name: getattr(t, name) for name, _ in capi.LinesTiming._fields_}
+
+
 def search_raw(fm, templates, scene, max_tmpl_lines, max_scene_lines, optimizer=capi.BATCH_OPTIMIZE, batch_size=10,
                tmpl_index_base=0):
     """Run the search and return the raw matches as a structured array (capi.MATCH_DTYPE)."""
