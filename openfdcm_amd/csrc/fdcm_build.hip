@@ -726,11 +726,9 @@ static void stage_pass1(fdcm_featuremap* fm, const BuildLayout& L, const PlanOnD
         const uint8_t* labels = P.pixels;
         fm->built.seeds_fused = src.kind == SeedKind::labels;
         if (src.kind == SeedKind::image) {
-            if (src.edge_plain())
-                launch_edge_labels(st, P.pixels, src.width, src.height, P.pixel_stride, P.keys, m, src.edge.high, fm->build.labels.as<uint8_t>());
-            else
-                launch_edge_labels_ex(st, P.pixels, src.width, src.height, P.pixel_stride, P.keys, m, src.edge, fm->build.labels.as<uint8_t>(),
-                                      fm->build.edge_parent.as<int32_t>(), fm->build.edge_roots.as<uint32_t>());
+            const bool hyst = !src.edge_plain();  // (the scratch of an earlier build with hysteresis may still be there)
+            launch_edge_labels(st, P.pixels, src.width, src.height, P.pixel_stride, P.keys, m, src.edge, fm->build.labels.as<uint8_t>(),
+                               hyst ? fm->build.edge_parent.as<int32_t>() : nullptr, hyst ? fm->build.edge_roots.as<uint32_t>() : nullptr);
             labels = fm->build.labels.as<uint8_t>();
             mark(fm, 1, fm->built.stage_events);
         }

@@ -212,7 +212,7 @@ int fdcm_edge_labels(const uint8_t* image, int64_t width, int64_t height, int64_
         require(depth >= 1, "depth must be >= 1");
         BuildPlan plan;
         pixel_plan(image, width, height, row_stride, 0, SeedKind::image, EdgeArg::plain(threshold), 0, depth, 0.f, plan);
-        edge_labels_host(g_device, image, (int)width, (int)height, (int)row_stride, depth, threshold, labels_out);
+        edge_labels_host(g_device, image, (int)width, (int)height, (int)row_stride, depth, plan.seeds.edge, false, labels_out);
     });
 }
 
@@ -223,7 +223,7 @@ int fdcm_edge_labels_ex(const uint8_t* image, int64_t width, int64_t height, int
         require(depth >= 1, "depth must be >= 1");
         BuildPlan plan;
         pixel_plan(image, width, height, row_stride, 0, SeedKind::image, EdgeArg::params(params), 0, depth, 0.f, plan);
-        edge_labels_host_ex(g_device, image, (int)width, (int)height, (int)row_stride, depth, plan.seeds.edge, labels_out);
+        edge_labels_host(g_device, image, (int)width, (int)height, (int)row_stride, depth, plan.seeds.edge, true, labels_out);
     });
 }
 

@@ -1,16 +1,20 @@
 // fdcm_image.hip -- DT3 seeds from pixels on gfx950: oriented edge pixels of a grey image as a label image, and pass 1 of the
 // distance transform with its seeds taken from a label image (include/fdcm.h, "feature maps from images").
 //
-//   k_edge_labels      uint8 image -> label image: integer Sobel, thresholded and thinned along the gradient, the edge's tangent
-//                      binned by closest_orientation over the build's keys               read W H, write W H
+//   edge_tile<S, HYST> the one body of the two edge kernels: the tile and its halo into LDS (load_clamped_tile), smoothed for
+//                      S > 0, integer Sobel, thresholded and thinned along the gradient, the edge's tangent binned by
+//                      closest_orientation over the build's keys
+//   k_edge_labels      edge_tile<0, false>: uint8 image -> label image by one threshold    read W H, write W H
 //   k_coldesc_labels   k_coldesc_tile's sibling: the bitmap tile in LDS comes from the label image instead of RasterLines, the
 //                      descriptor step (coldesc_from_bits) is shared                     read m W H (from L2), write ~V/16
-//   k_edge_candidates<S>, k_edge_union, k_edge_roots, k_edge_resolve
-//                      the same label image with smoothing, hysteresis and a minimum component size: candidates (thinned,
-//                      m2 >= low^2) with their provisional labels, their 8-connected components by union-find on one parent
-//                      per pixel, strong flag and size per root, and the candidates of the other roots back to 255
+//   k_edge_candidates<S>, k_edge_tiles, k_edge_borders, k_edge_roots, k_edge_resolve
+//                      the same label image with smoothing, hysteresis and a minimum component size: candidates
+//                      (edge_tile<S, true>: thinned, m2 >= low^2) with their provisional labels and strong flags, their
+//                      8-connected components by the tiled labeller of fdcm_unionfind.h with one partition (a tile merged in
+//                      LDS, the pairs across tile borders in global memory), strong flag and size per root, and the candidates
+//                      of the other roots back to 255
 // All index with the caller's sizes only: every load is of a pixel inside [0, width) x [0, height), every store inside the label
-// image or the descriptors of the block's own columns.
+// image, the words of the image's own pixels or the descriptors of the block's own columns.
 #include <algorithm>
 
 #include "fdcm_build_dev.h"
@@ -20,11 +24,11 @@
 namespace fdcm {
 
 // ------------------------------------------------------------------------------------------ image -> labels
-static constexpr int kEdgeTW = 64, kEdgeTH = 16;  // pixels a workgroup labels
-static constexpr int kEdgeHalo = 2;               // 1 for Sobel + 1 for the neighbours' m2
+static constexpr int kEdgeTW = kTileW, kEdgeTH = kTileH;  // pixels a workgroup labels: the tiles of the component kernels
+static constexpr int kEdgeHalo = 2;                       // 1 for Sobel + 1 for the neighbours' m2
 static constexpr int kEdgePW = kEdgeTW + 2 * kEdgeHalo, kEdgePH = kEdgeTH + 2 * kEdgeHalo;  // pixels held
 static constexpr int kEdgeMW = kEdgeTW + 2, kEdgeMH = kEdgeTH + 2;                          // squared magnitudes held
-static constexpr int kEdgeRowDwords = (kEdgePW + 3 + 3) / 4;  // aligned dwords that cover a row of held pixels wherever it starts
+static constexpr unsigned kStrongBit = 0x80000000u;  // roots[]: bit 31 strong, bits 0-30 the component's candidates
 
 // Sobel at tile position (r, c) of the held pixels (replicate border: the loads clamped the coordinates)
 __device__ __forceinline__ void sobel_at(const unsigned char (*px)[kEdgePW + 4], int r, int c, int& gx, int& gy) {
@@ -35,102 +39,19 @@ __device__ __forceinline__ void sobel_at(const unsigned char (*px)[kEdgePW + 4],
     gy = (g + 2 * h + i) - (a + 2 * b + d);
 }
 
-__global__ void __launch_bounds__(256) k_edge_labels(const uint8_t* __restrict__ image, int W, int H, int stride, const float* __restrict__ keys,
-                                                     int m, int thr2, uint8_t* __restrict__ labels) {
-    __shared__ unsigned char px[kEdgePH][kEdgePW + 4];
-    __shared__ int sm2[kEdgeMH][kEdgeMW];
-    __shared__ float skeys[256];
-    const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * kEdgeTW, y0 = blockIdx.y * kEdgeTH;
-    const int xa = x0 - kEdgeHalo;                           // image column of held column 0
-    const int lo = max(xa, 0), hi = min(xa + kEdgePW, W);    // the held columns inside the image: [lo, hi), never empty (x0 < W)
-    if (tid < m) skeys[tid] = keys[tid];
-    // the pixels inside the image: aligned dwords where all four bytes are the row's, single bytes at the ragged ends
-    for (int idx = tid; idx < kEdgePH * kEdgeRowDwords; idx += 256) {
-        const int r = idx / kEdgeRowDwords, j = idx - r * kEdgeRowDwords;
-        const int y = min(max(y0 - kEdgeHalo + r, 0), H - 1);
-        const uint8_t* rp = image + (size_t)y * stride;
-        const int mis = (int)((uintptr_t)(rp + lo) & 3u);    // bytes between the aligned address below the first pixel and it
-        const int xf = lo - mis + 4 * j;                     // column of the dword's first byte
-        if (xf >= hi) continue;
-        if (xf >= lo && xf + 4 <= hi) {
-            const unsigned v = *reinterpret_cast<const unsigned*>(rp + xf);
-            unsigned char* dst = &px[r][xf - xa];
-            dst[0] = (unsigned char)v; dst[1] = (unsigned char)(v >> 8); dst[2] = (unsigned char)(v >> 16); dst[3] = (unsigned char)(v >> 24);
-        } else {
-            for (int b = 0; b < 4; ++b) {
-                const int x = xf + b;
-                if (x >= lo && x < hi) px[r][x - xa] = rp[x];
-            }
-        }
-    }
-    // the held columns outside it: the row's first / last pixel (replicate border)
-    for (int idx = tid; idx < kEdgePH * kEdgePW; idx += 256) {
-        const int r = idx / kEdgePW, c = idx - r * kEdgePW, x = xa + c;
-        if (x >= 0 && x < W) continue;
-        const int y = min(max(y0 - kEdgeHalo + r, 0), H - 1);
-        px[r][c] = image[(size_t)y * stride + (x < 0 ? 0 : W - 1)];
-    }
-    __syncthreads();
-    // squared gradient magnitude of the tile and one pixel around it; 0 outside the image
-    for (int idx = tid; idx < kEdgeMH * kEdgeMW; idx += 256) {
-        const int rr = idx / kEdgeMW, cc = idx - rr * kEdgeMW;
-        const int x = x0 - 1 + cc, y = y0 - 1 + rr;
-        int v = 0;
-        if (x >= 0 && x < W && y >= 0 && y < H) {
-            int gx, gy;
-            sobel_at(px, rr + 1, cc + 1, gx, gy);
-            v = gx * gx + gy * gy;  // <= 2 * 1020^2
-        }
-        sm2[rr][cc] = v;
-    }
-    __syncthreads();
-    const int lx = tid & 63;
-#pragma unroll
-    for (int i = 0; i < kEdgeTH / 4; ++i) {
-        const int ly = (tid >> 6) + 4 * i;
-        const int x = x0 + lx, y = y0 + ly;
-        if (x >= W || y >= H) continue;
-        int gx, gy;
-        sobel_at(px, ly + kEdgeHalo, lx + kEdgeHalo, gx, gy);
-        const int m2 = sm2[ly + 1][lx + 1];
-        const int a = abs(gx), b = abs(gy);
-        int dx, dy;  // the step along the gradient, quantised to 8 neighbours (12 / 29 ~ tan 22.5 deg)
-        if (29 * b < 12 * a) { dx = 1; dy = 0; }
-        else if (29 * a < 12 * b) { dx = 0; dy = 1; }
-        else { dx = 1; dy = ((gx >= 0) == (gy >= 0)) ? 1 : -1; }
-        const int before = sm2[ly + 1 - dy][lx + 1 - dx], after = sm2[ly + 1 + dy][lx + 1 + dx];
-        unsigned char label = 255;
-        if (m2 >= thr2 && m2 > before && m2 >= after) {
-            // the edge's tangent (-gy, gx) as getAngle sees a line from the origin to it (math.h:295-299); the integer is negated, so gy = 0 gives +0
-            const float tdx = (float)(-gy), tdy = (float)gx;
-            label = (unsigned char)closest_orientation(skeys, m, atanf_glibc(tdy / tdx));
-        }
-        labels[(size_t)y * W + x] = label;
-    }
-}
-
-void launch_edge_labels(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
-                        int threshold, uint8_t* labels) {
-    const dim3 grid((unsigned)((width + kEdgeTW - 1) / kEdgeTW), (unsigned)((height + kEdgeTH - 1) / kEdgeTH));
-    hipLaunchKernelGGL(k_edge_labels, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, threshold * threshold, labels);
-}
-
-// ------------------------------------------------------------------------------------------ image -> labels, with hysteresis
-// (include/fdcm.h, "edges with smoothing, hysteresis and a minimum chain length")
-// The tile of k_edge_labels with `halo` pixels around it, from the image into LDS: rows as aligned dwords where all four bytes
-// are the row's, single bytes at the ragged ends, and the columns and rows outside the image replicated.
+// PH x PW pixels of the image from (xa, ya) on into LDS: the pixels inside the image as aligned dwords where all four bytes are
+// the row's and single bytes at the ragged ends, the columns and rows outside it replicated (the row's first / last pixel).
 template <int PH, int PW, int STR>
 __device__ __forceinline__ void load_clamped_tile(unsigned char (*px)[STR], const uint8_t* __restrict__ image, int W, int H, int stride,
                                                   int xa, int ya, int tid) {
-    constexpr int kRowDwords = (PW + 3 + 3) / 4;
+    constexpr int kRowDwords = (PW + 3 + 3) / 4;      // aligned dwords that cover a row of held pixels wherever it starts
     const int lo = max(xa, 0), hi = min(xa + PW, W);  // the held columns inside the image: [lo, hi), never empty
     for (int idx = tid; idx < PH * kRowDwords; idx += 256) {
         const int r = idx / kRowDwords, j = idx - r * kRowDwords;
         const int y = min(max(ya + r, 0), H - 1);
         const uint8_t* rp = image + (size_t)y * stride;
-        const int mis = (int)((uintptr_t)(rp + lo) & 3u);
-        const int xf = lo - mis + 4 * j;
+        const int mis = (int)((uintptr_t)(rp + lo) & 3u);  // bytes between the aligned address below the first pixel and it
+        const int xf = lo - mis + 4 * j;                   // column of the dword's first byte
         if (xf >= hi) continue;
         if (xf >= lo && xf + 4 <= hi) {
             const unsigned v = *reinterpret_cast<const unsigned*>(rp + xf);
@@ -151,17 +72,16 @@ __device__ __forceinline__ void load_clamped_tile(unsigned char (*px)[STR], cons
     }
 }
 
-static constexpr unsigned kStrongBit = 0x80000000u;  // roots[]: bit 31 strong, bits 0-30 the component's candidates
-
-// k_edge_labels with S in place of I and low^2 for the threshold; per pixel the provisional label (255: no candidate), the
-// parent (itself for a candidate) and the root word (the pixel's own strong flag, count 0).
-template <int S>
-__global__ void __launch_bounds__(256) k_edge_candidates(const uint8_t* __restrict__ image, int W, int H, int stride, const float* __restrict__ keys,
-                                                         int m, int low2, int high2, uint8_t* __restrict__ labels, int32_t* __restrict__ parent,
-                                                         uint32_t* __restrict__ roots) {
+// The edge detector of one 64 x 16 tile (include/fdcm.h, "edges with smoothing, hysteresis and a minimum chain length"): S is the
+// image smoothed S times (S = 0: the image), a candidate passes low2 and thinning, and its label is the bin of its tangent.
+// Every pixel of the tile inside the image gets its label (255: no candidate); with HYST also its root word (the pixel's own
+// strong flag, m2 >= high2, and count 0), so `roots` needs no clearing.  Without HYST low2 is the one threshold.
+template <int S, bool HYST>
+__device__ __forceinline__ void edge_tile(const uint8_t* __restrict__ image, int W, int H, int stride, const float* __restrict__ keys, int m,
+                                          int low2, int high2, uint8_t* __restrict__ labels, uint32_t* __restrict__ roots) {
     constexpr int HALO = kEdgeHalo + S, RH = kEdgeTH + 2 * HALO, RW = kEdgeTW + 2 * HALO;
     __shared__ unsigned char raw[S ? RH : 1][S ? RW + 4 : 4];  // the image around the tile (smoothing only)
-    __shared__ unsigned char px[kEdgePH][kEdgePW + 4];         // S around the tile, as k_edge_labels holds I
+    __shared__ unsigned char px[kEdgePH][kEdgePW + 4];         // S on the tile and kEdgeHalo pixels around it
     __shared__ int sm2[kEdgeMH][kEdgeMW];
     __shared__ float skeys[256];
     const int tid = threadIdx.x;
@@ -192,6 +112,7 @@ __global__ void __launch_bounds__(256) k_edge_candidates(const uint8_t* __restri
         }
     }
     __syncthreads();
+    // squared gradient magnitude of the tile and one pixel around it; 0 outside the image
     for (int idx = tid; idx < kEdgeMH * kEdgeMW; idx += 256) {
         const int rr = idx / kEdgeMW, cc = idx - rr * kEdgeMW;
         const int x = x0 - 1 + cc, y = y0 - 1 + rr;
@@ -199,7 +120,7 @@ __global__ void __launch_bounds__(256) k_edge_candidates(const uint8_t* __restri
         if (x >= 0 && x < W && y >= 0 && y < H) {
             int gx, gy;
             sobel_at(px, rr + 1, cc + 1, gx, gy);
-            v = gx * gx + gy * gy;
+            v = gx * gx + gy * gy;  // <= 2 * 1020^2
         }
         sm2[rr][cc] = v;
     }
@@ -214,7 +135,7 @@ __global__ void __launch_bounds__(256) k_edge_candidates(const uint8_t* __restri
         sobel_at(px, ly + kEdgeHalo, lx + kEdgeHalo, gx, gy);
         const int m2 = sm2[ly + 1][lx + 1];
         const int a = abs(gx), b = abs(gy);
-        int dx, dy;
+        int dx, dy;  // the step along the gradient, quantised to 8 neighbours (12 / 29 ~ tan 22.5 deg)
         if (29 * b < 12 * a) { dx = 1; dy = 0; }
         else if (29 * a < 12 * b) { dx = 0; dy = 1; }
         else { dx = 1; dy = ((gx >= 0) == (gy >= 0)) ? 1 : -1; }
@@ -222,28 +143,38 @@ __global__ void __launch_bounds__(256) k_edge_candidates(const uint8_t* __restri
         const bool cand = m2 >= low2 && m2 > before && m2 >= after;
         unsigned char label = 255;
         if (cand) {
+            // the edge's tangent (-gy, gx) as getAngle sees a line from the origin to it (math.h:295-299); the integer is negated, so gy = 0 gives +0
             const float tdx = (float)(-gy), tdy = (float)gx;
             label = (unsigned char)closest_orientation(skeys, m, atanf_glibc(tdy / tdx));
         }
         const int p = y * W + x;  // < 2^24
         labels[p] = label;
-        parent[p] = cand ? p : kNoParent;
-        roots[p] = cand && m2 >= high2 ? kStrongBit : 0u;
+        if constexpr (HYST) roots[p] = cand && m2 >= high2 ? kStrongBit : 0u;
     }
 }
 
-// a candidate with each candidate among its four neighbours of the rows above and the column before: every 8-neighbour pair once
-__global__ void __launch_bounds__(256) k_edge_union(int W, int H, int32_t* parent) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= W * H || uf_load(parent, p) == kNoParent) return;
-    const int y = p / W, x = p - y * W;
-    if (x > 0 && uf_load(parent, p - 1) != kNoParent) uf_union(parent, p, p - 1);
-    if (y > 0) {
-        const int q = p - W;
-        if (x > 0 && uf_load(parent, q - 1) != kNoParent) uf_union(parent, p, q - 1);
-        if (uf_load(parent, q) != kNoParent) uf_union(parent, p, q);
-        if (x + 1 < W && uf_load(parent, q + 1) != kNoParent) uf_union(parent, p, q + 1);
-    }
+__global__ void __launch_bounds__(256) k_edge_labels(const uint8_t* __restrict__ image, int W, int H, int stride, const float* __restrict__ keys,
+                                                     int m, int thr2, uint8_t* __restrict__ labels) {
+    edge_tile<0, false>(image, W, H, stride, keys, m, thr2, 0, labels, nullptr);
+}
+template <int S>
+__global__ void __launch_bounds__(256) k_edge_candidates(const uint8_t* __restrict__ image, int W, int H, int stride, const float* __restrict__ keys,
+                                                         int m, int low2, int high2, uint8_t* __restrict__ labels, uint32_t* __restrict__ roots) {
+    edge_tile<S, true>(image, W, H, stride, keys, m, low2, high2, labels, roots);
+}
+
+// The candidates' 8-connected components: the shared labeller with one partition, whose key says "a candidate".  k_edge_tiles
+// writes a parent for every pixel of the image (kNoParent off the candidates), as k_line_tiles does, so `parent` needs no
+// clearing and holds nothing of an earlier call when the kernels below read it.
+struct EdgeKeys {
+    static constexpr int P = 1;
+    __device__ __forceinline__ int key(int, int label) const { return label < 255 ? 0 : kNoKey; }
+};
+__global__ void __launch_bounds__(256) k_edge_tiles(const uint8_t* __restrict__ labels, int W, int H, int32_t* __restrict__ parent) {
+    uf_tile_merge(EdgeKeys{}, labels, W, H, parent);
+}
+__global__ void __launch_bounds__(kBorderThreads) k_edge_borders(const uint8_t* __restrict__ labels, int W, int H, int32_t* parent) {
+    uf_border_merge(EdgeKeys{}, labels, W, H, parent);
 }
 // flatten, and per root the candidates' count and strong flag.  Bit 31 of roots[p] is p's own flag until this kernel adds to a
 // root's word; a root that reads its component's flag for its own ORs it into itself.
@@ -267,18 +198,23 @@ __global__ void __launch_bounds__(256) k_edge_resolve(int n, const int32_t* __re
     if (!(w & kStrongBit) || (int)(w & ~kStrongBit) < min_pixels) labels[p] = 255;
 }
 
-void launch_edge_labels_ex(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
-                           const fdcm_edge_params& e, uint8_t* labels, int32_t* parent, uint32_t* roots) {
-    const dim3 grid((unsigned)((width + kEdgeTW - 1) / kEdgeTW), (unsigned)((height + kEdgeTH - 1) / kEdgeTH));
+void launch_edge_labels(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
+                        const fdcm_edge_params& e, uint8_t* labels, int32_t* parent, uint32_t* roots) {
+    const dim3 grid = uf_tile_grid(width, height);
     const int low2 = e.low * e.low, high2 = e.high * e.high, n = width * height;
+    if (!parent) {
+        hipLaunchKernelGGL(k_edge_labels, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, high2, labels);
+        return;
+    }
     switch (e.smooth) {
-    case 0: hipLaunchKernelGGL(k_edge_candidates<0>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, parent, roots); break;
-    case 1: hipLaunchKernelGGL(k_edge_candidates<1>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, parent, roots); break;
-    default: hipLaunchKernelGGL(k_edge_candidates<2>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, parent, roots); break;
+    case 0: hipLaunchKernelGGL(k_edge_candidates<0>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, roots); break;
+    case 1: hipLaunchKernelGGL(k_edge_candidates<1>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, roots); break;
+    default: hipLaunchKernelGGL(k_edge_candidates<2>, grid, dim3(256), 0, st, image, width, height, row_stride, keys, m, low2, high2, labels, roots); break;
     }
     // launch counts and grids depend on the size alone: the components are resolved without a look at them from the host
     const dim3 flat((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(k_edge_union, flat, dim3(256), 0, st, width, height, parent);
+    hipLaunchKernelGGL(k_edge_tiles, grid, dim3(256), 0, st, (const uint8_t*)labels, width, height, parent);
+    hipLaunchKernelGGL(k_edge_borders, grid, dim3(kBorderThreads), 0, st, (const uint8_t*)labels, width, height, parent);
     hipLaunchKernelGGL(k_edge_roots, flat, dim3(256), 0, st, n, parent, roots);
     hipLaunchKernelGGL(k_edge_resolve, flat, dim3(256), 0, st, n, (const int32_t*)parent, (const uint32_t*)roots, e.min_pixels, labels);
 }
@@ -334,40 +270,34 @@ void launch_coldesc_labels(hipStream_t st, const uint8_t* labels, int width, int
     else hipLaunchKernelGGL((k_coldesc_labels<64, 32>), grid, dim3(256), lds, st, labels, width, height, border, d, W, H, HW64, colmask, cost);
 }
 
-// ------------------------------------------------------------------------------------------ fdcm_edge_labels
-void edge_labels_host(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth, int threshold,
-                      uint8_t* labels_out) {
-    std::vector<float> keys;
-    plan_keys(depth, keys);
-    FDCM_HIP(hipSetDevice(device));
-    struct Scratch { DevBuf image, labels, keys; ~Scratch() { image.release(); labels.release(); keys.release(); } } s;
-    const size_t n = (size_t)width * height;
-    s.image.reserve(n); s.labels.reserve(n); s.keys.reserve(std::max<size_t>(1, keys.size()) * sizeof(float));
-    FDCM_HIP(hipMemcpy2D(s.image.p, (size_t)width, image, (size_t)row_stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
-    FDCM_HIP(hipMemcpy(s.keys.p, keys.data(), keys.size() * sizeof(float), hipMemcpyHostToDevice));
-    launch_edge_labels(nullptr, s.image.as<uint8_t>(), width, height, width, s.keys.as<float>(), (int)keys.size(), threshold, s.labels.as<uint8_t>());
-    FDCM_HIP(hipGetLastError());
-    FDCM_HIP(hipDeviceSynchronize());
-    FDCM_HIP(hipMemcpy(labels_out, s.labels.p, n, hipMemcpyDeviceToHost));
+// ------------------------------------------------------------------------------------------ the calls without a handle
+PixelScratch::~PixelScratch() { for (DevBuf* b : {&pixels, &labels, &keys, &parent, &counts, &comps, &out}) b->release(); }
+
+const uint8_t* PixelScratch::upload(const uint8_t* host_or_device, int width, int height, int& row_stride, bool on_device,
+                                    const std::vector<float>* host_keys) {
+    if (host_keys) {
+        keys.reserve(std::max<size_t>(1, host_keys->size()) * sizeof(float));
+        FDCM_HIP(hipMemcpy(keys.p, host_keys->data(), host_keys->size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (on_device) return host_or_device;
+    pixels.reserve((size_t)width * height);
+    FDCM_HIP(hipMemcpy2D(pixels.p, (size_t)width, host_or_device, (size_t)row_stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
+    row_stride = width;
+    return pixels.as<uint8_t>();
 }
 
-
-void edge_labels_host_ex(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth,
-                         const fdcm_edge_params& e, uint8_t* labels_out) {
+void edge_labels_host(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth, const fdcm_edge_params& e,
+                      bool hysteresis, uint8_t* labels_out) {
     std::vector<float> keys;
     plan_keys(depth, keys);
     FDCM_HIP(hipSetDevice(device));
-    struct Scratch {
-        DevBuf image, labels, keys, parent, roots;
-        ~Scratch() { for (DevBuf* b : {&image, &labels, &keys, &parent, &roots}) b->release(); }
-    } s;
+    PixelScratch s;
     const size_t n = (size_t)width * height;
-    s.image.reserve(n); s.labels.reserve(n); s.keys.reserve(std::max<size_t>(1, keys.size()) * sizeof(float));
-    s.parent.reserve(n * 4); s.roots.reserve(n * 4);
-    FDCM_HIP(hipMemcpy2D(s.image.p, (size_t)width, image, (size_t)row_stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
-    FDCM_HIP(hipMemcpy(s.keys.p, keys.data(), keys.size() * sizeof(float), hipMemcpyHostToDevice));
-    launch_edge_labels_ex(nullptr, s.image.as<uint8_t>(), width, height, width, s.keys.as<float>(), (int)keys.size(), e, s.labels.as<uint8_t>(),
-                          s.parent.as<int32_t>(), s.roots.as<uint32_t>());
+    const uint8_t* d = s.upload(image, width, height, row_stride, false, &keys);
+    s.labels.reserve(n);
+    if (hysteresis) s.comps.reserve(n * 8);  // a parent and a root word per pixel
+    launch_edge_labels(nullptr, d, width, height, row_stride, s.keys.as<float>(), (int)keys.size(), e, s.labels.as<uint8_t>(),
+                       hysteresis ? s.comps.as<int32_t>() : nullptr, hysteresis ? s.comps.as<uint32_t>() + n : nullptr);
     FDCM_HIP(hipGetLastError());
     FDCM_HIP(hipDeviceSynchronize());
     FDCM_HIP(hipMemcpy(labels_out, s.labels.p, n, hipMemcpyDeviceToHost));

@@ -195,7 +195,7 @@ struct BuildBuffers {  // what a build needs besides the volume, sized by BuildL
     DevBuf coldesc;  // m*ceil(H/64)*W column-chunk descriptors (16 B)
     DevBuf colmask;  // m*ceil(W/64) words: the seeded columns of every slice (k_coldesc_tile, for the L2 sweep)
     DevBuf labels;   // image builds: the label image k_edge_labels writes and k_coldesc_labels reads
-    DevBuf edge_parent, edge_roots;  // image builds with hysteresis: the union-find of the candidates (launch_edge_labels_ex)
+    DevBuf edge_parent, edge_roots;  // image builds with hysteresis: the union-find of the candidates (launch_edge_labels)
     DevBuf offtab;   // per slice: one word per group of 4 columns for the shallow sweeps of the line integral (k_groups)
     DevBuf stack;    // the sweep's scratch: the balanced sweep's stack and owner entries (slot-major per chunk), launch order,
                      // per-chunk costs and steal counter; or the literal pass's scratch; or the L1 pass's minima / carries
@@ -278,20 +278,31 @@ BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after);  
 // had to move drops the sweep's cost history and steal counter)
 void reserve_build(fdcm_featuremap* fm, const BuildLayout& L);
 void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after);
-// implemented in fdcm_image.hip: image -> label image (k_edge_labels), and pass 1 with its seeds from a label image
-// (k_coldesc_labels); `cost`, where given, receives the sweep's per-chunk proxy (zeroed by the caller)
+// implemented in fdcm_image.hip: image -> label image by `e` (include/fdcm.h, "edges with smoothing, hysteresis and a minimum
+// chain length"), queued on st.  With `parent` and `roots` (width * height words each): candidates, their components by
+// union-find in `parent`, strong flag and size per root in `roots`.  With both null: k_edge_labels with the one threshold
+// e.high, which is the same for {0, t, t, 1} and needs no scratch.
 void launch_edge_labels(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
-                        int threshold, uint8_t* labels);
-// the same by `e` (include/fdcm.h, "edges with smoothing, hysteresis and a minimum chain length"): candidates, their components
-// by union-find in `parent`, strong flag and size per root in `roots` (width * height words each), all queued on st
-void launch_edge_labels_ex(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
-                           const fdcm_edge_params& e, uint8_t* labels, int32_t* parent, uint32_t* roots);
+                        const fdcm_edge_params& e, uint8_t* labels, int32_t* parent, uint32_t* roots);
+// pass 1 with its seeds from a label image (k_coldesc_labels); `cost`, where given, receives the sweep's per-chunk proxy (zeroed
+// by the caller)
 void launch_coldesc_labels(hipStream_t st, const uint8_t* labels, int width, int height, int border, void* desc, int W, int H,
                            int HW64, int m, unsigned* colmask, int* cost);
-void edge_labels_host(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth, int threshold,
-                      uint8_t* labels_out);
-void edge_labels_host_ex(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth,
-                         const fdcm_edge_params& e, uint8_t* labels_out);
+// What a call without a handle holds on the device, allocated per call and released at its end: the pixels and keys it
+// uploaded, the label image, and the scratch of the edge and line stages.
+struct PixelScratch {
+    // edge_labels_host: pixels, keys, labels, and comps for the edge kernels' parent and root words.  lines_from_labels_host:
+    // pixels (the labels), parent (both partitions), counts, comps (the components' sums), out.  lines_from_image_host: all of
+    // them; comps serves the edge kernels first and the components' sums afterwards.
+    DevBuf pixels, labels, keys, parent, counts, comps, out;
+    ~PixelScratch();
+    // The caller's image or label array where the kernels read it: device memory stays in place; host memory is copied into
+    // `pixels` with rows packed, and row_stride becomes width.  The keys, where given, go into `keys`.
+    const uint8_t* upload(const uint8_t* host_or_device, int width, int height, int& row_stride, bool on_device, const std::vector<float>* host_keys);
+};
+// host image -> host labels, blocking, on the null stream of `device`: the hysteresis kernels, or k_edge_labels by e.high
+void edge_labels_host(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth, const fdcm_edge_params& e,
+                      bool hysteresis, uint8_t* labels_out);
 // implemented in fdcm_lines.hip: label image -> line segments (include/fdcm.h, "line segments from images"); blocking, on the
 // null stream of `device`; *lines is malloc'ed (fdcm_lines_free) or null when nothing is kept
 void lines_from_labels_host(int device, const uint8_t* labels, int width, int height, bool on_device, int m, const fdcm_line_params& lp,

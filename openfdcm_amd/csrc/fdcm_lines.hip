@@ -5,6 +5,7 @@
 //   k_line_tiles     labels -> both buckets per pixel; union-find of a 64 x 16 tile in LDS, both partitions; per pixel the
 //                    tile-local root as a global index (kNoParent off the edges)                     read W H, write 8 W H
 //   k_line_borders   the 8-neighbour pairs that straddle two tiles, merged in global memory (uf_union)
+//                    (both are the tiled labeller of fdcm_unionfind.h with LineKeys: two partitions, the key a bucket)
 //   k_line_roots     flatten, and the roots of every 1024 pixels counted
 //   k_line_scan      exclusive scan of block counts in place, the total behind them (one workgroup; used twice)
 //   k_line_number    a root's parent becomes -(id + 2): ids ascend with 2 * root + partition
@@ -21,113 +22,24 @@
 
 namespace fdcm {
 
-static constexpr int kLineTW = 64, kLineTH = 16, kLineTile = kLineTW * kLineTH;  // pixels a workgroup merges in LDS
-static constexpr int kNoBucket = 255;       // a label < m <= 255 has a bucket <= 254
 static constexpr int kLineBlock = 1024;     // pixels per workgroup of the flat kernels that scan (4 per thread)
 
-__device__ __forceinline__ int bucket_a(int l, int m, int w) { return l < m ? l / w : kNoBucket; }
-__device__ __forceinline__ int bucket_b(int l, int m, int w) {
-    if (l >= m) return kNoBucket;
-    const int s = l + w / 2;  // < 2 m
-    return (s >= m ? s - m : s) / w;
+// The two partitions of the labels: partition A cuts the m orientations into buckets of w from 0 on, partition B from w / 2 on
+// (cyclic).  A label < m <= 255 has a bucket <= 254 in both; any other byte is no edge pixel.
+struct LineKeys {
+    static constexpr int P = 2;
+    int m, w;
+    __device__ __forceinline__ int key(int part, int l) const {
+        const int s = l + w / 2;  // < 2 m for an edge pixel
+        const int k = (part == 0 ? l : (s >= m ? s - m : s)) / w;  // (divided whatever l is: every call shares one reciprocal of w)
+        return l < m ? k : kNoKey;
+    }
+};
+__global__ void __launch_bounds__(256) k_line_tiles(const uint8_t* __restrict__ labels, int W, int H, LineKeys keys, int32_t* __restrict__ parent) {
+    uf_tile_merge(keys, labels, W, H, parent);
 }
-
-// union-find of a tile in LDS: uf_union at workgroup scope on tile-local indices (row-major in the tile, so their order is that
-// of the global indices of the same pixels)
-static constexpr int kTileScope = __HIP_MEMORY_SCOPE_WORKGROUP;
-
-__global__ void __launch_bounds__(256) k_line_tiles(const uint8_t* __restrict__ labels, int W, int H, int m, int w,
-                                                    int32_t* __restrict__ parent_a, int32_t* __restrict__ parent_b) {
-    __shared__ unsigned char sb[2][kLineTile];
-    __shared__ int lp[2][kLineTile];
-    const int tid = threadIdx.x, lx = tid & 63;
-    const int x0 = blockIdx.x * kLineTW, y0 = blockIdx.y * kLineTH;
-#pragma unroll
-    for (int i = 0; i < kLineTH / 4; ++i) {
-        const int ly = (tid >> 6) + 4 * i, li = ly * kLineTW + lx;
-        const int x = x0 + lx, y = y0 + ly;
-        const int l = x < W && y < H ? labels[(size_t)y * W + x] : 255;
-        const int a = bucket_a(l, m, w);
-        sb[0][li] = (unsigned char)a; sb[1][li] = (unsigned char)bucket_b(l, m, w);
-        lp[0][li] = lp[1][li] = a != kNoBucket ? li : kNoParent;
-    }
-    __syncthreads();
-    // an edge pixel with the pixels of its bucket among its west, north-west, north and north-east neighbours inside the tile
-#pragma unroll
-    for (int i = 0; i < kLineTH / 4; ++i) {
-        const int ly = (tid >> 6) + 4 * i, li = ly * kLineTW + lx;
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-            const int bk = sb[part][li];
-            if (bk == kNoBucket) continue;
-            if (lx > 0 && sb[part][li - 1] == bk) uf_union<kTileScope>(lp[part], li, li - 1);
-            if (ly > 0) {
-                if (lx > 0 && sb[part][li - kLineTW - 1] == bk) uf_union<kTileScope>(lp[part], li, li - kLineTW - 1);
-                if (sb[part][li - kLineTW] == bk) uf_union<kTileScope>(lp[part], li, li - kLineTW);
-                if (lx + 1 < kLineTW && sb[part][li - kLineTW + 1] == bk) uf_union<kTileScope>(lp[part], li, li - kLineTW + 1);
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < kLineTH / 4; ++i) {
-        const int ly = (tid >> 6) + 4 * i, li = ly * kLineTW + lx;
-        const int x = x0 + lx, y = y0 + ly;
-        if (x >= W || y >= H) continue;
-        const int p = y * W + x;  // < 2^24
-        int ra = kNoParent, rb = kNoParent;
-        if (sb[0][li] != kNoBucket) {
-            const int a = uf_find<kTileScope>(lp[0], li), b = uf_find<kTileScope>(lp[1], li);
-            ra = (y0 + (a >> 6)) * W + x0 + (a & 63);
-            rb = (y0 + (b >> 6)) * W + x0 + (b & 63);
-        }
-        parent_a[p] = ra; parent_b[p] = rb;
-    }
-}
-
-// pixel p = (x, y) with its neighbour q = (xq, yq) of the row above or the column before, in another tile: merged per
-// partition where the buckets agree
-__device__ __forceinline__ void border_link(const uint8_t* __restrict__ labels, int W, int m, int w, int p, int ba, int bb, int xq, int yq,
-                                            int32_t* parent_a, int32_t* parent_b) {
-    const int q = yq * W + xq;
-    const int l = labels[q];
-    if (l >= m) return;
-    if (bucket_a(l, m, w) == ba) uf_union(parent_a, p, q);
-    if (bucket_b(l, m, w) == bb) uf_union(parent_b, p, q);
-}
-// one workgroup per tile, a thread per pixel of its top row (north-west, north, north-east; west at the corner), its left column
-// (west, north-west) and its right column (north-east) below the top row: every pair across a tile border once
-__global__ void __launch_bounds__(128) k_line_borders(const uint8_t* __restrict__ labels, int W, int H, int m, int w, int32_t* parent_a,
-                                                      int32_t* parent_b) {
-    const int t = threadIdx.x;
-    if (t >= kLineTW + 2 * kLineTH) return;
-    int lx, ly;
-    if (t < kLineTW) { lx = t; ly = 0; }
-    else if (t < kLineTW + kLineTH) { lx = 0; ly = t - kLineTW; }
-    else { lx = kLineTW - 1; ly = t - kLineTW - kLineTH; }
-    if (t >= kLineTW && ly == 0) return;  // the corners belong to the top row
-    const int x = blockIdx.x * kLineTW + lx, y = blockIdx.y * kLineTH + ly;
-    if (x >= W || y >= H) return;
-    const int p = y * W + x;
-    const int l = labels[p];
-    if (l >= m) return;
-    const int ba = bucket_a(l, m, w), bb = bucket_b(l, m, w);
-    const bool west = lx == 0 && x > 0, north = ly == 0 && y > 0, east = x + 1 < W;
-    if (t < kLineTW) {
-        if (west) border_link(labels, W, m, w, p, ba, bb, x - 1, y, parent_a, parent_b);
-        if (north) {
-            if (x > 0) border_link(labels, W, m, w, p, ba, bb, x - 1, y - 1, parent_a, parent_b);
-            border_link(labels, W, m, w, p, ba, bb, x, y - 1, parent_a, parent_b);
-            if (east) border_link(labels, W, m, w, p, ba, bb, x + 1, y - 1, parent_a, parent_b);
-        }
-    } else if (t < kLineTW + kLineTH) {
-        if (west) {
-            border_link(labels, W, m, w, p, ba, bb, x - 1, y, parent_a, parent_b);
-            border_link(labels, W, m, w, p, ba, bb, x - 1, y - 1, parent_a, parent_b);  // (ly >= 1: the row above is the image's)
-        }
-    } else if (east) {
-        border_link(labels, W, m, w, p, ba, bb, x + 1, y - 1, parent_a, parent_b);
-    }
+__global__ void __launch_bounds__(kBorderThreads) k_line_borders(const uint8_t* __restrict__ labels, int W, int H, LineKeys keys, int32_t* parent) {
+    uf_border_merge(keys, labels, W, H, parent);
 }
 
 // ------------------------------------------------------------------------------------------ numbering
@@ -308,10 +220,6 @@ __global__ void __launch_bounds__(256) k_line_fit(int nc, LineComps c, const int
 
 // ------------------------------------------------------------------------------------------ host
 namespace {
-struct LineScratch {
-    DevBuf image, labels, keys, parent, counts, comps, out;
-    ~LineScratch() { for (DevBuf* b : {&image, &labels, &keys, &parent, &counts, &comps, &out}) b->release(); }
-};
 // The events of a call, for fdcm_lines_last_timing: one behind every stage, and one in front of the two stages that follow host
 // work (a count read back, buffers sized by it), so that a stage's time is its kernels' alone.
 enum Mark { kStart, kEdges, kTiles, kBorders, kNumber, kSumsBegin, kSums, kVotes, kKeep, kFitBegin, kFit, kMarks };
@@ -335,7 +243,7 @@ int read_int(const int* device_word) {
 }
 
 // labels (device, packed rows) -> segments on the host; marks are taken on the null stream, where everything runs
-void lines_of_device_labels(LineScratch& s, StageClock& clk, const uint8_t* labels, int W, int H, int m, const fdcm_line_params& lp,
+void lines_of_device_labels(PixelScratch& s, StageClock& clk, const uint8_t* labels, int W, int H, int m, const fdcm_line_params& lp,
                             float** lines, int64_t* n_lines) {
     *lines = nullptr; *n_lines = 0;
     const int n = W * H, nb = (n + kLineBlock - 1) / kLineBlock;
@@ -345,10 +253,11 @@ void lines_of_device_labels(LineScratch& s, StageClock& clk, const uint8_t* labe
     // block counts of the pixels' scan and of the components' (at most 2 n components, 256 per block), a total behind each
     s.counts.reserve(((size_t)nb + 1 + (2 * (size_t)n + 255) / 256 + 1) * sizeof(int));
     int* counts = s.counts.as<int>();
-    const dim3 tiles((unsigned)((W + kLineTW - 1) / kLineTW), (unsigned)((H + kLineTH - 1) / kLineTH));
-    hipLaunchKernelGGL(k_line_tiles, tiles, dim3(256), 0, nullptr, labels, W, H, m, lp.bucket, pa, pb);
+    const dim3 tiles = uf_tile_grid(W, H);
+    const LineKeys keys{m, lp.bucket};
+    hipLaunchKernelGGL(k_line_tiles, tiles, dim3(256), 0, nullptr, labels, W, H, keys, pa);
     clk.mark(kTiles);
-    hipLaunchKernelGGL(k_line_borders, tiles, dim3(128), 0, nullptr, labels, W, H, m, lp.bucket, pa, pb);
+    hipLaunchKernelGGL(k_line_borders, tiles, dim3(kBorderThreads), 0, nullptr, labels, W, H, keys, pa);
     clk.mark(kBorders);
     hipLaunchKernelGGL(k_line_roots, dim3((unsigned)nb), dim3(256), 0, nullptr, n, pa, pb, counts);
     hipLaunchKernelGGL(k_line_scan, dim3(1), dim3(256), 0, nullptr, counts, nb);
@@ -409,15 +318,10 @@ void lines_last_timing(fdcm_lines_timing* out) { *out = g_last_timing; }
 void lines_from_labels_host(int device, const uint8_t* labels, int width, int height, bool on_device, int m, const fdcm_line_params& lp,
                             float** lines, int64_t* n_lines) {
     FDCM_HIP(hipSetDevice(device));
-    LineScratch s;
+    PixelScratch s;
     StageClock clk;
-    const size_t n = (size_t)width * height;
-    const uint8_t* d = labels;
-    if (!on_device) {
-        s.labels.reserve(n);
-        FDCM_HIP(hipMemcpy(s.labels.p, labels, n, hipMemcpyHostToDevice));
-        d = s.labels.as<uint8_t>();
-    }
+    int stride = width;
+    const uint8_t* d = s.upload(labels, width, height, stride, on_device, nullptr);
     clk.mark(kEdges);  // (no edge stage)
     lines_of_device_labels(s, clk, d, width, height, m, lp, lines, n_lines);
     finish_timing(clk, false, *n_lines);
@@ -428,22 +332,15 @@ void lines_from_image_host(int device, const uint8_t* image, int width, int heig
     std::vector<float> keys;
     plan_keys(depth, keys);
     FDCM_HIP(hipSetDevice(device));
-    LineScratch s;
+    PixelScratch s;
     StageClock clk;
     const size_t n = (size_t)width * height;
-    const uint8_t* d = image;
-    int stride = row_stride;
-    if (!on_device) {
-        s.image.reserve(n);
-        FDCM_HIP(hipMemcpy2D(s.image.p, (size_t)width, image, (size_t)row_stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
-        d = s.image.as<uint8_t>(); stride = width;
-    }
-    s.labels.reserve(n); s.keys.reserve(keys.size() * sizeof(float));
+    const uint8_t* d = s.upload(image, width, height, row_stride, on_device, &keys);
+    s.labels.reserve(n);
     s.comps.reserve(n * 8);  // the edge kernels' parent and root words; the components' sums take their place afterwards
-    FDCM_HIP(hipMemcpy(s.keys.p, keys.data(), keys.size() * sizeof(float), hipMemcpyHostToDevice));
     clk.mark(kStart);
-    launch_edge_labels_ex(nullptr, d, width, height, stride, s.keys.as<float>(), (int)keys.size(), e, s.labels.as<uint8_t>(),
-                          s.comps.as<int32_t>(), s.comps.as<uint32_t>() + n);
+    launch_edge_labels(nullptr, d, width, height, row_stride, s.keys.as<float>(), (int)keys.size(), e, s.labels.as<uint8_t>(),
+                       s.comps.as<int32_t>(), s.comps.as<uint32_t>() + n);
     clk.mark(kEdges);
     lines_of_device_labels(s, clk, s.labels.as<uint8_t>(), width, height, (int)keys.size(), lp, lines, n_lines);
     finish_timing(clk, true, *n_lines);

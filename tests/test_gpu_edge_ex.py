@@ -1,6 +1,6 @@
 """Edges with smoothing, hysteresis and a minimum chain length on the GPU (include/fdcm.h) against tests/edge_ex_ref.py: label
-images over the sizes that matter to the 64 x 16 tile, the serpentines, the identity with the single-threshold kernel, volumes,
-rebuilds on one handle, device input and the blank image.  Every comparison is on bytes."""
+images over the sizes that matter to the 64 x 16 tile, the serpentines, an edge that leaves its tiles diagonally, the identity with
+the single-threshold kernel, volumes, rebuilds on one handle, device input and the blank image.  Every comparison is on bytes."""
 import ctypes as C
 import functools
 
@@ -121,6 +121,35 @@ def test_serpentines(width, height, ramp, smooth):
     for view in (img, strided(img)):
         got = openfdcm_amd.edge_labels(view, depth=30, threshold=100, low=20, smooth=smooth)
         assert np.array_equal(got, want), (int((got != 255).sum()), n)
+
+
+def diagonal_step(width, height, mirrored):
+    """70 left of and on the line x = y, max(80, 130 - 2 y) right of it: one edge that leaves every tile it crosses through a
+    corner or a side, strong only where the step is high, in the first rows."""
+    y, x = np.mgrid[0:height, 0:width]
+    img = np.where(x <= y, 70, np.maximum(80, 130 - 2 * y)).astype(np.uint8)
+    return np.ascontiguousarray(img[:, ::-1]) if mirrored else img
+
+
+@pytest.mark.parametrize("smooth", [0, 1])
+@pytest.mark.parametrize("mirrored", [False, True], ids=["diagonal", "mirrored"])
+@pytest.mark.parametrize("width,height", [(130, 200), (200, 200)], ids=lambda v: str(v))
+def test_diagonal_edge_across_tile_corners(width, height, mirrored, smooth):
+    """The whole chain hangs on strong pixels in one corner of the image, through links that cross tile borders diagonally."""
+    import openfdcm_amd
+    img = diagonal_step(width, height, mirrored)
+    edge, cand, strong, gx, gy = X.edge_mask(img, smooth, 20, 100, 1)
+    ys, xs = np.nonzero(edge)
+    assert X.components(cand)[1] == 1 and np.array_equal(edge, cand)          # one chain, kept whole
+    assert len(ys) == {130: (257, 258), 200: (397, 398)}[width][smooth]
+    assert len(set(zip(ys // 16, xs // 64))) == {130: 11, 200: 16}[width]     # the 64 x 16 tiles it crosses
+    sy, sx = np.nonzero(strong)
+    assert len(sy) > 0 and sy.max() < 32 and ys.max() >= min(width, height) - 2  # strong in the first two tile rows only
+    assert (sx.min() >= width - 64) if mirrored else (sx.max() < 64)
+    want = X.labels_of(edge, gx, gy, 30)
+    for view in (img, strided(img)):
+        got = openfdcm_amd.edge_labels(view, depth=30, threshold=100, low=20, smooth=smooth, min_pixels=1)
+        assert np.array_equal(got, want), (int((got != 255).sum()), len(ys), np.argwhere(got != want)[:5])
 
 
 @pytest.mark.parametrize("width,height", [(48, 40), (97, 61), (130, 200), (700, 9)], ids=lambda v: str(v))
