@@ -440,6 +440,41 @@ int fdcm_search_exhaustive_rotations(const fdcm_featuremap* fm, const fdcm_templ
 int fdcm_score_map_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
                              const fdcm_grid* grid, float* out_host);
 
+/* Pose windows: a list of jobs for refinement (a small box of fine poses around each coarse peak) and tracking (a small box
+ * around the last frame's pose).  A job is one template, a run of rotations of the table `rot` (n rotations) and a small
+ * translation grid of its own, searched exhaustively.  Job j has the grid G_j = (x0, y0, nx, ny, sx, sy) with the call's
+ * strides and N_j = nx ny points; position e of its run is rotation a = (a0 + e) mod n.  score, admissibility and the NaN
+ * rule are those of fdcm_search_exhaustive_rotations for template tmpl, rotation a, pivot pivots[tmpl] and grid point
+ * g = jj nx + ii of G_j; key(e, g) = (score bits << 32) | (e N_j + g).
+ * Output: the jobs in the order given; per job its admissible (e, g) ordered by key, the first min(k, count) of them
+ * (1 <= k <= 64), as records {tmpl + tmpl_index_base, score, {c, -s, m.x + t.x, s, c, m.y + t.y}} of rotation a.
+ * job_offsets (n_jobs + 1 values, or NULL): the records of job j are job_offsets[j] .. job_offsets[j + 1].  A job whose
+ * template has no lines gives nothing, as does a job without an admissible point; duplicate jobs give duplicate records.
+ * rot == NULL is the translations only: the table is one rotation, every job must have a0 = 0 and na = 1, the lines are
+ * scored as they are (not passed through an identity rotation, which would turn a -0 coordinate into +0) and the records
+ * are fdcm_search_exhaustive's {1, 0, t.x, 0, 1, t.y}.
+ * By definition job j's records are those of fdcm_search_exhaustive_rotations on the one-template set {tmpl} with that
+ * template's pivot, the rotations of the run in run order, the grid G_j, rx = ry = ra = 0 and base tmpl + tmpl_index_base;
+ * with rot == NULL those of fdcm_search_exhaustive.
+ * FDCM_EINVAL, before any GPU work: jobs NULL with n_jobs > 0, n_jobs < 0; tmpl outside the set; na < 1 or na > n; a0
+ * outside 0 .. n - 1; a0 + na > n with wrap = 0 (wrap = 1: the run continues at rotation 0); nx or ny < 1;
+ * na nx ny > 65536 (a larger search is the dense call's); a grid point with |t| >= 2^24; sx or sy < 1; k outside 1 .. 64;
+ * wrap not 0 or 1; and whatever fdcm_search_exhaustive_rotations rejects about rot.  n_jobs = 0, an empty feature map or an
+ * empty template list give zero records and job_offsets all 0.  Device memory stays below 1 GB however many jobs there
+ * are: the list is worked through in parts.  One job is never cut, and the rotated lines of its run go up together, na x
+ * the template's lines x 32 bytes, as the dense call uploads those of all its rotations: only a job of tens of thousands
+ * of rotations of a template of hundreds of lines comes near that bound.  The call blocks; concurrent callers of one
+ * feature map take turns.  Release with fdcm_matches_free. */
+typedef struct fdcm_pose_window {
+    int32_t tmpl;           /* template index, 0 .. n_templates - 1 */
+    int32_t a0, na;         /* the run of rotations a0, a0 + 1, .., a0 + na - 1 of the table (mod n when wrap = 1) */
+    int32_t x0, y0, nx, ny; /* this job's translation grid, with the call's strides */
+} fdcm_pose_window;
+int fdcm_search_exhaustive_windows(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                   const fdcm_pose_window* jobs, int64_t n_jobs, int32_t sx, int32_t sy, int32_t wrap,
+                                   int32_t k, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                   int64_t* job_offsets /* n_jobs + 1, or NULL */);
+
 /* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
  *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as
  *      fdcm_edge_labels makes it (m = the distinct keys of `depth`, a byte < m an edge pixel of that label, labels circular)

@@ -607,4 +607,79 @@ def rotation_score_map(featuremap, templates, angles, stride=1, pivot="center", 
         return _np.zeros((tset.count, cs.shape[0], g[3], g[2]), dtype=_np.float32), g
     return fm.rotation_score_map(tset, g, cs, pv), g
 
+
+# ---------------------------------------------------------------- pose windows: refinement and tracking (extension)
+def template_pivots(templates, pivot="center"):
+    """The (T, 2) float32 pivots the rotation searches use for pivot="center" (each template's bounding box centre), an
+    explicit (T, 2) array as it is, or None for the origin: what pose_windows needs to read a record's translation."""
+    return _pivots(templates, pivot, len(templates))
+
+
+def exhaustive_window_search(featuremap, templates, jobs, angles=None, stride=1, k=1, pivot="center", wrap=False,
+                             tmpl_index_base=0):
+    """A list of small exhaustive searches in one call: coarse-to-fine refinement and tracking.  jobs is an (n, 7) int32
+    array of rows (tmpl, a0, na, x0, y0, nx, ny): template tmpl, the run of angles a0 .. a0 + na - 1 of `angles` (mod
+    len(angles) with wrap) and the translations (x0 + i sx, y0 + j sy), 0 <= i < nx, 0 <= j < ny, with na nx ny <= 65536.
+    Per job, in the order given, its k best poses (1 <= k <= 64) by (score, position in the run, grid index): exactly what
+    exhaustive_rotation_search(radius=0, angle_radius=0) returns for that template, those angles and that window alone.
+    angles and pivot are exhaustive_rotation_search's; angles=None searches translations only (a0 = 0, na = 1) and returns
+    exhaustive_search's pure translations.  Returns (MatchList, offsets): job j's matches are offsets[j] .. offsets[j + 1]."""
+    sx, sy = _strides(stride)
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates)
+    cs = pv = None
+    if angles is not None:
+        cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
+    rec, offsets = fm.exhaustive_window_search(tset, jobs, cs, pv, sx=sx, sy=sy, wrap=wrap, k=k, tmpl_index_base=tmpl_index_base)
+    return MatchList(rec), offsets
+
+
+def pose_windows(records, coarse_angles, fine_angles, pivots, half_angles, half_x, half_y, stride=1, wrap=False):
+    """Jobs for exhaustive_window_search around detections: pure numpy.  records: the matches of
+    exhaustive_rotation_search over coarse_angles (a MatchList or its record array, tmpl_idx without a base); pivots: the
+    (T, 2) pivots of that search (template_pivots) or None for the origin.  Per record, one row (tmpl, a0, na, x0, y0, nx,
+    ny) on the table fine_angles:
+      - the coarse angle is the index whose (float32(cos), float32(sin)) equal (transform[0], transform[3]) exactly;
+      - the translation is t = rint(float64(transform[2]) - float64(m.x)), likewise y, m the record's float32 offset
+        p - R p.  transform[2] is float32(m.x + t.x): the difference is t within half a float32 ulp of transform[2], so
+        the result is exact while |transform[2]|, |transform[5]| < 2^22 -- any pose on a map of 4096 x 4096 and beyond;
+      - the centre of the run is the fine angle nearest the coarse one on the circle (the lowest index on a tie), the run
+        centre - half_angles .. centre + half_angles, cut at 0 and len(fine_angles) - 1, or circular with wrap (a0 taken
+        mod the table, at most the whole table);
+      - the window holds the multiples of stride (an int or (sx, sy)) from the last one <= t - half to the first one
+        >= t + half on each axis: 2 half + 1 points around t at stride 1."""
+    rec = records.records() if isinstance(records, MatchList) else _np.asarray(records)
+    sx, sy = _strides(stride)
+    coarse, fine = _angles(coarse_angles), _np.asarray(fine_angles, dtype=_np.float64).reshape(-1)
+    ca = _np.asarray(coarse_angles, dtype=_np.float64).reshape(-1)
+    n, ha = fine.shape[0], int(half_angles)
+    if n < 1 or ha < 0 or int(half_x) < 0 or int(half_y) < 0 or sx < 1 or sy < 1:
+        raise ValueError("pose_windows: an empty fine table, a negative half width or a stride below 1")
+    jobs = _np.zeros((rec.shape[0], 7), dtype=_np.int32)
+    two_pi = 2 * _np.pi
+    pv = None if pivots is None else _np.asarray(pivots, dtype=_np.float32)
+    for q in range(rec.shape[0]):
+        tr, t = rec["transform"][q], int(rec["tmpl_idx"][q])
+        hit = _np.nonzero((coarse[:, 0] == tr[0]) & (coarse[:, 1] == tr[3]))[0]
+        if hit.size == 0:
+            raise ValueError(f"pose_windows: record {q} has a rotation that is none of coarse_angles")
+        c, s = coarse[hit[0]]
+        px, py = (_np.float32(0), _np.float32(0)) if pv is None else pv[t]
+        ns = -s
+        mx, my = px - (c * px + ns * py), py - (s * px + c * py)  # float32, left to right: the library's M_a
+        tx = int(_np.rint(_np.float64(tr[2]) - _np.float64(mx)))
+        ty = int(_np.rint(_np.float64(tr[5]) - _np.float64(my)))
+        d = _np.abs((fine - ca[hit[0]] + _np.pi) % two_pi - _np.pi)
+        centre = int(_np.argmin(d))
+        if wrap:
+            a0, na = (centre - ha) % n, min(2 * ha + 1, n)
+        else:
+            a0 = max(0, centre - ha)
+            na = min(n - 1, centre + ha) - a0 + 1
+        x0, y0 = (tx - int(half_x)) // sx * sx, (ty - int(half_y)) // sy * sy
+        nx, ny = -((x0 - tx - int(half_x)) // sx) + 1, -((y0 - ty - int(half_y)) // sy) + 1
+        jobs[q] = (t, a0, na, x0, y0, nx, ny)
+    return jobs
+
+
 from .lineio import read, write  # noqa: E402  (.lines/.scene/.tmpl files, serialization.h)

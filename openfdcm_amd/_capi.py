@@ -55,6 +55,16 @@ class Rotations(C.Structure):
     _fields_ = [("cs", C.POINTER(C.c_float)), ("n", C.c_int32), ("pivots", C.POINTER(C.c_float))]
 
 
+class PoseWindow(C.Structure):
+    """fdcm_pose_window: one job of fdcm_search_exhaustive_windows: a template, a run of rotations, a translation grid."""
+    _fields_ = [("tmpl", C.c_int32), ("a0", C.c_int32), ("na", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32),
+                ("nx", C.c_int32), ("ny", C.c_int32)]
+
+
+POSE_WINDOW_DTYPE = np.dtype([(n, "<i4") for n in ("tmpl", "a0", "na", "x0", "y0", "nx", "ny")])
+assert POSE_WINDOW_DTYPE.itemsize == C.sizeof(PoseWindow) == 28
+
+
 class EdgeParams(C.Structure):
     """fdcm_edge_params: smoothing (0, 1, 2), the low and high thresholds and the smallest component kept."""
     _fields_ = [("smooth", C.c_int32), ("low", C.c_int32), ("high", C.c_int32), ("min_pixels", C.c_int32)]
@@ -156,6 +166,8 @@ SYMBOLS = [
     ("fdcm_search_exhaustive_rotations", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int32, C.c_int32,
                                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp), _i64p]),
     ("fdcm_score_map_rotations", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), _fp]),
+    ("fdcm_search_exhaustive_windows", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(PoseWindow), C.c_int64, C.c_int32,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp), _i64p, _i64p]),
     ("fdcm_score_map_device", C.c_int, [_vp, _vp, C.POINTER(Grid), _vp]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),

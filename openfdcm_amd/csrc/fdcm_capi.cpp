@@ -724,6 +724,52 @@ int fdcm_search_exhaustive_rotations(const fdcm_featuremap* fm, const fdcm_templ
     });
 }
 
+// Pose windows: include/fdcm.h, "Pose windows".  Everything that needs no handle is checked first, the jobs' templates
+// against the set last: nothing here touches the device.
+static void check_pose_windows(const fdcm_pose_window* jobs, int64_t n_jobs, int32_t n, int32_t sx, int32_t sy, int32_t wrap) {
+    const int64_t lim = (int64_t)1 << 24;
+    for (int64_t j = 0; j < n_jobs; ++j) {
+        const fdcm_pose_window& J = jobs[j];
+        require(J.tmpl >= 0, "jobs: tmpl is outside the template set");
+        require(J.na >= 1 && J.na <= n, "jobs: na must be in [1, n]");
+        require(J.a0 >= 0 && J.a0 < n, "jobs: a0 must be in [0, n - 1]");
+        require(wrap == 1 || (int64_t)J.a0 + J.na <= n, "jobs: a0 + na must be at most n without wrap");
+        require(J.nx >= 1 && J.ny >= 1, "jobs: nx and ny must be >= 1");
+        require(J.nx <= 65536 && J.ny <= 65536 && (int64_t)J.na * J.nx * J.ny <= 65536, "jobs: na * nx * ny must be at most 65536");
+        const int64_t xe = (int64_t)J.x0 + (int64_t)(J.nx - 1) * sx, ye = (int64_t)J.y0 + (int64_t)(J.ny - 1) * sy;
+        require(J.x0 > -lim && xe < lim && J.y0 > -lim && ye < lim, "jobs: every translation must satisfy |t| < 2^24");
+    }
+}
+
+int fdcm_search_exhaustive_windows(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                   const fdcm_pose_window* jobs, int64_t n_jobs, int32_t sx, int32_t sy, int32_t wrap, int32_t k,
+                                   int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out, int64_t* job_offsets) {
+    return guarded([&] {
+        require(k >= 1 && k <= 64, "k must be in [1, 64]");
+        require(sx >= 1 && sy >= 1, "strides sx and sy must be >= 1");
+        require(wrap == 0 || wrap == 1, "wrap must be 0 or 1");
+        require(n_jobs >= 0 && (n_jobs == 0 || jobs), "jobs is null or n_jobs is negative");
+        if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
+        check_pose_windows(jobs, n_jobs, rot ? rot->n : 1, sx, sy, wrap);
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        require(out && n_out, "null output");
+        if (rot) check_pivots(templates, rot);
+        for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
+            require(jobs[j].tmpl < templates->T, "jobs: tmpl is outside the template set");
+        *out = nullptr;
+        try {
+            run_search_exhaustive_windows(const_cast<fdcm_featuremap*>(fm), templates, rot, jobs, n_jobs, sx, sy, k, tmpl_index_base, out,
+                                          n_out, job_offsets);
+        } catch (...) {
+            result_release(*out);
+            *out = nullptr;
+            throw;
+        }
+        if (!*out) *out = result_acquire(sizeof(fdcm_match));  // no records: an empty (non-null) array
+    });
+}
+
 int fdcm_score_map_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
                              const fdcm_grid* grid, float* out_host) {
     return guarded([&] {

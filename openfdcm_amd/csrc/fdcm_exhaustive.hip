@@ -11,6 +11,8 @@
 //                                     key is the minimum of its window to a per-wave k-best list; ANGLES: the window spans
 //                                     several angles' planes (64-bit keys in LDS), else one plane (32-bit score bits)
 //   k_exhaustive_merge_groups         one wave per template of a batch: its merged list so far and its units' lists
+//   k_exhaustive_windows<BUF32>       pose windows: a wave takes a run of 4 x 16 patches of the clipped boxes of a batch's
+//                                     (job, rotation) planes, a lane per translation, and keeps a k-best list per job
 //
 // Keys of the top-k are (score bits << 32) | grid index: scores are >= +0 (+inf included), so the key order is the
 // (score, g) order, which is total -- the result does not depend on which wave saw which point first.  A NaN score has
@@ -386,6 +388,109 @@ __global__ void __launch_bounds__(256) k_exhaustive_merge_groups(const unsigned 
     if (lane < k) b[lane] = e;
 }
 
+// ---- pose windows (include/fdcm.h, "Pose windows"): a list of jobs, each one template, a run of rotations and a small grid
+// of its own.  A plane is one (job, run position e) whose admissible box, clipped to the job's grid, is not empty; the host
+// cuts every plane's clipped box into patches of 4 (i) x 16 (j) grid points and lists them, job by job, in one table.  Wave w
+// of a launch takes the patches [w ipw, (w + 1) ipw) of the table, a lane per point (lane & 3 along i, lane >> 2 along j: at
+// stride 1 the 64 reads of one line end are 16 rows of 4 columns, whole 256-byte runs of the volume when the column is a
+// multiple of 4).  Nothing exists for the part of a window outside the box.  The plane and its lines are wave-uniform and
+// come through scalar loads.  A wave keeps the sorted k-best list of the job it is in (list_offer) and writes it when the
+// job changes: the waves that hold patches of job j are consecutive, wave0 .. wave0 + lists - 1, and wave w's list of job j
+// is candidate list list0 + (w - wave0), so k_exhaustive_merge_groups folds a job's lists as one group.
+struct WinPlane {
+    int line0, n;        // its lines in the line array
+    int i0, i1, j0, j1;  // the admissible box clipped to the job's grid, in grid indices (never empty)
+    int x0, y0, nx;      // the job's grid: origin and points per row
+    unsigned koff;       // e * N_j, added to the grid index of its keys
+    int job;             // the job's place in the batch
+    int pad;
+};
+struct WinJob { int wave0, list0; };
+constexpr int kPatchX = 4, kPatchY = 16;
+
+// evaluate at one translation per lane: k_exhaustive's sum (pair_score's order) with one row per lane
+template <bool BUF32>
+__device__ __forceinline__ float window_score(const VolRef& V, const ExLine* __restrict__ Lt, int n, float offx, float offy, int W,
+                                              unsigned uH, size_t SL) {
+    const int aligned2 = (n / 8) * 8, aligned = (n / 4) * 4;
+    float p0[4] = {0.f, 0.f, 0.f, 0.f}, p1[4] = {0.f, 0.f, 0.f, 0.f};  // 0 + v == v for v >= +0
+    for (int b = 0; b < aligned2; b += 8) {
+        float va[8], vb[8];
+#pragma unroll
+        for (int l = 0; l < 8; ++l) {
+            const ExLine ln = Lt[b + l];
+            va[l] = ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL), (int)(ln.y1 + offy), uH);
+            vb[l] = ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL), (int)(ln.y2 + offy), uH);
+        }
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            p0[l] = p0[l] + f_abs(va[l] - vb[l]);
+            p1[l] = p1[l] + f_abs(va[l + 4] - vb[l + 4]);
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 4; ++l) p0[l] = p0[l] + p1[l];
+    if (aligned > aligned2) {  // the trailing packet
+        float va[4], vb[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const ExLine ln = Lt[aligned2 + l];
+            va[l] = ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL), (int)(ln.y1 + offy), uH);
+            vb[l] = ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL), (int)(ln.y2 + offy), uH);
+        }
+#pragma unroll
+        for (int l = 0; l < 4; ++l) p0[l] = p0[l] + f_abs(va[l] - vb[l]);
+    }
+    float res = 0.f;
+    if (aligned) res = (p0[0] + p0[2]) + (p0[1] + p0[3]);  // predux
+    for (int idx = aligned; idx < n; ++idx) {              // the scalar tail, in order
+        const ExLine ln = Lt[idx];
+        res = res + f_abs(ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL), (int)(ln.y1 + offy), uH) -
+                          ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL), (int)(ln.y2 + offy), uH));
+    }
+    return res;
+}
+
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_exhaustive_windows(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
+                                                            float ty, const ExLine* __restrict__ lines,
+                                                            const WinPlane* __restrict__ planes, const int2* __restrict__ items,
+                                                            const WinJob* __restrict__ jobs, int n_items, int ipw, int sx, int sy,
+                                                            int k, unsigned long long* __restrict__ cand) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    const int it0 = w * ipw, it1 = min(n_items, it0 + ipw);
+    if (it0 >= it1) return;  // wave-uniform
+    const VolRef V = make_volref(vol, SL, m, BUF32);
+    const unsigned uH = (unsigned)H;
+    unsigned long long e = kNoKey, thr = kNoKey;
+    int job = -1;
+    auto flush = [&]() {
+        const WinJob J = jobs[job];
+        if (lane < k) cand[(long long)(J.list0 + (w - J.wave0)) * k + lane] = e;
+    };
+    for (int it = it0; it < it1; ++it) {
+        const int2 I = items[it];  // x: the plane, y: the patch in its clipped box, pj << 16 | pi
+        const WinPlane P = planes[I.x];
+        if (P.job != job) {
+            if (job >= 0) flush();
+            job = P.job;
+            e = thr = kNoKey;
+        }
+        const int i = P.i0 + (I.y & 0xffff) * kPatchX + (lane & 3), j = P.j0 + (int)((unsigned)I.y >> 16) * kPatchY + (lane >> 2);
+        // a lane outside the clipped box reads at the box's corner, which is admissible: every read stays inside the volume
+        const bool act = i <= P.i1 && j <= P.j1;
+        const float offx = tx + (float)(P.x0 + (act ? i : P.i0) * sx);  // translate(tmpl, sceneTranslation + translation)
+        const float offy = ty + (float)(P.y0 + (act ? j : P.j0) * sy);
+        const float res = window_score<BUF32>(V, lines + P.line0, P.n, offx, offy, W, uH, SL);
+        const unsigned long long key = act && !(res != res)  // a NaN score has no key
+                                           ? ((unsigned long long)__float_as_uint(res) << 32) | ((unsigned)(j * P.nx + i) + P.koff)
+                                           : kNoKey;
+        thr = list_offer(e, key, thr, k, lane);
+    }
+    flush();
+}
+
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // The integer translations t in [-kMaxCoord, kMaxCoord] with lo < fl(p + fl(off + t)) < hi for p = pmin and p = pmax, i.e.
@@ -454,19 +559,20 @@ struct Prepared {
     size_t SL = 0;
 };
 
-// closestOrientation of every template line with the host libm (dt3cpu.cpp:144-148, as fdcm_seam.hip's run_evaluate) and
-// the admissible box of every template in grid indices.
+// One line for the kernels: closestOrientation with the host libm (dt3cpu.cpp:144-148, as fdcm_seam.hip's run_evaluate).
+ExLine line_record(const fdcm_featuremap* fm, const float* p, bool buf32, size_t SL) {
+    const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
+    const int bin = closest_orientation(fm->keys.data(), (int)fm->m, angle);
+    return ExLine{p[0], p[1], p[2], p[3], buf32 ? (int)((unsigned)bin * (unsigned)SL) : bin, 0, 0, 0};
+}
+
+// line_record of every template line and the admissible box of every template in grid indices.
 void prepare(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, Prepared& P) {
     P.SL = ivol_slice_floats(fm->W, fm->H);
     P.buf32 = (size_t)fm->m * P.SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
     P.lines.resize((size_t)std::max<int64_t>(1, t->n_lines));
     if (t->n_lines > 0x7fffffffll) throw std::string("too many template lines for one exhaustive search");
-    for (int64_t q = 0; q < t->n_lines && fm->m > 0; ++q) {
-        const float* p = &t->lines[(size_t)q * 4];
-        const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
-        const int bin = closest_orientation(fm->keys.data(), (int)fm->m, angle);
-        P.lines[(size_t)q] = ExLine{p[0], p[1], p[2], p[3], P.buf32 ? (int)((unsigned)bin * (unsigned)P.SL) : bin, 0, 0, 0};
-    }
+    for (int64_t q = 0; q < t->n_lines && fm->m > 0; ++q) P.lines[(size_t)q] = line_record(fm, &t->lines[(size_t)q * 4], P.buf32, P.SL);
     P.tm.resize((size_t)t->T);
     for (int64_t i = 0; i < t->T; ++i) {
         const int64_t l0 = t->offsets[(size_t)i], n = t->offsets[(size_t)i + 1] - l0;
@@ -567,27 +673,18 @@ void check_rotated_size(const fdcm_templates* t, int n) {
         throw std::string("too many rotated templates or template lines for one call");
 }
 
-// prepare() of the rotated set of all templates: P.tm[t * n + a] is (t, a), M its transforms.  The rotation, bins (host
-// atan) and admissible boxes run in up to 16 threads over ranges of templates, each of about 2^12 rotated lines or more.
-void prepare_rotated(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g, Prepared& P,
-                     std::vector<RotM>& M) {
-    const int n = rot.n;
-    check_rotated_size(t, n);
-    M.resize((size_t)(t->T * n));
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({16, t->T, (t->n_lines * n) >> 12}));
-    std::vector<int64_t> cut((size_t)nth + 1);
-    for (int c = 0; c <= nth; ++c) cut[(size_t)c] = t->T * c / nth;
-    std::vector<Prepared> part((size_t)nth);
+// part(c) for every c < nth, on nth threads (on the caller's when nth is 1).  A part that throws stops alone; the first
+// error is thrown again after all have joined (`what`: the message of an error that is not the library's own).
+template <class F>
+void on_threads(int nth, const char* what, F part) {
     std::vector<std::string> err((size_t)nth);
     auto job = [&](int c) {
         try {
-            fdcm_templates rt;
-            rotated_set(t, rot, cut[(size_t)c], cut[(size_t)c + 1], rt, M.data() + cut[(size_t)c] * n);
-            prepare(fm, &rt, g, part[(size_t)c]);
+            part(c);
         } catch (const std::string& e) {
             err[(size_t)c] = e;
         } catch (...) {
-            err[(size_t)c] = "host preparation of the rotated templates failed";
+            err[(size_t)c] = what;
         }
     };
     if (nth == 1) {
@@ -599,6 +696,24 @@ void prepare_rotated(const fdcm_featuremap* fm, const fdcm_templates* t, const f
     }
     for (const std::string& e : err)
         if (!e.empty()) throw e;
+}
+
+// prepare() of the rotated set of all templates: P.tm[t * n + a] is (t, a), M its transforms.  The rotation, bins (host
+// atan) and admissible boxes run in up to 16 threads over ranges of templates, each of about 2^12 rotated lines or more.
+void prepare_rotated(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g, Prepared& P,
+                     std::vector<RotM>& M) {
+    const int n = rot.n;
+    check_rotated_size(t, n);
+    M.resize((size_t)(t->T * n));
+    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({16, t->T, (t->n_lines * n) >> 12}));
+    std::vector<int64_t> cut((size_t)nth + 1);
+    for (int c = 0; c <= nth; ++c) cut[(size_t)c] = t->T * c / nth;
+    std::vector<Prepared> part((size_t)nth);
+    on_threads(nth, "host preparation of the rotated templates failed", [&](int c) {
+        fdcm_templates rt;
+        rotated_set(t, rot, cut[(size_t)c], cut[(size_t)c + 1], rt, M.data() + cut[(size_t)c] * n);
+        prepare(fm, &rt, g, part[(size_t)c]);
+    });
     P.SL = part[0].SL;
     P.buf32 = part[0].buf32;
     P.lines.clear();
@@ -618,17 +733,20 @@ void prepare_rotated(const fdcm_featuremap* fm, const fdcm_templates* t, const f
     if (P.lines.empty()) P.lines.resize(1);
 }
 
-// The records of the merged lists best[q][k] of the templates index[q]: key a N + g -> transform [R | m + (tx, ty)], R | m
-// the transform M[index[q] n + a] of the rotation search, or a pure translation when M is null.
-void emit_records(const std::vector<unsigned long long>& best, int k, const std::vector<int32_t>& index, int n, const fdcm_grid& g,
-                  int32_t base, const RotM* M, fdcm_match** out, int64_t* n_out) {
-    const int T = (int)index.size();
-    const unsigned long long N = (unsigned long long)g.nx * g.ny;
+// The records of the merged lists best[q][k], q < Q (kNoKey ends a list).  List q is template tmpl_of(q)'s on the grid
+// grid_of(q) with N = nx ny points: key a N + g -> transform [R | m + (tx, ty)], R | m = *rot_of(q, a), or the pure translation
+// when that is null.  offsets (Q + 1, or null): where each list's records begin.
+template <class TmplOf, class GridOf, class RotOf>
+void emit_records(const std::vector<unsigned long long>& best, int k, int64_t Q, TmplOf tmpl_of, GridOf grid_of, RotOf rot_of,
+                  fdcm_match** out, int64_t* n_out, int64_t* offsets) {
     int64_t cnt = 0;
     for (unsigned long long v : best) cnt += v != kNoKey;
     fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, cnt) * sizeof(fdcm_match));
     int64_t w = 0;
-    for (int q = 0; q < T; ++q)
+    for (int64_t q = 0; q < Q; ++q) {
+        if (offsets) offsets[q] = w;
+        const fdcm_grid& g = grid_of(q);
+        const unsigned long long N = (unsigned long long)g.nx * g.ny;
         for (int r = 0; r < k; ++r) {
             const unsigned long long v = best[(size_t)q * k + r];
             if (v == kNoKey) break;
@@ -638,19 +756,29 @@ void emit_records(const std::vector<unsigned long long>& best, int k, const std:
             const int i = (int)(gi % (unsigned)g.nx), j = (int)(gi / (unsigned)g.nx);
             const float tx = (float)(g.x0 + i * g.sx), ty = (float)(g.y0 + j * g.sy);
             fdcm_match& rec = m[w++];
-            rec.tmpl_idx = base + index[(size_t)q];
+            rec.tmpl_idx = tmpl_of(q);
             rec.score = f_from_bits((uint32_t)(v >> 32));
-            if (M) {  // combine(translation, M_a), float32 adds
-                const RotM& R = M[(size_t)index[(size_t)q] * n + a];
-                rec.transform[0] = R.c; rec.transform[1] = R.ns; rec.transform[2] = R.mx + tx;
-                rec.transform[3] = R.s; rec.transform[4] = R.c; rec.transform[5] = R.my + ty;
+            if (const RotM* R = rot_of(q, a)) {  // combine(translation, M_a), float32 adds
+                rec.transform[0] = R->c; rec.transform[1] = R->ns; rec.transform[2] = R->mx + tx;
+                rec.transform[3] = R->s; rec.transform[4] = R->c; rec.transform[5] = R->my + ty;
             } else {  // combine(t, identity): the transform of a pure translation (Match.transform)
                 rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = tx;
                 rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = ty;
             }
         }
+    }
+    if (offsets) offsets[Q] = w;
     *out = m;
     *n_out = cnt;
+}
+
+// The dense searches' lists: template index[q] on the one grid g, R | m the transform M[index[q] n + a] of the rotation
+// search, or a pure translation when M is null.
+void emit_records(const std::vector<unsigned long long>& best, int k, const std::vector<int32_t>& index, int n, const fdcm_grid& g,
+                  int32_t base, const RotM* M, fdcm_match** out, int64_t* n_out) {
+    emit_records(
+        best, k, (int64_t)index.size(), [&](int64_t q) { return base + index[(size_t)q]; }, [&](int64_t) -> const fdcm_grid& { return g; },
+        [&](int64_t q, int a) { return M ? &M[(size_t)index[(size_t)q] * n + a] : nullptr; }, out, n_out, nullptr);
 }
 
 constexpr size_t kMapBytes = (size_t)768 << 20;     // the score planes of one batch (peaks): translations
@@ -850,6 +978,198 @@ void search(fdcm_featuremap* fm, const Prepared& P, int n, const fdcm_grid& g, i
     FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
 }
 
+// ---- pose windows: the host driver
+// The distinct (template, rotation) pairs a run of jobs names, each prepared once: its rotated lines (RotM's rule; the
+// caller's own lines when there is no table), their bins and its admissible box in translation coordinates.
+struct WinPairs {
+    std::vector<int64_t> key;  // tmpl * n + a, ascending
+    std::vector<ExLine> lines;
+    std::vector<int> line0, nl;  // per pair: its lines
+    std::vector<Box> box;
+    std::vector<RotM> M;  // (rotations only)
+    size_t find(int64_t k) const { return (size_t)(std::lower_bound(key.begin(), key.end(), k) - key.begin()); }
+};
+
+// rotated_set, line_record and admissible_box of every pair, in up to 16 threads over ranges of pairs of about 2^12 lines
+// or more (as prepare_rotated).  Inside a range the pairs of one template are one rotated_set over their rotations.
+void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, int n, bool buf32, size_t SL,
+                   WinPairs& W) {
+    const size_t np = W.key.size();
+    W.line0.assign(np, 0);
+    W.nl.assign(np, 0);
+    W.box.assign(np, Box{false, 0, 0, 0, 0});
+    if (rot) W.M.resize(np);
+    int64_t total = 0;
+    for (int64_t k : W.key) total += t->offsets[(size_t)(k / n) + 1] - t->offsets[(size_t)(k / n)];
+    if (total > 0x7fffffffll) throw std::string("too many rotated template lines for one call");
+    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)np, total >> 12}));
+    std::vector<size_t> cut((size_t)nth + 1);
+    for (int c = 0; c <= nth; ++c) cut[(size_t)c] = np * (size_t)c / (size_t)nth;
+    std::vector<std::vector<ExLine>> part((size_t)nth);
+    on_threads(nth, "host preparation of the pose windows failed", [&](int c) {
+        std::vector<float> cs;
+        for (size_t p = cut[(size_t)c]; p < cut[(size_t)c + 1];) {
+            const int64_t i = W.key[p] / n;
+            size_t q = p;
+            cs.clear();
+            for (; q < cut[(size_t)c + 1] && W.key[q] / n == i; ++q)
+                if (rot) {
+                    const int64_t a = W.key[q] % n;
+                    cs.push_back(rot->cs[2 * a]);
+                    cs.push_back(rot->cs[2 * a + 1]);
+                }
+            fdcm_templates rt;
+            if (rot) {
+                const fdcm_rotations sub{cs.data(), (int32_t)(q - p), rot->pivots};
+                rotated_set(t, sub, i, i + 1, rt, W.M.data() + p);
+            } else {  // the caller's lines as they are (run_search_exhaustive_peaks' note on -0)
+                const int64_t l0 = t->offsets[(size_t)i], l1 = t->offsets[(size_t)i + 1];
+                rt.T = 1;
+                rt.n_lines = l1 - l0;
+                rt.lines.assign(t->lines.begin() + 4 * l0, t->lines.begin() + 4 * l1);
+                rt.offsets = {0, l1 - l0};
+            }
+            for (size_t u = p; u < q; ++u) {
+                const int64_t l0 = rt.offsets[u - p], nl = rt.offsets[u - p + 1] - l0;
+                W.line0[u] = (int)part[(size_t)c].size();
+                W.nl[u] = (int)nl;
+                W.box[u] = admissible_box(fm, &rt, l0, nl);
+                for (int64_t x = l0; x < l0 + nl && fm->m > 0; ++x)
+                    part[(size_t)c].push_back(line_record(fm, &rt.lines[(size_t)x * 4], buf32, SL));
+                if (fm->m <= 0) W.box[u].any = false;
+            }
+            p = q;
+        }
+    });
+    W.lines.clear();
+    W.lines.reserve((size_t)std::max<int64_t>(1, total));
+    for (int c = 0; c < nth; ++c) {
+        for (size_t u = cut[(size_t)c]; u < cut[(size_t)c + 1]; ++u) W.line0[u] += (int)W.lines.size();
+        W.lines.insert(W.lines.end(), part[(size_t)c].begin(), part[(size_t)c].end());
+    }
+    if (W.lines.empty()) W.lines.resize(1);
+}
+
+constexpr int kWinPlanes = 65536;       // planes of a batch, at most (a batch always takes one job)
+constexpr int kWinItems = 1 << 20;      // patches of a batch, at most (a job has 2^16 at most)
+constexpr int kWinWaves = 16384;        // waves of a launch, about: twice what is resident at 8 waves per SIMD
+constexpr size_t kWinStageBytes = (size_t)256 << 20;  // what one upload holds, about: longer job lists go in rounds
+
+// The jobs [j0, j1) of a call: their pairs prepared, their planes cut into batches, one upload, two kernels per batch and
+// the download of the jobs' merged lists into best[j0 k ..].  Mjob[m0[j] + e]: the transform of job j's run position e.
+void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs, int64_t j0,
+                   int64_t j1, int sx, int sy, int k, unsigned long long* best, const std::vector<int64_t>& m0, std::vector<RotM>& Mjob) {
+    const int n = rot ? rot->n : 1;
+    const size_t SL = ivol_slice_floats(fm->W, fm->H);
+    const bool buf32 = !test_switches().windows_flat && (size_t)fm->m * SL * sizeof(float) < ((size_t)1 << 32);
+    WinPairs W;
+    for (int64_t j = j0; j < j1; ++j)
+        for (int e = 0; e < jobs[j].na; ++e) W.key.push_back((int64_t)jobs[j].tmpl * n + (jobs[j].a0 + e) % n);
+    std::sort(W.key.begin(), W.key.end());
+    W.key.erase(std::unique(W.key.begin(), W.key.end()), W.key.end());
+    prepare_pairs(fm, t, rot, n, buf32, SL, W);
+
+    // Batches of whole jobs.  Per batch: its planes and their patches (job by job, run position by run position, a box's
+    // patches along j first), per job with patches its first wave and candidate list, and its group for the merge
+    // (x: first list, y: lists, z: the job's merged list).
+    struct Batch { size_t p0, i0, b0, s0; int items, jobs, groups, ipw, waves, lists; };
+    std::vector<Batch> batches;
+    std::vector<WinPlane> planes;
+    std::vector<int2> items;
+    std::vector<WinJob> jtab;
+    std::vector<int4> seg;
+    struct Span { int first, count, job; };
+    std::vector<Span> span;  // per job of the open batch: its first patch, its patches, its place in the round
+    const int cap = test_switches().windows_batch > 0 ? test_switches().windows_batch : kWinPlanes;
+    Batch cur{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int cur_planes = 0;
+    size_t max_lists = 1;
+    auto close = [&]() {
+        if (cur.items > 0) {
+            cur.ipw = std::max(1, (cur.items + kWinWaves - 1) / kWinWaves);
+            cur.waves = (cur.items + cur.ipw - 1) / cur.ipw;
+            for (int b = 0; b < cur.jobs; ++b) {
+                const Span sp = span[(size_t)b];
+                const int wave0 = sp.first / cur.ipw, lists = sp.count ? (sp.first + sp.count - 1) / cur.ipw - wave0 + 1 : 0;
+                jtab.push_back(WinJob{wave0, cur.lists});
+                if (lists) seg.push_back(make_int4(cur.lists, lists, sp.job, 0));
+                cur.lists += lists;
+            }
+            cur.groups = (int)(seg.size() - cur.s0);
+            max_lists = std::max(max_lists, (size_t)cur.lists);
+            batches.push_back(cur);
+        }  // (no patches: no planes either, nothing to launch, the jobs' lists stay empty)
+        cur = Batch{planes.size(), items.size(), jtab.size(), seg.size(), 0, 0, 0, 0, 0, 0};
+        cur_planes = 0;
+        span.clear();
+    };
+    for (int64_t j = j0; j < j1; ++j) {
+        const fdcm_pose_window& J = jobs[j];
+        std::vector<WinPlane> jp;
+        long long ji = 0;
+        for (int e = 0; e < J.na; ++e) {
+            const size_t u = W.find((int64_t)J.tmpl * n + (J.a0 + e) % n);
+            if (rot) Mjob[(size_t)(m0[(size_t)j] + e)] = W.M[u];
+            if (W.nl[u] == 0 || !W.box[u].any) continue;  // a template without lines gives nothing
+            WinPlane P{W.line0[u], W.nl[u], 0, -1, 0, -1, J.x0, J.y0, J.nx, (unsigned)((long long)e * J.nx * J.ny), 0, 0};
+            grid_range(W.box[u].x0, W.box[u].x1, J.x0, J.nx, sx, P.i0, P.i1);
+            grid_range(W.box[u].y0, W.box[u].y1, J.y0, J.ny, sy, P.j0, P.j1);
+            if (P.i0 > P.i1 || P.j0 > P.j1) continue;
+            ji += (long long)((P.i1 - P.i0) / kPatchX + 1) * ((P.j1 - P.j0) / kPatchY + 1);
+            jp.push_back(P);
+        }
+        if (cur.jobs > 0 && (cur_planes + J.na > cap || cur.items + ji > kWinItems)) close();
+        span.push_back(Span{cur.items, (int)ji, (int)(j - j0)});
+        for (WinPlane& P : jp) {
+            P.job = cur.jobs;
+            const int npi = (P.i1 - P.i0) / kPatchX + 1, npj = (P.j1 - P.j0) / kPatchY + 1;
+            for (int pi = 0; pi < npi; ++pi)
+                for (int pj = 0; pj < npj; ++pj) items.push_back(make_int2((int)(planes.size() - cur.p0), (pj << 16) | pi));
+            planes.push_back(P);
+        }
+        cur.items += (int)ji;
+        cur.jobs += 1;
+        cur_planes += J.na;
+    }
+    close();
+    const size_t nj = (size_t)(j1 - j0);
+    if (batches.empty()) return;  // (best is kNoKey already)
+
+    // One pinned buffer, one asynchronous copy: lines, planes, patches, job and group tables and the merged lists; the
+    // candidate lists of one batch follow on the device.
+    const size_t o_pl = al256(W.lines.size() * sizeof(ExLine)), o_it = o_pl + al256(planes.size() * sizeof(WinPlane)),
+                 o_jt = o_it + al256(items.size() * sizeof(int2)), o_seg = o_jt + al256(jtab.size() * sizeof(WinJob)),
+                 o_best = o_seg + al256(seg.size() * sizeof(int4)), o_cand = o_best + al256(nj * k * 8),
+                 total = o_cand + al256(max_lists * k * 8);
+    fm->search.eval.reserve(total);
+    fm->search.eval_stage.reserve(o_cand);
+    char* d = (char*)fm->search.eval.p;
+    char* h = (char*)fm->search.eval_stage.p;
+    std::memcpy(h, W.lines.data(), W.lines.size() * sizeof(ExLine));
+    std::memcpy(h + o_pl, planes.data(), planes.size() * sizeof(WinPlane));
+    std::memcpy(h + o_it, items.data(), items.size() * sizeof(int2));
+    std::memcpy(h + o_jt, jtab.data(), jtab.size() * sizeof(WinJob));
+    std::memcpy(h + o_seg, seg.data(), seg.size() * sizeof(int4));
+    std::memset(h + o_best, 0xff, nj * k * 8);  // kNoKey
+    hipStream_t st = fm->stream;
+    FDCM_HIP(hipMemcpyAsync(d, h, o_cand, hipMemcpyHostToDevice, st));
+    unsigned long long* cand = (unsigned long long*)(d + o_cand);
+    unsigned long long* d_best = (unsigned long long*)(d + o_best);
+    const float* vol = fm->vol.as<float>();
+    for (const Batch& B : batches) {
+        auto kern = buf32 ? k_exhaustive_windows<true> : k_exhaustive_windows<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((B.waves + 3) / 4)), dim3(256), 0, st, vol, SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
+                           fm->ty, (const ExLine*)d, (const WinPlane*)(d + o_pl) + B.p0, (const int2*)(d + o_it) + B.i0,
+                           (const WinJob*)(d + o_jt) + B.b0, B.items, B.ipw, sx, sy, k, cand);
+        FDCM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_exhaustive_merge_groups, dim3((unsigned)((B.groups + 3) / 4)), dim3(256), 0, st,
+                           (const unsigned long long*)cand, (const int4*)(d + o_seg) + B.s0, B.groups, 1, k, d_best);
+        FDCM_HIP(hipGetLastError());
+    }
+    FDCM_HIP(hipMemcpyAsync(best, d_best, nj * k * 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
+}
+
 }  // namespace
 
 void exhaustive_window(fdcm_featuremap* fm, const fdcm_templates* t, int32_t sx, int32_t sy, fdcm_grid* out) {
@@ -972,6 +1292,43 @@ void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* 
     std::vector<int32_t> index;
     search(fm, P, n, g, k, rx, ry, ra, wrap, best, index);
     emit_records(best, k, index, n, g, base, M.data(), out, n_out);
+}
+
+// Pose windows (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  Jobs go in rounds of about kWinStageBytes of
+// tables, one in practice; a job is never cut, so the lines of one job's run are the one part no round bounds.
+void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
+                                   int64_t n_jobs, int sx, int sy, int k, int32_t base, fdcm_match** out, int64_t* n_out,
+                                   int64_t* job_offsets) {
+    *n_out = 0;
+    if (job_offsets) std::fill(job_offsets, job_offsets + n_jobs + 1, (int64_t)0);
+    if (n_jobs == 0 || t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    std::vector<unsigned long long> best((size_t)n_jobs * k, kNoKey);
+    std::vector<int64_t> m0((size_t)n_jobs + 1, 0);
+    for (int64_t j = 0; j < n_jobs; ++j) m0[(size_t)j + 1] = m0[(size_t)j] + jobs[j].na;
+    std::vector<RotM> Mjob(rot ? (size_t)m0[(size_t)n_jobs] : 0);
+    // (a forced batch size also shrinks the rounds, to 4 KB a plane: the tests' small lists then go in several)
+    const size_t round_bytes = test_switches().windows_batch > 0 ? (size_t)test_switches().windows_batch << 12 : kWinStageBytes;
+    for (int64_t j0 = 0; j0 < n_jobs;) {
+        int64_t j1 = j0;
+        size_t bytes = 0;
+        do {  // an upper bound of the job's share of the upload: no pair counted as shared
+            const fdcm_pose_window& J = jobs[j1];
+            const size_t nl = (size_t)(t->offsets[(size_t)J.tmpl + 1] - t->offsets[(size_t)J.tmpl]);
+            bytes += (size_t)J.na * (sizeof(WinPlane) + nl * sizeof(ExLine) +
+                                     (size_t)((J.nx + kPatchX - 1) / kPatchX) * (size_t)((J.ny + kPatchY - 1) / kPatchY) * sizeof(int2)) +
+                     sizeof(WinJob) + sizeof(int4) + (size_t)k * 8;
+            ++j1;
+        } while (j1 < n_jobs && bytes < round_bytes);
+        windows_round(fm, t, rot, jobs, j0, j1, sx, sy, k, best.data() + (size_t)j0 * k, m0, Mjob);
+        j0 = j1;
+    }
+    std::vector<fdcm_grid> grids((size_t)n_jobs);
+    for (int64_t j = 0; j < n_jobs; ++j) grids[(size_t)j] = fdcm_grid{jobs[j].x0, jobs[j].y0, jobs[j].nx, jobs[j].ny, sx, sy};
+    emit_records(
+        best, k, n_jobs, [&](int64_t q) { return base + jobs[q].tmpl; }, [&](int64_t q) -> const fdcm_grid& { return grids[(size_t)q]; },
+        [&](int64_t q, int e) { return rot ? &Mjob[(size_t)(m0[(size_t)q] + e)] : nullptr; }, out, n_out, job_offsets);
 }
 
 }  // namespace fdcm

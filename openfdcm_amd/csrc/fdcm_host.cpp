@@ -32,6 +32,8 @@ const TestSwitches& test_switches() {
         r.host_bins = set("FDCM_FORCE_HOST_BINS");
         r.search_flat = set("FDCM_SEARCH_FLAT");
         r.search_compact2 = set("FDCM_SEARCH_COMPACT2");
+        r.windows_batch = std::max(0, num("FDCM_WINDOWS_BATCH", 0));
+        r.windows_flat = set("FDCM_WINDOWS_FLAT");
         return r;
     }();
     return s;

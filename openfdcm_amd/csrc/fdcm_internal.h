@@ -35,12 +35,17 @@ struct HipError { hipError_t code; const char* what; int line; };
 //   FDCM_FORCE_HOST_BINS       the candidates' orientation bins from the host libm (orientation_bins_on_host)
 //   FDCM_SEARCH_FLAT           the search with 64-bit flat addresses (run_search)
 //   FDCM_SEARCH_COMPACT2       the search's two-kernel compaction at every size (run_search)
+//   FDCM_WINDOWS_BATCH=1..     planes a batch of the pose-window search holds at most, instead of 65536 (windows_round),
+//                              and 4 KB of tables per such plane a round, instead of 256 MB (run_search_exhaustive_windows)
+//   FDCM_WINDOWS_FLAT          the pose-window search with 64-bit flat addresses (windows_round)
 struct TestSwitches {
     bool literal_sweep, sweep_order;
     int sweep_min_cols;  // 16 unless forced
     int sweep_steal;     // -1: not forced
     int int_xc;          // 0: not forced
     bool host_bins, search_flat, search_compact2;
+    int windows_batch;  // 0: not forced
+    bool windows_flat;
 };
 const TestSwitches& test_switches();
 
@@ -340,6 +345,10 @@ void run_score_map_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const
                              float* out_host);
 void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
                                      int k, int rx, int ry, int ra, int wrap, int32_t base, fdcm_match** out, int64_t* n_out);
+// rot: null for translations only; job_offsets: n_jobs + 1, or null
+void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
+                                   int64_t n_jobs, int sx, int sy, int k, int32_t base, fdcm_match** out, int64_t* n_out,
+                                   int64_t* job_offsets);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

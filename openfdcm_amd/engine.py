@@ -44,6 +44,20 @@ def as_grid(grid):
     return capi.Grid(*vals)
 
 
+def as_pose_windows(jobs):
+    """(n, 7) contiguous int32 rows in fdcm_pose_window's order, from such an array or a POSE_WINDOW_DTYPE array."""
+    a = np.asarray(jobs)
+    if a.dtype == capi.POSE_WINDOW_DTYPE:
+        a = a.view(np.int32).reshape(-1, 7)
+    if a.size == 0:
+        return np.zeros((0, 7), dtype=np.int32)
+    if a.ndim != 2 or a.shape[1] != 7 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("jobs must be an (n, 7) integer array: tmpl, a0, na, x0, y0, nx, ny")
+    if np.any(a != a.astype(np.int32)):
+        raise ValueError("jobs: a value does not fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def _pixels(a, what):
     """(pointer, width, height, row_stride, on_device, keep-alive) of a 2-D uint8 numpy array (copied unless its rows are
     contiguous) or a 2-D CUDA torch.uint8 tensor (by data_ptr(), after its stream's pending work)."""
@@ -293,6 +307,21 @@ class DeviceFeatureMap:
                                                                int(rx), int(ry), int(ra), int(bool(wrap)),
                                                                int(tmpl_index_base), C.byref(out), C.byref(n)))
         return _adopt_matches(out, n.value)
+
+    def exhaustive_window_search(self, templates, jobs, cs=None, pivots=None, sx=1, sy=1, wrap=False, k=1, tmpl_index_base=0):
+        """Pose windows (include/fdcm.h): jobs (n, 7) int32 rows (tmpl, a0, na, x0, y0, nx, ny), each one template, a run of
+        the rotations cs and a translation grid of its own with strides (sx, sy).  Per job, in the order given, its k best
+        (run position, grid point) by (score, position, grid index).  cs None: translations only (a0 = 0, na = 1).
+        Returns (raw match records, int64 offsets of n + 1: job j's records are offsets[j] .. offsets[j + 1])."""
+        jobs = as_pose_windows(jobs)
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        out, n = C.c_void_p(), C.c_int64()
+        offsets = np.zeros(jobs.shape[0] + 1, dtype=np.int64)
+        capi.check(capi.lib().fdcm_search_exhaustive_windows(
+            self._h, templates._h, C.byref(rot) if rot is not None else None, jobs.ctypes.data_as(C.POINTER(capi.PoseWindow)),
+            jobs.shape[0], int(sx), int(sy), int(bool(wrap)), int(k), int(tmpl_index_base), C.byref(out), C.byref(n),
+            offsets.ctypes.data_as(C.POINTER(C.c_int64))))
+        return _adopt_matches(out, n.value), offsets
 
     def rotation_score_map(self, templates, grid, cs, pivots=None):
         """(T, n, ny, nx) float32: the score of every rotated template at every grid point, NaN where not admissible."""
