@@ -50,6 +50,21 @@ static void require(bool ok, const char* msg) {
     if (!ok) throw std::string(msg);
 }
 
+// A call that returns records in *out (checked non-null): what it had acquired is released when it throws, and a call
+// without records leaves an empty (non-null) array.
+template <class F>
+static void records_call(fdcm_match** out, F&& call) {
+    *out = nullptr;
+    try {
+        call();
+    } catch (...) {
+        result_release(*out);
+        *out = nullptr;
+        throw;
+    }
+    if (!*out) *out = result_acquire(sizeof(fdcm_match));
+}
+
 static void upload_keys_only(fdcm_featuremap* fm) {
     // feature maps adopted from caller slices carry no build plan: the keys go where a plan's keys would be (the search reads them there)
     BuildPlan keys_only;
@@ -640,15 +655,9 @@ int fdcm_search_exhaustive(const fdcm_featuremap* fm, const fdcm_templates* temp
         require(k >= 1 && k <= 64, "k must be in [1, 64]");
         check_exhaustive_args(fm, templates, grid);
         require(out && n_out, "null output");
-        *out = nullptr;
-        try {
+        records_call(out, [&] {
             run_search_exhaustive(const_cast<fdcm_featuremap*>(fm), templates, *grid, k, tmpl_index_base, out, n_out);
-        } catch (...) {
-            result_release(*out);
-            *out = nullptr;
-            throw;
-        }
-        if (!*out) *out = result_acquire(sizeof(fdcm_match));  // no records: an empty (non-null) array
+        });
     });
 }
 
@@ -659,15 +668,9 @@ int fdcm_search_exhaustive_peaks(const fdcm_featuremap* fm, const fdcm_templates
         require(rx >= 0 && rx <= 32 && ry >= 0 && ry <= 32, "radii rx and ry must be in [0, 32]");
         check_exhaustive_args(fm, templates, grid);
         require(out && n_out, "null output");
-        *out = nullptr;
-        try {
+        records_call(out, [&] {
             run_search_exhaustive_peaks(const_cast<fdcm_featuremap*>(fm), templates, *grid, k, rx, ry, tmpl_index_base, out, n_out);
-        } catch (...) {
-            result_release(*out);
-            *out = nullptr;
-            throw;
-        }
-        if (!*out) *out = result_acquire(sizeof(fdcm_match));  // no records: an empty (non-null) array
+        });
     });
 }
 
@@ -711,16 +714,10 @@ int fdcm_search_exhaustive_rotations(const fdcm_featuremap* fm, const fdcm_templ
         check_exhaustive_args(fm, templates, grid);
         require(out && n_out, "null output");
         check_pivots(templates, rot);
-        *out = nullptr;
-        try {
+        records_call(out, [&] {
             run_search_exhaustive_rotations(const_cast<fdcm_featuremap*>(fm), templates, *rot, *grid, k, rx, ry, ra, wrap,
                                             tmpl_index_base, out, n_out);
-        } catch (...) {
-            result_release(*out);
-            *out = nullptr;
-            throw;
-        }
-        if (!*out) *out = result_acquire(sizeof(fdcm_match));  // no records: an empty (non-null) array
+        });
     });
 }
 
@@ -757,16 +754,10 @@ int fdcm_search_exhaustive_windows(const fdcm_featuremap* fm, const fdcm_templat
         if (rot) check_pivots(templates, rot);
         for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
             require(jobs[j].tmpl < templates->T, "jobs: tmpl is outside the template set");
-        *out = nullptr;
-        try {
+        records_call(out, [&] {
             run_search_exhaustive_windows(const_cast<fdcm_featuremap*>(fm), templates, rot, jobs, n_jobs, sx, sy, k, tmpl_index_base, out,
                                           n_out, job_offsets);
-        } catch (...) {
-            result_release(*out);
-            *out = nullptr;
-            throw;
-        }
-        if (!*out) *out = result_acquire(sizeof(fdcm_match));  // no records: an empty (non-null) array
+        });
     });
 }
 
@@ -777,7 +768,7 @@ int fdcm_score_map_rotations(const fdcm_featuremap* fm, const fdcm_templates* te
         check_exhaustive_args(fm, templates, grid);
         check_pivots(templates, rot);
         require(out_host != nullptr || templates->T == 0, "out_host is null");
-        run_score_map_rotations(const_cast<fdcm_featuremap*>(fm), templates, *rot, *grid, out_host);
+        run_score_map(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, out_host, nullptr);
     });
 }
 
@@ -785,7 +776,7 @@ int fdcm_score_map(const fdcm_featuremap* fm, const fdcm_templates* templates, c
     return guarded([&] {
         check_exhaustive_args(fm, templates, grid);
         require(out_host != nullptr || templates->T == 0, "out_host is null");
-        run_score_map(const_cast<fdcm_featuremap*>(fm), templates, *grid, out_host, nullptr);
+        run_score_map(const_cast<fdcm_featuremap*>(fm), templates, nullptr, *grid, out_host, nullptr);
     });
 }
 
@@ -793,7 +784,7 @@ int fdcm_score_map_device(const fdcm_featuremap* fm, const fdcm_templates* templ
     return guarded([&] {
         check_exhaustive_args(fm, templates, grid);
         require(out_device != nullptr || templates->T == 0, "out_device is null");
-        run_score_map(const_cast<fdcm_featuremap*>(fm), templates, *grid, nullptr, out_device);
+        run_score_map(const_cast<fdcm_featuremap*>(fm), templates, nullptr, *grid, nullptr, out_device);
     });
 }
 

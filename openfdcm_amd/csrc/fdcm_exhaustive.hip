@@ -14,6 +14,11 @@
 //   k_exhaustive_windows<BUF32>       pose windows: a wave takes a run of 4 x 16 patches of the clipped boxes of a batch's
 //                                     (job, rotation) planes, a lane per translation, and keeps a k-best list per job
 //
+// Both scoring kernels evaluate through rows_score<BUF32, ROWS>, the one statement of the sum (4 rows per lane in
+// k_exhaustive, 1 in k_exhaustive_windows).  On the host every call prepares its templates through prepare_pairs: the
+// lines, bins and admissible box of (template, rotation) pairs, every pair of the set for the dense calls and the pairs a
+// job list names for the pose windows; the drivers clip a pair's box to their grid (grid_range).
+//
 // Keys of the top-k are (score bits << 32) | grid index: scores are >= +0 (+inf included), so the key order is the
 // (score, g) order, which is total -- the result does not depend on which wave saw which point first.  A NaN score has
 // no key.  No atomics.
@@ -92,6 +97,77 @@ __device__ __forceinline__ unsigned long long list_offer(unsigned long long& e, 
     return thr;
 }
 
+// evaluate at ROWS translations of one column per lane, rows offy[r]: score_per_line.sum(), dt3cpu.cpp:175, in Eigen
+// 3.4.0's order (as pair_score, fdcm_score.h): packets p0 = lines 8b..8b+3 and p1 = 8b+4..8b+7 summed over the blocks of
+// 8, p0 += p1, the trailing packet, predux (p0[0] + p0[2]) + (p0[1] + p0[3]), then the scalar tail.  Zero-initialised
+// accumulators give the same bits (0 + v == v for v >= +0), so one code path serves every n.  The one statement of the
+// sum for every kernel of this file.  res: zero on entry (the caller's initialiser: zeroing it here costs k_exhaustive
+// registers).
+template <bool BUF32, int ROWS>
+__device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __restrict__ Lt, int n, float offx, const float (&offy)[ROWS],
+                                           int W, unsigned uH, size_t SL, float (&res)[ROWS]) {
+    const int aligned2 = (n / 8) * 8, aligned = (n / 4) * 4;
+    float p0[ROWS][4], p1[ROWS][4];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int l = 0; l < 4; ++l) p0[r][l] = p1[r][l] = 0.f;
+    for (int b = 0; b < aligned2; b += 8) {
+        float va[8][ROWS], vb[8][ROWS];
+#pragma unroll
+        for (int l = 0; l < 8; ++l) {
+            const ExLine ln = Lt[b + l];
+            const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
+            const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {  // translate then cast<int>()
+                va[l][r] = ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH);
+                vb[l][r] = ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                p0[r][l] = p0[r][l] + f_abs(va[l][r] - vb[l][r]);
+                p1[r][l] = p1[r][l] + f_abs(va[l + 4][r] - vb[l + 4][r]);
+            }
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + p1[r][l];
+    if (aligned > aligned2) {  // the trailing packet
+        float va[4][ROWS], vb[4][ROWS];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const ExLine ln = Lt[aligned2 + l];
+            const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
+            const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                va[l][r] = ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH);
+                vb[l][r] = ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+            for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + f_abs(va[l][r] - vb[l][r]);
+    }
+    if (aligned)
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) res[r] = (p0[r][0] + p0[r][2]) + (p0[r][1] + p0[r][3]);  // predux
+    for (int idx = aligned; idx < n; ++idx) {  // the scalar tail, in order
+        const ExLine ln = Lt[idx];
+        const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
+        const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r)
+            res[r] = res[r] + f_abs(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH) - ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH));
+    }
+}
+
 template <bool BUF32, bool TOPK>
 __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
                                                     float ty, const ExLine* __restrict__ lines, const ExTmpl* __restrict__ tm,
@@ -140,74 +216,7 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
                 offy[r] = ty + (float)(y0 + (act[r] ? j : P.j0) * sy);
             }
             float res[kRows] = {0.f, 0.f, 0.f, 0.f};
-            if (meets) {
-                // score_per_line.sum(), dt3cpu.cpp:175, in Eigen 3.4.0's order (as pair_score, fdcm_score.h): packets
-                // p0 = lines 8b..8b+3 and p1 = 8b+4..8b+7 summed over the blocks of 8, p0 += p1, the trailing packet,
-                // predux (p0[0] + p0[2]) + (p0[1] + p0[3]), then the scalar tail.  Zero-initialised accumulators give the
-                // same bits (0 + v == v for v >= +0), so one code path serves every n.
-                const ExLine* Lt = lines + P.line0;
-                const int n = P.n, aligned2 = (n / 8) * 8, aligned = (n / 4) * 4;
-                float p0[kRows][4], p1[kRows][4];
-#pragma unroll
-                for (int r = 0; r < kRows; ++r)
-#pragma unroll
-                    for (int l = 0; l < 4; ++l) p0[r][l] = p1[r][l] = 0.f;
-                for (int b = 0; b < aligned2; b += 8) {
-                    float va[8][kRows], vb[8][kRows];
-#pragma unroll
-                    for (int l = 0; l < 8; ++l) {
-                        const ExLine ln = Lt[b + l];
-                        const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
-                        const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
-#pragma unroll
-                        for (int r = 0; r < kRows; ++r) {  // translate then cast<int>()
-                            va[l][r] = ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH);
-                            vb[l][r] = ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH);
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < kRows; ++r)
-#pragma unroll
-                        for (int l = 0; l < 4; ++l) {
-                            p0[r][l] = p0[r][l] + f_abs(va[l][r] - vb[l][r]);
-                            p1[r][l] = p1[r][l] + f_abs(va[l + 4][r] - vb[l + 4][r]);
-                        }
-                }
-#pragma unroll
-                for (int r = 0; r < kRows; ++r)
-#pragma unroll
-                    for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + p1[r][l];
-                if (aligned > aligned2) {  // the trailing packet
-                    float va[4][kRows], vb[4][kRows];
-#pragma unroll
-                    for (int l = 0; l < 4; ++l) {
-                        const ExLine ln = Lt[aligned2 + l];
-                        const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
-                        const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
-#pragma unroll
-                        for (int r = 0; r < kRows; ++r) {
-                            va[l][r] = ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH);
-                            vb[l][r] = ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH);
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < kRows; ++r)
-#pragma unroll
-                        for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + f_abs(va[l][r] - vb[l][r]);
-                }
-                if (aligned)
-#pragma unroll
-                    for (int r = 0; r < kRows; ++r) res[r] = (p0[r][0] + p0[r][2]) + (p0[r][1] + p0[r][3]);
-                for (int idx = aligned; idx < n; ++idx) {  // the scalar tail, in order
-                    const ExLine ln = Lt[idx];
-                    const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
-                    const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
-#pragma unroll
-                    for (int r = 0; r < kRows; ++r)
-                        res[r] = res[r] + f_abs(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH) -
-                                                ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH));
-                }
-            }
+            if (meets) rows_score<BUF32, kRows>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
             if (!TOPK) {
                 if (i < nx) {
                     float* out = map + (long long)P.slot * plane;
@@ -408,49 +417,6 @@ struct WinPlane {
 struct WinJob { int wave0, list0; };
 constexpr int kPatchX = 4, kPatchY = 16;
 
-// evaluate at one translation per lane: k_exhaustive's sum (pair_score's order) with one row per lane
-template <bool BUF32>
-__device__ __forceinline__ float window_score(const VolRef& V, const ExLine* __restrict__ Lt, int n, float offx, float offy, int W,
-                                              unsigned uH, size_t SL) {
-    const int aligned2 = (n / 8) * 8, aligned = (n / 4) * 4;
-    float p0[4] = {0.f, 0.f, 0.f, 0.f}, p1[4] = {0.f, 0.f, 0.f, 0.f};  // 0 + v == v for v >= +0
-    for (int b = 0; b < aligned2; b += 8) {
-        float va[8], vb[8];
-#pragma unroll
-        for (int l = 0; l < 8; ++l) {
-            const ExLine ln = Lt[b + l];
-            va[l] = ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL), (int)(ln.y1 + offy), uH);
-            vb[l] = ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL), (int)(ln.y2 + offy), uH);
-        }
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            p0[l] = p0[l] + f_abs(va[l] - vb[l]);
-            p1[l] = p1[l] + f_abs(va[l + 4] - vb[l + 4]);
-        }
-    }
-#pragma unroll
-    for (int l = 0; l < 4; ++l) p0[l] = p0[l] + p1[l];
-    if (aligned > aligned2) {  // the trailing packet
-        float va[4], vb[4];
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            const ExLine ln = Lt[aligned2 + l];
-            va[l] = ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL), (int)(ln.y1 + offy), uH);
-            vb[l] = ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL), (int)(ln.y2 + offy), uH);
-        }
-#pragma unroll
-        for (int l = 0; l < 4; ++l) p0[l] = p0[l] + f_abs(va[l] - vb[l]);
-    }
-    float res = 0.f;
-    if (aligned) res = (p0[0] + p0[2]) + (p0[1] + p0[3]);  // predux
-    for (int idx = aligned; idx < n; ++idx) {              // the scalar tail, in order
-        const ExLine ln = Lt[idx];
-        res = res + f_abs(ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL), (int)(ln.y1 + offy), uH) -
-                          ex_read<BUF32>(V, ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL), (int)(ln.y2 + offy), uH));
-    }
-    return res;
-}
-
 template <bool BUF32>
 __global__ void __launch_bounds__(256) k_exhaustive_windows(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
                                                             float ty, const ExLine* __restrict__ lines,
@@ -481,10 +447,11 @@ __global__ void __launch_bounds__(256) k_exhaustive_windows(const float* __restr
         // a lane outside the clipped box reads at the box's corner, which is admissible: every read stays inside the volume
         const bool act = i <= P.i1 && j <= P.j1;
         const float offx = tx + (float)(P.x0 + (act ? i : P.i0) * sx);  // translate(tmpl, sceneTranslation + translation)
-        const float offy = ty + (float)(P.y0 + (act ? j : P.j0) * sy);
-        const float res = window_score<BUF32>(V, lines + P.line0, P.n, offx, offy, W, uH, SL);
-        const unsigned long long key = act && !(res != res)  // a NaN score has no key
-                                           ? ((unsigned long long)__float_as_uint(res) << 32) | ((unsigned)(j * P.nx + i) + P.koff)
+        const float offy[1] = {ty + (float)(P.y0 + (act ? j : P.j0) * sy)};
+        float res[1] = {0.f};
+        rows_score<BUF32, 1>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
+        const unsigned long long key = act && !(res[0] != res[0])  // a NaN score has no key
+                                           ? ((unsigned long long)__float_as_uint(res[0]) << 32) | ((unsigned)(j * P.nx + i) + P.koff)
                                            : kNoKey;
         thr = list_offer(e, key, thr, k, lane);
     }
@@ -552,38 +519,11 @@ void check_grid(const fdcm_grid& g) {
         throw std::string("grid: every translation must satisfy |t| < 2^24");
 }
 
-struct Prepared {
-    std::vector<ExLine> lines;
-    std::vector<ExTmpl> tm;  // every template of the set, slot = its index
-    bool buf32 = true;
-    size_t SL = 0;
-};
-
 // One line for the kernels: closestOrientation with the host libm (dt3cpu.cpp:144-148, as fdcm_seam.hip's run_evaluate).
 ExLine line_record(const fdcm_featuremap* fm, const float* p, bool buf32, size_t SL) {
     const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
     const int bin = closest_orientation(fm->keys.data(), (int)fm->m, angle);
     return ExLine{p[0], p[1], p[2], p[3], buf32 ? (int)((unsigned)bin * (unsigned)SL) : bin, 0, 0, 0};
-}
-
-// line_record of every template line and the admissible box of every template in grid indices.
-void prepare(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, Prepared& P) {
-    P.SL = ivol_slice_floats(fm->W, fm->H);
-    P.buf32 = (size_t)fm->m * P.SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
-    P.lines.resize((size_t)std::max<int64_t>(1, t->n_lines));
-    if (t->n_lines > 0x7fffffffll) throw std::string("too many template lines for one exhaustive search");
-    for (int64_t q = 0; q < t->n_lines && fm->m > 0; ++q) P.lines[(size_t)q] = line_record(fm, &t->lines[(size_t)q * 4], P.buf32, P.SL);
-    P.tm.resize((size_t)t->T);
-    for (int64_t i = 0; i < t->T; ++i) {
-        const int64_t l0 = t->offsets[(size_t)i], n = t->offsets[(size_t)i + 1] - l0;
-        const Box b = admissible_box(fm, t, l0, n);
-        ExTmpl& e = P.tm[(size_t)i];
-        e = ExTmpl{(int)l0, (int)n, 0, -1, 0, -1, (int)i, 0};
-        if (b.any) {
-            grid_range(b.x0, b.x1, g.x0, g.nx, g.sx, e.i0, e.i1);
-            grid_range(b.y0, b.y1, g.y0, g.ny, g.sy, e.j0, e.j1);
-        }
-    }
 }
 
 void begin(fdcm_featuremap* fm) {
@@ -594,39 +534,6 @@ void begin(fdcm_featuremap* fm) {
 }
 
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Launches k_exhaustive over the templates tm (already on the device at d_tm) with the lines at d_lines.
-template <bool TOPK>
-void launch(fdcm_featuremap* fm, const Prepared& P, const fdcm_grid& g, const ExLine* d_lines, const ExTmpl* d_tm, int T, int k,
-            int portions, float* map, unsigned long long* cand) {
-    const int tiles_x = (g.nx + kTileX - 1) / kTileX, tiles_y = (g.ny + kTileY - 1) / kTileY;
-    const int n_subtiles = tiles_x * tiles_y;
-    const float* vol = fm->vol.as<float>();
-    const long long plane = (long long)g.nx * g.ny;
-    const int per_launch = (1 << 20) * kChunk;  // keeps portions x chunks in range; outputs go by slot
-    for (int t0 = 0; t0 < T; t0 += per_launch) {
-        const int nt = std::min(per_launch, T - t0);
-        const dim3 grid((unsigned)(portions * ((nt + kChunk - 1) / kChunk)));  // portions: a multiple of 8
-        if (P.buf32)
-            hipLaunchKernelGGL((k_exhaustive<true, TOPK>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
-                               fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
-                               map, plane, cand);
-        else
-            hipLaunchKernelGGL((k_exhaustive<false, TOPK>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
-                               fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
-                               map, plane, cand);
-        FDCM_HIP(hipGetLastError());
-    }
-}
-
-// Workgroups along the grid (a multiple of 8, one group per XCD): about as many workgroups of all template chunks as are
-// resident at once (4 per compute unit: 128 VGPRs), no more groups than sub-tiles.
-int portions_for(const fdcm_featuremap* fm, const fdcm_grid& g, int T) {
-    const long long n_subtiles = (long long)((g.nx + kTileX - 1) / kTileX) * ((g.ny + kTileY - 1) / kTileY);
-    const long long chunks = (std::min(T, (1 << 20) * kChunk) + kChunk - 1) / kChunk;
-    const long long per_xcd = std::max<long long>(1, (4ll * device_cus(fm->device) / 8) / chunks);
-    return 8 * (int)std::max<long long>(1, std::min<long long>(per_xcd, (n_subtiles + 7) / 8));
-}
 
 // ---- rotations (include/fdcm.h, "Rotations")
 // M_a = [R | m] of rotate(lines, R, rot_point), math.h:372-378, with R = [[c, -s], [s, c]] and m = p - R p: every product
@@ -698,39 +605,88 @@ void on_threads(int nth, const char* what, F part) {
         if (!e.empty()) throw e;
 }
 
-// prepare() of the rotated set of all templates: P.tm[t * n + a] is (t, a), M its transforms.  The rotation, bins (host
-// atan) and admissible boxes run in up to 16 threads over ranges of templates, each of about 2^12 rotated lines or more.
-void prepare_rotated(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g, Prepared& P,
-                     std::vector<RotM>& M) {
-    const int n = rot.n;
-    check_rotated_size(t, n);
-    M.resize((size_t)(t->T * n));
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({16, t->T, (t->n_lines * n) >> 12}));
-    std::vector<int64_t> cut((size_t)nth + 1);
-    for (int c = 0; c <= nth; ++c) cut[(size_t)c] = t->T * c / nth;
-    std::vector<Prepared> part((size_t)nth);
-    on_threads(nth, "host preparation of the rotated templates failed", [&](int c) {
-        fdcm_templates rt;
-        rotated_set(t, rot, cut[(size_t)c], cut[(size_t)c + 1], rt, M.data() + cut[(size_t)c] * n);
-        prepare(fm, &rt, g, part[(size_t)c]);
-    });
-    P.SL = part[0].SL;
-    P.buf32 = part[0].buf32;
-    P.lines.clear();
-    P.lines.reserve((size_t)std::max<int64_t>(1, t->n_lines * n));
-    P.tm.clear();
-    P.tm.reserve((size_t)(t->T * n));
-    for (int c = 0; c < nth; ++c) {
-        const int line0 = (int)P.lines.size(), slot0 = (int)(cut[(size_t)c] * n);
-        for (ExTmpl e : part[(size_t)c].tm) {
-            e.line0 += line0;
-            e.slot += slot0;
-            P.tm.push_back(e);
-        }
-        const size_t nl = (size_t)((t->offsets[(size_t)cut[(size_t)c + 1]] - t->offsets[(size_t)cut[(size_t)c]]) * n);
-        P.lines.insert(P.lines.end(), part[(size_t)c].lines.begin(), part[(size_t)c].lines.begin() + nl);
+// ---- the host preparation, the one of every call
+// (template, rotation) pairs, each prepared once: its rotated lines (RotM's rule; the caller's own lines when there is no
+// table), their bins (line_record) and its admissible box in translation coordinates.  The dense calls prepare every pair
+// of the set; the pose windows the distinct pairs a run of jobs names.
+struct Pairs {
+    std::vector<int64_t> key;    // tmpl * n + a, ascending; empty: every pair of the set, pair u being tmpl * n + a = u
+    std::vector<ExLine> lines;   // (never empty)
+    std::vector<int> line0, nl;  // per pair: its lines
+    std::vector<Box> box;
+    std::vector<RotM> M;  // (rotations only)
+    bool buf32 = true;    // VolRef's form for the kernels that read the lines
+    size_t SL = 0;
+    size_t find(int64_t k) const { return (size_t)(std::lower_bound(key.begin(), key.end(), k) - key.begin()); }
+};
+
+// rotated_set, line_record and admissible_box of every pair of W.key, in up to 16 threads over ranges of pairs of about
+// 2^12 lines or more.  Inside a range the pairs of one template are one rotated_set over their rotations, so a template's
+// lines are read once; every output is written by pair index, so the result does not depend on the cuts.  rot null: the
+// translations, a table of one rotation (n = 1).  flat: the 64-bit form of VolRef whatever the volume's size.
+void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, bool flat, Pairs& W) {
+    const int n = rot ? rot->n : 1;
+    const bool all = W.key.empty();
+    const size_t np = all ? (size_t)(t->T * n) : W.key.size();
+    auto key_of = [&](size_t u) { return all ? (int64_t)u : W.key[u]; };
+    W.SL = ivol_slice_floats(fm->W, fm->H);
+    W.buf32 = !flat && (size_t)fm->m * W.SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
+    W.line0.assign(np, 0);
+    W.nl.assign(np, 0);
+    W.box.assign(np, Box{false, 0, 0, 0, 0});
+    if (rot) W.M.resize(np);
+    int64_t total = 0;
+    for (size_t u = 0; u < np; ++u) {  // pair u's lines follow pair u - 1's
+        const int64_t i = key_of(u) / n;
+        W.line0[u] = (int)total;  // (in range once total is, below)
+        W.nl[u] = (int)(t->offsets[(size_t)i + 1] - t->offsets[(size_t)i]);
+        total += W.nl[u];
     }
-    if (P.lines.empty()) P.lines.resize(1);
+    if (total > 0x7fffffffll)
+        throw std::string(all && !rot ? "too many template lines for one exhaustive search"
+                                      : "too many rotated template lines for one call");
+    W.lines.assign((size_t)std::max<int64_t>(1, total), ExLine{});
+    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)np, total >> 12}));
+    std::vector<size_t> cut((size_t)nth + 1);
+    for (int c = 0; c <= nth; ++c) cut[(size_t)c] = np * (size_t)c / (size_t)nth;
+    const char* what = all ? "host preparation of the rotated templates failed" : "host preparation of the pose windows failed";
+    on_threads(nth, what, [&](int c) {
+        std::vector<float> cs;
+        fdcm_templates rt;
+        for (size_t p = cut[(size_t)c]; p < cut[(size_t)c + 1];) {
+            const int64_t i = key_of(p) / n;
+            size_t q = p;
+            cs.clear();
+            for (; q < cut[(size_t)c + 1] && key_of(q) / n == i; ++q)
+                if (rot) {
+                    const int64_t a = key_of(q) % n;
+                    cs.push_back(rot->cs[2 * a]);
+                    cs.push_back(rot->cs[2 * a + 1]);
+                }
+            if (rot) {
+                const fdcm_rotations sub{cs.data(), (int32_t)(q - p), rot->pivots};
+                rotated_set(t, sub, i, i + 1, rt, W.M.data() + p);
+            }
+            const fdcm_templates* src = rot ? &rt : t;  // the caller's lines as they are (run_search_exhaustive_peaks' note on -0)
+            for (size_t u = p; u < q; ++u) {
+                const int64_t l0 = rot ? rt.offsets[u - p] : t->offsets[(size_t)i];
+                W.box[u] = admissible_box(fm, src, l0, W.nl[u]);
+                for (int x = 0; x < W.nl[u] && fm->m > 0; ++x)  // (an empty map has no bins: no line is read there)
+                    W.lines[(size_t)W.line0[u] + x] = line_record(fm, &src->lines[(size_t)(l0 + x) * 4], W.buf32, W.SL);
+            }
+            p = q;
+        }
+    });
+}
+
+// Pair u of W on the grid g as a template of a launch: its admissible box in grid indices.
+ExTmpl grid_tmpl(const Pairs& W, size_t u, const fdcm_grid& g, int slot) {
+    ExTmpl e{W.line0[u], W.nl[u], 0, -1, 0, -1, slot, 0};
+    if (W.box[u].any) {
+        grid_range(W.box[u].x0, W.box[u].x1, g.x0, g.nx, g.sx, e.i0, e.i1);
+        grid_range(W.box[u].y0, W.box[u].y1, g.y0, g.ny, g.sy, e.j0, e.j1);
+    }
+    return e;
 }
 
 // The records of the merged lists best[q][k], q < Q (kNoKey ends a list).  List q is template tmpl_of(q)'s on the grid
@@ -781,22 +737,57 @@ void emit_records(const std::vector<unsigned long long>& best, int k, const std:
         [&](int64_t q, int a) { return M ? &M[(size_t)index[(size_t)q] * n + a] : nullptr; }, out, n_out, nullptr);
 }
 
+// Launches k_exhaustive over the templates tm (already on the device at d_tm) with the lines at d_lines.
+template <bool TOPK>
+void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLine* d_lines, const ExTmpl* d_tm, int T, int k,
+            int portions, float* map, unsigned long long* cand) {
+    const int tiles_x = (g.nx + kTileX - 1) / kTileX, tiles_y = (g.ny + kTileY - 1) / kTileY;
+    const int n_subtiles = tiles_x * tiles_y;
+    const float* vol = fm->vol.as<float>();
+    const long long plane = (long long)g.nx * g.ny;
+    const int per_launch = (1 << 20) * kChunk;  // keeps portions x chunks in range; outputs go by slot
+    for (int t0 = 0; t0 < T; t0 += per_launch) {
+        const int nt = std::min(per_launch, T - t0);
+        const dim3 grid((unsigned)(portions * ((nt + kChunk - 1) / kChunk)));  // portions: a multiple of 8
+        if (P.buf32)
+            hipLaunchKernelGGL((k_exhaustive<true, TOPK>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+                               fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
+                               map, plane, cand);
+        else
+            hipLaunchKernelGGL((k_exhaustive<false, TOPK>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+                               fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
+                               map, plane, cand);
+        FDCM_HIP(hipGetLastError());
+    }
+}
+
+// Workgroups along the grid (a multiple of 8, one group per XCD): about as many workgroups of all template chunks as are
+// resident at once (4 per compute unit: 128 VGPRs), no more groups than sub-tiles.
+int portions_for(const fdcm_featuremap* fm, const fdcm_grid& g, int T) {
+    const long long n_subtiles = (long long)((g.nx + kTileX - 1) / kTileX) * ((g.ny + kTileY - 1) / kTileY);
+    const long long chunks = (std::min(T, (1 << 20) * kChunk) + kChunk - 1) / kChunk;
+    const long long per_xcd = std::max<long long>(1, (4ll * device_cus(fm->device) / 8) / chunks);
+    return 8 * (int)std::max<long long>(1, std::min<long long>(per_xcd, (n_subtiles + 7) / 8));
+}
+
 constexpr size_t kMapBytes = (size_t)768 << 20;     // the score planes of one batch (peaks): translations
 constexpr size_t kRotMapBytes = (size_t)512 << 20;  // .. rotations (n > 1): larger batches slow their stride-2 passes
 constexpr size_t kCandBytes = (size_t)128 << 20;  // the candidate lists of one batch (top-k)
 
-// The search driver, the top-k when rx = ry = ra = 0 and the peaks otherwise.  P: T x n planes, plane t n + a being
-// template t at angle a (n = 1: the translations).  Out: index, the templates that can emit -- lines, and an admissible
-// grid point under some angle -- in ascending order, and best[q][k], the merged list of template index[q] (kNoKey ends
-// a list).
-void search(fdcm_featuremap* fm, const Prepared& P, int n, const fdcm_grid& g, int k, int rx, int ry, int ra, int wrap,
+// The search driver, the top-k when rx = ry = ra = 0 and the peaks otherwise.  P: every pair of T templates and n angles,
+// prepared: T x n planes, plane t n + a being template t at angle a (n = 1: the translations).  Out: index, the templates
+// that can emit -- lines, and an admissible grid point under some angle -- in ascending order, and best[q][k], the merged
+// list of template index[q] (kNoKey ends a list).
+void search(fdcm_featuremap* fm, const Pairs& P, int n, const fdcm_grid& g, int k, int rx, int ry, int ra, int wrap,
             std::vector<unsigned long long>& best, std::vector<int32_t>& index) {
-    const int64_t T = (int64_t)P.tm.size() / n;
+    std::vector<ExTmpl> tm(P.nl.size());  // every plane on the full grid, slot = its index
+    for (size_t u = 0; u < tm.size(); ++u) tm[u] = grid_tmpl(P, u, g, (int)u);
+    const int64_t T = (int64_t)tm.size() / n;
     const unsigned long long N = (unsigned long long)g.nx * g.ny;
     for (int64_t i = 0; i < T; ++i) {
-        if (P.tm[(size_t)(i * n)].n == 0) continue;
+        if (tm[(size_t)(i * n)].n == 0) continue;
         for (int a = 0; a < n; ++a) {
-            const ExTmpl& e = P.tm[(size_t)(i * n + a)];
+            const ExTmpl& e = tm[(size_t)(i * n + a)];
             if (e.i0 <= e.i1 && e.j0 <= e.j1) { index.push_back((int32_t)i); break; }
         }
     }
@@ -883,7 +874,7 @@ void search(fdcm_featuremap* fm, const Prepared& P, int n, const fdcm_grid& g, i
             const int64_t ti = index[(size_t)G.q];
             for (int p = 0; p < G.np; ++p) {
                 const int a2 = (G.lo + p) % n;
-                ExTmpl e = P.tm[(size_t)(ti * n + a2)];
+                ExTmpl e = tm[(size_t)(ti * n + a2)];
                 e.slot = G.plane0 + p;
                 e.koff = (unsigned)((unsigned long long)a2 * N);
                 planes.push_back(e);
@@ -979,77 +970,6 @@ void search(fdcm_featuremap* fm, const Prepared& P, int n, const fdcm_grid& g, i
 }
 
 // ---- pose windows: the host driver
-// The distinct (template, rotation) pairs a run of jobs names, each prepared once: its rotated lines (RotM's rule; the
-// caller's own lines when there is no table), their bins and its admissible box in translation coordinates.
-struct WinPairs {
-    std::vector<int64_t> key;  // tmpl * n + a, ascending
-    std::vector<ExLine> lines;
-    std::vector<int> line0, nl;  // per pair: its lines
-    std::vector<Box> box;
-    std::vector<RotM> M;  // (rotations only)
-    size_t find(int64_t k) const { return (size_t)(std::lower_bound(key.begin(), key.end(), k) - key.begin()); }
-};
-
-// rotated_set, line_record and admissible_box of every pair, in up to 16 threads over ranges of pairs of about 2^12 lines
-// or more (as prepare_rotated).  Inside a range the pairs of one template are one rotated_set over their rotations.
-void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, int n, bool buf32, size_t SL,
-                   WinPairs& W) {
-    const size_t np = W.key.size();
-    W.line0.assign(np, 0);
-    W.nl.assign(np, 0);
-    W.box.assign(np, Box{false, 0, 0, 0, 0});
-    if (rot) W.M.resize(np);
-    int64_t total = 0;
-    for (int64_t k : W.key) total += t->offsets[(size_t)(k / n) + 1] - t->offsets[(size_t)(k / n)];
-    if (total > 0x7fffffffll) throw std::string("too many rotated template lines for one call");
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)np, total >> 12}));
-    std::vector<size_t> cut((size_t)nth + 1);
-    for (int c = 0; c <= nth; ++c) cut[(size_t)c] = np * (size_t)c / (size_t)nth;
-    std::vector<std::vector<ExLine>> part((size_t)nth);
-    on_threads(nth, "host preparation of the pose windows failed", [&](int c) {
-        std::vector<float> cs;
-        for (size_t p = cut[(size_t)c]; p < cut[(size_t)c + 1];) {
-            const int64_t i = W.key[p] / n;
-            size_t q = p;
-            cs.clear();
-            for (; q < cut[(size_t)c + 1] && W.key[q] / n == i; ++q)
-                if (rot) {
-                    const int64_t a = W.key[q] % n;
-                    cs.push_back(rot->cs[2 * a]);
-                    cs.push_back(rot->cs[2 * a + 1]);
-                }
-            fdcm_templates rt;
-            if (rot) {
-                const fdcm_rotations sub{cs.data(), (int32_t)(q - p), rot->pivots};
-                rotated_set(t, sub, i, i + 1, rt, W.M.data() + p);
-            } else {  // the caller's lines as they are (run_search_exhaustive_peaks' note on -0)
-                const int64_t l0 = t->offsets[(size_t)i], l1 = t->offsets[(size_t)i + 1];
-                rt.T = 1;
-                rt.n_lines = l1 - l0;
-                rt.lines.assign(t->lines.begin() + 4 * l0, t->lines.begin() + 4 * l1);
-                rt.offsets = {0, l1 - l0};
-            }
-            for (size_t u = p; u < q; ++u) {
-                const int64_t l0 = rt.offsets[u - p], nl = rt.offsets[u - p + 1] - l0;
-                W.line0[u] = (int)part[(size_t)c].size();
-                W.nl[u] = (int)nl;
-                W.box[u] = admissible_box(fm, &rt, l0, nl);
-                for (int64_t x = l0; x < l0 + nl && fm->m > 0; ++x)
-                    part[(size_t)c].push_back(line_record(fm, &rt.lines[(size_t)x * 4], buf32, SL));
-                if (fm->m <= 0) W.box[u].any = false;
-            }
-            p = q;
-        }
-    });
-    W.lines.clear();
-    W.lines.reserve((size_t)std::max<int64_t>(1, total));
-    for (int c = 0; c < nth; ++c) {
-        for (size_t u = cut[(size_t)c]; u < cut[(size_t)c + 1]; ++u) W.line0[u] += (int)W.lines.size();
-        W.lines.insert(W.lines.end(), part[(size_t)c].begin(), part[(size_t)c].end());
-    }
-    if (W.lines.empty()) W.lines.resize(1);
-}
-
 constexpr int kWinPlanes = 65536;       // planes of a batch, at most (a batch always takes one job)
 constexpr int kWinItems = 1 << 20;      // patches of a batch, at most (a job has 2^16 at most)
 constexpr int kWinWaves = 16384;        // waves of a launch, about: twice what is resident at 8 waves per SIMD
@@ -1060,14 +980,12 @@ constexpr size_t kWinStageBytes = (size_t)256 << 20;  // what one upload holds, 
 void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs, int64_t j0,
                    int64_t j1, int sx, int sy, int k, unsigned long long* best, const std::vector<int64_t>& m0, std::vector<RotM>& Mjob) {
     const int n = rot ? rot->n : 1;
-    const size_t SL = ivol_slice_floats(fm->W, fm->H);
-    const bool buf32 = !test_switches().windows_flat && (size_t)fm->m * SL * sizeof(float) < ((size_t)1 << 32);
-    WinPairs W;
+    Pairs W;
     for (int64_t j = j0; j < j1; ++j)
         for (int e = 0; e < jobs[j].na; ++e) W.key.push_back((int64_t)jobs[j].tmpl * n + (jobs[j].a0 + e) % n);
     std::sort(W.key.begin(), W.key.end());
     W.key.erase(std::unique(W.key.begin(), W.key.end()), W.key.end());
-    prepare_pairs(fm, t, rot, n, buf32, SL, W);
+    prepare_pairs(fm, t, rot, test_switches().windows_flat, W);
 
     // Batches of whole jobs.  Per batch: its planes and their patches (job by job, run position by run position, a box's
     // patches along j first), per job with patches its first wave and candidate list, and its group for the merge
@@ -1157,8 +1075,8 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     unsigned long long* d_best = (unsigned long long*)(d + o_best);
     const float* vol = fm->vol.as<float>();
     for (const Batch& B : batches) {
-        auto kern = buf32 ? k_exhaustive_windows<true> : k_exhaustive_windows<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((B.waves + 3) / 4)), dim3(256), 0, st, vol, SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
+        auto kern = W.buf32 ? k_exhaustive_windows<true> : k_exhaustive_windows<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((B.waves + 3) / 4)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
                            fm->ty, (const ExLine*)d, (const WinPlane*)(d + o_pl) + B.p0, (const int2*)(d + o_it) + B.i0,
                            (const WinJob*)(d + o_jt) + B.b0, B.items, B.ipw, sx, sy, k, cand);
         FDCM_HIP(hipGetLastError());
@@ -1195,27 +1113,28 @@ void exhaustive_window(fdcm_featuremap* fm, const fdcm_templates* t, int32_t sx,
     *out = g;
 }
 
-void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, float* out_host, float* out_device) {
+// rot null: the translations, a plane per template; else [t][a][ny][nx]: (t, a) is plane t * n_rot + a.
+void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, float* out_host,
+                   float* out_device) {
     check_grid(g);
+    if (rot) check_rotated_size(t, rot->n);
     if (t->T == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);  // concurrent callers of one feature map take turns (shared search.eval)
     begin(fm);
-    Prepared P;
-    prepare(fm, t, g, P);
-    const int64_t T = t->T;
+    Pairs P;
+    prepare_pairs(fm, t, rot, false, P);
+    const int64_t T = (int64_t)P.nl.size();
     const size_t plane_bytes = (size_t)g.nx * g.ny * sizeof(float);
     // host output: templates in batches whose maps fit a 256 MB workspace; device output: one launch
     const int64_t batch = out_device ? T : std::max<int64_t>(1, std::min<int64_t>(T, ((size_t)256 << 20) / plane_bytes));
-    const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_map = o_tm + al256(P.tm.size() * sizeof(ExTmpl));
+    std::vector<ExTmpl> tm((size_t)T);
+    for (int64_t i = 0; i < T; ++i) tm[(size_t)i] = grid_tmpl(P, (size_t)i, g, (int)(out_device ? i : i % batch));
+    const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_map = o_tm + al256(tm.size() * sizeof(ExTmpl));
     fm->search.eval.reserve(o_map + (out_device ? 0 : (size_t)batch * plane_bytes));
     char* d = (char*)fm->search.eval.p;
     hipStream_t st = fm->stream;
-    for (int64_t b0 = 0; b0 < T; b0 += batch) {
-        const int nb = (int)std::min<int64_t>(batch, T - b0);
-        for (int q = 0; q < nb; ++q) P.tm[(size_t)(b0 + q)].slot = out_device ? (int)(b0 + q) : q;
-    }
     FDCM_HIP(hipMemcpyAsync(d + o_lines, P.lines.data(), P.lines.size() * sizeof(ExLine), hipMemcpyHostToDevice, st));
-    FDCM_HIP(hipMemcpyAsync(d + o_tm, P.tm.data(), P.tm.size() * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
+    FDCM_HIP(hipMemcpyAsync(d + o_tm, tm.data(), tm.size() * sizeof(ExTmpl), hipMemcpyHostToDevice, st));
     for (int64_t b0 = 0; b0 < T; b0 += batch) {
         const int nb = (int)std::min<int64_t>(batch, T - b0);
         float* map = out_device ? out_device : (float*)(d + o_map);
@@ -1224,7 +1143,7 @@ void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid
         if (!out_device)
             FDCM_HIP(hipMemcpyAsync(out_host + (size_t)b0 * g.nx * g.ny, map, (size_t)nb * plane_bytes, hipMemcpyDeviceToHost, st));
     }
-    FDCM_HIP(hipStreamSynchronize(st));  // (P stays alive until here)
+    FDCM_HIP(hipStreamSynchronize(st));  // (P and tm stay alive until here)
 }
 
 void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int32_t base,
@@ -1232,8 +1151,8 @@ void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const f
     run_search_exhaustive_peaks(fm, t, g, k, 0, 0, base, out, n_out);  // radius 0: every point is a peak
 }
 
-// The driver on the caller's lines, not on rotated_set's identity rotation: that turns a -0 coordinate into +0, which
-// can change the sign of x2 - x1 and with it a line's orientation bin.
+// The driver on the caller's lines (prepare_pairs without a table), not on rotated_set's identity rotation: that turns a
+// -0 coordinate into +0, which can change the sign of x2 - x1 and with it a line's orientation bin.
 void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int rx, int ry,
                                  int32_t base, fdcm_match** out, int64_t* n_out) {
     check_grid(g);
@@ -1243,8 +1162,8 @@ void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, c
     if (t->T == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
     begin(fm);
-    Prepared P;
-    prepare(fm, t, g, P);
+    Pairs P;
+    prepare_pairs(fm, t, nullptr, false, P);
     std::vector<unsigned long long> best;
     std::vector<int32_t> index;
     search(fm, P, 1, g, k, rx, ry, 0, 0, best, index);
@@ -1261,16 +1180,6 @@ void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, c
     exhaustive_window(fm, &rt, sx, sy, out);
 }
 
-void run_score_map_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
-                             float* out_host) {
-    check_grid(g);
-    check_rotated_size(t, rot.n);
-    fdcm_templates rt;
-    std::vector<RotM> M((size_t)(t->T * rot.n));
-    rotated_set(t, rot, 0, t->T, rt, M.data());
-    run_score_map(fm, &rt, g, out_host, nullptr);  // [t][a][ny][nx]: (t, a) is template t * n_rot + a
-}
-
 void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
                                      int k, int rx, int ry, int ra, int wrap, int32_t base, fdcm_match** out, int64_t* n_out) {
     check_grid(g);
@@ -1285,13 +1194,13 @@ void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* 
     if (t->T == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
     begin(fm);
-    Prepared P;
-    std::vector<RotM> M;
-    prepare_rotated(fm, t, rot, g, P, M);
+    check_rotated_size(t, n);
+    Pairs P;
+    prepare_pairs(fm, t, &rot, false, P);
     std::vector<unsigned long long> best;
     std::vector<int32_t> index;
     search(fm, P, n, g, k, rx, ry, ra, wrap, best, index);
-    emit_records(best, k, index, n, g, base, M.data(), out, n_out);
+    emit_records(best, k, index, n, g, base, P.M.data(), out, n_out);
 }
 
 // Pose windows (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  Jobs go in rounds of about kWinStageBytes of

@@ -334,15 +334,14 @@ void run_evaluate(fdcm_featuremap* fm, const float* lines, const int64_t* offset
                   const int64_t* tr_offsets, float* scores);
 // implemented in fdcm_exhaustive.hip: the exhaustive translation search (include/fdcm.h)
 void exhaustive_window(fdcm_featuremap* fm, const fdcm_templates* t, int32_t sx, int32_t sy, fdcm_grid* out);
-void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, float* out_host, float* out_device);
+void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, float* out_host,
+                   float* out_device);  // rot null: the translations
 void run_search_exhaustive(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int32_t base,
                            fdcm_match** out, int64_t* n_out);
 void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_grid& g, int k, int rx, int ry,
                                  int32_t base, fdcm_match** out, int64_t* n_out);
 void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, int32_t sx, int32_t sy,
                                  fdcm_grid* out);
-void run_score_map_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
-                             float* out_host);
 void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
                                      int k, int rx, int ry, int ra, int wrap, int32_t base, fdcm_match** out, int64_t* n_out);
 // rot: null for translations only; job_offsets: n_jobs + 1, or null

@@ -59,7 +59,7 @@ def _oracle_volume(orc, sets, master):
 
 @pytest.fixture(scope="module")
 def world():
-    """A 307 x 307 x 12 map and templates of every shape of the sum (window_score): no lines; 5 = the packet and one tail
+    """A 307 x 307 x 12 map and templates of every shape of the sum (rows_score): no lines; 5 = the packet and one tail
     line; 12 = a block of 8 and the packet; 23 = two blocks, the packet and a tail of 3; 8 and 16 = blocks alone; 9 = a block
     and a tail without a packet; 3 = the tail alone.  Per template with lines its oracle volumes over the 8 rotations and
     over the lines as they are.  Computed once and left unchanged."""
