@@ -475,6 +475,43 @@ int fdcm_search_exhaustive_windows(const fdcm_featuremap* fm, const fdcm_templat
                                    int32_t k, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
                                    int64_t* job_offsets /* n_jobs + 1, or NULL */);
 
+/* Best map and detections: the templates compared with each other.  A template set is usually many views or rotations of a
+ * few objects, so one object in the scene gives a peak in almost every template's map at about the same place; these two
+ * calls reduce over the templates on the device.  The definitions are this project's (README.md, "Best template per point
+ * and detections"; numpy statement: tests/detect_ref.py).
+ * Inputs as fdcm_search_exhaustive_rotations: a feature map, T templates, a grid.  rot is optional: rot == NULL is one
+ * "rotation" (n = 1), the lines scored as they are (not passed through an identity rotation, which would turn a -0
+ * coordinate into +0) and the transforms {1, 0, t.x, 0, 1, t.y}.  Pair u = t n + a is template t under rotation a;
+ * score(t, a, g) and admissibility are the rotation search's.
+ * Normalised score q(t, a, g): the value fdcm_penalize(penalty, tau, ..) gives a record {t, score(t, a, g)} with the
+ * lengths of fdcm_templates_lengths: score / max(len_t, 1e-6f) (FDCM_DEFAULT_PENALTY), score / std::pow(max(len_t, 1e-6f),
+ * tau) (FDCM_EXPONENTIAL_PENALTY), the denominators computed on the host and one IEEE float32 division on the device;
+ * penalty = -1: q = score.  Rotation or scale in rot does not change len_t.
+ * Candidates of grid point g: the pairs u of templates with lines that are admissible at g and whose q is not NaN
+ * (templates without lines score 0 everywhere and take no part; an infinite q is a candidate and orders last).
+ * pairkey(u, g) = (bits of q << 32) | u; best(g) is the candidate with the smallest pairkey: the lowest q, ties to the
+ * lowest t, then the lowest a.
+ * fdcm_best_map: two planes of ny x nx, row-major: the float32 q of best(g), NaN where g has no candidate, and the int32
+ * u of best(g), -1 there.  Either output may be NULL, not both.
+ * fdcm_search_exhaustive_detect: the peaks of the best-score plane by the rule of fdcm_search_exhaustive_peaks:
+ * key(g) = (bits of q(best(g)) << 32) | g; g is a detection when its key is below the key of every other point with a
+ * candidate within rx, ry grid steps (0 <= rx, ry <= 32).  Output: the first min(k, count) detections by key
+ * (1 <= k <= 64), as records {t + tmpl_index_base, q, {c, -s, m.x + t.x, s, c, m.y + t.y}} of the pair u = best(g): the
+ * score is the normalised one and the records are in ascending order, so the caller neither penalises nor sorts.  The
+ * minimum over rotations is taken before the peaks: suppression does not look at angles.  Results are a function of the
+ * inputs alone.
+ * FDCM_EINVAL, before any GPU work: what fdcm_search_exhaustive_rotations rejects about its handles, grid, rot and
+ * pivots (its bound n nx ny <= 2^32 belongs to its keys and does not apply); T n > 2^31 - 1; nx ny > 2^26 (a larger grid
+ * is the caller's to cut: 8 bytes of keys and 4 of scores per point stay below 1 GB); penalty not -1, FDCM_DEFAULT_PENALTY
+ * or FDCM_EXPONENTIAL_PENALTY; a tau that is not finite; k or a radius out of range; NULL outputs.  An empty feature map,
+ * an empty template list or no template with lines give zero records and planes of NaN / -1.  Both calls block;
+ * concurrent callers of one feature map take turns.  Release the records with fdcm_matches_free. */
+int fdcm_best_map(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                  const fdcm_grid* grid, int penalty, float tau, float* score_out_host, int32_t* pair_out_host);
+int fdcm_search_exhaustive_detect(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                                  const fdcm_grid* grid, int32_t k, int32_t rx, int32_t ry, int penalty, float tau,
+                                  int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out);
+
 /* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
  *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as
  *      fdcm_edge_labels makes it (m = the distinct keys of `depth`, a byte < m an edge pixel of that label, labels circular)

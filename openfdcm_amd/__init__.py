@@ -608,6 +608,55 @@ def rotation_score_map(featuremap, templates, angles, stride=1, pivot="center", 
     return fm.rotation_score_map(tset, g, cs, pv), g
 
 
+# ---------------------------------------------------------------- best template per point and detections (extension)
+def _penalty_args(penalty):
+    penalty = _unwrap(penalty, PenaltyStrategy)
+    if penalty is None:
+        return None, 1.0
+    if isinstance(penalty, ExponentialPenalty):
+        return _capi.EXPONENTIAL_PENALTY, penalty.get_tau()
+    if isinstance(penalty, DefaultPenalty):
+        return _capi.DEFAULT_PENALTY, 1.0
+    raise TypeError("penalty must be None, DefaultPenalty or ExponentialPenalty")
+
+
+def _detect_args(featuremap, templates, angles, pivot, stride, window):
+    """(device map, template set, cs, pivots, grid): angles None is the translations alone, on exhaustive_window."""
+    if angles is None:
+        fm, tset = _device_map(featuremap), _template_cache.get(templates)
+        return fm, tset, None, None, _window(fm, tset, stride, window)
+    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot)
+    return fm, tset, cs, pv, _rotation_window(fm, tset, cs, pv, stride, window)
+
+
+def best_score_map(featuremap, templates, stride=1, penalty=None, angles=None, pivot="center", window=None):
+    """The templates compared with each other: per grid point the lowest score over all templates with lines and all
+    angles, each score divided as penalize(penalty, ...) divides it (None: as it is), and which pair gave it.  Returns
+    (scores [ny, nx] float32, NaN where no template fits; pairs [ny, nx] int32, -1 there; grid).  With n = len(angles)
+    (1 without angles) pairs // n is the template and pairs % n the angle; equal scores go to the lowest template, then
+    the lowest angle.  angles, pivot and window are exhaustive_rotation_search's."""
+    kind, tau = _penalty_args(penalty)
+    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window)
+    if g[2] == 0 or g[3] == 0:
+        return _np.zeros((g[3], g[2]), dtype=_np.float32), _np.zeros((g[3], g[2]), dtype=_np.int32), g
+    scores, pairs = fm.best_map(tset, g, cs, pv, penalty=kind, tau=tau)
+    return scores, pairs, g
+
+
+def exhaustive_detect(featuremap, templates, radius, stride=1, k=8, penalty=None, angles=None, pivot="center", window=None):
+    """The dense search as a detector: the k best peaks (1 <= k <= 64) of best_score_map's score plane, a peak being a
+    grid point whose (score, grid index) is the smallest within radius = r or (rx, ry) grid steps (0 to 32), whichever
+    template and angle won each point.  One object in the scene gives one detection, not one per template.  Returns a
+    MatchList of the winning templates' poses with the normalised scores, already in ascending score: neither penalize
+    nor sort_matches is needed."""
+    rx, ry = _strides(radius)
+    kind, tau = _penalty_args(penalty)
+    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window)
+    if g[2] == 0 or g[3] == 0:
+        return MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
+    return MatchList(fm.exhaustive_detect(tset, g, cs, pv, k=k, rx=rx, ry=ry, penalty=kind, tau=tau))
+
+
 # ---------------------------------------------------------------- pose windows: refinement and tracking (extension)
 def template_pivots(templates, pivot="center"):
     """The (T, 2) float32 pivots the rotation searches use for pivot="center" (each template's bounding box centre), an

@@ -169,6 +169,9 @@ SYMBOLS = [
     ("fdcm_search_exhaustive_windows", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(PoseWindow), C.c_int64, C.c_int32,
                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_vp), _i64p, _i64p]),
     ("fdcm_score_map_device", C.c_int, [_vp, _vp, C.POINTER(Grid), _vp]),
+    ("fdcm_best_map", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int, C.c_float, _fp, C.POINTER(C.c_int32)]),
+    ("fdcm_search_exhaustive_detect", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int, C.c_float, C.c_int32, C.POINTER(_vp), _i64p]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),
     ("fdcm_lines_free", None, [C.POINTER(C.c_float)]),

@@ -761,6 +761,44 @@ int fdcm_search_exhaustive_windows(const fdcm_featuremap* fm, const fdcm_templat
     });
 }
 
+// Best map and detections: include/fdcm.h, "Best map and detections".  What the rotation call rejects, then the limits of
+// these two: nothing here touches the device.
+static void check_best_args(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid* grid,
+                            int penalty, float tau) {
+    require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
+    require(std::isfinite(tau), "tau must be finite");
+    require(grid != nullptr, "grid is null");
+    if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
+    require((int64_t)std::max(0, grid->nx) * (int64_t)std::max(0, grid->ny) <= ((int64_t)1 << 26), "grid: nx * ny must be at most 2^26");
+    check_exhaustive_args(fm, t, grid);
+    require(t->T * (int64_t)(rot ? rot->n : 1) <= 0x7fffffffll, "T * n_rot must be at most 2^31 - 1");
+    if (rot) check_pivots(t, rot);
+}
+
+int fdcm_best_map(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot, const fdcm_grid* grid,
+                  int penalty, float tau, float* score_out_host, int32_t* pair_out_host) {
+    return guarded([&] {
+        require(score_out_host || pair_out_host, "score_out_host and pair_out_host are both null");
+        check_best_args(fm, templates, rot, grid, penalty, tau);
+        run_best_map(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, penalty, tau, score_out_host, pair_out_host);
+    });
+}
+
+int fdcm_search_exhaustive_detect(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                  const fdcm_grid* grid, int32_t k, int32_t rx, int32_t ry, int penalty, float tau,
+                                  int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out) {
+    return guarded([&] {
+        require(k >= 1 && k <= 64, "k must be in [1, 64]");
+        require(rx >= 0 && rx <= 32 && ry >= 0 && ry <= 32, "radii rx and ry must be in [0, 32]");
+        require(out && n_out, "null output");
+        check_best_args(fm, templates, rot, grid, penalty, tau);
+        records_call(out, [&] {
+            run_search_exhaustive_detect(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, k, rx, ry, penalty, tau,
+                                         tmpl_index_base, out, n_out);
+        });
+    });
+}
+
 int fdcm_score_map_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
                              const fdcm_grid* grid, float* out_host) {
     return guarded([&] {

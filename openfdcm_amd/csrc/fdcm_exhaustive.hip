@@ -3,10 +3,12 @@
 // "exhaustive search").  A score is evaluate<Dt3Cpu> (dt3cpu.cpp:126-179) at one translation: the bits
 // fdcm_featuremap_evaluate returns there.
 //
-//   k_exhaustive<BUF32, TOPK>         a workgroup takes a contiguous run of 16 x 64 sub-tiles of the grid (a portion) and a
+//   k_exhaustive<BUF32, MODE>         a workgroup takes a contiguous run of 16 x 64 sub-tiles of the grid (a portion) and a
 //                                     chunk of kChunk templates; for every sub-tile it scores every template of the chunk (a
-//                                     lane per 4 translations), then writes the scores (map) or offers them to a running
-//                                     k-best list per wave and template kept in LDS (top-k)
+//                                     lane per 4 translations), then writes the scores (map), offers them to a running
+//                                     k-best list per wave and template kept in LDS (top-k), or keeps per point the smallest
+//                                     (normalised score, pair) key of the chunk and merges it into one plane of keys (best)
+//   k_best_unpack, k_best_gather      best map: the key plane as row-major score and pair planes; the pairs of k points
 //   k_exhaustive_peaks<R, ANGLES>     peaks: reads the score planes k_exhaustive<., false> wrote and offers every point whose
 //                                     key is the minimum of its window to a per-wave k-best list; ANGLES: the window spans
 //                                     several angles' planes (64-bit keys in LDS), else one plane (32-bit score bits)
@@ -21,7 +23,8 @@
 //
 // Keys of the top-k are (score bits << 32) | grid index: scores are >= +0 (+inf included), so the key order is the
 // (score, g) order, which is total -- the result does not depend on which wave saw which point first.  A NaN score has
-// no key.  No atomics.
+// no key.  No atomics there.  The best map ("Best map and detections") is the one place with atomics: a 64-bit minimum per
+// point across the workgroups of different template chunks, whose result does not depend on the order they arrive in.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -50,8 +53,18 @@ struct ExTmpl {    // one template of a launch
     int line0, n;  // its lines in the line array
     int i0, i1, j0, j1;  // grid indices of its admissible translations: [i0, i1] x [j0, j1] (empty when i0 > i1 or j0 > j1)
     int slot;            // where its output goes: map plane / candidate lists
-    unsigned koff;       // added to the grid index of its keys (a rotation's a * nx * ny; 0 otherwise)
+    unsigned koff;       // added to the grid index of its keys (a rotation's a * nx * ny; 0 otherwise); best map: the
+                         // bits of the float32 its scores are divided by
 };
+enum ExMode { kMap = 0, kTopK = 1, kBest = 2 };
+
+// Best map: where the key of grid point (i, j) lies in the key plane.  The plane is kept in the order k_exhaustive walks
+// it, sub-tile by sub-tile and inside one [row group j / 16][wave][lane], so the 64 keys a wave merges at once are 512
+// contiguous bytes.
+__device__ __forceinline__ long long best_key_index(int i, int j, int tiles_x) {
+    const int ti = i / kTileX, tj = j / kTileY, li = i % kTileX, lj = j % kTileY;
+    return ((long long)tj * tiles_x + ti) * (kTileX * kTileY) + (lj / 16) * 256 + (li / 4) * 64 + (lj % 16) * 4 + (li % 4);
+}
 
 // One read of the interleaved volume (ivol_index) at column x, row y of the line's slice.  xw: the column's part of the
 // element index (with the slice) from ex_column.  The 64-bit form clamps to the slice: its translations are admissible,
@@ -168,12 +181,13 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
     }
 }
 
-template <bool BUF32, bool TOPK>
+template <bool BUF32, int MODE>
 __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
                                                     float ty, const ExLine* __restrict__ lines, const ExTmpl* __restrict__ tm,
                                                     int T, int x0, int y0, int nx, int ny, int sx, int sy, int tiles_x,
                                                     int n_subtiles, int portions, int k, float* __restrict__ map,
                                                     long long plane, unsigned long long* __restrict__ cand) {
+    constexpr bool TOPK = MODE == kTopK, BEST = MODE == kBest;
     __shared__ unsigned long long lists[TOPK ? 4 * kChunk * kMaxK : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // Workgroup b -> (portion, template chunk).  Workgroups are observed to be dealt round-robin over the 8 XCDs (b and
@@ -197,12 +211,13 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
         const int i = ti * kTileX + wave * 4 + (lane & 3);
         const int jb = tj * kTileY + (lane >> 2);
         const int tile_i0 = ti * kTileX, tile_j0 = tj * kTileY;
+        unsigned long long bk[kRows] = {kNoKey, kNoKey, kNoKey, kNoKey};  // (best) the chunk's smallest key per point
         for (int t = t_first; t < t_end; ++t) {
             const ExTmpl P = tm[t];
             // the sub-tile against the template's admissible box (all wave-uniform)
             const bool meets = P.i0 <= P.i1 && P.j0 <= P.j1 && P.i0 < tile_i0 + kTileX && P.i1 >= tile_i0 &&
                                P.j0 < tile_j0 + kTileY && P.j1 >= tile_j0;
-            if (TOPK && !meets) continue;
+            if ((TOPK || BEST) && !meets) continue;
             bool act[kRows];
             float offy[kRows];
             // translate(tmpl, sceneTranslation + translation), dt3cpu.cpp:153.  A translation outside the box is
@@ -217,7 +232,16 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
             }
             float res[kRows] = {0.f, 0.f, 0.f, 0.f};
             if (meets) rows_score<BUF32, kRows>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
-            if (!TOPK) {
+            if (BEST) {
+                // q = score / the template's denominator, one IEEE division; pairkey = (bits of q << 32) | pair.  q >= +0
+                // or NaN, so the key order is (q, pair); a NaN q is no candidate
+                const float den = __uint_as_float(P.koff);
+#pragma unroll
+                for (int r = 0; r < kRows; ++r) {
+                    const float q = res[r] / den;
+                    if (act[r] && !(q != q)) bk[r] = min(bk[r], ((unsigned long long)__float_as_uint(q) << 32) | (unsigned)P.slot);
+                }
+            } else if (!TOPK) {
                 if (i < nx) {
                     float* out = map + (long long)P.slot * plane;
 #pragma unroll
@@ -246,6 +270,15 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
                     Lc[lane] = e;
                 }
             }
+        }
+        if (BEST) {
+            // The minimum across the workgroups that meet at this sub-tile (other chunks, other launches of the call): a
+            // 64-bit atomic minimum at agent scope.  The plain load before it may be stale, but keys only fall, so a key
+            // that does not beat it cannot beat the current one either.  The plane holds whole sub-tiles.
+            unsigned long long* kp = cand + (long long)s * (kTileX * kTileY) + threadIdx.x;
+#pragma unroll
+            for (int r = 0; r < kRows; ++r)
+                if (bk[r] < kp[r * 256]) atomicMin(kp + r * 256, bk[r]);
         }
     }
     if (TOPK) {
@@ -395,6 +428,30 @@ __global__ void __launch_bounds__(256) k_exhaustive_merge_groups(const unsigned 
     const long long n_lists = (long long)G.y * lpu;
     for (long long q = 0; q < n_lists; ++q) thr = list_offer(e, lane < k ? c[q * k + lane] : kNoKey, thr, k, lane);
     if (lane < k) b[lane] = e;
+}
+
+// ---- best map (include/fdcm.h, "Best map and detections")
+// The key plane k_exhaustive<., kBest> merged (best_key_index's order) as row-major planes of the grid: the normalised
+// score, NaN where no pair has a key, and the pair, -1 there.  Either output may be null.
+__global__ void __launch_bounds__(256) k_best_unpack(const unsigned long long* __restrict__ keys, int nx, int ny, int tiles_x,
+                                                     float* __restrict__ score, int* __restrict__ pair) {
+    const int i = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63), j = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6);
+    if (i >= nx || j >= ny) return;
+    const unsigned long long v = keys[best_key_index(i, j, tiles_x)];
+    const long long g = (long long)j * nx + i;
+    if (score) score[g] = v == kNoKey ? f_nan() : __uint_as_float((unsigned)(v >> 32));
+    if (pair) pair[g] = v == kNoKey ? -1 : (int)(unsigned)v;
+}
+
+// The pairs of the detections: best[l] is a key (score bits << 32) | g of the merged list, kNoKey from its end on.
+__global__ void k_best_gather(const unsigned long long* __restrict__ best, int k, const unsigned long long* __restrict__ keys, int nx,
+                              int tiles_x, int* __restrict__ pair) {
+    const int l = threadIdx.x;
+    if (l >= k) return;
+    const unsigned long long v = best[l];
+    if (v == kNoKey) { pair[l] = -1; return; }
+    const unsigned g = (unsigned)v;
+    pair[l] = (int)(unsigned)keys[best_key_index((int)(g % (unsigned)nx), (int)(g / (unsigned)nx), tiles_x)];
 }
 
 // ---- pose windows (include/fdcm.h, "Pose windows"): a list of jobs, each one template, a run of rotations and a small grid
@@ -738,7 +795,7 @@ void emit_records(const std::vector<unsigned long long>& best, int k, const std:
 }
 
 // Launches k_exhaustive over the templates tm (already on the device at d_tm) with the lines at d_lines.
-template <bool TOPK>
+template <int MODE>
 void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLine* d_lines, const ExTmpl* d_tm, int T, int k,
             int portions, float* map, unsigned long long* cand) {
     const int tiles_x = (g.nx + kTileX - 1) / kTileX, tiles_y = (g.ny + kTileY - 1) / kTileY;
@@ -750,11 +807,11 @@ void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLin
         const int nt = std::min(per_launch, T - t0);
         const dim3 grid((unsigned)(portions * ((nt + kChunk - 1) / kChunk)));  // portions: a multiple of 8
         if (P.buf32)
-            hipLaunchKernelGGL((k_exhaustive<true, TOPK>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+            hipLaunchKernelGGL((k_exhaustive<true, MODE>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
                                fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
                                map, plane, cand);
         else
-            hipLaunchKernelGGL((k_exhaustive<false, TOPK>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+            hipLaunchKernelGGL((k_exhaustive<false, MODE>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
                                fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
                                map, plane, cand);
         FDCM_HIP(hipGetLastError());
@@ -944,11 +1001,11 @@ void search(fdcm_featuremap* fm, const Pairs& P, int n, const fdcm_grid& g, int 
             int lpu;
             if (topk) {
                 lpu = G;
-                launch<true>(fm, P, g, (const ExLine*)d, tm, B.planes, k, G / 4, nullptr, cand);
+                launch<kTopK>(fm, P, g, (const ExLine*)d, tm, B.planes, k, G / 4, nullptr, cand);
             } else {
                 lpu = 4 * G;
                 const fdcm_grid rg{g.x0 + R.ia * g.sx, g.y0 + R.ja * g.sy, R.w, R.h, g.sx, g.sy};
-                launch<false>(fm, P, rg, (const ExLine*)d, tm, B.planes, 0, portions_for(fm, rg, B.planes), map, nullptr);
+                launch<kMap>(fm, P, rg, (const ExLine*)d, tm, B.planes, 0, portions_for(fm, rg, B.planes), map, nullptr);
                 // 32-bit keys in LDS when the angle window holds one plane: 4 workgroups per CU at R = 8 instead of 2.
                 // That kernel reads plane u for unit u: with one plane per window every group has as many planes as units.
                 if (need == 1 && B.planes != B.units) throw std::string("exhaustive search: batch planes and units differ");
@@ -967,6 +1024,83 @@ void search(fdcm_featuremap* fm, const Pairs& P, int n, const fdcm_grid& g, int 
     best.resize((size_t)TA * k);
     FDCM_HIP(hipMemcpyAsync(best.data(), d_best, best.size() * 8, hipMemcpyDeviceToHost, st));
     FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
+}
+
+// ---- best map and detections: the host driver (include/fdcm.h, "Best map and detections")
+constexpr int kBestPeakWorkgroups = 256;  // peak workgroups of the one plane: one wave folds their 4 lists each
+
+// The penalty's denominator per template, on the host as run_topk_device's: max(len, 1e-6f), or std::pow of that and tau;
+// 1 without a penalty (a division by 1 leaves every score as it is).
+std::vector<float> best_denominators(const fdcm_templates* t, int penalty, float tau) {
+    std::vector<float> den((size_t)t->T, 1.f);
+    if (penalty < 0 || t->T == 0) return den;
+    if (fdcm_templates_lengths(t, den.data()) != FDCM_OK) throw std::string(fdcm_last_error());
+    for (float& v : den) {
+        const float l = std::max(v, 1e-6f);
+        v = penalty == FDCM_DEFAULT_PENALTY ? l : std::pow(l, tau);
+    }
+    return den;
+}
+
+struct BestRun {
+    char* d = nullptr;  // search.eval
+    size_t o_unit = 0, o_seg = 0, o_best = 0, o_pair = 0, o_keys = 0, o_plane = 0, o_cand = 0;
+    int tiles_x = 0, parts = 0;
+};
+
+// Scores every pair of P (T templates x n rotations, prepared) on the grid and leaves, on the device, the merged key
+// plane of the call: one launch chain of k_exhaustive<., kBest> over all pairs into one plane set to "no key" before.
+// Pairs of templates without lines take no part.  k > 0 also lays out what the peak pass needs (the one unit, its group,
+// the merged list, the pairs of its entries, the candidate lists).  Returns false, with nothing queued, when no pair has
+// a grid point: every point is then without a candidate.
+bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau, int k,
+               BestRun& R) {
+    const std::vector<float> den = best_denominators(t, penalty, tau);
+    const size_t np = P.nl.size();
+    std::vector<ExTmpl> tm(np + 1);
+    bool any = false;
+    for (size_t u = 0; u < np; ++u) {
+        ExTmpl e = grid_tmpl(P, u, g, (int)u);
+        if (e.n == 0) { e.i0 = 0; e.i1 = -1; e.j0 = 0; e.j1 = -1; }
+        e.koff = bits_from_f(den[u / (size_t)n]);
+        any = any || (e.i0 <= e.i1 && e.j0 <= e.j1);
+        tm[u] = e;
+    }
+    if (!any) return false;
+    tm[np] = ExTmpl{0, 0, 0, g.nx - 1, 0, g.ny - 1, 0, 0};  // the peak pass's unit: the score plane, its box the whole grid
+    const int4 seg = make_int4(0, 1, 0, 0);
+    R.tiles_x = (g.nx + kTileX - 1) / kTileX;
+    const size_t n_keys = (size_t)R.tiles_x * (size_t)((g.ny + kTileY - 1) / kTileY) * (kTileX * kTileY);
+    const int max_tiles = ((g.nx - 1) / kPkTX + 1) * ((g.ny - 1) / kPkTY + 1);
+    R.parts = std::max(1, std::min(max_tiles, kBestPeakWorkgroups));
+    const size_t o_tm = al256(P.lines.size() * sizeof(ExLine));
+    R.o_unit = o_tm + np * sizeof(ExTmpl);
+    R.o_seg = al256(R.o_unit + sizeof(ExTmpl));
+    R.o_best = R.o_seg + 256;
+    R.o_pair = R.o_best + al256((size_t)kMaxK * 8);
+    R.o_keys = R.o_pair + al256((size_t)kMaxK * 4);
+    R.o_plane = R.o_keys + al256(n_keys * 8);
+    R.o_cand = R.o_plane + al256((size_t)g.nx * g.ny * 4);
+    fm->search.eval.reserve(R.o_cand + (k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0));
+    fm->search.eval_stage.reserve(R.o_pair);
+    char* d = R.d = (char*)fm->search.eval.p;
+    char* h = (char*)fm->search.eval_stage.p;
+    std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
+    std::memcpy(h + o_tm, tm.data(), tm.size() * sizeof(ExTmpl));
+    std::memcpy(h + R.o_seg, &seg, sizeof seg);
+    std::memset(h + R.o_best, 0xff, (size_t)kMaxK * 8);  // kNoKey
+    hipStream_t st = fm->stream;
+    FDCM_HIP(hipMemcpyAsync(d, h, R.o_pair, hipMemcpyHostToDevice, st));
+    FDCM_HIP(hipMemsetAsync(d + R.o_keys, 0xff, n_keys * 8, st));  // no key anywhere
+    launch<kBest>(fm, P, g, (const ExLine*)d, (const ExTmpl*)(d + o_tm), (int)np, 0, portions_for(fm, g, (int)np), nullptr,
+                  (unsigned long long*)(d + R.o_keys));
+    return true;
+}
+
+void best_unpack(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, float* score, int* pair) {
+    hipLaunchKernelGGL(k_best_unpack, dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4)), dim3(256), 0, fm->stream,
+                       (const unsigned long long*)(R.d + R.o_keys), g.nx, g.ny, R.tiles_x, score, pair);
+    FDCM_HIP(hipGetLastError());
 }
 
 // ---- pose windows: the host driver
@@ -1138,7 +1272,7 @@ void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     for (int64_t b0 = 0; b0 < T; b0 += batch) {
         const int nb = (int)std::min<int64_t>(batch, T - b0);
         float* map = out_device ? out_device : (float*)(d + o_map);
-        launch<false>(fm, P, g, (const ExLine*)(d + o_lines), (const ExTmpl*)(d + o_tm) + b0, nb, 0, portions_for(fm, g, nb), map,
+        launch<kMap>(fm, P, g, (const ExLine*)(d + o_lines), (const ExTmpl*)(d + o_tm) + b0, nb, 0, portions_for(fm, g, nb), map,
                       nullptr);
         if (!out_device)
             FDCM_HIP(hipMemcpyAsync(out_host + (size_t)b0 * g.nx * g.ny, map, (size_t)nb * plane_bytes, hipMemcpyDeviceToHost, st));
@@ -1168,6 +1302,95 @@ void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, c
     std::vector<int32_t> index;
     search(fm, P, 1, g, k, rx, ry, 0, 0, best, index);
     emit_records(best, k, index, 1, g, base, nullptr, out, n_out);
+}
+
+// Best map and detections (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  rot null: the caller's lines as they
+// are (run_search_exhaustive_peaks' note on -0).
+void run_best_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty, float tau,
+                  float* score_out, int32_t* pair_out) {
+    check_grid(g);
+    const size_t N = (size_t)g.nx * g.ny;
+    auto none = [&]() {
+        if (score_out) std::fill(score_out, score_out + N, f_nan());
+        if (pair_out) std::fill(pair_out, pair_out + N, (int32_t)-1);
+    };
+    if (t->T == 0) return none();
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    if (rot) check_rotated_size(t, rot->n);
+    Pairs P;
+    prepare_pairs(fm, t, rot, false, P);
+    BestRun R;
+    if (!best_keys(fm, P, t, rot ? rot->n : 1, g, penalty, tau, 0, R)) return none();
+    hipStream_t st = fm->stream;
+    char* plane = R.d + R.o_plane;  // one 4-byte plane, the scores and then the pairs
+    if (score_out) {
+        best_unpack(fm, R, g, (float*)plane, nullptr);
+        FDCM_HIP(hipMemcpyAsync(score_out, plane, N * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (pair_out) {
+        best_unpack(fm, R, g, nullptr, (int*)plane);
+        FDCM_HIP(hipMemcpyAsync(pair_out, plane, N * 4, hipMemcpyDeviceToHost, st));
+    }
+    FDCM_HIP(hipStreamSynchronize(st));
+}
+
+void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
+                                  int rx, int ry, int penalty, float tau, int32_t base, fdcm_match** out, int64_t* n_out) {
+    check_grid(g);
+    *n_out = 0;
+    if (t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int n = rot ? rot->n : 1;
+    if (rot) check_rotated_size(t, n);
+    Pairs P;
+    prepare_pairs(fm, t, rot, false, P);
+    BestRun R;
+    if (!best_keys(fm, P, t, n, g, penalty, tau, k, R)) return;
+    hipStream_t st = fm->stream;
+    char* d = R.d;
+    float* plane = (float*)(d + R.o_plane);
+    unsigned long long* cand = (unsigned long long*)(d + R.o_cand);
+    unsigned long long* d_best = (unsigned long long*)(d + R.o_best);
+    best_unpack(fm, R, g, plane, nullptr);
+    // the peaks of the score plane: one unit of one plane, its 32-bit form (k_exhaustive_peaks' !ANGLES)
+    auto peaks = std::max(rx, ry) <= 8 ? k_exhaustive_peaks<8, false> : k_exhaustive_peaks<kMaxRadius, false>;
+    hipLaunchKernelGGL(peaks, dim3((unsigned)R.parts), dim3(256), 0, st, (const float*)plane, g.nx, g.ny, (const ExTmpl*)(d + R.o_unit),
+                       (const int4*)nullptr, R.parts, rx, ry, 0, 1, 0, 0, g.nx - 1, 0, g.ny - 1, 0, 0, g.nx, (unsigned)(g.nx * g.ny), k, cand);
+    FDCM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_exhaustive_merge_groups, dim3(1), dim3(256), 0, st, (const unsigned long long*)cand, (const int4*)(d + R.o_seg),
+                       1, 4 * R.parts, k, d_best);
+    FDCM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_best_gather, dim3(1), dim3(64), 0, st, (const unsigned long long*)d_best, k,
+                       (const unsigned long long*)(d + R.o_keys), g.nx, R.tiles_x, (int*)(d + R.o_pair));
+    FDCM_HIP(hipGetLastError());
+    std::vector<unsigned long long> best((size_t)k);
+    std::vector<int32_t> pair((size_t)k);
+    FDCM_HIP(hipMemcpyAsync(best.data(), d_best, (size_t)k * 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipMemcpyAsync(pair.data(), d + R.o_pair, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    // one list: entry l is the pair t n + a = pair[l] at the grid point of its key (kNoKey ends the list)
+    int64_t cnt = 0;
+    while (cnt < k && best[(size_t)cnt] != kNoKey) ++cnt;
+    fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, cnt) * sizeof(fdcm_match));
+    for (int64_t l = 0; l < cnt; ++l) {
+        const unsigned gi = (unsigned)best[(size_t)l];
+        const float tx = (float)(g.x0 + (int)(gi % (unsigned)g.nx) * g.sx), ty = (float)(g.y0 + (int)(gi / (unsigned)g.nx) * g.sy);
+        fdcm_match& rec = m[l];
+        rec.tmpl_idx = base + pair[(size_t)l] / n;
+        rec.score = f_from_bits((uint32_t)(best[(size_t)l] >> 32));
+        if (rot) {  // combine(translation, M_a), float32 adds: emit_records' rule
+            const RotM& M = P.M[(size_t)pair[(size_t)l]];
+            rec.transform[0] = M.c; rec.transform[1] = M.ns; rec.transform[2] = M.mx + tx;
+            rec.transform[3] = M.s; rec.transform[4] = M.c; rec.transform[5] = M.my + ty;
+        } else {
+            rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = tx;
+            rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = ty;
+        }
+    }
+    *out = m;
+    *n_out = cnt;
 }
 
 void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, int32_t sx, int32_t sy,

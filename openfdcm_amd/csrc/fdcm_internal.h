@@ -345,6 +345,10 @@ void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, c
 void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, const fdcm_grid& g,
                                      int k, int rx, int ry, int ra, int wrap, int32_t base, fdcm_match** out, int64_t* n_out);
 // rot: null for translations only; job_offsets: n_jobs + 1, or null
+void run_best_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty, float tau,
+                  float* score_out, int32_t* pair_out);
+void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
+                                  int rx, int ry, int penalty, float tau, int32_t base, fdcm_match** out, int64_t* n_out);
 void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
                                    int64_t n_jobs, int sx, int sy, int k, int32_t base, fdcm_match** out, int64_t* n_out,
                                    int64_t* job_offsets);

@@ -323,6 +323,32 @@ class DeviceFeatureMap:
             offsets.ctypes.data_as(C.POINTER(C.c_int64))))
         return _adopt_matches(out, n.value), offsets
 
+    # ---- best map and detections (include/fdcm.h, "Best map and detections"): cs None is the translations alone
+    def best_map(self, templates, grid, cs=None, pivots=None, penalty=None, tau=1.0):
+        """(scores, pairs): per grid point the lowest length-normalised score over all templates with lines and all
+        rotations, (ny, nx) float32 with NaN where no pair is admissible, and the pair t * n + a that gave it, (ny, nx)
+        int32 with -1 there.  penalty: None, capi.DEFAULT_PENALTY or capi.EXPONENTIAL_PENALTY (with tau)."""
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        g = as_grid(grid)
+        scores = np.empty((g.ny, g.nx), dtype=np.float32)
+        pairs = np.empty((g.ny, g.nx), dtype=np.int32)
+        capi.check(capi.lib().fdcm_best_map(self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g),
+                                            -1 if penalty is None else int(penalty), float(tau), capi.fptr(scores),
+                                            pairs.ctypes.data_as(C.POINTER(C.c_int32))))
+        return scores, pairs
+
+    def exhaustive_detect(self, templates, grid, cs=None, pivots=None, k=8, rx=0, ry=0, penalty=None, tau=1.0, tmpl_index_base=0):
+        """The detections: the first k peaks of best_map's score plane by (score, grid index), a peak being a point whose
+        key is the minimum of its (2 rx + 1) x (2 ry + 1) window, as raw match records of the winning (template, rotation)
+        with the normalised score, in ascending order."""
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        g = as_grid(grid)
+        out, n = C.c_void_p(), C.c_int64()
+        capi.check(capi.lib().fdcm_search_exhaustive_detect(
+            self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), int(k), int(rx), int(ry),
+            -1 if penalty is None else int(penalty), float(tau), int(tmpl_index_base), C.byref(out), C.byref(n)))
+        return _adopt_matches(out, n.value)
+
     def rotation_score_map(self, templates, grid, cs, pivots=None):
         """(T, n, ny, nx) float32: the score of every rotated template at every grid point, NaN where not admissible."""
         rot, keep = _rotations(cs, pivots, templates.count)

@@ -1,0 +1,119 @@
+"""Times the detections (include/fdcm.h, "Best map and detections") on config 2': the feature map and the 1000 x 32-line
+synthetic templates bench.py uses, all templates on their default window (exhaustive_window) at stride 1, 2 and 4, k = 8,
+radius 8, ExponentialPenalty(1.5).  In the same run, on the same grid:
+
+  detect        one blocking fdcm_search_exhaustive_detect call
+  best_map      one blocking fdcm_best_map call (both planes to the host)
+  top-k         fdcm_search_exhaustive with the same k: the same scoring, a list per template instead of the reduction
+  peaks         fdcm_search_exhaustive_peaks with the same k and radius: a score plane per template written and read again
+  host          what a caller had before these calls: fdcm_score_map to the host (T x ny x nx floats) and the reduction of
+                tests/detect_ref.py in numpy (penalise, minimum pairkey over the templates in batches, peaks of the best
+                plane, records); its records are compared with the detect call's
+
+Each device figure is the median of --reps blocking calls after a warm-up; the host composition runs --host-reps times.
+
+    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def host_composition(dev, tset, grid, lengths, penalty, tau, k, r, batch=50):
+    """(records, seconds of the download, seconds of the reduction)."""
+    from detect_ref import normalised, pair_keys, records
+    from peaks_ref import NO_KEY, peaks
+    t0 = time.perf_counter()
+    maps = dev.score_map(tset, grid)
+    t1 = time.perf_counter()
+    T, ny, nx = maps.shape
+    best = np.full((ny, nx), NO_KEY, dtype=np.uint64)
+    for b0 in range(0, T, batch):
+        b1 = min(T, b0 + batch)
+        q = normalised(maps[b0:b1, None], lengths[b0:b1], penalty, tau)
+        keys = pair_keys(q)
+        keys[keys != NO_KEY] += np.uint64(b0)  # the pair index of the whole set
+        np.minimum(best, keys.min(axis=0), out=best)
+    none = best == NO_KEY
+    scores = (best >> np.uint64(32)).astype(np.uint32).view(np.float32).copy()
+    scores[none] = np.nan
+    pairs = (best & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    pairs[none] = -1
+    g, s = peaks(scores, k, r, r)
+    rec = records(g, s, pairs, 1, None, None, grid)
+    return rec, t1 - t0, time.perf_counter() - t1
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--host-reps", type=int, default=1, help="runs of the host composition (0: leave it out)")
+    ap.add_argument("--strides", default="1,2,4")
+    ap.add_argument("--k", type=int, default=8)
+    ap.add_argument("--radius", type=int, default=8)
+    ap.add_argument("--tau", type=float, default=1.5)
+    ap.add_argument("--json", default=None, help="also write the results here")
+    args = ap.parse_args()
+
+    from openfdcm_amd import _capi, synthetic
+    from openfdcm_amd.engine import DeviceFeatureMap, DeviceTemplates
+
+    cfg, scene, tmpls = synthetic.make_config("2p")
+    dev = DeviceFeatureMap.build(scene, depth=cfg["depth"], coeff=5.0, padding=1.0, distance=cfg["distance"])
+    tset = DeviceTemplates(tmpls)
+    lengths = tset.lengths()
+    k, r, pen, tau = args.k, args.radius, _capi.EXPONENTIAL_PENALTY, args.tau
+
+    def timed(call):
+        call()  # warm-up: workspaces, code objects
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            out = call()
+            times.append(time.perf_counter() - t0)
+        return float(np.median(times)) * 1e3, min(times) * 1e3, out
+
+    rows = []
+    for s in [int(v) for v in args.strides.split(",")]:
+        grid = dev.exhaustive_window(tset, s, s).as_tuple()
+        det_ms, det_min, recs = timed(lambda: dev.exhaustive_detect(tset, grid, k=k, rx=r, ry=r, penalty=pen, tau=tau))
+        map_ms, map_min, _ = timed(lambda: dev.best_map(tset, grid, penalty=pen, tau=tau))
+        top_ms, top_min, _ = timed(lambda: dev.exhaustive_search(tset, grid, k=k))
+        pk_ms, pk_min, per = timed(lambda: dev.exhaustive_peaks(tset, grid, k=k, rx=r, ry=r))
+        row = {"stride": s, "k": k, "r": r, "grid": list(grid), "grid_points": grid[2] * grid[3],
+               "detect_ms": round(det_ms, 3), "detect_ms_min": round(det_min, 3), "best_map_ms": round(map_ms, 3),
+               "best_map_ms_min": round(map_min, 3), "topk_ms": round(top_ms, 3), "topk_ms_min": round(top_min, 3),
+               "peaks_ms": round(pk_ms, 3), "peaks_ms_min": round(pk_min, 3), "detect_to_topk": round(det_ms / top_ms, 3),
+               "detect_to_peaks": round(det_ms / pk_ms, 3), "detections": int(len(recs)), "per_template_records": int(len(per))}
+        print(f"stride {s}: grid {grid[2]}x{grid[3]}, detect {det_ms:.2f} ms (min {det_min:.2f}), best_map {map_ms:.2f} ms, "
+              f"top-k {top_ms:.2f} ms, peaks r {r} {pk_ms:.2f} ms: detect / top-k {det_ms / top_ms:.3f}, detect / peaks "
+              f"{det_ms / pk_ms:.3f}; {len(recs)} detections for {len(per)} per-template records", flush=True)
+        if args.host_reps > 0:
+            runs = [host_composition(dev, tset, grid, lengths, pen, tau, k, r) for _ in range(args.host_reps)]
+            dl = float(np.median([v[1] for v in runs])) * 1e3
+            red = float(np.median([v[2] for v in runs])) * 1e3
+            same = runs[0][0].tobytes() == recs.tobytes()
+            row.update({"host_score_map_ms": round(dl, 1), "host_reduction_ms": round(red, 1), "host_total_ms": round(dl + red, 1),
+                        "host_to_detect": round((dl + red) / det_ms, 1), "host_records_equal": bool(same)})
+            print(f"stride {s}: host composition: score_map {dl:.0f} ms + numpy reduction {red:.0f} ms = {(dl + red) / det_ms:.0f}x "
+                  f"the detect call; records equal: {same}", flush=True)
+        rows.append(row)
+    res = {"workload": "config 2': 1024x1024 scene (200 lines, seed 1), depth 30, L2, padding 1.0; 1000 templates x 32 lines "
+                       "(seed 2), default window per stride; k %d, radius %d, ExponentialPenalty(%g)" % (k, r, tau),
+           "reps": args.reps, "host_reps": args.host_reps, "rows": rows}
+    print(json.dumps(res))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
