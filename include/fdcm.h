@@ -512,6 +512,48 @@ int fdcm_search_exhaustive_detect(const fdcm_featuremap* fm, const fdcm_template
                                   const fdcm_grid* grid, int32_t k, int32_t rx, int32_t ry, int penalty, float tau,
                                   int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out);
 
+/* Per-line caps and line costs: the truncated directional chamfer cost.  A score is a plain sum over the template's lines,
+ * so one line whose scene edge is missing (occlusion, a gap in the edges, a line the fit dropped) can cost as much as all
+ * the others matched badly.  A template set may carry one cap per line; every exhaustive call above then clamps each
+ * line's term to its cap.  The definitions are this project's (README.md, "Per-line caps and line costs"; numpy statement:
+ * tests/capped_ref.py); the reference has no counterpart.
+ * Line cost: cost_i(t) = |I_bin(i)(floor(p1_i + T + t)) - I_bin(i)(floor(p2_i + T + t))|, the term of evaluate<Dt3Cpu>; the
+ * rotation calls use the rotated line.  It is >= +0 or NaN.
+ * Cap: one float32 cap_i per template line, cap_i >= 0, finite or +inf, never NaN; +inf: no cap (-0 is stored as +0).
+ * Capped cost: capped_i = cost_i > cap_i ? cap_i : cost_i.  A NaN cost stays NaN (the point is left out of top-k, peaks,
+ * best map and detections and is NaN in maps, as before); an infinite cost under a finite cap becomes the cap; cap_i = 0
+ * switches the line off.
+ * Score of a capped set: the sum of capped_i in the order of every score here (Eigen's sum(): blocks of 8 in two packets,
+ * the trailing packet, predux, the scalar tail).  Admissibility, default windows, keys, peak rules, the denominators of q
+ * and the record layout do not look at caps.  A line keeps its cap under every rotation; a rot entry with scale does not
+ * rescale caps, as it does not rescale lengths.  A set without caps, or with every cap +inf, gives the bytes
+ * fdcm_templates_create's set gives in every call.  fdcm_search, fdcm_topk, the frame pipeline and the sharded engine
+ * ignore caps: their contract is the reference's.
+ * What a cap means: cost_i is roughly the sum of the DT3 values under the line's rasterised pixels, so cap_i = tau len_i
+ * with len_i = getLength of the line (fdcm_templates_line_lengths) means roughly "a line whose mean directional distance
+ * exceeds tau pixels counts as tau" -- approximately, within the rasteriser's factor between pixel count and length.  With
+ * FDCM_DEFAULT_PENALTY q then lies in [0, tau] up to rounding.
+ * fdcm_templates_create_capped: fdcm_templates_create with caps (one per line, in line order; NULL: all +inf).
+ * fdcm_templates_line_caps / _line_lengths: the caps (+inf for a set made by fdcm_templates_create) and the float32
+ * lengths of the lines, n_lines floats each.
+ * fdcm_line_costs: the uncapped cost of every line at n poses.  A pose is four int32 (tmpl, a, x, y): a is a rotation
+ * index of rot and must be 0 with rot == NULL, where the lines are scored as they are; (x, y) is the translation.
+ * offsets (n + 1) says where each pose's floats begin in *costs: the cost_i of tmpl's lines in line order, all NaN when the
+ * pose is not admissible for (tmpl, a) by the rule of the searches.  A template without lines contributes no floats.
+ * Identity: for an admissible pose, clamping the costs with the set's caps and summing in the order above gives exactly the
+ * score bits fdcm_search_exhaustive_windows returns for the job {tmpl, a, 1, x, y, 1, 1} at stride 1 (rot == NULL: those
+ * of fdcm_search_exhaustive on the one-point grid).
+ * FDCM_EINVAL, before any GPU work: a NaN or negative cap; n < 0; poses NULL with n > 0; what the rotation call rejects
+ * about rot; a out of range; |x| or |y| >= 2^24; tmpl outside the set; NULL outputs.  n = 0, an empty feature map or an
+ * empty template list give offsets of 0.  The call blocks; *costs (never NULL after FDCM_OK) is released with
+ * fdcm_lines_free. */
+int fdcm_templates_create_capped(const float* lines, const int64_t* offsets /* n_templates+1, in lines */, int64_t n_templates,
+                                 const float* caps /* one per line, or NULL */, fdcm_templates** out);
+int fdcm_templates_line_caps(const fdcm_templates* t, float* caps /* n_lines */);
+int fdcm_templates_line_lengths(const fdcm_templates* t, float* lengths /* n_lines */);
+int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                    const int32_t* poses /* n x 4: tmpl, a, x, y */, int64_t n, float** costs, int64_t* offsets /* n + 1 */);
+
 /* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
  *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as
  *      fdcm_edge_labels makes it (m = the distinct keys of `depth`, a byte < m an edge pixel of that label, labels circular)

@@ -12,6 +12,7 @@ import numpy as _np
 
 from . import _capi
 from .matchlist import Match, MatchList, records_of  # noqa: F401
+from . import engine as _engine
 from .engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, ShardedEngine, edge_labels, lines_from_image, lines_from_labels, search_raw, topk  # noqa: F401  (extensions)
 
 __version__ = "0.10.0"  # API level of the reference this mirrors (openfdcm.cpp:43)
@@ -336,15 +337,18 @@ class _TemplateCache:
     reference's callers pass the same Python list frame after frame (matching.cpp:279-300 copies it into a std::vector
     on every call); here that would be a device upload per call.  A hit needs the same list object with the same
     line counts and the same bytes: the list is packed (one concatenate, ~0.3 ms for 1000 x 32 lines) and compared with
-    what was uploaded, so a template edited in place is seen.  Four lists are remembered; `clear_template_cache()`
-    drops them (each holds its list and a device copy alive)."""
+    what was uploaded, so a template edited in place is seen.  The per-line caps of the exhaustive calls (line_caps) are
+    part of the key: a list used without caps and then with them gets two handles.  Four entries are remembered;
+    `clear_template_cache()` drops them (each holds its list and a device copy alive)."""
     SLOTS = 4
 
     def __init__(self):
-        self._entries = []  # most recent first: (list object, line counts, packed lines, DeviceTemplates)
+        self._entries = []  # most recent first: (list object, line counts, packed lines, DeviceTemplates, caps bytes or None)
 
-    def get(self, templates):
+    def get(self, templates, line_caps=None):
         if isinstance(templates, DeviceTemplates):
+            if line_caps is not None:
+                raise ValueError("line_caps with a DeviceTemplates: give the caps to DeviceTemplates(templates, line_caps=...)")
             return templates
         if not isinstance(templates, (list, tuple)):
             templates = list(templates)
@@ -355,19 +359,21 @@ class _TemplateCache:
         else:
             packed = _capi.pack_templates(templates)
             counts, data = packed[1].tolist(), packed[0]
-        for k, (obj, ecounts, edata, tset) in enumerate(self._entries):
-            if (obj is templates and tset._h and ecounts == counts and edata.dtype == data.dtype
+        caps = _engine.flat_line_caps(templates, line_caps, counts)
+        ckey = None if caps is None else caps.tobytes()
+        for k, (obj, ecounts, edata, tset, ecaps) in enumerate(self._entries):
+            if (obj is templates and tset._h and ecaps == ckey and ecounts == counts and edata.dtype == data.dtype
                     and edata.shape == data.shape and _np.array_equal(edata, data)):
                 if k:
                     self._entries.insert(0, self._entries.pop(k))
                 return tset
-        self._entries = [e for e in self._entries if e[0] is not templates]
+        self._entries = [e for e in self._entries if not (e[0] is templates and e[4] == ckey)]
         if packed is None:
             offsets = _np.zeros(len(counts) + 1, dtype=_np.int64)
             _np.cumsum(counts, out=offsets[1:])
             packed = (_np.ascontiguousarray(data.T, dtype=_np.float32).reshape(-1, 4), offsets)
-        tset = DeviceTemplates(templates, _packed=packed)
-        self._entries.insert(0, (templates, counts, data, tset))
+        tset = DeviceTemplates(templates, _packed=packed, _caps=caps)
+        self._entries.insert(0, (templates, counts, data, tset, ckey))
         del self._entries[self.SLOTS:]
         return tset
 
@@ -492,38 +498,40 @@ def _window(fm, tset, stride, window):
     return fm.exhaustive_window(tset, sx, sy).as_tuple()
 
 
-def exhaustive_search(featuremap, templates, stride=1, k=1, window=None):
+def exhaustive_search(featuremap, templates, stride=1, k=1, window=None, line_caps=None):
     """Score every template at every translation of a grid and keep the k best of each (1 <= k <= 64), ordered by
     (score, grid index); templates without lines give nothing.  window: (x0, y0, nx, ny, sx, sy), by default
     exhaustive_window(featuremap, templates, stride).  Returns a MatchList whose transforms are the pure translations
-    [[1, 0, tx], [0, 1, ty]], ready for penalize / sort_matches."""
+    [[1, 0, tx], [0, 1, ty]], ready for penalize / sort_matches.  line_caps: None, a scalar tau or one float array per
+    template: every line's cost is clamped to its cap (line_caps(templates, tau) states the scalar's caps)."""
     fm = _device_map(featuremap)
-    tset = _template_cache.get(templates)
+    tset = _template_cache.get(templates, line_caps)
     g = _window(fm, tset, stride, window)
     if g[2] == 0 or g[3] == 0:
         return MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
     return MatchList(fm.exhaustive_search(tset, g, k=k))
 
 
-def exhaustive_peaks(featuremap, templates, radius, stride=1, k=1, window=None):
+def exhaustive_peaks(featuremap, templates, radius, stride=1, k=1, window=None, line_caps=None):
     """exhaustive_search for detection: per template its k best peaks of the score map, ordered by (score, grid index).  A
     peak is an admissible grid point whose (score, grid index) is the smallest within radius = r or (rx, ry) grid steps
     (0 <= rx, ry <= 32) on either axis, so two peaks of one template are never that close; radius 0 is exhaustive_search.
-    Returns a MatchList of pure translations, ready for penalize / sort_matches."""
+    Returns a MatchList of pure translations, ready for penalize / sort_matches.  line_caps: exhaustive_search's."""
     rx, ry = _strides(radius)
     fm = _device_map(featuremap)
-    tset = _template_cache.get(templates)
+    tset = _template_cache.get(templates, line_caps)
     g = _window(fm, tset, stride, window)
     if g[2] == 0 or g[3] == 0:
         return MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
     return MatchList(fm.exhaustive_peaks(tset, g, k=k, rx=rx, ry=ry))
 
 
-def score_map(featuremap, templates, stride=1, window=None):
+def score_map(featuremap, templates, stride=1, window=None, line_caps=None):
     """The dense chamfer score map: (float32 array [T, ny, nx] of the scores, NaN where a translation puts the template
-    outside the feature map; grid (x0, y0, nx, ny, sx, sy)).  Point (i, j) is the translation (x0 + i sx, y0 + j sy)."""
+    outside the feature map; grid (x0, y0, nx, ny, sx, sy)).  Point (i, j) is the translation (x0 + i sx, y0 + j sy).
+    line_caps: exhaustive_search's."""
     fm = _device_map(featuremap)
-    tset = _template_cache.get(templates)
+    tset = _template_cache.get(templates, line_caps)
     g = _window(fm, tset, stride, window)
     if g[2] == 0 or g[3] == 0:
         return _np.zeros((tset.count, g[3], g[2]), dtype=_np.float32), g
@@ -561,9 +569,9 @@ def _pivots(templates, pivot, T):
     return pv
 
 
-def _rotation_args(featuremap, templates, angles, pivot):
+def _rotation_args(featuremap, templates, angles, pivot, line_caps=None):
     fm = _device_map(featuremap)
-    tset = _template_cache.get(templates)
+    tset = _template_cache.get(templates, line_caps)
     return fm, tset, _angles(angles), _pivots(templates, pivot, tset.count)
 
 
@@ -584,24 +592,25 @@ def rotation_window(featuremap, templates, angles, stride=1, pivot="center"):
 
 
 def exhaustive_rotation_search(featuremap, templates, angles, stride=1, k=1, radius=0, angle_radius=0, wrap=False,
-                               pivot="center", window=None):
+                               pivot="center", window=None, line_caps=None):
     """exhaustive_peaks over rotations: every template rotated by every angle (radians) about its pivot ("center": its
     bounding box centre, None: the origin, or a (T, 2) array) and scored at every translation of the grid.  Per template
     its k best peaks over (angle, x, y), ordered by (score, angle index, grid index); a peak is the smallest within
     radius = r or (rx, ry) grid steps and angle_radius angle steps (0 to 32 each), circular over the angle list with
     wrap.  Radii 0 give the top-k over all poses.  Returns a MatchList whose transforms are [R | m + t], ready for
-    penalize / sort_matches."""
+    penalize / sort_matches.  line_caps: exhaustive_search's; a line keeps its cap under every rotation."""
     rx, ry = _strides(radius)
-    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot)
+    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot, line_caps)
     g = _rotation_window(fm, tset, cs, pv, stride, window)
     if g[2] == 0 or g[3] == 0:
         return MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
     return MatchList(fm.exhaustive_rotation_search(tset, g, cs, pv, k=k, rx=rx, ry=ry, ra=int(angle_radius), wrap=wrap))
 
 
-def rotation_score_map(featuremap, templates, angles, stride=1, pivot="center", window=None):
-    """The dense score maps of the rotated templates: (float32 array [T, A, ny, nx], NaN where not admissible; grid)."""
-    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot)
+def rotation_score_map(featuremap, templates, angles, stride=1, pivot="center", window=None, line_caps=None):
+    """The dense score maps of the rotated templates: (float32 array [T, A, ny, nx], NaN where not admissible; grid).
+    line_caps: exhaustive_search's."""
+    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot, line_caps)
     g = _rotation_window(fm, tset, cs, pv, stride, window)
     if g[2] == 0 or g[3] == 0:
         return _np.zeros((tset.count, cs.shape[0], g[3], g[2]), dtype=_np.float32), g
@@ -620,38 +629,41 @@ def _penalty_args(penalty):
     raise TypeError("penalty must be None, DefaultPenalty or ExponentialPenalty")
 
 
-def _detect_args(featuremap, templates, angles, pivot, stride, window):
+def _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps=None):
     """(device map, template set, cs, pivots, grid): angles None is the translations alone, on exhaustive_window."""
     if angles is None:
-        fm, tset = _device_map(featuremap), _template_cache.get(templates)
+        fm, tset = _device_map(featuremap), _template_cache.get(templates, line_caps)
         return fm, tset, None, None, _window(fm, tset, stride, window)
-    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot)
+    fm, tset, cs, pv = _rotation_args(featuremap, templates, angles, pivot, line_caps)
     return fm, tset, cs, pv, _rotation_window(fm, tset, cs, pv, stride, window)
 
 
-def best_score_map(featuremap, templates, stride=1, penalty=None, angles=None, pivot="center", window=None):
+def best_score_map(featuremap, templates, stride=1, penalty=None, angles=None, pivot="center", window=None, line_caps=None):
     """The templates compared with each other: per grid point the lowest score over all templates with lines and all
     angles, each score divided as penalize(penalty, ...) divides it (None: as it is), and which pair gave it.  Returns
     (scores [ny, nx] float32, NaN where no template fits; pairs [ny, nx] int32, -1 there; grid).  With n = len(angles)
     (1 without angles) pairs // n is the template and pairs % n the angle; equal scores go to the lowest template, then
-    the lowest angle.  angles, pivot and window are exhaustive_rotation_search's."""
+    the lowest angle.  angles, pivot, window and line_caps are exhaustive_rotation_search's; with caps tau len_i and
+    DefaultPenalty the scores lie in [0, tau] up to rounding."""
     kind, tau = _penalty_args(penalty)
-    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window)
+    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
     if g[2] == 0 or g[3] == 0:
         return _np.zeros((g[3], g[2]), dtype=_np.float32), _np.zeros((g[3], g[2]), dtype=_np.int32), g
     scores, pairs = fm.best_map(tset, g, cs, pv, penalty=kind, tau=tau)
     return scores, pairs, g
 
 
-def exhaustive_detect(featuremap, templates, radius, stride=1, k=8, penalty=None, angles=None, pivot="center", window=None):
+def exhaustive_detect(featuremap, templates, radius, stride=1, k=8, penalty=None, angles=None, pivot="center", window=None,
+                      line_caps=None):
     """The dense search as a detector: the k best peaks (1 <= k <= 64) of best_score_map's score plane, a peak being a
     grid point whose (score, grid index) is the smallest within radius = r or (rx, ry) grid steps (0 to 32), whichever
     template and angle won each point.  One object in the scene gives one detection, not one per template.  Returns a
     MatchList of the winning templates' poses with the normalised scores, already in ascending score: neither penalize
-    nor sort_matches is needed."""
+    nor sort_matches is needed.  line_caps (exhaustive_search's) keeps one occluded line from costing a correct view the
+    point; line_costs tells which lines of a detection matched."""
     rx, ry = _strides(radius)
     kind, tau = _penalty_args(penalty)
-    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window)
+    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
     if g[2] == 0 or g[3] == 0:
         return MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
     return MatchList(fm.exhaustive_detect(tset, g, cs, pv, k=k, rx=rx, ry=ry, penalty=kind, tau=tau))
@@ -665,17 +677,18 @@ def template_pivots(templates, pivot="center"):
 
 
 def exhaustive_window_search(featuremap, templates, jobs, angles=None, stride=1, k=1, pivot="center", wrap=False,
-                             tmpl_index_base=0):
+                             tmpl_index_base=0, line_caps=None):
     """A list of small exhaustive searches in one call: coarse-to-fine refinement and tracking.  jobs is an (n, 7) int32
     array of rows (tmpl, a0, na, x0, y0, nx, ny): template tmpl, the run of angles a0 .. a0 + na - 1 of `angles` (mod
     len(angles) with wrap) and the translations (x0 + i sx, y0 + j sy), 0 <= i < nx, 0 <= j < ny, with na nx ny <= 65536.
     Per job, in the order given, its k best poses (1 <= k <= 64) by (score, position in the run, grid index): exactly what
     exhaustive_rotation_search(radius=0, angle_radius=0) returns for that template, those angles and that window alone.
     angles and pivot are exhaustive_rotation_search's; angles=None searches translations only (a0 = 0, na = 1) and returns
-    exhaustive_search's pure translations.  Returns (MatchList, offsets): job j's matches are offsets[j] .. offsets[j + 1]."""
+    exhaustive_search's pure translations.  line_caps: exhaustive_search's.  Returns (MatchList, offsets): job j's matches
+    are offsets[j] .. offsets[j + 1]."""
     sx, sy = _strides(stride)
     fm = _device_map(featuremap)
-    tset = _template_cache.get(templates)
+    tset = _template_cache.get(templates, line_caps)
     cs = pv = None
     if angles is not None:
         cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
@@ -729,6 +742,33 @@ def pose_windows(records, coarse_angles, fine_angles, pivots, half_angles, half_
         nx, ny = -((x0 - tx - int(half_x)) // sx) + 1, -((y0 - ty - int(half_y)) // sy) + 1
         jobs[q] = (t, a0, na, x0, y0, nx, ny)
     return jobs
+
+
+# ---------------------------------------------------------------- per-line caps and line costs (extension)
+def line_caps(templates, tau):
+    """The caps a scalar line_caps=tau stands for: per template the float32 array float32(tau) * len_i, len_i the line's
+    length sqrt(dx * dx + dy * dy) in numpy float32.  A line's cost is roughly the sum of the directional distances under
+    its pixels, so such a cap means roughly "a line whose mean distance exceeds tau pixels counts as tau" (approximately:
+    within the rasteriser's factor between pixel count and length)."""
+    return [_np.float32(tau) * l for l in _engine.line_lengths(templates)]
+
+
+def line_costs(featuremap, templates, poses, angles=None, pivot="center"):
+    """The uncapped cost of every template line at a list of poses: which edges of a detection were found.  poses is an
+    (n, 4) int32 array of rows (tmpl, a, x, y): template tmpl under angle a of `angles` (0 without angles, the lines as they
+    are) translated by (x, y).  Returns (float32 flat array, int64 offsets of n + 1): pose q's costs, one per line of its
+    template in line order, are flat[offsets[q]:offsets[q + 1]]; all NaN when the pose puts the template outside the feature
+    map.  Clamping them with the caps and summing in the scores' order gives the score of that pose bit for bit.
+    pose_windows(records, angles, angles, pivots, 0, 0, 0)[:, [0, 1, 3, 4]] turns the records of the dense searches over
+    `angles` (pivots = template_pivots(templates, pivot)) into poses; for searches without angles the poses are
+    (tmpl_idx, 0, transform[2], transform[5]).  With caps c, the matched fraction of a pose is
+    sum(len_i[cost_i <= c_i]) / sum(len_i)."""
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates)
+    cs = pv = None
+    if angles is not None:
+        cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
+    return fm.line_costs(tset, poses, cs, pv)
 
 
 from .lineio import read, write  # noqa: E402  (.lines/.scene/.tmpl files, serialization.h)

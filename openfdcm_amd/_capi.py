@@ -172,6 +172,11 @@ SYMBOLS = [
     ("fdcm_best_map", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int, C.c_float, _fp, C.POINTER(C.c_int32)]),
     ("fdcm_search_exhaustive_detect", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int32, C.c_int32, C.c_int32,
                                                C.c_int, C.c_float, C.c_int32, C.POINTER(_vp), _i64p]),
+    ("fdcm_templates_create_capped", C.c_int, [_fp, _i64p, C.c_int64, _fp, C.POINTER(_vp)]),
+    ("fdcm_templates_line_caps", C.c_int, [_vp, _fp]),
+    ("fdcm_templates_line_lengths", C.c_int, [_vp, _fp]),
+    ("fdcm_line_costs", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.POINTER(C.c_float)),
+                                  _i64p]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),
     ("fdcm_lines_free", None, [C.POINTER(C.c_float)]),

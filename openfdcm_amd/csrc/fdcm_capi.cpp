@@ -461,7 +461,8 @@ int fdcm_featuremap_evaluate(const fdcm_featuremap* fm, const float* tmpl_lines,
 }
 
 // ------------------------------------------------------------------------------------------ templates
-int fdcm_templates_create(const float* lines, const int64_t* offsets, int64_t n_templates, fdcm_templates** out) {
+// caps: one per line or null (all +inf), checked by the caller
+static int create_templates(const float* lines, const int64_t* offsets, int64_t n_templates, const float* caps, fdcm_templates** out) {
     fdcm_templates* t = nullptr;
     int rc = guarded([&] {
         require(out != nullptr, "out is null");
@@ -482,6 +483,11 @@ int fdcm_templates_create(const float* lines, const int64_t* offsets, int64_t n_
         for (int64_t i = 0; i < t->n_lines; ++i) {  // getLength, math.h:306-308
             const float dx = lines[4 * i + 2] - lines[4 * i], dy = lines[4 * i + 3] - lines[4 * i + 1];
             t->lengths[i] = std::sqrt(dx * dx + dy * dy);
+        }
+        t->caps.assign((size_t)t->n_lines, f_inf());
+        for (int64_t i = 0; i < t->n_lines && caps; ++i) {
+            t->caps[i] = caps[i] == 0.f ? 0.f : caps[i];  // (-0 as +0)
+            t->capped = t->capped || caps[i] < f_inf();
         }
         // argsort(tmpl_lengths, std::greater<>()), defaultsearch.cpp:35 / math.h:106-116: scene independent
         std::vector<long> ind;
@@ -508,6 +514,39 @@ int fdcm_templates_create(const float* lines, const int64_t* offsets, int64_t n_
     });
     if (rc != FDCM_OK) { if (t) fdcm_templates_free(t); if (out) *out = nullptr; }
     return rc;
+}
+
+int fdcm_templates_create(const float* lines, const int64_t* offsets, int64_t n_templates, fdcm_templates** out) {
+    return create_templates(lines, offsets, n_templates, nullptr, out);
+}
+
+// Per-line caps: include/fdcm.h, "Per-line caps and line costs".  The caps are checked before anything touches the device.
+int fdcm_templates_create_capped(const float* lines, const int64_t* offsets, int64_t n_templates, const float* caps,
+                                 fdcm_templates** out) {
+    int rc = guarded([&] {
+        require(out != nullptr, "out is null");
+        require(n_templates >= 0 && (n_templates == 0 || offsets), "bad offsets");
+        if (!caps || n_templates == 0) return;
+        require(offsets[0] == 0, "offsets[0] must be 0");
+        for (int64_t i = 0; i < n_templates; ++i) require(offsets[i] <= offsets[i + 1], "offsets must be ascending");
+        for (int64_t i = 0; i < offsets[n_templates]; ++i) require(caps[i] >= 0.f, "caps must be >= 0 or +inf, never NaN");
+    });
+    if (rc != FDCM_OK) { if (out) *out = nullptr; return rc; }
+    return create_templates(lines, offsets, n_templates, caps, out);
+}
+
+int fdcm_templates_line_caps(const fdcm_templates* t, float* caps) {
+    return guarded([&] {
+        require(t && (caps || t->n_lines == 0), "null argument");
+        std::copy(t->caps.begin(), t->caps.end(), caps);
+    });
+}
+
+int fdcm_templates_line_lengths(const fdcm_templates* t, float* lengths) {
+    return guarded([&] {
+        require(t && (lengths || t->n_lines == 0), "null argument");
+        std::copy(t->lengths.begin(), t->lengths.end(), lengths);
+    });
 }
 
 int fdcm_templates_free(fdcm_templates* t) {
@@ -796,6 +835,38 @@ int fdcm_search_exhaustive_detect(const fdcm_featuremap* fm, const fdcm_template
             run_search_exhaustive_detect(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, k, rx, ry, penalty, tau,
                                          tmpl_index_base, out, n_out);
         });
+    });
+}
+
+// Line costs: include/fdcm.h, "Per-line caps and line costs".  Everything that needs no handle is checked first, the poses'
+// templates against the set last: nothing here touches the device.
+int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot, const int32_t* poses,
+                    int64_t n, float** costs, int64_t* offsets) {
+    if (costs) *costs = nullptr;
+    return guarded([&] {
+        require(n >= 0, "n is negative");
+        require(n == 0 || poses, "poses is null");
+        if (rot) check_rotations(rot);  // null: the lines as they are, a table of one rotation
+        const int32_t n_rot = rot ? rot->n : 1, lim = 1 << 24;
+        for (int64_t q = 0; q < n; ++q) {
+            const int32_t* p = poses + 4 * q;
+            require(p[0] >= 0, "poses: tmpl is outside the template set");
+            require(p[1] >= 0 && p[1] < n_rot, rot ? "poses: a must be in [0, n - 1]" : "poses: a must be 0 without rotations");
+            require(p[2] > -lim && p[2] < lim && p[3] > -lim && p[3] < lim, "poses: every translation must satisfy |t| < 2^24");
+        }
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        require(costs && offsets, "null output");
+        if (rot) check_pivots(templates, rot);
+        for (int64_t q = 0; q < n && templates->T > 0; ++q)
+            require(poses[4 * q] < templates->T, "poses: tmpl is outside the template set");
+        try {
+            run_line_costs(const_cast<fdcm_featuremap*>(fm), templates, rot, poses, n, costs, offsets);
+        } catch (...) {
+            std::free(*costs);
+            *costs = nullptr;
+            throw;
+        }
     });
 }
 

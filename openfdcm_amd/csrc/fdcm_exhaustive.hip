@@ -15,9 +15,12 @@
 //   k_exhaustive_merge_groups         one wave per template of a batch: its merged list so far and its units' lists
 //   k_exhaustive_windows<BUF32>       pose windows: a wave takes a run of 4 x 16 patches of the clipped boxes of a batch's
 //                                     (job, rotation) planes, a lane per translation, and keeps a k-best list per job
+//   k_line_costs<BUF32>               line costs: a wave per pose, a lane per line of its template: the terms of the sum
 //
-// Both scoring kernels evaluate through rows_score<BUF32, ROWS>, the one statement of the sum (4 rows per lane in
-// k_exhaustive, 1 in k_exhaustive_windows).  On the host every call prepares its templates through prepare_pairs: the
+// Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP>, the one statement of the sum (4 rows per lane in
+// k_exhaustive, 1 in k_exhaustive_windows).  CAP: every term clamped to its line's cap (include/fdcm.h, "Per-line caps and
+// line costs"); the kernels are instantiated both ways and a set without a finite cap launches the ones without the clamp,
+// which are the code they were before caps existed.  On the host every call prepares its templates through prepare_pairs: the
 // lines, bins and admissible box of (template, rotation) pairs, every pair of the set for the dense calls and the pairs a
 // job list names for the pose windows; the drivers clip a pair's box to their grid (grid_range).
 //
@@ -45,10 +48,20 @@ constexpr int kMaxK = 64;
 constexpr unsigned long long kNoKey = ~0ull;
 constexpr int kMaxCoord = (1 << 24) - 1;  // valid translations: |t| < 2^24
 
-struct ExLine {  // one template line: end points, and the line's slice (bin * floats per slice, or the bin: see VolRef)
+struct ExLine {  // one template line: end points, the line's slice (bin * floats per slice, or the bin: see VolRef), its cap
     float x1, y1, x2, y2;
-    int se, pad0, pad1, pad2;
+    int se;
+    float cap;  // +inf: none
+    int pad1, pad2;
 };
+static_assert(sizeof(ExLine) == 32, "ExLine is 32 bytes");
+
+// One term of the sum: |a - b|, clamped to the line's cap when CAP.  A compare and a select, not fminf: a NaN term stays NaN.
+template <bool CAP>
+__device__ __forceinline__ float line_term(float a, float b, float cap) {
+    const float v = f_abs(a - b);
+    return CAP && v > cap ? cap : v;
+}
 struct ExTmpl {    // one template of a launch
     int line0, n;  // its lines in the line array
     int i0, i1, j0, j1;  // grid indices of its admissible translations: [i0, i1] x [j0, j1] (empty when i0 > i1 or j0 > j1)
@@ -115,8 +128,8 @@ __device__ __forceinline__ unsigned long long list_offer(unsigned long long& e, 
 // 8, p0 += p1, the trailing packet, predux (p0[0] + p0[2]) + (p0[1] + p0[3]), then the scalar tail.  Zero-initialised
 // accumulators give the same bits (0 + v == v for v >= +0), so one code path serves every n.  The one statement of the
 // sum for every kernel of this file.  res: zero on entry (the caller's initialiser: zeroing it here costs k_exhaustive
-// registers).
-template <bool BUF32, int ROWS>
+// registers).  CAP: term i is line_term's clamp of it to Lt[i].cap.
+template <bool BUF32, int ROWS, bool CAP>
 __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __restrict__ Lt, int n, float offx, const float (&offy)[ROWS],
                                            int W, unsigned uH, size_t SL, float (&res)[ROWS]) {
     const int aligned2 = (n / 8) * 8, aligned = (n / 4) * 4;
@@ -126,10 +139,11 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
 #pragma unroll
         for (int l = 0; l < 4; ++l) p0[r][l] = p1[r][l] = 0.f;
     for (int b = 0; b < aligned2; b += 8) {
-        float va[8][ROWS], vb[8][ROWS];
+        float va[8][ROWS], vb[8][ROWS], cp[8];
 #pragma unroll
         for (int l = 0; l < 8; ++l) {
             const ExLine ln = Lt[b + l];
+            cp[l] = ln.cap;
             const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
             const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
 #pragma unroll
@@ -142,8 +156,8 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
         for (int r = 0; r < ROWS; ++r)
 #pragma unroll
             for (int l = 0; l < 4; ++l) {
-                p0[r][l] = p0[r][l] + f_abs(va[l][r] - vb[l][r]);
-                p1[r][l] = p1[r][l] + f_abs(va[l + 4][r] - vb[l + 4][r]);
+                p0[r][l] = p0[r][l] + line_term<CAP>(va[l][r], vb[l][r], cp[l]);
+                p1[r][l] = p1[r][l] + line_term<CAP>(va[l + 4][r], vb[l + 4][r], cp[l + 4]);
             }
     }
 #pragma unroll
@@ -151,10 +165,11 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
 #pragma unroll
         for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + p1[r][l];
     if (aligned > aligned2) {  // the trailing packet
-        float va[4][ROWS], vb[4][ROWS];
+        float va[4][ROWS], vb[4][ROWS], cp[4];
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
             const ExLine ln = Lt[aligned2 + l];
+            cp[l] = ln.cap;
             const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
             const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
 #pragma unroll
@@ -166,7 +181,7 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
 #pragma unroll
         for (int r = 0; r < ROWS; ++r)
 #pragma unroll
-            for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + f_abs(va[l][r] - vb[l][r]);
+            for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + line_term<CAP>(va[l][r], vb[l][r], cp[l]);
     }
     if (aligned)
 #pragma unroll
@@ -177,11 +192,11 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
         const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
 #pragma unroll
         for (int r = 0; r < ROWS; ++r)
-            res[r] = res[r] + f_abs(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH) - ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH));
+            res[r] = res[r] + line_term<CAP>(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH), ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH), ln.cap);
     }
 }
 
-template <bool BUF32, int MODE>
+template <bool BUF32, int MODE, bool CAP>
 __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
                                                     float ty, const ExLine* __restrict__ lines, const ExTmpl* __restrict__ tm,
                                                     int T, int x0, int y0, int nx, int ny, int sx, int sy, int tiles_x,
@@ -231,7 +246,7 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
                 offy[r] = ty + (float)(y0 + (act[r] ? j : P.j0) * sy);
             }
             float res[kRows] = {0.f, 0.f, 0.f, 0.f};
-            if (meets) rows_score<BUF32, kRows>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
+            if (meets) rows_score<BUF32, kRows, CAP>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
             if (BEST) {
                 // q = score / the template's denominator, one IEEE division; pairkey = (bits of q << 32) | pair.  q >= +0
                 // or NaN, so the key order is (q, pair); a NaN q is no candidate
@@ -474,7 +489,7 @@ struct WinPlane {
 struct WinJob { int wave0, list0; };
 constexpr int kPatchX = 4, kPatchY = 16;
 
-template <bool BUF32>
+template <bool BUF32, bool CAP>
 __global__ void __launch_bounds__(256) k_exhaustive_windows(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
                                                             float ty, const ExLine* __restrict__ lines,
                                                             const WinPlane* __restrict__ planes, const int2* __restrict__ items,
@@ -506,13 +521,46 @@ __global__ void __launch_bounds__(256) k_exhaustive_windows(const float* __restr
         const float offx = tx + (float)(P.x0 + (act ? i : P.i0) * sx);  // translate(tmpl, sceneTranslation + translation)
         const float offy[1] = {ty + (float)(P.y0 + (act ? j : P.j0) * sy)};
         float res[1] = {0.f};
-        rows_score<BUF32, 1>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
+        rows_score<BUF32, 1, CAP>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
         const unsigned long long key = act && !(res[0] != res[0])  // a NaN score has no key
                                            ? ((unsigned long long)__float_as_uint(res[0]) << 32) | ((unsigned)(j * P.nx + i) + P.koff)
                                            : kNoKey;
         thr = list_offer(e, key, thr, k, lane);
     }
     flush();
+}
+
+// ---- line costs (include/fdcm.h, "Per-line caps and line costs"): the uncapped terms of rows_score's sum at a list of
+// poses.  A wave per pose, a lane per line, in rounds of 64 lines; the pose and where its lines and its floats are come
+// through scalar loads.  The host decided admissibility: a pose that is not writes NaN and reads nothing of the volume.
+struct CostPose {
+    int line0, n;   // its pair's lines in the line array
+    int x, y;       // the translation
+    long long out;  // where its n floats go
+    int adm, pad;
+};
+
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_line_costs(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
+                                                    const ExLine* __restrict__ lines, const CostPose* __restrict__ poses, int n_poses,
+                                                    float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (w >= n_poses) return;  // wave-uniform
+    const CostPose P = poses[w];
+    const VolRef V = make_volref(vol, SL, m, BUF32);
+    const unsigned uH = (unsigned)H;
+    const float offx = tx + (float)P.x, offy = ty + (float)P.y;  // translate(tmpl, sceneTranslation + translation)
+    for (int l = lane; l < P.n; l += 64) {
+        float v = f_nan();
+        if (P.adm) {  // wave-uniform
+            const ExLine ln = lines[P.line0 + l];
+            const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
+            const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
+            v = line_term<false>(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy), uH), ex_read<BUF32>(V, c2, (int)(ln.y2 + offy), uH), 0.f);
+        }
+        out[P.out + l] = v;
+    }
 }
 
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
@@ -577,10 +625,10 @@ void check_grid(const fdcm_grid& g) {
 }
 
 // One line for the kernels: closestOrientation with the host libm (dt3cpu.cpp:144-148, as fdcm_seam.hip's run_evaluate).
-ExLine line_record(const fdcm_featuremap* fm, const float* p, bool buf32, size_t SL) {
+ExLine line_record(const fdcm_featuremap* fm, const float* p, float cap, bool buf32, size_t SL) {
     const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
     const int bin = closest_orientation(fm->keys.data(), (int)fm->m, angle);
-    return ExLine{p[0], p[1], p[2], p[3], buf32 ? (int)((unsigned)bin * (unsigned)SL) : bin, 0, 0, 0};
+    return ExLine{p[0], p[1], p[2], p[3], buf32 ? (int)((unsigned)bin * (unsigned)SL) : bin, cap, 0, 0};
 }
 
 void begin(fdcm_featuremap* fm) {
@@ -664,7 +712,8 @@ void on_threads(int nth, const char* what, F part) {
 
 // ---- the host preparation, the one of every call
 // (template, rotation) pairs, each prepared once: its rotated lines (RotM's rule; the caller's own lines when there is no
-// table), their bins (line_record) and its admissible box in translation coordinates.  The dense calls prepare every pair
+// table), their bins (line_record), their caps (the line's own under every rotation) and its admissible box in translation
+// coordinates.  The dense calls prepare every pair
 // of the set; the pose windows the distinct pairs a run of jobs names.
 struct Pairs {
     std::vector<int64_t> key;    // tmpl * n + a, ascending; empty: every pair of the set, pair u being tmpl * n + a = u
@@ -673,6 +722,7 @@ struct Pairs {
     std::vector<Box> box;
     std::vector<RotM> M;  // (rotations only)
     bool buf32 = true;    // VolRef's form for the kernels that read the lines
+    bool capped = false;  // the set has a finite cap: the scoring kernels that clamp
     size_t SL = 0;
     size_t find(int64_t k) const { return (size_t)(std::lower_bound(key.begin(), key.end(), k) - key.begin()); }
 };
@@ -687,6 +737,7 @@ void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdc
     const size_t np = all ? (size_t)(t->T * n) : W.key.size();
     auto key_of = [&](size_t u) { return all ? (int64_t)u : W.key[u]; };
     W.SL = ivol_slice_floats(fm->W, fm->H);
+    W.capped = t->capped;
     W.buf32 = !flat && (size_t)fm->m * W.SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
     W.line0.assign(np, 0);
     W.nl.assign(np, 0);
@@ -729,7 +780,8 @@ void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdc
                 const int64_t l0 = rot ? rt.offsets[u - p] : t->offsets[(size_t)i];
                 W.box[u] = admissible_box(fm, src, l0, W.nl[u]);
                 for (int x = 0; x < W.nl[u] && fm->m > 0; ++x)  // (an empty map has no bins: no line is read there)
-                    W.lines[(size_t)W.line0[u] + x] = line_record(fm, &src->lines[(size_t)(l0 + x) * 4], W.buf32, W.SL);
+                    W.lines[(size_t)W.line0[u] + x] =
+                        line_record(fm, &src->lines[(size_t)(l0 + x) * 4], t->caps[(size_t)(t->offsets[(size_t)i] + x)], W.buf32, W.SL);
             }
             p = q;
         }
@@ -806,14 +858,10 @@ void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLin
     for (int t0 = 0; t0 < T; t0 += per_launch) {
         const int nt = std::min(per_launch, T - t0);
         const dim3 grid((unsigned)(portions * ((nt + kChunk - 1) / kChunk)));  // portions: a multiple of 8
-        if (P.buf32)
-            hipLaunchKernelGGL((k_exhaustive<true, MODE>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
-                               fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
-                               map, plane, cand);
-        else
-            hipLaunchKernelGGL((k_exhaustive<false, MODE>), grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
-                               fm->tx, fm->ty, d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k,
-                               map, plane, cand);
+        auto kern = P.capped ? (P.buf32 ? k_exhaustive<true, MODE, true> : k_exhaustive<false, MODE, true>)
+                             : (P.buf32 ? k_exhaustive<true, MODE, false> : k_exhaustive<false, MODE, false>);
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty, d_lines,
+                           d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k, map, plane, cand);
         FDCM_HIP(hipGetLastError());
     }
 }
@@ -1209,7 +1257,8 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     unsigned long long* d_best = (unsigned long long*)(d + o_best);
     const float* vol = fm->vol.as<float>();
     for (const Batch& B : batches) {
-        auto kern = W.buf32 ? k_exhaustive_windows<true> : k_exhaustive_windows<false>;
+        auto kern = W.capped ? (W.buf32 ? k_exhaustive_windows<true, true> : k_exhaustive_windows<false, true>)
+                             : (W.buf32 ? k_exhaustive_windows<true, false> : k_exhaustive_windows<false, false>);
         hipLaunchKernelGGL(kern, dim3((unsigned)((B.waves + 3) / 4)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
                            fm->ty, (const ExLine*)d, (const WinPlane*)(d + o_pl) + B.p0, (const int2*)(d + o_it) + B.i0,
                            (const WinJob*)(d + o_jt) + B.b0, B.items, B.ipw, sx, sy, k, cand);
@@ -1461,6 +1510,64 @@ void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t,
     emit_records(
         best, k, n_jobs, [&](int64_t q) { return base + jobs[q].tmpl; }, [&](int64_t q) -> const fdcm_grid& { return grids[(size_t)q]; },
         [&](int64_t q, int e) { return rot ? &Mjob[(size_t)(m0[(size_t)q] + e)] : nullptr; }, out, n_out, job_offsets);
+}
+
+// Line costs (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  Poses go in rounds of kCostPoses; a round
+// prepares the distinct pairs its poses name as the pose windows prepare theirs, uploads lines and poses in one copy,
+// runs k_line_costs and downloads its floats.  rot null: the caller's lines as they are.
+constexpr int64_t kCostPoses = 1 << 20;
+
+void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                    float** costs, int64_t* offsets) {
+    std::fill(offsets, offsets + n + 1, (int64_t)0);
+    *costs = (float*)std::malloc(sizeof(float));
+    if (!*costs) throw std::string("out of memory");
+    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
+    for (int64_t q = 0; q < n; ++q) {
+        const int64_t i = poses[4 * q];
+        offsets[q + 1] = offsets[q] + (t->offsets[(size_t)i + 1] - t->offsets[(size_t)i]);
+    }
+    const int64_t total = offsets[n];
+    if (total == 0) return;
+    std::free(*costs);
+    *costs = (float*)std::malloc((size_t)total * sizeof(float));
+    if (!*costs) throw std::string("out of memory");
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int nr = rot ? rot->n : 1;
+    const float* vol = fm->vol.as<float>();
+    hipStream_t st = fm->stream;
+    for (int64_t q0 = 0; q0 < n; q0 += kCostPoses) {
+        const int64_t q1 = std::min(n, q0 + kCostPoses), floats = offsets[q1] - offsets[q0];
+        if (floats == 0) continue;
+        Pairs W;
+        for (int64_t q = q0; q < q1; ++q) W.key.push_back((int64_t)poses[4 * q] * nr + poses[4 * q + 1]);
+        std::sort(W.key.begin(), W.key.end());
+        W.key.erase(std::unique(W.key.begin(), W.key.end()), W.key.end());
+        prepare_pairs(fm, t, rot, false, W);
+        std::vector<CostPose> tab((size_t)(q1 - q0));
+        for (int64_t q = q0; q < q1; ++q) {
+            const int32_t* p = poses + 4 * q;
+            const size_t u = W.find((int64_t)p[0] * nr + p[1]);
+            const Box& b = W.box[u];
+            const bool adm = b.any && p[2] >= b.x0 && p[2] <= b.x1 && p[3] >= b.y0 && p[3] <= b.y1;
+            tab[(size_t)(q - q0)] = CostPose{W.line0[u], W.nl[u], p[2], p[3], (long long)(offsets[q] - offsets[q0]), adm ? 1 : 0, 0};
+        }
+        const size_t o_tab = al256(W.lines.size() * sizeof(ExLine)), o_out = o_tab + al256(tab.size() * sizeof(CostPose));
+        fm->search.eval.reserve(o_out + al256((size_t)floats * sizeof(float)));
+        fm->search.eval_stage.reserve(o_out);
+        char* d = (char*)fm->search.eval.p;
+        char* h = (char*)fm->search.eval_stage.p;
+        std::memcpy(h, W.lines.data(), W.lines.size() * sizeof(ExLine));
+        std::memcpy(h + o_tab, tab.data(), tab.size() * sizeof(CostPose));
+        FDCM_HIP(hipMemcpyAsync(d, h, o_out, hipMemcpyHostToDevice, st));
+        auto kern = W.buf32 ? k_line_costs<true> : k_line_costs<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((tab.size() + 3) / 4)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+                           fm->tx, fm->ty, (const ExLine*)d, (const CostPose*)(d + o_tab), (int)tab.size(), (float*)(d + o_out));
+        FDCM_HIP(hipGetLastError());
+        FDCM_HIP(hipMemcpyAsync(*costs + offsets[q0], d + o_out, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here; the next round reuses the staging)
+    }
 }
 
 }  // namespace fdcm

@@ -271,6 +271,8 @@ struct fdcm_templates {
     std::vector<float> lines;       // host copy
     std::vector<int64_t> offsets;   // T+1
     std::vector<float> lengths;     // per line: getLength, math.h:306-308
+    std::vector<float> caps;        // per line: the cap of its cost in the exhaustive calls, +inf for none (include/fdcm.h)
+    bool capped = false;            // some cap is finite: the exhaustive calls take their clamping kernels
     std::vector<int32_t> sorted;    // per template: line indices by descending length (argsort, math.h:106-116)
     fdcm::DevBuf d_lines, d_offsets, d_lengths, d_sorted;
 };
@@ -352,6 +354,9 @@ void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, 
 void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
                                    int64_t n_jobs, int sx, int sy, int k, int32_t base, fdcm_match** out, int64_t* n_out,
                                    int64_t* job_offsets);
+// poses: n x (tmpl, a, x, y), checked; *costs is malloc'ed; offsets: n + 1
+void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                    float** costs, int64_t* offsets);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

@@ -58,6 +58,47 @@ def as_pose_windows(jobs):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def as_poses(poses):
+    """(n, 4) contiguous int32 rows (tmpl, a, x, y) of fdcm_line_costs."""
+    a = np.asarray(poses)
+    if a.size == 0:
+        return np.zeros((0, 4), dtype=np.int32)
+    if a.ndim != 2 or a.shape[1] != 4 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("poses must be an (n, 4) integer array: tmpl, a, x, y")
+    if np.any(a != a.astype(np.int32)):
+        raise ValueError("poses: a value does not fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def line_lengths(templates):
+    """Per template the float32 lengths of its lines, sqrt(dx * dx + dy * dy) in numpy float32."""
+    out = []
+    for t in templates:
+        a = np.asarray(t, dtype=np.float32).reshape(4, -1)
+        dx, dy = a[2] - a[0], a[3] - a[1]
+        out.append(np.sqrt(dx * dx + dy * dy))
+    return out
+
+
+def flat_line_caps(templates, line_caps, counts=None):
+    """The caps of a template list as one float32 array in line order, or None for no caps.  line_caps: None, a scalar tau
+    (caps float32(tau) * len_i, line_lengths) or one float array per template."""
+    if line_caps is None:
+        return None
+    if np.isscalar(line_caps) or (isinstance(line_caps, np.ndarray) and line_caps.ndim == 0):
+        per = [np.float32(line_caps) * l for l in line_lengths(templates)]
+    else:
+        per = [np.asarray(c, dtype=np.float32).reshape(-1) for c in line_caps]
+    if counts is None:
+        counts = [np.asarray(t).reshape(4, -1).shape[1] for t in templates]
+    if len(per) != len(counts) or any(len(c) != n for c, n in zip(per, counts)):
+        raise ValueError("line_caps needs one array per template with one cap per line")
+    flat = np.concatenate(per).astype(np.float32) if per else np.zeros(0, dtype=np.float32)
+    if np.any(np.isnan(flat)) or np.any(flat < 0):
+        raise ValueError("line_caps must be >= 0 or +inf, never NaN")
+    return np.ascontiguousarray(flat)
+
+
 def _pixels(a, what):
     """(pointer, width, height, row_stride, on_device, keep-alive) of a 2-D uint8 numpy array (copied unless its rows are
     contiguous) or a 2-D CUDA torch.uint8 tensor (by data_ptr(), after its stream's pending work)."""
@@ -349,6 +390,24 @@ class DeviceFeatureMap:
             -1 if penalty is None else int(penalty), float(tau), int(tmpl_index_base), C.byref(out), C.byref(n)))
         return _adopt_matches(out, n.value)
 
+    def line_costs(self, templates, poses, cs=None, pivots=None):
+        """Line costs (include/fdcm.h, "Per-line caps and line costs"): poses (n, 4) int32 rows (tmpl, a, x, y), a an index
+        into the rotations cs (0 with cs None, the lines as they are).  Returns (float32 costs, int64 offsets of n + 1): pose
+        q's floats are costs[offsets[q]:offsets[q + 1]], the uncapped cost of every line of its template in line order, NaN
+        throughout when the pose is not admissible."""
+        poses = as_poses(poses)
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        out = C.POINTER(C.c_float)()
+        offsets = np.zeros(poses.shape[0] + 1, dtype=np.int64)
+        capi.check(capi.lib().fdcm_line_costs(self._h, templates._h, C.byref(rot) if rot is not None else None,
+                                              poses.ctypes.data_as(C.POINTER(C.c_int32)), poses.shape[0], C.byref(out),
+                                              offsets.ctypes.data_as(C.POINTER(C.c_int64))))
+        try:
+            n = int(offsets[-1])
+            return (np.ctypeslib.as_array(out, shape=(n,)).copy() if n else np.zeros(0, dtype=np.float32)), offsets
+        finally:
+            capi.lib().fdcm_lines_free(out)
+
     def rotation_score_map(self, templates, grid, cs, pivots=None):
         """(T, n, ny, nx) float32: the score of every rotated template at every grid point, NaN where not admissible."""
         rot, keep = _rotations(cs, pivots, templates.count)
@@ -397,15 +456,36 @@ class DeviceFeatureMap:
 
 
 class DeviceTemplates:
-    """Owns an fdcm_templates handle: a list of LineArrays resident in HBM."""
+    """Owns an fdcm_templates handle: a list of LineArrays resident in HBM.  line_caps (None, a scalar tau or one float
+    array per template: flat_line_caps) gives every line a cap of its cost in the exhaustive calls (include/fdcm.h, "Per-line
+    caps and line costs"); search() and the rest of the reference path ignore it."""
 
-    def __init__(self, templates, _packed=None):
+    def __init__(self, templates, line_caps=None, _packed=None, _caps=None):
         flat, offsets = _packed if _packed is not None else capi.pack_templates(templates)
         self.count = len(offsets) - 1
+        self.n_lines = int(offsets[-1])
+        caps = _caps if _caps is not None else flat_line_caps(templates, line_caps, np.diff(offsets).tolist())
         h = C.c_void_p()
-        capi.check(capi.lib().fdcm_templates_create(capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                    self.count, C.byref(h)))
+        if caps is None:
+            capi.check(capi.lib().fdcm_templates_create(capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                        self.count, C.byref(h)))
+        else:
+            capi.check(capi.lib().fdcm_templates_create_capped(capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                               self.count, capi.fptr(caps), C.byref(h)))
         self._h = h
+        self._offsets = np.array(offsets, dtype=np.int64)
+
+    def line_caps(self):
+        """One float32 array of caps per template (+inf: no cap)."""
+        out = np.zeros(self.n_lines, dtype=np.float32)
+        capi.check(capi.lib().fdcm_templates_line_caps(self._h, capi.fptr(out)))
+        return [out[a:b] for a, b in zip(self._offsets[:-1], self._offsets[1:])]
+
+    def line_lengths(self):
+        """One float32 array per template: the lengths of its lines as the handle holds them."""
+        out = np.zeros(self.n_lines, dtype=np.float32)
+        capi.check(capi.lib().fdcm_templates_line_lengths(self._h, capi.fptr(out)))
+        return [out[a:b] for a, b in zip(self._offsets[:-1], self._offsets[1:])]
 
     def lengths(self):
         out = np.zeros(self.count, dtype=np.float32)

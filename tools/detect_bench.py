@@ -11,8 +11,10 @@ radius 8, ExponentialPenalty(1.5).  In the same run, on the same grid:
                 plane, records); its records are compared with the detect call's
 
 Each device figure is the median of --reps blocking calls after a warm-up; the host composition runs --host-reps times.
+--line-caps TAU gives every template line the cap TAU * its length (include/fdcm.h, "Per-line caps and line costs") in every
+call of the run, the host composition's score map included.  Off by default.
 
-    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--json out.json]
+    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--line-caps TAU] [--json out.json]
 """
 import argparse
 import json
@@ -60,6 +62,7 @@ def main():
     ap.add_argument("--k", type=int, default=8)
     ap.add_argument("--radius", type=int, default=8)
     ap.add_argument("--tau", type=float, default=1.5)
+    ap.add_argument("--line-caps", type=float, default=None, metavar="TAU", help="cap every line's cost at TAU * its length")
     ap.add_argument("--json", default=None, help="also write the results here")
     args = ap.parse_args()
 
@@ -68,7 +71,7 @@ def main():
 
     cfg, scene, tmpls = synthetic.make_config("2p")
     dev = DeviceFeatureMap.build(scene, depth=cfg["depth"], coeff=5.0, padding=1.0, distance=cfg["distance"])
-    tset = DeviceTemplates(tmpls)
+    tset = DeviceTemplates(tmpls, line_caps=args.line_caps)
     lengths = tset.lengths()
     k, r, pen, tau = args.k, args.radius, _capi.EXPONENTIAL_PENALTY, args.tau
 
@@ -109,6 +112,8 @@ def main():
     res = {"workload": "config 2': 1024x1024 scene (200 lines, seed 1), depth 30, L2, padding 1.0; 1000 templates x 32 lines "
                        "(seed 2), default window per stride; k %d, radius %d, ExponentialPenalty(%g)" % (k, r, tau),
            "reps": args.reps, "host_reps": args.host_reps, "rows": rows}
+    if args.line_caps is not None:
+        res["line_caps_tau"] = args.line_caps
     print(json.dumps(res))
     if args.json:
         with open(args.json, "w") as f:

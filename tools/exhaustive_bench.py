@@ -14,8 +14,11 @@ box), and the lookup rate: 2 lookups per template line and admissible translatio
 evaluate<Dt3Cpu> (the reference's code, one host thread) on a random sample of admissible translations, the same
 lookups per translation.
 
+--line-caps TAU gives every template line the cap TAU * its length (include/fdcm.h, "Per-line caps and line costs"): the
+same cases on the kernels that clamp each line's cost.  Off by default.
+
     python tools/exhaustive_bench.py [--reps 5] [--cpu-sample 20000] [--radii 1,8,32] [--rot-cases 0:0,8:1,8:2]
-                                     [--only-rotations] [--json out.json]
+                                     [--only-rotations] [--line-caps TAU] [--json out.json]
 """
 import argparse
 import json
@@ -56,8 +59,9 @@ def rotation_cases(args, dev, tmpls, timed):
     angles = np.arange(args.rot_angles) * (2 * np.pi / args.rot_angles)
     cs = openfdcm._angles(angles)
     piv = openfdcm._pivots(sub, "center", len(sub))
-    tset = DeviceTemplates(sub)
-    rs = DeviceTemplates([openfdcm_rotate(t, c, s, p) for t, p in zip(sub, piv) for c, s in cs])
+    tset = DeviceTemplates(sub, line_caps=args.line_caps)
+    caps = None if args.line_caps is None else [c for c in openfdcm.line_caps(sub, args.line_caps) for _ in cs]  # a line keeps its cap
+    rs = DeviceTemplates([openfdcm_rotate(t, c, s, p) for t, p in zip(sub, piv) for c, s in cs], line_caps=caps)
     k = args.peak_k
     cases = [tuple(int(v) for v in c.split(":")) for c in args.rot_cases.split(",")]
     out = {"templates": len(sub), "angles": len(cs), "k": k, "wrap": True, "rows": []}
@@ -108,6 +112,7 @@ def main():
     ap.add_argument("--rot-strides", default="1,2")
     ap.add_argument("--rot-cases", default="0:0,8:1,8:2", help="rx=ry:ra pairs; empty: no rotation cases")
     ap.add_argument("--only-rotations", action="store_true", help="skip the translation-only cases and the CPU figure")
+    ap.add_argument("--line-caps", type=float, default=None, metavar="TAU", help="cap every line's cost at TAU * its length")
     ap.add_argument("--json", default=None, help="also write the results here")
     args = ap.parse_args()
 
@@ -117,7 +122,7 @@ def main():
 
     cfg, scene, tmpls = synthetic.make_config("2p")
     dev = DeviceFeatureMap.build(scene, depth=cfg["depth"], coeff=5.0, padding=1.0, distance=cfg["distance"])
-    tset = DeviceTemplates(tmpls)
+    tset = DeviceTemplates(tmpls, line_caps=args.line_caps)
     n_lines = int(sum(t.shape[1] for t in tmpls))
     bx = boxes(dev, tmpls)
     rows = []
@@ -165,6 +170,8 @@ def main():
     rot = rotation_cases(args, dev, tmpls, timed) if args.rot_cases else {}
     if args.only_rotations:
         res = {"workload": "config 2' rotations", "rotations": rot}
+        if args.line_caps is not None:
+            res["line_caps_tau"] = args.line_caps
         print(json.dumps(res))
         if args.json:
             with open(args.json, "w") as f:
@@ -193,6 +200,8 @@ def main():
     res = {"workload": "config 2': 1024x1024 scene (200 lines, seed 1), depth 30, L2, padding 1.0; 1000 templates x 32 lines "
                        "(seed 2), default window per stride", "template_lines": n_lines, "gpu": rows, "peaks": peaks, "rotations": rot,
            "cpu": cpu}
+    if args.line_caps is not None:
+        res["line_caps_tau"] = args.line_caps
     print(json.dumps(res))
     if args.json:
         with open(args.json, "w") as f:
