@@ -512,6 +512,43 @@ int fdcm_search_exhaustive_detect(const fdcm_featuremap* fm, const fdcm_template
                                   const fdcm_grid* grid, int32_t k, int32_t rx, int32_t ry, int penalty, float tau,
                                   int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out);
 
+/* Detections suppressed by footprint overlap: the greedy rule of object detectors in place of the radius.  A radius counts
+ * grid steps of the template origin and is one for all templates; here a detection suppresses the points whose posed
+ * template lies where its own does.  The definitions are this project's (README.md, "Detections by footprint overlap";
+ * numpy statement: tests/nms_ref.py).
+ * Inputs: those of fdcm_search_exhaustive_detect without rx, ry, with overlap_permille (0 .. 1000) and margin (0 .. 4096
+ * pixels).  Candidates, q, pairkey, best(g) and key(g) = (bits of q(best(g)) << 32) | g are the best map's, caps included.
+ * Footprint of a pair u = (t, a): over the end points of the lines of M_a(t), the float32 values the searches score (rot ==
+ * NULL: the caller's lines as they are), fx0 = floor(min x) - margin, fx1 = floor(max x) + margin, fy0 and fy1 likewise,
+ * computed in int64, clamped to [-2^25, 2^25] and stored as int32.  The box is the pixel rectangle [fx0, fx1] x [fy0, fy1],
+ * ends inclusive: width and height are at least 1.  A template without lines, or with a NaN end point, has the empty box
+ * (0, 0, -1, -1); it is never a candidate, so the box is never read.  Caps and penalties do not enter.  The footprint of
+ * grid point g is F(g) = box(best(g)) + t_g with t_g = (x0 + i sx, y0 + j sy); the scene translation T is common to all
+ * points and left out.
+ * Overlap, exact in int64: I(g, h) is the area of F(g) n F(h), max(0, min(x1) - max(x0) + 1) * max(0, min(y1) - max(y0) + 1);
+ * U = A(g) + A(h) - I; h suppresses g when 1000 I > overlap_permille U (sides are at most 2^26 + 1, so 1000 U < 2^63).
+ * Greedy rule: S_0 is the set of grid points with a candidate.  For n = 0, 1, ..: stop when n = k or S_n is empty;
+ * otherwise d_n is the point of the smallest key in S_n and S_(n+1) = S_n \ {d_n} \ {g : d_n suppresses g}.
+ * Output: the d_n in order (1 <= k <= 64), as records {t + tmpl_index_base, q, {c, -s, m.x + t.x, s, c, m.y + t.y}} of
+ * best(d_n), exactly the record fdcm_search_exhaustive_detect would emit for that point; keys ascend.  boxes_out (4 k
+ * int32, or NULL): F(d_n) as x0, y0, x1, y1 per record.
+ * Identities: overlap_permille = 1000 suppresses nothing (I <= U): the call is fdcm_search_exhaustive_detect with rx = ry =
+ * 0, record for record, whatever the margin.  overlap_permille = 0 accepts no two detections whose footprints share a
+ * pixel.  Results are a function of the inputs alone.
+ * fdcm_templates_footprints (host only, no device work): the footprints the call uses, 4 int32 x0, y0, x1, y1 per pair u =
+ * t n + a (n = 1 with rot == NULL).  fdcm_lines_footprints: the same for a set given as fdcm_templates_create takes it
+ * (packed lines, n_templates + 1 offsets), for callers without a handle: a process without a device has none.
+ * FDCM_EINVAL, before any GPU work: everything fdcm_search_exhaustive_detect rejects (nx ny > 2^26 and T n > 2^31 - 1
+ * included), overlap_permille outside 0 .. 1000, margin outside 0 .. 4096.  Empty inputs give zero records.  The call
+ * blocks; concurrent callers of one feature map take turns.  Release the records with fdcm_matches_free. */
+int fdcm_search_exhaustive_detect_nms(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                                      const fdcm_grid* grid, int32_t k, int32_t overlap_permille, int32_t margin, int penalty, float tau,
+                                      int32_t tmpl_index_base, fdcm_match** out, int32_t* boxes_out /* 4 k, or NULL */, int64_t* n_out);
+int fdcm_templates_footprints(const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */, int32_t margin,
+                              int32_t* boxes_out);
+int fdcm_lines_footprints(const float* lines, const int64_t* offsets, int64_t n_templates, const fdcm_rotations* rot /* or NULL */,
+                          int32_t margin, int32_t* boxes_out);
+
 /* Per-line caps and line costs: the truncated directional chamfer cost.  A score is a plain sum over the template's lines,
  * so one line whose scene edge is missing (occlusion, a gap in the edges, a line the fit dropped) can cost as much as all
  * the others matched badly.  A template set may carry one cap per line; every exhaustive call above then clamps each

@@ -669,6 +669,36 @@ def exhaustive_detect(featuremap, templates, radius, stride=1, k=8, penalty=None
     return MatchList(fm.exhaustive_detect(tset, g, cs, pv, k=k, rx=rx, ry=ry, penalty=kind, tau=tau))
 
 
+def exhaustive_detect_nms(featuremap, templates, overlap=0.3, stride=1, k=8, penalty=None, angles=None, pivot="center", window=None,
+                          line_caps=None, margin=0, return_boxes=False):
+    """exhaustive_detect with greedy suppression by footprint overlap in place of the radius: the best point of
+    best_score_map's plane is a detection, every point whose footprint overlaps the detection's by more than `overlap`
+    (intersection over union, 0 to 1, taken in thousandths) is dropped, and so on up to k detections (1 <= k <= 64).  The
+    footprint of a point is the bounding box of the winning template's (rotated) line end points, widened by margin pixels
+    (0 to 4096), at the point's translation: parts of different sizes lying against each other each keep their
+    detections, and one large part is reported once.  overlap=1 suppresses nothing and equals exhaustive_detect(radius=0).
+    Returns a MatchList in ascending score, and with return_boxes also the (n, 4) int32 footprints x0, y0, x1, y1 (ends
+    inclusive, in the translations' coordinates).  The other arguments are exhaustive_detect's."""
+    kind, tau = _penalty_args(penalty)
+    permille = int(round(1000 * float(overlap)))
+    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
+    if g[2] == 0 or g[3] == 0:
+        empty = MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
+        return (empty, _np.zeros((0, 4), dtype=_np.int32)) if return_boxes else empty
+    res = fm.exhaustive_detect_nms(tset, g, cs, pv, k=k, overlap_permille=permille, margin=margin, penalty=kind, tau=tau,
+                                   boxes=return_boxes)
+    return (MatchList(res[0]), res[1]) if return_boxes else MatchList(res)
+
+
+def template_footprints(templates, angles=None, pivot="center", margin=0):
+    """The (T, A, 4) int32 footprints x0, y0, x1, y1 exhaustive_detect_nms uses for every template and angle (A = 1 without
+    angles: the lines as they are); (0, 0, -1, -1) for a template without lines.  No device work."""
+    from .engine import lines_footprints
+    if angles is None:
+        return lines_footprints(templates, margin=margin)
+    return lines_footprints(templates, _angles(angles), _pivots(templates, pivot, len(templates)), margin=margin)
+
+
 # ---------------------------------------------------------------- pose windows: refinement and tracking (extension)
 def template_pivots(templates, pivot="center"):
     """The (T, 2) float32 pivots the rotation searches use for pivot="center" (each template's bounding box centre), an

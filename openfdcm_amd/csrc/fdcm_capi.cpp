@@ -838,6 +838,54 @@ int fdcm_search_exhaustive_detect(const fdcm_featuremap* fm, const fdcm_template
     });
 }
 
+// Detections by footprint overlap: include/fdcm.h, "Detections suppressed by footprint overlap".  The detect call's checks
+// with the overlap threshold and the margin in place of the radii: nothing here touches the device.
+int fdcm_search_exhaustive_detect_nms(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                      const fdcm_grid* grid, int32_t k, int32_t overlap_permille, int32_t margin, int penalty, float tau,
+                                      int32_t tmpl_index_base, fdcm_match** out, int32_t* boxes_out, int64_t* n_out) {
+    return guarded([&] {
+        require(k >= 1 && k <= 64, "k must be in [1, 64]");
+        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(out && n_out, "null output");
+        check_best_args(fm, templates, rot, grid, penalty, tau);
+        records_call(out, [&] {
+            run_search_exhaustive_detect_nms(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, k, overlap_permille, margin, penalty,
+                                             tau, tmpl_index_base, out, boxes_out, n_out);
+        });
+    });
+}
+
+int fdcm_templates_footprints(const fdcm_templates* templates, const fdcm_rotations* rot, int32_t margin, int32_t* boxes_out) {
+    return guarded([&] {
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        if (rot) check_rotations(rot);  // null: the lines as they are, a table of one rotation
+        require(templates != nullptr, "templates is null");
+        require(templates->T * (int64_t)(rot ? rot->n : 1) <= 0x7fffffffll, "T * n_rot must be at most 2^31 - 1");
+        require(boxes_out != nullptr || templates->T == 0, "boxes_out is null");
+        if (rot) check_pivots(templates, rot);
+        templates_footprints(templates, rot, margin, boxes_out);
+    });
+}
+
+int fdcm_lines_footprints(const float* lines, const int64_t* offsets, int64_t n_templates, const fdcm_rotations* rot, int32_t margin,
+                          int32_t* boxes_out) {
+    return guarded([&] {
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        if (rot) check_rotations(rot);
+        require(n_templates >= 0 && (n_templates == 0 || offsets), "bad offsets");
+        if (n_templates == 0) return;
+        require(offsets[0] == 0, "offsets[0] must be 0");
+        for (int64_t i = 0; i < n_templates; ++i) require(offsets[i] <= offsets[i + 1], "offsets must be ascending");
+        require(offsets[n_templates] == 0 || lines, "lines is null");
+        require(n_templates * (int64_t)(rot ? rot->n : 1) <= 0x7fffffffll, "T * n_rot must be at most 2^31 - 1");
+        require(boxes_out != nullptr, "boxes_out is null");
+        if (rot && rot->pivots)
+            for (int64_t i = 0; i < 2 * n_templates; ++i) require(std::isfinite(rot->pivots[i]), "rotations: pivots must be finite");
+        lines_footprints(lines, offsets, n_templates, rot, margin, boxes_out);
+    });
+}
+
 // Line costs: include/fdcm.h, "Per-line caps and line costs".  Everything that needs no handle is checked first, the poses'
 // templates against the set last: nothing here touches the device.
 int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot, const int32_t* poses,

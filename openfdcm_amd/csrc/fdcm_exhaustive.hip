@@ -9,6 +9,8 @@
 //                                     k-best list per wave and template kept in LDS (top-k), or keeps per point the smallest
 //                                     (normalised score, pair) key of the chunk and merges it into one plane of keys (best)
 //   k_best_unpack, k_best_gather      best map: the key plane as row-major score and pair planes; the pairs of k points
+//   k_nms_round                       detections by footprint overlap: one round of the greedy rule on the key plane, the
+//                                     previous round's winner reduced from per-workgroup minima, its victims erased
 //   k_exhaustive_peaks<R, ANGLES>     peaks: reads the score planes k_exhaustive<., false> wrote and offers every point whose
 //                                     key is the minimum of its window to a per-wave k-best list; ANGLES: the window spans
 //                                     several angles' planes (64-bit keys in LDS), else one plane (32-bit score bits)
@@ -467,6 +469,107 @@ __global__ void k_best_gather(const unsigned long long* __restrict__ best, int k
     if (v == kNoKey) { pair[l] = -1; return; }
     const unsigned g = (unsigned)v;
     pair[l] = (int)(unsigned)keys[best_key_index((int)(g % (unsigned)nx), (int)(g / (unsigned)nx), tiles_x)];
+}
+
+// ---- detections by footprint overlap (include/fdcm.h, "Detections suppressed by footprint overlap")
+// The greedy rule on the key plane k_exhaustive<., kBest> merged, one launch per round, k + 1 launches on one stream and no
+// host round trip between them.  A launch has at most kNmsWorkgroups workgroups; workgroup b owns a contiguous run of the
+// plane in storage order and leaves its partial minimum, a key (bits of q << 32) | g and the pair of that point, in entry
+// b of the arrays of this round (two sets, used in turn).  Round r:
+//   1. every workgroup reduces the partials of round r - 1 to the same winner d(r-1), key and pair (round 0: none)
+//   2. workgroup 0 writes them to the result list; a winner kNoKey ends the list: the workgroups leave kNoKey partials
+//      behind (the next launches read them) and return.  The last launch (r = k) returns here too: it only reduces.
+//   3. each workgroup walks its run, consecutive lanes reading consecutive keys: (i, j) from the storage index (the inverse
+//      of best_key_index), the point's footprint from its pair's box and its translation; the winner's once per workgroup
+//   4. the winner and every point it suppresses (1000 I > permille U, int64) become kNoKey, a plain store by the one
+//      thread that owns the entry in every round; each surviving key enters the workgroup's minimum as (q bits << 32) | g
+// The pair travels with the partial because the winner's entry of the plane is erased in the launch that needs its box.
+// A minimum does not depend on the order of its operands and suppression is a function of d(r-1) alone: no atomics, no
+// cooperative launch, and the bytes do not depend on scheduling.
+constexpr int kNmsWorkgroups = 256;
+
+// The minimum key of the workgroup and its pair, in every thread.  sk, sp: 4 entries of LDS, free on entry.
+__device__ __forceinline__ void nms_block_min(unsigned long long& key, int& pair, unsigned long long* sk, int* sp) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long k2 = __shfl_xor(key, d);
+        const int p2 = __shfl_xor(pair, d);
+        if (k2 < key) { key = k2; pair = p2; }
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sk[wave] = key; sp[wave] = pair; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        if (sk[w] < key) { key = sk[w]; pair = sp[w]; }
+    __syncthreads();  // sk and sp are free again
+}
+
+__global__ void __launch_bounds__(256) k_nms_round(unsigned long long* keys, long long n_chunks, int x0, int y0, int sx, int sy, int nx,
+                                                   int tiles_x, const int4* __restrict__ boxes, int permille, int round, int last,
+                                                   const unsigned long long* __restrict__ pk_in, const int* __restrict__ pp_in,
+                                                   unsigned long long* __restrict__ pk_out, int* __restrict__ pp_out,
+                                                   unsigned long long* __restrict__ best, int* __restrict__ pair) {
+    __shared__ unsigned long long sk[4];
+    __shared__ int sp[4];
+    unsigned long long W = kNoKey;
+    int Wp = -1;
+    if (round > 0) {
+        if (threadIdx.x < gridDim.x) { W = pk_in[threadIdx.x]; Wp = pp_in[threadIdx.x]; }
+        nms_block_min(W, Wp, sk, sp);
+        if (blockIdx.x == 0 && threadIdx.x == 0) { best[round - 1] = W; pair[round - 1] = W == kNoKey ? -1 : Wp; }
+        if (W == kNoKey || last) {  // workgroup-uniform
+            if (threadIdx.x == 0) { pk_out[blockIdx.x] = kNoKey; pp_out[blockIdx.x] = -1; }
+            return;
+        }
+    }
+    // the winner's footprint F(d) = box(pair) + t_d and its area (round 0: unused)
+    const unsigned gw = (unsigned)W;
+    int wx0 = 0, wy0 = 0, wx1 = -1, wy1 = -1;
+    if (round > 0) {
+        const int4 b = boxes[Wp];
+        const int tx = x0 + (int)(gw % (unsigned)nx) * sx, ty = y0 + (int)(gw / (unsigned)nx) * sy;
+        wx0 = b.x + tx; wy0 = b.y + ty; wx1 = b.z + tx; wy1 = b.w + ty;
+    }
+    const long long Aw = (long long)(wx1 - wx0 + 1) * (long long)(wy1 - wy0 + 1);
+    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
+    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
+    unsigned long long mk = kNoKey;
+    int mp = -1;
+    for (long long c = c0; c < c1; ++c) {
+        const long long idx = c * 256 + threadIdx.x;
+        const unsigned long long v = keys[idx];
+        if (v == kNoKey) continue;
+        // best_key_index backwards: 1024 keys per sub-tile, [row group][wave][row % 16][column % 4]
+        const int tile = (int)(idx >> 10), r = (int)(idx & 1023);
+        const int i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
+        const int j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
+        const unsigned g = (unsigned)(j * nx + i);
+        const int u = (int)(unsigned)v;
+        bool drop = false;
+        if (round > 0) {
+            drop = g == gw;
+            if (!drop) {
+                const int4 b = boxes[u];
+                const int tx = x0 + i * sx, ty = y0 + j * sy;
+                const int fx0 = b.x + tx, fy0 = b.y + ty, fx1 = b.z + tx, fy1 = b.w + ty;
+                const int ix = min(fx1, wx1) - max(fx0, wx0) + 1, iy = min(fy1, wy1) - max(fy0, wy0) + 1;
+                if (ix > 0 && iy > 0) {
+                    const long long I = (long long)ix * (long long)iy;
+                    const long long U = (long long)(fx1 - fx0 + 1) * (long long)(fy1 - fy0 + 1) + Aw - I;
+                    drop = 1000ll * I > (long long)permille * U;
+                }
+            }
+        }
+        if (drop) {
+            keys[idx] = kNoKey;
+        } else {
+            const unsigned long long key = (v & 0xffffffff00000000ull) | g;
+            if (key < mk) { mk = key; mp = u; }
+        }
+    }
+    nms_block_min(mk, mp, sk, sp);
+    if (threadIdx.x == 0) { pk_out[blockIdx.x] = mk; pp_out[blockIdx.x] = mp; }
 }
 
 // ---- pose windows (include/fdcm.h, "Pose windows"): a list of jobs, each one template, a run of rotations and a small grid
@@ -1092,17 +1195,24 @@ std::vector<float> best_denominators(const fdcm_templates* t, int penalty, float
 
 struct BestRun {
     char* d = nullptr;  // search.eval
-    size_t o_unit = 0, o_seg = 0, o_best = 0, o_pair = 0, o_keys = 0, o_plane = 0, o_cand = 0;
+    size_t o_unit = 0, o_seg = 0, o_foot = 0, o_best = 0, o_pair = 0, o_keys = 0, o_plane = 0, o_cand = 0;
+    size_t n_keys = 0;
     int tiles_x = 0, parts = 0;
 };
+
+// The footprint of a pair (include/fdcm.h, "Detections suppressed by footprint overlap"): x0, y0, x1, y1.
+struct Foot { int32_t x0, y0, x1, y1; };
+static_assert(sizeof(Foot) == 16, "Foot is 16 bytes");
+constexpr size_t kNmsPartialBytes = 2 * kNmsWorkgroups * (8 + 4);  // two sets of partial minima: the keys, then the pairs
 
 // Scores every pair of P (T templates x n rotations, prepared) on the grid and leaves, on the device, the merged key
 // plane of the call: one launch chain of k_exhaustive<., kBest> over all pairs into one plane set to "no key" before.
 // Pairs of templates without lines take no part.  k > 0 also lays out what the peak pass needs (the one unit, its group,
 // the merged list, the pairs of its entries, the candidate lists).  Returns false, with nothing queued, when no pair has
-// a grid point: every point is then without a candidate.
+// a grid point: every point is then without a candidate.  foot (or null): a footprint per pair, for the rounds of the
+// overlap rule; it goes up with the same upload, and the partial minima of the rounds take the candidate lists' place.
 bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau, int k,
-               BestRun& R) {
+               BestRun& R, const std::vector<Foot>* foot = nullptr) {
     const std::vector<float> den = best_denominators(t, penalty, tau);
     const size_t np = P.nl.size();
     std::vector<ExTmpl> tm(np + 1);
@@ -1124,18 +1234,21 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
     const size_t o_tm = al256(P.lines.size() * sizeof(ExLine));
     R.o_unit = o_tm + np * sizeof(ExTmpl);
     R.o_seg = al256(R.o_unit + sizeof(ExTmpl));
-    R.o_best = R.o_seg + 256;
+    R.o_foot = R.o_seg + 256;
+    R.o_best = R.o_foot + (foot ? al256(np * sizeof(Foot)) : 0);
+    R.n_keys = n_keys;
     R.o_pair = R.o_best + al256((size_t)kMaxK * 8);
     R.o_keys = R.o_pair + al256((size_t)kMaxK * 4);
     R.o_plane = R.o_keys + al256(n_keys * 8);
     R.o_cand = R.o_plane + al256((size_t)g.nx * g.ny * 4);
-    fm->search.eval.reserve(R.o_cand + (k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0));
+    fm->search.eval.reserve(R.o_cand + (foot ? kNmsPartialBytes : k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0));
     fm->search.eval_stage.reserve(R.o_pair);
     char* d = R.d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
     std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
     std::memcpy(h + o_tm, tm.data(), tm.size() * sizeof(ExTmpl));
     std::memcpy(h + R.o_seg, &seg, sizeof seg);
+    if (foot) std::memcpy(h + R.o_foot, foot->data(), np * sizeof(Foot));
     std::memset(h + R.o_best, 0xff, (size_t)kMaxK * 8);  // kNoKey
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d, h, R.o_pair, hipMemcpyHostToDevice, st));
@@ -1149,6 +1262,66 @@ void best_unpack(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, floa
     hipLaunchKernelGGL(k_best_unpack, dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4)), dim3(256), 0, fm->stream,
                        (const unsigned long long*)(R.d + R.o_keys), g.nx, g.ny, R.tiles_x, score, pair);
     FDCM_HIP(hipGetLastError());
+}
+
+// The records of the detections (include/fdcm.h, "Best map and detections"): downloads the list of k keys (bits of q << 32)
+// | g at o_best and the pairs of its entries at o_pair, waits for the stream, and emits entry l as the pair t n + a = pair[l]
+// at the grid point of its key (kNoKey ends the list).  foot and boxes_out (or null): the footprint of each pair; the
+// footprint of record l, F(g) = foot[pair[l]] + t_g, goes to boxes_out[4 l ..].
+void detect_records(fdcm_featuremap* fm, const BestRun& R, const Pairs& P, bool rotated, int n, const fdcm_grid& g, int k, int32_t base,
+                    fdcm_match** out, int64_t* n_out, const Foot* foot, int32_t* boxes_out) {
+    hipStream_t st = fm->stream;
+    std::vector<unsigned long long> best((size_t)k);
+    std::vector<int32_t> pair((size_t)k);
+    FDCM_HIP(hipMemcpyAsync(best.data(), R.d + R.o_best, (size_t)k * 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipMemcpyAsync(pair.data(), R.d + R.o_pair, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    int64_t cnt = 0;
+    while (cnt < k && best[(size_t)cnt] != kNoKey) ++cnt;
+    fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, cnt) * sizeof(fdcm_match));
+    for (int64_t l = 0; l < cnt; ++l) {
+        const unsigned gi = (unsigned)best[(size_t)l];
+        const int px = g.x0 + (int)(gi % (unsigned)g.nx) * g.sx, py = g.y0 + (int)(gi / (unsigned)g.nx) * g.sy;
+        const float tx = (float)px, ty = (float)py;
+        fdcm_match& rec = m[l];
+        rec.tmpl_idx = base + pair[(size_t)l] / n;
+        rec.score = f_from_bits((uint32_t)(best[(size_t)l] >> 32));
+        if (rotated) {  // combine(translation, M_a), float32 adds: emit_records' rule
+            const RotM& M = P.M[(size_t)pair[(size_t)l]];
+            rec.transform[0] = M.c; rec.transform[1] = M.ns; rec.transform[2] = M.mx + tx;
+            rec.transform[3] = M.s; rec.transform[4] = M.c; rec.transform[5] = M.my + ty;
+        } else {
+            rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = tx;
+            rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = ty;
+        }
+        if (boxes_out) {
+            const Foot& F = foot[(size_t)pair[(size_t)l]];
+            int32_t* b = boxes_out + 4 * l;
+            b[0] = F.x0 + px; b[1] = F.y0 + py; b[2] = F.x1 + px; b[3] = F.y1 + py;
+        }
+    }
+    *out = m;
+    *n_out = cnt;
+}
+
+// The footprint of the n lines at p (4 floats each, `stride` floats apart) with a margin: floor of the smallest and the
+// largest end point coordinate, widened by the margin, clamped to +-2^25; (0, 0, -1, -1) without lines or with a NaN.
+Foot footprint(const float* p, size_t stride, int64_t n, int margin) {
+    const Foot none{0, 0, -1, -1};
+    if (n == 0) return none;
+    float mnx = f_inf(), mxx = -f_inf(), mny = f_inf(), mxy = -f_inf();
+    for (int64_t q = 0; q < n; ++q, p += stride)
+        for (int c = 0; c < 2; ++c) {
+            if (std::isnan(p[2 * c]) || std::isnan(p[2 * c + 1])) return none;
+            mnx = std::min(mnx, p[2 * c]); mxx = std::max(mxx, p[2 * c]);
+            mny = std::min(mny, p[2 * c + 1]); mxy = std::max(mxy, p[2 * c + 1]);
+        }
+    const int64_t lim = (int64_t)1 << 25;
+    auto at = [&](float v, int64_t d) {  // floor(v) + d in int64 (an infinite v: far outside the clamp), clamped
+        const double f = std::min(std::max(std::floor((double)v), -1099511627776.0), 1099511627776.0);
+        return (int32_t)std::min(std::max((int64_t)f + d, -lim), lim);
+    };
+    return Foot{at(mnx, -margin), at(mny, -margin), at(mxx, margin), at(mxy, margin)};
 }
 
 // ---- pose windows: the host driver
@@ -1414,32 +1587,71 @@ void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, 
     hipLaunchKernelGGL(k_best_gather, dim3(1), dim3(64), 0, st, (const unsigned long long*)d_best, k,
                        (const unsigned long long*)(d + R.o_keys), g.nx, R.tiles_x, (int*)(d + R.o_pair));
     FDCM_HIP(hipGetLastError());
-    std::vector<unsigned long long> best((size_t)k);
-    std::vector<int32_t> pair((size_t)k);
-    FDCM_HIP(hipMemcpyAsync(best.data(), d_best, (size_t)k * 8, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipMemcpyAsync(pair.data(), d + R.o_pair, (size_t)k * 4, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipStreamSynchronize(st));
-    // one list: entry l is the pair t n + a = pair[l] at the grid point of its key (kNoKey ends the list)
-    int64_t cnt = 0;
-    while (cnt < k && best[(size_t)cnt] != kNoKey) ++cnt;
-    fdcm_match* m = result_acquire((size_t)std::max<int64_t>(1, cnt) * sizeof(fdcm_match));
-    for (int64_t l = 0; l < cnt; ++l) {
-        const unsigned gi = (unsigned)best[(size_t)l];
-        const float tx = (float)(g.x0 + (int)(gi % (unsigned)g.nx) * g.sx), ty = (float)(g.y0 + (int)(gi / (unsigned)g.nx) * g.sy);
-        fdcm_match& rec = m[l];
-        rec.tmpl_idx = base + pair[(size_t)l] / n;
-        rec.score = f_from_bits((uint32_t)(best[(size_t)l] >> 32));
-        if (rot) {  // combine(translation, M_a), float32 adds: emit_records' rule
-            const RotM& M = P.M[(size_t)pair[(size_t)l]];
-            rec.transform[0] = M.c; rec.transform[1] = M.ns; rec.transform[2] = M.mx + tx;
-            rec.transform[3] = M.s; rec.transform[4] = M.c; rec.transform[5] = M.my + ty;
-        } else {
-            rec.transform[0] = 1.f; rec.transform[1] = 0.f; rec.transform[2] = tx;
-            rec.transform[3] = 0.f; rec.transform[4] = 1.f; rec.transform[5] = ty;
+    detect_records(fm, R, P, rot != nullptr, n, g, k, base, out, n_out, nullptr, nullptr);
+}
+
+// The footprints of every pair of a set given by its packed lines and offsets (no handle, no device): the lines rotated_set
+// makes, which are prepare_pairs'.
+void lines_footprints(const float* lines, const int64_t* offsets, int64_t T, const fdcm_rotations* rot, int margin, int32_t* boxes_out) {
+    const int n = rot ? rot->n : 1;
+    Foot* out = (Foot*)boxes_out;
+    std::vector<RotM> M((size_t)n);
+    fdcm_templates one, rt;  // one template at a time, as a set of its own (pivot 2 i is its pivot 0)
+    one.T = 1;
+    for (int64_t i = 0; i < T; ++i) {
+        const int64_t l0 = offsets[i], nl = offsets[i + 1] - l0;
+        if (rot) {
+            one.lines.assign(lines + 4 * l0, lines + 4 * (l0 + nl));
+            one.offsets = {0, nl};
+            one.n_lines = nl;
+            const fdcm_rotations sub{rot->cs, rot->n, rot->pivots ? rot->pivots + 2 * i : nullptr};
+            rotated_set(&one, sub, 0, 1, rt, M.data());
         }
+        for (int a = 0; a < n; ++a)
+            out[i * n + a] = rot ? footprint(rt.lines.data() + (size_t)rt.offsets[(size_t)a] * 4, 4, nl, margin)
+                                 : footprint(lines + 4 * l0, 4, nl, margin);
     }
-    *out = m;
-    *n_out = cnt;
+}
+
+void templates_footprints(const fdcm_templates* t, const fdcm_rotations* rot, int margin, int32_t* boxes_out) {
+    lines_footprints(t->lines.data(), t->offsets.data(), t->T, rot, margin, boxes_out);
+}
+
+// Detections by footprint overlap (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  The key plane is
+// best_keys', the rounds are k_nms_round's, the records run_search_exhaustive_detect's.
+void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
+                                      int permille, int margin, int penalty, float tau, int32_t base, fdcm_match** out,
+                                      int32_t* boxes_out, int64_t* n_out) {
+    check_grid(g);
+    *n_out = 0;
+    if (t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int n = rot ? rot->n : 1;
+    if (rot) check_rotated_size(t, n);
+    Pairs P;
+    prepare_pairs(fm, t, rot, false, P);
+    // the footprints, from the lines the kernels score (a pair without a grid point is never read)
+    std::vector<Foot> foot(P.nl.size());
+    for (size_t u = 0; u < foot.size(); ++u)
+        foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    BestRun R;
+    if (!best_keys(fm, P, t, n, g, penalty, tau, k, R, &foot)) return;
+    hipStream_t st = fm->stream;
+    char* d = R.d;
+    unsigned long long* pk = (unsigned long long*)(d + R.o_cand);
+    int* pp = (int*)(d + R.o_cand + 2 * kNmsWorkgroups * 8);
+    const long long n_chunks = (long long)(R.n_keys / 256);  // whole sub-tiles: a multiple of 4
+    const unsigned wgs = (unsigned)std::min<long long>(kNmsWorkgroups, n_chunks);
+    for (int r = 0; r <= k; ++r) {
+        const int in = (r + 1) & 1, to = r & 1;
+        hipLaunchKernelGGL(k_nms_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)(d + R.o_keys), n_chunks, g.x0, g.y0, g.sx, g.sy,
+                           g.nx, R.tiles_x, (const int4*)(d + R.o_foot), permille, r, (int)(r == k),
+                           (const unsigned long long*)(pk + in * kNmsWorkgroups), (const int*)(pp + in * kNmsWorkgroups),
+                           pk + to * kNmsWorkgroups, pp + to * kNmsWorkgroups, (unsigned long long*)(d + R.o_best), (int*)(d + R.o_pair));
+        FDCM_HIP(hipGetLastError());
+    }
+    detect_records(fm, R, P, rot != nullptr, n, g, k, base, out, n_out, foot.data(), boxes_out);
 }
 
 void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, int32_t sx, int32_t sy,

@@ -351,6 +351,13 @@ void run_best_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotat
                   float* score_out, int32_t* pair_out);
 void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
                                   int rx, int ry, int penalty, float tau, int32_t base, fdcm_match** out, int64_t* n_out);
+// boxes_out: 4 k int32, or null
+void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
+                                      int permille, int margin, int penalty, float tau, int32_t base, fdcm_match** out,
+                                      int32_t* boxes_out, int64_t* n_out);
+// host only: 4 int32 per pair t n + a (rot null: n = 1, the lines as they are)
+void templates_footprints(const fdcm_templates* t, const fdcm_rotations* rot, int margin, int32_t* boxes_out);
+void lines_footprints(const float* lines, const int64_t* offsets, int64_t T, const fdcm_rotations* rot, int margin, int32_t* boxes_out);
 void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
                                    int64_t n_jobs, int sx, int sy, int k, int32_t base, fdcm_match** out, int64_t* n_out,
                                    int64_t* job_offsets);

@@ -390,6 +390,23 @@ class DeviceFeatureMap:
             -1 if penalty is None else int(penalty), float(tau), int(tmpl_index_base), C.byref(out), C.byref(n)))
         return _adopt_matches(out, n.value)
 
+    def exhaustive_detect_nms(self, templates, grid, cs=None, pivots=None, k=8, overlap_permille=300, margin=0, penalty=None,
+                              tau=1.0, tmpl_index_base=0, boxes=False):
+        """Detections by footprint overlap (include/fdcm.h): greedily the point of the smallest best-map key, then without
+        every point whose footprint (the winning pair's box of line end points, widened by margin pixels, at the point's
+        translation) overlaps the detection's by more than overlap_permille / 1000 of their union; at most k.  Raw match
+        records as exhaustive_detect's, in ascending order; with boxes also the (n, 4) int32 footprints x0, y0, x1, y1."""
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        g = as_grid(grid)
+        out, n = C.c_void_p(), C.c_int64()
+        fp = np.zeros((int(k) if 1 <= int(k) <= 64 else 0, 4), dtype=np.int32)
+        capi.check(capi.lib().fdcm_search_exhaustive_detect_nms(
+            self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), int(k), int(overlap_permille), int(margin),
+            -1 if penalty is None else int(penalty), float(tau), int(tmpl_index_base), C.byref(out),
+            fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and fp.size else None, C.byref(n)))
+        rec = _adopt_matches(out, n.value)
+        return (rec, fp[:n.value].copy()) if boxes else rec
+
     def line_costs(self, templates, poses, cs=None, pivots=None):
         """Line costs (include/fdcm.h, "Per-line caps and line costs"): poses (n, 4) int32 rows (tmpl, a, x, y), a an index
         into the rotations cs (0 with cs None, the lines as they are).  Returns (float32 costs, int64 offsets of n + 1): pose
@@ -455,6 +472,18 @@ class DeviceFeatureMap:
             pass
 
 
+def lines_footprints(templates, cs=None, pivots=None, margin=0):
+    """DeviceTemplates.footprints for a plain list of line arrays: (T, n, 4) int32, no handle and no device."""
+    flat, offsets = capi.pack_templates(templates)
+    T = len(offsets) - 1
+    rot, keep = _rotations(cs, pivots, T) if cs is not None else (None, None)
+    out = np.zeros((T, 1 if rot is None else rot.n, 4), dtype=np.int32)
+    capi.check(capi.lib().fdcm_lines_footprints(capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)), T,
+                                                C.byref(rot) if rot is not None else None, int(margin),
+                                                out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
+
+
 class DeviceTemplates:
     """Owns an fdcm_templates handle: a list of LineArrays resident in HBM.  line_caps (None, a scalar tau or one float
     array per template: flat_line_caps) gives every line a cap of its cost in the exhaustive calls (include/fdcm.h, "Per-line
@@ -486,6 +515,16 @@ class DeviceTemplates:
         out = np.zeros(self.n_lines, dtype=np.float32)
         capi.check(capi.lib().fdcm_templates_line_lengths(self._h, capi.fptr(out)))
         return [out[a:b] for a, b in zip(self._offsets[:-1], self._offsets[1:])]
+
+    def footprints(self, cs=None, pivots=None, margin=0):
+        """(T, n, 4) int32 footprints x0, y0, x1, y1 of every (template, rotation) pair (n = 1 with cs None: the lines as
+        they are), as exhaustive_detect_nms uses them; (0, 0, -1, -1) for a template without lines.  Host only."""
+        rot, keep = _rotations(cs, pivots, self.count) if cs is not None else (None, None)
+        n = 1 if rot is None else rot.n
+        out = np.zeros((self.count, n, 4), dtype=np.int32)
+        capi.check(capi.lib().fdcm_templates_footprints(self._h, C.byref(rot) if rot is not None else None, int(margin),
+                                                        out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
 
     def lengths(self):
         out = np.zeros(self.count, dtype=np.float32)

@@ -10,11 +10,16 @@ radius 8, ExponentialPenalty(1.5).  In the same run, on the same grid:
                 tests/detect_ref.py in numpy (penalise, minimum pairkey over the templates in batches, peaks of the best
                 plane, records); its records are compared with the detect call's
 
+  nms           (--nms) one blocking fdcm_search_exhaustive_detect_nms call (include/fdcm.h, "Detections suppressed by
+                footprint overlap") at the same k and at k = 64, overlap --overlap, margin 0; and once what a caller had before
+                it: fdcm_best_map to the host (both planes) and the greedy rule of tests/nms_ref.py in numpy, whose records
+                are compared with the call's
+
 Each device figure is the median of --reps blocking calls after a warm-up; the host composition runs --host-reps times.
 --line-caps TAU gives every template line the cap TAU * its length (include/fdcm.h, "Per-line caps and line costs") in every
 call of the run, the host composition's score map included.  Off by default.
 
-    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--line-caps TAU] [--json out.json]
+    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--line-caps TAU] [--nms] [--json out.json]
 """
 import argparse
 import json
@@ -54,6 +59,16 @@ def host_composition(dev, tset, grid, lengths, penalty, tau, k, r, batch=50):
     return rec, t1 - t0, time.perf_counter() - t1
 
 
+def nms_host_composition(dev, tset, grid, penalty, tau, k, permille):
+    """(records, seconds of fdcm_best_map to the host, seconds of the greedy rule in numpy)."""
+    from nms_ref import detect_nms_ref
+    t0 = time.perf_counter()
+    scores, pairs = dev.best_map(tset, grid, penalty=penalty, tau=tau)
+    t1 = time.perf_counter()
+    rec, _ = detect_nms_ref(scores, pairs, tset.footprints().reshape(-1, 4), grid, k, permille)
+    return rec, t1 - t0, time.perf_counter() - t1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=5)
@@ -63,6 +78,8 @@ def main():
     ap.add_argument("--radius", type=int, default=8)
     ap.add_argument("--tau", type=float, default=1.5)
     ap.add_argument("--line-caps", type=float, default=None, metavar="TAU", help="cap every line's cost at TAU * its length")
+    ap.add_argument("--nms", action="store_true", help="also time the detections suppressed by footprint overlap")
+    ap.add_argument("--overlap", type=float, default=0.3, help="the overlap threshold of --nms")
     ap.add_argument("--json", default=None, help="also write the results here")
     args = ap.parse_args()
 
@@ -82,12 +99,14 @@ def main():
             t0 = time.perf_counter()
             out = call()
             times.append(time.perf_counter() - t0)
+        spread.append((max(times) - min(times)) * 1e3)
         return float(np.median(times)) * 1e3, min(times) * 1e3, out
 
-    rows = []
+    rows, spread = [], []  # spread: max - min of the last timed() call's repetitions
     for s in [int(v) for v in args.strides.split(",")]:
         grid = dev.exhaustive_window(tset, s, s).as_tuple()
         det_ms, det_min, recs = timed(lambda: dev.exhaustive_detect(tset, grid, k=k, rx=r, ry=r, penalty=pen, tau=tau))
+        det_spread = spread[-1]
         map_ms, map_min, _ = timed(lambda: dev.best_map(tset, grid, penalty=pen, tau=tau))
         top_ms, top_min, _ = timed(lambda: dev.exhaustive_search(tset, grid, k=k))
         pk_ms, pk_min, per = timed(lambda: dev.exhaustive_peaks(tset, grid, k=k, rx=r, ry=r))
@@ -95,7 +114,8 @@ def main():
                "detect_ms": round(det_ms, 3), "detect_ms_min": round(det_min, 3), "best_map_ms": round(map_ms, 3),
                "best_map_ms_min": round(map_min, 3), "topk_ms": round(top_ms, 3), "topk_ms_min": round(top_min, 3),
                "peaks_ms": round(pk_ms, 3), "peaks_ms_min": round(pk_min, 3), "detect_to_topk": round(det_ms / top_ms, 3),
-               "detect_to_peaks": round(det_ms / pk_ms, 3), "detections": int(len(recs)), "per_template_records": int(len(per))}
+               "detect_to_peaks": round(det_ms / pk_ms, 3), "detections": int(len(recs)), "per_template_records": int(len(per)),
+               "detect_ms_spread": round(det_spread, 3)}
         print(f"stride {s}: grid {grid[2]}x{grid[3]}, detect {det_ms:.2f} ms (min {det_min:.2f}), best_map {map_ms:.2f} ms, "
               f"top-k {top_ms:.2f} ms, peaks r {r} {pk_ms:.2f} ms: detect / top-k {det_ms / top_ms:.3f}, detect / peaks "
               f"{det_ms / pk_ms:.3f}; {len(recs)} detections for {len(per)} per-template records", flush=True)
@@ -108,6 +128,22 @@ def main():
                         "host_to_detect": round((dl + red) / det_ms, 1), "host_records_equal": bool(same)})
             print(f"stride {s}: host composition: score_map {dl:.0f} ms + numpy reduction {red:.0f} ms = {(dl + red) / det_ms:.0f}x "
                   f"the detect call; records equal: {same}", flush=True)
+        if args.nms:
+            pm = int(round(1000 * args.overlap))
+            nms_ms, nms_min, nrec = timed(lambda: dev.exhaustive_detect_nms(tset, grid, k=k, overlap_permille=pm, penalty=pen, tau=tau))
+            nms_spread = spread[-1]
+            n64_ms, n64_min, nrec64 = timed(lambda: dev.exhaustive_detect_nms(tset, grid, k=64, overlap_permille=pm, penalty=pen, tau=tau))
+            href, dl, red = nms_host_composition(dev, tset, grid, pen, tau, k, pm)
+            same = href.tobytes() == nrec.tobytes()
+            row.update({"overlap_permille": pm, "nms_ms": round(nms_ms, 3), "nms_ms_min": round(nms_min, 3),
+                        "nms_ms_spread": round(nms_spread, 3), "nms_k64_ms": round(n64_ms, 3), "nms_k64_ms_min": round(n64_min, 3),
+                        "nms_k64_ms_spread": round(spread[-1], 3), "nms_detections": int(len(nrec)),
+                        "nms_k64_detections": int(len(nrec64)), "nms_to_detect": round(nms_ms / det_ms, 3),
+                        "nms_host_best_map_ms": round(dl * 1e3, 2), "nms_host_rule_ms": round(red * 1e3, 2),
+                        "nms_host_total_ms": round((dl + red) * 1e3, 2), "nms_host_records_equal": bool(same)})
+            print(f"stride {s}: nms overlap {args.overlap:g}: k {k} {nms_ms:.2f} ms (min {nms_min:.2f}, spread {nms_spread:.2f}; detect "
+                  f"{det_ms:.2f}, spread {det_spread:.2f}), k 64 {n64_ms:.2f} ms; {len(nrec)} / {len(nrec64)} detections; host "
+                  f"composition: best_map {dl * 1e3:.1f} ms + numpy rule {red * 1e3:.1f} ms; records equal: {same}", flush=True)
         rows.append(row)
     res = {"workload": "config 2': 1024x1024 scene (200 lines, seed 1), depth 30, L2, padding 1.0; 1000 templates x 32 lines "
                        "(seed 2), default window per stride; k %d, radius %d, ExponentialPenalty(%g)" % (k, r, tau),
