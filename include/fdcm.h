@@ -549,6 +549,37 @@ int fdcm_templates_footprints(const fdcm_templates* templates, const fdcm_rotati
 int fdcm_lines_footprints(const float* lines, const int64_t* offsets, int64_t n_templates, const fdcm_rotations* rot /* or NULL */,
                           int32_t margin, int32_t* boxes_out);
 
+/* All detections below a score: the detector's threshold.  The two detection calls above return "the k best" (k <= 64),
+ * whatever their scores; this call returns every detection that matches at least as well as max_score, up to a bound the
+ * caller sets.  The definitions are this project's (README.md, "All detections below a score"; numpy statement:
+ * tests/detect_all_ref.py).
+ * Inputs: those of fdcm_search_exhaustive_detect_nms with k replaced by max_score (float32, >= +0 or +inf) and
+ * max_detections (1 .. 4096).  Candidates, q, pairkey, best(g), key(g), the footprints, the overlap test and the record
+ * layout are that call's, caps, rot == NULL and the meaning of margin and overlap_permille included.
+ * S_0 is the set of grid points with a candidate whose q(best(g)) <= max_score, compared in float32 on the q fdcm_best_map
+ * would hold.  The rule is the greedy rule of fdcm_search_exhaustive_detect_nms on this S_0, stopping when n =
+ * max_detections or S_n is empty.  Output: the d_n in order as records, *n_out of them; boxes_out (4 max_detections int32,
+ * or NULL): F(d_n) per record.
+ * Identities: max_score = +inf and max_detections = k <= 64 give fdcm_search_exhaustive_detect_nms' records, byte for byte.
+ * For any max_score the records are the leading records with score <= max_score of the +inf list at the same
+ * max_detections: keys ascend, and a point over the threshold never precedes, so never suppresses, one under it.
+ * The device skips work the threshold makes pointless: a score is a sum of terms >= +0, so a partial sum that is over the
+ * template's bound ends that template for the points of a wave once all of them are over it.  The
+ * records do not depend on it.
+ * fdcm_detect_score_bounds (host only, no device work): per template B_t, the largest float32 s >= +0, possibly +inf, whose
+ * IEEE float32 quotient s / den_t is <= max_score, den_t the denominator of q above (1 with penalty = -1); 0 for a template
+ * without lines.  A sum above B_t is exactly a sum whose q is above max_score.  fdcm_score_bound: the same for one
+ * denominator given as a number, for callers without a handle (a process without a device has none).
+ * FDCM_EINVAL, before any GPU work: everything fdcm_search_exhaustive_detect_nms rejects; max_score NaN or < 0;
+ * max_detections outside 1 .. 4096.  Empty inputs give zero records.  The call blocks; concurrent callers of one feature map
+ * take turns.  Results are a function of the inputs alone.  Release the records with fdcm_matches_free. */
+int fdcm_search_exhaustive_detect_all(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                                      const fdcm_grid* grid, float max_score, int32_t max_detections, int32_t overlap_permille,
+                                      int32_t margin, int penalty, float tau, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                      int32_t* boxes_out /* 4 max_detections, or NULL */);
+int fdcm_detect_score_bounds(const fdcm_templates* templates, int penalty, float tau, float max_score, float* bounds /* n_templates */);
+int fdcm_score_bound(float den, float max_score, float* bound);
+
 /* Per-line caps and line costs: the truncated directional chamfer cost.  A score is a plain sum over the template's lines,
  * so one line whose scene edge is missing (occlusion, a gap in the edges, a line the fit dropped) can cost as much as all
  * the others matched badly.  A template set may carry one cap per line; every exhaustive call above then clamps each

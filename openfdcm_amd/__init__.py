@@ -690,6 +690,34 @@ def exhaustive_detect_nms(featuremap, templates, overlap=0.3, stride=1, k=8, pen
     return (MatchList(res[0]), res[1]) if return_boxes else MatchList(res)
 
 
+def exhaustive_detect_all(featuremap, templates, max_score, overlap=0.3, stride=1, max_detections=1024, penalty=None, angles=None,
+                          pivot="center", window=None, line_caps=None, margin=0, return_boxes=False):
+    """Every detection that matches at least as well as max_score: exhaustive_detect_nms' greedy rule on the points of
+    best_score_map's plane whose score is <= max_score (>= 0 or inf), until they run out or max_detections (1 to 4096) is
+    reached.  A scene with two parts gives two detections, not k records of which six are junk, and a bin of 200 small
+    parts gives 200.  max_score=inf with max_detections=k is exhaustive_detect_nms(k=k); a lower max_score returns the
+    leading part of that list, and costs less: a template is dropped for a patch of points as soon as its partial sums put
+    all of them over the threshold.  Returns a MatchList in ascending score, and with return_boxes also the (n, 4) int32
+    footprints.  The other arguments are exhaustive_detect_nms'."""
+    kind, tau = _penalty_args(penalty)
+    permille = int(round(1000 * float(overlap)))
+    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
+    if g[2] == 0 or g[3] == 0:
+        empty = MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
+        return (empty, _np.zeros((0, 4), dtype=_np.int32)) if return_boxes else empty
+    res = fm.exhaustive_detect_all(tset, g, cs, pv, max_score=max_score, max_detections=max_detections, overlap_permille=permille,
+                                   margin=margin, penalty=kind, tau=tau, boxes=return_boxes)
+    return (MatchList(res[0]), res[1]) if return_boxes else MatchList(res)
+
+
+def detect_score_bounds(templates, penalty, max_score):
+    """Per template the largest float32 score sum whose normalised score (penalty: None, DefaultPenalty or
+    ExponentialPenalty) is <= max_score: what exhaustive_detect_all's threshold means for each template's raw score.  0 for
+    a template without lines.  No device work."""
+    kind, tau = _penalty_args(penalty)
+    return _template_cache.get(templates).score_bounds(max_score, penalty=kind, tau=tau)
+
+
 def template_footprints(templates, angles=None, pivot="center", margin=0):
     """The (T, A, 4) int32 footprints x0, y0, x1, y1 exhaustive_detect_nms uses for every template and angle (A = 1 without
     angles: the lines as they are); (0, 0, -1, -1) for a template without lines.  No device work."""

@@ -174,6 +174,11 @@ SYMBOLS = [
                                                C.c_int, C.c_float, C.c_int32, C.POINTER(_vp), _i64p]),
     ("fdcm_search_exhaustive_detect_nms", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int32, C.c_int32, C.c_int32,
                                                    C.c_int, C.c_float, C.c_int32, C.POINTER(_vp), C.POINTER(C.c_int32), _i64p]),
+    ("fdcm_search_exhaustive_detect_all", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_float, C.c_int32, C.c_int32,
+                                                   C.c_int32, C.c_int, C.c_float, C.c_int32, C.POINTER(_vp), _i64p,
+                                                   C.POINTER(C.c_int32)]),
+    ("fdcm_detect_score_bounds", C.c_int, [_vp, C.c_int, C.c_float, C.c_float, _fp]),
+    ("fdcm_score_bound", C.c_int, [C.c_float, C.c_float, _fp]),
     ("fdcm_templates_footprints", C.c_int, [_vp, C.POINTER(Rotations), C.c_int32, C.POINTER(C.c_int32)]),
     ("fdcm_lines_footprints", C.c_int, [_fp, _i64p, C.c_int64, C.POINTER(Rotations), C.c_int32, C.POINTER(C.c_int32)]),
     ("fdcm_templates_create_capped", C.c_int, [_fp, _i64p, C.c_int64, _fp, C.POINTER(_vp)]),

@@ -856,6 +856,46 @@ int fdcm_search_exhaustive_detect_nms(const fdcm_featuremap* fm, const fdcm_temp
     });
 }
 
+// All detections below a score: include/fdcm.h, "All detections below a score".  The overlap call's checks with the threshold
+// and the bound on the list in place of k: nothing here touches the device.
+int fdcm_search_exhaustive_detect_all(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                      const fdcm_grid* grid, float max_score, int32_t max_detections, int32_t overlap_permille,
+                                      int32_t margin, int penalty, float tau, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                      int32_t* boxes_out) {
+    return guarded([&] {
+        require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
+        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
+        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(out && n_out, "null output");
+        check_best_args(fm, templates, rot, grid, penalty, tau);
+        records_call(out, [&] {
+            run_search_exhaustive_detect_all(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, max_score == 0.f ? 0.f : max_score,
+                                             max_detections, overlap_permille, margin, penalty, tau, tmpl_index_base, out, n_out,
+                                             boxes_out);
+        });
+    });
+}
+
+int fdcm_score_bound(float den, float max_score, float* bound) {
+    return guarded([&] {
+        require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
+        require(bound != nullptr, "bound is null");
+        *bound = detect_score_bound(den, max_score);
+    });
+}
+
+int fdcm_detect_score_bounds(const fdcm_templates* templates, int penalty, float tau, float max_score, float* bounds) {
+    return guarded([&] {
+        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
+        require(std::isfinite(tau), "tau must be finite");
+        require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
+        require(templates != nullptr, "templates is null");
+        require(bounds != nullptr || templates->T == 0, "bounds is null");
+        detect_score_bounds(templates, penalty, tau, max_score, bounds);
+    });
+}
+
 int fdcm_templates_footprints(const fdcm_templates* templates, const fdcm_rotations* rot, int32_t margin, int32_t* boxes_out) {
     return guarded([&] {
         require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");

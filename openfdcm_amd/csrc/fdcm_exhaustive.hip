@@ -7,7 +7,8 @@
 //                                     chunk of kChunk templates; for every sub-tile it scores every template of the chunk (a
 //                                     lane per 4 translations), then writes the scores (map), offers them to a running
 //                                     k-best list per wave and template kept in LDS (top-k), or keeps per point the smallest
-//                                     (normalised score, pair) key of the chunk and merges it into one plane of keys (best)
+//                                     (normalised score, pair) key of the chunk and merges it into one plane of keys (best);
+//                                     kBestBound: best for the points at or below a score, with rows_score's early exit
 //   k_best_unpack, k_best_gather      best map: the key plane as row-major score and pair planes; the pairs of k points
 //   k_nms_round                       detections by footprint overlap: one round of the greedy rule on the key plane, the
 //                                     previous round's winner reduced from per-workgroup minima, its victims erased
@@ -19,7 +20,7 @@
 //                                     (job, rotation) planes, a lane per translation, and keeps a k-best list per job
 //   k_line_costs<BUF32>               line costs: a wave per pose, a lane per line of its template: the terms of the sum
 //
-// Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP>, the one statement of the sum (4 rows per lane in
+// Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP, EXIT>, the one statement of the sum (4 rows per lane in
 // k_exhaustive, 1 in k_exhaustive_windows).  CAP: every term clamped to its line's cap (include/fdcm.h, "Per-line caps and
 // line costs"); the kernels are instantiated both ways and a set without a finite cap launches the ones without the clamp,
 // which are the code they were before caps existed.  On the host every call prepares its templates through prepare_pairs: the
@@ -71,7 +72,16 @@ struct ExTmpl {    // one template of a launch
     unsigned koff;       // added to the grid index of its keys (a rotation's a * nx * ny; 0 otherwise); best map: the
                          // bits of the float32 its scores are divided by
 };
-enum ExMode { kMap = 0, kTopK = 1, kBest = 2 };
+enum ExMode { kMap = 0, kTopK = 1, kBest = 2, kBestBound = 3 };
+template <bool ON>
+struct ExBound {};  // k_exhaustive's last argument: nothing, or (kBestBound) the pairs' exit bounds and the threshold on q
+template <>
+struct ExBound<true> {
+    const float* bc;
+    float max_score;
+};
+__device__ __forceinline__ bool under(float, const ExBound<false>&) { return true; }
+__device__ __forceinline__ bool under(float q, const ExBound<true>& b) { return q <= b.max_score; }
 
 // Best map: where the key of grid point (i, j) lies in the key plane.  The plane is kept in the order k_exhaustive walks
 // it, sub-tile by sub-tile and inside one [row group j / 16][wave][lane], so the 64 keys a wave merges at once are 512
@@ -131,16 +141,36 @@ __device__ __forceinline__ unsigned long long list_offer(unsigned long long& e, 
 // accumulators give the same bits (0 + v == v for v >= +0), so one code path serves every n.  The one statement of the
 // sum for every kernel of this file.  res: zero on entry (the caller's initialiser: zeroing it here costs k_exhaustive
 // registers).  CAP: term i is line_term's clamp of it to Lt[i].cap.
-template <bool BUF32, int ROWS, bool CAP>
-__device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __restrict__ Lt, int n, float offx, const float (&offy)[ROWS],
-                                           int W, unsigned uH, size_t SL, float (&res)[ROWS]) {
+//
+// EXIT (detections below a score): after a block of 8 and after the trailing packet, when lines remain,
+// the wave abandons the sum -- true is returned and res means nothing -- if every one of its 64 x ROWS slots is masked
+// (!act[r]) or proved over the bound: C > bc, C the float32 sum of the slot's accumulators so far.  Terms are >= +0 or NaN,
+// so the finished sum of such a slot would be above bc (1 - 2 n u), u = 2^-24, or NaN; the host chose bc for that to mean
+// "no key".  A NaN C fails the comparison and the slot scores on.  One __ballot, wave-uniform.  Without EXIT: false.
+template <int ROWS, bool TWO>
+__device__ __forceinline__ bool rows_over(const float (&p0)[ROWS][4], const float (&p1)[ROWS][4], const bool* act, float bc) {
+    bool live = false;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const float C = TWO ? ((p0[r][0] + p1[r][0]) + (p0[r][1] + p1[r][1])) + ((p0[r][2] + p1[r][2]) + (p0[r][3] + p1[r][3]))
+                            : (p0[r][0] + p0[r][2]) + (p0[r][1] + p0[r][3]);
+        live = live || (act[r] && !(C > bc));
+    }
+    return __ballot(live) == 0;
+}
+
+template <bool BUF32, int ROWS, bool CAP, bool EXIT = false>
+__device__ __forceinline__ bool rows_score(const VolRef& V, const ExLine* __restrict__ Lt, int n, float offx, const float (&offy)[ROWS],
+                                           int W, unsigned uH, size_t SL, float (&res)[ROWS], const bool* act = nullptr,
+                                           float bc = 0.f) {
     const int aligned2 = (n / 8) * 8, aligned = (n / 4) * 4;
     float p0[ROWS][4], p1[ROWS][4];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r)
 #pragma unroll
         for (int l = 0; l < 4; ++l) p0[r][l] = p1[r][l] = 0.f;
-    for (int b = 0; b < aligned2; b += 8) {
+    bool gone = false;  // (EXIT) part of the loop's condition, so the loop keeps its one block and its one way out
+    for (int b = 0; b < aligned2 && !(EXIT && gone); b += 8) {
         float va[8][ROWS], vb[8][ROWS], cp[8];
 #pragma unroll
         for (int l = 0; l < 8; ++l) {
@@ -161,7 +191,9 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
                 p0[r][l] = p0[r][l] + line_term<CAP>(va[l][r], vb[l][r], cp[l]);
                 p1[r][l] = p1[r][l] + line_term<CAP>(va[l + 4][r], vb[l + 4][r], cp[l + 4]);
             }
+        if constexpr (EXIT) gone = b + 8 < n && rows_over<ROWS, true>(p0, p1, act, bc);
     }
+    if (EXIT && gone) return true;
 #pragma unroll
     for (int r = 0; r < ROWS; ++r)
 #pragma unroll
@@ -184,6 +216,8 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
         for (int r = 0; r < ROWS; ++r)
 #pragma unroll
             for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + line_term<CAP>(va[l][r], vb[l][r], cp[l]);
+        if constexpr (EXIT)
+            if (aligned < n && rows_over<ROWS, false>(p0, p1, act, bc)) return true;
     }
     if (aligned)
 #pragma unroll
@@ -196,15 +230,21 @@ __device__ __forceinline__ void rows_score(const VolRef& V, const ExLine* __rest
         for (int r = 0; r < ROWS; ++r)
             res[r] = res[r] + line_term<CAP>(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH), ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH), ln.cap);
     }
+    return false;
 }
 
+// MODE kBestBound (include/fdcm.h, "All detections below a score") is kBest with a threshold: a point's key enters the plane
+// only when q <= bound.max_score, and rows_score may abandon a template for the sub-tile (its EXIT) against bound.bc[slot],
+// the pair's bound.  The other modes take an empty argument in bound's place and are the code they were without it.
 template <bool BUF32, int MODE, bool CAP>
 __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
                                                     float ty, const ExLine* __restrict__ lines, const ExTmpl* __restrict__ tm,
                                                     int T, int x0, int y0, int nx, int ny, int sx, int sy, int tiles_x,
                                                     int n_subtiles, int portions, int k, float* __restrict__ map,
-                                                    long long plane, unsigned long long* __restrict__ cand) {
-    constexpr bool TOPK = MODE == kTopK, BEST = MODE == kBest;
+                                                    long long plane, unsigned long long* __restrict__ cand,
+                                                    ExBound<MODE == kBestBound> bound) {
+    constexpr bool BOUND = MODE == kBestBound;
+    constexpr bool TOPK = MODE == kTopK, BEST = MODE == kBest || BOUND;
     __shared__ unsigned long long lists[TOPK ? 4 * kChunk * kMaxK : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // Workgroup b -> (portion, template chunk).  Workgroups are observed to be dealt round-robin over the 8 XCDs (b and
@@ -248,7 +288,11 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
                 offy[r] = ty + (float)(y0 + (act[r] ? j : P.j0) * sy);
             }
             float res[kRows] = {0.f, 0.f, 0.f, 0.f};
-            if (meets) rows_score<BUF32, kRows, CAP>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
+            if constexpr (BOUND) {  // (meets: a sub-tile that does not was skipped above)
+                if (rows_score<BUF32, kRows, CAP, true>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res, act, bound.bc[P.slot])) continue;
+            } else {
+                if (meets) rows_score<BUF32, kRows, CAP>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
+            }
             if (BEST) {
                 // q = score / the template's denominator, one IEEE division; pairkey = (bits of q << 32) | pair.  q >= +0
                 // or NaN, so the key order is (q, pair); a NaN q is no candidate
@@ -256,7 +300,8 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
 #pragma unroll
                 for (int r = 0; r < kRows; ++r) {
                     const float q = res[r] / den;
-                    if (act[r] && !(q != q)) bk[r] = min(bk[r], ((unsigned long long)__float_as_uint(q) << 32) | (unsigned)P.slot);
+                    if (act[r] && !(q != q) && under(q, bound))
+                        bk[r] = min(bk[r], ((unsigned long long)__float_as_uint(q) << 32) | (unsigned)P.slot);
                 }
             } else if (!TOPK) {
                 if (i < nx) {
@@ -950,9 +995,10 @@ void emit_records(const std::vector<unsigned long long>& best, int k, const std:
 }
 
 // Launches k_exhaustive over the templates tm (already on the device at d_tm) with the lines at d_lines.
+// d_bc (best map only, or null): the pairs' exit bounds, with max_score: k_exhaustive<., kBestBound, .> in place of kBest.
 template <int MODE>
 void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLine* d_lines, const ExTmpl* d_tm, int T, int k,
-            int portions, float* map, unsigned long long* cand) {
+            int portions, float* map, unsigned long long* cand, const float* d_bc = nullptr, float max_score = 0.f) {
     const int tiles_x = (g.nx + kTileX - 1) / kTileX, tiles_y = (g.ny + kTileY - 1) / kTileY;
     const int n_subtiles = tiles_x * tiles_y;
     const float* vol = fm->vol.as<float>();
@@ -961,10 +1007,23 @@ void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLin
     for (int t0 = 0; t0 < T; t0 += per_launch) {
         const int nt = std::min(per_launch, T - t0);
         const dim3 grid((unsigned)(portions * ((nt + kChunk - 1) / kChunk)));  // portions: a multiple of 8
+        if constexpr (MODE == kBest)
+            if (d_bc) {
+                // (the 64-bit form always clamps: caps of +inf change no term, and without the clamp that form takes 130
+                // registers, a wave per SIMD fewer than the best map's -- DESIGN.md section 20)
+                auto kern = !P.buf32 ? k_exhaustive<false, kBestBound, true>
+                                     : (P.capped ? k_exhaustive<true, kBestBound, true> : k_exhaustive<true, kBestBound, false>);
+                hipLaunchKernelGGL(kern, grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty,
+                                   d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k, map, plane,
+                                   cand, ExBound<true>{d_bc, max_score});
+                FDCM_HIP(hipGetLastError());
+                continue;
+            }
         auto kern = P.capped ? (P.buf32 ? k_exhaustive<true, MODE, true> : k_exhaustive<false, MODE, true>)
                              : (P.buf32 ? k_exhaustive<true, MODE, false> : k_exhaustive<false, MODE, false>);
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty, d_lines,
-                           d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k, map, plane, cand);
+                           d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k, map, plane, cand,
+                           ExBound<false>{});
         FDCM_HIP(hipGetLastError());
     }
 }
@@ -1193,9 +1252,41 @@ std::vector<float> best_denominators(const fdcm_templates* t, int penalty, float
     return den;
 }
 
+// B of include/fdcm.h, "All detections below a score": the largest float32 s >= +0, possibly +inf, whose IEEE float32
+// quotient s / den is <= max_score.  The quotient rises with s, so the patterns that pass are a prefix of 0 .. +inf's: the
+// last one by bisection, as axis_interval.  (A denominator that is 0, infinite or NaN breaks that at the ends alone: +inf
+// when +inf passes, 0 when +0 does not.)
+float score_bound(float den, float max_score) {
+    auto ok = [&](uint32_t b) { return f_from_bits(b) / den <= max_score; };
+    const uint32_t inf = 0x7f800000u;
+    if (ok(inf)) return f_inf();
+    if (!ok(0)) return 0.f;
+    uint32_t lo = 0, hi = inf - 1;  // the last pattern that passes
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (ok(mid)) lo = mid; else hi = mid - 1;
+    }
+    return f_from_bits(lo);
+}
+
+// The bound rows_score's exit compares a partial sum with: B / (1 - 2 n u), u = 2^-24, rounded
+// upward, for a template of n lines.  A partial sum C of terms >= +0 is at most (1 + u)^(n-1) times their exact sum and the
+// finished float32 sum at least (1 - u)^(n-1) times the exact sum of all terms, so C > this bound puts the finished sum
+// above B.  +inf, the exit switched off, for an infinite B, for n > 2^20 (the factor has lost its meaning long before 2 n u
+// reaches 1) and for a bound above 1e38 (a partial sum that overflowed then still proves its point).
+constexpr int kExitMaxLines = 1 << 20;
+float exit_bound(float B, int n) {
+    if (!(B < f_inf()) || n > kExitMaxLines) return f_inf();
+    const double f = (double)B / (1.0 - 2.0 * (double)n * 0x1p-24);
+    float c = (float)f;
+    if ((double)c < f) c = std::nextafter(c, f_inf());
+    c = std::nextafter(c, f_inf());  // the double quotient's own rounding
+    return c > 1e38f ? f_inf() : c;
+}
+
 struct BestRun {
     char* d = nullptr;  // search.eval
-    size_t o_unit = 0, o_seg = 0, o_foot = 0, o_best = 0, o_pair = 0, o_keys = 0, o_plane = 0, o_cand = 0;
+    size_t o_unit = 0, o_seg = 0, o_foot = 0, o_bc = 0, o_best = 0, o_pair = 0, o_keys = 0, o_plane = 0, o_cand = 0;
     size_t n_keys = 0;
     int tiles_x = 0, parts = 0;
 };
@@ -1211,10 +1302,14 @@ constexpr size_t kNmsPartialBytes = 2 * kNmsWorkgroups * (8 + 4);  // two sets o
 // the merged list, the pairs of its entries, the candidate lists).  Returns false, with nothing queued, when no pair has
 // a grid point: every point is then without a candidate.  foot (or null): a footprint per pair, for the rounds of the
 // overlap rule; it goes up with the same upload, and the partial minima of the rounds take the candidate lists' place.
+// list: the entries of the result list and of its pairs.  max_score (or null): only the points with q <= *max_score get a
+// key (k_exhaustive<., kBestBound, .>); the exit bound of every pair goes up with the same upload.
 bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau, int k,
-               BestRun& R, const std::vector<Foot>* foot = nullptr) {
+               BestRun& R, const std::vector<Foot>* foot = nullptr, int list = kMaxK, const float* max_score = nullptr) {
     const std::vector<float> den = best_denominators(t, penalty, tau);
     const size_t np = P.nl.size();
+    std::vector<float> bc(max_score ? np : 0);
+    for (size_t u = 0; u < bc.size(); ++u) bc[u] = exit_bound(score_bound(den[u / (size_t)n], *max_score), P.nl[u]);
     std::vector<ExTmpl> tm(np + 1);
     bool any = false;
     for (size_t u = 0; u < np; ++u) {
@@ -1235,10 +1330,11 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
     R.o_unit = o_tm + np * sizeof(ExTmpl);
     R.o_seg = al256(R.o_unit + sizeof(ExTmpl));
     R.o_foot = R.o_seg + 256;
-    R.o_best = R.o_foot + (foot ? al256(np * sizeof(Foot)) : 0);
+    R.o_bc = R.o_foot + (foot ? al256(np * sizeof(Foot)) : 0);
+    R.o_best = R.o_bc + al256(bc.size() * sizeof(float));
     R.n_keys = n_keys;
-    R.o_pair = R.o_best + al256((size_t)kMaxK * 8);
-    R.o_keys = R.o_pair + al256((size_t)kMaxK * 4);
+    R.o_pair = R.o_best + al256((size_t)list * 8);
+    R.o_keys = R.o_pair + al256((size_t)list * 4);
     R.o_plane = R.o_keys + al256(n_keys * 8);
     R.o_cand = R.o_plane + al256((size_t)g.nx * g.ny * 4);
     fm->search.eval.reserve(R.o_cand + (foot ? kNmsPartialBytes : k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0));
@@ -1249,12 +1345,13 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
     std::memcpy(h + o_tm, tm.data(), tm.size() * sizeof(ExTmpl));
     std::memcpy(h + R.o_seg, &seg, sizeof seg);
     if (foot) std::memcpy(h + R.o_foot, foot->data(), np * sizeof(Foot));
-    std::memset(h + R.o_best, 0xff, (size_t)kMaxK * 8);  // kNoKey
+    if (max_score) std::memcpy(h + R.o_bc, bc.data(), bc.size() * sizeof(float));
+    std::memset(h + R.o_best, 0xff, (size_t)list * 8);  // kNoKey
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d, h, R.o_pair, hipMemcpyHostToDevice, st));
     FDCM_HIP(hipMemsetAsync(d + R.o_keys, 0xff, n_keys * 8, st));  // no key anywhere
     launch<kBest>(fm, P, g, (const ExLine*)d, (const ExTmpl*)(d + o_tm), (int)np, 0, portions_for(fm, g, (int)np), nullptr,
-                  (unsigned long long*)(d + R.o_keys));
+                  (unsigned long long*)(d + R.o_keys), max_score ? (const float*)(d + R.o_bc) : nullptr, max_score ? *max_score : 0.f);
     return true;
 }
 
@@ -1652,6 +1749,65 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
         FDCM_HIP(hipGetLastError());
     }
     detect_records(fm, R, P, rot != nullptr, n, g, k, base, out, n_out, foot.data(), boxes_out);
+}
+
+// All detections below a score (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  The key plane holds the points
+// with q <= max_score alone (best_keys with a threshold), the rounds are k_nms_round's on result arrays of max_det entries,
+// queued kNmsBatch at a time: after each batch the host reads the batch's last winner and stops when the list has ended, so
+// a short list costs one batch and no round costs a host round trip.
+constexpr int kNmsBatch = 64;
+
+void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
+                                      float max_score, int max_det, int permille, int margin, int penalty, float tau, int32_t base,
+                                      fdcm_match** out, int64_t* n_out, int32_t* boxes_out) {
+    check_grid(g);
+    *n_out = 0;
+    if (t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int n = rot ? rot->n : 1;
+    if (rot) check_rotated_size(t, n);
+    Pairs P;
+    prepare_pairs(fm, t, rot, false, P);
+    std::vector<Foot> foot(P.nl.size());
+    for (size_t u = 0; u < foot.size(); ++u)
+        foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    BestRun R;
+    // (+inf is no threshold: the plane is the best map's own, by the kernel without the checks)
+    if (!best_keys(fm, P, t, n, g, penalty, tau, 0, R, &foot, max_det, max_score < f_inf() ? &max_score : nullptr)) return;
+    hipStream_t st = fm->stream;
+    char* d = R.d;
+    unsigned long long* pk = (unsigned long long*)(d + R.o_cand);
+    int* pp = (int*)(d + R.o_cand + 2 * kNmsWorkgroups * 8);
+    unsigned long long* d_best = (unsigned long long*)(d + R.o_best);
+    const long long n_chunks = (long long)(R.n_keys / 256);
+    const unsigned wgs = (unsigned)std::min<long long>(kNmsWorkgroups, n_chunks);
+    for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
+        const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));  // winners [.., r1) after this batch: whole batches
+        for (; r <= r1; ++r) {
+            const int in = (r + 1) & 1, to = r & 1;
+            hipLaunchKernelGGL(k_nms_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)(d + R.o_keys), n_chunks, g.x0, g.y0, g.sx,
+                               g.sy, g.nx, R.tiles_x, (const int4*)(d + R.o_foot), permille, r, (int)(r == max_det),
+                               (const unsigned long long*)(pk + in * kNmsWorkgroups), (const int*)(pp + in * kNmsWorkgroups),
+                               pk + to * kNmsWorkgroups, pp + to * kNmsWorkgroups, d_best, (int*)(d + R.o_pair));
+            FDCM_HIP(hipGetLastError());
+        }
+        if (r > max_det) break;
+        unsigned long long last = kNoKey;  // winner r1 - 1, the batch's last
+        FDCM_HIP(hipMemcpyAsync(&last, d_best + (r1 - 1), 8, hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+        if (last == kNoKey) break;  // the list has ended: the entries from there on are kNoKey (written, or the upload's)
+    }
+    detect_records(fm, R, P, rot != nullptr, n, g, max_det, base, out, n_out, foot.data(), boxes_out);
+}
+
+float detect_score_bound(float den, float max_score) { return score_bound(den, max_score); }
+
+// B_t per template (include/fdcm.h): score_bound of best_denominators' den_t; 0 for a template without lines.  Host only.
+void detect_score_bounds(const fdcm_templates* t, int penalty, float tau, float max_score, float* bounds) {
+    const std::vector<float> den = best_denominators(t, penalty, tau);
+    for (int64_t i = 0; i < t->T; ++i)
+        bounds[i] = t->offsets[(size_t)i + 1] == t->offsets[(size_t)i] ? 0.f : score_bound(den[(size_t)i], max_score);
 }
 
 void exhaustive_rotations_window(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations& rot, int32_t sx, int32_t sy,

@@ -355,6 +355,13 @@ void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, 
 void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
                                       int permille, int margin, int penalty, float tau, int32_t base, fdcm_match** out,
                                       int32_t* boxes_out, int64_t* n_out);
+// boxes_out: 4 max_det int32, or null
+void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
+                                      float max_score, int max_det, int permille, int margin, int penalty, float tau, int32_t base,
+                                      fdcm_match** out, int64_t* n_out, int32_t* boxes_out);
+// host only: per template the largest sum whose normalised score is <= max_score
+void detect_score_bounds(const fdcm_templates* t, int penalty, float tau, float max_score, float* bounds);
+float detect_score_bound(float den, float max_score);  // the same for one denominator
 // host only: 4 int32 per pair t n + a (rot null: n = 1, the lines as they are)
 void templates_footprints(const fdcm_templates* t, const fdcm_rotations* rot, int margin, int32_t* boxes_out);
 void lines_footprints(const float* lines, const int64_t* offsets, int64_t T, const fdcm_rotations* rot, int margin, int32_t* boxes_out);

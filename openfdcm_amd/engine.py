@@ -407,6 +407,22 @@ class DeviceFeatureMap:
         rec = _adopt_matches(out, n.value)
         return (rec, fp[:n.value].copy()) if boxes else rec
 
+    def exhaustive_detect_all(self, templates, grid, cs=None, pivots=None, max_score=float("inf"), max_detections=1024,
+                              overlap_permille=300, margin=0, penalty=None, tau=1.0, tmpl_index_base=0, boxes=False):
+        """All detections below a score (include/fdcm.h): exhaustive_detect_nms' greedy rule on the points whose normalised
+        score is at most max_score, until they run out or max_detections (1 to 4096) is reached.  Raw match records in
+        ascending order; with boxes also the (n, 4) int32 footprints."""
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        g = as_grid(grid)
+        out, n = C.c_void_p(), C.c_int64()
+        fp = np.zeros((int(max_detections) if 1 <= int(max_detections) <= 4096 else 0, 4), dtype=np.int32)
+        capi.check(capi.lib().fdcm_search_exhaustive_detect_all(
+            self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), float(max_score), int(max_detections),
+            int(overlap_permille), int(margin), -1 if penalty is None else int(penalty), float(tau), int(tmpl_index_base),
+            C.byref(out), C.byref(n), fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and fp.size else None))
+        rec = _adopt_matches(out, n.value)
+        return (rec, fp[:n.value].copy()) if boxes else rec
+
     def line_costs(self, templates, poses, cs=None, pivots=None):
         """Line costs (include/fdcm.h, "Per-line caps and line costs"): poses (n, 4) int32 rows (tmpl, a, x, y), a an index
         into the rotations cs (0 with cs None, the lines as they are).  Returns (float32 costs, int64 offsets of n + 1): pose
@@ -524,6 +540,14 @@ class DeviceTemplates:
         out = np.zeros((self.count, n, 4), dtype=np.int32)
         capi.check(capi.lib().fdcm_templates_footprints(self._h, C.byref(rot) if rot is not None else None, int(margin),
                                                         out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def score_bounds(self, max_score, penalty=None, tau=1.0):
+        """Per template the largest float32 sum whose normalised score is <= max_score (fdcm_detect_score_bounds); 0 for a
+        template without lines.  Host only."""
+        out = np.zeros(self.count, dtype=np.float32)
+        capi.check(capi.lib().fdcm_detect_score_bounds(self._h, -1 if penalty is None else int(penalty), float(tau), float(max_score),
+                                                       capi.fptr(out)))
         return out
 
     def lengths(self):

@@ -15,11 +15,17 @@ radius 8, ExponentialPenalty(1.5).  In the same run, on the same grid:
                 it: fdcm_best_map to the host (both planes) and the greedy rule of tests/nms_ref.py in numpy, whose records
                 are compared with the call's
 
+  all           (--all, on its own: the rows above are left out) "All detections below a score": per stride one blocking
+                fdcm_search_exhaustive_detect_nms call at k = 64, the yardstick, which a build from before the new call has
+                too; then, where the library has it, fdcm_search_exhaustive_detect_all at max_detections = 64 and max_score =
+                +inf and the 50 %, 5 % and 0.5 % quantiles of the finite scores of fdcm_best_map on that grid, each compared
+                with the leading records of the +inf list; and once max_detections = 4096 at overlap 1000, the most rounds
+
 Each device figure is the median of --reps blocking calls after a warm-up; the host composition runs --host-reps times.
 --line-caps TAU gives every template line the cap TAU * its length (include/fdcm.h, "Per-line caps and line costs") in every
 call of the run, the host composition's score map included.  Off by default.
 
-    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--line-caps TAU] [--nms] [--json out.json]
+    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--line-caps TAU] [--nms | --all] [--json out.json]
 """
 import argparse
 import json
@@ -69,6 +75,47 @@ def nms_host_composition(dev, tset, grid, penalty, tau, k, permille):
     return rec, t1 - t0, time.perf_counter() - t1
 
 
+def all_mode(args, dev, tset, pen, tau, timed, spread):
+    """The rows of --all."""
+    pm = int(round(1000 * args.overlap))
+    has_all = hasattr(dev, "exhaustive_detect_all")
+    rows = []
+    for s in [int(v) for v in args.strides.split(",")]:
+        grid = dev.exhaustive_window(tset, s, s).as_tuple()
+        n64_ms, n64_min, nrec = timed(lambda: dev.exhaustive_detect_nms(tset, grid, k=64, overlap_permille=pm, penalty=pen, tau=tau))
+        row = {"stride": s, "grid": list(grid), "grid_points": grid[2] * grid[3], "overlap_permille": pm,
+               "nms_k64_ms": round(n64_ms, 3), "nms_k64_ms_min": round(n64_min, 3), "nms_k64_ms_spread": round(spread[-1], 3),
+               "nms_k64_detections": int(len(nrec))}
+        print(f"stride {s}: grid {grid[2]}x{grid[3]}: nms k 64 {n64_ms:.2f} ms (min {n64_min:.2f}, spread {spread[-1]:.2f}), "
+              f"{len(nrec)} detections", flush=True)
+        if has_all:
+            scores, _ = dev.best_map(tset, grid, penalty=pen, tau=tau)
+            fin = np.sort(scores[np.isfinite(scores)])
+            cases = [("inf", float("inf"))] + [(name, float(fin[min(len(fin) - 1, int(f * len(fin)))]))
+                                               for name, f in (("q50", 0.5), ("q5", 0.05), ("q0.5", 0.005))]
+            full = None
+            for name, ms in cases:
+                call = lambda: dev.exhaustive_detect_all(tset, grid, max_score=ms, max_detections=64, overlap_permille=pm, penalty=pen,
+                                                         tau=tau)
+                a_ms, a_min, rec = timed(call)
+                full = rec if full is None else full
+                cnt = int((full["score"] <= np.float32(ms)).sum())
+                same = rec.tobytes() == (nrec if name == "inf" else full[:cnt]).tobytes()
+                row["all_" + name] = {"max_score": ms, "ms": round(a_ms, 3), "ms_min": round(a_min, 3), "ms_spread": round(spread[-1], 3),
+                                      "detections": int(len(rec)), "to_nms_k64": round(a_ms / n64_ms, 3), "records_as_predicted": bool(same)}
+                print(f"stride {s}: all max_score {name} = {ms:.6g}: {a_ms:.2f} ms (min {a_min:.2f}, spread {spread[-1]:.2f}), "
+                      f"{a_ms / n64_ms:.3f} of nms k 64; {len(rec)} detections; as predicted: {same}", flush=True)
+            t0 = time.perf_counter()
+            rec = dev.exhaustive_detect_all(tset, grid, max_score=float("inf"), max_detections=4096, overlap_permille=1000, penalty=pen,
+                                            tau=tau)
+            row["all_4096_overlap_1000_ms_once"] = round((time.perf_counter() - t0) * 1e3, 3)
+            row["all_4096_overlap_1000_detections"] = int(len(rec))
+            print(f"stride {s}: all max_detections 4096, overlap 1000, once: {row['all_4096_overlap_1000_ms_once']:.2f} ms, "
+                  f"{len(rec)} detections", flush=True)
+        rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=5)
@@ -79,7 +126,8 @@ def main():
     ap.add_argument("--tau", type=float, default=1.5)
     ap.add_argument("--line-caps", type=float, default=None, metavar="TAU", help="cap every line's cost at TAU * its length")
     ap.add_argument("--nms", action="store_true", help="also time the detections suppressed by footprint overlap")
-    ap.add_argument("--overlap", type=float, default=0.3, help="the overlap threshold of --nms")
+    ap.add_argument("--all", action="store_true", help="time all detections below a score, against nms at k = 64 (only)")
+    ap.add_argument("--overlap", type=float, default=0.3, help="the overlap threshold of --nms and --all")
     ap.add_argument("--json", default=None, help="also write the results here")
     args = ap.parse_args()
 
@@ -103,7 +151,9 @@ def main():
         return float(np.median(times)) * 1e3, min(times) * 1e3, out
 
     rows, spread = [], []  # spread: max - min of the last timed() call's repetitions
-    for s in [int(v) for v in args.strides.split(",")]:
+    if args.all:
+        rows = all_mode(args, dev, tset, pen, tau, timed, spread)
+    for s in [] if args.all else [int(v) for v in args.strides.split(",")]:
         grid = dev.exhaustive_window(tset, s, s).as_tuple()
         det_ms, det_min, recs = timed(lambda: dev.exhaustive_detect(tset, grid, k=k, rx=r, ry=r, penalty=pen, tau=tau))
         det_spread = spread[-1]
