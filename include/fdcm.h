@@ -622,6 +622,53 @@ int fdcm_templates_line_lengths(const fdcm_templates* t, float* lengths /* n_lin
 int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
                     const int32_t* poses /* n x 4: tmpl, a, x, y */, int64_t n, float** costs, int64_t* offsets /* n + 1 */);
 
+/* Detections by matched fraction: how much of the template was found.  With caps q lies in [0, tau] and saturates: a view
+ * that is mediocre on every line can have the q of a correct view with a third of its lines hidden, and max_score cannot
+ * tell them apart.  The matched fraction can, and the gate below applies it before the greedy rule, so that a junk point
+ * never suppresses a good neighbour.  The definitions are this project's (README.md, "Detections by matched fraction"; numpy
+ * statement: tests/matched_ref.py).  Everything not restated here is fdcm_search_exhaustive_detect_all's, unchanged:
+ * candidates, q, pairkey, best(g), key(g), footprints, the overlap test, the record layout, admissibility and rot == NULL.
+ * Line quantities: for line i of template t, len_i is the float32 fdcm_templates_line_lengths returns, the length of the
+ * unrotated line; like a cap it is kept under every rotation and is not rescaled by a rot entry with scale.  cap_i is the
+ * set's cap of line i (+inf for a set without caps).  cost_i(u, t) is the uncapped line cost of the pair u = (t, a) at the
+ * translation, exactly the float fdcm_line_costs returns.
+ * Matched: line i is matched at (u, t) when cost_i <= cap_i, one float32 compare: a NaN cost is not matched, an infinite
+ * cost under cap_i = +inf is, and a line with cap_i = 0 is matched only at cost 0.
+ * Matched length: ML(u, t) = (((+0 + w_0) + w_1) + ..) in float32, in line order, w_i = len_i when line i is matched and +0
+ * otherwise.  TL_t is the same sum with every line matched, so +0 <= ML <= TL_t (float addition is monotone).
+ * Fraction: frac(u, t) = ML / TL_t, one IEEE float32 division; 1 when TL_t == 0 (a template without lines, or with lines of
+ * length zero only); NaN when the pose is not admissible for u, whatever TL_t.
+ * Gate: min_matched is a float32 in [0, 1]; need_t = float32(min_matched * TL_t), one float32 product.  A grid point g with a
+ * candidate passes when ML(best(g), t_g) >= need_t, t the template of best(g).  S_0 is the set of points with a candidate,
+ * q(best(g)) <= max_score, that pass the gate; the greedy rule runs on this S_0, stopping at max_detections.
+ * What the gate looks at: the pair the best map holds at g, and only that pair.  A point whose best pair fails is dropped,
+ * even if another pair at g would pass: the gate is not part of the minimum that chooses best(g).
+ * fdcm_search_exhaustive_detect_all_matched: fdcm_search_exhaustive_detect_all with the gate.  matched_out (max_detections
+ * floats, or NULL): entry l is frac of record l; the entries from *n_out on are not specified.
+ * fdcm_matched_fractions: frac at n poses (tmpl, a, x, y); poses, admissibility and rot are fdcm_line_costs'.
+ * fdcm_templates_matched_totals (host only, no device work): TL_t per template.
+ * Identities: min_matched = 0 gives fdcm_search_exhaustive_detect_all's records and boxes, byte for byte (no gate pass is
+ * queued).  A set whose caps are all +inf, on a volume without NaN or infinity, has frac = 1 everywhere, and any
+ * min_matched gives those bytes.  At a fixed min_matched the records for any max_score are the leading records with score
+ * <= max_score of the +inf list.  With overlap_permille = 1000 and max_detections not reached the records are the
+ * min_matched = 0 list without the failing points, order kept.  matched_out[l] is, bit for bit, what
+ * fdcm_matched_fractions returns for record l's (tmpl, a, x, y); and for an admissible pose ML computed from
+ * fdcm_line_costs' floats, the set's caps and lengths by the rule above is the device's, bit for bit.  Results are a
+ * function of the inputs alone.
+ * FDCM_EINVAL, before any GPU work: everything fdcm_search_exhaustive_detect_all rejects; min_matched NaN, < 0 or > 1; for
+ * fdcm_matched_fractions what fdcm_line_costs rejects about n, poses, rot and the handles, and fractions NULL with n > 0.
+ * n = 0, an empty feature map or an empty template list return FDCM_OK and write nothing.  The calls block; concurrent
+ * callers of one feature map take turns.  Release the records with fdcm_matches_free. */
+int fdcm_search_exhaustive_detect_all_matched(const fdcm_featuremap* fm, const fdcm_templates* templates,
+                                              const fdcm_rotations* rot /* or NULL */, const fdcm_grid* grid, float max_score,
+                                              int32_t max_detections, int32_t overlap_permille, int32_t margin, int penalty, float tau,
+                                              float min_matched, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                              int32_t* boxes_out /* 4 max_detections, or NULL */,
+                                              float* matched_out /* max_detections, or NULL */);
+int fdcm_matched_fractions(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                           const int32_t* poses /* n x 4: tmpl, a, x, y */, int64_t n, float* fractions /* n */);
+int fdcm_templates_matched_totals(const fdcm_templates* templates, float* totals /* n_templates */);
+
 /* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
  *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as
  *      fdcm_edge_labels makes it (m = the distinct keys of `depth`, a byte < m an edge pixel of that label, labels circular)

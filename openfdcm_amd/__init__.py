@@ -691,23 +691,30 @@ def exhaustive_detect_nms(featuremap, templates, overlap=0.3, stride=1, k=8, pen
 
 
 def exhaustive_detect_all(featuremap, templates, max_score, overlap=0.3, stride=1, max_detections=1024, penalty=None, angles=None,
-                          pivot="center", window=None, line_caps=None, margin=0, return_boxes=False):
+                          pivot="center", window=None, line_caps=None, margin=0, return_boxes=False, min_matched=None,
+                          return_matched=False):
     """Every detection that matches at least as well as max_score: exhaustive_detect_nms' greedy rule on the points of
     best_score_map's plane whose score is <= max_score (>= 0 or inf), until they run out or max_detections (1 to 4096) is
     reached.  A scene with two parts gives two detections, not k records of which six are junk, and a bin of 200 small
     parts gives 200.  max_score=inf with max_detections=k is exhaustive_detect_nms(k=k); a lower max_score returns the
     leading part of that list, and costs less: a template is dropped for a patch of points as soon as its partial sums put
     all of them over the threshold.  Returns a MatchList in ascending score, and with return_boxes also the (n, 4) int32
-    footprints.  The other arguments are exhaustive_detect_nms'."""
+    footprints.  min_matched (0 to 1): a point is dropped, before the greedy rule, unless the lines of its winning template
+    that cost at most their caps there make up at least that share of the template's line length; a junk point then never
+    suppresses a good neighbour.  Only the winning pair of a point is looked at.  return_matched: that share of every
+    detection as an (n,) float32 array, last in the returned tuple: (dets, matched) or (dets, boxes, matched).  The other
+    arguments are exhaustive_detect_nms'."""
     kind, tau = _penalty_args(penalty)
     permille = int(round(1000 * float(overlap)))
     fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
     if g[2] == 0 or g[3] == 0:
-        empty = MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE))
-        return (empty, _np.zeros((0, 4), dtype=_np.int32)) if return_boxes else empty
+        res = (MatchList(_np.zeros(0, dtype=_capi.MATCH_DTYPE)),) + ((_np.zeros((0, 4), dtype=_np.int32),) if return_boxes else ())
+        res += (_np.zeros(0, dtype=_np.float32),) if return_matched else ()
+        return res if len(res) > 1 else res[0]
     res = fm.exhaustive_detect_all(tset, g, cs, pv, max_score=max_score, max_detections=max_detections, overlap_permille=permille,
-                                   margin=margin, penalty=kind, tau=tau, boxes=return_boxes)
-    return (MatchList(res[0]), res[1]) if return_boxes else MatchList(res)
+                                   margin=margin, penalty=kind, tau=tau, boxes=return_boxes, min_matched=min_matched,
+                                   matched=return_matched)
+    return (MatchList(res[0]),) + tuple(res[1:]) if return_boxes or return_matched else MatchList(res)
 
 
 def detect_score_bounds(templates, penalty, max_score):
@@ -820,13 +827,27 @@ def line_costs(featuremap, templates, poses, angles=None, pivot="center"):
     pose_windows(records, angles, angles, pivots, 0, 0, 0)[:, [0, 1, 3, 4]] turns the records of the dense searches over
     `angles` (pivots = template_pivots(templates, pivot)) into poses; for searches without angles the poses are
     (tmpl_idx, 0, transform[2], transform[5]).  With caps c, the matched fraction of a pose is
-    sum(len_i[cost_i <= c_i]) / sum(len_i)."""
+    sum(len_i[cost_i <= c_i]) / sum(len_i); matched_fractions computes it on the device."""
     fm = _device_map(featuremap)
     tset = _template_cache.get(templates)
     cs = pv = None
     if angles is not None:
         cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
     return fm.line_costs(tset, poses, cs, pv)
+
+
+def matched_fractions(featuremap, templates, poses, angles=None, pivot="center", line_caps=None):
+    """The matched fraction of every pose of an (n, 4) int32 array of rows (tmpl, a, x, y), as line_costs takes them: the
+    share of the template's line length whose lines cost at most their caps (line_caps, exhaustive_search's) at the pose,
+    computed on the device by exhaustive_detect_all's rule.  1 for a template whose line lengths sum to 0, NaN where the pose
+    puts the template outside the feature map.  In a tracker that follows a pose with exhaustive_window_search, a fraction
+    that falls means the track is lost.  Returns an (n,) float32 array."""
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates, line_caps)
+    cs = pv = None
+    if angles is not None:
+        cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
+    return fm.matched_fractions(tset, poses, cs, pv)
 
 
 from .lineio import read, write  # noqa: E402  (.lines/.scene/.tmpl files, serialization.h)

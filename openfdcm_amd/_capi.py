@@ -177,6 +177,11 @@ SYMBOLS = [
     ("fdcm_search_exhaustive_detect_all", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_float, C.c_int32, C.c_int32,
                                                    C.c_int32, C.c_int, C.c_float, C.c_int32, C.POINTER(_vp), _i64p,
                                                    C.POINTER(C.c_int32)]),
+    ("fdcm_search_exhaustive_detect_all_matched", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_float, C.c_int32,
+                                                           C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int32,
+                                                           C.POINTER(_vp), _i64p, C.POINTER(C.c_int32), _fp]),
+    ("fdcm_matched_fractions", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64, _fp]),
+    ("fdcm_templates_matched_totals", C.c_int, [_vp, _fp]),
     ("fdcm_detect_score_bounds", C.c_int, [_vp, C.c_int, C.c_float, C.c_float, _fp]),
     ("fdcm_score_bound", C.c_int, [C.c_float, C.c_float, _fp]),
     ("fdcm_templates_footprints", C.c_int, [_vp, C.POINTER(Rotations), C.c_int32, C.POINTER(C.c_int32)]),

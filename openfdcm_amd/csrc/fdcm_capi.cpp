@@ -877,6 +877,61 @@ int fdcm_search_exhaustive_detect_all(const fdcm_featuremap* fm, const fdcm_temp
     });
 }
 
+// Detections by matched fraction: include/fdcm.h, "Detections by matched fraction".  The threshold call's checks and the
+// gate's: nothing here touches the device.
+int fdcm_search_exhaustive_detect_all_matched(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                              const fdcm_grid* grid, float max_score, int32_t max_detections, int32_t overlap_permille,
+                                              int32_t margin, int penalty, float tau, float min_matched, int32_t tmpl_index_base,
+                                              fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
+    return guarded([&] {
+        require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
+        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
+        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(min_matched >= 0.f && min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
+        require(out && n_out, "null output");
+        check_best_args(fm, templates, rot, grid, penalty, tau);
+        records_call(out, [&] {
+            run_search_exhaustive_detect_all_matched(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid,
+                                                     max_score == 0.f ? 0.f : max_score, max_detections, overlap_permille, margin, penalty,
+                                                     tau, min_matched == 0.f ? 0.f : min_matched, tmpl_index_base, out, n_out, boxes_out,
+                                                     matched_out);
+        });
+    });
+}
+
+// The line costs' checks, with the one output: nothing here touches the device.
+int fdcm_matched_fractions(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot, const int32_t* poses,
+                           int64_t n, float* fractions) {
+    return guarded([&] {
+        require(n >= 0, "n is negative");
+        require(n == 0 || poses, "poses is null");
+        require(n == 0 || fractions, "fractions is null");
+        if (rot) check_rotations(rot);  // null: the lines as they are, a table of one rotation
+        const int32_t n_rot = rot ? rot->n : 1, lim = 1 << 24;
+        for (int64_t q = 0; q < n; ++q) {
+            const int32_t* p = poses + 4 * q;
+            require(p[0] >= 0, "poses: tmpl is outside the template set");
+            require(p[1] >= 0 && p[1] < n_rot, rot ? "poses: a must be in [0, n - 1]" : "poses: a must be 0 without rotations");
+            require(p[2] > -lim && p[2] < lim && p[3] > -lim && p[3] < lim, "poses: every translation must satisfy |t| < 2^24");
+        }
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        if (rot) check_pivots(templates, rot);
+        for (int64_t q = 0; q < n && templates->T > 0; ++q)
+            require(poses[4 * q] < templates->T, "poses: tmpl is outside the template set");
+        run_matched_fractions(const_cast<fdcm_featuremap*>(fm), templates, rot, poses, n, fractions);
+    });
+}
+
+int fdcm_templates_matched_totals(const fdcm_templates* templates, float* totals) {
+    return guarded([&] {
+        require(templates != nullptr, "templates is null");
+        require(totals != nullptr || templates->T == 0, "totals is null");
+        templates_matched_totals(templates, totals);
+    });
+}
+
 int fdcm_score_bound(float den, float max_score, float* bound) {
     return guarded([&] {
         require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");

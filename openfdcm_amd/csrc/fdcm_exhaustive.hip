@@ -19,6 +19,10 @@
 //   k_exhaustive_windows<BUF32>       pose windows: a wave takes a run of 4 x 16 patches of the clipped boxes of a batch's
 //                                     (job, rotation) planes, a lane per translation, and keeps a k-best list per job
 //   k_line_costs<BUF32>               line costs: a wave per pose, a lane per line of its template: the terms of the sum
+//   k_matched_gate<BUF32>, k_matched_list<BUF32>, k_matched_fractions<BUF32>
+//                                     matched fraction: a thread per point of the key plane (the gate before the rounds of
+//                                     k_nms_round), per entry of the result list, per pose of a list; all three through
+//                                     matched_length<BUF32>, the one statement of the matched length
 //
 // Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP, EXIT>, the one statement of the sum (4 rows per lane in
 // k_exhaustive, 1 in k_exhaustive_windows).  CAP: every term clamped to its line's cap (include/fdcm.h, "Per-line caps and
@@ -711,6 +715,95 @@ __global__ void __launch_bounds__(256) k_line_costs(const float* __restrict__ vo
     }
 }
 
+// ---- matched length (include/fdcm.h, "Detections by matched fraction"): the one statement of ML for every kernel below.
+// Line i of the n lines at Lt is matched at the translation when its uncapped cost, k_line_costs' float, is <= its cap: one
+// float32 compare, so a NaN cost is not matched and an infinite one under a cap of +inf is.  ML is the float32 sum of the
+// matched lines' lengths len[i] (an array parallel to the lines) in line order, from +0: sequential by definition, so a
+// thread walks its pose's lines alone.  The translation is admissible: every read stays inside the volume.
+template <bool BUF32>
+__device__ __forceinline__ float matched_length(const VolRef& V, const ExLine* __restrict__ Lt, const float* __restrict__ len, int n,
+                                                float offx, float offy, int W, unsigned uH, size_t SL) {
+    float ml = 0.f;
+    for (int i = 0; i < n; ++i) {
+        const ExLine ln = Lt[i];
+        const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
+        const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
+        const float c = line_term<false>(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy), uH), ex_read<BUF32>(V, c2, (int)(ln.y2 + offy), uH), 0.f);
+        if (c <= ln.cap) ml = ml + len[i];
+    }
+    return ml;
+}
+// frac = ML / TL, one IEEE division; 1 for a template whose lengths sum to 0
+__device__ __forceinline__ float matched_fraction(float ml, float tl) { return tl == 0.f ? 1.f : ml / tl; }
+
+// The gate: one thread per entry of the key plane k_exhaustive<., kBest> merged, in the plane's own order (k_nms_round's
+// inverse of best_key_index).  An entry with a key computes ML of its pair at its point and loses its key unless
+// ML >= need[pair].  Each entry is read and written by its one thread; lanes of a wave hold different pairs.
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_matched_gate(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
+                                                      const ExLine* __restrict__ lines, const float* __restrict__ len,
+                                                      const ExTmpl* __restrict__ tm, const float* __restrict__ need,
+                                                      unsigned long long* keys, long long n_keys, int x0, int y0, int sx, int sy,
+                                                      int tiles_x) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_keys) return;
+    const unsigned long long v = keys[idx];
+    if (v == kNoKey) return;
+    const int tile = (int)(idx >> 10), r = (int)(idx & 1023);
+    const int i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
+    const int j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
+    const int u = (int)(unsigned)v;
+    const int line0 = tm[u].line0, n = tm[u].n;
+    const VolRef V = make_volref(vol, SL, m, BUF32);
+    const float ml = matched_length<BUF32>(V, lines + line0, len + line0, n, tx + (float)(x0 + i * sx), ty + (float)(y0 + j * sy), W,
+                                           (unsigned)H, SL);
+    if (!(ml >= need[u])) keys[idx] = kNoKey;
+}
+
+// The fractions of the result list: entry l < k of best (a key (bits of q << 32) | g, kNoKey from the list's end on) with
+// its pair; tl: TL of every pair's template.  NaN from the end of the list on.
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_matched_list(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
+                                                      const ExLine* __restrict__ lines, const float* __restrict__ len,
+                                                      const ExTmpl* __restrict__ tm, const float* __restrict__ tl,
+                                                      const unsigned long long* __restrict__ best, const int* __restrict__ pair, int k,
+                                                      int x0, int y0, int sx, int sy, int nx, float* __restrict__ frac) {
+    const int l = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (l >= k) return;
+    const unsigned long long v = best[l];
+    if (v == kNoKey) { frac[l] = f_nan(); return; }
+    const unsigned g = (unsigned)v;
+    const int i = (int)(g % (unsigned)nx), j = (int)(g / (unsigned)nx);
+    const int u = pair[l];
+    const int line0 = tm[u].line0, n = tm[u].n;
+    const VolRef V = make_volref(vol, SL, m, BUF32);
+    const float ml = matched_length<BUF32>(V, lines + line0, len + line0, n, tx + (float)(x0 + i * sx), ty + (float)(y0 + j * sy), W,
+                                           (unsigned)H, SL);
+    frac[l] = matched_fraction(ml, tl[u]);
+}
+
+// The fractions of a pose list (fdcm_matched_fractions): a thread per pose.  The host decided admissibility, as for
+// k_line_costs: a pose that is not admissible writes NaN and reads nothing of the volume.
+struct FracPose {
+    int line0, n;  // its pair's lines in the line array
+    int x, y;      // the translation
+    float tl;      // TL of its template
+    int adm;
+};
+
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_matched_fractions(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
+                                                           float ty, const ExLine* __restrict__ lines, const float* __restrict__ len,
+                                                           const FracPose* __restrict__ poses, int n_poses, float* __restrict__ out) {
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (q >= n_poses) return;
+    const FracPose P = poses[q];
+    if (!P.adm) { out[q] = f_nan(); return; }
+    const VolRef V = make_volref(vol, SL, m, BUF32);
+    const float ml = matched_length<BUF32>(V, lines + P.line0, len + P.line0, P.n, tx + (float)P.x, ty + (float)P.y, W, (unsigned)H, SL);
+    out[q] = matched_fraction(ml, P.tl);
+}
+
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // The integer translations t in [-kMaxCoord, kMaxCoord] with lo < fl(p + fl(off + t)) < hi for p = pmin and p = pmax, i.e.
@@ -866,6 +959,8 @@ void on_threads(int nth, const char* what, F part) {
 struct Pairs {
     std::vector<int64_t> key;    // tmpl * n + a, ascending; empty: every pair of the set, pair u being tmpl * n + a = u
     std::vector<ExLine> lines;   // (never empty)
+    bool lens = false;           // set before prepare_pairs: also fill len (the matched fraction's calls)
+    std::vector<float> len;      // per line of `lines`: its template line's length, kept under every rotation (or empty)
     std::vector<int> line0, nl;  // per pair: its lines
     std::vector<Box> box;
     std::vector<RotM> M;  // (rotations only)
@@ -902,6 +997,11 @@ void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdc
         throw std::string(all && !rot ? "too many template lines for one exhaustive search"
                                       : "too many rotated template lines for one call");
     W.lines.assign((size_t)std::max<int64_t>(1, total), ExLine{});
+    if (W.lens) {
+        W.len.assign(W.lines.size(), 0.f);
+        for (size_t u = 0; u < np; ++u)
+            std::copy_n(t->lengths.begin() + t->offsets[(size_t)(key_of(u) / n)], W.nl[u], W.len.begin() + W.line0[u]);
+    }
     const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)np, total >> 12}));
     std::vector<size_t> cut((size_t)nth + 1);
     for (int c = 0; c <= nth; ++c) cut[(size_t)c] = np * (size_t)c / (size_t)nth;
@@ -1287,6 +1387,7 @@ float exit_bound(float B, int n) {
 struct BestRun {
     char* d = nullptr;  // search.eval
     size_t o_unit = 0, o_seg = 0, o_foot = 0, o_bc = 0, o_best = 0, o_pair = 0, o_keys = 0, o_plane = 0, o_cand = 0;
+    size_t o_tm = 0, o_len = 0, o_need = 0, o_tl = 0, o_frac = 0;  // (the matched fraction's calls)
     size_t n_keys = 0;
     int tiles_x = 0, parts = 0;
 };
@@ -1303,9 +1404,14 @@ constexpr size_t kNmsPartialBytes = 2 * kNmsWorkgroups * (8 + 4);  // two sets o
 // a grid point: every point is then without a candidate.  foot (or null): a footprint per pair, for the rounds of the
 // overlap rule; it goes up with the same upload, and the partial minima of the rounds take the candidate lists' place.
 // list: the entries of the result list and of its pairs.  max_score (or null): only the points with q <= *max_score get a
-// key (k_exhaustive<., kBestBound, .>); the exit bound of every pair goes up with the same upload.
+// key (k_exhaustive<., kBestBound, .>); the exit bound of every pair goes up with the same upload.  mt (or null; include/fdcm.h,
+// "Detections by matched fraction"): P.len, and per pair the gate's need and the template's TL, whichever is given, go up
+// with the same upload too, and the list gets a float per entry for its fractions.
+struct MatchedIn { const float* need; const float* tl; };  // one float per pair each, or null
+
 bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau, int k,
-               BestRun& R, const std::vector<Foot>* foot = nullptr, int list = kMaxK, const float* max_score = nullptr) {
+               BestRun& R, const std::vector<Foot>* foot = nullptr, int list = kMaxK, const float* max_score = nullptr,
+               const MatchedIn* mt = nullptr) {
     const std::vector<float> den = best_denominators(t, penalty, tau);
     const size_t np = P.nl.size();
     std::vector<float> bc(max_score ? np : 0);
@@ -1331,10 +1437,15 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
     R.o_seg = al256(R.o_unit + sizeof(ExTmpl));
     R.o_foot = R.o_seg + 256;
     R.o_bc = R.o_foot + (foot ? al256(np * sizeof(Foot)) : 0);
-    R.o_best = R.o_bc + al256(bc.size() * sizeof(float));
+    R.o_tm = o_tm;
+    R.o_len = R.o_bc + al256(bc.size() * sizeof(float));
+    R.o_need = R.o_len + (mt ? al256(P.len.size() * sizeof(float)) : 0);
+    R.o_tl = R.o_need + (mt && mt->need ? al256(np * sizeof(float)) : 0);
+    R.o_best = R.o_tl + (mt && mt->tl ? al256(np * sizeof(float)) : 0);
     R.n_keys = n_keys;
     R.o_pair = R.o_best + al256((size_t)list * 8);
-    R.o_keys = R.o_pair + al256((size_t)list * 4);
+    R.o_frac = R.o_pair + al256((size_t)list * 4);
+    R.o_keys = R.o_frac + (mt ? al256((size_t)list * 4) : 0);
     R.o_plane = R.o_keys + al256(n_keys * 8);
     R.o_cand = R.o_plane + al256((size_t)g.nx * g.ny * 4);
     fm->search.eval.reserve(R.o_cand + (foot ? kNmsPartialBytes : k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0));
@@ -1346,6 +1457,9 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
     std::memcpy(h + R.o_seg, &seg, sizeof seg);
     if (foot) std::memcpy(h + R.o_foot, foot->data(), np * sizeof(Foot));
     if (max_score) std::memcpy(h + R.o_bc, bc.data(), bc.size() * sizeof(float));
+    if (mt) std::memcpy(h + R.o_len, P.len.data(), P.len.size() * sizeof(float));
+    if (mt && mt->need) std::memcpy(h + R.o_need, mt->need, np * sizeof(float));
+    if (mt && mt->tl) std::memcpy(h + R.o_tl, mt->tl, np * sizeof(float));
     std::memset(h + R.o_best, 0xff, (size_t)list * 8);  // kNoKey
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d, h, R.o_pair, hipMemcpyHostToDevice, st));
@@ -1364,14 +1478,16 @@ void best_unpack(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, floa
 // The records of the detections (include/fdcm.h, "Best map and detections"): downloads the list of k keys (bits of q << 32)
 // | g at o_best and the pairs of its entries at o_pair, waits for the stream, and emits entry l as the pair t n + a = pair[l]
 // at the grid point of its key (kNoKey ends the list).  foot and boxes_out (or null): the footprint of each pair; the
-// footprint of record l, F(g) = foot[pair[l]] + t_g, goes to boxes_out[4 l ..].
+// footprint of record l, F(g) = foot[pair[l]] + t_g, goes to boxes_out[4 l ..].  matched_out (or null): the k floats
+// k_matched_list left at o_frac, of which the first *n_out are the records' fractions.
 void detect_records(fdcm_featuremap* fm, const BestRun& R, const Pairs& P, bool rotated, int n, const fdcm_grid& g, int k, int32_t base,
-                    fdcm_match** out, int64_t* n_out, const Foot* foot, int32_t* boxes_out) {
+                    fdcm_match** out, int64_t* n_out, const Foot* foot, int32_t* boxes_out, float* matched_out = nullptr) {
     hipStream_t st = fm->stream;
     std::vector<unsigned long long> best((size_t)k);
     std::vector<int32_t> pair((size_t)k);
     FDCM_HIP(hipMemcpyAsync(best.data(), R.d + R.o_best, (size_t)k * 8, hipMemcpyDeviceToHost, st));
     FDCM_HIP(hipMemcpyAsync(pair.data(), R.d + R.o_pair, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    if (matched_out) FDCM_HIP(hipMemcpyAsync(matched_out, R.d + R.o_frac, (size_t)k * 4, hipMemcpyDeviceToHost, st));
     FDCM_HIP(hipStreamSynchronize(st));
     int64_t cnt = 0;
     while (cnt < k && best[(size_t)cnt] != kNoKey) ++cnt;
@@ -1757,9 +1873,21 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
 // a short list costs one batch and no round costs a host round trip.
 constexpr int kNmsBatch = 64;
 
-void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
-                                      float max_score, int max_det, int permille, int margin, int penalty, float tau, int32_t base,
-                                      fdcm_match** out, int64_t* n_out, int32_t* boxes_out) {
+// TL_t (include/fdcm.h, "Detections by matched fraction"): the float32 sum of the template's line lengths in line order, from +0.
+void templates_matched_totals(const fdcm_templates* t, float* totals) {
+    for (int64_t i = 0; i < t->T; ++i) {
+        float tl = 0.f;
+        for (int64_t q = t->offsets[(size_t)i]; q < t->offsets[(size_t)i + 1]; ++q) tl = tl + t->lengths[(size_t)q];
+        totals[i] = tl;
+    }
+}
+
+// Both detection calls with a threshold.  matched: the call by matched fraction (include/fdcm.h), the other's own work plus,
+// with min_matched > 0, the gate pass over the key plane before the first round and, with matched_out, the fractions of the
+// result list after the last; min_matched = 0 and no matched_out queue what the other call queues.
+static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, float max_score,
+                       int max_det, int permille, int margin, int penalty, float tau, bool matched, float min_matched, int32_t base,
+                       fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
     check_grid(g);
     *n_out = 0;
     if (t->T == 0) return;
@@ -1767,16 +1895,42 @@ void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates*
     begin(fm);
     const int n = rot ? rot->n : 1;
     if (rot) check_rotated_size(t, n);
+    const bool gate = matched && min_matched > 0.f, fracs = matched && matched_out != nullptr;
     Pairs P;
-    prepare_pairs(fm, t, rot, false, P);
+    P.lens = gate || fracs;
+    prepare_pairs(fm, t, rot, matched && test_switches().matched_flat, P);
     std::vector<Foot> foot(P.nl.size());
     for (size_t u = 0; u < foot.size(); ++u)
         foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    // per pair: need = float32(min_matched * TL) of its template, and TL
+    std::vector<float> need, tl;
+    if (P.lens) {
+        std::vector<float> totals((size_t)t->T);
+        templates_matched_totals(t, totals.data());
+        tl.resize(P.nl.size());
+        for (size_t u = 0; u < tl.size(); ++u) tl[u] = totals[u / (size_t)n];
+        if (gate) {
+            need.resize(tl.size());
+            for (size_t u = 0; u < tl.size(); ++u) need[u] = min_matched * tl[u];
+        }
+    }
+    const MatchedIn mt{gate ? need.data() : nullptr, fracs ? tl.data() : nullptr};
     BestRun R;
     // (+inf is no threshold: the plane is the best map's own, by the kernel without the checks)
-    if (!best_keys(fm, P, t, n, g, penalty, tau, 0, R, &foot, max_det, max_score < f_inf() ? &max_score : nullptr)) return;
+    if (!best_keys(fm, P, t, n, g, penalty, tau, 0, R, &foot, max_det, max_score < f_inf() ? &max_score : nullptr,
+                   P.lens ? &mt : nullptr))
+        return;
     hipStream_t st = fm->stream;
     char* d = R.d;
+    const float* vol = fm->vol.as<float>();
+    if (gate) {
+        auto kern = P.buf32 ? k_matched_gate<true> : k_matched_gate<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(R.n_keys / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
+                           fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
+                           (const float*)(d + R.o_need), (unsigned long long*)(d + R.o_keys), (long long)R.n_keys, g.x0, g.y0, g.sx, g.sy,
+                           R.tiles_x);
+        FDCM_HIP(hipGetLastError());
+    }
     unsigned long long* pk = (unsigned long long*)(d + R.o_cand);
     int* pp = (int*)(d + R.o_cand + 2 * kNmsWorkgroups * 8);
     unsigned long long* d_best = (unsigned long long*)(d + R.o_best);
@@ -1798,7 +1952,29 @@ void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates*
         FDCM_HIP(hipStreamSynchronize(st));
         if (last == kNoKey) break;  // the list has ended: the entries from there on are kNoKey (written, or the upload's)
     }
-    detect_records(fm, R, P, rot != nullptr, n, g, max_det, base, out, n_out, foot.data(), boxes_out);
+    if (fracs) {
+        auto kern = P.buf32 ? k_matched_list<true> : k_matched_list<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((max_det + 255) / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+                           fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
+                           (const float*)(d + R.o_tl), (const unsigned long long*)d_best, (const int*)(d + R.o_pair), max_det, g.x0, g.y0,
+                           g.sx, g.sy, g.nx, (float*)(d + R.o_frac));
+        FDCM_HIP(hipGetLastError());
+    }
+    detect_records(fm, R, P, rot != nullptr, n, g, max_det, base, out, n_out, foot.data(), boxes_out, fracs ? matched_out : nullptr);
+}
+
+void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
+                                      float max_score, int max_det, int permille, int margin, int penalty, float tau, int32_t base,
+                                      fdcm_match** out, int64_t* n_out, int32_t* boxes_out) {
+    detect_all(fm, t, rot, g, max_score, max_det, permille, margin, penalty, tau, false, 0.f, base, out, n_out, boxes_out, nullptr);
+}
+
+void run_search_exhaustive_detect_all_matched(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
+                                              float max_score, int max_det, int permille, int margin, int penalty, float tau,
+                                              float min_matched, int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out,
+                                              float* matched_out) {
+    detect_all(fm, t, rot, g, max_score, max_det, permille, margin, penalty, tau, true, min_matched, base, out, n_out, boxes_out,
+               matched_out);
 }
 
 float detect_score_bound(float den, float max_score) { return score_bound(den, max_score); }
@@ -1934,6 +2110,55 @@ void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rot
                            fm->tx, fm->ty, (const ExLine*)d, (const CostPose*)(d + o_tab), (int)tab.size(), (float*)(d + o_out));
         FDCM_HIP(hipGetLastError());
         FDCM_HIP(hipMemcpyAsync(*costs + offsets[q0], d + o_out, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here; the next round reuses the staging)
+    }
+}
+
+// Matched fractions (include/fdcm.h, "Detections by matched fraction"): the arguments are checked (fdcm_capi.cpp).  The rounds,
+// the pairs and admissibility are run_line_costs'; a round uploads lines, lengths and poses in one copy, runs
+// k_matched_fractions and downloads a float per pose.
+void run_matched_fractions(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                           float* fractions) {
+    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int nr = rot ? rot->n : 1;
+    const float* vol = fm->vol.as<float>();
+    hipStream_t st = fm->stream;
+    std::vector<float> totals((size_t)t->T);
+    templates_matched_totals(t, totals.data());
+    for (int64_t q0 = 0; q0 < n; q0 += kCostPoses) {
+        const int64_t q1 = std::min(n, q0 + kCostPoses);
+        Pairs W;
+        W.lens = true;
+        for (int64_t q = q0; q < q1; ++q) W.key.push_back((int64_t)poses[4 * q] * nr + poses[4 * q + 1]);
+        std::sort(W.key.begin(), W.key.end());
+        W.key.erase(std::unique(W.key.begin(), W.key.end()), W.key.end());
+        prepare_pairs(fm, t, rot, test_switches().matched_flat, W);
+        std::vector<FracPose> tab((size_t)(q1 - q0));
+        for (int64_t q = q0; q < q1; ++q) {
+            const int32_t* p = poses + 4 * q;
+            const size_t u = W.find((int64_t)p[0] * nr + p[1]);
+            const Box& b = W.box[u];
+            const bool adm = b.any && p[2] >= b.x0 && p[2] <= b.x1 && p[3] >= b.y0 && p[3] <= b.y1;
+            tab[(size_t)(q - q0)] = FracPose{W.line0[u], W.nl[u], p[2], p[3], totals[(size_t)p[0]], adm ? 1 : 0};
+        }
+        const size_t o_len = al256(W.lines.size() * sizeof(ExLine)), o_tab = o_len + al256(W.len.size() * sizeof(float)),
+                     o_out = o_tab + al256(tab.size() * sizeof(FracPose));
+        fm->search.eval.reserve(o_out + al256(tab.size() * sizeof(float)));
+        fm->search.eval_stage.reserve(o_out);
+        char* d = (char*)fm->search.eval.p;
+        char* h = (char*)fm->search.eval_stage.p;
+        std::memcpy(h, W.lines.data(), W.lines.size() * sizeof(ExLine));
+        std::memcpy(h + o_len, W.len.data(), W.len.size() * sizeof(float));
+        std::memcpy(h + o_tab, tab.data(), tab.size() * sizeof(FracPose));
+        FDCM_HIP(hipMemcpyAsync(d, h, o_out, hipMemcpyHostToDevice, st));
+        auto kern = W.buf32 ? k_matched_fractions<true> : k_matched_fractions<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((tab.size() + 255) / 256)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W,
+                           (int)fm->H, fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + o_len), (const FracPose*)(d + o_tab),
+                           (int)tab.size(), (float*)(d + o_out));
+        FDCM_HIP(hipGetLastError());
+        FDCM_HIP(hipMemcpyAsync(fractions + q0, d + o_out, tab.size() * sizeof(float), hipMemcpyDeviceToHost, st));
         FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here; the next round reuses the staging)
     }
 }

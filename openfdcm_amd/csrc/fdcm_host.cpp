@@ -34,6 +34,7 @@ const TestSwitches& test_switches() {
         r.search_compact2 = set("FDCM_SEARCH_COMPACT2");
         r.windows_batch = std::max(0, num("FDCM_WINDOWS_BATCH", 0));
         r.windows_flat = set("FDCM_WINDOWS_FLAT");
+        r.matched_flat = set("FDCM_MATCHED_FLAT");
         return r;
     }();
     return s;

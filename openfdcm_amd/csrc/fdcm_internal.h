@@ -38,6 +38,7 @@ struct HipError { hipError_t code; const char* what; int line; };
 //   FDCM_WINDOWS_BATCH=1..     planes a batch of the pose-window search holds at most, instead of 65536 (windows_round),
 //                              and 4 KB of tables per such plane a round, instead of 256 MB (run_search_exhaustive_windows)
 //   FDCM_WINDOWS_FLAT          the pose-window search with 64-bit flat addresses (windows_round)
+//   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (detect_all, run_matched_fractions)
 struct TestSwitches {
     bool literal_sweep, sweep_order;
     int sweep_min_cols;  // 16 unless forced
@@ -45,7 +46,7 @@ struct TestSwitches {
     int int_xc;          // 0: not forced
     bool host_bins, search_flat, search_compact2;
     int windows_batch;  // 0: not forced
-    bool windows_flat;
+    bool windows_flat, matched_flat;
 };
 const TestSwitches& test_switches();
 
@@ -359,6 +360,15 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
 void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                       float max_score, int max_det, int permille, int margin, int penalty, float tau, int32_t base,
                                       fdcm_match** out, int64_t* n_out, int32_t* boxes_out);
+// detect_all with the gate by matched fraction; matched_out: max_det floats, or null
+void run_search_exhaustive_detect_all_matched(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
+                                              float max_score, int max_det, int permille, int margin, int penalty, float tau,
+                                              float min_matched, int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out,
+                                              float* matched_out);
+// poses as run_line_costs'; fractions: n floats
+void run_matched_fractions(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                           float* fractions);
+void templates_matched_totals(const fdcm_templates* t, float* totals);  // host only: TL per template
 // host only: per template the largest sum whose normalised score is <= max_score
 void detect_score_bounds(const fdcm_templates* t, int penalty, float tau, float max_score, float* bounds);
 float detect_score_bound(float den, float max_score);  // the same for one denominator

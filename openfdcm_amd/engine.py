@@ -408,20 +408,47 @@ class DeviceFeatureMap:
         return (rec, fp[:n.value].copy()) if boxes else rec
 
     def exhaustive_detect_all(self, templates, grid, cs=None, pivots=None, max_score=float("inf"), max_detections=1024,
-                              overlap_permille=300, margin=0, penalty=None, tau=1.0, tmpl_index_base=0, boxes=False):
+                              overlap_permille=300, margin=0, penalty=None, tau=1.0, tmpl_index_base=0, boxes=False,
+                              min_matched=None, matched=False):
         """All detections below a score (include/fdcm.h): exhaustive_detect_nms' greedy rule on the points whose normalised
         score is at most max_score, until they run out or max_detections (1 to 4096) is reached.  Raw match records in
-        ascending order; with boxes also the (n, 4) int32 footprints."""
+        ascending order; with boxes also the (n, 4) int32 footprints.  min_matched (0 to 1) or matched: the call by matched
+        fraction (include/fdcm.h, "Detections by matched fraction"): points whose best pair has less than min_matched of its
+        line length matched are dropped before the greedy rule, and with matched the (n,) float32 fractions of the records
+        come last in the returned tuple."""
         rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
         g = as_grid(grid)
         out, n = C.c_void_p(), C.c_int64()
-        fp = np.zeros((int(max_detections) if 1 <= int(max_detections) <= 4096 else 0, 4), dtype=np.int32)
-        capi.check(capi.lib().fdcm_search_exhaustive_detect_all(
+        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0
+        fp = np.zeros((md, 4), dtype=np.int32)
+        fp_arg = fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and fp.size else None
+        if min_matched is None and not matched:
+            capi.check(capi.lib().fdcm_search_exhaustive_detect_all(
+                self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), float(max_score), int(max_detections),
+                int(overlap_permille), int(margin), -1 if penalty is None else int(penalty), float(tau), int(tmpl_index_base),
+                C.byref(out), C.byref(n), fp_arg))
+            rec = _adopt_matches(out, n.value)
+            return (rec, fp[:n.value].copy()) if boxes else rec
+        fr = np.zeros(md, dtype=np.float32)
+        capi.check(capi.lib().fdcm_search_exhaustive_detect_all_matched(
             self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), float(max_score), int(max_detections),
-            int(overlap_permille), int(margin), -1 if penalty is None else int(penalty), float(tau), int(tmpl_index_base),
-            C.byref(out), C.byref(n), fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and fp.size else None))
-        rec = _adopt_matches(out, n.value)
-        return (rec, fp[:n.value].copy()) if boxes else rec
+            int(overlap_permille), int(margin), -1 if penalty is None else int(penalty), float(tau),
+            0.0 if min_matched is None else float(min_matched), int(tmpl_index_base), C.byref(out), C.byref(n), fp_arg,
+            capi.fptr(fr) if matched and fr.size else None))
+        res = (_adopt_matches(out, n.value),) + ((fp[:n.value].copy(),) if boxes else ()) + ((fr[:n.value].copy(),) if matched else ())
+        return res if len(res) > 1 else res[0]
+
+    def matched_fractions(self, templates, poses, cs=None, pivots=None):
+        """Matched fractions (include/fdcm.h, "Detections by matched fraction"): per pose (tmpl, a, x, y), as line_costs takes
+        them, the float32 share of the template's line length whose lines cost at most their caps there; 1 for a template
+        whose lengths sum to 0, NaN for a pose that is not admissible.  (n,) float32."""
+        poses = as_poses(poses)
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        out = np.zeros(poses.shape[0], dtype=np.float32)
+        capi.check(capi.lib().fdcm_matched_fractions(self._h, templates._h, C.byref(rot) if rot is not None else None,
+                                                     poses.ctypes.data_as(C.POINTER(C.c_int32)), poses.shape[0],
+                                                     capi.fptr(out) if out.size else None))
+        return out
 
     def line_costs(self, templates, poses, cs=None, pivots=None):
         """Line costs (include/fdcm.h, "Per-line caps and line costs"): poses (n, 4) int32 rows (tmpl, a, x, y), a an index
@@ -540,6 +567,13 @@ class DeviceTemplates:
         out = np.zeros((self.count, n, 4), dtype=np.int32)
         capi.check(capi.lib().fdcm_templates_footprints(self._h, C.byref(rot) if rot is not None else None, int(margin),
                                                         out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def matched_totals(self):
+        """Per template the float32 sum of its line lengths in line order (fdcm_templates_matched_totals): the denominator
+        of the matched fraction.  Host only."""
+        out = np.zeros(self.count, dtype=np.float32)
+        capi.check(capi.lib().fdcm_templates_matched_totals(self._h, capi.fptr(out) if out.size else None))
         return out
 
     def score_bounds(self, max_score, penalty=None, tau=1.0):

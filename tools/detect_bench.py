@@ -21,11 +21,18 @@ radius 8, ExponentialPenalty(1.5).  In the same run, on the same grid:
                 +inf and the 50 %, 5 % and 0.5 % quantiles of the finite scores of fdcm_best_map on that grid, each compared
                 with the leading records of the +inf list; and once max_detections = 4096 at overlap 1000, the most rounds
 
+  matched       (--matched, on its own) "Detections by matched fraction": per stride fdcm_search_exhaustive_detect_all at
+                max_detections = 64, the yardstick, which a build from before the new call has too, at max_score = +inf and the
+                5 % quantile of fdcm_best_map's finite scores; then, where the library has it, the call by matched fraction at
+                min_matched 0.5 and 0.9, at 0.5 with the fractions returned, without a gate with the fractions returned, and at
+                the median of those fractions; and once per run fdcm_matched_fractions beside
+                fdcm_line_costs on the poses of 64 and of 8000 grid points.  Meant with --line-caps.
+
 Each device figure is the median of --reps blocking calls after a warm-up; the host composition runs --host-reps times.
 --line-caps TAU gives every template line the cap TAU * its length (include/fdcm.h, "Per-line caps and line costs") in every
 call of the run, the host composition's score map included.  Off by default.
 
-    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--line-caps TAU] [--nms | --all] [--json out.json]
+    python tools/detect_bench.py [--reps 5] [--host-reps 1] [--strides 1,2,4] [--line-caps TAU] [--nms | --all | --matched] [--json out.json]
 """
 import argparse
 import json
@@ -116,6 +123,54 @@ def all_mode(args, dev, tset, pen, tau, timed, spread):
     return rows
 
 
+def matched_mode(args, dev, tset, pen, tau, timed, spread):
+    """The rows of --matched."""
+    pm = int(round(1000 * args.overlap))
+    has = hasattr(dev, "matched_fractions")
+    rows = []
+    for s in [int(v) for v in args.strides.split(",")]:
+        grid = dev.exhaustive_window(tset, s, s).as_tuple()
+        scores, pairs = dev.best_map(tset, grid, penalty=pen, tau=tau)
+        fin = np.sort(scores[np.isfinite(scores)])
+        row = {"stride": s, "grid": list(grid), "grid_points": grid[2] * grid[3], "overlap_permille": pm}
+        for name, ms in [("inf", float("inf")), ("q5", float(fin[min(len(fin) - 1, int(0.05 * len(fin)))]))]:
+            cases = [("off", {})]
+            if has:  # ("median": the median of the fractions the ungated list comes with, so that about half of it passes)
+                cases += [("0.5", {"min_matched": 0.5}), ("0.9", {"min_matched": 0.9}), ("0.5_fractions", {"min_matched": 0.5, "matched": True}),
+                          ("off_fractions", {"matched": True}), ("median", None)]
+            for what, kw in cases:
+                if kw is None:
+                    kw = {"min_matched": float(np.median(out[1])) if len(out[1]) else 0.0, "matched": True}
+                    row[f"{name}_median_min_matched"] = kw["min_matched"]
+                call = lambda: dev.exhaustive_detect_all(tset, grid, max_score=ms, max_detections=64, overlap_permille=pm, penalty=pen,
+                                                         tau=tau, **kw)
+                c_ms, c_min, out = timed(call)
+                rec = out[0] if isinstance(out, tuple) else out
+                row[f"{name}_{what}"] = {"max_score": ms, "ms": round(c_ms, 3), "ms_min": round(c_min, 3), "ms_spread": round(spread[-1], 3),
+                                         "detections": int(len(rec))}
+                if isinstance(out, tuple):
+                    row[f"{name}_{what}"]["fractions_min_median_max"] = [round(float(v), 4) for v in
+                                                                         (out[1].min(), np.median(out[1]), out[1].max())] if len(rec) else []
+                print(f"stride {s}: max_score {name} = {ms:.6g}, min_matched {what}: {c_ms:.2f} ms (min {c_min:.2f}, spread "
+                      f"{spread[-1]:.2f}); {len(rec)} detections", flush=True)
+        if has and s == 1:  # the pose calls, on points that have a candidate
+            cand = np.flatnonzero(pairs.reshape(-1) >= 0)
+            for n in (64, 8000):
+                g = cand[np.linspace(0, len(cand) - 1, n).astype(np.int64)]
+                poses = np.stack([pairs.reshape(-1)[g], np.zeros(n, dtype=np.int64), grid[0] + (g % grid[2]) * s, grid[1] + (g // grid[2]) * s],
+                                 axis=1).astype(np.int32)
+                f_ms, f_min, fr = timed(lambda: dev.matched_fractions(tset, poses))
+                f_spread = spread[-1]
+                l_ms, l_min, _ = timed(lambda: dev.line_costs(tset, poses))
+                row[f"poses_{n}"] = {"matched_fractions_ms": round(f_ms, 3), "matched_fractions_ms_min": round(f_min, 3),
+                                     "matched_fractions_ms_spread": round(f_spread, 3), "line_costs_ms": round(l_ms, 3),
+                                     "line_costs_ms_min": round(l_min, 3), "fraction_median": round(float(np.median(fr)), 4)}
+                print(f"stride {s}: {n} poses: matched_fractions {f_ms:.3f} ms (min {f_min:.3f}), line_costs {l_ms:.3f} ms (min {l_min:.3f})",
+                      flush=True)
+        rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=5)
@@ -127,7 +182,8 @@ def main():
     ap.add_argument("--line-caps", type=float, default=None, metavar="TAU", help="cap every line's cost at TAU * its length")
     ap.add_argument("--nms", action="store_true", help="also time the detections suppressed by footprint overlap")
     ap.add_argument("--all", action="store_true", help="time all detections below a score, against nms at k = 64 (only)")
-    ap.add_argument("--overlap", type=float, default=0.3, help="the overlap threshold of --nms and --all")
+    ap.add_argument("--matched", action="store_true", help="time the detections by matched fraction, against --all's call (only)")
+    ap.add_argument("--overlap", type=float, default=0.3, help="the overlap threshold of --nms, --all and --matched")
     ap.add_argument("--json", default=None, help="also write the results here")
     args = ap.parse_args()
 
@@ -153,7 +209,9 @@ def main():
     rows, spread = [], []  # spread: max - min of the last timed() call's repetitions
     if args.all:
         rows = all_mode(args, dev, tset, pen, tau, timed, spread)
-    for s in [] if args.all else [int(v) for v in args.strides.split(",")]:
+    if args.matched:
+        rows = matched_mode(args, dev, tset, pen, tau, timed, spread)
+    for s in [] if args.all or args.matched else [int(v) for v in args.strides.split(",")]:
         grid = dev.exhaustive_window(tset, s, s).as_tuple()
         det_ms, det_min, recs = timed(lambda: dev.exhaustive_detect(tset, grid, k=k, rx=r, ry=r, penalty=pen, tau=tau))
         det_spread = spread[-1]
