@@ -846,6 +846,10 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
     fm->pixel_seeded = plan.seeds.kind != SeedKind::lines;
     fm->last_build = fdcm_build_timing{}; fm->built.reset(); fm->holds = VolStage::none;
     if (L.empty) return;
+    // FDCM_POISON (fdcm_internal.h, "the tests' switches"): the whole allocation of the volume, the columns and the rows of
+    // padding included, holds the word before the first stage writes; what the search reads afterwards the build has written
+    if (test_switches().poison && fm->vol.cap >= 4)
+        FDCM_HIP(hipMemsetD32Async((hipDeviceptr_t)fm->vol.p, (int)test_switches().poison_word, fm->vol.cap / 4, fm->stream));
     SweepBuf sb{};
     std::vector<int32_t> proxy_cost;  // (stays empty unless the sweep's launch order takes it)
     bool device_proxy = false;        // the launch order's costs are counted by pass 1

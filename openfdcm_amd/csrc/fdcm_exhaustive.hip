@@ -1283,8 +1283,7 @@ void search(fdcm_featuremap* fm, const Pairs& P, int n, const fdcm_grid& g, int 
                  o_seg = o_dec + al256(bdec.size() * sizeof(int4)), o_best = o_seg + al256(bseg.size() * sizeof(int4)),
                  o_map = o_best + al256((size_t)TA * k * 8),
                  o_cand = o_map + (topk ? 0 : al256(max_planes * plane_max * sizeof(float))), total = o_cand + al256(max_cand * k * 8);
-    fm->search.eval.reserve(total);
-    fm->search.eval_stage.reserve(o_map);
+    reserve_eval(fm, total, o_map);
     char* d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
     std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
@@ -1448,8 +1447,7 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
     R.o_keys = R.o_frac + (mt ? al256((size_t)list * 4) : 0);
     R.o_plane = R.o_keys + al256(n_keys * 8);
     R.o_cand = R.o_plane + al256((size_t)g.nx * g.ny * 4);
-    fm->search.eval.reserve(R.o_cand + (foot ? kNmsPartialBytes : k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0));
-    fm->search.eval_stage.reserve(R.o_pair);
+    reserve_eval(fm, R.o_cand + (foot ? kNmsPartialBytes : k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0), R.o_pair);
     char* d = R.d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
     std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
@@ -1627,8 +1625,7 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
                  o_jt = o_it + al256(items.size() * sizeof(int2)), o_seg = o_jt + al256(jtab.size() * sizeof(WinJob)),
                  o_best = o_seg + al256(seg.size() * sizeof(int4)), o_cand = o_best + al256(nj * k * 8),
                  total = o_cand + al256(max_lists * k * 8);
-    fm->search.eval.reserve(total);
-    fm->search.eval_stage.reserve(o_cand);
+    reserve_eval(fm, total, o_cand);
     char* d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
     std::memcpy(h, W.lines.data(), W.lines.size() * sizeof(ExLine));
@@ -1691,7 +1688,7 @@ void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     std::lock_guard<std::mutex> turn(fm->seam_mutex);  // concurrent callers of one feature map take turns (shared search.eval)
     begin(fm);
     Pairs P;
-    prepare_pairs(fm, t, rot, false, P);
+    prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, P);
     const int64_t T = (int64_t)P.nl.size();
     const size_t plane_bytes = (size_t)g.nx * g.ny * sizeof(float);
     // host output: templates in batches whose maps fit a 256 MB workspace; device output: one launch
@@ -1699,7 +1696,7 @@ void run_score_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     std::vector<ExTmpl> tm((size_t)T);
     for (int64_t i = 0; i < T; ++i) tm[(size_t)i] = grid_tmpl(P, (size_t)i, g, (int)(out_device ? i : i % batch));
     const size_t o_lines = 0, o_tm = al256(P.lines.size() * sizeof(ExLine)), o_map = o_tm + al256(tm.size() * sizeof(ExTmpl));
-    fm->search.eval.reserve(o_map + (out_device ? 0 : (size_t)batch * plane_bytes));
+    reserve_eval(fm, o_map + (out_device ? 0 : (size_t)batch * plane_bytes), 0);
     char* d = (char*)fm->search.eval.p;
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d + o_lines, P.lines.data(), P.lines.size() * sizeof(ExLine), hipMemcpyHostToDevice, st));
@@ -1732,7 +1729,7 @@ void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, c
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
     begin(fm);
     Pairs P;
-    prepare_pairs(fm, t, nullptr, false, P);
+    prepare_pairs(fm, t, nullptr, test_switches().exhaustive_flat, P);
     std::vector<unsigned long long> best;
     std::vector<int32_t> index;
     search(fm, P, 1, g, k, rx, ry, 0, 0, best, index);
@@ -1754,7 +1751,7 @@ void run_best_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotat
     begin(fm);
     if (rot) check_rotated_size(t, rot->n);
     Pairs P;
-    prepare_pairs(fm, t, rot, false, P);
+    prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, P);
     BestRun R;
     if (!best_keys(fm, P, t, rot ? rot->n : 1, g, penalty, tau, 0, R)) return none();
     hipStream_t st = fm->stream;
@@ -1780,7 +1777,7 @@ void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, 
     const int n = rot ? rot->n : 1;
     if (rot) check_rotated_size(t, n);
     Pairs P;
-    prepare_pairs(fm, t, rot, false, P);
+    prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, P);
     BestRun R;
     if (!best_keys(fm, P, t, n, g, penalty, tau, k, R)) return;
     hipStream_t st = fm->stream;
@@ -1843,7 +1840,7 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
     const int n = rot ? rot->n : 1;
     if (rot) check_rotated_size(t, n);
     Pairs P;
-    prepare_pairs(fm, t, rot, false, P);
+    prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, P);
     // the footprints, from the lines the kernels score (a pair without a grid point is never read)
     std::vector<Foot> foot(P.nl.size());
     for (size_t u = 0; u < foot.size(); ++u)
@@ -1898,7 +1895,7 @@ static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
     const bool gate = matched && min_matched > 0.f, fracs = matched && matched_out != nullptr;
     Pairs P;
     P.lens = gate || fracs;
-    prepare_pairs(fm, t, rot, matched && test_switches().matched_flat, P);
+    prepare_pairs(fm, t, rot, matched ? test_switches().matched_flat : test_switches().exhaustive_flat, P);
     std::vector<Foot> foot(P.nl.size());
     for (size_t u = 0; u < foot.size(); ++u)
         foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
@@ -2012,7 +2009,7 @@ void run_search_exhaustive_rotations(fdcm_featuremap* fm, const fdcm_templates* 
     begin(fm);
     check_rotated_size(t, n);
     Pairs P;
-    prepare_pairs(fm, t, &rot, false, P);
+    prepare_pairs(fm, t, &rot, test_switches().exhaustive_flat, P);
     std::vector<unsigned long long> best;
     std::vector<int32_t> index;
     search(fm, P, n, g, k, rx, ry, ra, wrap, best, index);
@@ -2088,7 +2085,7 @@ void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rot
         for (int64_t q = q0; q < q1; ++q) W.key.push_back((int64_t)poses[4 * q] * nr + poses[4 * q + 1]);
         std::sort(W.key.begin(), W.key.end());
         W.key.erase(std::unique(W.key.begin(), W.key.end()), W.key.end());
-        prepare_pairs(fm, t, rot, false, W);
+        prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, W);
         std::vector<CostPose> tab((size_t)(q1 - q0));
         for (int64_t q = q0; q < q1; ++q) {
             const int32_t* p = poses + 4 * q;
@@ -2098,8 +2095,7 @@ void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rot
             tab[(size_t)(q - q0)] = CostPose{W.line0[u], W.nl[u], p[2], p[3], (long long)(offsets[q] - offsets[q0]), adm ? 1 : 0, 0};
         }
         const size_t o_tab = al256(W.lines.size() * sizeof(ExLine)), o_out = o_tab + al256(tab.size() * sizeof(CostPose));
-        fm->search.eval.reserve(o_out + al256((size_t)floats * sizeof(float)));
-        fm->search.eval_stage.reserve(o_out);
+        reserve_eval(fm, o_out + al256((size_t)floats * sizeof(float)), o_out);
         char* d = (char*)fm->search.eval.p;
         char* h = (char*)fm->search.eval_stage.p;
         std::memcpy(h, W.lines.data(), W.lines.size() * sizeof(ExLine));
@@ -2145,8 +2141,7 @@ void run_matched_fractions(fdcm_featuremap* fm, const fdcm_templates* t, const f
         }
         const size_t o_len = al256(W.lines.size() * sizeof(ExLine)), o_tab = o_len + al256(W.len.size() * sizeof(float)),
                      o_out = o_tab + al256(tab.size() * sizeof(FracPose));
-        fm->search.eval.reserve(o_out + al256(tab.size() * sizeof(float)));
-        fm->search.eval_stage.reserve(o_out);
+        reserve_eval(fm, o_out + al256(tab.size() * sizeof(float)), o_out);
         char* d = (char*)fm->search.eval.p;
         char* h = (char*)fm->search.eval_stage.p;
         std::memcpy(h, W.lines.data(), W.lines.size() * sizeof(ExLine));

@@ -2,6 +2,8 @@
 // the scene bounding box, line classification and Cohen-Sutherland clipping.  O(scene lines)
 // work; the O(volume) work is in fdcm_build.hip.
 #include <algorithm>
+#include <cctype>
+#include <cerrno>
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -35,6 +37,19 @@ const TestSwitches& test_switches() {
         r.windows_batch = std::max(0, num("FDCM_WINDOWS_BATCH", 0));
         r.windows_flat = set("FDCM_WINDOWS_FLAT");
         r.matched_flat = set("FDCM_MATCHED_FLAT");
+        r.exhaustive_flat = set("FDCM_EXHAUSTIVE_FLAT");
+        r.poison = false;
+        r.poison_word = 0;
+        if (const char* e = getenv("FDCM_POISON")) {  // a uint32, decimal or 0x-hex, and nothing after it
+            char* end = nullptr;
+            errno = 0;
+            const bool hex = e[0] == '0' && (e[1] == 'x' || e[1] == 'X');
+            const unsigned long long v = std::strtoull(e, &end, hex ? 16 : 10);
+            if (std::isxdigit((unsigned char)e[hex ? 2 : 0]) && *end == 0 && errno == 0 && v <= 0xffffffffull) {
+                r.poison = true;
+                r.poison_word = (uint32_t)v;
+            }
+        }
         return r;
     }();
     return s;
@@ -72,6 +87,19 @@ void PinnedBuf::release() {
     if (p) (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
+}
+
+void reserve_eval(fdcm_featuremap* fm, size_t device_bytes, size_t stage_bytes) {
+    SearchBuffers& s = fm->search;
+    s.eval.reserve(device_bytes);
+    if (stage_bytes) s.eval_stage.reserve(stage_bytes);
+    const TestSwitches& sw = test_switches();
+    if (!sw.poison) return;
+    // the whole capacity of both, not this call's share: what an earlier, larger call left behind is part of the question
+    FDCM_HIP(hipStreamSynchronize(fm->stream));  // (nothing queued still reads the staging)
+    if (s.eval.cap >= 4) FDCM_HIP(hipMemsetD32Async((hipDeviceptr_t)s.eval.p, (int)sw.poison_word, s.eval.cap / 4, fm->stream));
+    uint32_t* h = (uint32_t*)s.eval_stage.p;
+    std::fill(h, h + s.eval_stage.cap / 4, sw.poison_word);
 }
 
 // ---- clipLines with the box [0, W-1] x [0, H-1] (drawing.cpp:29-112, deleteOob = true) ----

@@ -39,6 +39,22 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              and 4 KB of tables per such plane a round, instead of 256 MB (run_search_exhaustive_windows)
 //   FDCM_WINDOWS_FLAT          the pose-window search with 64-bit flat addresses (windows_round)
 //   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (detect_all, run_matched_fractions)
+//   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
+//                              takes that form for a volume of 4 GB or more alone (score maps, top-k, peaks, rotations, best
+//                              map, the detections, line costs); the pose windows and the calls by matched fraction keep
+//                              their own switches
+//   FDCM_POISON=<uint32>       (decimal or 0x-hex) what a call finds in memory it did not write: reserve_eval fills the whole
+//                              capacity of search.eval and of search.eval_stage with the word before the call writes anything,
+//                              and run_build fills the whole allocation of the volume, padding included, ahead of its first
+//                              stage (an adopted volume is not touched).  Nothing else is filled: the build's scratch buffers
+//                              and the reference search's buffers carry documented state from one call to the next (the
+//                              sweep's cost history and steal counter, the line integral's group table, the last search's
+//                              matches) and want a piece of work of their own.  The tests use the words 0 and 1 alone.  1 is
+//                              the smallest denormal as a float (a near-perfect score), 0x0000000100000001 as a 64-bit key
+//                              (below every real key in every min and atomicMin), one too many as a count and in bounds as
+//                              an index: a kernel that reads what nobody wrote reads a wrong value from a valid place.  Words
+//                              that are large as integers (0xFFFFFFFF, NaN patterns) hide a missing "no key" initialisation
+//                              and leave the allocation as an index; they are not for the GPU machines.
 struct TestSwitches {
     bool literal_sweep, sweep_order;
     int sweep_min_cols;  // 16 unless forced
@@ -46,7 +62,9 @@ struct TestSwitches {
     int int_xc;          // 0: not forced
     bool host_bins, search_flat, search_compact2;
     int windows_batch;  // 0: not forced
-    bool windows_flat, matched_flat;
+    bool windows_flat, matched_flat, exhaustive_flat;
+    bool poison;           // FDCM_POISON holds a valid word
+    uint32_t poison_word;
 };
 const TestSwitches& test_switches();
 
@@ -331,6 +349,11 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
 void reserve_search(fdcm_featuremap* fm, const fdcm_templates* t, int64_t n_scene, int64_t maxT, int64_t maxS);
 // the searches of this process take the candidates' orientation bins from the host libm (decided once: see fdcm.h)
 bool orientation_bins_on_host();
+// The one way a call sizes the workspace the seam and the exhaustive calls share (fdcm_host.cpp): search.eval to device_bytes
+// and, where the call stages its upload in pinned memory, search.eval_stage to stage_bytes (0: the call has none).  The
+// caller holds seam_mutex and the handle has its stream.  Under FDCM_POISON it then waits for the stream and fills the whole
+// capacity of both buffers with the word, so the call finds the word wherever it does not write.
+void reserve_eval(fdcm_featuremap* fm, size_t device_bytes, size_t stage_bytes);
 // implemented in fdcm_seam.hip: minmaxTranslation<Dt3Cpu> / evaluate<Dt3Cpu> batched over templates
 void run_minmax(fdcm_featuremap* fm, const float* lines, const int64_t* offsets, int64_t T, const float* align, float* out);
 void run_evaluate(fdcm_featuremap* fm, const float* lines, const int64_t* offsets, int64_t T, const float* translations,

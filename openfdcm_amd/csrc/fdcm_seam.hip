@@ -95,7 +95,7 @@ void run_minmax(fdcm_featuremap* fm, const float* lines, const int64_t* offsets,
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t o_lines = 0, o_off = al((size_t)n_lines * 16), o_al = o_off + al((size_t)(T + 1) * 8), o_out = o_al + al((size_t)T * 8),
                  total = o_out + al((size_t)T * 8);
-    fm->search.eval.reserve(total);
+    reserve_eval(fm, total, 0);
     char* d = (char*)fm->search.eval.p;
     if (n_lines) FDCM_HIP(hipMemcpyAsync(d + o_lines, lines, (size_t)n_lines * 16, hipMemcpyHostToDevice, st));
     FDCM_HIP(hipMemcpyAsync(d + o_off, offsets, (size_t)(T + 1) * 8, hipMemcpyHostToDevice, st));
@@ -142,7 +142,7 @@ void run_evaluate(fdcm_featuremap* fm, const float* lines, const int64_t* offset
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t o_l5 = 0, o_off = al(l5.size() * 4), o_tr = o_off + al((size_t)(T + 1) * 8), o_it = o_tr + al((size_t)n_tr * 8),
                  o_sc = o_it + al(items.size() * sizeof(EvalItem)), total = o_sc + al((size_t)n_tr * 4);
-    fm->search.eval.reserve(total);
+    reserve_eval(fm, total, 0);
     char* d = (char*)fm->search.eval.p;
     if (n_lines) FDCM_HIP(hipMemcpyAsync(d + o_l5, l5.data(), l5.size() * 4, hipMemcpyHostToDevice, st));
     FDCM_HIP(hipMemcpyAsync(d + o_off, offsets, (size_t)(T + 1) * 8, hipMemcpyHostToDevice, st));
