@@ -669,6 +669,56 @@ int fdcm_matched_fractions(const fdcm_featuremap* fm, const fdcm_templates* temp
                            const int32_t* poses /* n x 4: tmpl, a, x, y */, int64_t n, float* fractions /* n */);
 int fdcm_templates_matched_totals(const fdcm_templates* templates, float* totals /* n_templates */);
 
+/* Detections over pose windows: the detector's rule applied to the winners of a job list.  The detector above is a dense
+ * search of one grid and the whole rotation table; the pose windows are the coarse-to-fine and tracking path, but return raw
+ * top-k records per job.  This call joins them: every job is searched as a pose window, its best pose is normalised,
+ * thresholded and gated as a point of the detector is, and the jobs' best poses suppress each other by footprint overlap.
+ * The definitions are this project's (README.md, "Detections over pose windows"; numpy statement:
+ * tests/window_detect_ref.py).  Everything not restated here is taken unchanged from fdcm_search_exhaustive_windows (jobs,
+ * runs, wrap, rot == NULL, admissibility, the score with the set's line caps) and from
+ * fdcm_search_exhaustive_detect_all_matched (q and its denominators, footprints with margin, the overlap test in int64, ML,
+ * TL, need, frac, the record layout).
+ * Inputs: a feature map, templates, rot or NULL, pivots; jobs (fdcm_pose_window, n_jobs), sx, sy, wrap; max_score,
+ * max_detections (1 .. 4096), overlap_permille, margin, penalty, tau, min_matched, tmpl_index_base.
+ * Winner of job j: the admissible (e, g) of the job with the smallest windows key (score bits << 32) | (e N_j + g), exactly
+ * the one record fdcm_search_exhaustive_windows returns for that job at k = 1.  A job whose template has no lines, or that
+ * has no admissible point, has no winner.  For a job with a winner a_j = (a0 + e) mod n is the winner's rotation, t_j its
+ * translation and q_j = score / den(tmpl), one IEEE float32 division with the denominators of fdcm_penalize; penalty = -1
+ * gives q = score.  The winner is chosen on the raw score, before the division.
+ * Candidates S_0: the jobs that have a winner, whose q_j is not NaN, with q_j <= max_score and ML((tmpl, a_j), t_j) >=
+ * need_tmpl.  What the gate looks at: the winner, and only the winner, as the dense call's gate looks at best(g) only.  A
+ * job whose winner fails is dropped, even if another pose of its window would pass: the gate is not part of the minimum
+ * that chooses the winner.
+ * key(j) = (bits of q_j << 32) | j.  Duplicate jobs are distinct candidates; the later one loses the tie and is then
+ * suppressed by the earlier, unless overlap_permille = 1000.  Footprint F(j) = box(tmpl, a_j) + t_j, box as
+ * fdcm_templates_footprints gives it at margin.  The rule is the greedy rule of fdcm_search_exhaustive_detect_nms on S_0 with
+ * these keys and footprints, stopping at max_detections.
+ * Output: the d_n in order, as records {tmpl + tmpl_index_base, q, {c, -s, m.x + t.x, s, c, m.y + t.y}}; with rot == NULL
+ * the transform is {1, 0, t.x, 0, 1, t.y}.  boxes_out (4 max_detections int32, or NULL): F(d_n) per record.  matched_out
+ * (max_detections floats, or NULL): frac of record l, bit for bit fdcm_matched_fractions of the record's (tmpl, a, x, y).
+ * jobs_out (max_detections int32, or NULL): the job each record came from.  The entries from *n_out on are not specified.
+ * Identities: (1) with overlap_permille = 1000, max_score = +inf, min_matched = 0 and max_detections >= the number of
+ * winners the records are the k = 1 records of fdcm_search_exhaustive_windows, passed through fdcm_penalize and ordered by
+ * (score bits, job), byte for byte.  (2) One-point jobs (na = nx = ny = 1) for every keyed point of fdcm_best_map, carrying
+ * that point's best pair, listed by ascending g, give the records, boxes and fractions of
+ * fdcm_search_exhaustive_detect_all_matched on that grid with the same parameters, byte for byte.  (3) At fixed other
+ * parameters the records for any max_score are the leading records with score <= max_score of the +inf list.  (4)
+ * overlap_permille = 0: no two returned boxes share a pixel.  (5) Results are a function of the inputs alone.
+ * FDCM_EINVAL, before any GPU work: everything fdcm_search_exhaustive_windows rejects about jobs, rot, strides and wrap;
+ * everything fdcm_search_exhaustive_detect_all_matched rejects about max_score, max_detections, overlap_permille, margin,
+ * penalty, tau and min_matched; n_jobs > 2^22 (the winners' list is 24 bytes per job and is not cut into parts); NULL out
+ * or n_out.  No jobs, an empty feature map or an empty template list give zero records and FDCM_OK.  The call blocks;
+ * concurrent callers of one feature map take turns.  Device memory stays below 1 GB: the scoring goes through the job list
+ * in parts, as fdcm_search_exhaustive_windows does.  Release the records with fdcm_matches_free. */
+int fdcm_search_exhaustive_detect_windows(const fdcm_featuremap* fm, const fdcm_templates* templates,
+                                          const fdcm_rotations* rot /* or NULL */, const fdcm_pose_window* jobs, int64_t n_jobs,
+                                          int32_t sx, int32_t sy, int32_t wrap, float max_score, int32_t max_detections,
+                                          int32_t overlap_permille, int32_t margin, int penalty, float tau, float min_matched,
+                                          int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                          int32_t* boxes_out /* 4 max_detections, or NULL */,
+                                          float* matched_out /* max_detections, or NULL */,
+                                          int32_t* jobs_out /* max_detections, or NULL */);
+
 /* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
  *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as
  *      fdcm_edge_labels makes it (m = the distinct keys of `depth`, a byte < m an edge pixel of that label, labels circular)

@@ -809,6 +809,64 @@ def pose_windows(records, coarse_angles, fine_angles, pivots, half_angles, half_
     return jobs
 
 
+def exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=0.3, angles=None, stride=1, max_detections=1024,
+                              penalty=None, pivot="center", wrap=False, line_caps=None, margin=0, min_matched=None,
+                              return_boxes=False, return_matched=False, return_jobs=False):
+    """exhaustive_detect_all over a job list in place of a dense grid: coarse-to-fine detection and tracking in one call.
+    jobs are exhaustive_window_search's (n, 7) rows (tmpl, a0, na, x0, y0, nx, ny).  Each job gives its best pose, exactly
+    its record of exhaustive_window_search(k=1); the score is divided as penalize(penalty, ...) divides it; a job stays when
+    that score is <= max_score (>= 0 or inf) and, with min_matched (0 to 1), when the lines of its best pose that cost at
+    most their caps make up at least that share of the template's line length (only the best pose of a job is looked at).
+    The jobs left go through exhaustive_detect_nms' greedy rule in the order (score, job index): a job's footprint is its
+    template's box under its best pose's angle, widened by margin, at its best pose's translation, and a detection drops
+    every job whose footprint overlaps its own by more than `overlap`; at most max_detections (1 to 4096).  Several jobs
+    around one object (neighbouring views in a tracker, overlapping boxes of coarse seeds, duplicates) end up as one
+    detection.  Returns a MatchList in ascending score, then with return_boxes the (n, 4) int32 footprints, with
+    return_matched the (n,) float32 matched fractions (matched_fractions of each detection's pose) and with return_jobs the
+    (n,) int32 index of the job each detection came from, in that order.  angles, pivot, wrap, stride and line_caps are
+    exhaustive_window_search's."""
+    kind, tau = _penalty_args(penalty)
+    permille = int(round(1000 * float(overlap)))
+    sx, sy = _strides(stride)
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates, line_caps)
+    cs = pv = None
+    if angles is not None:
+        cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
+    res = fm.exhaustive_detect_windows(tset, jobs, cs, pv, sx=sx, sy=sy, wrap=wrap, max_score=max_score, max_detections=max_detections,
+                                       overlap_permille=permille, margin=margin, penalty=kind, tau=tau, min_matched=min_matched,
+                                       boxes=return_boxes, matched=return_matched, job_index=return_jobs)
+    return (MatchList(res[0]),) + tuple(res[1:]) if isinstance(res, tuple) else MatchList(res)
+
+
+def exhaustive_detect_refined(featuremap, templates, max_score, coarse_angles, fine_angles, coarse_stride, half_angles, half_x, half_y,
+                              coarse_max_score=None, coarse_overlap=1.0, coarse_max_detections=1024, overlap=0.3, stride=1,
+                              max_detections=1024, penalty=None, pivot="center", wrap=False, line_caps=None, margin=0,
+                              min_matched=None, return_boxes=False, return_matched=False, return_jobs=False):
+    """Every part in the frame to the fine table's angle step and `stride` pixels, without the dense fine search: pure
+    Python over three calls, and by definition exactly their composition:
+      seeds = exhaustive_detect_all(featuremap, templates, coarse_max_score (None: inf), overlap=coarse_overlap,
+                                    stride=coarse_stride, max_detections=coarse_max_detections, penalty=penalty,
+                                    angles=coarse_angles, pivot=pivot, line_caps=line_caps, margin=margin)
+      jobs = pose_windows(seeds, coarse_angles, fine_angles, template_pivots(templates, pivot), half_angles, half_x, half_y,
+                          stride=stride, wrap=wrap)
+      exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=overlap, angles=fine_angles, stride=stride,
+                                max_detections=max_detections, penalty=penalty, pivot=pivot, wrap=wrap, line_caps=line_caps,
+                                margin=margin, min_matched=min_matched, return_boxes=.., return_matched=.., return_jobs=..)
+    The coarse stage has no matched-fraction gate (a pose a few degrees off matches few lines) and by default neither a
+    threshold nor suppression: its coarse_max_detections best grid points are the seeds, and the fine stage's rule reduces the
+    refined seeds of one object to one detection.  return_jobs indexes the seeds."""
+    seeds = exhaustive_detect_all(featuremap, templates, float("inf") if coarse_max_score is None else coarse_max_score,
+                                  overlap=coarse_overlap, stride=coarse_stride, max_detections=coarse_max_detections, penalty=penalty,
+                                  angles=coarse_angles, pivot=pivot, line_caps=line_caps, margin=margin)
+    jobs = pose_windows(seeds, coarse_angles, fine_angles, template_pivots(templates, pivot), half_angles, half_x, half_y,
+                        stride=stride, wrap=wrap)
+    return exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=overlap, angles=fine_angles, stride=stride,
+                                     max_detections=max_detections, penalty=penalty, pivot=pivot, wrap=wrap, line_caps=line_caps,
+                                     margin=margin, min_matched=min_matched, return_boxes=return_boxes,
+                                     return_matched=return_matched, return_jobs=return_jobs)
+
+
 # ---------------------------------------------------------------- per-line caps and line costs (extension)
 def line_caps(templates, tau):
     """The caps a scalar line_caps=tau stands for: per template the float32 array float32(tau) * len_i, len_i the line's

@@ -180,6 +180,10 @@ SYMBOLS = [
     ("fdcm_search_exhaustive_detect_all_matched", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_float, C.c_int32,
                                                            C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int32,
                                                            C.POINTER(_vp), _i64p, C.POINTER(C.c_int32), _fp]),
+    ("fdcm_search_exhaustive_detect_windows", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(PoseWindow), C.c_int64, C.c_int32,
+                                                       C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int,
+                                                       C.c_float, C.c_float, C.c_int32, C.POINTER(_vp), _i64p, C.POINTER(C.c_int32),
+                                                       _fp, C.POINTER(C.c_int32)]),
     ("fdcm_matched_fractions", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64, _fp]),
     ("fdcm_templates_matched_totals", C.c_int, [_vp, _fp]),
     ("fdcm_detect_score_bounds", C.c_int, [_vp, C.c_int, C.c_float, C.c_float, _fp]),

@@ -800,6 +800,42 @@ int fdcm_search_exhaustive_windows(const fdcm_featuremap* fm, const fdcm_templat
     });
 }
 
+// Detections over pose windows: include/fdcm.h, "Detections over pose windows".  The detector's limits, then the pose
+// windows' checks in their order: nothing here touches the device.
+int fdcm_search_exhaustive_detect_windows(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                          const fdcm_pose_window* jobs, int64_t n_jobs, int32_t sx, int32_t sy, int32_t wrap,
+                                          float max_score, int32_t max_detections, int32_t overlap_permille, int32_t margin, int penalty,
+                                          float tau, float min_matched, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                          int32_t* boxes_out, float* matched_out, int32_t* jobs_out) {
+    return guarded([&] {
+        require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
+        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
+        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(min_matched >= 0.f && min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
+        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
+        require(std::isfinite(tau), "tau must be finite");
+        require(out && n_out, "null output");
+        require(sx >= 1 && sy >= 1, "strides sx and sy must be >= 1");
+        require(wrap == 0 || wrap == 1, "wrap must be 0 or 1");
+        require(n_jobs >= 0 && (n_jobs == 0 || jobs), "jobs is null or n_jobs is negative");
+        require(n_jobs <= ((int64_t)1 << 22), "n_jobs must be at most 2^22");
+        if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
+        check_pose_windows(jobs, n_jobs, rot ? rot->n : 1, sx, sy, wrap);
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        if (rot) check_pivots(templates, rot);
+        for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
+            require(jobs[j].tmpl < templates->T, "jobs: tmpl is outside the template set");
+        records_call(out, [&] {
+            run_search_exhaustive_detect_windows(const_cast<fdcm_featuremap*>(fm), templates, rot, jobs, n_jobs, sx, sy,
+                                                 max_score == 0.f ? 0.f : max_score, max_detections, overlap_permille, margin, penalty, tau,
+                                                 min_matched == 0.f ? 0.f : min_matched, tmpl_index_base, out, n_out, boxes_out,
+                                                 matched_out, jobs_out);
+        });
+    });
+}
+
 // Best map and detections: include/fdcm.h, "Best map and detections".  What the rotation call rejects, then the limits of
 // these two: nothing here touches the device.
 static void check_best_args(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid* grid,

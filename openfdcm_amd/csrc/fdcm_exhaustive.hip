@@ -23,6 +23,10 @@
 //                                     matched fraction: a thread per point of the key plane (the gate before the rounds of
 //                                     k_nms_round), per entry of the result list, per pose of a list; all three through
 //                                     matched_length<BUF32>, the one statement of the matched length
+//   k_window_winners<BUF32>, k_nms_list_round
+//                                     detections over pose windows: a thread per job turns the job's merged k = 1 list into
+//                                     its entry of the winners' list (normalised key, footprint), and one round of the greedy
+//                                     rule on that list, k_nms_round's scheme with a list in place of the key plane
 //
 // Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP, EXIT>, the one statement of the sum (4 rows per lane in
 // k_exhaustive, 1 in k_exhaustive_windows).  CAP: every term clamped to its line's cap (include/fdcm.h, "Per-line caps and
@@ -554,6 +558,17 @@ __device__ __forceinline__ void nms_block_min(unsigned long long& key, int& pair
     __syncthreads();  // sk and sp are free again
 }
 
+// The overlap test, the one statement of it: the footprint [fx0, fx1] x [fy0, fy1] against the winner's, whose area is Aw.
+// 1000 I > permille U in int64, U = A + Aw - I; boxes that share no pixel never suppress each other.
+__device__ __forceinline__ bool nms_suppresses(int fx0, int fy0, int fx1, int fy1, int wx0, int wy0, int wx1, int wy1, long long Aw,
+                                               int permille) {
+    const int ix = min(fx1, wx1) - max(fx0, wx0) + 1, iy = min(fy1, wy1) - max(fy0, wy0) + 1;
+    if (ix <= 0 || iy <= 0) return false;
+    const long long I = (long long)ix * (long long)iy;
+    const long long U = (long long)(fx1 - fx0 + 1) * (long long)(fy1 - fy0 + 1) + Aw - I;
+    return 1000ll * I > (long long)permille * U;
+}
+
 __global__ void __launch_bounds__(256) k_nms_round(unsigned long long* keys, long long n_chunks, int x0, int y0, int sx, int sy, int nx,
                                                    int tiles_x, const int4* __restrict__ boxes, int permille, int round, int last,
                                                    const unsigned long long* __restrict__ pk_in, const int* __restrict__ pp_in,
@@ -601,13 +616,7 @@ __global__ void __launch_bounds__(256) k_nms_round(unsigned long long* keys, lon
             if (!drop) {
                 const int4 b = boxes[u];
                 const int tx = x0 + i * sx, ty = y0 + j * sy;
-                const int fx0 = b.x + tx, fy0 = b.y + ty, fx1 = b.z + tx, fy1 = b.w + ty;
-                const int ix = min(fx1, wx1) - max(fx0, wx0) + 1, iy = min(fy1, wy1) - max(fy0, wy0) + 1;
-                if (ix > 0 && iy > 0) {
-                    const long long I = (long long)ix * (long long)iy;
-                    const long long U = (long long)(fx1 - fx0 + 1) * (long long)(fy1 - fy0 + 1) + Aw - I;
-                    drop = 1000ll * I > (long long)permille * U;
-                }
+                drop = nms_suppresses(b.x + tx, b.y + ty, b.z + tx, b.w + ty, wx0, wy0, wx1, wy1, Aw, permille);
             }
         }
         if (drop) {
@@ -804,6 +813,106 @@ __global__ void __launch_bounds__(256) k_matched_fractions(const float* __restri
     out[q] = matched_fraction(ml, P.tl);
 }
 
+// ---- detections over pose windows (include/fdcm.h, "Detections over pose windows")
+// The winners of a part of the job list: one thread per job, after the part's last merge.  best[j] is the job's merged list
+// at k = 1, its winner's key (score bits << 32) | (e N_j + g) or kNoKey.  The thread decodes it to the run position, the grid
+// point and the translation, finds the prepared pair of that run position (run[run0 + e]: its lines, the bits of its
+// denominator in koff, its footprint, its need), divides once, applies the threshold and, with a gate (need not null),
+// matched_length at the translation, and writes the job's entry of the list: key (bits of q << 32) | the job's index in the
+// call, kNoKey for a job without a winner or one the threshold or the gate removes, and the footprint F(j).  An entry has one
+// writer; lanes of a wave hold different pairs.
+struct WinnerJob {
+    int run0;        // where its run's pairs begin in `run`
+    int x0, y0, nx;  // its grid
+    unsigned N;      // nx ny
+    int pad[3];
+};
+static_assert(sizeof(WinnerJob) == 32, "WinnerJob is 32 bytes");
+
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_window_winners(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
+                                                        const ExLine* __restrict__ lines, const float* __restrict__ len,
+                                                        const ExTmpl* __restrict__ tm, const int4* __restrict__ foot,
+                                                        const float* __restrict__ need, const WinnerJob* __restrict__ jobs,
+                                                        const int* __restrict__ run, const unsigned long long* __restrict__ best,
+                                                        int n_jobs, unsigned job0, int sx, int sy, float max_score,
+                                                        unsigned long long* __restrict__ keys, int4* __restrict__ boxes) {
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (j >= n_jobs) return;
+    const unsigned long long v = best[j];
+    if (v == kNoKey) {
+        keys[j] = kNoKey;
+        boxes[j] = make_int4(0, 0, -1, -1);
+        return;
+    }
+    const WinnerJob J = jobs[j];
+    const unsigned low = (unsigned)v, e = low / J.N, g = low % J.N;
+    const int x = J.x0 + (int)(g % (unsigned)J.nx) * sx, y = J.y0 + (int)(g / (unsigned)J.nx) * sy;
+    const int u = run[J.run0 + (int)e];
+    const ExTmpl P = tm[u];
+    const float q = __uint_as_float((unsigned)(v >> 32)) / __uint_as_float(P.koff);  // one IEEE division, as the best map's
+    bool keep = !(q != q) && q <= max_score;
+    if (keep && need) {
+        const VolRef V = make_volref(vol, SL, m, BUF32);
+        const float ml = matched_length<BUF32>(V, lines + P.line0, len + P.line0, P.n, tx + (float)x, ty + (float)y, W, (unsigned)H, SL);
+        keep = ml >= need[u];
+    }
+    const int4 b = foot[u];
+    keys[j] = keep ? ((unsigned long long)__float_as_uint(q) << 32) | (job0 + (unsigned)j) : kNoKey;
+    boxes[j] = make_int4(b.x + x, b.y + y, b.z + x, b.w + y);
+}
+
+// One round of the greedy rule on the winners' list: k_nms_round's scheme with the list in place of the key plane.  Entry j
+// is (keys[j], boxes[j]), its key's low half j itself and its footprint its own, so nothing goes through a pair; the partial
+// minima are keys alone.  Round r reduces the partials of round r - 1 to the winner d(r-1), workgroup 0 writes it to
+// best[r - 1], and every workgroup walks its run of the list: the winner and every entry it suppresses (nms_suppresses)
+// become kNoKey by a plain store of the entry's one owner, the others enter the workgroup's minimum.  A winner kNoKey, or the
+// last launch, leaves kNoKey partials and returns.  The winner's box is read from the list: a round erases keys, never boxes.
+__global__ void __launch_bounds__(256) k_nms_list_round(unsigned long long* keys, const int4* __restrict__ boxes, long long n,
+                                                        int permille, int round, int last,
+                                                        const unsigned long long* __restrict__ pk_in,
+                                                        unsigned long long* __restrict__ pk_out, unsigned long long* __restrict__ best) {
+    __shared__ unsigned long long sk[4];
+    __shared__ int sp[4];
+    unsigned long long W = kNoKey;
+    int none = 0;
+    if (round > 0) {
+        if (threadIdx.x < gridDim.x) W = pk_in[threadIdx.x];
+        nms_block_min(W, none, sk, sp);
+        if (blockIdx.x == 0 && threadIdx.x == 0) best[round - 1] = W;
+        if (W == kNoKey || last) {  // workgroup-uniform
+            if (threadIdx.x == 0) pk_out[blockIdx.x] = kNoKey;
+            return;
+        }
+    }
+    const long long jw = (long long)(unsigned)W;
+    int4 w = make_int4(0, 0, -1, -1);
+    if (round > 0) w = boxes[jw];
+    const long long Aw = (long long)(w.z - w.x + 1) * (long long)(w.w - w.y + 1);
+    const long long n_chunks = (n + 255) / 256;
+    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
+    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
+    unsigned long long mk = kNoKey;
+    for (long long c = c0; c < c1; ++c) {
+        const long long idx = c * 256 + threadIdx.x;
+        if (idx >= n) continue;
+        const unsigned long long v = keys[idx];
+        if (v == kNoKey) continue;
+        bool drop = false;
+        if (round > 0) {
+            drop = idx == jw;
+            if (!drop) {
+                const int4 b = boxes[idx];
+                drop = nms_suppresses(b.x, b.y, b.z, b.w, w.x, w.y, w.z, w.w, Aw, permille);
+            }
+        }
+        if (drop) keys[idx] = kNoKey;
+        else if (v < mk) mk = v;
+    }
+    nms_block_min(mk, none, sk, sp);
+    if (threadIdx.x == 0) pk_out[blockIdx.x] = mk;
+}
+
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // The integer translations t in [-kMaxCoord, kMaxCoord] with lo < fl(p + fl(off + t)) < hi for p = pmin and p = pmax, i.e.
@@ -951,6 +1060,11 @@ void on_threads(int nth, const char* what, F part) {
         if (!e.empty()) throw e;
 }
 
+// The footprint of a pair (include/fdcm.h, "Detections suppressed by footprint overlap"): x0, y0, x1, y1.
+struct Foot { int32_t x0, y0, x1, y1; };
+static_assert(sizeof(Foot) == 16, "Foot is 16 bytes");
+Foot footprint(const float* p, size_t stride, int64_t n, int margin);
+
 // ---- the host preparation, the one of every call
 // (template, rotation) pairs, each prepared once: its rotated lines (RotM's rule; the caller's own lines when there is no
 // table), their bins (line_record), their caps (the line's own under every rotation) and its admissible box in translation
@@ -964,6 +1078,8 @@ struct Pairs {
     std::vector<int> line0, nl;  // per pair: its lines
     std::vector<Box> box;
     std::vector<RotM> M;  // (rotations only)
+    int foot_margin = -1;    // set >= 0 before prepare_pairs: also fill foot, the pairs' footprints at that margin
+    std::vector<Foot> foot;  // (or empty)
     bool buf32 = true;    // VolRef's form for the kernels that read the lines
     bool capped = false;  // the set has a finite cap: the scoring kernels that clamp
     size_t SL = 0;
@@ -986,6 +1102,7 @@ void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdc
     W.nl.assign(np, 0);
     W.box.assign(np, Box{false, 0, 0, 0, 0});
     if (rot) W.M.resize(np);
+    if (W.foot_margin >= 0) W.foot.assign(np, Foot{0, 0, -1, -1});
     int64_t total = 0;
     for (size_t u = 0; u < np; ++u) {  // pair u's lines follow pair u - 1's
         const int64_t i = key_of(u) / n;
@@ -1030,6 +1147,7 @@ void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdc
                 for (int x = 0; x < W.nl[u] && fm->m > 0; ++x)  // (an empty map has no bins: no line is read there)
                     W.lines[(size_t)W.line0[u] + x] =
                         line_record(fm, &src->lines[(size_t)(l0 + x) * 4], t->caps[(size_t)(t->offsets[(size_t)i] + x)], W.buf32, W.SL);
+                if (W.foot_margin >= 0) W.foot[u] = footprint(&src->lines[(size_t)l0 * 4], 4, W.nl[u], W.foot_margin);
             }
             p = q;
         }
@@ -1391,9 +1509,6 @@ struct BestRun {
     int tiles_x = 0, parts = 0;
 };
 
-// The footprint of a pair (include/fdcm.h, "Detections suppressed by footprint overlap"): x0, y0, x1, y1.
-struct Foot { int32_t x0, y0, x1, y1; };
-static_assert(sizeof(Foot) == 16, "Foot is 16 bytes");
 constexpr size_t kNmsPartialBytes = 2 * kNmsWorkgroups * (8 + 4);  // two sets of partial minima: the keys, then the pairs
 
 // Scores every pair of P (T templates x n rotations, prepared) on the grid and leaves, on the device, the merged key
@@ -1541,17 +1656,34 @@ constexpr int kWinItems = 1 << 20;      // patches of a batch, at most (a job ha
 constexpr int kWinWaves = 16384;        // waves of a launch, about: twice what is resident at 8 waves per SIMD
 constexpr size_t kWinStageBytes = (size_t)256 << 20;  // what one upload holds, about: longer job lists go in rounds
 
+// What the detections over pose windows add to a round (k = 1): after the last merge k_window_winners turns the round's
+// merged lists into the jobs' entries of the winners' list, which come down with the lists.
+struct WinnersIn {
+    const float* den;          // per template: the denominator of q
+    const float* need;         // per template: the gate's need, or null without a gate
+    int margin;                // of the footprints
+    float max_score;
+    unsigned long long* keys;  // per job of the call, on the host: (bits of q << 32) | job, or kNoKey
+    Foot* boxes;               // .. F(job)
+};
+
 // The jobs [j0, j1) of a call: their pairs prepared, their planes cut into batches, one upload, two kernels per batch and
 // the download of the jobs' merged lists into best[j0 k ..].  Mjob[m0[j] + e]: the transform of job j's run position e.
+// flat: the 64-bit form of VolRef whatever the volume's size.  wn (or null): the winners' pass, see WinnersIn.
 void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs, int64_t j0,
-                   int64_t j1, int sx, int sy, int k, unsigned long long* best, const std::vector<int64_t>& m0, std::vector<RotM>& Mjob) {
+                   int64_t j1, int sx, int sy, int k, unsigned long long* best, const std::vector<int64_t>& m0, std::vector<RotM>& Mjob,
+                   bool flat, const WinnersIn* wn = nullptr) {
     const int n = rot ? rot->n : 1;
     Pairs W;
+    W.lens = wn && wn->need;
+    if (wn) W.foot_margin = wn->margin;
     for (int64_t j = j0; j < j1; ++j)
         for (int e = 0; e < jobs[j].na; ++e) W.key.push_back((int64_t)jobs[j].tmpl * n + (jobs[j].a0 + e) % n);
     std::sort(W.key.begin(), W.key.end());
     W.key.erase(std::unique(W.key.begin(), W.key.end()), W.key.end());
-    prepare_pairs(fm, t, rot, test_switches().windows_flat, W);
+    prepare_pairs(fm, t, rot, flat, W);
+    std::vector<WinnerJob> wjob;  // (winners only) per job of the round, and the pair of each of its run positions
+    std::vector<int> wrun;
 
     // Batches of whole jobs.  Per batch: its planes and their patches (job by job, run position by run position, a box's
     // patches along j first), per job with patches its first wave and candidate list, and its group for the merge
@@ -1591,8 +1723,10 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
         const fdcm_pose_window& J = jobs[j];
         std::vector<WinPlane> jp;
         long long ji = 0;
+        if (wn) wjob.push_back(WinnerJob{(int)wrun.size(), J.x0, J.y0, J.nx, (unsigned)(J.nx * J.ny), {0, 0, 0}});
         for (int e = 0; e < J.na; ++e) {
             const size_t u = W.find((int64_t)J.tmpl * n + (J.a0 + e) % n);
+            if (wn) wrun.push_back((int)u);
             if (rot) Mjob[(size_t)(m0[(size_t)j] + e)] = W.M[u];
             if (W.nl[u] == 0 || !W.box[u].any) continue;  // a template without lines gives nothing
             WinPlane P{W.line0[u], W.nl[u], 0, -1, 0, -1, J.x0, J.y0, J.nx, (unsigned)((long long)e * J.nx * J.ny), 0, 0};
@@ -1621,10 +1755,24 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
 
     // One pinned buffer, one asynchronous copy: lines, planes, patches, job and group tables and the merged lists; the
     // candidate lists of one batch follow on the device.
+    // The winners' pass: per pair its lines, denominator (koff), footprint and need, the line lengths (with a gate), the
+    // jobs' grids and runs go up with the rest; the round's part of the list follows the candidate lists on the device.
+    const size_t np = W.nl.size();
+    std::vector<ExTmpl> wtm(wn ? np : 0);
+    std::vector<float> wneed(wn && wn->need ? np : 0);
+    for (size_t u = 0; u < wtm.size(); ++u) {
+        const size_t tmpl = (size_t)(W.key[u] / n);
+        wtm[u] = ExTmpl{W.line0[u], W.nl[u], 0, -1, 0, -1, 0, bits_from_f(wn->den[tmpl])};
+        if (wn->need) wneed[u] = wn->need[tmpl];
+    }
     const size_t o_pl = al256(W.lines.size() * sizeof(ExLine)), o_it = o_pl + al256(planes.size() * sizeof(WinPlane)),
                  o_jt = o_it + al256(items.size() * sizeof(int2)), o_seg = o_jt + al256(jtab.size() * sizeof(WinJob)),
-                 o_best = o_seg + al256(seg.size() * sizeof(int4)), o_cand = o_best + al256(nj * k * 8),
-                 total = o_cand + al256(max_lists * k * 8);
+                 o_wtm = o_seg + al256(seg.size() * sizeof(int4)), o_wfoot = o_wtm + al256(wtm.size() * sizeof(ExTmpl)),
+                 o_wneed = o_wfoot + al256(W.foot.size() * sizeof(Foot)), o_wlen = o_wneed + al256(wneed.size() * sizeof(float)),
+                 o_wjob = o_wlen + (W.lens ? al256(W.len.size() * sizeof(float)) : 0), o_wrun = o_wjob + al256(wjob.size() * sizeof(WinnerJob)),
+                 o_best = o_wrun + al256(wrun.size() * sizeof(int)), o_cand = o_best + al256(nj * k * 8),
+                 o_wkeys = o_cand + al256(max_lists * k * 8), o_wboxes = o_wkeys + (wn ? al256(nj * 8) : 0),
+                 total = o_wboxes + (wn ? al256(nj * sizeof(Foot)) : 0);
     reserve_eval(fm, total, o_cand);
     char* d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
@@ -1633,6 +1781,14 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     std::memcpy(h + o_it, items.data(), items.size() * sizeof(int2));
     std::memcpy(h + o_jt, jtab.data(), jtab.size() * sizeof(WinJob));
     std::memcpy(h + o_seg, seg.data(), seg.size() * sizeof(int4));
+    if (wn) {
+        std::memcpy(h + o_wtm, wtm.data(), wtm.size() * sizeof(ExTmpl));
+        std::memcpy(h + o_wfoot, W.foot.data(), W.foot.size() * sizeof(Foot));
+        std::memcpy(h + o_wneed, wneed.data(), wneed.size() * sizeof(float));
+        if (W.lens) std::memcpy(h + o_wlen, W.len.data(), W.len.size() * sizeof(float));
+        std::memcpy(h + o_wjob, wjob.data(), wjob.size() * sizeof(WinnerJob));
+        std::memcpy(h + o_wrun, wrun.data(), wrun.size() * sizeof(int));
+    }
     std::memset(h + o_best, 0xff, nj * k * 8);  // kNoKey
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d, h, o_cand, hipMemcpyHostToDevice, st));
@@ -1650,8 +1806,38 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
                            (const unsigned long long*)cand, (const int4*)(d + o_seg) + B.s0, B.groups, 1, k, d_best);
         FDCM_HIP(hipGetLastError());
     }
+    if (wn) {  // (k = 1: a job's merged list is its winner)
+        auto kern = W.buf32 ? k_window_winners<true> : k_window_winners<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
+                           fm->ty, (const ExLine*)d, (const float*)(d + o_wlen), (const ExTmpl*)(d + o_wtm), (const int4*)(d + o_wfoot),
+                           wn->need ? (const float*)(d + o_wneed) : (const float*)nullptr, (const WinnerJob*)(d + o_wjob),
+                           (const int*)(d + o_wrun), (const unsigned long long*)d_best, (int)nj, (unsigned)j0, sx, sy, wn->max_score,
+                           (unsigned long long*)(d + o_wkeys), (int4*)(d + o_wboxes));
+        FDCM_HIP(hipGetLastError());
+        FDCM_HIP(hipMemcpyAsync(wn->keys + j0, d + o_wkeys, nj * 8, hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipMemcpyAsync(wn->boxes + j0, d + o_wboxes, nj * sizeof(Foot), hipMemcpyDeviceToHost, st));
+    }
     FDCM_HIP(hipMemcpyAsync(best, d_best, nj * k * 8, hipMemcpyDeviceToHost, st));
     FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
+}
+
+// Where the round that begins at job j0 ends: jobs of about kWinStageBytes of tables, one job at least.  winners: with the
+// tables of the winners' pass.
+int64_t windows_round_end(const fdcm_templates* t, const fdcm_pose_window* jobs, int64_t j0, int64_t n_jobs, int k, bool winners = false) {
+    // (a forced batch size also shrinks the rounds, to 4 KB a plane: the tests' small lists then go in several)
+    const size_t round_bytes = test_switches().windows_batch > 0 ? (size_t)test_switches().windows_batch << 12 : kWinStageBytes;
+    int64_t j1 = j0;
+    size_t bytes = 0;
+    do {  // an upper bound of the job's share of the upload: no pair counted as shared
+        const fdcm_pose_window& J = jobs[j1];
+        const size_t nl = (size_t)(t->offsets[(size_t)J.tmpl + 1] - t->offsets[(size_t)J.tmpl]);
+        bytes += (size_t)J.na * (sizeof(WinPlane) + nl * sizeof(ExLine) +
+                                 (size_t)((J.nx + kPatchX - 1) / kPatchX) * (size_t)((J.ny + kPatchY - 1) / kPatchY) * sizeof(int2)) +
+                 sizeof(WinJob) + sizeof(int4) + (size_t)k * 8;
+        if (winners) bytes += (size_t)J.na * (sizeof(ExTmpl) + sizeof(Foot) + 2 * sizeof(float) + nl * sizeof(float)) + sizeof(WinnerJob);
+        ++j1;
+    } while (j1 < n_jobs && bytes < round_bytes);
+    return j1;
 }
 
 }  // namespace
@@ -2030,20 +2216,9 @@ void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t,
     std::vector<int64_t> m0((size_t)n_jobs + 1, 0);
     for (int64_t j = 0; j < n_jobs; ++j) m0[(size_t)j + 1] = m0[(size_t)j] + jobs[j].na;
     std::vector<RotM> Mjob(rot ? (size_t)m0[(size_t)n_jobs] : 0);
-    // (a forced batch size also shrinks the rounds, to 4 KB a plane: the tests' small lists then go in several)
-    const size_t round_bytes = test_switches().windows_batch > 0 ? (size_t)test_switches().windows_batch << 12 : kWinStageBytes;
     for (int64_t j0 = 0; j0 < n_jobs;) {
-        int64_t j1 = j0;
-        size_t bytes = 0;
-        do {  // an upper bound of the job's share of the upload: no pair counted as shared
-            const fdcm_pose_window& J = jobs[j1];
-            const size_t nl = (size_t)(t->offsets[(size_t)J.tmpl + 1] - t->offsets[(size_t)J.tmpl]);
-            bytes += (size_t)J.na * (sizeof(WinPlane) + nl * sizeof(ExLine) +
-                                     (size_t)((J.nx + kPatchX - 1) / kPatchX) * (size_t)((J.ny + kPatchY - 1) / kPatchY) * sizeof(int2)) +
-                     sizeof(WinJob) + sizeof(int4) + (size_t)k * 8;
-            ++j1;
-        } while (j1 < n_jobs && bytes < round_bytes);
-        windows_round(fm, t, rot, jobs, j0, j1, sx, sy, k, best.data() + (size_t)j0 * k, m0, Mjob);
+        const int64_t j1 = windows_round_end(t, jobs, j0, n_jobs, k);
+        windows_round(fm, t, rot, jobs, j0, j1, sx, sy, k, best.data() + (size_t)j0 * k, m0, Mjob, test_switches().windows_flat);
         j0 = j1;
     }
     std::vector<fdcm_grid> grids((size_t)n_jobs);
@@ -2051,6 +2226,111 @@ void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t,
     emit_records(
         best, k, n_jobs, [&](int64_t q) { return base + jobs[q].tmpl; }, [&](int64_t q) -> const fdcm_grid& { return grids[(size_t)q]; },
         [&](int64_t q, int e) { return rot ? &Mjob[(size_t)(m0[(size_t)q] + e)] : nullptr; }, out, n_out, job_offsets);
+}
+
+static void matched_fractions_rounds(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses,
+                                     int64_t n, float* fractions);
+
+// Detections over pose windows (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  The job list goes through
+// windows_round at k = 1 in the pose windows' rounds, each with the winners' pass behind its last merge; the rounds leave
+// the winners' list on the host, a key and a footprint per job, which goes up whole for the rounds of k_nms_list_round,
+// queued kNmsBatch at a time as detect_all queues k_nms_round's.  A record is emit_records' for the key (bits of q << 32) |
+// (e N_j + g) of its job's winner; its box is the list's; its fraction k_matched_fractions' at the record's pose, in a
+// round of its own after the last launch.  The 64-bit form follows FDCM_WINDOWS_FLAT and FDCM_MATCHED_FLAT.
+void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot,
+                                          const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, float max_score, int max_det,
+                                          int permille, int margin, int penalty, float tau, float min_matched, int32_t base,
+                                          fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out, int32_t* jobs_out) {
+    *n_out = 0;
+    if (n_jobs == 0 || t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int n = rot ? rot->n : 1;
+    const size_t nj = (size_t)n_jobs;
+    std::vector<unsigned long long> raw(nj, kNoKey), keys(nj, kNoKey);  // the winners' window keys; the list's keys
+    std::vector<Foot> boxes(nj, Foot{0, 0, -1, -1});
+    std::vector<int64_t> m0(nj + 1, 0);
+    for (int64_t j = 0; j < n_jobs; ++j) m0[(size_t)j + 1] = m0[(size_t)j] + jobs[j].na;
+    std::vector<RotM> Mjob(rot ? (size_t)m0[nj] : 0);
+    const std::vector<float> den = best_denominators(t, penalty, tau);
+    std::vector<float> totals, need;
+    if (min_matched > 0.f) {  // need = float32(min_matched * TL) of the template
+        totals.resize((size_t)t->T);
+        templates_matched_totals(t, totals.data());
+        need.resize(totals.size());
+        for (size_t i = 0; i < need.size(); ++i) need[i] = min_matched * totals[i];
+    }
+    const WinnersIn wn{den.data(), need.empty() ? nullptr : need.data(), margin, max_score, keys.data(), boxes.data()};
+    const bool flat = test_switches().windows_flat || test_switches().matched_flat;
+    for (int64_t j0 = 0; j0 < n_jobs;) {
+        const int64_t j1 = windows_round_end(t, jobs, j0, n_jobs, 1, true);
+        windows_round(fm, t, rot, jobs, j0, j1, sx, sy, 1, raw.data() + j0, m0, Mjob, flat, &wn);
+        j0 = j1;
+    }
+    if (std::all_of(keys.begin(), keys.end(), [](unsigned long long v) { return v == kNoKey; })) return;
+
+    // The rounds: the list (keys, boxes) and the result list (kNoKey) by one upload; two sets of partial minima behind them.
+    const size_t o_box = al256(nj * 8), o_best = o_box + al256(nj * sizeof(Foot)), o_pk = o_best + al256((size_t)max_det * 8);
+    reserve_eval(fm, o_pk + 2 * kNmsWorkgroups * 8, o_pk);
+    char* d = (char*)fm->search.eval.p;
+    char* h = (char*)fm->search.eval_stage.p;
+    std::memcpy(h, keys.data(), nj * 8);
+    std::memcpy(h + o_box, boxes.data(), nj * sizeof(Foot));
+    std::memset(h + o_best, 0xff, (size_t)max_det * 8);  // kNoKey
+    hipStream_t st = fm->stream;
+    FDCM_HIP(hipMemcpyAsync(d, h, o_pk, hipMemcpyHostToDevice, st));
+    unsigned long long* pk = (unsigned long long*)(d + o_pk);
+    unsigned long long* d_best = (unsigned long long*)(d + o_best);
+    const unsigned wgs = (unsigned)std::min<size_t>(kNmsWorkgroups, (nj + 255) / 256);
+    for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
+        const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));
+        for (; r <= r1; ++r) {
+            hipLaunchKernelGGL(k_nms_list_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
+                               (long long)n_jobs, permille, r, (int)(r == max_det),
+                               (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups, d_best);
+            FDCM_HIP(hipGetLastError());
+        }
+        if (r > max_det) break;
+        unsigned long long last = kNoKey;  // winner r1 - 1, the batch's last
+        FDCM_HIP(hipMemcpyAsync(&last, d_best + (r1 - 1), 8, hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+        if (last == kNoKey) break;
+    }
+    std::vector<unsigned long long> best((size_t)max_det);
+    FDCM_HIP(hipMemcpyAsync(best.data(), d_best, (size_t)max_det * 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+
+    // Record l is job jl[l]'s winner with q for its score: emit_records on lists of one key each.
+    std::vector<int64_t> jl;
+    std::vector<unsigned long long> rk;
+    for (int l = 0; l < max_det && best[(size_t)l] != kNoKey; ++l) {
+        const size_t j = (size_t)(uint32_t)best[(size_t)l];
+        jl.push_back((int64_t)j);
+        rk.push_back((best[(size_t)l] & 0xffffffff00000000ull) | (raw[j] & 0xffffffffull));
+    }
+    std::vector<fdcm_grid> grids(jl.size());
+    for (size_t l = 0; l < jl.size(); ++l) {
+        const fdcm_pose_window& J = jobs[jl[l]];
+        grids[l] = fdcm_grid{J.x0, J.y0, J.nx, J.ny, sx, sy};
+    }
+    emit_records(
+        rk, 1, (int64_t)jl.size(), [&](int64_t q) { return base + jobs[jl[(size_t)q]].tmpl; },
+        [&](int64_t q) -> const fdcm_grid& { return grids[(size_t)q]; },
+        [&](int64_t q, int e) { return rot ? &Mjob[(size_t)(m0[(size_t)jl[(size_t)q]] + e)] : nullptr; }, out, n_out, nullptr);
+    std::vector<int32_t> poses(matched_out ? 4 * jl.size() : 0);
+    for (size_t l = 0; l < jl.size(); ++l) {
+        const size_t j = (size_t)jl[l];
+        if (boxes_out) std::memcpy(boxes_out + 4 * l, &boxes[j], sizeof(Foot));
+        if (jobs_out) jobs_out[l] = (int32_t)j;
+        if (matched_out) {
+            const fdcm_pose_window& J = jobs[j];
+            const uint32_t low = (uint32_t)raw[j], N = (uint32_t)(J.nx * J.ny), g = low % N;
+            int32_t* p = &poses[4 * l];
+            p[0] = J.tmpl; p[1] = (int32_t)((J.a0 + (int64_t)(low / N)) % n);
+            p[2] = J.x0 + (int32_t)(g % (uint32_t)J.nx) * sx; p[3] = J.y0 + (int32_t)(g / (uint32_t)J.nx) * sy;
+        }
+    }
+    if (matched_out && !jl.empty()) matched_fractions_rounds(fm, t, rot, poses.data(), (int64_t)jl.size(), matched_out);
 }
 
 // Line costs (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  Poses go in rounds of kCostPoses; a round
@@ -2118,6 +2398,12 @@ void run_matched_fractions(fdcm_featuremap* fm, const fdcm_templates* t, const f
     if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
     begin(fm);
+    matched_fractions_rounds(fm, t, rot, poses, n, fractions);
+}
+
+// The rounds of run_matched_fractions, for a caller that holds the feature map's turn and has begun.
+static void matched_fractions_rounds(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses,
+                                     int64_t n, float* fractions) {
     const int nr = rot ? rot->n : 1;
     const float* vol = fm->vol.as<float>();
     hipStream_t st = fm->stream;

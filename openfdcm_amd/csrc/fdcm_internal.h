@@ -37,8 +37,10 @@ struct HipError { hipError_t code; const char* what; int line; };
 //   FDCM_SEARCH_COMPACT2       the search's two-kernel compaction at every size (run_search)
 //   FDCM_WINDOWS_BATCH=1..     planes a batch of the pose-window search holds at most, instead of 65536 (windows_round),
 //                              and 4 KB of tables per such plane a round, instead of 256 MB (run_search_exhaustive_windows)
-//   FDCM_WINDOWS_FLAT          the pose-window search with 64-bit flat addresses (windows_round)
-//   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (detect_all, run_matched_fractions)
+//   FDCM_WINDOWS_FLAT          the pose-window search with 64-bit flat addresses (windows_round), the scoring and the winners'
+//                              pass of the detections over pose windows with it
+//   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (detect_all, run_matched_fractions,
+//                              run_search_exhaustive_detect_windows: its scoring, its winners' pass and its fractions)
 //   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
 //                              takes that form for a volume of 4 GB or more alone (score maps, top-k, peaks, rotations, best
 //                              map, the detections, line costs); the pose windows and the calls by matched fraction keep
@@ -401,6 +403,11 @@ void lines_footprints(const float* lines, const int64_t* offsets, int64_t T, con
 void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
                                    int64_t n_jobs, int sx, int sy, int k, int32_t base, fdcm_match** out, int64_t* n_out,
                                    int64_t* job_offsets);
+// detections over pose windows (include/fdcm.h): boxes_out, matched_out (max_det entries each) and jobs_out may be null
+void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot,
+                                          const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, float max_score, int max_det,
+                                          int permille, int margin, int penalty, float tau, float min_matched, int32_t base,
+                                          fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out, int32_t* jobs_out);
 // poses: n x (tmpl, a, x, y), checked; *costs is malloc'ed; offsets: n + 1
 void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                     float** costs, int64_t* offsets);

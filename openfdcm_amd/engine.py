@@ -364,6 +364,31 @@ class DeviceFeatureMap:
             offsets.ctypes.data_as(C.POINTER(C.c_int64))))
         return _adopt_matches(out, n.value), offsets
 
+    def exhaustive_detect_windows(self, templates, jobs, cs=None, pivots=None, sx=1, sy=1, wrap=False, max_score=float("inf"),
+                                  max_detections=1024, overlap_permille=300, margin=0, penalty=None, tau=1.0, min_matched=None,
+                                  tmpl_index_base=0, boxes=False, matched=False, job_index=False):
+        """Detections over pose windows (include/fdcm.h): every job of exhaustive_window_search gives its best pose (k = 1);
+        the best poses, normalised by the penalty, at most max_score and with at least min_matched of their line length
+        matched, go through exhaustive_detect_all's greedy rule by footprint overlap, keyed by (score, job).  Raw match
+        records in ascending order; with boxes the (n, 4) int32 footprints, with matched the (n,) float32 fractions, with
+        job_index the (n,) int32 job of each record, in that order."""
+        jobs = as_pose_windows(jobs)
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        out, n = C.c_void_p(), C.c_int64()
+        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0
+        fp = np.zeros((md, 4), dtype=np.int32)
+        fr = np.zeros(md, dtype=np.float32)
+        ji = np.zeros(md, dtype=np.int32)
+        capi.check(capi.lib().fdcm_search_exhaustive_detect_windows(
+            self._h, templates._h, C.byref(rot) if rot is not None else None, jobs.ctypes.data_as(C.POINTER(capi.PoseWindow)),
+            jobs.shape[0], int(sx), int(sy), int(bool(wrap)), float(max_score), int(max_detections), int(overlap_permille),
+            int(margin), -1 if penalty is None else int(penalty), float(tau), 0.0 if min_matched is None else float(min_matched),
+            int(tmpl_index_base), C.byref(out), C.byref(n), fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None,
+            capi.fptr(fr) if matched and md else None, ji.ctypes.data_as(C.POINTER(C.c_int32)) if job_index and md else None))
+        res = (_adopt_matches(out, n.value),) + ((fp[:n.value].copy(),) if boxes else ()) + ((fr[:n.value].copy(),) if matched else ())
+        res += (ji[:n.value].copy(),) if job_index else ()
+        return res if len(res) > 1 else res[0]
+
     # ---- best map and detections (include/fdcm.h, "Best map and detections"): cs None is the translations alone
     def best_map(self, templates, grid, cs=None, pivots=None, penalty=None, tau=1.0):
         """(scores, pairs): per grid point the lowest length-normalised score over all templates with lines and all

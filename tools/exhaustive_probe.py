@@ -32,7 +32,7 @@ COVERED = {
     "fdcm_score_map", "fdcm_score_map_rotations", "fdcm_search_exhaustive", "fdcm_search_exhaustive_peaks",
     "fdcm_search_exhaustive_rotations", "fdcm_best_map", "fdcm_search_exhaustive_detect", "fdcm_search_exhaustive_detect_nms",
     "fdcm_search_exhaustive_detect_all", "fdcm_search_exhaustive_detect_all_matched", "fdcm_search_exhaustive_windows",
-    "fdcm_line_costs", "fdcm_matched_fractions",
+    "fdcm_search_exhaustive_detect_windows", "fdcm_line_costs", "fdcm_matched_fractions",
 }
 EXEMPT = {
     "fdcm_score_map_device": "fdcm_score_map's driver and workspace layout with the planes in the caller's device memory, which is "
@@ -224,6 +224,20 @@ def _windows(x, note):
     return out
 
 
+def _detect_windows(x, note):
+    out = []
+    jobs = x.c["jobs"]
+    for s in x.sets:
+        got = x.dev.exhaustive_detect_windows(s, jobs, x.cs, x.piv, wrap=True, max_detections=MAX_DET, overlap_permille=300, margin=1,
+                                              penalty=DEFAULT, min_matched=0.2, boxes=True, matched=True, job_index=True)
+        note(len(got[0]), MAX_DET)
+        out += list(got)
+        got = x.dev.exhaustive_detect_windows(s, [(j[0], 0, 1, j[3], j[4], j[5], j[6]) for j in jobs], sx=3, sy=2, max_detections=2,
+                                              overlap_permille=1000, penalty=DEFAULT, boxes=True, job_index=True)
+        out += list(got)
+    return out
+
+
 def _line_costs(x, note):
     out = []
     for s in x.sets:
@@ -244,7 +258,7 @@ CALLS = [
     ("exhaustive_rotation_search", _rotation_search), ("best_score_map", _best_map), ("exhaustive_detect", _detect),
     ("exhaustive_detect_nms", _detect_nms), ("exhaustive_detect_all_inf", _detect_all(False)),
     ("exhaustive_detect_all_threshold", _detect_all(True)), ("exhaustive_detect_all_matched", _detect_all_matched),
-    ("exhaustive_window_search", _windows), ("line_costs", _line_costs), ("matched_fractions", _matched_fractions),
+    ("exhaustive_window_search", _windows), ("exhaustive_detect_windows", _detect_windows), ("line_costs", _line_costs), ("matched_fractions", _matched_fractions),
 ]
 NAMES = [name for name, _ in CALLS]
 
