@@ -642,7 +642,8 @@ int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, 
  * candidate passes when ML(best(g), t_g) >= need_t, t the template of best(g).  S_0 is the set of points with a candidate,
  * q(best(g)) <= max_score, that pass the gate; the greedy rule runs on this S_0, stopping at max_detections.
  * What the gate looks at: the pair the best map holds at g, and only that pair.  A point whose best pair fails is dropped,
- * even if another pair at g would pass: the gate is not part of the minimum that chooses best(g).
+ * even if another pair at g would pass: the gate is not part of the minimum that chooses best(g).  FDCM_GATE_ALL ("Gate
+ * inside the minimum", below) lifts this limitation.
  * fdcm_search_exhaustive_detect_all_matched: fdcm_search_exhaustive_detect_all with the gate.  matched_out (max_detections
  * floats, or NULL): entry l is frac of record l; the entries from *n_out on are not specified.
  * fdcm_matched_fractions: frac at n poses (tmpl, a, x, y); poses, admissibility and rot are fdcm_line_costs'.
@@ -688,7 +689,7 @@ int fdcm_templates_matched_totals(const fdcm_templates* templates, float* totals
  * Candidates S_0: the jobs that have a winner, whose q_j is not NaN, with q_j <= max_score and ML((tmpl, a_j), t_j) >=
  * need_tmpl.  What the gate looks at: the winner, and only the winner, as the dense call's gate looks at best(g) only.  A
  * job whose winner fails is dropped, even if another pose of its window would pass: the gate is not part of the minimum
- * that chooses the winner.
+ * that chooses the winner.  FDCM_GATE_ALL ("Gate inside the minimum", below) lifts this limitation.
  * key(j) = (bits of q_j << 32) | j.  Duplicate jobs are distinct candidates; the later one loses the tie and is then
  * suppressed by the earlier, unless overlap_permille = 1000.  Footprint F(j) = box(tmpl, a_j) + t_j, box as
  * fdcm_templates_footprints gives it at margin.  The rule is the greedy rule of fdcm_search_exhaustive_detect_nms on S_0 with
@@ -718,6 +719,62 @@ int fdcm_search_exhaustive_detect_windows(const fdcm_featuremap* fm, const fdcm_
                                           int32_t* boxes_out /* 4 max_detections, or NULL */,
                                           float* matched_out /* max_detections, or NULL */,
                                           int32_t* jobs_out /* max_detections, or NULL */);
+
+/* Gate inside the minimum: the matched-fraction gate as a condition on candidates, not a filter on winners.  With line caps q
+ * saturates in [0, tau]: at the point where an object lies a wrong view that matches half of its lines perfectly and has the
+ * other half capped can win the minimum over the right view, which matches every line moderately.  The gate above then
+ * deletes the point although the right view was scored there and would have passed.  Here a pair is a candidate of a point
+ * only if it passes the gate there, and a pose is a candidate of its window only if it passes.  The definitions are this
+ * project's (README.md, "Gate inside the minimum"; numpy statement: tests/gate_ref.py).  Everything not restated here is
+ * taken unchanged from fdcm_search_exhaustive_detect_all_matched and fdcm_search_exhaustive_detect_windows: score, caps,
+ * admissibility, rot == NULL, q and its denominators, pairkey, key(g), footprints, the overlap test, the greedy rule, the
+ * record layout, len_i, cap_i, the uncapped cost_i, matched (cost_i <= cap_i), ML (sequential float32 sum in line order from
+ * +0), TL_t, need_t = float32(min_matched * TL_t) and frac = ML / TL (1 when TL == 0).
+ * Gates: FDCM_GATE_WINNER is the gate of the two calls above.  FDCM_GATE_ALL is the gate inside the minimum:
+ * Dense, gate ALL: the candidates of grid point g are the pairs u = (t, a) of templates with lines that are admissible at g,
+ * whose q is not NaN and with ML(u, t_g) >= need_t.  best(g) is the candidate of the smallest pairkey; a point without a
+ * candidate has no key.  S_0 is the set of points with a candidate and q(best(g)) <= max_score; no second gate pass follows.
+ * The rest is the greedy rule and the output of fdcm_search_exhaustive_detect_all_matched: records, boxes, fractions.
+ * Gated best map (fdcm_best_map_gated): the planes q(best(g)), u(best(g)) and frac(best(g), t_g) for best as just defined,
+ * row-major [ny][nx]; NaN, -1 and NaN where g has no candidate.  Any of the three may be NULL, not all of them.
+ * Windows, gate ALL: the winner of job j is the admissible (e, g) with the smallest windows key (score bits << 32) | (e N_j +
+ * g) whose score is not NaN and whose pose passes ML((tmpl, a_e), t_g) >= need_tmpl.  A job with no such pose has no winner.
+ * The winner is still chosen on the raw score.  q_j, the threshold, key(j), footprints, the greedy rule and the outputs are
+ * unchanged.
+ * Identities: gate = FDCM_GATE_WINNER gives the bytes of the call without the argument (it is that call).  min_matched = 0
+ * gives, under either gate, the ungated bytes, and the gated best map at 0 gives fdcm_best_map's planes.  A set whose caps are
+ * all +inf, on a volume without NaN or infinity, gives the ungated bytes for any min_matched under either gate.  With
+ * overlap_permille = 1000 and max_detections not reached every record of gate WINNER is a record of gate ALL, same bytes: a
+ * point whose unrestricted best pair passes keeps it.  At fixed other parameters the records for any max_score are the
+ * leading records with score <= max_score of the +inf list.  Every record's fraction is, bit for bit, what
+ * fdcm_matched_fractions returns for its (tmpl, a, x, y), and its ML is >= need.  Results are a function of the inputs alone,
+ * whatever order workgroups run in.
+ * Which gate: WINNER when the gate only has to remove junk and the score alone should choose the view (it costs one pass over
+ * the key plane); ALL when caps are in use and occluded or partly matching views compete at one point, so that the object
+ * under the junk is kept (it costs a compare, a select and an add per term in the scoring kernel, and no gate pass).
+ * FDCM_EINVAL, before any GPU work: everything the call without the argument rejects; gate not FDCM_GATE_WINNER or
+ * FDCM_GATE_ALL; for fdcm_best_map_gated what fdcm_best_map rejects, min_matched NaN, < 0 or > 1, and all three planes NULL.
+ * Empty inputs give FDCM_OK and zero records (planes of NaN / -1 / NaN), as the siblings do.  The calls block; concurrent
+ * callers of one feature map take turns.  Release the records with fdcm_matches_free. */
+#define FDCM_GATE_WINNER 0
+#define FDCM_GATE_ALL 1
+int fdcm_best_map_gated(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                        const fdcm_grid* grid, int penalty, float tau, float min_matched, float* score_out_host /* or NULL */,
+                        int32_t* pair_out_host /* or NULL */, float* matched_out_host /* or NULL */);
+int fdcm_search_exhaustive_detect_all_gated(const fdcm_featuremap* fm, const fdcm_templates* templates,
+                                            const fdcm_rotations* rot /* or NULL */, const fdcm_grid* grid, float max_score,
+                                            int32_t max_detections, int32_t overlap_permille, int32_t margin, int penalty, float tau,
+                                            float min_matched, int gate, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                            int32_t* boxes_out /* 4 max_detections, or NULL */,
+                                            float* matched_out /* max_detections, or NULL */);
+int fdcm_search_exhaustive_detect_windows_gated(const fdcm_featuremap* fm, const fdcm_templates* templates,
+                                                const fdcm_rotations* rot /* or NULL */, const fdcm_pose_window* jobs, int64_t n_jobs,
+                                                int32_t sx, int32_t sy, int32_t wrap, float max_score, int32_t max_detections,
+                                                int32_t overlap_permille, int32_t margin, int penalty, float tau, float min_matched,
+                                                int gate, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                                int32_t* boxes_out /* 4 max_detections, or NULL */,
+                                                float* matched_out /* max_detections, or NULL */,
+                                                int32_t* jobs_out /* max_detections, or NULL */);
 
 /* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
  *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as

@@ -638,19 +638,27 @@ def _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps
     return fm, tset, cs, pv, _rotation_window(fm, tset, cs, pv, stride, window)
 
 
-def best_score_map(featuremap, templates, stride=1, penalty=None, angles=None, pivot="center", window=None, line_caps=None):
+def best_score_map(featuremap, templates, stride=1, penalty=None, angles=None, pivot="center", window=None, line_caps=None,
+                   min_matched=None, return_matched=False):
     """The templates compared with each other: per grid point the lowest score over all templates with lines and all
     angles, each score divided as penalize(penalty, ...) divides it (None: as it is), and which pair gave it.  Returns
     (scores [ny, nx] float32, NaN where no template fits; pairs [ny, nx] int32, -1 there; grid).  With n = len(angles)
     (1 without angles) pairs // n is the template and pairs % n the angle; equal scores go to the lowest template, then
     the lowest angle.  angles, pivot, window and line_caps are exhaustive_rotation_search's; with caps tau len_i and
-    DefaultPenalty the scores lie in [0, tau] up to rounding."""
+    DefaultPenalty the scores lie in [0, tau] up to rounding.  min_matched (0 to 1) or return_matched: the gated best map,
+    the plane exhaustive_detect_all(gate="all") works on: only the pairs whose lines that cost at most their caps at the
+    point make up at least min_matched of the template's line length compete for it, and a point where none does has NaN
+    and -1.  With return_matched the result is (scores, pairs, matched, grid), matched [ny, nx] float32 the winning pair's
+    share, NaN where there is none."""
     kind, tau = _penalty_args(penalty)
     fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
     if g[2] == 0 or g[3] == 0:
-        return _np.zeros((g[3], g[2]), dtype=_np.float32), _np.zeros((g[3], g[2]), dtype=_np.int32), g
-    scores, pairs = fm.best_map(tset, g, cs, pv, penalty=kind, tau=tau)
-    return scores, pairs, g
+        empty = (_np.zeros((g[3], g[2]), dtype=_np.float32), _np.zeros((g[3], g[2]), dtype=_np.int32))
+        return empty + ((_np.zeros((g[3], g[2]), dtype=_np.float32),) if return_matched else ()) + (g,)
+    if min_matched is None and not return_matched:
+        scores, pairs = fm.best_map(tset, g, cs, pv, penalty=kind, tau=tau)
+        return scores, pairs, g
+    return fm.best_map(tset, g, cs, pv, penalty=kind, tau=tau, min_matched=min_matched, matched=return_matched) + (g,)
 
 
 def exhaustive_detect(featuremap, templates, radius, stride=1, k=8, penalty=None, angles=None, pivot="center", window=None,
@@ -692,7 +700,7 @@ def exhaustive_detect_nms(featuremap, templates, overlap=0.3, stride=1, k=8, pen
 
 def exhaustive_detect_all(featuremap, templates, max_score, overlap=0.3, stride=1, max_detections=1024, penalty=None, angles=None,
                           pivot="center", window=None, line_caps=None, margin=0, return_boxes=False, min_matched=None,
-                          return_matched=False):
+                          return_matched=False, gate="winner"):
     """Every detection that matches at least as well as max_score: exhaustive_detect_nms' greedy rule on the points of
     best_score_map's plane whose score is <= max_score (>= 0 or inf), until they run out or max_detections (1 to 4096) is
     reached.  A scene with two parts gives two detections, not k records of which six are junk, and a bin of 200 small
@@ -702,8 +710,11 @@ def exhaustive_detect_all(featuremap, templates, max_score, overlap=0.3, stride=
     footprints.  min_matched (0 to 1): a point is dropped, before the greedy rule, unless the lines of its winning template
     that cost at most their caps there make up at least that share of the template's line length; a junk point then never
     suppresses a good neighbour.  Only the winning pair of a point is looked at.  return_matched: that share of every
-    detection as an (n,) float32 array, last in the returned tuple: (dets, matched) or (dets, boxes, matched).  The other
-    arguments are exhaustive_detect_nms'."""
+    detection as an (n,) float32 array, last in the returned tuple: (dets, matched) or (dets, boxes, matched).  gate="all"
+    puts min_matched inside the minimum instead: the pairs that fail it at a point do not compete for the point, so a wrong
+    view that wins a point on a few perfectly matched lines no longer deletes the right view under it (README, "Gate inside
+    the minimum").  The other arguments are exhaustive_detect_nms'."""
+    _engine.gate_kind(gate)
     kind, tau = _penalty_args(penalty)
     permille = int(round(1000 * float(overlap)))
     fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
@@ -713,7 +724,7 @@ def exhaustive_detect_all(featuremap, templates, max_score, overlap=0.3, stride=
         return res if len(res) > 1 else res[0]
     res = fm.exhaustive_detect_all(tset, g, cs, pv, max_score=max_score, max_detections=max_detections, overlap_permille=permille,
                                    margin=margin, penalty=kind, tau=tau, boxes=return_boxes, min_matched=min_matched,
-                                   matched=return_matched)
+                                   matched=return_matched, gate=gate)
     return (MatchList(res[0]),) + tuple(res[1:]) if return_boxes or return_matched else MatchList(res)
 
 
@@ -811,7 +822,7 @@ def pose_windows(records, coarse_angles, fine_angles, pivots, half_angles, half_
 
 def exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=0.3, angles=None, stride=1, max_detections=1024,
                               penalty=None, pivot="center", wrap=False, line_caps=None, margin=0, min_matched=None,
-                              return_boxes=False, return_matched=False, return_jobs=False):
+                              return_boxes=False, return_matched=False, return_jobs=False, gate="winner"):
     """exhaustive_detect_all over a job list in place of a dense grid: coarse-to-fine detection and tracking in one call.
     jobs are exhaustive_window_search's (n, 7) rows (tmpl, a0, na, x0, y0, nx, ny).  Each job gives its best pose, exactly
     its record of exhaustive_window_search(k=1); the score is divided as penalize(penalty, ...) divides it; a job stays when
@@ -823,8 +834,10 @@ def exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=0.
     around one object (neighbouring views in a tracker, overlapping boxes of coarse seeds, duplicates) end up as one
     detection.  Returns a MatchList in ascending score, then with return_boxes the (n, 4) int32 footprints, with
     return_matched the (n,) float32 matched fractions (matched_fractions of each detection's pose) and with return_jobs the
-    (n,) int32 index of the job each detection came from, in that order.  angles, pivot, wrap, stride and line_caps are
-    exhaustive_window_search's."""
+    (n,) int32 index of the job each detection came from, in that order.  gate="all": a job's best pose is the best among
+    its poses that pass min_matched, so a job whose overall best pose fails still gives the pose next to it that passes.
+    angles, pivot, wrap, stride and line_caps are exhaustive_window_search's."""
+    _engine.gate_kind(gate)
     kind, tau = _penalty_args(penalty)
     permille = int(round(1000 * float(overlap)))
     sx, sy = _strides(stride)
@@ -835,14 +848,14 @@ def exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=0.
         cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
     res = fm.exhaustive_detect_windows(tset, jobs, cs, pv, sx=sx, sy=sy, wrap=wrap, max_score=max_score, max_detections=max_detections,
                                        overlap_permille=permille, margin=margin, penalty=kind, tau=tau, min_matched=min_matched,
-                                       boxes=return_boxes, matched=return_matched, job_index=return_jobs)
+                                       boxes=return_boxes, matched=return_matched, job_index=return_jobs, gate=gate)
     return (MatchList(res[0]),) + tuple(res[1:]) if isinstance(res, tuple) else MatchList(res)
 
 
 def exhaustive_detect_refined(featuremap, templates, max_score, coarse_angles, fine_angles, coarse_stride, half_angles, half_x, half_y,
                               coarse_max_score=None, coarse_overlap=1.0, coarse_max_detections=1024, overlap=0.3, stride=1,
                               max_detections=1024, penalty=None, pivot="center", wrap=False, line_caps=None, margin=0,
-                              min_matched=None, return_boxes=False, return_matched=False, return_jobs=False):
+                              min_matched=None, return_boxes=False, return_matched=False, return_jobs=False, gate="winner"):
     """Every part in the frame to the fine table's angle step and `stride` pixels, without the dense fine search: pure
     Python over three calls, and by definition exactly their composition:
       seeds = exhaustive_detect_all(featuremap, templates, coarse_max_score (None: inf), overlap=coarse_overlap,
@@ -852,10 +865,12 @@ def exhaustive_detect_refined(featuremap, templates, max_score, coarse_angles, f
                           stride=stride, wrap=wrap)
       exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=overlap, angles=fine_angles, stride=stride,
                                 max_detections=max_detections, penalty=penalty, pivot=pivot, wrap=wrap, line_caps=line_caps,
-                                margin=margin, min_matched=min_matched, return_boxes=.., return_matched=.., return_jobs=..)
+                                margin=margin, min_matched=min_matched, return_boxes=.., return_matched=.., return_jobs=..,
+                                gate=gate)
     The coarse stage has no matched-fraction gate (a pose a few degrees off matches few lines) and by default neither a
     threshold nor suppression: its coarse_max_detections best grid points are the seeds, and the fine stage's rule reduces the
-    refined seeds of one object to one detection.  return_jobs indexes the seeds."""
+    refined seeds of one object to one detection.  return_jobs indexes the seeds.  gate applies to the fine stage only."""
+    _engine.gate_kind(gate)
     seeds = exhaustive_detect_all(featuremap, templates, float("inf") if coarse_max_score is None else coarse_max_score,
                                   overlap=coarse_overlap, stride=coarse_stride, max_detections=coarse_max_detections, penalty=penalty,
                                   angles=coarse_angles, pivot=pivot, line_caps=line_caps, margin=margin)
@@ -864,7 +879,7 @@ def exhaustive_detect_refined(featuremap, templates, max_score, coarse_angles, f
     return exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=overlap, angles=fine_angles, stride=stride,
                                      max_detections=max_detections, penalty=penalty, pivot=pivot, wrap=wrap, line_caps=line_caps,
                                      margin=margin, min_matched=min_matched, return_boxes=return_boxes,
-                                     return_matched=return_matched, return_jobs=return_jobs)
+                                     return_matched=return_matched, return_jobs=return_jobs, gate=gate)
 
 
 # ---------------------------------------------------------------- per-line caps and line costs (extension)

@@ -14,6 +14,7 @@ FDCM_OK = 0
 L2, L2_SQUARED, L1 = 0, 1, 2
 DEFAULT_OPTIMIZE, BATCH_OPTIMIZE, INDULGENT_OPTIMIZE = 0, 1, 2
 DEFAULT_PENALTY, EXPONENTIAL_PENALTY = 0, 1
+GATE_WINNER, GATE_ALL = 0, 1  # FDCM_GATE_WINNER, FDCM_GATE_ALL
 SHARDED_ALWAYS_COLLECTIVE = 1
 SHARDED_ALLOW_SAME_DEVICE = 2
 SHARD_TEMPLATES, SHARD_FRAMES = 0, 1
@@ -184,6 +185,15 @@ SYMBOLS = [
                                                        C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int,
                                                        C.c_float, C.c_float, C.c_int32, C.POINTER(_vp), _i64p, C.POINTER(C.c_int32),
                                                        _fp, C.POINTER(C.c_int32)]),
+    ("fdcm_best_map_gated", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int, C.c_float, C.c_float, _fp,
+                                     C.POINTER(C.c_int32), _fp]),
+    ("fdcm_search_exhaustive_detect_all_gated", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_float, C.c_int32,
+                                                         C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int32,
+                                                         C.POINTER(_vp), _i64p, C.POINTER(C.c_int32), _fp]),
+    ("fdcm_search_exhaustive_detect_windows_gated", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(PoseWindow), C.c_int64,
+                                                             C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
+                                                             C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int32,
+                                                             C.POINTER(_vp), _i64p, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32)]),
     ("fdcm_matched_fractions", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64, _fp]),
     ("fdcm_templates_matched_totals", C.c_int, [_vp, _fp]),
     ("fdcm_detect_score_bounds", C.c_int, [_vp, C.c_int, C.c_float, C.c_float, _fp]),

@@ -807,7 +807,21 @@ int fdcm_search_exhaustive_detect_windows(const fdcm_featuremap* fm, const fdcm_
                                           float max_score, int32_t max_detections, int32_t overlap_permille, int32_t margin, int penalty,
                                           float tau, float min_matched, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
                                           int32_t* boxes_out, float* matched_out, int32_t* jobs_out) {
+    return fdcm_search_exhaustive_detect_windows_gated(fm, templates, rot, jobs, n_jobs, sx, sy, wrap, max_score, max_detections,
+                                                       overlap_permille, margin, penalty, tau, min_matched, FDCM_GATE_WINNER,
+                                                       tmpl_index_base, out, n_out, boxes_out, matched_out, jobs_out);
+}
+
+// Gate inside the minimum: include/fdcm.h, "Gate inside the minimum".  The call above with the kind of gate, checked with the
+// other limits; FDCM_GATE_WINNER is the call above, the same driver with the same arguments.
+int fdcm_search_exhaustive_detect_windows_gated(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                                const fdcm_pose_window* jobs, int64_t n_jobs, int32_t sx, int32_t sy, int32_t wrap,
+                                                float max_score, int32_t max_detections, int32_t overlap_permille, int32_t margin,
+                                                int penalty, float tau, float min_matched, int gate, int32_t tmpl_index_base,
+                                                fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out,
+                                                int32_t* jobs_out) {
     return guarded([&] {
+        require(gate == FDCM_GATE_WINNER || gate == FDCM_GATE_ALL, "gate must be FDCM_GATE_WINNER or FDCM_GATE_ALL");
         require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
         require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
         require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
@@ -830,7 +844,7 @@ int fdcm_search_exhaustive_detect_windows(const fdcm_featuremap* fm, const fdcm_
         records_call(out, [&] {
             run_search_exhaustive_detect_windows(const_cast<fdcm_featuremap*>(fm), templates, rot, jobs, n_jobs, sx, sy,
                                                  max_score == 0.f ? 0.f : max_score, max_detections, overlap_permille, margin, penalty, tau,
-                                                 min_matched == 0.f ? 0.f : min_matched, tmpl_index_base, out, n_out, boxes_out,
+                                                 min_matched == 0.f ? 0.f : min_matched, gate, tmpl_index_base, out, n_out, boxes_out,
                                                  matched_out, jobs_out);
         });
     });
@@ -919,7 +933,18 @@ int fdcm_search_exhaustive_detect_all_matched(const fdcm_featuremap* fm, const f
                                               const fdcm_grid* grid, float max_score, int32_t max_detections, int32_t overlap_permille,
                                               int32_t margin, int penalty, float tau, float min_matched, int32_t tmpl_index_base,
                                               fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
+    return fdcm_search_exhaustive_detect_all_gated(fm, templates, rot, grid, max_score, max_detections, overlap_permille, margin, penalty,
+                                                   tau, min_matched, FDCM_GATE_WINNER, tmpl_index_base, out, n_out, boxes_out, matched_out);
+}
+
+// Gate inside the minimum: include/fdcm.h, "Gate inside the minimum".  The call above with the kind of gate, checked with the
+// other limits; FDCM_GATE_WINNER is the call above, the same driver with the same arguments.
+int fdcm_search_exhaustive_detect_all_gated(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                            const fdcm_grid* grid, float max_score, int32_t max_detections, int32_t overlap_permille,
+                                            int32_t margin, int penalty, float tau, float min_matched, int gate, int32_t tmpl_index_base,
+                                            fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
     return guarded([&] {
+        require(gate == FDCM_GATE_WINNER || gate == FDCM_GATE_ALL, "gate must be FDCM_GATE_WINNER or FDCM_GATE_ALL");
         require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
         require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
         require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
@@ -930,9 +955,21 @@ int fdcm_search_exhaustive_detect_all_matched(const fdcm_featuremap* fm, const f
         records_call(out, [&] {
             run_search_exhaustive_detect_all_matched(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid,
                                                      max_score == 0.f ? 0.f : max_score, max_detections, overlap_permille, margin, penalty,
-                                                     tau, min_matched == 0.f ? 0.f : min_matched, tmpl_index_base, out, n_out, boxes_out,
-                                                     matched_out);
+                                                     tau, min_matched == 0.f ? 0.f : min_matched, gate, tmpl_index_base, out, n_out,
+                                                     boxes_out, matched_out);
         });
+    });
+}
+
+int fdcm_best_map_gated(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot, const fdcm_grid* grid,
+                        int penalty, float tau, float min_matched, float* score_out_host, int32_t* pair_out_host,
+                        float* matched_out_host) {
+    return guarded([&] {
+        require(score_out_host || pair_out_host || matched_out_host, "score_out_host, pair_out_host and matched_out_host are all null");
+        require(min_matched >= 0.f && min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
+        check_best_args(fm, templates, rot, grid, penalty, tau);
+        run_best_map_gated(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, penalty, tau, min_matched == 0.f ? 0.f : min_matched,
+                           score_out_host, pair_out_host, matched_out_host);
     });
 }
 

@@ -8,7 +8,8 @@
 //                                     lane per 4 translations), then writes the scores (map), offers them to a running
 //                                     k-best list per wave and template kept in LDS (top-k), or keeps per point the smallest
 //                                     (normalised score, pair) key of the chunk and merges it into one plane of keys (best);
-//                                     kBestBound: best for the points at or below a score, with rows_score's early exit
+//                                     kBestBound: best for the points at or below a score, with rows_score's early exit;
+//                                     kBestGate, kBestBoundGate: both with the matched-fraction gate inside the minimum
 //   k_best_unpack, k_best_gather      best map: the key plane as row-major score and pair planes; the pairs of k points
 //   k_nms_round                       detections by footprint overlap: one round of the greedy rule on the key plane, the
 //                                     previous round's winner reduced from per-workgroup minima, its victims erased
@@ -19,17 +20,19 @@
 //   k_exhaustive_windows<BUF32>       pose windows: a wave takes a run of 4 x 16 patches of the clipped boxes of a batch's
 //                                     (job, rotation) planes, a lane per translation, and keeps a k-best list per job
 //   k_line_costs<BUF32>               line costs: a wave per pose, a lane per line of its template: the terms of the sum
-//   k_matched_gate<BUF32>, k_matched_list<BUF32>, k_matched_fractions<BUF32>
+//   k_matched_gate<BUF32>, k_matched_list<BUF32>, k_matched_fractions<BUF32>, k_matched_plane<BUF32>
 //                                     matched fraction: a thread per point of the key plane (the gate before the rounds of
-//                                     k_nms_round), per entry of the result list, per pose of a list; all three through
-//                                     matched_length<BUF32>, the one statement of the matched length
+//                                     k_nms_round), per entry of the result list, per pose of a list, per grid point (the
+//                                     gated best map's fractions); all through matched_length<BUF32>, the one statement of
+//                                     the matched length for a pose on its own
 //   k_window_winners<BUF32>, k_nms_list_round
 //                                     detections over pose windows: a thread per job turns the job's merged k = 1 list into
 //                                     its entry of the winners' list (normalised key, footprint), and one round of the greedy
 //                                     rule on that list, k_nms_round's scheme with a list in place of the key plane
 //
-// Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP, EXIT>, the one statement of the sum (4 rows per lane in
-// k_exhaustive, 1 in k_exhaustive_windows).  CAP: every term clamped to its line's cap (include/fdcm.h, "Per-line caps and
+// Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP, EXIT, GATE>, the one statement of the sum (4 rows per lane
+// in k_exhaustive, 1 in k_exhaustive_windows).  GATE: the matched length of every slot beside its sum, by matched_length's
+// rule (include/fdcm.h, "Gate inside the minimum").  CAP: every term clamped to its line's cap (include/fdcm.h, "Per-line caps and
 // line costs"); the kernels are instantiated both ways and a set without a finite cap launches the ones without the clamp,
 // which are the code they were before caps existed.  On the host every call prepares its templates through prepare_pairs: the
 // lines, bins and admissible box of (template, rotation) pairs, every pair of the set for the dense calls and the pairs a
@@ -63,7 +66,8 @@ struct ExLine {  // one template line: end points, the line's slice (bin * float
     float x1, y1, x2, y2;
     int se;
     float cap;  // +inf: none
-    int pad1, pad2;
+    float len;  // its template line's length (P.len's float): read by the gated forms of rows_score alone
+    int pad;
 };
 static_assert(sizeof(ExLine) == 32, "ExLine is 32 bytes");
 
@@ -73,6 +77,11 @@ __device__ __forceinline__ float line_term(float a, float b, float cap) {
     const float v = f_abs(a - b);
     return CAP && v > cap ? cap : v;
 }
+// The matched length after one more line (include/fdcm.h, "Gate inside the minimum"): matched_length's compare, on the
+// uncapped term, and its add.  A NaN term is not matched.
+__device__ __forceinline__ float line_matched(float ml, float a, float b, float cap, float len) {
+    return f_abs(a - b) <= cap ? ml + len : ml;
+}
 struct ExTmpl {    // one template of a launch
     int line0, n;  // its lines in the line array
     int i0, i1, j0, j1;  // grid indices of its admissible translations: [i0, i1] x [j0, j1] (empty when i0 > i1 or j0 > j1)
@@ -80,16 +89,32 @@ struct ExTmpl {    // one template of a launch
     unsigned koff;       // added to the grid index of its keys (a rotation's a * nx * ny; 0 otherwise); best map: the
                          // bits of the float32 its scores are divided by
 };
-enum ExMode { kMap = 0, kTopK = 1, kBest = 2, kBestBound = 3 };
-template <bool ON>
-struct ExBound {};  // k_exhaustive's last argument: nothing, or (kBestBound) the pairs' exit bounds and the threshold on q
+// kBestGate, kBestBoundGate: kBest and kBestBound with the matched-fraction gate inside the minimum ("Gate inside the minimum")
+enum ExMode { kMap = 0, kTopK = 1, kBest = 2, kBestBound = 3, kBestGate = 4, kBestBoundGate = 5 };
+constexpr bool ex_bound(int mode) { return mode == kBestBound || mode == kBestBoundGate; }
+constexpr bool ex_gate(int mode) { return mode == kBestGate || mode == kBestBoundGate; }
+// k_exhaustive's last argument: nothing, (BOUND) the pairs' exit bounds and the threshold on q, (GATE) the pairs' needs
+template <bool BOUND, bool GATE = false>
+struct ExBound {};
 template <>
-struct ExBound<true> {
+struct ExBound<true, false> {
     const float* bc;
     float max_score;
 };
-__device__ __forceinline__ bool under(float, const ExBound<false>&) { return true; }
-__device__ __forceinline__ bool under(float q, const ExBound<true>& b) { return q <= b.max_score; }
+template <>
+struct ExBound<false, true> {
+    const float* need;
+};
+template <>
+struct ExBound<true, true> {
+    const float* bc;
+    float max_score;
+    const float* need;
+};
+template <bool GATE>
+__device__ __forceinline__ bool under(float, const ExBound<false, GATE>&) { return true; }
+template <bool GATE>
+__device__ __forceinline__ bool under(float q, const ExBound<true, GATE>& b) { return q <= b.max_score; }
 
 // Best map: where the key of grid point (i, j) lies in the key plane.  The plane is kept in the order k_exhaustive walks
 // it, sub-tile by sub-tile and inside one [row group j / 16][wave][lane], so the 64 keys a wave merges at once are 512
@@ -167,10 +192,15 @@ __device__ __forceinline__ bool rows_over(const float (&p0)[ROWS][4], const floa
     return __ballot(live) == 0;
 }
 
-template <bool BUF32, int ROWS, bool CAP, bool EXIT = false>
+//
+// GATE (include/fdcm.h, "Gate inside the minimum"): beside the sum, ml[r] (zero on entry, as res) becomes ML of the slot, the
+// matched length by matched_length's rule: after the loads of a block, of the trailing packet and of each tail line the
+// lines are walked in line order, one line_matched each, so the float32 sum is sequential from +0 whatever the score's
+// own order.  The score's sum is untouched.  A wave that leaves through EXIT leaves ml without meaning, as res.
+template <bool BUF32, int ROWS, bool CAP, bool EXIT = false, bool GATE = false>
 __device__ __forceinline__ bool rows_score(const VolRef& V, const ExLine* __restrict__ Lt, int n, float offx, const float (&offy)[ROWS],
                                            int W, unsigned uH, size_t SL, float (&res)[ROWS], const bool* act = nullptr,
-                                           float bc = 0.f) {
+                                           float bc = 0.f, float* ml = nullptr) {
     const int aligned2 = (n / 8) * 8, aligned = (n / 4) * 4;
     float p0[ROWS][4], p1[ROWS][4];
 #pragma unroll
@@ -179,11 +209,12 @@ __device__ __forceinline__ bool rows_score(const VolRef& V, const ExLine* __rest
         for (int l = 0; l < 4; ++l) p0[r][l] = p1[r][l] = 0.f;
     bool gone = false;  // (EXIT) part of the loop's condition, so the loop keeps its one block and its one way out
     for (int b = 0; b < aligned2 && !(EXIT && gone); b += 8) {
-        float va[8][ROWS], vb[8][ROWS], cp[8];
+        float va[8][ROWS], vb[8][ROWS], cp[8], ll[GATE ? 8 : 1];
 #pragma unroll
         for (int l = 0; l < 8; ++l) {
             const ExLine ln = Lt[b + l];
             cp[l] = ln.cap;
+            if constexpr (GATE) ll[l] = ln.len;
             const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
             const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
 #pragma unroll
@@ -199,6 +230,12 @@ __device__ __forceinline__ bool rows_score(const VolRef& V, const ExLine* __rest
                 p0[r][l] = p0[r][l] + line_term<CAP>(va[l][r], vb[l][r], cp[l]);
                 p1[r][l] = p1[r][l] + line_term<CAP>(va[l + 4][r], vb[l + 4][r], cp[l + 4]);
             }
+        if constexpr (GATE) {
+#pragma unroll
+            for (int l = 0; l < 8; ++l)
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) ml[r] = line_matched(ml[r], va[l][r], vb[l][r], cp[l], ll[l]);
+        }
         if constexpr (EXIT) gone = b + 8 < n && rows_over<ROWS, true>(p0, p1, act, bc);
     }
     if (EXIT && gone) return true;
@@ -207,11 +244,12 @@ __device__ __forceinline__ bool rows_score(const VolRef& V, const ExLine* __rest
 #pragma unroll
         for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + p1[r][l];
     if (aligned > aligned2) {  // the trailing packet
-        float va[4][ROWS], vb[4][ROWS], cp[4];
+        float va[4][ROWS], vb[4][ROWS], cp[4], ll[GATE ? 4 : 1];
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
             const ExLine ln = Lt[aligned2 + l];
             cp[l] = ln.cap;
+            if constexpr (GATE) ll[l] = ln.len;
             const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
             const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
 #pragma unroll
@@ -224,6 +262,12 @@ __device__ __forceinline__ bool rows_score(const VolRef& V, const ExLine* __rest
         for (int r = 0; r < ROWS; ++r)
 #pragma unroll
             for (int l = 0; l < 4; ++l) p0[r][l] = p0[r][l] + line_term<CAP>(va[l][r], vb[l][r], cp[l]);
+        if constexpr (GATE) {
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) ml[r] = line_matched(ml[r], va[l][r], vb[l][r], cp[l], ll[l]);
+        }
         if constexpr (EXIT)
             if (aligned < n && rows_over<ROWS, false>(p0, p1, act, bc)) return true;
     }
@@ -235,8 +279,15 @@ __device__ __forceinline__ bool rows_score(const VolRef& V, const ExLine* __rest
         const size_t c1 = ex_column<BUF32>((int)(ln.x1 + offx), ln.se, W, uH, SL);
         const size_t c2 = ex_column<BUF32>((int)(ln.x2 + offx), ln.se, W, uH, SL);
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r)
-            res[r] = res[r] + line_term<CAP>(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH), ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH), ln.cap);
+        for (int r = 0; r < ROWS; ++r) {
+            if constexpr (GATE) {
+                const float a = ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH), b = ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH);
+                res[r] = res[r] + line_term<CAP>(a, b, ln.cap);
+                ml[r] = line_matched(ml[r], a, b, ln.cap, ln.len);
+            } else {
+                res[r] = res[r] + line_term<CAP>(ex_read<BUF32>(V, c1, (int)(ln.y1 + offy[r]), uH), ex_read<BUF32>(V, c2, (int)(ln.y2 + offy[r]), uH), ln.cap);
+            }
+        }
     }
     return false;
 }
@@ -244,15 +295,18 @@ __device__ __forceinline__ bool rows_score(const VolRef& V, const ExLine* __rest
 // MODE kBestBound (include/fdcm.h, "All detections below a score") is kBest with a threshold: a point's key enters the plane
 // only when q <= bound.max_score, and rows_score may abandon a template for the sub-tile (its EXIT) against bound.bc[slot],
 // the pair's bound.  The other modes take an empty argument in bound's place and are the code they were without it.
+// MODE kBestGate / kBestBoundGate (include/fdcm.h, "Gate inside the minimum"): kBest / kBestBound whose keys enter bk only when
+// the slot's ML, from rows_score's GATE, is >= bound.need[slot], the pair's need.  The exit stays as it is: a slot proved
+// over its score bound is no candidate under any gate.
 template <bool BUF32, int MODE, bool CAP>
 __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
                                                     float ty, const ExLine* __restrict__ lines, const ExTmpl* __restrict__ tm,
                                                     int T, int x0, int y0, int nx, int ny, int sx, int sy, int tiles_x,
                                                     int n_subtiles, int portions, int k, float* __restrict__ map,
                                                     long long plane, unsigned long long* __restrict__ cand,
-                                                    ExBound<MODE == kBestBound> bound) {
-    constexpr bool BOUND = MODE == kBestBound;
-    constexpr bool TOPK = MODE == kTopK, BEST = MODE == kBest || BOUND;
+                                                    ExBound<ex_bound(MODE), ex_gate(MODE)> bound) {
+    constexpr bool BOUND = ex_bound(MODE), GATE = ex_gate(MODE);
+    constexpr bool TOPK = MODE == kTopK, BEST = MODE == kBest || BOUND || GATE;
     __shared__ unsigned long long lists[TOPK ? 4 * kChunk * kMaxK : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // Workgroup b -> (portion, template chunk).  Workgroups are observed to be dealt round-robin over the 8 XCDs (b and
@@ -296,7 +350,12 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
                 offy[r] = ty + (float)(y0 + (act[r] ? j : P.j0) * sy);
             }
             float res[kRows] = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (BOUND) {  // (meets: a sub-tile that does not was skipped above)
+            float ml[GATE ? kRows : 1] = {};
+            if constexpr (BOUND && GATE) {
+                if (rows_score<BUF32, kRows, CAP, true, true>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res, act, bound.bc[P.slot], ml)) continue;
+            } else if constexpr (GATE) {
+                rows_score<BUF32, kRows, CAP, false, true>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res, nullptr, 0.f, ml);
+            } else if constexpr (BOUND) {  // (meets: a sub-tile that does not was skipped above)
                 if (rows_score<BUF32, kRows, CAP, true>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res, act, bound.bc[P.slot])) continue;
             } else {
                 if (meets) rows_score<BUF32, kRows, CAP>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
@@ -305,11 +364,14 @@ __global__ void __launch_bounds__(256) k_exhaustive(const float* __restrict__ vo
                 // q = score / the template's denominator, one IEEE division; pairkey = (bits of q << 32) | pair.  q >= +0
                 // or NaN, so the key order is (q, pair); a NaN q is no candidate
                 const float den = __uint_as_float(P.koff);
+                float need = 0.f;
+                if constexpr (GATE) need = bound.need[P.slot];
 #pragma unroll
                 for (int r = 0; r < kRows; ++r) {
                     const float q = res[r] / den;
-                    if (act[r] && !(q != q) && under(q, bound))
-                        bk[r] = min(bk[r], ((unsigned long long)__float_as_uint(q) << 32) | (unsigned)P.slot);
+                    bool cand_r = act[r] && !(q != q) && under(q, bound);
+                    if constexpr (GATE) cand_r = cand_r && ml[r] >= need;
+                    if (cand_r) bk[r] = min(bk[r], ((unsigned long long)__float_as_uint(q) << 32) | (unsigned)P.slot);
                 }
             } else if (!TOPK) {
                 if (i < nx) {
@@ -639,18 +701,20 @@ __global__ void __launch_bounds__(256) k_nms_round(unsigned long long* keys, lon
 // come through scalar loads.  A wave keeps the sorted k-best list of the job it is in (list_offer) and writes it when the
 // job changes: the waves that hold patches of job j are consecutive, wave0 .. wave0 + lists - 1, and wave w's list of job j
 // is candidate list list0 + (w - wave0), so k_exhaustive_merge_groups folds a job's lists as one group.
+// GATE (include/fdcm.h, "Gate inside the minimum"): a pose's key is offered to the list only when its ML, from rows_score's
+// GATE, is >= the plane's need: the job's winner is then the smallest key among the poses that pass.
 struct WinPlane {
     int line0, n;        // its lines in the line array
     int i0, i1, j0, j1;  // the admissible box clipped to the job's grid, in grid indices (never empty)
     int x0, y0, nx;      // the job's grid: origin and points per row
     unsigned koff;       // e * N_j, added to the grid index of its keys
     int job;             // the job's place in the batch
-    int pad;
+    float need;          // (GATE) need of its template
 };
 struct WinJob { int wave0, list0; };
 constexpr int kPatchX = 4, kPatchY = 16;
 
-template <bool BUF32, bool CAP>
+template <bool BUF32, bool CAP, bool GATE = false>
 __global__ void __launch_bounds__(256) k_exhaustive_windows(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
                                                             float ty, const ExLine* __restrict__ lines,
                                                             const WinPlane* __restrict__ planes, const int2* __restrict__ items,
@@ -682,8 +746,10 @@ __global__ void __launch_bounds__(256) k_exhaustive_windows(const float* __restr
         const float offx = tx + (float)(P.x0 + (act ? i : P.i0) * sx);  // translate(tmpl, sceneTranslation + translation)
         const float offy[1] = {ty + (float)(P.y0 + (act ? j : P.j0) * sy)};
         float res[1] = {0.f};
-        rows_score<BUF32, 1, CAP>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
-        const unsigned long long key = act && !(res[0] != res[0])  // a NaN score has no key
+        float ml[1] = {0.f};
+        if constexpr (GATE) rows_score<BUF32, 1, CAP, false, true>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res, nullptr, 0.f, ml);
+        else rows_score<BUF32, 1, CAP>(V, lines + P.line0, P.n, offx, offy, W, uH, SL, res);
+        const unsigned long long key = act && !(res[0] != res[0]) && (!GATE || ml[0] >= P.need)  // a NaN score has no key
                                            ? ((unsigned long long)__float_as_uint(res[0]) << 32) | ((unsigned)(j * P.nx + i) + P.koff)
                                            : kNoKey;
         thr = list_offer(e, key, thr, k, lane);
@@ -767,6 +833,27 @@ __global__ void __launch_bounds__(256) k_matched_gate(const float* __restrict__ 
     const float ml = matched_length<BUF32>(V, lines + line0, len + line0, n, tx + (float)(x0 + i * sx), ty + (float)(y0 + j * sy), W,
                                            (unsigned)H, SL);
     if (!(ml >= need[u])) keys[idx] = kNoKey;
+}
+
+// The fractions of the gated best map (include/fdcm.h, "Gate inside the minimum"): one thread per grid point, row-major.  A
+// point with a key writes frac of its pair there, ML / TL by matched_length; a point without one NaN.
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_matched_plane(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
+                                                       const ExLine* __restrict__ lines, const float* __restrict__ len,
+                                                       const ExTmpl* __restrict__ tm, const float* __restrict__ tl,
+                                                       const unsigned long long* __restrict__ keys, int x0, int y0, int sx, int sy, int nx,
+                                                       int ny, int tiles_x, float* __restrict__ frac) {
+    const int i = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63), j = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6);
+    if (i >= nx || j >= ny) return;
+    const unsigned long long v = keys[best_key_index(i, j, tiles_x)];
+    const long long g = (long long)j * nx + i;
+    if (v == kNoKey) { frac[g] = f_nan(); return; }
+    const int u = (int)(unsigned)v;
+    const int line0 = tm[u].line0, n = tm[u].n;
+    const VolRef V = make_volref(vol, SL, m, BUF32);
+    const float ml = matched_length<BUF32>(V, lines + line0, len + line0, n, tx + (float)(x0 + i * sx), ty + (float)(y0 + j * sy), W,
+                                           (unsigned)H, SL);
+    frac[g] = matched_fraction(ml, tl[u]);
 }
 
 // The fractions of the result list: entry l < k of best (a key (bits of q << 32) | g, kNoKey from the list's end on) with
@@ -975,10 +1062,10 @@ void check_grid(const fdcm_grid& g) {
 }
 
 // One line for the kernels: closestOrientation with the host libm (dt3cpu.cpp:144-148, as fdcm_seam.hip's run_evaluate).
-ExLine line_record(const fdcm_featuremap* fm, const float* p, float cap, bool buf32, size_t SL) {
+ExLine line_record(const fdcm_featuremap* fm, const float* p, float cap, float len, bool buf32, size_t SL) {
     const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
     const int bin = closest_orientation(fm->keys.data(), (int)fm->m, angle);
-    return ExLine{p[0], p[1], p[2], p[3], buf32 ? (int)((unsigned)bin * (unsigned)SL) : bin, cap, 0, 0};
+    return ExLine{p[0], p[1], p[2], p[3], buf32 ? (int)((unsigned)bin * (unsigned)SL) : bin, cap, len, 0};
 }
 
 void begin(fdcm_featuremap* fm) {
@@ -1146,7 +1233,8 @@ void prepare_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdc
                 W.box[u] = admissible_box(fm, src, l0, W.nl[u]);
                 for (int x = 0; x < W.nl[u] && fm->m > 0; ++x)  // (an empty map has no bins: no line is read there)
                     W.lines[(size_t)W.line0[u] + x] =
-                        line_record(fm, &src->lines[(size_t)(l0 + x) * 4], t->caps[(size_t)(t->offsets[(size_t)i] + x)], W.buf32, W.SL);
+                        line_record(fm, &src->lines[(size_t)(l0 + x) * 4], t->caps[(size_t)(t->offsets[(size_t)i] + x)],
+                                    t->lengths[(size_t)(t->offsets[(size_t)i] + x)], W.buf32, W.SL);
                 if (W.foot_margin >= 0) W.foot[u] = footprint(&src->lines[(size_t)l0 * 4], 4, W.nl[u], W.foot_margin);
             }
             p = q;
@@ -1216,7 +1304,8 @@ void emit_records(const std::vector<unsigned long long>& best, int k, const std:
 // d_bc (best map only, or null): the pairs' exit bounds, with max_score: k_exhaustive<., kBestBound, .> in place of kBest.
 template <int MODE>
 void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLine* d_lines, const ExTmpl* d_tm, int T, int k,
-            int portions, float* map, unsigned long long* cand, const float* d_bc = nullptr, float max_score = 0.f) {
+            int portions, float* map, unsigned long long* cand, const float* d_bc = nullptr, float max_score = 0.f,
+            const float* d_need = nullptr) {
     const int tiles_x = (g.nx + kTileX - 1) / kTileX, tiles_y = (g.ny + kTileY - 1) / kTileY;
     const int n_subtiles = tiles_x * tiles_y;
     const float* vol = fm->vol.as<float>();
@@ -1225,7 +1314,21 @@ void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLin
     for (int t0 = 0; t0 < T; t0 += per_launch) {
         const int nt = std::min(per_launch, T - t0);
         const dim3 grid((unsigned)(portions * ((nt + kChunk - 1) / kChunk)));  // portions: a multiple of 8
-        if constexpr (MODE == kBest)
+        if constexpr (MODE == kBest) {
+            if (d_need) {  // the gate inside the minimum (these forms always clamp too: caps of +inf change no term)
+                auto args = [&](auto kern, auto bound) {
+                    hipLaunchKernelGGL(kern, grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty,
+                                       d_lines, d_tm + t0, nt, g.x0, g.y0, g.nx, g.ny, g.sx, g.sy, tiles_x, n_subtiles, portions, k, map,
+                                       plane, cand, bound);
+                };
+                if (d_bc)
+                    args(P.buf32 ? k_exhaustive<true, kBestBoundGate, true> : k_exhaustive<false, kBestBoundGate, true>,
+                         ExBound<true, true>{d_bc, max_score, d_need});
+                else
+                    args(P.buf32 ? k_exhaustive<true, kBestGate, true> : k_exhaustive<false, kBestGate, true>, ExBound<false, true>{d_need});
+                FDCM_HIP(hipGetLastError());
+                continue;
+            }
             if (d_bc) {
                 // (the 64-bit form always clamps: caps of +inf change no term, and without the clamp that form takes 130
                 // registers, a wave per SIMD fewer than the best map's -- DESIGN.md section 20)
@@ -1237,6 +1340,7 @@ void launch(fdcm_featuremap* fm, const Pairs& P, const fdcm_grid& g, const ExLin
                 FDCM_HIP(hipGetLastError());
                 continue;
             }
+        }
         auto kern = P.capped ? (P.buf32 ? k_exhaustive<true, MODE, true> : k_exhaustive<false, MODE, true>)
                              : (P.buf32 ? k_exhaustive<true, MODE, false> : k_exhaustive<false, MODE, false>);
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, fm->stream, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty, d_lines,
@@ -1520,8 +1624,9 @@ constexpr size_t kNmsPartialBytes = 2 * kNmsWorkgroups * (8 + 4);  // two sets o
 // list: the entries of the result list and of its pairs.  max_score (or null): only the points with q <= *max_score get a
 // key (k_exhaustive<., kBestBound, .>); the exit bound of every pair goes up with the same upload.  mt (or null; include/fdcm.h,
 // "Detections by matched fraction"): P.len, and per pair the gate's need and the template's TL, whichever is given, go up
-// with the same upload too, and the list gets a float per entry for its fractions.
-struct MatchedIn { const float* need; const float* tl; };  // one float per pair each, or null
+// with the same upload too, and the list gets a float per entry for its fractions.  gate_all ("Gate inside the minimum"): the
+// needs go to the scoring kernel, its gated form; else they wait for k_matched_gate.
+struct MatchedIn { const float* need; const float* tl; bool gate_all = false; };  // one float per pair each, or null
 
 bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau, int k,
                BestRun& R, const std::vector<Foot>* foot = nullptr, int list = kMaxK, const float* max_score = nullptr,
@@ -1578,7 +1683,8 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
     FDCM_HIP(hipMemcpyAsync(d, h, R.o_pair, hipMemcpyHostToDevice, st));
     FDCM_HIP(hipMemsetAsync(d + R.o_keys, 0xff, n_keys * 8, st));  // no key anywhere
     launch<kBest>(fm, P, g, (const ExLine*)d, (const ExTmpl*)(d + o_tm), (int)np, 0, portions_for(fm, g, (int)np), nullptr,
-                  (unsigned long long*)(d + R.o_keys), max_score ? (const float*)(d + R.o_bc) : nullptr, max_score ? *max_score : 0.f);
+                  (unsigned long long*)(d + R.o_keys), max_score ? (const float*)(d + R.o_bc) : nullptr, max_score ? *max_score : 0.f,
+                  mt && mt->need && mt->gate_all ? (const float*)(d + R.o_need) : nullptr);
     return true;
 }
 
@@ -1661,6 +1767,7 @@ constexpr size_t kWinStageBytes = (size_t)256 << 20;  // what one upload holds, 
 struct WinnersIn {
     const float* den;          // per template: the denominator of q
     const float* need;         // per template: the gate's need, or null without a gate
+    bool gate_all;             // the gate inside the minimum (k_exhaustive_windows' GATE); else k_window_winners applies it
     int margin;                // of the footprints
     float max_score;
     unsigned long long* keys;  // per job of the call, on the host: (bits of q << 32) | job, or kNoKey
@@ -1675,7 +1782,8 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
                    bool flat, const WinnersIn* wn = nullptr) {
     const int n = rot ? rot->n : 1;
     Pairs W;
-    W.lens = wn && wn->need;
+    const bool gate_all = wn && wn->need && wn->gate_all;
+    W.lens = wn && wn->need && !gate_all;
     if (wn) W.foot_margin = wn->margin;
     for (int64_t j = j0; j < j1; ++j)
         for (int e = 0; e < jobs[j].na; ++e) W.key.push_back((int64_t)jobs[j].tmpl * n + (jobs[j].a0 + e) % n);
@@ -1729,7 +1837,8 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
             if (wn) wrun.push_back((int)u);
             if (rot) Mjob[(size_t)(m0[(size_t)j] + e)] = W.M[u];
             if (W.nl[u] == 0 || !W.box[u].any) continue;  // a template without lines gives nothing
-            WinPlane P{W.line0[u], W.nl[u], 0, -1, 0, -1, J.x0, J.y0, J.nx, (unsigned)((long long)e * J.nx * J.ny), 0, 0};
+            WinPlane P{W.line0[u], W.nl[u], 0, -1, 0, -1, J.x0, J.y0, J.nx, (unsigned)((long long)e * J.nx * J.ny), 0,
+                       gate_all ? wn->need[(size_t)J.tmpl] : 0.f};
             grid_range(W.box[u].x0, W.box[u].x1, J.x0, J.nx, sx, P.i0, P.i1);
             grid_range(W.box[u].y0, W.box[u].y1, J.y0, J.ny, sy, P.j0, P.j1);
             if (P.i0 > P.i1 || P.j0 > P.j1) continue;
@@ -1759,11 +1868,11 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     // jobs' grids and runs go up with the rest; the round's part of the list follows the candidate lists on the device.
     const size_t np = W.nl.size();
     std::vector<ExTmpl> wtm(wn ? np : 0);
-    std::vector<float> wneed(wn && wn->need ? np : 0);
+    std::vector<float> wneed(wn && wn->need && !gate_all ? np : 0);
     for (size_t u = 0; u < wtm.size(); ++u) {
         const size_t tmpl = (size_t)(W.key[u] / n);
         wtm[u] = ExTmpl{W.line0[u], W.nl[u], 0, -1, 0, -1, 0, bits_from_f(wn->den[tmpl])};
-        if (wn->need) wneed[u] = wn->need[tmpl];
+        if (!wneed.empty()) wneed[u] = wn->need[tmpl];
     }
     const size_t o_pl = al256(W.lines.size() * sizeof(ExLine)), o_it = o_pl + al256(planes.size() * sizeof(WinPlane)),
                  o_jt = o_it + al256(items.size() * sizeof(int2)), o_seg = o_jt + al256(jtab.size() * sizeof(WinJob)),
@@ -1796,8 +1905,10 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     unsigned long long* d_best = (unsigned long long*)(d + o_best);
     const float* vol = fm->vol.as<float>();
     for (const Batch& B : batches) {
-        auto kern = W.capped ? (W.buf32 ? k_exhaustive_windows<true, true> : k_exhaustive_windows<false, true>)
-                             : (W.buf32 ? k_exhaustive_windows<true, false> : k_exhaustive_windows<false, false>);
+        // (the gated form always clamps: caps of +inf change no term)
+        auto kern = gate_all ? (W.buf32 ? k_exhaustive_windows<true, true, true> : k_exhaustive_windows<false, true, true>)
+                    : W.capped ? (W.buf32 ? k_exhaustive_windows<true, true> : k_exhaustive_windows<false, true>)
+                               : (W.buf32 ? k_exhaustive_windows<true, false> : k_exhaustive_windows<false, false>);
         hipLaunchKernelGGL(kern, dim3((unsigned)((B.waves + 3) / 4)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
                            fm->ty, (const ExLine*)d, (const WinPlane*)(d + o_pl) + B.p0, (const int2*)(d + o_it) + B.i0,
                            (const WinJob*)(d + o_jt) + B.b0, B.items, B.ipw, sx, sy, k, cand);
@@ -1810,7 +1921,7 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
         auto kern = W.buf32 ? k_window_winners<true> : k_window_winners<false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
                            fm->ty, (const ExLine*)d, (const float*)(d + o_wlen), (const ExTmpl*)(d + o_wtm), (const int4*)(d + o_wfoot),
-                           wn->need ? (const float*)(d + o_wneed) : (const float*)nullptr, (const WinnerJob*)(d + o_wjob),
+                           wneed.empty() ? (const float*)nullptr : (const float*)(d + o_wneed), (const WinnerJob*)(d + o_wjob),
                            (const int*)(d + o_wrun), (const unsigned long long*)d_best, (int)nj, (unsigned)j0, sx, sy, wn->max_score,
                            (unsigned long long*)(d + o_wkeys), (int4*)(d + o_wboxes));
         FDCM_HIP(hipGetLastError());
@@ -1953,6 +2064,63 @@ void run_best_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotat
     FDCM_HIP(hipStreamSynchronize(st));
 }
 
+// Gated best map (include/fdcm.h, "Gate inside the minimum"): run_best_map with the needs in the scoring kernel (none at
+// min_matched = 0: the best map's own kernel) and a third plane, the fractions of the points' pairs (k_matched_plane).  The
+// 64-bit form follows FDCM_MATCHED_FLAT, as the calls by matched fraction.
+void run_best_map_gated(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty, float tau,
+                        float min_matched, float* score_out, int32_t* pair_out, float* matched_out) {
+    check_grid(g);
+    const size_t N = (size_t)g.nx * g.ny;
+    auto none = [&]() {
+        if (score_out) std::fill(score_out, score_out + N, f_nan());
+        if (pair_out) std::fill(pair_out, pair_out + N, (int32_t)-1);
+        if (matched_out) std::fill(matched_out, matched_out + N, f_nan());
+    };
+    if (t->T == 0) return none();
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int n = rot ? rot->n : 1;
+    if (rot) check_rotated_size(t, n);
+    const bool gate = min_matched > 0.f;
+    Pairs P;
+    P.lens = matched_out != nullptr;
+    prepare_pairs(fm, t, rot, test_switches().matched_flat, P);
+    std::vector<float> need, tl;
+    if (gate || matched_out) {  // per pair, as detect_all's
+        std::vector<float> totals((size_t)t->T);
+        templates_matched_totals(t, totals.data());
+        tl.resize(P.nl.size());
+        for (size_t u = 0; u < tl.size(); ++u) tl[u] = totals[u / (size_t)n];
+        if (gate) {
+            need.resize(tl.size());
+            for (size_t u = 0; u < tl.size(); ++u) need[u] = min_matched * tl[u];
+        }
+    }
+    const MatchedIn mt{gate ? need.data() : nullptr, matched_out ? tl.data() : nullptr, true};
+    BestRun R;
+    if (!best_keys(fm, P, t, n, g, penalty, tau, 0, R, nullptr, kMaxK, nullptr, gate || matched_out ? &mt : nullptr)) return none();
+    hipStream_t st = fm->stream;
+    char* plane = R.d + R.o_plane;  // one 4-byte plane: the scores, then the pairs, then the fractions
+    if (score_out) {
+        best_unpack(fm, R, g, (float*)plane, nullptr);
+        FDCM_HIP(hipMemcpyAsync(score_out, plane, N * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (pair_out) {
+        best_unpack(fm, R, g, nullptr, (int*)plane);
+        FDCM_HIP(hipMemcpyAsync(pair_out, plane, N * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (matched_out) {
+        auto kern = P.buf32 ? k_matched_plane<true> : k_matched_plane<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4)), dim3(256), 0, st, fm->vol.as<float>(), P.SL,
+                           (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty, (const ExLine*)R.d, (const float*)(R.d + R.o_len),
+                           (const ExTmpl*)(R.d + R.o_tm), (const float*)(R.d + R.o_tl), (const unsigned long long*)(R.d + R.o_keys), g.x0,
+                           g.y0, g.sx, g.sy, g.nx, g.ny, R.tiles_x, (float*)plane);
+        FDCM_HIP(hipGetLastError());
+        FDCM_HIP(hipMemcpyAsync(matched_out, plane, N * 4, hipMemcpyDeviceToHost, st));
+    }
+    FDCM_HIP(hipStreamSynchronize(st));
+}
+
 void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
                                   int rx, int ry, int penalty, float tau, int32_t base, fdcm_match** out, int64_t* n_out) {
     check_grid(g);
@@ -2069,8 +2237,8 @@ void templates_matched_totals(const fdcm_templates* t, float* totals) {
 // with min_matched > 0, the gate pass over the key plane before the first round and, with matched_out, the fractions of the
 // result list after the last; min_matched = 0 and no matched_out queue what the other call queues.
 static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, float max_score,
-                       int max_det, int permille, int margin, int penalty, float tau, bool matched, float min_matched, int32_t base,
-                       fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
+                       int max_det, int permille, int margin, int penalty, float tau, bool matched, float min_matched, int gate_kind,
+                       int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
     check_grid(g);
     *n_out = 0;
     if (t->T == 0) return;
@@ -2097,7 +2265,8 @@ static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
             for (size_t u = 0; u < tl.size(); ++u) need[u] = min_matched * tl[u];
         }
     }
-    const MatchedIn mt{gate ? need.data() : nullptr, fracs ? tl.data() : nullptr};
+    const bool gate_all = gate && gate_kind == FDCM_GATE_ALL;  // the gate inside the minimum: no gate pass
+    const MatchedIn mt{gate ? need.data() : nullptr, fracs ? tl.data() : nullptr, gate_all};
     BestRun R;
     // (+inf is no threshold: the plane is the best map's own, by the kernel without the checks)
     if (!best_keys(fm, P, t, n, g, penalty, tau, 0, R, &foot, max_det, max_score < f_inf() ? &max_score : nullptr,
@@ -2106,7 +2275,7 @@ static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
     hipStream_t st = fm->stream;
     char* d = R.d;
     const float* vol = fm->vol.as<float>();
-    if (gate) {
+    if (gate && !gate_all) {
         auto kern = P.buf32 ? k_matched_gate<true> : k_matched_gate<false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)(R.n_keys / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
                            fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
@@ -2149,14 +2318,15 @@ static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
 void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                       float max_score, int max_det, int permille, int margin, int penalty, float tau, int32_t base,
                                       fdcm_match** out, int64_t* n_out, int32_t* boxes_out) {
-    detect_all(fm, t, rot, g, max_score, max_det, permille, margin, penalty, tau, false, 0.f, base, out, n_out, boxes_out, nullptr);
+    detect_all(fm, t, rot, g, max_score, max_det, permille, margin, penalty, tau, false, 0.f, FDCM_GATE_WINNER, base, out, n_out,
+               boxes_out, nullptr);
 }
 
 void run_search_exhaustive_detect_all_matched(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                               float max_score, int max_det, int permille, int margin, int penalty, float tau,
-                                              float min_matched, int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out,
-                                              float* matched_out) {
-    detect_all(fm, t, rot, g, max_score, max_det, permille, margin, penalty, tau, true, min_matched, base, out, n_out, boxes_out,
+                                              float min_matched, int gate, int32_t base, fdcm_match** out, int64_t* n_out,
+                                              int32_t* boxes_out, float* matched_out) {
+    detect_all(fm, t, rot, g, max_score, max_det, permille, margin, penalty, tau, true, min_matched, gate, base, out, n_out, boxes_out,
                matched_out);
 }
 
@@ -2236,10 +2406,11 @@ static void matched_fractions_rounds(fdcm_featuremap* fm, const fdcm_templates* 
 // the winners' list on the host, a key and a footprint per job, which goes up whole for the rounds of k_nms_list_round,
 // queued kNmsBatch at a time as detect_all queues k_nms_round's.  A record is emit_records' for the key (bits of q << 32) |
 // (e N_j + g) of its job's winner; its box is the list's; its fraction k_matched_fractions' at the record's pose, in a
-// round of its own after the last launch.  The 64-bit form follows FDCM_WINDOWS_FLAT and FDCM_MATCHED_FLAT.
+// round of its own after the last launch.  The 64-bit form follows FDCM_WINDOWS_FLAT and FDCM_MATCHED_FLAT.  gate
+// FDCM_GATE_ALL ("Gate inside the minimum") with min_matched > 0: the scoring kernel's gated form, and the winners' pass without need.
 void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot,
                                           const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, float max_score, int max_det,
-                                          int permille, int margin, int penalty, float tau, float min_matched, int32_t base,
+                                          int permille, int margin, int penalty, float tau, float min_matched, int gate, int32_t base,
                                           fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out, int32_t* jobs_out) {
     *n_out = 0;
     if (n_jobs == 0 || t->T == 0) return;
@@ -2260,7 +2431,8 @@ void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templa
         need.resize(totals.size());
         for (size_t i = 0; i < need.size(); ++i) need[i] = min_matched * totals[i];
     }
-    const WinnersIn wn{den.data(), need.empty() ? nullptr : need.data(), margin, max_score, keys.data(), boxes.data()};
+    const WinnersIn wn{den.data(), need.empty() ? nullptr : need.data(), gate == FDCM_GATE_ALL, margin, max_score, keys.data(),
+                       boxes.data()};
     const bool flat = test_switches().windows_flat || test_switches().matched_flat;
     for (int64_t j0 = 0; j0 < n_jobs;) {
         const int64_t j1 = windows_round_end(t, jobs, j0, n_jobs, 1, true);

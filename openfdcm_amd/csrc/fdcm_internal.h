@@ -39,8 +39,9 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              and 4 KB of tables per such plane a round, instead of 256 MB (run_search_exhaustive_windows)
 //   FDCM_WINDOWS_FLAT          the pose-window search with 64-bit flat addresses (windows_round), the scoring and the winners'
 //                              pass of the detections over pose windows with it
-//   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (detect_all, run_matched_fractions,
-//                              run_search_exhaustive_detect_windows: its scoring, its winners' pass and its fractions)
+//   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (detect_all, run_best_map_gated,
+//                              run_matched_fractions, run_search_exhaustive_detect_windows: its scoring, its winners' pass and
+//                              its fractions)
 //   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
 //                              takes that form for a volume of 4 GB or more alone (score maps, top-k, peaks, rotations, best
 //                              map, the detections, line costs); the pose windows and the calls by matched fraction keep
@@ -385,11 +386,14 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
 void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                       float max_score, int max_det, int permille, int margin, int penalty, float tau, int32_t base,
                                       fdcm_match** out, int64_t* n_out, int32_t* boxes_out);
-// detect_all with the gate by matched fraction; matched_out: max_det floats, or null
+// detect_all with the gate by matched fraction (gate: FDCM_GATE_WINNER or FDCM_GATE_ALL); matched_out: max_det floats, or null
 void run_search_exhaustive_detect_all_matched(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                               float max_score, int max_det, int permille, int margin, int penalty, float tau,
-                                              float min_matched, int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out,
-                                              float* matched_out);
+                                              float min_matched, int gate, int32_t base, fdcm_match** out, int64_t* n_out,
+                                              int32_t* boxes_out, float* matched_out);
+// the best map with the gate inside the minimum (include/fdcm.h, "Gate inside the minimum"): any output may be null
+void run_best_map_gated(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty, float tau,
+                        float min_matched, float* score_out, int32_t* pair_out, float* matched_out);
 // poses as run_line_costs'; fractions: n floats
 void run_matched_fractions(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                            float* fractions);
@@ -406,7 +410,7 @@ void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t,
 // detections over pose windows (include/fdcm.h): boxes_out, matched_out (max_det entries each) and jobs_out may be null
 void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot,
                                           const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, float max_score, int max_det,
-                                          int permille, int margin, int penalty, float tau, float min_matched, int32_t base,
+                                          int permille, int margin, int penalty, float tau, float min_matched, int gate, int32_t base,
                                           fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out, int32_t* jobs_out);
 // poses: n x (tmpl, a, x, y), checked; *costs is malloc'ed; offsets: n + 1
 void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,

@@ -34,6 +34,15 @@ def _rotations(cs, pivots, T):
     return rot, keep
 
 
+def gate_kind(gate):
+    """FDCM_GATE_WINNER / FDCM_GATE_ALL (include/fdcm.h, "Gate inside the minimum") for gate = "winner" / "all"."""
+    if gate == "winner":
+        return capi.GATE_WINNER
+    if gate == "all":
+        return capi.GATE_ALL
+    raise ValueError('gate must be "winner" or "all"')
+
+
 def as_grid(grid):
     """capi.Grid from a capi.Grid or an (x0, y0, nx, ny, sx, sy) sequence."""
     if isinstance(grid, capi.Grid):
@@ -366,12 +375,14 @@ class DeviceFeatureMap:
 
     def exhaustive_detect_windows(self, templates, jobs, cs=None, pivots=None, sx=1, sy=1, wrap=False, max_score=float("inf"),
                                   max_detections=1024, overlap_permille=300, margin=0, penalty=None, tau=1.0, min_matched=None,
-                                  tmpl_index_base=0, boxes=False, matched=False, job_index=False):
+                                  tmpl_index_base=0, boxes=False, matched=False, job_index=False, gate="winner"):
         """Detections over pose windows (include/fdcm.h): every job of exhaustive_window_search gives its best pose (k = 1);
         the best poses, normalised by the penalty, at most max_score and with at least min_matched of their line length
         matched, go through exhaustive_detect_all's greedy rule by footprint overlap, keyed by (score, job).  Raw match
         records in ascending order; with boxes the (n, 4) int32 footprints, with matched the (n,) float32 fractions, with
-        job_index the (n,) int32 job of each record, in that order."""
+        job_index the (n,) int32 job of each record, in that order.  gate "all" ("Gate inside the minimum"): a job's best pose
+        is the best among its poses that pass min_matched, not the best pose whatever it matches."""
+        kind = gate_kind(gate)
         jobs = as_pose_windows(jobs)
         rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
         out, n = C.c_void_p(), C.c_int64()
@@ -379,25 +390,38 @@ class DeviceFeatureMap:
         fp = np.zeros((md, 4), dtype=np.int32)
         fr = np.zeros(md, dtype=np.float32)
         ji = np.zeros(md, dtype=np.int32)
-        capi.check(capi.lib().fdcm_search_exhaustive_detect_windows(
-            self._h, templates._h, C.byref(rot) if rot is not None else None, jobs.ctypes.data_as(C.POINTER(capi.PoseWindow)),
-            jobs.shape[0], int(sx), int(sy), int(bool(wrap)), float(max_score), int(max_detections), int(overlap_permille),
-            int(margin), -1 if penalty is None else int(penalty), float(tau), 0.0 if min_matched is None else float(min_matched),
-            int(tmpl_index_base), C.byref(out), C.byref(n), fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None,
-            capi.fptr(fr) if matched and md else None, ji.ctypes.data_as(C.POINTER(C.c_int32)) if job_index and md else None))
+        head = (self._h, templates._h, C.byref(rot) if rot is not None else None, jobs.ctypes.data_as(C.POINTER(capi.PoseWindow)),
+                jobs.shape[0], int(sx), int(sy), int(bool(wrap)), float(max_score), int(max_detections), int(overlap_permille),
+                int(margin), -1 if penalty is None else int(penalty), float(tau), 0.0 if min_matched is None else float(min_matched))
+        tail = (int(tmpl_index_base), C.byref(out), C.byref(n), fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None,
+                capi.fptr(fr) if matched and md else None, ji.ctypes.data_as(C.POINTER(C.c_int32)) if job_index and md else None)
+        if kind == capi.GATE_WINNER:
+            capi.check(capi.lib().fdcm_search_exhaustive_detect_windows(*head, *tail))
+        else:
+            capi.check(capi.lib().fdcm_search_exhaustive_detect_windows_gated(*head, kind, *tail))
         res = (_adopt_matches(out, n.value),) + ((fp[:n.value].copy(),) if boxes else ()) + ((fr[:n.value].copy(),) if matched else ())
         res += (ji[:n.value].copy(),) if job_index else ()
         return res if len(res) > 1 else res[0]
 
     # ---- best map and detections (include/fdcm.h, "Best map and detections"): cs None is the translations alone
-    def best_map(self, templates, grid, cs=None, pivots=None, penalty=None, tau=1.0):
+    def best_map(self, templates, grid, cs=None, pivots=None, penalty=None, tau=1.0, min_matched=None, matched=False):
         """(scores, pairs): per grid point the lowest length-normalised score over all templates with lines and all
         rotations, (ny, nx) float32 with NaN where no pair is admissible, and the pair t * n + a that gave it, (ny, nx)
-        int32 with -1 there.  penalty: None, capi.DEFAULT_PENALTY or capi.EXPONENTIAL_PENALTY (with tau)."""
+        int32 with -1 there.  penalty: None, capi.DEFAULT_PENALTY or capi.EXPONENTIAL_PENALTY (with tau).  min_matched (0 to 1)
+        or matched: the gated best map (include/fdcm.h, "Gate inside the minimum"): only pairs with at least min_matched of
+        their line length matched at the point compete, and with matched the (ny, nx) float32 fractions of the winning
+        pairs, NaN where there is none, come last: (scores, pairs, fractions)."""
         rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
         g = as_grid(grid)
         scores = np.empty((g.ny, g.nx), dtype=np.float32)
         pairs = np.empty((g.ny, g.nx), dtype=np.int32)
+        if min_matched is not None or matched:
+            frac = np.empty((g.ny, g.nx), dtype=np.float32)
+            capi.check(capi.lib().fdcm_best_map_gated(
+                self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), -1 if penalty is None else int(penalty),
+                float(tau), 0.0 if min_matched is None else float(min_matched), capi.fptr(scores),
+                pairs.ctypes.data_as(C.POINTER(C.c_int32)), capi.fptr(frac) if matched else None))
+            return (scores, pairs, frac) if matched else (scores, pairs)
         capi.check(capi.lib().fdcm_best_map(self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g),
                                             -1 if penalty is None else int(penalty), float(tau), capi.fptr(scores),
                                             pairs.ctypes.data_as(C.POINTER(C.c_int32))))
@@ -434,13 +458,15 @@ class DeviceFeatureMap:
 
     def exhaustive_detect_all(self, templates, grid, cs=None, pivots=None, max_score=float("inf"), max_detections=1024,
                               overlap_permille=300, margin=0, penalty=None, tau=1.0, tmpl_index_base=0, boxes=False,
-                              min_matched=None, matched=False):
+                              min_matched=None, matched=False, gate="winner"):
         """All detections below a score (include/fdcm.h): exhaustive_detect_nms' greedy rule on the points whose normalised
         score is at most max_score, until they run out or max_detections (1 to 4096) is reached.  Raw match records in
         ascending order; with boxes also the (n, 4) int32 footprints.  min_matched (0 to 1) or matched: the call by matched
         fraction (include/fdcm.h, "Detections by matched fraction"): points whose best pair has less than min_matched of its
         line length matched are dropped before the greedy rule, and with matched the (n,) float32 fractions of the records
-        come last in the returned tuple."""
+        come last in the returned tuple.  gate "all" ("Gate inside the minimum"): a point's best pair is the best among its
+        pairs that pass min_matched there, and no point is dropped afterwards."""
+        kind = gate_kind(gate)
         rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
         g = as_grid(grid)
         out, n = C.c_void_p(), C.c_int64()
@@ -455,11 +481,14 @@ class DeviceFeatureMap:
             rec = _adopt_matches(out, n.value)
             return (rec, fp[:n.value].copy()) if boxes else rec
         fr = np.zeros(md, dtype=np.float32)
-        capi.check(capi.lib().fdcm_search_exhaustive_detect_all_matched(
-            self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), float(max_score), int(max_detections),
-            int(overlap_permille), int(margin), -1 if penalty is None else int(penalty), float(tau),
-            0.0 if min_matched is None else float(min_matched), int(tmpl_index_base), C.byref(out), C.byref(n), fp_arg,
-            capi.fptr(fr) if matched and fr.size else None))
+        head = (self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), float(max_score), int(max_detections),
+                int(overlap_permille), int(margin), -1 if penalty is None else int(penalty), float(tau),
+                0.0 if min_matched is None else float(min_matched))
+        tail = (int(tmpl_index_base), C.byref(out), C.byref(n), fp_arg, capi.fptr(fr) if matched and fr.size else None)
+        if kind == capi.GATE_WINNER:
+            capi.check(capi.lib().fdcm_search_exhaustive_detect_all_matched(*head, *tail))
+        else:
+            capi.check(capi.lib().fdcm_search_exhaustive_detect_all_gated(*head, kind, *tail))
         res = (_adopt_matches(out, n.value),) + ((fp[:n.value].copy(),) if boxes else ()) + ((fr[:n.value].copy(),) if matched else ())
         return res if len(res) > 1 else res[0]
 

@@ -32,7 +32,8 @@ COVERED = {
     "fdcm_score_map", "fdcm_score_map_rotations", "fdcm_search_exhaustive", "fdcm_search_exhaustive_peaks",
     "fdcm_search_exhaustive_rotations", "fdcm_best_map", "fdcm_search_exhaustive_detect", "fdcm_search_exhaustive_detect_nms",
     "fdcm_search_exhaustive_detect_all", "fdcm_search_exhaustive_detect_all_matched", "fdcm_search_exhaustive_windows",
-    "fdcm_search_exhaustive_detect_windows", "fdcm_line_costs", "fdcm_matched_fractions",
+    "fdcm_search_exhaustive_detect_windows", "fdcm_line_costs", "fdcm_matched_fractions", "fdcm_best_map_gated",
+    "fdcm_search_exhaustive_detect_all_gated", "fdcm_search_exhaustive_detect_windows_gated",
 }
 EXEMPT = {
     "fdcm_score_map_device": "fdcm_score_map's driver and workspace layout with the planes in the caller's device memory, which is "
@@ -215,6 +216,27 @@ def _detect_all_matched(x, note):
     return out
 
 
+def _gate_all(x, note):
+    """The gate inside the minimum (include/fdcm.h): the gated best map, the dense call with and without a threshold and the
+    windows' call, all at FDCM_GATE_ALL."""
+    out = []
+    jobs = x.c["jobs"]
+    for s in x.sets:
+        for cs, pv in x.rots():
+            g = x.small[0]
+            out += list(x.dev.best_map(s, g, cs, pv, penalty=DEFAULT, min_matched=0.4, matched=True))
+            for max_score in (float("inf"), x.threshold):
+                got = x.dev.exhaustive_detect_all(s, g, cs, pv, max_score=max_score, max_detections=MAX_DET, overlap_permille=300, margin=1,
+                                                  penalty=DEFAULT, min_matched=0.4, boxes=True, matched=True, gate="all")
+                note(len(got[0]), MAX_DET)
+                out += list(got)
+        got = x.dev.exhaustive_detect_windows(s, jobs, x.cs, x.piv, wrap=True, max_detections=MAX_DET, overlap_permille=300, margin=1,
+                                              penalty=DEFAULT, min_matched=0.2, boxes=True, matched=True, job_index=True, gate="all")
+        note(len(got[0]), MAX_DET)
+        out += list(got)
+    return out
+
+
 def _windows(x, note):
     out = []
     jobs = x.c["jobs"]
@@ -259,6 +281,7 @@ CALLS = [
     ("exhaustive_detect_nms", _detect_nms), ("exhaustive_detect_all_inf", _detect_all(False)),
     ("exhaustive_detect_all_threshold", _detect_all(True)), ("exhaustive_detect_all_matched", _detect_all_matched),
     ("exhaustive_window_search", _windows), ("exhaustive_detect_windows", _detect_windows), ("line_costs", _line_costs), ("matched_fractions", _matched_fractions),
+    ("gate_all", _gate_all),
 ]
 NAMES = [name for name, _ in CALLS]
 
