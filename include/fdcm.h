@@ -82,7 +82,11 @@ typedef struct fdcm_search_timing {
                       * candidate pairs, work list) on a second stream beside a build that is still running: the part of it
                       * that overlaps the build is then not inside kernel_ms / total_ms */
     int64_t candidates;
-    int64_t evaluations; /* translations scored by the reference rule (kept + rejected batches) */
+    int64_t evaluations; /* translations scored by the reference rule (kept + rejected batches), summed over the candidates;
+                          * every translation counts once.  For DefaultOptimize and BatchOptimize that is the number of the
+                          * rule's scorings.  IndulgentOptimize(p)'s rule scores a translation it rejects p more times at the
+                          * same place before it gives up; those repeats read nothing new and are not counted, so the value is
+                          * the number of scorings of IndulgentOptimize(0), which walks and returns the same */
 } fdcm_search_timing;
 
 const char* fdcm_last_error(void);
