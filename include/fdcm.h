@@ -780,6 +780,71 @@ int fdcm_search_exhaustive_detect_windows_gated(const fdcm_featuremap* fm, const
                                                 float* matched_out /* max_detections, or NULL */,
                                                 int32_t* jobs_out /* max_detections, or NULL */);
 
+/* Objects: templates carry an object label, and every stage keeps a best pair per (grid point, object) instead of per grid
+ * point.  A set is usually many views of a few parts: with one pair per point two parts at one translation compete for the
+ * point, one threshold serves parts of every size, and one overlap limit serves suppression within a part and across parts.
+ * The definitions are this project's (README.md, "Objects"; numpy statement: tests/objects_ref.py).  Everything not restated
+ * here is taken unchanged from fdcm_search_exhaustive_detect_all_gated, fdcm_best_map_gated and
+ * fdcm_search_exhaustive_detect_windows_gated: score, caps, admissibility, rot == NULL, q, its denominators and pairkey,
+ * footprints with margin, I and U in int64, len_i, cap_i, matched, ML, TL_t and frac, the record layout and both gates.
+ * Inputs: objects, n_templates int32 with objects[t] in [0, G), G = n_objects, 1 <= G <= 256 (an object may hold no template,
+ * or only templates without lines: its plane is empty); max_score, G float32, each >= +0 or +inf; min_matched, G float32 in
+ * [0, 1], NULL meaning all 0; overlap_permille and cross_permille, 0 .. 1000; gate, margin, penalty, tau, max_detections
+ * (1 .. 4096) and tmpl_index_base as in the siblings.
+ * Candidates: the candidates of an entry (g, o) are the pairs u = (t, a) with objects[t] = o of templates with lines,
+ * admissible at g, with q not NaN; under FDCM_GATE_ALL also ML(u, t_g) >= need_t, need_t = float32(min_matched[objects[t]] *
+ * TL_t).  best(g, o) is the candidate of the smallest pairkey.  Under FDCM_GATE_WINNER the entry is dropped unless
+ * ML(best(g, o), t_g) >= need; as in the sibling, only that pair is looked at.
+ * Object best map (fdcm_best_map_objects): three planes [G][ny][nx], row-major: q(best(g, o)), u(best(g, o)) and
+ * frac(best(g, o), t_g); NaN, -1 and NaN mark entries without a candidate.  Any plane may be NULL, not all three.  There is no
+ * gate argument: as in fdcm_best_map_gated, min_matched[o] > 0 restricts the minimum.
+ * Dense detections (fdcm_search_exhaustive_detect_objects): S_0 is the set of entries (g, o) that have a candidate, pass the
+ * gate and have q(best(g, o)) <= max_score[o].  Order: key(g, o) = (bits of q, g, u), u = best(g, o), compared
+ * lexicographically: a total order, because the pairs of different objects differ; the label does not enter.  Footprint:
+ * F(g, o) = box(best(g, o)) + t_g.  Greedy rule: d_n is the smallest entry of S_n and S_(n+1) = S_n \ {d_n} \ {e : d_n
+ * suppresses e}, where d = (g_d, o_d) suppresses e = (g, o) when 1000 I > overlap_permille U and o = o_d, or when 1000 I >
+ * cross_permille U and o != o_d; the rule stops at max_detections or when S_n is empty.  Output: the d_n in order, as the
+ * sibling's records, with optional boxes_out and matched_out.  The object of a record is objects[tmpl_idx - tmpl_index_base].
+ * Windows (fdcm_search_exhaustive_detect_windows_objects): job j's object is objects[tmpl_j]; its winner, q_j, key(j) and
+ * footprint are the sibling's; the threshold is max_score[o_j], the need comes from min_matched[o_j], and the suppression
+ * test is the two-limit test above.  The outputs are the sibling's, jobs_out included.
+ * Identities: G = 1 gives the bytes of the siblings at max_score[0], min_matched[0] and the same gate, whatever
+ * cross_permille is.  cross_permille = 1000 with max_detections not reached: objects do not interact, and the records are
+ * those of the sibling run once per object on that object's templates, merged in the order (score bits, g, u); plane o of the
+ * object best map is fdcm_best_map_gated of object o's sub-set with pairs mapped back.  One-point window jobs for every keyed
+ * entry of the object best map, listed by ascending (g, u), give the dense call's records.  Relabelling the objects by a
+ * bijection, the per-object arrays permuted alike, changes no output byte.  With one max_score for all objects the records
+ * for any max_score are the leading records with score <= max_score of the +inf list.  overlap_permille = cross_permille = 0:
+ * no two returned boxes share a pixel.  Every record's fraction is fdcm_matched_fractions of its pose, bit for bit, and its
+ * ML >= need.  Results are a function of the inputs alone.
+ * FDCM_EINVAL, before any GPU work: everything the siblings reject; n_objects outside 1 .. 256; objects NULL with templates,
+ * or an entry outside [0, G); max_score NULL, or an entry NaN or < 0; a min_matched entry NaN or outside [0, 1];
+ * cross_permille outside 0 .. 1000; n_objects * nx * ny > 2^26 in the dense calls.  That bound holds G key planes of 8 bytes
+ * per point in whole 16 x 64 sub-tiles: a grid much narrower than 16 or much lower than 64 points pads each plane by up to
+ * those factors.  Empty inputs give FDCM_OK and nothing.  The calls block; concurrent callers of one feature map take turns. */
+int fdcm_best_map_objects(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                          const fdcm_grid* grid, int penalty, float tau, const int32_t* objects /* n_templates */, int32_t n_objects,
+                          const float* min_matched /* n_objects, or NULL */, float* score_out_host /* n_objects ny nx, or NULL */,
+                          int32_t* pair_out_host /* or NULL */, float* matched_out_host /* or NULL */);
+int fdcm_search_exhaustive_detect_objects(const fdcm_featuremap* fm, const fdcm_templates* templates,
+                                          const fdcm_rotations* rot /* or NULL */, const fdcm_grid* grid,
+                                          const int32_t* objects /* n_templates */, int32_t n_objects,
+                                          const float* max_score /* n_objects */, const float* min_matched /* n_objects, or NULL */,
+                                          int32_t max_detections, int32_t overlap_permille, int32_t cross_permille, int32_t margin,
+                                          int penalty, float tau, int gate, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                          int32_t* boxes_out /* 4 max_detections, or NULL */,
+                                          float* matched_out /* max_detections, or NULL */);
+int fdcm_search_exhaustive_detect_windows_objects(const fdcm_featuremap* fm, const fdcm_templates* templates,
+                                                  const fdcm_rotations* rot /* or NULL */, const fdcm_pose_window* jobs, int64_t n_jobs,
+                                                  int32_t sx, int32_t sy, int32_t wrap, const int32_t* objects /* n_templates */,
+                                                  int32_t n_objects, const float* max_score /* n_objects */,
+                                                  const float* min_matched /* n_objects, or NULL */, int32_t max_detections,
+                                                  int32_t overlap_permille, int32_t cross_permille, int32_t margin, int penalty,
+                                                  float tau, int gate, int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out,
+                                                  int32_t* boxes_out /* 4 max_detections, or NULL */,
+                                                  float* matched_out /* max_detections, or NULL */,
+                                                  int32_t* jobs_out /* max_detections, or NULL */);
+
 /* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
  *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as
  *      fdcm_edge_labels makes it (m = the distinct keys of `depth`, a byte < m an edge pixel of that label, labels circular)

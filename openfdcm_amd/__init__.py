@@ -882,6 +882,122 @@ def exhaustive_detect_refined(featuremap, templates, max_score, coarse_angles, f
                                      return_matched=return_matched, return_jobs=return_jobs, gate=gate)
 
 
+# ---------------------------------------------------------------- objects: many views of a few parts (extension)
+def object_score_maps(featuremap, templates, objects, stride=1, penalty=None, angles=None, pivot="center", window=None, line_caps=None,
+                      min_matched=None, return_matched=False, n_objects=None):
+    """best_score_map per object: objects[t] (0 .. G - 1) names the part template t is a view of, and every grid point keeps
+    one best pair per object instead of one in all.  Returns (scores [G, ny, nx] float32, pairs [G, ny, nx] int32, grid), or
+    with return_matched (scores, pairs, matched, grid): plane o is best_score_map of the templates of object o alone, with the
+    pairs numbered in the whole set (NaN, -1 and NaN where no template of the object fits; an object without templates has an
+    empty plane).  min_matched: None, a scalar, or one value per object.  n_objects None means max(objects) + 1.  The other
+    arguments are best_score_map's."""
+    kind, tau = _penalty_args(penalty)
+    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
+    obj, G, _, mm = _engine.object_arrays(objects, n_objects, tset.count, None, min_matched)
+    if g[2] == 0 or g[3] == 0:
+        empty = (_np.zeros((G, g[3], g[2]), dtype=_np.float32), _np.zeros((G, g[3], g[2]), dtype=_np.int32))
+        return empty + ((_np.zeros((G, g[3], g[2]), dtype=_np.float32),) if return_matched else ()) + (g,)
+    return fm.best_map_objects(tset, g, obj, G, cs, pv, penalty=kind, tau=tau, min_matched=mm, matched=return_matched) + (g,)
+
+
+def exhaustive_detect_objects(featuremap, templates, objects, max_score, overlap=0.3, cross_overlap=None, stride=1, max_detections=1024,
+                              penalty=None, angles=None, pivot="center", window=None, line_caps=None, margin=0, return_boxes=False,
+                              min_matched=None, return_matched=False, n_objects=None, return_objects=False, gate="winner"):
+    """exhaustive_detect_all for a set that holds many views of a few parts.  objects[t] (0 .. G - 1) is the part of template
+    t; the candidates of the greedy rule are the (grid point, object) entries, each with the best pair among its object's
+    templates, so two parts lying at one translation are both candidates.  max_score and min_matched are a scalar or one
+    value per object: a clip of 6 lines and a housing of 40 each get their own.  A detection drops the entries of its own
+    object whose footprints overlap its own by more than `overlap`, and the entries of other objects by more than
+    cross_overlap (None: equal to overlap; 1 lets the objects ignore each other).  Entries are taken in the order (score, grid
+    index, pair).  n_objects None means max(objects) + 1.  Returns a MatchList in ascending score, then with return_boxes the
+    (n, 4) int32 footprints, with return_matched the (n,) float32 matched fractions and with return_objects the (n,) int32
+    objects[tmpl_idx] of the detections, in that order.  The remaining arguments, gate included, are exhaustive_detect_all's;
+    with one object the result is exhaustive_detect_all's."""
+    _engine.gate_kind(gate)
+    kind, tau = _penalty_args(penalty)
+    permille = int(round(1000 * float(overlap)))
+    cross = permille if cross_overlap is None else int(round(1000 * float(cross_overlap)))
+    fm, tset, cs, pv, g = _detect_args(featuremap, templates, angles, pivot, stride, window, line_caps)
+    obj, G, ms, mm = _engine.object_arrays(objects, n_objects, tset.count, max_score, min_matched)
+    if g[2] == 0 or g[3] == 0:
+        res = (_np.zeros(0, dtype=_capi.MATCH_DTYPE),) + ((_np.zeros((0, 4), dtype=_np.int32),) if return_boxes else ())
+        res += (_np.zeros(0, dtype=_np.float32),) if return_matched else ()
+    else:
+        res = fm.exhaustive_detect_objects(tset, g, obj, ms, G, cs, pv, max_detections=max_detections, overlap_permille=permille,
+                                           cross_permille=cross, margin=margin, penalty=kind, tau=tau, min_matched=mm,
+                                           boxes=return_boxes, matched=return_matched, gate=gate)
+        res = res if isinstance(res, tuple) else (res,)
+    res += (obj[res[0]["tmpl_idx"]].astype(_np.int32),) if return_objects else ()
+    res = (MatchList(res[0]),) + tuple(res[1:])
+    return res if len(res) > 1 else res[0]
+
+
+def exhaustive_detect_windows_objects(featuremap, templates, jobs, objects, max_score, overlap=0.3, cross_overlap=None, angles=None,
+                                      stride=1, max_detections=1024, penalty=None, pivot="center", wrap=False, line_caps=None, margin=0,
+                                      min_matched=None, return_boxes=False, return_matched=False, return_jobs=False, n_objects=None,
+                                      return_objects=False, gate="winner"):
+    """exhaustive_detect_windows with objects: a job's object is objects[tmpl] of its template; the job stays when its best
+    pose's score is <= its object's max_score and, with min_matched, matches at least its object's share; a detection drops
+    the jobs of its own object above `overlap` and those of other objects above cross_overlap (None: equal to overlap).
+    max_score and min_matched are a scalar or one value per object; n_objects None means max(objects) + 1.  Returns
+    exhaustive_detect_windows' results, and with return_objects the (n,) int32 objects of the detections last.  The other
+    arguments are exhaustive_detect_windows'."""
+    _engine.gate_kind(gate)
+    kind, tau = _penalty_args(penalty)
+    permille = int(round(1000 * float(overlap)))
+    cross = permille if cross_overlap is None else int(round(1000 * float(cross_overlap)))
+    sx, sy = _strides(stride)
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates, line_caps)
+    obj, G, ms, mm = _engine.object_arrays(objects, n_objects, tset.count, max_score, min_matched)
+    cs = pv = None
+    if angles is not None:
+        cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
+    res = fm.exhaustive_detect_windows_objects(tset, jobs, obj, ms, G, cs, pv, sx=sx, sy=sy, wrap=wrap, max_detections=max_detections,
+                                               overlap_permille=permille, cross_permille=cross, margin=margin, penalty=kind, tau=tau,
+                                               min_matched=mm, boxes=return_boxes, matched=return_matched, job_index=return_jobs,
+                                               gate=gate)
+    res = res if isinstance(res, tuple) else (res,)
+    res += (obj[res[0]["tmpl_idx"]].astype(_np.int32),) if return_objects else ()
+    res = (MatchList(res[0]),) + tuple(res[1:])
+    return res if len(res) > 1 else res[0]
+
+
+def exhaustive_detect_refined_objects(featuremap, templates, objects, max_score, coarse_angles, fine_angles, coarse_stride, half_angles,
+                                      half_x, half_y, coarse_max_score=None, coarse_overlap=1.0, coarse_cross_overlap=None,
+                                      coarse_max_detections=1024, overlap=0.3, cross_overlap=None, stride=1, max_detections=1024,
+                                      penalty=None, pivot="center", wrap=False, line_caps=None, margin=0, min_matched=None,
+                                      return_boxes=False, return_matched=False, return_jobs=False, n_objects=None,
+                                      return_objects=False, gate="winner"):
+    """exhaustive_detect_refined with objects: pure Python over three calls, and by definition exactly their composition:
+      seeds = exhaustive_detect_objects(featuremap, templates, objects, coarse_max_score (None: inf), overlap=coarse_overlap,
+                                        cross_overlap=coarse_cross_overlap, stride=coarse_stride,
+                                        max_detections=coarse_max_detections, penalty=penalty, angles=coarse_angles, pivot=pivot,
+                                        line_caps=line_caps, margin=margin, n_objects=n_objects)
+      jobs = pose_windows(seeds, coarse_angles, fine_angles, template_pivots(templates, pivot), half_angles, half_x, half_y,
+                          stride=stride, wrap=wrap)
+      exhaustive_detect_windows_objects(featuremap, templates, jobs, objects, max_score, overlap=overlap,
+                                        cross_overlap=cross_overlap, angles=fine_angles, stride=stride,
+                                        max_detections=max_detections, penalty=penalty, pivot=pivot, wrap=wrap,
+                                        line_caps=line_caps, margin=margin, min_matched=min_matched, return_boxes=..,
+                                        return_matched=.., return_jobs=.., n_objects=n_objects, return_objects=.., gate=gate)
+    The coarse stage has no matched-fraction gate and by default neither a threshold nor suppression; its seeds are the best
+    (grid point, object) entries, so every object at a point seeds a window of its own.  pose_windows needs no objects: a
+    seed carries its template.  return_jobs indexes the seeds.  gate applies to the fine stage only."""
+    _engine.gate_kind(gate)
+    seeds = exhaustive_detect_objects(featuremap, templates, objects, float("inf") if coarse_max_score is None else coarse_max_score,
+                                      overlap=coarse_overlap, cross_overlap=coarse_cross_overlap, stride=coarse_stride,
+                                      max_detections=coarse_max_detections, penalty=penalty, angles=coarse_angles, pivot=pivot,
+                                      line_caps=line_caps, margin=margin, n_objects=n_objects)
+    jobs = pose_windows(seeds, coarse_angles, fine_angles, template_pivots(templates, pivot), half_angles, half_x, half_y,
+                        stride=stride, wrap=wrap)
+    return exhaustive_detect_windows_objects(featuremap, templates, jobs, objects, max_score, overlap=overlap, cross_overlap=cross_overlap,
+                                             angles=fine_angles, stride=stride, max_detections=max_detections, penalty=penalty,
+                                             pivot=pivot, wrap=wrap, line_caps=line_caps, margin=margin, min_matched=min_matched,
+                                             return_boxes=return_boxes, return_matched=return_matched, return_jobs=return_jobs,
+                                             n_objects=n_objects, return_objects=return_objects, gate=gate)
+
+
 # ---------------------------------------------------------------- per-line caps and line costs (extension)
 def line_caps(templates, tau):
     """The caps a scalar line_caps=tau stands for: per template the float32 array float32(tau) * len_i, len_i the line's

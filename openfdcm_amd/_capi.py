@@ -194,6 +194,16 @@ SYMBOLS = [
                                                              C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                                              C.c_int32, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int32,
                                                              C.POINTER(_vp), _i64p, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32)]),
+    ("fdcm_best_map_objects", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.c_int, C.c_float, C.POINTER(C.c_int32),
+                                       C.c_int32, _fp, _fp, C.POINTER(C.c_int32), _fp]),
+    ("fdcm_search_exhaustive_detect_objects", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(Grid), C.POINTER(C.c_int32), C.c_int32,
+                                                       _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int,
+                                                       C.c_int32, C.POINTER(_vp), _i64p, C.POINTER(C.c_int32), _fp]),
+    ("fdcm_search_exhaustive_detect_windows_objects", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(PoseWindow), C.c_int64,
+                                                               C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _fp, _fp,
+                                                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int,
+                                                               C.c_int32, C.POINTER(_vp), _i64p, C.POINTER(C.c_int32), _fp,
+                                                               C.POINTER(C.c_int32)]),
     ("fdcm_matched_fractions", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64, _fp]),
     ("fdcm_templates_matched_totals", C.c_int, [_vp, _fp]),
     ("fdcm_detect_score_bounds", C.c_int, [_vp, C.c_int, C.c_float, C.c_float, _fp]),

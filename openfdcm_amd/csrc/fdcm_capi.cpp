@@ -973,6 +973,117 @@ int fdcm_best_map_gated(const fdcm_featuremap* fm, const fdcm_templates* templat
     });
 }
 
+// Objects: include/fdcm.h, "Objects".  The per-object arrays are checked with the other limits, before any handle; the labels,
+// whose count is the templates', after the null checks (they read no device state).  The thresholds are copied with -0 as +0,
+// as the siblings pass theirs.
+static void check_object_limits(int32_t n_objects, const float* max_score, bool with_max_score, const float* min_matched,
+                                std::vector<float>& ms, std::vector<float>& mm) {
+    require(n_objects >= 1 && n_objects <= 256, "n_objects must be in [1, 256]");
+    if (with_max_score) {
+        require(max_score != nullptr, "max_score is null");
+        ms.assign(max_score, max_score + n_objects);
+        for (float& v : ms) {
+            require(v >= 0.f, "max_score must be >= 0 or +inf, never NaN");
+            if (v == 0.f) v = 0.f;
+        }
+    }
+    if (min_matched) {
+        mm.assign(min_matched, min_matched + n_objects);
+        for (float& v : mm) {
+            require(v >= 0.f && v <= 1.f, "min_matched must be in [0, 1], never NaN");
+            if (v == 0.f) v = 0.f;
+        }
+    }
+}
+static void check_object_labels(const fdcm_templates* t, const int32_t* objects, int32_t n_objects) {
+    require(t->T == 0 || objects != nullptr, "objects is null");
+    for (int64_t i = 0; i < t->T; ++i) require(objects[i] >= 0 && objects[i] < n_objects, "objects: an entry is outside [0, n_objects)");
+}
+static void check_object_planes(const fdcm_grid* grid, int32_t n_objects) {
+    require(grid != nullptr, "grid is null");
+    require((int64_t)n_objects * (int64_t)std::max(0, grid->nx) * (int64_t)std::max(0, grid->ny) <= ((int64_t)1 << 26),
+            "n_objects * nx * ny must be at most 2^26");
+}
+
+int fdcm_best_map_objects(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot, const fdcm_grid* grid,
+                          int penalty, float tau, const int32_t* objects, int32_t n_objects, const float* min_matched,
+                          float* score_out_host, int32_t* pair_out_host, float* matched_out_host) {
+    return guarded([&] {
+        require(score_out_host || pair_out_host || matched_out_host, "score_out_host, pair_out_host and matched_out_host are all null");
+        std::vector<float> ms, mm;
+        check_object_limits(n_objects, nullptr, false, min_matched, ms, mm);
+        check_object_planes(grid, n_objects);
+        check_best_args(fm, templates, rot, grid, penalty, tau);
+        check_object_labels(templates, objects, n_objects);
+        run_best_map_objects(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, penalty, tau, objects, n_objects,
+                             min_matched ? mm.data() : nullptr, score_out_host, pair_out_host, matched_out_host);
+    });
+}
+
+int fdcm_search_exhaustive_detect_objects(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                          const fdcm_grid* grid, const int32_t* objects, int32_t n_objects, const float* max_score,
+                                          const float* min_matched, int32_t max_detections, int32_t overlap_permille,
+                                          int32_t cross_permille, int32_t margin, int penalty, float tau, int gate, int32_t tmpl_index_base,
+                                          fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
+    return guarded([&] {
+        require(gate == FDCM_GATE_WINNER || gate == FDCM_GATE_ALL, "gate must be FDCM_GATE_WINNER or FDCM_GATE_ALL");
+        std::vector<float> ms, mm;
+        check_object_limits(n_objects, max_score, true, min_matched, ms, mm);
+        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
+        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
+        require(cross_permille >= 0 && cross_permille <= 1000, "cross_permille must be in [0, 1000]");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(out && n_out, "null output");
+        check_object_planes(grid, n_objects);
+        check_best_args(fm, templates, rot, grid, penalty, tau);
+        check_object_labels(templates, objects, n_objects);
+        records_call(out, [&] {
+            run_search_exhaustive_detect_objects(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, objects, n_objects, ms.data(),
+                                                 min_matched ? mm.data() : nullptr, max_detections, overlap_permille, cross_permille, margin,
+                                                 penalty, tau, gate, tmpl_index_base, out, n_out, boxes_out, matched_out);
+        });
+    });
+}
+
+int fdcm_search_exhaustive_detect_windows_objects(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                                  const fdcm_pose_window* jobs, int64_t n_jobs, int32_t sx, int32_t sy, int32_t wrap,
+                                                  const int32_t* objects, int32_t n_objects, const float* max_score,
+                                                  const float* min_matched, int32_t max_detections, int32_t overlap_permille,
+                                                  int32_t cross_permille, int32_t margin, int penalty, float tau, int gate,
+                                                  int32_t tmpl_index_base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out,
+                                                  float* matched_out, int32_t* jobs_out) {
+    return guarded([&] {
+        require(gate == FDCM_GATE_WINNER || gate == FDCM_GATE_ALL, "gate must be FDCM_GATE_WINNER or FDCM_GATE_ALL");
+        std::vector<float> ms, mm;
+        check_object_limits(n_objects, max_score, true, min_matched, ms, mm);
+        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
+        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
+        require(cross_permille >= 0 && cross_permille <= 1000, "cross_permille must be in [0, 1000]");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
+        require(std::isfinite(tau), "tau must be finite");
+        require(out && n_out, "null output");
+        require(sx >= 1 && sy >= 1, "strides sx and sy must be >= 1");
+        require(wrap == 0 || wrap == 1, "wrap must be 0 or 1");
+        require(n_jobs >= 0 && (n_jobs == 0 || jobs), "jobs is null or n_jobs is negative");
+        require(n_jobs <= ((int64_t)1 << 22), "n_jobs must be at most 2^22");
+        if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
+        check_pose_windows(jobs, n_jobs, rot ? rot->n : 1, sx, sy, wrap);
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        if (rot) check_pivots(templates, rot);
+        for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
+            require(jobs[j].tmpl < templates->T, "jobs: tmpl is outside the template set");
+        check_object_labels(templates, objects, n_objects);
+        records_call(out, [&] {
+            run_search_exhaustive_detect_windows_objects(const_cast<fdcm_featuremap*>(fm), templates, rot, jobs, n_jobs, sx, sy, objects,
+                                                         n_objects, ms.data(), min_matched ? mm.data() : nullptr, max_detections,
+                                                         overlap_permille, cross_permille, margin, penalty, tau, gate, tmpl_index_base, out,
+                                                         n_out, boxes_out, matched_out, jobs_out);
+        });
+    });
+}
+
 // The line costs' checks, with the one output: nothing here touches the device.
 int fdcm_matched_fractions(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot, const int32_t* poses,
                            int64_t n, float* fractions) {

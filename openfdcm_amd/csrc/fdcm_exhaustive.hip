@@ -29,6 +29,10 @@
 //                                     detections over pose windows: a thread per job turns the job's merged k = 1 list into
 //                                     its entry of the winners' list (normalised key, footprint), and one round of the greedy
 //                                     rule on that list, k_nms_round's scheme with a list in place of the key plane
+//   k_nms_objects_round, k_nms_list_objects_round, k_window_winners_objects<BUF32>
+//                                     objects (include/fdcm.h, "Objects"): the round of the greedy rule over G key planes, one
+//                                     per object, and over a winners' list with an object per job, each with one overlap limit
+//                                     within an object and one across objects; the winners' pass with a threshold per pair
 //
 // Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP, EXIT, GATE>, the one statement of the sum (4 rows per lane
 // in k_exhaustive, 1 in k_exhaustive_windows).  GATE: the matched length of every slot beside its sum, by matched_length's
@@ -692,6 +696,99 @@ __global__ void __launch_bounds__(256) k_nms_round(unsigned long long* keys, lon
     if (threadIdx.x == 0) { pk_out[blockIdx.x] = mk; pp_out[blockIdx.x] = mp; }
 }
 
+// ---- objects (include/fdcm.h, "Objects"): G key planes, one behind the other, plane o holding best(g, o)
+// nms_block_min with the pair as the second part of the order: two objects can tie on (bits of q, g), and their pairs differ.
+// kNoKey travels with the pair -1, the largest as unsigned.
+__device__ __forceinline__ bool nms_pair_less(unsigned long long k2, int p2, unsigned long long key, int pair) {
+    return k2 < key || (k2 == key && (unsigned)p2 < (unsigned)pair);
+}
+__device__ __forceinline__ void nms_block_min_pair(unsigned long long& key, int& pair, unsigned long long* sk, int* sp) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long k2 = __shfl_xor(key, d);
+        const int p2 = __shfl_xor(pair, d);
+        if (nms_pair_less(k2, p2, key, pair)) { key = k2; pair = p2; }
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sk[wave] = key; sp[wave] = pair; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        if (nms_pair_less(sk[w], sp[w], key, pair)) { key = sk[w]; pair = sp[w]; }
+    __syncthreads();  // sk and sp are free again
+}
+
+// One round of the greedy rule over the G planes: k_nms_round's scheme, launch by launch.  The planes are one array of
+// n_chunks runs of 256 keys, plane_chunks of them per plane (a plane is whole sub-tiles, so a run lies in one plane): the
+// object of an entry is its run's plane, (i, j) the inverse of best_key_index inside the plane.  A partial is a key
+// (bits of q << 32) | g and its pair, ordered as (key, pair): the order of include/fdcm.h, "Objects".  The winner's object is
+// pobj[its pair] (a per-pair table), its entry the one at its point in its object's plane: that entry is erased by object
+// and point, an entry of another object at the same point only when the cross limit says so.  The limit of an entry is
+// `permille` when its object is the winner's and `cross` otherwise.  One writer per entry, no atomics, no cooperative launch.
+__global__ void __launch_bounds__(256) k_nms_objects_round(unsigned long long* keys, long long n_chunks, long long plane_chunks, int x0,
+                                                           int y0, int sx, int sy, int nx, int tiles_x, const int4* __restrict__ boxes,
+                                                           const int* __restrict__ pobj, int permille, int cross, int round, int last,
+                                                           const unsigned long long* __restrict__ pk_in, const int* __restrict__ pp_in,
+                                                           unsigned long long* __restrict__ pk_out, int* __restrict__ pp_out,
+                                                           unsigned long long* __restrict__ best, int* __restrict__ pair) {
+    __shared__ unsigned long long sk[4];
+    __shared__ int sp[4];
+    unsigned long long W = kNoKey;
+    int Wp = -1;
+    if (round > 0) {
+        if (threadIdx.x < gridDim.x) { W = pk_in[threadIdx.x]; Wp = pp_in[threadIdx.x]; }
+        nms_block_min_pair(W, Wp, sk, sp);
+        if (blockIdx.x == 0 && threadIdx.x == 0) { best[round - 1] = W; pair[round - 1] = W == kNoKey ? -1 : Wp; }
+        if (W == kNoKey || last) {  // workgroup-uniform
+            if (threadIdx.x == 0) { pk_out[blockIdx.x] = kNoKey; pp_out[blockIdx.x] = -1; }
+            return;
+        }
+    }
+    // the winner's object, footprint and area (round 0: unused)
+    const unsigned gw = (unsigned)W;
+    int wx0 = 0, wy0 = 0, wx1 = -1, wy1 = -1, ow = -1;
+    if (round > 0) {
+        const int4 b = boxes[Wp];
+        const int tx = x0 + (int)(gw % (unsigned)nx) * sx, ty = y0 + (int)(gw / (unsigned)nx) * sy;
+        wx0 = b.x + tx; wy0 = b.y + ty; wx1 = b.z + tx; wy1 = b.w + ty;
+        ow = pobj[Wp];
+    }
+    const long long Aw = (long long)(wx1 - wx0 + 1) * (long long)(wy1 - wy0 + 1);
+    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
+    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
+    unsigned long long mk = kNoKey;
+    int mp = -1;
+    for (long long c = c0; c < c1; ++c) {
+        const long long idx = c * 256 + threadIdx.x;
+        const unsigned long long v = keys[idx];
+        if (v == kNoKey) continue;
+        const int o = (int)(c / plane_chunks);  // (wave-uniform)
+        const long long in_plane = idx - (long long)o * plane_chunks * 256;
+        const int tile = (int)(in_plane >> 10), r = (int)(in_plane & 1023);
+        const int i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
+        const int j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
+        const unsigned g = (unsigned)(j * nx + i);
+        const int u = (int)(unsigned)v;
+        bool drop = false;
+        if (round > 0) {
+            drop = g == gw && o == ow;
+            if (!drop) {
+                const int4 b = boxes[u];
+                const int tx = x0 + i * sx, ty = y0 + j * sy;
+                drop = nms_suppresses(b.x + tx, b.y + ty, b.z + tx, b.w + ty, wx0, wy0, wx1, wy1, Aw, o == ow ? permille : cross);
+            }
+        }
+        if (drop) {
+            keys[idx] = kNoKey;
+        } else {
+            const unsigned long long key = (v & 0xffffffff00000000ull) | g;
+            if (nms_pair_less(key, u, mk, mp)) { mk = key; mp = u; }
+        }
+    }
+    nms_block_min_pair(mk, mp, sk, sp);
+    if (threadIdx.x == 0) { pk_out[blockIdx.x] = mk; pp_out[blockIdx.x] = mp; }
+}
+
 // ---- pose windows (include/fdcm.h, "Pose windows"): a list of jobs, each one template, a run of rotations and a small grid
 // of its own.  A plane is one (job, run position e) whose admissible box, clipped to the job's grid, is not empty; the host
 // cuts every plane's clipped box into patches of 4 (i) x 16 (j) grid points and lists them, job by job, in one table.  Wave w
@@ -916,14 +1013,15 @@ struct WinnerJob {
 };
 static_assert(sizeof(WinnerJob) == 32, "WinnerJob is 32 bytes");
 
-template <bool BUF32>
-__global__ void __launch_bounds__(256) k_window_winners(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
-                                                        const ExLine* __restrict__ lines, const float* __restrict__ len,
-                                                        const ExTmpl* __restrict__ tm, const int4* __restrict__ foot,
-                                                        const float* __restrict__ need, const WinnerJob* __restrict__ jobs,
-                                                        const int* __restrict__ run, const unsigned long long* __restrict__ best,
-                                                        int n_jobs, unsigned job0, int sx, int sy, float max_score,
-                                                        unsigned long long* __restrict__ keys, int4* __restrict__ boxes) {
+// The one statement of a job's entry of the winners' list, for both kernels below.  limit(u): the threshold of pair u.
+template <bool BUF32, class Limit>
+__device__ __forceinline__ void window_winner(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
+                                              const ExLine* __restrict__ lines, const float* __restrict__ len,
+                                              const ExTmpl* __restrict__ tm, const int4* __restrict__ foot,
+                                              const float* __restrict__ need, const WinnerJob* __restrict__ jobs,
+                                              const int* __restrict__ run, const unsigned long long* __restrict__ best, int n_jobs,
+                                              unsigned job0, int sx, int sy, Limit limit, unsigned long long* __restrict__ keys,
+                                              int4* __restrict__ boxes) {
     const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (j >= n_jobs) return;
     const unsigned long long v = best[j];
@@ -938,7 +1036,7 @@ __global__ void __launch_bounds__(256) k_window_winners(const float* __restrict_
     const int u = run[J.run0 + (int)e];
     const ExTmpl P = tm[u];
     const float q = __uint_as_float((unsigned)(v >> 32)) / __uint_as_float(P.koff);  // one IEEE division, as the best map's
-    bool keep = !(q != q) && q <= max_score;
+    bool keep = !(q != q) && q <= limit(u);
     if (keep && need) {
         const VolRef V = make_volref(vol, SL, m, BUF32);
         const float ml = matched_length<BUF32>(V, lines + P.line0, len + P.line0, P.n, tx + (float)x, ty + (float)y, W, (unsigned)H, SL);
@@ -947,6 +1045,18 @@ __global__ void __launch_bounds__(256) k_window_winners(const float* __restrict_
     const int4 b = foot[u];
     keys[j] = keep ? ((unsigned long long)__float_as_uint(q) << 32) | (job0 + (unsigned)j) : kNoKey;
     boxes[j] = make_int4(b.x + x, b.y + y, b.z + x, b.w + y);
+}
+
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_window_winners(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
+                                                        const ExLine* __restrict__ lines, const float* __restrict__ len,
+                                                        const ExTmpl* __restrict__ tm, const int4* __restrict__ foot,
+                                                        const float* __restrict__ need, const WinnerJob* __restrict__ jobs,
+                                                        const int* __restrict__ run, const unsigned long long* __restrict__ best,
+                                                        int n_jobs, unsigned job0, int sx, int sy, float max_score,
+                                                        unsigned long long* __restrict__ keys, int4* __restrict__ boxes) {
+    window_winner<BUF32>(vol, SL, m, W, H, tx, ty, lines, len, tm, foot, need, jobs, run, best, n_jobs, job0, sx, sy,
+                         [=](int) { return max_score; }, keys, boxes);
 }
 
 // One round of the greedy rule on the winners' list: k_nms_round's scheme with the list in place of the key plane.  Entry j
@@ -991,6 +1101,70 @@ __global__ void __launch_bounds__(256) k_nms_list_round(unsigned long long* keys
             if (!drop) {
                 const int4 b = boxes[idx];
                 drop = nms_suppresses(b.x, b.y, b.z, b.w, w.x, w.y, w.z, w.w, Aw, permille);
+            }
+        }
+        if (drop) keys[idx] = kNoKey;
+        else if (v < mk) mk = v;
+    }
+    nms_block_min(mk, none, sk, sp);
+    if (threadIdx.x == 0) pk_out[blockIdx.x] = mk;
+}
+
+// Objects (include/fdcm.h, "Objects"), the windows' call.  k_window_winners with the threshold of the job's object: ms[u] is
+// max_score[objects[template of pair u]], as need[u] is that object's need; everything else is k_window_winners'.
+template <bool BUF32>
+__global__ void __launch_bounds__(256) k_window_winners_objects(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx,
+                                                                float ty, const ExLine* __restrict__ lines, const float* __restrict__ len,
+                                                                const ExTmpl* __restrict__ tm, const int4* __restrict__ foot,
+                                                                const float* __restrict__ need, const float* __restrict__ ms,
+                                                                const WinnerJob* __restrict__ jobs, const int* __restrict__ run,
+                                                                const unsigned long long* __restrict__ best, int n_jobs, unsigned job0,
+                                                                int sx, int sy, unsigned long long* __restrict__ keys,
+                                                                int4* __restrict__ boxes) {
+    window_winner<BUF32>(vol, SL, m, W, H, tx, ty, lines, len, tm, foot, need, jobs, run, best, n_jobs, job0, sx, sy,
+                         [=](int u) { return ms[u]; }, keys, boxes);
+}
+
+// k_nms_list_round with an object per entry: entry j's limit is `permille` when jobj[j] is the winner's object and `cross`
+// otherwise.  A key's low half is its entry, so no two keys are equal and the partial minima stay keys alone.
+__global__ void __launch_bounds__(256) k_nms_list_objects_round(unsigned long long* keys, const int4* __restrict__ boxes,
+                                                                const int* __restrict__ jobj, long long n, int permille, int cross,
+                                                                int round, int last, const unsigned long long* __restrict__ pk_in,
+                                                                unsigned long long* __restrict__ pk_out,
+                                                                unsigned long long* __restrict__ best) {
+    __shared__ unsigned long long sk[4];
+    __shared__ int sp[4];
+    unsigned long long W = kNoKey;
+    int none = 0;
+    if (round > 0) {
+        if (threadIdx.x < gridDim.x) W = pk_in[threadIdx.x];
+        nms_block_min(W, none, sk, sp);
+        if (blockIdx.x == 0 && threadIdx.x == 0) best[round - 1] = W;
+        if (W == kNoKey || last) {  // workgroup-uniform
+            if (threadIdx.x == 0) pk_out[blockIdx.x] = kNoKey;
+            return;
+        }
+    }
+    const long long jw = (long long)(unsigned)W;
+    int4 w = make_int4(0, 0, -1, -1);
+    int ow = -1;
+    if (round > 0) { w = boxes[jw]; ow = jobj[jw]; }
+    const long long Aw = (long long)(w.z - w.x + 1) * (long long)(w.w - w.y + 1);
+    const long long n_chunks = (n + 255) / 256;
+    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
+    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
+    unsigned long long mk = kNoKey;
+    for (long long c = c0; c < c1; ++c) {
+        const long long idx = c * 256 + threadIdx.x;
+        if (idx >= n) continue;
+        const unsigned long long v = keys[idx];
+        if (v == kNoKey) continue;
+        bool drop = false;
+        if (round > 0) {
+            drop = idx == jw;
+            if (!drop) {
+                const int4 b = boxes[idx];
+                drop = nms_suppresses(b.x, b.y, b.z, b.w, w.x, w.y, w.z, w.w, Aw, jobj[idx] == ow ? permille : cross);
             }
         }
         if (drop) keys[idx] = kNoKey;
@@ -1772,6 +1946,7 @@ struct WinnersIn {
     float max_score;
     unsigned long long* keys;  // per job of the call, on the host: (bits of q << 32) | job, or kNoKey
     Foot* boxes;               // .. F(job)
+    const float* ms = nullptr;  // ("Objects") per template: the threshold of its object, in max_score's place (k_window_winners_objects)
 };
 
 // The jobs [j0, j1) of a call: their pairs prepared, their planes cut into batches, one upload, two kernels per batch and
@@ -1869,17 +2044,20 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
     const size_t np = W.nl.size();
     std::vector<ExTmpl> wtm(wn ? np : 0);
     std::vector<float> wneed(wn && wn->need && !gate_all ? np : 0);
+    std::vector<float> wms(wn && wn->ms ? np : 0);
     for (size_t u = 0; u < wtm.size(); ++u) {
         const size_t tmpl = (size_t)(W.key[u] / n);
         wtm[u] = ExTmpl{W.line0[u], W.nl[u], 0, -1, 0, -1, 0, bits_from_f(wn->den[tmpl])};
         if (!wneed.empty()) wneed[u] = wn->need[tmpl];
+        if (!wms.empty()) wms[u] = wn->ms[tmpl];
     }
     const size_t o_pl = al256(W.lines.size() * sizeof(ExLine)), o_it = o_pl + al256(planes.size() * sizeof(WinPlane)),
                  o_jt = o_it + al256(items.size() * sizeof(int2)), o_seg = o_jt + al256(jtab.size() * sizeof(WinJob)),
                  o_wtm = o_seg + al256(seg.size() * sizeof(int4)), o_wfoot = o_wtm + al256(wtm.size() * sizeof(ExTmpl)),
                  o_wneed = o_wfoot + al256(W.foot.size() * sizeof(Foot)), o_wlen = o_wneed + al256(wneed.size() * sizeof(float)),
                  o_wjob = o_wlen + (W.lens ? al256(W.len.size() * sizeof(float)) : 0), o_wrun = o_wjob + al256(wjob.size() * sizeof(WinnerJob)),
-                 o_best = o_wrun + al256(wrun.size() * sizeof(int)), o_cand = o_best + al256(nj * k * 8),
+                 o_wms = o_wrun + al256(wrun.size() * sizeof(int)), o_best = o_wms + al256(wms.size() * sizeof(float)),
+                 o_cand = o_best + al256(nj * k * 8),
                  o_wkeys = o_cand + al256(max_lists * k * 8), o_wboxes = o_wkeys + (wn ? al256(nj * 8) : 0),
                  total = o_wboxes + (wn ? al256(nj * sizeof(Foot)) : 0);
     reserve_eval(fm, total, o_cand);
@@ -1897,6 +2075,7 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
         if (W.lens) std::memcpy(h + o_wlen, W.len.data(), W.len.size() * sizeof(float));
         std::memcpy(h + o_wjob, wjob.data(), wjob.size() * sizeof(WinnerJob));
         std::memcpy(h + o_wrun, wrun.data(), wrun.size() * sizeof(int));
+        std::memcpy(h + o_wms, wms.data(), wms.size() * sizeof(float));
     }
     std::memset(h + o_best, 0xff, nj * k * 8);  // kNoKey
     hipStream_t st = fm->stream;
@@ -1917,7 +2096,15 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
                            (const unsigned long long*)cand, (const int4*)(d + o_seg) + B.s0, B.groups, 1, k, d_best);
         FDCM_HIP(hipGetLastError());
     }
-    if (wn) {  // (k = 1: a job's merged list is its winner)
+    if (wn && wn->ms) {  // (objects: the threshold per pair)
+        auto kern = W.buf32 ? k_window_winners_objects<true> : k_window_winners_objects<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
+                           fm->ty, (const ExLine*)d, (const float*)(d + o_wlen), (const ExTmpl*)(d + o_wtm), (const int4*)(d + o_wfoot),
+                           wneed.empty() ? (const float*)nullptr : (const float*)(d + o_wneed), (const float*)(d + o_wms),
+                           (const WinnerJob*)(d + o_wjob), (const int*)(d + o_wrun), (const unsigned long long*)d_best, (int)nj,
+                           (unsigned)j0, sx, sy, (unsigned long long*)(d + o_wkeys), (int4*)(d + o_wboxes));
+        FDCM_HIP(hipGetLastError());
+    } else if (wn) {  // (k = 1: a job's merged list is its winner)
         auto kern = W.buf32 ? k_window_winners<true> : k_window_winners<false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, st, vol, W.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
                            fm->ty, (const ExLine*)d, (const float*)(d + o_wlen), (const ExTmpl*)(d + o_wtm), (const int4*)(d + o_wfoot),
@@ -1925,6 +2112,8 @@ void windows_round(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rota
                            (const int*)(d + o_wrun), (const unsigned long long*)d_best, (int)nj, (unsigned)j0, sx, sy, wn->max_score,
                            (unsigned long long*)(d + o_wkeys), (int4*)(d + o_wboxes));
         FDCM_HIP(hipGetLastError());
+    }
+    if (wn) {
         FDCM_HIP(hipMemcpyAsync(wn->keys + j0, d + o_wkeys, nj * 8, hipMemcpyDeviceToHost, st));
         FDCM_HIP(hipMemcpyAsync(wn->boxes + j0, d + o_wboxes, nj * sizeof(Foot), hipMemcpyDeviceToHost, st));
     }
@@ -2224,6 +2413,15 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
 // a short list costs one batch and no round costs a host round trip.
 constexpr int kNmsBatch = 64;
 
+// What the calls with objects (include/fdcm.h, "Objects") take beside their siblings' arguments.
+struct ObjectsIn {
+    const int32_t* objects;    // per template
+    int G;
+    const float* max_score;    // per object
+    const float* min_matched;  // per object, or null: all 0
+    int cross;                 // the limit between entries of different objects, in permille
+};
+
 // TL_t (include/fdcm.h, "Detections by matched fraction"): the float32 sum of the template's line lengths in line order, from +0.
 void templates_matched_totals(const fdcm_templates* t, float* totals) {
     for (int64_t i = 0; i < t->T; ++i) {
@@ -2330,6 +2528,238 @@ void run_search_exhaustive_detect_all_matched(fdcm_featuremap* fm, const fdcm_te
                matched_out);
 }
 
+// ---- objects: the dense calls (include/fdcm.h, "Objects")
+// best_keys for G planes, one behind the other at o_keys, n_keys keys each in sub-tile order, all set to "no key" once.  The
+// template records go up twice: by pair, for the kernels that look a pair up (k_matched_gate, k_matched_plane,
+// k_matched_list), and object by object, each with slot = its pair, for one launch chain of k_exhaustive<., kBest*> per
+// object into that object's plane with that object's threshold (the scoring kernels read their bounds and needs by slot and
+// write the slot into the key, so they run as they are).  An object without templates queues nothing and keeps an empty
+// plane.  pobj: the object of every pair, for the rounds.  planes4: the 4-byte planes of G N floats a best map stages its
+// downloads in.  Returns false, with nothing queued, when no pair has a grid point.
+struct ObjectsRun : BestRun {
+    size_t o_sorted = 0, o_pobj = 0;
+    int G = 0;
+};
+
+static bool objects_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau,
+                         const ObjectsIn& ob, bool gate_all, bool want_tl, const std::vector<Foot>* foot, int list, bool planes4,
+                         ObjectsRun& R) {
+    const std::vector<float> den = best_denominators(t, penalty, tau);
+    const size_t np = P.nl.size();
+    const int G = ob.G;
+    auto obj_of = [&](size_t u) { return ob.objects[u / (size_t)n]; };
+    const bool bounded = std::any_of(ob.max_score, ob.max_score + G, [](float v) { return v < f_inf(); });
+    const bool gated = ob.min_matched && std::any_of(ob.min_matched, ob.min_matched + G, [](float v) { return v > 0.f; });
+    std::vector<float> bc(bounded ? np : 0);
+    for (size_t u = 0; u < bc.size(); ++u) bc[u] = exit_bound(score_bound(den[u / (size_t)n], ob.max_score[obj_of(u)]), P.nl[u]);
+    std::vector<ExTmpl> tm(np), sorted(np);
+    std::vector<int32_t> pobj(np);
+    std::vector<size_t> start((size_t)G + 1, 0);
+    bool any = false;
+    for (size_t u = 0; u < np; ++u) {
+        ExTmpl e = grid_tmpl(P, u, g, (int)u);
+        if (e.n == 0) { e.i0 = 0; e.i1 = -1; e.j0 = 0; e.j1 = -1; }
+        e.koff = bits_from_f(den[u / (size_t)n]);
+        any = any || (e.i0 <= e.i1 && e.j0 <= e.j1);
+        tm[u] = e;
+        pobj[u] = obj_of(u);
+        ++start[(size_t)pobj[u] + 1];
+    }
+    if (!any) return false;
+    for (int o = 0; o < G; ++o) start[(size_t)o + 1] += start[(size_t)o];
+    {
+        std::vector<size_t> at(start.begin(), start.end() - 1);
+        for (size_t u = 0; u < np; ++u) sorted[at[(size_t)pobj[u]]++] = tm[u];  // (pair order inside an object)
+    }
+    std::vector<float> need, tl;
+    if (gated || want_tl) {  // per pair: TL of its template and need = float32(min_matched[object] * TL)
+        std::vector<float> totals((size_t)t->T);
+        templates_matched_totals(t, totals.data());
+        tl.resize(np);
+        for (size_t u = 0; u < np; ++u) tl[u] = totals[u / (size_t)n];
+        if (gated) {
+            need.resize(np);
+            for (size_t u = 0; u < np; ++u) need[u] = ob.min_matched[obj_of(u)] * tl[u];
+        }
+    }
+    R.G = G;
+    R.tiles_x = (g.nx + kTileX - 1) / kTileX;
+    const size_t n_keys = (size_t)R.tiles_x * (size_t)((g.ny + kTileY - 1) / kTileY) * (kTileX * kTileY);
+    const size_t N = (size_t)g.nx * g.ny;
+    R.n_keys = n_keys;
+    R.o_tm = al256(P.lines.size() * sizeof(ExLine));
+    R.o_sorted = al256(R.o_tm + np * sizeof(ExTmpl));
+    R.o_foot = al256(R.o_sorted + np * sizeof(ExTmpl));
+    R.o_pobj = R.o_foot + (foot ? al256(np * sizeof(Foot)) : 0);
+    R.o_bc = R.o_pobj + (foot ? al256(np * sizeof(int32_t)) : 0);
+    R.o_len = R.o_bc + al256(bc.size() * sizeof(float));
+    R.o_need = R.o_len + (P.lens ? al256(P.len.size() * sizeof(float)) : 0);
+    R.o_tl = R.o_need + al256(need.size() * sizeof(float));
+    R.o_best = R.o_tl + (want_tl ? al256(np * sizeof(float)) : 0);
+    R.o_pair = R.o_best + al256((size_t)list * 8);
+    R.o_frac = R.o_pair + al256((size_t)list * 4);
+    R.o_keys = R.o_frac + al256((size_t)list * 4);
+    R.o_plane = R.o_keys + al256((size_t)G * n_keys * 8);
+    R.o_cand = R.o_plane + (planes4 ? al256((size_t)G * N * 4) : 0);
+    reserve_eval(fm, R.o_cand + (foot ? kNmsPartialBytes : 0), R.o_pair);
+    char* d = R.d = (char*)fm->search.eval.p;
+    char* h = (char*)fm->search.eval_stage.p;
+    std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
+    std::memcpy(h + R.o_tm, tm.data(), np * sizeof(ExTmpl));
+    std::memcpy(h + R.o_sorted, sorted.data(), np * sizeof(ExTmpl));
+    if (foot) {
+        std::memcpy(h + R.o_foot, foot->data(), np * sizeof(Foot));
+        std::memcpy(h + R.o_pobj, pobj.data(), np * sizeof(int32_t));
+    }
+    if (bounded) std::memcpy(h + R.o_bc, bc.data(), np * sizeof(float));
+    if (P.lens) std::memcpy(h + R.o_len, P.len.data(), P.len.size() * sizeof(float));
+    if (gated) std::memcpy(h + R.o_need, need.data(), np * sizeof(float));
+    if (want_tl) std::memcpy(h + R.o_tl, tl.data(), np * sizeof(float));
+    std::memset(h + R.o_best, 0xff, (size_t)list * 8);  // kNoKey
+    hipStream_t st = fm->stream;
+    FDCM_HIP(hipMemcpyAsync(d, h, R.o_pair, hipMemcpyHostToDevice, st));
+    FDCM_HIP(hipMemsetAsync(d + R.o_keys, 0xff, (size_t)G * n_keys * 8, st));  // no key anywhere, in any plane
+    for (int o = 0; o < G; ++o) {
+        const int cnt = (int)(start[(size_t)o + 1] - start[(size_t)o]);
+        if (cnt == 0) continue;
+        const float ms = ob.max_score[o];
+        const bool need_o = gate_all && gated && ob.min_matched[o] > 0.f;
+        launch<kBest>(fm, P, g, (const ExLine*)d, (const ExTmpl*)(d + R.o_sorted) + start[(size_t)o], cnt, 0, portions_for(fm, g, cnt),
+                      nullptr, (unsigned long long*)(d + R.o_keys) + (size_t)o * n_keys, ms < f_inf() ? (const float*)(d + R.o_bc) : nullptr,
+                      ms < f_inf() ? ms : 0.f, need_o ? (const float*)(d + R.o_need) : nullptr);
+    }
+    return true;
+}
+
+// Object best map (include/fdcm.h, "Objects"): run_best_map_gated per plane.  The arguments are checked (fdcm_capi.cpp).
+void run_best_map_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty,
+                          float tau, const int32_t* objects, int n_objects, const float* min_matched, float* score_out, int32_t* pair_out,
+                          float* matched_out) {
+    check_grid(g);
+    const size_t N = (size_t)g.nx * g.ny, GN = (size_t)n_objects * N;
+    auto none = [&]() {
+        if (score_out) std::fill(score_out, score_out + GN, f_nan());
+        if (pair_out) std::fill(pair_out, pair_out + GN, (int32_t)-1);
+        if (matched_out) std::fill(matched_out, matched_out + GN, f_nan());
+    };
+    if (t->T == 0) return none();
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int n = rot ? rot->n : 1;
+    if (rot) check_rotated_size(t, n);
+    Pairs P;
+    P.lens = matched_out != nullptr;
+    prepare_pairs(fm, t, rot, test_switches().matched_flat, P);
+    const std::vector<float> inf((size_t)n_objects, f_inf());
+    const ObjectsIn ob{objects, n_objects, inf.data(), min_matched, 0};
+    ObjectsRun R;
+    if (!objects_keys(fm, P, t, n, g, penalty, tau, ob, true, matched_out != nullptr, nullptr, kMaxK, true, R)) return none();
+    hipStream_t st = fm->stream;
+    char* plane = R.d + R.o_plane;  // G 4-byte planes: the scores, then the pairs, then the fractions
+    const dim3 grid((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4));
+    auto keys_of = [&](int o) { return (const unsigned long long*)(R.d + R.o_keys) + (size_t)o * R.n_keys; };
+    if (score_out) {
+        for (int o = 0; o < n_objects; ++o) {
+            hipLaunchKernelGGL(k_best_unpack, grid, dim3(256), 0, st, keys_of(o), g.nx, g.ny, R.tiles_x, (float*)plane + (size_t)o * N,
+                               (int*)nullptr);
+            FDCM_HIP(hipGetLastError());
+        }
+        FDCM_HIP(hipMemcpyAsync(score_out, plane, GN * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (pair_out) {
+        for (int o = 0; o < n_objects; ++o) {
+            hipLaunchKernelGGL(k_best_unpack, grid, dim3(256), 0, st, keys_of(o), g.nx, g.ny, R.tiles_x, (float*)nullptr,
+                               (int*)plane + (size_t)o * N);
+            FDCM_HIP(hipGetLastError());
+        }
+        FDCM_HIP(hipMemcpyAsync(pair_out, plane, GN * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (matched_out) {
+        auto kern = P.buf32 ? k_matched_plane<true> : k_matched_plane<false>;
+        for (int o = 0; o < n_objects; ++o) {
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, fm->vol.as<float>(), P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty,
+                               (const ExLine*)R.d, (const float*)(R.d + R.o_len), (const ExTmpl*)(R.d + R.o_tm),
+                               (const float*)(R.d + R.o_tl), keys_of(o), g.x0, g.y0, g.sx, g.sy, g.nx, g.ny, R.tiles_x,
+                               (float*)plane + (size_t)o * N);
+            FDCM_HIP(hipGetLastError());
+        }
+        FDCM_HIP(hipMemcpyAsync(matched_out, plane, GN * 4, hipMemcpyDeviceToHost, st));
+    }
+    FDCM_HIP(hipStreamSynchronize(st));
+}
+
+// Dense detections with objects (include/fdcm.h, "Objects"): detect_all on G planes.  The gate of FDCM_GATE_WINNER is
+// k_matched_gate on the planes of the objects with min_matched > 0; the rounds are k_nms_objects_round's over all planes,
+// queued kNmsBatch at a time; the fractions and the records are detect_all's.  The arguments are checked (fdcm_capi.cpp).
+void run_search_exhaustive_detect_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
+                                          const int32_t* objects, int n_objects, const float* max_score, const float* min_matched,
+                                          int max_det, int permille, int cross, int margin, int penalty, float tau, int gate_kind,
+                                          int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
+    check_grid(g);
+    *n_out = 0;
+    if (t->T == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    const int n = rot ? rot->n : 1;
+    if (rot) check_rotated_size(t, n);
+    const bool gate = min_matched && std::any_of(min_matched, min_matched + n_objects, [](float v) { return v > 0.f; });
+    const bool fracs = matched_out != nullptr, gate_all = gate && gate_kind == FDCM_GATE_ALL;
+    Pairs P;
+    P.lens = gate || fracs;
+    prepare_pairs(fm, t, rot, test_switches().matched_flat, P);
+    std::vector<Foot> foot(P.nl.size());
+    for (size_t u = 0; u < foot.size(); ++u)
+        foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    const ObjectsIn ob{objects, n_objects, max_score, min_matched, cross};
+    ObjectsRun R;
+    if (!objects_keys(fm, P, t, n, g, penalty, tau, ob, gate_all, fracs, &foot, max_det, false, R)) return;
+    hipStream_t st = fm->stream;
+    char* d = R.d;
+    const float* vol = fm->vol.as<float>();
+    unsigned long long* keys = (unsigned long long*)(d + R.o_keys);
+    if (gate && !gate_all) {
+        auto kern = P.buf32 ? k_matched_gate<true> : k_matched_gate<false>;
+        for (int o = 0; o < n_objects; ++o) {
+            if (!(min_matched[o] > 0.f)) continue;
+            hipLaunchKernelGGL(kern, dim3((unsigned)(R.n_keys / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+                               fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
+                               (const float*)(d + R.o_need), keys + (size_t)o * R.n_keys, (long long)R.n_keys, g.x0, g.y0, g.sx, g.sy,
+                               R.tiles_x);
+            FDCM_HIP(hipGetLastError());
+        }
+    }
+    unsigned long long* pk = (unsigned long long*)(d + R.o_cand);
+    int* pp = (int*)(d + R.o_cand + 2 * kNmsWorkgroups * 8);
+    unsigned long long* d_best = (unsigned long long*)(d + R.o_best);
+    const long long plane_chunks = (long long)(R.n_keys / 256), n_chunks = plane_chunks * n_objects;
+    const unsigned wgs = (unsigned)std::min<long long>(kNmsWorkgroups, n_chunks);
+    for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
+        const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));  // winners [.., r1) after this batch: whole batches
+        for (; r <= r1; ++r) {
+            const int in = (r + 1) & 1, to = r & 1;
+            hipLaunchKernelGGL(k_nms_objects_round, dim3(wgs), dim3(256), 0, st, keys, n_chunks, plane_chunks, g.x0, g.y0, g.sx, g.sy, g.nx,
+                               R.tiles_x, (const int4*)(d + R.o_foot), (const int*)(d + R.o_pobj), permille, cross, r, (int)(r == max_det),
+                               (const unsigned long long*)(pk + in * kNmsWorkgroups), (const int*)(pp + in * kNmsWorkgroups),
+                               pk + to * kNmsWorkgroups, pp + to * kNmsWorkgroups, d_best, (int*)(d + R.o_pair));
+            FDCM_HIP(hipGetLastError());
+        }
+        if (r > max_det) break;
+        unsigned long long last = kNoKey;  // winner r1 - 1, the batch's last
+        FDCM_HIP(hipMemcpyAsync(&last, d_best + (r1 - 1), 8, hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+        if (last == kNoKey) break;  // the list has ended: the entries from there on are kNoKey (written, or the upload's)
+    }
+    if (fracs) {
+        auto kern = P.buf32 ? k_matched_list<true> : k_matched_list<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((max_det + 255) / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
+                           fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
+                           (const float*)(d + R.o_tl), (const unsigned long long*)d_best, (const int*)(d + R.o_pair), max_det, g.x0, g.y0,
+                           g.sx, g.sy, g.nx, (float*)(d + R.o_frac));
+        FDCM_HIP(hipGetLastError());
+    }
+    detect_records(fm, R, P, rot != nullptr, n, g, max_det, base, out, n_out, foot.data(), boxes_out, fracs ? matched_out : nullptr);
+}
+
 float detect_score_bound(float den, float max_score) { return score_bound(den, max_score); }
 
 // B_t per template (include/fdcm.h): score_bound of best_denominators' den_t; 0 for a template without lines.  Host only.
@@ -2408,10 +2838,14 @@ static void matched_fractions_rounds(fdcm_featuremap* fm, const fdcm_templates* 
 // (e N_j + g) of its job's winner; its box is the list's; its fraction k_matched_fractions' at the record's pose, in a
 // round of its own after the last launch.  The 64-bit form follows FDCM_WINDOWS_FLAT and FDCM_MATCHED_FLAT.  gate
 // FDCM_GATE_ALL ("Gate inside the minimum") with min_matched > 0: the scoring kernel's gated form, and the winners' pass without need.
-void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot,
-                                          const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, float max_score, int max_det,
-                                          int permille, int margin, int penalty, float tau, float min_matched, int gate, int32_t base,
-                                          fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out, int32_t* jobs_out) {
+//
+// ob (ObjectsIn, or null): the threshold and the need of a job are its object's (max_score and min_matched are then unused),
+// the winners' pass is k_window_winners_objects and the rounds are k_nms_list_objects_round's, with the jobs' objects behind
+// the boxes in the same upload.  Without it the call queues what it queued before objects existed.
+static void detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
+                           int64_t n_jobs, int sx, int sy, float max_score, int max_det, int permille, int margin, int penalty, float tau,
+                           float min_matched, int gate, int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out,
+                           float* matched_out, int32_t* jobs_out, const ObjectsIn* ob) {
     *n_out = 0;
     if (n_jobs == 0 || t->T == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
@@ -2425,14 +2859,21 @@ void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templa
     std::vector<RotM> Mjob(rot ? (size_t)m0[nj] : 0);
     const std::vector<float> den = best_denominators(t, penalty, tau);
     std::vector<float> totals, need;
-    if (min_matched > 0.f) {  // need = float32(min_matched * TL) of the template
+    std::vector<float> ms;  // (objects) per template: its object's threshold
+    bool gated = min_matched > 0.f;
+    if (ob) {
+        gated = ob->min_matched && std::any_of(ob->min_matched, ob->min_matched + ob->G, [](float v) { return v > 0.f; });
+        ms.resize((size_t)t->T);
+        for (size_t i = 0; i < ms.size(); ++i) ms[i] = ob->max_score[ob->objects[i]];
+    }
+    if (gated) {  // need = float32(min_matched * TL) of the template
         totals.resize((size_t)t->T);
         templates_matched_totals(t, totals.data());
         need.resize(totals.size());
-        for (size_t i = 0; i < need.size(); ++i) need[i] = min_matched * totals[i];
+        for (size_t i = 0; i < need.size(); ++i) need[i] = (ob ? ob->min_matched[ob->objects[i]] : min_matched) * totals[i];
     }
     const WinnersIn wn{den.data(), need.empty() ? nullptr : need.data(), gate == FDCM_GATE_ALL, margin, max_score, keys.data(),
-                       boxes.data()};
+                       boxes.data(), ob ? ms.data() : nullptr};
     const bool flat = test_switches().windows_flat || test_switches().matched_flat;
     for (int64_t j0 = 0; j0 < n_jobs;) {
         const int64_t j1 = windows_round_end(t, jobs, j0, n_jobs, 1, true);
@@ -2442,12 +2883,15 @@ void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templa
     if (std::all_of(keys.begin(), keys.end(), [](unsigned long long v) { return v == kNoKey; })) return;
 
     // The rounds: the list (keys, boxes) and the result list (kNoKey) by one upload; two sets of partial minima behind them.
-    const size_t o_box = al256(nj * 8), o_best = o_box + al256(nj * sizeof(Foot)), o_pk = o_best + al256((size_t)max_det * 8);
+    const size_t o_box = al256(nj * 8), o_obj = o_box + al256(nj * sizeof(Foot)), o_best = o_obj + (ob ? al256(nj * 4) : 0),
+                 o_pk = o_best + al256((size_t)max_det * 8);
     reserve_eval(fm, o_pk + 2 * kNmsWorkgroups * 8, o_pk);
     char* d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
     std::memcpy(h, keys.data(), nj * 8);
     std::memcpy(h + o_box, boxes.data(), nj * sizeof(Foot));
+    if (ob)
+        for (size_t j = 0; j < nj; ++j) ((int32_t*)(h + o_obj))[j] = ob->objects[jobs[j].tmpl];
     std::memset(h + o_best, 0xff, (size_t)max_det * 8);  // kNoKey
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d, h, o_pk, hipMemcpyHostToDevice, st));
@@ -2457,9 +2901,15 @@ void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templa
     for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
         const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));
         for (; r <= r1; ++r) {
-            hipLaunchKernelGGL(k_nms_list_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
-                               (long long)n_jobs, permille, r, (int)(r == max_det),
-                               (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups, d_best);
+            if (ob)
+                hipLaunchKernelGGL(k_nms_list_objects_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
+                                   (const int*)(d + o_obj), (long long)n_jobs, permille, ob->cross, r, (int)(r == max_det),
+                                   (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups,
+                                   d_best);
+            else
+                hipLaunchKernelGGL(k_nms_list_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
+                                   (long long)n_jobs, permille, r, (int)(r == max_det),
+                                   (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups, d_best);
             FDCM_HIP(hipGetLastError());
         }
         if (r > max_det) break;
@@ -2503,6 +2953,26 @@ void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templa
         }
     }
     if (matched_out && !jl.empty()) matched_fractions_rounds(fm, t, rot, poses.data(), (int64_t)jl.size(), matched_out);
+}
+
+void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot,
+                                          const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, float max_score, int max_det,
+                                          int permille, int margin, int penalty, float tau, float min_matched, int gate, int32_t base,
+                                          fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out, int32_t* jobs_out) {
+    detect_windows(fm, t, rot, jobs, n_jobs, sx, sy, max_score, max_det, permille, margin, penalty, tau, min_matched, gate, base, out, n_out,
+                   boxes_out, matched_out, jobs_out, nullptr);
+}
+
+// Objects (include/fdcm.h, "Objects"): the arguments are checked (fdcm_capi.cpp), objects against the set included.
+void run_search_exhaustive_detect_windows_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot,
+                                                  const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, const int32_t* objects,
+                                                  int n_objects, const float* max_score, const float* min_matched, int max_det,
+                                                  int permille, int cross, int margin, int penalty, float tau, int gate, int32_t base,
+                                                  fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out,
+                                                  int32_t* jobs_out) {
+    const ObjectsIn ob{objects, n_objects, max_score, min_matched, cross};
+    detect_windows(fm, t, rot, jobs, n_jobs, sx, sy, 0.f, max_det, permille, margin, penalty, tau, 0.f, gate, base, out, n_out, boxes_out,
+                   matched_out, jobs_out, &ob);
 }
 
 // Line costs (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  Poses go in rounds of kCostPoses; a round

@@ -412,6 +412,21 @@ void run_search_exhaustive_detect_windows(fdcm_featuremap* fm, const fdcm_templa
                                           const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, float max_score, int max_det,
                                           int permille, int margin, int penalty, float tau, float min_matched, int gate, int32_t base,
                                           fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out, int32_t* jobs_out);
+// objects (include/fdcm.h, "Objects"): objects has T checked entries in [0, n_objects); max_score has n_objects floats, min_matched
+// n_objects floats or is null (all 0); the outputs are the siblings', the best map's planes n_objects times as large
+void run_best_map_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty,
+                          float tau, const int32_t* objects, int n_objects, const float* min_matched, float* score_out, int32_t* pair_out,
+                          float* matched_out);
+void run_search_exhaustive_detect_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
+                                          const int32_t* objects, int n_objects, const float* max_score, const float* min_matched,
+                                          int max_det, int permille, int cross, int margin, int penalty, float tau, int gate, int32_t base,
+                                          fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out);
+void run_search_exhaustive_detect_windows_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot,
+                                                  const fdcm_pose_window* jobs, int64_t n_jobs, int sx, int sy, const int32_t* objects,
+                                                  int n_objects, const float* max_score, const float* min_matched, int max_det,
+                                                  int permille, int cross, int margin, int penalty, float tau, int gate, int32_t base,
+                                                  fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out,
+                                                  int32_t* jobs_out);
 // poses: n x (tmpl, a, x, y), checked; *costs is malloc'ed; offsets: n + 1
 void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                     float** costs, int64_t* offsets);

@@ -43,6 +43,31 @@ def gate_kind(gate):
     raise ValueError('gate must be "winner" or "all"')
 
 
+def object_arrays(objects, n_objects, T, max_score, min_matched):
+    """(objects int32 (T,), G, max_score float32 (G,) or None, min_matched float32 (G,) or None) for the calls with objects
+    (include/fdcm.h, "Objects").  n_objects None: max(objects) + 1 (1 for an empty set).  max_score and min_matched: None, a
+    scalar for every object, or one value per object.  The library checks the values."""
+    obj = np.asarray(objects)
+    if obj.size and not np.issubdtype(obj.dtype, np.integer):
+        raise ValueError("objects must be integers, one per template")
+    obj = np.ascontiguousarray(obj.reshape(-1), dtype=np.int32)
+    if obj.shape[0] != T:
+        raise ValueError("one object label per template is required")
+    G = int(n_objects) if n_objects is not None else (int(obj.max()) + 1 if obj.size else 1)
+
+    def per_object(v, what):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float32)
+        if a.ndim == 0:
+            return np.full(max(G, 1), a, dtype=np.float32)
+        if a.ndim != 1 or a.shape[0] != G:
+            raise ValueError(what + " must be a scalar or one value per object")
+        return np.ascontiguousarray(a)
+
+    return obj, G, per_object(max_score, "max_score"), per_object(min_matched, "min_matched")
+
+
 def as_grid(grid):
     """capi.Grid from a capi.Grid or an (x0, y0, nx, ny, sx, sy) sequence."""
     if isinstance(grid, capi.Grid):
@@ -490,6 +515,78 @@ class DeviceFeatureMap:
         else:
             capi.check(capi.lib().fdcm_search_exhaustive_detect_all_gated(*head, kind, *tail))
         res = (_adopt_matches(out, n.value),) + ((fp[:n.value].copy(),) if boxes else ()) + ((fr[:n.value].copy(),) if matched else ())
+        return res if len(res) > 1 else res[0]
+
+    # ---- objects (include/fdcm.h, "Objects"): a best pair per (grid point, object), thresholds per object
+    def best_map_objects(self, templates, grid, objects, n_objects=None, cs=None, pivots=None, penalty=None, tau=1.0, min_matched=None,
+                         matched=False):
+        """(scores, pairs) as best_map's, one plane per object: (G, ny, nx) float32 and int32, plane o the best map of the
+        templates with objects[t] == o (NaN and -1 where none is a candidate; an object without templates has an empty
+        plane).  min_matched: None, a scalar or one value per object, the gate inside the minimum per object.  matched: also
+        the (G, ny, nx) float32 fractions of the winning pairs."""
+        obj, G, _, mm = object_arrays(objects, n_objects, templates.count, None, min_matched)
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        g = as_grid(grid)
+        shape = (G if 1 <= G <= 256 else 0, g.ny, g.nx)
+        scores, pairs = np.empty(shape, dtype=np.float32), np.empty(shape, dtype=np.int32)
+        frac = np.empty(shape, dtype=np.float32) if matched else None
+        capi.check(capi.lib().fdcm_best_map_objects(
+            self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), -1 if penalty is None else int(penalty),
+            float(tau), obj.ctypes.data_as(C.POINTER(C.c_int32)), G, capi.fptr(mm) if mm is not None else None, capi.fptr(scores),
+            pairs.ctypes.data_as(C.POINTER(C.c_int32)), capi.fptr(frac) if matched else None))
+        return (scores, pairs, frac) if matched else (scores, pairs)
+
+    def exhaustive_detect_objects(self, templates, grid, objects, max_score=float("inf"), n_objects=None, cs=None, pivots=None,
+                                  max_detections=1024, overlap_permille=300, cross_permille=None, margin=0, penalty=None, tau=1.0,
+                                  min_matched=None, tmpl_index_base=0, boxes=False, matched=False, gate="winner"):
+        """exhaustive_detect_all with objects (include/fdcm.h, "Objects"): the entries are (grid point, object), each with the
+        best pair among its object's templates; max_score and min_matched are a scalar or one value per object; a detection
+        drops an entry of its own object above overlap_permille and one of another object above cross_permille (None: the
+        same limit).  Raw match records in ascending order, then with boxes the (n, 4) int32 footprints and with matched
+        the (n,) float32 fractions."""
+        kind = gate_kind(gate)
+        obj, G, ms, mm = object_arrays(objects, n_objects, templates.count, max_score, min_matched)
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        g = as_grid(grid)
+        out, n = C.c_void_p(), C.c_int64()
+        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0
+        fp = np.zeros((md, 4), dtype=np.int32)
+        fr = np.zeros(md, dtype=np.float32)
+        capi.check(capi.lib().fdcm_search_exhaustive_detect_objects(
+            self._h, templates._h, C.byref(rot) if rot is not None else None, C.byref(g), obj.ctypes.data_as(C.POINTER(C.c_int32)), G,
+            capi.fptr(ms), capi.fptr(mm) if mm is not None else None, int(max_detections), int(overlap_permille),
+            int(overlap_permille if cross_permille is None else cross_permille), int(margin), -1 if penalty is None else int(penalty),
+            float(tau), kind, int(tmpl_index_base), C.byref(out), C.byref(n),
+            fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None, capi.fptr(fr) if matched and md else None))
+        res = (_adopt_matches(out, n.value),) + ((fp[:n.value].copy(),) if boxes else ()) + ((fr[:n.value].copy(),) if matched else ())
+        return res if len(res) > 1 else res[0]
+
+    def exhaustive_detect_windows_objects(self, templates, jobs, objects, max_score=float("inf"), n_objects=None, cs=None, pivots=None,
+                                          sx=1, sy=1, wrap=False, max_detections=1024, overlap_permille=300, cross_permille=None,
+                                          margin=0, penalty=None, tau=1.0, min_matched=None, tmpl_index_base=0, boxes=False,
+                                          matched=False, job_index=False, gate="winner"):
+        """exhaustive_detect_windows with objects (include/fdcm.h, "Objects"): a job's object is its template's; its threshold
+        and its need are that object's, and the greedy rule uses overlap_permille between jobs of one object and
+        cross_permille (None: the same) between jobs of different objects.  The outputs are exhaustive_detect_windows'."""
+        kind = gate_kind(gate)
+        obj, G, ms, mm = object_arrays(objects, n_objects, templates.count, max_score, min_matched)
+        jobs = as_pose_windows(jobs)
+        rot, keep = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        out, n = C.c_void_p(), C.c_int64()
+        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0
+        fp = np.zeros((md, 4), dtype=np.int32)
+        fr = np.zeros(md, dtype=np.float32)
+        ji = np.zeros(md, dtype=np.int32)
+        capi.check(capi.lib().fdcm_search_exhaustive_detect_windows_objects(
+            self._h, templates._h, C.byref(rot) if rot is not None else None, jobs.ctypes.data_as(C.POINTER(capi.PoseWindow)),
+            jobs.shape[0], int(sx), int(sy), int(bool(wrap)), obj.ctypes.data_as(C.POINTER(C.c_int32)), G, capi.fptr(ms),
+            capi.fptr(mm) if mm is not None else None, int(max_detections), int(overlap_permille),
+            int(overlap_permille if cross_permille is None else cross_permille), int(margin), -1 if penalty is None else int(penalty),
+            float(tau), kind, int(tmpl_index_base), C.byref(out), C.byref(n),
+            fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None, capi.fptr(fr) if matched and md else None,
+            ji.ctypes.data_as(C.POINTER(C.c_int32)) if job_index and md else None))
+        res = (_adopt_matches(out, n.value),) + ((fp[:n.value].copy(),) if boxes else ()) + ((fr[:n.value].copy(),) if matched else ())
+        res += (ji[:n.value].copy(),) if job_index else ()
         return res if len(res) > 1 else res[0]
 
     def matched_fractions(self, templates, poses, cs=None, pivots=None):

@@ -34,6 +34,7 @@ COVERED = {
     "fdcm_search_exhaustive_detect_all", "fdcm_search_exhaustive_detect_all_matched", "fdcm_search_exhaustive_windows",
     "fdcm_search_exhaustive_detect_windows", "fdcm_line_costs", "fdcm_matched_fractions", "fdcm_best_map_gated",
     "fdcm_search_exhaustive_detect_all_gated", "fdcm_search_exhaustive_detect_windows_gated",
+    "fdcm_best_map_objects", "fdcm_search_exhaustive_detect_objects", "fdcm_search_exhaustive_detect_windows_objects",
 }
 EXEMPT = {
     "fdcm_score_map_device": "fdcm_score_map's driver and workspace layout with the planes in the caller's device memory, which is "
@@ -237,6 +238,30 @@ def _gate_all(x, note):
     return out
 
 
+def _objects(x, note):
+    """Objects (include/fdcm.h): the object best map, the dense call under both gates and the windows' call, three objects
+    of which one is empty, thresholds and needs per object."""
+    out = []
+    jobs = x.c["jobs"]
+    obj, mm = [2, 0, 2, 0], [0.4, 0.0, 0.2]
+    for s in x.sets:
+        for cs, pv in x.rots():
+            g = x.small[0]
+            out += list(x.dev.best_map_objects(s, g, obj, 3, cs, pv, penalty=DEFAULT, min_matched=mm, matched=True))
+            for gate, ms in (("winner", [float("inf"), 0.0, x.threshold]), ("all", float("inf"))):
+                got = x.dev.exhaustive_detect_objects(s, g, obj, ms, 3, cs, pv, max_detections=MAX_DET, overlap_permille=300,
+                                                      cross_permille=600, margin=1, penalty=DEFAULT, min_matched=mm, boxes=True,
+                                                      matched=True, gate=gate)
+                note(len(got[0]), MAX_DET)
+                out += list(got)
+        got = x.dev.exhaustive_detect_windows_objects(s, jobs, obj, [float("inf"), 0.0, 1e30], 3, x.cs, x.piv, wrap=True,
+                                                      max_detections=MAX_DET, overlap_permille=300, cross_permille=600, margin=1,
+                                                      penalty=DEFAULT, min_matched=mm, boxes=True, matched=True, job_index=True)
+        note(len(got[0]), MAX_DET)
+        out += list(got)
+    return out
+
+
 def _windows(x, note):
     out = []
     jobs = x.c["jobs"]
@@ -281,7 +306,7 @@ CALLS = [
     ("exhaustive_detect_nms", _detect_nms), ("exhaustive_detect_all_inf", _detect_all(False)),
     ("exhaustive_detect_all_threshold", _detect_all(True)), ("exhaustive_detect_all_matched", _detect_all_matched),
     ("exhaustive_window_search", _windows), ("exhaustive_detect_windows", _detect_windows), ("line_costs", _line_costs), ("matched_fractions", _matched_fractions),
-    ("gate_all", _gate_all),
+    ("gate_all", _gate_all), ("objects", _objects),
 ]
 NAMES = [name for name, _ in CALLS]
 
