@@ -845,6 +845,53 @@ int fdcm_search_exhaustive_detect_windows_objects(const fdcm_featuremap* fm, con
                                                   float* matched_out /* max_detections, or NULL */,
                                                   int32_t* jobs_out /* max_detections, or NULL */);
 
+/* Hull footprints: a second footprint shape for the overlap rule, chosen per template set.  The box of an elongated part
+ * changes with its angle and is mostly empty at 45 degrees, so two parallel rods that share no pixel suppress each other
+ * there and not at 0 degrees; the hull of the posed end points turns with the part.  The definitions are this project's
+ * (README.md, "Hull footprints"; numpy statement: tests/hull_ref.py).  Everything not restated is taken unchanged from
+ * "Detections suppressed by footprint overlap" and its descendants: candidates, q, keys, the greedy rule, both limits of the
+ * objects' rule, records, gates, boxes_out.
+ * Kind: FDCM_FOOTPRINT_BOX (0, the default: today's rule) or FDCM_FOOTPRINT_HULL (1), a property of the template set
+ * (fdcm_templates_create_shaped; fdcm_templates_create and _create_capped make BOX sets).
+ * Vertices of a pair u = (t, a): the posed end points the searches score (float32; rot == NULL: the caller's lines as they
+ * are); with margin m each end point v contributes the four corners (floor(v.x) -+ m, floor(v.y) -+ m), every coordinate
+ * floored in int64 and clamped to [-2^25, 2^25] after the margin, which is the box's own arithmetic.  A template without lines,
+ * or with a NaN end point, has the empty shape; it is never a candidate.
+ * Shape P(u): the integer points of the closed convex hull of the vertices, stated row by row without a hull.  For an
+ * integer y between the least and the greatest vertex y take all ordered vertex pairs (p, q), p = q included, with p.y <= y
+ * <= q.y: a pair with p.y = q.y contributes both x, any other x* = p.x + (q.x - p.x)(y - p.y) / (q.y - p.y) as an exact
+ * rational.  xl(y) = ceil(min x*), xr(y) = floor(max x*); the row holds the pixels xl .. xr and is empty when xl > xr (a
+ * segment that passes between lattice points).  All products stay below 2^55: exact in int64.
+ * Consequences: the bounding box of P(u) is the box of fdcm_templates_footprints at the same margin, so boxes_out and
+ * fdcm_templates_footprints do not change for a hull set; A(u) = |P(u)| >= 1 for a pair with lines and no NaN.
+ * Overlap: F(g) = P(best(g)) + t_g;  I(g, h) = |F(g) n F(h)|, the sum over common rows of max(0, min(xr) - max(xl) + 1);
+ * U = A(g) + A(h) - I;  h suppresses g when 1000 I > permille U, in int64, permille being overlap_permille within an object
+ * and cross_permille across objects.
+ * Identities: (1) a BOX set gives the bytes it gave before hull sets existed, in every call.  (2) overlap_permille = 1000 (and
+ * cross_permille = 1000) gives the BOX records, whatever the kind.  (3) A set in which every template's posed end points
+ * include the four corners of their own bounding box gives the BOX records at any margin and overlap.  (4) overlap = cross
+ * = 0: no two returned shapes share a pixel (their boxes may).  (5) Identity (3) of "Objects" holds for a hull set.  (6)
+ * Results are a function of the inputs alone.  (7) n_objects = 1 gives the calls without objects, byte for byte.
+ * Calls that honour the kind: fdcm_search_exhaustive_detect_nms, _detect_all, _detect_all_matched, _detect_all_gated,
+ * _detect_objects, _detect_windows, _detect_windows_gated, _detect_windows_objects.  fdcm_search_exhaustive_detect (radius),
+ * every call without an overlap, fdcm_search, the pipeline and the shards ignore it.
+ * Span tables: fdcm_templates_footprint_spans and fdcm_lines_footprint_spans (host only, whatever the set's kind) give the
+ * shapes of every pair u = t n + a.  row_offsets: P + 1 int64 (P = T n); pair u has the rows row_offsets[u] ..
+ * row_offsets[u + 1], row r at y = box(u).y0 + (r - row_offsets[u]); areas: P int64, or NULL; spans: 2 int32 (xl, xr) per row
+ * in the frame of the box, (0, -1) for an empty row, or NULL to get offsets and areas only.
+ * FDCM_EINVAL, before any device work: footprint not 0 or 1; row_offsets NULL; everything the siblings reject; in the dense
+ * detection calls on a hull set a span table (the rows of every pair of the call) of more than 2^26 rows.  The windows'
+ * calls build the shapes of the winners that enter S_0 alone and apply the same limit to them once they are known. */
+#define FDCM_FOOTPRINT_BOX 0
+#define FDCM_FOOTPRINT_HULL 1
+int fdcm_templates_create_shaped(const float* lines, const int64_t* offsets, int64_t n_templates, const float* caps /* or NULL */,
+                                 int32_t footprint, fdcm_templates** out);
+int fdcm_templates_footprint_kind(const fdcm_templates* t, int32_t* kind);
+int fdcm_templates_footprint_spans(const fdcm_templates* t, const fdcm_rotations* rot /* or NULL */, int32_t margin,
+                                   int64_t* row_offsets, int64_t* areas /* or NULL */, int32_t* spans /* or NULL */);
+int fdcm_lines_footprint_spans(const float* lines, const int64_t* offsets, int64_t n_templates, const fdcm_rotations* rot /* or NULL */,
+                               int32_t margin, int64_t* row_offsets, int64_t* areas /* or NULL */, int32_t* spans /* or NULL */);
+
 /* ---- line segments from images (not in the reference, which reads its lines from .scene / .tmpl files; the definitions are
  *      this project's: README.md, "Line segments from images"; numpy statement: tests/lines_ref.py).  From a label image as
  *      fdcm_edge_labels makes it (m = the distinct keys of `depth`, a byte < m an edge pixel of that label, labels circular)

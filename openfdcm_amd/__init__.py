@@ -338,12 +338,13 @@ class _TemplateCache:
     on every call); here that would be a device upload per call.  A hit needs the same list object with the same
     line counts and the same bytes: the list is packed (one concatenate, ~0.3 ms for 1000 x 32 lines) and compared with
     what was uploaded, so a template edited in place is seen.  The per-line caps of the exhaustive calls (line_caps) are
-    part of the key: a list used without caps and then with them gets two handles.  Four entries are remembered;
+    part of the key: a list used without caps and then with them gets two handles.  So is the kind of footprint a list
+    carries (with_footprint): the same arrays, plain and wrapped, get two handles.  Four entries are remembered;
     `clear_template_cache()` drops them (each holds its list and a device copy alive)."""
     SLOTS = 4
 
     def __init__(self):
-        self._entries = []  # most recent first: (list object, line counts, packed lines, DeviceTemplates, caps bytes or None)
+        self._entries = []  # most recent first: (list object, line counts, packed lines, DeviceTemplates, (caps bytes or None, kind))
 
     def get(self, templates, line_caps=None):
         if isinstance(templates, DeviceTemplates):
@@ -360,7 +361,9 @@ class _TemplateCache:
             packed = _capi.pack_templates(templates)
             counts, data = packed[1].tolist(), packed[0]
         caps = _engine.flat_line_caps(templates, line_caps, counts)
-        ckey = None if caps is None else caps.tobytes()
+        kind = getattr(templates, "footprint", "box")
+        _engine.footprint_kind(kind)
+        ckey = (None if caps is None else caps.tobytes(), kind)
         for k, (obj, ecounts, edata, tset, ecaps) in enumerate(self._entries):
             if (obj is templates and tset._h and ecaps == ckey and ecounts == counts and edata.dtype == data.dtype
                     and edata.shape == data.shape and _np.array_equal(edata, data)):
@@ -372,7 +375,7 @@ class _TemplateCache:
             offsets = _np.zeros(len(counts) + 1, dtype=_np.int64)
             _np.cumsum(counts, out=offsets[1:])
             packed = (_np.ascontiguousarray(data.T, dtype=_np.float32).reshape(-1, 4), offsets)
-        tset = DeviceTemplates(templates, _packed=packed, _caps=caps)
+        tset = DeviceTemplates(templates, _packed=packed, _caps=caps, footprint=kind)
         self._entries.insert(0, (templates, counts, data, tset, ckey))
         del self._entries[self.SLOTS:]
         return tset
@@ -382,6 +385,24 @@ class _TemplateCache:
 
 
 _template_cache = _TemplateCache()
+
+
+class _ShapedTemplates(list):
+    """A template list that carries its kind of footprint (with_footprint)."""
+    footprint = "box"
+
+
+def with_footprint(templates, footprint):
+    """The template list with a kind of footprint, "box" or "hull" (include/fdcm.h, "Hull footprints"): a list of the same
+    arrays that every function taking `templates` accepts.  The detection calls with an `overlap` give the pairs of a "hull"
+    list the lattice points of the convex hull of their posed line end points as footprint, in place of the bounding box;
+    every other call treats the list as the plain one.  A DeviceTemplates takes the kind as its own keyword."""
+    _engine.footprint_kind(footprint)
+    if isinstance(templates, DeviceTemplates):
+        raise ValueError("with_footprint takes a template list: give the kind to DeviceTemplates(templates, footprint=...)")
+    out = _ShapedTemplates(templates)
+    out.footprint = footprint
+    return out
 
 
 def clear_template_cache():
@@ -734,6 +755,17 @@ def detect_score_bounds(templates, penalty, max_score):
     a template without lines.  No device work."""
     kind, tau = _penalty_args(penalty)
     return _template_cache.get(templates).score_bounds(max_score, penalty=kind, tau=tau)
+
+
+def template_footprint_spans(templates, angles=None, pivot="center", margin=0):
+    """The hull shapes of every template and angle (include/fdcm.h, "Hull footprints"), without a device: (row_offsets, spans,
+    areas).  Pair u = t A + a (A = 1 without angles) has the rows row_offsets[u] .. row_offsets[u + 1] of the (R, 2) int32
+    spans, row r at y = y0 of template_footprints(..)[t, a] + (r - row_offsets[u]), holding the pixels xl .. xr in the frame
+    of that box, (0, -1) when empty; areas[u] is its pixel count."""
+    from .engine import lines_footprint_spans
+    if angles is None:
+        return lines_footprint_spans(templates, margin=margin)
+    return lines_footprint_spans(templates, _angles(angles), _pivots(templates, pivot, len(templates)), margin=margin)
 
 
 def template_footprints(templates, angles=None, pivot="center", margin=0):

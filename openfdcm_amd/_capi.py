@@ -15,6 +15,7 @@ L2, L2_SQUARED, L1 = 0, 1, 2
 DEFAULT_OPTIMIZE, BATCH_OPTIMIZE, INDULGENT_OPTIMIZE = 0, 1, 2
 DEFAULT_PENALTY, EXPONENTIAL_PENALTY = 0, 1
 GATE_WINNER, GATE_ALL = 0, 1  # FDCM_GATE_WINNER, FDCM_GATE_ALL
+FOOTPRINT_BOX, FOOTPRINT_HULL = 0, 1  # FDCM_FOOTPRINT_BOX, FDCM_FOOTPRINT_HULL
 SHARDED_ALWAYS_COLLECTIVE = 1
 SHARDED_ALLOW_SAME_DEVICE = 2
 SHARD_TEMPLATES, SHARD_FRAMES = 0, 1
@@ -211,6 +212,11 @@ SYMBOLS = [
     ("fdcm_templates_footprints", C.c_int, [_vp, C.POINTER(Rotations), C.c_int32, C.POINTER(C.c_int32)]),
     ("fdcm_lines_footprints", C.c_int, [_fp, _i64p, C.c_int64, C.POINTER(Rotations), C.c_int32, C.POINTER(C.c_int32)]),
     ("fdcm_templates_create_capped", C.c_int, [_fp, _i64p, C.c_int64, _fp, C.POINTER(_vp)]),
+    ("fdcm_templates_create_shaped", C.c_int, [_fp, _i64p, C.c_int64, _fp, C.c_int32, C.POINTER(_vp)]),
+    ("fdcm_templates_footprint_kind", C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    ("fdcm_templates_footprint_spans", C.c_int, [_vp, C.POINTER(Rotations), C.c_int32, _i64p, _i64p, C.POINTER(C.c_int32)]),
+    ("fdcm_lines_footprint_spans", C.c_int, [_fp, _i64p, C.c_int64, C.POINTER(Rotations), C.c_int32, _i64p, _i64p,
+                                             C.POINTER(C.c_int32)]),
     ("fdcm_templates_line_caps", C.c_int, [_vp, _fp]),
     ("fdcm_templates_line_lengths", C.c_int, [_vp, _fp]),
     ("fdcm_line_costs", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.POINTER(C.c_float)),

@@ -462,13 +462,15 @@ int fdcm_featuremap_evaluate(const fdcm_featuremap* fm, const float* tmpl_lines,
 
 // ------------------------------------------------------------------------------------------ templates
 // caps: one per line or null (all +inf), checked by the caller
-static int create_templates(const float* lines, const int64_t* offsets, int64_t n_templates, const float* caps, fdcm_templates** out) {
+static int create_templates(const float* lines, const int64_t* offsets, int64_t n_templates, const float* caps, fdcm_templates** out,
+                            int32_t footprint = FDCM_FOOTPRINT_BOX) {
     fdcm_templates* t = nullptr;
     int rc = guarded([&] {
         require(out != nullptr, "out is null");
         require(n_templates >= 0 && (n_templates == 0 || offsets), "bad offsets");
         t = new fdcm_templates();
         t->device = g_device;
+        t->footprint = footprint;
         FDCM_HIP(hipSetDevice(t->device));
         t->T = n_templates;
         t->offsets.assign(n_templates + 1, 0);
@@ -533,6 +535,29 @@ int fdcm_templates_create_capped(const float* lines, const int64_t* offsets, int
     });
     if (rc != FDCM_OK) { if (out) *out = nullptr; return rc; }
     return create_templates(lines, offsets, n_templates, caps, out);
+}
+
+// Hull footprints: include/fdcm.h, "Hull footprints".  fdcm_templates_create_capped with the kind of footprint, checked first.
+int fdcm_templates_create_shaped(const float* lines, const int64_t* offsets, int64_t n_templates, const float* caps, int32_t footprint,
+                                 fdcm_templates** out) {
+    int rc = guarded([&] {
+        require(footprint == FDCM_FOOTPRINT_BOX || footprint == FDCM_FOOTPRINT_HULL, "footprint must be FDCM_FOOTPRINT_BOX or FDCM_FOOTPRINT_HULL");
+        require(out != nullptr, "out is null");
+        require(n_templates >= 0 && (n_templates == 0 || offsets), "bad offsets");
+        if (!caps || n_templates == 0) return;
+        require(offsets[0] == 0, "offsets[0] must be 0");
+        for (int64_t i = 0; i < n_templates; ++i) require(offsets[i] <= offsets[i + 1], "offsets must be ascending");
+        for (int64_t i = 0; i < offsets[n_templates]; ++i) require(caps[i] >= 0.f, "caps must be >= 0 or +inf, never NaN");
+    });
+    if (rc != FDCM_OK) { if (out) *out = nullptr; return rc; }
+    return create_templates(lines, offsets, n_templates, caps, out, footprint);
+}
+
+int fdcm_templates_footprint_kind(const fdcm_templates* t, int32_t* kind) {
+    return guarded([&] {
+        require(t && kind, "null argument");
+        *kind = t->footprint;
+    });
 }
 
 int fdcm_templates_line_caps(const fdcm_templates* t, float* caps) {
@@ -899,6 +924,7 @@ int fdcm_search_exhaustive_detect_nms(const fdcm_featuremap* fm, const fdcm_temp
         require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
         require(out && n_out, "null output");
         check_best_args(fm, templates, rot, grid, penalty, tau);
+        check_hull_rows(templates, rot, margin);
         records_call(out, [&] {
             run_search_exhaustive_detect_nms(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, k, overlap_permille, margin, penalty,
                                              tau, tmpl_index_base, out, boxes_out, n_out);
@@ -919,6 +945,7 @@ int fdcm_search_exhaustive_detect_all(const fdcm_featuremap* fm, const fdcm_temp
         require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
         require(out && n_out, "null output");
         check_best_args(fm, templates, rot, grid, penalty, tau);
+        check_hull_rows(templates, rot, margin);
         records_call(out, [&] {
             run_search_exhaustive_detect_all(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, max_score == 0.f ? 0.f : max_score,
                                              max_detections, overlap_permille, margin, penalty, tau, tmpl_index_base, out, n_out,
@@ -952,6 +979,7 @@ int fdcm_search_exhaustive_detect_all_gated(const fdcm_featuremap* fm, const fdc
         require(min_matched >= 0.f && min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
         require(out && n_out, "null output");
         check_best_args(fm, templates, rot, grid, penalty, tau);
+        check_hull_rows(templates, rot, margin);
         records_call(out, [&] {
             run_search_exhaustive_detect_all_matched(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid,
                                                      max_score == 0.f ? 0.f : max_score, max_detections, overlap_permille, margin, penalty,
@@ -1037,6 +1065,7 @@ int fdcm_search_exhaustive_detect_objects(const fdcm_featuremap* fm, const fdcm_
         check_object_planes(grid, n_objects);
         check_best_args(fm, templates, rot, grid, penalty, tau);
         check_object_labels(templates, objects, n_objects);
+        check_hull_rows(templates, rot, margin);
         records_call(out, [&] {
             run_search_exhaustive_detect_objects(const_cast<fdcm_featuremap*>(fm), templates, rot, *grid, objects, n_objects, ms.data(),
                                                  min_matched ? mm.data() : nullptr, max_detections, overlap_permille, cross_permille, margin,
@@ -1162,6 +1191,39 @@ int fdcm_lines_footprints(const float* lines, const int64_t* offsets, int64_t n_
         if (rot && rot->pivots)
             for (int64_t i = 0; i < 2 * n_templates; ++i) require(std::isfinite(rot->pivots[i]), "rotations: pivots must be finite");
         lines_footprints(lines, offsets, n_templates, rot, margin, boxes_out);
+    });
+}
+
+// Hull footprints: include/fdcm.h, "Hull footprints".  The footprints' checks with the three outputs: host only.
+int fdcm_templates_footprint_spans(const fdcm_templates* templates, const fdcm_rotations* rot, int32_t margin, int64_t* row_offsets,
+                                   int64_t* areas, int32_t* spans) {
+    return guarded([&] {
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        if (rot) check_rotations(rot);
+        require(row_offsets != nullptr, "row_offsets is null");
+        require(templates != nullptr, "templates is null");
+        require(templates->T * (int64_t)(rot ? rot->n : 1) <= 0x7fffffffll, "T * n_rot must be at most 2^31 - 1");
+        if (rot) check_pivots(templates, rot);
+        templates_footprint_spans(templates, rot, margin, row_offsets, areas, spans);
+    });
+}
+
+int fdcm_lines_footprint_spans(const float* lines, const int64_t* offsets, int64_t n_templates, const fdcm_rotations* rot, int32_t margin,
+                               int64_t* row_offsets, int64_t* areas, int32_t* spans) {
+    return guarded([&] {
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        if (rot) check_rotations(rot);
+        require(row_offsets != nullptr, "row_offsets is null");
+        require(n_templates >= 0 && (n_templates == 0 || offsets), "bad offsets");
+        row_offsets[0] = 0;
+        if (n_templates == 0) return;
+        require(offsets[0] == 0, "offsets[0] must be 0");
+        for (int64_t i = 0; i < n_templates; ++i) require(offsets[i] <= offsets[i + 1], "offsets must be ascending");
+        require(offsets[n_templates] == 0 || lines, "lines is null");
+        require(n_templates * (int64_t)(rot ? rot->n : 1) <= 0x7fffffffll, "T * n_rot must be at most 2^31 - 1");
+        if (rot && rot->pivots)
+            for (int64_t i = 0; i < 2 * n_templates; ++i) require(std::isfinite(rot->pivots[i]), "rotations: pivots must be finite");
+        lines_footprint_spans(lines, offsets, n_templates, rot, margin, row_offsets, areas, spans);
     });
 }
 

@@ -33,6 +33,10 @@
 //                                     objects (include/fdcm.h, "Objects"): the round of the greedy rule over G key planes, one
 //                                     per object, and over a winners' list with an object per job, each with one overlap limit
 //                                     within an object and one across objects; the winners' pass with a threshold per pair
+//   k_nms_hull_round, k_nms_hull_list_round
+//                                     hull footprints (include/fdcm.h, "Hull footprints"): the two rounds with objects on shapes,
+//                                     the lattice points of the convex hull of a pair's end points as row spans, for template
+//                                     sets of that kind; sets of kind BOX launch the rounds above
 //
 // Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP, EXIT, GATE>, the one statement of the sum (4 rows per lane
 // in k_exhaustive, 1 in k_exhaustive_windows).  GATE: the matched length of every slot beside its sum, by matched_length's
@@ -49,6 +53,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <thread>
 #include <type_traits>
 
@@ -1174,6 +1179,184 @@ __global__ void __launch_bounds__(256) k_nms_list_objects_round(unsigned long lo
     if (threadIdx.x == 0) pk_out[blockIdx.x] = mk;
 }
 
+// ---- hull footprints (include/fdcm.h, "Hull footprints"): the rounds above with the shape of an entry the lattice points of
+// the convex hull of its pair's posed end points, row by row.  A shape is its box (the rounds' own), its area and a run of
+// the span table: row r of the box is the pixels xl .. xr in the box's frame, (0, -1) when it is empty.  Two kernels, the
+// plane form and the list form of the rounds with objects; a call without objects runs them with one object (no table of
+// objects: every entry's object is 0), which gives the same list since one plane holds no two equal keys.
+struct HullShape {
+    long long area;  // A(u) = |P(u)|
+    int row0;        // its first row of the span table; it has y1 - y0 + 1 rows
+    int pad;
+};
+static_assert(sizeof(HullShape) == 16, "HullShape is 16 bytes");
+
+constexpr int kHullStagedRows = 1024;  // rows of the winner's spans a workgroup keeps in LDS (8 KB); a taller winner is read from memory
+
+// The winner's spans for its workgroup: staged when they fit.  Every thread of the workgroup calls it (round > 0).
+__device__ __forceinline__ bool hull_stage(const int2* __restrict__ spans, int row0, int rows, int2* ws) {
+    const bool staged = rows <= kHullStagedRows;  // workgroup-uniform
+    if (staged) {
+        for (int r = threadIdx.x; r < rows; r += 256) ws[r] = spans[row0 + r];
+        __syncthreads();
+    }
+    return staged;
+}
+
+// The overlap test on shapes, the one statement of it: the entry's shape (box f, area A, rows from f_row0) against the
+// winner's (box w, area Aw, rows from w_row0 or in ws).  Boxes that share no pixel never suppress each other; I <= I_box, so
+// 1000 I_box <= permille (A + Aw - I_box) proves the same without a span; else I is the sum over the common rows, in int64.
+__device__ __forceinline__ bool hull_suppresses(int fx0, int fy0, int fx1, int fy1, long long A, int f_row0, int wx0, int wy0, int wx1,
+                                                int wy1, long long Aw, int w_row0, bool staged, const int2* ws,
+                                                const int2* __restrict__ spans, int permille) {
+    const int ya = max(fy0, wy0), yb = min(fy1, wy1);
+    const int ix = min(fx1, wx1) - max(fx0, wx0) + 1, iy = yb - ya + 1;
+    if (ix <= 0 || iy <= 0) return false;
+    const long long Ibox = (long long)ix * (long long)iy;
+    if (1000ll * Ibox <= (long long)permille * (A + Aw - Ibox)) return false;
+    long long I = 0;
+    for (int y = ya; y <= yb; ++y) {
+        const int2 a = spans[f_row0 + (y - fy0)];
+        const int2 b = staged ? ws[y - wy0] : spans[w_row0 + (y - wy0)];
+        I += max(0, min(a.y + fx0, b.y + wx0) - max(a.x + fx0, b.x + wx0) + 1);
+    }
+    return 1000ll * I > (long long)permille * (A + Aw - I);
+}
+
+// k_nms_objects_round on shapes.  shapes: per pair; pobj null: one object.
+__global__ void __launch_bounds__(256) k_nms_hull_round(unsigned long long* keys, long long n_chunks, long long plane_chunks, int x0, int y0,
+                                                        int sx, int sy, int nx, int tiles_x, const int4* __restrict__ boxes,
+                                                        const HullShape* __restrict__ shapes, const int2* __restrict__ spans,
+                                                        const int* __restrict__ pobj, int permille, int cross, int round, int last,
+                                                        const unsigned long long* __restrict__ pk_in, const int* __restrict__ pp_in,
+                                                        unsigned long long* __restrict__ pk_out, int* __restrict__ pp_out,
+                                                        unsigned long long* __restrict__ best, int* __restrict__ pair) {
+    __shared__ unsigned long long sk[4];
+    __shared__ int sp[4];
+    __shared__ int2 ws[kHullStagedRows];
+    unsigned long long W = kNoKey;
+    int Wp = -1;
+    if (round > 0) {
+        if (threadIdx.x < gridDim.x) { W = pk_in[threadIdx.x]; Wp = pp_in[threadIdx.x]; }
+        nms_block_min_pair(W, Wp, sk, sp);
+        if (blockIdx.x == 0 && threadIdx.x == 0) { best[round - 1] = W; pair[round - 1] = W == kNoKey ? -1 : Wp; }
+        if (W == kNoKey || last) {  // workgroup-uniform
+            if (threadIdx.x == 0) { pk_out[blockIdx.x] = kNoKey; pp_out[blockIdx.x] = -1; }
+            return;
+        }
+    }
+    // the winner's object and shape (round 0: unused)
+    const unsigned gw = (unsigned)W;
+    int wx0 = 0, wy0 = 0, wx1 = -1, wy1 = -1, ow = -1, w_row0 = 0;
+    long long Aw = 0;
+    bool staged = false;
+    if (round > 0) {
+        const int4 b = boxes[Wp];
+        const HullShape s = shapes[Wp];
+        const int tx = x0 + (int)(gw % (unsigned)nx) * sx, ty = y0 + (int)(gw / (unsigned)nx) * sy;
+        wx0 = b.x + tx; wy0 = b.y + ty; wx1 = b.z + tx; wy1 = b.w + ty;
+        ow = pobj ? pobj[Wp] : 0;
+        Aw = s.area;
+        w_row0 = s.row0;
+        staged = hull_stage(spans, w_row0, b.w - b.y + 1, ws);
+    }
+    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
+    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
+    unsigned long long mk = kNoKey;
+    int mp = -1;
+    for (long long c = c0; c < c1; ++c) {
+        const long long idx = c * 256 + threadIdx.x;
+        const unsigned long long v = keys[idx];
+        if (v == kNoKey) continue;
+        const int o = (int)(c / plane_chunks);  // (wave-uniform)
+        const long long in_plane = idx - (long long)o * plane_chunks * 256;
+        const int tile = (int)(in_plane >> 10), r = (int)(in_plane & 1023);
+        const int i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
+        const int j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
+        const unsigned g = (unsigned)(j * nx + i);
+        const int u = (int)(unsigned)v;
+        bool drop = false;
+        if (round > 0) {
+            drop = g == gw && o == ow;
+            if (!drop) {
+                const int4 b = boxes[u];
+                const HullShape s = shapes[u];
+                const int tx = x0 + i * sx, ty = y0 + j * sy;
+                drop = hull_suppresses(b.x + tx, b.y + ty, b.z + tx, b.w + ty, s.area, s.row0, wx0, wy0, wx1, wy1, Aw, w_row0, staged, ws,
+                                       spans, o == ow ? permille : cross);
+            }
+        }
+        if (drop) {
+            keys[idx] = kNoKey;
+        } else {
+            const unsigned long long key = (v & 0xffffffff00000000ull) | g;
+            if (nms_pair_less(key, u, mk, mp)) { mk = key; mp = u; }
+        }
+    }
+    nms_block_min_pair(mk, mp, sk, sp);
+    if (threadIdx.x == 0) { pk_out[blockIdx.x] = mk; pp_out[blockIdx.x] = mp; }
+}
+
+// k_nms_list_objects_round on shapes.  shapes: per entry of the list, its box the list's own; jobj null: one object.
+__global__ void __launch_bounds__(256) k_nms_hull_list_round(unsigned long long* keys, const int4* __restrict__ boxes,
+                                                             const HullShape* __restrict__ shapes, const int2* __restrict__ spans,
+                                                             const int* __restrict__ jobj, long long n, int permille, int cross, int round,
+                                                             int last, const unsigned long long* __restrict__ pk_in,
+                                                             unsigned long long* __restrict__ pk_out,
+                                                             unsigned long long* __restrict__ best) {
+    __shared__ unsigned long long sk[4];
+    __shared__ int sp[4];
+    __shared__ int2 ws[kHullStagedRows];
+    unsigned long long W = kNoKey;
+    int none = 0;
+    if (round > 0) {
+        if (threadIdx.x < gridDim.x) W = pk_in[threadIdx.x];
+        nms_block_min(W, none, sk, sp);
+        if (blockIdx.x == 0 && threadIdx.x == 0) best[round - 1] = W;
+        if (W == kNoKey || last) {  // workgroup-uniform
+            if (threadIdx.x == 0) pk_out[blockIdx.x] = kNoKey;
+            return;
+        }
+    }
+    const long long jw = (long long)(unsigned)W;
+    int4 w = make_int4(0, 0, -1, -1);
+    int ow = -1, w_row0 = 0;
+    long long Aw = 0;
+    bool staged = false;
+    if (round > 0) {
+        w = boxes[jw];
+        const HullShape s = shapes[jw];
+        ow = jobj ? jobj[jw] : 0;
+        Aw = s.area;
+        w_row0 = s.row0;
+        staged = hull_stage(spans, w_row0, w.w - w.y + 1, ws);
+    }
+    const long long n_chunks = (n + 255) / 256;
+    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
+    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
+    unsigned long long mk = kNoKey;
+    for (long long c = c0; c < c1; ++c) {
+        const long long idx = c * 256 + threadIdx.x;
+        if (idx >= n) continue;
+        const unsigned long long v = keys[idx];
+        if (v == kNoKey) continue;
+        bool drop = false;
+        if (round > 0) {
+            drop = idx == jw;
+            if (!drop) {
+                const int4 b = boxes[idx];
+                const HullShape s = shapes[idx];
+                drop = hull_suppresses(b.x, b.y, b.z, b.w, s.area, s.row0, w.x, w.y, w.z, w.w, Aw, w_row0, staged, ws, spans,
+                                       (jobj ? jobj[idx] : 0) == ow ? permille : cross);
+            }
+        }
+        if (drop) keys[idx] = kNoKey;
+        else if (v < mk) mk = v;
+    }
+    nms_block_min(mk, none, sk, sp);
+    if (threadIdx.x == 0) pk_out[blockIdx.x] = mk;
+}
+
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // The integer translations t in [-kMaxCoord, kMaxCoord] with lo < fl(p + fl(off + t)) < hi for p = pmin and p = pmax, i.e.
@@ -1783,6 +1966,7 @@ struct BestRun {
     char* d = nullptr;  // search.eval
     size_t o_unit = 0, o_seg = 0, o_foot = 0, o_bc = 0, o_best = 0, o_pair = 0, o_keys = 0, o_plane = 0, o_cand = 0;
     size_t o_tm = 0, o_len = 0, o_need = 0, o_tl = 0, o_frac = 0;  // (the matched fraction's calls)
+    size_t o_hull = 0;  // (hull footprints) the shapes and the span table, behind everything else; staged behind o_pair
     size_t n_keys = 0;
     int tiles_x = 0, parts = 0;
 };
@@ -1804,7 +1988,7 @@ struct MatchedIn { const float* need; const float* tl; bool gate_all = false; };
 
 bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau, int k,
                BestRun& R, const std::vector<Foot>* foot = nullptr, int list = kMaxK, const float* max_score = nullptr,
-               const MatchedIn* mt = nullptr) {
+               const MatchedIn* mt = nullptr, size_t hull_bytes = 0) {
     const std::vector<float> den = best_denominators(t, penalty, tau);
     const size_t np = P.nl.size();
     std::vector<float> bc(max_score ? np : 0);
@@ -1841,7 +2025,8 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
     R.o_keys = R.o_frac + (mt ? al256((size_t)list * 4) : 0);
     R.o_plane = R.o_keys + al256(n_keys * 8);
     R.o_cand = R.o_plane + al256((size_t)g.nx * g.ny * 4);
-    reserve_eval(fm, R.o_cand + (foot ? kNmsPartialBytes : k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0), R.o_pair);
+    R.o_hull = al256(R.o_cand + (foot ? kNmsPartialBytes : k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0));
+    reserve_eval(fm, R.o_hull + hull_bytes, R.o_pair + hull_bytes);
     char* d = R.d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
     std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
@@ -1928,6 +2113,106 @@ Foot footprint(const float* p, size_t stride, int64_t n, int margin) {
         return (int32_t)std::min(std::max((int64_t)f + d, -lim), lim);
     };
     return Foot{at(mnx, -margin), at(mny, -margin), at(mxx, margin), at(mxy, margin)};
+}
+
+// ---- hull footprints: the host's tables (include/fdcm.h, "Hull footprints")
+struct HullPt { int64_t x, y; };
+
+// The convex hull of the vertices of the n lines at p (footprint's arguments): per end point the four corners
+// clamp(floor(v) -+ margin), the box's own arithmetic, so the hull's box is the footprint.  Counter-clockwise without
+// collinear points (monotone chain, cross products below 2^55); one point, or two for collinear vertices; empty for the
+// empty shape.
+void hull_of(const float* p, size_t stride, int64_t n, int margin, std::vector<HullPt>& h) {
+    h.clear();
+    std::vector<HullPt> v;
+    const int64_t lim = (int64_t)1 << 25;
+    auto at = [&](float c, int64_t d) {  // (footprint's)
+        const double f = std::min(std::max(std::floor((double)c), -1099511627776.0), 1099511627776.0);
+        return std::min(std::max((int64_t)f + d, -lim), lim);
+    };
+    for (int64_t q = 0; q < n; ++q, p += stride)
+        for (int c = 0; c < 2; ++c) {
+            if (std::isnan(p[2 * c]) || std::isnan(p[2 * c + 1])) return;
+            for (int k = 0; k < (margin ? 4 : 1); ++k)
+                v.push_back(HullPt{at(p[2 * c], k & 1 ? margin : -margin), at(p[2 * c + 1], k & 2 ? margin : -margin)});
+        }
+    std::sort(v.begin(), v.end(), [](const HullPt& a, const HullPt& b) { return a.x < b.x || (a.x == b.x && a.y < b.y); });
+    v.erase(std::unique(v.begin(), v.end(), [](const HullPt& a, const HullPt& b) { return a.x == b.x && a.y == b.y; }), v.end());
+    if (v.size() < 3) { h = v; return; }
+    auto cross = [](const HullPt& o, const HullPt& a, const HullPt& b) { return (a.x - o.x) * (b.y - o.y) - (a.y - o.y) * (b.x - o.x); };
+    h.resize(2 * v.size());
+    size_t k = 0;
+    for (size_t i = 0; i < v.size(); ++i) {  // lower chain
+        while (k >= 2 && cross(h[k - 2], h[k - 1], v[i]) <= 0) --k;
+        h[k++] = v[i];
+    }
+    for (size_t i = v.size() - 1, t = k + 1; i > 0; --i) {  // upper chain
+        while (k >= t && cross(h[k - 2], h[k - 1], v[i - 1]) <= 0) --k;
+        h[k++] = v[i - 1];
+    }
+    h.resize(k - 1);  // (the last point is the first)
+}
+
+// The rows of the shape whose box is F (footprint's, at the same margin): per row of the box xl = ceil(min x*), xr =
+// floor(max x*) over the hull's edges that reach the row, in the box's frame, (0, -1) for an empty row; into spans (2 int32
+// per row, or null).  The ends of a row of a convex polygon lie on its boundary, so the edges give what all vertex pairs give.
+// Returns the area.
+int64_t hull_rows(const std::vector<HullPt>& h, const Foot& F, int32_t* spans) {
+    int64_t area = 0;
+    const size_t m = h.size();
+    for (int64_t y = F.y0; y <= F.y1 && m > 0; ++y) {
+        int64_t xl = INT64_MAX, xr = INT64_MIN;
+        for (size_t e = 0; e < m; ++e) {
+            HullPt a = h[e], b = h[(e + 1) % m];
+            if (a.y > b.y) std::swap(a, b);
+            if (y < a.y || y > b.y) continue;
+            if (a.y == b.y) {
+                xl = std::min({xl, a.x, b.x});
+                xr = std::max({xr, a.x, b.x});
+            } else {  // x* = num / dy, exact
+                const int64_t dy = b.y - a.y, num = a.x * dy + (b.x - a.x) * (y - a.y);
+                xl = std::min<int64_t>(xl, -floor_div(-num, dy));
+                xr = std::max<int64_t>(xr, floor_div(num, dy));
+            }
+        }
+        const bool none = xl > xr;
+        if (!none) area += xr - xl + 1;
+        if (spans) {
+            int32_t* s = spans + 2 * (y - F.y0);
+            s[0] = none ? 0 : (int32_t)(xl - F.x0);
+            s[1] = none ? -1 : (int32_t)(xr - F.x0);
+        }
+    }
+    return area;
+}
+
+int64_t foot_rows(const Foot& F) { return F.y1 < F.y0 ? 0 : (int64_t)F.y1 - F.y0 + 1; }
+
+constexpr int64_t kHullMaxRows = (int64_t)1 << 26;  // of one call's span table: 512 MB
+
+// The shapes of the pairs of P, whose boxes are foot: the rows each has in the table (row0) first, so that the table can be
+// sized; then, while the device scores, the areas and the spans, written where the upload reads them.
+size_t hull_layout(const std::vector<Foot>& foot, std::vector<HullShape>& shapes) {
+    shapes.assign(foot.size(), HullShape{0, 0, 0});
+    int64_t rows = 0;
+    for (size_t u = 0; u < foot.size(); ++u) {
+        shapes[u].row0 = (int)rows;
+        rows += foot_rows(foot[u]);
+        if (rows > kHullMaxRows) throw std::string("hull footprints: the span table of the call has more than 2^26 rows");
+    }
+    return (size_t)rows;
+}
+
+void hull_fill(const Pairs& P, const std::vector<Foot>& foot, int margin, HullShape* shapes, int32_t* spans) {
+    const size_t np = foot.size();
+    const int nth = (int)std::max<size_t>(1, std::min<size_t>({16, np, P.lines.size() >> 10}));
+    on_threads(nth, "host preparation of the hull footprints failed", [&](int c) {
+        std::vector<HullPt> h;
+        for (size_t u = np * (size_t)c / (size_t)nth; u < np * (size_t)(c + 1) / (size_t)nth; ++u) {
+            hull_of((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin, h);
+            shapes[u].area = hull_rows(h, foot[u], spans + 2 * (size_t)shapes[u].row0);
+        }
+    });
 }
 
 // ---- pose windows: the host driver
@@ -2370,6 +2655,78 @@ void templates_footprints(const fdcm_templates* t, const fdcm_rotations* rot, in
     lines_footprints(t->lines.data(), t->offsets.data(), t->T, rot, margin, boxes_out);
 }
 
+// Hull footprints (include/fdcm.h): the shapes of every pair of a set given by its packed lines, as lines_footprints.
+void lines_footprint_spans(const float* lines, const int64_t* offsets, int64_t T, const fdcm_rotations* rot, int margin,
+                           int64_t* row_offsets, int64_t* areas, int32_t* spans) {
+    const int n = rot ? rot->n : 1;
+    std::vector<RotM> M((size_t)n);
+    std::vector<HullPt> h;
+    fdcm_templates one, rt;  // one template at a time, as lines_footprints
+    one.T = 1;
+    row_offsets[0] = 0;
+    for (int64_t i = 0; i < T; ++i) {
+        const int64_t l0 = offsets[i], nl = offsets[i + 1] - l0;
+        if (rot) {
+            one.lines.assign(lines + 4 * l0, lines + 4 * (l0 + nl));
+            one.offsets = {0, nl};
+            one.n_lines = nl;
+            const fdcm_rotations sub{rot->cs, rot->n, rot->pivots ? rot->pivots + 2 * i : nullptr};
+            rotated_set(&one, sub, 0, 1, rt, M.data());
+        }
+        for (int a = 0; a < n; ++a) {
+            const float* p = rot ? rt.lines.data() + (size_t)rt.offsets[(size_t)a] * 4 : lines + 4 * l0;
+            const Foot F = footprint(p, 4, nl, margin);
+            const int64_t u = i * n + a;
+            row_offsets[u + 1] = row_offsets[u] + foot_rows(F);
+            if (!areas && !spans) continue;
+            hull_of(p, 4, nl, margin, h);
+            const int64_t A = hull_rows(h, F, spans ? spans + 2 * row_offsets[u] : nullptr);
+            if (areas) areas[u] = A;
+        }
+    }
+}
+
+void templates_footprint_spans(const fdcm_templates* t, const fdcm_rotations* rot, int margin, int64_t* row_offsets, int64_t* areas,
+                               int32_t* spans) {
+    lines_footprint_spans(t->lines.data(), t->offsets.data(), t->T, rot, margin, row_offsets, areas, spans);
+}
+
+// The rows the span table of a dense call on a hull set would have: host only, for the check before any device work.
+void check_hull_rows(const fdcm_templates* t, const fdcm_rotations* rot, int margin) {
+    if (t->footprint != FDCM_FOOTPRINT_HULL || t->T == 0) return;
+    std::vector<int64_t> off((size_t)(t->T * (rot ? rot->n : 1)) + 1);
+    templates_footprint_spans(t, rot, margin, off.data(), nullptr, nullptr);
+    if (off.back() > kHullMaxRows) throw std::string("hull footprints: the span table of the call has more than 2^26 rows");
+}
+
+// Hull sets, the dense calls: the shapes of the call's pairs.  plan() before best_keys / objects_keys, which reserve bytes()
+// behind their own layout; upload() after them: the tables are built in the staging behind the first upload's bytes while the
+// scoring launches run, and go up on the same stream before the rounds; round() is one launch of k_nms_hull_round.
+struct HullRun {
+    std::vector<HullShape> shapes;
+    size_t rows = 0;
+    size_t o_spans() const { return al256(shapes.size() * sizeof(HullShape)); }
+    size_t bytes() const { return o_spans() + al256(rows * 8); }
+    void plan(const std::vector<Foot>& foot) { rows = hull_layout(foot, shapes); }
+    void upload(fdcm_featuremap* fm, const BestRun& R, const Pairs& P, const std::vector<Foot>& foot, int margin) {
+        char* h = (char*)fm->search.eval_stage.p + R.o_pair;
+        std::memcpy(h, shapes.data(), shapes.size() * sizeof(HullShape));
+        hull_fill(P, foot, margin, (HullShape*)h, (int32_t*)(h + o_spans()));
+        FDCM_HIP(hipMemcpyAsync(R.d + R.o_hull, h, bytes(), hipMemcpyHostToDevice, fm->stream));
+    }
+    void round(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, unsigned wgs, long long n_chunks, long long plane_chunks,
+               const int* pobj, int permille, int cross, int r, int last, unsigned long long* pk, int* pp) const {
+        const int in = (r + 1) & 1, to = r & 1;
+        char* d = R.d;
+        hipLaunchKernelGGL(k_nms_hull_round, dim3(wgs), dim3(256), 0, fm->stream, (unsigned long long*)(d + R.o_keys), n_chunks, plane_chunks,
+                           g.x0, g.y0, g.sx, g.sy, g.nx, R.tiles_x, (const int4*)(d + R.o_foot), (const HullShape*)(d + R.o_hull),
+                           (const int2*)(d + R.o_hull + o_spans()), pobj, permille, cross, r, last,
+                           (const unsigned long long*)(pk + in * kNmsWorkgroups), (const int*)(pp + in * kNmsWorkgroups),
+                           pk + to * kNmsWorkgroups, pp + to * kNmsWorkgroups, (unsigned long long*)(d + R.o_best), (int*)(d + R.o_pair));
+        FDCM_HIP(hipGetLastError());
+    }
+};
+
 // Detections by footprint overlap (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  The key plane is
 // best_keys', the rounds are k_nms_round's, the records run_search_exhaustive_detect's.
 void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
@@ -2388,8 +2745,12 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
     std::vector<Foot> foot(P.nl.size());
     for (size_t u = 0; u < foot.size(); ++u)
         foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
+    HullRun H;
+    if (hull) H.plan(foot);
     BestRun R;
-    if (!best_keys(fm, P, t, n, g, penalty, tau, k, R, &foot)) return;
+    if (!best_keys(fm, P, t, n, g, penalty, tau, k, R, &foot, kMaxK, nullptr, nullptr, hull ? H.bytes() : 0)) return;
+    if (hull) H.upload(fm, R, P, foot, margin);
     hipStream_t st = fm->stream;
     char* d = R.d;
     unsigned long long* pk = (unsigned long long*)(d + R.o_cand);
@@ -2397,6 +2758,10 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
     const long long n_chunks = (long long)(R.n_keys / 256);  // whole sub-tiles: a multiple of 4
     const unsigned wgs = (unsigned)std::min<long long>(kNmsWorkgroups, n_chunks);
     for (int r = 0; r <= k; ++r) {
+        if (hull) {
+            H.round(fm, R, g, wgs, n_chunks, n_chunks, nullptr, permille, permille, r, (int)(r == k), pk, pp);
+            continue;
+        }
         const int in = (r + 1) & 1, to = r & 1;
         hipLaunchKernelGGL(k_nms_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)(d + R.o_keys), n_chunks, g.x0, g.y0, g.sx, g.sy,
                            g.nx, R.tiles_x, (const int4*)(d + R.o_foot), permille, r, (int)(r == k),
@@ -2465,11 +2830,15 @@ static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
     }
     const bool gate_all = gate && gate_kind == FDCM_GATE_ALL;  // the gate inside the minimum: no gate pass
     const MatchedIn mt{gate ? need.data() : nullptr, fracs ? tl.data() : nullptr, gate_all};
+    const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
+    HullRun H;
+    if (hull) H.plan(foot);
     BestRun R;
     // (+inf is no threshold: the plane is the best map's own, by the kernel without the checks)
     if (!best_keys(fm, P, t, n, g, penalty, tau, 0, R, &foot, max_det, max_score < f_inf() ? &max_score : nullptr,
-                   P.lens ? &mt : nullptr))
+                   P.lens ? &mt : nullptr, hull ? H.bytes() : 0))
         return;
+    if (hull) H.upload(fm, R, P, foot, margin);
     hipStream_t st = fm->stream;
     char* d = R.d;
     const float* vol = fm->vol.as<float>();
@@ -2489,6 +2858,10 @@ static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
     for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
         const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));  // winners [.., r1) after this batch: whole batches
         for (; r <= r1; ++r) {
+            if (hull) {
+                H.round(fm, R, g, wgs, n_chunks, n_chunks, nullptr, permille, permille, r, (int)(r == max_det), pk, pp);
+                continue;
+            }
             const int in = (r + 1) & 1, to = r & 1;
             hipLaunchKernelGGL(k_nms_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)(d + R.o_keys), n_chunks, g.x0, g.y0, g.sx,
                                g.sy, g.nx, R.tiles_x, (const int4*)(d + R.o_foot), permille, r, (int)(r == max_det),
@@ -2543,7 +2916,7 @@ struct ObjectsRun : BestRun {
 
 static bool objects_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau,
                          const ObjectsIn& ob, bool gate_all, bool want_tl, const std::vector<Foot>* foot, int list, bool planes4,
-                         ObjectsRun& R) {
+                         ObjectsRun& R, size_t hull_bytes = 0) {
     const std::vector<float> den = best_denominators(t, penalty, tau);
     const size_t np = P.nl.size();
     const int G = ob.G;
@@ -2601,7 +2974,8 @@ static bool objects_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templat
     R.o_keys = R.o_frac + al256((size_t)list * 4);
     R.o_plane = R.o_keys + al256((size_t)G * n_keys * 8);
     R.o_cand = R.o_plane + (planes4 ? al256((size_t)G * N * 4) : 0);
-    reserve_eval(fm, R.o_cand + (foot ? kNmsPartialBytes : 0), R.o_pair);
+    R.o_hull = al256(R.o_cand + (foot ? kNmsPartialBytes : 0));
+    reserve_eval(fm, R.o_hull + hull_bytes, R.o_pair + hull_bytes);
     char* d = R.d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
     std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
@@ -2711,8 +3085,12 @@ void run_search_exhaustive_detect_objects(fdcm_featuremap* fm, const fdcm_templa
     for (size_t u = 0; u < foot.size(); ++u)
         foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
     const ObjectsIn ob{objects, n_objects, max_score, min_matched, cross};
+    const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
+    HullRun H;
+    if (hull) H.plan(foot);
     ObjectsRun R;
-    if (!objects_keys(fm, P, t, n, g, penalty, tau, ob, gate_all, fracs, &foot, max_det, false, R)) return;
+    if (!objects_keys(fm, P, t, n, g, penalty, tau, ob, gate_all, fracs, &foot, max_det, false, R, hull ? H.bytes() : 0)) return;
+    if (hull) H.upload(fm, R, P, foot, margin);
     hipStream_t st = fm->stream;
     char* d = R.d;
     const float* vol = fm->vol.as<float>();
@@ -2736,6 +3114,10 @@ void run_search_exhaustive_detect_objects(fdcm_featuremap* fm, const fdcm_templa
     for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
         const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));  // winners [.., r1) after this batch: whole batches
         for (; r <= r1; ++r) {
+            if (hull) {
+                H.round(fm, R, g, wgs, n_chunks, plane_chunks, (const int*)(d + R.o_pobj), permille, cross, r, (int)(r == max_det), pk, pp);
+                continue;
+            }
             const int in = (r + 1) & 1, to = r & 1;
             hipLaunchKernelGGL(k_nms_objects_round, dim3(wgs), dim3(256), 0, st, keys, n_chunks, plane_chunks, g.x0, g.y0, g.sx, g.sy, g.nx,
                                R.tiles_x, (const int4*)(d + R.o_foot), (const int*)(d + R.o_pobj), permille, cross, r, (int)(r == max_det),
@@ -2882,8 +3264,48 @@ static void detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const f
     }
     if (std::all_of(keys.begin(), keys.end(), [](unsigned long long v) { return v == kNoKey; })) return;
 
+    // Hull sets: the shapes of the entries of S_0 alone, built here on the host once the winners are known.  An entry's shape
+    // is its pair's (tmpl, a_j), a function of the pair and the margin: distinct pairs are built once, from the lines
+    // prepare_pairs makes, and every entry of a pair points at the same rows.
+    const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
+    std::vector<HullShape> shapes;
+    std::vector<int32_t> spans;
+    if (hull) {
+        shapes.assign(nj, HullShape{0, 0, 0});
+        std::map<int64_t, HullShape> done;
+        std::vector<HullPt> hp;
+        fdcm_templates rt;
+        RotM M1;
+        for (size_t j = 0; j < nj; ++j) {
+            if (keys[j] == kNoKey) continue;
+            const fdcm_pose_window& J = jobs[j];
+            const int a = (int)((J.a0 + (int64_t)((uint32_t)raw[j] / (uint32_t)(J.nx * J.ny))) % n);
+            const int64_t u = (int64_t)J.tmpl * n + a;
+            auto it = done.find(u);
+            if (it == done.end()) {
+                const int64_t l0 = t->offsets[(size_t)J.tmpl], nl = t->offsets[(size_t)J.tmpl + 1] - l0;
+                const float* p = t->lines.data() + 4 * l0;
+                if (rot) {
+                    const fdcm_rotations sub{rot->cs + 2 * a, 1, rot->pivots};
+                    rotated_set(t, sub, J.tmpl, J.tmpl + 1, rt, &M1);
+                    p = rt.lines.data();
+                }
+                const Foot F = footprint(p, 4, nl, margin);
+                const size_t row0 = spans.size() / 2;
+                if ((int64_t)row0 + foot_rows(F) > kHullMaxRows)
+                    throw std::string("hull footprints: the span table of the call has more than 2^26 rows");
+                spans.resize(spans.size() + 2 * (size_t)foot_rows(F));
+                hull_of(p, 4, nl, margin, hp);
+                const int64_t A = hull_rows(hp, F, spans.data() + 2 * row0);
+                it = done.emplace(u, HullShape{A, (int)row0, 0}).first;
+            }
+            shapes[j] = it->second;
+        }
+    }
+
     // The rounds: the list (keys, boxes) and the result list (kNoKey) by one upload; two sets of partial minima behind them.
-    const size_t o_box = al256(nj * 8), o_obj = o_box + al256(nj * sizeof(Foot)), o_best = o_obj + (ob ? al256(nj * 4) : 0),
+    const size_t o_box = al256(nj * 8), o_obj = o_box + al256(nj * sizeof(Foot)), o_shape = o_obj + (ob ? al256(nj * 4) : 0),
+                 o_spans = o_shape + (hull ? al256(nj * sizeof(HullShape)) : 0), o_best = o_spans + (hull ? al256(spans.size() * 4) : 0),
                  o_pk = o_best + al256((size_t)max_det * 8);
     reserve_eval(fm, o_pk + 2 * kNmsWorkgroups * 8, o_pk);
     char* d = (char*)fm->search.eval.p;
@@ -2892,6 +3314,10 @@ static void detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const f
     std::memcpy(h + o_box, boxes.data(), nj * sizeof(Foot));
     if (ob)
         for (size_t j = 0; j < nj; ++j) ((int32_t*)(h + o_obj))[j] = ob->objects[jobs[j].tmpl];
+    if (hull) {
+        std::memcpy(h + o_shape, shapes.data(), nj * sizeof(HullShape));
+        std::memcpy(h + o_spans, spans.data(), spans.size() * 4);
+    }
     std::memset(h + o_best, 0xff, (size_t)max_det * 8);  // kNoKey
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d, h, o_pk, hipMemcpyHostToDevice, st));
@@ -2901,7 +3327,13 @@ static void detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const f
     for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
         const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));
         for (; r <= r1; ++r) {
-            if (ob)
+            if (hull)
+                hipLaunchKernelGGL(k_nms_hull_list_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
+                                   (const HullShape*)(d + o_shape), (const int2*)(d + o_spans), ob ? (const int*)(d + o_obj) : nullptr,
+                                   (long long)n_jobs, permille, ob ? ob->cross : permille, r, (int)(r == max_det),
+                                   (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups,
+                                   d_best);
+            else if (ob)
                 hipLaunchKernelGGL(k_nms_list_objects_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
                                    (const int*)(d + o_obj), (long long)n_jobs, permille, ob->cross, r, (int)(r == max_det),
                                    (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups,

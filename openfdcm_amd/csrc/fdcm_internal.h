@@ -295,7 +295,8 @@ struct fdcm_templates {
     std::vector<float> lengths;     // per line: getLength, math.h:306-308
     std::vector<float> caps;        // per line: the cap of its cost in the exhaustive calls, +inf for none (include/fdcm.h)
     bool capped = false;            // some cap is finite: the exhaustive calls take their clamping kernels
-    std::vector<int32_t> sorted;    // per template: line indices by descending length (argsort, math.h:106-116)
+    int32_t footprint = 0;          // FDCM_FOOTPRINT_BOX or _HULL: the shape the overlap rule gives its pairs (include/fdcm.h)
+    std::vector<int32_t> sorted;   // per template: line indices by descending length (argsort, math.h:106-116)
     fdcm::DevBuf d_lines, d_offsets, d_lengths, d_sorted;
 };
 
@@ -404,6 +405,13 @@ float detect_score_bound(float den, float max_score);  // the same for one denom
 // host only: 4 int32 per pair t n + a (rot null: n = 1, the lines as they are)
 void templates_footprints(const fdcm_templates* t, const fdcm_rotations* rot, int margin, int32_t* boxes_out);
 void lines_footprints(const float* lines, const int64_t* offsets, int64_t T, const fdcm_rotations* rot, int margin, int32_t* boxes_out);
+// host only (include/fdcm.h, "Hull footprints"): the hull shapes of every pair; areas and spans may be null
+void templates_footprint_spans(const fdcm_templates* t, const fdcm_rotations* rot, int margin, int64_t* row_offsets, int64_t* areas,
+                               int32_t* spans);
+void lines_footprint_spans(const float* lines, const int64_t* offsets, int64_t T, const fdcm_rotations* rot, int margin,
+                           int64_t* row_offsets, int64_t* areas, int32_t* spans);
+// host only: throws when a dense detection call on the hull set t would need a span table of more than 2^26 rows
+void check_hull_rows(const fdcm_templates* t, const fdcm_rotations* rot, int margin);
 void run_search_exhaustive_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
                                    int64_t n_jobs, int sx, int sy, int k, int32_t base, fdcm_match** out, int64_t* n_out,
                                    int64_t* job_offsets);

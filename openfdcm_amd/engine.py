@@ -678,18 +678,55 @@ def lines_footprints(templates, cs=None, pivots=None, margin=0):
     return out
 
 
+FOOTPRINT_KINDS = {"box": capi.FOOTPRINT_BOX, "hull": capi.FOOTPRINT_HULL}
+
+
+def footprint_kind(name):
+    """The FDCM_FOOTPRINT_* value of "box" or "hull"; ValueError for anything else."""
+    if not isinstance(name, str) or name not in FOOTPRINT_KINDS:
+        raise ValueError(f'footprint must be "box" or "hull", got {name!r}')
+    return FOOTPRINT_KINDS[name]
+
+
+def _spans_result(T, n, call):
+    """(row_offsets, spans, areas) of a span call: the offsets and areas first, then the spans into an array of that size."""
+    off = np.zeros(T * n + 1, dtype=np.int64)
+    areas = np.zeros(T * n, dtype=np.int64)
+    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+    call(i64(off), i64(areas) if areas.size else None, None)
+    spans = np.zeros((int(off[-1]), 2), dtype=np.int32)
+    if spans.size:
+        call(i64(off), None, spans.ctypes.data_as(C.POINTER(C.c_int32)))
+    return off, spans, areas
+
+
+def lines_footprint_spans(templates, cs=None, pivots=None, margin=0):
+    """DeviceTemplates.footprint_spans for a plain list of line arrays: no handle and no device."""
+    flat, offsets = capi.pack_templates(templates)
+    T = len(offsets) - 1
+    rot, keep = _rotations(cs, pivots, T) if cs is not None else (None, None)
+    return _spans_result(T, 1 if rot is None else rot.n, lambda off, areas, spans: capi.check(capi.lib().fdcm_lines_footprint_spans(
+        capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)), T, C.byref(rot) if rot is not None else None, int(margin), off,
+        areas, spans)))
+
+
 class DeviceTemplates:
     """Owns an fdcm_templates handle: a list of LineArrays resident in HBM.  line_caps (None, a scalar tau or one float
     array per template: flat_line_caps) gives every line a cap of its cost in the exhaustive calls (include/fdcm.h, "Per-line
-    caps and line costs"); search() and the rest of the reference path ignore it."""
+    caps and line costs"); search() and the rest of the reference path ignore it.  footprint ("box" or "hull": include/fdcm.h,
+    "Hull footprints") is the shape the detection calls with an overlap give the set's pairs; every other call ignores it."""
 
-    def __init__(self, templates, line_caps=None, _packed=None, _caps=None):
+    def __init__(self, templates, line_caps=None, _packed=None, _caps=None, footprint="box"):
+        kind = footprint_kind(footprint)
         flat, offsets = _packed if _packed is not None else capi.pack_templates(templates)
         self.count = len(offsets) - 1
         self.n_lines = int(offsets[-1])
         caps = _caps if _caps is not None else flat_line_caps(templates, line_caps, np.diff(offsets).tolist())
         h = C.c_void_p()
-        if caps is None:
+        if kind != capi.FOOTPRINT_BOX:
+            capi.check(capi.lib().fdcm_templates_create_shaped(capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)), self.count,
+                                                               capi.fptr(caps) if caps is not None else None, kind, C.byref(h)))
+        elif caps is None:
             capi.check(capi.lib().fdcm_templates_create(capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)),
                                                         self.count, C.byref(h)))
         else:
@@ -709,6 +746,21 @@ class DeviceTemplates:
         out = np.zeros(self.n_lines, dtype=np.float32)
         capi.check(capi.lib().fdcm_templates_line_lengths(self._h, capi.fptr(out)))
         return [out[a:b] for a, b in zip(self._offsets[:-1], self._offsets[1:])]
+
+    @property
+    def footprint(self):
+        """"box" or "hull": the set's kind of footprint (fdcm_templates_footprint_kind)."""
+        kind = C.c_int32()
+        capi.check(capi.lib().fdcm_templates_footprint_kind(self._h, C.byref(kind)))
+        return {v: k for k, v in FOOTPRINT_KINDS.items()}[kind.value]
+
+    def footprint_spans(self, cs=None, pivots=None, margin=0):
+        """The hull shapes of every (template, rotation) pair u = t n + a, whatever the set's kind: (row_offsets, spans, areas).
+        Pair u has the rows row_offsets[u] .. row_offsets[u + 1] of spans, row r at y = y0 of footprints()[u] + (r -
+        row_offsets[u]), its pixels xl .. xr in the frame of that box, (0, -1) when the row is empty.  Host only."""
+        rot, keep = _rotations(cs, pivots, self.count) if cs is not None else (None, None)
+        return _spans_result(self.count, 1 if rot is None else rot.n, lambda off, areas, spans: capi.check(
+            capi.lib().fdcm_templates_footprint_spans(self._h, C.byref(rot) if rot is not None else None, int(margin), off, areas, spans)))
 
     def footprints(self, cs=None, pivots=None, margin=0):
         """(T, n, 4) int32 footprints x0, y0, x1, y1 of every (template, rotation) pair (n = 1 with cs None: the lines as
