@@ -201,6 +201,39 @@ int fdcm_featuremap_build_image_staged(const uint8_t* image, int64_t width, int6
                                        int threshold, int64_t border, int64_t depth, float dt3_coeff, int distance,
                                        int stop_after, fdcm_featuremap** out);
 
+/* ---- image pyramid: the image reduced by 2^level on the device, and the feature map of a level, for coarse-to-fine detection
+ *      (Python: exhaustive_detect_pyramid).  All integer.
+ * Level images: P_0 = I, the caller's image.  W_(l+1) = (W_l + 1) >> 1, H_(l+1) likewise.  P_(l+1)(x, y) = S2(P_l)(2x, 2y),
+ *   S2 the smooth = 2 image above: (sum_ij w(i) w(j) P_l(clamp(2x+i), clamp(2y+j)) + 128) >> 8 with w = [1 4 6 4 1] and the
+ *   coordinates clamped to P_l (replicate border).  Pixel x of level l is pixel 2^l x of level 0: there is no half-pixel shift.
+ *   0 <= level <= 12; a side of 1 stays 1.
+ * Feature map of level l: by definition fdcm_featuremap_build_image_ex of the image P_l with the same params, border, depth,
+ *   dt3_coeff and distance -- border in level-l pixels, size (W_l + 2b, H_l + 2b), scene translation (b, b).  level = 0 is
+ *   that call, byte for byte.  The levels between live in a workspace of the handle (two buffers, level l + 1 made from level
+ *   l by one kernel) and are freed with it.  The input sizes stay within 1 .. 4096.
+ * Lifting a level-l record to level 0.  Search the level-l map with every template end point and pivot multiplied by 2^-l
+ *   (exact in float32).  Every product and sum of M_a (the record's rotation part and its offset m = p - R p) is then the
+ *   level-0 value times 2^-l exactly -- a power of two scales every operand of every rounding alike, and no underflow is
+ *   reachable for |coordinate| < 2^24 -- so m_l = 2^-l m, and fl(m_l.x + t_l.x) * 2^l = fl(m.x + 2^l t_l.x).  A level-l
+ *   record whose transform[2] and transform[5] are multiplied by 2^l is therefore bit for bit the record a level-0 search
+ *   emits for the translation 2^l t_l and the same angle.  Angles, orientation bins and caps given as one scalar follow
+ *   exactly: dy / dx is unchanged and lengths are multiplied by 2^-l.  Scores do NOT carry over between levels.
+ * Argument errors besides the _ex siblings': level outside [0, 12], a size outside [1, 4096], NULL image, out or params:
+ *   FDCM_EINVAL before any GPU work.  Like their siblings the builds return once queued, and with on_device = 1 the image is
+ *   read in place while they run. ---- */
+/* The size of level `level` of a width x height image.  Host only. */
+int fdcm_image_pyramid_size(int64_t width, int64_t height, int32_t level, int64_t* w_out, int64_t* h_out);
+/* P_level into out: W_l * H_l bytes, rows contiguous, host memory or (out_on_device = 1) memory of the current device.  Level
+ * 0 copies the image with its rows packed.  Blocks until out is written. */
+int fdcm_image_pyramid_level(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                             int32_t level, uint8_t* out, int out_on_device);
+int fdcm_featuremap_build_image_level(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device,
+                                      int32_t level, const fdcm_edge_params* params, int64_t border, int64_t depth,
+                                      float dt3_coeff, int distance, fdcm_featuremap** out);
+int fdcm_featuremap_rebuild_image_level(fdcm_featuremap* fm, const uint8_t* image, int64_t width, int64_t height,
+                                        int64_t row_stride, int on_device, int32_t level, const fdcm_edge_params* params,
+                                        int64_t border);
+
 /* ---- the feature-map plug-in seam: what a FeatureMapInstance specialises besides getFeatureSize
  *      (featuremap.h:27-52; FeatureMapModel<T> forwards to them, featuremap.h:80-92) and what every optimiser of the
  *      reference calls (defaultoptimize.cpp:26,49-64, batchoptimize.cpp:27,58-62).  With these three a reference

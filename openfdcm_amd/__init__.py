@@ -13,7 +13,7 @@ import numpy as _np
 from . import _capi
 from .matchlist import Match, MatchList, records_of  # noqa: F401
 from . import engine as _engine
-from .engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, ShardedEngine, edge_labels, lines_from_image, lines_from_labels, search_raw, topk  # noqa: F401  (extensions)
+from .engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, ShardedEngine, edge_labels, image_pyramid, image_pyramid_size, lines_from_image, lines_from_labels, search_raw, topk  # noqa: F401  (extensions)
 
 __version__ = "0.10.0"  # API level of the reference this mirrors (openfdcm.cpp:43)
 
@@ -408,6 +408,7 @@ def with_footprint(templates, footprint):
 def clear_template_cache():
     """Forget the template lists uploaded on behalf of search() / get_template_lengths() (extension)."""
     _template_cache.clear()
+    _scaled_lists.clear()
 
 
 def search(matcher, searcher, optimizer, featuremap, templates, scene):
@@ -912,6 +913,156 @@ def exhaustive_detect_refined(featuremap, templates, max_score, coarse_angles, f
                                      max_detections=max_detections, penalty=penalty, pivot=pivot, wrap=wrap, line_caps=line_caps,
                                      margin=margin, min_matched=min_matched, return_boxes=return_boxes,
                                      return_matched=return_matched, return_jobs=return_jobs, gate=gate)
+
+
+# ---------------------------------------------------------------- image pyramid: coarse-to-fine over levels (extension)
+def build_image_featuremap_level(image, level, params=None, threshold=60, border=0, low=None, smooth=0, min_pixels=1):
+    """build_image_featuremap of level `level` (0 to 12) of `image` (include/fdcm.h, "image pyramid"): by definition the feature
+    map of image_pyramid(image, level) with the same options, the levels made on the device in a workspace of the handle.
+    border is in the level's pixels: feature size (W_l + 2 border, H_l + 2 border), scene translation (border, border)."""
+    import ctypes as C
+    params = params if params is not None else Dt3CpuParameters()
+    dev = C.c_int()
+    _capi.check(_capi.lib().fdcm_get_device(C.byref(dev)))
+    key = ("image", int(params.depth), float(params.dt3_coeff), int(params.distance), dev.value, "level", int(level))
+    fm = _featuremap_pool.take(key)
+    if fm is None:
+        fm = DeviceFeatureMap.build_image_level(image, level, threshold, border=border, depth=key[1], coeff=key[2], distance=key[3],
+                                                low=low, smooth=smooth, min_pixels=min_pixels)
+    else:
+        try:
+            fm.rebuild_image_level(image, level, threshold, border=border, low=low, smooth=smooth, min_pixels=min_pixels)
+        except Exception:
+            fm.close()
+            raise
+    out = Dt3Cpu(None, _device=fm)
+    out._pool_key = key
+    return out
+
+
+def _level_factor(level, sign):
+    level = int(level)
+    if not 0 <= level <= 12:
+        raise ValueError("level must be in [0, 12]")
+    return _np.float32(2.0 ** (sign * level))
+
+
+def scaled_templates(templates, level):
+    """The template list of pyramid level `level`: the same list with every coordinate multiplied by float32(2^-level), which
+    is exact.  A list from with_footprint keeps its kind.  Searched on the level's feature map, its records lift to the
+    level-0 records of the unscaled list (lift_records)."""
+    if isinstance(templates, DeviceTemplates):
+        raise ValueError("scaled_templates takes a template list, not a DeviceTemplates")
+    f = _level_factor(level, -1)
+    out = [_np.asarray(t, dtype=_np.float32) * f for t in templates]
+    kind = getattr(templates, "footprint", None)
+    return out if kind is None else with_footprint(out, kind)
+
+
+def lift_records(records, level):
+    """A copy of the records of a search on pyramid level `level` (a MatchList or its record array) as level-0 records:
+    transform[2] and transform[5] multiplied by float32(2^level), everything else unchanged.  For a search of
+    scaled_templates(templates, level) with pivots scaled alike, the result is bit for bit what a level-0 search of
+    `templates` emits for the translation 2^level t and the same angle (include/fdcm.h, "image pyramid")."""
+    f = _level_factor(level, 1)
+    rec = records_of(records)
+    rec["transform"][:, 2] *= f
+    rec["transform"][:, 5] *= f
+    return MatchList(rec) if isinstance(records, MatchList) else rec
+
+
+_scaled_lists = []  # most recent first: (list object, level, its scaled list), so that a list searched again finds its upload
+
+
+def _scaled_cached(templates, level):
+    """scaled_templates(templates, level), as the list object an earlier call made when it holds the same bytes: the template
+    cache goes by the list object, and a fresh list per call would be a device upload per call."""
+    small = scaled_templates(templates, level)
+    for k, (obj, lvl, cached) in enumerate(_scaled_lists):
+        if (obj is templates and lvl == int(level) and len(cached) == len(small)
+                and getattr(cached, "footprint", None) == getattr(small, "footprint", None)
+                and all(a.shape == b.shape and _np.array_equal(a.view(_np.uint32), b.view(_np.uint32)) for a, b in zip(cached, small))):
+            if k:
+                _scaled_lists.insert(0, _scaled_lists.pop(k))
+            return cached
+    _scaled_lists[:] = [e for e in _scaled_lists if not (e[0] is templates and e[1] == int(level))]
+    _scaled_lists.insert(0, (templates, int(level), small))
+    del _scaled_lists[_TemplateCache.SLOTS:]
+    return small
+
+
+def _pyramid_coarse_args(templates, level, pivot, half_x, half_y, coarse_max_score, coarse_margin, margin):
+    small = _scaled_cached(templates, level)
+    pv = template_pivots(templates, pivot)
+    pv_small = None if pv is None else pv * _level_factor(level, -1)
+    hx = 2 ** int(level) if half_x is None else half_x
+    hy = 2 ** int(level) if half_y is None else half_y
+    cms = float("inf") if coarse_max_score is None else coarse_max_score
+    cm = -(-int(margin) >> int(level)) if coarse_margin is None else coarse_margin
+    return small, pv, pv_small, hx, hy, cms, cm
+
+
+def exhaustive_detect_pyramid(featuremap, level_featuremap, level, templates, max_score, coarse_angles, fine_angles, half_angles,
+                              half_x=None, half_y=None, coarse_stride=1, coarse_max_score=None, coarse_overlap=1.0,
+                              coarse_max_detections=1024, coarse_line_caps=None, coarse_margin=None, overlap=0.3, stride=1,
+                              max_detections=1024, penalty=None, pivot="center", wrap=False, line_caps=None, margin=0,
+                              min_matched=None, return_boxes=False, return_matched=False, return_jobs=False, gate="winner"):
+    """exhaustive_detect_refined with its coarse pass on a pyramid level: level_featuremap is the map of the frame reduced by
+    2^level (build_image_featuremap_level, or build_cpu_featuremap(scene * 2^-level) for a scene given as lines), featuremap the
+    full-resolution one.  Pure Python, and by definition exactly this composition:
+      small = scaled_templates(templates, level)
+      pv = template_pivots(templates, pivot)                     # None stays None; small's pivots are pv * 2^-level, exact
+      seeds_L = exhaustive_detect_all(level_featuremap, small, coarse_max_score (None: inf), overlap=coarse_overlap,
+                                      stride=coarse_stride, max_detections=coarse_max_detections, penalty=penalty,
+                                      angles=coarse_angles, pivot=None if pv is None else pv * 2^-level,
+                                      line_caps=coarse_line_caps, margin=coarse_margin (None: -(-margin >> level)))
+      seeds = lift_records(seeds_L, level)
+      jobs = pose_windows(seeds, coarse_angles, fine_angles, pv, half_angles, half_x (None: 2^level), half_y (None: 2^level),
+                          stride=stride, wrap=wrap)
+      exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=overlap, angles=fine_angles, stride=stride,
+                                max_detections=max_detections, penalty=penalty, pivot=pivot, wrap=wrap, line_caps=line_caps,
+                                margin=margin, min_matched=min_matched, return_boxes=.., return_matched=.., return_jobs=..,
+                                gate=gate)
+    The coarse pass runs at stride 1 on a map with 4^-level of the pixels, so neighbouring lanes read neighbouring pixels again.
+    A lifted seed is bit for bit the level-0 record of the translation 2^level t, so pose_windows reads it by its own rule; the
+    default half widths cover the 2^level pixels a level pixel stands for.  Scores do not carry over between levels: the coarse
+    stage has its own threshold, caps and margin.  return_jobs indexes the seeds."""
+    _engine.gate_kind(gate)
+    small, pv, pv_small, hx, hy, cms, cm = _pyramid_coarse_args(templates, level, pivot, half_x, half_y, coarse_max_score,
+                                                                coarse_margin, margin)
+    seeds_l = exhaustive_detect_all(level_featuremap, small, cms, overlap=coarse_overlap, stride=coarse_stride,
+                                    max_detections=coarse_max_detections, penalty=penalty, angles=coarse_angles, pivot=pv_small,
+                                    line_caps=coarse_line_caps, margin=cm)
+    jobs = pose_windows(lift_records(seeds_l, level), coarse_angles, fine_angles, pv, half_angles, hx, hy, stride=stride, wrap=wrap)
+    return exhaustive_detect_windows(featuremap, templates, jobs, max_score, overlap=overlap, angles=fine_angles, stride=stride,
+                                     max_detections=max_detections, penalty=penalty, pivot=pivot, wrap=wrap, line_caps=line_caps,
+                                     margin=margin, min_matched=min_matched, return_boxes=return_boxes,
+                                     return_matched=return_matched, return_jobs=return_jobs, gate=gate)
+
+
+def exhaustive_detect_pyramid_objects(featuremap, level_featuremap, level, templates, objects, max_score, coarse_angles, fine_angles,
+                                      half_angles, half_x=None, half_y=None, coarse_stride=1, coarse_max_score=None,
+                                      coarse_overlap=1.0, coarse_cross_overlap=None, coarse_max_detections=1024,
+                                      coarse_line_caps=None, coarse_margin=None, overlap=0.3, cross_overlap=None, stride=1,
+                                      max_detections=1024, penalty=None, pivot="center", wrap=False, line_caps=None, margin=0,
+                                      min_matched=None, return_boxes=False, return_matched=False, return_jobs=False,
+                                      n_objects=None, return_objects=False, gate="winner"):
+    """exhaustive_detect_pyramid with objects: the same composition over exhaustive_detect_objects (on level_featuremap, with
+    cross_overlap=coarse_cross_overlap and n_objects) and exhaustive_detect_windows_objects, with the keywords of
+    exhaustive_detect_refined_objects."""
+    _engine.gate_kind(gate)
+    small, pv, pv_small, hx, hy, cms, cm = _pyramid_coarse_args(templates, level, pivot, half_x, half_y, coarse_max_score,
+                                                                coarse_margin, margin)
+    seeds_l = exhaustive_detect_objects(level_featuremap, small, objects, cms, overlap=coarse_overlap,
+                                        cross_overlap=coarse_cross_overlap, stride=coarse_stride,
+                                        max_detections=coarse_max_detections, penalty=penalty, angles=coarse_angles, pivot=pv_small,
+                                        line_caps=coarse_line_caps, margin=cm, n_objects=n_objects)
+    jobs = pose_windows(lift_records(seeds_l, level), coarse_angles, fine_angles, pv, half_angles, hx, hy, stride=stride, wrap=wrap)
+    return exhaustive_detect_windows_objects(featuremap, templates, jobs, objects, max_score, overlap=overlap, cross_overlap=cross_overlap,
+                                             angles=fine_angles, stride=stride, max_detections=max_detections, penalty=penalty,
+                                             pivot=pivot, wrap=wrap, line_caps=line_caps, margin=margin, min_matched=min_matched,
+                                             return_boxes=return_boxes, return_matched=return_matched, return_jobs=return_jobs,
+                                             n_objects=n_objects, return_objects=return_objects, gate=gate)
 
 
 # ---------------------------------------------------------------- objects: many views of a few parts (extension)

@@ -118,6 +118,12 @@ SYMBOLS = [
                                                  C.c_int64, C.c_float, C.c_int, C.POINTER(_vp)]),
     ("fdcm_featuremap_rebuild_image_ex", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(EdgeParams),
                                                    C.c_int64]),
+    ("fdcm_image_pyramid_size", C.c_int, [C.c_int64, C.c_int64, C.c_int32, _i64p, _i64p]),
+    ("fdcm_image_pyramid_level", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int32, _vp, C.c_int]),
+    ("fdcm_featuremap_build_image_level", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.POINTER(EdgeParams),
+                                                    C.c_int64, C.c_int64, C.c_float, C.c_int, C.POINTER(_vp)]),
+    ("fdcm_featuremap_rebuild_image_level", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int32,
+                                                      C.POINTER(EdgeParams), C.c_int64]),
     ("fdcm_featuremap_minmax_translation", C.c_int, [_vp, _fp, C.c_int64, _fp, _fp]),
     ("fdcm_featuremap_minmax_translation_batch", C.c_int, [_vp, _fp, _i64p, C.c_int64, _fp, _fp]),
     ("fdcm_featuremap_evaluate", C.c_int, [_vp, _fp, _i64p, C.c_int64, _fp, _i64p, _fp]),

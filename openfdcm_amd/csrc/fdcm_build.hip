@@ -601,12 +601,19 @@ BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after) {
     L.off_keys = L.off_integral + align16(plan.integral.size() * sizeof(IntegralDesc));
     L.off_slice = L.off_keys + align16(plan.keys.size() * sizeof(float));
     L.off_pixels = L.off_slice + align16(plan.slice_first.size() * sizeof(int32_t));
-    L.off_cost = L.off_pixels + align16(plan.seeds.on_device ? 0 : plan.seeds.bytes());  // (pixels in front of the cost: one copy takes them)
+    L.off_cost = L.off_pixels + align16(plan.seeds.on_device ? 0 : plan.seeds.source_bytes());  // (pixels in front of the cost: one copy takes them)
     L.plan = L.off_cost + align16((size_t)L.nchunks * sizeof(int32_t));
     if (L.empty) return L;
     if (plan.seeds.kind != SeedKind::lines && HW64 > 64) throw std::string("feature maps from images or labels are limited to 4096 x 4096");
     if (plan.seeds.kind == SeedKind::image) L.labels = plan.seeds.bytes();
     if (plan.seeds.kind == SeedKind::image && !plan.seeds.edge_plain()) L.edge_parent = L.edge_roots = plan.seeds.bytes() * 4;
+    if (plan.seeds.level > 0) {
+        int64_t w1, h1, w2, h2;
+        pyramid_size(plan.seeds.width0, plan.seeds.height0, 1, &w1, &h1);
+        pyramid_size(w1, h1, 1, &w2, &h2);
+        L.pyr_b = align16((size_t)(w1 * h1));
+        L.pyr = L.pyr_b + (size_t)(w2 * h2);
+    }
     const size_t ncols = (size_t)m * W, islices = (size_t)m * ivol_slice_floats(W, H);
     L.vol = islices * sizeof(float);  // the transforms, and later the integrated volume, interleaved (>= m W H floats)
     if (HW64 > 64) L.bitmap = ncols * HW64 * 8;        // (feature sizes above 4096 only: k_seeds + k_coldesc)
@@ -644,7 +651,7 @@ void reserve_build(fdcm_featuremap* fm, const BuildLayout& L) {
     BuildBuffers& b = fm->build;
     fm->vol.reserve(L.vol); b.bitmap.reserve(L.bitmap); fm->ivol.reserve(L.ivol);
     b.coldesc.reserve(L.coldesc); b.colmask.reserve(L.colmask); b.labels.reserve(L.labels);
-    b.edge_parent.reserve(L.edge_parent); b.edge_roots.reserve(L.edge_roots);
+    b.edge_parent.reserve(L.edge_parent); b.edge_roots.reserve(L.edge_roots); b.pyr.reserve(L.pyr);
     const void *stack_before = b.stack.p, *offtab_before = b.offtab.p;
     b.stack.reserve(L.stack); b.offtab.reserve(L.offtab);
     if (b.stack.p != stack_before) fm->sweep.reset();  // a new scratch: no cost table, no steal counter
@@ -705,8 +712,8 @@ static PlanOnDevice upload_plan(fdcm_featuremap* fm, const BuildLayout& L, const
     put(L.off_raster, plan.raster); put(L.off_prop, plan.prop); put(L.off_integral, plan.integral);
     put(L.off_keys, plan.keys); put(L.off_slice, plan.slice_first); put(L.off_cost, proxy_cost);
     const SeedSource& src = plan.seeds;
-    if (src.bytes() && !src.on_device)  // rows packed: the kernels read them with a stride of `width`
-        for (int y = 0; y < src.height; ++y) std::memcpy(hs + L.off_pixels + (size_t)y * src.width, src.pixels + (size_t)y * src.row_stride, (size_t)src.width);
+    if (src.source_bytes() && !src.on_device)  // rows packed: the kernels read them with a stride of `width0`
+        for (int y = 0; y < src.height0; ++y) std::memcpy(hs + L.off_pixels + (size_t)y * src.width0, src.pixels + (size_t)y * src.row_stride, (size_t)src.width0);
     const char* dp = (const char*)fm->build.plan.p;
     FDCM_HIP(hipMemcpyAsync(fm->build.plan.p, hs, proxy_order ? L.plan : L.off_cost, hipMemcpyHostToDevice, fm->stream));
     if (proxy_order)
@@ -714,7 +721,7 @@ static PlanOnDevice upload_plan(fdcm_featuremap* fm, const BuildLayout& L, const
     return PlanOnDevice{(const RasterLine*)(dp + L.off_raster), (const int*)(dp + L.off_slice), (const PropStep*)(dp + L.off_prop),
                         (const IntegralDesc*)(dp + L.off_integral), (int)plan.raster.size(), (int)plan.prop.size(),
                         (const float*)(dp + L.off_keys), src.on_device ? src.pixels : (const uint8_t*)(dp + L.off_pixels),
-                        src.on_device ? src.row_stride : src.width};
+                        src.on_device ? src.row_stride : src.width0};
 }
 // pass 1: the seeds and the column descriptors
 static void stage_pass1(fdcm_featuremap* fm, const BuildLayout& L, const PlanOnDevice& P, const SeedSource& src, bool device_proxy) {
@@ -727,7 +734,10 @@ static void stage_pass1(fdcm_featuremap* fm, const BuildLayout& L, const PlanOnD
         fm->built.seeds_fused = src.kind == SeedKind::labels;
         if (src.kind == SeedKind::image) {
             const bool hyst = !src.edge_plain();  // (the scratch of an earlier build with hysteresis may still be there)
-            launch_edge_labels(st, P.pixels, src.width, src.height, P.pixel_stride, P.keys, m, src.edge, fm->build.labels.as<uint8_t>(),
+            // the image of the build's level: the caller's pixels, or its reduction in the handle's two level buffers
+            uint8_t* pyr = fm->build.pyr.as<uint8_t>();
+            const uint8_t* pixels = launch_pyramid(st, P.pixels, src.width0, src.height0, P.pixel_stride, src.level, pyr, pyr + L.pyr_b);
+            launch_edge_labels(st, pixels, src.width, src.height, src.level > 0 ? src.width : P.pixel_stride, P.keys, m, src.edge, fm->build.labels.as<uint8_t>(),
                                hyst ? fm->build.edge_parent.as<int32_t>() : nullptr, hyst ? fm->build.edge_roots.as<uint32_t>() : nullptr);
             labels = fm->build.labels.as<uint8_t>();
             mark(fm, 1, fm->built.stage_events);

@@ -164,13 +164,19 @@ struct EdgeArg {
     static EdgeArg plain(int t) { EdgeArg a; a.threshold = t; return a; }
     static EdgeArg params(const fdcm_edge_params* p) { EdgeArg a; a.ex = p; a.is_ex = true; return a; }
 };
+// level > 0 (images only): the seeds come from P_level of the image (include/fdcm.h, "image pyramid"), and border and the map's
+// size are in its pixels.
 static void pixel_plan(const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device, SeedKind kind,
-                       const EdgeArg& edge, int64_t border, int64_t depth, float coeff, BuildPlan& plan) {
+                       const EdgeArg& edge, int64_t border, int64_t depth, float coeff, BuildPlan& plan, int32_t level = 0) {
+    require(level >= 0 && level <= 12, "level must be in [0, 12]");
     require(pixels != nullptr, kind == SeedKind::image ? "image is null" : "labels is null");
     require(width >= 1 && height >= 1, "width and height must be at least 1");
     require(border >= 0, "border must be >= 0");
+    require(level == 0 || (width <= 4096 && height <= 4096), "width and height must be at most 4096");
+    const int64_t width0 = width, height0 = height;
+    pyramid_size(width0, height0, level, &width, &height);
     require(width + 2 * border <= 4096 && height + 2 * border <= 4096, "feature maps from images are limited to 4096 x 4096 (border included)");
-    require(row_stride >= width, "row_stride must be >= width");
+    require(row_stride >= width0, "row_stride must be >= width");
     require(on_device == 0 || on_device == 1, "on_device must be 0 or 1");
     fdcm_edge_params e = {0, edge.threshold, edge.threshold, 1};
     if (kind == SeedKind::image && !edge.is_ex) require(edge.threshold >= 1 && edge.threshold <= 1442, "threshold must be in [1, 1442]");
@@ -189,17 +195,19 @@ static void pixel_plan(const uint8_t* pixels, int64_t width, int64_t height, int
     plan.seeds.kind = kind; plan.seeds.pixels = pixels; plan.seeds.on_device = on_device != 0;
     plan.seeds.width = (int)width; plan.seeds.height = (int)height; plan.seeds.row_stride = (int)row_stride;
     plan.seeds.border = (int)border; plan.seeds.edge = e;
+    plan.seeds.level = level; plan.seeds.width0 = (int)width0; plan.seeds.height0 = (int)height0;
 }
 
 static int build_from_pixels(const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device, SeedKind kind,
-                             const EdgeArg& edge, int64_t border, int64_t depth, float coeff, int distance, int stop_after, fdcm_featuremap** out) {
+                             const EdgeArg& edge, int64_t border, int64_t depth, float coeff, int distance, int stop_after, fdcm_featuremap** out,
+                             int32_t level = 0) {
     fdcm_featuremap* fm = nullptr;
     int rc = guarded([&] {
         require(out != nullptr, "out is null");
         require(distance >= FDCM_L2 && distance <= FDCM_L1, "unknown distance");
         require(stop_after >= 1 && stop_after <= 3, "stop_after must be 1..3");
         BuildPlan plan;
-        pixel_plan(pixels, width, height, row_stride, on_device, kind, edge, border, depth, coeff, plan);
+        pixel_plan(pixels, width, height, row_stride, on_device, kind, edge, border, depth, coeff, plan, level);
         fm = new fdcm_featuremap();
         fm->device = g_device;
         fm->depth_param = depth; fm->coeff = coeff; fm->padding = 0.f; fm->distance = distance;
@@ -211,11 +219,11 @@ static int build_from_pixels(const uint8_t* pixels, int64_t width, int64_t heigh
 }
 
 static int rebuild_from_pixels(fdcm_featuremap* fm, const uint8_t* pixels, int64_t width, int64_t height, int64_t row_stride, int on_device,
-                               SeedKind kind, const EdgeArg& edge, int64_t border) {
+                               SeedKind kind, const EdgeArg& edge, int64_t border, int32_t level = 0) {
     return guarded([&] {
         require(fm != nullptr, "featuremap is null");
         BuildPlan plan;
-        pixel_plan(pixels, width, height, row_stride, on_device, kind, edge, border, fm->depth_param, fm->coeff, plan);
+        pixel_plan(pixels, width, height, row_stride, on_device, kind, edge, border, fm->depth_param, fm->coeff, plan, level);
         run_build(fm, plan, 3);
     });
 }
@@ -293,6 +301,46 @@ int fdcm_featuremap_build_image_ex(const uint8_t* image, int64_t width, int64_t 
 int fdcm_featuremap_rebuild_image_ex(fdcm_featuremap* fm, const uint8_t* image, int64_t width, int64_t height, int64_t row_stride,
                                      int on_device, const fdcm_edge_params* params, int64_t border) {
     return rebuild_from_pixels(fm, image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::params(params), border);
+}
+
+// ------------------------------------------------------------------------------------------ image pyramid
+static void check_pyramid_args(int64_t width, int64_t height, int32_t level) {
+    require(level >= 0 && level <= 12, "level must be in [0, 12]");
+    require(width >= 1 && height >= 1 && width <= 4096 && height <= 4096, "width and height must be in [1, 4096]");
+}
+
+int fdcm_image_pyramid_size(int64_t width, int64_t height, int32_t level, int64_t* w_out, int64_t* h_out) {
+    return guarded([&] {
+        require(w_out != nullptr, "w_out is null");
+        require(h_out != nullptr, "h_out is null");
+        check_pyramid_args(width, height, level);
+        pyramid_size(width, height, level, w_out, h_out);
+    });
+}
+
+int fdcm_image_pyramid_level(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device, int32_t level,
+                             uint8_t* out, int out_on_device) {
+    return guarded([&] {
+        require(image != nullptr, "image is null");
+        require(out != nullptr, "out is null");
+        check_pyramid_args(width, height, level);
+        require(row_stride >= width, "row_stride must be >= width");
+        require(on_device == 0 || on_device == 1, "on_device must be 0 or 1");
+        require(out_on_device == 0 || out_on_device == 1, "out_on_device must be 0 or 1");
+        image_pyramid_host(g_device, image, (int)width, (int)height, (int)row_stride, on_device != 0, level, out, out_on_device != 0);
+    });
+}
+
+int fdcm_featuremap_build_image_level(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device, int32_t level,
+                                      const fdcm_edge_params* params, int64_t border, int64_t depth, float dt3_coeff, int distance,
+                                      fdcm_featuremap** out) {
+    return build_from_pixels(image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::params(params), border, depth, dt3_coeff,
+                             distance, 3, out, level);
+}
+
+int fdcm_featuremap_rebuild_image_level(fdcm_featuremap* fm, const uint8_t* image, int64_t width, int64_t height, int64_t row_stride,
+                                        int on_device, int32_t level, const fdcm_edge_params* params, int64_t border) {
+    return rebuild_from_pixels(fm, image, width, height, row_stride, on_device, SeedKind::image, EdgeArg::params(params), border, level);
 }
 
 int fdcm_featuremap_build_image(const uint8_t* image, int64_t width, int64_t height, int64_t row_stride, int on_device, int threshold,

@@ -13,6 +13,8 @@
 //                      8-connected components by the tiled labeller of fdcm_unionfind.h with one partition (a tile merged in
 //                      LDS, the pairs across tile borders in global memory), strong flag and size per root, and the candidates
 //                      of the other roots back to 255
+//   k_pyr_down         the next level of the image pyramid: the smooth = 2 image at the even coordinates (include/fdcm.h, "image
+//                      pyramid"); a level-l build runs it l times in front of the edge kernels   read W H, write W H / 4
 // All index with the caller's sizes only: every load is of a pixel inside [0, width) x [0, height), every store inside the label
 // image, the words of the image's own pixels or the descriptors of the block's own columns.
 #include <algorithm>
@@ -270,6 +272,59 @@ void launch_coldesc_labels(hipStream_t st, const uint8_t* labels, int width, int
     else hipLaunchKernelGGL((k_coldesc_labels<64, 32>), grid, dim3(256), lds, st, labels, width, height, border, d, W, H, HW64, colmask, cost);
 }
 
+// ------------------------------------------------------------------------------------------ image -> the next level's image
+// P_(l+1)(x, y) = S2(P_l)(2x, 2y) (include/fdcm.h, "image pyramid"): the smooth = 2 image of edge_tile<2, ..>, sampled at the even
+// coordinates.  A workgroup makes one kTileW x kTileH tile of P_(l+1) from the (2 kTileW + 3) x (2 kTileH + 3) pixels of P_l
+// around it, which load_clamped_tile holds with the replicate border; a thread makes four pixels, a wave 64 neighbours of a row.
+static constexpr int kPyrPW = 2 * kTileW + 3, kPyrPH = 2 * kTileH + 3;
+__global__ void __launch_bounds__(256) k_pyr_down(const uint8_t* __restrict__ src, int W, int H, int stride, uint8_t* __restrict__ dst, int Wn,
+                                                  int Hn) {
+    __shared__ unsigned char raw[kPyrPH][kPyrPW + 5];
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;  // 2 x0 <= W - 1 and 2 y0 <= H - 1: the held region meets the image
+    load_clamped_tile<kPyrPH, kPyrPW>(raw, src, W, H, stride, 2 * x0 - 2, 2 * y0 - 2, tid);
+    __syncthreads();
+    const int lx = tid & 63;
+#pragma unroll
+    for (int i = 0; i < kTileH / 4; ++i) {
+        const int ly = (tid >> 6) + 4 * i;
+        const int x = x0 + lx, y = y0 + ly;
+        if (x >= Wn || y >= Hn) continue;
+        int sum = 0;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            int row = 0;
+#pragma unroll
+            for (int t = 0; t < 5; ++t) row += (t == 2 ? 6 : (t == 1 || t == 3 ? 4 : 1)) * raw[2 * ly + j][2 * lx + t];
+            sum += (j == 2 ? 6 : (j == 1 || j == 3 ? 4 : 1)) * row;
+        }
+        dst[(size_t)y * Wn + x] = (unsigned char)((sum + 128) >> 8);
+    }
+}
+
+void pyramid_size(int64_t width, int64_t height, int level, int64_t* w_out, int64_t* h_out) {
+    for (int l = 0; l < level; ++l) { width = (width + 1) >> 1; height = (height + 1) >> 1; }
+    *w_out = width; *h_out = height;
+}
+
+// level 0 of the call without a handle: the image's rows, packed (the caller's device memory is read and written by kernels only)
+__global__ void __launch_bounds__(256) k_pack_rows(const uint8_t* __restrict__ src, int W, int H, int stride, uint8_t* __restrict__ dst) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x < W && y < H) dst[(size_t)y * W + x] = src[(size_t)y * stride + x];
+}
+
+const uint8_t* launch_pyramid(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, int level, uint8_t* a, uint8_t* b,
+                              uint8_t* last) {
+    const uint8_t* src = image;
+    for (int l = 0; l < level; ++l) {
+        const int wn = (width + 1) >> 1, hn = (height + 1) >> 1;
+        uint8_t* dst = (last && l == level - 1) ? last : ((l & 1) ? b : a);
+        hipLaunchKernelGGL(k_pyr_down, uf_tile_grid(wn, hn), dim3(256), 0, st, src, width, height, row_stride, dst, wn, hn);
+        src = dst; width = wn; height = hn; row_stride = wn;
+    }
+    return src;
+}
+
 // ------------------------------------------------------------------------------------------ the calls without a handle
 PixelScratch::~PixelScratch() { for (DevBuf* b : {&pixels, &labels, &keys, &parent, &counts, &comps, &out}) b->release(); }
 
@@ -284,6 +339,29 @@ const uint8_t* PixelScratch::upload(const uint8_t* host_or_device, int width, in
     FDCM_HIP(hipMemcpy2D(pixels.p, (size_t)width, host_or_device, (size_t)row_stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
     row_stride = width;
     return pixels.as<uint8_t>();
+}
+
+void image_pyramid_host(int device, const uint8_t* image, int width, int height, int row_stride, bool on_device, int level, uint8_t* out,
+                        bool out_on_device) {
+    FDCM_HIP(hipSetDevice(device));
+    PixelScratch s;
+    int64_t w1, h1, w2, h2, wl, hl;
+    pyramid_size(width, height, 1, &w1, &h1);
+    pyramid_size(w1, h1, 1, &w2, &h2);
+    pyramid_size(width, height, level, &wl, &hl);
+    const size_t n = (size_t)(wl * hl);
+    const uint8_t* d = s.upload(image, width, height, row_stride, on_device, nullptr);
+    const size_t off_b = ((size_t)(w1 * h1) + 15) & ~(size_t)15;
+    if (level > 1) s.labels.reserve(off_b + (size_t)(w2 * h2));  // (the two buffers of the levels between)
+    if (!out_on_device) s.out.reserve(n);
+    uint8_t* dst = out_on_device ? out : s.out.as<uint8_t>();  // the last level goes where it is wanted: device memory of the caller's is written by a kernel
+    if (level == 0)
+        hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)((width + 255) / 256), (unsigned)height), dim3(256), 0, nullptr, d, width, height, row_stride, dst);
+    else
+        launch_pyramid(nullptr, d, width, height, row_stride, level, s.labels.as<uint8_t>(), s.labels.as<uint8_t>() + off_b, dst);
+    FDCM_HIP(hipGetLastError());
+    FDCM_HIP(hipDeviceSynchronize());
+    if (!out_on_device) FDCM_HIP(hipMemcpy(out, s.out.p, n, hipMemcpyDeviceToHost));
 }
 
 void edge_labels_host(int device, const uint8_t* image, int width, int height, int row_stride, int64_t depth, const fdcm_edge_params& e,

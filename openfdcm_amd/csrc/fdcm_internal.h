@@ -122,16 +122,19 @@ struct LineBox { int32_t slice; float xlo, xhi, ylo, yhi; };
 // (k_edge_labels; `edge` holds the detector's parameters, and unless they are k_edge_labels' own -- edge_plain -- the
 // candidate kernel and the component kernels make the labels).  Pixel (x, y) seeds map pixel (x + border, y + border).  The
 // pixels are host memory, which travels in the plan's blob with rows packed, or memory of the handle's device, which is read
-// in place while the build runs.
+// in place while the build runs.  An image build of level l > 0 (include/fdcm.h, "image pyramid") takes its seeds from P_l: the
+// caller's pixels are width0 x height0, the build reduces them l times in the handle's workspace, and width x height is P_l's size.
 enum class SeedKind { lines, labels, image };
 struct SeedSource {
     SeedKind kind = SeedKind::lines;
     const uint8_t* pixels = nullptr;
     bool on_device = false;
     int width = 0, height = 0, row_stride = 0, border = 0;
+    int level = 0, width0 = 0, height0 = 0;  // the caller's pixels: width0 x height0 with row_stride (level 0: width x height)
     fdcm_edge_params edge = {0, 0, 0, 1};  // (image only; one threshold t: {0, t, t, 1})
     bool edge_plain() const { return edge.smooth == 0 && edge.low == edge.high && edge.min_pixels == 1; }
     size_t bytes() const { return kind == SeedKind::lines ? 0 : (size_t)width * (size_t)height; }
+    size_t source_bytes() const { return kind == SeedKind::lines ? 0 : (size_t)width0 * (size_t)height0; }
 };
 
 struct BuildPlan {
@@ -156,6 +159,7 @@ struct BuildLayout {
     size_t vol = 0, ivol = 0, bitmap = 0, coldesc = 0, colmask = 0, offtab = 0, stack = 0;
     size_t labels = 0;      // the label image an image build makes of its pixels
     size_t edge_parent = 0, edge_roots = 0;  // image builds with hysteresis: a parent and a (strong flag | count) word per pixel
+    size_t pyr = 0, pyr_b = 0;  // image builds of a level > 0: the two buffers the levels go through, and where the second begins
     size_t o_ent = 0, o_own = 0, o_ord = 0, o_cost = 0, o_steals = 0;  // inside `stack` (balanced sweep)
     // plan blob: RasterLine[] | PropStep[] | IntegralDesc[] | keys[] | slice_first[] | host pixels of the seed source | per-chunk proxy cost[]
     size_t off_raster = 0, off_prop = 0, off_integral = 0, off_keys = 0, off_slice = 0, off_pixels = 0, off_cost = 0, plan = 0;
@@ -223,11 +227,12 @@ struct BuildBuffers {  // what a build needs besides the volume, sized by BuildL
     DevBuf colmask;  // m*ceil(W/64) words: the seeded columns of every slice (k_coldesc_tile, for the L2 sweep)
     DevBuf labels;   // image builds: the label image k_edge_labels writes and k_coldesc_labels reads
     DevBuf edge_parent, edge_roots;  // image builds with hysteresis: the union-find of the candidates (launch_edge_labels)
+    DevBuf pyr;      // image builds of a level > 0: P_1, P_3, .. at its start and P_2, P_4, .. at BuildLayout::pyr_b (launch_pyramid)
     DevBuf offtab;   // per slice: one word per group of 4 columns for the shallow sweeps of the line integral (k_groups)
     DevBuf stack;    // the sweep's scratch: the balanced sweep's stack and owner entries (slot-major per chunk), launch order,
                      // per-chunk costs and steal counter; or the literal pass's scratch; or the L1 pass's minima / carries
     DevBuf plan; PinnedBuf stage;  // the last build's plan (BuildLayout's blob) or the keys of an adopted volume; its host staging
-    void release() { for (DevBuf* b : {&bitmap, &coldesc, &colmask, &labels, &edge_parent, &edge_roots, &offtab, &stack, &plan}) b->release(); stage.release(); }
+    void release() { for (DevBuf* b : {&bitmap, &coldesc, &colmask, &labels, &edge_parent, &edge_roots, &pyr, &offtab, &stack, &plan}) b->release(); stage.release(); }
 };
 struct SearchBuffers {
     DevBuf scene;     // scene lines + sorted lengths + sorted idx + candidate offsets
@@ -314,6 +319,15 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after);
 // e.high, which is the same for {0, t, t, 1} and needs no scratch.
 void launch_edge_labels(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, const float* keys, int m,
                         const fdcm_edge_params& e, uint8_t* labels, int32_t* parent, uint32_t* roots);
+// The image pyramid (include/fdcm.h, "image pyramid"): the size of P_level, and `level` launches of k_pyr_down queued on st, level
+// l + 1 from level l, the odd levels into `a` (W_1 H_1 bytes) and the even ones into `b` (W_2 H_2 bytes).  Returns where P_level
+// is, rows contiguous: the image itself for level 0.  The caller's device memory is only ever read and written by kernels.
+void pyramid_size(int64_t width, int64_t height, int level, int64_t* w_out, int64_t* h_out);
+const uint8_t* launch_pyramid(hipStream_t st, const uint8_t* image, int width, int height, int row_stride, int level, uint8_t* a, uint8_t* b,
+                              uint8_t* last = nullptr);  // last: where the last level goes in place of its buffer
+// host or device image -> P_level into host or device memory, blocking, on the null stream of `device`
+void image_pyramid_host(int device, const uint8_t* image, int width, int height, int row_stride, bool on_device, int level, uint8_t* out,
+                        bool out_on_device);
 // pass 1 with its seeds from a label image (k_coldesc_labels); `cost`, where given, receives the sweep's per-chunk proxy (zeroed
 // by the caller)
 void launch_coldesc_labels(hipStream_t st, const uint8_t* labels, int width, int height, int border, void* desc, int W, int H,

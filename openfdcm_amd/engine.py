@@ -162,6 +162,35 @@ def _edge_params(threshold, low, smooth, min_pixels):
     return capi.EdgeParams(int(smooth), int(threshold if low is None else low), int(threshold), int(min_pixels))
 
 
+def _level_edge_params(threshold, low, smooth, min_pixels):
+    """The fdcm_edge_params of the entry points with a level, which take no bare threshold: the defaults are {0, t, t, 1}."""
+    return capi.EdgeParams(int(smooth), int(threshold if low is None else low), int(threshold), int(min_pixels))
+
+
+def image_pyramid_size(width, height, level):
+    """(W_l, H_l) of level `level` of a width x height image: W_(l+1) = (W_l + 1) >> 1.  No device work."""
+    w, h = C.c_int64(), C.c_int64()
+    capi.check(capi.lib().fdcm_image_pyramid_size(int(width), int(height), int(level), C.byref(w), C.byref(h)))
+    return w.value, h.value
+
+
+def image_pyramid(image, level):
+    """Level `level` (0 to 12) of a 2-D uint8 image (include/fdcm.h, "image pyramid"): P_(l+1)(x, y) is the smooth = 2 image of
+    P_l at (2x, 2y), made on the GPU.  A numpy array gives a numpy array; a CUDA torch tensor gives a tensor on its device,
+    written there."""
+    p, w, h, stride, dev, keep = _pixels(image, "image")
+    wl, hl = image_pyramid_size(w, h, level)
+    if dev:
+        import torch
+        out = torch.empty((hl, wl), dtype=torch.uint8, device=keep.device)
+        q = C.c_void_p(out.data_ptr())
+    else:
+        out = np.empty((hl, wl), dtype=np.uint8)
+        q = C.c_void_p(out.ctypes.data)
+    capi.check(capi.lib().fdcm_image_pyramid_level(p, w, h, stride, dev, int(level), q, dev))
+    return out
+
+
 class DeviceFeatureMap:
     """Owns an fdcm_featuremap handle (DT3 volume resident in HBM)."""
 
@@ -260,6 +289,28 @@ class DeviceFeatureMap:
             capi.check(capi.lib().fdcm_featuremap_rebuild_image_ex(self._h, p, w, h, stride, dev, C.byref(ex), int(border)))
         else:
             capi.check(capi.lib().fdcm_featuremap_rebuild_image(self._h, p, w, h, stride, dev, int(threshold), int(border)))
+        self._seed_pixels = keep
+        self.refresh()
+
+    # ---- feature maps of a pyramid level (include/fdcm.h, "image pyramid"): build_image of the image reduced by 2^level
+    @classmethod
+    def build_image_level(cls, image, level, threshold, border=0, depth=30, coeff=5.0, distance=capi.L2, low=None, smooth=0,
+                          min_pixels=1):
+        """The DT3 volume of level `level` (0 to 12) of `image`: by definition build_image of image_pyramid(image, level) with
+        the same options; border is in the level's pixels.  The levels are made on the device, in a workspace of the handle."""
+        p, w, h, stride, dev, keep = _pixels(image, "image")
+        out = C.c_void_p()
+        ex = _level_edge_params(threshold, low, smooth, min_pixels)
+        capi.check(capi.lib().fdcm_featuremap_build_image_level(p, w, h, stride, dev, int(level), C.byref(ex), int(border), int(depth),
+                                                                float(coeff), int(distance), C.byref(out)))
+        fm = cls(out)
+        fm._seed_pixels = keep
+        return fm
+
+    def rebuild_image_level(self, image, level, threshold, border=0, low=None, smooth=0, min_pixels=1):
+        p, w, h, stride, dev, keep = _pixels(image, "image")
+        ex = _level_edge_params(threshold, low, smooth, min_pixels)
+        capi.check(capi.lib().fdcm_featuremap_rebuild_image_level(self._h, p, w, h, stride, dev, int(level), C.byref(ex), int(border)))
         self._seed_pixels = keep
         self.refresh()
 
