@@ -11,8 +11,11 @@
 //                                     kBestBound: best for the points at or below a score, with rows_score's early exit;
 //                                     kBestGate, kBestBoundGate: both with the matched-fraction gate inside the minimum
 //   k_best_unpack, k_best_gather      best map: the key plane as row-major score and pair planes; the pairs of k points
-//   k_nms_round                       detections by footprint overlap: one round of the greedy rule on the key plane, the
-//                                     previous round's winner reduced from per-workgroup minima, its victims erased
+//   k_nms_round<LIST, HULL, OBJ>      detections by footprint overlap: one round of the greedy rule, the previous round's
+//                                     winner reduced from per-workgroup minima, its victims erased.  The one round of every
+//                                     detection call: on G key planes or (LIST) on the winners' list of the windows' calls,
+//                                     by boxes or (HULL) by hull shapes, and (OBJ) with one overlap limit within an object
+//                                     and one across objects; six instantiations (nms_rounds)
 //   k_exhaustive_peaks<R, ANGLES>     peaks: reads the score planes k_exhaustive<., false> wrote and offers every point whose
 //                                     key is the minimum of its window to a per-wave k-best list; ANGLES: the window spans
 //                                     several angles' planes (64-bit keys in LDS), else one plane (32-bit score bits)
@@ -25,18 +28,13 @@
 //                                     k_nms_round), per entry of the result list, per pose of a list, per grid point (the
 //                                     gated best map's fractions); all through matched_length<BUF32>, the one statement of
 //                                     the matched length for a pose on its own
-//   k_window_winners<BUF32>, k_nms_list_round
+//   k_window_winners<BUF32>, k_window_winners_objects<BUF32>
 //                                     detections over pose windows: a thread per job turns the job's merged k = 1 list into
-//                                     its entry of the winners' list (normalised key, footprint), and one round of the greedy
-//                                     rule on that list, k_nms_round's scheme with a list in place of the key plane
-//   k_nms_objects_round, k_nms_list_objects_round, k_window_winners_objects<BUF32>
-//                                     objects (include/fdcm.h, "Objects"): the round of the greedy rule over G key planes, one
-//                                     per object, and over a winners' list with an object per job, each with one overlap limit
-//                                     within an object and one across objects; the winners' pass with a threshold per pair
-//   k_nms_hull_round, k_nms_hull_list_round
-//                                     hull footprints (include/fdcm.h, "Hull footprints"): the two rounds with objects on shapes,
-//                                     the lattice points of the convex hull of a pair's end points as row spans, for template
-//                                     sets of that kind; sets of kind BOX launch the rounds above
+//                                     its entry of the winners' list (normalised key, footprint), for the list forms of
+//                                     k_nms_round; objects (include/fdcm.h, "Objects"): the same pass with a threshold per pair
+//   hull_suppresses, hull_stage       hull footprints (include/fdcm.h, "Hull footprints"): the overlap test on shapes, the
+//                                     lattice points of the convex hull of a pair's end points as row spans, for template
+//                                     sets of that kind; sets of kind BOX run the round's box forms
 //
 // Both scoring kernels evaluate through rows_score<BUF32, ROWS, CAP, EXIT, GATE>, the one statement of the sum (4 rows per lane
 // in k_exhaustive, 1 in k_exhaustive_windows).  GATE: the matched length of every slot beside its sum, by matched_length's
@@ -131,6 +129,12 @@ __device__ __forceinline__ bool under(float q, const ExBound<true, GATE>& b) { r
 __device__ __forceinline__ long long best_key_index(int i, int j, int tiles_x) {
     const int ti = i / kTileX, tj = j / kTileY, li = i % kTileX, lj = j % kTileY;
     return ((long long)tj * tiles_x + ti) * (kTileX * kTileY) + (lj / 16) * 256 + (li / 4) * 64 + (lj % 16) * 4 + (li % 4);
+}
+// best_key_index backwards, the one statement of it: 1024 keys per sub-tile, [row group][wave][row % 16][column % 4].
+__device__ __forceinline__ void best_key_point(long long idx, int tiles_x, int& i, int& j) {
+    const int tile = (int)(idx >> 10), r = (int)(idx & 1023);
+    i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
+    j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
 }
 
 // One read of the interleaved volume (ivol_index) at column x, row y of the line's slice.  xw: the column's part of the
@@ -603,13 +607,14 @@ __global__ void k_best_gather(const unsigned long long* __restrict__ best, int k
 //   1. every workgroup reduces the partials of round r - 1 to the same winner d(r-1), key and pair (round 0: none)
 //   2. workgroup 0 writes them to the result list; a winner kNoKey ends the list: the workgroups leave kNoKey partials
 //      behind (the next launches read them) and return.  The last launch (r = k) returns here too: it only reduces.
-//   3. each workgroup walks its run, consecutive lanes reading consecutive keys: (i, j) from the storage index (the inverse
-//      of best_key_index), the point's footprint from its pair's box and its translation; the winner's once per workgroup
+//   3. each workgroup walks its run, consecutive lanes reading consecutive keys: (i, j) from the storage index
+//      (best_key_point), the point's footprint from its pair's box and its translation; the winner's once per workgroup
 //   4. the winner and every point it suppresses (1000 I > permille U, int64) become kNoKey, a plain store by the one
 //      thread that owns the entry in every round; each surviving key enters the workgroup's minimum as (q bits << 32) | g
 // The pair travels with the partial because the winner's entry of the plane is erased in the launch that needs its box.
 // A minimum does not depend on the order of its operands and suppression is a function of d(r-1) alone: no atomics, no
-// cooperative launch, and the bytes do not depend on scheduling.
+// cooperative launch, and the bytes do not depend on scheduling.  The launch is k_nms_round<LIST, HULL, OBJ>, below the
+// overlap tests; what follows here is what it is made of.
 constexpr int kNmsWorkgroups = 256;
 
 // The minimum key of the workgroup and its pair, in every thread.  sk, sp: 4 entries of LDS, free on entry.
@@ -629,6 +634,17 @@ __device__ __forceinline__ void nms_block_min(unsigned long long& key, int& pair
     __syncthreads();  // sk and sp are free again
 }
 
+// The same for partials that are keys alone (the list forms of the round): no pair is reduced.
+__device__ __forceinline__ void nms_block_min(unsigned long long& key, unsigned long long* sk) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) key = min(key, __shfl_xor(key, d));
+    if ((threadIdx.x & 63) == 0) sk[threadIdx.x >> 6] = key;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w) key = min(key, sk[w]);
+    __syncthreads();  // sk is free again
+}
+
 // The overlap test, the one statement of it: the footprint [fx0, fx1] x [fy0, fy1] against the winner's, whose area is Aw.
 // 1000 I > permille U in int64, U = A + Aw - I; boxes that share no pixel never suppress each other.
 __device__ __forceinline__ bool nms_suppresses(int fx0, int fy0, int fx1, int fy1, int wx0, int wy0, int wx1, int wy1, long long Aw,
@@ -638,67 +654,6 @@ __device__ __forceinline__ bool nms_suppresses(int fx0, int fy0, int fx1, int fy
     const long long I = (long long)ix * (long long)iy;
     const long long U = (long long)(fx1 - fx0 + 1) * (long long)(fy1 - fy0 + 1) + Aw - I;
     return 1000ll * I > (long long)permille * U;
-}
-
-__global__ void __launch_bounds__(256) k_nms_round(unsigned long long* keys, long long n_chunks, int x0, int y0, int sx, int sy, int nx,
-                                                   int tiles_x, const int4* __restrict__ boxes, int permille, int round, int last,
-                                                   const unsigned long long* __restrict__ pk_in, const int* __restrict__ pp_in,
-                                                   unsigned long long* __restrict__ pk_out, int* __restrict__ pp_out,
-                                                   unsigned long long* __restrict__ best, int* __restrict__ pair) {
-    __shared__ unsigned long long sk[4];
-    __shared__ int sp[4];
-    unsigned long long W = kNoKey;
-    int Wp = -1;
-    if (round > 0) {
-        if (threadIdx.x < gridDim.x) { W = pk_in[threadIdx.x]; Wp = pp_in[threadIdx.x]; }
-        nms_block_min(W, Wp, sk, sp);
-        if (blockIdx.x == 0 && threadIdx.x == 0) { best[round - 1] = W; pair[round - 1] = W == kNoKey ? -1 : Wp; }
-        if (W == kNoKey || last) {  // workgroup-uniform
-            if (threadIdx.x == 0) { pk_out[blockIdx.x] = kNoKey; pp_out[blockIdx.x] = -1; }
-            return;
-        }
-    }
-    // the winner's footprint F(d) = box(pair) + t_d and its area (round 0: unused)
-    const unsigned gw = (unsigned)W;
-    int wx0 = 0, wy0 = 0, wx1 = -1, wy1 = -1;
-    if (round > 0) {
-        const int4 b = boxes[Wp];
-        const int tx = x0 + (int)(gw % (unsigned)nx) * sx, ty = y0 + (int)(gw / (unsigned)nx) * sy;
-        wx0 = b.x + tx; wy0 = b.y + ty; wx1 = b.z + tx; wy1 = b.w + ty;
-    }
-    const long long Aw = (long long)(wx1 - wx0 + 1) * (long long)(wy1 - wy0 + 1);
-    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
-    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
-    unsigned long long mk = kNoKey;
-    int mp = -1;
-    for (long long c = c0; c < c1; ++c) {
-        const long long idx = c * 256 + threadIdx.x;
-        const unsigned long long v = keys[idx];
-        if (v == kNoKey) continue;
-        // best_key_index backwards: 1024 keys per sub-tile, [row group][wave][row % 16][column % 4]
-        const int tile = (int)(idx >> 10), r = (int)(idx & 1023);
-        const int i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
-        const int j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
-        const unsigned g = (unsigned)(j * nx + i);
-        const int u = (int)(unsigned)v;
-        bool drop = false;
-        if (round > 0) {
-            drop = g == gw;
-            if (!drop) {
-                const int4 b = boxes[u];
-                const int tx = x0 + i * sx, ty = y0 + j * sy;
-                drop = nms_suppresses(b.x + tx, b.y + ty, b.z + tx, b.w + ty, wx0, wy0, wx1, wy1, Aw, permille);
-            }
-        }
-        if (drop) {
-            keys[idx] = kNoKey;
-        } else {
-            const unsigned long long key = (v & 0xffffffff00000000ull) | g;
-            if (key < mk) { mk = key; mp = u; }
-        }
-    }
-    nms_block_min(mk, mp, sk, sp);
-    if (threadIdx.x == 0) { pk_out[blockIdx.x] = mk; pp_out[blockIdx.x] = mp; }
 }
 
 // ---- objects (include/fdcm.h, "Objects"): G key planes, one behind the other, plane o holding best(g, o)
@@ -721,77 +676,6 @@ __device__ __forceinline__ void nms_block_min_pair(unsigned long long& key, int&
     for (int w = 0; w < 4; ++w)
         if (nms_pair_less(sk[w], sp[w], key, pair)) { key = sk[w]; pair = sp[w]; }
     __syncthreads();  // sk and sp are free again
-}
-
-// One round of the greedy rule over the G planes: k_nms_round's scheme, launch by launch.  The planes are one array of
-// n_chunks runs of 256 keys, plane_chunks of them per plane (a plane is whole sub-tiles, so a run lies in one plane): the
-// object of an entry is its run's plane, (i, j) the inverse of best_key_index inside the plane.  A partial is a key
-// (bits of q << 32) | g and its pair, ordered as (key, pair): the order of include/fdcm.h, "Objects".  The winner's object is
-// pobj[its pair] (a per-pair table), its entry the one at its point in its object's plane: that entry is erased by object
-// and point, an entry of another object at the same point only when the cross limit says so.  The limit of an entry is
-// `permille` when its object is the winner's and `cross` otherwise.  One writer per entry, no atomics, no cooperative launch.
-__global__ void __launch_bounds__(256) k_nms_objects_round(unsigned long long* keys, long long n_chunks, long long plane_chunks, int x0,
-                                                           int y0, int sx, int sy, int nx, int tiles_x, const int4* __restrict__ boxes,
-                                                           const int* __restrict__ pobj, int permille, int cross, int round, int last,
-                                                           const unsigned long long* __restrict__ pk_in, const int* __restrict__ pp_in,
-                                                           unsigned long long* __restrict__ pk_out, int* __restrict__ pp_out,
-                                                           unsigned long long* __restrict__ best, int* __restrict__ pair) {
-    __shared__ unsigned long long sk[4];
-    __shared__ int sp[4];
-    unsigned long long W = kNoKey;
-    int Wp = -1;
-    if (round > 0) {
-        if (threadIdx.x < gridDim.x) { W = pk_in[threadIdx.x]; Wp = pp_in[threadIdx.x]; }
-        nms_block_min_pair(W, Wp, sk, sp);
-        if (blockIdx.x == 0 && threadIdx.x == 0) { best[round - 1] = W; pair[round - 1] = W == kNoKey ? -1 : Wp; }
-        if (W == kNoKey || last) {  // workgroup-uniform
-            if (threadIdx.x == 0) { pk_out[blockIdx.x] = kNoKey; pp_out[blockIdx.x] = -1; }
-            return;
-        }
-    }
-    // the winner's object, footprint and area (round 0: unused)
-    const unsigned gw = (unsigned)W;
-    int wx0 = 0, wy0 = 0, wx1 = -1, wy1 = -1, ow = -1;
-    if (round > 0) {
-        const int4 b = boxes[Wp];
-        const int tx = x0 + (int)(gw % (unsigned)nx) * sx, ty = y0 + (int)(gw / (unsigned)nx) * sy;
-        wx0 = b.x + tx; wy0 = b.y + ty; wx1 = b.z + tx; wy1 = b.w + ty;
-        ow = pobj[Wp];
-    }
-    const long long Aw = (long long)(wx1 - wx0 + 1) * (long long)(wy1 - wy0 + 1);
-    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
-    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
-    unsigned long long mk = kNoKey;
-    int mp = -1;
-    for (long long c = c0; c < c1; ++c) {
-        const long long idx = c * 256 + threadIdx.x;
-        const unsigned long long v = keys[idx];
-        if (v == kNoKey) continue;
-        const int o = (int)(c / plane_chunks);  // (wave-uniform)
-        const long long in_plane = idx - (long long)o * plane_chunks * 256;
-        const int tile = (int)(in_plane >> 10), r = (int)(in_plane & 1023);
-        const int i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
-        const int j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
-        const unsigned g = (unsigned)(j * nx + i);
-        const int u = (int)(unsigned)v;
-        bool drop = false;
-        if (round > 0) {
-            drop = g == gw && o == ow;
-            if (!drop) {
-                const int4 b = boxes[u];
-                const int tx = x0 + i * sx, ty = y0 + j * sy;
-                drop = nms_suppresses(b.x + tx, b.y + ty, b.z + tx, b.w + ty, wx0, wy0, wx1, wy1, Aw, o == ow ? permille : cross);
-            }
-        }
-        if (drop) {
-            keys[idx] = kNoKey;
-        } else {
-            const unsigned long long key = (v & 0xffffffff00000000ull) | g;
-            if (nms_pair_less(key, u, mk, mp)) { mk = key; mp = u; }
-        }
-    }
-    nms_block_min_pair(mk, mp, sk, sp);
-    if (threadIdx.x == 0) { pk_out[blockIdx.x] = mk; pp_out[blockIdx.x] = mp; }
 }
 
 // ---- pose windows (include/fdcm.h, "Pose windows"): a list of jobs, each one template, a run of rotations and a small grid
@@ -913,8 +797,8 @@ __device__ __forceinline__ float matched_length(const VolRef& V, const ExLine* _
 // frac = ML / TL, one IEEE division; 1 for a template whose lengths sum to 0
 __device__ __forceinline__ float matched_fraction(float ml, float tl) { return tl == 0.f ? 1.f : ml / tl; }
 
-// The gate: one thread per entry of the key plane k_exhaustive<., kBest> merged, in the plane's own order (k_nms_round's
-// inverse of best_key_index).  An entry with a key computes ML of its pair at its point and loses its key unless
+// The gate: one thread per entry of the key plane k_exhaustive<., kBest> merged, in the plane's own order
+// (best_key_point).  An entry with a key computes ML of its pair at its point and loses its key unless
 // ML >= need[pair].  Each entry is read and written by its one thread; lanes of a wave hold different pairs.
 template <bool BUF32>
 __global__ void __launch_bounds__(256) k_matched_gate(const float* __restrict__ vol, size_t SL, int m, int W, int H, float tx, float ty,
@@ -926,9 +810,8 @@ __global__ void __launch_bounds__(256) k_matched_gate(const float* __restrict__ 
     if (idx >= n_keys) return;
     const unsigned long long v = keys[idx];
     if (v == kNoKey) return;
-    const int tile = (int)(idx >> 10), r = (int)(idx & 1023);
-    const int i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
-    const int j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
+    int i, j;
+    best_key_point(idx, tiles_x, i, j);
     const int u = (int)(unsigned)v;
     const int line0 = tm[u].line0, n = tm[u].n;
     const VolRef V = make_volref(vol, SL, m, BUF32);
@@ -1064,57 +947,6 @@ __global__ void __launch_bounds__(256) k_window_winners(const float* __restrict_
                          [=](int) { return max_score; }, keys, boxes);
 }
 
-// One round of the greedy rule on the winners' list: k_nms_round's scheme with the list in place of the key plane.  Entry j
-// is (keys[j], boxes[j]), its key's low half j itself and its footprint its own, so nothing goes through a pair; the partial
-// minima are keys alone.  Round r reduces the partials of round r - 1 to the winner d(r-1), workgroup 0 writes it to
-// best[r - 1], and every workgroup walks its run of the list: the winner and every entry it suppresses (nms_suppresses)
-// become kNoKey by a plain store of the entry's one owner, the others enter the workgroup's minimum.  A winner kNoKey, or the
-// last launch, leaves kNoKey partials and returns.  The winner's box is read from the list: a round erases keys, never boxes.
-__global__ void __launch_bounds__(256) k_nms_list_round(unsigned long long* keys, const int4* __restrict__ boxes, long long n,
-                                                        int permille, int round, int last,
-                                                        const unsigned long long* __restrict__ pk_in,
-                                                        unsigned long long* __restrict__ pk_out, unsigned long long* __restrict__ best) {
-    __shared__ unsigned long long sk[4];
-    __shared__ int sp[4];
-    unsigned long long W = kNoKey;
-    int none = 0;
-    if (round > 0) {
-        if (threadIdx.x < gridDim.x) W = pk_in[threadIdx.x];
-        nms_block_min(W, none, sk, sp);
-        if (blockIdx.x == 0 && threadIdx.x == 0) best[round - 1] = W;
-        if (W == kNoKey || last) {  // workgroup-uniform
-            if (threadIdx.x == 0) pk_out[blockIdx.x] = kNoKey;
-            return;
-        }
-    }
-    const long long jw = (long long)(unsigned)W;
-    int4 w = make_int4(0, 0, -1, -1);
-    if (round > 0) w = boxes[jw];
-    const long long Aw = (long long)(w.z - w.x + 1) * (long long)(w.w - w.y + 1);
-    const long long n_chunks = (n + 255) / 256;
-    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
-    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
-    unsigned long long mk = kNoKey;
-    for (long long c = c0; c < c1; ++c) {
-        const long long idx = c * 256 + threadIdx.x;
-        if (idx >= n) continue;
-        const unsigned long long v = keys[idx];
-        if (v == kNoKey) continue;
-        bool drop = false;
-        if (round > 0) {
-            drop = idx == jw;
-            if (!drop) {
-                const int4 b = boxes[idx];
-                drop = nms_suppresses(b.x, b.y, b.z, b.w, w.x, w.y, w.z, w.w, Aw, permille);
-            }
-        }
-        if (drop) keys[idx] = kNoKey;
-        else if (v < mk) mk = v;
-    }
-    nms_block_min(mk, none, sk, sp);
-    if (threadIdx.x == 0) pk_out[blockIdx.x] = mk;
-}
-
 // Objects (include/fdcm.h, "Objects"), the windows' call.  k_window_winners with the threshold of the job's object: ms[u] is
 // max_score[objects[template of pair u]], as need[u] is that object's need; everything else is k_window_winners'.
 template <bool BUF32>
@@ -1130,60 +962,11 @@ __global__ void __launch_bounds__(256) k_window_winners_objects(const float* __r
                          [=](int u) { return ms[u]; }, keys, boxes);
 }
 
-// k_nms_list_round with an object per entry: entry j's limit is `permille` when jobj[j] is the winner's object and `cross`
-// otherwise.  A key's low half is its entry, so no two keys are equal and the partial minima stay keys alone.
-__global__ void __launch_bounds__(256) k_nms_list_objects_round(unsigned long long* keys, const int4* __restrict__ boxes,
-                                                                const int* __restrict__ jobj, long long n, int permille, int cross,
-                                                                int round, int last, const unsigned long long* __restrict__ pk_in,
-                                                                unsigned long long* __restrict__ pk_out,
-                                                                unsigned long long* __restrict__ best) {
-    __shared__ unsigned long long sk[4];
-    __shared__ int sp[4];
-    unsigned long long W = kNoKey;
-    int none = 0;
-    if (round > 0) {
-        if (threadIdx.x < gridDim.x) W = pk_in[threadIdx.x];
-        nms_block_min(W, none, sk, sp);
-        if (blockIdx.x == 0 && threadIdx.x == 0) best[round - 1] = W;
-        if (W == kNoKey || last) {  // workgroup-uniform
-            if (threadIdx.x == 0) pk_out[blockIdx.x] = kNoKey;
-            return;
-        }
-    }
-    const long long jw = (long long)(unsigned)W;
-    int4 w = make_int4(0, 0, -1, -1);
-    int ow = -1;
-    if (round > 0) { w = boxes[jw]; ow = jobj[jw]; }
-    const long long Aw = (long long)(w.z - w.x + 1) * (long long)(w.w - w.y + 1);
-    const long long n_chunks = (n + 255) / 256;
-    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
-    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
-    unsigned long long mk = kNoKey;
-    for (long long c = c0; c < c1; ++c) {
-        const long long idx = c * 256 + threadIdx.x;
-        if (idx >= n) continue;
-        const unsigned long long v = keys[idx];
-        if (v == kNoKey) continue;
-        bool drop = false;
-        if (round > 0) {
-            drop = idx == jw;
-            if (!drop) {
-                const int4 b = boxes[idx];
-                drop = nms_suppresses(b.x, b.y, b.z, b.w, w.x, w.y, w.z, w.w, Aw, jobj[idx] == ow ? permille : cross);
-            }
-        }
-        if (drop) keys[idx] = kNoKey;
-        else if (v < mk) mk = v;
-    }
-    nms_block_min(mk, none, sk, sp);
-    if (threadIdx.x == 0) pk_out[blockIdx.x] = mk;
-}
-
-// ---- hull footprints (include/fdcm.h, "Hull footprints"): the rounds above with the shape of an entry the lattice points of
+// ---- hull footprints (include/fdcm.h, "Hull footprints"): the rounds with the shape of an entry the lattice points of
 // the convex hull of its pair's posed end points, row by row.  A shape is its box (the rounds' own), its area and a run of
-// the span table: row r of the box is the pixels xl .. xr in the box's frame, (0, -1) when it is empty.  Two kernels, the
-// plane form and the list form of the rounds with objects; a call without objects runs them with one object (no table of
-// objects: every entry's object is 0), which gives the same list since one plane holds no two equal keys.
+// the span table: row r of the box is the pixels xl .. xr in the box's frame, (0, -1) when it is empty.  Two forms of the
+// round below, the plane form and the list form with objects; a call without objects runs them with one object (no table
+// of objects: every entry's object is 0), which gives the same list since one plane holds no two equal keys.
 struct HullShape {
     long long area;  // A(u) = |P(u)|
     int row0;        // its first row of the span table; it has y1 - y0 + 1 rows
@@ -1223,138 +1006,146 @@ __device__ __forceinline__ bool hull_suppresses(int fx0, int fy0, int fx1, int f
     return 1000ll * I > (long long)permille * (A + Aw - I);
 }
 
-// k_nms_objects_round on shapes.  shapes: per pair; pobj null: one object.
-__global__ void __launch_bounds__(256) k_nms_hull_round(unsigned long long* keys, long long n_chunks, long long plane_chunks, int x0, int y0,
-                                                        int sx, int sy, int nx, int tiles_x, const int4* __restrict__ boxes,
-                                                        const HullShape* __restrict__ shapes, const int2* __restrict__ spans,
-                                                        const int* __restrict__ pobj, int permille, int cross, int round, int last,
-                                                        const unsigned long long* __restrict__ pk_in, const int* __restrict__ pp_in,
-                                                        unsigned long long* __restrict__ pk_out, int* __restrict__ pp_out,
-                                                        unsigned long long* __restrict__ best, int* __restrict__ pair) {
-    __shared__ unsigned long long sk[4];
-    __shared__ int sp[4];
-    __shared__ int2 ws[kHullStagedRows];
-    unsigned long long W = kNoKey;
-    int Wp = -1;
-    if (round > 0) {
-        if (threadIdx.x < gridDim.x) { W = pk_in[threadIdx.x]; Wp = pp_in[threadIdx.x]; }
-        nms_block_min_pair(W, Wp, sk, sp);
-        if (blockIdx.x == 0 && threadIdx.x == 0) { best[round - 1] = W; pair[round - 1] = W == kNoKey ? -1 : Wp; }
-        if (W == kNoKey || last) {  // workgroup-uniform
-            if (threadIdx.x == 0) { pk_out[blockIdx.x] = kNoKey; pp_out[blockIdx.x] = -1; }
-            return;
-        }
-    }
-    // the winner's object and shape (round 0: unused)
-    const unsigned gw = (unsigned)W;
-    int wx0 = 0, wy0 = 0, wx1 = -1, wy1 = -1, ow = -1, w_row0 = 0;
-    long long Aw = 0;
-    bool staged = false;
-    if (round > 0) {
-        const int4 b = boxes[Wp];
-        const HullShape s = shapes[Wp];
-        const int tx = x0 + (int)(gw % (unsigned)nx) * sx, ty = y0 + (int)(gw / (unsigned)nx) * sy;
-        wx0 = b.x + tx; wy0 = b.y + ty; wx1 = b.z + tx; wy1 = b.w + ty;
-        ow = pobj ? pobj[Wp] : 0;
-        Aw = s.area;
-        w_row0 = s.row0;
-        staged = hull_stage(spans, w_row0, b.w - b.y + 1, ws);
-    }
-    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
-    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
-    unsigned long long mk = kNoKey;
-    int mp = -1;
-    for (long long c = c0; c < c1; ++c) {
-        const long long idx = c * 256 + threadIdx.x;
-        const unsigned long long v = keys[idx];
-        if (v == kNoKey) continue;
-        const int o = (int)(c / plane_chunks);  // (wave-uniform)
-        const long long in_plane = idx - (long long)o * plane_chunks * 256;
-        const int tile = (int)(in_plane >> 10), r = (int)(in_plane & 1023);
-        const int i = (tile % tiles_x) * kTileX + ((r >> 6) & 3) * 4 + (r & 3);
-        const int j = (tile / tiles_x) * kTileY + (r >> 8) * 16 + ((r >> 2) & 15);
-        const unsigned g = (unsigned)(j * nx + i);
-        const int u = (int)(unsigned)v;
-        bool drop = false;
-        if (round > 0) {
-            drop = g == gw && o == ow;
-            if (!drop) {
-                const int4 b = boxes[u];
-                const HullShape s = shapes[u];
-                const int tx = x0 + i * sx, ty = y0 + j * sy;
-                drop = hull_suppresses(b.x + tx, b.y + ty, b.z + tx, b.w + ty, s.area, s.row0, wx0, wy0, wx1, wy1, Aw, w_row0, staged, ws,
-                                       spans, o == ow ? permille : cross);
-            }
-        }
-        if (drop) {
-            keys[idx] = kNoKey;
-        } else {
-            const unsigned long long key = (v & 0xffffffff00000000ull) | g;
-            if (nms_pair_less(key, u, mk, mp)) { mk = key; mp = u; }
-        }
-    }
-    nms_block_min_pair(mk, mp, sk, sp);
-    if (threadIdx.x == 0) { pk_out[blockIdx.x] = mk; pp_out[blockIdx.x] = mp; }
+// ---- the round of the greedy rule, every form of it: one launch of the scheme under "detections by footprint overlap".
+//   LIST  the entries.  Plane forms: G key planes, one behind the other, plane o holding best(g, o) (G = 1 without objects):
+//         one array of n_chunks runs of 256 keys, plane_chunks of them per plane (a plane is whole sub-tiles, so a run lies
+//         in one plane).  An entry's object is its run's plane, its point best_key_point inside the plane, its pair its key's
+//         low half; boxes, shapes and obj are per pair, and a footprint is the pair's box moved to the point's translation.
+//         The winner's entry is the one at its point in its object's plane: it is erased by object and point, an entry of
+//         another object at the same point only when the cross limit says so.  A partial carries the pair with the key,
+//         because the winner's entry of the plane is erased in the launch that needs its box.
+//         List forms: the winners' list of the windows' calls, n entries.  Entry j is (keys[j], boxes[j]), its key's low half
+//         j itself and its footprint its own, in the scene already; boxes, shapes and obj are per entry, so nothing goes
+//         through a pair.  No two keys are equal, so the partials are keys alone, ordered by key, and `pair` is not written.
+//         The winner's box is read from the list: a round erases keys, never boxes.
+//   HULL  the overlap test: hull_suppresses on shapes, else nms_suppresses on boxes.
+//   OBJ   objects (include/fdcm.h, "Objects"): the limit of an entry is `permille` when its object is the winner's and `cross`
+//         otherwise, and the plane forms order their partials as (key, pair); without, `permille` and by key.  The hull
+//         forms exist with objects alone: a null obj is "every entry's object is 0", which gives the list of a call without
+//         objects since one plane holds no two equal keys.
+// The instantiations are the six nms_rounds launches.  One writer per entry, no atomics, no cooperative launch.
+struct NmsArgs {
+    unsigned long long* keys;
+    const int4* boxes;
+    const HullShape* shapes;  // (HULL)
+    const int2* spans;        // (HULL) the span table
+    const int* obj;           // (OBJ) the objects' table; (HULL) or null
+    long long n;              // (LIST) entries
+    long long n_chunks, plane_chunks;  // runs of 256 entries: all of them, (plane forms) per plane
+    int x0, y0, sx, sy, nx, tiles_x;   // (plane forms) the grid
+    int permille, cross, round, last;
+    const unsigned long long* pk_in;  // the partials of round - 1 and of this round: keys, (plane forms) pairs
+    const int* pp_in;
+    unsigned long long* pk_out;
+    int* pp_out;
+    unsigned long long* best;  // the result list: keys, (plane forms) pairs
+    int* pair;
+};
+
+template <bool LIST, bool OBJ>
+__device__ __forceinline__ void nms_min(unsigned long long& key, int& pair, unsigned long long* sk, int* sp) {
+    if (LIST) nms_block_min(key, sk);
+    else if (OBJ) nms_block_min_pair(key, pair, sk, sp);
+    else nms_block_min(key, pair, sk, sp);
+}
+// An entry's footprint in the scene: entry u of boxes, in a plane form moved to grid point (i, j).
+template <bool LIST>
+__device__ __forceinline__ int4 nms_footprint(const NmsArgs& a, long long u, int i, int j) {
+    const int4 b = a.boxes[u];
+    if (LIST) return b;
+    const int tx = a.x0 + i * a.sx, ty = a.y0 + j * a.sy;
+    return make_int4(b.x + tx, b.y + ty, b.z + tx, b.w + ty);
+}
+template <bool HULL>
+__device__ __forceinline__ int nms_object(const NmsArgs& a, long long u) {
+    return HULL && !a.obj ? 0 : a.obj[u];
 }
 
-// k_nms_list_objects_round on shapes.  shapes: per entry of the list, its box the list's own; jobj null: one object.
-__global__ void __launch_bounds__(256) k_nms_hull_list_round(unsigned long long* keys, const int4* __restrict__ boxes,
-                                                             const HullShape* __restrict__ shapes, const int2* __restrict__ spans,
-                                                             const int* __restrict__ jobj, long long n, int permille, int cross, int round,
-                                                             int last, const unsigned long long* __restrict__ pk_in,
-                                                             unsigned long long* __restrict__ pk_out,
-                                                             unsigned long long* __restrict__ best) {
+template <bool LIST, bool HULL, bool OBJ>
+__global__ void __launch_bounds__(256) k_nms_round(const NmsArgs a) {
+    static_assert(OBJ || !HULL, "the hull forms exist with objects alone");
     __shared__ unsigned long long sk[4];
     __shared__ int sp[4];
-    __shared__ int2 ws[kHullStagedRows];
+    __shared__ int2 ws[HULL ? kHullStagedRows : 1];
     unsigned long long W = kNoKey;
-    int none = 0;
-    if (round > 0) {
-        if (threadIdx.x < gridDim.x) W = pk_in[threadIdx.x];
-        nms_block_min(W, none, sk, sp);
-        if (blockIdx.x == 0 && threadIdx.x == 0) best[round - 1] = W;
-        if (W == kNoKey || last) {  // workgroup-uniform
-            if (threadIdx.x == 0) pk_out[blockIdx.x] = kNoKey;
+    int Wp = -1;
+    if (a.round > 0) {
+        if (threadIdx.x < gridDim.x) {
+            W = a.pk_in[threadIdx.x];
+            if (!LIST) Wp = a.pp_in[threadIdx.x];
+        }
+        nms_min<LIST, OBJ>(W, Wp, sk, sp);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            a.best[a.round - 1] = W;
+            if (!LIST) a.pair[a.round - 1] = W == kNoKey ? -1 : Wp;
+        }
+        if (W == kNoKey || a.last) {  // workgroup-uniform
+            if (threadIdx.x == 0) {
+                a.pk_out[blockIdx.x] = kNoKey;
+                if (!LIST) a.pp_out[blockIdx.x] = -1;
+            }
             return;
         }
     }
-    const long long jw = (long long)(unsigned)W;
+    // the winner: its point or entry gw, its entry uw of the tables, its object, its footprint and area or shape (round 0: unused)
+    const unsigned gw = (unsigned)W;
+    const long long uw = LIST ? (long long)gw : (long long)Wp;
     int4 w = make_int4(0, 0, -1, -1);
     int ow = -1, w_row0 = 0;
     long long Aw = 0;
     bool staged = false;
-    if (round > 0) {
-        w = boxes[jw];
-        const HullShape s = shapes[jw];
-        ow = jobj ? jobj[jw] : 0;
-        Aw = s.area;
-        w_row0 = s.row0;
-        staged = hull_stage(spans, w_row0, w.w - w.y + 1, ws);
+    if (a.round > 0) {
+        w = nms_footprint<LIST>(a, uw, (int)(gw % (unsigned)a.nx), (int)(gw / (unsigned)a.nx));
+        const HullShape s = HULL ? a.shapes[uw] : HullShape{};  // (before the object, as in the walk below)
+        if (OBJ) ow = nms_object<HULL>(a, uw);
+        if (HULL) {
+            Aw = s.area;
+            w_row0 = s.row0;
+            staged = hull_stage(a.spans, w_row0, w.w - w.y + 1, ws);
+        }
     }
-    const long long n_chunks = (n + 255) / 256;
-    const long long c0 = n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
-    const long long c1 = n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
+    if (!HULL) Aw = (long long)(w.z - w.x + 1) * (long long)(w.w - w.y + 1);
+    const long long c0 = a.n_chunks * (long long)blockIdx.x / (long long)gridDim.x;
+    const long long c1 = a.n_chunks * ((long long)blockIdx.x + 1) / (long long)gridDim.x;
     unsigned long long mk = kNoKey;
+    int mp = -1;
     for (long long c = c0; c < c1; ++c) {
         const long long idx = c * 256 + threadIdx.x;
-        if (idx >= n) continue;
-        const unsigned long long v = keys[idx];
+        if (LIST && idx >= a.n) continue;
+        const unsigned long long v = a.keys[idx];
         if (v == kNoKey) continue;
+        // the entry: its plane, its point (i, j) = g or its place in the list, its entry u of the tables
+        const int plane = !LIST && OBJ ? (int)(c / a.plane_chunks) : 0;  // (wave-uniform)
+        int i = 0, j = 0;
+        if (!LIST) best_key_point(idx - (long long)plane * a.plane_chunks * 256, a.tiles_x, i, j);
+        const unsigned g = LIST ? (unsigned)idx : (unsigned)(j * a.nx + i);
+        const long long u = LIST ? idx : (long long)(int)(unsigned)v;
         bool drop = false;
-        if (round > 0) {
-            drop = idx == jw;
+        if (a.round > 0) {
+            drop = g == gw && (LIST || !OBJ || plane == ow);
             if (!drop) {
-                const int4 b = boxes[idx];
-                const HullShape s = shapes[idx];
-                drop = hull_suppresses(b.x, b.y, b.z, b.w, s.area, s.row0, w.x, w.y, w.z, w.w, Aw, w_row0, staged, ws, spans,
-                                       (jobj ? jobj[idx] : 0) == ow ? permille : cross);
+                // (the box and the shape before the object: their loads then go out together, ahead of the table's null test)
+                const int4 f = nms_footprint<LIST>(a, u, i, j);
+                const HullShape s = HULL ? a.shapes[u] : HullShape{};
+                const int limit = !OBJ || (LIST ? nms_object<HULL>(a, u) : plane) == ow ? a.permille : a.cross;
+                drop = HULL ? hull_suppresses(f.x, f.y, f.z, f.w, s.area, s.row0, w.x, w.y, w.z, w.w, Aw, w_row0, staged, ws, a.spans, limit)
+                            : nms_suppresses(f.x, f.y, f.z, f.w, w.x, w.y, w.z, w.w, Aw, limit);
             }
         }
-        if (drop) keys[idx] = kNoKey;
-        else if (v < mk) mk = v;
+        if (drop) {
+            a.keys[idx] = kNoKey;
+        } else if (LIST) {
+            if (v < mk) mk = v;
+        } else {
+            const unsigned long long key = (v & 0xffffffff00000000ull) | g;
+            if (OBJ ? nms_pair_less(key, (int)u, mk, mp) : key < mk) { mk = key; mp = (int)u; }
+        }
     }
-    nms_block_min(mk, none, sk, sp);
-    if (threadIdx.x == 0) pk_out[blockIdx.x] = mk;
+    nms_min<LIST, OBJ>(mk, mp, sk, sp);
+    if (threadIdx.x == 0) {
+        a.pk_out[blockIdx.x] = mk;
+        if (!LIST) a.pp_out[blockIdx.x] = mp;
+    }
 }
 
 long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
@@ -2701,7 +2492,7 @@ void check_hull_rows(const fdcm_templates* t, const fdcm_rotations* rot, int mar
 
 // Hull sets, the dense calls: the shapes of the call's pairs.  plan() before best_keys / objects_keys, which reserve bytes()
 // behind their own layout; upload() after them: the tables are built in the staging behind the first upload's bytes while the
-// scoring launches run, and go up on the same stream before the rounds; round() is one launch of k_nms_hull_round.
+// scoring launches run, and go up on the same stream before the rounds (plane_rounds).
 struct HullRun {
     std::vector<HullShape> shapes;
     size_t rows = 0;
@@ -2714,21 +2505,82 @@ struct HullRun {
         hull_fill(P, foot, margin, (HullShape*)h, (int32_t*)(h + o_spans()));
         FDCM_HIP(hipMemcpyAsync(R.d + R.o_hull, h, bytes(), hipMemcpyHostToDevice, fm->stream));
     }
-    void round(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, unsigned wgs, long long n_chunks, long long plane_chunks,
-               const int* pobj, int permille, int cross, int r, int last, unsigned long long* pk, int* pp) const {
-        const int in = (r + 1) & 1, to = r & 1;
-        char* d = R.d;
-        hipLaunchKernelGGL(k_nms_hull_round, dim3(wgs), dim3(256), 0, fm->stream, (unsigned long long*)(d + R.o_keys), n_chunks, plane_chunks,
-                           g.x0, g.y0, g.sx, g.sy, g.nx, R.tiles_x, (const int4*)(d + R.o_foot), (const HullShape*)(d + R.o_hull),
-                           (const int2*)(d + R.o_hull + o_spans()), pobj, permille, cross, r, last,
-                           (const unsigned long long*)(pk + in * kNmsWorkgroups), (const int*)(pp + in * kNmsWorkgroups),
-                           pk + to * kNmsWorkgroups, pp + to * kNmsWorkgroups, (unsigned long long*)(d + R.o_best), (int*)(d + R.o_pair));
-        FDCM_HIP(hipGetLastError());
-    }
 };
 
+// The rounds of the overlap rule, for every call that has them: round r = 0 .. max_det writes winner r - 1, and the last one
+// only reduces.  They are queued kNmsBatch at a time: after each batch the host reads the batch's last winner and stops when
+// the list has ended, so a short list costs one batch and no round costs a host round trip.  a: everything but round, last
+// and the partials of round - 1; pk_out, pp_out (null for a list form): the first of the two sets of partials, the second
+// kNmsWorkgroups entries behind it, used in turn.  The form is the arguments': a list form has no planes (plane_chunks 0),
+// a hull form has shapes, and a form with objects is a hull form or one with a table of objects.
+constexpr int kNmsBatch = 64;
+// so fdcm_search_exhaustive_detect_nms, whose k is at most kMaxK, queues its k + 1 launches with no host synchronisation
+static_assert(kMaxK <= kNmsBatch, "a call with k <= kMaxK results is one batch");
+
+static void nms_rounds(NmsArgs a, unsigned wgs, int max_det, hipStream_t st) {
+    const bool list = a.plane_chunks == 0, hull = a.shapes != nullptr, obj = hull || a.obj != nullptr;
+    auto kern = list ? (hull ? k_nms_round<true, true, true> : obj ? k_nms_round<true, false, true> : k_nms_round<true, false, false>)
+                     : (hull ? k_nms_round<false, true, true> : obj ? k_nms_round<false, false, true> : k_nms_round<false, false, false>);
+    unsigned long long* const pk = a.pk_out;
+    int* const pp = a.pp_out;
+    for (int r = 0; r <= max_det;) {
+        const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));  // winners [.., r1) after this batch: whole batches
+        for (; r <= r1; ++r) {
+            const int in = (r + 1) & 1, to = r & 1;
+            a.round = r;
+            a.last = (int)(r == max_det);
+            a.pk_in = pk + in * kNmsWorkgroups;
+            a.pk_out = pk + to * kNmsWorkgroups;
+            a.pp_in = pp ? pp + in * kNmsWorkgroups : nullptr;
+            a.pp_out = pp ? pp + to * kNmsWorkgroups : nullptr;
+            hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), 0, st, a);
+            FDCM_HIP(hipGetLastError());
+        }
+        if (r > max_det) break;
+        unsigned long long last = kNoKey;  // winner r1 - 1, the batch's last
+        FDCM_HIP(hipMemcpyAsync(&last, a.best + (r1 - 1), 8, hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+        if (last == kNoKey) break;  // the list has ended: the entries from there on are kNoKey (written, or the upload's)
+    }
+}
+
+// The rounds of a dense call on the G key planes best_keys or objects_keys left at R.o_keys, with the pairs' footprints at
+// o_foot, the partials at o_cand and the result list at o_best and o_pair.  H (or null): the set's shapes, uploaded.  pobj (or
+// null): the objects' per-pair table, on the device.
+static void plane_rounds(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, int G, const HullRun* H, const int* pobj,
+                         int permille, int cross, int max_det) {
+    char* d = R.d;
+    NmsArgs a{};
+    a.keys = (unsigned long long*)(d + R.o_keys);
+    a.boxes = (const int4*)(d + R.o_foot);
+    if (H) {
+        a.shapes = (const HullShape*)(d + R.o_hull);
+        a.spans = (const int2*)(d + R.o_hull + H->o_spans());
+    }
+    a.obj = pobj;
+    a.plane_chunks = (long long)(R.n_keys / 256);  // whole sub-tiles: a multiple of 4
+    a.n_chunks = a.plane_chunks * G;
+    a.n = a.n_chunks * 256;
+    a.x0 = g.x0; a.y0 = g.y0; a.sx = g.sx; a.sy = g.sy; a.nx = g.nx; a.tiles_x = R.tiles_x;
+    a.permille = permille;
+    a.cross = cross;
+    a.pk_out = (unsigned long long*)(d + R.o_cand);
+    a.pp_out = (int*)(d + R.o_cand + 2 * kNmsWorkgroups * 8);
+    a.best = (unsigned long long*)(d + R.o_best);
+    a.pair = (int*)(d + R.o_pair);
+    nms_rounds(a, (unsigned)std::min<long long>(kNmsWorkgroups, a.n_chunks), max_det, fm->stream);
+}
+
+// The footprints of the pairs of a dense call, from the lines the kernels score (a pair without a grid point is never read).
+static std::vector<Foot> pair_footprints(const Pairs& P, int margin) {
+    std::vector<Foot> foot(P.nl.size());
+    for (size_t u = 0; u < foot.size(); ++u)
+        foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    return foot;
+}
+
 // Detections by footprint overlap (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  The key plane is
-// best_keys', the rounds are k_nms_round's, the records run_search_exhaustive_detect's.
+// best_keys', the rounds are plane_rounds', the records run_search_exhaustive_detect's.
 void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
                                       int permille, int margin, int penalty, float tau, int32_t base, fdcm_match** out,
                                       int32_t* boxes_out, int64_t* n_out) {
@@ -2741,42 +2593,16 @@ void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates*
     if (rot) check_rotated_size(t, n);
     Pairs P;
     prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, P);
-    // the footprints, from the lines the kernels score (a pair without a grid point is never read)
-    std::vector<Foot> foot(P.nl.size());
-    for (size_t u = 0; u < foot.size(); ++u)
-        foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    const std::vector<Foot> foot = pair_footprints(P, margin);
     const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
     HullRun H;
     if (hull) H.plan(foot);
     BestRun R;
     if (!best_keys(fm, P, t, n, g, penalty, tau, k, R, &foot, kMaxK, nullptr, nullptr, hull ? H.bytes() : 0)) return;
     if (hull) H.upload(fm, R, P, foot, margin);
-    hipStream_t st = fm->stream;
-    char* d = R.d;
-    unsigned long long* pk = (unsigned long long*)(d + R.o_cand);
-    int* pp = (int*)(d + R.o_cand + 2 * kNmsWorkgroups * 8);
-    const long long n_chunks = (long long)(R.n_keys / 256);  // whole sub-tiles: a multiple of 4
-    const unsigned wgs = (unsigned)std::min<long long>(kNmsWorkgroups, n_chunks);
-    for (int r = 0; r <= k; ++r) {
-        if (hull) {
-            H.round(fm, R, g, wgs, n_chunks, n_chunks, nullptr, permille, permille, r, (int)(r == k), pk, pp);
-            continue;
-        }
-        const int in = (r + 1) & 1, to = r & 1;
-        hipLaunchKernelGGL(k_nms_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)(d + R.o_keys), n_chunks, g.x0, g.y0, g.sx, g.sy,
-                           g.nx, R.tiles_x, (const int4*)(d + R.o_foot), permille, r, (int)(r == k),
-                           (const unsigned long long*)(pk + in * kNmsWorkgroups), (const int*)(pp + in * kNmsWorkgroups),
-                           pk + to * kNmsWorkgroups, pp + to * kNmsWorkgroups, (unsigned long long*)(d + R.o_best), (int*)(d + R.o_pair));
-        FDCM_HIP(hipGetLastError());
-    }
+    plane_rounds(fm, R, g, 1, hull ? &H : nullptr, nullptr, permille, permille, k);
     detect_records(fm, R, P, rot != nullptr, n, g, k, base, out, n_out, foot.data(), boxes_out);
 }
-
-// All detections below a score (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  The key plane holds the points
-// with q <= max_score alone (best_keys with a threshold), the rounds are k_nms_round's on result arrays of max_det entries,
-// queued kNmsBatch at a time: after each batch the host reads the batch's last winner and stops when the list has ended, so
-// a short list costs one batch and no round costs a host round trip.
-constexpr int kNmsBatch = 64;
 
 // What the calls with objects (include/fdcm.h, "Objects") take beside their siblings' arguments.
 struct ObjectsIn {
@@ -2796,7 +2622,20 @@ void templates_matched_totals(const fdcm_templates* t, float* totals) {
     }
 }
 
-// Both detection calls with a threshold.  matched: the call by matched fraction (include/fdcm.h), the other's own work plus,
+// The fractions of the result list of a dense call, at R.o_frac: k_matched_list on the max_det entries at o_best and o_pair.
+static void matched_list(fdcm_featuremap* fm, const Pairs& P, const BestRun& R, const fdcm_grid& g, int max_det) {
+    char* d = R.d;
+    auto kern = P.buf32 ? k_matched_list<true> : k_matched_list<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((max_det + 255) / 256)), dim3(256), 0, fm->stream, fm->vol.as<float>(), P.SL, (int)fm->m,
+                       (int)fm->W, (int)fm->H, fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
+                       (const float*)(d + R.o_tl), (const unsigned long long*)(d + R.o_best), (const int*)(d + R.o_pair), max_det, g.x0,
+                       g.y0, g.sx, g.sy, g.nx, (float*)(d + R.o_frac));
+    FDCM_HIP(hipGetLastError());
+}
+
+// Both detection calls with a threshold (include/fdcm.h, "All detections below a score"): the arguments are checked
+// (fdcm_capi.cpp).  The key plane holds the points with q <= max_score alone (best_keys with a threshold), the rounds are
+// plane_rounds' on result arrays of max_det entries.  matched: the call by matched fraction (include/fdcm.h), the other's own work plus,
 // with min_matched > 0, the gate pass over the key plane before the first round and, with matched_out, the fractions of the
 // result list after the last; min_matched = 0 and no matched_out queue what the other call queues.
 static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, float max_score,
@@ -2813,9 +2652,7 @@ static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
     Pairs P;
     P.lens = gate || fracs;
     prepare_pairs(fm, t, rot, matched ? test_switches().matched_flat : test_switches().exhaustive_flat, P);
-    std::vector<Foot> foot(P.nl.size());
-    for (size_t u = 0; u < foot.size(); ++u)
-        foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    const std::vector<Foot> foot = pair_footprints(P, margin);
     // per pair: need = float32(min_matched * TL) of its template, and TL
     std::vector<float> need, tl;
     if (P.lens) {
@@ -2850,39 +2687,8 @@ static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
                            R.tiles_x);
         FDCM_HIP(hipGetLastError());
     }
-    unsigned long long* pk = (unsigned long long*)(d + R.o_cand);
-    int* pp = (int*)(d + R.o_cand + 2 * kNmsWorkgroups * 8);
-    unsigned long long* d_best = (unsigned long long*)(d + R.o_best);
-    const long long n_chunks = (long long)(R.n_keys / 256);
-    const unsigned wgs = (unsigned)std::min<long long>(kNmsWorkgroups, n_chunks);
-    for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
-        const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));  // winners [.., r1) after this batch: whole batches
-        for (; r <= r1; ++r) {
-            if (hull) {
-                H.round(fm, R, g, wgs, n_chunks, n_chunks, nullptr, permille, permille, r, (int)(r == max_det), pk, pp);
-                continue;
-            }
-            const int in = (r + 1) & 1, to = r & 1;
-            hipLaunchKernelGGL(k_nms_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)(d + R.o_keys), n_chunks, g.x0, g.y0, g.sx,
-                               g.sy, g.nx, R.tiles_x, (const int4*)(d + R.o_foot), permille, r, (int)(r == max_det),
-                               (const unsigned long long*)(pk + in * kNmsWorkgroups), (const int*)(pp + in * kNmsWorkgroups),
-                               pk + to * kNmsWorkgroups, pp + to * kNmsWorkgroups, d_best, (int*)(d + R.o_pair));
-            FDCM_HIP(hipGetLastError());
-        }
-        if (r > max_det) break;
-        unsigned long long last = kNoKey;  // winner r1 - 1, the batch's last
-        FDCM_HIP(hipMemcpyAsync(&last, d_best + (r1 - 1), 8, hipMemcpyDeviceToHost, st));
-        FDCM_HIP(hipStreamSynchronize(st));
-        if (last == kNoKey) break;  // the list has ended: the entries from there on are kNoKey (written, or the upload's)
-    }
-    if (fracs) {
-        auto kern = P.buf32 ? k_matched_list<true> : k_matched_list<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((max_det + 255) / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
-                           fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
-                           (const float*)(d + R.o_tl), (const unsigned long long*)d_best, (const int*)(d + R.o_pair), max_det, g.x0, g.y0,
-                           g.sx, g.sy, g.nx, (float*)(d + R.o_frac));
-        FDCM_HIP(hipGetLastError());
-    }
+    plane_rounds(fm, R, g, 1, hull ? &H : nullptr, nullptr, permille, permille, max_det);
+    if (fracs) matched_list(fm, P, R, g, max_det);
     detect_records(fm, R, P, rot != nullptr, n, g, max_det, base, out, n_out, foot.data(), boxes_out, fracs ? matched_out : nullptr);
 }
 
@@ -3063,8 +2869,8 @@ void run_best_map_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fd
 }
 
 // Dense detections with objects (include/fdcm.h, "Objects"): detect_all on G planes.  The gate of FDCM_GATE_WINNER is
-// k_matched_gate on the planes of the objects with min_matched > 0; the rounds are k_nms_objects_round's over all planes,
-// queued kNmsBatch at a time; the fractions and the records are detect_all's.  The arguments are checked (fdcm_capi.cpp).
+// k_matched_gate on the planes of the objects with min_matched > 0; the rounds are plane_rounds' over all planes, with
+// the objects' table; the fractions and the records are detect_all's.  The arguments are checked (fdcm_capi.cpp).
 void run_search_exhaustive_detect_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                           const int32_t* objects, int n_objects, const float* max_score, const float* min_matched,
                                           int max_det, int permille, int cross, int margin, int penalty, float tau, int gate_kind,
@@ -3081,9 +2887,7 @@ void run_search_exhaustive_detect_objects(fdcm_featuremap* fm, const fdcm_templa
     Pairs P;
     P.lens = gate || fracs;
     prepare_pairs(fm, t, rot, test_switches().matched_flat, P);
-    std::vector<Foot> foot(P.nl.size());
-    for (size_t u = 0; u < foot.size(); ++u)
-        foot[u] = footprint((const float*)(P.lines.data() + P.line0[u]), sizeof(ExLine) / sizeof(float), P.nl[u], margin);
+    const std::vector<Foot> foot = pair_footprints(P, margin);
     const ObjectsIn ob{objects, n_objects, max_score, min_matched, cross};
     const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
     HullRun H;
@@ -3106,39 +2910,8 @@ void run_search_exhaustive_detect_objects(fdcm_featuremap* fm, const fdcm_templa
             FDCM_HIP(hipGetLastError());
         }
     }
-    unsigned long long* pk = (unsigned long long*)(d + R.o_cand);
-    int* pp = (int*)(d + R.o_cand + 2 * kNmsWorkgroups * 8);
-    unsigned long long* d_best = (unsigned long long*)(d + R.o_best);
-    const long long plane_chunks = (long long)(R.n_keys / 256), n_chunks = plane_chunks * n_objects;
-    const unsigned wgs = (unsigned)std::min<long long>(kNmsWorkgroups, n_chunks);
-    for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
-        const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));  // winners [.., r1) after this batch: whole batches
-        for (; r <= r1; ++r) {
-            if (hull) {
-                H.round(fm, R, g, wgs, n_chunks, plane_chunks, (const int*)(d + R.o_pobj), permille, cross, r, (int)(r == max_det), pk, pp);
-                continue;
-            }
-            const int in = (r + 1) & 1, to = r & 1;
-            hipLaunchKernelGGL(k_nms_objects_round, dim3(wgs), dim3(256), 0, st, keys, n_chunks, plane_chunks, g.x0, g.y0, g.sx, g.sy, g.nx,
-                               R.tiles_x, (const int4*)(d + R.o_foot), (const int*)(d + R.o_pobj), permille, cross, r, (int)(r == max_det),
-                               (const unsigned long long*)(pk + in * kNmsWorkgroups), (const int*)(pp + in * kNmsWorkgroups),
-                               pk + to * kNmsWorkgroups, pp + to * kNmsWorkgroups, d_best, (int*)(d + R.o_pair));
-            FDCM_HIP(hipGetLastError());
-        }
-        if (r > max_det) break;
-        unsigned long long last = kNoKey;  // winner r1 - 1, the batch's last
-        FDCM_HIP(hipMemcpyAsync(&last, d_best + (r1 - 1), 8, hipMemcpyDeviceToHost, st));
-        FDCM_HIP(hipStreamSynchronize(st));
-        if (last == kNoKey) break;  // the list has ended: the entries from there on are kNoKey (written, or the upload's)
-    }
-    if (fracs) {
-        auto kern = P.buf32 ? k_matched_list<true> : k_matched_list<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((max_det + 255) / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
-                           fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
-                           (const float*)(d + R.o_tl), (const unsigned long long*)d_best, (const int*)(d + R.o_pair), max_det, g.x0, g.y0,
-                           g.sx, g.sy, g.nx, (float*)(d + R.o_frac));
-        FDCM_HIP(hipGetLastError());
-    }
+    plane_rounds(fm, R, g, n_objects, hull ? &H : nullptr, (const int*)(d + R.o_pobj), permille, cross, max_det);
+    if (fracs) matched_list(fm, P, R, g, max_det);
     detect_records(fm, R, P, rot != nullptr, n, g, max_det, base, out, n_out, foot.data(), boxes_out, fracs ? matched_out : nullptr);
 }
 
@@ -3215,14 +2988,14 @@ static void matched_fractions_rounds(fdcm_featuremap* fm, const fdcm_templates* 
 
 // Detections over pose windows (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  The job list goes through
 // windows_round at k = 1 in the pose windows' rounds, each with the winners' pass behind its last merge; the rounds leave
-// the winners' list on the host, a key and a footprint per job, which goes up whole for the rounds of k_nms_list_round,
-// queued kNmsBatch at a time as detect_all queues k_nms_round's.  A record is emit_records' for the key (bits of q << 32) |
+// the winners' list on the host, a key and a footprint per job, which goes up whole for the rounds of the list
+// forms of k_nms_round, queued by nms_rounds as the dense calls' are.  A record is emit_records' for the key (bits of q << 32) |
 // (e N_j + g) of its job's winner; its box is the list's; its fraction k_matched_fractions' at the record's pose, in a
 // round of its own after the last launch.  The 64-bit form follows FDCM_WINDOWS_FLAT and FDCM_MATCHED_FLAT.  gate
 // FDCM_GATE_ALL ("Gate inside the minimum") with min_matched > 0: the scoring kernel's gated form, and the winners' pass without need.
 //
 // ob (ObjectsIn, or null): the threshold and the need of a job are its object's (max_score and min_matched are then unused),
-// the winners' pass is k_window_winners_objects and the rounds are k_nms_list_objects_round's, with the jobs' objects behind
+// the winners' pass is k_window_winners_objects and the rounds are the list form's with objects, the jobs' objects behind
 // the boxes in the same upload.  Without it the call queues what it queued before objects existed.
 static void detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_pose_window* jobs,
                            int64_t n_jobs, int sx, int sy, float max_score, int max_det, int permille, int margin, int penalty, float tau,
@@ -3321,35 +3094,22 @@ static void detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const f
     std::memset(h + o_best, 0xff, (size_t)max_det * 8);  // kNoKey
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d, h, o_pk, hipMemcpyHostToDevice, st));
-    unsigned long long* pk = (unsigned long long*)(d + o_pk);
     unsigned long long* d_best = (unsigned long long*)(d + o_best);
-    const unsigned wgs = (unsigned)std::min<size_t>(kNmsWorkgroups, (nj + 255) / 256);
-    for (int r = 0; r <= max_det;) {  // round r writes winner r - 1; the last one (r = max_det) only reduces
-        const int r1 = std::min(max_det, r + kNmsBatch - (r == 0 ? 0 : 1));
-        for (; r <= r1; ++r) {
-            if (hull)
-                hipLaunchKernelGGL(k_nms_hull_list_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
-                                   (const HullShape*)(d + o_shape), (const int2*)(d + o_spans), ob ? (const int*)(d + o_obj) : nullptr,
-                                   (long long)n_jobs, permille, ob ? ob->cross : permille, r, (int)(r == max_det),
-                                   (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups,
-                                   d_best);
-            else if (ob)
-                hipLaunchKernelGGL(k_nms_list_objects_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
-                                   (const int*)(d + o_obj), (long long)n_jobs, permille, ob->cross, r, (int)(r == max_det),
-                                   (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups,
-                                   d_best);
-            else
-                hipLaunchKernelGGL(k_nms_list_round, dim3(wgs), dim3(256), 0, st, (unsigned long long*)d, (const int4*)(d + o_box),
-                                   (long long)n_jobs, permille, r, (int)(r == max_det),
-                                   (const unsigned long long*)(pk + ((r + 1) & 1) * kNmsWorkgroups), pk + (r & 1) * kNmsWorkgroups, d_best);
-            FDCM_HIP(hipGetLastError());
-        }
-        if (r > max_det) break;
-        unsigned long long last = kNoKey;  // winner r1 - 1, the batch's last
-        FDCM_HIP(hipMemcpyAsync(&last, d_best + (r1 - 1), 8, hipMemcpyDeviceToHost, st));
-        FDCM_HIP(hipStreamSynchronize(st));
-        if (last == kNoKey) break;
+    NmsArgs a{};  // a list form: no planes, no pairs
+    a.keys = (unsigned long long*)d;
+    a.boxes = (const int4*)(d + o_box);
+    if (hull) {
+        a.shapes = (const HullShape*)(d + o_shape);
+        a.spans = (const int2*)(d + o_spans);
     }
+    if (ob) a.obj = (const int*)(d + o_obj);
+    a.n = (long long)n_jobs;
+    a.n_chunks = (a.n + 255) / 256;
+    a.permille = permille;
+    a.cross = ob ? ob->cross : permille;
+    a.pk_out = (unsigned long long*)(d + o_pk);
+    a.best = d_best;
+    nms_rounds(a, (unsigned)std::min<long long>(kNmsWorkgroups, a.n_chunks), max_det, st);
     std::vector<unsigned long long> best((size_t)max_det);
     FDCM_HIP(hipMemcpyAsync(best.data(), d_best, (size_t)max_det * 8, hipMemcpyDeviceToHost, st));
     FDCM_HIP(hipStreamSynchronize(st));
