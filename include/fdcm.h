@@ -981,6 +981,59 @@ int fdcm_lines_read(const char* path, float** lines, int64_t* n_lines);
 int fdcm_lines_write(const char* path, const float* lines, int64_t n_lines);
 void fdcm_lines_free(float* lines);
 
+/* ---- Scene coverage: which edge pixels of a label image a pose explains, and the label image without them (not in the
+ *      reference).  Every other cue runs from the template to the scene -- does each template line lie on scene edges? --, and
+ *      in dense texture the answer is yes for any template of few lines.  This one runs from the scene to the template: of the
+ *      edge pixels inside a detection's footprint, how many does the posed template account for?  Near all of them for a part
+ *      lying alone, few for a hit in clutter.  The same decision per pixel gives the residual: the labels without the pixels
+ *      the accepted detections explain, which fdcm_featuremap_rebuild_labels turns into the map of the next round of a
+ *      detect, explain away, detect again loop.  All arithmetic is integer; the results are a function of the inputs alone,
+ *      whatever order the GPU visits pixels in.  The definition in plain Python integers: tests/coverage_ref.py.
+ *
+ *      Inputs.  fm is used for its size (W, H), its scene translation T, its m keys and the admissibility rule; the volume is
+ *      not read.  labels is a label image as fdcm_edge_labels makes it, width x height bytes without gaps: a byte < m is an
+ *      edge pixel of that slice, anything else is no edge.  templates, rot (or NULL) and the n poses (tmpl, a, x, y) are
+ *      fdcm_line_costs'.
+ *      Frames.  T must be whole pixels, T = (bx, by) with integers bx, by >= 0, and width + 2 bx == W, height + 2 by == H: any
+ *      map built from an image or from labels (bx = by = border).  Label pixel (px, py) is map pixel (px + bx, py + by) and
+ *      scene point (px, py).
+ *      Segment of line i of pair u = (tmpl, a) at (x, y): it joins the two map pixels A_i, B_i whose integral values the line's
+ *      cost subtracts -- fdcm_line_costs' rule for the (rotated) line at offset T + t, truncation included --, moved to the
+ *      label frame by -(bx, by); its bin b_i is the slice that line reads.
+ *      Window of pose q: F = box(tmpl, a) + (x, y), the box fdcm_templates_footprints gives at `margin`, intersected with
+ *      [0, width - 1] x [0, height - 1]; it may be empty.  The footprint kind of a set with hull footprints is ignored.
+ *      Explained.  An edge pixel P with label l is explained by pose q when some line i of the pair passes both tests:
+ *        min(|l - b_i|, m - |l - b_i|) <= bin_tolerance;
+ *        the squared distance from P to the segment A_i B_i is <= radius^2, decided exactly in int64: with d = B - A,
+ *        w = P - A, dot = w.d and len2 = d.d: if dot <= 0 (also A = B): w.w <= r^2; else if dot >= len2: |P - B|^2 <= r^2;
+ *        else cross^2 <= r^2 len2 with cross = w.x d.y - w.y d.x.
+ *      Counts.  For an admissible pose, edges[q] is the number of edge pixels in its window and explained[q] the number of
+ *      those explained by pose q itself; a template without lines has an empty window: (0, 0).  A pose that is not admissible
+ *      for (tmpl, a) gives (-1, -1) and explains nothing.
+ *      Residual (optional): the labels, with 255 at every edge pixel P that some admissible pose q of the list has in its
+ *      window and explains.  Duplicate poses change nothing.  residual_out must not overlap labels.
+ *      Identities: explained <= edges; explained does not fall when radius or bin_tolerance grows at a fixed margin; with
+ *      bin_tolerance = m / 2 the labels' values stop mattering beyond "is an edge"; the residual of the concatenation of two
+ *      pose lists is the per-pixel "255 if either" of the two residuals; a label image without edges gives (0, 0) for
+ *      admissible poses and itself as residual.
+ *      FDCM_EINVAL, before any GPU work: what fdcm_line_costs rejects about n, poses, rot, pivots and the handles; n > 2^20;
+ *      params NULL, radius outside 0 .. 32, bin_tolerance < 0 or > m / 2, margin outside 0 .. 4096; labels NULL, width or
+ *      height outside 1 .. 4096; counts_out NULL with n > 0; a map whose scene translation is not whole non-negative pixels, or
+ *      whose size is not (width + 2 bx, height + 2 by) -- the message names which.  n = 0 writes the residual, a copy, and
+ *      returns FDCM_OK; so does an empty feature map (no pixels or no keys: it has no frame to check) or an empty template
+ *      set, which leave the counts unwritten as the siblings do.  The call blocks.  on_device = 1: labels and residual_out are memory of the handle's device, and labels is read in
+ *      place.  The buffers are the handle's own, not the workspace the exhaustive calls share. ---- */
+typedef struct fdcm_coverage_params {
+    int32_t radius;         /* 0 .. 32 pixels */
+    int32_t bin_tolerance;  /* 0 .. m / 2 slices, circular */
+    int32_t margin;         /* 0 .. 4096: the footprint's margin */
+} fdcm_coverage_params;     /* 12 bytes */
+int fdcm_scene_coverage(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device,
+                        const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                        const int32_t* poses /* n x 4: tmpl, a, x, y */, int64_t n, const fdcm_coverage_params* params,
+                        int32_t* counts_out /* n x 2: edges, explained (host) */,
+                        uint8_t* residual_out /* width * height, or NULL; device memory when on_device = 1 */);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

@@ -1222,4 +1222,41 @@ def matched_fractions(featuremap, templates, poses, angles=None, pivot="center",
     return fm.matched_fractions(tset, poses, cs, pv)
 
 
+# ---------------------------------------------------------------- scene coverage (extension)
+def record_poses(records, angles=None, pivots=None):
+    """The (n, 4) int32 poses (tmpl, a, x, y) of detection records (a MatchList or its record array, tmpl_idx without a
+    base), as line_costs, matched_fractions and scene_coverage take them: pure numpy.  With the angles of the search (and its
+    pivots, template_pivots, or None for the origin) exactly pose_windows(records, angles, angles, pivots, 0, 0, 0)[:, [0, 1, 3, 4]];
+    without angles (tmpl_idx, 0, rint(transform[2]), rint(transform[5]))."""
+    if angles is not None:
+        return _np.ascontiguousarray(pose_windows(records, angles, angles, pivots, 0, 0, 0)[:, [0, 1, 3, 4]], dtype=_np.int32)
+    rec = records.records() if isinstance(records, MatchList) else _np.asarray(records)
+    out = _np.zeros((rec.shape[0], 4), dtype=_np.int32)
+    out[:, 0] = rec["tmpl_idx"]
+    out[:, 2] = _np.rint(rec["transform"][:, 2].astype(_np.float64)).astype(_np.int64)
+    out[:, 3] = _np.rint(rec["transform"][:, 5].astype(_np.float64)).astype(_np.int64)
+    return out
+
+
+def scene_coverage(featuremap, labels, templates, poses, angles=None, pivot="center", radius=2, bin_tolerance=1, margin=None,
+                   return_residual=False):
+    """Which edge pixels a pose explains: the cue that runs from the scene to the template.  labels is the label image the
+    feature map was built from (edge_labels; a numpy array or a contiguous CUDA tensor), poses an (n, 4) int32 array of rows
+    (tmpl, a, x, y) as line_costs takes them (record_poses makes them from detections).  Per pose: the number of edge pixels in
+    its window -- the template's footprint there, widened by margin (None: radius) and cut to the image -- and the number of
+    those within radius pixels of one of the posed template's segments whose orientation slice is within bin_tolerance of the
+    pixel's (circular).  explained / edges is near 1 for a part lying alone and low for a hit in clutter, which the score
+    and the matched fraction cannot tell apart.  (-1, -1) where the pose puts the template outside the feature map.  Returns
+    the (n, 2) int32 counts, and with return_residual also the labels with 255 at every explained pixel (a tensor on the
+    same device for a tensor): rebuild_labels(residual) gives the map of the next round of a detect, explain away, detect
+    again loop.  The map must be one built from an image or from labels."""
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates)
+    cs = pv = None
+    if angles is not None:
+        cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
+    return fm.scene_coverage(labels, tset, poses, cs, pv, radius=radius, bin_tolerance=bin_tolerance, margin=margin,
+                             residual=return_residual)
+
+
 from .lineio import read, write  # noqa: E402  (.lines/.scene/.tmpl files, serialization.h)

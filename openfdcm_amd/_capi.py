@@ -83,6 +83,13 @@ class LinesTiming(C.Structure):
                                          "fit_ms", "total_ms")] + [("n_lines", C.c_int64)]
 
 
+class CoverageParams(C.Structure):
+    """fdcm_coverage_params: the radius in pixels, the circular tolerance in slices and the footprint's margin."""
+    _fields_ = [("radius", C.c_int32), ("bin_tolerance", C.c_int32), ("margin", C.c_int32)]
+
+
+assert C.sizeof(CoverageParams) == 12
+
 # every symbol include/fdcm.h declares: (name, restype, argtypes)
 _fp, _i64p, _vp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_void_p
 SYMBOLS = [
@@ -227,6 +234,8 @@ SYMBOLS = [
     ("fdcm_templates_line_lengths", C.c_int, [_vp, _fp]),
     ("fdcm_line_costs", C.c_int, [_vp, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.POINTER(C.c_float)),
                                   _i64p]),
+    ("fdcm_scene_coverage", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64,
+                                      C.POINTER(CoverageParams), C.POINTER(C.c_int32), _vp]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),
     ("fdcm_lines_free", None, [C.POINTER(C.c_float)]),

@@ -1,0 +1,290 @@
+// fdcm_coverage.hip -- scene coverage (include/fdcm.h, "Scene coverage"): which edge pixels of a label image the posed
+// templates explain, per pose the counts (edges, explained), and the label image without the explained pixels.
+//
+//   k_scene_coverage    a workgroup per item (pose, strip of rows of its window).  The items are a 1-D list the poses'
+//                       prefix sums describe: item e belongs to the pose p with item0[p] <= e < item0[p + 1], found by
+//                       bisection on scalar loads, and is strip e - item0[p] of that pose's clipped window.  The workgroup
+//                         1. stages the pose's segments in LDS: per line the two map pixels k_line_costs reads (its float
+//                            adds and truncation), moved to the label frame, the segment's bounding box widened by the
+//                            radius, len2 and the bin; in chunks of kCovLines when the template has more;
+//                         2. scans its strip with aligned dword loads, 4 label bytes per lane (the head and tail words of
+//                            the image byte by byte), and compacts the edge pixels into a queue in LDS: a ballot and a
+//                            popcount per byte position, one LDS atomic per wave for the queue's space;
+//                         3. once the queue holds 256 pixels or the strip ends, gives every thread one queued pixel and
+//                            walks the segments at a wave-uniform index (an LDS broadcast): bin test, box test, then the
+//                            exact squared distance in int64.
+//                       Counts: wave-uniform popcounts, one atomicAdd per wave and counter at the item's end.  Residual:
+//                       byte stores of 255 into a copy of the labels; the decision reads the labels alone.
+//
+// All arithmetic of the decision is integer; the float adds of step 1 are the cost rule's own (-ffp-contract=off as everywhere).
+#include <algorithm>
+#include <cstring>
+
+#include "fdcm_internal.h"
+
+namespace fdcm {
+
+namespace {
+
+constexpr int kCovThreads = 256;
+constexpr int kCovLines = 256;                      // segments per LDS chunk
+constexpr int kCovQueue = kCovThreads + 4 * kCovThreads;  // what a scan pass finds at most, on top of an unprocessed rest
+constexpr int kCovStripPixels = 2048;               // window pixels per item, about (at least one row)
+constexpr long long kCovMaxGrid = 1ll << 30;        // items per launch
+
+struct CovPose {  // one admissible pose with a window: its pair's lines, its translation, its clipped window, rows per strip
+    int line0, n;
+    int x, y;
+    int wx0, wy0, wx1, wy1;
+    int rows, pad[3];
+};
+static_assert(sizeof(CovPose) == 48, "CovPose is 48 bytes");
+
+struct alignas(16) CovSeg {  // one segment in the label frame
+    int ax, ay, bx, by;
+    int x0, y0, x1, y1;  // its bounding box widened by the radius: outside it no pixel is within the radius
+    long long len2;
+    int bin, pad;
+};
+static_assert(sizeof(CovSeg) == 48, "CovSeg is 48 bytes");
+
+// Is P = (px, py) within r of the segment?  include/fdcm.h, "Scene coverage": exact in int64.  P lies in the widened box, the
+// segment's ends in the map, so |w|, |d| stay below 2^31; a cross product of 2^31 or more is farther than any radius.
+__device__ __forceinline__ bool near_segment(const CovSeg& s, int px, int py, long long r2) {
+    const long long dx = (long long)s.bx - s.ax, dy = (long long)s.by - s.ay;
+    const long long wx = (long long)px - s.ax, wy = (long long)py - s.ay;
+    const long long dot = wx * dx + wy * dy;
+    if (dot <= 0) return wx * wx + wy * wy <= r2;
+    if (dot >= s.len2) {
+        const long long ux = (long long)px - s.bx, uy = (long long)py - s.by;
+        return ux * ux + uy * uy <= r2;
+    }
+    const long long cross = wx * dy - wy * dx;
+    if (cross >= (1ll << 31) || cross <= -(1ll << 31)) return false;
+    return cross * cross <= r2 * s.len2;
+}
+
+__global__ void __launch_bounds__(kCovThreads) k_scene_coverage(const uint8_t* __restrict__ labels, int width, int height, int m, float tx,
+                                                                float ty, int bx, int by, int radius, int tol,
+                                                                const CoverageLine* __restrict__ lines, const CovPose* __restrict__ poses,
+                                                                const long long* __restrict__ item0, int n_poses, long long item_base,
+                                                                int* __restrict__ counts, uint8_t* __restrict__ residual) {
+    __shared__ CovSeg seg[kCovLines];
+    __shared__ unsigned queue[kCovQueue];
+    __shared__ int q_count;
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    const long long item = item_base + (long long)blockIdx.x;
+    int lo = 0, hi = n_poses - 1;  // the last pose whose first item is <= item (item0[0] = 0 <= item < item0[n_poses])
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (item0[mid] <= item) lo = mid; else hi = mid - 1;
+    }
+    const CovPose P = poses[lo];
+    const int strip = (int)(item - item0[lo]);
+    const int r0 = P.wy0 + strip * P.rows, r1 = min(P.wy1 + 1, r0 + P.rows);  // rows [r0, r1) of the image
+    const int w = P.wx1 - P.wx0 + 1;
+    const float offx = tx + (float)P.x, offy = ty + (float)P.y;  // translate(tmpl, sceneTranslation + translation)
+    const long long r2 = (long long)radius * radius;
+
+    auto stage = [&](int c0) {  // segments [c0, c0 + kCovLines) of the pose into LDS
+        for (int i = tid; i < min(kCovLines, P.n - c0); i += kCovThreads) {
+            const CoverageLine ln = lines[P.line0 + c0 + i];
+            CovSeg s;
+            s.ax = (int)(ln.x1 + offx) - bx; s.ay = (int)(ln.y1 + offy) - by;
+            s.bx = (int)(ln.x2 + offx) - bx; s.by = (int)(ln.y2 + offy) - by;
+            s.x0 = min(s.ax, s.bx) - radius; s.x1 = max(s.ax, s.bx) + radius;
+            s.y0 = min(s.ay, s.by) - radius; s.y1 = max(s.ay, s.by) + radius;
+            const long long dx = (long long)s.bx - s.ax, dy = (long long)s.by - s.ay;
+            s.len2 = dx * dx + dy * dy;
+            s.bin = ln.bin; s.pad = 0;
+            seg[i] = s;
+        }
+    };
+    int resident = 0;  // the chunk in LDS
+    if (tid == 0) q_count = 0;
+    stage(0);
+    __syncthreads();
+
+    // the strip as words of 4 bytes at addresses that are multiples of 4: row y spans the words [wf, wf + nw) of the image's
+    // byte string, nw <= nwm; slot s of the strip is word s % nwm of row r0 + s / nwm
+    const int al = (int)((size_t)labels & 3);
+    const int N = width * height;  // (<= 2^24)
+    const int nwm = (w + 2) / 4 + 1;
+    const int slots = (r1 - r0) * nwm;
+    const int passes = (slots + kCovThreads - 1) / kCovThreads;
+    int edges = 0, explained = 0;  // of this wave: wave-uniform
+    for (int pass = 0; pass < passes; ++pass) {
+        const int s = pass * kCovThreads + tid;
+        unsigned word = 0xffffffffu;
+        int valid = 0, y = 0, f0 = 0;
+        if (s < slots) {
+            y = r0 + s / nwm;
+            const int fs = y * width + P.wx0, fe = fs + w - 1;  // the row's bytes of the window
+            f0 = ((((fs + al) >> 2) + s % nwm) << 2) - al;      // this word's first byte
+            for (int j = 0; j < 4; ++j) valid |= (f0 + j >= fs && f0 + j <= fe) ? 1 << j : 0;
+            if (valid) {
+                if (f0 >= 0 && f0 + 3 < N) {
+                    word = *reinterpret_cast<const unsigned*>(labels + f0);
+                } else {  // the first or last word of the image: only the bytes that exist
+                    word = 0;
+                    for (int j = 0; j < 4; ++j) word |= (unsigned)((valid >> j) & 1 ? labels[f0 + j] : 255) << (8 * j);
+                }
+            }
+        }
+        // compaction: per byte position a ballot; the wave takes its space in the queue with one LDS atomic
+        unsigned long long bal[4];
+        int tot = 0;
+        for (int j = 0; j < 4; ++j) {
+            bal[j] = __ballot(((valid >> j) & 1) && (int)((word >> (8 * j)) & 255u) < m);
+            tot += __popcll(bal[j]);
+        }
+        edges += tot;
+        if (tot) {  // wave-uniform
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&q_count, tot);
+            base = __builtin_amdgcn_readfirstlane(base);
+            const unsigned long long below = (1ull << lane) - 1ull;
+            for (int j = 0; j < 4; ++j) {
+                if ((bal[j] >> lane) & 1ull) {
+                    const int x = f0 + j - y * width;
+                    queue[base + __popcll(bal[j] & below)] = (unsigned)x | ((unsigned)y << 12) | (((word >> (8 * j)) & 255u) << 24);
+                }
+                base += __popcll(bal[j]);
+            }
+        }
+        __syncthreads();
+        const int cnt = q_count;
+        __syncthreads();  // (everyone has read the count before anyone changes it)
+        const bool last = pass == passes - 1;
+        const int rounds = last ? (cnt + kCovThreads - 1) / kCovThreads : cnt / kCovThreads;
+        for (int r = 0; r < rounds; ++r) {
+            const int e = r * kCovThreads + tid;
+            const bool have = e < cnt;
+            const unsigned q = have ? queue[e] : 0u;
+            const int px = (int)(q & 4095u), py = (int)((q >> 12) & 4095u), lab = (int)(q >> 24);
+            bool hit = false;
+            for (int c0 = 0; c0 < P.n; c0 += kCovLines) {
+                if (c0 != resident) {  // (templates of more than one chunk only)
+                    __syncthreads();
+                    stage(c0);
+                    __syncthreads();
+                    resident = c0;
+                }
+                const int nc = min(kCovLines, P.n - c0);
+                for (int i = 0; i < nc; ++i) {
+                    const CovSeg sg = seg[i];  // wave-uniform index: a broadcast
+                    int d = lab - sg.bin;
+                    d = d < 0 ? -d : d;
+                    d = min(d, m - d);
+                    if (have && !hit && d <= tol && px >= sg.x0 && px <= sg.x1 && py >= sg.y0 && py <= sg.y1) hit = near_segment(sg, px, py, r2);
+                }
+            }
+            explained += __popcll(__ballot(hit));
+            if (hit && residual) residual[py * width + px] = 255;
+        }
+        if (!last && rounds > 0) {  // the rest moves to the queue's front
+            const int rest = cnt - rounds * kCovThreads;
+            const unsigned v = tid < rest ? queue[rounds * kCovThreads + tid] : 0u;
+            __syncthreads();
+            if (tid < rest) queue[tid] = v;
+            if (tid == 0) q_count = rest;
+            __syncthreads();
+        }
+    }
+    if (lane == 0) {
+        if (edges) atomicAdd(&counts[2 * lo], edges);
+        if (explained) atomicAdd(&counts[2 * lo + 1], explained);
+    }
+}
+
+size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+// The arguments are checked (fdcm_capi.cpp).  One prepare_pairs for the distinct pairs of the list (n <= 2^20), one upload of
+// lines, poses and item offsets (and a host caller's labels), the counters zeroed and the residual copied on the stream, then
+// the launches.  The buffers are the handle's own (coverage, coverage_stage), not the exhaustive calls' shared workspace.
+void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                        const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                        const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual) {
+    const size_t npix = (size_t)width * (size_t)height;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    FDCM_HIP(hipSetDevice(fm->device));
+    ensure_stream(fm);
+    hipStream_t st = fm->stream;
+    // no poses, an empty set or an empty map: nothing is explained, the residual is the labels, the counts stay unwritten
+    const bool nothing = n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0;
+    std::vector<CovPose> tab;
+    std::vector<long long> item0;
+    std::vector<int64_t> pose_of;  // per entry of tab: its pose
+    CoveragePairs W;
+    if (!nothing) {
+        coverage_pairs(fm, t, rot, poses, n, params.margin, W);
+        const int nr = rot ? rot->n : 1;
+        item0.push_back(0);
+        for (int64_t q = 0; q < n; ++q) {
+            const int32_t* p = poses + 4 * q;
+            const size_t u = W.find((int64_t)p[0] * nr + p[1]);
+            const int32_t* a = &W.adm[5 * u];
+            const bool adm = a[0] && p[2] >= a[1] && p[2] <= a[2] && p[3] >= a[3] && p[3] <= a[4];
+            counts[2 * q] = counts[2 * q + 1] = adm ? 0 : -1;
+            if (!adm) continue;
+            const int32_t* f = &W.foot[4 * u];  // (|f| <= 2^25, |p| < 2^24)
+            const int x0 = std::max(0, f[0] + p[2]), y0 = std::max(0, f[1] + p[3]);
+            const int x1 = std::min(width - 1, f[2] + p[2]), y1 = std::min(height - 1, f[3] + p[3]);
+            if (x0 > x1 || y0 > y1) continue;  // an empty window: (0, 0)
+            const int rows = std::max(1, kCovStripPixels / (x1 - x0 + 1));
+            tab.push_back(CovPose{W.line0[u], W.nl[u], p[2], p[3], x0, y0, x1, y1, rows, {0, 0, 0}});
+            pose_of.push_back(q);
+            item0.push_back(item0.back() + (y1 - y0 + rows) / rows);
+        }
+    }
+    if (tab.empty()) {  // no window holds a pixel: the residual is a copy
+        if (residual && on_device) {
+            FDCM_HIP(hipMemcpyAsync(residual, labels, npix, hipMemcpyDeviceToDevice, st));
+            FDCM_HIP(hipStreamSynchronize(st));
+        } else if (residual) {
+            std::memcpy(residual, labels, npix);
+        }
+        return;
+    }
+    // device: lines | poses | item offsets | counters | labels (host callers) | residual (host callers)
+    const size_t o_tab = al256(W.lines.size() * sizeof(CoverageLine)), o_item = o_tab + al256(tab.size() * sizeof(CovPose)),
+                 o_cnt = o_item + al256(item0.size() * sizeof(long long)), o_lab = o_cnt + al256(tab.size() * 2 * sizeof(int32_t)),
+                 o_res = o_lab + (on_device ? 0 : al256(npix)), total = o_res + (on_device || !residual ? 0 : al256(npix));
+    fm->coverage.reserve(total);
+    fm->coverage_stage.reserve(o_cnt);
+    char* d = (char*)fm->coverage.p;
+    char* h = (char*)fm->coverage_stage.p;
+    const uint8_t* d_labels = labels;
+    uint8_t* d_res = residual;
+    if (!on_device) {
+        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
+        d_labels = (const uint8_t*)(d + o_lab);
+        d_res = residual ? (uint8_t*)(d + o_res) : nullptr;
+    }
+    std::memcpy(h, W.lines.data(), W.lines.size() * sizeof(CoverageLine));
+    std::memcpy(h + o_tab, tab.data(), tab.size() * sizeof(CovPose));
+    std::memcpy(h + o_item, item0.data(), item0.size() * sizeof(long long));
+    FDCM_HIP(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, st));
+    FDCM_HIP(hipMemsetAsync(d + o_cnt, 0, tab.size() * 2 * sizeof(int32_t), st));
+    if (d_res) FDCM_HIP(hipMemcpyAsync(d_res, d_labels, npix, hipMemcpyDeviceToDevice, st));
+    const long long items = item0.back();
+    for (long long base = 0; base < items; base += kCovMaxGrid) {
+        const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
+        hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by,
+                           (int)params.radius, (int)params.bin_tolerance, (const CoverageLine*)d, (const CovPose*)(d + o_tab),
+                           (const long long*)(d + o_item), (int)tab.size(), base, (int*)(d + o_cnt), d_res);
+        FDCM_HIP(hipGetLastError());
+    }
+    int32_t* h_cnt = (int32_t*)h;  // (the staging is free again: this copy is behind the upload on the stream)
+    FDCM_HIP(hipMemcpyAsync(h_cnt, d + o_cnt, tab.size() * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (!on_device && residual) FDCM_HIP(hipMemcpyAsync(residual, d_res, npix, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    for (size_t i = 0; i < tab.size(); ++i) {
+        counts[2 * pose_of[i]] = h_cnt[2 * i];
+        counts[2 * pose_of[i] + 1] = h_cnt[2 * i + 1];
+    }
+}
+
+}  // namespace fdcm

@@ -3278,4 +3278,34 @@ static void matched_fractions_rounds(fdcm_featuremap* fm, const fdcm_templates* 
     }
 }
 
+// Scene coverage (include/fdcm.h, "Scene coverage"; fdcm_coverage.hip): prepare_pairs of the distinct pairs a checked pose list
+// names, as run_line_costs prepares them, with their footprints at `margin`.  The lines come in the 64-bit form, whose `se` is
+// the bin itself.  Host only.
+void coverage_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                    int margin, CoveragePairs& out) {
+    const int nr = rot ? rot->n : 1;
+    Pairs W;
+    W.foot_margin = margin;
+    for (int64_t q = 0; q < n; ++q) W.key.push_back((int64_t)poses[4 * q] * nr + poses[4 * q + 1]);
+    std::sort(W.key.begin(), W.key.end());
+    W.key.erase(std::unique(W.key.begin(), W.key.end()), W.key.end());
+    prepare_pairs(fm, t, rot, true, W);
+    const size_t np = W.key.size();
+    out.key = W.key;
+    out.line0 = W.line0;
+    out.nl = W.nl;
+    out.lines.resize(W.lines.size());
+    for (size_t i = 0; i < W.lines.size(); ++i) out.lines[i] = CoverageLine{W.lines[i].x1, W.lines[i].y1, W.lines[i].x2, W.lines[i].y2, W.lines[i].se};
+    out.adm.resize(np * 5);
+    out.foot.resize(np * 4);
+    for (size_t u = 0; u < np; ++u) {
+        const Box& b = W.box[u];
+        const int32_t a[5] = {b.any ? 1 : 0, b.x0, b.x1, b.y0, b.y1};
+        std::copy_n(a, 5, out.adm.begin() + 5 * u);
+        const Foot& f = W.foot[u];
+        const int32_t g[4] = {f.x0, f.y0, f.x1, f.y1};
+        std::copy_n(g, 4, out.foot.begin() + 4 * u);
+    }
+}
+
 }  // namespace fdcm

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -284,6 +285,8 @@ struct fdcm_featuremap {
     fdcm::BuildRecord built;
     int* steal_counter() const { return sweep.steals_off ? (int*)((char*)build.stack.p + sweep.steals_off) : nullptr; }
     fdcm::SearchBuffers search;
+    fdcm::DevBuf coverage;            // fdcm_scene_coverage: lines, poses, item offsets, counters, and a host caller's labels and residual
+    fdcm::PinnedBuf coverage_stage;   // its upload and the counters' download
     std::mutex seam_mutex;  // evaluate / minmax_translation (called from pool threads on one feature map, batchoptimize.cpp:102-110) and
                             // the exhaustive search share search.eval and the stream: they take turns
     int64_t last_n_out = 0; // matches of the last host-output search, still in search.out
@@ -452,6 +455,26 @@ void run_search_exhaustive_detect_windows_objects(fdcm_featuremap* fm, const fdc
 // poses: n x (tmpl, a, x, y), checked; *costs is malloc'ed; offsets: n + 1
 void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                     float** costs, int64_t* offsets);
+// Scene coverage (include/fdcm.h, "Scene coverage").  What prepare_pairs yields for the distinct pairs of a pose list, in the
+// plain form fdcm_coverage.hip takes: pair u = find(tmpl * n_rot + a) has the lines [line0[u], line0[u] + nl[u]) -- the (rotated)
+// end points and the bin k_line_costs reads --, its admissible translations adm[5 u ..] = any, x0, x1, y0, y1 and its footprint
+// foot[4 u ..] = x0, y0, x1, y1 at the call's margin.
+struct CoverageLine { float x1, y1, x2, y2; int32_t bin; };
+struct CoveragePairs {
+    std::vector<int64_t> key;  // ascending
+    std::vector<CoverageLine> lines;
+    std::vector<int> line0, nl;
+    std::vector<int32_t> adm, foot;
+    size_t find(int64_t k) const { return (size_t)(std::lower_bound(key.begin(), key.end(), k) - key.begin()); }
+};
+// implemented in fdcm_exhaustive.hip (host only; n > 0 checked poses)
+void coverage_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                    int margin, CoveragePairs& out);
+// implemented in fdcm_coverage.hip: the arguments are checked (fdcm_capi.cpp), the frame (bx, by) included; counts: 2 n int32 on
+// the host; residual: width * height bytes where the labels are (host, or the handle's device), or null
+void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                        const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                        const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

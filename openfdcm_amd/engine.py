@@ -670,6 +670,36 @@ class DeviceFeatureMap:
         finally:
             capi.lib().fdcm_lines_free(out)
 
+    def scene_coverage(self, labels, templates, poses, cs=None, pivots=None, radius=2, bin_tolerance=1, margin=None, residual=False):
+        """Scene coverage (include/fdcm.h, "Scene coverage"): per pose (tmpl, a, x, y), as line_costs takes them, the number of
+        edge pixels of `labels` in the pose's window (its footprint at `margin`, None: radius) and how many of them the posed
+        template explains (within `radius` pixels of one of its segments whose slice is within bin_tolerance of the pixel's).
+        (-1, -1) for a pose that is not admissible.  `labels`: 2-D uint8, a numpy array or a contiguous CUDA torch tensor, the
+        image this map was built from.  Returns counts, an (n, 2) int32 array, or with residual (counts, residual): the labels
+        with 255 at every pixel an admissible pose of the list explains, a tensor on the same device for a tensor."""
+        if hasattr(labels, "data_ptr") and not isinstance(labels, np.ndarray) and labels.dim() == 2 and not labels.is_contiguous():
+            raise ValueError("labels on the device must be contiguous")
+        p, w, h, _, dev, keep = _pixels(labels, "labels")
+        if not dev and keep.size and keep.strides[0] != w:
+            keep = np.ascontiguousarray(keep)
+            p = C.c_void_p(keep.ctypes.data)
+        poses = as_poses(poses)
+        rot, keep_rot = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        par = capi.CoverageParams(int(radius), int(bin_tolerance), int(radius if margin is None else margin))
+        counts = np.zeros((poses.shape[0], 2), dtype=np.int32)
+        res, q = None, None
+        if residual and dev:
+            import torch
+            res = torch.empty((h, w), dtype=torch.uint8, device=keep.device)
+            q = C.c_void_p(res.data_ptr())
+        elif residual:
+            res = np.empty((h, w), dtype=np.uint8)
+            q = C.c_void_p(res.ctypes.data)
+        capi.check(capi.lib().fdcm_scene_coverage(self._h, p, w, h, dev, templates._h, C.byref(rot) if rot is not None else None,
+                                                  poses.ctypes.data_as(C.POINTER(C.c_int32)), poses.shape[0], C.byref(par),
+                                                  counts.ctypes.data_as(C.POINTER(C.c_int32)) if counts.size else None, q))
+        return (counts, res) if residual else counts
+
     def rotation_score_map(self, templates, grid, cs, pivots=None):
         """(T, n, ny, nx) float32: the score of every rotated template at every grid point, NaN where not admissible."""
         rot, keep = _rotations(cs, pivots, templates.count)
