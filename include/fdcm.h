@@ -1034,6 +1034,69 @@ int fdcm_scene_coverage(const fdcm_featuremap* fm, const uint8_t* labels, int64_
                         int32_t* counts_out /* n x 2: edges, explained (host) */,
                         uint8_t* residual_out /* width * height, or NULL; device memory when on_device = 1 */);
 
+/* ---- Scene selection: greedy explain-away over a pose list (not in the reference).  Every detector resolves conflicts
+ *      between hypotheses by the template's geometry: radius, box IoU, hull overlap.  For parts that interlock or lie on each
+ *      other that is the wrong question: two poses conflict when they claim the same scene edges, not when their boxes
+ *      overlap.  This call is the greedy rule of fdcm_search_exhaustive_detect_nms with "footprints overlap" replaced by
+ *      "claims the same edge pixels": it takes a pose list in priority order, accepts a pose when enough of what it explains
+ *      is not yet claimed by the poses accepted before it, and returns the accepted poses and the residual.  All arithmetic is
+ *      integer; the result is a function of the inputs alone, whatever order the GPU visits pixels or poses in.  The rule in
+ *      plain Python: tests/select_ref.py, on tests/coverage_ref.py.
+ *
+ *      Everything not restated is Scene coverage's, unchanged: the inputs and the frame check, segments, bins and windows at
+ *      `margin`, "explained" (exact in int64), admissibility, the poses (tmpl, a, x, y) with rot == NULL meaning the lines as
+ *      they are.
+ *      Per pose q: E_q is the set of edge pixels in its window that it explains; edges_q and explained_q = |E_q| are the two
+ *      counts fdcm_scene_coverage returns for it.
+ *      Order.  The list order is the priority: pose 0 first.  Detection records ascend by key, so the poses of a detection list
+ *      are best first.
+ *      Candidates S_0: the admissible poses with explained_q >= min_pixels and
+ *      1000 explained_q >= min_coverage_permille * edges_q (int64).
+ *      Rule.  C, the set of claimed pixels, is empty at the start.  For q = 0, 1, .., n - 1, stopping once max_selected poses
+ *      are accepted: skip q when it is not in S_0; new_q = |E_q \ C|; q is accepted when new_q >= min_pixels and
+ *      1000 new_q >= min_new_permille * explained_q (int64); on acceptance C = C u E_q.
+ *      Output.  *n_out = k, the number accepted; selected_out[0 .. k) their indices into the list, ascending; counts_out
+ *      k x 3 values (edges, explained, new), new as at acceptance; entries from k on are not written.  residual_out
+ *      (optional): the labels with 255 at every pixel of the final C.  The caller supplies max_selected entries of
+ *      selected_out and 3 max_selected of counts_out.
+ *      Identities: the residual is fdcm_scene_coverage's residual of the list poses[selected], and the first two columns of
+ *      counts_out are that call's counts; the new column sums to the number of bytes in which the residual differs from the
+ *      labels, and the first record has new == explained; the result for max_selected = k is the first k entries of the
+ *      result for any larger value; a duplicate of an accepted pose is never accepted (new = 0 < min_pixels); with
+ *      min_new_permille = 1000 the accepted poses' explained sets are pairwise disjoint; with min_coverage_permille =
+ *      min_new_permille = 0 and min_pixels = 1 a pose is accepted exactly when it explains a pixel nobody before it claimed,
+ *      and the residual is fdcm_scene_coverage's of the whole list; one fdcm_scene_coverage call per candidate on the
+ *      running residual, after one on the labels for the static test, selects the same poses (explained on the running
+ *      residual is new).
+ *      Rounds.  edges_q and explained_q are fixed and new_q only falls as C grows, so a candidate that fails its test against
+ *      any subset of the final C before its turn also fails at its turn.  The device counts everything once; then, per
+ *      accepted pose d, it claims E_d, recounts only the surviving later candidates whose window meets d's window, drops
+ *      those that now fail, and accepts the first survivor next.  A round is three launches; rounds are queued 64 at a time
+ *      between host synchronisations, and the call stops at the first batch that ends with no survivor.
+ *      Measured on one MI355X (tools/select_bench.py, profiles/select_bench_config2p.json; a 1024 x 1024 frame, 100 templates
+ *      of 32 lines, radius 2, bin_tolerance 1, min_new_permille 500, labels and residual on the device, median of 5 calls):
+ *      1024 candidates, 44 accepted: 3.52 ms, against 76.9 ms for the composition available before, one fdcm_scene_coverage
+ *      call per candidate on the running residual; 64 candidates, 7 accepted: 0.71 ms against 5.10 ms.  Not measured: lists
+ *      of more than 1024 candidates, calls that accept more than 64 poses, poses with rotations, hardware counters.
+ *      FDCM_EINVAL, before any GPU work: everything fdcm_scene_coverage rejects, with its messages (counts_out aside); sel
+ *      NULL, min_coverage_permille or min_new_permille outside 0 .. 1000, min_pixels outside 1 .. 2^24, max_selected outside
+ *      1 .. 4096; selected_out, counts_out or n_out NULL.  n = 0, an empty feature map or an empty template set give
+ *      *n_out = 0, a residual that is a copy, and FDCM_OK.  The call blocks.  on_device is fdcm_scene_coverage's.  The buffers
+ *      are the handle's coverage buffers, not the workspace the exhaustive calls share. ---- */
+typedef struct fdcm_select_params {
+    int32_t min_coverage_permille;  /* 0 .. 1000: the static test, explained / edges */
+    int32_t min_new_permille;       /* 0 .. 1000: at the pose's turn, new / explained */
+    int32_t min_pixels;             /* 1 .. 2^24: explained and new at least this */
+    int32_t max_selected;           /* 1 .. 4096 */
+} fdcm_select_params;               /* 16 bytes */
+int fdcm_scene_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device,
+                      const fdcm_templates* templates, const fdcm_rotations* rot /* or NULL */,
+                      const int32_t* poses /* n x 4: tmpl, a, x, y, in priority order */, int64_t n,
+                      const fdcm_coverage_params* params, const fdcm_select_params* sel,
+                      int32_t* selected_out /* max_selected (host) */,
+                      int32_t* counts_out /* max_selected x 3: edges, explained, new (host) */, int64_t* n_out,
+                      uint8_t* residual_out /* width * height, or NULL; device memory when on_device = 1 */);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

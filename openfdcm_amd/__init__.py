@@ -1259,4 +1259,27 @@ def scene_coverage(featuremap, labels, templates, poses, angles=None, pivot="cen
                              residual=return_residual)
 
 
+def scene_select(featuremap, labels, templates, poses, angles=None, pivot="center", radius=2, bin_tolerance=1, margin=None,
+                 min_coverage=0.0, min_new=0.5, min_pixels=1, max_selected=1024, return_residual=False):
+    """Greedy explain-away over a pose list, on the device: which of the poses, taken in list order (record_poses of a
+    detection list is best first), account for scene edges nobody before them has claimed.  Two poses conflict when they
+    claim the same edge pixels, not when their boxes overlap, so parts that interlock or lie in each other's notches are
+    both kept while shifted copies of an accepted pose are not.  labels, templates, poses, angles, pivot, radius,
+    bin_tolerance and margin are scene_coverage's.  A pose is a candidate when it is admissible, explains at least
+    min_pixels edge pixels and at least the share min_coverage of the edge pixels in its window; a candidate is accepted
+    when at least min_pixels and the share min_new of the pixels it explains are unclaimed at its turn, and then claims what
+    it explains; at most max_selected (1 .. 4096) are accepted.  Shares are taken in permille, int(round(1000 * v)).
+    Returns (selected, counts): the (k,) int32 indices into poses, ascending, and (k, 3) int32 rows (edges, explained, new);
+    with return_residual also the labels with 255 at every claimed pixel (a tensor on the same device for a tensor), which
+    is scene_coverage's residual of poses[selected]."""
+    fm = _device_map(featuremap)
+    tset = _template_cache.get(templates)
+    cs = pv = None
+    if angles is not None:
+        cs, pv = _angles(angles), _pivots(templates, pivot, tset.count)
+    return fm.scene_select(labels, tset, poses, cs, pv, radius=radius, bin_tolerance=bin_tolerance, margin=margin,
+                           min_coverage=min_coverage, min_new=min_new, min_pixels=min_pixels, max_selected=max_selected,
+                           residual=return_residual)
+
+
 from .lineio import read, write  # noqa: E402  (.lines/.scene/.tmpl files, serialization.h)

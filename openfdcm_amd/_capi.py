@@ -90,6 +90,16 @@ class CoverageParams(C.Structure):
 
 assert C.sizeof(CoverageParams) == 12
 
+
+class SelectParams(C.Structure):
+    """fdcm_select_params: the static test's share (explained / edges), the share of a pose's explained pixels that must be
+    unclaimed at its turn, both in permille, the least number of pixels for either, and the most poses to accept."""
+    _fields_ = [("min_coverage_permille", C.c_int32), ("min_new_permille", C.c_int32), ("min_pixels", C.c_int32),
+                ("max_selected", C.c_int32)]
+
+
+assert C.sizeof(SelectParams) == 16
+
 # every symbol include/fdcm.h declares: (name, restype, argtypes)
 _fp, _i64p, _vp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_void_p
 SYMBOLS = [
@@ -236,6 +246,9 @@ SYMBOLS = [
                                   _i64p]),
     ("fdcm_scene_coverage", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64,
                                       C.POINTER(CoverageParams), C.POINTER(C.c_int32), _vp]),
+    ("fdcm_scene_select", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, C.POINTER(Rotations), C.POINTER(C.c_int32), C.c_int64,
+                                    C.POINTER(CoverageParams), C.POINTER(SelectParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i64p,
+                                    _vp]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),
     ("fdcm_lines_free", None, [C.POINTER(C.c_float)]),

@@ -1310,44 +1310,80 @@ int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, 
 
 // Scene coverage: include/fdcm.h, "Scene coverage".  The line costs' checks, then the call's own; everything that needs no handle
 // first, and nothing on the device.
+// The checks fdcm_scene_coverage and fdcm_scene_select share, in the section's order: the pose list, the parameters and the
+// image (front), then, after the call's own output pointers, the residual, the handles and the frame (back).
+static void check_coverage_front(const uint8_t* labels, int64_t width, int64_t height, const fdcm_rotations* rot, const int32_t* poses,
+                                 int64_t n, const fdcm_coverage_params* params) {
+    require(n >= 0, "n is negative");
+    require(n == 0 || poses, "poses is null");
+    if (rot) check_rotations(rot);  // null: the lines as they are, a table of one rotation
+    const int32_t n_rot = rot ? rot->n : 1, lim = 1 << 24;
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t* p = poses + 4 * q;
+        require(p[0] >= 0, "poses: tmpl is outside the template set");
+        require(p[1] >= 0 && p[1] < n_rot, rot ? "poses: a must be in [0, n - 1]" : "poses: a must be 0 without rotations");
+        require(p[2] > -lim && p[2] < lim && p[3] > -lim && p[3] < lim, "poses: every translation must satisfy |t| < 2^24");
+    }
+    require(n <= ((int64_t)1 << 20), "n must be at most 2^20");
+    require(params != nullptr, "params is null");
+    require(params->radius >= 0 && params->radius <= 32, "radius must be in [0, 32]");
+    require(params->bin_tolerance >= 0, "bin_tolerance must be in [0, m / 2]");
+    require(params->margin >= 0 && params->margin <= 4096, "margin must be in [0, 4096]");
+    require(labels != nullptr, "labels is null");
+    require(width >= 1 && width <= 4096 && height >= 1 && height <= 4096, "width and height must be in [1, 4096]");
+}
+
+static void check_coverage_back(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height,
+                                const fdcm_templates* templates, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                                const fdcm_coverage_params* params, const uint8_t* residual_out, float* bx, float* by) {
+    if (residual_out)
+        require(residual_out + width * height <= labels || labels + width * height <= residual_out, "residual_out must not overlap labels");
+    require(fm && templates, "null featuremap/templates");
+    require(fm->device == templates->device, "featuremap and templates live on different devices");
+    if (rot) check_pivots(templates, rot);
+    for (int64_t q = 0; q < n && templates->T > 0; ++q)
+        require(poses[4 * q] < templates->T, "poses: tmpl is outside the template set");
+    *bx = *by = 0.f;
+    if (fm->W > 0 && fm->H > 0 && fm->m > 0) {  // (an empty map has no frame and no slices: nothing is explained on it)
+        require(params->bin_tolerance <= fm->m / 2, "bin_tolerance must be in [0, m / 2]");
+        *bx = fm->tx; *by = fm->ty;  // whole pixels below 2^24 are exact floats
+        require(*bx >= 0.f && *by >= 0.f && *bx < 16777216.f && *by < 16777216.f && *bx == std::floor(*bx) && *by == std::floor(*by),
+                "the map's scene translation must be whole non-negative pixels (a map built from an image or from labels)");
+        require(width + 2 * (int64_t)*bx == fm->W && height + 2 * (int64_t)*by == fm->H,
+                "the map's size must be (width + 2 bx, height + 2 by) for its scene translation (bx, by)");
+    }
+}
+
+// Scene selection: include/fdcm.h, "Scene selection".  Scene coverage's checks around the call's own.
+int fdcm_scene_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device,
+                      const fdcm_templates* templates, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                      const fdcm_coverage_params* params, const fdcm_select_params* sel, int32_t* selected_out, int32_t* counts_out,
+                      int64_t* n_out, uint8_t* residual_out) {
+    return guarded([&] {
+        check_coverage_front(labels, width, height, rot, poses, n, params);
+        require(sel != nullptr, "sel is null");
+        require(sel->min_coverage_permille >= 0 && sel->min_coverage_permille <= 1000, "min_coverage_permille must be in [0, 1000]");
+        require(sel->min_new_permille >= 0 && sel->min_new_permille <= 1000, "min_new_permille must be in [0, 1000]");
+        require(sel->min_pixels >= 1 && sel->min_pixels <= (1 << 24), "min_pixels must be in [1, 2^24]");
+        require(sel->max_selected >= 1 && sel->max_selected <= 4096, "max_selected must be in [1, 4096]");
+        require(selected_out != nullptr, "selected_out is null");
+        require(counts_out != nullptr, "counts_out is null");
+        require(n_out != nullptr, "n_out is null");
+        float bx, by;
+        check_coverage_back(fm, labels, width, height, templates, rot, poses, n, params, residual_out, &bx, &by);
+        run_scene_select(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, on_device != 0, (int)bx, (int)by, templates, rot,
+                         poses, n, *params, *sel, selected_out, counts_out, n_out, residual_out);
+    });
+}
+
 int fdcm_scene_coverage(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device,
                         const fdcm_templates* templates, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                         const fdcm_coverage_params* params, int32_t* counts_out, uint8_t* residual_out) {
     return guarded([&] {
-        require(n >= 0, "n is negative");
-        require(n == 0 || poses, "poses is null");
-        if (rot) check_rotations(rot);  // null: the lines as they are, a table of one rotation
-        const int32_t n_rot = rot ? rot->n : 1, lim = 1 << 24;
-        for (int64_t q = 0; q < n; ++q) {
-            const int32_t* p = poses + 4 * q;
-            require(p[0] >= 0, "poses: tmpl is outside the template set");
-            require(p[1] >= 0 && p[1] < n_rot, rot ? "poses: a must be in [0, n - 1]" : "poses: a must be 0 without rotations");
-            require(p[2] > -lim && p[2] < lim && p[3] > -lim && p[3] < lim, "poses: every translation must satisfy |t| < 2^24");
-        }
-        require(n <= ((int64_t)1 << 20), "n must be at most 2^20");
-        require(params != nullptr, "params is null");
-        require(params->radius >= 0 && params->radius <= 32, "radius must be in [0, 32]");
-        require(params->bin_tolerance >= 0, "bin_tolerance must be in [0, m / 2]");
-        require(params->margin >= 0 && params->margin <= 4096, "margin must be in [0, 4096]");
-        require(labels != nullptr, "labels is null");
-        require(width >= 1 && width <= 4096 && height >= 1 && height <= 4096, "width and height must be in [1, 4096]");
+        check_coverage_front(labels, width, height, rot, poses, n, params);
         require(n == 0 || counts_out, "counts_out is null");
-        if (residual_out)
-            require(residual_out + width * height <= labels || labels + width * height <= residual_out, "residual_out must not overlap labels");
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
-        if (rot) check_pivots(templates, rot);
-        for (int64_t q = 0; q < n && templates->T > 0; ++q)
-            require(poses[4 * q] < templates->T, "poses: tmpl is outside the template set");
-        float bx = 0.f, by = 0.f;
-        if (fm->W > 0 && fm->H > 0 && fm->m > 0) {  // (an empty map has no frame and no slices: nothing is explained on it)
-            require(params->bin_tolerance <= fm->m / 2, "bin_tolerance must be in [0, m / 2]");
-            bx = fm->tx; by = fm->ty;  // whole pixels below 2^24 are exact floats
-            require(bx >= 0.f && by >= 0.f && bx < 16777216.f && by < 16777216.f && bx == std::floor(bx) && by == std::floor(by),
-                    "the map's scene translation must be whole non-negative pixels (a map built from an image or from labels)");
-            require(width + 2 * (int64_t)bx == fm->W && height + 2 * (int64_t)by == fm->H,
-                    "the map's size must be (width + 2 bx, height + 2 by) for its scene translation (bx, by)");
-        }
+        float bx, by;
+        check_coverage_back(fm, labels, width, height, templates, rot, poses, n, params, residual_out, &bx, &by);
         run_scene_coverage(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, on_device != 0, (int)bx, (int)by, templates, rot,
                            poses, n, *params, counts_out, residual_out);
     });

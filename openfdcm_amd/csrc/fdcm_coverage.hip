@@ -16,6 +16,16 @@
 //                       Counts: wave-uniform popcounts, one atomicAdd per wave and counter at the item's end.  Residual:
 //                       byte stores of 255 into a copy of the labels; the decision reads the labels alone.
 //
+// Scene selection (include/fdcm.h, "Scene selection") runs the same body, coverage_item, in two more modes, with the residual as
+// the claim plane (an edge pixel whose residual byte is 255 is claimed):
+//
+//   k_select_claim      a workgroup per strip of the pose the round accepted, sel[round], read from device memory: stores 255
+//                       at the pixels it explains.
+//   k_select_recount    the grid of k_scene_coverage; a workgroup leaves at once unless its pose comes after the accepted one,
+//                       survives and has a window that meets the accepted one's: counts the explained pixels not claimed.
+//   k_select_decide     a thread per pose: takes the recount, drops the pose when it fails the rule's test, and the smallest
+//                       survivor's index becomes sel[round + 1] (atomicMin, one per wave).  Its first form makes S_0.
+//
 // All arithmetic of the decision is integer; the float adds of step 1 are the cost rule's own (-ffp-contract=off as everywhere).
 #include <algorithm>
 #include <cstring>
@@ -64,23 +74,19 @@ __device__ __forceinline__ bool near_segment(const CovSeg& s, int px, int py, lo
     return cross * cross <= r2 * s.len2;
 }
 
-__global__ void __launch_bounds__(kCovThreads) k_scene_coverage(const uint8_t* __restrict__ labels, int width, int height, int m, float tx,
-                                                                float ty, int bx, int by, int radius, int tol,
-                                                                const CoverageLine* __restrict__ lines, const CovPose* __restrict__ poses,
-                                                                const long long* __restrict__ item0, int n_poses, long long item_base,
-                                                                int* __restrict__ counts, uint8_t* __restrict__ residual) {
+enum { kCovCount = 0, kCovClaim = 1, kCovRecount = 2 };
+
+// Strip `strip` of the pose P: steps 1 to 3 above.  kCovCount: edges and explained, of this wave (wave-uniform), and 255 into
+// the residual, if there is one.  kCovClaim: the stores alone.  kCovRecount: explained counts the pixels the pose explains
+// whose residual byte is not 255, and nothing is stored.  The decision reads the labels alone in every mode.
+template <int kMode>
+__device__ __forceinline__ void coverage_item(const uint8_t* __restrict__ labels, int width, int height, int m, float tx, float ty, int bx,
+                                              int by, int radius, int tol, const CoverageLine* __restrict__ lines, const CovPose& P,
+                                              int strip, uint8_t* __restrict__ residual, int& edges, int& explained) {
     __shared__ CovSeg seg[kCovLines];
     __shared__ unsigned queue[kCovQueue];
     __shared__ int q_count;
     const int tid = (int)threadIdx.x, lane = tid & 63;
-    const long long item = item_base + (long long)blockIdx.x;
-    int lo = 0, hi = n_poses - 1;  // the last pose whose first item is <= item (item0[0] = 0 <= item < item0[n_poses])
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (item0[mid] <= item) lo = mid; else hi = mid - 1;
-    }
-    const CovPose P = poses[lo];
-    const int strip = (int)(item - item0[lo]);
     const int r0 = P.wy0 + strip * P.rows, r1 = min(P.wy1 + 1, r0 + P.rows);  // rows [r0, r1) of the image
     const int w = P.wx1 - P.wx0 + 1;
     const float offx = tx + (float)P.x, offy = ty + (float)P.y;  // translate(tmpl, sceneTranslation + translation)
@@ -112,7 +118,7 @@ __global__ void __launch_bounds__(kCovThreads) k_scene_coverage(const uint8_t* _
     const int nwm = (w + 2) / 4 + 1;
     const int slots = (r1 - r0) * nwm;
     const int passes = (slots + kCovThreads - 1) / kCovThreads;
-    int edges = 0, explained = 0;  // of this wave: wave-uniform
+    edges = explained = 0;
     for (int pass = 0; pass < passes; ++pass) {
         const int s = pass * kCovThreads + tid;
         unsigned word = 0xffffffffu;
@@ -138,7 +144,7 @@ __global__ void __launch_bounds__(kCovThreads) k_scene_coverage(const uint8_t* _
             bal[j] = __ballot(((valid >> j) & 1) && (int)((word >> (8 * j)) & 255u) < m);
             tot += __popcll(bal[j]);
         }
-        edges += tot;
+        if (kMode == kCovCount) edges += tot;
         if (tot) {  // wave-uniform
             int base = 0;
             if (lane == 0) base = atomicAdd(&q_count, tot);
@@ -179,8 +185,9 @@ __global__ void __launch_bounds__(kCovThreads) k_scene_coverage(const uint8_t* _
                     if (have && !hit && d <= tol && px >= sg.x0 && px <= sg.x1 && py >= sg.y0 && py <= sg.y1) hit = near_segment(sg, px, py, r2);
                 }
             }
-            explained += __popcll(__ballot(hit));
-            if (hit && residual) residual[py * width + px] = 255;
+            if (kMode == kCovRecount) hit = hit && residual[py * width + px] != 255;
+            if (kMode != kCovClaim) explained += __popcll(__ballot(hit));
+            if (kMode != kCovRecount && hit && residual) residual[py * width + px] = 255;
         }
         if (!last && rounds > 0) {  // the rest moves to the queue's front
             const int rest = cnt - rounds * kCovThreads;
@@ -191,13 +198,170 @@ __global__ void __launch_bounds__(kCovThreads) k_scene_coverage(const uint8_t* _
             __syncthreads();
         }
     }
-    if (lane == 0) {
+}
+
+// the last pose whose first item is <= item (item0[0] = 0 <= item < item0[n_poses])
+__device__ __forceinline__ int pose_of_item(const long long* __restrict__ item0, int n_poses, long long item) {
+    int lo = 0, hi = n_poses - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (item0[mid] <= item) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(kCovThreads) k_scene_coverage(const uint8_t* __restrict__ labels, int width, int height, int m, float tx,
+                                                                float ty, int bx, int by, int radius, int tol,
+                                                                const CoverageLine* __restrict__ lines, const CovPose* __restrict__ poses,
+                                                                const long long* __restrict__ item0, int n_poses, long long item_base,
+                                                                int* __restrict__ counts, uint8_t* __restrict__ residual) {
+    const long long item = item_base + (long long)blockIdx.x;
+    const int lo = pose_of_item(item0, n_poses, item);
+    const CovPose P = poses[lo];
+    int edges, explained;
+    coverage_item<kCovCount>(labels, width, height, m, tx, ty, bx, by, radius, tol, lines, P, (int)(item - item0[lo]), residual, edges,
+                             explained);
+    if ((threadIdx.x & 63) == 0) {
         if (edges) atomicAdd(&counts[2 * lo], edges);
         if (explained) atomicAdd(&counts[2 * lo + 1], explained);
     }
 }
 
+// ---------------------------------------------------------------------------------------------- scene selection
+// The rule of include/fdcm.h, "Scene selection", in rounds.  Poses are the entries of the pose table, in
+// list order.  sel[r] is the pose round r accepts, kSelNone or more when the list has ended: every kernel of a round reads it
+// and leaves when it has.  alive[i]: i is in S_0 and has not failed its test yet.  cur[i]: |E_i \ C| as last counted, exact for
+// every i alive, because only an accepted pose whose window meets i's can change it.  fresh[i]: the recount's counter, 0
+// between rounds.  Nothing waits on another workgroup: claim, recount and decide are three launches.
+constexpr int kSelNone = 0x7f7f7f7f;  // (what hipMemsetAsync writes with 0x7f: above any pose index)
+
+struct SelArgs {  // k_scene_coverage's arguments, the counters aside
+    const uint8_t* labels;
+    int width, height, m;
+    float tx, ty;
+    int bx, by, radius, tol;
+    const CoverageLine* lines;
+    const CovPose* poses;
+    const long long* item0;
+    int n_poses;
+};
+
+__device__ __forceinline__ bool windows_meet(const CovPose& a, const CovPose& b) {
+    return a.wx0 <= b.wx1 && b.wx0 <= a.wx1 && a.wy0 <= b.wy1 && b.wy0 <= a.wy1;
+}
+
+// Grid: the largest number of strips a pose has.  Stores 255 into the claim plane at every pixel of E_d, d = sel[round], and
+// writes the new count d was accepted with.
+__global__ void __launch_bounds__(kCovThreads) k_select_claim(SelArgs a, const int* __restrict__ sel, int round, const int* __restrict__ cur,
+                                                              int* __restrict__ sel_new, uint8_t* __restrict__ plane) {
+    const int d = sel[round];
+    if (d >= a.n_poses) return;
+    const long long i0 = a.item0[d];
+    if ((long long)blockIdx.x >= a.item0[d + 1] - i0) return;
+    const CovPose P = a.poses[d];
+    if (blockIdx.x == 0 && threadIdx.x == 0) sel_new[round] = cur[d];
+    int edges, explained;
+    coverage_item<kCovClaim>(a.labels, a.width, a.height, a.m, a.tx, a.ty, a.bx, a.by, a.radius, a.tol, a.lines, P, (int)blockIdx.x, plane,
+                             edges, explained);
+}
+
+// Grid: k_scene_coverage's.  fresh[i] += the pixels of the item that pose i explains and nobody has claimed, for the poses i
+// after d = sel[round] that are alive and whose window meets d's.
+__global__ void __launch_bounds__(kCovThreads) k_select_recount(SelArgs a, long long item_base, const int* __restrict__ sel, int round,
+                                                                const uint8_t* __restrict__ alive, int* __restrict__ fresh,
+                                                                uint8_t* __restrict__ plane) {
+    const int d = sel[round];
+    if (d >= a.n_poses) return;
+    const long long item = item_base + (long long)blockIdx.x;
+    if (item < a.item0[d + 1]) return;  // a pose at or before d
+    const int i = pose_of_item(a.item0, a.n_poses, item);
+    if (!alive[i]) return;
+    const CovPose P = a.poses[i], D = a.poses[d];
+    if (!windows_meet(P, D)) return;
+    int edges, explained;
+    coverage_item<kCovRecount>(a.labels, a.width, a.height, a.m, a.tx, a.ty, a.bx, a.by, a.radius, a.tol, a.lines, P, (int)(item - a.item0[i]),
+                               plane, edges, explained);
+    if ((threadIdx.x & 63) == 0 && explained) atomicAdd(&fresh[i], explained);
+}
+
+// Grid: a thread per pose.  round < 0: S_0 from the counts (edges, explained), cur = explained; with C empty every pose of S_0
+// passes its test.  round >= 0: the poses the recount visited take their count, leave fresh at 0, and fail or stay.  The
+// smallest pose alive after d goes to *next, which holds kSelNone: one atomicMin per wave.
+__global__ void __launch_bounds__(256) k_select_decide(const CovPose* __restrict__ poses, int n_poses, const int* __restrict__ counts,
+                                                       const int* __restrict__ sel, int round, fdcm_select_params par,
+                                                       uint8_t* __restrict__ alive, int* __restrict__ fresh, int* __restrict__ cur,
+                                                       int* __restrict__ next) {
+    int d = -1;
+    if (round >= 0) {
+        d = sel[round];
+        if (d >= n_poses) return;
+    }
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    bool live = false;
+    if (i < n_poses && i > d) {
+        const long long explained = counts[2 * i + 1];
+        if (round < 0) {
+            live = explained >= par.min_pixels && 1000ll * explained >= (long long)par.min_coverage_permille * counts[2 * i];
+            cur[i] = (int)explained;
+            alive[i] = live;
+        } else if (alive[i]) {
+            live = true;
+            if (windows_meet(poses[i], poses[d])) {
+                const long long c = fresh[i];
+                fresh[i] = 0;
+                cur[i] = (int)c;
+                live = c >= par.min_pixels && 1000ll * c >= (long long)par.min_new_permille * explained;
+                if (!live) alive[i] = 0;
+            }
+        }
+    }
+    const unsigned long long any = __ballot(live);
+    if (any && (threadIdx.x & 63) == 0) atomicMin(next, i + (int)__builtin_ctzll(any));
+}
+
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// What both calls make of a checked pose list: the pairs, one CovPose per admissible pose with a window that holds a pixel, in
+// list order, the items' prefix sums and, per entry, its pose.  adm[q]: pose q is admissible.
+struct CovTable {
+    CoveragePairs W;
+    std::vector<CovPose> tab;
+    std::vector<long long> item0;
+    std::vector<int64_t> pose_of;
+    std::vector<char> adm;
+    void make(const fdcm_featuremap* fm, int width, int height, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses,
+              int64_t n, int margin) {
+        coverage_pairs(fm, t, rot, poses, n, margin, W);
+        const int nr = rot ? rot->n : 1;
+        adm.assign((size_t)n, 0);
+        item0.push_back(0);
+        for (int64_t q = 0; q < n; ++q) {
+            const int32_t* p = poses + 4 * q;
+            const size_t u = W.find((int64_t)p[0] * nr + p[1]);
+            const int32_t* a = &W.adm[5 * u];
+            adm[q] = a[0] && p[2] >= a[1] && p[2] <= a[2] && p[3] >= a[3] && p[3] <= a[4];
+            if (!adm[q]) continue;
+            const int32_t* f = &W.foot[4 * u];  // (|f| <= 2^25, |p| < 2^24)
+            const int x0 = std::max(0, f[0] + p[2]), y0 = std::max(0, f[1] + p[3]);
+            const int x1 = std::min(width - 1, f[2] + p[2]), y1 = std::min(height - 1, f[3] + p[3]);
+            if (x0 > x1 || y0 > y1) continue;  // an empty window: (0, 0)
+            const int rows = std::max(1, kCovStripPixels / (x1 - x0 + 1));
+            tab.push_back(CovPose{W.line0[u], W.nl[u], p[2], p[3], x0, y0, x1, y1, rows, {0, 0, 0}});
+            pose_of.push_back(q);
+            item0.push_back(item0.back() + (y1 - y0 + rows) / rows);
+        }
+    }
+};
+
+// no window holds a pixel: the residual is a copy
+void copy_labels(const uint8_t* labels, size_t npix, bool on_device, uint8_t* residual, hipStream_t st) {
+    if (residual && on_device) {
+        FDCM_HIP(hipMemcpyAsync(residual, labels, npix, hipMemcpyDeviceToDevice, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+    } else if (residual) {
+        std::memcpy(residual, labels, npix);
+    }
+}
 
 }  // namespace
 
@@ -214,40 +378,16 @@ void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, i
     hipStream_t st = fm->stream;
     // no poses, an empty set or an empty map: nothing is explained, the residual is the labels, the counts stay unwritten
     const bool nothing = n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0;
-    std::vector<CovPose> tab;
-    std::vector<long long> item0;
-    std::vector<int64_t> pose_of;  // per entry of tab: its pose
-    CoveragePairs W;
+    CovTable T;
     if (!nothing) {
-        coverage_pairs(fm, t, rot, poses, n, params.margin, W);
-        const int nr = rot ? rot->n : 1;
-        item0.push_back(0);
-        for (int64_t q = 0; q < n; ++q) {
-            const int32_t* p = poses + 4 * q;
-            const size_t u = W.find((int64_t)p[0] * nr + p[1]);
-            const int32_t* a = &W.adm[5 * u];
-            const bool adm = a[0] && p[2] >= a[1] && p[2] <= a[2] && p[3] >= a[3] && p[3] <= a[4];
-            counts[2 * q] = counts[2 * q + 1] = adm ? 0 : -1;
-            if (!adm) continue;
-            const int32_t* f = &W.foot[4 * u];  // (|f| <= 2^25, |p| < 2^24)
-            const int x0 = std::max(0, f[0] + p[2]), y0 = std::max(0, f[1] + p[3]);
-            const int x1 = std::min(width - 1, f[2] + p[2]), y1 = std::min(height - 1, f[3] + p[3]);
-            if (x0 > x1 || y0 > y1) continue;  // an empty window: (0, 0)
-            const int rows = std::max(1, kCovStripPixels / (x1 - x0 + 1));
-            tab.push_back(CovPose{W.line0[u], W.nl[u], p[2], p[3], x0, y0, x1, y1, rows, {0, 0, 0}});
-            pose_of.push_back(q);
-            item0.push_back(item0.back() + (y1 - y0 + rows) / rows);
-        }
+        T.make(fm, width, height, t, rot, poses, n, params.margin);
+        for (int64_t q = 0; q < n; ++q) counts[2 * q] = counts[2 * q + 1] = T.adm[q] ? 0 : -1;
     }
-    if (tab.empty()) {  // no window holds a pixel: the residual is a copy
-        if (residual && on_device) {
-            FDCM_HIP(hipMemcpyAsync(residual, labels, npix, hipMemcpyDeviceToDevice, st));
-            FDCM_HIP(hipStreamSynchronize(st));
-        } else if (residual) {
-            std::memcpy(residual, labels, npix);
-        }
-        return;
-    }
+    const CoveragePairs& W = T.W;
+    const std::vector<CovPose>& tab = T.tab;
+    const std::vector<long long>& item0 = T.item0;
+    const std::vector<int64_t>& pose_of = T.pose_of;  // per entry of tab: its pose
+    if (tab.empty()) return copy_labels(labels, npix, on_device, residual, st);
     // device: lines | poses | item offsets | counters | labels (host callers) | residual (host callers)
     const size_t o_tab = al256(W.lines.size() * sizeof(CoverageLine)), o_item = o_tab + al256(tab.size() * sizeof(CovPose)),
                  o_cnt = o_item + al256(item0.size() * sizeof(long long)), o_lab = o_cnt + al256(tab.size() * 2 * sizeof(int32_t)),
@@ -285,6 +425,111 @@ void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, i
         counts[2 * pose_of[i]] = h_cnt[2 * i];
         counts[2 * pose_of[i] + 1] = h_cnt[2 * i + 1];
     }
+}
+
+// Rounds are queued kSelBatch at a time, as nms_rounds queues its own: after a batch the host reads the pose the next round
+// would accept and stops when there is none, so no round costs a host round trip, and the launches queued behind the list's
+// end leave at their first load.
+constexpr int kSelBatch = 64;
+
+// The arguments are checked (fdcm_capi.cpp).  run_scene_coverage's preparation and buffers; then one k_scene_coverage launch
+// for the counts, k_select_decide's first form for S_0, and per round claim, recount, decide.
+void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                      const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                      const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
+                      int64_t* n_out, uint8_t* residual) {
+    const size_t npix = (size_t)width * (size_t)height;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    FDCM_HIP(hipSetDevice(fm->device));
+    ensure_stream(fm);
+    hipStream_t st = fm->stream;
+    *n_out = 0;
+    CovTable T;
+    if (!(n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0)) T.make(fm, width, height, t, rot, poses, n, params.margin);
+    if (T.tab.empty()) return copy_labels(labels, npix, on_device, residual, st);  // nothing explains a pixel: nothing is accepted
+    const size_t nt = T.tab.size(), ms = (size_t)sel.max_selected;
+    // device: lines | poses | item offsets | counters, sel, sel_new (what comes down) | fresh | cur | alive | labels (host
+    // callers) | claim plane (unless the caller's residual is on the device)
+    const size_t o_tab = al256(T.W.lines.size() * sizeof(CoverageLine)), o_item = o_tab + al256(nt * sizeof(CovPose)),
+                 o_cnt = o_item + al256(T.item0.size() * sizeof(long long)), o_sel = o_cnt + al256(nt * 2 * sizeof(int32_t)),
+                 o_new = o_sel + al256(ms * sizeof(int32_t)), o_fresh = o_new + al256(ms * sizeof(int32_t)),
+                 o_cur = o_fresh + al256(nt * sizeof(int32_t)), o_alive = o_cur + al256(nt * sizeof(int32_t)), o_lab = o_alive + al256(nt),
+                 o_plane = o_lab + (on_device ? 0 : al256(npix)), total = o_plane + (on_device && residual ? 0 : al256(npix));
+    fm->coverage.reserve(total);
+    fm->coverage_stage.reserve(std::max(o_cnt, o_fresh - o_cnt));
+    char* d = (char*)fm->coverage.p;
+    char* h = (char*)fm->coverage_stage.p;
+    const uint8_t* d_labels = labels;
+    if (!on_device) {
+        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
+        d_labels = (const uint8_t*)(d + o_lab);
+    }
+    uint8_t* plane = on_device && residual ? residual : (uint8_t*)(d + o_plane);
+    std::memcpy(h, T.W.lines.data(), T.W.lines.size() * sizeof(CoverageLine));
+    std::memcpy(h + o_tab, T.tab.data(), nt * sizeof(CovPose));
+    std::memcpy(h + o_item, T.item0.data(), T.item0.size() * sizeof(long long));
+    FDCM_HIP(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, st));
+    FDCM_HIP(hipMemsetAsync(d + o_cnt, 0, nt * 2 * sizeof(int32_t), st));
+    FDCM_HIP(hipMemsetAsync(d + o_sel, 0x7f, ms * sizeof(int32_t), st));  // kSelNone
+    FDCM_HIP(hipMemsetAsync(d + o_fresh, 0, nt * sizeof(int32_t), st));
+    FDCM_HIP(hipMemcpyAsync(plane, d_labels, npix, hipMemcpyDeviceToDevice, st));
+    SelArgs a{d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by, (int)params.radius, (int)params.bin_tolerance,
+              (const CoverageLine*)d, (const CovPose*)(d + o_tab), (const long long*)(d + o_item), (int)nt};
+    int* d_cnt = (int*)(d + o_cnt);
+    int* d_sel = (int*)(d + o_sel);
+    int* d_new = (int*)(d + o_new);
+    int* d_fresh = (int*)(d + o_fresh);
+    int* d_cur = (int*)(d + o_cur);
+    uint8_t* d_alive = (uint8_t*)(d + o_alive);
+    const long long items = T.item0.back();
+    long long strips = 1;  // of the pose with most
+    for (size_t i = 0; i < nt; ++i) strips = std::max(strips, T.item0[i + 1] - T.item0[i]);
+    const unsigned pose_wgs = (unsigned)((nt + 255) / 256);
+    for (long long base = 0; base < items; base += kCovMaxGrid) {
+        const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
+        hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, a.labels, a.width, a.height, a.m, a.tx, a.ty, a.bx, a.by,
+                           a.radius, a.tol, a.lines, a.poses, a.item0, a.n_poses, base, d_cnt, (uint8_t*)nullptr);
+        FDCM_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_select_decide, dim3(pose_wgs), dim3(256), 0, st, a.poses, a.n_poses, d_cnt, d_sel, -1, sel, d_alive, d_fresh, d_cur,
+                       d_sel);
+    FDCM_HIP(hipGetLastError());
+    const int rounds = (int)std::min(ms, nt);  // a round accepts a pose of the table or finds the list ended
+    for (int r = 0; r < rounds;) {
+        for (const int r1 = std::min(rounds, r + kSelBatch); r < r1; ++r) {
+            hipLaunchKernelGGL(k_select_claim, dim3((unsigned)strips), dim3(kCovThreads), 0, st, a, d_sel, r, d_cur, d_new, plane);
+            FDCM_HIP(hipGetLastError());
+            if (r + 1 == rounds) continue;  // the last pose the call may accept: nobody asks who is next
+            for (long long base = 0; base < items; base += kCovMaxGrid) {
+                const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
+                hipLaunchKernelGGL(k_select_recount, dim3(grid), dim3(kCovThreads), 0, st, a, base, d_sel, r, d_alive, d_fresh, plane);
+                FDCM_HIP(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_select_decide, dim3(pose_wgs), dim3(256), 0, st, a.poses, a.n_poses, d_cnt, d_sel, r, sel, d_alive, d_fresh,
+                               d_cur, d_sel + r + 1);
+            FDCM_HIP(hipGetLastError());
+        }
+        if (r == rounds) break;
+        int next = kSelNone;  // the pose round r would accept
+        FDCM_HIP(hipMemcpyAsync(&next, d_sel + r, sizeof(int), hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+        if (next >= (int)nt) break;
+    }
+    FDCM_HIP(hipMemcpyAsync(h, d + o_cnt, o_fresh - o_cnt, hipMemcpyDeviceToHost, st));  // (the staging is free again)
+    if (residual && !on_device) FDCM_HIP(hipMemcpyAsync(residual, plane, npix, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    const int32_t* h_cnt = (const int32_t*)h;
+    const int32_t* h_sel = (const int32_t*)(h + (o_sel - o_cnt));
+    const int32_t* h_new = (const int32_t*)(h + (o_new - o_cnt));
+    size_t k = 0;
+    for (; k < ms && h_sel[k] < (int32_t)nt; ++k) {
+        const int32_t i = h_sel[k];
+        selected[k] = (int32_t)T.pose_of[i];
+        counts[3 * k] = h_cnt[2 * i];
+        counts[3 * k + 1] = h_cnt[2 * i + 1];
+        counts[3 * k + 2] = h_new[k];
+    }
+    *n_out = (int64_t)k;
 }
 
 }  // namespace fdcm

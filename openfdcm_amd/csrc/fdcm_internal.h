@@ -285,7 +285,7 @@ struct fdcm_featuremap {
     fdcm::BuildRecord built;
     int* steal_counter() const { return sweep.steals_off ? (int*)((char*)build.stack.p + sweep.steals_off) : nullptr; }
     fdcm::SearchBuffers search;
-    fdcm::DevBuf coverage;            // fdcm_scene_coverage: lines, poses, item offsets, counters, and a host caller's labels and residual
+    fdcm::DevBuf coverage;            // fdcm_scene_coverage, fdcm_scene_select: lines, poses, item offsets, counters, and a host caller's labels and residual
     fdcm::PinnedBuf coverage_stage;   // its upload and the counters' download
     std::mutex seam_mutex;  // evaluate / minmax_translation (called from pool threads on one feature map, batchoptimize.cpp:102-110) and
                             // the exhaustive search share search.eval and the stream: they take turns
@@ -475,6 +475,13 @@ void coverage_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fd
 void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
                         const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                         const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual);
+// Scene selection (include/fdcm.h, "Scene selection"), implemented in fdcm_coverage.hip with run_scene_coverage's preparation
+// and buffers: the arguments are checked; selected: max_selected int32 and counts: 3 max_selected int32 on the host, *n_out the
+// number accepted; residual as above
+void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                      const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                      const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
+                      int64_t* n_out, uint8_t* residual);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

@@ -700,6 +700,45 @@ class DeviceFeatureMap:
                                                   counts.ctypes.data_as(C.POINTER(C.c_int32)) if counts.size else None, q))
         return (counts, res) if residual else counts
 
+    def scene_select(self, labels, templates, poses, cs=None, pivots=None, radius=2, bin_tolerance=1, margin=None, min_coverage=0.0,
+                     min_new=0.5, min_pixels=1, max_selected=1024, residual=False):
+        """Scene selection (include/fdcm.h, "Scene selection"): greedy explain-away over the poses (tmpl, a, x, y), the list
+        order being the priority.  A pose is a candidate when it is admissible, explains at least min_pixels edge pixels of its
+        window and at least the share min_coverage of the window's edge pixels; a candidate is accepted, in order, when at
+        least min_pixels and the share min_new of the pixels it explains are not yet claimed by the poses accepted before it,
+        and then claims its own; at most max_selected are accepted.  The shares are taken in permille, int(round(1000 * v)).
+        labels, templates, cs, pivots, radius, bin_tolerance and margin are scene_coverage's.  Returns (selected, counts): the
+        (k,) int32 indices of the accepted poses, ascending, and (k, 3) int32 rows (edges, explained, new), new as at
+        acceptance; with residual also the labels with 255 at every claimed pixel, a tensor on the same device for a tensor."""
+        if hasattr(labels, "data_ptr") and not isinstance(labels, np.ndarray) and labels.dim() == 2 and not labels.is_contiguous():
+            raise ValueError("labels on the device must be contiguous")
+        p, w, h, _, dev, keep = _pixels(labels, "labels")
+        if not dev and keep.size and keep.strides[0] != w:
+            keep = np.ascontiguousarray(keep)
+            p = C.c_void_p(keep.ctypes.data)
+        poses = as_poses(poses)
+        rot, keep_rot = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        par = capi.CoverageParams(int(radius), int(bin_tolerance), int(radius if margin is None else margin))
+        sel = capi.SelectParams(int(round(1000 * min_coverage)), int(round(1000 * min_new)), int(min_pixels), int(max_selected))
+        room = max(1, min(int(max_selected), 4096))          # (an argument out of range is the library's to refuse)
+        selected = np.zeros(room, dtype=np.int32)
+        counts = np.zeros((room, 3), dtype=np.int32)
+        k = C.c_int64(0)
+        res, q = None, None
+        if residual and dev:
+            import torch
+            res = torch.empty((h, w), dtype=torch.uint8, device=keep.device)
+            q = C.c_void_p(res.data_ptr())
+        elif residual:
+            res = np.empty((h, w), dtype=np.uint8)
+            q = C.c_void_p(res.ctypes.data)
+        capi.check(capi.lib().fdcm_scene_select(self._h, p, w, h, dev, templates._h, C.byref(rot) if rot is not None else None,
+                                                poses.ctypes.data_as(C.POINTER(C.c_int32)), poses.shape[0], C.byref(par), C.byref(sel),
+                                                selected.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k), q))
+        selected, counts = selected[:k.value].copy(), counts[:k.value].copy()
+        return (selected, counts, res) if residual else (selected, counts)
+
     def rotation_score_map(self, templates, grid, cs, pivots=None):
         """(T, n, ny, nx) float32: the score of every rotated template at every grid point, NaN where not admissible."""
         rot, keep = _rotations(cs, pivots, templates.count)
