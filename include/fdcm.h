@@ -1097,6 +1097,85 @@ int fdcm_scene_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_t 
                       int32_t* counts_out /* max_selected x 3: edges, explained, new (host) */, int64_t* n_out,
                       uint8_t* residual_out /* width * height, or NULL; device memory when on_device = 1 */);
 
+/* ---- Match lists: the records of fdcm_search, verified and suppressed on the device.  No counterpart in the reference; these
+ *      definitions are the project's own.  fdcm_search, the frame pipeline, the sharded engine and fdcm_topk return records
+ *      {tmpl_idx, score, transform[6]} whose transform is a free float matrix; every detection call above takes poses
+ *      (tmpl, a, x, y), which only the exhaustive calls produce.  These calls are the detection family's line costs, matched
+ *      fraction, caps, threshold and greedy overlap rule for such records: a caller of fdcm_search gets a record for every
+ *      pair of aligned lines near a true pose, and fdcm_matches_detect reduces the list to one record per part.  The rule in
+ *      numpy: tests/match_ref.py.
+ *
+ *      r is a record, t = r.tmpl_idx - tmpl_index_base, M = r.transform (row-major 2 x 3), T the set's template count.
+ *      Valid record: 0 <= t < T.  Any other record takes part in nothing: its outputs are NaN, its box is empty and it is
+ *      never a candidate, on the host and on the device alike (fdcm_topk's rule, not fdcm_penalize's error).
+ *      Posed lines P(r): each end point (x, y) of template t becomes ((M0 x + M1 y) + M2, (M3 x + M4 y) + M5), every product and
+ *      sum float32 and unfused: the reference's transform (math.h:341-344).  A NaN or an infinity in M flows through.
+ *      Bin of posed line i: closestOrientation(keys, atanf(dy / dx)) of the posed line, as evaluate<Dt3Cpu> classifies a line
+ *      it is given (dt3cpu.cpp:144-148).
+ *      Admissible: fdcm_featuremap_evaluate of P(r) at translation (0, 0) is not NaN: every posed coordinate plus the scene
+ *      translation, summed in float32, lies in (-1, W) x (-1, H).  A NaN coordinate: not admissible.  A valid record whose
+ *      template has no lines is admissible.
+ *      Line cost cost_i(r): the term of evaluate for posed line i at translation (0, 0), uncapped: bit for bit the score
+ *      fdcm_featuremap_evaluate returns for the one-line template {posed line i} at (0, 0).  NaN for every line of a record
+ *      that is not admissible.
+ *      Score s(r): the sum, in Eigen's sum() order, of capped_i = cost_i > cap_i ? cap_i : cost_i with the set's caps (+inf
+ *      without caps); +0 for a template without lines, NaN when r is not admissible.  Without caps s(r) is bit for bit
+ *      fdcm_featuremap_evaluate(P(r), (0, 0)).
+ *      s(r) is not r.score.  The search scores transform(lines, A) at a translation k v along the scene line and then stores A
+ *      with that translation folded into M2 and M5; posing again with the folded matrix rounds differently.  s(r) is usually
+ *      close to r.score but is not its bits, and a record on the map's border can come out not admissible.
+ *      Matched length and fraction: ML, TL and frac of "Detections by matched fraction": w_i = len_i when cost_i <= cap_i, len_i
+ *      the unposed line's length; ML the float32 sum in line order from +0; frac = ML / TL, 1 when TL == 0, NaN when r is not
+ *      admissible.
+ *      Footprint F(r): the footprint's arithmetic ("Detections suppressed by footprint overlap") on the end points of P(r) at
+ *      `margin`: floor(min x) - margin, floor(min y) - margin, floor(max x) + margin, floor(max y) + margin in int64, clamped to
+ *      [-2^25, 2^25].  A template without lines, a NaN end point or an invalid record: the empty box (0, 0, -1, -1).  An
+ *      infinite end point does not empty the box: its floor is far outside the clamp.  The kind of a hull set is ignored, as
+ *      Scene coverage ignores it: the shape is the box.
+ *      Candidates S_0 of fdcm_matches_detect: the records that are valid with a template that has lines, admissible, whose
+ *      q_j = v_j / den(t) is not NaN, has a clear sign bit and is <= max_score, and, when min_matched > 0, have
+ *      ML >= need_t = float32(min_matched * TL_t).  v_j = r.score with rescore = 0 and s(r) with rescore = 1; the denominators
+ *      are fdcm_penalize's (penalty = -1: q = v).  A caller who has penalised already passes -1 and rescore = 0.
+ *      Key, rule, output: key(j) = (bits of q_j << 32) | j, j the record's position in the list.  The greedy rule of
+ *      fdcm_search_exhaustive_detect_nms runs on S_0 with these keys and footprints and stops at max_detections (1 .. 4096).
+ *      *out receives the d_n in order, each {r.tmpl_idx, q, r.transform} (fdcm_matches_free), *n_out their count; optional
+ *      indices_out (the position j of each), boxes_out (4 int32 each) and matched_out (frac), max_detections entries each.
+ *      Identities.  With overlap_permille = 1000, max_score = +inf, min_matched = 0, rescore = 0 and max_detections >= |S_0|, on
+ *      a list whose records are all candidates, the output is fdcm_topk of the same records at the same penalty with k = n,
+ *      byte for byte.  At fixed other parameters the records for any max_score are the leading records with score <= max_score
+ *      of the +inf list.  With overlap_permille = 0 no two returned boxes share a pixel.  A duplicate of a returned record is
+ *      never returned unless overlap_permille = 1000.  For a record with transform {1, 0, x, 0, 1, y}, x and y integers below
+ *      2^24 in magnitude, costs, s and frac are fdcm_line_costs, the k = 1 score of fdcm_search_exhaustive_windows for the job
+ *      (t, 0, 1, x, y, 1, 1) and fdcm_matched_fractions for the pose (t, 0, x, y), bit for bit wherever every x_i + float32(x) is
+ *      exact.  Results are a function of the inputs alone.
+ *      matches: n host records (on_device = 0); n records on the handle's device (on_device = 1), such as a buffer filled by
+ *      fdcm_search_device; or NULL with on_device = 0: the records of the last fdcm_search on fm, as fdcm_topk takes them (n
+ *      is then ignored).
+ *      fdcm_matches_verify: scores_out s(r) and fractions_out frac(r), n floats each; costs_out a regular n x Lmax float32 array,
+ *      Lmax the set's largest line count, NaN at and beyond a template's line count.  Any output may be NULL, not all of them.
+ *      fdcm_matches_footprints: F(r) of n host records, 4 int32 each; host only, no device is touched.
+ *      The device.  One pass, a wave per record and a lane per line, writes every record's score, fraction, box and key
+ *      straight into the arrays the rounds of the overlap rule read; the rounds are those of the detections over pose windows,
+ *      unchanged; a gather kernel writes the result records into pinned memory.  The list never returns to the host between
+ *      them.  Where fdcm_orientation_bins_mode() is 1 the bins are computed on the host and uploaded; device records then cost
+ *      one download.
+ *      FDCM_EINVAL, before any GPU work: n < 0 or n > 2^22; on_device not 0 or 1; matches NULL with n > 0 and on_device = 1;
+ *      max_score NaN or < 0; max_detections outside 1 .. 4096; overlap_permille outside 0 .. 1000; margin outside 0 .. 4096; an
+ *      unknown penalty or a tau that is not finite; min_matched NaN or outside [0, 1]; rescore not 0 or 1; out or n_out NULL
+ *      (verify: every output NULL; footprints: matches or boxes_out NULL with n > 0); NULL handles.  n = 0, an empty feature
+ *      map or an empty template set give FDCM_OK and nothing (*n_out = 0; verify's outputs are not written).  The calls block;
+ *      concurrent callers of one feature map take turns. ---- */
+int fdcm_matches_footprints(const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int32_t tmpl_index_base,
+                            int32_t margin, int32_t* boxes_out /* n x 4 */);
+int fdcm_matches_verify(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n,
+                        int on_device, int32_t tmpl_index_base, float* scores_out /* n, or NULL */,
+                        float* fractions_out /* n, or NULL */, float* costs_out /* n x Lmax, or NULL */);
+int fdcm_matches_detect(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n,
+                        int on_device, int32_t tmpl_index_base, float max_score, int32_t max_detections, int32_t overlap_permille,
+                        int32_t margin, int penalty, float tau, float min_matched, int rescore, fdcm_match** out, int64_t* n_out,
+                        int32_t* indices_out /* max_detections, or NULL */, int32_t* boxes_out /* max_detections x 4, or NULL */,
+                        float* matched_out /* max_detections, or NULL */);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

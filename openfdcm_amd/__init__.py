@@ -1282,4 +1282,44 @@ def scene_select(featuremap, labels, templates, poses, angles=None, pivot="cente
                            residual=return_residual)
 
 
+# ---------------------------------------------------------------- match lists (extension)
+def detect_matches(featuremap, templates, matches, max_score=float("inf"), overlap=0.3, max_detections=1024, penalty=None, margin=0,
+                   line_caps=None, min_matched=0.0, rescore=False, return_indices=False, return_boxes=False, return_matched=False,
+                   device_ptr=None, n=0):
+    """One record per part out of what search() returns: the greedy rule of exhaustive_detect_all by footprint overlap on a
+    match list, on the device.  search() gives a record for every pair of aligned lines near a true pose; each record is
+    posed again with its own transform, its lines are costed (line_caps as in exhaustive_search), and the records that lie
+    inside the map, whose score divided by the penalty's denominator (penalty: None, DefaultPenalty or ExponentialPenalty) is
+    at most max_score and whose matched fraction is at least min_matched go through the rule keyed by (score, position in
+    the list), until they run out or max_detections (1 to 4096) is reached.  The score is the record's own (a caller who has
+    penalised already passes penalty=None) or, with rescore, the sum of the capped line costs of the posed lines, which is
+    close to the search's score but not its bits.  matches: a MatchList or a record array; None for the records of the
+    last search() on this feature map, still on the device; or device_ptr and n for records in device memory.  Returns a
+    MatchList in ascending score, and in a tuple with it, in this order, with return_indices the (k,) int32 positions of the
+    records in the list, with return_boxes the (k, 4) int32 footprints, with return_matched the (k,) float32 fractions."""
+    kind, tau = _penalty_args(penalty)
+    permille = int(round(1000 * float(overlap)))
+    fm, tset = _device_map(featuremap), _template_cache.get(templates, line_caps)
+    res = fm.detect_matches(tset, matches, max_score=max_score, overlap_permille=permille, max_detections=max_detections, penalty=kind,
+                            tau=tau, margin=margin, min_matched=min_matched, rescore=rescore, indices=return_indices, boxes=return_boxes,
+                            matched=return_matched, device_ptr=device_ptr, n=n)
+    return (MatchList(res[0]),) + tuple(res[1:]) if isinstance(res, tuple) else MatchList(res)
+
+
+def verify_matches(featuremap, templates, matches, line_caps=None, device_ptr=None, n=0):
+    """Which lines of a match were found: (scores, fractions, costs) of every record of a match list, the forms of which are
+    detect_matches'.  costs is an (n, Lmax) float32 array, the uncapped cost of every line of the record's template posed by
+    the record's transform, NaN beyond the template's line count; scores the sum of the costs clamped to line_caps, in the
+    scores' order; fractions the matched fraction of matched_fractions.  All NaN for a record whose posed lines leave the
+    map or whose tmpl_idx is outside the list."""
+    fm, tset = _device_map(featuremap), _template_cache.get(templates, line_caps)
+    return fm.verify_matches(tset, matches, device_ptr=device_ptr, n=n)
+
+
+def match_footprints(templates, matches, margin=0):
+    """The (n, 4) int32 footprints x0, y0, x1, y1 of the posed lines of every record of a match list, as detect_matches uses
+    them; (0, 0, -1, -1) for a record whose tmpl_idx is outside the list, a template without lines or a NaN end point."""
+    return _engine.match_footprints(_template_cache.get(templates), matches, margin)
+
+
 from .lineio import read, write  # noqa: E402  (.lines/.scene/.tmpl files, serialization.h)

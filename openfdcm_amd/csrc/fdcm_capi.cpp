@@ -1308,6 +1308,78 @@ int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, 
     });
 }
 
+// Match lists: include/fdcm.h, "Match lists".  Everything that needs no handle is checked first, in the section's order; nothing
+// here touches the device.
+static void check_match_list(const fdcm_match* matches, int64_t n, int on_device) {
+    require(n >= 0, "n is negative");
+    require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
+    require(on_device == 0 || on_device == 1, "on_device must be 0 or 1");
+    require(!(on_device == 1 && n > 0 && !matches), "matches is null");
+}
+
+// matches NULL with on_device = 0: the records of the last fdcm_search on the handle, as fdcm_topk takes them.
+static void last_search_matches(const fdcm_featuremap* fm, const fdcm_match*& matches, int64_t& n, int& on_device) {
+    if (matches || on_device) return;
+    matches = fm->search.out.as<fdcm_match>();
+    n = fm->last_n_out;
+    on_device = 1;
+    require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
+    require(n == 0 || matches, "the handle holds no matches of a search");
+}
+
+int fdcm_matches_footprints(const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int32_t tmpl_index_base,
+                            int32_t margin, int32_t* boxes_out) {
+    return guarded([&] {
+        require(n >= 0, "n is negative");
+        require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
+        require(n == 0 || matches, "matches is null");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(n == 0 || boxes_out, "boxes_out is null");
+        require(templates != nullptr, "templates is null");
+        matches_footprints(templates, matches, n, tmpl_index_base, margin, boxes_out);
+    });
+}
+
+int fdcm_matches_verify(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int on_device,
+                        int32_t tmpl_index_base, float* scores_out, float* fractions_out, float* costs_out) {
+    return guarded([&] {
+        check_match_list(matches, n, on_device);
+        require(scores_out || fractions_out || costs_out, "every output is null");
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        last_search_matches(fm, matches, n, on_device);
+        run_matches(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, nullptr, scores_out,
+                    fractions_out, costs_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+    });
+}
+
+int fdcm_matches_detect(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int on_device,
+                        int32_t tmpl_index_base, float max_score, int32_t max_detections, int32_t overlap_permille, int32_t margin,
+                        int penalty, float tau, float min_matched, int rescore, fdcm_match** out, int64_t* n_out, int32_t* indices_out,
+                        int32_t* boxes_out, float* matched_out) {
+    return guarded([&] {
+        check_match_list(matches, n, on_device);
+        require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
+        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
+        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
+        require(std::isfinite(tau), "tau must be finite");
+        require(min_matched >= 0.f && min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
+        require(rescore == 0 || rescore == 1, "rescore must be 0 or 1");
+        require(out && n_out, "null output");
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        last_search_matches(fm, matches, n, on_device);
+        const MatchesDetect det{max_score == 0.f ? 0.f : max_score, max_detections, overlap_permille, margin, penalty, tau,
+                                min_matched == 0.f ? 0.f : min_matched, rescore};
+        records_call(out, [&] {
+            run_matches(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, &det, nullptr, nullptr,
+                        nullptr, out, n_out, indices_out, boxes_out, matched_out);
+        });
+    });
+}
+
 // Scene coverage: include/fdcm.h, "Scene coverage".  The line costs' checks, then the call's own; everything that needs no handle
 // first, and nothing on the device.
 // The checks fdcm_scene_coverage and fdcm_scene_select share, in the section's order: the pose list, the parameters and the

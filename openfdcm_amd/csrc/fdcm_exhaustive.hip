@@ -32,6 +32,10 @@
 //                                     detections over pose windows: a thread per job turns the job's merged k = 1 list into
 //                                     its entry of the winners' list (normalised key, footprint), for the list forms of
 //                                     k_nms_round; objects (include/fdcm.h, "Objects"): the same pass with a threshold per pair
+//   k_matches_verify<BUF32, CAP>, k_matches_gather
+//                                     match lists (include/fdcm.h, "Match lists"): a wave per record of search() turns it into
+//                                     line costs, a score, a matched fraction, a box and a key for the list form of
+//                                     k_nms_round; the gather writes the result records into pinned memory (at the file's end)
 //   hull_suppresses, hull_stage       hull footprints (include/fdcm.h, "Hull footprints"): the overlap test on shapes, the
 //                                     lattice points of the convex hull of a pair's end points as row spans, for template
 //                                     sets of that kind; sets of kind BOX run the round's box forms
@@ -3306,6 +3310,352 @@ void coverage_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fd
         const int32_t g[4] = {f.x0, f.y0, f.x1, f.y1};
         std::copy_n(g, 4, out.foot.begin() + 4 * u);
     }
+}
+
+// ---- match lists (include/fdcm.h, "Match lists"): the records of the reference's own path, {tmpl_idx, score, transform[6]}
+// with a free float transform, verified and suppressed on the device.
+//   k_matches_verify<BUF32, CAP>   a wave per record, a lane per line of its template in rounds of 64.  The record comes by
+//                                  wave-uniform loads; the lines and lengths are the set's resident d_lines and d_lengths.
+//                                  Pass 1 poses every end point (transform, math.h:341-344: unfused float32), decides
+//                                  admissibility by the seam's rule (k_evaluate at translation (0, 0)) and reduces the box
+//                                  (footprint()'s arithmetic) -- before any read of the volume.  Pass 2, admissible records
+//                                  alone: the bin by atanf_glibc + closest_orientation as k_search (or the host's bins), the
+//                                  uncapped cost by ex_column / ex_read, s in Eigen's order (rows_score's statement of it,
+//                                  with the lines spread over the lanes: line i is lane i % 64, whose class i % 8 is fixed,
+//                                  so the eight accumulators are eight sequential sums over the lanes of a class, round
+//                                  after round), ML in line order (matched_length's rule).  Lane 0 writes the record's
+//                                  score, fraction, q, key and box straight into the list form's arrays.
+//   k_matches_gather               the result keys as 64-byte entries (record with q, box, fraction, position) in pinned memory
+// The rounds between them are nms_rounds' list form, k_nms_round<true, false, false>, unchanged.
+namespace {
+
+struct MatchesArgs {
+    const float* vol;
+    size_t SL;
+    int m, W, H;
+    float tx, ty;
+    const float* keys;  // the map's m orientation keys
+    const float4* tlines;  // the set's resident lines, lengths and offsets
+    const float* tlen;
+    const long long* toff;
+    const float* caps;  // (CAP) per line of the set, the call's upload
+    const float* den;   // per template: the penalty's denominator
+    const float* need;  // per template: float32(min_matched * TL), or null for no gate
+    const float* tl;    // per template: TL
+    const unsigned short* bins;  // [record][Lmax] bins from the host libm, or null
+    const fdcm_match* rec;
+    int n, base, T, Lmax, margin, rescore;
+    float max_score;
+    float* score;  // s(r)
+    float* frac;
+    float* costs;  // [record][Lmax], or null
+    float* q;
+    unsigned long long* keys_out;
+    int4* boxes;
+};
+
+// One side of footprint(): floor(v) + d in int64, clamped (v is not NaN).
+__device__ __forceinline__ int matches_side(float v, int d) {
+    const float f = fminf(fmaxf(floorf(v), -1099511627776.f), 1099511627776.f);
+    const long long lim = 1ll << 25;
+    return (int)min(max((long long)f + d, -lim), lim);
+}
+
+template <bool BUF32, bool CAP>
+__global__ void __launch_bounds__(256) k_matches_verify(const MatchesArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int j = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (j >= a.n) return;  // wave-uniform
+    const fdcm_match R = a.rec[j];
+    const long long t = (long long)R.tmpl_idx - (long long)a.base;
+    float* const crow = a.costs ? a.costs + (size_t)j * (size_t)a.Lmax : nullptr;
+    if (t < 0 || t >= a.T) {  // not a valid record: it takes part in nothing
+        if (crow)
+            for (int i = lane; i < a.Lmax; i += 64) crow[i] = f_nan();
+        if (lane == 0) {
+            a.score[j] = f_nan(); a.frac[j] = f_nan(); a.q[j] = f_nan();
+            a.keys_out[j] = kNoKey;
+            a.boxes[j] = make_int4(0, 0, -1, -1);
+        }
+        return;
+    }
+    const long long l0 = a.toff[t];
+    const int nl = (int)(a.toff[t + 1] - l0);
+    const float M0 = R.transform[0], M1 = R.transform[1], M2 = R.transform[2], M3 = R.transform[3], M4 = R.transform[4],
+                M5 = R.transform[5];
+    const float offx = a.tx + 0.f, offy = a.ty + 0.f;  // sceneTranslation + translation, the translation (0, 0)
+    // ---- pass 1: admissibility and the box
+    bool inside = true, has_nan = false;
+    float mnx = f_inf(), mny = f_inf(), mxx = -f_inf(), mxy = -f_inf();
+    for (int i = lane; i < nl; i += 64) {
+        const float4 p = a.tlines[l0 + i];
+        const float x[2] = {(M0 * p.x + M1 * p.y) + M2, (M0 * p.z + M1 * p.w) + M2};
+        const float y[2] = {(M3 * p.x + M4 * p.y) + M5, (M3 * p.z + M4 * p.w) + M5};
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float px = x[c] + offx, py = y[c] + offy;
+            inside = inside && px > -1.f && px < (float)a.W && py > -1.f && py < (float)a.H;  // false for NaN
+            has_nan = has_nan || f_isnan(x[c]) || f_isnan(y[c]);
+            mnx = std_min(mnx, x[c]); mxx = std_max(mxx, x[c]);
+            mny = std_min(mny, y[c]); mxy = std_max(mxy, y[c]);
+        }
+    }
+    const bool adm = __ballot(!inside) == 0;
+    const bool any_nan = __ballot(has_nan) != 0;
+    mnx = wave_min_f(mnx); mny = wave_min_f(mny); mxx = wave_max_f(mxx); mxy = wave_max_f(mxy);
+    int4 box = make_int4(0, 0, -1, -1);
+    if (nl > 0 && !any_nan)
+        box = make_int4(matches_side(mnx, -a.margin), matches_side(mny, -a.margin), matches_side(mxx, a.margin), matches_side(mxy, a.margin));
+    // ---- pass 2: costs, s in Eigen's order, ML in line order
+    const VolRef V = make_volref(a.vol, a.SL, a.m, BUF32);
+    const unsigned uH = (unsigned)a.H;
+    const int aligned2 = (nl / 8) * 8, aligned = (nl / 4) * 4;
+    float acc = 0.f, res = 0.f, ml = 0.f;
+    for (int r0 = 0; r0 < nl; r0 += 64) {  // wave-uniform
+        const int i = r0 + lane;
+        float cost = f_nan(), cap = f_inf(), len = 0.f;
+        if (i < nl) {
+            if (adm) {
+                const float4 p = a.tlines[l0 + i];
+                const float x1 = (M0 * p.x + M1 * p.y) + M2, y1 = (M3 * p.x + M4 * p.y) + M5;
+                const float x2 = (M0 * p.z + M1 * p.w) + M2, y2 = (M3 * p.z + M4 * p.w) + M5;
+                int bin;
+                if (a.bins) {
+                    bin = (int)a.bins[(size_t)j * (size_t)a.Lmax + i];
+                } else {
+                    const float angle = atanf_glibc((y2 - y1) / (x2 - x1));  // getAngle, math.h:295-299
+                    bin = closest_orientation(a.keys, a.m, angle);           // dt3cpu.cpp:144-148
+                }
+                const int se = BUF32 ? (int)((unsigned)bin * (unsigned)a.SL) : bin;
+                const size_t c1 = ex_column<BUF32>((int)(x1 + offx), se, a.W, uH, a.SL);
+                const size_t c2 = ex_column<BUF32>((int)(x2 + offx), se, a.W, uH, a.SL);
+                cost = line_term<false>(ex_read<BUF32>(V, c1, (int)(y1 + offy), uH), ex_read<BUF32>(V, c2, (int)(y2 + offy), uH), 0.f);
+                if (CAP) cap = a.caps[l0 + i];
+                len = a.tlen[l0 + i];
+            }
+            if (crow) crow[i] = cost;
+        }
+        if (!adm) continue;  // wave-uniform
+        const float capped = CAP && cost > cap ? cap : cost;
+        // the blocks of 8: lane c < 8 of a class sums the lines 8 b + c of this round, b ascending
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int src = (lane & 7) + 8 * k;
+            const float v = __shfl(capped, src);
+            if (r0 + src < aligned2) acc = acc + v;
+        }
+        // ML: the matched lines of this round in line order
+        unsigned long long mm = __ballot(i < nl && cost <= cap);
+        while (mm) {  // wave-uniform
+            const int src = __ffsll((long long)mm) - 1;
+            mm &= mm - 1;
+            ml = ml + __shfl(len, src);
+        }
+        if (r0 + 64 >= nl) {  // the last round holds the trailing packet and the scalar tail
+            float p = __shfl(acc, lane & 3) + __shfl(acc, (lane & 3) + 4);  // p0 += p1
+            if (aligned > aligned2) p = p + __shfl(capped, (aligned2 - r0) + (lane & 3));
+            if (aligned) res = (__shfl(p, 0) + __shfl(p, 2)) + (__shfl(p, 1) + __shfl(p, 3));  // predux
+            for (int idx = aligned; idx < nl; ++idx) res = res + __shfl(capped, idx - r0);
+        }
+    }
+    if (crow)
+        for (int i = nl + lane; i < a.Lmax; i += 64) crow[i] = f_nan();
+    if (lane == 0) {
+        const float s = adm ? res : f_nan();
+        const float qv = (a.rescore ? s : R.score) / a.den[t];
+        bool cand = nl > 0 && adm && !f_isnan(qv) && !f_signbit(qv) && qv <= a.max_score;
+        if (cand && a.need) cand = ml >= a.need[t];
+        a.score[j] = s;
+        a.frac[j] = adm ? matched_fraction(ml, a.tl[t]) : f_nan();
+        a.q[j] = qv;
+        a.keys_out[j] = cand ? ((unsigned long long)__float_as_uint(qv) << 32) | (unsigned)j : kNoKey;
+        a.boxes[j] = box;
+    }
+}
+
+struct MatchOut {  // one result of the detect call
+    fdcm_match rec;  // the record with q for its score
+    int4 box;
+    float frac;
+    int idx;  // its position in the list; -1: the result list ended before this entry
+    int pad[2];
+};
+static_assert(sizeof(MatchOut) == 64, "MatchOut is 64 bytes");
+
+__global__ void __launch_bounds__(256) k_matches_gather(const unsigned long long* __restrict__ best, int max_det,
+                                                        const fdcm_match* __restrict__ rec, const float* __restrict__ q,
+                                                        const int4* __restrict__ boxes, const float* __restrict__ frac,
+                                                        MatchOut* __restrict__ out) {
+    const int l = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (l >= max_det) return;
+    const unsigned long long key = best[l];
+    MatchOut o{};
+    o.idx = -1;
+    if (key != kNoKey) {
+        const unsigned j = (unsigned)key;
+        o.rec = rec[j];
+        o.rec.score = q[j];
+        o.box = boxes[j];
+        o.frac = frac[j];
+        o.idx = (int)j;
+    }
+    out[l] = o;
+}
+
+// P(r) of a valid record on the host: the kernel's arithmetic (the Makefile's -ffp-contract=off keeps it unfused here too).
+void pose_lines(const fdcm_templates* t, int64_t tmpl, const float* M, std::vector<float>& out) {
+    const int64_t l0 = t->offsets[(size_t)tmpl], nl = t->offsets[(size_t)tmpl + 1] - l0;
+    out.resize((size_t)nl * 4);
+    for (int64_t i = 0; i < nl; ++i) {
+        const float* p = &t->lines[(size_t)(l0 + i) * 4];
+        float* o = &out[(size_t)i * 4];
+        for (int c = 0; c < 2; ++c) {
+            o[2 * c] = (M[0] * p[2 * c] + M[1] * p[2 * c + 1]) + M[2];
+            o[2 * c + 1] = (M[3] * p[2 * c] + M[4] * p[2 * c + 1]) + M[5];
+        }
+    }
+}
+
+}  // namespace
+
+// Host only: F(r) of every record (include/fdcm.h, "Match lists").
+void matches_footprints(const fdcm_templates* t, const fdcm_match* matches, int64_t n, int32_t base, int margin, int32_t* boxes_out) {
+    std::vector<float> posed;
+    for (int64_t j = 0; j < n; ++j) {
+        const int64_t tm = (int64_t)matches[j].tmpl_idx - base;
+        Foot F{0, 0, -1, -1};
+        if (tm >= 0 && tm < t->T) {
+            pose_lines(t, tm, matches[j].transform, posed);
+            F = footprint(posed.data(), 4, (int64_t)(posed.size() / 4), margin);
+        }
+        std::memcpy(boxes_out + 4 * j, &F, sizeof F);
+    }
+}
+
+// Both device calls on match lists (include/fdcm.h, "Match lists"): the arguments are checked (fdcm_capi.cpp).  det null: the
+// verify call, whose outputs are scores_out, fractions_out and costs_out (each may be null).  Else the detect call: the
+// rounds on the verify pass's keys and boxes, then the gather.  One reserve_eval lays out the whole call: the upload (host
+// records, caps, denominators, needs, totals, host bins), the list's arrays, the result list and the rounds' partials.
+void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
+                 const MatchesDetect* det, float* scores_out, float* fractions_out, float* costs_out, fdcm_match** out, int64_t* n_out,
+                 int32_t* indices_out, int32_t* boxes_out, float* matched_out) {
+    if (n_out) *n_out = 0;
+    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    hipStream_t st = fm->stream;
+    const size_t N = (size_t)n, T = (size_t)t->T, Lmax = (size_t)t->max_lines;
+    const bool flat = test_switches().matched_flat;
+    const size_t SL = ivol_slice_floats(fm->W, fm->H);
+    const bool buf32 = !flat && (size_t)fm->m * SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
+    const bool gated = det && det->min_matched > 0.f;
+    const std::vector<float> den = best_denominators(t, det ? det->penalty : -1, det ? det->tau : 1.f);
+    std::vector<float> totals(T);
+    templates_matched_totals(t, totals.data());
+    // Host-libm bins (fdcm_orientation_bins_mode() == 1): the bins of every posed line, on the host, from host records; device
+    // records cost one download.
+    std::vector<unsigned short> bins;
+    std::vector<fdcm_match> fetched;
+    if (orientation_bins_on_host()) {
+        if (fm->m > 65535) throw std::string("host-side orientation bins need depth <= 65535");
+        const fdcm_match* h = matches;
+        if (on_device) {
+            fetched.resize(N);
+            FDCM_HIP(hipMemcpyAsync(fetched.data(), matches, N * sizeof(fdcm_match), hipMemcpyDeviceToHost, st));
+            FDCM_HIP(hipStreamSynchronize(st));
+            h = fetched.data();
+        }
+        bins.assign(std::max<size_t>(1, N * Lmax), 0);
+        std::vector<float> posed;
+        for (size_t j = 0; j < N; ++j) {
+            const int64_t tm = (int64_t)h[j].tmpl_idx - base;
+            if (tm < 0 || tm >= t->T) continue;
+            pose_lines(t, tm, h[j].transform, posed);
+            for (size_t i = 0; i < posed.size() / 4; ++i) {
+                const float* p = &posed[4 * i];
+                const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
+                bins[j * Lmax + i] = (unsigned short)closest_orientation(fm->keys.data(), (int)fm->m, angle);
+            }
+        }
+    }
+    const int max_det = det ? det->max_detections : 0;
+    const size_t o_caps = on_device ? 0 : al256(N * sizeof(fdcm_match)), o_den = o_caps + (t->capped ? al256((size_t)t->n_lines * 4) : 0),
+                 o_need = o_den + al256(T * 4), o_tl = o_need + (gated ? al256(T * 4) : 0), o_bins = o_tl + al256(T * 4),
+                 o_score = o_bins + (bins.empty() ? 0 : al256(bins.size() * 2)), o_frac = o_score + al256(N * 4), o_q = o_frac + al256(N * 4),
+                 o_keys = o_q + al256(N * 4), o_box = o_keys + al256(N * 8), o_costs = o_box + al256(N * 16),
+                 o_best = o_costs + (costs_out ? al256(N * Lmax * 4) : 0), o_pk = o_best + al256((size_t)max_det * 8),
+                 total = o_pk + 2 * kNmsWorkgroups * 8;
+    reserve_eval(fm, total, o_score);
+    char* d = (char*)fm->search.eval.p;
+    char* h = (char*)fm->search.eval_stage.p;
+    if (!on_device) std::memcpy(h, matches, N * sizeof(fdcm_match));
+    if (t->capped) std::memcpy(h + o_caps, t->caps.data(), (size_t)t->n_lines * 4);
+    std::memcpy(h + o_den, den.data(), T * 4);
+    if (gated)
+        for (size_t i = 0; i < T; ++i) ((float*)(h + o_need))[i] = det->min_matched * totals[i];  // need = float32(min_matched * TL)
+    std::memcpy(h + o_tl, totals.data(), T * 4);
+    if (!bins.empty()) std::memcpy(h + o_bins, bins.data(), bins.size() * 2);
+    FDCM_HIP(hipMemcpyAsync(d, h, o_score, hipMemcpyHostToDevice, st));
+    MatchesArgs a{};
+    a.vol = fm->vol.as<float>(); a.SL = SL; a.m = (int)fm->m; a.W = (int)fm->W; a.H = (int)fm->H; a.tx = fm->tx; a.ty = fm->ty;
+    a.keys = (const float*)((const char*)fm->build.plan.p + fm->off_keys);
+    a.tlines = t->d_lines.as<float4>(); a.tlen = t->d_lengths.as<float>(); a.toff = t->d_offsets.as<long long>();
+    a.caps = t->capped ? (const float*)(d + o_caps) : nullptr;
+    a.den = (const float*)(d + o_den);
+    a.need = gated ? (const float*)(d + o_need) : nullptr;
+    a.tl = (const float*)(d + o_tl);
+    a.bins = bins.empty() ? nullptr : (const unsigned short*)(d + o_bins);
+    a.rec = on_device ? matches : (const fdcm_match*)d;
+    a.n = (int)n; a.base = base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax;
+    a.margin = det ? det->margin : 0; a.rescore = det ? det->rescore : 0;
+    a.max_score = det ? det->max_score : f_inf();
+    a.score = (float*)(d + o_score); a.frac = (float*)(d + o_frac); a.q = (float*)(d + o_q);
+    a.costs = costs_out ? (float*)(d + o_costs) : nullptr;
+    a.keys_out = (unsigned long long*)(d + o_keys);
+    a.boxes = (int4*)(d + o_box);
+    auto kern = buf32 ? (t->capped ? k_matches_verify<true, true> : k_matches_verify<true, false>)
+                      : (t->capped ? k_matches_verify<false, true> : k_matches_verify<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, a);
+    FDCM_HIP(hipGetLastError());
+    if (!det) {
+        if (scores_out) FDCM_HIP(hipMemcpyAsync(scores_out, d + o_score, N * 4, hipMemcpyDeviceToHost, st));
+        if (fractions_out) FDCM_HIP(hipMemcpyAsync(fractions_out, d + o_frac, N * 4, hipMemcpyDeviceToHost, st));
+        if (costs_out && Lmax) FDCM_HIP(hipMemcpyAsync(costs_out, d + o_costs, N * Lmax * 4, hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
+        return;
+    }
+    // The rounds: the list form on the keys and boxes the pass wrote; the result list begins as kNoKey throughout.
+    unsigned long long* d_best = (unsigned long long*)(d + o_best);
+    FDCM_HIP(hipMemsetAsync(d_best, 0xff, (size_t)max_det * 8, st));
+    NmsArgs r{};  // a list form: no planes, no pairs, boxes whatever the set's kind
+    r.keys = a.keys_out;
+    r.boxes = a.boxes;
+    r.n = (long long)n;
+    r.n_chunks = (r.n + 255) / 256;
+    r.permille = det->overlap_permille;
+    r.cross = det->overlap_permille;
+    r.pk_out = (unsigned long long*)(d + o_pk);
+    r.best = d_best;
+    nms_rounds(r, (unsigned)std::min<long long>(kNmsWorkgroups, r.n_chunks), max_det, st);
+    // The gather, into pinned memory: 64-byte entries, which the host then packs into the records at the array's front.
+    *out = result_acquire((size_t)max_det * sizeof(MatchOut));
+    MatchOut* out_dev = nullptr;
+    FDCM_HIP(hipHostGetDevicePointer((void**)&out_dev, *out, 0));
+    hipLaunchKernelGGL(k_matches_gather, dim3((unsigned)((max_det + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)d_best, max_det,
+                       a.rec, (const float*)a.q, (const int4*)a.boxes, (const float*)a.frac, out_dev);
+    FDCM_HIP(hipGetLastError());
+    FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
+    int64_t k = 0;
+    for (; k < max_det; ++k) {
+        MatchOut o;
+        std::memcpy(&o, (const char*)*out + (size_t)k * sizeof(MatchOut), sizeof o);
+        if (o.idx < 0) break;
+        std::memcpy((char*)*out + (size_t)k * sizeof(fdcm_match), &o.rec, sizeof(fdcm_match));  // (in front of entry k, or in it)
+        if (indices_out) indices_out[k] = o.idx;
+        if (boxes_out) std::memcpy(boxes_out + 4 * k, &o.box, 16);
+        if (matched_out) matched_out[k] = o.frac;
+    }
+    *n_out = k;
 }
 
 }  // namespace fdcm

@@ -42,7 +42,8 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              pass of the detections over pose windows with it
 //   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (detect_all, run_best_map_gated,
 //                              run_matched_fractions, run_search_exhaustive_detect_windows: its scoring, its winners' pass and
-//                              its fractions)
+//                              its fractions; run_matches: the verify pass of the calls on match lists, which also take
+//                              their bins from the host under FDCM_FORCE_HOST_BINS)
 //   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
 //                              takes that form for a volume of 4 GB or more alone (score maps, top-k, peaks, rotations, best
 //                              map, the detections, line costs); the pose windows and the calls by matched fraction keep
@@ -455,6 +456,21 @@ void run_search_exhaustive_detect_windows_objects(fdcm_featuremap* fm, const fdc
 // poses: n x (tmpl, a, x, y), checked; *costs is malloc'ed; offsets: n + 1
 void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                     float** costs, int64_t* offsets);
+// Match lists (include/fdcm.h, "Match lists"), implemented in fdcm_exhaustive.hip: the arguments are checked.
+// matches_footprints: host only, 4 int32 per record.  run_matches: both device calls; `matches` are n records on the host or
+// (on_device) on the handle's device; det null: the verify call, whose outputs scores_out, fractions_out (n floats) and
+// costs_out (n x max_lines floats) may each be null; else the detect call with *out acquired (max_detections entries at
+// most), *n_out its count, and indices_out, boxes_out (4 per entry), matched_out of max_detections entries or null.
+struct MatchesDetect {
+    float max_score;
+    int max_detections, overlap_permille, margin, penalty;
+    float tau, min_matched;
+    int rescore;
+};
+void matches_footprints(const fdcm_templates* t, const fdcm_match* matches, int64_t n, int32_t base, int margin, int32_t* boxes_out);
+void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
+                 const MatchesDetect* det, float* scores_out, float* fractions_out, float* costs_out, fdcm_match** out, int64_t* n_out,
+                 int32_t* indices_out, int32_t* boxes_out, float* matched_out);
 // Scene coverage (include/fdcm.h, "Scene coverage").  What prepare_pairs yields for the distinct pairs of a pose list, in the
 // plain form fdcm_coverage.hip takes: pair u = find(tmpl * n_rot + a) has the lines [line0[u], line0[u] + nl[u]) -- the (rotated)
 // end points and the bin k_line_costs reads --, its admissible translations adm[5 u ..] = any, x0, x1, y0, y1 and its footprint

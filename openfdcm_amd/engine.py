@@ -104,6 +104,27 @@ def as_poses(poses):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def match_records(matches):
+    """A match list as one contiguous record array (capi.MATCH_DTYPE): a MatchList's records or such an array, not copied when
+    it is contiguous already."""
+    rec = matches.records() if hasattr(matches, "records") else np.asarray(matches)
+    if rec.dtype != capi.MATCH_DTYPE:
+        raise ValueError("matches must be a MatchList or an array of match records")
+    return np.ascontiguousarray(rec.reshape(-1))
+
+
+def match_footprints(templates, matches, margin=0, tmpl_index_base=0):
+    """fdcm_matches_footprints: the (n, 4) int32 footprints x0, y0, x1, y1 of the posed lines of every record of a match list
+    (include/fdcm.h, "Match lists"); (0, 0, -1, -1) for an invalid record, a template without lines or a NaN end point.  Host
+    only.  templates: a DeviceTemplates."""
+    rec = match_records(matches)
+    out = np.zeros((rec.shape[0], 4), dtype=np.int32)
+    capi.check(capi.lib().fdcm_matches_footprints(templates._h, C.c_void_p(rec.ctypes.data) if rec.shape[0] else None, rec.shape[0],
+                                                  int(tmpl_index_base), int(margin),
+                                                  out.ctypes.data_as(C.POINTER(C.c_int32)) if rec.shape[0] else None))
+    return out
+
+
 def line_lengths(templates):
     """Per template the float32 lengths of its lines, sqrt(dx * dx + dy * dy) in numpy float32."""
     out = []
@@ -670,6 +691,50 @@ class DeviceFeatureMap:
         finally:
             capi.lib().fdcm_lines_free(out)
 
+    # ---- match lists (include/fdcm.h, "Match lists"): the records of search(), verified and suppressed on the device
+    def _match_input(self, matches, device_ptr, n):
+        """(pointer, n, on_device, the array kept alive) of the three forms: host records, a device buffer, the last search."""
+        if device_ptr:
+            return C.c_void_p(int(device_ptr)), int(n), 1, None
+        if matches is None:
+            return None, int(getattr(self, "last_search_count", 0)), 0, None
+        rec = match_records(matches)
+        return (C.c_void_p(rec.ctypes.data) if rec.shape[0] else None), rec.shape[0], 0, rec
+
+    def verify_matches(self, templates, matches=None, tmpl_index_base=0, device_ptr=None, n=0):
+        """fdcm_matches_verify: (scores, fractions, costs) of every record: s(r) and frac(r) as (n,) float32 and the uncapped
+        line costs as an (n, Lmax) float32 array, NaN beyond a template's line count, all NaN for a record that is invalid or
+        not admissible.  matches: a MatchList or record array on the host; None: the records of the last search_raw on this
+        map; device_ptr, n: records in device memory (search_into)."""
+        ptr, n, on_device, keep = self._match_input(matches, device_ptr, n)
+        lmax = templates.max_lines
+        nan = np.float32(np.nan)
+        s, f, c = np.full(n, nan, dtype=np.float32), np.full(n, nan, dtype=np.float32), np.full((n, lmax), nan, dtype=np.float32)
+        capi.check(capi.lib().fdcm_matches_verify(self._h, templates._h, ptr, n, on_device, int(tmpl_index_base), capi.fptr(s),
+                                                  capi.fptr(f), capi.fptr(c)))
+        return s, f, c
+
+    def detect_matches(self, templates, matches=None, max_score=float("inf"), overlap_permille=300, max_detections=1024, penalty=None,
+                       tau=1.0, margin=0, min_matched=None, rescore=False, tmpl_index_base=0, indices=False, boxes=False,
+                       matched=False, device_ptr=None, n=0):
+        """fdcm_matches_detect: the greedy rule by footprint overlap on a match list, keyed by (q, position): raw match records
+        in ascending order with q for their score; with indices the (k,) int32 positions in the list, with boxes the (k, 4)
+        int32 footprints, with matched the (k,) float32 fractions, in that order.  The forms of matches are verify_matches'."""
+        ptr, n, on_device, keep = self._match_input(matches, device_ptr, n)
+        out, k = C.c_void_p(), C.c_int64()
+        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0
+        ji = np.zeros(md, dtype=np.int32)
+        fp = np.zeros((md, 4), dtype=np.int32)
+        fr = np.zeros(md, dtype=np.float32)
+        capi.check(capi.lib().fdcm_matches_detect(
+            self._h, templates._h, ptr, n, on_device, int(tmpl_index_base), float(max_score), int(max_detections), int(overlap_permille),
+            int(margin), -1 if penalty is None else int(penalty), float(tau), 0.0 if min_matched is None else float(min_matched),
+            int(bool(rescore)), C.byref(out), C.byref(k), ji.ctypes.data_as(C.POINTER(C.c_int32)) if indices and md else None,
+            fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None, capi.fptr(fr) if matched and md else None))
+        res = (_adopt_matches(out, k.value),) + ((ji[:k.value].copy(),) if indices else ()) + ((fp[:k.value].copy(),) if boxes else ())
+        res += (fr[:k.value].copy(),) if matched else ()
+        return res if len(res) > 1 else res[0]
+
     def scene_coverage(self, labels, templates, poses, cs=None, pivots=None, radius=2, bin_tolerance=1, margin=None, residual=False):
         """Scene coverage (include/fdcm.h, "Scene coverage"): per pose (tmpl, a, x, y), as line_costs takes them, the number of
         edge pixels of `labels` in the pose's window (its footprint at `margin`, None: radius) and how many of them the posed
@@ -855,6 +920,11 @@ class DeviceTemplates:
         self._h = h
         self._offsets = np.array(offsets, dtype=np.int64)
 
+    @property
+    def max_lines(self):
+        """The set's largest line count (0 for an empty set): the row length of verify_matches' costs."""
+        return int(np.diff(self._offsets).max()) if self.count else 0
+
     def line_caps(self):
         """One float32 array of caps per template (+inf: no cap)."""
         out = np.zeros(self.n_lines, dtype=np.float32)
@@ -1002,6 +1072,7 @@ def search_raw(fm, templates, scene, max_tmpl_lines, max_scene_lines, optimizer=
     capi.check(capi.lib().fdcm_search(fm._h, templates._h, capi.fptr(rec), rec.shape[0], int(max_tmpl_lines),
                                       int(max_scene_lines), int(optimizer), int(batch_size), int(tmpl_index_base),
                                       C.byref(out), C.byref(n)))
+    fm.last_search_count = n.value  # the records the handle keeps on the device (topk, verify_matches, detect_matches)
     return _adopt_matches(out, n.value)
 
 
