@@ -1200,6 +1200,25 @@ int fdcm_selftest_sweep_order_counts(int64_t* from_history, int64_t* from_proxy)
  * started; by default only where one blocking build has the GPU to itself, FDCM_SWEEP_STEAL=<blocks> forces a threshold,
  * 0 = never).  Lets a test see that the path it means to exercise ran. */
 int fdcm_selftest_sweep_steals(fdcm_featuremap* fm, int64_t* count);
+/* The buffers the test switch FDCM_POISON fills (openfdcm_amd/csrc/fdcm_internal.h, "the tests' switches"; DESIGN.md, section
+ * 32), by the names of their members: the exhaustive calls' workspace and the volume, the build's scratch, the reference
+ * search's workspaces, the device tail's, scene coverage's and the scratch of the calls without a handle. */
+enum fdcm_poison_buffer {
+    FDCM_FILL_EVAL = 0, FDCM_FILL_EVAL_STAGE, FDCM_FILL_VOL,
+    FDCM_FILL_IVOL, FDCM_FILL_BITMAP, FDCM_FILL_COLDESC, FDCM_FILL_COLMASK, FDCM_FILL_LABELS, FDCM_FILL_EDGE_PARENT,
+    FDCM_FILL_EDGE_ROOTS, FDCM_FILL_PYR, FDCM_FILL_OFFTAB, FDCM_FILL_STACK, FDCM_FILL_PLAN, FDCM_FILL_BUILD_STAGE,
+    FDCM_FILL_SCENE, FDCM_FILL_PAIRS, FDCM_FILL_RECORDS, FDCM_FILL_FLAGS, FDCM_FILL_WORK, FDCM_FILL_COUNTER, FDCM_FILL_BINS,
+    FDCM_FILL_OUT, FDCM_FILL_SEARCH_STAGE, FDCM_FILL_BINS_STAGE, FDCM_FILL_CNT,
+    FDCM_FILL_TAIL, FDCM_FILL_TAIL_OUT,
+    FDCM_FILL_COVERAGE, FDCM_FILL_COVERAGE_STAGE,
+    FDCM_FILL_PIXEL_PIXELS, FDCM_FILL_PIXEL_LABELS, FDCM_FILL_PIXEL_KEYS, FDCM_FILL_PIXEL_PARENT, FDCM_FILL_PIXEL_COUNTS,
+    FDCM_FILL_PIXEL_COMPS, FDCM_FILL_PIXEL_OUT,
+    FDCM_FILL_BUFFERS  /* how many there are */
+};
+/* counts[i]: how often this process filled buffer ids[i] (an fdcm_poison_buffer) with FDCM_POISON's word; all 0 without the
+ * switch.  A fill of a buffer without capacity does not count.  Lets a test see that the word reached the buffers it means to
+ * cover. */
+int fdcm_selftest_poison_fills(const int32_t* ids, int64_t n, int64_t* counts);
 
 #ifdef __cplusplus
 }

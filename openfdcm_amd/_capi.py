@@ -19,6 +19,11 @@ FOOTPRINT_BOX, FOOTPRINT_HULL = 0, 1  # FDCM_FOOTPRINT_BOX, FDCM_FOOTPRINT_HULL
 SHARDED_ALWAYS_COLLECTIVE = 1
 SHARDED_ALLOW_SAME_DEVICE = 2
 SHARD_TEMPLATES, SHARD_FRAMES = 0, 1
+# enum fdcm_poison_buffer, in its order: FDCM_FILL_EVAL = 0, .., FDCM_FILL_PIXEL_OUT (fdcm_selftest_poison_fills)
+POISON_BUFFERS = ("eval", "eval_stage", "vol", "ivol", "bitmap", "coldesc", "colmask", "labels", "edge_parent", "edge_roots", "pyr", "offtab",
+                  "stack", "plan", "build_stage", "scene", "pairs", "records", "flags", "work", "counter", "bins", "out", "search_stage",
+                  "bins_stage", "cnt", "tail", "tail_out", "coverage", "coverage_stage", "pixel_pixels", "pixel_labels", "pixel_keys",
+                  "pixel_parent", "pixel_counts", "pixel_comps", "pixel_out")
 
 MATCH_DTYPE = np.dtype([("tmpl_idx", "<i4"), ("score", "<f4"), ("transform", "<f4", (6,))])
 assert MATCH_DTYPE.itemsize == 32
@@ -267,6 +272,7 @@ SYMBOLS = [
     ("fdcm_selftest_sweep_ranges", C.c_int, [C.c_int]),
     ("fdcm_selftest_sweep_order_counts", C.c_int, [_i64p, _i64p]),
     ("fdcm_selftest_sweep_steals", C.c_int, [_vp, _i64p]),
+    ("fdcm_selftest_poison_fills", C.c_int, [C.POINTER(C.c_int32), C.c_int64, _i64p]),
 ]
 
 _lib = None

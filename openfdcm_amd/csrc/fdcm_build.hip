@@ -848,6 +848,31 @@ static void stage_integral(fdcm_featuremap* fm, const PlanOnDevice& P) {
 #undef FDCM_INTEGRAL
 }
 
+// FDCM_POISON: every buffer of the build, behind reserve_build and in front of the first command of run_build.  Three regions
+// are state and stay while the handle's record says they are valid: the balanced sweep's per-chunk
+// costs, its steal counter, and the line integral's group table.  A record that does not cover this build's shape leaves the
+// region to the fill like the rest -- except a group table this build will not rewrite (it stops before the line integral):
+// that one stays for the build its record names.  The records themselves are not touched.
+static void poison_build(fdcm_featuremap* fm, const BuildLayout& L, int stop_after) {
+    hipStream_t st = fm->stream;
+    BuildBuffers& b = fm->build;
+    FDCM_HIP(hipStreamSynchronize(st));  // (nothing queued still reads the pinned staging)
+    poison_fill(fm->vol, st, FDCM_FILL_VOL); poison_fill(fm->ivol, st, FDCM_FILL_IVOL);
+    poison_fill(b.bitmap, st, FDCM_FILL_BITMAP); poison_fill(b.coldesc, st, FDCM_FILL_COLDESC); poison_fill(b.colmask, st, FDCM_FILL_COLMASK);
+    poison_fill(b.labels, st, FDCM_FILL_LABELS); poison_fill(b.edge_parent, st, FDCM_FILL_EDGE_PARENT);
+    poison_fill(b.edge_roots, st, FDCM_FILL_EDGE_ROOTS); poison_fill(b.pyr, st, FDCM_FILL_PYR);
+    const bool table_valid = fm->groups.m == (int)fm->m && fm->groups.steps == (int)fm->W;
+    const bool table_of_another_build = fm->groups.m != 0 && stop_after < 3;
+    if (!table_valid && !table_of_another_build) poison_fill(b.offtab, st, FDCM_FILL_OFFTAB);
+    KeepRange keep[2];
+    int n_keep = 0;
+    if (L.balanced && fm->sweep.cost_chunks == L.nchunks && fm->sweep.cost_w == (int)fm->W) keep[n_keep++] = KeepRange{L.o_cost, L.o_cost + 4 * (size_t)L.nchunks};
+    if (L.balanced && fm->sweep.steals_off == L.o_steals) keep[n_keep++] = KeepRange{L.o_steals, L.o_steals + 256};
+    poison_fill(b.stack, st, FDCM_FILL_STACK, keep, n_keep);
+    poison_fill(b.plan, st, FDCM_FILL_PLAN);
+    poison_fill(b.stage, FDCM_FILL_BUILD_STAGE);
+}
+
 void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
     const auto t0 = std::chrono::steady_clock::now();
     const BuildLayout L = build_layout(plan, fm->distance, stop_after);
@@ -857,9 +882,9 @@ void run_build(fdcm_featuremap* fm, const BuildPlan& plan, int stop_after) {
     fm->last_build = fdcm_build_timing{}; fm->built.reset(); fm->holds = VolStage::none;
     if (L.empty) return;
     // FDCM_POISON (fdcm_internal.h, "the tests' switches"): the whole allocation of the volume, the columns and the rows of
-    // padding included, holds the word before the first stage writes; what the search reads afterwards the build has written
-    if (test_switches().poison && fm->vol.cap >= 4)
-        FDCM_HIP(hipMemsetD32Async((hipDeviceptr_t)fm->vol.p, (int)test_switches().poison_word, fm->vol.cap / 4, fm->stream));
+    // padding included, and of every scratch buffer holds the word before the first stage writes; what the search reads
+    // afterwards the build has written
+    if (test_switches().poison) poison_build(fm, L, stop_after);
     SweepBuf sb{};
     std::vector<int32_t> proxy_cost;  // (stays empty unless the sweep's launch order takes it)
     bool device_proxy = false;        // the launch order's costs are counted by pass 1

@@ -1728,6 +1728,13 @@ int fdcm_selftest_sweep_order_counts(int64_t* from_history, int64_t* from_proxy)
         fdcm::sweep_order_counts(from_history, from_proxy);
     });
 }
+int fdcm_selftest_poison_fills(const int32_t* ids, int64_t n, int64_t* counts) {
+    return guarded([&] {
+        require(n >= 0 && (n == 0 || (ids && counts)), "null argument");
+        for (int64_t i = 0; i < n; ++i) require(ids[i] >= 0 && ids[i] < FDCM_FILL_BUFFERS, "no such buffer");
+        for (int64_t i = 0; i < n; ++i) counts[i] = fdcm::poison_fill_count(ids[i]);
+    });
+}
 int fdcm_selftest_sweep_steals(fdcm_featuremap* fm, int64_t* count) {
     return guarded([&] {
         require(fm && count, "null argument");

@@ -353,6 +353,15 @@ struct CovTable {
     }
 };
 
+// FDCM_POISON (fdcm_internal.h, "the tests' switches"): the handle's coverage buffers hold the word at the head of a call, before a
+// host caller's labels go up
+void poison_coverage(fdcm_featuremap* fm) {
+    if (!test_switches().poison) return;
+    FDCM_HIP(hipStreamSynchronize(fm->stream));  // (nothing queued still reads the staging)
+    poison_fill(fm->coverage, fm->stream, FDCM_FILL_COVERAGE);
+    poison_fill(fm->coverage_stage, FDCM_FILL_COVERAGE_STAGE);
+}
+
 // no window holds a pixel: the residual is a copy
 void copy_labels(const uint8_t* labels, size_t npix, bool on_device, uint8_t* residual, hipStream_t st) {
     if (residual && on_device) {
@@ -394,6 +403,7 @@ void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, i
                  o_res = o_lab + (on_device ? 0 : al256(npix)), total = o_res + (on_device || !residual ? 0 : al256(npix));
     fm->coverage.reserve(total);
     fm->coverage_stage.reserve(o_cnt);
+    poison_coverage(fm);
     char* d = (char*)fm->coverage.p;
     char* h = (char*)fm->coverage_stage.p;
     const uint8_t* d_labels = labels;
@@ -457,6 +467,7 @@ void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int
                  o_plane = o_lab + (on_device ? 0 : al256(npix)), total = o_plane + (on_device && residual ? 0 : al256(npix));
     fm->coverage.reserve(total);
     fm->coverage_stage.reserve(std::max(o_cnt, o_fresh - o_cnt));
+    poison_coverage(fm);
     char* d = (char*)fm->coverage.p;
     char* h = (char*)fm->coverage_stage.p;
     const uint8_t* d_labels = labels;

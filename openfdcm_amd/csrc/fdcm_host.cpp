@@ -2,6 +2,7 @@
 // the scene bounding box, line classification and Cohen-Sutherland clipping.  O(scene lines)
 // work; the O(volume) work is in fdcm_build.hip.
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <cerrno>
 #include <cmath>
@@ -89,17 +90,46 @@ void PinnedBuf::release() {
     cap = 0;
 }
 
+// ---- FDCM_POISON's fills: the whole capacity, not the call's share -- what an earlier, larger call left behind is part of the question
+static std::atomic<int64_t> g_poison_fills[FDCM_FILL_BUFFERS];
+int64_t poison_fill_count(int id) { return id >= 0 && id < FDCM_FILL_BUFFERS ? g_poison_fills[id].load() : 0; }
+
+// the bytes [begin, end) of device memory: whole words where they are aligned, the word's bytes one by one at the ends
+static void poison_span(char* p, size_t begin, size_t end, uint32_t word, hipStream_t st) {
+    auto byte_at = [word](size_t off) { return (int)((word >> (8 * (off & 3))) & 0xff); };
+    for (; begin < end && (begin & 3); ++begin) FDCM_HIP(hipMemsetAsync(p + begin, byte_at(begin), 1, st));
+    const size_t words = (end - begin) / 4;
+    if (words) FDCM_HIP(hipMemsetD32Async((hipDeviceptr_t)(p + begin), (int)word, words, st));
+    for (begin += words * 4; begin < end; ++begin) FDCM_HIP(hipMemsetAsync(p + begin, byte_at(begin), 1, st));
+}
+void poison_fill(DevBuf& b, hipStream_t st, int id, const KeepRange* keep, int n_keep) {
+    const TestSwitches& sw = test_switches();
+    if (!sw.poison || !b.cap) return;
+    size_t at = 0;
+    for (int i = 0; i < n_keep; ++i) {
+        const size_t k0 = std::min(keep[i].begin, b.cap), k1 = std::min(keep[i].end, b.cap);
+        if (k0 > at) poison_span((char*)b.p, at, k0, sw.poison_word, st);
+        at = std::max(at, k1);
+    }
+    poison_span((char*)b.p, at, b.cap, sw.poison_word, st);
+    g_poison_fills[id].fetch_add(1, std::memory_order_relaxed);
+}
+void poison_fill(PinnedBuf& b, int id) {
+    const TestSwitches& sw = test_switches();
+    if (!sw.poison || !b.cap) return;
+    unsigned char* h = (unsigned char*)b.p;
+    for (size_t i = 0; i < b.cap; ++i) h[i] = (unsigned char)(sw.poison_word >> (8 * (i & 3)));
+    g_poison_fills[id].fetch_add(1, std::memory_order_relaxed);
+}
+
 void reserve_eval(fdcm_featuremap* fm, size_t device_bytes, size_t stage_bytes) {
     SearchBuffers& s = fm->search;
     s.eval.reserve(device_bytes);
     if (stage_bytes) s.eval_stage.reserve(stage_bytes);
-    const TestSwitches& sw = test_switches();
-    if (!sw.poison) return;
-    // the whole capacity of both, not this call's share: what an earlier, larger call left behind is part of the question
+    if (!test_switches().poison) return;
     FDCM_HIP(hipStreamSynchronize(fm->stream));  // (nothing queued still reads the staging)
-    if (s.eval.cap >= 4) FDCM_HIP(hipMemsetD32Async((hipDeviceptr_t)s.eval.p, (int)sw.poison_word, s.eval.cap / 4, fm->stream));
-    uint32_t* h = (uint32_t*)s.eval_stage.p;
-    std::fill(h, h + s.eval_stage.cap / 4, sw.poison_word);
+    poison_fill(s.eval, fm->stream, FDCM_FILL_EVAL);
+    poison_fill(s.eval_stage, FDCM_FILL_EVAL_STAGE);
 }
 
 // ---- clipLines with the box [0, W-1] x [0, H-1] (drawing.cpp:29-112, deleteOob = true) ----

@@ -328,14 +328,20 @@ const uint8_t* launch_pyramid(hipStream_t st, const uint8_t* image, int width, i
 // ------------------------------------------------------------------------------------------ the calls without a handle
 PixelScratch::~PixelScratch() { for (DevBuf* b : {&pixels, &labels, &keys, &parent, &counts, &comps, &out}) b->release(); }
 
+void PixelScratch::take(DevBuf& b, size_t bytes, int id) {
+    const void* before = b.p;
+    b.reserve(bytes);
+    if (b.p != before) poison_fill(b, nullptr, id);
+}
+
 const uint8_t* PixelScratch::upload(const uint8_t* host_or_device, int width, int height, int& row_stride, bool on_device,
                                     const std::vector<float>* host_keys) {
     if (host_keys) {
-        keys.reserve(std::max<size_t>(1, host_keys->size()) * sizeof(float));
+        take(keys, std::max<size_t>(1, host_keys->size()) * sizeof(float), FDCM_FILL_PIXEL_KEYS);
         FDCM_HIP(hipMemcpy(keys.p, host_keys->data(), host_keys->size() * sizeof(float), hipMemcpyHostToDevice));
     }
     if (on_device) return host_or_device;
-    pixels.reserve((size_t)width * height);
+    take(pixels, (size_t)width * height, FDCM_FILL_PIXEL_PIXELS);
     FDCM_HIP(hipMemcpy2D(pixels.p, (size_t)width, host_or_device, (size_t)row_stride, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
     row_stride = width;
     return pixels.as<uint8_t>();
@@ -352,8 +358,8 @@ void image_pyramid_host(int device, const uint8_t* image, int width, int height,
     const size_t n = (size_t)(wl * hl);
     const uint8_t* d = s.upload(image, width, height, row_stride, on_device, nullptr);
     const size_t off_b = ((size_t)(w1 * h1) + 15) & ~(size_t)15;
-    if (level > 1) s.labels.reserve(off_b + (size_t)(w2 * h2));  // (the two buffers of the levels between)
-    if (!out_on_device) s.out.reserve(n);
+    if (level > 1) s.take(s.labels, off_b + (size_t)(w2 * h2), FDCM_FILL_PIXEL_LABELS);  // (the two buffers of the levels between)
+    if (!out_on_device) s.take(s.out, n, FDCM_FILL_PIXEL_OUT);
     uint8_t* dst = out_on_device ? out : s.out.as<uint8_t>();  // the last level goes where it is wanted: device memory of the caller's is written by a kernel
     if (level == 0)
         hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)((width + 255) / 256), (unsigned)height), dim3(256), 0, nullptr, d, width, height, row_stride, dst);
@@ -372,8 +378,8 @@ void edge_labels_host(int device, const uint8_t* image, int width, int height, i
     PixelScratch s;
     const size_t n = (size_t)width * height;
     const uint8_t* d = s.upload(image, width, height, row_stride, false, &keys);
-    s.labels.reserve(n);
-    if (hysteresis) s.comps.reserve(n * 8);  // a parent and a root word per pixel
+    s.take(s.labels, n, FDCM_FILL_PIXEL_LABELS);
+    if (hysteresis) s.take(s.comps, n * 8, FDCM_FILL_PIXEL_COMPS);  // a parent and a root word per pixel
     launch_edge_labels(nullptr, d, width, height, row_stride, s.keys.as<float>(), (int)keys.size(), e, s.labels.as<uint8_t>(),
                        hysteresis ? s.comps.as<int32_t>() : nullptr, hysteresis ? s.comps.as<uint32_t>() + n : nullptr);
     FDCM_HIP(hipGetLastError());

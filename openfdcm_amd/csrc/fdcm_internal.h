@@ -48,16 +48,24 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              takes that form for a volume of 4 GB or more alone (score maps, top-k, peaks, rotations, best
 //                              map, the detections, line costs); the pose windows and the calls by matched fraction keep
 //                              their own switches
-//   FDCM_POISON=<uint32>       (decimal or 0x-hex) what a call finds in memory it did not write: reserve_eval fills the whole
-//                              capacity of search.eval and of search.eval_stage with the word before the call writes anything,
-//                              and run_build fills the whole allocation of the volume, padding included, ahead of its first
-//                              stage (an adopted volume is not touched).  Nothing else is filled: the build's scratch buffers
-//                              and the reference search's buffers carry documented state from one call to the next (the
-//                              sweep's cost history and steal counter, the line integral's group table, the last search's
-//                              matches) and want a piece of work of their own.  The tests use the words 0 and 1 alone.  1 is
+//   FDCM_POISON=<uint32>       (decimal or 0x-hex) what a call finds in memory it did not write: the whole capacity of a
+//                              buffer holds the word before the call's first write (poison_fill; DESIGN.md sections 22 and
+//                              32).  reserve_eval: search.eval and search.eval_stage.  run_build: the whole allocation of the
+//                              volume, padding included (an adopted volume is not touched), ivol, bitmap, coldesc, colmask,
+//                              labels, edge_parent, edge_roots, pyr, offtab, stack, plan and the pinned build.stage.
+//                              run_search: scene, pairs, records, flags, work, counter, bins, the pinned stage, bins_stage
+//                              and cnt, and search.out in a host-output search.  run_topk_device / run_topk: search.tail,
+//                              search.stage, search.tail_out.  The coverage calls: coverage, coverage_stage.  The calls
+//                              without a handle: every member of PixelScratch as it is allocated.  What is state stays
+//                              while the handle's record says it is valid: the balanced sweep's per-chunk costs
+//                              (sweep.cost_chunks, cost_w) and steal counter (sweep.steals_off) in stack, the line integral's
+//                              group table (groups) in offtab, and the last search's matches in search.out, which only the
+//                              host-output search that overwrites them fills.  Without the switch nothing is queued, copied,
+//                              waited for or allocated that was not before.  The tests use the words 0 and 1 alone.  1 is
 //                              the smallest denormal as a float (a near-perfect score), 0x0000000100000001 as a 64-bit key
 //                              (below every real key in every min and atomicMin), one too many as a count and in bounds as
-//                              an index: a kernel that reads what nobody wrote reads a wrong value from a valid place.  Words
+//                              an index, and as a union-find parent (parent[0] == 0, parent[1] == 1) a root that ends the
+//                              walk: a kernel that reads what nobody wrote reads a wrong value from a valid place.  Words
 //                              that are large as integers (0xFFFFFFFF, NaN patterns) hide a missing "no key" initialisation
 //                              and leave the allocation as an index; they are not for the GPU machines.
 struct TestSwitches {
@@ -91,6 +99,15 @@ struct PinnedBuf {
 // instead of allocating.  The sharded engine's slot workers run their frames inside one: every allocation of a frame
 // happens on the caller's thread before the workers get it (fdcm_sharded.cpp, submit_frame).
 struct NoGrowScope { NoGrowScope(); ~NoGrowScope(); };
+// FDCM_POISON's fill (above): the whole capacity of a buffer holds the word -- a device buffer by one
+// fill queued on `st`, which must be the stream whose work touches the buffer first; a pinned one by the host, and nothing in
+// flight may still read it (the caller has waited).  `keep`: byte ranges of the buffer, ascending and disjoint, that are
+// state and stay as they are.  `id` (fdcm_poison_buffer) counts the fill for fdcm_selftest_poison_fills.  Without the switch,
+// and for a buffer without capacity, they do nothing; they allocate nothing.
+struct KeepRange { size_t begin, end; };
+void poison_fill(DevBuf& b, hipStream_t st, int id, const KeepRange* keep = nullptr, int n_keep = 0);
+void poison_fill(PinnedBuf& b, int id);
+int64_t poison_fill_count(int id);
 
 // ---------------------------------------------------------------- build plan (host -> device)
 // One clipped scene line to rasterise (drawLines, drawing.h:111-125).  Each axis is either a
@@ -344,6 +361,9 @@ struct PixelScratch {
     // them; comps serves the edge kernels first and the components' sums afterwards.
     DevBuf pixels, labels, keys, parent, counts, comps, out;
     ~PixelScratch();
+    // reserve of a member: under FDCM_POISON a member that this allocated holds the word throughout, by a fill on the null
+    // stream, where the calls' kernels and copies run (id: its fdcm_poison_buffer)
+    void take(DevBuf& b, size_t bytes, int id);
     // The caller's image or label array where the kernels read it: device memory stays in place; host memory is copied into
     // `pixels` with rows packed, and row_stride becomes width.  The keys, where given, go into `keys`.
     const uint8_t* upload(const uint8_t* host_or_device, int width, int height, int& row_stride, bool on_device, const std::vector<float>* host_keys);

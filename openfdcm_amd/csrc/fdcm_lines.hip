@@ -247,11 +247,11 @@ void lines_of_device_labels(PixelScratch& s, StageClock& clk, const uint8_t* lab
                             float** lines, int64_t* n_lines) {
     *lines = nullptr; *n_lines = 0;
     const int n = W * H, nb = (n + kLineBlock - 1) / kLineBlock;
-    s.parent.reserve((size_t)n * 8);
+    s.take(s.parent, (size_t)n * 8, FDCM_FILL_PIXEL_PARENT);
     int32_t* pa = s.parent.as<int32_t>();
     int32_t* pb = pa + n;
     // block counts of the pixels' scan and of the components' (at most 2 n components, 256 per block), a total behind each
-    s.counts.reserve(((size_t)nb + 1 + (2 * (size_t)n + 255) / 256 + 1) * sizeof(int));
+    s.take(s.counts, ((size_t)nb + 1 + (2 * (size_t)n + 255) / 256 + 1) * sizeof(int), FDCM_FILL_PIXEL_COUNTS);
     int* counts = s.counts.as<int>();
     const dim3 tiles = uf_tile_grid(W, H);
     const LineKeys keys{m, lp.bucket};
@@ -266,7 +266,7 @@ void lines_of_device_labels(PixelScratch& s, StageClock& clk, const uint8_t* lab
     FDCM_HIP(hipGetLastError());
     const int nc = read_int(counts + nb);
     if (nc == 0) return;
-    s.comps.reserve(LineComps::bytes((size_t)nc));
+    s.take(s.comps, LineComps::bytes((size_t)nc), FDCM_FILL_PIXEL_COMPS);  // (lines_from_image_host: the edge kernels' words unless it has to grow)
     const LineComps c = LineComps::at(s.comps.p, (size_t)nc);
     FDCM_HIP(hipMemsetAsync(s.comps.p, 0, LineComps::bytes((size_t)nc), nullptr));
     FDCM_HIP(hipMemsetAsync(c.x0, 0xFF, (size_t)nc * 8, nullptr));  // x0 and y0
@@ -284,7 +284,7 @@ void lines_of_device_labels(PixelScratch& s, StageClock& clk, const uint8_t* lab
     FDCM_HIP(hipGetLastError());
     const int kept = read_int(ccounts + cb);
     if (kept == 0) return;
-    s.out.reserve((size_t)kept * sizeof(float4));
+    s.take(s.out, (size_t)kept * sizeof(float4), FDCM_FILL_PIXEL_OUT);
     clk.mark(kFitBegin);
     hipLaunchKernelGGL(k_line_fit, dim3((unsigned)cb), dim3(256), 0, nullptr, nc, c, (const int*)ccounts, s.out.as<float4>());
     clk.mark(kFit);
@@ -336,8 +336,8 @@ void lines_from_image_host(int device, const uint8_t* image, int width, int heig
     StageClock clk;
     const size_t n = (size_t)width * height;
     const uint8_t* d = s.upload(image, width, height, row_stride, on_device, &keys);
-    s.labels.reserve(n);
-    s.comps.reserve(n * 8);  // the edge kernels' parent and root words; the components' sums take their place afterwards
+    s.take(s.labels, n, FDCM_FILL_PIXEL_LABELS);
+    s.take(s.comps, n * 8, FDCM_FILL_PIXEL_COMPS);  // the edge kernels' parent and root words; the components' sums take their place afterwards
     clk.mark(kStart);
     launch_edge_labels(nullptr, d, width, height, row_stride, s.keys.as<float>(), (int)keys.size(), e, s.labels.as<uint8_t>(),
                        s.comps.as<int32_t>(), s.comps.as<uint32_t>() + n);

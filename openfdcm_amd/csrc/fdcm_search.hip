@@ -712,12 +712,6 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
     if (host_bins_needed && fm->m > 65535) throw std::string("host-side orientation bins need depth <= 65535");
     // ---- stage + upload: scene lines | sorted lengths | sorted idx | candidate offsets
     reserve_workspaces(fm, L, host_bins_needed);
-    char* hs = (char*)fm->search.stage.p;
-    std::memcpy(hs + L.o_lines, scene, (size_t)n_s * 16);
-    float* hl = (float*)(hs + L.o_len);
-    int* hi = (int*)(hs + L.o_idx);
-    for (int i = 0; i < n_s; ++i) { hl[i] = slen[sidx[i]]; hi[i] = (int)sidx[i]; }
-    std::memcpy(hs + L.o_coff, coff.data(), coff.size() * 8);
     // The search's preparation (scene upload, k_pairs, the work list) needs nothing of the volume: on a handle that has the GPU
     // to itself it goes to a second stream, beside the kernels of a build that is still running on `st` (a blocking
     // rebuild -> search spends ~25 us less); k_search waits for it through an event.  A slot of a frame pipeline keeps one
@@ -730,6 +724,26 @@ void run_search(fdcm_featuremap* fm, const fdcm_templates* t, const float* scene
         }
         sp = fm->prep_stream;
     }
+    // FDCM_POISON (fdcm_internal.h, "the tests' switches"): every workspace holds the word before the
+    // search's first write, each device buffer by a fill on the stream whose work touches it first.  search.out is the last
+    // host-output search's matches until the next such search overwrites them: it is filled here by that search alone.
+    if (test_switches().poison) {
+        SearchBuffers& s = fm->search;
+        if (!out_device) s.out.reserve(L.out);  // (what the call reserves further down)
+        if (!out_host) s.cnt.reserve(L.counters);
+        FDCM_HIP(hipStreamSynchronize(sp));  // (nothing queued still reads the pinned staging: the handle's last search or top-k waited for `st`)
+        poison_fill(s.scene, sp, FDCM_FILL_SCENE); poison_fill(s.pairs, sp, FDCM_FILL_PAIRS); poison_fill(s.work, sp, FDCM_FILL_WORK);
+        poison_fill(s.records, st, FDCM_FILL_RECORDS); poison_fill(s.flags, st, FDCM_FILL_FLAGS); poison_fill(s.counter, st, FDCM_FILL_COUNTER);
+        poison_fill(s.bins, st, FDCM_FILL_BINS);
+        if (!out_device) poison_fill(s.out, st, FDCM_FILL_OUT);
+        poison_fill(s.stage, FDCM_FILL_SEARCH_STAGE); poison_fill(s.bins_stage, FDCM_FILL_BINS_STAGE); poison_fill(s.cnt, FDCM_FILL_CNT);
+    }
+    char* hs = (char*)fm->search.stage.p;
+    std::memcpy(hs + L.o_lines, scene, (size_t)n_s * 16);
+    float* hl = (float*)(hs + L.o_len);
+    int* hi = (int*)(hs + L.o_idx);
+    for (int i = 0; i < n_s; ++i) { hl[i] = slen[sidx[i]]; hi[i] = (int)sidx[i]; }
+    std::memcpy(hs + L.o_coff, coff.data(), coff.size() * 8);
     FDCM_HIP(hipMemcpyAsync(fm->search.scene.p, hs, L.scene, hipMemcpyHostToDevice, sp));
     const int nchunks = L.nchunks;
     // keys live at the end of the build plan blob; for adopted volumes they are uploaded there too

@@ -135,6 +135,12 @@ void run_topk_device(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_ma
     char* d = (char*)fm->search.tail.p;
     // ---- denominators on the host (getTemplateLengths + the penalty's formula), uploaded through pinned staging
     const bool pen = penalty >= 0;
+    if (test_switches().poison) {  // the tail's workspace and the staging hold the word before the denominators are staged
+        if (pen) fm->search.stage.reserve(L.stage);
+        FDCM_HIP(hipStreamSynchronize(st));  // (nothing queued still reads the staging)
+        poison_fill(fm->search.tail, st, FDCM_FILL_TAIL);
+        poison_fill(fm->search.stage, FDCM_FILL_SEARCH_STAGE);
+    }
     if (pen) {
         std::vector<float> len((size_t)t->T);
         if (t->T) {
@@ -171,6 +177,7 @@ void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* ma
     *out = result_acquire(std::max<size_t>(1, (size_t)k) * sizeof(fdcm_match));
     if (k == 0) return;
     fm->search.tail_out.reserve(tail_layout(t->T, n, k).out);
+    poison_fill(fm->search.tail_out, fm->stream, FDCM_FILL_TAIL_OUT);  // (FDCM_POISON: the k best are written behind it)
     run_topk_device(fm, t, matches_device, n, base, penalty, tau, k, fm->search.tail_out.as<fdcm_match>());
     records_to_host(fm->stream, fm->search.tail_out.as<fdcm_match>(), k, *out);
     FDCM_HIP(hipStreamSynchronize(fm->stream));

@@ -94,3 +94,54 @@ def test_case_and_orders_are_deterministic(probe):
     assert sorted(o["shuffled"]) == sorted(names) and o["shuffled"] != o["listed"] and o["shuffled"] != o["reversed"]
     assert o["listed"][0].startswith("large")  # the large grid first
     assert probe.MAX_DET == 200
+
+
+def test_switch_comment_struct_and_reader_agree():
+    """The switches the header documents are the ones test_switches() reads and TestSwitches carries, and nothing else in the
+    library reads the environment; the buffers FDCM_POISON's paragraph promises are the ones the binding names, the header's
+    enum lists and tools/build_probe.py claims to use."""
+    import re
+    from openfdcm_amd import _capi
+    csrc = os.path.join(ROOT, "openfdcm_amd", "csrc")
+    with open(os.path.join(csrc, "fdcm_internal.h")) as f:
+        header = f.read()
+    block = header[header.index("the tests' switches"):header.index("const TestSwitches& test_switches();")]
+    comment, struct = block[:block.index("struct TestSwitches {")], block[block.index("struct TestSwitches {"):]
+    documented = set(re.findall(r"^//   (FDCM_[A-Z0-9_]+)", comment, re.M))
+    with open(os.path.join(csrc, "fdcm_host.cpp")) as f:
+        host = f.read()
+    body = host[host.index("const TestSwitches& test_switches() {"):host.index("static thread_local bool g_no_grow")]
+    read = set(re.findall(r'"(FDCM_[A-Z0-9_]+)"', body))
+    assert documented == read and len(read) >= 13, (sorted(documented - read), sorted(read - documented))
+    members = set()
+    for kind, names in re.findall(r"^\s*(bool|int|uint32_t)\s+([^;]+);", re.sub(r"//.*", "", struct), re.M):
+        members |= {n.strip() for n in names.split(",")}
+    assert members == set(re.findall(r"\br\.(\w+) = ", body)), (members, set(re.findall(r"\br\.(\w+) = ", body)))
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".cpp", ".h")) and name != "fdcm_host.cpp":
+            with open(os.path.join(csrc, name)) as f:
+                assert "getenv(" not in f.read(), name
+    # FDCM_POISON's buffers: the header's enum, the binding's names and the paragraph
+    with open(os.path.join(ROOT, "include", "fdcm.h")) as f:
+        public = f.read()
+    enum = public[public.index("enum fdcm_poison_buffer {"):public.index("FDCM_FILL_BUFFERS")]
+    names = [n.lower() for n in re.findall(r"FDCM_FILL_([A-Z_]+)", enum)]
+    assert tuple(names) == _capi.POISON_BUFFERS and "fdcm_selftest_poison_fills" in [s[0] for s in _capi.SYMBOLS]
+    poison = comment[comment.index("FDCM_POISON="):]
+    member = {"vol": "volume", "build_stage": "build.stage", "search_stage": "search.stage", "out": "search.out", "tail": "search.tail",
+              "tail_out": "search.tail_out", "eval": "search.eval", "eval_stage": "search.eval_stage", "cnt": " cnt"}
+    for n in names:
+        assert ("PixelScratch" if n.startswith("pixel_") else member.get(n, n)) in poison, n
+    for word in ("sweep.cost_chunks", "sweep.steals_off", "groups", "DESIGN.md"):
+        assert word in poison
+    spec = importlib.util.spec_from_file_location("build_probe", os.path.join(ROOT, "tools", "build_probe.py"))
+    bp = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bp)
+    assert set(bp.USED_BUFFERS) | set(bp.HOST_BINS_BUFFERS) == set(names) - {"eval", "eval_stage"}
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        design = f.read()
+    section = design[design.index("## 32."):]
+    for word in ("poison_fill", "fdcm_selftest_poison_fills", "tools/build_probe.py", "tests/test_gpu_build_workspace.py", "sweep.steals_off",
+                 "sweep.cost_chunks", "groups == (m, W)", "search.out", "PixelScratch", "coverage_stage"):
+        assert word in section, word
+    assert "tools/build_probe.py" in design[design.index("## 10. Tools and switches"):design.index("## 11.")]
