@@ -1176,6 +1176,54 @@ int fdcm_matches_detect(const fdcm_featuremap* fm, const fdcm_templates* templat
                         int32_t* indices_out /* max_detections, or NULL */, int32_t* boxes_out /* max_detections x 4, or NULL */,
                         float* matched_out /* max_detections, or NULL */);
 
+/* ---- Match lists: scene coverage and selection.  fdcm_scene_coverage and fdcm_scene_select for match records instead of
+ *      poses: the cue that runs from the scene to the template, for the records of fdcm_search.  Every definition not restated
+ *      here is "Scene coverage"'s and "Scene selection"'s, unchanged; "Match lists"' definitions apply unchanged: valid record,
+ *      posed lines P(r), bin of a posed line, admissible, footprint F(r).  The referee is tests/match_coverage_ref.py.
+ *      Frames.  The frame check is scene coverage's, with its messages: T = (bx, by) whole and non-negative, width + 2 bx == W
+ *      and height + 2 by == H.  A transform maps template coordinates to scene coordinates, so a record does not depend on the
+ *      map it was searched on; scene point = label pixel.
+ *      Segment of line i of record r: it joins the two map pixels whose integral values cost_i(r) subtracts -- each end point
+ *      of P(r) plus the scene translation, summed in float32 and truncated, exactly the pixel fdcm_matches_verify reads -- moved
+ *      to the label frame by -(bx, by).  Its bin is the posed line's: closestOrientation of atanf(dy / dx) of the posed line.
+ *      Window of r: F(r) at params->margin by the footprint arithmetic of fdcm_matches_footprints, cut to
+ *      [0, width - 1] x [0, height - 1]; it may be empty.
+ *      Explained: scene coverage's test on these segments, bins and window, exact in int64.
+ *      Counts: an admissible record gives (edges, explained); a valid record whose template has no lines is admissible with the
+ *      empty box and gives (0, 0); an invalid record or one that is not admissible gives (-1, -1), explains nothing and is never
+ *      a candidate.  Residual: scene coverage's, over the admissible records of the list.
+ *      Selection: E_j, S_0, the rule, the outputs and fdcm_select_params are scene selection's with "pose q" read as "record j";
+ *      the list order is the priority (fdcm_matches_detect with overlap_permille = 1000 returns a list that ascends by key).
+ *      matches: the forms of fdcm_matches_detect -- n host records (matches_on_device = 0), n records on the handle's device
+ *      (1), or NULL with matches_on_device = 0 for the records of the last fdcm_search on fm.  Labels and residual on the host
+ *      or the device (labels_on_device) are scene coverage's on_device, independent of the records' form.
+ *      Identities.  For a record {1, 0, x, 0, 1, y} with integers |x|, |y| < 2^24, wherever every x_i + float32(x) is exact,
+ *      counts and residual are fdcm_scene_coverage's for the pose (t, 0, x, y) with rot NULL and the same parameters, byte for
+ *      byte, and the selection is fdcm_scene_select's.  Scene coverage's and scene selection's identities carry over.  The
+ *      segment end points of an admissible record are the pixels at which fdcm_featuremap_evaluate reads the one-line template
+ *      {posed line i} at (0, 0).  Results are a function of the inputs alone: the three forms of matches give the same bytes,
+ *      and so do the host's bins (fdcm_orientation_bins_mode() == 1) wherever they equal the device's.
+ *      The device.  One pass, a wave per record and a lane per line (the verify pass's own posing, admissibility and box code),
+ *      writes every record's segments' lines, bins and window into the table scene coverage's kernels read; a scan makes the
+ *      strip offsets; only the number of strips comes to the host.  Coverage walks a long list in parts of at most 768 MB of
+ *      table, one record never cut; selection keeps its table whole, hence its bound on n.
+ *      FDCM_EINVAL, before any GPU work, each with its own message: n < 0; n > 2^20 (coverage) or n > 2^16 (select: cut a longer
+ *      list with fdcm_matches_detect first; so is a selection whose table, n x Lmax lines of 20 bytes, would exceed 2 GB);
+ *      matches_on_device not 0 or 1; matches NULL with n > 0 and matches_on_device = 1;
+ *      then everything fdcm_scene_coverage or fdcm_scene_select rejects about params, labels, sizes, sel, the outputs, the overlap
+ *      of residual and labels, the handles and the frame.  n = 0, an empty map or an empty template set give FDCM_OK, the
+ *      residual as a copy and *n_out = 0; counts_out is not written.  The calls block; concurrent callers of one feature map
+ *      take turns. ---- */
+int fdcm_matches_coverage(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int labels_on_device,
+                          const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int matches_on_device,
+                          int32_t tmpl_index_base, const fdcm_coverage_params* params, int32_t* counts_out /* n x 2 */,
+                          uint8_t* residual_out /* width * height where the labels are, or NULL */);
+int fdcm_matches_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int labels_on_device,
+                        const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int matches_on_device,
+                        int32_t tmpl_index_base, const fdcm_coverage_params* params, const fdcm_select_params* sel,
+                        int32_t* selected_out /* max_selected */, int32_t* counts_out /* max_selected x 3 */, int64_t* n_out,
+                        uint8_t* residual_out /* width * height where the labels are, or NULL */);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

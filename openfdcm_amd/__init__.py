@@ -1316,6 +1316,40 @@ def verify_matches(featuremap, templates, matches, line_caps=None, device_ptr=No
     return fm.verify_matches(tset, matches, device_ptr=device_ptr, n=n)
 
 
+def match_coverage(featuremap, labels, templates, matches, radius=2, bin_tolerance=1, margin=None, return_residual=False,
+                   device_ptr=None, n=0):
+    """scene_coverage for what search() returns: which edge pixels of labels each record explains, the record posed by its
+    own free transform (no angle table, no integer translation).  It tells a hit in texture (explained / edges low) from a
+    clean part.  labels is the label image the feature map was built from (a numpy array or a contiguous CUDA tensor; a
+    tensor gives the residual as a tensor); a transform maps template to scene coordinates and a scene point is a label
+    pixel, so the records may come from a search on any map of the scene.  matches follows detect_matches: a MatchList or a
+    record array, None for the records of the last search() on this feature map, or device_ptr and n for a device buffer.
+    radius, bin_tolerance and margin (None: the radius) are scene_coverage's; the window of a record is its footprint
+    (match_footprints) at the margin, cut to the image.  Returns the (n, 2) int32 counts (edges, explained), (-1, -1) for a
+    record whose posed lines leave the map or whose tmpl_idx is outside the list, and with return_residual also the labels
+    with 255 at every explained pixel."""
+    fm, tset = _device_map(featuremap), _template_cache.get(templates)
+    return fm.match_coverage(labels, tset, matches, radius=radius, bin_tolerance=bin_tolerance, margin=margin, residual=return_residual,
+                             device_ptr=device_ptr, n=n)
+
+
+def select_matches(featuremap, labels, templates, matches, radius=2, bin_tolerance=1, margin=None, min_coverage=0.0, min_new=0.5,
+                   min_pixels=1, max_selected=1024, return_residual=False, device_ptr=None, n=0):
+    """scene_select for what search() returns: greedy explain-away over match records, on the device.  Records conflict when
+    they claim the same edge pixels, not when their boxes overlap, so parts that interlock or lie in each other's notches are
+    both kept.  The list order is the priority: pass sort_matches(penalize(..)), or the output of
+    detect_matches(.., overlap=1.0), which ascends by key and has dropped what lies outside the map.  At most 2^16 records:
+    cut a longer list with detect_matches first.  labels, matches, radius, bin_tolerance and margin are match_coverage's;
+    min_coverage, min_new, min_pixels and max_selected are scene_select's, the shares taken in permille,
+    int(round(1000 * v)).  Returns (selected, counts): the (k,) int32 positions in matches, ascending, and (k, 3) int32 rows
+    (edges, explained, new); with return_residual also the labels with 255 at every claimed pixel.  matches[selected] are the
+    parts."""
+    fm, tset = _device_map(featuremap), _template_cache.get(templates)
+    return fm.select_matches(labels, tset, matches, radius=radius, bin_tolerance=bin_tolerance, margin=margin, min_coverage=min_coverage,
+                             min_new=min_new, min_pixels=min_pixels, max_selected=max_selected, residual=return_residual,
+                             device_ptr=device_ptr, n=n)
+
+
 def match_footprints(templates, matches, margin=0):
     """The (n, 4) int32 footprints x0, y0, x1, y1 of the posed lines of every record of a match list, as detect_matches uses
     them; (0, 0, -1, -1) for a record whose tmpl_idx is outside the list, a template without lines or a NaN end point."""

@@ -1426,6 +1426,18 @@ static void check_coverage_back(const fdcm_featuremap* fm, const uint8_t* labels
     }
 }
 
+// the rule's parameters and the outputs of a selection call (fdcm_scene_select, fdcm_matches_select)
+static void check_select_params(const fdcm_select_params* sel, const int32_t* selected_out, const int32_t* counts_out, const int64_t* n_out) {
+    require(sel != nullptr, "sel is null");
+    require(sel->min_coverage_permille >= 0 && sel->min_coverage_permille <= 1000, "min_coverage_permille must be in [0, 1000]");
+    require(sel->min_new_permille >= 0 && sel->min_new_permille <= 1000, "min_new_permille must be in [0, 1000]");
+    require(sel->min_pixels >= 1 && sel->min_pixels <= (1 << 24), "min_pixels must be in [1, 2^24]");
+    require(sel->max_selected >= 1 && sel->max_selected <= 4096, "max_selected must be in [1, 4096]");
+    require(selected_out != nullptr, "selected_out is null");
+    require(counts_out != nullptr, "counts_out is null");
+    require(n_out != nullptr, "n_out is null");
+}
+
 // Scene selection: include/fdcm.h, "Scene selection".  Scene coverage's checks around the call's own.
 int fdcm_scene_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int on_device,
                       const fdcm_templates* templates, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
@@ -1433,14 +1445,7 @@ int fdcm_scene_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_t 
                       int64_t* n_out, uint8_t* residual_out) {
     return guarded([&] {
         check_coverage_front(labels, width, height, rot, poses, n, params);
-        require(sel != nullptr, "sel is null");
-        require(sel->min_coverage_permille >= 0 && sel->min_coverage_permille <= 1000, "min_coverage_permille must be in [0, 1000]");
-        require(sel->min_new_permille >= 0 && sel->min_new_permille <= 1000, "min_new_permille must be in [0, 1000]");
-        require(sel->min_pixels >= 1 && sel->min_pixels <= (1 << 24), "min_pixels must be in [1, 2^24]");
-        require(sel->max_selected >= 1 && sel->max_selected <= 4096, "max_selected must be in [1, 4096]");
-        require(selected_out != nullptr, "selected_out is null");
-        require(counts_out != nullptr, "counts_out is null");
-        require(n_out != nullptr, "n_out is null");
+        check_select_params(sel, selected_out, counts_out, n_out);
         float bx, by;
         check_coverage_back(fm, labels, width, height, templates, rot, poses, n, params, residual_out, &bx, &by);
         run_scene_select(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, on_device != 0, (int)bx, (int)by, templates, rot,
@@ -1458,6 +1463,62 @@ int fdcm_scene_coverage(const fdcm_featuremap* fm, const uint8_t* labels, int64_
         check_coverage_back(fm, labels, width, height, templates, rot, poses, n, params, residual_out, &bx, &by);
         run_scene_coverage(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, on_device != 0, (int)bx, (int)by, templates, rot,
                            poses, n, *params, counts_out, residual_out);
+    });
+}
+
+// Match lists: scene coverage and selection (include/fdcm.h).  The match calls' checks of the list with the call's own bound
+// on n, then scene coverage's of the parameters and the image; after the call's own outputs the residual, the handles and the
+// frame.  max_n: 2^20 (coverage) or 2^16 (select).
+static void check_matches_coverage_front(const uint8_t* labels, int64_t width, int64_t height, const fdcm_match* matches, int64_t n,
+                                         int on_device, bool select, const fdcm_coverage_params* params) {
+    require(n >= 0, "n is negative");
+    if (select)
+        require(n <= ((int64_t)1 << 16), "n must be at most 2^16: cut a longer list with fdcm_matches_detect first");
+    else
+        require(n <= ((int64_t)1 << 20), "n must be at most 2^20");
+    require(on_device == 0 || on_device == 1, "on_device must be 0 or 1");
+    require(!(on_device == 1 && n > 0 && !matches), "matches is null");
+    check_coverage_front(labels, width, height, nullptr, nullptr, 0, params);
+}
+
+// the records of the last search (matches NULL with on_device = 0) under the call's bound
+static void last_search_matches_bounded(const fdcm_featuremap* fm, const fdcm_match*& matches, int64_t& n, int& on_device, bool select) {
+    if (matches || on_device) return;
+    last_search_matches(fm, matches, n, on_device);
+    if (select)
+        require(n <= ((int64_t)1 << 16), "n must be at most 2^16: cut a longer list with fdcm_matches_detect first");
+    else
+        require(n <= ((int64_t)1 << 20), "n must be at most 2^20");
+}
+
+int fdcm_matches_coverage(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int labels_on_device,
+                          const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int matches_on_device,
+                          int32_t tmpl_index_base, const fdcm_coverage_params* params, int32_t* counts_out, uint8_t* residual_out) {
+    return guarded([&] {
+        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, false, params);
+        require(n == 0 || counts_out, "counts_out is null");
+        float bx, by;
+        check_coverage_back(fm, labels, width, height, templates, nullptr, nullptr, 0, params, residual_out, &bx, &by);
+        last_search_matches_bounded(fm, matches, n, matches_on_device, false);
+        require(n == 0 || counts_out, "counts_out is null");
+        run_matches_coverage(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, labels_on_device != 0, (int)bx, (int)by,
+                             templates, matches, n, matches_on_device != 0, tmpl_index_base, *params, counts_out, residual_out);
+    });
+}
+
+int fdcm_matches_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int labels_on_device,
+                        const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int matches_on_device,
+                        int32_t tmpl_index_base, const fdcm_coverage_params* params, const fdcm_select_params* sel, int32_t* selected_out,
+                        int32_t* counts_out, int64_t* n_out, uint8_t* residual_out) {
+    return guarded([&] {
+        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, true, params);
+        check_select_params(sel, selected_out, counts_out, n_out);
+        float bx, by;
+        check_coverage_back(fm, labels, width, height, templates, nullptr, nullptr, 0, params, residual_out, &bx, &by);
+        last_search_matches_bounded(fm, matches, n, matches_on_device, true);
+        run_matches_select(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, labels_on_device != 0, (int)bx, (int)by,
+                           templates, matches, n, matches_on_device != 0, tmpl_index_base, *params, *sel, selected_out, counts_out, n_out,
+                           residual_out);
     });
 }
 

@@ -26,11 +26,25 @@
 //   k_select_decide     a thread per pose: takes the recount, drops the pose when it fails the rule's test, and the smallest
 //                       survivor's index becomes sel[round + 1] (atomicMin, one per wave).  Its first form makes S_0.
 //
+// Both run as well on match records (include/fdcm.h, "Match lists: scene coverage and selection"), whose table is made on the
+// device:
+//
+//   k_matches_table     a wave per record, a lane per line in rounds of 64, as k_matches_verify: poses the template's resident
+//                       lines with the record's matrix, decides admissibility and reduces the box (match_frame, fdcm_score.h,
+//                       the verify kernel's own pass 1), computes the bins (atanf_glibc + closest_orientation, or the host's),
+//                       and writes the record's CoverageLines, its CovPose with x = y = 0 and the window F(r) cut to the image,
+//                       its number of strips and its counts' initial value, (0, 0) or (-1, -1).
+//   k_strip_scan        one workgroup: item0 = the exclusive prefix sums of the strips, their total and their largest.
+//
+// Entries without strips stay in the table: pose_of_item returns the last entry whose first item is <= the item, and an entry
+// without strips that shares its offset with its successor is never the last such entry.
+//
 // All arithmetic of the decision is integer; the float adds of step 1 are the cost rule's own (-ffp-contract=off as everywhere).
 #include <algorithm>
 #include <cstring>
 
 #include "fdcm_internal.h"
+#include "fdcm_score.h"
 
 namespace fdcm {
 
@@ -319,6 +333,103 @@ __global__ void __launch_bounds__(256) k_select_decide(const CovPose* __restrict
     if (any && (threadIdx.x & 63) == 0) atomicMin(next, i + (int)__builtin_ctzll(any));
 }
 
+// ---------------------------------------------------------------------------------------------- the table of a match list
+struct TableArgs {
+    const float4* tlines;  // the set's resident lines and offsets
+    const long long* toff;
+    const float* keys;            // the map's m orientation keys
+    const unsigned short* bins;   // [record][Lmax] bins from the host libm, or null
+    const fdcm_match* rec;        // the part's records
+    int n, base, T, Lmax, m, W, H;
+    float tx, ty;
+    int margin, width, height;
+    CoverageLine* lines;  // [record][Lmax]
+    CovPose* poses;
+    int* strips;
+    int* counts;  // [record][2]
+};
+
+__global__ void __launch_bounds__(256) k_matches_table(const TableArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int j = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (j >= a.n) return;  // wave-uniform
+    const fdcm_match R = a.rec[j];
+    const long long t = (long long)R.tmpl_idx - (long long)a.base;
+    CovPose P{j * a.Lmax, 0, 0, 0, 0, 0, -1, -1, 1, {0, 0, 0}};
+    int strips = 0, count = -1;  // not valid or not admissible: (-1, -1), no strips
+    if (t >= 0 && t < a.T) {
+        const long long l0 = a.toff[t];
+        const int nl = (int)(a.toff[t + 1] - l0);
+        const MatchTransform M{R.transform[0], R.transform[1], R.transform[2], R.transform[3], R.transform[4], R.transform[5]};
+        const float offx = a.tx + 0.f, offy = a.ty + 0.f;  // sceneTranslation + translation, the translation (0, 0)
+        const MatchFrame F = match_frame(a.tlines, l0, nl, M, offx, offy, a.W, a.H, a.margin, lane);
+        if (F.adm) {  // wave-uniform
+            count = 0;
+            const int x0 = max(0, F.box.x), y0 = max(0, F.box.y), x1 = min(a.width - 1, F.box.z), y1 = min(a.height - 1, F.box.w);
+            if (x0 <= x1 && y0 <= y1) {  // (an empty window: (0, 0), and nobody reads its lines)
+                for (int i = lane; i < nl; i += 64) {
+                    const float4 p = match_pose_line(M, a.tlines[l0 + i]);
+                    int bin;
+                    if (a.bins) {
+                        bin = (int)a.bins[(size_t)j * (size_t)a.Lmax + i];
+                    } else {
+                        const float angle = atanf_glibc((p.w - p.y) / (p.z - p.x));  // getAngle, math.h:295-299
+                        bin = closest_orientation(a.keys, a.m, angle);               // dt3cpu.cpp:144-148
+                    }
+                    a.lines[(size_t)P.line0 + i] = CoverageLine{p.x, p.y, p.z, p.w, bin};
+                }
+                P.n = nl;
+                P.wx0 = x0; P.wy0 = y0; P.wx1 = x1; P.wy1 = y1;
+                P.rows = max(1, kCovStripPixels / (x1 - x0 + 1));
+                strips = (y1 - y0 + P.rows) / P.rows;
+            }
+        }
+    }
+    if (lane == 0) {
+        a.poses[j] = P;
+        a.strips[j] = strips;
+        a.counts[2 * j] = a.counts[2 * j + 1] = count;
+    }
+}
+
+// One workgroup: item0[i] = strips[0] + .. + strips[i - 1] for i <= n, out[0] = item0[n], out[1] = the largest of the strips.
+__global__ void __launch_bounds__(1024) k_strip_scan(const int* __restrict__ strips, int n, long long* __restrict__ item0,
+                                                     long long* __restrict__ out) {
+    __shared__ int wsum[16], wmax[16];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long carry = 0;
+    int mx = 0;
+    for (int base = 0; base < n; base += 1024) {  // uniform
+        const int i = base + tid;
+        const int v = i < n ? strips[i] : 0;  // (<= 4096 each: a wave's sum stays an int)
+        int inc = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int u = __shfl_up(inc, d);
+            if (lane >= d) inc += u;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        long long before = 0, all = 0;
+        for (int w = 0; w < 16; ++w) {
+            if (w < wave) before += wsum[w];
+            all += wsum[w];
+        }
+        if (i < n) item0[i] = carry + before + (long long)(inc - v);
+        carry += all;
+        mx = max(mx, v);
+        __syncthreads();
+    }
+    for (int d = 32; d >= 1; d >>= 1) mx = max(mx, __shfl_xor(mx, d));
+    if (lane == 0) wmax[wave] = mx;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w) mx = max(mx, wmax[w]);
+        item0[n] = carry;
+        out[0] = carry;
+        out[1] = mx;
+    }
+}
+
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // What both calls make of a checked pose list: the pairs, one CovPose per admissible pose with a window that holds a pixel, in
@@ -442,6 +553,44 @@ void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, i
 // end leave at their first load.
 constexpr int kSelBatch = 64;
 
+// The launches of the rule on a table that is on the device with its counters (zero, or what k_matches_table left), sel at
+// kSelNone and fresh at 0: one k_scene_coverage launch for the counts, k_select_decide's first form for S_0, and per round
+// claim, recount, decide.  items: the table's strips; strips: of the entry with most.
+void select_rounds(hipStream_t st, const SelArgs& a, long long items, long long strips, size_t ms, const fdcm_select_params& sel, int* d_cnt,
+                   int* d_sel, int* d_new, int* d_fresh, int* d_cur, uint8_t* d_alive, uint8_t* plane) {
+    const unsigned pose_wgs = (unsigned)(((size_t)a.n_poses + 255) / 256);
+    for (long long base = 0; base < items; base += kCovMaxGrid) {
+        const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
+        hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, a.labels, a.width, a.height, a.m, a.tx, a.ty, a.bx, a.by,
+                           a.radius, a.tol, a.lines, a.poses, a.item0, a.n_poses, base, d_cnt, (uint8_t*)nullptr);
+        FDCM_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_select_decide, dim3(pose_wgs), dim3(256), 0, st, a.poses, a.n_poses, d_cnt, d_sel, -1, sel, d_alive, d_fresh, d_cur,
+                       d_sel);
+    FDCM_HIP(hipGetLastError());
+    const int rounds = (int)std::min(ms, (size_t)a.n_poses);  // a round accepts a pose of the table or finds the list ended
+    for (int r = 0; r < rounds;) {
+        for (const int r1 = std::min(rounds, r + kSelBatch); r < r1; ++r) {
+            hipLaunchKernelGGL(k_select_claim, dim3((unsigned)strips), dim3(kCovThreads), 0, st, a, d_sel, r, d_cur, d_new, plane);
+            FDCM_HIP(hipGetLastError());
+            if (r + 1 == rounds) continue;  // the last pose the call may accept: nobody asks who is next
+            for (long long base = 0; base < items; base += kCovMaxGrid) {
+                const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
+                hipLaunchKernelGGL(k_select_recount, dim3(grid), dim3(kCovThreads), 0, st, a, base, d_sel, r, d_alive, d_fresh, plane);
+                FDCM_HIP(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_select_decide, dim3(pose_wgs), dim3(256), 0, st, a.poses, a.n_poses, d_cnt, d_sel, r, sel, d_alive, d_fresh,
+                               d_cur, d_sel + r + 1);
+            FDCM_HIP(hipGetLastError());
+        }
+        if (r == rounds) break;
+        int next = kSelNone;  // the pose round r would accept
+        FDCM_HIP(hipMemcpyAsync(&next, d_sel + r, sizeof(int), hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+        if (next >= a.n_poses) break;
+    }
+}
+
 // The arguments are checked (fdcm_capi.cpp).  run_scene_coverage's preparation and buffers; then one k_scene_coverage launch
 // for the counts, k_select_decide's first form for S_0, and per round claim, recount, decide.
 void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
@@ -495,37 +644,7 @@ void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int
     const long long items = T.item0.back();
     long long strips = 1;  // of the pose with most
     for (size_t i = 0; i < nt; ++i) strips = std::max(strips, T.item0[i + 1] - T.item0[i]);
-    const unsigned pose_wgs = (unsigned)((nt + 255) / 256);
-    for (long long base = 0; base < items; base += kCovMaxGrid) {
-        const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
-        hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, a.labels, a.width, a.height, a.m, a.tx, a.ty, a.bx, a.by,
-                           a.radius, a.tol, a.lines, a.poses, a.item0, a.n_poses, base, d_cnt, (uint8_t*)nullptr);
-        FDCM_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_select_decide, dim3(pose_wgs), dim3(256), 0, st, a.poses, a.n_poses, d_cnt, d_sel, -1, sel, d_alive, d_fresh, d_cur,
-                       d_sel);
-    FDCM_HIP(hipGetLastError());
-    const int rounds = (int)std::min(ms, nt);  // a round accepts a pose of the table or finds the list ended
-    for (int r = 0; r < rounds;) {
-        for (const int r1 = std::min(rounds, r + kSelBatch); r < r1; ++r) {
-            hipLaunchKernelGGL(k_select_claim, dim3((unsigned)strips), dim3(kCovThreads), 0, st, a, d_sel, r, d_cur, d_new, plane);
-            FDCM_HIP(hipGetLastError());
-            if (r + 1 == rounds) continue;  // the last pose the call may accept: nobody asks who is next
-            for (long long base = 0; base < items; base += kCovMaxGrid) {
-                const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
-                hipLaunchKernelGGL(k_select_recount, dim3(grid), dim3(kCovThreads), 0, st, a, base, d_sel, r, d_alive, d_fresh, plane);
-                FDCM_HIP(hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_select_decide, dim3(pose_wgs), dim3(256), 0, st, a.poses, a.n_poses, d_cnt, d_sel, r, sel, d_alive, d_fresh,
-                               d_cur, d_sel + r + 1);
-            FDCM_HIP(hipGetLastError());
-        }
-        if (r == rounds) break;
-        int next = kSelNone;  // the pose round r would accept
-        FDCM_HIP(hipMemcpyAsync(&next, d_sel + r, sizeof(int), hipMemcpyDeviceToHost, st));
-        FDCM_HIP(hipStreamSynchronize(st));
-        if (next >= (int)nt) break;
-    }
+    select_rounds(st, a, items, strips, ms, sel, d_cnt, d_sel, d_new, d_fresh, d_cur, d_alive, plane);
     FDCM_HIP(hipMemcpyAsync(h, d + o_cnt, o_fresh - o_cnt, hipMemcpyDeviceToHost, st));  // (the staging is free again)
     if (residual && !on_device) FDCM_HIP(hipMemcpyAsync(residual, plane, npix, hipMemcpyDeviceToHost, st));
     FDCM_HIP(hipStreamSynchronize(st));
@@ -536,6 +655,201 @@ void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int
     for (; k < ms && h_sel[k] < (int32_t)nt; ++k) {
         const int32_t i = h_sel[k];
         selected[k] = (int32_t)T.pose_of[i];
+        counts[3 * k] = h_cnt[2 * i];
+        counts[3 * k + 1] = h_cnt[2 * i + 1];
+        counts[3 * k + 2] = h_new[k];
+    }
+    *n_out = (int64_t)k;
+}
+
+// ---------------------------------------------------------------------------------------------- match lists
+namespace {
+
+constexpr size_t kCovPartBytes = (size_t)768 << 20;  // what a part's table may take (lines, host bins, poses, strips, offsets)
+
+size_t table_record_bytes(const fdcm_templates* t, bool host_bins) {
+    return (size_t)t->max_lines * (sizeof(CoverageLine) + (host_bins ? 2 : 0)) + sizeof(CovPose) + sizeof(int) + sizeof(long long);
+}
+
+// What both calls on match lists lay out for a table of pn records, from `at` on: host bins | lines | poses | strips | item
+// offsets | total and largest
+struct TableLayout {
+    size_t o_bins, o_lines, o_tab, o_strips, o_item, o_tot, end;
+    TableLayout(size_t at, size_t pn, size_t Lmax, bool host_bins) {
+        o_bins = at;
+        o_lines = o_bins + (host_bins ? al256(pn * Lmax * 2) : 0);
+        o_tab = o_lines + al256(pn * Lmax * sizeof(CoverageLine));
+        o_strips = o_tab + al256(pn * sizeof(CovPose));
+        o_item = o_strips + al256(pn * sizeof(int));
+        o_tot = o_item + al256((pn + 1) * sizeof(long long));
+        end = o_tot + 256;
+    }
+};
+
+// Queues k_matches_table and k_strip_scan for the records [q0, q0 + cnt) of the list at d_rec (the host bins of the part are
+// uploaded through h_bins first), waits, and returns the part's strips in all and of the entry with most.
+void make_table(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* d_rec, size_t q0, size_t cnt, int32_t base, int margin,
+                int width, int height, const std::vector<unsigned short>& bins, char* d, char* h_bins, const TableLayout& L, int* d_cnt,
+                long long* items, long long* most) {
+    hipStream_t st = fm->stream;
+    const size_t Lmax = (size_t)t->max_lines;
+    if (!bins.empty() && Lmax) {
+        std::memcpy(h_bins, bins.data() + q0 * Lmax, cnt * Lmax * 2);
+        FDCM_HIP(hipMemcpyAsync(d + L.o_bins, h_bins, cnt * Lmax * 2, hipMemcpyHostToDevice, st));
+    }
+    TableArgs a{};
+    a.tlines = t->d_lines.as<float4>(); a.toff = t->d_offsets.as<long long>();
+    a.keys = (const float*)((const char*)fm->build.plan.p + fm->off_keys);
+    a.bins = bins.empty() ? nullptr : (const unsigned short*)(d + L.o_bins);
+    a.rec = d_rec + q0;
+    a.n = (int)cnt; a.base = base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax;
+    a.m = (int)fm->m; a.W = (int)fm->W; a.H = (int)fm->H; a.tx = fm->tx; a.ty = fm->ty;
+    a.margin = margin; a.width = width; a.height = height;
+    a.lines = (CoverageLine*)(d + L.o_lines); a.poses = (CovPose*)(d + L.o_tab); a.strips = (int*)(d + L.o_strips);
+    a.counts = d_cnt + 2 * q0;
+    hipLaunchKernelGGL(k_matches_table, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, a);
+    FDCM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_strip_scan, dim3(1), dim3(1024), 0, st, (const int*)a.strips, (int)cnt, (long long*)(d + L.o_item),
+                       (long long*)(d + L.o_tot));
+    FDCM_HIP(hipGetLastError());
+    long long tot[2] = {0, 0};
+    FDCM_HIP(hipMemcpyAsync(tot, d + L.o_tot, sizeof tot, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    *items = tot[0];
+    *most = tot[1];
+}
+
+}  // namespace
+
+// Scene coverage of match records (include/fdcm.h, "Match lists: scene coverage and selection"): the arguments are checked
+// (fdcm_capi.cpp).  The list is walked in parts of at most kCovPartBytes of table (FDCM_COVERAGE_PART: of that many records):
+// per part the table pass, the scan, one download of the number of items, and k_scene_coverage on it; the counts are per
+// record and the residual is an OR, so parts compose.  Only host records and the host's bins go up; counts and residual come down.
+void run_matches_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                          const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
+                          const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual) {
+    const size_t npix = (size_t)width * (size_t)height;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    FDCM_HIP(hipSetDevice(fm->device));
+    ensure_stream(fm);
+    hipStream_t st = fm->stream;
+    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return copy_labels(labels, npix, on_device, residual, st);
+    const size_t N = (size_t)n, Lmax = (size_t)t->max_lines;
+    std::vector<unsigned short> bins;
+    matches_host_bins(fm, t, matches, n, matches_on_device, base, bins);
+    size_t pn = std::max<size_t>(1, std::min(N, kCovPartBytes / table_record_bytes(t, !bins.empty())));
+    if (test_switches().coverage_part > 0) pn = std::min(pn, (size_t)test_switches().coverage_part);
+    // device: records (host callers) | the part's table | counters | labels (host callers) | residual (host callers)
+    const TableLayout L(matches_on_device ? 0 : al256(N * sizeof(fdcm_match)), pn, Lmax, !bins.empty());
+    const size_t o_cnt = L.end, o_lab = o_cnt + al256(N * 2 * sizeof(int32_t)), o_res = o_lab + (on_device ? 0 : al256(npix)),
+                 total = o_res + (on_device || !residual ? 0 : al256(npix));
+    // staging: records (host callers) | the part's bins; then the counters
+    const size_t s_bins = matches_on_device ? 0 : al256(N * sizeof(fdcm_match));
+    fm->coverage.reserve(total);
+    fm->coverage_stage.reserve(std::max(s_bins + al256(bins.empty() ? 0 : pn * Lmax * 2), N * 2 * sizeof(int32_t)));
+    poison_coverage(fm);
+    char* d = (char*)fm->coverage.p;
+    char* h = (char*)fm->coverage_stage.p;
+    const uint8_t* d_labels = labels;
+    uint8_t* d_res = residual;
+    if (!on_device) {
+        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
+        d_labels = (const uint8_t*)(d + o_lab);
+        d_res = residual ? (uint8_t*)(d + o_res) : nullptr;
+    }
+    const fdcm_match* d_rec = matches;
+    if (!matches_on_device) {
+        std::memcpy(h, matches, N * sizeof(fdcm_match));
+        FDCM_HIP(hipMemcpyAsync(d, h, N * sizeof(fdcm_match), hipMemcpyHostToDevice, st));
+        d_rec = (const fdcm_match*)d;
+    }
+    if (d_res) FDCM_HIP(hipMemcpyAsync(d_res, d_labels, npix, hipMemcpyDeviceToDevice, st));
+    int* d_cnt = (int*)(d + o_cnt);
+    for (size_t q0 = 0; q0 < N; q0 += pn) {
+        const size_t cnt = std::min(pn, N - q0);
+        long long items = 0, most = 0;
+        make_table(fm, t, d_rec, q0, cnt, base, (int)params.margin, width, height, bins, d, h + s_bins, L, d_cnt, &items, &most);
+        for (long long ib = 0; ib < items; ib += kCovMaxGrid) {
+            const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - ib);
+            hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by,
+                               (int)params.radius, (int)params.bin_tolerance, (const CoverageLine*)(d + L.o_lines),
+                               (const CovPose*)(d + L.o_tab), (const long long*)(d + L.o_item), (int)cnt, ib, d_cnt + 2 * q0, d_res);
+            FDCM_HIP(hipGetLastError());
+        }
+    }
+    FDCM_HIP(hipMemcpyAsync(h, d_cnt, N * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));  // (the staging is free: every part has waited)
+    if (!on_device && residual) FDCM_HIP(hipMemcpyAsync(residual, d_res, npix, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    std::memcpy(counts, h, N * 2 * sizeof(int32_t));
+}
+
+// Scene selection of match records: the arguments are checked (fdcm_capi.cpp), n <= 2^16.  The table is whole, every record an
+// entry: a record that is not admissible holds (-1, -1) and one without a window (0, 0), so neither is in S_0, and the indices
+// the rounds accept are the list's own.  Then run_scene_select's rounds.
+void run_matches_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                        const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
+                        const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
+                        int64_t* n_out, uint8_t* residual) {
+    const size_t npix = (size_t)width * (size_t)height;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    FDCM_HIP(hipSetDevice(fm->device));
+    ensure_stream(fm);
+    hipStream_t st = fm->stream;
+    *n_out = 0;
+    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return copy_labels(labels, npix, on_device, residual, st);
+    const size_t N = (size_t)n, Lmax = (size_t)t->max_lines, ms = (size_t)sel.max_selected;
+    if (N * table_record_bytes(t, orientation_bins_on_host()) > ((size_t)2 << 30))  // (FDCM_EINVAL, before any GPU work)
+        throw std::string("the selection's table, n records of max_lines lines each, would exceed 2 GB: cut the list with "
+                          "fdcm_matches_detect first");
+    std::vector<unsigned short> bins;
+    matches_host_bins(fm, t, matches, n, matches_on_device, base, bins);
+    // device: records (host callers) | the table | counters, sel, sel_new (what comes down) | fresh | cur | alive | labels (host
+    // callers) | claim plane (unless the caller's residual is on the device)
+    const TableLayout L(matches_on_device ? 0 : al256(N * sizeof(fdcm_match)), N, Lmax, !bins.empty());
+    const size_t o_cnt = L.end, o_sel = o_cnt + al256(N * 2 * sizeof(int32_t)), o_new = o_sel + al256(ms * sizeof(int32_t)),
+                 o_fresh = o_new + al256(ms * sizeof(int32_t)), o_cur = o_fresh + al256(N * sizeof(int32_t)),
+                 o_alive = o_cur + al256(N * sizeof(int32_t)), o_lab = o_alive + al256(N), o_plane = o_lab + (on_device ? 0 : al256(npix)),
+                 total = o_plane + (on_device && residual ? 0 : al256(npix));
+    const size_t s_bins = matches_on_device ? 0 : al256(N * sizeof(fdcm_match));
+    fm->coverage.reserve(total);
+    fm->coverage_stage.reserve(std::max(s_bins + al256(bins.empty() ? 0 : N * Lmax * 2), o_fresh - o_cnt));
+    poison_coverage(fm);
+    char* d = (char*)fm->coverage.p;
+    char* h = (char*)fm->coverage_stage.p;
+    const uint8_t* d_labels = labels;
+    if (!on_device) {
+        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
+        d_labels = (const uint8_t*)(d + o_lab);
+    }
+    uint8_t* plane = on_device && residual ? residual : (uint8_t*)(d + o_plane);
+    const fdcm_match* d_rec = matches;
+    if (!matches_on_device) {
+        std::memcpy(h, matches, N * sizeof(fdcm_match));
+        FDCM_HIP(hipMemcpyAsync(d, h, N * sizeof(fdcm_match), hipMemcpyHostToDevice, st));
+        d_rec = (const fdcm_match*)d;
+    }
+    FDCM_HIP(hipMemsetAsync(d + o_sel, 0x7f, ms * sizeof(int32_t), st));  // kSelNone
+    FDCM_HIP(hipMemsetAsync(d + o_fresh, 0, N * sizeof(int32_t), st));
+    FDCM_HIP(hipMemcpyAsync(plane, d_labels, npix, hipMemcpyDeviceToDevice, st));
+    int* d_cnt = (int*)(d + o_cnt);
+    long long items = 0, most = 0;
+    make_table(fm, t, d_rec, 0, N, base, (int)params.margin, width, height, bins, d, h + s_bins, L, d_cnt, &items, &most);
+    if (items > 0) {  // (else nothing explains a pixel: nothing is accepted, and the plane is the labels)
+        const SelArgs a{d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by, (int)params.radius, (int)params.bin_tolerance,
+                        (const CoverageLine*)(d + L.o_lines), (const CovPose*)(d + L.o_tab), (const long long*)(d + L.o_item), (int)N};
+        select_rounds(st, a, items, most, ms, sel, d_cnt, (int*)(d + o_sel), (int*)(d + o_new), (int*)(d + o_fresh), (int*)(d + o_cur),
+                      (uint8_t*)(d + o_alive), plane);
+    }
+    FDCM_HIP(hipMemcpyAsync(h, d + o_cnt, o_fresh - o_cnt, hipMemcpyDeviceToHost, st));  // (the staging is free again)
+    if (residual && !on_device) FDCM_HIP(hipMemcpyAsync(residual, plane, npix, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    const int32_t* h_cnt = (const int32_t*)h;
+    const int32_t* h_sel = (const int32_t*)(h + (o_sel - o_cnt));
+    const int32_t* h_new = (const int32_t*)(h + (o_new - o_cnt));
+    size_t k = 0;
+    for (; k < ms && h_sel[k] < (int32_t)N; ++k) {
+        const int32_t i = h_sel[k];
+        selected[k] = i;
         counts[3 * k] = h_cnt[2 * i];
         counts[3 * k + 1] = h_cnt[2 * i + 1];
         counts[3 * k + 2] = h_new[k];

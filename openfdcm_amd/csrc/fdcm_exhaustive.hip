@@ -3354,13 +3354,6 @@ struct MatchesArgs {
     int4* boxes;
 };
 
-// One side of footprint(): floor(v) + d in int64, clamped (v is not NaN).
-__device__ __forceinline__ int matches_side(float v, int d) {
-    const float f = fminf(fmaxf(floorf(v), -1099511627776.f), 1099511627776.f);
-    const long long lim = 1ll << 25;
-    return (int)min(max((long long)f + d, -lim), lim);
-}
-
 template <bool BUF32, bool CAP>
 __global__ void __launch_bounds__(256) k_matches_verify(const MatchesArgs a) {
     const int lane = threadIdx.x & 63;
@@ -3381,31 +3374,12 @@ __global__ void __launch_bounds__(256) k_matches_verify(const MatchesArgs a) {
     }
     const long long l0 = a.toff[t];
     const int nl = (int)(a.toff[t + 1] - l0);
-    const float M0 = R.transform[0], M1 = R.transform[1], M2 = R.transform[2], M3 = R.transform[3], M4 = R.transform[4],
-                M5 = R.transform[5];
+    const MatchTransform M{R.transform[0], R.transform[1], R.transform[2], R.transform[3], R.transform[4], R.transform[5]};
     const float offx = a.tx + 0.f, offy = a.ty + 0.f;  // sceneTranslation + translation, the translation (0, 0)
-    // ---- pass 1: admissibility and the box
-    bool inside = true, has_nan = false;
-    float mnx = f_inf(), mny = f_inf(), mxx = -f_inf(), mxy = -f_inf();
-    for (int i = lane; i < nl; i += 64) {
-        const float4 p = a.tlines[l0 + i];
-        const float x[2] = {(M0 * p.x + M1 * p.y) + M2, (M0 * p.z + M1 * p.w) + M2};
-        const float y[2] = {(M3 * p.x + M4 * p.y) + M5, (M3 * p.z + M4 * p.w) + M5};
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const float px = x[c] + offx, py = y[c] + offy;
-            inside = inside && px > -1.f && px < (float)a.W && py > -1.f && py < (float)a.H;  // false for NaN
-            has_nan = has_nan || f_isnan(x[c]) || f_isnan(y[c]);
-            mnx = std_min(mnx, x[c]); mxx = std_max(mxx, x[c]);
-            mny = std_min(mny, y[c]); mxy = std_max(mxy, y[c]);
-        }
-    }
-    const bool adm = __ballot(!inside) == 0;
-    const bool any_nan = __ballot(has_nan) != 0;
-    mnx = wave_min_f(mnx); mny = wave_min_f(mny); mxx = wave_max_f(mxx); mxy = wave_max_f(mxy);
-    int4 box = make_int4(0, 0, -1, -1);
-    if (nl > 0 && !any_nan)
-        box = make_int4(matches_side(mnx, -a.margin), matches_side(mny, -a.margin), matches_side(mxx, a.margin), matches_side(mxy, a.margin));
+    // ---- pass 1: admissibility and the box (fdcm_score.h)
+    const MatchFrame F = match_frame(a.tlines, l0, nl, M, offx, offy, a.W, a.H, a.margin, lane);
+    const bool adm = F.adm;
+    const int4 box = F.box;
     // ---- pass 2: costs, s in Eigen's order, ML in line order
     const VolRef V = make_volref(a.vol, a.SL, a.m, BUF32);
     const unsigned uH = (unsigned)a.H;
@@ -3416,9 +3390,8 @@ __global__ void __launch_bounds__(256) k_matches_verify(const MatchesArgs a) {
         float cost = f_nan(), cap = f_inf(), len = 0.f;
         if (i < nl) {
             if (adm) {
-                const float4 p = a.tlines[l0 + i];
-                const float x1 = (M0 * p.x + M1 * p.y) + M2, y1 = (M3 * p.x + M4 * p.y) + M5;
-                const float x2 = (M0 * p.z + M1 * p.w) + M2, y2 = (M3 * p.z + M4 * p.w) + M5;
+                const float4 p = match_pose_line(M, a.tlines[l0 + i]);
+                const float x1 = p.x, y1 = p.y, x2 = p.z, y2 = p.w;
                 int bin;
                 if (a.bins) {
                     bin = (int)a.bins[(size_t)j * (size_t)a.Lmax + i];
@@ -3532,6 +3505,36 @@ void matches_footprints(const fdcm_templates* t, const fdcm_match* matches, int6
     }
 }
 
+// Host-libm bins (fdcm_orientation_bins_mode() == 1; empty otherwise): the bins of every posed line as [record][max_lines], on
+// the host, from host records; device records cost one download on the handle's stream.
+void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
+                       std::vector<unsigned short>& bins) {
+    bins.clear();
+    if (!orientation_bins_on_host()) return;
+    if (fm->m > 65535) throw std::string("host-side orientation bins need depth <= 65535");
+    const size_t N = (size_t)n, Lmax = (size_t)t->max_lines;
+    std::vector<fdcm_match> fetched;
+    const fdcm_match* h = matches;
+    if (on_device) {
+        fetched.resize(N);
+        FDCM_HIP(hipMemcpyAsync(fetched.data(), matches, N * sizeof(fdcm_match), hipMemcpyDeviceToHost, fm->stream));
+        FDCM_HIP(hipStreamSynchronize(fm->stream));
+        h = fetched.data();
+    }
+    bins.assign(std::max<size_t>(1, N * Lmax), 0);
+    std::vector<float> posed;
+    for (size_t j = 0; j < N; ++j) {
+        const int64_t tm = (int64_t)h[j].tmpl_idx - base;
+        if (tm < 0 || tm >= t->T) continue;
+        pose_lines(t, tm, h[j].transform, posed);
+        for (size_t i = 0; i < posed.size() / 4; ++i) {
+            const float* p = &posed[4 * i];
+            const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
+            bins[j * Lmax + i] = (unsigned short)closest_orientation(fm->keys.data(), (int)fm->m, angle);
+        }
+    }
+}
+
 // Both device calls on match lists (include/fdcm.h, "Match lists"): the arguments are checked (fdcm_capi.cpp).  det null: the
 // verify call, whose outputs are scores_out, fractions_out and costs_out (each may be null).  Else the detect call: the
 // rounds on the verify pass's keys and boxes, then the gather.  One reserve_eval lays out the whole call: the upload (host
@@ -3552,32 +3555,8 @@ void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match*
     const std::vector<float> den = best_denominators(t, det ? det->penalty : -1, det ? det->tau : 1.f);
     std::vector<float> totals(T);
     templates_matched_totals(t, totals.data());
-    // Host-libm bins (fdcm_orientation_bins_mode() == 1): the bins of every posed line, on the host, from host records; device
-    // records cost one download.
     std::vector<unsigned short> bins;
-    std::vector<fdcm_match> fetched;
-    if (orientation_bins_on_host()) {
-        if (fm->m > 65535) throw std::string("host-side orientation bins need depth <= 65535");
-        const fdcm_match* h = matches;
-        if (on_device) {
-            fetched.resize(N);
-            FDCM_HIP(hipMemcpyAsync(fetched.data(), matches, N * sizeof(fdcm_match), hipMemcpyDeviceToHost, st));
-            FDCM_HIP(hipStreamSynchronize(st));
-            h = fetched.data();
-        }
-        bins.assign(std::max<size_t>(1, N * Lmax), 0);
-        std::vector<float> posed;
-        for (size_t j = 0; j < N; ++j) {
-            const int64_t tm = (int64_t)h[j].tmpl_idx - base;
-            if (tm < 0 || tm >= t->T) continue;
-            pose_lines(t, tm, h[j].transform, posed);
-            for (size_t i = 0; i < posed.size() / 4; ++i) {
-                const float* p = &posed[4 * i];
-                const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
-                bins[j * Lmax + i] = (unsigned short)closest_orientation(fm->keys.data(), (int)fm->m, angle);
-            }
-        }
-    }
+    matches_host_bins(fm, t, matches, n, on_device, base, bins);
     const int max_det = det ? det->max_detections : 0;
     const size_t o_caps = on_device ? 0 : al256(N * sizeof(fdcm_match)), o_den = o_caps + (t->capped ? al256((size_t)t->n_lines * 4) : 0),
                  o_need = o_den + al256(T * 4), o_tl = o_need + (gated ? al256(T * 4) : 0), o_bins = o_tl + al256(T * 4),

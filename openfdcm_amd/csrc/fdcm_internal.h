@@ -44,6 +44,8 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              run_matched_fractions, run_search_exhaustive_detect_windows: its scoring, its winners' pass and
 //                              its fractions; run_matches: the verify pass of the calls on match lists, which also take
 //                              their bins from the host under FDCM_FORCE_HOST_BINS)
+//   FDCM_COVERAGE_PART=1..     records a part of the scene coverage of a match list holds at most, instead of what 768 MB of
+//                              table hold (run_matches_coverage)
 //   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
 //                              takes that form for a volume of 4 GB or more alone (score maps, top-k, peaks, rotations, best
 //                              map, the detections, line costs); the pose windows and the calls by matched fraction keep
@@ -76,6 +78,7 @@ struct TestSwitches {
     bool host_bins, search_flat, search_compact2;
     int windows_batch;  // 0: not forced
     bool windows_flat, matched_flat, exhaustive_flat;
+    int coverage_part;  // 0: not forced
     bool poison;           // FDCM_POISON holds a valid word
     uint32_t poison_word;
 };
@@ -491,6 +494,10 @@ void matches_footprints(const fdcm_templates* t, const fdcm_match* matches, int6
 void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
                  const MatchesDetect* det, float* scores_out, float* fractions_out, float* costs_out, fdcm_match** out, int64_t* n_out,
                  int32_t* indices_out, int32_t* boxes_out, float* matched_out);
+// the bins of every posed line from the host libm, [record][max_lines], where fdcm_orientation_bins_mode() is 1 (else empty); the
+// handle has its stream
+void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
+                       std::vector<unsigned short>& bins);
 // Scene coverage (include/fdcm.h, "Scene coverage").  What prepare_pairs yields for the distinct pairs of a pose list, in the
 // plain form fdcm_coverage.hip takes: pair u = find(tmpl * n_rot + a) has the lines [line0[u], line0[u] + nl[u]) -- the (rotated)
 // end points and the bin k_line_costs reads --, its admissible translations adm[5 u ..] = any, x0, x1, y0, y1 and its footprint
@@ -518,6 +525,16 @@ void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int
                       const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                       const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
                       int64_t* n_out, uint8_t* residual);
+// Scene coverage and selection of match records (include/fdcm.h, "Match lists: scene coverage and selection"), implemented in
+// fdcm_coverage.hip: the siblings' arguments with run_matches' records (n on the host or, matches_on_device, on the handle's
+// device) in place of the poses; the table is made on the device (k_matches_table).  counts: 2 n int32 on the host.
+void run_matches_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                          const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
+                          const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual);
+void run_matches_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                        const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
+                        const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
+                        int64_t* n_out, uint8_t* residual);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

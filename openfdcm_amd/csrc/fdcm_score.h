@@ -14,6 +14,51 @@ __device__ __forceinline__ float wave_max_f(float v) {
     return v;
 }
 
+// ---- match lists (include/fdcm.h, "Match lists"): what a wave makes of one record before it reads anything but the
+// template's lines, shared by k_matches_verify (fdcm_exhaustive.hip) and k_matches_table (fdcm_coverage.hip).
+struct MatchTransform { float M0, M1, M2, M3, M4, M5; };
+// P(r) of one line: transform, math.h:341-344, float32 and unfused: (M0 x + M1 y) + M2.
+__device__ __forceinline__ float4 match_pose_line(const MatchTransform& M, const float4 p) {
+    return make_float4((M.M0 * p.x + M.M1 * p.y) + M.M2, (M.M3 * p.x + M.M4 * p.y) + M.M5, (M.M0 * p.z + M.M1 * p.w) + M.M2,
+                       (M.M3 * p.z + M.M4 * p.w) + M.M5);
+}
+// One side of footprint(): floor(v) + d in int64, clamped (v is not NaN).
+__device__ __forceinline__ int matches_side(float v, int d) {
+    const float f = fminf(fmaxf(floorf(v), -1099511627776.f), 1099511627776.f);
+    const long long lim = 1ll << 25;
+    return (int)min(max((long long)f + d, -lim), lim);
+}
+// Admissibility and box of the record whose template has the lines [l0, l0 + nl) of tlines, a lane per line in rounds of 64:
+// every posed coordinate plus off = sceneTranslation + (0, 0) lies in (-1, W) x (-1, H) (the seam's rule, false for a NaN),
+// and F(r) at `margin` by footprint()'s arithmetic, (0, 0, -1, -1) without lines or with a NaN end point.  Wave-uniform.
+struct MatchFrame { bool adm; int4 box; };
+__device__ __forceinline__ MatchFrame match_frame(const float4* __restrict__ tlines, long long l0, int nl, const MatchTransform& M, float offx,
+                                                  float offy, int W, int H, int margin, int lane) {
+    bool inside = true, has_nan = false;
+    float mnx = f_inf(), mny = f_inf(), mxx = -f_inf(), mxy = -f_inf();
+    for (int i = lane; i < nl; i += 64) {
+        const float4 q = match_pose_line(M, tlines[l0 + i]);
+        const float x[2] = {q.x, q.z};
+        const float y[2] = {q.y, q.w};
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const float px = x[c] + offx, py = y[c] + offy;
+            inside = inside && px > -1.f && px < (float)W && py > -1.f && py < (float)H;  // false for NaN
+            has_nan = has_nan || f_isnan(x[c]) || f_isnan(y[c]);
+            mnx = std_min(mnx, x[c]); mxx = std_max(mxx, x[c]);
+            mny = std_min(mny, y[c]); mxy = std_max(mxy, y[c]);
+        }
+    }
+    MatchFrame F;
+    F.adm = __ballot(!inside) == 0;
+    const bool any_nan = __ballot(has_nan) != 0;
+    mnx = wave_min_f(mnx); mny = wave_min_f(mny); mxx = wave_max_f(mxx); mxy = wave_max_f(mxy);
+    F.box = make_int4(0, 0, -1, -1);
+    if (nl > 0 && !any_nan)
+        F.box = make_int4(matches_side(mnx, -margin), matches_side(mny, -margin), matches_side(mxx, margin), matches_side(mxy, margin));
+    return F;
+}
+
 // evaluate<Dt3Cpu> for one line and one translation, dt3cpu.cpp:153-173.  L = per-wave LDS lines
 // (x1,y1,x2,y2,slice), off = sceneTranslation + translation.  The two reads are split from the subtraction so that a
 // caller can have the reads of many lines in flight.

@@ -804,6 +804,59 @@ class DeviceFeatureMap:
         selected, counts = selected[:k.value].copy(), counts[:k.value].copy()
         return (selected, counts, res) if residual else (selected, counts)
 
+    # ---- match lists: scene coverage and selection (include/fdcm.h, "Match lists: scene coverage and selection")
+    def _labels_input(self, labels, residual):
+        """(pointer, width, height, on_device, kept alive, residual array or tensor, its pointer) of scene coverage's labels."""
+        if hasattr(labels, "data_ptr") and not isinstance(labels, np.ndarray) and labels.dim() == 2 and not labels.is_contiguous():
+            raise ValueError("labels on the device must be contiguous")
+        p, w, h, _, dev, keep = _pixels(labels, "labels")
+        if not dev and keep.size and keep.strides[0] != w:
+            keep = np.ascontiguousarray(keep)
+            p = C.c_void_p(keep.ctypes.data)
+        res, q = None, None
+        if residual and dev:
+            import torch
+            res = torch.empty((h, w), dtype=torch.uint8, device=keep.device)
+            q = C.c_void_p(res.data_ptr())
+        elif residual:
+            res = np.empty((h, w), dtype=np.uint8)
+            q = C.c_void_p(res.ctypes.data)
+        return p, w, h, dev, keep, res, q
+
+    def match_coverage(self, labels, templates, matches=None, radius=2, bin_tolerance=1, margin=None, tmpl_index_base=0, residual=False,
+                       device_ptr=None, n=0):
+        """fdcm_matches_coverage: scene_coverage for match records, each posed by its own transform.  Returns counts, an (n, 2)
+        int32 array of (edges, explained), (-1, -1) for a record that is invalid or not admissible, or with residual (counts,
+        residual).  labels, radius, bin_tolerance, margin and the residual are scene_coverage's; the forms of matches are
+        verify_matches'."""
+        p, w, h, dev, keep, res, q = self._labels_input(labels, residual)
+        ptr, n, on_device, keep_rec = self._match_input(matches, device_ptr, n)
+        par = capi.CoverageParams(int(radius), int(bin_tolerance), int(radius if margin is None else margin))
+        counts = np.zeros((n, 2), dtype=np.int32)
+        capi.check(capi.lib().fdcm_matches_coverage(self._h, p, w, h, dev, templates._h, ptr, n, on_device, int(tmpl_index_base),
+                                                    C.byref(par), counts.ctypes.data_as(C.POINTER(C.c_int32)) if counts.size else None, q))
+        return (counts, res) if residual else counts
+
+    def select_matches(self, labels, templates, matches=None, radius=2, bin_tolerance=1, margin=None, min_coverage=0.0, min_new=0.5,
+                       min_pixels=1, max_selected=1024, tmpl_index_base=0, residual=False, device_ptr=None, n=0):
+        """fdcm_matches_select: scene_select for match records, the list order being the priority.  Returns (selected, counts):
+        the (k,) int32 positions of the accepted records, ascending, and (k, 3) int32 rows (edges, explained, new); with
+        residual also the labels with 255 at every claimed pixel.  The rule's parameters are scene_select's, the rest
+        match_coverage's."""
+        p, w, h, dev, keep, res, q = self._labels_input(labels, residual)
+        ptr, n, on_device, keep_rec = self._match_input(matches, device_ptr, n)
+        par = capi.CoverageParams(int(radius), int(bin_tolerance), int(radius if margin is None else margin))
+        sel = capi.SelectParams(int(round(1000 * min_coverage)), int(round(1000 * min_new)), int(min_pixels), int(max_selected))
+        room = max(1, min(int(max_selected), 4096))          # (an argument out of range is the library's to refuse)
+        selected = np.zeros(room, dtype=np.int32)
+        counts = np.zeros((room, 3), dtype=np.int32)
+        k = C.c_int64(0)
+        capi.check(capi.lib().fdcm_matches_select(self._h, p, w, h, dev, templates._h, ptr, n, on_device, int(tmpl_index_base),
+                                                  C.byref(par), C.byref(sel), selected.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k), q))
+        selected, counts = selected[:k.value].copy(), counts[:k.value].copy()
+        return (selected, counts, res) if residual else (selected, counts)
+
     def rotation_score_map(self, templates, grid, cs, pivots=None):
         """(T, n, ny, nx) float32: the score of every rotated template at every grid point, NaN where not admissible."""
         rot, keep = _rotations(cs, pivots, templates.count)

@@ -137,6 +137,8 @@ class MatchList(MutableSequence):
         return self._s.rec.shape[0] if self._items is None else len(self._items)
 
     def __getitem__(self, i):
+        if isinstance(i, np.ndarray) and i.ndim == 1 and i.dtype.kind in "iu":  # positions, as select_matches returns them
+            return MatchList(np.ascontiguousarray(self.records()[i]))
         if self._items is not None:
             r = self._items[i]
             return MatchList._of_items(r) if isinstance(i, slice) else r
