@@ -874,6 +874,35 @@ int fdcm_search_exhaustive_windows(const fdcm_featuremap* fm, const fdcm_templat
     });
 }
 
+// The detector's limits, in the order every detection call checks them.  cross_permille: null for a call without objects.
+static void check_detect_limits(int32_t max_detections, int32_t overlap_permille, const int32_t* cross_permille, int32_t margin) {
+    require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
+    require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
+    if (cross_permille) require(*cross_permille >= 0 && *cross_permille <= 1000, "cross_permille must be in [0, 1000]");
+    require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+}
+
+// What both detection calls over pose windows check behind their limits: the penalty, then the pose windows' checks in
+// their order.
+static void check_detect_windows_args(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
+                                      const fdcm_pose_window* jobs, int64_t n_jobs, int32_t sx, int32_t sy, int32_t wrap, int penalty,
+                                      float tau, fdcm_match** out, int64_t* n_out) {
+    require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
+    require(std::isfinite(tau), "tau must be finite");
+    require(out && n_out, "null output");
+    require(sx >= 1 && sy >= 1, "strides sx and sy must be >= 1");
+    require(wrap == 0 || wrap == 1, "wrap must be 0 or 1");
+    require(n_jobs >= 0 && (n_jobs == 0 || jobs), "jobs is null or n_jobs is negative");
+    require(n_jobs <= ((int64_t)1 << 22), "n_jobs must be at most 2^22");
+    if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
+    check_pose_windows(jobs, n_jobs, rot ? rot->n : 1, sx, sy, wrap);
+    require(fm && templates, "null featuremap/templates");
+    require(fm->device == templates->device, "featuremap and templates live on different devices");
+    if (rot) check_pivots(templates, rot);
+    for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
+        require(jobs[j].tmpl < templates->T, "jobs: tmpl is outside the template set");
+}
+
 // Detections over pose windows: include/fdcm.h, "Detections over pose windows".  The detector's limits, then the pose
 // windows' checks in their order: nothing here touches the device.
 int fdcm_search_exhaustive_detect_windows(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
@@ -897,24 +926,9 @@ int fdcm_search_exhaustive_detect_windows_gated(const fdcm_featuremap* fm, const
     return guarded([&] {
         require(gate == FDCM_GATE_WINNER || gate == FDCM_GATE_ALL, "gate must be FDCM_GATE_WINNER or FDCM_GATE_ALL");
         require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
-        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
-        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
-        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        check_detect_limits(max_detections, overlap_permille, nullptr, margin);
         require(min_matched >= 0.f && min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
-        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
-        require(std::isfinite(tau), "tau must be finite");
-        require(out && n_out, "null output");
-        require(sx >= 1 && sy >= 1, "strides sx and sy must be >= 1");
-        require(wrap == 0 || wrap == 1, "wrap must be 0 or 1");
-        require(n_jobs >= 0 && (n_jobs == 0 || jobs), "jobs is null or n_jobs is negative");
-        require(n_jobs <= ((int64_t)1 << 22), "n_jobs must be at most 2^22");
-        if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
-        check_pose_windows(jobs, n_jobs, rot ? rot->n : 1, sx, sy, wrap);
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
-        if (rot) check_pivots(templates, rot);
-        for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
-            require(jobs[j].tmpl < templates->T, "jobs: tmpl is outside the template set");
+        check_detect_windows_args(fm, templates, rot, jobs, n_jobs, sx, sy, wrap, penalty, tau, out, n_out);
         records_call(out, [&] {
             run_search_exhaustive_detect_windows(const_cast<fdcm_featuremap*>(fm), templates, rot, jobs, n_jobs, sx, sy,
                                                  max_score == 0.f ? 0.f : max_score, max_detections, overlap_permille, margin, penalty, tau,
@@ -989,9 +1003,7 @@ int fdcm_search_exhaustive_detect_all(const fdcm_featuremap* fm, const fdcm_temp
                                       int32_t* boxes_out) {
     return guarded([&] {
         require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
-        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
-        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
-        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        check_detect_limits(max_detections, overlap_permille, nullptr, margin);
         require(out && n_out, "null output");
         check_best_args(fm, templates, rot, grid, penalty, tau);
         check_hull_rows(templates, rot, margin);
@@ -1022,9 +1034,7 @@ int fdcm_search_exhaustive_detect_all_gated(const fdcm_featuremap* fm, const fdc
     return guarded([&] {
         require(gate == FDCM_GATE_WINNER || gate == FDCM_GATE_ALL, "gate must be FDCM_GATE_WINNER or FDCM_GATE_ALL");
         require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
-        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
-        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
-        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        check_detect_limits(max_detections, overlap_permille, nullptr, margin);
         require(min_matched >= 0.f && min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
         require(out && n_out, "null output");
         check_best_args(fm, templates, rot, grid, penalty, tau);
@@ -1106,10 +1116,7 @@ int fdcm_search_exhaustive_detect_objects(const fdcm_featuremap* fm, const fdcm_
         require(gate == FDCM_GATE_WINNER || gate == FDCM_GATE_ALL, "gate must be FDCM_GATE_WINNER or FDCM_GATE_ALL");
         std::vector<float> ms, mm;
         check_object_limits(n_objects, max_score, true, min_matched, ms, mm);
-        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
-        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
-        require(cross_permille >= 0 && cross_permille <= 1000, "cross_permille must be in [0, 1000]");
-        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        check_detect_limits(max_detections, overlap_permille, &cross_permille, margin);
         require(out && n_out, "null output");
         check_object_planes(grid, n_objects);
         check_best_args(fm, templates, rot, grid, penalty, tau);
@@ -1134,24 +1141,8 @@ int fdcm_search_exhaustive_detect_windows_objects(const fdcm_featuremap* fm, con
         require(gate == FDCM_GATE_WINNER || gate == FDCM_GATE_ALL, "gate must be FDCM_GATE_WINNER or FDCM_GATE_ALL");
         std::vector<float> ms, mm;
         check_object_limits(n_objects, max_score, true, min_matched, ms, mm);
-        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
-        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
-        require(cross_permille >= 0 && cross_permille <= 1000, "cross_permille must be in [0, 1000]");
-        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
-        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
-        require(std::isfinite(tau), "tau must be finite");
-        require(out && n_out, "null output");
-        require(sx >= 1 && sy >= 1, "strides sx and sy must be >= 1");
-        require(wrap == 0 || wrap == 1, "wrap must be 0 or 1");
-        require(n_jobs >= 0 && (n_jobs == 0 || jobs), "jobs is null or n_jobs is negative");
-        require(n_jobs <= ((int64_t)1 << 22), "n_jobs must be at most 2^22");
-        if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
-        check_pose_windows(jobs, n_jobs, rot ? rot->n : 1, sx, sy, wrap);
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
-        if (rot) check_pivots(templates, rot);
-        for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
-            require(jobs[j].tmpl < templates->T, "jobs: tmpl is outside the template set");
+        check_detect_limits(max_detections, overlap_permille, &cross_permille, margin);
+        check_detect_windows_args(fm, templates, rot, jobs, n_jobs, sx, sy, wrap, penalty, tau, out, n_out);
         check_object_labels(templates, objects, n_objects);
         records_call(out, [&] {
             run_search_exhaustive_detect_windows_objects(const_cast<fdcm_featuremap*>(fm), templates, rot, jobs, n_jobs, sx, sy, objects,

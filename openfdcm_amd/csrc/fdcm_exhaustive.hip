@@ -1757,38 +1757,92 @@ float exit_bound(float B, int n) {
     return c > 1e38f ? f_inf() : c;
 }
 
-struct BestRun {
-    char* d = nullptr;  // search.eval
-    size_t o_unit = 0, o_seg = 0, o_foot = 0, o_bc = 0, o_best = 0, o_pair = 0, o_keys = 0, o_plane = 0, o_cand = 0;
-    size_t o_tm = 0, o_len = 0, o_need = 0, o_tl = 0, o_frac = 0;  // (the matched fraction's calls)
-    size_t o_hull = 0;  // (hull footprints) the shapes and the span table, behind everything else; staged behind o_pair
-    size_t n_keys = 0;
-    int tiles_x = 0, parts = 0;
+// What the calls with objects (include/fdcm.h, "Objects") take beside their siblings' arguments.
+struct ObjectsIn {
+    const int32_t* objects;    // per template
+    int G;
+    const float* max_score;    // per object
+    const float* min_matched;  // per object, or null: all 0
+    int cross;                 // the limit between entries of different objects, in permille
 };
+
+// TL and the gate's need for every entry e < T n of a call, entry e being template e / n's (the pairs of a dense call; n = 1:
+// the templates themselves): tl[e] = TL of its template and, with `needs`, need[e] = float32(min_matched_of(template) * TL),
+// one multiply.
+template <class MinMatchedOf>
+static void matched_needs(const fdcm_templates* t, size_t n, bool needs, MinMatchedOf min_matched_of, std::vector<float>& tl,
+                          std::vector<float>& need) {
+    std::vector<float> totals((size_t)t->T);
+    templates_matched_totals(t, totals.data());
+    tl.resize(totals.size() * n);
+    for (size_t e = 0; e < tl.size(); ++e) tl[e] = totals[e / n];
+    if (!needs) return;
+    need.resize(tl.size());
+    for (size_t e = 0; e < tl.size(); ++e) need[e] = min_matched_of(e / n) * tl[e];
+}
 
 constexpr size_t kNmsPartialBytes = 2 * kNmsWorkgroups * (8 + 4);  // two sets of partial minima: the keys, then the pairs
 
-// Scores every pair of P (T templates x n rotations, prepared) on the grid and leaves, on the device, the merged key
-// plane of the call: one launch chain of k_exhaustive<., kBest> over all pairs into one plane set to "no key" before.
-// Pairs of templates without lines take no part.  k > 0 also lays out what the peak pass needs (the one unit, its group,
-// the merged list, the pairs of its entries, the candidate lists).  Returns false, with nothing queued, when no pair has
-// a grid point: every point is then without a candidate.  foot (or null): a footprint per pair, for the rounds of the
-// overlap rule; it goes up with the same upload, and the partial minima of the rounds take the candidate lists' place.
-// list: the entries of the result list and of its pairs.  max_score (or null): only the points with q <= *max_score get a
-// key (k_exhaustive<., kBestBound, .>); the exit bound of every pair goes up with the same upload.  mt (or null; include/fdcm.h,
-// "Detections by matched fraction"): P.len, and per pair the gate's need and the template's TL, whichever is given, go up
-// with the same upload too, and the list gets a float per entry for its fractions.  gate_all ("Gate inside the minimum"): the
-// needs go to the scoring kernel, its gated form; else they wait for k_matched_gate.
-struct MatchedIn { const float* need; const float* tl; bool gate_all = false; };  // one float per pair each, or null
+// ---- the key planes of a dense call, and its workspace
+// What a dense call asks of dense_keys.  The single calls are the case G = 1 of the calls with objects: without `ob` the one
+// object has all templates, the threshold max_score (+inf: none) and the gate min_matched.
+struct DenseIn {
+    const ObjectsIn* ob = nullptr;
+    float max_score = f_inf(), min_matched = 0.f;  // (without ob)
+    bool gate_all = false;  // the kind of gate, "Gate inside the minimum": the needs go to the scoring kernel, its gated form;
+                            // else they wait for k_matched_gate
+    const std::vector<Foot>* foot = nullptr;  // a footprint per pair, for the rounds of the overlap rule
+    int list = kMaxK;                         // the entries of the result list and of its pairs
+    int k = 0;                                // > 0: also what the peak pass needs (run_search_exhaustive_detect)
+    bool planes4 = false;                     // the G 4-byte planes a best map stages its downloads in
+    bool want_tl = false;                     // the fractions: TL per pair, and a float per entry of the list
+    size_t hull_bytes = 0;                    // (hull footprints) HullRun's tables
+};
 
-bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau, int k,
-               BestRun& R, const std::vector<Foot>* foot = nullptr, int list = kMaxK, const float* max_score = nullptr,
-               const MatchedIn* mt = nullptr, size_t hull_bytes = 0) {
+// Where dense_keys left what: offsets into d = search.eval.  Everything before o_pair is written by the one upload.
+struct DenseRun {
+    char* d = nullptr;
+    size_t o_tm = 0, o_unit = 0, o_seg = 0, o_foot = 0, o_pobj = 0, o_len = 0, o_need = 0, o_tl = 0, o_best = 0;
+    size_t o_pair = 0, o_frac = 0, o_keys = 0, o_plane = 0, o_cand = 0, o_hull = 0;
+    size_t n_keys = 0;
+    int tiles_x = 0, parts = 0, G = 1;
+    bool objects = false;  // the call has objects: their per-pair table is at o_pobj when there are footprints
+};
+
+// Scores every pair of P (T templates x n rotations, prepared) on the grid and leaves, on the device, the G merged key
+// planes of the call, one per object, one behind the other at o_keys: n_keys keys each in sub-tile order, all set to "no key"
+// once, then one launch chain of k_exhaustive<., kBest*> per object over that object's pairs into that object's plane, with
+// that object's threshold (only the points with q <= max_score get a key; +inf: the kernel without the checks) and, under
+// gate_all, that object's needs.  Pairs of templates without lines take no part; an object without templates queues nothing
+// and keeps an empty plane.  Returns false, with nothing queued or reserved, when no pair has a grid point: every point is
+// then without a candidate.
+//
+// The workspace is the list `blocks` below, in that order, each block aligned to 256 bytes and absent (0 bytes) unless its
+// condition holds.  One upload writes the blocks up to the result list: the lines (at 0); the template records by pair,
+// each with slot = its pair, which the kernels that look a pair up read (k_matched_gate, k_matched_plane, k_matched_list),
+// followed by the peak pass's unit; with objects the same records object by object, for the launch chains (the scoring
+// kernels read their bounds and needs by slot and write the slot into the key; without objects pair order is that order, and
+// the chain reads the records by pair); the peak pass's group; the footprints and with objects the object of every pair,
+// for the rounds; the exit bound of every pair when an object has a threshold; P.len; the needs when an object has a gate;
+// TL; the result list, all "no key".  Behind them, written by kernels alone: the pairs and the fractions of the list's
+// entries, the key planes, the 4-byte planes (the peak pass's score plane is one), the partial minima of the rounds or the
+// peak pass's candidate lists, and the hull tables, which go up in a second copy staged behind the first one's bytes.
+bool dense_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau,
+                const DenseIn& in, DenseRun& R) {
     const std::vector<float> den = best_denominators(t, penalty, tau);
     const size_t np = P.nl.size();
-    std::vector<float> bc(max_score ? np : 0);
-    for (size_t u = 0; u < bc.size(); ++u) bc[u] = exit_bound(score_bound(den[u / (size_t)n], *max_score), P.nl[u]);
-    std::vector<ExTmpl> tm(np + 1);
+    const ObjectsIn* ob = in.ob;
+    const int G = ob ? ob->G : 1;
+    const float* ms = ob ? ob->max_score : &in.max_score;
+    const float* mm = ob ? ob->min_matched : &in.min_matched;
+    auto obj_of = [&](size_t u) { return ob ? ob->objects[u / (size_t)n] : 0; };
+    const bool bounded = std::any_of(ms, ms + G, [](float v) { return v < f_inf(); });
+    const bool gated = mm && std::any_of(mm, mm + G, [](float v) { return v > 0.f; });
+    std::vector<float> bc(bounded ? np : 0);
+    for (size_t u = 0; u < bc.size(); ++u) bc[u] = exit_bound(score_bound(den[u / (size_t)n], ms[obj_of(u)]), P.nl[u]);
+    std::vector<ExTmpl> tm(np + 1), sorted(ob ? np : 0);
+    std::vector<int32_t> pobj(ob ? np : 0);
+    std::vector<size_t> start((size_t)G + 1, 0);  // the pairs of object o: [start[o], start[o + 1]) of the records by object
     bool any = false;
     for (size_t u = 0; u < np; ++u) {
         ExTmpl e = grid_tmpl(P, u, g, (int)u);
@@ -1796,55 +1850,79 @@ bool best_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int
         e.koff = bits_from_f(den[u / (size_t)n]);
         any = any || (e.i0 <= e.i1 && e.j0 <= e.j1);
         tm[u] = e;
+        if (ob) pobj[u] = obj_of(u);
+        ++start[(size_t)obj_of(u) + 1];
     }
     if (!any) return false;
+    for (int o = 0; o < G; ++o) start[(size_t)o + 1] += start[(size_t)o];
+    if (ob) {
+        std::vector<size_t> at(start.begin(), start.end() - 1);
+        for (size_t u = 0; u < np; ++u) sorted[at[(size_t)pobj[u]]++] = tm[u];  // (pair order inside an object)
+    }
     tm[np] = ExTmpl{0, 0, 0, g.nx - 1, 0, g.ny - 1, 0, 0};  // the peak pass's unit: the score plane, its box the whole grid
     const int4 seg = make_int4(0, 1, 0, 0);
+    std::vector<float> need, tl;
+    if (gated || in.want_tl) matched_needs(t, (size_t)n, gated, [&](size_t i) { return mm[ob ? ob->objects[i] : 0]; }, tl, need);
+    R.G = G;
+    R.objects = ob != nullptr;
     R.tiles_x = (g.nx + kTileX - 1) / kTileX;
-    const size_t n_keys = (size_t)R.tiles_x * (size_t)((g.ny + kTileY - 1) / kTileY) * (kTileX * kTileY);
+    const size_t n_keys = R.n_keys = (size_t)R.tiles_x * (size_t)((g.ny + kTileY - 1) / kTileY) * (kTileX * kTileY);
+    const size_t N = (size_t)g.nx * g.ny, list = (size_t)in.list;
     const int max_tiles = ((g.nx - 1) / kPkTX + 1) * ((g.ny - 1) / kPkTY + 1);
     R.parts = std::max(1, std::min(max_tiles, kBestPeakWorkgroups));
-    const size_t o_tm = al256(P.lines.size() * sizeof(ExLine));
-    R.o_unit = o_tm + np * sizeof(ExTmpl);
-    R.o_seg = al256(R.o_unit + sizeof(ExTmpl));
-    R.o_foot = R.o_seg + 256;
-    R.o_bc = R.o_foot + (foot ? al256(np * sizeof(Foot)) : 0);
-    R.o_tm = o_tm;
-    R.o_len = R.o_bc + al256(bc.size() * sizeof(float));
-    R.o_need = R.o_len + (mt ? al256(P.len.size() * sizeof(float)) : 0);
-    R.o_tl = R.o_need + (mt && mt->need ? al256(np * sizeof(float)) : 0);
-    R.o_best = R.o_tl + (mt && mt->tl ? al256(np * sizeof(float)) : 0);
-    R.n_keys = n_keys;
-    R.o_pair = R.o_best + al256((size_t)list * 8);
-    R.o_frac = R.o_pair + al256((size_t)list * 4);
-    R.o_keys = R.o_frac + (mt ? al256((size_t)list * 4) : 0);
-    R.o_plane = R.o_keys + al256(n_keys * 8);
-    R.o_cand = R.o_plane + al256((size_t)g.nx * g.ny * 4);
-    R.o_hull = al256(R.o_cand + (foot ? kNmsPartialBytes : k > 0 ? al256((size_t)4 * R.parts * k * 8) : 0));
-    reserve_eval(fm, R.o_hull + hull_bytes, R.o_pair + hull_bytes);
+    const bool peaks = in.k > 0, foot = in.foot != nullptr;
+    size_t o_lines = 0, o_sorted = 0, o_bc = 0;
+    struct Block { size_t* at; size_t bytes; const void* src; };  // src: what the upload carries there
+    const Block blocks[] = {
+        {&o_lines, P.lines.size() * sizeof(ExLine), P.lines.data()},
+        {&R.o_tm, (np + (peaks ? 1 : 0)) * sizeof(ExTmpl), tm.data()},
+        {&o_sorted, sorted.size() * sizeof(ExTmpl), sorted.data()},  // (np records with objects, else none)
+        {&R.o_seg, peaks ? sizeof seg : 0, &seg},
+        {&R.o_foot, foot ? np * sizeof(Foot) : 0, foot ? in.foot->data() : nullptr},
+        {&R.o_pobj, foot ? pobj.size() * sizeof(int32_t) : 0, pobj.data()},  // (np entries with objects, else none)
+        {&o_bc, bc.size() * sizeof(float), bc.data()},             // (np floats when an object has a threshold, else none)
+        {&R.o_len, P.len.size() * sizeof(float), P.len.data()},    // (a float per line when the caller set P.lens, else none)
+        {&R.o_need, need.size() * sizeof(float), need.data()},     // (np floats when an object has min_matched > 0, else none)
+        {&R.o_tl, in.want_tl ? np * sizeof(float) : 0, tl.data()},
+        {&R.o_best, list * 8, nullptr},  // kNoKey, below
+        {&R.o_pair, list * 4, nullptr},  // the upload ends here
+        {&R.o_frac, in.want_tl ? list * 4 : 0, nullptr},
+        {&R.o_keys, (size_t)G * n_keys * 8, nullptr},
+        {&R.o_plane, in.planes4 || peaks ? (size_t)G * N * 4 : 0, nullptr},
+        {&R.o_cand, foot ? kNmsPartialBytes : peaks ? (size_t)4 * R.parts * in.k * 8 : 0, nullptr},
+        {&R.o_hull, in.hull_bytes, nullptr},
+    };
+    size_t end = 0;
+    for (const Block& b : blocks) {
+        *b.at = end;
+        end += al256(b.bytes);
+    }
+    R.o_unit = R.o_tm + np * sizeof(ExTmpl);
+    reserve_eval(fm, end, R.o_pair + in.hull_bytes);
     char* d = R.d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
-    std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
-    std::memcpy(h + o_tm, tm.data(), tm.size() * sizeof(ExTmpl));
-    std::memcpy(h + R.o_seg, &seg, sizeof seg);
-    if (foot) std::memcpy(h + R.o_foot, foot->data(), np * sizeof(Foot));
-    if (max_score) std::memcpy(h + R.o_bc, bc.data(), bc.size() * sizeof(float));
-    if (mt) std::memcpy(h + R.o_len, P.len.data(), P.len.size() * sizeof(float));
-    if (mt && mt->need) std::memcpy(h + R.o_need, mt->need, np * sizeof(float));
-    if (mt && mt->tl) std::memcpy(h + R.o_tl, mt->tl, np * sizeof(float));
-    std::memset(h + R.o_best, 0xff, (size_t)list * 8);  // kNoKey
+    for (const Block& b : blocks)
+        if (b.src && b.bytes) std::memcpy(h + *b.at, b.src, b.bytes);
+    std::memset(h + R.o_best, 0xff, list * 8);  // kNoKey
     hipStream_t st = fm->stream;
     FDCM_HIP(hipMemcpyAsync(d, h, R.o_pair, hipMemcpyHostToDevice, st));
-    FDCM_HIP(hipMemsetAsync(d + R.o_keys, 0xff, n_keys * 8, st));  // no key anywhere
-    launch<kBest>(fm, P, g, (const ExLine*)d, (const ExTmpl*)(d + o_tm), (int)np, 0, portions_for(fm, g, (int)np), nullptr,
-                  (unsigned long long*)(d + R.o_keys), max_score ? (const float*)(d + R.o_bc) : nullptr, max_score ? *max_score : 0.f,
-                  mt && mt->need && mt->gate_all ? (const float*)(d + R.o_need) : nullptr);
+    FDCM_HIP(hipMemsetAsync(d + R.o_keys, 0xff, (size_t)G * n_keys * 8, st));  // no key anywhere, in any plane
+    const ExTmpl* by_object = (const ExTmpl*)(d + (ob ? o_sorted : R.o_tm));
+    for (int o = 0; o < G; ++o) {
+        const int cnt = (int)(start[(size_t)o + 1] - start[(size_t)o]);
+        if (cnt == 0) continue;
+        const bool bound_o = ms[o] < f_inf(), need_o = in.gate_all && gated && mm[o] > 0.f;
+        launch<kBest>(fm, P, g, (const ExLine*)d, by_object + start[(size_t)o], cnt, 0, portions_for(fm, g, cnt), nullptr,
+                      (unsigned long long*)(d + R.o_keys) + (size_t)o * n_keys, bound_o ? (const float*)(d + o_bc) : nullptr,
+                      bound_o ? ms[o] : 0.f, need_o ? (const float*)(d + R.o_need) : nullptr);
+    }
     return true;
 }
 
-void best_unpack(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, float* score, int* pair) {
+// Plane o of the call's key planes as a plane of scores or of pairs (k_best_unpack).
+void best_unpack(fdcm_featuremap* fm, const DenseRun& R, const fdcm_grid& g, int o, float* score, int* pair) {
     hipLaunchKernelGGL(k_best_unpack, dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4)), dim3(256), 0, fm->stream,
-                       (const unsigned long long*)(R.d + R.o_keys), g.nx, g.ny, R.tiles_x, score, pair);
+                       (const unsigned long long*)(R.d + R.o_keys) + (size_t)o * R.n_keys, g.nx, g.ny, R.tiles_x, score, pair);
     FDCM_HIP(hipGetLastError());
 }
 
@@ -1853,7 +1931,7 @@ void best_unpack(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, floa
 // at the grid point of its key (kNoKey ends the list).  foot and boxes_out (or null): the footprint of each pair; the
 // footprint of record l, F(g) = foot[pair[l]] + t_g, goes to boxes_out[4 l ..].  matched_out (or null): the k floats
 // k_matched_list left at o_frac, of which the first *n_out are the records' fractions.
-void detect_records(fdcm_featuremap* fm, const BestRun& R, const Pairs& P, bool rotated, int n, const fdcm_grid& g, int k, int32_t base,
+void detect_records(fdcm_featuremap* fm, const DenseRun& R, const Pairs& P, bool rotated, int n, const fdcm_grid& g, int k, int32_t base,
                     fdcm_match** out, int64_t* n_out, const Foot* foot, int32_t* boxes_out, float* matched_out = nullptr) {
     hipStream_t st = fm->stream;
     std::vector<unsigned long long> best((size_t)k);
@@ -2302,92 +2380,87 @@ void run_search_exhaustive_peaks(fdcm_featuremap* fm, const fdcm_templates* t, c
     emit_records(best, k, index, 1, g, base, nullptr, out, n_out);
 }
 
-// Best map and detections (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  rot null: the caller's lines as they
-// are (run_search_exhaustive_peaks' note on -0).
-void run_best_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty, float tau,
-                  float* score_out, int32_t* pair_out) {
+// What every dense call does under the handle's lock before its keys: the pairs of the whole set, prepared.  Returns the
+// number of rotations (rot null: 1, the caller's lines as they are -- run_search_exhaustive_peaks' note on -0).
+static int dense_begin(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, bool flat, bool lens, Pairs& P) {
+    begin(fm);
+    const int n = rot ? rot->n : 1;
+    if (rot) check_rotated_size(t, n);
+    P.lens = lens;
+    prepare_pairs(fm, t, rot, flat, P);
+    return n;
+}
+
+// The best maps (include/fdcm.h, "Best map and detections", "Gate inside the minimum", "Objects"): the arguments are checked
+// (fdcm_capi.cpp).  G planes per output, object after object (ob null: the one object with the gate min_matched).  The needs go
+// to the scoring kernel (none for an object with min_matched = 0: the best map's own kernel).  Each output wanted is unpacked
+// from the key planes into the G 4-byte planes at o_plane, the fractions of the points' pairs by k_matched_plane, and comes
+// down before the next one takes its place.
+static void best_maps(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty, float tau,
+                      bool flat, const ObjectsIn* ob, float min_matched, float* score_out, int32_t* pair_out, float* matched_out) {
     check_grid(g);
-    const size_t N = (size_t)g.nx * g.ny;
+    const int G = ob ? ob->G : 1;
+    const size_t N = (size_t)g.nx * g.ny, GN = (size_t)G * N;
     auto none = [&]() {
-        if (score_out) std::fill(score_out, score_out + N, f_nan());
-        if (pair_out) std::fill(pair_out, pair_out + N, (int32_t)-1);
+        if (score_out) std::fill(score_out, score_out + GN, f_nan());
+        if (pair_out) std::fill(pair_out, pair_out + GN, (int32_t)-1);
+        if (matched_out) std::fill(matched_out, matched_out + GN, f_nan());
     };
     if (t->T == 0) return none();
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    if (rot) check_rotated_size(t, rot->n);
     Pairs P;
-    prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, P);
-    BestRun R;
-    if (!best_keys(fm, P, t, rot ? rot->n : 1, g, penalty, tau, 0, R)) return none();
+    const int n = dense_begin(fm, t, rot, flat, matched_out != nullptr, P);
+    DenseIn in;
+    in.ob = ob;
+    in.min_matched = min_matched;
+    in.gate_all = true;
+    in.planes4 = true;
+    in.want_tl = matched_out != nullptr;
+    DenseRun R;
+    if (!dense_keys(fm, P, t, n, g, penalty, tau, in, R)) return none();
     hipStream_t st = fm->stream;
-    char* plane = R.d + R.o_plane;  // one 4-byte plane, the scores and then the pairs
+    char* plane = R.d + R.o_plane;
+    auto down = [&](void* out) { FDCM_HIP(hipMemcpyAsync(out, plane, GN * 4, hipMemcpyDeviceToHost, st)); };
     if (score_out) {
-        best_unpack(fm, R, g, (float*)plane, nullptr);
-        FDCM_HIP(hipMemcpyAsync(score_out, plane, N * 4, hipMemcpyDeviceToHost, st));
+        for (int o = 0; o < G; ++o) best_unpack(fm, R, g, o, (float*)plane + (size_t)o * N, nullptr);
+        down(score_out);
     }
     if (pair_out) {
-        best_unpack(fm, R, g, nullptr, (int*)plane);
-        FDCM_HIP(hipMemcpyAsync(pair_out, plane, N * 4, hipMemcpyDeviceToHost, st));
+        for (int o = 0; o < G; ++o) best_unpack(fm, R, g, o, nullptr, (int*)plane + (size_t)o * N);
+        down(pair_out);
+    }
+    if (matched_out) {
+        auto kern = P.buf32 ? k_matched_plane<true> : k_matched_plane<false>;
+        for (int o = 0; o < G; ++o) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4)), dim3(256), 0, st, fm->vol.as<float>(),
+                               P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty, (const ExLine*)R.d, (const float*)(R.d + R.o_len),
+                               (const ExTmpl*)(R.d + R.o_tm), (const float*)(R.d + R.o_tl),
+                               (const unsigned long long*)(R.d + R.o_keys) + (size_t)o * R.n_keys, g.x0, g.y0, g.sx, g.sy, g.nx, g.ny,
+                               R.tiles_x, (float*)plane + (size_t)o * N);
+            FDCM_HIP(hipGetLastError());
+        }
+        down(matched_out);
     }
     FDCM_HIP(hipStreamSynchronize(st));
 }
 
-// Gated best map (include/fdcm.h, "Gate inside the minimum"): run_best_map with the needs in the scoring kernel (none at
-// min_matched = 0: the best map's own kernel) and a third plane, the fractions of the points' pairs (k_matched_plane).  The
-// 64-bit form follows FDCM_MATCHED_FLAT, as the calls by matched fraction.
+void run_best_map(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty, float tau,
+                  float* score_out, int32_t* pair_out) {
+    best_maps(fm, t, rot, g, penalty, tau, test_switches().exhaustive_flat, nullptr, 0.f, score_out, pair_out, nullptr);
+}
+
+// The 64-bit form of the gated and the object best maps follows FDCM_MATCHED_FLAT, as the calls by matched fraction.
 void run_best_map_gated(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty, float tau,
                         float min_matched, float* score_out, int32_t* pair_out, float* matched_out) {
-    check_grid(g);
-    const size_t N = (size_t)g.nx * g.ny;
-    auto none = [&]() {
-        if (score_out) std::fill(score_out, score_out + N, f_nan());
-        if (pair_out) std::fill(pair_out, pair_out + N, (int32_t)-1);
-        if (matched_out) std::fill(matched_out, matched_out + N, f_nan());
-    };
-    if (t->T == 0) return none();
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    const int n = rot ? rot->n : 1;
-    if (rot) check_rotated_size(t, n);
-    const bool gate = min_matched > 0.f;
-    Pairs P;
-    P.lens = matched_out != nullptr;
-    prepare_pairs(fm, t, rot, test_switches().matched_flat, P);
-    std::vector<float> need, tl;
-    if (gate || matched_out) {  // per pair, as detect_all's
-        std::vector<float> totals((size_t)t->T);
-        templates_matched_totals(t, totals.data());
-        tl.resize(P.nl.size());
-        for (size_t u = 0; u < tl.size(); ++u) tl[u] = totals[u / (size_t)n];
-        if (gate) {
-            need.resize(tl.size());
-            for (size_t u = 0; u < tl.size(); ++u) need[u] = min_matched * tl[u];
-        }
-    }
-    const MatchedIn mt{gate ? need.data() : nullptr, matched_out ? tl.data() : nullptr, true};
-    BestRun R;
-    if (!best_keys(fm, P, t, n, g, penalty, tau, 0, R, nullptr, kMaxK, nullptr, gate || matched_out ? &mt : nullptr)) return none();
-    hipStream_t st = fm->stream;
-    char* plane = R.d + R.o_plane;  // one 4-byte plane: the scores, then the pairs, then the fractions
-    if (score_out) {
-        best_unpack(fm, R, g, (float*)plane, nullptr);
-        FDCM_HIP(hipMemcpyAsync(score_out, plane, N * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (pair_out) {
-        best_unpack(fm, R, g, nullptr, (int*)plane);
-        FDCM_HIP(hipMemcpyAsync(pair_out, plane, N * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (matched_out) {
-        auto kern = P.buf32 ? k_matched_plane<true> : k_matched_plane<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4)), dim3(256), 0, st, fm->vol.as<float>(), P.SL,
-                           (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty, (const ExLine*)R.d, (const float*)(R.d + R.o_len),
-                           (const ExTmpl*)(R.d + R.o_tm), (const float*)(R.d + R.o_tl), (const unsigned long long*)(R.d + R.o_keys), g.x0,
-                           g.y0, g.sx, g.sy, g.nx, g.ny, R.tiles_x, (float*)plane);
-        FDCM_HIP(hipGetLastError());
-        FDCM_HIP(hipMemcpyAsync(matched_out, plane, N * 4, hipMemcpyDeviceToHost, st));
-    }
-    FDCM_HIP(hipStreamSynchronize(st));
+    best_maps(fm, t, rot, g, penalty, tau, test_switches().matched_flat, nullptr, min_matched, score_out, pair_out, matched_out);
+}
+
+void run_best_map_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty,
+                          float tau, const int32_t* objects, int n_objects, const float* min_matched, float* score_out, int32_t* pair_out,
+                          float* matched_out) {
+    const std::vector<float> inf((size_t)n_objects, f_inf());
+    const ObjectsIn ob{objects, n_objects, inf.data(), min_matched, 0};
+    best_maps(fm, t, rot, g, penalty, tau, test_switches().matched_flat, &ob, 0.f, score_out, pair_out, matched_out);
 }
 
 void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
@@ -2396,19 +2469,18 @@ void run_search_exhaustive_detect(fdcm_featuremap* fm, const fdcm_templates* t, 
     *n_out = 0;
     if (t->T == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    const int n = rot ? rot->n : 1;
-    if (rot) check_rotated_size(t, n);
     Pairs P;
-    prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, P);
-    BestRun R;
-    if (!best_keys(fm, P, t, n, g, penalty, tau, k, R)) return;
+    const int n = dense_begin(fm, t, rot, test_switches().exhaustive_flat, false, P);
+    DenseIn in;
+    in.k = k;
+    DenseRun R;
+    if (!dense_keys(fm, P, t, n, g, penalty, tau, in, R)) return;
     hipStream_t st = fm->stream;
     char* d = R.d;
     float* plane = (float*)(d + R.o_plane);
     unsigned long long* cand = (unsigned long long*)(d + R.o_cand);
     unsigned long long* d_best = (unsigned long long*)(d + R.o_best);
-    best_unpack(fm, R, g, plane, nullptr);
+    best_unpack(fm, R, g, 0, plane, nullptr);
     // the peaks of the score plane: one unit of one plane, its 32-bit form (k_exhaustive_peaks' !ANGLES)
     auto peaks = std::max(rx, ry) <= 8 ? k_exhaustive_peaks<8, false> : k_exhaustive_peaks<kMaxRadius, false>;
     hipLaunchKernelGGL(peaks, dim3((unsigned)R.parts), dim3(256), 0, st, (const float*)plane, g.nx, g.ny, (const ExTmpl*)(d + R.o_unit),
@@ -2494,8 +2566,8 @@ void check_hull_rows(const fdcm_templates* t, const fdcm_rotations* rot, int mar
     if (off.back() > kHullMaxRows) throw std::string("hull footprints: the span table of the call has more than 2^26 rows");
 }
 
-// Hull sets, the dense calls: the shapes of the call's pairs.  plan() before best_keys / objects_keys, which reserve bytes()
-// behind their own layout; upload() after them: the tables are built in the staging behind the first upload's bytes while the
+// Hull sets, the dense calls: the shapes of the call's pairs.  plan() before dense_keys, which reserves bytes() as the last
+// block of its layout; upload() after it: the tables are built in the staging behind the first upload's bytes while the
 // scoring launches run, and go up on the same stream before the rounds (plane_rounds).
 struct HullRun {
     std::vector<HullShape> shapes;
@@ -2503,7 +2575,7 @@ struct HullRun {
     size_t o_spans() const { return al256(shapes.size() * sizeof(HullShape)); }
     size_t bytes() const { return o_spans() + al256(rows * 8); }
     void plan(const std::vector<Foot>& foot) { rows = hull_layout(foot, shapes); }
-    void upload(fdcm_featuremap* fm, const BestRun& R, const Pairs& P, const std::vector<Foot>& foot, int margin) {
+    void upload(fdcm_featuremap* fm, const DenseRun& R, const Pairs& P, const std::vector<Foot>& foot, int margin) {
         char* h = (char*)fm->search.eval_stage.p + R.o_pair;
         std::memcpy(h, shapes.data(), shapes.size() * sizeof(HullShape));
         hull_fill(P, foot, margin, (HullShape*)h, (int32_t*)(h + o_spans()));
@@ -2548,11 +2620,11 @@ static void nms_rounds(NmsArgs a, unsigned wgs, int max_det, hipStream_t st) {
     }
 }
 
-// The rounds of a dense call on the G key planes best_keys or objects_keys left at R.o_keys, with the pairs' footprints at
-// o_foot, the partials at o_cand and the result list at o_best and o_pair.  H (or null): the set's shapes, uploaded.  pobj (or
-// null): the objects' per-pair table, on the device.
-static void plane_rounds(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid& g, int G, const HullRun* H, const int* pobj,
-                         int permille, int cross, int max_det) {
+// The rounds of a dense call on the G key planes dense_keys left at R.o_keys, with the pairs' footprints at o_foot, the
+// partials at o_cand and the result list at o_best and o_pair.  H (or null): the set's shapes, uploaded.  A call with objects
+// reads their per-pair table; one without runs the round kernel without objects (or the hull form).
+static void plane_rounds(fdcm_featuremap* fm, const DenseRun& R, const fdcm_grid& g, const HullRun* H, int permille, int cross,
+                         int max_det) {
     char* d = R.d;
     NmsArgs a{};
     a.keys = (unsigned long long*)(d + R.o_keys);
@@ -2561,9 +2633,9 @@ static void plane_rounds(fdcm_featuremap* fm, const BestRun& R, const fdcm_grid&
         a.shapes = (const HullShape*)(d + R.o_hull);
         a.spans = (const int2*)(d + R.o_hull + H->o_spans());
     }
-    a.obj = pobj;
+    a.obj = R.objects ? (const int*)(d + R.o_pobj) : nullptr;
     a.plane_chunks = (long long)(R.n_keys / 256);  // whole sub-tiles: a multiple of 4
-    a.n_chunks = a.plane_chunks * G;
+    a.n_chunks = a.plane_chunks * R.G;
     a.n = a.n_chunks * 256;
     a.x0 = g.x0; a.y0 = g.y0; a.sx = g.sx; a.sy = g.sy; a.nx = g.nx; a.tiles_x = R.tiles_x;
     a.permille = permille;
@@ -2583,40 +2655,6 @@ static std::vector<Foot> pair_footprints(const Pairs& P, int margin) {
     return foot;
 }
 
-// Detections by footprint overlap (include/fdcm.h): the arguments are checked (fdcm_capi.cpp).  The key plane is
-// best_keys', the rounds are plane_rounds', the records run_search_exhaustive_detect's.
-void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
-                                      int permille, int margin, int penalty, float tau, int32_t base, fdcm_match** out,
-                                      int32_t* boxes_out, int64_t* n_out) {
-    check_grid(g);
-    *n_out = 0;
-    if (t->T == 0) return;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    const int n = rot ? rot->n : 1;
-    if (rot) check_rotated_size(t, n);
-    Pairs P;
-    prepare_pairs(fm, t, rot, test_switches().exhaustive_flat, P);
-    const std::vector<Foot> foot = pair_footprints(P, margin);
-    const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
-    HullRun H;
-    if (hull) H.plan(foot);
-    BestRun R;
-    if (!best_keys(fm, P, t, n, g, penalty, tau, k, R, &foot, kMaxK, nullptr, nullptr, hull ? H.bytes() : 0)) return;
-    if (hull) H.upload(fm, R, P, foot, margin);
-    plane_rounds(fm, R, g, 1, hull ? &H : nullptr, nullptr, permille, permille, k);
-    detect_records(fm, R, P, rot != nullptr, n, g, k, base, out, n_out, foot.data(), boxes_out);
-}
-
-// What the calls with objects (include/fdcm.h, "Objects") take beside their siblings' arguments.
-struct ObjectsIn {
-    const int32_t* objects;    // per template
-    int G;
-    const float* max_score;    // per object
-    const float* min_matched;  // per object, or null: all 0
-    int cross;                 // the limit between entries of different objects, in permille
-};
-
 // TL_t (include/fdcm.h, "Detections by matched fraction"): the float32 sum of the template's line lengths in line order, from +0.
 void templates_matched_totals(const fdcm_templates* t, float* totals) {
     for (int64_t i = 0; i < t->T; ++i) {
@@ -2627,7 +2665,7 @@ void templates_matched_totals(const fdcm_templates* t, float* totals) {
 }
 
 // The fractions of the result list of a dense call, at R.o_frac: k_matched_list on the max_det entries at o_best and o_pair.
-static void matched_list(fdcm_featuremap* fm, const Pairs& P, const BestRun& R, const fdcm_grid& g, int max_det) {
+static void matched_list(fdcm_featuremap* fm, const Pairs& P, const DenseRun& R, const fdcm_grid& g, int max_det) {
     char* d = R.d;
     auto kern = P.buf32 ? k_matched_list<true> : k_matched_list<false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)((max_det + 255) / 256)), dim3(256), 0, fm->stream, fm->vol.as<float>(), P.SL, (int)fm->m,
@@ -2637,286 +2675,120 @@ static void matched_list(fdcm_featuremap* fm, const Pairs& P, const BestRun& R, 
     FDCM_HIP(hipGetLastError());
 }
 
-// Both detection calls with a threshold (include/fdcm.h, "All detections below a score"): the arguments are checked
-// (fdcm_capi.cpp).  The key plane holds the points with q <= max_score alone (best_keys with a threshold), the rounds are
-// plane_rounds' on result arrays of max_det entries.  matched: the call by matched fraction (include/fdcm.h), the other's own work plus,
-// with min_matched > 0, the gate pass over the key plane before the first round and, with matched_out, the fractions of the
-// result list after the last; min_matched = 0 and no matched_out queue what the other call queues.
-static void detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, float max_score,
-                       int max_det, int permille, int margin, int penalty, float tau, bool matched, float min_matched, int gate_kind,
-                       int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
+// The gate pass of FDCM_GATE_WINNER before the first round: k_matched_gate on the key plane of every object with
+// min_matched > 0 (mm: per object).
+static void gate_pass(fdcm_featuremap* fm, const Pairs& P, const DenseRun& R, const fdcm_grid& g, const float* mm) {
+    char* d = R.d;
+    auto kern = P.buf32 ? k_matched_gate<true> : k_matched_gate<false>;
+    for (int o = 0; o < R.G; ++o) {
+        if (!(mm[o] > 0.f)) continue;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(R.n_keys / 256)), dim3(256), 0, fm->stream, fm->vol.as<float>(), P.SL, (int)fm->m,
+                           (int)fm->W, (int)fm->H, fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + R.o_len),
+                           (const ExTmpl*)(d + R.o_tm), (const float*)(d + R.o_need),
+                           (unsigned long long*)(d + R.o_keys) + (size_t)o * R.n_keys, (long long)R.n_keys, g.x0, g.y0, g.sx, g.sy, R.tiles_x);
+        FDCM_HIP(hipGetLastError());
+    }
+}
+
+// What a dense detection call passes that is its own.  keys: its objects or its one threshold and gate, and the entries of its
+// result list; dense_detect fills in the rest.
+struct DetectIn {
+    DenseIn keys;
+    bool flat = false;                 // the 64-bit form of VolRef: the call's test switch
+    int gate_kind = FDCM_GATE_WINNER;
+    int max_det = 0;                   // the rounds and the records, at most
+    int permille = 0, cross = 0, margin = 0;
+};
+
+// The dense detections by footprint overlap (include/fdcm.h, "Detections suppressed by footprint overlap", "All detections
+// below a score", "Detections by matched fraction", "Objects"): the arguments are checked (fdcm_capi.cpp).  The key planes
+// are dense_keys', one per object, each holding the points with q <= its object's max_score alone; the hull tables go up
+// behind the scoring launches; with FDCM_GATE_WINNER the gate pass runs over the planes of the objects with min_matched > 0
+// (FDCM_GATE_ALL: the gate was inside the minimum); the rounds are plane_rounds' over all planes; with matched_out the
+// fractions of the result list follow the last round; the records are run_search_exhaustive_detect's.  min_matched = 0
+// and no matched_out queue what the call without a gate queues.
+static void dense_detect(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, const DetectIn& c,
+                         int penalty, float tau, int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
     check_grid(g);
     *n_out = 0;
     if (t->T == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    const int n = rot ? rot->n : 1;
-    if (rot) check_rotated_size(t, n);
-    const bool gate = matched && min_matched > 0.f, fracs = matched && matched_out != nullptr;
+    const ObjectsIn* ob = c.keys.ob;
+    const float* mm = ob ? ob->min_matched : &c.keys.min_matched;
+    const bool gate = mm && std::any_of(mm, mm + (ob ? ob->G : 1), [](float v) { return v > 0.f; });
+    const bool fracs = matched_out != nullptr, gate_all = gate && c.gate_kind == FDCM_GATE_ALL;
     Pairs P;
-    P.lens = gate || fracs;
-    prepare_pairs(fm, t, rot, matched ? test_switches().matched_flat : test_switches().exhaustive_flat, P);
-    const std::vector<Foot> foot = pair_footprints(P, margin);
-    // per pair: need = float32(min_matched * TL) of its template, and TL
-    std::vector<float> need, tl;
-    if (P.lens) {
-        std::vector<float> totals((size_t)t->T);
-        templates_matched_totals(t, totals.data());
-        tl.resize(P.nl.size());
-        for (size_t u = 0; u < tl.size(); ++u) tl[u] = totals[u / (size_t)n];
-        if (gate) {
-            need.resize(tl.size());
-            for (size_t u = 0; u < tl.size(); ++u) need[u] = min_matched * tl[u];
-        }
-    }
-    const bool gate_all = gate && gate_kind == FDCM_GATE_ALL;  // the gate inside the minimum: no gate pass
-    const MatchedIn mt{gate ? need.data() : nullptr, fracs ? tl.data() : nullptr, gate_all};
+    const int n = dense_begin(fm, t, rot, c.flat, gate || fracs, P);
+    const std::vector<Foot> foot = pair_footprints(P, c.margin);
     const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
     HullRun H;
     if (hull) H.plan(foot);
-    BestRun R;
-    // (+inf is no threshold: the plane is the best map's own, by the kernel without the checks)
-    if (!best_keys(fm, P, t, n, g, penalty, tau, 0, R, &foot, max_det, max_score < f_inf() ? &max_score : nullptr,
-                   P.lens ? &mt : nullptr, hull ? H.bytes() : 0))
-        return;
-    if (hull) H.upload(fm, R, P, foot, margin);
-    hipStream_t st = fm->stream;
-    char* d = R.d;
-    const float* vol = fm->vol.as<float>();
-    if (gate && !gate_all) {
-        auto kern = P.buf32 ? k_matched_gate<true> : k_matched_gate<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(R.n_keys / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx,
-                           fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
-                           (const float*)(d + R.o_need), (unsigned long long*)(d + R.o_keys), (long long)R.n_keys, g.x0, g.y0, g.sx, g.sy,
-                           R.tiles_x);
-        FDCM_HIP(hipGetLastError());
-    }
-    plane_rounds(fm, R, g, 1, hull ? &H : nullptr, nullptr, permille, permille, max_det);
-    if (fracs) matched_list(fm, P, R, g, max_det);
-    detect_records(fm, R, P, rot != nullptr, n, g, max_det, base, out, n_out, foot.data(), boxes_out, fracs ? matched_out : nullptr);
+    DenseIn in = c.keys;
+    in.gate_all = gate_all;
+    in.foot = &foot;
+    in.want_tl = fracs;
+    in.hull_bytes = hull ? H.bytes() : 0;
+    DenseRun R;
+    if (!dense_keys(fm, P, t, n, g, penalty, tau, in, R)) return;
+    if (hull) H.upload(fm, R, P, foot, c.margin);
+    if (gate && !gate_all) gate_pass(fm, P, R, g, mm);
+    plane_rounds(fm, R, g, hull ? &H : nullptr, c.permille, c.cross, c.max_det);
+    if (fracs) matched_list(fm, P, R, g, c.max_det);
+    detect_records(fm, R, P, rot != nullptr, n, g, c.max_det, base, out, n_out, foot.data(), boxes_out, matched_out);
+}
+
+void run_search_exhaustive_detect_nms(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int k,
+                                      int permille, int margin, int penalty, float tau, int32_t base, fdcm_match** out,
+                                      int32_t* boxes_out, int64_t* n_out) {
+    DetectIn c;  // no threshold, no gate, a list of kMaxK entries
+    c.flat = test_switches().exhaustive_flat;
+    c.max_det = k;
+    c.permille = c.cross = permille;
+    c.margin = margin;
+    dense_detect(fm, t, rot, g, c, penalty, tau, base, out, n_out, boxes_out, nullptr);
 }
 
 void run_search_exhaustive_detect_all(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                       float max_score, int max_det, int permille, int margin, int penalty, float tau, int32_t base,
                                       fdcm_match** out, int64_t* n_out, int32_t* boxes_out) {
-    detect_all(fm, t, rot, g, max_score, max_det, permille, margin, penalty, tau, false, 0.f, FDCM_GATE_WINNER, base, out, n_out,
-               boxes_out, nullptr);
+    DetectIn c;
+    c.keys.max_score = max_score;
+    c.keys.list = c.max_det = max_det;
+    c.flat = test_switches().exhaustive_flat;
+    c.permille = c.cross = permille;
+    c.margin = margin;
+    dense_detect(fm, t, rot, g, c, penalty, tau, base, out, n_out, boxes_out, nullptr);
 }
 
 void run_search_exhaustive_detect_all_matched(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                               float max_score, int max_det, int permille, int margin, int penalty, float tau,
                                               float min_matched, int gate, int32_t base, fdcm_match** out, int64_t* n_out,
                                               int32_t* boxes_out, float* matched_out) {
-    detect_all(fm, t, rot, g, max_score, max_det, permille, margin, penalty, tau, true, min_matched, gate, base, out, n_out, boxes_out,
-               matched_out);
+    DetectIn c;
+    c.keys.max_score = max_score;
+    c.keys.min_matched = min_matched;
+    c.keys.list = c.max_det = max_det;
+    c.flat = test_switches().matched_flat;
+    c.gate_kind = gate;
+    c.permille = c.cross = permille;
+    c.margin = margin;
+    dense_detect(fm, t, rot, g, c, penalty, tau, base, out, n_out, boxes_out, matched_out);
 }
 
-// ---- objects: the dense calls (include/fdcm.h, "Objects")
-// best_keys for G planes, one behind the other at o_keys, n_keys keys each in sub-tile order, all set to "no key" once.  The
-// template records go up twice: by pair, for the kernels that look a pair up (k_matched_gate, k_matched_plane,
-// k_matched_list), and object by object, each with slot = its pair, for one launch chain of k_exhaustive<., kBest*> per
-// object into that object's plane with that object's threshold (the scoring kernels read their bounds and needs by slot and
-// write the slot into the key, so they run as they are).  An object without templates queues nothing and keeps an empty
-// plane.  pobj: the object of every pair, for the rounds.  planes4: the 4-byte planes of G N floats a best map stages its
-// downloads in.  Returns false, with nothing queued, when no pair has a grid point.
-struct ObjectsRun : BestRun {
-    size_t o_sorted = 0, o_pobj = 0;
-    int G = 0;
-};
-
-static bool objects_keys(fdcm_featuremap* fm, const Pairs& P, const fdcm_templates* t, int n, const fdcm_grid& g, int penalty, float tau,
-                         const ObjectsIn& ob, bool gate_all, bool want_tl, const std::vector<Foot>* foot, int list, bool planes4,
-                         ObjectsRun& R, size_t hull_bytes = 0) {
-    const std::vector<float> den = best_denominators(t, penalty, tau);
-    const size_t np = P.nl.size();
-    const int G = ob.G;
-    auto obj_of = [&](size_t u) { return ob.objects[u / (size_t)n]; };
-    const bool bounded = std::any_of(ob.max_score, ob.max_score + G, [](float v) { return v < f_inf(); });
-    const bool gated = ob.min_matched && std::any_of(ob.min_matched, ob.min_matched + G, [](float v) { return v > 0.f; });
-    std::vector<float> bc(bounded ? np : 0);
-    for (size_t u = 0; u < bc.size(); ++u) bc[u] = exit_bound(score_bound(den[u / (size_t)n], ob.max_score[obj_of(u)]), P.nl[u]);
-    std::vector<ExTmpl> tm(np), sorted(np);
-    std::vector<int32_t> pobj(np);
-    std::vector<size_t> start((size_t)G + 1, 0);
-    bool any = false;
-    for (size_t u = 0; u < np; ++u) {
-        ExTmpl e = grid_tmpl(P, u, g, (int)u);
-        if (e.n == 0) { e.i0 = 0; e.i1 = -1; e.j0 = 0; e.j1 = -1; }
-        e.koff = bits_from_f(den[u / (size_t)n]);
-        any = any || (e.i0 <= e.i1 && e.j0 <= e.j1);
-        tm[u] = e;
-        pobj[u] = obj_of(u);
-        ++start[(size_t)pobj[u] + 1];
-    }
-    if (!any) return false;
-    for (int o = 0; o < G; ++o) start[(size_t)o + 1] += start[(size_t)o];
-    {
-        std::vector<size_t> at(start.begin(), start.end() - 1);
-        for (size_t u = 0; u < np; ++u) sorted[at[(size_t)pobj[u]]++] = tm[u];  // (pair order inside an object)
-    }
-    std::vector<float> need, tl;
-    if (gated || want_tl) {  // per pair: TL of its template and need = float32(min_matched[object] * TL)
-        std::vector<float> totals((size_t)t->T);
-        templates_matched_totals(t, totals.data());
-        tl.resize(np);
-        for (size_t u = 0; u < np; ++u) tl[u] = totals[u / (size_t)n];
-        if (gated) {
-            need.resize(np);
-            for (size_t u = 0; u < np; ++u) need[u] = ob.min_matched[obj_of(u)] * tl[u];
-        }
-    }
-    R.G = G;
-    R.tiles_x = (g.nx + kTileX - 1) / kTileX;
-    const size_t n_keys = (size_t)R.tiles_x * (size_t)((g.ny + kTileY - 1) / kTileY) * (kTileX * kTileY);
-    const size_t N = (size_t)g.nx * g.ny;
-    R.n_keys = n_keys;
-    R.o_tm = al256(P.lines.size() * sizeof(ExLine));
-    R.o_sorted = al256(R.o_tm + np * sizeof(ExTmpl));
-    R.o_foot = al256(R.o_sorted + np * sizeof(ExTmpl));
-    R.o_pobj = R.o_foot + (foot ? al256(np * sizeof(Foot)) : 0);
-    R.o_bc = R.o_pobj + (foot ? al256(np * sizeof(int32_t)) : 0);
-    R.o_len = R.o_bc + al256(bc.size() * sizeof(float));
-    R.o_need = R.o_len + (P.lens ? al256(P.len.size() * sizeof(float)) : 0);
-    R.o_tl = R.o_need + al256(need.size() * sizeof(float));
-    R.o_best = R.o_tl + (want_tl ? al256(np * sizeof(float)) : 0);
-    R.o_pair = R.o_best + al256((size_t)list * 8);
-    R.o_frac = R.o_pair + al256((size_t)list * 4);
-    R.o_keys = R.o_frac + al256((size_t)list * 4);
-    R.o_plane = R.o_keys + al256((size_t)G * n_keys * 8);
-    R.o_cand = R.o_plane + (planes4 ? al256((size_t)G * N * 4) : 0);
-    R.o_hull = al256(R.o_cand + (foot ? kNmsPartialBytes : 0));
-    reserve_eval(fm, R.o_hull + hull_bytes, R.o_pair + hull_bytes);
-    char* d = R.d = (char*)fm->search.eval.p;
-    char* h = (char*)fm->search.eval_stage.p;
-    std::memcpy(h, P.lines.data(), P.lines.size() * sizeof(ExLine));
-    std::memcpy(h + R.o_tm, tm.data(), np * sizeof(ExTmpl));
-    std::memcpy(h + R.o_sorted, sorted.data(), np * sizeof(ExTmpl));
-    if (foot) {
-        std::memcpy(h + R.o_foot, foot->data(), np * sizeof(Foot));
-        std::memcpy(h + R.o_pobj, pobj.data(), np * sizeof(int32_t));
-    }
-    if (bounded) std::memcpy(h + R.o_bc, bc.data(), np * sizeof(float));
-    if (P.lens) std::memcpy(h + R.o_len, P.len.data(), P.len.size() * sizeof(float));
-    if (gated) std::memcpy(h + R.o_need, need.data(), np * sizeof(float));
-    if (want_tl) std::memcpy(h + R.o_tl, tl.data(), np * sizeof(float));
-    std::memset(h + R.o_best, 0xff, (size_t)list * 8);  // kNoKey
-    hipStream_t st = fm->stream;
-    FDCM_HIP(hipMemcpyAsync(d, h, R.o_pair, hipMemcpyHostToDevice, st));
-    FDCM_HIP(hipMemsetAsync(d + R.o_keys, 0xff, (size_t)G * n_keys * 8, st));  // no key anywhere, in any plane
-    for (int o = 0; o < G; ++o) {
-        const int cnt = (int)(start[(size_t)o + 1] - start[(size_t)o]);
-        if (cnt == 0) continue;
-        const float ms = ob.max_score[o];
-        const bool need_o = gate_all && gated && ob.min_matched[o] > 0.f;
-        launch<kBest>(fm, P, g, (const ExLine*)d, (const ExTmpl*)(d + R.o_sorted) + start[(size_t)o], cnt, 0, portions_for(fm, g, cnt),
-                      nullptr, (unsigned long long*)(d + R.o_keys) + (size_t)o * n_keys, ms < f_inf() ? (const float*)(d + R.o_bc) : nullptr,
-                      ms < f_inf() ? ms : 0.f, need_o ? (const float*)(d + R.o_need) : nullptr);
-    }
-    return true;
-}
-
-// Object best map (include/fdcm.h, "Objects"): run_best_map_gated per plane.  The arguments are checked (fdcm_capi.cpp).
-void run_best_map_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g, int penalty,
-                          float tau, const int32_t* objects, int n_objects, const float* min_matched, float* score_out, int32_t* pair_out,
-                          float* matched_out) {
-    check_grid(g);
-    const size_t N = (size_t)g.nx * g.ny, GN = (size_t)n_objects * N;
-    auto none = [&]() {
-        if (score_out) std::fill(score_out, score_out + GN, f_nan());
-        if (pair_out) std::fill(pair_out, pair_out + GN, (int32_t)-1);
-        if (matched_out) std::fill(matched_out, matched_out + GN, f_nan());
-    };
-    if (t->T == 0) return none();
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    const int n = rot ? rot->n : 1;
-    if (rot) check_rotated_size(t, n);
-    Pairs P;
-    P.lens = matched_out != nullptr;
-    prepare_pairs(fm, t, rot, test_switches().matched_flat, P);
-    const std::vector<float> inf((size_t)n_objects, f_inf());
-    const ObjectsIn ob{objects, n_objects, inf.data(), min_matched, 0};
-    ObjectsRun R;
-    if (!objects_keys(fm, P, t, n, g, penalty, tau, ob, true, matched_out != nullptr, nullptr, kMaxK, true, R)) return none();
-    hipStream_t st = fm->stream;
-    char* plane = R.d + R.o_plane;  // G 4-byte planes: the scores, then the pairs, then the fractions
-    const dim3 grid((unsigned)((g.nx + 63) / 64), (unsigned)((g.ny + 3) / 4));
-    auto keys_of = [&](int o) { return (const unsigned long long*)(R.d + R.o_keys) + (size_t)o * R.n_keys; };
-    if (score_out) {
-        for (int o = 0; o < n_objects; ++o) {
-            hipLaunchKernelGGL(k_best_unpack, grid, dim3(256), 0, st, keys_of(o), g.nx, g.ny, R.tiles_x, (float*)plane + (size_t)o * N,
-                               (int*)nullptr);
-            FDCM_HIP(hipGetLastError());
-        }
-        FDCM_HIP(hipMemcpyAsync(score_out, plane, GN * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (pair_out) {
-        for (int o = 0; o < n_objects; ++o) {
-            hipLaunchKernelGGL(k_best_unpack, grid, dim3(256), 0, st, keys_of(o), g.nx, g.ny, R.tiles_x, (float*)nullptr,
-                               (int*)plane + (size_t)o * N);
-            FDCM_HIP(hipGetLastError());
-        }
-        FDCM_HIP(hipMemcpyAsync(pair_out, plane, GN * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (matched_out) {
-        auto kern = P.buf32 ? k_matched_plane<true> : k_matched_plane<false>;
-        for (int o = 0; o < n_objects; ++o) {
-            hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, fm->vol.as<float>(), P.SL, (int)fm->m, (int)fm->W, (int)fm->H, fm->tx, fm->ty,
-                               (const ExLine*)R.d, (const float*)(R.d + R.o_len), (const ExTmpl*)(R.d + R.o_tm),
-                               (const float*)(R.d + R.o_tl), keys_of(o), g.x0, g.y0, g.sx, g.sy, g.nx, g.ny, R.tiles_x,
-                               (float*)plane + (size_t)o * N);
-            FDCM_HIP(hipGetLastError());
-        }
-        FDCM_HIP(hipMemcpyAsync(matched_out, plane, GN * 4, hipMemcpyDeviceToHost, st));
-    }
-    FDCM_HIP(hipStreamSynchronize(st));
-}
-
-// Dense detections with objects (include/fdcm.h, "Objects"): detect_all on G planes.  The gate of FDCM_GATE_WINNER is
-// k_matched_gate on the planes of the objects with min_matched > 0; the rounds are plane_rounds' over all planes, with
-// the objects' table; the fractions and the records are detect_all's.  The arguments are checked (fdcm_capi.cpp).
 void run_search_exhaustive_detect_objects(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const fdcm_grid& g,
                                           const int32_t* objects, int n_objects, const float* max_score, const float* min_matched,
                                           int max_det, int permille, int cross, int margin, int penalty, float tau, int gate_kind,
                                           int32_t base, fdcm_match** out, int64_t* n_out, int32_t* boxes_out, float* matched_out) {
-    check_grid(g);
-    *n_out = 0;
-    if (t->T == 0) return;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    const int n = rot ? rot->n : 1;
-    if (rot) check_rotated_size(t, n);
-    const bool gate = min_matched && std::any_of(min_matched, min_matched + n_objects, [](float v) { return v > 0.f; });
-    const bool fracs = matched_out != nullptr, gate_all = gate && gate_kind == FDCM_GATE_ALL;
-    Pairs P;
-    P.lens = gate || fracs;
-    prepare_pairs(fm, t, rot, test_switches().matched_flat, P);
-    const std::vector<Foot> foot = pair_footprints(P, margin);
     const ObjectsIn ob{objects, n_objects, max_score, min_matched, cross};
-    const bool hull = t->footprint == FDCM_FOOTPRINT_HULL;
-    HullRun H;
-    if (hull) H.plan(foot);
-    ObjectsRun R;
-    if (!objects_keys(fm, P, t, n, g, penalty, tau, ob, gate_all, fracs, &foot, max_det, false, R, hull ? H.bytes() : 0)) return;
-    if (hull) H.upload(fm, R, P, foot, margin);
-    hipStream_t st = fm->stream;
-    char* d = R.d;
-    const float* vol = fm->vol.as<float>();
-    unsigned long long* keys = (unsigned long long*)(d + R.o_keys);
-    if (gate && !gate_all) {
-        auto kern = P.buf32 ? k_matched_gate<true> : k_matched_gate<false>;
-        for (int o = 0; o < n_objects; ++o) {
-            if (!(min_matched[o] > 0.f)) continue;
-            hipLaunchKernelGGL(kern, dim3((unsigned)(R.n_keys / 256)), dim3(256), 0, st, vol, P.SL, (int)fm->m, (int)fm->W, (int)fm->H,
-                               fm->tx, fm->ty, (const ExLine*)d, (const float*)(d + R.o_len), (const ExTmpl*)(d + R.o_tm),
-                               (const float*)(d + R.o_need), keys + (size_t)o * R.n_keys, (long long)R.n_keys, g.x0, g.y0, g.sx, g.sy,
-                               R.tiles_x);
-            FDCM_HIP(hipGetLastError());
-        }
-    }
-    plane_rounds(fm, R, g, n_objects, hull ? &H : nullptr, (const int*)(d + R.o_pobj), permille, cross, max_det);
-    if (fracs) matched_list(fm, P, R, g, max_det);
-    detect_records(fm, R, P, rot != nullptr, n, g, max_det, base, out, n_out, foot.data(), boxes_out, fracs ? matched_out : nullptr);
+    DetectIn c;
+    c.keys.ob = &ob;
+    c.keys.list = c.max_det = max_det;
+    c.flat = test_switches().matched_flat;
+    c.gate_kind = gate_kind;
+    c.permille = permille;
+    c.cross = cross;
+    c.margin = margin;
+    dense_detect(fm, t, rot, g, c, penalty, tau, base, out, n_out, boxes_out, matched_out);
 }
 
 float detect_score_bound(float den, float max_score) { return score_bound(den, max_score); }
@@ -3017,7 +2889,7 @@ static void detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const f
     for (int64_t j = 0; j < n_jobs; ++j) m0[(size_t)j + 1] = m0[(size_t)j] + jobs[j].na;
     std::vector<RotM> Mjob(rot ? (size_t)m0[nj] : 0);
     const std::vector<float> den = best_denominators(t, penalty, tau);
-    std::vector<float> totals, need;
+    std::vector<float> totals, need;  // per template
     std::vector<float> ms;  // (objects) per template: its object's threshold
     bool gated = min_matched > 0.f;
     if (ob) {
@@ -3025,12 +2897,7 @@ static void detect_windows(fdcm_featuremap* fm, const fdcm_templates* t, const f
         ms.resize((size_t)t->T);
         for (size_t i = 0; i < ms.size(); ++i) ms[i] = ob->max_score[ob->objects[i]];
     }
-    if (gated) {  // need = float32(min_matched * TL) of the template
-        totals.resize((size_t)t->T);
-        templates_matched_totals(t, totals.data());
-        need.resize(totals.size());
-        for (size_t i = 0; i < need.size(); ++i) need[i] = (ob ? ob->min_matched[ob->objects[i]] : min_matched) * totals[i];
-    }
+    if (gated) matched_needs(t, 1, true, [&](size_t i) { return ob ? ob->min_matched[ob->objects[i]] : min_matched; }, totals, need);
     const WinnersIn wn{den.data(), need.empty() ? nullptr : need.data(), gate == FDCM_GATE_ALL, margin, max_score, keys.data(),
                        boxes.data(), ob ? ms.data() : nullptr};
     const bool flat = test_switches().windows_flat || test_switches().matched_flat;

@@ -40,10 +40,10 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              and 4 KB of tables per such plane a round, instead of 256 MB (run_search_exhaustive_windows)
 //   FDCM_WINDOWS_FLAT          the pose-window search with 64-bit flat addresses (windows_round), the scoring and the winners'
 //                              pass of the detections over pose windows with it
-//   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (detect_all, run_best_map_gated,
-//                              run_matched_fractions, run_search_exhaustive_detect_windows: its scoring, its winners' pass and
-//                              its fractions; run_matches: the verify pass of the calls on match lists, which also take
-//                              their bins from the host under FDCM_FORCE_HOST_BINS)
+//   FDCM_MATCHED_FLAT          the calls by matched fraction with 64-bit flat addresses (dense_detect and best_maps with a
+//                              gate or objects, run_matched_fractions, run_search_exhaustive_detect_windows: its scoring,
+//                              its winners' pass and its fractions; run_matches: the verify pass of the calls on match
+//                              lists, which also take their bins from the host under FDCM_FORCE_HOST_BINS)
 //   FDCM_COVERAGE_PART=1..     records a part of the scene coverage of a match list holds at most, instead of what 768 MB of
 //                              table hold (run_matches_coverage)
 //   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
