@@ -906,8 +906,9 @@ int fdcm_search_exhaustive_detect_windows_objects(const fdcm_featuremap* fm, con
  * = 0: no two returned shapes share a pixel (their boxes may).  (5) Identity (3) of "Objects" holds for a hull set.  (6)
  * Results are a function of the inputs alone.  (7) n_objects = 1 gives the calls without objects, byte for byte.
  * Calls that honour the kind: fdcm_search_exhaustive_detect_nms, _detect_all, _detect_all_matched, _detect_all_gated,
- * _detect_objects, _detect_windows, _detect_windows_gated, _detect_windows_objects.  fdcm_search_exhaustive_detect (radius),
- * every call without an overlap, fdcm_search, the pipeline and the shards ignore it.
+ * _detect_objects, _detect_windows, _detect_windows_gated, _detect_windows_objects, and fdcm_matches_detect_objects ("Match
+ * lists: objects and hull shapes").  fdcm_search_exhaustive_detect (radius), fdcm_matches_detect, every call without an overlap,
+ * fdcm_search, the pipeline and the shards ignore it.
  * Span tables: fdcm_templates_footprint_spans and fdcm_lines_footprint_spans (host only, whatever the set's kind) give the
  * shapes of every pair u = t n + a.  row_offsets: P + 1 int64 (P = T n); pair u has the rows row_offsets[u] ..
  * row_offsets[u + 1], row r at y = box(u).y0 + (r - row_offsets[u]); areas: P int64, or NULL; spans: 2 int32 (xl, xr) per row
@@ -1131,7 +1132,7 @@ int fdcm_scene_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_t 
  *      `margin`: floor(min x) - margin, floor(min y) - margin, floor(max x) + margin, floor(max y) + margin in int64, clamped to
  *      [-2^25, 2^25].  A template without lines, a NaN end point or an invalid record: the empty box (0, 0, -1, -1).  An
  *      infinite end point does not empty the box: its floor is far outside the clamp.  The kind of a hull set is ignored, as
- *      Scene coverage ignores it: the shape is the box.
+ *      Scene coverage ignores it: the shape is the box (fdcm_matches_detect_objects, below, honours it).
  *      Candidates S_0 of fdcm_matches_detect: the records that are valid with a template that has lines, admissible, whose
  *      q_j = v_j / den(t) is not NaN, has a clear sign bit and is <= max_score, and, when min_matched > 0, have
  *      ML >= need_t = float32(min_matched * TL_t).  v_j = r.score with rescore = 0 and s(r) with rescore = 1; the denominators
@@ -1175,6 +1176,63 @@ int fdcm_matches_detect(const fdcm_featuremap* fm, const fdcm_templates* templat
                         int32_t margin, int penalty, float tau, float min_matched, int rescore, fdcm_match** out, int64_t* n_out,
                         int32_t* indices_out /* max_detections, or NULL */, int32_t* boxes_out /* max_detections x 4, or NULL */,
                         float* matched_out /* max_detections, or NULL */);
+
+/* ---- Match lists: objects and hull shapes.  fdcm_matches_detect with the template set's objects and its kind of footprint
+ *      (README.md, "Match lists: objects and hull shapes"; the referee is tests/match_objects_ref.py).  Everything not restated
+ *      is taken unchanged.  From "Match lists": valid record, P(r), bins, admissibility, cost_i, s(r), ML, TL, frac, F(r), q_j,
+ *      key(j) = (bits of q_j << 32) | j, the three input forms, rescore.  From "Objects": objects, G, per-object max_score and
+ *      min_matched, cross_permille, the suppression test with two limits.  From "Hull footprints": vertices, the shape row by
+ *      row, I, U.
+ *      Object of record j: o_j = objects[t_j].
+ *      Candidates S_0: the valid records whose template has lines, that are admissible, with q_j not NaN, its sign bit clear,
+ *      q_j <= max_score[o_j] and, where min_matched[o_j] > 0, ML >= need_t = float32(min_matched[o_j] * TL_t).
+ *      Shape of record j: F(j) = F(r_j) at `margin` for a BOX set.  For a HULL set P(j) is "Hull footprints"' shape on the
+ *      vertices of the posed end points P(r_j): float32 posing as fdcm_matches_verify, every coordinate floored in int64, the
+ *      four corners -+ margin when margin > 0, clamped to [-2^25, 2^25].  Its bounding box is F(r_j), so boxes_out does not
+ *      depend on the kind.
+ *      Rule: the greedy rule on S_0 by key, stopping at max_detections.  d suppresses e when 1000 I > overlap_permille U and
+ *      o_e = o_d, or when 1000 I > cross_permille U and o_e != o_d; I and U on boxes (BOX set) or on shapes (HULL set), in
+ *      int64.
+ *      Output: fdcm_matches_detect's: the records {r.tmpl_idx, q, r.transform}, indices_out, boxes_out, matched_out.  The object
+ *      of a record is objects[tmpl_idx - base]; there is no separate output for it.
+ *      Identities.  (1) G = 1 on a BOX set gives fdcm_matches_detect's bytes at max_score[0] and min_matched[0], whatever
+ *      cross_permille is.  (2) With cross_permille = 1000 and max_detections not reached, the records are the merge by key of
+ *      fdcm_matches_detect, per object, on the list with every record of another object made invalid (tmpl_idx = base - 1, so
+ *      positions stay), for a BOX set.  (3) overlap = cross = 1000 on a HULL set gives the BOX set's records.  (4) A HULL set
+ *      whose posed end points always contain the four corners of their bounding box gives the BOX records at any overlap and
+ *      margin.  (5) overlap = cross = 0 on a HULL set: no two returned shapes share a pixel (their boxes may).  (6)
+ *      Relabelling the objects by a bijection, the per-object arrays permuted alike, changes no byte.  (7) For integer
+ *      templates and records {1, 0, x, 0, 1, y} with whole x, y and rescore = 1, the records, boxes and fractions are those of
+ *      fdcm_search_exhaustive_detect_windows_objects on the one-point jobs (t, 0, 1, x, y, 1, 1) in list order, on the same set
+ *      at the same thresholds with rot NULL, byte for byte.  (8) With one max_score for all objects, the records for any
+ *      max_score are the leading records with score <= max_score of the +inf list.  (9) The three input forms give the same
+ *      bytes; results are a function of the inputs alone.
+ *      Span tables, fdcm_lines_footprint_spans' layout with one shape per record: fdcm_matches_footprint_spans (host only,
+ *      whatever the set's kind) gives the shape of every record, no rows for an invalid one; fdcm_matches_shapes gives the
+ *      same table from the device kernel for the records that are valid and admissible on fm and whose template has lines,
+ *      the others with no rows and area 0 (matches NULL is no form of it: n sizes the outputs).
+ *      The device.  The pass of fdcm_matches_detect with a threshold and a need per template (its object's) writes the object of
+ *      every record beside its key and box.  On a HULL set a scan over the candidates' box heights gives every candidate its
+ *      rows of the span table, and one 8-byte read brings their total to the host; k_matches_shapes, a wave per candidate,
+ *      then builds rows and area by gift wrapping over the posed end points, in int64 throughout.  The rounds are the list form
+ *      of the detections over pose windows with objects and shapes, unchanged; the list never returns to the host.
+ *      FDCM_EINVAL, before any GPU work: everything fdcm_matches_detect rejects; n_objects outside 1 .. 256; max_score NULL, or
+ *      an entry NaN or < 0; an entry of min_matched NaN or outside [0, 1]; cross_permille outside 0 .. 1000; objects NULL for a
+ *      set with templates, or an entry outside [0, n_objects); row_offsets NULL.  After the pass, on a HULL set and in
+ *      fdcm_matches_shapes: a span table of the candidates of more than 2^26 rows ("cut the list with max_score or fdcm_topk
+ *      first").  Empty inputs give FDCM_OK and nothing (row_offsets and areas all 0). ---- */
+int fdcm_matches_detect_objects(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n,
+                                int on_device, int32_t tmpl_index_base, const int32_t* objects /* T */, int32_t n_objects,
+                                const float* max_score /* G */, const float* min_matched /* G, or NULL */, int32_t max_detections,
+                                int32_t overlap_permille, int32_t cross_permille, int32_t margin, int penalty, float tau, int rescore,
+                                fdcm_match** out, int64_t* n_out, int32_t* indices_out /* max_detections, or NULL */,
+                                int32_t* boxes_out /* max_detections x 4, or NULL */, float* matched_out /* max_detections, or NULL */);
+int fdcm_matches_footprint_spans(const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int32_t tmpl_index_base,
+                                 int32_t margin, int64_t* row_offsets /* n + 1 */, int64_t* areas /* n, or NULL */,
+                                 int32_t* spans /* 2 per row, or NULL */);
+int fdcm_matches_shapes(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int on_device,
+                        int32_t tmpl_index_base, int32_t margin, int64_t* row_offsets /* n + 1 */, int64_t* areas /* n, or NULL */,
+                        int32_t* spans /* 2 per row, or NULL */);
 
 /* ---- Match lists: scene coverage and selection.  fdcm_scene_coverage and fdcm_scene_select for match records instead of
  *      poses: the cue that runs from the scene to the template, for the records of fdcm_search.  Every definition not restated

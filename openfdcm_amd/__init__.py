@@ -1306,6 +1306,48 @@ def detect_matches(featuremap, templates, matches, max_score=float("inf"), overl
     return (MatchList(res[0]),) + tuple(res[1:]) if isinstance(res, tuple) else MatchList(res)
 
 
+def detect_matches_objects(featuremap, templates, matches, objects=None, max_score=float("inf"), overlap=0.3, cross_overlap=None,
+                           max_detections=1024, penalty=None, margin=0, line_caps=None, min_matched=None, rescore=False,
+                           n_objects=None, return_indices=False, return_boxes=False, return_matched=False, return_objects=False,
+                           device_ptr=None, n=0):
+    """detect_matches for a template list that holds views of several parts, on the list's kind of footprint.  objects[t]
+    (0 .. G - 1) is the part of template t (None: one object); max_score and min_matched are a scalar or one value per
+    object; a record drops the records of its own object whose footprints overlap its own by more than `overlap` and those
+    of other objects by more than cross_overlap (None: equal to overlap; 1 lets the objects ignore each other).  For
+    with_footprint(templates, "hull") the footprint of a record is the lattice points of the convex hull of its posed end
+    points, built on the device for every candidate record -- the shape that tells two parallel rods at 45 degrees apart,
+    whose boxes overlap -- and objects=None is the way to get it without labels.  n_objects None means max(objects) + 1.
+    Returns detect_matches' results, and with return_objects the (k,) int32 objects of the records last.  The other arguments
+    are detect_matches'."""
+    kind, tau = _penalty_args(penalty)
+    permille = int(round(1000 * float(overlap)))
+    cross = permille if cross_overlap is None else int(round(1000 * float(cross_overlap)))
+    fm, tset = _device_map(featuremap), _template_cache.get(templates, line_caps)
+    obj = _np.zeros(tset.count, dtype=_np.int32) if objects is None else _np.asarray(objects)
+    res = fm.detect_matches_objects(tset, matches, obj, max_score, n_objects=n_objects, overlap_permille=permille, cross_permille=cross,
+                                    max_detections=max_detections, penalty=kind, tau=tau, margin=margin, min_matched=min_matched,
+                                    rescore=rescore, indices=return_indices, boxes=return_boxes, matched=return_matched,
+                                    device_ptr=device_ptr, n=n)
+    res = res if isinstance(res, tuple) else (res,)
+    res += (obj.reshape(-1).astype(_np.int32)[res[0]["tmpl_idx"]],) if return_objects else ()
+    res = (MatchList(res[0]),) + tuple(res[1:])
+    return res if len(res) > 1 else res[0]
+
+
+def match_footprint_spans(templates, matches, margin=0):
+    """The hull shapes of the posed lines of every record of a match list, as detect_matches_objects uses them on a "hull"
+    list: (row_offsets, spans, areas), record j having the rows row_offsets[j] .. row_offsets[j + 1] of spans, row r at
+    y = y0 of match_footprints()[j] + (r - row_offsets[j]), its pixels xl .. xr in the frame of that box, (0, -1) when the row
+    is empty.  Host only."""
+    return _engine.match_footprint_spans(_template_cache.get(templates), matches, margin)
+
+
+def match_shapes(featuremap, templates, matches, margin=0, device_ptr=None, n=0):
+    """match_footprint_spans from the device kernel, for the records that lie inside the feature map (the others have no rows
+    and area 0).  matches: a MatchList or a record array, or device_ptr and n."""
+    return _device_map(featuremap).match_shapes(_template_cache.get(templates), matches, margin=margin, device_ptr=device_ptr, n=n)
+
+
 def verify_matches(featuremap, templates, matches, line_caps=None, device_ptr=None, n=0):
     """Which lines of a match were found: (scores, fractions, costs) of every record of a match list, the forms of which are
     detect_matches'.  costs is an (n, Lmax) float32 array, the uncapped cost of every line of the record's template posed by

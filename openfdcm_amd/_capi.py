@@ -259,6 +259,11 @@ SYMBOLS = [
     ("fdcm_matches_detect", C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int,
                                       C.c_float, C.c_float, C.c_int, C.POINTER(_vp), _i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       _fp]),
+    ("fdcm_matches_detect_objects", C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _fp, _fp,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_float, C.c_int, C.POINTER(_vp),
+                                              _i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp]),
+    ("fdcm_matches_footprint_spans", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _i64p, _i64p, C.POINTER(C.c_int32)]),
+    ("fdcm_matches_shapes", C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int32, C.c_int32, _i64p, _i64p, C.POINTER(C.c_int32)]),
     ("fdcm_matches_coverage", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, C.c_int64, C.c_int, C.c_int32,
                                         C.POINTER(CoverageParams), C.POINTER(C.c_int32), _vp]),
     ("fdcm_matches_select", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, C.c_int64, C.c_int, C.c_int32,

@@ -1371,6 +1371,64 @@ int fdcm_matches_detect(const fdcm_featuremap* fm, const fdcm_templates* templat
     });
 }
 
+// Match lists with objects and hull shapes: include/fdcm.h, "Match lists: objects and hull shapes".  fdcm_matches_detect's
+// checks with the per-object arrays in place of its two thresholds, then the labels; the one refusal behind GPU work is the
+// span table's size (run_matches).
+int fdcm_matches_detect_objects(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n,
+                                int on_device, int32_t tmpl_index_base, const int32_t* objects, int32_t n_objects, const float* max_score,
+                                const float* min_matched, int32_t max_detections, int32_t overlap_permille, int32_t cross_permille,
+                                int32_t margin, int penalty, float tau, int rescore, fdcm_match** out, int64_t* n_out,
+                                int32_t* indices_out, int32_t* boxes_out, float* matched_out) {
+    return guarded([&] {
+        check_match_list(matches, n, on_device);
+        std::vector<float> ms, mm;
+        check_object_limits(n_objects, max_score, true, min_matched, ms, mm);
+        check_detect_limits(max_detections, overlap_permille, &cross_permille, margin);
+        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
+        require(std::isfinite(tau), "tau must be finite");
+        require(rescore == 0 || rescore == 1, "rescore must be 0 or 1");
+        require(out && n_out, "null output");
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_object_labels(templates, objects, n_objects);
+        last_search_matches(fm, matches, n, on_device);
+        const MatchesDetect det{0.f, max_detections, overlap_permille, margin, penalty, tau, 0.f, rescore};
+        const MatchesObjectsIn ob{objects, n_objects, ms.data(), min_matched ? mm.data() : nullptr, cross_permille};
+        records_call(out, [&] {
+            run_matches(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, &det, nullptr, nullptr,
+                        nullptr, out, n_out, indices_out, boxes_out, matched_out, &ob, nullptr);
+        });
+    });
+}
+
+int fdcm_matches_footprint_spans(const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int32_t tmpl_index_base,
+                                 int32_t margin, int64_t* row_offsets, int64_t* areas, int32_t* spans) {
+    return guarded([&] {
+        require(n >= 0, "n is negative");
+        require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
+        require(n == 0 || matches, "matches is null");
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(row_offsets != nullptr, "row_offsets is null");
+        require(templates != nullptr, "templates is null");
+        matches_footprint_spans(templates, matches, n, tmpl_index_base, margin, row_offsets, areas, spans);
+    });
+}
+
+int fdcm_matches_shapes(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int on_device,
+                        int32_t tmpl_index_base, int32_t margin, int64_t* row_offsets, int64_t* areas, int32_t* spans) {
+    return guarded([&] {
+        check_match_list(matches, n, on_device);
+        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
+        require(row_offsets != nullptr, "row_offsets is null");
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        require(matches || on_device || n == 0, "matches is null");  // (the rows are sized by n: the last search is no form here)
+        const MatchesShapesOut so{margin, row_offsets, areas, spans};
+        run_matches(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &so);
+    });
+}
+
 // Scene coverage: include/fdcm.h, "Scene coverage".  The line costs' checks, then the call's own; everything that needs no handle
 // first, and nothing on the device.
 // The checks fdcm_scene_coverage and fdcm_scene_select share, in the section's order: the pose list, the parameters and the

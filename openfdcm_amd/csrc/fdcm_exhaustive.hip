@@ -32,10 +32,14 @@
 //                                     detections over pose windows: a thread per job turns the job's merged k = 1 list into
 //                                     its entry of the winners' list (normalised key, footprint), for the list forms of
 //                                     k_nms_round; objects (include/fdcm.h, "Objects"): the same pass with a threshold per pair
-//   k_matches_verify<BUF32, CAP>, k_matches_gather
+//   k_matches_verify<BUF32, CAP, OBJ>, k_matches_gather
 //                                     match lists (include/fdcm.h, "Match lists"): a wave per record of search() turns it into
 //                                     line costs, a score, a matched fraction, a box and a key for the list form of
 //                                     k_nms_round; the gather writes the result records into pinned memory (at the file's end)
+//   k_shape_rows<PHASE>, k_matches_shapes
+//                                     match lists with hull shapes ("Match lists: objects and hull shapes"): the rows of every
+//                                     candidate record by a scan, and a wave per record that wraps the hull of its posed end
+//                                     points and writes its row spans and area, what hull_rows writes on the host
 //   hull_suppresses, hull_stage       hull footprints (include/fdcm.h, "Hull footprints"): the overlap test on shapes, the
 //                                     lattice points of the convex hull of a pair's end points as row spans, for template
 //                                     sets of that kind; sets of kind BOX run the round's box forms
@@ -3181,7 +3185,7 @@ void coverage_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fd
 
 // ---- match lists (include/fdcm.h, "Match lists"): the records of the reference's own path, {tmpl_idx, score, transform[6]}
 // with a free float transform, verified and suppressed on the device.
-//   k_matches_verify<BUF32, CAP>   a wave per record, a lane per line of its template in rounds of 64.  The record comes by
+//   k_matches_verify<BUF32, CAP, OBJ>  a wave per record, a lane per line of its template in rounds of 64.  The record comes by
 //                                  wave-uniform loads; the lines and lengths are the set's resident d_lines and d_lengths.
 //                                  Pass 1 poses every end point (transform, math.h:341-344: unfused float32), decides
 //                                  admissibility by the seam's rule (k_evaluate at translation (0, 0)) and reduces the box
@@ -3193,7 +3197,8 @@ void coverage_pairs(const fdcm_featuremap* fm, const fdcm_templates* t, const fd
 //                                  after round), ML in line order (matched_length's rule).  Lane 0 writes the record's
 //                                  score, fraction, q, key and box straight into the list form's arrays.
 //   k_matches_gather               the result keys as 64-byte entries (record with q, box, fraction, position) in pinned memory
-// The rounds between them are nms_rounds' list form, k_nms_round<true, false, false>, unchanged.
+// The rounds between them are nms_rounds' list form, k_nms_round<true, false, false>, unchanged (with objects <true, false, true>,
+// on a hull set <true, true, true>).
 namespace {
 
 struct MatchesArgs {
@@ -3221,8 +3226,17 @@ struct MatchesArgs {
     int4* boxes;
 };
 
-template <bool BUF32, bool CAP>
-__global__ void __launch_bounds__(256) k_matches_verify(const MatchesArgs a) {
+// (OBJ) what the pass with objects reads and writes beside MatchesArgs ("Match lists: objects and hull shapes"): the threshold
+// of a record is its template's object's, as its need is (host-made tables, as detect_windows makes ms and need), and the
+// record's object goes to the rounds.  Without OBJ nothing of it is read.
+struct MatchesObjArgs {
+    const float* ms;   // per template: max_score[objects[t]]
+    const int* tobj;   // per template: objects[t]
+    int* obj;          // per record: its object when it is valid, admissible and has lines (it may need a shape), else -1
+};
+
+template <bool BUF32, bool CAP, bool OBJ>
+__global__ void __launch_bounds__(256) k_matches_verify(const MatchesArgs a, const MatchesObjArgs ob) {
     const int lane = threadIdx.x & 63;
     const int j = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
     if (j >= a.n) return;  // wave-uniform
@@ -3236,6 +3250,7 @@ __global__ void __launch_bounds__(256) k_matches_verify(const MatchesArgs a) {
             a.score[j] = f_nan(); a.frac[j] = f_nan(); a.q[j] = f_nan();
             a.keys_out[j] = kNoKey;
             a.boxes[j] = make_int4(0, 0, -1, -1);
+            if (OBJ) ob.obj[j] = -1;
         }
         return;
     }
@@ -3303,15 +3318,17 @@ __global__ void __launch_bounds__(256) k_matches_verify(const MatchesArgs a) {
     if (lane == 0) {
         const float s = adm ? res : f_nan();
         const float qv = (a.rescore ? s : R.score) / a.den[t];
-        bool cand = nl > 0 && adm && !f_isnan(qv) && !f_signbit(qv) && qv <= a.max_score;
+        bool cand = nl > 0 && adm && !f_isnan(qv) && !f_signbit(qv) && qv <= (OBJ ? ob.ms[t] : a.max_score);
         if (cand && a.need) cand = ml >= a.need[t];
         a.score[j] = s;
         a.frac[j] = adm ? matched_fraction(ml, a.tl[t]) : f_nan();
         a.q[j] = qv;
         a.keys_out[j] = cand ? ((unsigned long long)__float_as_uint(qv) << 32) | (unsigned)j : kNoKey;
         a.boxes[j] = box;
+        if (OBJ) ob.obj[j] = nl > 0 && adm ? ob.tobj[t] : -1;
     }
 }
+
 
 struct MatchOut {  // one result of the detect call
     fdcm_match rec;  // the record with q for its score
@@ -3342,6 +3359,179 @@ __global__ void __launch_bounds__(256) k_matches_gather(const unsigned long long
     out[l] = o;
 }
 
+// ---- the shapes of a match list on the device (include/fdcm.h, "Match lists: objects and hull shapes"): per record that
+// needs one, the rows and the area of the convex hull of its posed end points, what hull_of and hull_rows make on the host.
+//   k_shape_rows<PHASE>   the rows each record has in the span table, by a scan over the box heights in three launches:
+//                         0: the sum of each run of 256 records; 1: one workgroup turns the sums into their exclusive prefix
+//                         and writes the total behind them; 2: HullShape{0, row0, 0} of every record.
+//   k_matches_shapes      a wave per record.  Gift wrapping from the lowest, leftmost vertex: each step poses the template's
+//                         resident lines again, a lane per line, and takes the vertex that has no other to its right, the
+//                         farthest of collinear ones, by a wave reduction on exact cross products.  Every hull edge updates
+//                         xl / xr of the rows it reaches; row r of the box belongs to lane r % 64 from the first write to the
+//                         last, so nothing is shared.  A last pass moves the rows into the box's frame and sums the area.
+// Every loop is bounded by the vertex count or the box height; nothing waits, nothing is atomic.
+struct ShapesArgs {
+    const float4* tlines;
+    const long long* toff;
+    const fdcm_match* rec;
+    const unsigned long long* keys;  // the records with a key need a shape; null: those with an object
+    const int* obj;
+    const int4* boxes;
+    HullShape* shapes;
+    long long* sums;  // ceil(n / 256) + 1
+    int2* spans;
+    int n, base, margin;
+};
+
+__device__ __forceinline__ long long shape_rows_of(const ShapesArgs& a, int j) {
+    if (j >= a.n || !(a.keys ? a.keys[j] != kNoKey : a.obj[j] >= 0)) return 0;
+    const int4 b = a.boxes[j];
+    return b.w < b.y ? 0 : (long long)b.w - b.y + 1;
+}
+
+// exclusive prefix of v over the 256 threads of a workgroup and their total (sw: 4 words of LDS, a barrier inside)
+__device__ __forceinline__ long long block_scan_excl64(long long v, long long* sw, long long& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long o = __shfl_up(incl, d);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) sw[wave] = incl;
+    __syncthreads();
+    long long before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long long s = sw[k];
+        if (k < wave) before += s;
+        total += s;
+    }
+    return before + incl - v;
+}
+
+template <int PHASE>
+__global__ void __launch_bounds__(256) k_shape_rows(const ShapesArgs a) {
+    __shared__ long long sw[4];
+    const int nb = (a.n + 255) / 256;
+    long long total;
+    if (PHASE == 1) {  // one workgroup: thread i owns the sums [i per, (i + 1) per)
+        const int per = (nb + 255) / 256, b0 = min(nb, (int)threadIdx.x * per), b1 = min(nb, b0 + per);
+        long long mine = 0;
+        for (int b = b0; b < b1; ++b) mine += a.sums[b];
+        long long at = block_scan_excl64(mine, sw, total);
+        for (int b = b0; b < b1; ++b) {
+            const long long v = a.sums[b];
+            a.sums[b] = at;
+            at += v;
+        }
+        if (threadIdx.x == 0) a.sums[nb] = total;
+        return;
+    }
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const long long rows = shape_rows_of(a, j);
+    const long long before = block_scan_excl64(rows, sw, total);
+    if (PHASE == 0) {
+        if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
+    } else if (j < a.n) {  // (a table of more than 2^26 rows is refused before a row0 is read)
+        a.shapes[j] = HullShape{0, (int)min(a.sums[blockIdx.x] + before, 0x7fffffffll), 0};
+    }
+}
+
+__device__ __forceinline__ long long floor_div_dev(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+// The candidate (px, py) against the best (bx, by) of a step from (cx, cy); (bx, by) == (cx, cy): none yet.  All vertices lie
+// in a cone of less than 180 degrees at a hull vertex, so "to the right of" orders their directions.
+__device__ __forceinline__ void shape_better(int cx, int cy, int px, int py, int& bx, int& by) {
+    if (px == cx && py == cy) return;
+    const long long ux = bx - cx, uy = by - cy, vx = px - cx, vy = py - cy;
+    const long long cr = ux * vy - uy * vx;  // < 0: p lies to the right of c -> b
+    if ((ux == 0 && uy == 0) || cr < 0 || (cr == 0 && vx * vx + vy * vy > ux * ux + uy * uy)) { bx = px; by = py; }
+}
+
+// xl / xr of the rows the edge (ax, ay) - (ex, ey) reaches, hull_rows' arithmetic; sp: the record's rows, y0 its first.
+__device__ __forceinline__ void shape_edge(int ax, int ay, int ex, int ey, int y0, int rows, int2* sp, int lane) {
+    if (ay > ey) { int t = ax; ax = ex; ex = t; t = ay; ay = ey; ey = t; }
+    const int r0 = ay - y0, r1 = ey - y0;
+    const int first = r0 + ((lane - r0) & 63);  // the first row >= r0 of this lane
+    const int iters = first > r1 ? 0 : (r1 - first) / 64 + 1;
+    const long long dy = (long long)ey - ay, dx = (long long)ex - ax;
+    for (int k = 0; k < iters; ++k) {
+        const int r = first + 64 * k;
+        if ((unsigned)r >= (unsigned)rows) continue;  // (never: the box is the vertices' own)
+        int lo, hi;
+        if (dy == 0) {
+            lo = min(ax, ex); hi = max(ax, ex);
+        } else {  // x* = num / dy, exact
+            const long long num = (long long)ax * dy + dx * (long long)(r - r0);
+            const long long q = floor_div_dev(num, dy);
+            hi = (int)q;
+            lo = (int)(q + (num - q * dy != 0 ? 1 : 0));
+        }
+        int2 s = sp[r];
+        s.x = min(s.x, lo); s.y = max(s.y, hi);
+        sp[r] = s;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_matches_shapes(const ShapesArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int j = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (j >= a.n) return;  // wave-uniform
+    const int4 box = a.boxes[j];
+    const int rows = (int)shape_rows_of(a, j);
+    if (rows <= 0) return;  // wave-uniform: no shape
+    const fdcm_match R = a.rec[j];
+    const long long t = (long long)R.tmpl_idx - (long long)a.base;  // valid: the record has a key or an object
+    const long long l0 = a.toff[t];
+    const int nl = (int)(a.toff[t + 1] - l0);
+    const MatchTransform M{R.transform[0], R.transform[1], R.transform[2], R.transform[3], R.transform[4], R.transform[5]};
+    int2* const sp = a.spans + a.shapes[j].row0;
+    const int m = a.margin, corners = m > 0 ? 4 : 1;
+    for (int r = lane; r < rows; r += 64) sp[r] = make_int2(0x7fffffff, (int)0x80000000);
+    // every vertex of the lines of this lane: per end point the corners clamp(floor(v) -+ m), hull_of's
+    auto vertices = [&](auto&& f) {
+        for (int i = lane; i < nl; i += 64) {
+            const float4 p = match_pose_line(M, a.tlines[l0 + i]);
+            for (int e = 0; e < 2; ++e) {
+                const float fx = e ? p.z : p.x, fy = e ? p.w : p.y;
+                for (int k = 0; k < corners; ++k) f(matches_side(fx, k & 1 ? m : -m), matches_side(fy, k & 2 ? m : -m));
+            }
+        }
+    };
+    // the start: the lowest vertex, the leftmost of those
+    long long sk = 0x7fffffffffffffffll;
+    vertices([&](int x, int y) { sk = min(sk, (long long)(((unsigned long long)(unsigned)(y + (1 << 26)) << 32) | (unsigned)(x + (1 << 26)))); });
+    for (int d = 32; d >= 1; d >>= 1) sk = min(sk, (long long)__shfl_xor(sk, d));
+    const int sx = __builtin_amdgcn_readfirstlane((int)(unsigned)sk - (1 << 26));
+    const int sy = __builtin_amdgcn_readfirstlane((int)(unsigned)(sk >> 32) - (1 << 26));
+    const long long steps = (long long)nl * 2 * corners + 1;  // the hull has at most V vertices
+    int cx = sx, cy = sy;
+    for (long long step = 0; step < steps; ++step) {
+        int bx = cx, by = cy;
+        vertices([&](int x, int y) { shape_better(cx, cy, x, y, bx, by); });
+        for (int d = 32; d >= 1; d >>= 1) {
+            const int ox = __shfl_xor(bx, d), oy = __shfl_xor(by, d);
+            shape_better(cx, cy, ox, oy, bx, by);
+        }
+        bx = __builtin_amdgcn_readfirstlane(bx);
+        by = __builtin_amdgcn_readfirstlane(by);
+        shape_edge(cx, cy, bx, by, box.y, rows, sp, lane);  // (one vertex: the edge from it to itself)
+        if ((bx == cx && by == cy) || (bx == sx && by == sy)) break;  // wave-uniform
+        cx = bx; cy = by;
+    }
+    long long area = 0;
+    for (int r = lane; r < rows; r += 64) {
+        const int2 s = sp[r];
+        const bool none = s.x > s.y;
+        if (!none) area += (long long)s.y - s.x + 1;
+        sp[r] = none ? make_int2(0, -1) : make_int2(s.x - box.x, s.y - box.x);
+    }
+    for (int d = 32; d >= 1; d >>= 1) area += __shfl_xor(area, d);
+    if (lane == 0) a.shapes[j].area = area;
+}
+
 // P(r) of a valid record on the host: the kernel's arithmetic (the Makefile's -ffp-contract=off keeps it unfused here too).
 void pose_lines(const fdcm_templates* t, int64_t tmpl, const float* M, std::vector<float>& out) {
     const int64_t l0 = t->offsets[(size_t)tmpl], nl = t->offsets[(size_t)tmpl + 1] - l0;
@@ -3369,6 +3559,28 @@ void matches_footprints(const fdcm_templates* t, const fdcm_match* matches, int6
             F = footprint(posed.data(), 4, (int64_t)(posed.size() / 4), margin);
         }
         std::memcpy(boxes_out + 4 * j, &F, sizeof F);
+    }
+}
+
+// Host only: the hull shape of every record ("Match lists: objects and hull shapes"), hull_of and hull_rows on P(r).
+void matches_footprint_spans(const fdcm_templates* t, const fdcm_match* matches, int64_t n, int32_t base, int margin, int64_t* row_offsets,
+                             int64_t* areas, int32_t* spans) {
+    std::vector<float> posed;
+    std::vector<HullPt> h;
+    row_offsets[0] = 0;
+    for (int64_t j = 0; j < n; ++j) {
+        const int64_t tm = (int64_t)matches[j].tmpl_idx - base;
+        Foot F{0, 0, -1, -1};
+        if (tm >= 0 && tm < t->T) {
+            pose_lines(t, tm, matches[j].transform, posed);
+            F = footprint(posed.data(), 4, (int64_t)(posed.size() / 4), margin);
+        }
+        row_offsets[j + 1] = row_offsets[j] + foot_rows(F);
+        if (areas) areas[j] = 0;
+        if ((!areas && !spans) || foot_rows(F) == 0) continue;
+        hull_of(posed.data(), 4, (int64_t)(posed.size() / 4), margin, h);
+        const int64_t A = hull_rows(h, F, spans ? spans + 2 * row_offsets[j] : nullptr);
+        if (areas) areas[j] = A;
     }
 }
 
@@ -3406,11 +3618,23 @@ void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_
 // verify call, whose outputs are scores_out, fractions_out and costs_out (each may be null).  Else the detect call: the
 // rounds on the verify pass's keys and boxes, then the gather.  One reserve_eval lays out the whole call: the upload (host
 // records, caps, denominators, needs, totals, host bins), the list's arrays, the result list and the rounds' partials.
+// objects_in (fdcm_matches_detect_objects) and shapes_out (fdcm_matches_shapes): fdcm_internal.h; with neither, nothing of
+// "Match lists: objects and hull shapes" is laid out, launched or read.
 void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
                  const MatchesDetect* det, float* scores_out, float* fractions_out, float* costs_out, fdcm_match** out, int64_t* n_out,
-                 int32_t* indices_out, int32_t* boxes_out, float* matched_out) {
+                 int32_t* indices_out, int32_t* boxes_out, float* matched_out, const MatchesObjectsIn* objects_in,
+                 const MatchesShapesOut* shapes_out) {
     if (n_out) *n_out = 0;
+    if (shapes_out) std::fill_n(shapes_out->row_offsets, n + 1, (int64_t)0);
+    if (shapes_out && shapes_out->areas) std::fill_n(shapes_out->areas, n, (int64_t)0);
     if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
+    // The calls of "Match lists: objects and hull shapes".  The shapes call is the pass with one object and no threshold, whose
+    // table of objects says which records are valid and admissible and have lines.
+    const std::vector<int32_t> one_object(shapes_out ? (size_t)t->T : 0, 0);
+    const float no_limit = f_inf();
+    const MatchesObjectsIn all{one_object.data(), 1, &no_limit, nullptr, 1000};
+    const MatchesObjectsIn* const ob = shapes_out ? &all : objects_in;
+    const bool hull = shapes_out || (ob && t->footprint == FDCM_FOOTPRINT_HULL);
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
     begin(fm);
     hipStream_t st = fm->stream;
@@ -3418,7 +3642,8 @@ void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match*
     const bool flat = test_switches().matched_flat;
     const size_t SL = ivol_slice_floats(fm->W, fm->H);
     const bool buf32 = !flat && (size_t)fm->m * SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
-    const bool gated = det && det->min_matched > 0.f;
+    const bool gated = ob ? ob->min_matched && std::any_of(ob->min_matched, ob->min_matched + ob->G, [](float v) { return v > 0.f; })
+                          : det && det->min_matched > 0.f;
     const std::vector<float> den = best_denominators(t, det ? det->penalty : -1, det ? det->tau : 1.f);
     std::vector<float> totals(T);
     templates_matched_totals(t, totals.data());
@@ -3426,19 +3651,31 @@ void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match*
     matches_host_bins(fm, t, matches, n, on_device, base, bins);
     const int max_det = det ? det->max_detections : 0;
     const size_t o_caps = on_device ? 0 : al256(N * sizeof(fdcm_match)), o_den = o_caps + (t->capped ? al256((size_t)t->n_lines * 4) : 0),
-                 o_need = o_den + al256(T * 4), o_tl = o_need + (gated ? al256(T * 4) : 0), o_bins = o_tl + al256(T * 4),
+                 o_need = o_den + al256(T * 4), o_tl = o_need + (gated ? al256(T * 4) : 0), o_ms = o_tl + al256(T * 4),
+                 o_tobj = o_ms + (ob ? al256(T * 4) : 0), o_bins = o_tobj + (ob ? al256(T * 4) : 0),
                  o_score = o_bins + (bins.empty() ? 0 : al256(bins.size() * 2)), o_frac = o_score + al256(N * 4), o_q = o_frac + al256(N * 4),
                  o_keys = o_q + al256(N * 4), o_box = o_keys + al256(N * 8), o_costs = o_box + al256(N * 16),
                  o_best = o_costs + (costs_out ? al256(N * Lmax * 4) : 0), o_pk = o_best + al256((size_t)max_det * 8),
-                 total = o_pk + 2 * kNmsWorkgroups * 8;
+                 o_obj = o_pk + 2 * kNmsWorkgroups * 8, o_shape = o_obj + (ob ? al256(N * 4) : 0),
+                 o_sums = o_shape + (hull ? al256(N * sizeof(HullShape)) : 0), total = o_sums + (hull ? al256(((N + 255) / 256 + 1) * 8) : 0);
     reserve_eval(fm, total, o_score);
     char* d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
     if (!on_device) std::memcpy(h, matches, N * sizeof(fdcm_match));
     if (t->capped) std::memcpy(h + o_caps, t->caps.data(), (size_t)t->n_lines * 4);
     std::memcpy(h + o_den, den.data(), T * 4);
-    if (gated)
+    if (gated && !ob)
         for (size_t i = 0; i < T; ++i) ((float*)(h + o_need))[i] = det->min_matched * totals[i];  // need = float32(min_matched * TL)
+    if (gated && ob)  // the need of the template's object; an object without a gate: every ML passes
+        for (size_t i = 0; i < T; ++i) {
+            const float mm = ob->min_matched[ob->objects[i]];
+            ((float*)(h + o_need))[i] = mm > 0.f ? mm * totals[i] : -f_inf();
+        }
+    if (ob)
+        for (size_t i = 0; i < T; ++i) {
+            ((float*)(h + o_ms))[i] = ob->max_score[ob->objects[i]];
+            ((int32_t*)(h + o_tobj))[i] = ob->objects[i];
+        }
     std::memcpy(h + o_tl, totals.data(), T * 4);
     if (!bins.empty()) std::memcpy(h + o_bins, bins.data(), bins.size() * 2);
     FDCM_HIP(hipMemcpyAsync(d, h, o_score, hipMemcpyHostToDevice, st));
@@ -3453,16 +3690,64 @@ void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match*
     a.bins = bins.empty() ? nullptr : (const unsigned short*)(d + o_bins);
     a.rec = on_device ? matches : (const fdcm_match*)d;
     a.n = (int)n; a.base = base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax;
-    a.margin = det ? det->margin : 0; a.rescore = det ? det->rescore : 0;
+    a.margin = det ? det->margin : shapes_out ? shapes_out->margin : 0; a.rescore = det ? det->rescore : 0;
     a.max_score = det ? det->max_score : f_inf();
     a.score = (float*)(d + o_score); a.frac = (float*)(d + o_frac); a.q = (float*)(d + o_q);
     a.costs = costs_out ? (float*)(d + o_costs) : nullptr;
     a.keys_out = (unsigned long long*)(d + o_keys);
     a.boxes = (int4*)(d + o_box);
-    auto kern = buf32 ? (t->capped ? k_matches_verify<true, true> : k_matches_verify<true, false>)
-                      : (t->capped ? k_matches_verify<false, true> : k_matches_verify<false, false>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, a);
+    auto kern = buf32 ? (t->capped ? k_matches_verify<true, true, false> : k_matches_verify<true, false, false>)
+                      : (t->capped ? k_matches_verify<false, true, false> : k_matches_verify<false, false, false>);
+    auto kern_ob = buf32 ? (t->capped ? k_matches_verify<true, true, true> : k_matches_verify<true, false, true>)
+                         : (t->capped ? k_matches_verify<false, true, true> : k_matches_verify<false, false, true>);
+    const MatchesObjArgs oa{(const float*)(d + o_ms), (const int*)(d + o_tobj), (int*)(d + o_obj)};
+    hipLaunchKernelGGL(ob ? kern_ob : kern, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, a, ob ? oa : MatchesObjArgs{});
     FDCM_HIP(hipGetLastError());
+    // Hull shapes: the rows of every record that needs a shape by a scan on the device, whose total alone comes to the host,
+    // for the limit and for the size of the span table; then the shapes.  The table is a buffer of its own, so nothing here
+    // moves the workspace the pass has written; under FDCM_POISON it holds the word wherever the kernel does not write.
+    ShapesArgs sa{};
+    if (hull) {
+        sa.tlines = a.tlines; sa.toff = a.toff; sa.rec = a.rec;
+        sa.keys = shapes_out ? nullptr : a.keys_out;
+        sa.obj = (const int*)(d + o_obj);
+        sa.boxes = a.boxes;
+        sa.shapes = (HullShape*)(d + o_shape);
+        sa.sums = (long long*)(d + o_sums);
+        sa.n = a.n; sa.base = base; sa.margin = a.margin;
+        const unsigned nb = (unsigned)((N + 255) / 256);
+        hipLaunchKernelGGL(k_shape_rows<0>, dim3(nb), dim3(256), 0, st, sa);
+        hipLaunchKernelGGL(k_shape_rows<1>, dim3(1), dim3(256), 0, st, sa);
+        hipLaunchKernelGGL(k_shape_rows<2>, dim3(nb), dim3(256), 0, st, sa);
+        FDCM_HIP(hipGetLastError());
+        long long rows = 0;
+        FDCM_HIP(hipMemcpyAsync(&rows, sa.sums + nb, 8, hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+        if (rows > kHullMaxRows)
+            throw std::string("match lists: the span table of the candidates has more than 2^26 rows: cut the list with max_score or "
+                              "fdcm_topk first");
+        if (shapes_out) shapes_out->row_offsets[n] = rows;
+        DevBuf& table = fm->search.eval_spans;
+        table.reserve(std::max<size_t>(8, (size_t)rows * 8));
+        poison_fill(table, st, FDCM_FILL_EVAL);  // (counted with the workspace it belongs to)
+        sa.spans = table.as<int2>();
+        if (!shapes_out || shapes_out->areas || shapes_out->spans) {
+            hipLaunchKernelGGL(k_matches_shapes, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, sa);
+            FDCM_HIP(hipGetLastError());
+        }
+    }
+    if (shapes_out) {
+        std::vector<HullShape> shapes(N);
+        FDCM_HIP(hipMemcpyAsync(shapes.data(), sa.shapes, N * sizeof(HullShape), hipMemcpyDeviceToHost, st));
+        if (shapes_out->spans && shapes_out->row_offsets[n])
+            FDCM_HIP(hipMemcpyAsync(shapes_out->spans, sa.spans, (size_t)shapes_out->row_offsets[n] * 8, hipMemcpyDeviceToHost, st));
+        FDCM_HIP(hipStreamSynchronize(st));
+        for (size_t j = 0; j < N; ++j) {
+            shapes_out->row_offsets[j] = shapes[j].row0;
+            if (shapes_out->areas) shapes_out->areas[j] = shapes[j].area;
+        }
+        return;
+    }
     if (!det) {
         if (scores_out) FDCM_HIP(hipMemcpyAsync(scores_out, d + o_score, N * 4, hipMemcpyDeviceToHost, st));
         if (fractions_out) FDCM_HIP(hipMemcpyAsync(fractions_out, d + o_frac, N * 4, hipMemcpyDeviceToHost, st));
@@ -3479,7 +3764,12 @@ void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match*
     r.n = (long long)n;
     r.n_chunks = (r.n + 255) / 256;
     r.permille = det->overlap_permille;
-    r.cross = det->overlap_permille;
+    r.cross = ob ? ob->cross : det->overlap_permille;
+    if (ob) r.obj = (const int*)(d + o_obj);
+    if (hull) {
+        r.shapes = sa.shapes;
+        r.spans = sa.spans;
+    }
     r.pk_out = (unsigned long long*)(d + o_pk);
     r.best = d_best;
     nms_rounds(r, (unsigned)std::min<long long>(kNmsWorkgroups, r.n_chunks), max_det, st);

@@ -52,7 +52,8 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              their own switches
 //   FDCM_POISON=<uint32>       (decimal or 0x-hex) what a call finds in memory it did not write: the whole capacity of a
 //                              buffer holds the word before the call's first write (poison_fill; DESIGN.md sections 22 and
-//                              32).  reserve_eval: search.eval and search.eval_stage.  run_build: the whole allocation of the
+//                              32).  reserve_eval: search.eval and search.eval_stage (and run_matches the span table of a match
+//                              list's shapes, search.eval_spans, counted as a fill of eval).  run_build: the whole allocation of the
 //                              volume, padding included (an adopted volume is not touched), ivol, bitmap, coldesc, colmask,
 //                              labels, edge_parent, edge_roots, pyr, offtab, stack, plan and the pinned build.stage.
 //                              run_search: scene, pairs, records, flags, work, counter, bins, the pinned stage, bins_stage
@@ -266,10 +267,12 @@ struct SearchBuffers {
     DevBuf eval;      // fdcm_featuremap_evaluate / _minmax_translation, exhaustive search: lines, translations, work items, results
     DevBuf counter;   // the search's counters
     DevBuf bins;      // orientation bins per candidate line from the host libm (only when it differs from the device's atanf)
+    DevBuf eval_spans;  // the span table of the shapes of a match list: sized once the device has counted its rows, while eval
+                        // holds the pass's results (reserve_eval could move them); FDCM_POISON fills it as a part of eval
     PinnedBuf stage, bins_stage, eval_stage;  // host side of the uploads into scene (and the tail's denominators), bins, eval
     PinnedBuf cnt;    // the search's counters, written by k_scatter (device-output searches)
     void release() {
-        for (DevBuf* b : {&scene, &pairs, &records, &flags, &out, &work, &tail, &tail_out, &eval, &counter, &bins}) b->release();
+        for (DevBuf* b : {&scene, &pairs, &records, &flags, &out, &work, &tail, &tail_out, &eval, &eval_spans, &counter, &bins}) b->release();
         for (PinnedBuf* b : {&stage, &bins_stage, &eval_stage, &cnt}) b->release();
     }
 };
@@ -490,10 +493,31 @@ struct MatchesDetect {
     float tau, min_matched;
     int rescore;
 };
+// "Match lists: objects and hull shapes".  objects_in: the detect call with objects, which honours the set's kind of footprint
+// (objects: T checked labels; max_score: G floats; min_matched: G floats or null; det's max_score and min_matched are not
+// read).  shapes_out: the shapes call (det null), the table of every valid admissible record with lines from the device kernel:
+// row_offsets n + 1, areas n or null, spans 2 per row or null.
+struct MatchesObjectsIn {
+    const int32_t* objects;
+    int G;
+    const float* max_score;
+    const float* min_matched;
+    int cross;
+};
+struct MatchesShapesOut {
+    int margin;
+    int64_t* row_offsets;
+    int64_t* areas;
+    int32_t* spans;
+};
 void matches_footprints(const fdcm_templates* t, const fdcm_match* matches, int64_t n, int32_t base, int margin, int32_t* boxes_out);
+// host only: the hull shape of every record, lines_footprint_spans' layout (an invalid record: no rows)
+void matches_footprint_spans(const fdcm_templates* t, const fdcm_match* matches, int64_t n, int32_t base, int margin, int64_t* row_offsets,
+                             int64_t* areas, int32_t* spans);
 void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
                  const MatchesDetect* det, float* scores_out, float* fractions_out, float* costs_out, fdcm_match** out, int64_t* n_out,
-                 int32_t* indices_out, int32_t* boxes_out, float* matched_out);
+                 int32_t* indices_out, int32_t* boxes_out, float* matched_out, const MatchesObjectsIn* objects_in = nullptr,
+                 const MatchesShapesOut* shapes_out = nullptr);
 // the bins of every posed line from the host libm, [record][max_lines], where fdcm_orientation_bins_mode() is 1 (else empty); the
 // handle has its stream
 void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,

@@ -735,6 +735,42 @@ class DeviceFeatureMap:
         res += (fr[:k.value].copy(),) if matched else ()
         return res if len(res) > 1 else res[0]
 
+    def detect_matches_objects(self, templates, matches, objects, max_score, n_objects=None, overlap_permille=300, cross_permille=None,
+                               max_detections=1024, penalty=None, tau=1.0, margin=0, min_matched=None, rescore=False, tmpl_index_base=0,
+                               indices=False, boxes=False, matched=False, device_ptr=None, n=0):
+        """fdcm_matches_detect_objects (include/fdcm.h, "Match lists: objects and hull shapes"): detect_matches with objects --
+        objects[t] the object of template t, max_score and min_matched a scalar or one value per object, overlap_permille
+        between records of one object and cross_permille (None: the same) between records of different objects -- on the
+        set's kind of footprint: the box, or for a "hull" set the hull of the posed end points, built on the device.  The
+        outputs and the forms of matches are detect_matches'."""
+        obj, G, ms, mm = object_arrays(objects, n_objects, templates.count, max_score, min_matched)
+        ptr, n, on_device, keep = self._match_input(matches, device_ptr, n)
+        out, k = C.c_void_p(), C.c_int64()
+        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0
+        ji = np.zeros(md, dtype=np.int32)
+        fp = np.zeros((md, 4), dtype=np.int32)
+        fr = np.zeros(md, dtype=np.float32)
+        capi.check(capi.lib().fdcm_matches_detect_objects(
+            self._h, templates._h, ptr, n, on_device, int(tmpl_index_base), obj.ctypes.data_as(C.POINTER(C.c_int32)), G,
+            capi.fptr(ms) if ms is not None else None, capi.fptr(mm) if mm is not None else None, int(max_detections),
+            int(overlap_permille), int(overlap_permille if cross_permille is None else cross_permille), int(margin),
+            -1 if penalty is None else int(penalty), float(tau), int(bool(rescore)), C.byref(out), C.byref(k),
+            ji.ctypes.data_as(C.POINTER(C.c_int32)) if indices and md else None,
+            fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None, capi.fptr(fr) if matched and md else None))
+        res = (_adopt_matches(out, k.value),) + ((ji[:k.value].copy(),) if indices else ()) + ((fp[:k.value].copy(),) if boxes else ())
+        res += (fr[:k.value].copy(),) if matched else ()
+        return res if len(res) > 1 else res[0]
+
+    def match_shapes(self, templates, matches, margin=0, tmpl_index_base=0, device_ptr=None, n=0):
+        """fdcm_matches_shapes: match_footprint_spans' table from the device kernel, for the records that are valid and
+        admissible on this map and whose template has lines; the others have no rows and area 0.  (row_offsets, spans, areas).
+        matches: a MatchList or record array on the host, or device_ptr and n."""
+        if matches is None and not device_ptr:
+            raise ValueError("match_shapes takes host records or device_ptr and n")
+        ptr, n, on_device, keep = self._match_input(matches, device_ptr, n)
+        return _spans_result(n, 1, lambda off, areas, spans: capi.check(capi.lib().fdcm_matches_shapes(
+            self._h, templates._h, ptr, n, on_device, int(tmpl_index_base), int(margin), off, areas, spans)))
+
     def scene_coverage(self, labels, templates, poses, cs=None, pivots=None, radius=2, bin_tolerance=1, margin=None, residual=False):
         """Scene coverage (include/fdcm.h, "Scene coverage"): per pose (tmpl, a, x, y), as line_costs takes them, the number of
         edge pixels of `labels` in the pose's window (its footprint at `margin`, None: radius) and how many of them the posed
@@ -946,6 +982,17 @@ def lines_footprint_spans(templates, cs=None, pivots=None, margin=0):
     return _spans_result(T, 1 if rot is None else rot.n, lambda off, areas, spans: capi.check(capi.lib().fdcm_lines_footprint_spans(
         capi.fptr(flat), offsets.ctypes.data_as(C.POINTER(C.c_int64)), T, C.byref(rot) if rot is not None else None, int(margin), off,
         areas, spans)))
+
+
+def match_footprint_spans(templates, matches, margin=0, tmpl_index_base=0):
+    """fdcm_matches_footprint_spans: the hull shape of every record of a match list (include/fdcm.h, "Match lists: objects and
+    hull shapes"), whatever the set's kind: (row_offsets, spans, areas) in lines_footprint_spans' layout with one shape per
+    record, row r of record j at y = y0 of match_footprints()[j] + (r - row_offsets[j]); no rows for an invalid record.  Host
+    only.  templates: a DeviceTemplates."""
+    rec = match_records(matches)
+    ptr = C.c_void_p(rec.ctypes.data) if rec.shape[0] else None
+    return _spans_result(rec.shape[0], 1, lambda off, areas, spans: capi.check(capi.lib().fdcm_matches_footprint_spans(
+        templates._h, ptr, rec.shape[0], int(tmpl_index_base), int(margin), off, areas, spans)))
 
 
 class DeviceTemplates:
