@@ -1282,6 +1282,63 @@ int fdcm_matches_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_
                         int32_t* selected_out /* max_selected */, int32_t* counts_out /* max_selected x 3 */, int64_t* n_out,
                         uint8_t* residual_out /* width * height where the labels are, or NULL */);
 
+/* ---- Match lists: refinement.  Every record of a match list searched exhaustively in a small box of (delta rotation, dx, dy)
+ *      around its own transform and replaced by its best pose, on the device in one call (README.md, "Match lists: refinement";
+ *      the referee is tests/refine_ref.py).  fdcm_search takes a record's rotation from one aligned pair of lines and its
+ *      translation from a walk along one scene line, so a record near a true pose is typically a degree or two and a few
+ *      pixels off; the calls above judge it at that pose.  This is the pose windows' answer for records whose transform is a
+ *      free float matrix: fdcm_matches_refine, then fdcm_matches_detect.  "Match lists"' definitions apply unchanged: matches, n,
+ *      on_device and tmpl_index_base (matches NULL with on_device = 0: the records of the last fdcm_search on fm), valid record,
+ *      t, M, the set's caps.
+ *      Delta table: rot holds na = rot->n pairs (c, s) and optional pivots, one per template, in template coordinates (NULL:
+ *      the origin); all values finite.  rot NULL: na = 1 and nothing is rotated.
+ *      Lines of run position e: Q_e(t) is the rotated template of "Rotations" for (c, s) = cs[e] and the pivot of t: each end
+ *      point goes to ((c x + (-s) y) + m.x, (s x + c y) + m.y), float32, unfused.  P_e(r) is Q_e(t) posed by M with the
+ *      arithmetic of "Match lists": ((M0 x + M1 y) + M2, (M3 x + M4 y) + M5).  With rot NULL P_0(r) = P(r): the lines go through no
+ *      identity rotation.  The bin of a line is closestOrientation of the posed, untranslated line of P_e(r), as
+ *      fdcm_matches_verify computes it; where fdcm_orientation_bins_mode() is 1 the bins come from the host.
+ *      Window: i in -hx .. hx and j in -hy .. hy; the translation is tau = (i sx, j sy); N = (2 hx + 1)(2 hy + 1);
+ *      g = (j + hy)(2 hx + 1) + (i + hx).
+ *      Score of (r, e, i, j): the score of the lines P_e(r) at translation tau -- the seam's offset T + tau (summed first in
+ *      float32, then added to each coordinate), truncation, the set's caps, Eigen's sum() order.  Without caps it is bit for
+ *      bit fdcm_featuremap_evaluate(P_e(r), tau).  The pose is admissible by the seam's rule for P_e(r) at tau.  A NaN score has
+ *      no key, as in fdcm_search_exhaustive_windows.
+ *      Key: (score bits << 32) | low, low = 0 for the centre pose (e, i, j) = (centre, 0, 0) and 1 + e N + g for every other.
+ *      centre is the run position of the unrotated delta, or -1 for none (with rot NULL: 0 or -1).  Ties go to the centre first,
+ *      then to the lowest e, then to the lowest g: on a plateau of equal scores (saturated caps) a record stays where it was.
+ *      Winner of r: the admissible, keyed pose with the smallest key.  None when r is not valid, its template has no lines, no
+ *      pose of its window is admissible, or every admissible pose scores NaN.
+ *      Output, aligned with the input: with a winner out[j] = {r.tmpl_idx, score, M'} and pose_out[j] = (e, i, j); without
+ *      one out[j] = {r.tmpl_idx, NaN, r.transform} and pose_out[j] = (-1, 0, 0).  A NaN score is never a candidate of
+ *      fdcm_matches_detect, so the list can go straight on.  out may be the input buffer.
+ *      M', float32, unfused, left to right: M0' = (M0 c + M1 s), M1' = (M0 (-s) + M1 c), M3' = (M3 c + M4 s),
+ *      M4' = (M3 (-s) + M4 c), M2' = ((M0 m.x + M1 m.y) + M2) + float32(i sx), M5' = ((M3 m.x + M4 m.y) + M5) + float32(j sy).
+ *      With rot NULL the four rotation entries are copied, M2' = M2 + float32(i sx) and M5' = M5 + float32(j sy).
+ *      out.score is not s(out).  As with the search, the score is that of the posed lines P_e(r) at a translation, and the
+ *      stored matrix has rotation and translation folded in; posing the template again with M' rounds differently.  s(out) is
+ *      usually close to out.score but is not its bits, and a record on the map's border can come out not admissible.
+ *      Identities.  rot NULL and hx = hy = 0: out.score is s(r) of fdcm_matches_verify bit for bit and the transform is
+ *      unchanged as floats.  For records {1, 0, 0, 0, 1, 0} on a set none of whose rotated coordinates is a zero, with
+ *      centre = -1, scores and poses are the k = 1 records of fdcm_search_exhaustive_windows for the job (t, 0, na, -hx sx,
+ *      -hy sy, 2 hx + 1, 2 hy + 1), bit for bit, and the transforms are equal as floats.  A wider window with the same table
+ *      never raises a score; with the centre in the table the refined score of an admissible record is at most s(r).
+ *      Permuting the list permutes the output.  Results are a function of the inputs alone: the three forms of matches give
+ *      the same bytes.
+ *      The device.  Everything is made on the device; no per-record table comes from the host (but the bins, where the host's
+ *      libm makes them: device records then cost a download).  A pose pass, a wave per (record, e) and a lane per line, writes
+ *      the lines and bins of P_e(r) and, from the extremes of the posed coordinates, the admissible box of the window; a scoring
+ *      pass over the implicit table of 4 x 16 patches of every window keeps each patch's smallest key; a last pass takes each
+ *      record's smallest key and writes out and pose_out.  Device memory stays below 1 GB for any n: the list is worked through
+ *      in parts; one record is never cut, and its na x Lmax lines of 32 bytes go up together, as a job of the pose windows.
+ *      FDCM_EINVAL, before any GPU work: everything fdcm_matches_verify rejects about handles, n, on_device and matches; what the
+ *      rotations calls reject about rot; centre outside -1 .. na - 1; hx or hy outside 0 .. 4096; sx or sy outside 1 .. 4096;
+ *      na N > 65536; out NULL with n > 0; out_on_device not 0 or 1.  n = 0, an empty feature map or an empty template set
+ *      give FDCM_OK and write nothing.  The call blocks; concurrent callers of one feature map take turns. ---- */
+int fdcm_matches_refine(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n,
+                        int on_device, int32_t tmpl_index_base, const fdcm_rotations* rot /* delta table, or NULL */,
+                        int32_t centre, int32_t hx, int32_t hy, int32_t sx, int32_t sy, fdcm_match* out /* n records */,
+                        int out_on_device, int32_t* pose_out /* n x 3 host, or NULL */);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

@@ -1358,6 +1358,38 @@ def verify_matches(featuremap, templates, matches, line_caps=None, device_ptr=No
     return fm.verify_matches(tset, matches, device_ptr=device_ptr, n=n)
 
 
+def delta_angles(half_steps, step):
+    """The 2 * half_steps + 1 delta angles (-half_steps .. half_steps) * step in radians, float64, for refine_matches; the zero
+    is exact, at index half_steps."""
+    return _np.arange(-int(half_steps), int(half_steps) + 1, dtype=_np.float64) * float(step)
+
+
+def refine_matches(featuremap, templates, matches, angles=None, pivot="center", half_x=0, half_y=0, stride=1, line_caps=None,
+                   return_poses=False, device_ptr=None, n=0, out_device_ptr=None):
+    """The pose of every record of a match list refined on the device: search() takes a record's rotation from one aligned
+    pair of lines and its translation from a walk along one scene line, so a record near a true pose is typically a degree
+    or two and a few pixels off.  Every record is searched exhaustively in its own small box of poses: the delta rotations
+    `angles` (radians, delta_angles(..); None: none) about `pivot` in template coordinates ("center", None for the origin or a
+    (T, 2) array), times the translations (i * sx, j * sy) with |i| <= half_x, |j| <= half_y and stride an int or (sx, sy).
+    The record is replaced by the best pose of its box -- its score the sum of the line costs there, clamped to line_caps --
+    with ties going to the pose it had (the delta whose (cos, sin) is exactly (1, 0), with no translation).  A record whose
+    box holds no pose inside the map, or whose tmpl_idx is outside the list, keeps its transform and scores NaN, which
+    detect_matches never keeps: search -> refine_matches -> detect_matches is the chain.  matches follows detect_matches: a
+    MatchList or a record array, None for the records of the last search() on this feature map, or device_ptr and n for a
+    device buffer; out_device_ptr: a device buffer the records go to instead (it may be device_ptr), None standing in their
+    place.  Returns a MatchList aligned with the input, and with return_poses also the (n, 3) int32 rows (angle index, i, j),
+    (-1, 0, 0) for a record without a pose."""
+    fm, tset = _device_map(featuremap), _template_cache.get(templates, line_caps)
+    sx, sy = _strides(stride)
+    cs = None if angles is None else _angles(angles)
+    pv = None if angles is None else _pivots(templates, pivot, tset.count)
+    res = fm.refine_matches(tset, matches, cs=cs, pivots=pv, hx=half_x, hy=half_y, sx=sx, sy=sy, poses=return_poses, device_ptr=device_ptr,
+                            n=n, out_device_ptr=out_device_ptr)
+    recs = res[0] if return_poses else res
+    recs = None if recs is None else MatchList(recs)
+    return (recs, res[1]) if return_poses else recs
+
+
 def match_coverage(featuremap, labels, templates, matches, radius=2, bin_tolerance=1, margin=None, return_residual=False,
                    device_ptr=None, n=0):
     """scene_coverage for what search() returns: which edge pixels of labels each record explains, the record posed by its

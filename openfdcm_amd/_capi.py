@@ -269,6 +269,8 @@ SYMBOLS = [
     ("fdcm_matches_select", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, C.c_int64, C.c_int, C.c_int32,
                                       C.POINTER(CoverageParams), C.POINTER(SelectParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i64p,
                                       _vp]),
+    ("fdcm_matches_refine", C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int32, C.POINTER(Rotations), C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, _vp, C.c_int, C.POINTER(C.c_int32)]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),
     ("fdcm_lines_free", None, [C.POINTER(C.c_float)]),

@@ -1371,6 +1371,31 @@ int fdcm_matches_detect(const fdcm_featuremap* fm, const fdcm_templates* templat
     });
 }
 
+// Match lists, refinement: include/fdcm.h, "Match lists: refinement".  The list's checks, then the delta table, the window, the
+// outputs and last the handles (the pivots need the set's template count).
+int fdcm_matches_refine(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int on_device,
+                        int32_t tmpl_index_base, const fdcm_rotations* rot, int32_t centre, int32_t hx, int32_t hy, int32_t sx, int32_t sy,
+                        fdcm_match* out, int out_on_device, int32_t* pose_out) {
+    return guarded([&] {
+        check_match_list(matches, n, on_device);
+        if (rot) check_rotations(rot);  // null: nothing rotated, a table of one delta
+        const int32_t na = rot ? rot->n : 1;
+        require(centre >= -1 && centre < na, "centre must be in [-1, na - 1]");
+        require(hx >= 0 && hx <= 4096 && hy >= 0 && hy <= 4096, "hx and hy must be in [0, 4096]");
+        require(sx >= 1 && sx <= 4096 && sy >= 1 && sy <= 4096, "sx and sy must be in [1, 4096]");
+        require((int64_t)na * (2 * hx + 1) * (int64_t)(2 * hy + 1) <= 65536, "na (2 hx + 1) (2 hy + 1) must be at most 65536");
+        require(n == 0 || out, "out is null");
+        require(out_on_device == 0 || out_on_device == 1, "out_on_device must be 0 or 1");
+        require(fm && templates, "null featuremap/templates");
+        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        if (rot) check_pivots(templates, rot);
+        last_search_matches(fm, matches, n, on_device);
+        require(n == 0 || out, "out is null");
+        run_matches_refine(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, rot, centre, hx, hy, sx,
+                           sy, out, out_on_device != 0, pose_out);
+    });
+}
+
 // Match lists with objects and hull shapes: include/fdcm.h, "Match lists: objects and hull shapes".  fdcm_matches_detect's
 // checks with the per-object arrays in place of its two thresholds, then the labels; the one refusal behind GPU work is the
 // span table's size (run_matches).

@@ -3794,4 +3794,308 @@ void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match*
     *n_out = k;
 }
 
+// ---- match lists: refinement (include/fdcm.h, "Match lists: refinement"): every record's own box of (delta rotation, dx, dy)
+// searched exhaustively, the record replaced by its best pose.  Nothing per record comes from the host (but the bins, where
+// the host's libm makes them).  A plane is one (record, run position e); every record has the same window, so the table of
+// patches is implicit: item = plane * patches per plane + patch.
+//   k_refine_pose                 a wave per plane, a lane per line in rounds of 64: the ExLine entries of P_e(r) (Q_e(t) by
+//                                 "Rotations"' arithmetic, posed by M as match_pose_line; the bin by atanf_glibc +
+//                                 closest_orientation as k_matches_verify, or the host's), the extremes of the posed coordinates
+//                                 by wave reductions, and from them the admissible box in window indices: float addition is
+//                                 monotone, so a column or a row is admissible exactly when its two extreme coordinates are
+//                                 -- decided before any read of the volume
+//   k_refine_score<BUF32, CAP>    a wave per item, a lane per translation of a 4 x 16 patch of the window as
+//                                 k_exhaustive_windows; a patch that misses the box reads nothing, a lane outside the box
+//                                 reads at the box's corner; rows_score<BUF32, 1, CAP>, unchanged; the patch's smallest key by a
+//                                 wave reduction, one 8-byte store per item
+//   k_refine_write                a wave per record: the smallest of its items' keys, then lane 0 writes the record and its pose
+// No atomics: an item's key has one writer, and the minimum of a record's keys does not depend on an order.
+namespace {
+
+struct RefinePlane {
+    int n;               // lines to score; 0: nothing (invalid record, no lines, an empty box)
+    int i0, i1, j0, j1;  // the admissible box in window indices, i in [0, 2 hx], j in [0, 2 hy]
+    int pad[3];
+};
+static_assert(sizeof(RefinePlane) == 32, "RefinePlane is 32 bytes");
+
+struct RefineArgs {
+    const float* vol;
+    size_t SL;
+    int m, W, H;
+    float tx, ty;
+    const float* keys;           // the map's m orientation keys
+    const float4* tlines;        // the set's resident lines and offsets
+    const long long* toff;
+    const float* caps;           // per line of the set, or null: none
+    const float* cs;             // na pairs (c, s), or null: nothing rotated
+    const float* pivots;         // T pairs, or null: the origin
+    const unsigned short* bins;  // [record of the part][e][Lmax] from the host libm, or null
+    const fdcm_match* rec;       // the whole list
+    int r0, nr;                  // the part: records r0 .. r0 + nr - 1
+    int base, T, Lmax, na, centre, hx, hy, sx, sy;
+    int ppx, ppp;                // patches per window row, per plane
+    bool buf32;
+    ExLine* lines;               // [plane of the part][Lmax]
+    RefinePlane* planes;
+    unsigned long long* ikeys;   // per item of the part
+    fdcm_match* out;             // the whole list's
+    int* pose;                   // n x 3, or null
+};
+
+// [R | m] of run position e for template t, rot_matrix's arithmetic
+__device__ __forceinline__ RotM refine_rot(const RefineArgs& a, int e, long long t) {
+    const float c = a.cs[2 * e], s = a.cs[2 * e + 1];
+    const float px = a.pivots ? a.pivots[2 * t] : 0.f, py = a.pivots ? a.pivots[2 * t + 1] : 0.f;
+    const float ns = -s;
+    return RotM{c, ns, s, px - (c * px + ns * py), py - (s * px + c * py)};
+}
+
+__global__ void __launch_bounds__(256) k_refine_pose(const RefineArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int p = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (p >= a.nr * a.na) return;  // wave-uniform
+    const int rl = p / a.na, e = p - rl * a.na;
+    const fdcm_match R = a.rec[a.r0 + rl];
+    const long long t = (long long)R.tmpl_idx - (long long)a.base;
+    RefinePlane P{0, 0, -1, 0, -1, {0, 0, 0}};
+    const bool valid = t >= 0 && t < a.T;
+    const long long l0 = valid ? a.toff[t] : 0;
+    const int nl = valid ? (int)(a.toff[t + 1] - l0) : 0;
+    if (nl == 0) {  // wave-uniform
+        if (lane == 0) a.planes[p] = P;
+        return;
+    }
+    const MatchTransform M{R.transform[0], R.transform[1], R.transform[2], R.transform[3], R.transform[4], R.transform[5]};
+    RotM Q{};
+    if (a.cs) Q = refine_rot(a, e, t);
+    ExLine* const L = a.lines + (size_t)p * (size_t)a.Lmax;
+    bool has_nan = false;
+    float mnx = f_inf(), mny = f_inf(), mxx = -f_inf(), mxy = -f_inf();
+    for (int i = lane; i < nl; i += 64) {
+        float4 q = a.tlines[l0 + i];
+        if (a.cs)  // Q_e(t): transform, math.h:341-344, as rotated_set
+            q = make_float4((Q.c * q.x + Q.ns * q.y) + Q.mx, (Q.s * q.x + Q.c * q.y) + Q.my, (Q.c * q.z + Q.ns * q.w) + Q.mx,
+                            (Q.s * q.z + Q.c * q.w) + Q.my);
+        const float4 v = match_pose_line(M, q);
+        int bin;
+        if (a.bins) {
+            bin = (int)a.bins[(size_t)p * (size_t)a.Lmax + i];
+        } else {
+            const float angle = atanf_glibc((v.w - v.y) / (v.z - v.x));  // getAngle, math.h:295-299
+            bin = closest_orientation(a.keys, a.m, angle);              // dt3cpu.cpp:144-148
+        }
+        L[i] = ExLine{v.x, v.y, v.z, v.w, a.buf32 ? (int)((unsigned)bin * (unsigned)a.SL) : bin, a.caps ? a.caps[l0 + i] : f_inf(), 0.f, 0};
+        has_nan = has_nan || f_isnan(v.x) || f_isnan(v.y) || f_isnan(v.z) || f_isnan(v.w);
+        mnx = std_min(mnx, std_min(v.x, v.z)); mxx = std_max(mxx, std_max(v.x, v.z));
+        mny = std_min(mny, std_min(v.y, v.w)); mxy = std_max(mxy, std_max(v.y, v.w));
+    }
+    const bool any_nan = __ballot(has_nan) != 0;
+    mnx = wave_min_f(mnx); mny = wave_min_f(mny); mxx = wave_max_f(mxx); mxy = wave_max_f(mxy);
+    // the admissible columns and rows: the seam's rule on the extremes, offset = T + tau summed first
+    int i0 = 0x7fffffff, i1 = -1, j0 = 0x7fffffff, j1 = -1;
+    if (!any_nan) {
+        for (int i = lane; i <= 2 * a.hx; i += 64) {
+            const float off = a.tx + (float)((i - a.hx) * a.sx);
+            if (mnx + off > -1.f && mxx + off < (float)a.W) { i0 = min(i0, i); i1 = max(i1, i); }
+        }
+        for (int j = lane; j <= 2 * a.hy; j += 64) {
+            const float off = a.ty + (float)((j - a.hy) * a.sy);
+            if (mny + off > -1.f && mxy + off < (float)a.H) { j0 = min(j0, j); j1 = max(j1, j); }
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        i0 = min(i0, __shfl_xor(i0, d)); i1 = max(i1, __shfl_xor(i1, d));
+        j0 = min(j0, __shfl_xor(j0, d)); j1 = max(j1, __shfl_xor(j1, d));
+    }
+    if (i0 <= i1 && j0 <= j1) P = RefinePlane{nl, i0, i1, j0, j1, {0, 0, 0}};
+    if (lane == 0) a.planes[p] = P;
+}
+
+template <bool BUF32, bool CAP>
+__global__ void __launch_bounds__(256) k_refine_score(const RefineArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long w = ((long long)blockIdx.x * 4 + (long long)(threadIdx.x >> 6));
+    const long long n_items = (long long)a.nr * a.na * a.ppp;
+    if (w >= n_items) return;  // wave-uniform
+    const int p = __builtin_amdgcn_readfirstlane((int)(w / a.ppp)), patch = __builtin_amdgcn_readfirstlane((int)(w % a.ppp));
+    const RefinePlane P = a.planes[p];
+    const int ib = (patch % a.ppx) * kPatchX, jb = (patch / a.ppx) * kPatchY;
+    unsigned long long key = kNoKey;
+    if (P.n > 0 && ib <= P.i1 && ib + kPatchX > P.i0 && jb <= P.j1 && jb + kPatchY > P.j0) {  // wave-uniform
+        const VolRef V = make_volref(a.vol, a.SL, a.m, BUF32);
+        const int i = ib + (lane & 3), j = jb + (lane >> 2);
+        // a lane outside the box reads at the box's corner, which is admissible: every read stays inside the volume
+        const bool act = i >= P.i0 && i <= P.i1 && j >= P.j0 && j <= P.j1;
+        const float offx = a.tx + (float)(((act ? i : P.i0) - a.hx) * a.sx);  // sceneTranslation + translation
+        const float offy[1] = {a.ty + (float)(((act ? j : P.j0) - a.hy) * a.sy)};
+        float res[1] = {0.f};
+        rows_score<BUF32, 1, CAP>(V, a.lines + (size_t)p * (size_t)a.Lmax, P.n, offx, offy, a.W, (unsigned)a.H, a.SL, res);
+        const int e = p % a.na, nxw = 2 * a.hx + 1;
+        const unsigned N = (unsigned)nxw * (unsigned)(2 * a.hy + 1);
+        const unsigned low = e == a.centre && i == a.hx && j == a.hy ? 0u : 1u + (unsigned)e * N + (unsigned)(j * nxw + i);
+        if (act && !(res[0] != res[0])) key = ((unsigned long long)__float_as_uint(res[0]) << 32) | low;  // a NaN score has no key
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) key = min(key, __shfl_xor(key, d));
+    }
+    if (lane == 0) a.ikeys[w] = key;
+}
+
+__global__ void __launch_bounds__(256) k_refine_write(const RefineArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int rl = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (rl >= a.nr) return;  // wave-uniform
+    const long long per = (long long)a.na * a.ppp;
+    const unsigned long long* const K = a.ikeys + (long long)rl * per;
+    unsigned long long key = kNoKey;
+    for (long long q = lane; q < per; q += 64) key = min(key, K[q]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) key = min(key, __shfl_xor(key, d));
+    if (lane != 0) return;
+    const int j = a.r0 + rl;
+    fdcm_match R = a.rec[j];
+    int e = -1, di = 0, dj = 0;
+    if (key == kNoKey) {
+        R.score = f_nan();
+    } else {
+        const unsigned low = (unsigned)key;
+        const int nxw = 2 * a.hx + 1;
+        const unsigned N = (unsigned)nxw * (unsigned)(2 * a.hy + 1);
+        if (low == 0) {
+            e = a.centre;
+        } else {
+            e = (int)((low - 1) / N);
+            const int g = (int)((low - 1) % N);
+            di = g % nxw - a.hx;
+            dj = g / nxw - a.hy;
+        }
+        R.score = __uint_as_float((unsigned)(key >> 32));
+        const float fx = (float)(di * a.sx), fy = (float)(dj * a.sy);
+        const float M0 = R.transform[0], M1 = R.transform[1], M2 = R.transform[2], M3 = R.transform[3], M4 = R.transform[4], M5 = R.transform[5];
+        if (a.cs) {
+            const RotM Q = refine_rot(a, e, (long long)R.tmpl_idx - (long long)a.base);
+            R.transform[0] = (M0 * Q.c + M1 * Q.s);
+            R.transform[1] = (M0 * Q.ns + M1 * Q.c);
+            R.transform[2] = ((M0 * Q.mx + M1 * Q.my) + M2) + fx;
+            R.transform[3] = (M3 * Q.c + M4 * Q.s);
+            R.transform[4] = (M3 * Q.ns + M4 * Q.c);
+            R.transform[5] = ((M3 * Q.mx + M4 * Q.my) + M5) + fy;
+        } else {
+            R.transform[2] = M2 + fx;
+            R.transform[5] = M5 + fy;
+        }
+    }
+    a.out[j] = R;
+    if (a.pose) { a.pose[3 * j] = e; a.pose[3 * j + 1] = di; a.pose[3 * j + 2] = dj; }
+}
+
+constexpr size_t kRefinePartBytes = (size_t)512 << 20;  // a part's lines, planes, keys and bins
+
+}  // namespace
+
+// fdcm_matches_refine: the arguments are checked (fdcm_capi.cpp).  One reserve_eval lays out the whole call: the upload (host
+// records, caps, the delta table, the pivots, a part's host bins), the output records and poses of a list that leaves for the
+// host, and a part's lines, planes and keys.  The list is walked in parts of at most kRefinePartBytes of those
+// (FDCM_REFINE_PART: of that many records); a record is never cut.
+void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
+                        const fdcm_rotations* rot, int32_t centre, int32_t hx, int32_t hy, int32_t sx, int32_t sy, fdcm_match* out,
+                        bool out_on_device, int32_t* pose_out) {
+    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    hipStream_t st = fm->stream;
+    const size_t N = (size_t)n, T = (size_t)t->T, Lmax = (size_t)std::max<int64_t>(1, t->max_lines), na = rot ? (size_t)rot->n : 1;
+    const size_t SL = ivol_slice_floats(fm->W, fm->H);
+    const bool buf32 = !test_switches().matched_flat && (size_t)fm->m * SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
+    const bool host_bins = orientation_bins_on_host();
+    if (host_bins && fm->m > 65535) throw std::string("host-side orientation bins need depth <= 65535");
+    const int ppx = (2 * hx + kPatchX) / kPatchX, ppp = ppx * ((2 * hy + kPatchY) / kPatchY);  // ceil((2 h + 1) / patch)
+    const size_t per = na * Lmax * sizeof(ExLine) + na * sizeof(RefinePlane) + na * (size_t)ppp * 8 + (host_bins ? na * Lmax * 2 : 0);
+    size_t pn = std::max<size_t>(1, std::min(N, kRefinePartBytes / per));
+    if (test_switches().refine_part > 0) pn = std::min(pn, (size_t)test_switches().refine_part);
+    const bool pivots = rot && rot->pivots;
+    const size_t o_caps = on_device ? 0 : al256(N * sizeof(fdcm_match)), o_cs = o_caps + (t->capped ? al256((size_t)t->n_lines * 4) : 0),
+                 o_piv = o_cs + (rot ? al256(na * 8) : 0), o_bins = o_piv + (pivots ? al256(T * 8) : 0),
+                 o_out = o_bins + (host_bins ? al256(pn * na * Lmax * 2) : 0), o_pose = o_out + (out_on_device ? 0 : al256(N * sizeof(fdcm_match))),
+                 o_lines = o_pose + (pose_out ? al256(N * 12) : 0), o_planes = o_lines + al256(pn * na * Lmax * sizeof(ExLine)),
+                 o_ikeys = o_planes + al256(pn * na * sizeof(RefinePlane)), total = o_ikeys + al256(pn * na * (size_t)ppp * 8);
+    reserve_eval(fm, total, std::max<size_t>(o_out, 256));
+    char* d = (char*)fm->search.eval.p;
+    char* h = (char*)fm->search.eval_stage.p;
+    if (!on_device) std::memcpy(h, matches, N * sizeof(fdcm_match));
+    if (t->capped) std::memcpy(h + o_caps, t->caps.data(), (size_t)t->n_lines * 4);
+    if (rot) std::memcpy(h + o_cs, rot->cs, na * 8);
+    if (pivots) std::memcpy(h + o_piv, rot->pivots, T * 8);
+    if (o_bins) FDCM_HIP(hipMemcpyAsync(d, h, o_bins, hipMemcpyHostToDevice, st));
+    RefineArgs a{};
+    a.vol = fm->vol.as<float>(); a.SL = SL; a.m = (int)fm->m; a.W = (int)fm->W; a.H = (int)fm->H; a.tx = fm->tx; a.ty = fm->ty;
+    a.keys = (const float*)((const char*)fm->build.plan.p + fm->off_keys);
+    a.tlines = t->d_lines.as<float4>(); a.toff = t->d_offsets.as<long long>();
+    a.caps = t->capped ? (const float*)(d + o_caps) : nullptr;
+    a.cs = rot ? (const float*)(d + o_cs) : nullptr;
+    a.pivots = pivots ? (const float*)(d + o_piv) : nullptr;
+    a.bins = host_bins ? (const unsigned short*)(d + o_bins) : nullptr;
+    a.rec = on_device ? matches : (const fdcm_match*)d;
+    a.base = base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax; a.na = (int)na; a.centre = centre;
+    a.hx = hx; a.hy = hy; a.sx = sx; a.sy = sy; a.ppx = ppx; a.ppp = ppp; a.buf32 = buf32;
+    a.lines = (ExLine*)(d + o_lines); a.planes = (RefinePlane*)(d + o_planes); a.ikeys = (unsigned long long*)(d + o_ikeys);
+    a.out = out_on_device ? out : (fdcm_match*)(d + o_out);
+    a.pose = pose_out ? (int*)(d + o_pose) : nullptr;
+    auto score = buf32 ? (t->capped ? k_refine_score<true, true> : k_refine_score<true, false>)
+                       : (t->capped ? k_refine_score<false, true> : k_refine_score<false, false>);
+    std::vector<fdcm_match> fetched;
+    std::vector<float> posed, turned;
+    for (size_t r0 = 0; r0 < N; r0 += pn) {
+        const size_t nr = std::min(pn, N - r0);
+        a.r0 = (int)r0; a.nr = (int)nr;
+        if (host_bins) {  // the bins of this part's planes from the host libm; device records cost one download per part
+            const fdcm_match* hr = matches + r0;
+            if (on_device) {
+                fetched.resize(nr);
+                FDCM_HIP(hipMemcpyAsync(fetched.data(), matches + r0, nr * sizeof(fdcm_match), hipMemcpyDeviceToHost, st));
+                hr = fetched.data();
+            }
+            FDCM_HIP(hipStreamSynchronize(st));  // (the records are here, and nothing queued still reads the staging)
+            unsigned short* hb = (unsigned short*)(h + o_bins);
+            std::fill_n(hb, nr * na * Lmax, (unsigned short)0);
+            for (size_t rl = 0; rl < nr; ++rl) {
+                const int64_t tm = (int64_t)hr[rl].tmpl_idx - base;
+                if (tm < 0 || tm >= t->T) continue;
+                const int64_t l0 = t->offsets[(size_t)tm], nl = t->offsets[(size_t)tm + 1] - l0;
+                for (size_t e = 0; e < na; ++e) {
+                    turned.assign(t->lines.begin() + l0 * 4, t->lines.begin() + (l0 + nl) * 4);
+                    if (rot) {
+                        const RotM Q = rot_matrix(rot->cs[2 * e], rot->cs[2 * e + 1], pivots ? rot->pivots[2 * tm] : 0.f, pivots ? rot->pivots[2 * tm + 1] : 0.f);
+                        for (int64_t i = 0; i < 2 * nl; ++i) {
+                            const float x = turned[2 * i], y = turned[2 * i + 1];
+                            turned[2 * i] = (Q.c * x + Q.ns * y) + Q.mx;
+                            turned[2 * i + 1] = (Q.s * x + Q.c * y) + Q.my;
+                        }
+                    }
+                    const float* M = hr[rl].transform;
+                    for (int64_t i = 0; i < nl; ++i) {
+                        float v[4];
+                        for (int c = 0; c < 2; ++c) {
+                            const float x = turned[4 * i + 2 * c], y = turned[4 * i + 2 * c + 1];
+                            v[2 * c] = (M[0] * x + M[1] * y) + M[2];
+                            v[2 * c + 1] = (M[3] * x + M[4] * y) + M[5];
+                        }
+                        const float angle = std::atan((v[3] - v[1]) / (v[2] - v[0]));  // getAngle, math.h:295-299
+                        hb[(rl * na + e) * Lmax + i] = (unsigned short)closest_orientation(fm->keys.data(), (int)fm->m, angle);
+                    }
+                }
+            }
+            FDCM_HIP(hipMemcpyAsync(d + o_bins, hb, nr * na * Lmax * 2, hipMemcpyHostToDevice, st));
+        }
+        const size_t planes = nr * na, items = planes * (size_t)ppp;
+        hipLaunchKernelGGL(k_refine_pose, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(score, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_refine_write, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, st, a);
+        FDCM_HIP(hipGetLastError());
+    }
+    if (!out_on_device) FDCM_HIP(hipMemcpyAsync(out, d + o_out, N * sizeof(fdcm_match), hipMemcpyDeviceToHost, st));
+    if (pose_out) FDCM_HIP(hipMemcpyAsync(pose_out, d + o_pose, N * 12, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));  // the call blocks (and the host arrays stay alive until here)
+}
+
 }  // namespace fdcm

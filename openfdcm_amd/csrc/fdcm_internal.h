@@ -46,6 +46,8 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              lists, which also take their bins from the host under FDCM_FORCE_HOST_BINS)
 //   FDCM_COVERAGE_PART=1..     records a part of the scene coverage of a match list holds at most, instead of what 768 MB of
 //                              table hold (run_matches_coverage)
+//   FDCM_REFINE_PART=1..       records a part of the refinement of a match list holds at most, instead of what 512 MB of lines,
+//                              planes and keys hold (run_matches_refine)
 //   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
 //                              takes that form for a volume of 4 GB or more alone (score maps, top-k, peaks, rotations, best
 //                              map, the detections, line costs); the pose windows and the calls by matched fraction keep
@@ -80,6 +82,7 @@ struct TestSwitches {
     int windows_batch;  // 0: not forced
     bool windows_flat, matched_flat, exhaustive_flat;
     int coverage_part;  // 0: not forced
+    int refine_part;    // 0: not forced
     bool poison;           // FDCM_POISON holds a valid word
     uint32_t poison_word;
 };
@@ -518,6 +521,11 @@ void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match*
                  const MatchesDetect* det, float* scores_out, float* fractions_out, float* costs_out, fdcm_match** out, int64_t* n_out,
                  int32_t* indices_out, int32_t* boxes_out, float* matched_out, const MatchesObjectsIn* objects_in = nullptr,
                  const MatchesShapesOut* shapes_out = nullptr);
+// "Match lists: refinement": every record's window of (delta rotation, dx, dy) searched on the device; out: n records on the host
+// or (out_on_device) on the handle's device, which may be `matches`; pose_out: n x 3 on the host, or null.
+void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
+                        const fdcm_rotations* rot, int32_t centre, int32_t hx, int32_t hy, int32_t sx, int32_t sy, fdcm_match* out,
+                        bool out_on_device, int32_t* pose_out);
 // the bins of every posed line from the host libm, [record][max_lines], where fdcm_orientation_bins_mode() is 1 (else empty); the
 // handle has its stream
 void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,

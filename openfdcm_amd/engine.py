@@ -735,6 +735,34 @@ class DeviceFeatureMap:
         res += (fr[:k.value].copy(),) if matched else ()
         return res if len(res) > 1 else res[0]
 
+    def refine_matches(self, templates, matches=None, cs=None, pivots=None, centre=None, hx=0, hy=0, sx=1, sy=1, tmpl_index_base=0,
+                       poses=False, device_ptr=None, n=0, out_device_ptr=None):
+        """fdcm_matches_refine (include/fdcm.h, "Match lists: refinement"): every record searched in its own window of the
+        delta rotations cs ((na, 2) float32 (c, s); None: nothing rotated), about pivots in template coordinates, and the
+        translations (i sx, j sy), |i| <= hx, |j| <= hy, and replaced by its best pose; a record without one keeps its
+        transform and scores NaN.  centre: the run position of the unrotated delta, -1 for none; None: the first (1, 0) of cs,
+        else -1 (0 with cs None).  Returns the raw records aligned with the input, with poses also the (n, 3) int32 rows
+        (e, i, j), (-1, 0, 0) without a winner.  The forms of matches are verify_matches'; out_device_ptr: the records go to
+        that device buffer (it may be device_ptr: in place) and the return value holds None in their place."""
+        ptr, n, on_device, keep = self._match_input(matches, device_ptr, n)
+        rot, keep_rot = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
+        if centre is None:
+            centre = 0
+            if cs is not None:
+                unit = np.flatnonzero(np.all(keep_rot[0] == np.float32([1, 0]), axis=1))
+                centre = int(unit[0]) if unit.size else -1
+        out = None
+        if not out_device_ptr:  # (an empty map or an empty set writes nothing: no record has a winner)
+            out = keep.copy() if keep is not None else np.zeros(n, dtype=capi.MATCH_DTYPE)
+            out["score"] = np.float32(np.nan)
+        pose = np.zeros((n, 3), dtype=np.int32)
+        pose[:, 0] = -1
+        capi.check(capi.lib().fdcm_matches_refine(
+            self._h, templates._h, ptr, n, on_device, int(tmpl_index_base), C.byref(rot) if rot is not None else None, int(centre), int(hx),
+            int(hy), int(sx), int(sy), C.c_void_p(int(out_device_ptr)) if out_device_ptr else (C.c_void_p(out.ctypes.data) if n else None),
+            1 if out_device_ptr else 0, pose.ctypes.data_as(C.POINTER(C.c_int32)) if poses and n else None))
+        return (out, pose) if poses else out
+
     def detect_matches_objects(self, templates, matches, objects, max_score, n_objects=None, overlap_permille=300, cross_permille=None,
                                max_detections=1024, penalty=None, tau=1.0, margin=0, min_matched=None, rescore=False, tmpl_index_base=0,
                                indices=False, boxes=False, matched=False, device_ptr=None, n=0):
