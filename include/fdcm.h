@@ -1339,6 +1339,74 @@ int fdcm_matches_refine(const fdcm_featuremap* fm, const fdcm_templates* templat
                         int32_t centre, int32_t hx, int32_t hy, int32_t sx, int32_t sy, fdcm_match* out /* n records */,
                         int out_on_device, int32_t* pose_out /* n x 3 host, or NULL */);
 
+/* ---- Match lists: pose fit.  A rigid least-squares fit of every record to the edge pixels it explains: the continuous last
+ *      stage after fdcm_search and fdcm_matches_refine, whose poses sit on the lattice they were searched on (README.md, "Match
+ *      lists: pose fit"; the referee is tests/fit_ref.py, plain Python integers and float64 scalars).  It is no descent on the
+ *      chamfer score: each step is a closed-form solve with an exact, order-free definition.
+ *      Everything not restated is fdcm_matches_coverage's: the frames rule (a map built from an image or from labels, whole
+ *      translation (bx, by)), valid record and admissibility, segment A_i B_i of line i (the truncated map pixels moved to the
+ *      label frame) and its bin, the window at margin, radius and bin_tolerance, the three input forms of matches and
+ *      tmpl_index_base.  A label pixel P stands for the point (P.x, P.y).
+ *      Fit pixels of a record at its current transform.  Candidates are the edge pixels P of its window.  With d = B_i - A_i,
+ *      w = P - A_i, dot = w.d, len2 = d.d, cross = w.x d.y - w.y d.x, line i qualifies for P when its bin is within
+ *      bin_tolerance of P's label, len2 > 0, 0 < dot < len2 (the coverage rule's interior branch; the end caps take no part)
+ *      and cross^2 <= radius^2 len2.  P is assigned to the qualifying line with the smallest cross^2 / len2, compared exactly in
+ *      int64 (cross_i^2 len2_j < cross_j^2 len2_i; cross^2 <= 2^10 2^25 and len2 <= 2^25, so the products stay below 2^60), ties
+ *      to the lowest i.  A pixel without a qualifying line is no fit pixel; the fit pixels are a subset of the pixels
+ *      fdcm_matches_coverage counts as explained.
+ *      Moments.  Per line, with o = A_i and u = P - o, six exact int64 sums over its pixels: S1, Sx, Sy, Sxx, Sxy, Syy.  Sums of
+ *      small integers: any order of accumulation gives the same value.
+ *      Normal equations, one sequential pass in line order, every operation an unfused IEEE float64 operation.  pa, pb: the
+ *      float32 sums whose truncation gives A_i, B_i, taken before the truncation, converted to float64, minus the integer
+ *      border.  t = pb - pa, L = sqrt(t.x t.x + t.y t.y), nu = (t.y / L, -t.x / L); lines with S1 = 0 or L = 0 are skipped.
+ *      Pivot c: the integer point ((min + max) >> 1) per axis over all end pixels A_i, B_i of the record.
+ *      e0 = nu.x (o.x - pa.x) + nu.y (o.y - pa.y); g0 = nu.y (o.x - c.x) - nu.x (o.y - c.y).  Four affine functions of u with
+ *      coefficients (f0, fx, fy): a = (nu.x, 0, 0), b = (nu.y, 0, 0), g = (g0, nu.y, -nu.x), e = (e0, nu.x, nu.y).
+ *      S(p, q) = p0 q0 S1 + (p0 qx + px q0) Sx + (p0 qy + py q0) Sy + px qx Sxx + (px qy + py qx) Sxy + py qy Syy, summed
+ *      left to right.  N[r][s] += S(f_r, f_s) and v[r] += S(f_r, e) over f = (a, b, g); See += S(e, e); n += S1.  e is the
+ *      signed distance of a pixel to the posed float line; the unknown x = (dx, dy, dtheta) minimises the sum of
+ *      (e - nu.dt - dtheta g)^2.
+ *      Step.  Damping: tr = N00 + N11; N00 += damping tr; N11 += damping tr; N22 += damping N22.  LDL^T without pivoting:
+ *      d0 = N00; l10 = N01 / d0; l20 = N02 / d0; d1 = N11 - l10 N01; m21 = N12 - l20 N01; l21 = m21 / d1;
+ *      d2 = N22 - l20 N02 - l21 m21; y0 = v0; y1 = v1 - l10 y0; y2 = v2 - l20 y0 - l21 y1; x2 = y2 / d2;
+ *      x1 = y1 / d1 - l21 x2; x0 = y0 / d0 - l10 x1 - l20 x2.  Rotation without libm: h = x2 / 2; q = h h;
+ *      cc = (1 - q) / (1 + q); ss = (h + h) / (1 + q).  Fold, in float64 from the record's float32 m0 .. m5, each result rounded
+ *      to float32: m0' = cc m0 - ss m3; m1' = cc m1 - ss m4; m3' = ss m0 + cc m3; m4' = ss m1 + cc m4;
+ *      m2' = ((cc (m2 - c.x) - ss (m5 - c.y)) + c.x) + x0; m5' = ((ss (m2 - c.x) + cc (m5 - c.y)) + c.y) + x1.  If
+ *      x0 = x1 = x2 = 0 exactly, the transform is kept byte for byte.
+ *      Iterations and status.  iterations is 1 .. 8.  A record stops early, keeping the transform it has, with status 1:
+ *      n < min_pixels at this pass; 2: not (d0 > 0, d1 > 0 and d2 > 0), or an x or a folded float32 that is not finite; 3:
+ *      |x0| or |x1| > max_shift, or |x2| > max_angle (tested in this order, after 2's pivots and x); 4: the stepped transform is
+ *      not admissible (its posed lines leave the map): the step is not taken and does not count.  Status 0: all steps taken.
+ *      Status -1: the input record is invalid or not admissible; it is untouched.  After the last step one more pass at the
+ *      final transform gives the final pixel count and rms; a record of status 4 keeps the figures of the transform it keeps.
+ *      Output.  n records aligned with the input: tmpl_idx and score unchanged, the transform fitted.  info_out, n x 4 int32:
+ *      status, steps taken, fit pixels at the first pass, fit pixels at the final pass.  rms_out, n x 2 float32:
+ *      float32(sqrt(max(See, 0) / n)) in float64 at the first and the final pass, NaN when that pass has n = 0 or the status
+ *      is -1.  out may be host or device memory, and may be the input's buffer.  Permuting the list permutes the rows; the
+ *      three forms of matches and host or device labels give the same bytes.
+ *      The device.  The records stay on the device.  Per pass: the table of the current transforms and the strip scan of
+ *      fdcm_matches_coverage (only the number of strips comes to the host); a moments pass on the coverage grid, a workgroup
+ *      per (record, strip), which adds each fit pixel's six integers to its line's int64 accumulators in LDS and flushes them
+ *      with 64-bit atomics; a step pass, a thread per record.  The list is walked in parts under the coverage call's 768 MB,
+ *      moments included.  Where fdcm_orientation_bins_mode() is 1 every pass downloads the records for the host's bins.
+ *      FDCM_EINVAL, before any GPU work: everything fdcm_matches_coverage rejects (its residual aside); fit NULL; iterations
+ *      outside 1 .. 8; min_pixels < 3; damping NaN or < 0; max_shift or max_angle NaN or < 0; out NULL with n > 0;
+ *      out_on_device not 0 or 1; n > 2^20.  n = 0, an empty feature map or an empty template set give FDCM_OK and write
+ *      nothing.  The call blocks; concurrent callers of one feature map take turns. ---- */
+typedef struct fdcm_fit_params {
+    int32_t iterations;  /* 1 .. 8 steps */
+    int32_t min_pixels;  /* >= 3: fewer fit pixels stop a record (status 1) */
+    double damping;      /* >= 0: the share of the diagonal added to it */
+    double max_shift;    /* >= 0 pixels: a longer step per axis stops a record (status 3) */
+    double max_angle;    /* >= 0 radians */
+} fdcm_fit_params;       /* 32 bytes */
+int fdcm_matches_fit(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int labels_on_device,
+                     const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int matches_on_device,
+                     int32_t tmpl_index_base, const fdcm_coverage_params* params, const fdcm_fit_params* fit,
+                     fdcm_match* out /* n records */, int out_on_device, int32_t* info_out /* n x 4 host, or NULL */,
+                     float* rms_out /* n x 2 host, or NULL */);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

@@ -1407,6 +1407,31 @@ def match_coverage(featuremap, labels, templates, matches, radius=2, bin_toleran
                              device_ptr=device_ptr, n=n)
 
 
+def fit_matches(featuremap, labels, templates, matches, radius=3, bin_tolerance=1, margin=None, iterations=2, min_pixels=8,
+                damping=1e-3, max_shift=None, max_angle=0.1, return_info=False, return_rms=False, device_ptr=None, n=0,
+                out_device_ptr=None):
+    """The continuous last stage of search -> refine_matches -> fit_matches -> detect_matches(rescore=True): every record's
+    transform fitted by rigid least squares to the edge pixels of labels it explains, on the device.  search() and
+    refine_matches return poses on the lattice they searched; a step here is closed form: every edge pixel of the record's
+    window that lies within `radius` of the inside of a posed line of its orientation (bin_tolerance) is assigned to its
+    nearest such line, and the rotation and translation that minimise the squared distances to those lines are solved for
+    and folded into the transform; `iterations` (1 .. 8) such steps.  A record stops early when it has fewer than min_pixels
+    fit pixels (status 1), when the system is singular (2: a single straight line does not fix a pose), when a step exceeds
+    max_shift pixels (None: the radius) or max_angle radians (3), or when the step would leave the map (4, not taken); status
+    0 took every step and -1 is a record that is invalid or outside the map, which is returned as it is.  damping is the share
+    of the diagonal added to it.  labels, matches, radius, bin_tolerance and margin are match_coverage's; out_device_ptr is
+    refine_matches'.  Returns a MatchList aligned with the input, scores unchanged (rescore with detect_matches or
+    verify_matches); with return_info also the (n, 4) int32 rows (status, steps, fit pixels before, after), with return_rms
+    the (n, 2) float32 rms distances of the fit pixels to their lines before and after."""
+    fm, tset = _device_map(featuremap), _template_cache.get(templates)
+    res = fm.fit_matches(labels, tset, matches, radius=radius, bin_tolerance=bin_tolerance, margin=margin, iterations=iterations,
+                         min_pixels=min_pixels, damping=damping, max_shift=max_shift, max_angle=max_angle, info=return_info, rms=return_rms,
+                         device_ptr=device_ptr, n=n, out_device_ptr=out_device_ptr)
+    res = res if isinstance(res, tuple) else (res,)
+    res = (None if res[0] is None else MatchList(res[0]),) + res[1:]
+    return res if len(res) > 1 else res[0]
+
+
 def select_matches(featuremap, labels, templates, matches, radius=2, bin_tolerance=1, margin=None, min_coverage=0.0, min_new=0.5,
                    min_pixels=1, max_selected=1024, return_residual=False, device_ptr=None, n=0):
     """scene_select for what search() returns: greedy explain-away over match records, on the device.  Records conflict when

@@ -96,6 +96,16 @@ class CoverageParams(C.Structure):
 assert C.sizeof(CoverageParams) == 12
 
 
+class FitParams(C.Structure):
+    """fdcm_fit_params: the steps, the fewest fit pixels a step needs, the damping's share of the diagonal, and the longest
+    step per axis (pixels) and in angle (radians)."""
+    _fields_ = [("iterations", C.c_int32), ("min_pixels", C.c_int32), ("damping", C.c_double), ("max_shift", C.c_double),
+                ("max_angle", C.c_double)]
+
+
+assert C.sizeof(FitParams) == 32
+
+
 class SelectParams(C.Structure):
     """fdcm_select_params: the static test's share (explained / edges), the share of a pose's explained pixels that must be
     unclaimed at its turn, both in permille, the least number of pixels for either, and the most poses to accept."""
@@ -271,6 +281,8 @@ SYMBOLS = [
                                       _vp]),
     ("fdcm_matches_refine", C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int, C.c_int32, C.POINTER(Rotations), C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, _vp, C.c_int, C.POINTER(C.c_int32)]),
+    ("fdcm_matches_fit", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int, _vp, _vp, C.c_int64, C.c_int, C.c_int32,
+                                   C.POINTER(CoverageParams), C.POINTER(FitParams), _vp, C.c_int, C.POINTER(C.c_int32), _fp]),
     ("fdcm_lines_read", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int64)]),
     ("fdcm_lines_write", C.c_int, [C.c_char_p, _fp, C.c_int64]),
     ("fdcm_lines_free", None, [C.POINTER(C.c_float)]),

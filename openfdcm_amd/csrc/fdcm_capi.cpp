@@ -1596,6 +1596,30 @@ int fdcm_matches_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_
     });
 }
 
+// Match lists, pose fit: include/fdcm.h, "Match lists: pose fit".  The coverage call's checks around the call's own.
+int fdcm_matches_fit(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int labels_on_device,
+                     const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int matches_on_device, int32_t tmpl_index_base,
+                     const fdcm_coverage_params* params, const fdcm_fit_params* fit, fdcm_match* out, int out_on_device, int32_t* info_out,
+                     float* rms_out) {
+    return guarded([&] {
+        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, false, params);
+        require(fit != nullptr, "fit is null");
+        require(fit->iterations >= 1 && fit->iterations <= 8, "iterations must be in [1, 8]");
+        require(fit->min_pixels >= 3, "min_pixels must be at least 3");
+        require(fit->damping >= 0.0, "damping must be a number >= 0");  // (false for a NaN)
+        require(fit->max_shift >= 0.0, "max_shift must be a number >= 0");
+        require(fit->max_angle >= 0.0, "max_angle must be a number >= 0");
+        require(n == 0 || out, "out is null");
+        require(out_on_device == 0 || out_on_device == 1, "out_on_device must be 0 or 1");
+        float bx, by;
+        check_coverage_back(fm, labels, width, height, templates, nullptr, nullptr, 0, params, nullptr, &bx, &by);
+        last_search_matches_bounded(fm, matches, n, matches_on_device, false);
+        require(n == 0 || out, "out is null");
+        run_matches_fit(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, labels_on_device != 0, (int)bx, (int)by, templates,
+                        matches, n, matches_on_device != 0, tmpl_index_base, *params, *fit, out, out_on_device != 0, info_out, rms_out);
+    });
+}
+
 int fdcm_score_map_rotations(const fdcm_featuremap* fm, const fdcm_templates* templates, const fdcm_rotations* rot,
                              const fdcm_grid* grid, float* out_host) {
     return guarded([&] {

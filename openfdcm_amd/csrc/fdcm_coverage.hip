@@ -39,6 +39,17 @@
 // Entries without strips stay in the table: pose_of_item returns the last entry whose first item is <= the item, and an entry
 // without strips that shares its offset with its successor is never the last such entry.
 //
+// The pose fit of match records (include/fdcm.h, "Match lists: pose fit") runs the body in a fourth mode and adds a kernel:
+//
+//   k_fit_moments       the grid of k_scene_coverage on the table of the records' current transforms; a workgroup leaves at once
+//                       when its record has stopped.  Every queued pixel walks all the segments for the nearest qualifying
+//                       one (exact in int64, carried across chunks) and adds its six moments to that line's int64 accumulators
+//                       in LDS (global atomics for the lines beyond the first chunk); the non-zero accumulators are flushed once
+//                       per workgroup with 64-bit atomics.  Integer sums: the result does not depend on the schedule.
+//   k_fit_step          a thread per record: the normal equations in line order, the damped LDL^T solve, the fold and the
+//                       status, all in unfused float64; the transform a step replaces is kept, and put back when the next
+//                       table pass finds the stepped one outside the map.
+//
 // All arithmetic of the decision is integer; the float adds of step 1 are the cost rule's own (-ffp-contract=off as everywhere).
 #include <algorithm>
 #include <cstring>
@@ -88,15 +99,50 @@ __device__ __forceinline__ bool near_segment(const CovSeg& s, int px, int py, lo
     return cross * cross <= r2 * s.len2;
 }
 
-enum { kCovCount = 0, kCovClaim = 1, kCovRecount = 2 };
+enum { kCovCount = 0, kCovClaim = 1, kCovRecount = 2, kCovFit = 3 };
+
+// The pose fit's choice of a line for P (include/fdcm.h, "Match lists: pose fit"): segment i qualifies when P projects
+// strictly inside it and lies within the radius of its line; the nearest by cross^2 / len2 wins, compared exactly
+// (cross^2 <= 2^10 len2 and len2 <= 2^25, so the products stay below 2^60), ties to the segment seen first.  (wx, wy) = P - A.
+struct FitBest {
+    int i, wx, wy;
+    long long c2, l2;
+};
+__device__ __forceinline__ void fit_nearest(const CovSeg& s, int i, int px, int py, long long r2, FitBest& b) {
+    const long long dx = (long long)s.bx - s.ax, dy = (long long)s.by - s.ay;
+    const long long wx = (long long)px - s.ax, wy = (long long)py - s.ay;
+    const long long dot = wx * dx + wy * dy;
+    if (dot <= 0 || dot >= s.len2) return;  // (also A = B)
+    const long long cross = wx * dy - wy * dx;
+    if (cross >= (1ll << 31) || cross <= -(1ll << 31)) return;
+    const long long c2 = cross * cross;
+    if (c2 > r2 * s.len2) return;
+    if (b.i < 0 || c2 * b.l2 < b.c2 * s.len2) b = FitBest{i, (int)wx, (int)wy, c2, s.len2};
+}
+// S1, Sx, Sy, Sxx, Sxy, Syy of the line += the pixel's: LDS for a line of the first chunk, else global
+__device__ __forceinline__ void fit_add(const FitBest& b, long long* __restrict__ lds, unsigned long long* __restrict__ out) {
+    const long long wx = b.wx, wy = b.wy;
+    const long long v[6] = {1, wx, wy, wx * wx, wx * wy, wy * wy};
+    if (b.i < kCovLines) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            if (v[k]) atomicAdd(reinterpret_cast<unsigned long long*>(lds + 6 * b.i + k), (unsigned long long)v[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            if (v[k]) atomicAdd(out + 6 * (size_t)b.i + k, (unsigned long long)v[k]);
+    }
+}
 
 // Strip `strip` of the pose P: steps 1 to 3 above.  kCovCount: edges and explained, of this wave (wave-uniform), and 255 into
 // the residual, if there is one.  kCovClaim: the stores alone.  kCovRecount: explained counts the pixels the pose explains
-// whose residual byte is not 255, and nothing is stored.  The decision reads the labels alone in every mode.
+// whose residual byte is not 255, and nothing is stored.  The decision reads the labels alone in every mode.  kCovFit: nothing
+// is counted or stored but the moments of the pixels, at fit_lds (zeroed by the caller, 6 per line of the first chunk) and fit_out.
 template <int kMode>
 __device__ __forceinline__ void coverage_item(const uint8_t* __restrict__ labels, int width, int height, int m, float tx, float ty, int bx,
                                               int by, int radius, int tol, const CoverageLine* __restrict__ lines, const CovPose& P,
-                                              int strip, uint8_t* __restrict__ residual, int& edges, int& explained) {
+                                              int strip, uint8_t* __restrict__ residual, int& edges, int& explained,
+                                              long long* __restrict__ fit_lds = nullptr, unsigned long long* __restrict__ fit_out = nullptr) {
     __shared__ CovSeg seg[kCovLines];
     __shared__ unsigned queue[kCovQueue];
     __shared__ int q_count;
@@ -183,6 +229,7 @@ __device__ __forceinline__ void coverage_item(const uint8_t* __restrict__ labels
             const unsigned q = have ? queue[e] : 0u;
             const int px = (int)(q & 4095u), py = (int)((q >> 12) & 4095u), lab = (int)(q >> 24);
             bool hit = false;
+            FitBest best{-1, 0, 0, 0, 1};
             for (int c0 = 0; c0 < P.n; c0 += kCovLines) {
                 if (c0 != resident) {  // (templates of more than one chunk only)
                     __syncthreads();
@@ -196,8 +243,14 @@ __device__ __forceinline__ void coverage_item(const uint8_t* __restrict__ labels
                     int d = lab - sg.bin;
                     d = d < 0 ? -d : d;
                     d = min(d, m - d);
-                    if (have && !hit && d <= tol && px >= sg.x0 && px <= sg.x1 && py >= sg.y0 && py <= sg.y1) hit = near_segment(sg, px, py, r2);
+                    if (kMode == kCovFit) {
+                        if (have && d <= tol && px >= sg.x0 && px <= sg.x1 && py >= sg.y0 && py <= sg.y1) fit_nearest(sg, c0 + i, px, py, r2, best);
+                    } else if (have && !hit && d <= tol && px >= sg.x0 && px <= sg.x1 && py >= sg.y0 && py <= sg.y1) hit = near_segment(sg, px, py, r2);
                 }
+            }
+            if (kMode == kCovFit) {
+                if (best.i >= 0) fit_add(best, fit_lds, fit_out);
+                continue;
             }
             if (kMode == kCovRecount) hit = hit && residual[py * width + px] != 255;
             if (kMode != kCovClaim) explained += __popcll(__ballot(hit));
@@ -428,6 +481,146 @@ __global__ void __launch_bounds__(1024) k_strip_scan(const int* __restrict__ str
         out[0] = carry;
         out[1] = mx;
     }
+}
+
+// ---------------------------------------------------------------------------------------------- the pose fit of a match list
+// include/fdcm.h, "Match lists: pose fit".  info[record] = (status, steps, fit pixels at the first pass, at the last pass); a
+// record still stepping holds kFitActive as its status (what hipMemsetAsync writes with 0x7f).
+constexpr int kFitActive = 0x7f7f7f7f;
+
+// Grid: k_scene_coverage's, on the table of the current transforms.  mom: [record][Lmax][6], zero before the launch.
+__global__ void __launch_bounds__(kCovThreads) k_fit_moments(const uint8_t* __restrict__ labels, int width, int height, int m, float tx,
+                                                             float ty, int bx, int by, int radius, int tol,
+                                                             const CoverageLine* __restrict__ lines, const CovPose* __restrict__ poses,
+                                                             const long long* __restrict__ item0, int n_poses, long long item_base,
+                                                             const int* __restrict__ info, unsigned long long* __restrict__ mom, int Lmax) {
+    __shared__ long long acc[kCovLines * 6];
+    const long long item = item_base + (long long)blockIdx.x;
+    const int lo = pose_of_item(item0, n_poses, item);
+    if (info[4 * lo] != kFitActive) return;  // (uniform: the record has stopped)
+    const CovPose P = poses[lo];
+    const int na = min(P.n, kCovLines) * 6;
+    for (int e = (int)threadIdx.x; e < na; e += kCovThreads) acc[e] = 0;  // (coverage_item's first barrier is before its first pixel)
+    unsigned long long* out = mom + (size_t)lo * (size_t)Lmax * 6;
+    int edges, explained;
+    coverage_item<kCovFit>(labels, width, height, m, tx, ty, bx, by, radius, tol, lines, P, (int)(item - item0[lo]), nullptr, edges, explained,
+                           acc, out);
+    __syncthreads();
+    for (int e = (int)threadIdx.x; e < na; e += kCovThreads)
+        if (acc[e]) atomicAdd(out + e, (unsigned long long)acc[e]);
+}
+
+struct FitArgs {
+    const CoverageLine* lines;  // the part's table, at the current transforms
+    const CovPose* poses;
+    const int* counts;          // [record][2]: -1 where the current transform is not admissible
+    const long long* mom;       // [record][Lmax][6]
+    fdcm_match* cur;            // the part's records
+    float* prev;                // [record][6]: the transform the last step replaced
+    int* info;                  // [record][4]
+    float* rms;                 // [record][2]
+    int n, Lmax, pass;
+    fdcm_fit_params par;
+    float tx, ty;
+    int bx, by;
+};
+
+// S(p, q) of the section: the sum over a line's pixels of p(u) q(u) for affine p, q with coefficients (f0, fx, fy), from the
+// line's moments, left to right.
+__device__ __forceinline__ double fit_S(const double* p, const double* q, const double* S) {
+    return p[0] * q[0] * S[0] + (p[0] * q[1] + p[1] * q[0]) * S[1] + (p[0] * q[2] + p[2] * q[0]) * S[2] + p[1] * q[1] * S[3] +
+           (p[1] * q[2] + p[2] * q[1]) * S[4] + p[2] * q[2] * S[5];
+}
+__device__ __forceinline__ bool fit_finite(double v) { return fabs(v) < __builtin_inf(); }  // false for a NaN
+
+// Grid: a thread per record of the part.  Pass `pass` of 0 .. iterations: the last one only measures.
+__global__ void __launch_bounds__(256) k_fit_step(const FitArgs a) {
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (j >= a.n) return;
+    int* info = a.info + 4 * (size_t)j;
+    if (a.pass == 0) info[1] = info[2] = info[3] = 0;
+    else if (info[0] != kFitActive) return;
+    float* M = a.cur[j].transform;
+    if (a.counts[2 * j] < 0) {
+        if (a.pass == 0) {  // not valid or not admissible: untouched
+            info[0] = -1;
+            a.rms[2 * j] = a.rms[2 * j + 1] = __int_as_float(0x7fc00000);
+        } else {  // the step left the map: it is not taken, and the last pass's figures stand
+            for (int k = 0; k < 6; ++k) M[k] = a.prev[6 * (size_t)j + k];
+            info[0] = 4;
+            info[1] -= 1;
+        }
+        return;
+    }
+    const CovPose P = a.poses[j];
+    const CoverageLine* lines = a.lines + P.line0;
+    const long long* mom = a.mom + (size_t)j * (size_t)a.Lmax * 6;
+    const float offx = a.tx + 0.f, offy = a.ty + 0.f;  // k_matches_table's, coverage_item's
+    int mnx = 0x7fffffff, mny = 0x7fffffff, mxx = -0x7fffffff, mxy = -0x7fffffff;
+    for (int i = 0; i < P.n; ++i) {
+        const CoverageLine ln = lines[i];
+        const int ax = (int)(ln.x1 + offx) - a.bx, ay = (int)(ln.y1 + offy) - a.by;
+        const int ex = (int)(ln.x2 + offx) - a.bx, ey = (int)(ln.y2 + offy) - a.by;
+        mnx = min(mnx, min(ax, ex)); mxx = max(mxx, max(ax, ex));
+        mny = min(mny, min(ay, ey)); mxy = max(mxy, max(ay, ey));
+    }
+    const double cx = (double)((mnx + mxx) >> 1), cy = (double)((mny + mxy) >> 1);  // the pivot (unused without lines)
+    double N00 = 0, N01 = 0, N02 = 0, N11 = 0, N12 = 0, N22 = 0, v0 = 0, v1 = 0, v2 = 0, See = 0;
+    long long n = 0;
+    for (int i = 0; i < P.n; ++i) {
+        const long long* Si = mom + 6 * (size_t)i;
+        if (Si[0] == 0) continue;
+        const CoverageLine ln = lines[i];
+        const float fax = ln.x1 + offx, fay = ln.y1 + offy, fbx = ln.x2 + offx, fby = ln.y2 + offy;
+        const double pax = (double)fax - (double)a.bx, pay = (double)fay - (double)a.by;
+        const double pbx = (double)fbx - (double)a.bx, pby = (double)fby - (double)a.by;
+        const double tx = pbx - pax, ty = pby - pay;
+        const double L = sqrt(tx * tx + ty * ty);
+        if (L == 0.0) continue;
+        const double nx = ty / L, ny = -tx / L;
+        const double ox = (double)((int)fax - a.bx), oy = (double)((int)fay - a.by);
+        const double e0 = nx * (ox - pax) + ny * (oy - pay);
+        const double g0 = ny * (ox - cx) - nx * (oy - cy);
+        const double fa[3] = {nx, 0.0, 0.0}, fb[3] = {ny, 0.0, 0.0}, fg[3] = {g0, ny, -nx}, fe[3] = {e0, nx, ny};
+        const double S[6] = {(double)Si[0], (double)Si[1], (double)Si[2], (double)Si[3], (double)Si[4], (double)Si[5]};
+        N00 += fit_S(fa, fa, S); N01 += fit_S(fa, fb, S); N02 += fit_S(fa, fg, S);
+        N11 += fit_S(fb, fb, S); N12 += fit_S(fb, fg, S); N22 += fit_S(fg, fg, S);
+        v0 += fit_S(fa, fe, S); v1 += fit_S(fb, fe, S); v2 += fit_S(fg, fe, S);
+        See += fit_S(fe, fe, S);
+        n += Si[0];
+    }
+    const float rms = n > 0 ? (float)sqrt(fmax(See, 0.0) / (double)n) : __int_as_float(0x7fc00000);
+    if (a.pass == 0) {
+        info[2] = (int)n;
+        a.rms[2 * j] = rms;
+    }
+    info[3] = (int)n;
+    a.rms[2 * j + 1] = rms;
+    if (a.pass == a.par.iterations) { info[0] = 0; return; }
+    if (n < a.par.min_pixels) { info[0] = 1; return; }
+    const double tr = N00 + N11;
+    N00 += a.par.damping * tr; N11 += a.par.damping * tr; N22 += a.par.damping * N22;
+    const double d0 = N00, l10 = N01 / d0, l20 = N02 / d0;
+    const double d1 = N11 - l10 * N01, m21 = N12 - l20 * N01, l21 = m21 / d1;
+    const double d2 = N22 - l20 * N02 - l21 * m21;
+    if (!(d0 > 0.0 && d1 > 0.0 && d2 > 0.0)) { info[0] = 2; return; }
+    const double y0 = v0, y1 = v1 - l10 * y0, y2 = v2 - l20 * y0 - l21 * y1;
+    const double x2 = y2 / d2, x1 = y1 / d1 - l21 * x2, x0 = y0 / d0 - l10 * x1 - l20 * x2;
+    if (!(fit_finite(x0) && fit_finite(x1) && fit_finite(x2))) { info[0] = 2; return; }
+    if (fabs(x0) > a.par.max_shift || fabs(x1) > a.par.max_shift || fabs(x2) > a.par.max_angle) { info[0] = 3; return; }
+    const double h = x2 / 2.0, q = h * h, cc = (1.0 - q) / (1.0 + q), ss = (h + h) / (1.0 + q);
+    const double m0 = M[0], m1 = M[1], m2 = M[2], m3 = M[3], m4 = M[4], m5 = M[5];
+    const float r[6] = {(float)(cc * m0 - ss * m3), (float)(cc * m1 - ss * m4), (float)(((cc * (m2 - cx) - ss * (m5 - cy)) + cx) + x0),
+                        (float)(ss * m0 + cc * m3), (float)(ss * m1 + cc * m4), (float)(((ss * (m2 - cx) + cc * (m5 - cy)) + cy) + x1)};
+    bool fin = true;
+    for (int k = 0; k < 6; ++k) fin = fin && fabsf(r[k]) < __builtin_inff();
+    if (!fin) { info[0] = 2; return; }
+    const bool still = x0 == 0.0 && x1 == 0.0 && x2 == 0.0;  // the transform stays byte for byte
+    for (int k = 0; k < 6; ++k) {
+        a.prev[6 * (size_t)j + k] = M[k];
+        if (!still) M[k] = r[k];
+    }
+    info[1] += 1;
 }
 
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -855,6 +1048,91 @@ void run_matches_select(fdcm_featuremap* fm, const uint8_t* labels, int width, i
         counts[3 * k + 2] = h_new[k];
     }
     *n_out = (int64_t)k;
+}
+
+// The pose fit of match records (include/fdcm.h, "Match lists: pose fit"): the arguments are checked (fdcm_capi.cpp).  The
+// records are copied into the handle's buffer once and stay there; the list is walked in parts of at most kCovPartBytes of
+// table and moments (FDCM_COVERAGE_PART: of that many records), and per part iterations + 1 passes are queued: the table of the
+// current transforms and its scan (one download of the number of items, as in run_matches_coverage), the moments zeroed,
+// k_fit_moments, k_fit_step.  Where the host's libm makes the bins, every pass downloads the part's records for them
+// (matches_host_bins).  Records, info and rms come down once, at the end.
+void run_matches_fit(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                     const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
+                     const fdcm_coverage_params& params, const fdcm_fit_params& fit, fdcm_match* out, bool out_on_device, int32_t* info_out,
+                     float* rms_out) {
+    const size_t npix = (size_t)width * (size_t)height;
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    FDCM_HIP(hipSetDevice(fm->device));
+    ensure_stream(fm);
+    hipStream_t st = fm->stream;
+    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;  // nothing is written, as the coverage call's counts
+    const size_t N = (size_t)n, Lmax = (size_t)t->max_lines;
+    const bool host_bins = orientation_bins_on_host();
+    const size_t per_record = table_record_bytes(t, host_bins) + Lmax * 6 * sizeof(long long) + 2 * sizeof(int32_t);
+    size_t pn = std::max<size_t>(1, std::min(N, kCovPartBytes / per_record));
+    if (test_switches().coverage_part > 0) pn = std::min(pn, (size_t)test_switches().coverage_part);
+    // device: records | replaced transforms | info | rms (what comes down) | the part's table | its counters | its moments |
+    // labels (host callers)
+    const size_t o_prev = al256(N * sizeof(fdcm_match)), o_info = o_prev + al256(N * 6 * sizeof(float)),
+                 o_rms = o_info + al256(N * 4 * sizeof(int32_t));
+    const TableLayout L(o_rms + al256(N * 2 * sizeof(float)), pn, Lmax, host_bins);
+    const size_t o_cnt = L.end, o_mom = o_cnt + al256(pn * 2 * sizeof(int32_t)), o_lab = o_mom + al256(pn * Lmax * 6 * sizeof(long long)),
+                 total = o_lab + (on_device ? 0 : al256(npix));
+    // staging: host records up, then the results down; behind them the part's bins
+    const size_t s_bins = L.o_bins;  // (the results' extent)
+    fm->coverage.reserve(total);
+    fm->coverage_stage.reserve(s_bins + al256(host_bins ? pn * Lmax * 2 : 0));
+    poison_coverage(fm);
+    char* d = (char*)fm->coverage.p;
+    char* h = (char*)fm->coverage_stage.p;
+    const uint8_t* d_labels = labels;
+    if (!on_device) {
+        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
+        d_labels = (const uint8_t*)(d + o_lab);
+    }
+    fdcm_match* d_cur = (fdcm_match*)d;
+    if (matches_on_device) {
+        FDCM_HIP(hipMemcpyAsync(d_cur, matches, N * sizeof(fdcm_match), hipMemcpyDeviceToDevice, st));
+    } else {
+        std::memcpy(h, matches, N * sizeof(fdcm_match));
+        FDCM_HIP(hipMemcpyAsync(d_cur, h, N * sizeof(fdcm_match), hipMemcpyHostToDevice, st));
+    }
+    FDCM_HIP(hipMemsetAsync(d + o_info, 0x7f, N * 4 * sizeof(int32_t), st));  // kFitActive
+    std::vector<unsigned short> bins;
+    for (size_t q0 = 0; q0 < N; q0 += pn) {
+        const size_t cnt = std::min(pn, N - q0);
+        FitArgs a{};
+        a.lines = (const CoverageLine*)(d + L.o_lines); a.poses = (const CovPose*)(d + L.o_tab); a.counts = (const int*)(d + o_cnt);
+        a.mom = (const long long*)(d + o_mom);
+        a.cur = d_cur + q0; a.prev = (float*)(d + o_prev) + 6 * q0; a.info = (int*)(d + o_info) + 4 * q0; a.rms = (float*)(d + o_rms) + 2 * q0;
+        a.n = (int)cnt; a.Lmax = (int)Lmax; a.par = fit; a.tx = fm->tx; a.ty = fm->ty; a.bx = bx; a.by = by;
+        for (int pass = 0; pass <= fit.iterations; ++pass) {
+            long long items = 0, most = 0;
+            matches_host_bins(fm, t, d_cur + q0, (int64_t)cnt, true, base, bins);  // (empty unless the host's libm makes them)
+            make_table(fm, t, d_cur + q0, 0, cnt, base, (int)params.margin, width, height, bins, d, h + s_bins, L, (int*)(d + o_cnt), &items,
+                       &most);
+            if (Lmax) FDCM_HIP(hipMemsetAsync(d + o_mom, 0, cnt * Lmax * 6 * sizeof(long long), st));
+            for (long long ib = 0; ib < items; ib += kCovMaxGrid) {
+                const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - ib);
+                hipLaunchKernelGGL(k_fit_moments, dim3(grid), dim3(kCovThreads), 0, st, d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by,
+                                   (int)params.radius, (int)params.bin_tolerance, a.lines, a.poses, (const long long*)(d + L.o_item), (int)cnt, ib,
+                                   (const int*)a.info, (unsigned long long*)(d + o_mom), (int)Lmax);
+                FDCM_HIP(hipGetLastError());
+            }
+            a.pass = pass;
+            hipLaunchKernelGGL(k_fit_step, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, a);
+            FDCM_HIP(hipGetLastError());
+        }
+    }
+    // down: info and rms through the staging (free: every part has waited behind the upload), the records to where they go
+    FDCM_HIP(hipMemcpyAsync(h + o_info, d + o_info, N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipMemcpyAsync(h + o_rms, d + o_rms, N * 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (out_on_device) FDCM_HIP(hipMemcpyAsync(out, d_cur, N * sizeof(fdcm_match), hipMemcpyDeviceToDevice, st));
+    else FDCM_HIP(hipMemcpyAsync(h, d_cur, N * sizeof(fdcm_match), hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    if (!out_on_device) std::memcpy(out, h, N * sizeof(fdcm_match));
+    if (info_out) std::memcpy(info_out, h + o_info, N * 4 * sizeof(int32_t));
+    if (rms_out) std::memcpy(rms_out, h + o_rms, N * 2 * sizeof(float));
 }
 
 }  // namespace fdcm

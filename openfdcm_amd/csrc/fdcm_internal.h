@@ -45,7 +45,7 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              its winners' pass and its fractions; run_matches: the verify pass of the calls on match
 //                              lists, which also take their bins from the host under FDCM_FORCE_HOST_BINS)
 //   FDCM_COVERAGE_PART=1..     records a part of the scene coverage of a match list holds at most, instead of what 768 MB of
-//                              table hold (run_matches_coverage)
+//                              table hold (run_matches_coverage; run_matches_fit: of table and moments)
 //   FDCM_REFINE_PART=1..       records a part of the refinement of a match list holds at most, instead of what 512 MB of lines,
 //                              planes and keys hold (run_matches_refine)
 //   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
@@ -567,6 +567,13 @@ void run_matches_select(fdcm_featuremap* fm, const uint8_t* labels, int width, i
                         const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
                         const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
                         int64_t* n_out, uint8_t* residual);
+// "Match lists: pose fit": every record fitted to the edge pixels it explains, the records staying on the device between the
+// passes; out: n records on the host or (out_on_device) on the handle's device, which may be `matches`; info_out: 4 n int32,
+// rms_out: 2 n floats, on the host, or null.
+void run_matches_fit(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                     const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
+                     const fdcm_coverage_params& params, const fdcm_fit_params& fit, fdcm_match* out, bool out_on_device, int32_t* info_out,
+                     float* rms_out);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

@@ -921,6 +921,34 @@ class DeviceFeatureMap:
         selected, counts = selected[:k.value].copy(), counts[:k.value].copy()
         return (selected, counts, res) if residual else (selected, counts)
 
+    def fit_matches(self, labels, templates, matches=None, radius=3, bin_tolerance=1, margin=None, iterations=2, min_pixels=8,
+                    damping=1e-3, max_shift=None, max_angle=0.1, tmpl_index_base=0, info=False, rms=False, device_ptr=None, n=0,
+                    out_device_ptr=None):
+        """fdcm_matches_fit (include/fdcm.h, "Match lists: pose fit"): every record's transform fitted by least squares to the
+        edge pixels of labels its posed lines explain, in `iterations` closed-form steps on the device.  Returns the raw
+        records aligned with the input (tmpl_idx and score unchanged), with info also the (n, 4) int32 rows (status, steps, fit
+        pixels at the first pass, at the last) and with rms the (n, 2) float32 rms distances at the first and the last pass.
+        max_shift None: the radius.  labels, radius, bin_tolerance, margin and the forms of matches are match_coverage's;
+        out_device_ptr: the records go to that device buffer (it may be device_ptr: in place) and the return value holds None
+        in their place."""
+        p, w, h, dev, keep, _, _ = self._labels_input(labels, False)
+        ptr, n, on_device, keep_rec = self._match_input(matches, device_ptr, n)
+        par = capi.CoverageParams(int(radius), int(bin_tolerance), int(radius if margin is None else margin))
+        fit = capi.FitParams(int(iterations), int(min_pixels), float(damping), float(radius if max_shift is None else max_shift),
+                             float(max_angle))
+        out = None
+        if not out_device_ptr:  # (an empty map or an empty set writes nothing: every record stays as it is, status -1)
+            out = keep_rec.copy() if keep_rec is not None else np.zeros(n, dtype=capi.MATCH_DTYPE)
+        inf = np.zeros((n, 4), dtype=np.int32)
+        inf[:, 0] = -1
+        dist = np.full((n, 2), np.nan, dtype=np.float32)
+        capi.check(capi.lib().fdcm_matches_fit(
+            self._h, p, w, h, dev, templates._h, ptr, n, on_device, int(tmpl_index_base), C.byref(par), C.byref(fit),
+            C.c_void_p(int(out_device_ptr)) if out_device_ptr else (C.c_void_p(out.ctypes.data) if n else None), 1 if out_device_ptr else 0,
+            inf.ctypes.data_as(C.POINTER(C.c_int32)) if n else None, capi.fptr(dist) if n else None))
+        res = (out,) + ((inf,) if info else ()) + ((dist,) if rms else ())
+        return res if len(res) > 1 else res[0]
+
     def rotation_score_map(self, templates, grid, cs, pivots=None):
         """(T, n, ny, nx) float32: the score of every rotated template at every grid point, NaN where not admissible."""
         rot, keep = _rotations(cs, pivots, templates.count)
