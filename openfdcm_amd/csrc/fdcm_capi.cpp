@@ -49,6 +49,10 @@ static int guarded(F&& f) {
 static void require(bool ok, const char* msg) {
     if (!ok) throw std::string(msg);
 }
+static void check_handles(const fdcm_featuremap* fm, const fdcm_templates* t) {  // the two handles of a call, on one device
+    require(fm && t, "null featuremap/templates");
+    require(fm->device == t->device, "featuremap and templates live on different devices");
+}
 
 // A call that returns records in *out (checked non-null): what it had acquired is released when it throws, and a call
 // without records leaves an empty (non-null) array.
@@ -750,8 +754,7 @@ static void check_exhaustive_args(const fdcm_featuremap* fm, const fdcm_template
     require(grid->nx >= 1 && grid->ny >= 1, "grid: nx and ny must be >= 1");
     require(grid->sx >= 1 && grid->sy >= 1, "grid: strides sx and sy must be >= 1");
     require((int64_t)grid->nx * grid->ny < ((int64_t)1 << 31), "grid: nx * ny must be below 2^31");
-    require(fm && t, "null featuremap/templates");
-    require(fm->device == t->device, "featuremap and templates live on different devices");
+    check_handles(fm, t);
 }
 
 int fdcm_exhaustive_window(const fdcm_featuremap* fm, const fdcm_templates* templates, int32_t sx, int32_t sy, fdcm_grid* grid) {
@@ -861,8 +864,7 @@ int fdcm_search_exhaustive_windows(const fdcm_featuremap* fm, const fdcm_templat
         require(n_jobs >= 0 && (n_jobs == 0 || jobs), "jobs is null or n_jobs is negative");
         if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
         check_pose_windows(jobs, n_jobs, rot ? rot->n : 1, sx, sy, wrap);
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_handles(fm, templates);
         require(out && n_out, "null output");
         if (rot) check_pivots(templates, rot);
         for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
@@ -896,8 +898,7 @@ static void check_detect_windows_args(const fdcm_featuremap* fm, const fdcm_temp
     require(n_jobs <= ((int64_t)1 << 22), "n_jobs must be at most 2^22");
     if (rot) check_rotations(rot);  // null: the translations, a table of one rotation
     check_pose_windows(jobs, n_jobs, rot ? rot->n : 1, sx, sy, wrap);
-    require(fm && templates, "null featuremap/templates");
-    require(fm->device == templates->device, "featuremap and templates live on different devices");
+    check_handles(fm, templates);
     if (rot) check_pivots(templates, rot);
     for (int64_t j = 0; j < n_jobs && templates->T > 0; ++j)
         require(jobs[j].tmpl < templates->T, "jobs: tmpl is outside the template set");
@@ -1168,8 +1169,7 @@ int fdcm_matched_fractions(const fdcm_featuremap* fm, const fdcm_templates* temp
             require(p[1] >= 0 && p[1] < n_rot, rot ? "poses: a must be in [0, n - 1]" : "poses: a must be 0 without rotations");
             require(p[2] > -lim && p[2] < lim && p[3] > -lim && p[3] < lim, "poses: every translation must satisfy |t| < 2^24");
         }
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_handles(fm, templates);
         if (rot) check_pivots(templates, rot);
         for (int64_t q = 0; q < n && templates->T > 0; ++q)
             require(poses[4 * q] < templates->T, "poses: tmpl is outside the template set");
@@ -1283,8 +1283,7 @@ int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, 
             require(p[1] >= 0 && p[1] < n_rot, rot ? "poses: a must be in [0, n - 1]" : "poses: a must be 0 without rotations");
             require(p[2] > -lim && p[2] < lim && p[3] > -lim && p[3] < lim, "poses: every translation must satisfy |t| < 2^24");
         }
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_handles(fm, templates);
         require(costs && offsets, "null output");
         if (rot) check_pivots(templates, rot);
         for (int64_t q = 0; q < n && templates->T > 0; ++q)
@@ -1301,29 +1300,50 @@ int fdcm_line_costs(const fdcm_featuremap* fm, const fdcm_templates* templates, 
 
 // Match lists: include/fdcm.h, "Match lists".  Everything that needs no handle is checked first, in the section's order; nothing
 // here touches the device.
-static void check_match_list(const fdcm_match* matches, int64_t n, int on_device) {
+// the bound a call sets on its list: n <= 2^bits, 22 for the match calls, 20 for coverage and the fit, 16 for the selection
+static void check_list_bound(int64_t n, int bits) {
+    if (bits == 16) require(n <= ((int64_t)1 << 16), "n must be at most 2^16: cut a longer list with fdcm_matches_detect first");
+    else if (bits == 20) require(n <= ((int64_t)1 << 20), "n must be at most 2^20");
+    else require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
+}
+
+// a list in three forms: host records, device records, or (matches NULL with on_device = 0) the last search's; the host
+// calls, which have no last search, pass on_device = 1 for the test of the pointer
+static void check_match_list(const fdcm_match* matches, int64_t n, int on_device, int bits = 22) {
     require(n >= 0, "n is negative");
-    require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
+    check_list_bound(n, bits);
     require(on_device == 0 || on_device == 1, "on_device must be 0 or 1");
     require(!(on_device == 1 && n > 0 && !matches), "matches is null");
 }
 
-// matches NULL with on_device = 0: the records of the last fdcm_search on the handle, as fdcm_topk takes them.
-static void last_search_matches(const fdcm_featuremap* fm, const fdcm_match*& matches, int64_t& n, int& on_device) {
+// matches NULL with on_device = 0: the records of the last fdcm_search on the handle, as fdcm_topk takes them, under the
+// call's bound.
+static void last_search_matches(const fdcm_featuremap* fm, const fdcm_match*& matches, int64_t& n, int& on_device, int bits = 22) {
     if (matches || on_device) return;
     matches = fm->search.out.as<fdcm_match>();
     n = fm->last_n_out;
     on_device = 1;
-    require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
+    check_list_bound(n, 22);
     require(n == 0 || matches, "the handle holds no matches of a search");
+    check_list_bound(n, bits);
 }
+
+// what both detect calls on a match list check behind their limits (min_matched: the single call's gate, or null)
+static void check_matches_detect_args(const fdcm_featuremap* fm, const fdcm_templates* templates, int penalty, float tau,
+                                      const float* min_matched, int rescore, fdcm_match** out, int64_t* n_out) {
+    require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
+    require(std::isfinite(tau), "tau must be finite");
+    if (min_matched) require(*min_matched >= 0.f && *min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
+    require(rescore == 0 || rescore == 1, "rescore must be 0 or 1");
+    require(out && n_out, "null output");
+    check_handles(fm, templates);
+}
+
 
 int fdcm_matches_footprints(const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int32_t tmpl_index_base,
                             int32_t margin, int32_t* boxes_out) {
     return guarded([&] {
-        require(n >= 0, "n is negative");
-        require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
-        require(n == 0 || matches, "matches is null");
+        check_match_list(matches, n, 1);
         require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
         require(n == 0 || boxes_out, "boxes_out is null");
         require(templates != nullptr, "templates is null");
@@ -1336,11 +1356,11 @@ int fdcm_matches_verify(const fdcm_featuremap* fm, const fdcm_templates* templat
     return guarded([&] {
         check_match_list(matches, n, on_device);
         require(scores_out || fractions_out || costs_out, "every output is null");
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_handles(fm, templates);
         last_search_matches(fm, matches, n, on_device);
-        run_matches(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, nullptr, scores_out,
-                    fractions_out, costs_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+        MatchesIn in{MatchList{matches, n, on_device != 0, tmpl_index_base}};
+        in.verify = {scores_out, fractions_out, costs_out};
+        run_matches(const_cast<fdcm_featuremap*>(fm), templates, in);
     });
 }
 
@@ -1351,23 +1371,15 @@ int fdcm_matches_detect(const fdcm_featuremap* fm, const fdcm_templates* templat
     return guarded([&] {
         check_match_list(matches, n, on_device);
         require(max_score >= 0.f, "max_score must be >= 0 or +inf, never NaN");
-        require(max_detections >= 1 && max_detections <= 4096, "max_detections must be in [1, 4096]");
-        require(overlap_permille >= 0 && overlap_permille <= 1000, "overlap_permille must be in [0, 1000]");
-        require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
-        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
-        require(std::isfinite(tau), "tau must be finite");
-        require(min_matched >= 0.f && min_matched <= 1.f, "min_matched must be in [0, 1], never NaN");
-        require(rescore == 0 || rescore == 1, "rescore must be 0 or 1");
-        require(out && n_out, "null output");
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_detect_limits(max_detections, overlap_permille, nullptr, margin);
+        check_matches_detect_args(fm, templates, penalty, tau, &min_matched, rescore, out, n_out);
         last_search_matches(fm, matches, n, on_device);
         const MatchesDetect det{max_score == 0.f ? 0.f : max_score, max_detections, overlap_permille, margin, penalty, tau,
                                 min_matched == 0.f ? 0.f : min_matched, rescore};
-        records_call(out, [&] {
-            run_matches(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, &det, nullptr, nullptr,
-                        nullptr, out, n_out, indices_out, boxes_out, matched_out);
-        });
+        MatchesIn in{MatchList{matches, n, on_device != 0, tmpl_index_base}};
+        in.det = &det;
+        in.detect = {out, n_out, indices_out, boxes_out, matched_out};
+        records_call(out, [&] { run_matches(const_cast<fdcm_featuremap*>(fm), templates, in); });
     });
 }
 
@@ -1386,13 +1398,12 @@ int fdcm_matches_refine(const fdcm_featuremap* fm, const fdcm_templates* templat
         require((int64_t)na * (2 * hx + 1) * (int64_t)(2 * hy + 1) <= 65536, "na (2 hx + 1) (2 hy + 1) must be at most 65536");
         require(n == 0 || out, "out is null");
         require(out_on_device == 0 || out_on_device == 1, "out_on_device must be 0 or 1");
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_handles(fm, templates);
         if (rot) check_pivots(templates, rot);
         last_search_matches(fm, matches, n, on_device);
         require(n == 0 || out, "out is null");
-        run_matches_refine(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, rot, centre, hx, hy, sx,
-                           sy, out, out_on_device != 0, pose_out);
+        run_matches_refine(const_cast<fdcm_featuremap*>(fm), templates, MatchList{matches, n, on_device != 0, tmpl_index_base}, rot, centre,
+                           hx, hy, sx, sy, out, out_on_device != 0, pose_out);
     });
 }
 
@@ -1409,29 +1420,23 @@ int fdcm_matches_detect_objects(const fdcm_featuremap* fm, const fdcm_templates*
         std::vector<float> ms, mm;
         check_object_limits(n_objects, max_score, true, min_matched, ms, mm);
         check_detect_limits(max_detections, overlap_permille, &cross_permille, margin);
-        require(penalty == -1 || penalty == FDCM_DEFAULT_PENALTY || penalty == FDCM_EXPONENTIAL_PENALTY, "unknown penalty");
-        require(std::isfinite(tau), "tau must be finite");
-        require(rescore == 0 || rescore == 1, "rescore must be 0 or 1");
-        require(out && n_out, "null output");
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_matches_detect_args(fm, templates, penalty, tau, nullptr, rescore, out, n_out);
         check_object_labels(templates, objects, n_objects);
         last_search_matches(fm, matches, n, on_device);
         const MatchesDetect det{0.f, max_detections, overlap_permille, margin, penalty, tau, 0.f, rescore};
         const MatchesObjectsIn ob{objects, n_objects, ms.data(), min_matched ? mm.data() : nullptr, cross_permille};
-        records_call(out, [&] {
-            run_matches(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, &det, nullptr, nullptr,
-                        nullptr, out, n_out, indices_out, boxes_out, matched_out, &ob, nullptr);
-        });
+        MatchesIn in{MatchList{matches, n, on_device != 0, tmpl_index_base}};
+        in.det = &det;
+        in.objects = &ob;
+        in.detect = {out, n_out, indices_out, boxes_out, matched_out};
+        records_call(out, [&] { run_matches(const_cast<fdcm_featuremap*>(fm), templates, in); });
     });
 }
 
 int fdcm_matches_footprint_spans(const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int32_t tmpl_index_base,
                                  int32_t margin, int64_t* row_offsets, int64_t* areas, int32_t* spans) {
     return guarded([&] {
-        require(n >= 0, "n is negative");
-        require(n <= ((int64_t)1 << 22), "n must be at most 2^22");
-        require(n == 0 || matches, "matches is null");
+        check_match_list(matches, n, 1);
         require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
         require(row_offsets != nullptr, "row_offsets is null");
         require(templates != nullptr, "templates is null");
@@ -1445,12 +1450,12 @@ int fdcm_matches_shapes(const fdcm_featuremap* fm, const fdcm_templates* templat
         check_match_list(matches, n, on_device);
         require(margin >= 0 && margin <= 4096, "margin must be in [0, 4096]");
         require(row_offsets != nullptr, "row_offsets is null");
-        require(fm && templates, "null featuremap/templates");
-        require(fm->device == templates->device, "featuremap and templates live on different devices");
+        check_handles(fm, templates);
         require(matches || on_device || n == 0, "matches is null");  // (the rows are sized by n: the last search is no form here)
         const MatchesShapesOut so{margin, row_offsets, areas, spans};
-        run_matches(const_cast<fdcm_featuremap*>(fm), templates, matches, n, on_device != 0, tmpl_index_base, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &so);
+        MatchesIn in{MatchList{matches, n, on_device != 0, tmpl_index_base}};
+        in.shapes = &so;
+        run_matches(const_cast<fdcm_featuremap*>(fm), templates, in);
     });
 }
 
@@ -1484,8 +1489,7 @@ static void check_coverage_back(const fdcm_featuremap* fm, const uint8_t* labels
                                 const fdcm_coverage_params* params, const uint8_t* residual_out, float* bx, float* by) {
     if (residual_out)
         require(residual_out + width * height <= labels || labels + width * height <= residual_out, "residual_out must not overlap labels");
-    require(fm && templates, "null featuremap/templates");
-    require(fm->device == templates->device, "featuremap and templates live on different devices");
+    check_handles(fm, templates);
     if (rot) check_pivots(templates, rot);
     for (int64_t q = 0; q < n && templates->T > 0; ++q)
         require(poses[4 * q] < templates->T, "poses: tmpl is outside the template set");
@@ -1541,42 +1545,26 @@ int fdcm_scene_coverage(const fdcm_featuremap* fm, const uint8_t* labels, int64_
 }
 
 // Match lists: scene coverage and selection (include/fdcm.h).  The match calls' checks of the list with the call's own bound
-// on n, then scene coverage's of the parameters and the image; after the call's own outputs the residual, the handles and the
-// frame.  max_n: 2^20 (coverage) or 2^16 (select).
+// on n (check_list_bound's bits: 20, or 16 for the selection), then scene coverage's of the parameters and the image; after the
+// call's own outputs the residual, the handles and the frame, and last the records of the last search under the same bound.
 static void check_matches_coverage_front(const uint8_t* labels, int64_t width, int64_t height, const fdcm_match* matches, int64_t n,
-                                         int on_device, bool select, const fdcm_coverage_params* params) {
-    require(n >= 0, "n is negative");
-    if (select)
-        require(n <= ((int64_t)1 << 16), "n must be at most 2^16: cut a longer list with fdcm_matches_detect first");
-    else
-        require(n <= ((int64_t)1 << 20), "n must be at most 2^20");
-    require(on_device == 0 || on_device == 1, "on_device must be 0 or 1");
-    require(!(on_device == 1 && n > 0 && !matches), "matches is null");
+                                         int on_device, int bits, const fdcm_coverage_params* params) {
+    check_match_list(matches, n, on_device, bits);
     check_coverage_front(labels, width, height, nullptr, nullptr, 0, params);
-}
-
-// the records of the last search (matches NULL with on_device = 0) under the call's bound
-static void last_search_matches_bounded(const fdcm_featuremap* fm, const fdcm_match*& matches, int64_t& n, int& on_device, bool select) {
-    if (matches || on_device) return;
-    last_search_matches(fm, matches, n, on_device);
-    if (select)
-        require(n <= ((int64_t)1 << 16), "n must be at most 2^16: cut a longer list with fdcm_matches_detect first");
-    else
-        require(n <= ((int64_t)1 << 20), "n must be at most 2^20");
 }
 
 int fdcm_matches_coverage(const fdcm_featuremap* fm, const uint8_t* labels, int64_t width, int64_t height, int labels_on_device,
                           const fdcm_templates* templates, const fdcm_match* matches, int64_t n, int matches_on_device,
                           int32_t tmpl_index_base, const fdcm_coverage_params* params, int32_t* counts_out, uint8_t* residual_out) {
     return guarded([&] {
-        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, false, params);
+        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, 20, params);
         require(n == 0 || counts_out, "counts_out is null");
         float bx, by;
         check_coverage_back(fm, labels, width, height, templates, nullptr, nullptr, 0, params, residual_out, &bx, &by);
-        last_search_matches_bounded(fm, matches, n, matches_on_device, false);
+        last_search_matches(fm, matches, n, matches_on_device, 20);
         require(n == 0 || counts_out, "counts_out is null");
         run_matches_coverage(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, labels_on_device != 0, (int)bx, (int)by,
-                             templates, matches, n, matches_on_device != 0, tmpl_index_base, *params, counts_out, residual_out);
+                             templates, MatchList{matches, n, matches_on_device != 0, tmpl_index_base}, *params, counts_out, residual_out);
     });
 }
 
@@ -1585,14 +1573,14 @@ int fdcm_matches_select(const fdcm_featuremap* fm, const uint8_t* labels, int64_
                         int32_t tmpl_index_base, const fdcm_coverage_params* params, const fdcm_select_params* sel, int32_t* selected_out,
                         int32_t* counts_out, int64_t* n_out, uint8_t* residual_out) {
     return guarded([&] {
-        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, true, params);
+        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, 16, params);
         check_select_params(sel, selected_out, counts_out, n_out);
         float bx, by;
         check_coverage_back(fm, labels, width, height, templates, nullptr, nullptr, 0, params, residual_out, &bx, &by);
-        last_search_matches_bounded(fm, matches, n, matches_on_device, true);
+        last_search_matches(fm, matches, n, matches_on_device, 16);
         run_matches_select(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, labels_on_device != 0, (int)bx, (int)by,
-                           templates, matches, n, matches_on_device != 0, tmpl_index_base, *params, *sel, selected_out, counts_out, n_out,
-                           residual_out);
+                           templates, MatchList{matches, n, matches_on_device != 0, tmpl_index_base}, *params, *sel, selected_out, counts_out,
+                           n_out, residual_out);
     });
 }
 
@@ -1602,7 +1590,7 @@ int fdcm_matches_fit(const fdcm_featuremap* fm, const uint8_t* labels, int64_t w
                      const fdcm_coverage_params* params, const fdcm_fit_params* fit, fdcm_match* out, int out_on_device, int32_t* info_out,
                      float* rms_out) {
     return guarded([&] {
-        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, false, params);
+        check_matches_coverage_front(labels, width, height, matches, n, matches_on_device, 20, params);
         require(fit != nullptr, "fit is null");
         require(fit->iterations >= 1 && fit->iterations <= 8, "iterations must be in [1, 8]");
         require(fit->min_pixels >= 3, "min_pixels must be at least 3");
@@ -1613,10 +1601,11 @@ int fdcm_matches_fit(const fdcm_featuremap* fm, const uint8_t* labels, int64_t w
         require(out_on_device == 0 || out_on_device == 1, "out_on_device must be 0 or 1");
         float bx, by;
         check_coverage_back(fm, labels, width, height, templates, nullptr, nullptr, 0, params, nullptr, &bx, &by);
-        last_search_matches_bounded(fm, matches, n, matches_on_device, false);
+        last_search_matches(fm, matches, n, matches_on_device, 20);
         require(n == 0 || out, "out is null");
         run_matches_fit(const_cast<fdcm_featuremap*>(fm), labels, (int)width, (int)height, labels_on_device != 0, (int)bx, (int)by, templates,
-                        matches, n, matches_on_device != 0, tmpl_index_base, *params, *fit, out, out_on_device != 0, info_out, rms_out);
+                        MatchList{matches, n, matches_on_device != 0, tmpl_index_base}, *params, *fit, out, out_on_device != 0, info_out,
+                        rms_out);
     });
 }
 

@@ -51,6 +51,15 @@
 //                       table pass finds the stepped one outside the map.
 //
 // All arithmetic of the decision is integer; the float adds of step 1 are the cost rule's own (-ffp-contract=off as everywhere).
+//
+// The host side: five drivers made of stages that each exist once.  CovCall is the frame of a call (turn, device, stream, the
+// labels and their upload, the residual and the claim plane, a host list's records, the buffers and their poison; the workspace
+// layout is stated beside it); DevTable a table on the device, from upload_table (a pose list's HostTable) or make_table (a part
+// of a match list); for_items the items in launches of at most kCovMaxGrid; select_stage the selection on a table, counts_down
+// the coverage calls' way down, both with a map from table entry to list position.
+//   run_scene_coverage    HostTable, upload_table, launch_coverage, counts_down      run_scene_select    .., select_stage
+//   run_matches_coverage  records; per part make_table, launch_coverage; counts_down  run_matches_select  .., make_table, select_stage
+//   run_matches_fit       records; per part and pass make_table, k_fit_moments through for_items, k_fit_step
 #include <algorithm>
 #include <cstring>
 
@@ -623,22 +632,142 @@ __global__ void __launch_bounds__(256) k_fit_step(const FitArgs a) {
     info[1] += 1;
 }
 
+// ---------------------------------------------------------------------------------------------- the host side
+// The workspace of the coverage calls, stated once.  The buffers are the handle's own (coverage, coverage_stage), not the
+// exhaustive calls' shared workspace; every block is a multiple of 256 bytes, and a block in brackets is there for some calls only:
+//
+//   device    [records: a host list; the fit's own copy of any list, with replaced transforms | info | rms behind it]
+//             | the table: lines | poses | item offsets (HostTable, made on the host), or
+//                          [host bins] | lines | poses | strips | item offsets | total and largest (TableLayout, made on the device)
+//             | counters, (edges, explained) per entry
+//             | [selection: sel | sel_new | fresh | cur | alive (SelLayout)]   [fit: the part's moments]
+//             | [labels: host callers] | [the output plane: the residual of a host caller, the claim plane]
+//   staging   what goes up -- the host-made table, or [host records] | [a part's host bins] -- and then, the upload done, what
+//             comes down: the counters (with sel and sel_new), or the fit's records | info | rms
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// The frame of a call: the handle's turn, its device and stream, the label image with its frame (bx, by) and the call's
+// parameters.  It owns the labels -- the one place where a host caller's image goes up -- and the two ways a call treats its
+// output plane: the coverage calls' residual (optional, a copy of the labels where the labels are) and the selection calls'
+// claim plane (always there, the caller's own buffer when that is on the device).
+struct CovCall {
+    fdcm_featuremap* const fm;
+    const uint8_t* const image;
+    const int width, height;
+    const bool on_device;
+    const int bx, by;
+    const fdcm_coverage_params& par;
+    const size_t npix;
+    std::lock_guard<std::mutex> turn;
+    hipStream_t st = nullptr;
+    char *d = nullptr, *h = nullptr;    // the two buffers, after reserve
+    const uint8_t* d_labels = nullptr;  // after labels
+
+    CovCall(fdcm_featuremap* fm, const uint8_t* image, int width, int height, bool on_device, int bx, int by, const fdcm_coverage_params& par)
+        : fm(fm), image(image), width(width), height(height), on_device(on_device), bx(bx), by(by), par(par),
+          npix((size_t)width * (size_t)height), turn(fm->seam_mutex) {
+        FDCM_HIP(hipSetDevice(fm->device));
+        ensure_stream(fm);
+        st = fm->stream;
+    }
+    // no entries, an empty set or an empty map: nothing is explained
+    bool nothing(int64_t n, const fdcm_templates* t) const { return n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0; }
+    // what the last blocks of the device layout take
+    size_t labels_bytes() const { return on_device ? 0 : al256(npix); }
+    size_t residual_bytes(const uint8_t* residual) const { return on_device || !residual ? 0 : al256(npix); }
+    size_t claim_bytes(const uint8_t* residual) const { return on_device && residual ? 0 : al256(npix); }
+    // FDCM_POISON (fdcm_internal.h, "the tests' switches"): the buffers hold the word at the head of a call, before anything goes up
+    void reserve(size_t device, size_t staging) {
+        fm->coverage.reserve(device);
+        fm->coverage_stage.reserve(staging);
+        if (test_switches().poison) {
+            FDCM_HIP(hipStreamSynchronize(st));  // (nothing queued still reads the staging)
+            poison_fill(fm->coverage, st, FDCM_FILL_COVERAGE);
+            poison_fill(fm->coverage_stage, FDCM_FILL_COVERAGE_STAGE);
+        }
+        d = (char*)fm->coverage.p;
+        h = (char*)fm->coverage_stage.p;
+    }
+    void labels(size_t o_lab) {
+        d_labels = image;
+        if (on_device) return;
+        FDCM_HIP(hipMemcpyAsync(d + o_lab, image, npix, hipMemcpyHostToDevice, st));
+        d_labels = (const uint8_t*)(d + o_lab);
+    }
+    uint8_t* plane_copy(uint8_t* plane) {
+        if (plane) FDCM_HIP(hipMemcpyAsync(plane, d_labels, npix, hipMemcpyDeviceToDevice, st));
+        return plane;
+    }
+    uint8_t* residual_plane(uint8_t* residual, size_t o_res) { return plane_copy(on_device || !residual ? residual : (uint8_t*)(d + o_res)); }
+    uint8_t* claim_plane(uint8_t* residual, size_t o_plane) { return plane_copy(on_device && residual ? residual : (uint8_t*)(d + o_plane)); }
+    void plane_down(uint8_t* residual, const uint8_t* plane) {  // queued; the caller waits
+        if (residual && !on_device) FDCM_HIP(hipMemcpyAsync(residual, plane, npix, hipMemcpyDeviceToHost, st));
+    }
+    // no window holds a pixel: the residual is a copy
+    void copy_labels(uint8_t* residual) {
+        if (residual && on_device) {
+            FDCM_HIP(hipMemcpyAsync(residual, image, npix, hipMemcpyDeviceToDevice, st));
+            FDCM_HIP(hipStreamSynchronize(st));
+        } else if (residual) {
+            std::memcpy(residual, image, npix);
+        }
+    }
+    // the records of a host list go up through the staging's head to the device buffer's; a device list stays where it is
+    static size_t records_bytes(const MatchList& m) { return m.on_device ? 0 : al256((size_t)m.n * sizeof(fdcm_match)); }
+    const fdcm_match* records(const MatchList& m) {
+        if (m.on_device) return m.rec;
+        std::memcpy(h, m.rec, (size_t)m.n * sizeof(fdcm_match));
+        FDCM_HIP(hipMemcpyAsync(d, h, (size_t)m.n * sizeof(fdcm_match), hipMemcpyHostToDevice, st));
+        return (const fdcm_match*)d;
+    }
+};
+
+// A table on the device: the lines, one CovPose per entry, the items' prefix sums, the entries, the items (strips) in all and
+// of the entry with most.  Two producers: upload_table (a pose list's, made on the host) and make_table (a part of a match list).
+struct DevTable {
+    const CoverageLine* lines;
+    const CovPose* poses;
+    const long long* item0;
+    int n;
+    long long items, most;
+    SelArgs args(const CovCall& c) const {
+        return SelArgs{c.d_labels, c.width, c.height, (int)c.fm->m, c.fm->tx, c.fm->ty, c.bx, c.by, (int)c.par.radius, (int)c.par.bin_tolerance,
+                       lines, poses, item0, n};
+    }
+};
+
+// The items in launches of at most kCovMaxGrid: launch(grid, first item).
+template <class Launch>
+void for_items(long long items, Launch launch) {
+    for (long long base = 0; base < items; base += kCovMaxGrid) {
+        launch((unsigned)std::min(kCovMaxGrid, items - base), base);
+        FDCM_HIP(hipGetLastError());
+    }
+}
+
+void launch_coverage(hipStream_t st, const SelArgs& a, long long items, int* d_cnt, uint8_t* d_res) {
+    for_items(items, [&](unsigned grid, long long base) {
+        hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, a.labels, a.width, a.height, a.m, a.tx, a.ty, a.bx, a.by,
+                           a.radius, a.tol, a.lines, a.poses, a.item0, a.n_poses, base, d_cnt, d_res);
+    });
+}
+
 // What both calls make of a checked pose list: the pairs, one CovPose per admissible pose with a window that holds a pixel, in
-// list order, the items' prefix sums and, per entry, its pose.  adm[q]: pose q is admissible.
-struct CovTable {
+// list order, the items' prefix sums and, per entry, its pose.  adm[q]: pose q is admissible.  On the device the table is
+// lines | poses | item offsets from the buffer's head, and `end` is where the counters go.
+struct HostTable {
     CoveragePairs W;
     std::vector<CovPose> tab;
-    std::vector<long long> item0;
+    std::vector<long long> item0{0};
     std::vector<int64_t> pose_of;
     std::vector<char> adm;
+    long long most = 1;
+    size_t o_tab = 0, o_item = 0, end = 0;
     void make(const fdcm_featuremap* fm, int width, int height, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses,
               int64_t n, int margin) {
         coverage_pairs(fm, t, rot, poses, n, margin, W);
         const int nr = rot ? rot->n : 1;
         adm.assign((size_t)n, 0);
-        item0.push_back(0);
         for (int64_t q = 0; q < n; ++q) {
             const int32_t* p = poses + 4 * q;
             const size_t u = W.find((int64_t)p[0] * nr + p[1]);
@@ -650,128 +779,81 @@ struct CovTable {
             const int x1 = std::min(width - 1, f[2] + p[2]), y1 = std::min(height - 1, f[3] + p[3]);
             if (x0 > x1 || y0 > y1) continue;  // an empty window: (0, 0)
             const int rows = std::max(1, kCovStripPixels / (x1 - x0 + 1));
+            const long long strips = (y1 - y0 + rows) / rows;
             tab.push_back(CovPose{W.line0[u], W.nl[u], p[2], p[3], x0, y0, x1, y1, rows, {0, 0, 0}});
             pose_of.push_back(q);
-            item0.push_back(item0.back() + (y1 - y0 + rows) / rows);
+            item0.push_back(item0.back() + strips);
+            most = std::max(most, strips);
         }
+        o_tab = al256(W.lines.size() * sizeof(CoverageLine));
+        o_item = o_tab + al256(tab.size() * sizeof(CovPose));
+        end = o_item + al256(item0.size() * sizeof(long long));
     }
 };
 
-// FDCM_POISON (fdcm_internal.h, "the tests' switches"): the handle's coverage buffers hold the word at the head of a call, before a
-// host caller's labels go up
-void poison_coverage(fdcm_featuremap* fm) {
-    if (!test_switches().poison) return;
-    FDCM_HIP(hipStreamSynchronize(fm->stream));  // (nothing queued still reads the staging)
-    poison_fill(fm->coverage, fm->stream, FDCM_FILL_COVERAGE);
-    poison_fill(fm->coverage_stage, FDCM_FILL_COVERAGE_STAGE);
+// One upload of lines, poses and item offsets through the staging, and the counters behind them zeroed.
+DevTable upload_table(CovCall& c, const HostTable& T) {
+    std::memcpy(c.h, T.W.lines.data(), T.W.lines.size() * sizeof(CoverageLine));
+    std::memcpy(c.h + T.o_tab, T.tab.data(), T.tab.size() * sizeof(CovPose));
+    std::memcpy(c.h + T.o_item, T.item0.data(), T.item0.size() * sizeof(long long));
+    FDCM_HIP(hipMemcpyAsync(c.d, c.h, T.end, hipMemcpyHostToDevice, c.st));
+    FDCM_HIP(hipMemsetAsync(c.d + T.end, 0, T.tab.size() * 2 * sizeof(int32_t), c.st));
+    return DevTable{(const CoverageLine*)c.d, (const CovPose*)(c.d + T.o_tab), (const long long*)(c.d + T.o_item), (int)T.tab.size(),
+                    T.item0.back(), T.most};
 }
 
-// no window holds a pixel: the residual is a copy
-void copy_labels(const uint8_t* labels, size_t npix, bool on_device, uint8_t* residual, hipStream_t st) {
-    if (residual && on_device) {
-        FDCM_HIP(hipMemcpyAsync(residual, labels, npix, hipMemcpyDeviceToDevice, st));
-        FDCM_HIP(hipStreamSynchronize(st));
-    } else if (residual) {
-        std::memcpy(residual, labels, npix);
-    }
-}
-
-}  // namespace
-
-// The arguments are checked (fdcm_capi.cpp).  One prepare_pairs for the distinct pairs of the list (n <= 2^20), one upload of
-// lines, poses and item offsets (and a host caller's labels), the counters zeroed and the residual copied on the stream, then
-// the launches.  The buffers are the handle's own (coverage, coverage_stage), not the exhaustive calls' shared workspace.
-void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
-                        const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
-                        const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual) {
-    const size_t npix = (size_t)width * (size_t)height;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    FDCM_HIP(hipSetDevice(fm->device));
-    ensure_stream(fm);
-    hipStream_t st = fm->stream;
-    // no poses, an empty set or an empty map: nothing is explained, the residual is the labels, the counts stay unwritten
-    const bool nothing = n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0;
-    CovTable T;
-    if (!nothing) {
-        T.make(fm, width, height, t, rot, poses, n, params.margin);
-        for (int64_t q = 0; q < n; ++q) counts[2 * q] = counts[2 * q + 1] = T.adm[q] ? 0 : -1;
-    }
-    const CoveragePairs& W = T.W;
-    const std::vector<CovPose>& tab = T.tab;
-    const std::vector<long long>& item0 = T.item0;
-    const std::vector<int64_t>& pose_of = T.pose_of;  // per entry of tab: its pose
-    if (tab.empty()) return copy_labels(labels, npix, on_device, residual, st);
-    // device: lines | poses | item offsets | counters | labels (host callers) | residual (host callers)
-    const size_t o_tab = al256(W.lines.size() * sizeof(CoverageLine)), o_item = o_tab + al256(tab.size() * sizeof(CovPose)),
-                 o_cnt = o_item + al256(item0.size() * sizeof(long long)), o_lab = o_cnt + al256(tab.size() * 2 * sizeof(int32_t)),
-                 o_res = o_lab + (on_device ? 0 : al256(npix)), total = o_res + (on_device || !residual ? 0 : al256(npix));
-    fm->coverage.reserve(total);
-    fm->coverage_stage.reserve(o_cnt);
-    poison_coverage(fm);
-    char* d = (char*)fm->coverage.p;
-    char* h = (char*)fm->coverage_stage.p;
-    const uint8_t* d_labels = labels;
-    uint8_t* d_res = residual;
-    if (!on_device) {
-        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
-        d_labels = (const uint8_t*)(d + o_lab);
-        d_res = residual ? (uint8_t*)(d + o_res) : nullptr;
-    }
-    std::memcpy(h, W.lines.data(), W.lines.size() * sizeof(CoverageLine));
-    std::memcpy(h + o_tab, tab.data(), tab.size() * sizeof(CovPose));
-    std::memcpy(h + o_item, item0.data(), item0.size() * sizeof(long long));
-    FDCM_HIP(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, st));
-    FDCM_HIP(hipMemsetAsync(d + o_cnt, 0, tab.size() * 2 * sizeof(int32_t), st));
-    if (d_res) FDCM_HIP(hipMemcpyAsync(d_res, d_labels, npix, hipMemcpyDeviceToDevice, st));
-    const long long items = item0.back();
-    for (long long base = 0; base < items; base += kCovMaxGrid) {
-        const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
-        hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by,
-                           (int)params.radius, (int)params.bin_tolerance, (const CoverageLine*)d, (const CovPose*)(d + o_tab),
-                           (const long long*)(d + o_item), (int)tab.size(), base, (int*)(d + o_cnt), d_res);
-        FDCM_HIP(hipGetLastError());
-    }
-    int32_t* h_cnt = (int32_t*)h;  // (the staging is free again: this copy is behind the upload on the stream)
-    FDCM_HIP(hipMemcpyAsync(h_cnt, d + o_cnt, tab.size() * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (!on_device && residual) FDCM_HIP(hipMemcpyAsync(residual, d_res, npix, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipStreamSynchronize(st));
-    for (size_t i = 0; i < tab.size(); ++i) {
-        counts[2 * pose_of[i]] = h_cnt[2 * i];
-        counts[2 * pose_of[i] + 1] = h_cnt[2 * i + 1];
+// The counters of `entries` table entries come down through the staging (free again: the copy is behind the upload on the
+// stream), with a host caller's residual, and go to the list positions pose_of gives (null: the entry's own).
+void counts_down(CovCall& c, const int* d_cnt, size_t entries, const int64_t* pose_of, int32_t* counts, uint8_t* residual, const uint8_t* d_res) {
+    const int32_t* h_cnt = (const int32_t*)c.h;
+    FDCM_HIP(hipMemcpyAsync(c.h, d_cnt, entries * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
+    c.plane_down(residual, d_res);
+    FDCM_HIP(hipStreamSynchronize(c.st));
+    for (size_t i = 0; i < entries; ++i) {
+        const size_t q = pose_of ? (size_t)pose_of[i] : i;
+        counts[2 * q] = h_cnt[2 * i];
+        counts[2 * q + 1] = h_cnt[2 * i + 1];
     }
 }
 
+// ---- the selection stage
 // Rounds are queued kSelBatch at a time, as nms_rounds queues its own: after a batch the host reads the pose the next round
 // would accept and stops when there is none, so no round costs a host round trip, and the launches queued behind the list's
 // end leave at their first load.
 constexpr int kSelBatch = 64;
 
+// The selection's arrays, from the table's counters on: counters | sel | sel_new (what comes down) | fresh | cur | alive
+struct SelLayout {
+    size_t o_cnt, o_sel, o_new, o_fresh, o_cur, o_alive, end;
+    SelLayout(size_t at, size_t entries, size_t ms)
+        : o_cnt(at), o_sel(o_cnt + al256(entries * 2 * sizeof(int32_t))), o_new(o_sel + al256(ms * sizeof(int32_t))),
+          o_fresh(o_new + al256(ms * sizeof(int32_t))), o_cur(o_fresh + al256(entries * sizeof(int32_t))),
+          o_alive(o_cur + al256(entries * sizeof(int32_t))), end(o_alive + al256(entries)) {}
+    size_t down() const { return o_fresh - o_cnt; }
+};
+
 // The launches of the rule on a table that is on the device with its counters (zero, or what k_matches_table left), sel at
 // kSelNone and fresh at 0: one k_scene_coverage launch for the counts, k_select_decide's first form for S_0, and per round
-// claim, recount, decide.  items: the table's strips; strips: of the entry with most.
-void select_rounds(hipStream_t st, const SelArgs& a, long long items, long long strips, size_t ms, const fdcm_select_params& sel, int* d_cnt,
-                   int* d_sel, int* d_new, int* d_fresh, int* d_cur, uint8_t* d_alive, uint8_t* plane) {
+// claim, recount, decide.
+void select_rounds(hipStream_t st, const SelArgs& a, const DevTable& T, const fdcm_select_params& sel, char* d, const SelLayout& S,
+                   uint8_t* plane) {
+    int *d_cnt = (int*)(d + S.o_cnt), *d_sel = (int*)(d + S.o_sel), *d_new = (int*)(d + S.o_new), *d_fresh = (int*)(d + S.o_fresh),
+        *d_cur = (int*)(d + S.o_cur);
+    uint8_t* d_alive = (uint8_t*)(d + S.o_alive);
     const unsigned pose_wgs = (unsigned)(((size_t)a.n_poses + 255) / 256);
-    for (long long base = 0; base < items; base += kCovMaxGrid) {
-        const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
-        hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, a.labels, a.width, a.height, a.m, a.tx, a.ty, a.bx, a.by,
-                           a.radius, a.tol, a.lines, a.poses, a.item0, a.n_poses, base, d_cnt, (uint8_t*)nullptr);
-        FDCM_HIP(hipGetLastError());
-    }
+    launch_coverage(st, a, T.items, d_cnt, nullptr);
     hipLaunchKernelGGL(k_select_decide, dim3(pose_wgs), dim3(256), 0, st, a.poses, a.n_poses, d_cnt, d_sel, -1, sel, d_alive, d_fresh, d_cur,
                        d_sel);
     FDCM_HIP(hipGetLastError());
-    const int rounds = (int)std::min(ms, (size_t)a.n_poses);  // a round accepts a pose of the table or finds the list ended
+    const int rounds = (int)std::min((size_t)sel.max_selected, (size_t)a.n_poses);  // a round accepts a pose of the table or finds the list ended
     for (int r = 0; r < rounds;) {
         for (const int r1 = std::min(rounds, r + kSelBatch); r < r1; ++r) {
-            hipLaunchKernelGGL(k_select_claim, dim3((unsigned)strips), dim3(kCovThreads), 0, st, a, d_sel, r, d_cur, d_new, plane);
+            hipLaunchKernelGGL(k_select_claim, dim3((unsigned)T.most), dim3(kCovThreads), 0, st, a, d_sel, r, d_cur, d_new, plane);
             FDCM_HIP(hipGetLastError());
             if (r + 1 == rounds) continue;  // the last pose the call may accept: nobody asks who is next
-            for (long long base = 0; base < items; base += kCovMaxGrid) {
-                const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - base);
+            for_items(T.items, [&](unsigned grid, long long base) {
                 hipLaunchKernelGGL(k_select_recount, dim3(grid), dim3(kCovThreads), 0, st, a, base, d_sel, r, d_alive, d_fresh, plane);
-                FDCM_HIP(hipGetLastError());
-            }
+            });
             hipLaunchKernelGGL(k_select_decide, dim3(pose_wgs), dim3(256), 0, st, a.poses, a.n_poses, d_cnt, d_sel, r, sel, d_alive, d_fresh,
                                d_cur, d_sel + r + 1);
             FDCM_HIP(hipGetLastError());
@@ -784,70 +866,26 @@ void select_rounds(hipStream_t st, const SelArgs& a, long long items, long long 
     }
 }
 
-// The arguments are checked (fdcm_capi.cpp).  run_scene_coverage's preparation and buffers; then one k_scene_coverage launch
-// for the counts, k_select_decide's first form for S_0, and per round claim, recount, decide.
-void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
-                      const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
-                      const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
-                      int64_t* n_out, uint8_t* residual) {
-    const size_t npix = (size_t)width * (size_t)height;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    FDCM_HIP(hipSetDevice(fm->device));
-    ensure_stream(fm);
-    hipStream_t st = fm->stream;
-    *n_out = 0;
-    CovTable T;
-    if (!(n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0)) T.make(fm, width, height, t, rot, poses, n, params.margin);
-    if (T.tab.empty()) return copy_labels(labels, npix, on_device, residual, st);  // nothing explains a pixel: nothing is accepted
-    const size_t nt = T.tab.size(), ms = (size_t)sel.max_selected;
-    // device: lines | poses | item offsets | counters, sel, sel_new (what comes down) | fresh | cur | alive | labels (host
-    // callers) | claim plane (unless the caller's residual is on the device)
-    const size_t o_tab = al256(T.W.lines.size() * sizeof(CoverageLine)), o_item = o_tab + al256(nt * sizeof(CovPose)),
-                 o_cnt = o_item + al256(T.item0.size() * sizeof(long long)), o_sel = o_cnt + al256(nt * 2 * sizeof(int32_t)),
-                 o_new = o_sel + al256(ms * sizeof(int32_t)), o_fresh = o_new + al256(ms * sizeof(int32_t)),
-                 o_cur = o_fresh + al256(nt * sizeof(int32_t)), o_alive = o_cur + al256(nt * sizeof(int32_t)), o_lab = o_alive + al256(nt),
-                 o_plane = o_lab + (on_device ? 0 : al256(npix)), total = o_plane + (on_device && residual ? 0 : al256(npix));
-    fm->coverage.reserve(total);
-    fm->coverage_stage.reserve(std::max(o_cnt, o_fresh - o_cnt));
-    poison_coverage(fm);
-    char* d = (char*)fm->coverage.p;
-    char* h = (char*)fm->coverage_stage.p;
-    const uint8_t* d_labels = labels;
-    if (!on_device) {
-        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
-        d_labels = (const uint8_t*)(d + o_lab);
-    }
-    uint8_t* plane = on_device && residual ? residual : (uint8_t*)(d + o_plane);
-    std::memcpy(h, T.W.lines.data(), T.W.lines.size() * sizeof(CoverageLine));
-    std::memcpy(h + o_tab, T.tab.data(), nt * sizeof(CovPose));
-    std::memcpy(h + o_item, T.item0.data(), T.item0.size() * sizeof(long long));
-    FDCM_HIP(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, st));
-    FDCM_HIP(hipMemsetAsync(d + o_cnt, 0, nt * 2 * sizeof(int32_t), st));
-    FDCM_HIP(hipMemsetAsync(d + o_sel, 0x7f, ms * sizeof(int32_t), st));  // kSelNone
-    FDCM_HIP(hipMemsetAsync(d + o_fresh, 0, nt * sizeof(int32_t), st));
-    FDCM_HIP(hipMemcpyAsync(plane, d_labels, npix, hipMemcpyDeviceToDevice, st));
-    SelArgs a{d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by, (int)params.radius, (int)params.bin_tolerance,
-              (const CoverageLine*)d, (const CovPose*)(d + o_tab), (const long long*)(d + o_item), (int)nt};
-    int* d_cnt = (int*)(d + o_cnt);
-    int* d_sel = (int*)(d + o_sel);
-    int* d_new = (int*)(d + o_new);
-    int* d_fresh = (int*)(d + o_fresh);
-    int* d_cur = (int*)(d + o_cur);
-    uint8_t* d_alive = (uint8_t*)(d + o_alive);
-    const long long items = T.item0.back();
-    long long strips = 1;  // of the pose with most
-    for (size_t i = 0; i < nt; ++i) strips = std::max(strips, T.item0[i + 1] - T.item0[i]);
-    select_rounds(st, a, items, strips, ms, sel, d_cnt, d_sel, d_new, d_fresh, d_cur, d_alive, plane);
-    FDCM_HIP(hipMemcpyAsync(h, d + o_cnt, o_fresh - o_cnt, hipMemcpyDeviceToHost, st));  // (the staging is free again)
-    if (residual && !on_device) FDCM_HIP(hipMemcpyAsync(residual, plane, npix, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipStreamSynchronize(st));
-    const int32_t* h_cnt = (const int32_t*)h;
-    const int32_t* h_sel = (const int32_t*)(h + (o_sel - o_cnt));
-    const int32_t* h_new = (const int32_t*)(h + (o_new - o_cnt));
+// The selection on a table that is on the device, its counters at S.o_cnt: sel at kSelNone, fresh at 0, the claim plane a copy
+// of the labels, the rounds (none when no entry has a strip: nothing is accepted, and the plane is the labels), one download of
+// counters, sel and sel_new, and the accepted entries as positions of the list (pose_of; null: the entry's own).
+void select_stage(CovCall& c, const DevTable& T, const SelLayout& S, const fdcm_select_params& sel, uint8_t* residual, size_t o_plane,
+                  const int64_t* pose_of, int32_t* selected, int32_t* counts, int64_t* n_out) {
+    const size_t ms = (size_t)sel.max_selected;
+    FDCM_HIP(hipMemsetAsync(c.d + S.o_sel, 0x7f, ms * sizeof(int32_t), c.st));  // kSelNone
+    FDCM_HIP(hipMemsetAsync(c.d + S.o_fresh, 0, (size_t)T.n * sizeof(int32_t), c.st));
+    uint8_t* plane = c.claim_plane(residual, o_plane);
+    if (T.items > 0) select_rounds(c.st, T.args(c), T, sel, c.d, S, plane);
+    FDCM_HIP(hipMemcpyAsync(c.h, c.d + S.o_cnt, S.down(), hipMemcpyDeviceToHost, c.st));  // (the staging is free again)
+    c.plane_down(residual, plane);
+    FDCM_HIP(hipStreamSynchronize(c.st));
+    const int32_t* h_cnt = (const int32_t*)c.h;
+    const int32_t* h_sel = (const int32_t*)(c.h + (S.o_sel - S.o_cnt));
+    const int32_t* h_new = (const int32_t*)(c.h + (S.o_new - S.o_cnt));
     size_t k = 0;
-    for (; k < ms && h_sel[k] < (int32_t)nt; ++k) {
+    for (; k < ms && h_sel[k] < (int32_t)T.n; ++k) {
         const int32_t i = h_sel[k];
-        selected[k] = (int32_t)T.pose_of[i];
+        selected[k] = pose_of ? (int32_t)pose_of[i] : i;
         counts[3 * k] = h_cnt[2 * i];
         counts[3 * k + 1] = h_cnt[2 * i + 1];
         counts[3 * k + 2] = h_new[k];
@@ -855,16 +893,20 @@ void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int
     *n_out = (int64_t)k;
 }
 
-// ---------------------------------------------------------------------------------------------- match lists
-namespace {
-
+// ---- the table of a part of a match list
 constexpr size_t kCovPartBytes = (size_t)768 << 20;  // what a part's table may take (lines, host bins, poses, strips, offsets)
 
 size_t table_record_bytes(const fdcm_templates* t, bool host_bins) {
     return (size_t)t->max_lines * (sizeof(CoverageLine) + (host_bins ? 2 : 0)) + sizeof(CovPose) + sizeof(int) + sizeof(long long);
 }
 
-// What both calls on match lists lay out for a table of pn records, from `at` on: host bins | lines | poses | strips | item
+// The records a part holds: what per_record bytes each allow in kCovPartBytes, FDCM_COVERAGE_PART at most.
+size_t part_records(size_t N, size_t per_record) {
+    const size_t pn = std::max<size_t>(1, std::min(N, kCovPartBytes / per_record));
+    return test_switches().coverage_part > 0 ? std::min(pn, (size_t)test_switches().coverage_part) : pn;
+}
+
+// What the calls on match lists lay out for a table of pn records, from `at` on: host bins | lines | poses | strips | item
 // offsets | total and largest
 struct TableLayout {
     size_t o_bins, o_lines, o_tab, o_strips, o_item, o_tot, end;
@@ -877,18 +919,19 @@ struct TableLayout {
         o_tot = o_item + al256((pn + 1) * sizeof(long long));
         end = o_tot + 256;
     }
+    size_t bins_bytes() const { return o_lines - o_bins; }  // (of the staging as well)
 };
 
 // Queues k_matches_table and k_strip_scan for the records [q0, q0 + cnt) of the list at d_rec (the host bins of the part are
-// uploaded through h_bins first), waits, and returns the part's strips in all and of the entry with most.
-void make_table(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* d_rec, size_t q0, size_t cnt, int32_t base, int margin,
-                int width, int height, const std::vector<unsigned short>& bins, char* d, char* h_bins, const TableLayout& L, int* d_cnt,
-                long long* items, long long* most) {
-    hipStream_t st = fm->stream;
+// uploaded through h_bins first), waits, and returns the part's table; its counters go to d_cnt + 2 q0.
+DevTable make_table(CovCall& c, const fdcm_templates* t, const fdcm_match* d_rec, size_t q0, size_t cnt, int32_t base,
+                    const std::vector<unsigned short>& bins, char* h_bins, const TableLayout& L, int* d_cnt) {
+    fdcm_featuremap* fm = c.fm;
+    char* d = c.d;
     const size_t Lmax = (size_t)t->max_lines;
     if (!bins.empty() && Lmax) {
         std::memcpy(h_bins, bins.data() + q0 * Lmax, cnt * Lmax * 2);
-        FDCM_HIP(hipMemcpyAsync(d + L.o_bins, h_bins, cnt * Lmax * 2, hipMemcpyHostToDevice, st));
+        FDCM_HIP(hipMemcpyAsync(d + L.o_bins, h_bins, cnt * Lmax * 2, hipMemcpyHostToDevice, c.st));
     }
     TableArgs a{};
     a.tlines = t->d_lines.as<float4>(); a.toff = t->d_offsets.as<long long>();
@@ -897,157 +940,117 @@ void make_table(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* 
     a.rec = d_rec + q0;
     a.n = (int)cnt; a.base = base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax;
     a.m = (int)fm->m; a.W = (int)fm->W; a.H = (int)fm->H; a.tx = fm->tx; a.ty = fm->ty;
-    a.margin = margin; a.width = width; a.height = height;
+    a.margin = (int)c.par.margin; a.width = c.width; a.height = c.height;
     a.lines = (CoverageLine*)(d + L.o_lines); a.poses = (CovPose*)(d + L.o_tab); a.strips = (int*)(d + L.o_strips);
     a.counts = d_cnt + 2 * q0;
-    hipLaunchKernelGGL(k_matches_table, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_matches_table, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, c.st, a);
     FDCM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_strip_scan, dim3(1), dim3(1024), 0, st, (const int*)a.strips, (int)cnt, (long long*)(d + L.o_item),
+    hipLaunchKernelGGL(k_strip_scan, dim3(1), dim3(1024), 0, c.st, (const int*)a.strips, (int)cnt, (long long*)(d + L.o_item),
                        (long long*)(d + L.o_tot));
     FDCM_HIP(hipGetLastError());
     long long tot[2] = {0, 0};
-    FDCM_HIP(hipMemcpyAsync(tot, d + L.o_tot, sizeof tot, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipStreamSynchronize(st));
-    *items = tot[0];
-    *most = tot[1];
+    FDCM_HIP(hipMemcpyAsync(tot, d + L.o_tot, sizeof tot, hipMemcpyDeviceToHost, c.st));
+    FDCM_HIP(hipStreamSynchronize(c.st));
+    return DevTable{a.lines, a.poses, (const long long*)(d + L.o_item), (int)cnt, tot[0], tot[1]};
 }
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------- pose lists
+// The arguments are checked (fdcm_capi.cpp).  One prepare_pairs for the distinct pairs of the list (n <= 2^20), one upload of
+// lines, poses and item offsets (and a host caller's labels), the counters zeroed and the residual copied on the stream, then
+// the launches and the counts' way down.
+void run_scene_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                        const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                        const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual) {
+    CovCall c(fm, labels, width, height, on_device, bx, by, params);
+    HostTable T;
+    if (!c.nothing(n, t)) {  // (else the residual is the labels and the counts stay unwritten)
+        T.make(fm, width, height, t, rot, poses, n, params.margin);
+        for (int64_t q = 0; q < n; ++q) counts[2 * q] = counts[2 * q + 1] = T.adm[q] ? 0 : -1;
+    }
+    if (T.tab.empty()) return c.copy_labels(residual);
+    const size_t o_lab = T.end + al256(T.tab.size() * 2 * sizeof(int32_t)), o_res = o_lab + c.labels_bytes();
+    c.reserve(o_res + c.residual_bytes(residual), T.end);
+    c.labels(o_lab);
+    const DevTable D = upload_table(c, T);
+    int* d_cnt = (int*)(c.d + T.end);
+    uint8_t* d_res = c.residual_plane(residual, o_res);
+    launch_coverage(c.st, D.args(c), D.items, d_cnt, d_res);
+    counts_down(c, d_cnt, T.tab.size(), T.pose_of.data(), counts, residual, d_res);
+}
+
+// The arguments are checked (fdcm_capi.cpp).  run_scene_coverage's table, then the selection on it.
+void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
+                      const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
+                      const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
+                      int64_t* n_out, uint8_t* residual) {
+    CovCall c(fm, labels, width, height, on_device, bx, by, params);
+    *n_out = 0;
+    HostTable T;
+    if (!c.nothing(n, t)) T.make(fm, width, height, t, rot, poses, n, params.margin);
+    if (T.tab.empty()) return c.copy_labels(residual);  // nothing explains a pixel: nothing is accepted
+    const SelLayout S(T.end, T.tab.size(), (size_t)sel.max_selected);
+    const size_t o_lab = S.end, o_plane = o_lab + c.labels_bytes();
+    c.reserve(o_plane + c.claim_bytes(residual), std::max(T.end, S.down()));
+    c.labels(o_lab);
+    const DevTable D = upload_table(c, T);
+    select_stage(c, D, S, sel, residual, o_plane, T.pose_of.data(), selected, counts, n_out);
+}
+
+// ---------------------------------------------------------------------------------------------- match lists
 // Scene coverage of match records (include/fdcm.h, "Match lists: scene coverage and selection"): the arguments are checked
 // (fdcm_capi.cpp).  The list is walked in parts of at most kCovPartBytes of table (FDCM_COVERAGE_PART: of that many records):
 // per part the table pass, the scan, one download of the number of items, and k_scene_coverage on it; the counts are per
 // record and the residual is an OR, so parts compose.  Only host records and the host's bins go up; counts and residual come down.
 void run_matches_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
-                          const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
-                          const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual) {
-    const size_t npix = (size_t)width * (size_t)height;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    FDCM_HIP(hipSetDevice(fm->device));
-    ensure_stream(fm);
-    hipStream_t st = fm->stream;
-    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return copy_labels(labels, npix, on_device, residual, st);
-    const size_t N = (size_t)n, Lmax = (size_t)t->max_lines;
+                          const fdcm_templates* t, const MatchList& m, const fdcm_coverage_params& params, int32_t* counts,
+                          uint8_t* residual) {
+    CovCall c(fm, labels, width, height, on_device, bx, by, params);
+    if (c.nothing(m.n, t)) return c.copy_labels(residual);
+    const size_t N = (size_t)m.n;
     std::vector<unsigned short> bins;
-    matches_host_bins(fm, t, matches, n, matches_on_device, base, bins);
-    size_t pn = std::max<size_t>(1, std::min(N, kCovPartBytes / table_record_bytes(t, !bins.empty())));
-    if (test_switches().coverage_part > 0) pn = std::min(pn, (size_t)test_switches().coverage_part);
-    // device: records (host callers) | the part's table | counters | labels (host callers) | residual (host callers)
-    const TableLayout L(matches_on_device ? 0 : al256(N * sizeof(fdcm_match)), pn, Lmax, !bins.empty());
-    const size_t o_cnt = L.end, o_lab = o_cnt + al256(N * 2 * sizeof(int32_t)), o_res = o_lab + (on_device ? 0 : al256(npix)),
-                 total = o_res + (on_device || !residual ? 0 : al256(npix));
-    // staging: records (host callers) | the part's bins; then the counters
-    const size_t s_bins = matches_on_device ? 0 : al256(N * sizeof(fdcm_match));
-    fm->coverage.reserve(total);
-    fm->coverage_stage.reserve(std::max(s_bins + al256(bins.empty() ? 0 : pn * Lmax * 2), N * 2 * sizeof(int32_t)));
-    poison_coverage(fm);
-    char* d = (char*)fm->coverage.p;
-    char* h = (char*)fm->coverage_stage.p;
-    const uint8_t* d_labels = labels;
-    uint8_t* d_res = residual;
-    if (!on_device) {
-        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
-        d_labels = (const uint8_t*)(d + o_lab);
-        d_res = residual ? (uint8_t*)(d + o_res) : nullptr;
-    }
-    const fdcm_match* d_rec = matches;
-    if (!matches_on_device) {
-        std::memcpy(h, matches, N * sizeof(fdcm_match));
-        FDCM_HIP(hipMemcpyAsync(d, h, N * sizeof(fdcm_match), hipMemcpyHostToDevice, st));
-        d_rec = (const fdcm_match*)d;
-    }
-    if (d_res) FDCM_HIP(hipMemcpyAsync(d_res, d_labels, npix, hipMemcpyDeviceToDevice, st));
-    int* d_cnt = (int*)(d + o_cnt);
+    matches_host_bins(fm, t, m, bins);
+    const size_t pn = part_records(N, table_record_bytes(t, !bins.empty()));
+    const size_t s_bins = c.records_bytes(m);  // (the staging: host records | the part's bins; then the counters)
+    const TableLayout L(s_bins, pn, (size_t)t->max_lines, !bins.empty());
+    const size_t o_cnt = L.end, o_lab = o_cnt + al256(N * 2 * sizeof(int32_t)), o_res = o_lab + c.labels_bytes();
+    c.reserve(o_res + c.residual_bytes(residual), std::max(s_bins + L.bins_bytes(), N * 2 * sizeof(int32_t)));
+    c.labels(o_lab);
+    const fdcm_match* d_rec = c.records(m);
+    uint8_t* d_res = c.residual_plane(residual, o_res);
+    int* d_cnt = (int*)(c.d + o_cnt);
     for (size_t q0 = 0; q0 < N; q0 += pn) {
         const size_t cnt = std::min(pn, N - q0);
-        long long items = 0, most = 0;
-        make_table(fm, t, d_rec, q0, cnt, base, (int)params.margin, width, height, bins, d, h + s_bins, L, d_cnt, &items, &most);
-        for (long long ib = 0; ib < items; ib += kCovMaxGrid) {
-            const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - ib);
-            hipLaunchKernelGGL(k_scene_coverage, dim3(grid), dim3(kCovThreads), 0, st, d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by,
-                               (int)params.radius, (int)params.bin_tolerance, (const CoverageLine*)(d + L.o_lines),
-                               (const CovPose*)(d + L.o_tab), (const long long*)(d + L.o_item), (int)cnt, ib, d_cnt + 2 * q0, d_res);
-            FDCM_HIP(hipGetLastError());
-        }
+        const DevTable D = make_table(c, t, d_rec, q0, cnt, m.base, bins, c.h + s_bins, L, d_cnt);
+        launch_coverage(c.st, D.args(c), D.items, d_cnt + 2 * q0, d_res);
     }
-    FDCM_HIP(hipMemcpyAsync(h, d_cnt, N * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));  // (the staging is free: every part has waited)
-    if (!on_device && residual) FDCM_HIP(hipMemcpyAsync(residual, d_res, npix, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipStreamSynchronize(st));
-    std::memcpy(counts, h, N * 2 * sizeof(int32_t));
+    counts_down(c, d_cnt, N, nullptr, counts, residual, d_res);  // (the staging is free: every part has waited)
 }
 
 // Scene selection of match records: the arguments are checked (fdcm_capi.cpp), n <= 2^16.  The table is whole, every record an
 // entry: a record that is not admissible holds (-1, -1) and one without a window (0, 0), so neither is in S_0, and the indices
-// the rounds accept are the list's own.  Then run_scene_select's rounds.
+// the rounds accept are the list's own.  Then run_scene_select's selection.
 void run_matches_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
-                        const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
-                        const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
-                        int64_t* n_out, uint8_t* residual) {
-    const size_t npix = (size_t)width * (size_t)height;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    FDCM_HIP(hipSetDevice(fm->device));
-    ensure_stream(fm);
-    hipStream_t st = fm->stream;
+                        const fdcm_templates* t, const MatchList& m, const fdcm_coverage_params& params, const fdcm_select_params& sel,
+                        int32_t* selected, int32_t* counts, int64_t* n_out, uint8_t* residual) {
+    CovCall c(fm, labels, width, height, on_device, bx, by, params);
     *n_out = 0;
-    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return copy_labels(labels, npix, on_device, residual, st);
-    const size_t N = (size_t)n, Lmax = (size_t)t->max_lines, ms = (size_t)sel.max_selected;
+    if (c.nothing(m.n, t)) return c.copy_labels(residual);
+    const size_t N = (size_t)m.n;
     if (N * table_record_bytes(t, orientation_bins_on_host()) > ((size_t)2 << 30))  // (FDCM_EINVAL, before any GPU work)
         throw std::string("the selection's table, n records of max_lines lines each, would exceed 2 GB: cut the list with "
                           "fdcm_matches_detect first");
     std::vector<unsigned short> bins;
-    matches_host_bins(fm, t, matches, n, matches_on_device, base, bins);
-    // device: records (host callers) | the table | counters, sel, sel_new (what comes down) | fresh | cur | alive | labels (host
-    // callers) | claim plane (unless the caller's residual is on the device)
-    const TableLayout L(matches_on_device ? 0 : al256(N * sizeof(fdcm_match)), N, Lmax, !bins.empty());
-    const size_t o_cnt = L.end, o_sel = o_cnt + al256(N * 2 * sizeof(int32_t)), o_new = o_sel + al256(ms * sizeof(int32_t)),
-                 o_fresh = o_new + al256(ms * sizeof(int32_t)), o_cur = o_fresh + al256(N * sizeof(int32_t)),
-                 o_alive = o_cur + al256(N * sizeof(int32_t)), o_lab = o_alive + al256(N), o_plane = o_lab + (on_device ? 0 : al256(npix)),
-                 total = o_plane + (on_device && residual ? 0 : al256(npix));
-    const size_t s_bins = matches_on_device ? 0 : al256(N * sizeof(fdcm_match));
-    fm->coverage.reserve(total);
-    fm->coverage_stage.reserve(std::max(s_bins + al256(bins.empty() ? 0 : N * Lmax * 2), o_fresh - o_cnt));
-    poison_coverage(fm);
-    char* d = (char*)fm->coverage.p;
-    char* h = (char*)fm->coverage_stage.p;
-    const uint8_t* d_labels = labels;
-    if (!on_device) {
-        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
-        d_labels = (const uint8_t*)(d + o_lab);
-    }
-    uint8_t* plane = on_device && residual ? residual : (uint8_t*)(d + o_plane);
-    const fdcm_match* d_rec = matches;
-    if (!matches_on_device) {
-        std::memcpy(h, matches, N * sizeof(fdcm_match));
-        FDCM_HIP(hipMemcpyAsync(d, h, N * sizeof(fdcm_match), hipMemcpyHostToDevice, st));
-        d_rec = (const fdcm_match*)d;
-    }
-    FDCM_HIP(hipMemsetAsync(d + o_sel, 0x7f, ms * sizeof(int32_t), st));  // kSelNone
-    FDCM_HIP(hipMemsetAsync(d + o_fresh, 0, N * sizeof(int32_t), st));
-    FDCM_HIP(hipMemcpyAsync(plane, d_labels, npix, hipMemcpyDeviceToDevice, st));
-    int* d_cnt = (int*)(d + o_cnt);
-    long long items = 0, most = 0;
-    make_table(fm, t, d_rec, 0, N, base, (int)params.margin, width, height, bins, d, h + s_bins, L, d_cnt, &items, &most);
-    if (items > 0) {  // (else nothing explains a pixel: nothing is accepted, and the plane is the labels)
-        const SelArgs a{d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by, (int)params.radius, (int)params.bin_tolerance,
-                        (const CoverageLine*)(d + L.o_lines), (const CovPose*)(d + L.o_tab), (const long long*)(d + L.o_item), (int)N};
-        select_rounds(st, a, items, most, ms, sel, d_cnt, (int*)(d + o_sel), (int*)(d + o_new), (int*)(d + o_fresh), (int*)(d + o_cur),
-                      (uint8_t*)(d + o_alive), plane);
-    }
-    FDCM_HIP(hipMemcpyAsync(h, d + o_cnt, o_fresh - o_cnt, hipMemcpyDeviceToHost, st));  // (the staging is free again)
-    if (residual && !on_device) FDCM_HIP(hipMemcpyAsync(residual, plane, npix, hipMemcpyDeviceToHost, st));
-    FDCM_HIP(hipStreamSynchronize(st));
-    const int32_t* h_cnt = (const int32_t*)h;
-    const int32_t* h_sel = (const int32_t*)(h + (o_sel - o_cnt));
-    const int32_t* h_new = (const int32_t*)(h + (o_new - o_cnt));
-    size_t k = 0;
-    for (; k < ms && h_sel[k] < (int32_t)N; ++k) {
-        const int32_t i = h_sel[k];
-        selected[k] = i;
-        counts[3 * k] = h_cnt[2 * i];
-        counts[3 * k + 1] = h_cnt[2 * i + 1];
-        counts[3 * k + 2] = h_new[k];
-    }
-    *n_out = (int64_t)k;
+    matches_host_bins(fm, t, m, bins);
+    const size_t s_bins = c.records_bytes(m);
+    const TableLayout L(s_bins, N, (size_t)t->max_lines, !bins.empty());
+    const SelLayout S(L.end, N, (size_t)sel.max_selected);
+    const size_t o_lab = S.end, o_plane = o_lab + c.labels_bytes();
+    c.reserve(o_plane + c.claim_bytes(residual), std::max(s_bins + L.bins_bytes(), S.down()));
+    c.labels(o_lab);
+    const DevTable D = make_table(c, t, c.records(m), 0, N, m.base, bins, c.h + s_bins, L, (int*)(c.d + S.o_cnt));
+    select_stage(c, D, S, sel, residual, o_plane, nullptr, selected, counts, n_out);
 }
 
 // The pose fit of match records (include/fdcm.h, "Match lists: pose fit"): the arguments are checked (fdcm_capi.cpp).  The
@@ -1057,69 +1060,45 @@ void run_matches_select(fdcm_featuremap* fm, const uint8_t* labels, int width, i
 // k_fit_moments, k_fit_step.  Where the host's libm makes the bins, every pass downloads the part's records for them
 // (matches_host_bins).  Records, info and rms come down once, at the end.
 void run_matches_fit(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
-                     const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
-                     const fdcm_coverage_params& params, const fdcm_fit_params& fit, fdcm_match* out, bool out_on_device, int32_t* info_out,
-                     float* rms_out) {
-    const size_t npix = (size_t)width * (size_t)height;
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    FDCM_HIP(hipSetDevice(fm->device));
-    ensure_stream(fm);
-    hipStream_t st = fm->stream;
-    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;  // nothing is written, as the coverage call's counts
-    const size_t N = (size_t)n, Lmax = (size_t)t->max_lines;
+                     const fdcm_templates* t, const MatchList& m, const fdcm_coverage_params& params, const fdcm_fit_params& fit,
+                     fdcm_match* out, bool out_on_device, int32_t* info_out, float* rms_out) {
+    CovCall c(fm, labels, width, height, on_device, bx, by, params);
+    if (c.nothing(m.n, t)) return;  // nothing is written, as the coverage call's counts
+    const size_t N = (size_t)m.n, Lmax = (size_t)t->max_lines;
     const bool host_bins = orientation_bins_on_host();
-    const size_t per_record = table_record_bytes(t, host_bins) + Lmax * 6 * sizeof(long long) + 2 * sizeof(int32_t);
-    size_t pn = std::max<size_t>(1, std::min(N, kCovPartBytes / per_record));
-    if (test_switches().coverage_part > 0) pn = std::min(pn, (size_t)test_switches().coverage_part);
-    // device: records | replaced transforms | info | rms (what comes down) | the part's table | its counters | its moments |
-    // labels (host callers)
+    const size_t pn = part_records(N, table_record_bytes(t, host_bins) + Lmax * 6 * sizeof(long long) + 2 * sizeof(int32_t));
+    // records | replaced transforms | info | rms (what comes down), then the part's table, counters and moments
     const size_t o_prev = al256(N * sizeof(fdcm_match)), o_info = o_prev + al256(N * 6 * sizeof(float)),
                  o_rms = o_info + al256(N * 4 * sizeof(int32_t));
     const TableLayout L(o_rms + al256(N * 2 * sizeof(float)), pn, Lmax, host_bins);
-    const size_t o_cnt = L.end, o_mom = o_cnt + al256(pn * 2 * sizeof(int32_t)), o_lab = o_mom + al256(pn * Lmax * 6 * sizeof(long long)),
-                 total = o_lab + (on_device ? 0 : al256(npix));
-    // staging: host records up, then the results down; behind them the part's bins
-    const size_t s_bins = L.o_bins;  // (the results' extent)
-    fm->coverage.reserve(total);
-    fm->coverage_stage.reserve(s_bins + al256(host_bins ? pn * Lmax * 2 : 0));
-    poison_coverage(fm);
-    char* d = (char*)fm->coverage.p;
-    char* h = (char*)fm->coverage_stage.p;
-    const uint8_t* d_labels = labels;
-    if (!on_device) {
-        FDCM_HIP(hipMemcpyAsync(d + o_lab, labels, npix, hipMemcpyHostToDevice, st));
-        d_labels = (const uint8_t*)(d + o_lab);
-    }
+    const size_t o_cnt = L.end, o_mom = o_cnt + al256(pn * 2 * sizeof(int32_t)), o_lab = o_mom + al256(pn * Lmax * 6 * sizeof(long long));
+    const size_t s_bins = L.o_bins;  // (the staging: host records up, then the results down; behind them the part's bins)
+    c.reserve(o_lab + c.labels_bytes(), s_bins + L.bins_bytes());
+    c.labels(o_lab);
+    char *d = c.d, *h = c.h;
+    hipStream_t st = c.st;
     fdcm_match* d_cur = (fdcm_match*)d;
-    if (matches_on_device) {
-        FDCM_HIP(hipMemcpyAsync(d_cur, matches, N * sizeof(fdcm_match), hipMemcpyDeviceToDevice, st));
-    } else {
-        std::memcpy(h, matches, N * sizeof(fdcm_match));
-        FDCM_HIP(hipMemcpyAsync(d_cur, h, N * sizeof(fdcm_match), hipMemcpyHostToDevice, st));
-    }
+    if (m.on_device) FDCM_HIP(hipMemcpyAsync(d_cur, m.rec, N * sizeof(fdcm_match), hipMemcpyDeviceToDevice, st));
+    else c.records(m);
     FDCM_HIP(hipMemsetAsync(d + o_info, 0x7f, N * 4 * sizeof(int32_t), st));  // kFitActive
     std::vector<unsigned short> bins;
     for (size_t q0 = 0; q0 < N; q0 += pn) {
         const size_t cnt = std::min(pn, N - q0);
         FitArgs a{};
-        a.lines = (const CoverageLine*)(d + L.o_lines); a.poses = (const CovPose*)(d + L.o_tab); a.counts = (const int*)(d + o_cnt);
-        a.mom = (const long long*)(d + o_mom);
+        a.counts = (const int*)(d + o_cnt); a.mom = (const long long*)(d + o_mom);
         a.cur = d_cur + q0; a.prev = (float*)(d + o_prev) + 6 * q0; a.info = (int*)(d + o_info) + 4 * q0; a.rms = (float*)(d + o_rms) + 2 * q0;
         a.n = (int)cnt; a.Lmax = (int)Lmax; a.par = fit; a.tx = fm->tx; a.ty = fm->ty; a.bx = bx; a.by = by;
         for (int pass = 0; pass <= fit.iterations; ++pass) {
-            long long items = 0, most = 0;
-            matches_host_bins(fm, t, d_cur + q0, (int64_t)cnt, true, base, bins);  // (empty unless the host's libm makes them)
-            make_table(fm, t, d_cur + q0, 0, cnt, base, (int)params.margin, width, height, bins, d, h + s_bins, L, (int*)(d + o_cnt), &items,
-                       &most);
+            matches_host_bins(fm, t, MatchList{d_cur + q0, (int64_t)cnt, true, m.base}, bins);  // (empty unless the host's libm makes them)
+            const DevTable D = make_table(c, t, d_cur + q0, 0, cnt, m.base, bins, h + s_bins, L, (int*)(d + o_cnt));
+            const SelArgs s = D.args(c);
             if (Lmax) FDCM_HIP(hipMemsetAsync(d + o_mom, 0, cnt * Lmax * 6 * sizeof(long long), st));
-            for (long long ib = 0; ib < items; ib += kCovMaxGrid) {
-                const unsigned grid = (unsigned)std::min(kCovMaxGrid, items - ib);
-                hipLaunchKernelGGL(k_fit_moments, dim3(grid), dim3(kCovThreads), 0, st, d_labels, width, height, (int)fm->m, fm->tx, fm->ty, bx, by,
-                                   (int)params.radius, (int)params.bin_tolerance, a.lines, a.poses, (const long long*)(d + L.o_item), (int)cnt, ib,
-                                   (const int*)a.info, (unsigned long long*)(d + o_mom), (int)Lmax);
-                FDCM_HIP(hipGetLastError());
-            }
-            a.pass = pass;
+            for_items(D.items, [&](unsigned grid, long long base) {
+                hipLaunchKernelGGL(k_fit_moments, dim3(grid), dim3(kCovThreads), 0, st, s.labels, s.width, s.height, s.m, s.tx, s.ty, s.bx, s.by,
+                                   s.radius, s.tol, s.lines, s.poses, s.item0, s.n_poses, base, (const int*)a.info,
+                                   (unsigned long long*)(d + o_mom), (int)Lmax);
+            });
+            a.lines = D.lines; a.poses = D.poses; a.pass = pass;
             hipLaunchKernelGGL(k_fit_step, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, a);
             FDCM_HIP(hipGetLastError());
         }

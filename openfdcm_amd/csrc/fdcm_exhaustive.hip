@@ -3533,17 +3533,43 @@ __global__ void __launch_bounds__(256) k_matches_shapes(const ShapesArgs a) {
 }
 
 // P(r) of a valid record on the host: the kernel's arithmetic (the Makefile's -ffp-contract=off keeps it unfused here too).
-void pose_lines(const fdcm_templates* t, int64_t tmpl, const float* M, std::vector<float>& out) {
+// Q: a rotation in front of M, "Rotations"' arithmetic (the refinement's delta), or null.
+void pose_lines(const fdcm_templates* t, int64_t tmpl, const float* M, std::vector<float>& out, const RotM* Q = nullptr) {
     const int64_t l0 = t->offsets[(size_t)tmpl], nl = t->offsets[(size_t)tmpl + 1] - l0;
     out.resize((size_t)nl * 4);
     for (int64_t i = 0; i < nl; ++i) {
         const float* p = &t->lines[(size_t)(l0 + i) * 4];
         float* o = &out[(size_t)i * 4];
         for (int c = 0; c < 2; ++c) {
-            o[2 * c] = (M[0] * p[2 * c] + M[1] * p[2 * c + 1]) + M[2];
-            o[2 * c + 1] = (M[3] * p[2 * c] + M[4] * p[2 * c + 1]) + M[5];
+            float x = p[2 * c], y = p[2 * c + 1];
+            if (Q) {
+                const float qx = (Q->c * x + Q->ns * y) + Q->mx, qy = (Q->s * x + Q->c * y) + Q->my;
+                x = qx;
+                y = qy;
+            }
+            o[2 * c] = (M[0] * x + M[1] * y) + M[2];
+            o[2 * c + 1] = (M[3] * x + M[4] * y) + M[5];
         }
     }
+}
+
+// The bins of posed lines from the host libm, one per line.
+void posed_bins(const fdcm_featuremap* fm, const std::vector<float>& posed, unsigned short* out) {
+    for (size_t i = 0; i < posed.size() / 4; ++i) {
+        const float* p = &posed[4 * i];
+        const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
+        out[i] = (unsigned short)closest_orientation(fm->keys.data(), (int)fm->m, angle);
+    }
+}
+
+// P(r) and F(r) of record r; false, with F empty, for a record that is not valid.
+bool pose_record(const fdcm_templates* t, const fdcm_match& r, int32_t base, int margin, std::vector<float>& posed, Foot& F) {
+    const int64_t tm = (int64_t)r.tmpl_idx - base;
+    F = Foot{0, 0, -1, -1};
+    if (tm < 0 || tm >= t->T) return false;
+    pose_lines(t, tm, r.transform, posed);
+    F = footprint(posed.data(), 4, (int64_t)(posed.size() / 4), margin);
+    return true;
 }
 
 }  // namespace
@@ -3552,12 +3578,8 @@ void pose_lines(const fdcm_templates* t, int64_t tmpl, const float* M, std::vect
 void matches_footprints(const fdcm_templates* t, const fdcm_match* matches, int64_t n, int32_t base, int margin, int32_t* boxes_out) {
     std::vector<float> posed;
     for (int64_t j = 0; j < n; ++j) {
-        const int64_t tm = (int64_t)matches[j].tmpl_idx - base;
-        Foot F{0, 0, -1, -1};
-        if (tm >= 0 && tm < t->T) {
-            pose_lines(t, tm, matches[j].transform, posed);
-            F = footprint(posed.data(), 4, (int64_t)(posed.size() / 4), margin);
-        }
+        Foot F;
+        pose_record(t, matches[j], base, margin, posed, F);
         std::memcpy(boxes_out + 4 * j, &F, sizeof F);
     }
 }
@@ -3569,12 +3591,8 @@ void matches_footprint_spans(const fdcm_templates* t, const fdcm_match* matches,
     std::vector<HullPt> h;
     row_offsets[0] = 0;
     for (int64_t j = 0; j < n; ++j) {
-        const int64_t tm = (int64_t)matches[j].tmpl_idx - base;
-        Foot F{0, 0, -1, -1};
-        if (tm >= 0 && tm < t->T) {
-            pose_lines(t, tm, matches[j].transform, posed);
-            F = footprint(posed.data(), 4, (int64_t)(posed.size() / 4), margin);
-        }
+        Foot F;
+        pose_record(t, matches[j], base, margin, posed, F);
         row_offsets[j + 1] = row_offsets[j] + foot_rows(F);
         if (areas) areas[j] = 0;
         if ((!areas && !spans) || foot_rows(F) == 0) continue;
@@ -3586,82 +3604,73 @@ void matches_footprint_spans(const fdcm_templates* t, const fdcm_match* matches,
 
 // Host-libm bins (fdcm_orientation_bins_mode() == 1; empty otherwise): the bins of every posed line as [record][max_lines], on
 // the host, from host records; device records cost one download on the handle's stream.
-void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
-                       std::vector<unsigned short>& bins) {
+void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const MatchList& m, std::vector<unsigned short>& bins) {
     bins.clear();
     if (!orientation_bins_on_host()) return;
     if (fm->m > 65535) throw std::string("host-side orientation bins need depth <= 65535");
-    const size_t N = (size_t)n, Lmax = (size_t)t->max_lines;
+    const size_t N = (size_t)m.n, Lmax = (size_t)t->max_lines;
     std::vector<fdcm_match> fetched;
-    const fdcm_match* h = matches;
-    if (on_device) {
+    const fdcm_match* h = m.rec;
+    if (m.on_device) {
         fetched.resize(N);
-        FDCM_HIP(hipMemcpyAsync(fetched.data(), matches, N * sizeof(fdcm_match), hipMemcpyDeviceToHost, fm->stream));
+        FDCM_HIP(hipMemcpyAsync(fetched.data(), m.rec, N * sizeof(fdcm_match), hipMemcpyDeviceToHost, fm->stream));
         FDCM_HIP(hipStreamSynchronize(fm->stream));
         h = fetched.data();
     }
     bins.assign(std::max<size_t>(1, N * Lmax), 0);
     std::vector<float> posed;
     for (size_t j = 0; j < N; ++j) {
-        const int64_t tm = (int64_t)h[j].tmpl_idx - base;
+        const int64_t tm = (int64_t)h[j].tmpl_idx - m.base;
         if (tm < 0 || tm >= t->T) continue;
         pose_lines(t, tm, h[j].transform, posed);
-        for (size_t i = 0; i < posed.size() / 4; ++i) {
-            const float* p = &posed[4 * i];
-            const float angle = std::atan((p[3] - p[1]) / (p[2] - p[0]));  // getAngle, math.h:295-299
-            bins[j * Lmax + i] = (unsigned short)closest_orientation(fm->keys.data(), (int)fm->m, angle);
-        }
+        posed_bins(fm, posed, &bins[j * Lmax]);
     }
 }
 
-// Both device calls on match lists (include/fdcm.h, "Match lists"): the arguments are checked (fdcm_capi.cpp).  det null: the
-// verify call, whose outputs are scores_out, fractions_out and costs_out (each may be null).  Else the detect call: the
-// rounds on the verify pass's keys and boxes, then the gather.  One reserve_eval lays out the whole call: the upload (host
-// records, caps, denominators, needs, totals, host bins), the list's arrays, the result list and the rounds' partials.
-// objects_in (fdcm_matches_detect_objects) and shapes_out (fdcm_matches_shapes): fdcm_internal.h; with neither, nothing of
-// "Match lists: objects and hull shapes" is laid out, launched or read.
-void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
-                 const MatchesDetect* det, float* scores_out, float* fractions_out, float* costs_out, fdcm_match** out, int64_t* n_out,
-                 int32_t* indices_out, int32_t* boxes_out, float* matched_out, const MatchesObjectsIn* objects_in,
-                 const MatchesShapesOut* shapes_out) {
-    if (n_out) *n_out = 0;
-    if (shapes_out) std::fill_n(shapes_out->row_offsets, n + 1, (int64_t)0);
-    if (shapes_out && shapes_out->areas) std::fill_n(shapes_out->areas, n, (int64_t)0);
-    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
-    // The calls of "Match lists: objects and hull shapes".  The shapes call is the pass with one object and no threshold, whose
-    // table of objects says which records are valid and admissible and have lines.
-    const std::vector<int32_t> one_object(shapes_out ? (size_t)t->T : 0, 0);
-    const float no_limit = f_inf();
-    const MatchesObjectsIn all{one_object.data(), 1, &no_limit, nullptr, 1000};
-    const MatchesObjectsIn* const ob = shapes_out ? &all : objects_in;
-    const bool hull = shapes_out || (ob && t->footprint == FDCM_FOOTPRINT_HULL);
-    std::lock_guard<std::mutex> turn(fm->seam_mutex);
-    begin(fm);
-    hipStream_t st = fm->stream;
-    const size_t N = (size_t)n, T = (size_t)t->T, Lmax = (size_t)t->max_lines;
-    const bool flat = test_switches().matched_flat;
-    const size_t SL = ivol_slice_floats(fm->W, fm->H);
-    const bool buf32 = !flat && (size_t)fm->m * SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
+// ---- the device calls on match lists (include/fdcm.h, "Match lists"): run_matches and its stages
+namespace {
+
+// Where the stages left what: offsets into d = search.eval.  Everything before o_score is written by the one upload.
+struct MatchesRun {
+    const MatchesObjectsIn* ob = nullptr;  // the objects of the pass: the caller's, or the shapes call's one object; null: none
+    bool hull = false;                     // the records' hull shapes are built
+    size_t N = 0, Lmax = 0;
+    char* d = nullptr;
+    size_t o_ms = 0, o_tobj = 0, o_score = 0, o_frac = 0, o_costs = 0, o_best = 0, o_pk = 0, o_obj = 0, o_shape = 0, o_sums = 0;
+    MatchesArgs a{};  // the verify pass's: the records, and the scores, keys and boxes it leaves
+    ShapesArgs sa{};  // the hull shapes', with the span table
+};
+
+// Stage 1.  One reserve_eval lays out the whole call: the upload (host records, caps, denominators, needs, totals, the
+// objects' tables, host bins), the list's arrays, the result list, the rounds' partials, and with objects or shapes the
+// records' objects, shapes and the scan's sums.  One copy takes the upload to the device.
+void matches_upload(fdcm_featuremap* fm, const fdcm_templates* t, const MatchesIn& in, MatchesRun& R) {
+    const MatchList& m = in.list;
+    const MatchesDetect* det = in.det;
+    const MatchesObjectsIn* ob = R.ob;
+    const size_t N = R.N = (size_t)m.n, T = (size_t)t->T, Lmax = R.Lmax = (size_t)t->max_lines;
     const bool gated = ob ? ob->min_matched && std::any_of(ob->min_matched, ob->min_matched + ob->G, [](float v) { return v > 0.f; })
                           : det && det->min_matched > 0.f;
     const std::vector<float> den = best_denominators(t, det ? det->penalty : -1, det ? det->tau : 1.f);
     std::vector<float> totals(T);
     templates_matched_totals(t, totals.data());
     std::vector<unsigned short> bins;
-    matches_host_bins(fm, t, matches, n, on_device, base, bins);
+    matches_host_bins(fm, t, m, bins);
     const int max_det = det ? det->max_detections : 0;
-    const size_t o_caps = on_device ? 0 : al256(N * sizeof(fdcm_match)), o_den = o_caps + (t->capped ? al256((size_t)t->n_lines * 4) : 0),
-                 o_need = o_den + al256(T * 4), o_tl = o_need + (gated ? al256(T * 4) : 0), o_ms = o_tl + al256(T * 4),
-                 o_tobj = o_ms + (ob ? al256(T * 4) : 0), o_bins = o_tobj + (ob ? al256(T * 4) : 0),
-                 o_score = o_bins + (bins.empty() ? 0 : al256(bins.size() * 2)), o_frac = o_score + al256(N * 4), o_q = o_frac + al256(N * 4),
-                 o_keys = o_q + al256(N * 4), o_box = o_keys + al256(N * 8), o_costs = o_box + al256(N * 16),
-                 o_best = o_costs + (costs_out ? al256(N * Lmax * 4) : 0), o_pk = o_best + al256((size_t)max_det * 8),
-                 o_obj = o_pk + 2 * kNmsWorkgroups * 8, o_shape = o_obj + (ob ? al256(N * 4) : 0),
-                 o_sums = o_shape + (hull ? al256(N * sizeof(HullShape)) : 0), total = o_sums + (hull ? al256(((N + 255) / 256 + 1) * 8) : 0);
+    const bool costs = in.verify.costs != nullptr;
+    const size_t o_caps = m.on_device ? 0 : al256(N * sizeof(fdcm_match)), o_den = o_caps + (t->capped ? al256((size_t)t->n_lines * 4) : 0),
+                 o_need = o_den + al256(T * 4), o_tl = o_need + (gated ? al256(T * 4) : 0), o_ms = R.o_ms = o_tl + al256(T * 4),
+                 o_tobj = R.o_tobj = o_ms + (ob ? al256(T * 4) : 0), o_bins = o_tobj + (ob ? al256(T * 4) : 0),
+                 o_score = R.o_score = o_bins + (bins.empty() ? 0 : al256(bins.size() * 2)), o_frac = R.o_frac = o_score + al256(N * 4),
+                 o_q = o_frac + al256(N * 4), o_keys = o_q + al256(N * 4), o_box = o_keys + al256(N * 8),
+                 o_costs = R.o_costs = o_box + al256(N * 16), o_best = R.o_best = o_costs + (costs ? al256(N * Lmax * 4) : 0),
+                 o_pk = R.o_pk = o_best + al256((size_t)max_det * 8), o_obj = R.o_obj = o_pk + 2 * kNmsWorkgroups * 8,
+                 o_shape = R.o_shape = o_obj + (ob ? al256(N * 4) : 0), o_sums = R.o_sums = o_shape + (R.hull ? al256(N * sizeof(HullShape)) : 0),
+                 total = o_sums + (R.hull ? al256(((N + 255) / 256 + 1) * 8) : 0);
     reserve_eval(fm, total, o_score);
-    char* d = (char*)fm->search.eval.p;
+    char* d = R.d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
-    if (!on_device) std::memcpy(h, matches, N * sizeof(fdcm_match));
+    if (!m.on_device) std::memcpy(h, m.rec, N * sizeof(fdcm_match));
     if (t->capped) std::memcpy(h + o_caps, t->caps.data(), (size_t)t->n_lines * 4);
     std::memcpy(h + o_den, den.data(), T * 4);
     if (gated && !ob)
@@ -3678,120 +3687,159 @@ void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match*
         }
     std::memcpy(h + o_tl, totals.data(), T * 4);
     if (!bins.empty()) std::memcpy(h + o_bins, bins.data(), bins.size() * 2);
-    FDCM_HIP(hipMemcpyAsync(d, h, o_score, hipMemcpyHostToDevice, st));
-    MatchesArgs a{};
-    a.vol = fm->vol.as<float>(); a.SL = SL; a.m = (int)fm->m; a.W = (int)fm->W; a.H = (int)fm->H; a.tx = fm->tx; a.ty = fm->ty;
-    a.keys = (const float*)((const char*)fm->build.plan.p + fm->off_keys);
+    FDCM_HIP(hipMemcpyAsync(d, h, o_score, hipMemcpyHostToDevice, fm->stream));
+    MatchesArgs& a = R.a;
+    a.vol = fm->vol.as<float>(); a.SL = ivol_slice_floats(fm->W, fm->H); a.m = (int)fm->m; a.W = (int)fm->W; a.H = (int)fm->H;
+    a.tx = fm->tx; a.ty = fm->ty; a.keys = (const float*)((const char*)fm->build.plan.p + fm->off_keys);
     a.tlines = t->d_lines.as<float4>(); a.tlen = t->d_lengths.as<float>(); a.toff = t->d_offsets.as<long long>();
     a.caps = t->capped ? (const float*)(d + o_caps) : nullptr;
     a.den = (const float*)(d + o_den);
     a.need = gated ? (const float*)(d + o_need) : nullptr;
     a.tl = (const float*)(d + o_tl);
     a.bins = bins.empty() ? nullptr : (const unsigned short*)(d + o_bins);
-    a.rec = on_device ? matches : (const fdcm_match*)d;
-    a.n = (int)n; a.base = base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax;
-    a.margin = det ? det->margin : shapes_out ? shapes_out->margin : 0; a.rescore = det ? det->rescore : 0;
+    a.rec = m.on_device ? m.rec : (const fdcm_match*)d;
+    a.n = (int)m.n; a.base = m.base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax;
+    a.margin = det ? det->margin : in.shapes ? in.shapes->margin : 0; a.rescore = det ? det->rescore : 0;
     a.max_score = det ? det->max_score : f_inf();
     a.score = (float*)(d + o_score); a.frac = (float*)(d + o_frac); a.q = (float*)(d + o_q);
-    a.costs = costs_out ? (float*)(d + o_costs) : nullptr;
+    a.costs = costs ? (float*)(d + o_costs) : nullptr;
     a.keys_out = (unsigned long long*)(d + o_keys);
     a.boxes = (int4*)(d + o_box);
+}
+
+// Stage 2.  The verify pass: s, frac, q, the key and the box of every record, with objects the record's object.
+void matches_verify_pass(fdcm_featuremap* fm, const fdcm_templates* t, const MatchesRun& R) {
+    const bool buf32 = !test_switches().matched_flat && (size_t)fm->m * R.a.SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
     auto kern = buf32 ? (t->capped ? k_matches_verify<true, true, false> : k_matches_verify<true, false, false>)
                       : (t->capped ? k_matches_verify<false, true, false> : k_matches_verify<false, false, false>);
     auto kern_ob = buf32 ? (t->capped ? k_matches_verify<true, true, true> : k_matches_verify<true, false, true>)
                          : (t->capped ? k_matches_verify<false, true, true> : k_matches_verify<false, false, true>);
-    const MatchesObjArgs oa{(const float*)(d + o_ms), (const int*)(d + o_tobj), (int*)(d + o_obj)};
-    hipLaunchKernelGGL(ob ? kern_ob : kern, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, a, ob ? oa : MatchesObjArgs{});
+    const MatchesObjArgs oa{(const float*)(R.d + R.o_ms), (const int*)(R.d + R.o_tobj), (int*)(R.d + R.o_obj)};
+    hipLaunchKernelGGL(R.ob ? kern_ob : kern, dim3((unsigned)((R.N + 3) / 4)), dim3(256), 0, fm->stream, R.a, R.ob ? oa : MatchesObjArgs{});
     FDCM_HIP(hipGetLastError());
-    // Hull shapes: the rows of every record that needs a shape by a scan on the device, whose total alone comes to the host,
-    // for the limit and for the size of the span table; then the shapes.  The table is a buffer of its own, so nothing here
-    // moves the workspace the pass has written; under FDCM_POISON it holds the word wherever the kernel does not write.
-    ShapesArgs sa{};
-    if (hull) {
-        sa.tlines = a.tlines; sa.toff = a.toff; sa.rec = a.rec;
-        sa.keys = shapes_out ? nullptr : a.keys_out;
-        sa.obj = (const int*)(d + o_obj);
-        sa.boxes = a.boxes;
-        sa.shapes = (HullShape*)(d + o_shape);
-        sa.sums = (long long*)(d + o_sums);
-        sa.n = a.n; sa.base = base; sa.margin = a.margin;
-        const unsigned nb = (unsigned)((N + 255) / 256);
-        hipLaunchKernelGGL(k_shape_rows<0>, dim3(nb), dim3(256), 0, st, sa);
-        hipLaunchKernelGGL(k_shape_rows<1>, dim3(1), dim3(256), 0, st, sa);
-        hipLaunchKernelGGL(k_shape_rows<2>, dim3(nb), dim3(256), 0, st, sa);
+}
+
+// Stage 3.  Hull shapes: the rows of every record that needs a shape by a scan on the device, whose total alone comes to the
+// host, for the limit and for the size of the span table; then the shapes.  The table is a buffer of its own, so nothing here
+// moves the workspace the pass has written; under FDCM_POISON it holds the word wherever the kernel does not write.
+// Returns the rows of the table.
+long long matches_hull_shapes(fdcm_featuremap* fm, const MatchesIn& in, MatchesRun& R) {
+    hipStream_t st = fm->stream;
+    ShapesArgs& sa = R.sa;
+    sa.tlines = R.a.tlines; sa.toff = R.a.toff; sa.rec = R.a.rec;
+    sa.keys = in.shapes ? nullptr : R.a.keys_out; sa.obj = (const int*)(R.d + R.o_obj); sa.boxes = R.a.boxes;
+    sa.shapes = (HullShape*)(R.d + R.o_shape); sa.sums = (long long*)(R.d + R.o_sums);
+    sa.n = R.a.n; sa.base = R.a.base; sa.margin = R.a.margin;
+    const unsigned nb = (unsigned)((R.N + 255) / 256);
+    hipLaunchKernelGGL(k_shape_rows<0>, dim3(nb), dim3(256), 0, st, sa);
+    hipLaunchKernelGGL(k_shape_rows<1>, dim3(1), dim3(256), 0, st, sa);
+    hipLaunchKernelGGL(k_shape_rows<2>, dim3(nb), dim3(256), 0, st, sa);
+    FDCM_HIP(hipGetLastError());
+    long long rows = 0;
+    FDCM_HIP(hipMemcpyAsync(&rows, sa.sums + nb, 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    if (rows > kHullMaxRows)
+        throw std::string("match lists: the span table of the candidates has more than 2^26 rows: cut the list with max_score or "
+                          "fdcm_topk first");
+    DevBuf& table = fm->search.eval_spans;
+    table.reserve(std::max<size_t>(8, (size_t)rows * 8));
+    poison_fill(table, st, FDCM_FILL_EVAL);  // (counted with the workspace it belongs to)
+    sa.spans = table.as<int2>();
+    if (!in.shapes || in.shapes->areas || in.shapes->spans) {
+        hipLaunchKernelGGL(k_matches_shapes, dim3((unsigned)((R.N + 3) / 4)), dim3(256), 0, st, sa);
         FDCM_HIP(hipGetLastError());
-        long long rows = 0;
-        FDCM_HIP(hipMemcpyAsync(&rows, sa.sums + nb, 8, hipMemcpyDeviceToHost, st));
-        FDCM_HIP(hipStreamSynchronize(st));
-        if (rows > kHullMaxRows)
-            throw std::string("match lists: the span table of the candidates has more than 2^26 rows: cut the list with max_score or "
-                              "fdcm_topk first");
-        if (shapes_out) shapes_out->row_offsets[n] = rows;
-        DevBuf& table = fm->search.eval_spans;
-        table.reserve(std::max<size_t>(8, (size_t)rows * 8));
-        poison_fill(table, st, FDCM_FILL_EVAL);  // (counted with the workspace it belongs to)
-        sa.spans = table.as<int2>();
-        if (!shapes_out || shapes_out->areas || shapes_out->spans) {
-            hipLaunchKernelGGL(k_matches_shapes, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, sa);
-            FDCM_HIP(hipGetLastError());
-        }
     }
-    if (shapes_out) {
-        std::vector<HullShape> shapes(N);
-        FDCM_HIP(hipMemcpyAsync(shapes.data(), sa.shapes, N * sizeof(HullShape), hipMemcpyDeviceToHost, st));
-        if (shapes_out->spans && shapes_out->row_offsets[n])
-            FDCM_HIP(hipMemcpyAsync(shapes_out->spans, sa.spans, (size_t)shapes_out->row_offsets[n] * 8, hipMemcpyDeviceToHost, st));
-        FDCM_HIP(hipStreamSynchronize(st));
-        for (size_t j = 0; j < N; ++j) {
-            shapes_out->row_offsets[j] = shapes[j].row0;
-            if (shapes_out->areas) shapes_out->areas[j] = shapes[j].area;
-        }
-        return;
+    return rows;
+}
+
+// The shapes call's delivery: the rows and areas of every record, and the table.
+void matches_shapes_to_host(fdcm_featuremap* fm, const MatchesShapesOut& out, const MatchesRun& R, long long rows) {
+    hipStream_t st = fm->stream;
+    std::vector<HullShape> shapes(R.N);
+    FDCM_HIP(hipMemcpyAsync(shapes.data(), R.sa.shapes, R.N * sizeof(HullShape), hipMemcpyDeviceToHost, st));
+    if (out.spans && rows) FDCM_HIP(hipMemcpyAsync(out.spans, R.sa.spans, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));
+    for (size_t j = 0; j < R.N; ++j) {
+        out.row_offsets[j] = shapes[j].row0;
+        if (out.areas) out.areas[j] = shapes[j].area;
     }
-    if (!det) {
-        if (scores_out) FDCM_HIP(hipMemcpyAsync(scores_out, d + o_score, N * 4, hipMemcpyDeviceToHost, st));
-        if (fractions_out) FDCM_HIP(hipMemcpyAsync(fractions_out, d + o_frac, N * 4, hipMemcpyDeviceToHost, st));
-        if (costs_out && Lmax) FDCM_HIP(hipMemcpyAsync(costs_out, d + o_costs, N * Lmax * 4, hipMemcpyDeviceToHost, st));
-        FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
-        return;
-    }
-    // The rounds: the list form on the keys and boxes the pass wrote; the result list begins as kNoKey throughout.
-    unsigned long long* d_best = (unsigned long long*)(d + o_best);
+    out.row_offsets[R.N] = rows;
+}
+
+// The verify call's delivery: what the pass wrote, to the outputs that are not null.
+void matches_verify_to_host(fdcm_featuremap* fm, const MatchesIn& in, const MatchesRun& R) {
+    hipStream_t st = fm->stream;
+    if (in.verify.scores) FDCM_HIP(hipMemcpyAsync(in.verify.scores, R.d + R.o_score, R.N * 4, hipMemcpyDeviceToHost, st));
+    if (in.verify.fractions) FDCM_HIP(hipMemcpyAsync(in.verify.fractions, R.d + R.o_frac, R.N * 4, hipMemcpyDeviceToHost, st));
+    if (in.verify.costs && R.Lmax) FDCM_HIP(hipMemcpyAsync(in.verify.costs, R.d + R.o_costs, R.N * R.Lmax * 4, hipMemcpyDeviceToHost, st));
+    FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
+}
+
+// The detect calls' delivery: the rounds, the list form on the keys and boxes the pass wrote (the result list begins as kNoKey
+// throughout); the gather into pinned memory, 64-byte entries; and the host's packing of them into the records at the array's front.
+void matches_detect_to_host(fdcm_featuremap* fm, const MatchesIn& in, const MatchesRun& R) {
+    hipStream_t st = fm->stream;
+    const MatchesDetect& det = *in.det;
+    const int max_det = det.max_detections;
+    unsigned long long* d_best = (unsigned long long*)(R.d + R.o_best);
     FDCM_HIP(hipMemsetAsync(d_best, 0xff, (size_t)max_det * 8, st));
     NmsArgs r{};  // a list form: no planes, no pairs, boxes whatever the set's kind
-    r.keys = a.keys_out;
-    r.boxes = a.boxes;
-    r.n = (long long)n;
-    r.n_chunks = (r.n + 255) / 256;
-    r.permille = det->overlap_permille;
-    r.cross = ob ? ob->cross : det->overlap_permille;
-    if (ob) r.obj = (const int*)(d + o_obj);
-    if (hull) {
-        r.shapes = sa.shapes;
-        r.spans = sa.spans;
-    }
-    r.pk_out = (unsigned long long*)(d + o_pk);
-    r.best = d_best;
+    r.keys = R.a.keys_out; r.boxes = R.a.boxes;
+    r.n = (long long)R.N; r.n_chunks = (r.n + 255) / 256;
+    r.permille = det.overlap_permille; r.cross = R.ob ? R.ob->cross : det.overlap_permille;
+    if (R.ob) r.obj = (const int*)(R.d + R.o_obj);
+    if (R.hull) { r.shapes = R.sa.shapes; r.spans = R.sa.spans; }
+    r.pk_out = (unsigned long long*)(R.d + R.o_pk); r.best = d_best;
     nms_rounds(r, (unsigned)std::min<long long>(kNmsWorkgroups, r.n_chunks), max_det, st);
-    // The gather, into pinned memory: 64-byte entries, which the host then packs into the records at the array's front.
-    *out = result_acquire((size_t)max_det * sizeof(MatchOut));
+    fdcm_match*& out = *in.detect.out;
+    out = result_acquire((size_t)max_det * sizeof(MatchOut));
     MatchOut* out_dev = nullptr;
-    FDCM_HIP(hipHostGetDevicePointer((void**)&out_dev, *out, 0));
+    FDCM_HIP(hipHostGetDevicePointer((void**)&out_dev, out, 0));
     hipLaunchKernelGGL(k_matches_gather, dim3((unsigned)((max_det + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)d_best, max_det,
-                       a.rec, (const float*)a.q, (const int4*)a.boxes, (const float*)a.frac, out_dev);
+                       R.a.rec, (const float*)R.a.q, (const int4*)R.a.boxes, (const float*)R.a.frac, out_dev);
     FDCM_HIP(hipGetLastError());
     FDCM_HIP(hipStreamSynchronize(st));  // (the host arrays stay alive until here)
     int64_t k = 0;
     for (; k < max_det; ++k) {
         MatchOut o;
-        std::memcpy(&o, (const char*)*out + (size_t)k * sizeof(MatchOut), sizeof o);
+        std::memcpy(&o, (const char*)out + (size_t)k * sizeof(MatchOut), sizeof o);
         if (o.idx < 0) break;
-        std::memcpy((char*)*out + (size_t)k * sizeof(fdcm_match), &o.rec, sizeof(fdcm_match));  // (in front of entry k, or in it)
-        if (indices_out) indices_out[k] = o.idx;
-        if (boxes_out) std::memcpy(boxes_out + 4 * k, &o.box, 16);
-        if (matched_out) matched_out[k] = o.frac;
+        std::memcpy((char*)out + (size_t)k * sizeof(fdcm_match), &o.rec, sizeof(fdcm_match));  // (in front of entry k, or in it)
+        if (in.detect.indices) in.detect.indices[k] = o.idx;
+        if (in.detect.boxes) std::memcpy(in.detect.boxes + 4 * k, &o.box, 16);
+        if (in.detect.matched) in.detect.matched[k] = o.frac;
     }
-    *n_out = k;
+    *in.detect.n_out = k;
+}
+
+}  // namespace
+
+// The device calls on match lists: the arguments are checked (fdcm_capi.cpp).  What `in` names selects the call
+// (fdcm_internal.h): the verify call, the detect call, with objects or without, or the shapes call.  Every call is the upload
+// and the verify pass; the hull shapes where the overlap rule or the caller needs them -- with neither objects nor shapes,
+// nothing of "Match lists: objects and hull shapes" is laid out, launched or read --; and its own delivery.
+void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const MatchesIn& in) {
+    const int64_t n = in.list.n;
+    if (in.detect.n_out) *in.detect.n_out = 0;
+    if (in.shapes) std::fill_n(in.shapes->row_offsets, n + 1, (int64_t)0);
+    if (in.shapes && in.shapes->areas) std::fill_n(in.shapes->areas, n, (int64_t)0);
+    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
+    // The shapes call is the pass with one object and no threshold, whose table of objects says which records are valid and
+    // admissible and have lines.
+    const std::vector<int32_t> one_object(in.shapes ? (size_t)t->T : 0, 0);
+    const float no_limit = f_inf();
+    const MatchesObjectsIn all{one_object.data(), 1, &no_limit, nullptr, 1000};
+    MatchesRun R;
+    R.ob = in.shapes ? &all : in.objects;
+    R.hull = in.shapes || (R.ob && t->footprint == FDCM_FOOTPRINT_HULL);
+    std::lock_guard<std::mutex> turn(fm->seam_mutex);
+    begin(fm);
+    matches_upload(fm, t, in, R);
+    matches_verify_pass(fm, t, R);
+    const long long rows = R.hull ? matches_hull_shapes(fm, in, R) : 0;
+    if (in.shapes) return matches_shapes_to_host(fm, *in.shapes, R, rows);
+    if (!in.det) return matches_verify_to_host(fm, in, R);
+    matches_detect_to_host(fm, in, R);
 }
 
 // ---- match lists: refinement (include/fdcm.h, "Match lists: refinement"): every record's own box of (delta rotation, dx, dy)
@@ -3997,14 +4045,13 @@ constexpr size_t kRefinePartBytes = (size_t)512 << 20;  // a part's lines, plane
 // records, caps, the delta table, the pivots, a part's host bins), the output records and poses of a list that leaves for the
 // host, and a part's lines, planes and keys.  The list is walked in parts of at most kRefinePartBytes of those
 // (FDCM_REFINE_PART: of that many records); a record is never cut.
-void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
-                        const fdcm_rotations* rot, int32_t centre, int32_t hx, int32_t hy, int32_t sx, int32_t sy, fdcm_match* out,
-                        bool out_on_device, int32_t* pose_out) {
-    if (n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
+void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const MatchList& m, const fdcm_rotations* rot, int32_t centre,
+                        int32_t hx, int32_t hy, int32_t sx, int32_t sy, fdcm_match* out, bool out_on_device, int32_t* pose_out) {
+    if (m.n == 0 || t->T == 0 || fm->W == 0 || fm->H == 0 || fm->m == 0) return;
     std::lock_guard<std::mutex> turn(fm->seam_mutex);
     begin(fm);
     hipStream_t st = fm->stream;
-    const size_t N = (size_t)n, T = (size_t)t->T, Lmax = (size_t)std::max<int64_t>(1, t->max_lines), na = rot ? (size_t)rot->n : 1;
+    const size_t N = (size_t)m.n, T = (size_t)t->T, Lmax = (size_t)std::max<int64_t>(1, t->max_lines), na = rot ? (size_t)rot->n : 1;
     const size_t SL = ivol_slice_floats(fm->W, fm->H);
     const bool buf32 = !test_switches().matched_flat && (size_t)fm->m * SL * sizeof(float) < ((size_t)1 << 32);  // the rule k_search uses
     const bool host_bins = orientation_bins_on_host();
@@ -4014,7 +4061,7 @@ void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm
     size_t pn = std::max<size_t>(1, std::min(N, kRefinePartBytes / per));
     if (test_switches().refine_part > 0) pn = std::min(pn, (size_t)test_switches().refine_part);
     const bool pivots = rot && rot->pivots;
-    const size_t o_caps = on_device ? 0 : al256(N * sizeof(fdcm_match)), o_cs = o_caps + (t->capped ? al256((size_t)t->n_lines * 4) : 0),
+    const size_t o_caps = m.on_device ? 0 : al256(N * sizeof(fdcm_match)), o_cs = o_caps + (t->capped ? al256((size_t)t->n_lines * 4) : 0),
                  o_piv = o_cs + (rot ? al256(na * 8) : 0), o_bins = o_piv + (pivots ? al256(T * 8) : 0),
                  o_out = o_bins + (host_bins ? al256(pn * na * Lmax * 2) : 0), o_pose = o_out + (out_on_device ? 0 : al256(N * sizeof(fdcm_match))),
                  o_lines = o_pose + (pose_out ? al256(N * 12) : 0), o_planes = o_lines + al256(pn * na * Lmax * sizeof(ExLine)),
@@ -4022,7 +4069,7 @@ void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm
     reserve_eval(fm, total, std::max<size_t>(o_out, 256));
     char* d = (char*)fm->search.eval.p;
     char* h = (char*)fm->search.eval_stage.p;
-    if (!on_device) std::memcpy(h, matches, N * sizeof(fdcm_match));
+    if (!m.on_device) std::memcpy(h, m.rec, N * sizeof(fdcm_match));
     if (t->capped) std::memcpy(h + o_caps, t->caps.data(), (size_t)t->n_lines * 4);
     if (rot) std::memcpy(h + o_cs, rot->cs, na * 8);
     if (pivots) std::memcpy(h + o_piv, rot->pivots, T * 8);
@@ -4035,8 +4082,8 @@ void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm
     a.cs = rot ? (const float*)(d + o_cs) : nullptr;
     a.pivots = pivots ? (const float*)(d + o_piv) : nullptr;
     a.bins = host_bins ? (const unsigned short*)(d + o_bins) : nullptr;
-    a.rec = on_device ? matches : (const fdcm_match*)d;
-    a.base = base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax; a.na = (int)na; a.centre = centre;
+    a.rec = m.on_device ? m.rec : (const fdcm_match*)d;
+    a.base = m.base; a.T = (int)std::min<int64_t>(t->T, 0x7fffffff); a.Lmax = (int)Lmax; a.na = (int)na; a.centre = centre;
     a.hx = hx; a.hy = hy; a.sx = sx; a.sy = sy; a.ppx = ppx; a.ppp = ppp; a.buf32 = buf32;
     a.lines = (ExLine*)(d + o_lines); a.planes = (RefinePlane*)(d + o_planes); a.ikeys = (unsigned long long*)(d + o_ikeys);
     a.out = out_on_device ? out : (fdcm_match*)(d + o_out);
@@ -4044,45 +4091,28 @@ void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm
     auto score = buf32 ? (t->capped ? k_refine_score<true, true> : k_refine_score<true, false>)
                        : (t->capped ? k_refine_score<false, true> : k_refine_score<false, false>);
     std::vector<fdcm_match> fetched;
-    std::vector<float> posed, turned;
+    std::vector<float> posed;
     for (size_t r0 = 0; r0 < N; r0 += pn) {
         const size_t nr = std::min(pn, N - r0);
         a.r0 = (int)r0; a.nr = (int)nr;
         if (host_bins) {  // the bins of this part's planes from the host libm; device records cost one download per part
-            const fdcm_match* hr = matches + r0;
-            if (on_device) {
+            const fdcm_match* hr = m.rec + r0;
+            if (m.on_device) {
                 fetched.resize(nr);
-                FDCM_HIP(hipMemcpyAsync(fetched.data(), matches + r0, nr * sizeof(fdcm_match), hipMemcpyDeviceToHost, st));
+                FDCM_HIP(hipMemcpyAsync(fetched.data(), m.rec + r0, nr * sizeof(fdcm_match), hipMemcpyDeviceToHost, st));
                 hr = fetched.data();
             }
             FDCM_HIP(hipStreamSynchronize(st));  // (the records are here, and nothing queued still reads the staging)
             unsigned short* hb = (unsigned short*)(h + o_bins);
             std::fill_n(hb, nr * na * Lmax, (unsigned short)0);
             for (size_t rl = 0; rl < nr; ++rl) {
-                const int64_t tm = (int64_t)hr[rl].tmpl_idx - base;
+                const int64_t tm = (int64_t)hr[rl].tmpl_idx - m.base;
                 if (tm < 0 || tm >= t->T) continue;
-                const int64_t l0 = t->offsets[(size_t)tm], nl = t->offsets[(size_t)tm + 1] - l0;
-                for (size_t e = 0; e < na; ++e) {
-                    turned.assign(t->lines.begin() + l0 * 4, t->lines.begin() + (l0 + nl) * 4);
-                    if (rot) {
-                        const RotM Q = rot_matrix(rot->cs[2 * e], rot->cs[2 * e + 1], pivots ? rot->pivots[2 * tm] : 0.f, pivots ? rot->pivots[2 * tm + 1] : 0.f);
-                        for (int64_t i = 0; i < 2 * nl; ++i) {
-                            const float x = turned[2 * i], y = turned[2 * i + 1];
-                            turned[2 * i] = (Q.c * x + Q.ns * y) + Q.mx;
-                            turned[2 * i + 1] = (Q.s * x + Q.c * y) + Q.my;
-                        }
-                    }
-                    const float* M = hr[rl].transform;
-                    for (int64_t i = 0; i < nl; ++i) {
-                        float v[4];
-                        for (int c = 0; c < 2; ++c) {
-                            const float x = turned[4 * i + 2 * c], y = turned[4 * i + 2 * c + 1];
-                            v[2 * c] = (M[0] * x + M[1] * y) + M[2];
-                            v[2 * c + 1] = (M[3] * x + M[4] * y) + M[5];
-                        }
-                        const float angle = std::atan((v[3] - v[1]) / (v[2] - v[0]));  // getAngle, math.h:295-299
-                        hb[(rl * na + e) * Lmax + i] = (unsigned short)closest_orientation(fm->keys.data(), (int)fm->m, angle);
-                    }
+                for (size_t e = 0; e < na; ++e) {  // P_e(r): the delta in front of the record's transform
+                    RotM Q{};
+                    if (rot) Q = rot_matrix(rot->cs[2 * e], rot->cs[2 * e + 1], pivots ? rot->pivots[2 * tm] : 0.f, pivots ? rot->pivots[2 * tm + 1] : 0.f);
+                    pose_lines(t, tm, hr[rl].transform, posed, rot ? &Q : nullptr);
+                    posed_bins(fm, posed, hb + (rl * na + e) * Lmax);
                 }
             }
             FDCM_HIP(hipMemcpyAsync(d + o_bins, hb, nr * na * Lmax * 2, hipMemcpyHostToDevice, st));

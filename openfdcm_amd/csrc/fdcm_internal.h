@@ -486,20 +486,18 @@ void run_search_exhaustive_detect_windows_objects(fdcm_featuremap* fm, const fdc
 void run_line_costs(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_rotations* rot, const int32_t* poses, int64_t n,
                     float** costs, int64_t* offsets);
 // Match lists (include/fdcm.h, "Match lists"), implemented in fdcm_exhaustive.hip: the arguments are checked.
-// matches_footprints: host only, 4 int32 per record.  run_matches: both device calls; `matches` are n records on the host or
-// (on_device) on the handle's device; det null: the verify call, whose outputs scores_out, fractions_out (n floats) and
-// costs_out (n x max_lines floats) may each be null; else the detect call with *out acquired (max_detections entries at
-// most), *n_out its count, and indices_out, boxes_out (4 per entry), matched_out of max_detections entries or null.
+// A record list as every device call on one takes it: n records on the host or (on_device) on the handle's device, whose
+// tmpl_idx count from base.
+struct MatchList { const fdcm_match* rec; int64_t n; bool on_device; int32_t base; };
 struct MatchesDetect {
     float max_score;
     int max_detections, overlap_permille, margin, penalty;
     float tau, min_matched;
     int rescore;
 };
-// "Match lists: objects and hull shapes".  objects_in: the detect call with objects, which honours the set's kind of footprint
-// (objects: T checked labels; max_score: G floats; min_matched: G floats or null; det's max_score and min_matched are not
-// read).  shapes_out: the shapes call (det null), the table of every valid admissible record with lines from the device kernel:
-// row_offsets n + 1, areas n or null, spans 2 per row or null.
+// "Match lists: objects and hull shapes".  The objects of the detect call with objects, which honours the set's kind of
+// footprint (objects: T checked labels; max_score: G floats; min_matched: G floats or null; det's max_score and min_matched
+// are not read).
 struct MatchesObjectsIn {
     const int32_t* objects;
     int G;
@@ -507,29 +505,38 @@ struct MatchesObjectsIn {
     const float* min_matched;
     int cross;
 };
+// The shapes call's outputs: the table of every valid admissible record with lines from the device kernel: row_offsets n + 1,
+// areas n or null, spans 2 per row or null.
 struct MatchesShapesOut {
     int margin;
     int64_t* row_offsets;
     int64_t* areas;
     int32_t* spans;
 };
+// What a device call on a match list asks of run_matches; the callers fill the fields by name.  det null and shapes null: the
+// verify call.  det: a detect call, with `objects` or without.  shapes (det null): the shapes call.
+struct MatchesIn {
+    MatchList list{};
+    const MatchesDetect* det = nullptr;
+    const MatchesObjectsIn* objects = nullptr;
+    struct { float *scores, *fractions, *costs; } verify{};  // n floats each, costs n x max_lines floats; each may be null
+    // *out acquired (max_detections entries at most), *n_out its count; indices, boxes (4 per entry), matched: max_detections, or null
+    struct { fdcm_match** out; int64_t* n_out; int32_t *indices, *boxes; float* matched; } detect{};
+    const MatchesShapesOut* shapes = nullptr;
+};
+// matches_footprints: host only, 4 int32 per record.
 void matches_footprints(const fdcm_templates* t, const fdcm_match* matches, int64_t n, int32_t base, int margin, int32_t* boxes_out);
 // host only: the hull shape of every record, lines_footprint_spans' layout (an invalid record: no rows)
 void matches_footprint_spans(const fdcm_templates* t, const fdcm_match* matches, int64_t n, int32_t base, int margin, int64_t* row_offsets,
                              int64_t* areas, int32_t* spans);
-void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
-                 const MatchesDetect* det, float* scores_out, float* fractions_out, float* costs_out, fdcm_match** out, int64_t* n_out,
-                 int32_t* indices_out, int32_t* boxes_out, float* matched_out, const MatchesObjectsIn* objects_in = nullptr,
-                 const MatchesShapesOut* shapes_out = nullptr);
+void run_matches(fdcm_featuremap* fm, const fdcm_templates* t, const MatchesIn& in);
 // "Match lists: refinement": every record's window of (delta rotation, dx, dy) searched on the device; out: n records on the host
-// or (out_on_device) on the handle's device, which may be `matches`; pose_out: n x 3 on the host, or null.
-void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
-                        const fdcm_rotations* rot, int32_t centre, int32_t hx, int32_t hy, int32_t sx, int32_t sy, fdcm_match* out,
-                        bool out_on_device, int32_t* pose_out);
+// or (out_on_device) on the handle's device, which may be the list's; pose_out: n x 3 on the host, or null.
+void run_matches_refine(fdcm_featuremap* fm, const fdcm_templates* t, const MatchList& m, const fdcm_rotations* rot, int32_t centre,
+                        int32_t hx, int32_t hy, int32_t sx, int32_t sy, fdcm_match* out, bool out_on_device, int32_t* pose_out);
 // the bins of every posed line from the host libm, [record][max_lines], where fdcm_orientation_bins_mode() is 1 (else empty); the
 // handle has its stream
-void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool on_device, int32_t base,
-                       std::vector<unsigned short>& bins);
+void matches_host_bins(fdcm_featuremap* fm, const fdcm_templates* t, const MatchList& m, std::vector<unsigned short>& bins);
 // Scene coverage (include/fdcm.h, "Scene coverage").  What prepare_pairs yields for the distinct pairs of a pose list, in the
 // plain form fdcm_coverage.hip takes: pair u = find(tmpl * n_rot + a) has the lines [line0[u], line0[u] + nl[u]) -- the (rotated)
 // end points and the bin k_line_costs reads --, its admissible translations adm[5 u ..] = any, x0, x1, y0, y1 and its footprint
@@ -558,22 +565,20 @@ void run_scene_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int
                       const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
                       int64_t* n_out, uint8_t* residual);
 // Scene coverage and selection of match records (include/fdcm.h, "Match lists: scene coverage and selection"), implemented in
-// fdcm_coverage.hip: the siblings' arguments with run_matches' records (n on the host or, matches_on_device, on the handle's
-// device) in place of the poses; the table is made on the device (k_matches_table).  counts: 2 n int32 on the host.
+// fdcm_coverage.hip: the siblings' arguments with a record list in place of the poses; the table is made on the device
+// (k_matches_table), in parts under FDCM_COVERAGE_PART.  counts: 2 n int32 on the host.
 void run_matches_coverage(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
-                          const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
-                          const fdcm_coverage_params& params, int32_t* counts, uint8_t* residual);
+                          const fdcm_templates* t, const MatchList& m, const fdcm_coverage_params& params, int32_t* counts,
+                          uint8_t* residual);
 void run_matches_select(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
-                        const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
-                        const fdcm_coverage_params& params, const fdcm_select_params& sel, int32_t* selected, int32_t* counts,
-                        int64_t* n_out, uint8_t* residual);
+                        const fdcm_templates* t, const MatchList& m, const fdcm_coverage_params& params, const fdcm_select_params& sel,
+                        int32_t* selected, int32_t* counts, int64_t* n_out, uint8_t* residual);
 // "Match lists: pose fit": every record fitted to the edge pixels it explains, the records staying on the device between the
-// passes; out: n records on the host or (out_on_device) on the handle's device, which may be `matches`; info_out: 4 n int32,
+// passes; out: n records on the host or (out_on_device) on the handle's device, which may be the list's; info_out: 4 n int32,
 // rms_out: 2 n floats, on the host, or null.
 void run_matches_fit(fdcm_featuremap* fm, const uint8_t* labels, int width, int height, bool on_device, int bx, int by,
-                     const fdcm_templates* t, const fdcm_match* matches, int64_t n, bool matches_on_device, int32_t base,
-                     const fdcm_coverage_params& params, const fdcm_fit_params& fit, fdcm_match* out, bool out_on_device, int32_t* info_out,
-                     float* rms_out);
+                     const fdcm_templates* t, const MatchList& m, const fdcm_coverage_params& params, const fdcm_fit_params& fit,
+                     fdcm_match* out, bool out_on_device, int32_t* info_out, float* rms_out);
 // implemented in fdcm_tail.hip
 void run_topk(fdcm_featuremap* fm, const fdcm_templates* t, const fdcm_match* matches_device, int64_t n, int32_t base,
               int penalty, float tau, int64_t k, fdcm_match** out, int64_t* n_out);

@@ -701,6 +701,24 @@ class DeviceFeatureMap:
         rec = match_records(matches)
         return (C.c_void_p(rec.ctypes.data) if rec.shape[0] else None), rec.shape[0], 0, rec
 
+    @staticmethod
+    def _detect_outputs(max_detections, indices, boxes, matched):
+        """The outputs of a detect call on a match list: (out, k) for the records, the optional arrays' pointers in the C
+        order (None where not asked for) and result(), the method's return value after the call."""
+        out, k = C.c_void_p(), C.c_int64()
+        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0  # (an argument out of range is the library's to refuse)
+        ji = np.zeros(md, dtype=np.int32)
+        fp = np.zeros((md, 4), dtype=np.int32)
+        fr = np.zeros(md, dtype=np.float32)
+        optional = (ji.ctypes.data_as(C.POINTER(C.c_int32)) if indices and md else None,
+                    fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None, capi.fptr(fr) if matched and md else None)
+
+        def result():
+            res = (_adopt_matches(out, k.value),) + ((ji[:k.value].copy(),) if indices else ()) + ((fp[:k.value].copy(),) if boxes else ())
+            res += (fr[:k.value].copy(),) if matched else ()
+            return res if len(res) > 1 else res[0]
+        return out, k, optional, result
+
     def verify_matches(self, templates, matches=None, tmpl_index_base=0, device_ptr=None, n=0):
         """fdcm_matches_verify: (scores, fractions, costs) of every record: s(r) and frac(r) as (n,) float32 and the uncapped
         line costs as an (n, Lmax) float32 array, NaN beyond a template's line count, all NaN for a record that is invalid or
@@ -721,19 +739,12 @@ class DeviceFeatureMap:
         in ascending order with q for their score; with indices the (k,) int32 positions in the list, with boxes the (k, 4)
         int32 footprints, with matched the (k,) float32 fractions, in that order.  The forms of matches are verify_matches'."""
         ptr, n, on_device, keep = self._match_input(matches, device_ptr, n)
-        out, k = C.c_void_p(), C.c_int64()
-        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0
-        ji = np.zeros(md, dtype=np.int32)
-        fp = np.zeros((md, 4), dtype=np.int32)
-        fr = np.zeros(md, dtype=np.float32)
+        out, k, optional, result = self._detect_outputs(max_detections, indices, boxes, matched)
         capi.check(capi.lib().fdcm_matches_detect(
             self._h, templates._h, ptr, n, on_device, int(tmpl_index_base), float(max_score), int(max_detections), int(overlap_permille),
             int(margin), -1 if penalty is None else int(penalty), float(tau), 0.0 if min_matched is None else float(min_matched),
-            int(bool(rescore)), C.byref(out), C.byref(k), ji.ctypes.data_as(C.POINTER(C.c_int32)) if indices and md else None,
-            fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None, capi.fptr(fr) if matched and md else None))
-        res = (_adopt_matches(out, k.value),) + ((ji[:k.value].copy(),) if indices else ()) + ((fp[:k.value].copy(),) if boxes else ())
-        res += (fr[:k.value].copy(),) if matched else ()
-        return res if len(res) > 1 else res[0]
+            int(bool(rescore)), C.byref(out), C.byref(k), *optional))
+        return result()
 
     def refine_matches(self, templates, matches=None, cs=None, pivots=None, centre=None, hx=0, hy=0, sx=1, sy=1, tmpl_index_base=0,
                        poses=False, device_ptr=None, n=0, out_device_ptr=None):
@@ -773,21 +784,13 @@ class DeviceFeatureMap:
         outputs and the forms of matches are detect_matches'."""
         obj, G, ms, mm = object_arrays(objects, n_objects, templates.count, max_score, min_matched)
         ptr, n, on_device, keep = self._match_input(matches, device_ptr, n)
-        out, k = C.c_void_p(), C.c_int64()
-        md = int(max_detections) if 1 <= int(max_detections) <= 4096 else 0
-        ji = np.zeros(md, dtype=np.int32)
-        fp = np.zeros((md, 4), dtype=np.int32)
-        fr = np.zeros(md, dtype=np.float32)
+        out, k, optional, result = self._detect_outputs(max_detections, indices, boxes, matched)
         capi.check(capi.lib().fdcm_matches_detect_objects(
             self._h, templates._h, ptr, n, on_device, int(tmpl_index_base), obj.ctypes.data_as(C.POINTER(C.c_int32)), G,
             capi.fptr(ms) if ms is not None else None, capi.fptr(mm) if mm is not None else None, int(max_detections),
             int(overlap_permille), int(overlap_permille if cross_permille is None else cross_permille), int(margin),
-            -1 if penalty is None else int(penalty), float(tau), int(bool(rescore)), C.byref(out), C.byref(k),
-            ji.ctypes.data_as(C.POINTER(C.c_int32)) if indices and md else None,
-            fp.ctypes.data_as(C.POINTER(C.c_int32)) if boxes and md else None, capi.fptr(fr) if matched and md else None))
-        res = (_adopt_matches(out, k.value),) + ((ji[:k.value].copy(),) if indices else ()) + ((fp[:k.value].copy(),) if boxes else ())
-        res += (fr[:k.value].copy(),) if matched else ()
-        return res if len(res) > 1 else res[0]
+            -1 if penalty is None else int(penalty), float(tau), int(bool(rescore)), C.byref(out), C.byref(k), *optional))
+        return result()
 
     def match_shapes(self, templates, matches, margin=0, tmpl_index_base=0, device_ptr=None, n=0):
         """fdcm_matches_shapes: match_footprint_spans' table from the device kernel, for the records that are valid and
@@ -806,24 +809,11 @@ class DeviceFeatureMap:
         (-1, -1) for a pose that is not admissible.  `labels`: 2-D uint8, a numpy array or a contiguous CUDA torch tensor, the
         image this map was built from.  Returns counts, an (n, 2) int32 array, or with residual (counts, residual): the labels
         with 255 at every pixel an admissible pose of the list explains, a tensor on the same device for a tensor."""
-        if hasattr(labels, "data_ptr") and not isinstance(labels, np.ndarray) and labels.dim() == 2 and not labels.is_contiguous():
-            raise ValueError("labels on the device must be contiguous")
-        p, w, h, _, dev, keep = _pixels(labels, "labels")
-        if not dev and keep.size and keep.strides[0] != w:
-            keep = np.ascontiguousarray(keep)
-            p = C.c_void_p(keep.ctypes.data)
+        p, w, h, dev, keep, res, q = self._labels_input(labels, residual)
         poses = as_poses(poses)
         rot, keep_rot = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
         par = capi.CoverageParams(int(radius), int(bin_tolerance), int(radius if margin is None else margin))
         counts = np.zeros((poses.shape[0], 2), dtype=np.int32)
-        res, q = None, None
-        if residual and dev:
-            import torch
-            res = torch.empty((h, w), dtype=torch.uint8, device=keep.device)
-            q = C.c_void_p(res.data_ptr())
-        elif residual:
-            res = np.empty((h, w), dtype=np.uint8)
-            q = C.c_void_p(res.ctypes.data)
         capi.check(capi.lib().fdcm_scene_coverage(self._h, p, w, h, dev, templates._h, C.byref(rot) if rot is not None else None,
                                                   poses.ctypes.data_as(C.POINTER(C.c_int32)), poses.shape[0], C.byref(par),
                                                   counts.ctypes.data_as(C.POINTER(C.c_int32)) if counts.size else None, q))
@@ -839,36 +829,32 @@ class DeviceFeatureMap:
         labels, templates, cs, pivots, radius, bin_tolerance and margin are scene_coverage's.  Returns (selected, counts): the
         (k,) int32 indices of the accepted poses, ascending, and (k, 3) int32 rows (edges, explained, new), new as at
         acceptance; with residual also the labels with 255 at every claimed pixel, a tensor on the same device for a tensor."""
-        if hasattr(labels, "data_ptr") and not isinstance(labels, np.ndarray) and labels.dim() == 2 and not labels.is_contiguous():
-            raise ValueError("labels on the device must be contiguous")
-        p, w, h, _, dev, keep = _pixels(labels, "labels")
-        if not dev and keep.size and keep.strides[0] != w:
-            keep = np.ascontiguousarray(keep)
-            p = C.c_void_p(keep.ctypes.data)
+        p, w, h, dev, keep, res, q = self._labels_input(labels, residual)
         poses = as_poses(poses)
         rot, keep_rot = _rotations(cs, pivots, templates.count) if cs is not None else (None, None)
         par = capi.CoverageParams(int(radius), int(bin_tolerance), int(radius if margin is None else margin))
+        sel, outputs, result = self._select_outputs(min_coverage, min_new, min_pixels, max_selected, residual)
+        capi.check(capi.lib().fdcm_scene_select(self._h, p, w, h, dev, templates._h, C.byref(rot) if rot is not None else None,
+                                                poses.ctypes.data_as(C.POINTER(C.c_int32)), poses.shape[0], C.byref(par), C.byref(sel), *outputs, q))
+        return result(res)
+
+    @staticmethod
+    def _select_outputs(min_coverage, min_new, min_pixels, max_selected, residual):
+        """The rule's parameters and the outputs of a selection call: SelectParams, the pointers of selected, counts and k in
+        the C order, and result(res), the method's return value after the call."""
         sel = capi.SelectParams(int(round(1000 * min_coverage)), int(round(1000 * min_new)), int(min_pixels), int(max_selected))
         room = max(1, min(int(max_selected), 4096))          # (an argument out of range is the library's to refuse)
         selected = np.zeros(room, dtype=np.int32)
         counts = np.zeros((room, 3), dtype=np.int32)
         k = C.c_int64(0)
-        res, q = None, None
-        if residual and dev:
-            import torch
-            res = torch.empty((h, w), dtype=torch.uint8, device=keep.device)
-            q = C.c_void_p(res.data_ptr())
-        elif residual:
-            res = np.empty((h, w), dtype=np.uint8)
-            q = C.c_void_p(res.ctypes.data)
-        capi.check(capi.lib().fdcm_scene_select(self._h, p, w, h, dev, templates._h, C.byref(rot) if rot is not None else None,
-                                                poses.ctypes.data_as(C.POINTER(C.c_int32)), poses.shape[0], C.byref(par), C.byref(sel),
-                                                selected.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k), q))
-        selected, counts = selected[:k.value].copy(), counts[:k.value].copy()
-        return (selected, counts, res) if residual else (selected, counts)
+        outputs = (selected.ctypes.data_as(C.POINTER(C.c_int32)), counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k))
 
-    # ---- match lists: scene coverage and selection (include/fdcm.h, "Match lists: scene coverage and selection")
+        def result(res):
+            got = (selected[:k.value].copy(), counts[:k.value].copy())
+            return got + (res,) if residual else got
+        return sel, outputs, result
+
+    # ---- the labels of the coverage, selection and fit calls, pose lists and match lists alike
     def _labels_input(self, labels, residual):
         """(pointer, width, height, on_device, kept alive, residual array or tensor, its pointer) of scene coverage's labels."""
         if hasattr(labels, "data_ptr") and not isinstance(labels, np.ndarray) and labels.dim() == 2 and not labels.is_contiguous():
@@ -910,16 +896,10 @@ class DeviceFeatureMap:
         p, w, h, dev, keep, res, q = self._labels_input(labels, residual)
         ptr, n, on_device, keep_rec = self._match_input(matches, device_ptr, n)
         par = capi.CoverageParams(int(radius), int(bin_tolerance), int(radius if margin is None else margin))
-        sel = capi.SelectParams(int(round(1000 * min_coverage)), int(round(1000 * min_new)), int(min_pixels), int(max_selected))
-        room = max(1, min(int(max_selected), 4096))          # (an argument out of range is the library's to refuse)
-        selected = np.zeros(room, dtype=np.int32)
-        counts = np.zeros((room, 3), dtype=np.int32)
-        k = C.c_int64(0)
+        sel, outputs, result = self._select_outputs(min_coverage, min_new, min_pixels, max_selected, residual)
         capi.check(capi.lib().fdcm_matches_select(self._h, p, w, h, dev, templates._h, ptr, n, on_device, int(tmpl_index_base),
-                                                  C.byref(par), C.byref(sel), selected.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                  counts.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k), q))
-        selected, counts = selected[:k.value].copy(), counts[:k.value].copy()
-        return (selected, counts, res) if residual else (selected, counts)
+                                                  C.byref(par), C.byref(sel), *outputs, q))
+        return result(res)
 
     def fit_matches(self, labels, templates, matches=None, radius=3, bin_tolerance=1, margin=None, iterations=2, min_pixels=8,
                     damping=1e-3, max_shift=None, max_angle=0.1, tmpl_index_base=0, info=False, rms=False, device_ptr=None, n=0,

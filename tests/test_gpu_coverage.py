@@ -4,8 +4,12 @@ on label images of 96 x 80 and 70 x 37 at border 0 and 5 and depth 6 and 30, on 
 templates of 0, 1, 3 and 40 lines, one of 300 lines (more than the kernel's LDS chunk of 256 segments), one with a zero-length
 line, one whose window is the image and one whose window is a pixel wide; poses inside the image, cut by each border, wholly
 outside, not admissible, duplicated and overlapping, with and without a table of 7 angles.  Then the identities on device
-output, two runs byte for byte, tensors against arrays, n = 0, the refused maps, and one frame end to end."""
+output, two runs byte for byte, tensors against arrays, n = 0, the refused maps, one frame end to end, and the pose-list calls
+of coverage and selection under the poison in fresh processes (tools/coverage_probe.py)."""
 import functools
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -313,3 +317,24 @@ def test_end_to_end_part_against_clutter_and_the_next_round():
     after = fd.record_poses(fd.exhaustive_detect_all(fm, [tm], thr, overlap=0.3, max_detections=12))
     assert not any(abs(p[2] - PART_AT[0]) <= 2 and abs(p[3] - PART_AT[1]) <= 2 for p in after), after
     assert any(in_patch(p) for p in after)
+
+
+# ---- the pose-list calls in fresh processes, under the poison (tools/coverage_probe.py)
+def _probe(env):
+    probe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "coverage_probe.py")
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("FDCM_")}
+    out = subprocess.run([sys.executable, probe], capture_output=True, text=True, timeout=240, env={**clean, **env})
+    assert out.returncode == 0, out.stdout + out.stderr
+    return [l for l in out.stdout.splitlines() if l.startswith("coverage_probe ")][-1].split()
+
+
+def test_pose_list_calls_under_the_poison_in_fresh_processes():
+    """tools/coverage_probe.py -- scene_coverage and scene_select on host and device labels, with and without a residual, plain
+    and with angles -- in fresh processes, one after another, each under its own time limit: the default run, FDCM_POISON=0 and
+    FDCM_POISON=1 print one digest.  Nothing is started after a failure (an assertion ends the test).  The case holds what it
+    is for: poses that are not admissible, windows without an edge pixel, and a selection of more than the 64 rounds of a batch."""
+    want = _probe({})
+    lists = int(want[9]) // 6                                     # (6 calls per list of 294 poses, 5 of them placed off the map)
+    assert lists == 12 and int(want[3]) <= (294 - 5) * lists and int(want[5]) > 0 and int(want[7]) > 64, want
+    for env in ({"FDCM_POISON": "0"}, {"FDCM_POISON": "1"}):
+        assert _probe(env) == want, env
