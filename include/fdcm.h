@@ -1407,6 +1407,72 @@ int fdcm_matches_fit(const fdcm_featuremap* fm, const uint8_t* labels, int64_t w
                      fdcm_match* out /* n records */, int out_on_device, int32_t* info_out /* n x 4 host, or NULL */,
                      float* rms_out /* n x 2 host, or NULL */);
 
+/* ---- Templates from a mesh: the visible sharp edges and occluding contours of a triangle mesh, per view, as line templates.
+ *      This project's own: the reference samples its templates with an OpenGL renderer outside the library (README, "6-DOF
+ *      estimation", step 1).  Every float operation below is float32, rounded once and never fused, in the order written;
+ *      floor, ceil, sqrt and division are the correctly rounded ones, and no libm function runs on the device.
+ *      Mesh.  vertices: V x 3 float32, finite; faces: F x 3 int32 indices into them, 1 <= V, F <= 2^22; winding is free and a
+ *      face may be degenerate.  Edges: the undirected vertex pairs {i < j} of all faces (a pair a face names twice counts
+ *      once for it; a pair i = j is none), sorted by (i, j): that position is the edge index e.  An edge has one or two
+ *      incident faces f0 < f1; three or more are FDCM_EINVAL ("non-manifold edge").  The vertex of a face opposite an edge is
+ *      the index at the position of the face that the pair leaves out.  sharp(e) is decided once, on the host, in float64
+ *      (products and sums one operation each, a dot product as (a0 b0 + a1 b1) + a2 b2, the cross product's components as
+ *      differences of two products): the edge is a boundary edge (one face); or either face normal n = (v1 - v0) x (v2 - v0)
+ *      is the zero vector; or |n0 . n1| < (crease_cos * sqrt(n0 . n0)) * sqrt(n1 . n1).  crease_cos is a double in [-1, 1],
+ *      the cosine of the crease angle; the absolute value makes the flag independent of winding.
+ *      View.  A 3 x 3 float32 matrix R (row-major, finite, not required to be orthonormal) and one scale > 0, finite, in
+ *      pixels per mesh unit, for the call.  Vertex v projects to P = ((r00 x + r01 y) + r02 z, .., ..), X = scale * P.x,
+ *      Y = scale * P.y, Z = P.z; the viewer is at Z = +infinity.  Orthographic only.
+ *      Orientation.  o(A, B, C) = (B.X - A.X) * (C.Y - A.Y) - (B.Y - A.Y) * (C.X - A.X).
+ *      Candidate edge of a view.  A sharp edge; or one that is a contour: with c0, c1 the vertices of f0, f1 opposite
+ *      e = (A, B), o0 = o(A, B, c0) and o1 = o(A, B, c1), e is a contour unless o0 and o1 are strictly of opposite sign.
+ *      Pixel box of a view.  x0, y0, x1, y1: the least and largest floor(X) and floor(Y) over the vertices.  A view with a
+ *      vertex whose |X| or |Y| is not below 2^30, or whose box spans more than 4096 pixels on a side, is FDCM_EINVAL with its
+ *      index, after the projection pass and before any raster work.
+ *      Item buffer D of a view.  On the integer pixels (i, j) with centre c = (i + 0.5, j + 0.5).  Face f = (A, B, C) is tried
+ *      at the pixels of its own box (floor of its vertices' least and largest X and Y) and covers c when a = o(A, B, C) != 0
+ *      and e0 = o(B, C, c), e1 = o(C, A, c), e2 = o(A, B, c) are all >= 0 (a > 0) or all <= 0 (a < 0): the edges are
+ *      inclusive.  Its depth there is z = ((e0 * A.Z + e1 * B.Z) + e2 * C.Z) / a; a NaN z does not cover.  D(i, j) is the
+ *      largest key (ord(z) << 32) | f over the covering faces, ord the order-preserving map of float32 bits to uint32
+ *      (negative: all bits flipped; else the sign bit set); D = 0 is "empty", and so is every pixel outside the box.
+ *      Samples of a candidate edge (A, B).  dx = B.X - A.X, dy and dz likewise; n = max(1, (int)ceil(max(|dx|, |dy|))); for
+ *      k = 0 .. n: t = (float)k / (float)n, S_k = (A.X + t * dx, A.Y + t * dy, A.Z + t * dz), its pixel (floor(S.X),
+ *      floor(S.Y)).  Sample k is visible when D of its pixel is empty; or the face f in D is f0 or f1; or S.Z + depth_tol >=
+ *      zf, zf being face f's depth formula at (S.X, S.Y) in place of the centre: the plane of the occluder at the sample
+ *      itself, so that a coplanar sibling triangle never hides an edge, whatever the slope.  depth_tol >= 0, finite, in mesh
+ *      units.
+ *      Lines of a view.  Per candidate edge in edge order, the maximal runs k0 < k1 of consecutive visible samples; each gives
+ *      the line (S_k0.X, S_k0.Y, S_k1.X, S_k1.Y), kept when its length sqrt(ddx * ddx + ddy * ddy) is > 0 and >= min_length
+ *      (>= 0, finite).  Output order is (edge, k0).  Template coordinates have the projection of the mesh origin at (0, 0).
+ *      Each view is defined on its own: a list of views equals the views one call each.
+ *      The device.  A projection pass, a thread per (view, vertex), leaves each view's box (16 n_views bytes come to the
+ *      host).  Per part of the views: a raster pass, 16 lanes per (view, face) over 4 x 4 pixel tiles of the face's box with
+ *      64-bit atomic maxima, faces of more than 64 tiles through a list into a pass of 16 x 16 tiles; an edge pass, a lane
+ *      per (view, edge), that counts the lines, a scan, and the same pass writing them, in runs of views whose lines fit
+ *      256 MB.  Only the boxes and the totals come to the host.  Device memory stays below 1 GB however many views there
+ *      are -- one view is never cut, so a single view that alone gives more than 2^24 lines takes what its lines take on top
+ *      -- and projections are recomputed where they are used, never stored.
+ *      FDCM_EINVAL, before any GPU work: NULL pointers; V or F outside 1 .. 2^22; an index outside 0 .. V - 1; a non-finite
+ *      vertex or view entry; scale not finite or <= 0; depth_tol or min_length not finite or < 0; crease_cos NaN or outside
+ *      [-1, 1]; n_views outside 0 .. 2^16; a total of 2^31 lines or more (after the count).  Zero views give zero lines
+ *      (*lines_out NULL) and FDCM_OK.  The calls block and run on the calling thread's device (fdcm_set_device). ---- */
+typedef struct fdcm_mesh fdcm_mesh;
+/* host only: the edge table and the flags; no device is needed */
+int fdcm_mesh_create(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, double crease_cos,
+                     fdcm_mesh** out);
+int fdcm_mesh_free(fdcm_mesh* mesh);
+int fdcm_mesh_info(const fdcm_mesh* mesh, int64_t* n_edges, int64_t* n_sharp, int64_t* n_boundary);  /* each may be NULL */
+/* host only: verts 2 per edge, faces 2 per edge (-1: none), sharp 1 per edge; each may be NULL */
+int fdcm_mesh_edges(const fdcm_mesh* mesh, int32_t* verts, int32_t* faces, uint8_t* sharp);
+/* *lines_out: 4 floats per line, malloc'ed (fdcm_lines_free), NULL when there is none; offsets_out: n_views + 1 -- what
+ * fdcm_templates_create takes as its lines and offsets */
+int fdcm_mesh_view_lines(const fdcm_mesh* mesh, const float* views /* 9 per view */, int64_t n_views, float scale,
+                         float depth_tol, float min_length, float** lines_out, int64_t* offsets_out);
+/* test hook, like the _staged builds: one view's pixel box (x0, y0, x1, y1) and its item buffer, keys_out[(j - y0) * (x1 - x0
+ * + 1) + (i - x0)]; keys_out NULL: the box alone; else capacity keys must hold the box (FDCM_EINVAL after box_out is written) */
+int fdcm_mesh_view_items(const fdcm_mesh* mesh, const float* view /* 9 */, float scale, int32_t* box_out /* 4 */,
+                         uint64_t* keys_out, int64_t capacity);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

@@ -291,6 +291,12 @@ SYMBOLS = [
     ("fdcm_lines_from_image", C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.POINTER(EdgeParams),
                                         C.POINTER(LineParams), C.POINTER(C.POINTER(C.c_float)), _i64p]),
     ("fdcm_lines_last_timing", C.c_int, [C.POINTER(LinesTiming)]),
+    ("fdcm_mesh_create", C.c_int, [_fp, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_double, C.POINTER(_vp)]),
+    ("fdcm_mesh_free", C.c_int, [_vp]),
+    ("fdcm_mesh_info", C.c_int, [_vp, _i64p, _i64p, _i64p]),
+    ("fdcm_mesh_edges", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]),
+    ("fdcm_mesh_view_lines", C.c_int, [_vp, _fp, C.c_int64, C.c_float, C.c_float, C.c_float, C.POINTER(C.POINTER(C.c_float)), _i64p]),
+    ("fdcm_mesh_view_items", C.c_int, [_vp, _fp, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int64]),
     ("fdcm_selftest_atanf", C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint64]),
     ("fdcm_orientation_bins_mode", C.c_int, []),
     ("fdcm_selftest_sweep_ranges", C.c_int, [C.c_int]),

@@ -1848,6 +1848,72 @@ int fdcm_lines_write(const char* path, const float* lines, int64_t n_lines) {
 }
 void fdcm_lines_free(float* lines) { std::free(lines); }
 
+// ------------------------------------------------------------------------------------------ templates from a mesh (fdcm_mesh.hip)
+int fdcm_mesh_create(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, double crease_cos, fdcm_mesh** out) {
+    return guarded([&] {
+        require(out != nullptr, "out is null");
+        *out = nullptr;
+        require(vertices != nullptr, "vertices is null");
+        require(faces != nullptr, "faces is null");
+        require(n_vertices >= 1 && n_vertices <= ((int64_t)1 << 22), "n_vertices must be in [1, 2^22]");
+        require(n_faces >= 1 && n_faces <= ((int64_t)1 << 22), "n_faces must be in [1, 2^22]");
+        require(crease_cos >= -1.0 && crease_cos <= 1.0, "crease_cos must be in [-1, 1]");
+        *out = mesh_create(vertices, n_vertices, faces, n_faces, crease_cos);
+    });
+}
+int fdcm_mesh_free(fdcm_mesh* mesh) {
+    delete mesh;
+    return FDCM_OK;
+}
+int fdcm_mesh_info(const fdcm_mesh* mesh, int64_t* n_edges, int64_t* n_sharp, int64_t* n_boundary) {
+    return guarded([&] {
+        require(mesh != nullptr, "mesh is null");
+        if (n_edges) *n_edges = mesh->E;
+        if (n_sharp) *n_sharp = mesh->n_sharp;
+        if (n_boundary) *n_boundary = mesh->n_boundary;
+    });
+}
+int fdcm_mesh_edges(const fdcm_mesh* mesh, int32_t* verts, int32_t* faces, uint8_t* sharp) {
+    return guarded([&] {
+        require(mesh != nullptr, "mesh is null");
+        for (int64_t e = 0; e < mesh->E; ++e) {
+            if (verts) { verts[2 * e] = mesh->edges[4 * e]; verts[2 * e + 1] = mesh->edges[4 * e + 1]; }
+            if (faces) { faces[2 * e] = mesh->edges[4 * e + 2]; faces[2 * e + 1] = mesh->edges[4 * e + 3]; }
+            if (sharp) sharp[e] = mesh->sharp[e];
+        }
+    });
+}
+static void check_view(const fdcm_mesh* mesh, const float* views, int64_t n_views, float scale) {
+    require(mesh != nullptr, "mesh is null");
+    require(n_views >= 0 && n_views <= 65536, "n_views must be in [0, 2^16]");
+    require(views != nullptr || n_views == 0, "views is null");
+    require(std::isfinite(scale) && scale > 0.f, "scale must be finite and > 0");
+    for (int64_t i = 0; i < 9 * n_views; ++i)
+        if (!std::isfinite(views[i])) throw std::string("view " + std::to_string(i / 9) + " has an entry that is not finite");
+}
+int fdcm_mesh_view_lines(const fdcm_mesh* mesh, const float* views, int64_t n_views, float scale, float depth_tol, float min_length,
+                         float** lines_out, int64_t* offsets_out) {
+    return guarded([&] {
+        require(lines_out != nullptr, "lines_out is null");
+        require(offsets_out != nullptr, "offsets_out is null");
+        check_view(mesh, views, n_views, scale);
+        require(std::isfinite(depth_tol) && depth_tol >= 0.f, "depth_tol must be finite and >= 0");
+        require(std::isfinite(min_length) && min_length >= 0.f, "min_length must be finite and >= 0");
+        *lines_out = nullptr;
+        offsets_out[0] = 0;
+        if (n_views > 0) mesh_view_lines(g_device, mesh, views, n_views, scale, depth_tol, min_length, lines_out, offsets_out);
+    });
+}
+int fdcm_mesh_view_items(const fdcm_mesh* mesh, const float* view, float scale, int32_t* box_out, uint64_t* keys_out, int64_t capacity) {
+    return guarded([&] {
+        require(box_out != nullptr, "box_out is null");
+        require(view != nullptr, "view is null");
+        check_view(mesh, view, 1, scale);
+        require(capacity >= 0, "capacity must be >= 0");
+        mesh_view_items(g_device, mesh, view, scale, box_out, keys_out, capacity);
+    });
+}
+
 // ------------------------------------------------------------------------------------------ self checks
 int64_t fdcm_selftest_atanf(uint32_t first, uint32_t stride, uint64_t count) {
     if (stride == 0) stride = 1;

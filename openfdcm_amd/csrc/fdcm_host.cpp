@@ -41,6 +41,7 @@ const TestSwitches& test_switches() {
         r.exhaustive_flat = set("FDCM_EXHAUSTIVE_FLAT");
         r.coverage_part = std::max(0, num("FDCM_COVERAGE_PART", 0));
         r.refine_part = std::max(0, num("FDCM_REFINE_PART", 0));
+        r.mesh_part = std::max(0, num("FDCM_MESH_PART", 0));
         r.poison = false;
         r.poison_word = 0;
         if (const char* e = getenv("FDCM_POISON")) {  // a uint32, decimal or 0x-hex, and nothing after it

@@ -48,6 +48,9 @@ struct HipError { hipError_t code; const char* what; int line; };
 //                              table hold (run_matches_coverage; run_matches_fit: of table and moments)
 //   FDCM_REFINE_PART=1..       records a part of the refinement of a match list holds at most, instead of what 512 MB of lines,
 //                              planes and keys hold (run_matches_refine)
+//   FDCM_MESH_PART=1..         views a part of the templates from a mesh holds at most, instead of what 512 MB of item buffers,
+//                              lists and counts hold, and 16 lines per such view a writing pass, instead of 256 MB of them
+//                              (mesh_view_lines)
 //   FDCM_EXHAUSTIVE_FLAT       the dense exhaustive calls with 64-bit flat addresses: every prepare_pairs call that otherwise
 //                              takes that form for a volume of 4 GB or more alone (score maps, top-k, peaks, rotations, best
 //                              map, the detections, line costs); the pose windows and the calls by matched fraction keep
@@ -83,6 +86,7 @@ struct TestSwitches {
     bool windows_flat, matched_flat, exhaustive_flat;
     int coverage_part;  // 0: not forced
     int refine_part;    // 0: not forced
+    int mesh_part;      // 0: not forced
     bool poison;           // FDCM_POISON holds a valid word
     uint32_t poison_word;
 };
@@ -335,7 +339,23 @@ struct fdcm_templates {
     fdcm::DevBuf d_lines, d_offsets, d_lengths, d_sorted;
 };
 
+// A triangle mesh with its edge table (include/fdcm.h, "Templates from a mesh"): host memory alone; a view call uploads it.
+struct fdcm_mesh {
+    int64_t V = 0, F = 0, E = 0, n_sharp = 0, n_boundary = 0;
+    std::vector<float> vertices;   // 3 V
+    std::vector<int32_t> faces;    // 3 F
+    std::vector<int32_t> edges;    // 4 E: i < j, f0 < f1 (-1: a boundary edge), ascending (i, j)
+    std::vector<uint8_t> sharp;    // E
+};
+
 namespace fdcm {
+// implemented in fdcm_mesh.hip: the arguments are checked but for what needs the table (indices, finiteness, manifoldness),
+// which mesh_create refuses with a std::string.  The view calls block, on the null stream of `device`, and hold what they need
+// there in a PixelScratch of their own; n_views >= 1.  *lines_out is malloc'ed (fdcm_lines_free), untouched when there is no line.
+fdcm_mesh* mesh_create(const float* vertices, int64_t V, const int32_t* faces, int64_t F, double crease_cos);
+void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t n_views, float scale, float depth_tol, float min_length,
+                     float** lines_out, int64_t* offsets_out);
+void mesh_view_items(int device, const fdcm_mesh* m, const float* view, float scale, int32_t* box_out, uint64_t* keys_out, int64_t capacity);
 // implemented in fdcm_build.hip
 void ensure_stream(fdcm_featuremap* fm);  // the handle's stream and timing events, made on first use (on fm's device)
 BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after);  // from the plan's shape and counts
@@ -367,7 +387,8 @@ void launch_coldesc_labels(hipStream_t st, const uint8_t* labels, int width, int
 struct PixelScratch {
     // edge_labels_host: pixels, keys, labels, and comps for the edge kernels' parent and root words.  lines_from_labels_host:
     // pixels (the labels), parent (both partitions), counts, comps (the components' sums), out.  lines_from_image_host: all of
-    // them; comps serves the edge kernels first and the components' sums afterwards.
+    // them; comps serves the edge kernels first and the components' sums afterwards.  The mesh's view calls (fdcm_mesh.hip):
+    // keys (views, mesh tables, view records), comps (boxes), pixels (item buffers), parent (large faces), counts, out.
     DevBuf pixels, labels, keys, parent, counts, comps, out;
     ~PixelScratch();
     // reserve of a member: under FDCM_POISON a member that this allocated holds the word throughout, by a fill on the null

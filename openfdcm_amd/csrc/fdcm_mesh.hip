@@ -1,0 +1,514 @@
+// fdcm_mesh.hip -- line templates from a triangle mesh on gfx950 (include/fdcm.h, "Templates from a mesh"): per view the visible
+// sharp edges and occluding contours, as float line segments.
+//
+//   mesh_create        host: the edge table (sorted vertex pairs, their one or two faces) and the sharp flags in float64
+//   k_mesh_boxes       a thread per (view, vertex): the view's pixel box by wave reductions and four integer atomics per wave
+//   k_mesh_raster      16 lanes per (view, face): the face's box in 4 x 4 pixel tiles, one 64-bit atomicMax per covered
+//                      centre; a face of more than kSmallTiles tiles goes onto the part's list instead
+//   k_mesh_raster_big  the list: a workgroup per (entry, slice), 16 x 16 pixel tiles, so that one face of 2000 pixels is
+//                      spread over kBigSlices workgroups
+//   k_mesh_edges<0>    a lane per (view, edge): candidate test, the walk along the samples, the lines counted; per 256 edges a sum
+//   k_mesh_scan        exclusive scan of the sums in place (one workgroup), the total behind them
+//   k_mesh_edges<1>    the same walk, the lines written at their positions, in runs of views whose lines fit 256 MB
+// Nothing stores a projection: every kernel projects the vertices it reads with mesh_project, the one statement of the view, so
+// the passes agree to the bit and a part of the views costs its item buffers, counts and list alone.
+// Bounds: a face's box lies in its view's box (both are floors of the same projected values), and every access of the item
+// buffer tests the pixel against the view's box all the same; a list entry is below the part's views times F, the list's size;
+// counts and sums are indexed by (view, block) below the grid's size; a line's position is below the total the host read back.
+#include <algorithm>
+#include <cmath>
+#include <memory>
+
+#include "fdcm_internal.h"
+
+namespace fdcm {
+
+static constexpr int kSmallTiles = 64;     // 4 x 4 tiles a 16-lane group walks itself (a box of 32 x 32 pixels, or 256 x 4)
+static constexpr int kBigSlices = 16;      // workgroups a listed face is spread over
+static constexpr int kBigGrid = 2048;      // workgroups of k_mesh_raster_big, which strides over (entry, slice)
+static constexpr size_t kMeshPartBytes = (size_t)512 << 20;  // item buffers, list and counts of a part of the views
+static constexpr size_t kMeshWriteBytes = (size_t)256 << 20; // lines of one writing pass (a view's own lines whatever they take)
+static constexpr int kMeshMaxSpan = 4096;
+static constexpr float kMeshMaxCoord = 1073741824.f;  // 2^30
+
+struct MeshView { int32_t x0, y0, w, h; long long off; };  // the view's box and where its item buffer begins in the part's (keys)
+struct MeshPoint { float X, Y, Z; };
+
+__device__ __forceinline__ MeshPoint mesh_project(const float* __restrict__ R, float scale, const float* __restrict__ v) {
+    const float x = v[0], y = v[1], z = v[2];
+    MeshPoint p;
+    p.X = scale * ((R[0] * x + R[1] * y) + R[2] * z);
+    p.Y = scale * ((R[3] * x + R[4] * y) + R[5] * z);
+    p.Z = (R[6] * x + R[7] * y) + R[8] * z;
+    return p;
+}
+__device__ __forceinline__ float mesh_orient(float ax, float ay, float bx, float by, float cx, float cy) {
+    return (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
+}
+__device__ __forceinline__ unsigned mesh_ord(float z) {
+    const unsigned u = __float_as_uint(z);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// A projected face: whether it covers the point (x, y) and its depth there.
+struct MeshFace {
+    MeshPoint A, B, C;
+    float a;
+    __device__ __forceinline__ bool solid() const { return a > 0.f || a < 0.f; }  // (neither for a NaN)
+    __device__ __forceinline__ bool depth(float x, float y, float& z) const {
+        const float e0 = mesh_orient(B.X, B.Y, C.X, C.Y, x, y), e1 = mesh_orient(C.X, C.Y, A.X, A.Y, x, y),
+                    e2 = mesh_orient(A.X, A.Y, B.X, B.Y, x, y);
+        z = ((e0 * A.Z + e1 * B.Z) + e2 * C.Z) / a;
+        return a > 0.f ? (e0 >= 0.f && e1 >= 0.f && e2 >= 0.f) : (a < 0.f && e0 <= 0.f && e1 <= 0.f && e2 <= 0.f);
+    }
+};
+__device__ __forceinline__ MeshFace mesh_face(const float* __restrict__ R, float scale, const float* __restrict__ verts,
+                                              const int32_t* __restrict__ faces, int f) {
+    MeshFace t;
+    t.A = mesh_project(R, scale, verts + 3 * (size_t)faces[3 * (size_t)f]);
+    t.B = mesh_project(R, scale, verts + 3 * (size_t)faces[3 * (size_t)f + 1]);
+    t.C = mesh_project(R, scale, verts + 3 * (size_t)faces[3 * (size_t)f + 2]);
+    t.a = mesh_orient(t.A.X, t.A.Y, t.B.X, t.B.Y, t.C.X, t.C.Y);
+    return t;
+}
+struct MeshBox { int i0, j0, i1, j1; };
+__device__ __forceinline__ MeshBox mesh_face_box(const MeshFace& t) {  // (the views that reach a raster pass have |X|, |Y| < 2^30)
+    MeshBox b;
+    b.i0 = (int)floorf(fminf(fminf(t.A.X, t.B.X), t.C.X)); b.i1 = (int)floorf(fmaxf(fmaxf(t.A.X, t.B.X), t.C.X));
+    b.j0 = (int)floorf(fminf(fminf(t.A.Y, t.B.Y), t.C.Y)); b.j1 = (int)floorf(fmaxf(fmaxf(t.A.Y, t.B.Y), t.C.Y));
+    return b;
+}
+// the face's key into pixel (i, j) of the view's item buffer, where it covers the centre
+__device__ __forceinline__ void mesh_shade(const MeshFace& t, int f, const MeshView& d, unsigned long long* __restrict__ items, int i, int j) {
+    const unsigned ui = (unsigned)(i - d.x0), uj = (unsigned)(j - d.y0);
+    if (ui >= (unsigned)d.w || uj >= (unsigned)d.h) return;
+    float z;
+    if (!t.depth((float)i + 0.5f, (float)j + 0.5f, z) || z != z) return;
+    atomicMax(items + d.off + (long long)uj * d.w + ui, ((unsigned long long)mesh_ord(z) << 32) | (unsigned)f);
+}
+
+// ------------------------------------------------------------------------------------------ projection pass
+// boxes: 4 ints per view, x0 y0 x1 y1, from (INT_MAX, INT_MAX, INT_MIN, INT_MIN).  A coordinate that is not below 2^30 in
+// magnitude (a NaN too) makes the box span everything, which the host refuses like any box above 4096.
+__global__ void __launch_bounds__(256) k_mesh_boxes(const float* __restrict__ verts, int V, int nbV, const float* __restrict__ views,
+                                                    float scale, int32_t* boxes) {
+    const int view = blockIdx.x / nbV, v = (blockIdx.x % nbV) * 256 + threadIdx.x;
+    int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
+    if (v < V) {
+        const MeshPoint p = mesh_project(views + 9 * (size_t)view, scale, verts + 3 * (size_t)v);
+        if (fabsf(p.X) < kMeshMaxCoord && fabsf(p.Y) < kMeshMaxCoord) {
+            x0 = x1 = (int)floorf(p.X);
+            y0 = y1 = (int)floorf(p.Y);
+        } else {
+            x0 = y0 = INT32_MIN; x1 = y1 = INT32_MAX;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        x0 = min(x0, __shfl_xor(x0, d)); y0 = min(y0, __shfl_xor(y0, d));
+        x1 = max(x1, __shfl_xor(x1, d)); y1 = max(y1, __shfl_xor(y1, d));
+    }
+    if ((threadIdx.x & 63) == 0 && x0 <= x1) {  // (a wave past V holds no vertex)
+        int32_t* b = boxes + 4 * (size_t)view;
+        atomicMin(b, x0); atomicMin(b + 1, y0); atomicMax(b + 2, x1); atomicMax(b + 3, y1);
+    }
+}
+
+// ------------------------------------------------------------------------------------------ raster pass
+// views, descs: the part's.  list: its count in the first 8 bytes, then (view in the part, face) pairs.
+__global__ void __launch_bounds__(256) k_mesh_raster(const float* __restrict__ verts, const int32_t* __restrict__ faces, int F, int nbF,
+                                                     const float* __restrict__ views, float scale, const MeshView* __restrict__ descs,
+                                                     unsigned long long* __restrict__ items, unsigned long long* list) {
+    const int view = blockIdx.x / nbF, f = (blockIdx.x % nbF) * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
+    if (f >= F) return;
+    const MeshFace t = mesh_face(views + 9 * (size_t)view, scale, verts, faces, f);
+    if (!t.solid()) return;
+    const MeshBox b = mesh_face_box(t);
+    const int tx = ((b.i1 - b.i0) >> 2) + 1, ty = ((b.j1 - b.j0) >> 2) + 1;  // (a view's box spans 4096 at most: 1024 x 1024 tiles)
+    const int tiles = tx * ty;
+    if (tiles > kSmallTiles) {
+        if (l == 0) {
+            const unsigned long long at = atomicAdd(list, 1ull);
+            reinterpret_cast<int2*>(list + 1)[at] = make_int2(view, f);
+        }
+        return;
+    }
+    const MeshView d = descs[view];
+    for (int k = 0; k < tiles; ++k) {
+        const int i = b.i0 + (k % tx) * 4 + (l & 3), j = b.j0 + (k / tx) * 4 + (l >> 2);
+        if (i <= b.i1 && j <= b.j1) mesh_shade(t, f, d, items, i, j);
+    }
+}
+__global__ void __launch_bounds__(256) k_mesh_raster_big(const float* __restrict__ verts, const int32_t* __restrict__ faces,
+                                                         const float* __restrict__ views, float scale, const MeshView* __restrict__ descs,
+                                                         unsigned long long* __restrict__ items, const unsigned long long* __restrict__ list) {
+    const long long units = (long long)list[0] * kBigSlices;
+    const int2* entries = reinterpret_cast<const int2*>(list + 1);
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const int2 en = entries[u / kBigSlices];
+        const MeshFace t = mesh_face(views + 9 * (size_t)en.x, scale, verts, faces, en.y);
+        const MeshBox b = mesh_face_box(t);
+        const MeshView d = descs[en.x];
+        const int tx = ((b.i1 - b.i0) >> 4) + 1, ty = ((b.j1 - b.j0) >> 4) + 1;
+        for (int k = (int)(u % kBigSlices); k < tx * ty; k += kBigSlices) {
+            const int i = b.i0 + (k % tx) * 16 + (threadIdx.x & 15), j = b.j0 + (k / tx) * 16 + (threadIdx.x >> 4);
+            if (i <= b.i1 && j <= b.j1) mesh_shade(t, en.y, d, items, i, j);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------ edge pass
+// exclusive prefix of v over the 256 threads of a workgroup and their total (`sw`: 4 words of LDS; a barrier inside)
+__device__ __forceinline__ int mesh_block_scan(int v, int tid, int* sw, int& total) {
+    const int lane = tid & 63, wave = tid >> 6;
+    int incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(incl, d);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) sw[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int s = sw[k];
+        if (k < wave) before += s;
+        total += s;
+    }
+    return before + incl - v;
+}
+struct MeshEdgeArgs {
+    const float* verts;
+    const int32_t* faces;
+    const int4* edges;      // i, j, f0, f1 (-1: none)
+    const uint8_t* sharp;
+    int E, nbE;
+    const float* views;     // the part's
+    float scale, depth_tol, min_length;
+    const MeshView* descs;
+    const unsigned long long* items;
+    int* counts;            // per (view, block, thread)
+    long long* sums;        // per (view, block); scanned before the writing pass
+    float4* out;            // the writing pass: the lines of the blocks from block0 on, the first of them at out[0]
+    int block0;
+    long long out0;         // sums[block0]
+};
+// The vertex of face f opposite the edge (i, j): the one index that is neither.  (For a face that names a vertex twice this is
+// not the header's "index at the position the pair leaves out" -- but such a face has no normal, so its edges are sharp and
+// the walk never asks for their opposite vertices: mesh_create's flags are what makes the shortcut safe.)
+__device__ __forceinline__ int mesh_opposite(const int32_t* __restrict__ faces, int f, int i, int j) {
+    const int p0 = faces[3 * (size_t)f], p1 = faces[3 * (size_t)f + 1], p2 = faces[3 * (size_t)f + 2];
+    return p0 != i && p0 != j ? p0 : (p1 != i && p1 != j ? p1 : p2);
+}
+// the lines of edge e in the view: counted, and with WRITE stored from out[at] on
+template <bool WRITE>
+__device__ __forceinline__ int mesh_walk(const MeshEdgeArgs& g, const float* __restrict__ R, const MeshView& d, int e, long long at) {
+    const int4 ed = g.edges[e];
+    const MeshPoint A = mesh_project(R, g.scale, g.verts + 3 * (size_t)ed.x), B = mesh_project(R, g.scale, g.verts + 3 * (size_t)ed.y);
+    if (!g.sharp[e]) {
+        const MeshPoint c0 = mesh_project(R, g.scale, g.verts + 3 * (size_t)mesh_opposite(g.faces, ed.z, ed.x, ed.y));
+        const MeshPoint c1 = mesh_project(R, g.scale, g.verts + 3 * (size_t)mesh_opposite(g.faces, ed.w, ed.x, ed.y));
+        const float o0 = mesh_orient(A.X, A.Y, B.X, B.Y, c0.X, c0.Y), o1 = mesh_orient(A.X, A.Y, B.X, B.Y, c1.X, c1.Y);
+        if ((o0 > 0.f && o1 < 0.f) || (o0 < 0.f && o1 > 0.f)) return 0;
+    }
+    const float dx = B.X - A.X, dy = B.Y - A.Y, dz = B.Z - A.Z;
+    const int n = max(1, (int)ceilf(fmaxf(fabsf(dx), fabsf(dy))));  // (at most 4097: the view's box)
+    const float fn = (float)n;
+    int count = 0, k0 = 0, k1 = 0;
+    bool open = false;
+    float x0 = 0.f, y0 = 0.f, x1 = 0.f, y1 = 0.f;
+    auto close = [&] {
+        if (k1 > k0) {
+            const float ddx = x1 - x0, ddy = y1 - y0;
+            const float len = sqrtf(ddx * ddx + ddy * ddy);
+            if (len > 0.f && len >= g.min_length) {
+                if (WRITE) g.out[at + count] = make_float4(x0, y0, x1, y1);
+                ++count;
+            }
+        }
+        open = false;
+    };
+    for (int k = 0; k <= n; ++k) {
+        const float t = (float)k / fn;
+        const float sx = A.X + t * dx, sy = A.Y + t * dy, sz = A.Z + t * dz;
+        const unsigned ui = (unsigned)((int)floorf(sx) - d.x0), uj = (unsigned)((int)floorf(sy) - d.y0);
+        bool vis = true;
+        if (ui < (unsigned)d.w && uj < (unsigned)d.h) {
+            const unsigned long long key = g.items[d.off + (long long)uj * d.w + ui];
+            const int f = (int)(unsigned)key;
+            if (key != 0 && f != ed.z && f != ed.w) {
+                const MeshFace occ = mesh_face(R, g.scale, g.verts, g.faces, f);
+                float zf;
+                (void)occ.depth(sx, sy, zf);
+                vis = sz + g.depth_tol >= zf;
+            }
+        }
+        if (vis) {
+            if (!open) { open = true; k0 = k; x0 = sx; y0 = sy; }
+            k1 = k; x1 = sx; y1 = sy;
+        } else if (open) {
+            close();
+        }
+    }
+    if (open) close();
+    return count;
+}
+template <bool WRITE>
+__global__ void __launch_bounds__(256) k_mesh_edges(MeshEdgeArgs g) {
+    __shared__ int sw[4];
+    const int block = (WRITE ? g.block0 : 0) + (int)blockIdx.x;
+    const int view = block / g.nbE, e = (block % g.nbE) * 256 + threadIdx.x;
+    const size_t slot = (size_t)block * 256 + threadIdx.x;
+    int total;
+    if (!WRITE) {
+        const int c = e < g.E ? mesh_walk<false>(g, g.views + 9 * (size_t)view, g.descs[view], e, 0) : 0;
+        g.counts[slot] = c;
+        mesh_block_scan(c, threadIdx.x, sw, total);
+        if (threadIdx.x == 0) g.sums[block] = total;
+    } else {
+        const int c = g.counts[slot];
+        const long long at = g.sums[block] - g.out0 + mesh_block_scan(c, threadIdx.x, sw, total);
+        if (c) mesh_walk<true>(g, g.views + 9 * (size_t)view, g.descs[view], e, at);
+    }
+}
+// sums[0 .. nb) -> their exclusive prefix sums in place, sums[nb] = the total (a block's sum is below 2^20: 256 edges of at most
+// 2049 lines)
+__global__ void __launch_bounds__(256) k_mesh_scan(long long* sums, int nb) {
+    __shared__ int sw[4];
+    const int tid = threadIdx.x;
+    long long carry = 0;
+    for (int base = 0; base < nb; base += 256) {
+        const int i = base + tid;
+        const int v = i < nb ? (int)sums[i] : 0;
+        int total;
+        const int ex = mesh_block_scan(v, tid, sw, total);
+        if (i < nb) sums[i] = carry + ex;
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) sums[nb] = carry;
+}
+
+// ------------------------------------------------------------------------------------------ host: the mesh
+namespace {
+struct Incidence { uint64_t pair; int32_t face; };
+void face_normal(const float* v, const int32_t* tri, double n[3]) {
+    const float *p0 = v + 3 * (size_t)tri[0], *p1 = v + 3 * (size_t)tri[1], *p2 = v + 3 * (size_t)tri[2];
+    const double u[3] = {(double)p1[0] - p0[0], (double)p1[1] - p0[1], (double)p1[2] - p0[2]};
+    const double w[3] = {(double)p2[0] - p0[0], (double)p2[1] - p0[1], (double)p2[2] - p0[2]};
+    n[0] = u[1] * w[2] - u[2] * w[1]; n[1] = u[2] * w[0] - u[0] * w[2]; n[2] = u[0] * w[1] - u[1] * w[0];
+}
+double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+}  // namespace
+
+fdcm_mesh* mesh_create(const float* vertices, int64_t V, const int32_t* faces, int64_t F, double crease_cos) {
+    for (int64_t i = 0; i < 3 * V; ++i)
+        if (!std::isfinite(vertices[i])) throw std::string("vertex " + std::to_string(i / 3) + " is not finite");
+    for (int64_t i = 0; i < 3 * F; ++i)
+        if (faces[i] < 0 || faces[i] >= V) throw std::string("face " + std::to_string(i / 3) + " has an index outside 0 .. n_vertices - 1");
+    std::unique_ptr<fdcm_mesh> m(new fdcm_mesh);
+    m->V = V; m->F = F;
+    m->vertices.assign(vertices, vertices + 3 * V);
+    m->faces.assign(faces, faces + 3 * F);
+    std::vector<Incidence> inc;
+    inc.reserve((size_t)3 * F);
+    for (int64_t f = 0; f < F; ++f) {
+        const int32_t* t = faces + 3 * f;
+        uint64_t seen[3];
+        int ns = 0;
+        for (int k = 0; k < 3; ++k) {
+            const int32_t a = t[k], b = t[(k + 1) % 3];
+            if (a == b) continue;
+            const uint64_t pair = ((uint64_t)std::min(a, b) << 32) | (uint64_t)std::max(a, b);
+            if (std::find(seen, seen + ns, pair) != seen + ns) continue;
+            seen[ns++] = pair;
+            inc.push_back({pair, (int32_t)f});
+        }
+    }
+    std::sort(inc.begin(), inc.end(), [](const Incidence& a, const Incidence& b) { return a.pair != b.pair ? a.pair < b.pair : a.face < b.face; });
+    for (size_t i = 0; i < inc.size();) {
+        size_t j = i;
+        while (j < inc.size() && inc[j].pair == inc[i].pair) ++j;
+        const int32_t a = (int32_t)(inc[i].pair >> 32), b = (int32_t)(inc[i].pair & 0xffffffffu);
+        if (j - i > 2)
+            throw std::string("non-manifold edge (" + std::to_string(a) + ", " + std::to_string(b) + "): " + std::to_string(j - i) + " faces");
+        const int32_t f0 = inc[i].face, f1 = j - i == 2 ? inc[i + 1].face : -1;
+        bool sharp = f1 < 0;
+        if (sharp) {
+            ++m->n_boundary;
+        } else {
+            double n0[3], n1[3];
+            face_normal(vertices, faces + 3 * (size_t)f0, n0);
+            face_normal(vertices, faces + 3 * (size_t)f1, n1);
+            const bool zero0 = n0[0] == 0 && n0[1] == 0 && n0[2] == 0, zero1 = n1[0] == 0 && n1[1] == 0 && n1[2] == 0;
+            sharp = zero0 || zero1 || std::fabs(dot3(n0, n1)) < (crease_cos * std::sqrt(dot3(n0, n0))) * std::sqrt(dot3(n1, n1));
+        }
+        m->edges.insert(m->edges.end(), {a, b, f0, f1});
+        m->sharp.push_back(sharp ? 1 : 0);
+        m->n_sharp += sharp;
+        i = j;
+    }
+    m->E = (int64_t)m->sharp.size();
+    return m.release();
+}
+
+// ------------------------------------------------------------------------------------------ host: the views
+namespace {
+size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+// What a call holds on the device, in PixelScratch's members: keys -- the views, the mesh's tables and the part's view
+// records; comps -- the boxes; pixels -- the part's item buffers; parent -- its list of large faces; counts -- its per-edge
+// counts and block sums; out -- its lines.
+struct MeshDevice {
+    PixelScratch s;
+    const fdcm_mesh* m;
+    int64_t n_views;
+    float scale;
+    const float *views, *verts;
+    const int32_t* faces;
+    const int4* edges;
+    const uint8_t* sharp;
+    MeshView* descs;
+    std::vector<int32_t> boxes;  // 4 per view, checked
+    int nbE() const { return (int)((m->E + 255) / 256); }
+    int nbF() const { return (int)((m->F + 15) / 16); }
+
+    // uploads the mesh and the views, runs the projection pass and refuses the views it must
+    MeshDevice(const fdcm_mesh* mesh, const float* host_views, int64_t n, float sc) : m(mesh), n_views(n), scale(sc) {
+        const size_t o_views = 0, o_verts = align16((size_t)n * 36), o_faces = align16(o_verts + (size_t)m->V * 12),
+                     o_edges = align16(o_faces + (size_t)m->F * 12), o_sharp = o_edges + (size_t)m->E * 16,
+                     o_descs = align16(o_sharp + (size_t)m->E), bytes = o_descs + (size_t)n * sizeof(MeshView);
+        s.take(s.keys, bytes, FDCM_FILL_PIXEL_KEYS);
+        char* base = (char*)s.keys.p;
+        FDCM_HIP(hipMemcpy(base + o_views, host_views, (size_t)n * 36, hipMemcpyHostToDevice));
+        FDCM_HIP(hipMemcpy(base + o_verts, m->vertices.data(), (size_t)m->V * 12, hipMemcpyHostToDevice));
+        FDCM_HIP(hipMemcpy(base + o_faces, m->faces.data(), (size_t)m->F * 12, hipMemcpyHostToDevice));
+        FDCM_HIP(hipMemcpy(base + o_edges, m->edges.data(), (size_t)m->E * 16, hipMemcpyHostToDevice));
+        FDCM_HIP(hipMemcpy(base + o_sharp, m->sharp.data(), (size_t)m->E, hipMemcpyHostToDevice));
+        views = (const float*)(base + o_views); verts = (const float*)(base + o_verts); faces = (const int32_t*)(base + o_faces);
+        edges = (const int4*)(base + o_edges); sharp = (const uint8_t*)(base + o_sharp); descs = (MeshView*)(base + o_descs);
+        boxes.resize((size_t)4 * n);
+        for (int64_t v = 0; v < n; ++v) { boxes[4 * v] = boxes[4 * v + 1] = INT32_MAX; boxes[4 * v + 2] = boxes[4 * v + 3] = INT32_MIN; }
+        s.take(s.comps, boxes.size() * 4, FDCM_FILL_PIXEL_COMPS);
+        FDCM_HIP(hipMemcpy(s.comps.p, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice));
+        const int nbV = (int)((m->V + 255) / 256);  // (at most 2^14 blocks a view and 2^16 views: one grid)
+        hipLaunchKernelGGL(k_mesh_boxes, dim3((unsigned)(nbV * n)), dim3(256), 0, nullptr, verts, (int)m->V, nbV, views, scale, s.comps.as<int32_t>());
+        FDCM_HIP(hipGetLastError());
+        FDCM_HIP(hipMemcpy(boxes.data(), s.comps.p, boxes.size() * 4, hipMemcpyDeviceToHost));
+        for (int64_t v = 0; v < n; ++v) {
+            const int64_t w = (int64_t)boxes[4 * v + 2] - boxes[4 * v] + 1, h = (int64_t)boxes[4 * v + 3] - boxes[4 * v + 1] + 1;
+            if (w > kMeshMaxSpan || h > kMeshMaxSpan)
+                throw std::string("view " + std::to_string(v) + " spans more than 4096 pixels on a side (or a coordinate is not below 2^30)");
+        }
+    }
+    size_t view_items(int64_t v) const { return (size_t)(boxes[4 * v + 2] - boxes[4 * v] + 1) * (size_t)(boxes[4 * v + 3] - boxes[4 * v + 1] + 1); }
+    size_t view_bytes(int64_t v) const { return view_items(v) * 8 + (size_t)m->F * 8 + (size_t)nbE() * (256 * 4 + 8); }
+    // the views [v0, v0 + P) of one part: at most kMeshPartBytes (one view whatever it takes), FDCM_MESH_PART views at most
+    int64_t part_views(int64_t v0) const {
+        const int forced = test_switches().mesh_part;
+        size_t bytes = 0;
+        int64_t P = 0;
+        while (v0 + P < n_views && (P == 0 || (bytes + view_bytes(v0 + P) <= kMeshPartBytes && (forced == 0 || P < forced)))) bytes += view_bytes(v0 + P++);
+        return P;
+    }
+    // the item buffers of the part, rastered; returns their total of keys
+    size_t raster(int64_t v0, int64_t P) {
+        std::vector<MeshView> d((size_t)P);
+        size_t total = 0;
+        for (int64_t i = 0; i < P; ++i) {
+            const int32_t* b = &boxes[4 * (v0 + i)];
+            d[i] = MeshView{b[0], b[1], b[2] - b[0] + 1, b[3] - b[1] + 1, (long long)total};
+            total += view_items(v0 + i);
+        }
+        s.take(s.pixels, total * 8, FDCM_FILL_PIXEL_PIXELS);
+        s.take(s.parent, 8 + (size_t)P * (size_t)m->F * 8, FDCM_FILL_PIXEL_PARENT);
+        FDCM_HIP(hipMemcpy(descs, d.data(), (size_t)P * sizeof(MeshView), hipMemcpyHostToDevice));
+        FDCM_HIP(hipMemsetAsync(s.pixels.p, 0, total * 8, nullptr));
+        FDCM_HIP(hipMemsetAsync(s.parent.p, 0, 8, nullptr));
+        const float* pv = views + 9 * (size_t)v0;
+        hipLaunchKernelGGL(k_mesh_raster, dim3((unsigned)(P * nbF())), dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF(), pv, scale,
+                           (const MeshView*)descs, s.pixels.as<unsigned long long>(), s.parent.as<unsigned long long>());
+        hipLaunchKernelGGL(k_mesh_raster_big, dim3(kBigGrid), dim3(256), 0, nullptr, verts, faces, pv, scale, (const MeshView*)descs,
+                           s.pixels.as<unsigned long long>(), (const unsigned long long*)s.parent.as<unsigned long long>());
+        FDCM_HIP(hipGetLastError());
+        return total;
+    }
+};
+struct HostLines {  // the call's lines until they are the caller's
+    float* p = nullptr;
+    ~HostLines() { std::free(p); }
+    void grow(size_t lines) {
+        float* q = (float*)std::realloc(p, std::max<size_t>(1, lines) * 16);
+        if (!q) throw std::bad_alloc();
+        p = q;
+    }
+};
+}  // namespace
+
+void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t n_views, float scale, float depth_tol, float min_length,
+                     float** lines_out, int64_t* offsets_out) {
+    FDCM_HIP(hipSetDevice(device));
+    MeshDevice dev(m, views, n_views, scale);
+    HostLines host;
+    std::vector<int64_t> offsets((size_t)n_views + 1, 0);
+    std::vector<long long> view_at;
+    int64_t done = 0;
+    const int nbE = dev.nbE();
+    for (int64_t v0 = 0; v0 < n_views;) {
+        const int64_t P = dev.part_views(v0);
+        dev.raster(v0, P);
+        const int nb = (int)(P * nbE);
+        dev.s.take(dev.s.counts, (size_t)nb * 256 * 4 + ((size_t)nb + 1) * 8, FDCM_FILL_PIXEL_COUNTS);
+        MeshEdgeArgs g;
+        g.verts = dev.verts; g.faces = dev.faces; g.edges = dev.edges; g.sharp = dev.sharp; g.E = (int)m->E; g.nbE = nbE;
+        g.views = dev.views + 9 * (size_t)v0; g.scale = scale; g.depth_tol = depth_tol; g.min_length = min_length;
+        g.descs = dev.descs; g.items = dev.s.pixels.as<unsigned long long>();
+        g.sums = dev.s.counts.as<long long>(); g.counts = (int*)(g.sums + nb + 1); g.out = nullptr; g.block0 = 0; g.out0 = 0;
+        hipLaunchKernelGGL(k_mesh_edges<false>, dim3((unsigned)nb), dim3(256), 0, nullptr, g);
+        hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(256), 0, nullptr, g.sums, nb);
+        FDCM_HIP(hipGetLastError());
+        // where each view of the part begins among its lines, and their total
+        view_at.assign((size_t)P + 1, 0);
+        FDCM_HIP(hipMemcpy2D(view_at.data(), 8, g.sums, (size_t)nbE * 8, 8, (size_t)P, hipMemcpyDeviceToHost));
+        FDCM_HIP(hipMemcpy(&view_at[(size_t)P], g.sums + nb, 8, hipMemcpyDeviceToHost));
+        const long long total = view_at[(size_t)P];
+        if (done + total >= ((int64_t)1 << 31)) throw std::string("the views give 2^31 lines or more");
+        for (int64_t i = 0; i < P; ++i) offsets[(size_t)(v0 + i)] = done + view_at[(size_t)i];
+        if (total > 0) host.grow((size_t)(done + total));
+        // the writing passes: runs of the part's views whose lines fit kMeshWriteBytes (FDCM_MESH_PART = N: 16 N lines), a view
+        // with more than that on its own, so that `out` is bounded like the part's other buffers
+        const int forced = test_switches().mesh_part;
+        const long long room = forced ? 16ll * forced : (long long)(kMeshWriteBytes / 16);
+        for (int64_t a = 0; a < P && total > 0;) {
+            int64_t b = a + 1;
+            while (b < P && view_at[(size_t)b + 1] - view_at[(size_t)a] <= room) ++b;
+            const long long lines = view_at[(size_t)b] - view_at[(size_t)a];
+            if (lines > 0) {
+                dev.s.take(dev.s.out, (size_t)lines * 16, FDCM_FILL_PIXEL_OUT);
+                g.out = dev.s.out.as<float4>(); g.block0 = (int)(a * nbE); g.out0 = view_at[(size_t)a];
+                hipLaunchKernelGGL(k_mesh_edges<true>, dim3((unsigned)((b - a) * nbE)), dim3(256), 0, nullptr, g);
+                FDCM_HIP(hipGetLastError());
+                FDCM_HIP(hipMemcpy(host.p + 4 * (size_t)(done + view_at[(size_t)a]), dev.s.out.p, (size_t)lines * 16, hipMemcpyDeviceToHost));
+            }
+            a = b;
+        }
+        done += total;
+        v0 += P;
+    }
+    offsets[(size_t)n_views] = done;
+    std::copy(offsets.begin(), offsets.end(), offsets_out);
+    if (done > 0) { *lines_out = host.p; host.p = nullptr; }
+}
+
+void mesh_view_items(int device, const fdcm_mesh* m, const float* view, float scale, int32_t* box_out, uint64_t* keys_out, int64_t capacity) {
+    FDCM_HIP(hipSetDevice(device));
+    MeshDevice dev(m, view, 1, scale);
+    std::copy(dev.boxes.begin(), dev.boxes.end(), box_out);
+    if (!keys_out) return;
+    if ((int64_t)dev.view_items(0) > capacity)
+        throw std::string("keys_out holds " + std::to_string(capacity) + " keys, the view's box has " + std::to_string(dev.view_items(0)));
+    const size_t total = dev.raster(0, 1);
+    FDCM_HIP(hipMemcpy(keys_out, dev.s.pixels.p, total * 8, hipMemcpyDeviceToHost));
+}
+
+}  // namespace fdcm

@@ -1199,6 +1199,138 @@ def lines_last_timing():
     return {name: getattr(t, name) for name, _ in capi.LinesTiming._fields_}
 
 
+class Mesh:
+    """A triangle mesh with its edge table (include/fdcm.h, "Templates from a mesh"): `vertices` (V, 3) float32, `faces` (F, 3)
+    int32, and the crease angle above which an edge between two faces is sharp.  Host memory alone: making one needs no device."""
+
+    def __init__(self, vertices, faces, crease_angle=np.deg2rad(30)):
+        v = np.ascontiguousarray(vertices, dtype=np.float32)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"expected (V, 3) vertices and (F, 3) faces, got {v.shape} and {f.shape}")
+        self.vertices, self.faces = v, f
+        self._h = C.c_void_p()
+        capi.check(capi.lib().fdcm_mesh_create(capi.fptr(v), v.shape[0], f.ctypes.data_as(C.POINTER(C.c_int32)), f.shape[0],
+                                               float(np.cos(crease_angle)), C.byref(self._h)))
+        ne, ns, nb = C.c_int64(), C.c_int64(), C.c_int64()
+        capi.check(capi.lib().fdcm_mesh_info(self._h, C.byref(ne), C.byref(ns), C.byref(nb)))
+        self.n_edges, self.n_sharp, self.n_boundary = ne.value, ns.value, nb.value
+
+    def edges(self):
+        """(verts (E, 2) int32 with i < j, faces (E, 2) int32 with -1 for none, sharp (E,) uint8), in edge order."""
+        verts, faces = np.empty((self.n_edges, 2), dtype=np.int32), np.empty((self.n_edges, 2), dtype=np.int32)
+        sharp = np.empty(self.n_edges, dtype=np.uint8)
+        i32 = C.POINTER(C.c_int32)
+        capi.check(capi.lib().fdcm_mesh_edges(self._h, verts.ctypes.data_as(i32), faces.ctypes.data_as(i32),
+                                              sharp.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return verts, faces, sharp
+
+    def default_depth_tolerance(self):
+        """float32(1e-4 * the diagonal of the vertices' bounding box)."""
+        d = self.vertices.astype(np.float64).max(axis=0) - self.vertices.astype(np.float64).min(axis=0)
+        return np.float32(1e-4 * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))
+
+    def close(self):
+        if self._h:
+            capi.lib().fdcm_mesh_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _views(views):
+    r = np.ascontiguousarray(views, dtype=np.float32)
+    if r.ndim == 2 and r.shape == (3, 3):
+        r = r[None]
+    if r.ndim != 3 or r.shape[1:] != (3, 3):
+        raise ValueError(f"views must be (n, 3, 3), got {r.shape}")
+    return r
+
+
+def mesh_view_lines(mesh, views, scale, depth_tolerance=None, min_length=2.0):
+    """fdcm_mesh_view_lines as it is: ((N, 4) float32 line records of all views, int64 offsets of n_views + 1)."""
+    r = _views(views)
+    tol = mesh.default_depth_tolerance() if depth_tolerance is None else depth_tolerance
+    offsets = np.zeros(r.shape[0] + 1, dtype=np.int64)
+    out = C.POINTER(C.c_float)()
+    capi.check(capi.lib().fdcm_mesh_view_lines(mesh._h, capi.fptr(r), r.shape[0], float(scale), float(tol), float(min_length),
+                                               C.byref(out), offsets.ctypes.data_as(C.POINTER(C.c_int64))))
+    n = int(offsets[-1])
+    try:
+        rec = np.ctypeslib.as_array(out, shape=(n, 4)).copy() if n else np.zeros((0, 4), dtype=np.float32)
+    finally:
+        if out:
+            capi.lib().fdcm_lines_free(out)
+    return rec, offsets
+
+
+def templates_from_mesh(mesh, views, scale, depth_tolerance=None, min_length=2.0):
+    """The line template of every view of a mesh, computed on the GPU (include/fdcm.h, "Templates from a mesh"): a list of (4, N)
+    float32 arrays, template t being view t, with the projection of the mesh origin at (0, 0).  views: (n, 3, 3) rotations
+    (view_rotations makes them); scale: pixels per mesh unit; depth_tolerance: mesh units, None for 1e-4 of the bounding box's
+    diagonal; min_length: the shortest line kept, in pixels.  Orthographic."""
+    rec, offsets = mesh_view_lines(mesh, views, scale, depth_tolerance, min_length)
+    return [np.ascontiguousarray(rec[offsets[i]:offsets[i + 1]].T) for i in range(len(offsets) - 1)]
+
+
+def mesh_view_items(mesh, view, scale):
+    """Test hook (fdcm_mesh_view_items): one view's pixel box (x0, y0, x1, y1) and its item buffer, (rows, columns) uint64."""
+    r = _views(view)
+    if r.shape[0] != 1:
+        raise ValueError("one view")
+    box = np.zeros(4, dtype=np.int32)
+    i32 = C.POINTER(C.c_int32)
+    capi.check(capi.lib().fdcm_mesh_view_items(mesh._h, capi.fptr(r), float(scale), box.ctypes.data_as(i32), None, 0))
+    w, h = int(box[2]) - int(box[0]) + 1, int(box[3]) - int(box[1]) + 1
+    keys = np.empty((h, w), dtype=np.uint64)
+    capi.check(capi.lib().fdcm_mesh_view_items(mesh._h, capi.fptr(r), float(scale), box.ctypes.data_as(i32),
+                                               keys.ctypes.data_as(C.POINTER(C.c_uint64)), keys.size))
+    return tuple(int(b) for b in box), keys
+
+
+def view_rotations(n, hemisphere=True):
+    """n view rotations, (n, 3, 3) float32, pure numpy.  The directions d_k towards the viewer lie on a Fibonacci spiral:
+    z_k = 1 - (k + 0.5) / n (hemisphere: 0 < z <= 1) or 1 - (2 k + 1) / n (the sphere), at the azimuth k * pi * (3 - sqrt(5)).
+    View k is the matrix with the rows (x, y, d_k): it turns d_k onto +Z.  The in-plane axis is fixed by x = (-d.y, d.x, 0) /
+    |(d.x, d.y)|, the horizontal direction at right angles to d -- (1, 0, 0) where d is within 1e-9 of the pole -- and
+    y = d x x, so the determinant is +1.  In-plane rotation is what `angles=` and search() cover."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    k = np.arange(n, dtype=np.float64)
+    z = 1.0 - (k + 0.5) / n if hemisphere else 1.0 - (2.0 * k + 1.0) / n
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+    x = np.stack([-d[:, 1], d[:, 0], np.zeros(n)], axis=1)
+    norm = np.hypot(x[:, 0], x[:, 1])
+    pole = norm < 1e-9
+    x[~pole] /= norm[~pole, None]
+    x[pole] = (1.0, 0.0, 0.0)
+    y = np.cross(d, x)
+    return np.stack([x, y, d], axis=1).astype(np.float32)
+
+
+def record_rotations(records, views):
+    """Step 5 of the 6-DOF procedure, pure numpy: per match record the (3, 3) float64 rotation Rz(c, s) . views[tmpl_idx] with
+    (c, s) = (transform[0], transform[3]), and the image position (transform[2], transform[5]) of the mesh origin's projection.
+    Returns ((n, 3, 3) float64, (n, 2) float64)."""
+    from .matchlist import records_of
+    rec = records_of(records)
+    v = np.asarray(views, dtype=np.float64).reshape(-1, 3, 3)
+    idx = rec["tmpl_idx"].astype(np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= len(v)):
+        raise ValueError("a record's tmpl_idx is outside the views")
+    tr = rec["transform"].astype(np.float64).reshape(-1, 6)
+    rz = np.zeros((len(rec), 3, 3), dtype=np.float64)
+    rz[:, 0, 0], rz[:, 0, 1], rz[:, 1, 0], rz[:, 1, 1], rz[:, 2, 2] = tr[:, 0], -tr[:, 3], tr[:, 3], tr[:, 0], 1.0
+    return rz @ v[idx], tr[:, [2, 5]].copy()
+
+
 def search_raw(fm, templates, scene, max_tmpl_lines, max_scene_lines, optimizer=capi.BATCH_OPTIMIZE, batch_size=10,
                tmpl_index_base=0):
     """Run the search and return the raw matches as a structured array (capi.MATCH_DTYPE)."""
