@@ -1,7 +1,10 @@
 """The meshes and views of the mesh-template tests, built in code (include/fdcm.h, "Templates from a mesh"): small solids and
 sheets whose visible edges are known from geometry, and scales at which a rasteriser's lane / tile split and the two-pass
 write can go wrong -- triangles that cover no pixel centre or exactly one, vertices on pixel centres (inclusive edges, ties
-by face index), faces of 65 x 65, 256 x 3 and 257 x 3 pixels on either side of the small / large split, and one of 2000."""
+by face index), faces of 65 x 65, 256 x 3 and 257 x 3 pixels (and 3 x 256, 3 x 257) on either side of the small / large split, and
+one of 2000; and meshes past one block per view: a bumped icosphere of 642 vertices (3 vertex blocks, the box set by vertices of
+the later ones), 1280 faces and 1920 edges (8 edge blocks, lines in every one), and a fence whose two long edges are cut into 41
+lines each by the slats in front of them."""
 import numpy as np
 
 COS30 = float(np.cos(np.deg2rad(30.0)))
@@ -96,6 +99,27 @@ def icosphere(subdivisions=2, bump=None):
     return v.astype(np.float32), np.array(f, dtype=np.int32)
 
 
+def bump3(p):
+    return 1.0 + 0.25 * np.sin(5 * p[:, 0]) * np.cos(4 * p[:, 1])
+
+
+def icosphere3_bumped():
+    """642 vertices, 1280 faces, 1920 edges, 80 of them sharp at 30 degrees; concave in places."""
+    return icosphere(3, bump3)
+
+
+def fence(K=40):
+    """An open sheet [0, 3K + 1] x [0, 1] at z = 0 (vertices 0 .. 3, counter-clockwise from (0, 0)) and K slats in front of it,
+    [3k + 1.25, 3k + 2.75] x [-1, 2] at z = 1: the sheet's long edges (0, 1) and (2, 3) show in the K + 1 gaps."""
+    v = [(0, 0, 0), (3 * K + 1, 0, 0), (3 * K + 1, 1, 0), (0, 1, 0)]
+    f = _quad(0, 1, 2, 3)
+    for k in range(K):
+        n = len(v)
+        v += [(3 * k + 1.25, -1, 1), (3 * k + 2.75, -1, 1), (3 * k + 2.75, 2, 1), (3 * k + 1.25, 2, 1)]
+        f += _quad(n, n + 1, n + 2, n + 3)
+    return np.array(v, dtype=np.float32), np.array(f, dtype=np.int32)
+
+
 def roof():
     """Two slopes that meet in the ridge (vertices 0, 1), each quad cut into two triangles: the triangle of a slope that does
     not hold the ridge lies in the plane of the one that does."""
@@ -132,9 +156,13 @@ SIDE = f32(rot("x", 90.0))                      # axis-aligned, the sheets edge-
 GRAZING = f32(rot("x", 90.0 - 26.565 - 2.0))    # two degrees off the roof's far slope (atan(0.5) = 26.565 degrees)
 STRETCH_257 = f32(np.diag([256.5, 2.5, 1.0]))   # not orthonormal: the unit triangle becomes 257 x 3 pixels at scale 1
 STRETCH_256 = f32(np.diag([255.5, 2.5, 1.0]))
+TALL_257 = f32(np.diag([2.5, 256.5, 1.0]))      # 3 x 257 pixels: one column of tiles (tx == 1), 65 of them
+TALL_256 = f32(np.diag([2.5, 255.5, 1.0]))      # 3 x 256: 64 tiles, the most the small path takes
+FENCE_TURNED = f32(rot("z", 17.0))
 
 MESHES = {"cube": cube, "tetrahedron": tetrahedron, "triangle": triangle, "open_square": open_square, "l_prism": l_prism,
-          "occluded_cubes": occluded_cubes, "icosphere": icosphere, "roof": roof, "degenerate": with_degenerate_faces}
+          "occluded_cubes": occluded_cubes, "icosphere": icosphere, "roof": roof, "degenerate": with_degenerate_faces,
+          "icosphere3_bumped": icosphere3_bumped, "fence": fence}
 
 # (name, mesh, views, scale): what the GPU tests compare key for key and byte for byte
 CASES = [
@@ -152,6 +180,10 @@ CASES = [
     ("icosphere-small", "icosphere", [GENERIC], 3.1),             # most faces below a pixel
     ("roof", "roof", [GRAZING, IDENTITY, GENERIC], 60.0),
     ("degenerate", "degenerate", [IDENTITY, GENERIC], 12.5),
+    ("icosphere3_bumped", "icosphere3_bumped", [GENERIC, GENERIC2, IDENTITY], 33.7),   # 3 vertex, 80 face and 8 edge blocks a view
+    ("fence", "fence", [IDENTITY], 8.0),                          # 41 lines on each long edge, a box 969 pixels wide
+    ("fence-turned", "fence", [FENCE_TURNED], 7.3),               # (a case has one scale: the fence's two views are two cases)
+    ("triangle-3x257", "triangle", [TALL_257, TALL_256], 1.0),
 ]
 
 

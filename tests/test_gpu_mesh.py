@@ -1,7 +1,10 @@
 """The mesh templates on the device (include/fdcm.h, "Templates from a mesh") against the referee (tests/mesh_ref.py), byte for
 byte: every view's pixel box and item buffer, the offsets and lines of every case of tests/mesh_cases.py at both least
 lengths, both depth tolerances and three crease angles; lists of views against the views one call each; repeated calls;
-several parts and FDCM_POISON in fresh processes (tools/mesh_probe.py); no views; and the views the call refuses."""
+several parts and FDCM_POISON in fresh processes (tools/mesh_probe.py); no views; and the views the call refuses.  Past one block
+per view and one pass per loop: more than 128 listed faces and more than 256 block sums in one part, a mesh of 3 vertex and 8
+edge blocks in lists and in writing runs that start mid-part, 41 lines on one edge, and parts cut by the 512 MB limit
+(tests/test_mesh_definition.py states on the referee alone that the shapes used here do reach those paths)."""
 import os
 import subprocess
 import sys
@@ -113,6 +116,111 @@ def test_lists_of_views_are_the_views_one_call_each(engine):
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
 
 
+_views_ref = {}
+
+
+def views_ref(mesh_name, n_views, scale, min_length):
+    """MR.views_lines of view_rotations(n_views, hemisphere=False) at the default tolerance, computed once."""
+    key = (mesh_name, n_views, scale, min_length)
+    if key not in _views_ref:
+        from openfdcm_amd.engine import view_rotations
+        v, f = MC.MESHES[mesh_name]()
+        _views_ref[key] = MR.views_lines(MR.Mesh(v, f, MC.COS30), view_rotations(n_views, hemisphere=False), np.float32(scale),
+                                         MR.default_depth_tol(v), min_length)
+    return _views_ref[key]
+
+
+def _same(got, want):
+    assert got[1].tolist() == want[1].tolist()
+    assert got[0].shape == want[0].shape and got[0].tobytes() == want[0].tobytes()
+
+
+def test_more_listed_faces_than_one_pass_of_the_big_raster(engine):
+    """432 listed (view, face) pairs in one part are 6912 units on k_mesh_raster_big's grid of 2048: workgroups make up to four
+    passes (test_mesh_definition.test_forty_views_of_the_cubes_list_432_faces counts the pairs)."""
+    v, f = MC.occluded_cubes()
+    want = views_ref("occluded_cubes", 40, 40.0, 2.0)
+    assert len(want[0]) == 688
+    _same(engine.mesh_view_lines(engine.Mesh(v, f), engine.view_rotations(40, hemisphere=False), 40.0, None, 2.0), want)
+
+
+def test_more_block_sums_than_one_pass_of_the_scan(engine):
+    """300 (view, block) pairs: the second pass of k_mesh_scan adds a carry of 1321.  Then 40 views of 8 edge blocks: 320 pairs,
+    and the copy of every view's first sum strides over 8."""
+    v, f = MC.tetrahedron()
+    want = views_ref("tetrahedron", 300, 9.3, 0.0)
+    assert len(want[0]) == 1553 and want[1][256] == 1321
+    _same(engine.mesh_view_lines(engine.Mesh(v, f), engine.view_rotations(300, hemisphere=False), 9.3, None, 0.0), want)
+    v, f = MC.icosphere3_bumped()
+    want = views_ref("icosphere3_bumped", 40, 33.7, 0.0)
+    assert np.all(np.diff(want[1]) > 0)
+    _same(engine.mesh_view_lines(engine.Mesh(v, f), engine.view_rotations(40, hemisphere=False), 33.7, None, 0.0), want)
+
+
+def test_a_refused_view_late_in_a_long_list(engine):
+    from openfdcm_amd import _capi
+    v, f = MC.tetrahedron()
+    mesh = engine.Mesh(v, f)
+    views = engine.view_rotations(300, hemisphere=False)
+    bad = views.copy()
+    bad[299] = np.diag([5000.0, 1.0, 1.0])
+    assert MR.view_box(*MR.project(v, bad[299], np.float32(9.3))[:2]) is None
+    with pytest.raises(_capi.FdcmError, match="view 299 spans more than 4096"):
+        engine.mesh_view_lines(mesh, bad, 9.3, None, 0.0)
+    want = views_ref("tetrahedron", 300, 9.3, 0.0)
+    got = engine.mesh_view_lines(mesh, views[:299], 9.3, None, 0.0)     # the refusal left nothing behind
+    assert got[1].tolist() == want[1][:300].tolist() and got[0].tobytes() == want[0][:want[1][299]].tobytes()
+
+
+def test_lists_of_views_of_a_mesh_of_several_blocks(engine):
+    v, f = MC.icosphere3_bumped()
+    mesh = engine.Mesh(v, f)
+    views = engine.view_rotations(9, hemisphere=False)
+    single = [engine.mesh_view_lines(mesh, R, 33.7, None, 0.0)[0] for R in views]
+    assert all(len(s) > 0 for s in single)
+    a = engine.mesh_view_lines(mesh, views, 33.7, None, 0.0)
+    assert a[1].tolist() == np.concatenate([[0], np.cumsum([len(s) for s in single])]).tolist()
+    assert a[0].tobytes() == np.concatenate(single).tobytes()
+    for _ in range(2):
+        b = engine.mesh_view_lines(mesh, views, 33.7, None, 0.0)
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+
+
+SQUARE_4095 = [[-2047.5, -2047.5, 2047.5, -2047.5], [-2047.5, -2047.5, -2047.5, 2047.5], [2047.5, -2047.5, 2047.5, 2047.5],
+               [-2047.5, 2047.5, 2047.5, 2047.5]]   # the referee's lines of the cube at 4095 (test_mesh_definition computes them)
+
+
+def test_parts_cut_by_the_byte_limit(engine):
+    """Five item buffers of 128 MB: parts of 3 and 2 views under the 512 MB the header states, with no switch set."""
+    v, f = MC.cube()
+    box = MR.view_box(*MR.project(v, MC.IDENTITY, np.float32(4095.0))[:2])
+    one = (box[2] - box[0] + 1) * (box[3] - box[1] + 1) * 8
+    assert 5 * one > 512 << 20 and 4 * one >= 512 << 20 > 3 * one + (1 << 20)    # (the megabyte: the list and the counts)
+    assert "FDCM_MESH_PART" not in os.environ
+    rec, off = engine.mesh_view_lines(engine.Mesh(v, f), np.stack([MC.IDENTITY] * 5), 4095.0)
+    assert off.tolist() == [0, 4, 8, 12, 16, 20]
+    assert rec.tobytes() == np.array(SQUARE_4095 * 5, dtype=np.float32).tobytes()
+
+
+@pytest.mark.parametrize("name", ["fence", "fence-turned"])
+def test_fence_edges_carry_41_lines_each(engine, name):
+    v, f, views, scale = MC.case(name)
+    ref = MR.Mesh(v, f, MC.COS30)
+    got, off = engine.mesh_view_lines(engine.Mesh(v, f), views, scale, None, 0.0)
+    assert off.tolist() == [0, 244]
+    (X, Y, Z, box, D), = raster(name)
+    at = 0
+    long_edges = 0
+    for e in np.nonzero(MR.candidates(ref, X, Y))[0]:
+        lines = MR.edge_lines(ref, X, Y, Z, box, D, e, MR.default_depth_tol(v), 0.0)[0]
+        if ref.everts[e].tolist() in ([0, 1], [2, 3]):
+            assert len(lines) == 41
+            assert got[at:at + 41].tobytes() == np.array(lines, dtype=np.float32).tobytes(), ref.everts[e]
+            long_edges += 1
+        at += len(lines)
+    assert long_edges == 2 and at == 244
+
+
 def _probe(env):
     clean = {k: v for k, v in os.environ.items() if not k.startswith("FDCM_")}
     out = subprocess.run([sys.executable, PROBE], capture_output=True, text=True, timeout=120, env={**clean, **env})
@@ -122,14 +230,21 @@ def _probe(env):
 
 def test_parts_and_poison_in_fresh_processes(engine):
     """tools/mesh_probe.py in fresh processes, one after another, each under its own time limit; nothing is started after a
-    failure (an assertion ends the test).  65 views in parts of 7 (FDCM_MESH_PART, read once per process) are ten parts; the
-    digests equal this process's own."""
+    failure (an assertion ends the test).  65 views in parts of 7 (FDCM_MESH_PART, read once per process) are ten parts; in
+    parts of 2 the room of a writing run is 32 lines, so every view of the bumped icosphere (8 edge blocks) is a writing run of
+    its own, the second of a part starting at block 8.  The digests equal this process's own, whose lines of that mesh are the
+    referee's."""
     spec = __import__("importlib.util").util.spec_from_file_location("mesh_probe", PROBE)
     probe = __import__("importlib.util").util.module_from_spec(spec)
     spec.loader.exec_module(probe)
-    digest, n_lines = probe.run()
+    results = probe.results()
+    digest, n_lines = probe.digest(results)
     assert n_lines > 500
-    for env in ({"FDCM_MESH_PART": "7"}, {"FDCM_POISON": "0"}, {"FDCM_POISON": "1"}, {"FDCM_POISON": "1", "FDCM_MESH_PART": "1"}):
+    name, n, scale, min_length = probe.CALLS[2]
+    want = views_ref(name, n, scale, min_length)
+    assert name == "icosphere3_bumped" and np.all(np.diff(want[1]) > 32)
+    _same(results[2], want)
+    for env in ({"FDCM_MESH_PART": "7"}, {"FDCM_MESH_PART": "2"}, {"FDCM_POISON": "0"}, {"FDCM_POISON": "1"}, {"FDCM_POISON": "1", "FDCM_MESH_PART": "1"}):
         line = _probe(env)
         assert line[1] == digest and int(line[3]) == n_lines, (env, line)
 
