@@ -1473,6 +1473,50 @@ int fdcm_mesh_view_lines(const fdcm_mesh* mesh, const float* views /* 9 per view
 int fdcm_mesh_view_items(const fdcm_mesh* mesh, const float* view /* 9 */, float scale, int32_t* box_out /* 4 */,
                          uint64_t* keys_out, int64_t capacity);
 
+/* ---- Templates from a mesh: exact visibility and joined lines.  Two options of the call above, each off by default:
+ *      {depth_tol, min_length, FDCM_MESH_VIS_ITEMS, -1} gives fdcm_mesh_view_lines' bytes.  Everything not restated here is
+ *      that block's: projection, o, candidates, samples S_k, runs, float32 unfused in the order written, each view on its own.
+ *      A. visibility = FDCM_MESH_VIS_EXACT.  The item buffer judges a sample by the one face that owns its pixel's centre; on
+ *      a finely tessellated smooth surface that face's plane, continued to the sample, lies in front of it, and most of the
+ *      outline is lost.  This mode tests every face at the sample itself and builds no item buffer.  Face f = (A, B, C) covers
+ *      a sample S when a = o(A, B, C) != 0; S.X lies in [min, max] of the three X and S.Y in that of the three Y (so the
+ *      face's pixel box holds S's pixel whatever the rounding); and e0 = o(B, C, S), e1 = o(C, A, S), e2 = o(A, B, S) are all
+ *      >= 0 or all <= 0.  Its depth there is zf = ((e0 * A.Z + e1 * B.Z) + e2 * C.Z) / a.  Sample k of edge e = (A, B) is
+ *      hidden iff some face f that is neither f0 nor f1 of the edge -- and at k = 0 does not name vertex A, at k = n does not
+ *      name B: a face through a vertex cannot hide it, and its zf there is ill-conditioned when the face is edge-on -- covers
+ *      S_k with zf > S_k.Z + depth_tol (a NaN zf hides nothing).  Otherwise it is visible: an OR over the faces, independent
+ *      of their order.  Runs, the length test and the output order are the other block's.
+ *      B. join_tolerance = tol >= 0 (negative: off), with either visibility.  The lines before joining are the runs k0 < k1
+ *      of length > 0 in (edge, k0) order, indexed i per view; min_length is not applied to them.  Line i has a start end, at
+ *      vertex A when k0 = 0, and a finish end, at vertex B when k1 = n.  An end at a vertex has the point (X_v, Y_v) of the
+ *      projected vertex (not S_n, which need not equal it bit for bit); any other end has S_k0 or S_k1.  deg(v) is the number
+ *      of ends at vertex v in the view; two ends are linked iff they are at the same vertex with deg = 2; every other end is
+ *      free.  A chain is a maximal sequence of lines through links.  A path has two free ends and starts at the free end of
+ *      the lower-indexed of its two end lines (a path of one line at its own start end); a cycle has none and starts with
+ *      its lowest-indexed line, entered at its start end.  The chain's points P_0 .. P_m are the starting point and then the
+ *      far point of each line in turn (a cycle: P_m = P_0); chains are ordered by the index of their first line.  Each chain
+ *      is simplified greedily, in float32: a = 0; for j = 2 .. m, with d = P_j - P_a and L2 = d.x * d.x + d.y * d.y, the step
+ *      is ok iff L2 > 0, j - a <= 256, and every a < i < j has, with w = P_i - P_a, s = d.x * w.x + d.y * w.y and c = d.x *
+ *      w.y - d.y * w.x: 0 <= s, s <= L2 and c * c <= (tol * tol) * L2; when it is not, (P_a, P_(j-1)) is emitted and a = j - 1.
+ *      At the end (P_a, P_m) is emitted.  Output: chain order, then emission order; a line is kept when its length is > 0
+ *      and >= min_length.  Consequences: every chain point a line skips projects inside the line and lies within tol of it,
+ *      up to rounding; tol = 0 joins exactly collinear points only; a polyhedron whose corners turn by more than the tolerance
+ *      keeps its line count; a cycle may be cut at P_0 even where it is straight there; a joined line replaces at most 256
+ *      segments, which bounds one lane's work on a long straight chain.
+ *      The device.  A: the faces are binned into 8 x 8 pixel tiles of the view's box -- a count pass per (view, face) over
+ *      the tiles of the face's pixel box, a scan, a fill pass with an atomic cursor -- and the edge pass tests a sample
+ *      against the faces of its tile; the raster passes are skipped.  The lists count in the part's 512 MB, the parts being cut
+ *      from per-view totals computed first; a single view whose lists alone need more than 2^28 entries is FDCM_EINVAL with
+ *      its index.  B: the edge pass writes the lines before joining with (edge, end flags); a link pass counts the ends per
+ *      (view, vertex) and keeps two; a chain pass, a lane per line, emits where the line starts a chain, as count, scan and
+ *      write.  The link tables count in the 512 MB, a line before joining takes 44 bytes of the writing pass's 256 MB.
+ *      FDCM_EINVAL, before any GPU work: what fdcm_mesh_view_lines refuses; params NULL; visibility neither value;
+ *      join_tolerance NaN or +infinity. ---- */
+typedef struct { float depth_tol, min_length; int32_t visibility; float join_tolerance; } fdcm_mesh_line_params;  /* 16 bytes */
+enum { FDCM_MESH_VIS_ITEMS = 0, FDCM_MESH_VIS_EXACT = 1 };
+int fdcm_mesh_view_lines_ex(const fdcm_mesh* mesh, const float* views /* 9 per view */, int64_t n_views, float scale,
+                            const fdcm_mesh_line_params* params, float** lines_out, int64_t* offsets_out);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

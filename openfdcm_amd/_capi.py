@@ -115,6 +115,17 @@ class SelectParams(C.Structure):
 
 assert C.sizeof(SelectParams) == 16
 
+MESH_VIS_ITEMS, MESH_VIS_EXACT = 0, 1  # FDCM_MESH_VIS_ITEMS, FDCM_MESH_VIS_EXACT
+
+
+class MeshLineParams(C.Structure):
+    """fdcm_mesh_line_params: the depth tolerance, the shortest line kept, the visibility rule and the joining tolerance
+    (negative: no joining)."""
+    _fields_ = [("depth_tol", C.c_float), ("min_length", C.c_float), ("visibility", C.c_int32), ("join_tolerance", C.c_float)]
+
+
+assert C.sizeof(MeshLineParams) == 16
+
 # every symbol include/fdcm.h declares: (name, restype, argtypes)
 _fp, _i64p, _vp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_void_p
 SYMBOLS = [
@@ -296,6 +307,7 @@ SYMBOLS = [
     ("fdcm_mesh_info", C.c_int, [_vp, _i64p, _i64p, _i64p]),
     ("fdcm_mesh_edges", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]),
     ("fdcm_mesh_view_lines", C.c_int, [_vp, _fp, C.c_int64, C.c_float, C.c_float, C.c_float, C.POINTER(C.POINTER(C.c_float)), _i64p]),
+    ("fdcm_mesh_view_lines_ex", C.c_int, [_vp, _fp, C.c_int64, C.c_float, C.POINTER(MeshLineParams), C.POINTER(C.POINTER(C.c_float)), _i64p]),
     ("fdcm_mesh_view_items", C.c_int, [_vp, _fp, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int64]),
     ("fdcm_selftest_atanf", C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint64]),
     ("fdcm_orientation_bins_mode", C.c_int, []),

@@ -1891,18 +1891,27 @@ static void check_view(const fdcm_mesh* mesh, const float* views, int64_t n_view
     for (int64_t i = 0; i < 9 * n_views; ++i)
         if (!std::isfinite(views[i])) throw std::string("view " + std::to_string(i / 9) + " has an entry that is not finite");
 }
-int fdcm_mesh_view_lines(const fdcm_mesh* mesh, const float* views, int64_t n_views, float scale, float depth_tol, float min_length,
-                         float** lines_out, int64_t* offsets_out) {
+int fdcm_mesh_view_lines_ex(const fdcm_mesh* mesh, const float* views, int64_t n_views, float scale, const fdcm_mesh_line_params* params,
+                            float** lines_out, int64_t* offsets_out) {
     return guarded([&] {
         require(lines_out != nullptr, "lines_out is null");
         require(offsets_out != nullptr, "offsets_out is null");
         check_view(mesh, views, n_views, scale);
-        require(std::isfinite(depth_tol) && depth_tol >= 0.f, "depth_tol must be finite and >= 0");
-        require(std::isfinite(min_length) && min_length >= 0.f, "min_length must be finite and >= 0");
+        require(params != nullptr, "params is null");
+        require(std::isfinite(params->depth_tol) && params->depth_tol >= 0.f, "depth_tol must be finite and >= 0");
+        require(std::isfinite(params->min_length) && params->min_length >= 0.f, "min_length must be finite and >= 0");
+        require(params->visibility == FDCM_MESH_VIS_ITEMS || params->visibility == FDCM_MESH_VIS_EXACT,
+                "visibility must be FDCM_MESH_VIS_ITEMS or FDCM_MESH_VIS_EXACT");
+        require(params->join_tolerance < 0.f || std::isfinite(params->join_tolerance), "join_tolerance must be negative (off) or finite");
         *lines_out = nullptr;
         offsets_out[0] = 0;
-        if (n_views > 0) mesh_view_lines(g_device, mesh, views, n_views, scale, depth_tol, min_length, lines_out, offsets_out);
+        if (n_views > 0) mesh_view_lines(g_device, mesh, views, n_views, scale, *params, lines_out, offsets_out);
     });
+}
+int fdcm_mesh_view_lines(const fdcm_mesh* mesh, const float* views, int64_t n_views, float scale, float depth_tol, float min_length,
+                         float** lines_out, int64_t* offsets_out) {
+    const fdcm_mesh_line_params params = {depth_tol, min_length, FDCM_MESH_VIS_ITEMS, -1.f};
+    return fdcm_mesh_view_lines_ex(mesh, views, n_views, scale, &params, lines_out, offsets_out);
 }
 int fdcm_mesh_view_items(const fdcm_mesh* mesh, const float* view, float scale, int32_t* box_out, uint64_t* keys_out, int64_t capacity) {
     return guarded([&] {

@@ -353,7 +353,7 @@ namespace fdcm {
 // which mesh_create refuses with a std::string.  The view calls block, on the null stream of `device`, and hold what they need
 // there in a PixelScratch of their own; n_views >= 1.  *lines_out is malloc'ed (fdcm_lines_free), untouched when there is no line.
 fdcm_mesh* mesh_create(const float* vertices, int64_t V, const int32_t* faces, int64_t F, double crease_cos);
-void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t n_views, float scale, float depth_tol, float min_length,
+void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t n_views, float scale, const fdcm_mesh_line_params& p,
                      float** lines_out, int64_t* offsets_out);
 void mesh_view_items(int device, const fdcm_mesh* m, const float* view, float scale, int32_t* box_out, uint64_t* keys_out, int64_t capacity);
 // implemented in fdcm_build.hip
@@ -388,7 +388,9 @@ struct PixelScratch {
     // edge_labels_host: pixels, keys, labels, and comps for the edge kernels' parent and root words.  lines_from_labels_host:
     // pixels (the labels), parent (both partitions), counts, comps (the components' sums), out.  lines_from_image_host: all of
     // them; comps serves the edge kernels first and the components' sums afterwards.  The mesh's view calls (fdcm_mesh.hip):
-    // keys (views, mesh tables, view records), comps (boxes), pixels (item buffers), parent (large faces), counts, out.
+    // keys (views, mesh tables, view records), comps (boxes), pixels (item buffers), parent (large faces), counts, out; with
+    // exact visibility comps (the views' pair totals behind the boxes), pixels (tiles), parent (their face lists); with joining
+    // labels (a run's lines before joining, their links and chain counts).
     DevBuf pixels, labels, keys, parent, counts, comps, out;
     ~PixelScratch();
     // reserve of a member: under FDCM_POISON a member that this allocated holds the word throughout, by a fill on the null

@@ -1251,14 +1251,20 @@ def _views(views):
     return r
 
 
-def mesh_view_lines(mesh, views, scale, depth_tolerance=None, min_length=2.0):
-    """fdcm_mesh_view_lines as it is: ((N, 4) float32 line records of all views, int64 offsets of n_views + 1)."""
+MESH_VISIBILITY = {"items": capi.MESH_VIS_ITEMS, "exact": capi.MESH_VIS_EXACT}
+
+
+def mesh_view_lines(mesh, views, scale, depth_tolerance=None, min_length=2.0, visibility="items", join_tolerance=None):
+    """fdcm_mesh_view_lines_ex as it is: ((N, 4) float32 line records of all views, int64 offsets of n_views + 1).  visibility:
+    "items" or "exact" (an integer goes to the library as it is); join_tolerance: pixels, None for no joining."""
     r = _views(views)
     tol = mesh.default_depth_tolerance() if depth_tolerance is None else depth_tolerance
     offsets = np.zeros(r.shape[0] + 1, dtype=np.int64)
     out = C.POINTER(C.c_float)()
-    capi.check(capi.lib().fdcm_mesh_view_lines(mesh._h, capi.fptr(r), r.shape[0], float(scale), float(tol), float(min_length),
-                                               C.byref(out), offsets.ctypes.data_as(C.POINTER(C.c_int64))))
+    params = capi.MeshLineParams(float(tol), float(min_length), int(MESH_VISIBILITY.get(visibility, visibility)),
+                                 -1.0 if join_tolerance is None else float(join_tolerance))
+    capi.check(capi.lib().fdcm_mesh_view_lines_ex(mesh._h, capi.fptr(r), r.shape[0], float(scale), C.byref(params),
+                                                  C.byref(out), offsets.ctypes.data_as(C.POINTER(C.c_int64))))
     n = int(offsets[-1])
     try:
         rec = np.ctypeslib.as_array(out, shape=(n, 4)).copy() if n else np.zeros((0, 4), dtype=np.float32)
@@ -1268,12 +1274,15 @@ def mesh_view_lines(mesh, views, scale, depth_tolerance=None, min_length=2.0):
     return rec, offsets
 
 
-def templates_from_mesh(mesh, views, scale, depth_tolerance=None, min_length=2.0):
+def templates_from_mesh(mesh, views, scale, depth_tolerance=None, min_length=2.0, visibility="items", join_tolerance=None):
     """The line template of every view of a mesh, computed on the GPU (include/fdcm.h, "Templates from a mesh"): a list of (4, N)
     float32 arrays, template t being view t, with the projection of the mesh origin at (0, 0).  views: (n, 3, 3) rotations
     (view_rotations makes them); scale: pixels per mesh unit; depth_tolerance: mesh units, None for 1e-4 of the bounding box's
-    diagonal; min_length: the shortest line kept, in pixels.  Orthographic."""
-    rec, offsets = mesh_view_lines(mesh, views, scale, depth_tolerance, min_length)
+    diagonal; min_length: the shortest line kept, in pixels.  Orthographic.  For a smooth, tessellated part take
+    visibility="exact" (every face is tested at the sample itself, not the one that owns its pixel) and a join_tolerance in
+    pixels, such as 0.5 (the contour's runs are chained at shared vertices and simplified before min_length applies): the
+    defaults keep only fragments of such an outline."""
+    rec, offsets = mesh_view_lines(mesh, views, scale, depth_tolerance, min_length, visibility, join_tolerance)
     return [np.ascontiguousarray(rec[offsets[i]:offsets[i + 1]].T) for i in range(len(offsets) - 1)]
 
 

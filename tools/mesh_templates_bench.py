@@ -27,6 +27,40 @@ def bumpy_sphere():
     return MC.icosphere(5, bump=lambda p: 1.0 + 0.2 * np.sin(4.0 * p[:, 0]) * np.sin(4.0 * p[:, 1]) + 0.15 * np.cos(5.0 * p[:, 2]))
 
 
+def timed_mode(engine, mesh, views, visibility, join):
+    """A warm-up call, then CALLS blocking calls in the mode: (record of the times, line counts and kept length; lines, offsets)."""
+    import numpy as np
+    rec, offsets = engine.mesh_view_lines(mesh, views, SCALE, None, MIN_LENGTH, visibility, join)
+    times = []
+    for _ in range(CALLS):
+        t0 = time.perf_counter()
+        engine.templates_from_mesh(mesh, views, SCALE, None, MIN_LENGTH, visibility, join)
+        times.append(time.perf_counter() - t0)
+    length = float(np.hypot(rec[:, 2].astype(np.float64) - rec[:, 0], rec[:, 3].astype(np.float64) - rec[:, 1]).sum())
+    return {"visibility": visibility, "join_tolerance": join, "median_ms": 1e3 * statistics.median(times), "min_ms": 1e3 * min(times),
+            "max_ms": 1e3 * max(times), "lines": int(len(rec)), "kept_length_px": length}, rec, offsets
+
+
+def child_mode(n_views, referee_views, visibility, join):
+    """--visibility / --join: the mode beside the default mode in the same process; the referee of the mode on the first views."""
+    import numpy as np
+    import mesh_join_ref as JR
+    import mesh_ref as MR
+    from openfdcm_amd import engine
+    v, f = bumpy_sphere()
+    mesh = engine.Mesh(v, f)
+    views = engine.view_rotations(n_views)
+    out = {"default": timed_mode(engine, mesh, views, "items", None)[0], "views": n_views, "scale": SCALE, "faces": int(len(f))}
+    out["mode"], rec, offsets = timed_mode(engine, mesh, views, visibility, join)
+    if referee_views:
+        ref = MR.Mesh(v, f, float(np.cos(np.deg2rad(30))))
+        want, want_off = JR.views_lines(ref, views[:referee_views], np.float32(SCALE), mesh.default_depth_tolerance(), MIN_LENGTH, visibility, join)
+        out["referee_views"] = referee_views
+        out["referee_equal"] = bool(want_off.tolist() == offsets[:referee_views + 1].tolist() and want.tobytes() == rec[:want_off[-1]].tobytes())
+    print("mesh_templates_bench_child " + json.dumps(out), flush=True)
+    return 0 if out.get("referee_equal", True) else 1
+
+
 def child(n_views, referee_views):
     import numpy as np
     import mesh_ref as MR
@@ -64,19 +98,43 @@ def main():
     ap.add_argument("--referee-views", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_templates_bench.json"))
     ap.add_argument("--child", type=int, default=-1, help=argparse.SUPPRESS)
+    ap.add_argument("--visibility", choices=("items", "exact"), default=None, help="time this mode beside the default mode")
+    ap.add_argument("--join", type=float, default=None, help="the joining tolerance in pixels of the mode timed")
     a = ap.parse_args()
+    mode = a.visibility is not None or a.join is not None
+    if mode and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "mesh_exact_join_bench.json")
+    if a.child >= 0 and mode:
+        return child_mode(a.views, a.referee_views if a.child == 0 else 0, a.visibility or "items", a.join)
     if a.child >= 0:
         return child(a.views, a.referee_views if a.child == 0 else 0)
     runs = []
+    extra = (["--visibility", a.visibility] if a.visibility else []) + (["--join", str(a.join)] if a.join is not None else [])
     for i in range(2):      # one after another; nothing is started after a failure
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--views", str(a.views), "--referee-views", str(a.referee_views),
-                            "--child", str(i)], capture_output=True, text=True, timeout=900)
+                            "--child", str(i)] + extra, capture_output=True, text=True, timeout=900)
         lines = [l for l in p.stdout.splitlines() if l.startswith("mesh_templates_bench_child ")]
         if p.returncode != 0 or not lines:
             sys.stderr.write(p.stdout + p.stderr)
             print(json.dumps({"error": "process %d failed or disagrees with the referee" % i}))
             return 1
         runs.append(json.loads(lines[-1].split(" ", 1)[1]))
+    if mode:        # one mode per invocation: its record is added to the file's, keyed by the mode
+        key = "%s,join=%s" % (a.visibility or "items", a.join)
+        result = {"bench": "mesh_exact_join", "mode": key, "processes": runs, "referee_equal": runs[0].get("referee_equal"),
+                  "median_ms": [r["mode"]["median_ms"] for r in runs], "default_median_ms": [r["default"]["median_ms"] for r in runs],
+                  "lines": runs[0]["mode"]["lines"], "kept_length_px": runs[0]["mode"]["kept_length_px"],
+                  "default_lines": runs[0]["default"]["lines"], "default_kept_length_px": runs[0]["default"]["kept_length_px"]}
+        print(json.dumps(result))
+        allr = {}
+        if os.path.exists(a.out):
+            with open(a.out) as fh:
+                allr = json.load(fh)
+        allr[key] = result
+        with open(a.out, "w") as fh:
+            json.dump(allr, fh, indent=1)
+            fh.write("\n")
+        return 0
     result = {"bench": "mesh_templates", "processes": runs, "median_ms": [r["median_ms"] for r in runs],
               "ms_per_view": [r["median_ms"] / a.views for r in runs], "lines": runs[0]["lines"],
               "referee_ms_per_view": runs[0].get("referee_ms_per_view"), "referee_equal": runs[0].get("referee_equal")}
