@@ -1517,6 +1517,39 @@ enum { FDCM_MESH_VIS_ITEMS = 0, FDCM_MESH_VIS_EXACT = 1 };
 int fdcm_mesh_view_lines_ex(const fdcm_mesh* mesh, const float* views /* 9 per view */, int64_t n_views, float scale,
                             const fdcm_mesh_line_params* params, float** lines_out, int64_t* offsets_out);
 
+/* ---- Templates from a mesh: pinhole views.  A camera mode of the calls above, beside the orthographic one, which stays the
+ *      default and keeps its bytes.  Everything not restated here is the two blocks' above: orientation o, candidates, pixel
+ *      box, item buffer and its keys (ord(Z)), samples S_k, runs, exact visibility, joining, min_length, output order, "each
+ *      view on its own", the memory limits, float32 unfused in the order written.
+ *      Camera.  fdcm_mesh_camera {focal, near}: focal in pixels, near in mesh units, both finite and > 0, for the call.
+ *      View.  R as above, and a position t of 3 floats, finite, with -t.z > 0: where the mesh origin lies in the camera's
+ *      frame.  The camera is at the origin and looks down -Z; X and Y are as in the orthographic mode.
+ *      Projection of vertex v = (x, y, z).  P.c = ((r_c0 x + r_c1 y) + r_c2 z) + t.c for c = x, y, z; the depth d = -P.z;
+ *      Z = 1.0f / d; X = (focal * P.x) * Z - O.x and Y = (focal * P.y) * Z - O.y, with O.x = (focal * t.x) * (1.0f / (-t.z))
+ *      and O.y likewise: the projection of the mesh origin is the template's (0, 0), as above, and a larger Z is nearer, as
+ *      above.  Z = 1 / depth is linear in X and Y across a plane, so the orientation tests, the barycentric depth of a face
+ *      ((e0 * A.Z + e1 * B.Z) + e2 * C.Z) / a and the interpolation A.Z + t * dz of a sample along a projected edge are
+ *      perspective-correct as they stand.  With t = (0, 0, -D), focal = scale * D and D -> infinity the view tends to the
+ *      orthographic one.
+ *      Refused.  A view with a vertex whose d is not >= near (a NaN d too) is FDCM_EINVAL with the view's index, after the
+ *      projection pass and before any raster work, like an oversized box.  There is no clipping.
+ *      Depth tolerance.  Still in mesh units: in depth it means d_S <= d_f + depth_tol.  On Z, with zf the occluder's depth
+ *      formula at the sample: the item buffer's rule calls the sample visible iff (depth_tol * S.Z) * zf >= zf - S.Z (in
+ *      place of S.Z + depth_tol >= zf); the exact rule calls it hidden iff zf - S.Z > (depth_tol * S.Z) * zf (in place of
+ *      zf > S.Z + depth_tol; a NaN hides nothing).
+ *      The device.  The projection is a type parameter of the kernels above, so the orthographic instantiations are the
+ *      code they were; the projection pass marks a view with a vertex nearer than `near` the way it marks an oversized
+ *      coordinate.  The positions travel with the views (12 n_views bytes more on the device).
+ *      FDCM_EINVAL, before any GPU work: what fdcm_mesh_view_lines_ex refuses (focal in place of scale); camera or positions
+ *      NULL; focal, near or a position's entry not finite; focal <= 0, near <= 0 or -t.z <= 0 (with the position's index). ---- */
+typedef struct { float focal, near; } fdcm_mesh_camera;  /* 8 bytes */
+int fdcm_mesh_view_lines_cam(const fdcm_mesh* mesh, const float* views /* 9 per view */, const float* positions /* 3 per view */,
+                             int64_t n_views, const fdcm_mesh_camera* camera, const fdcm_mesh_line_params* params,
+                             float** lines_out, int64_t* offsets_out);
+/* the test hook fdcm_mesh_view_items through the camera */
+int fdcm_mesh_view_items_cam(const fdcm_mesh* mesh, const float* view /* 9 */, const float* position /* 3 */,
+                             const fdcm_mesh_camera* camera, int32_t* box_out /* 4 */, uint64_t* keys_out, int64_t capacity);
+
 /* ---- host-side self checks (no GPU needed) ---- */
 /* Compare the device-portable atanf restatement with this machine's libm atanf over the float
  * bit patterns first, first+stride, ... (count values); returns the number of mismatches. */

@@ -15,6 +15,7 @@ from .matchlist import Match, MatchList, records_of  # noqa: F401
 from . import engine as _engine
 from .engine import DeviceFeatureMap, DeviceTemplates, FramePipeline, ShardedEngine, edge_labels, image_pyramid, image_pyramid_size, lines_from_image, lines_from_labels, search_raw, topk  # noqa: F401  (extensions)
 from .engine import Mesh, mesh_view_lines, record_rotations, templates_from_mesh, view_rotations  # noqa: F401  (templates from a mesh)
+from .engine import mesh_view_items, record_camera_poses, view_positions  # noqa: F401  (pinhole views)
 
 __version__ = "0.10.0"  # API level of the reference this mirrors (openfdcm.cpp:43)
 

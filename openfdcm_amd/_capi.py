@@ -126,6 +126,14 @@ class MeshLineParams(C.Structure):
 
 assert C.sizeof(MeshLineParams) == 16
 
+
+class MeshCamera(C.Structure):
+    """fdcm_mesh_camera: the focal length in pixels and the near distance in mesh units."""
+    _fields_ = [("focal", C.c_float), ("near", C.c_float)]
+
+
+assert C.sizeof(MeshCamera) == 8
+
 # every symbol include/fdcm.h declares: (name, restype, argtypes)
 _fp, _i64p, _vp = C.POINTER(C.c_float), C.POINTER(C.c_int64), C.c_void_p
 SYMBOLS = [
@@ -309,6 +317,9 @@ SYMBOLS = [
     ("fdcm_mesh_view_lines", C.c_int, [_vp, _fp, C.c_int64, C.c_float, C.c_float, C.c_float, C.POINTER(C.POINTER(C.c_float)), _i64p]),
     ("fdcm_mesh_view_lines_ex", C.c_int, [_vp, _fp, C.c_int64, C.c_float, C.POINTER(MeshLineParams), C.POINTER(C.POINTER(C.c_float)), _i64p]),
     ("fdcm_mesh_view_items", C.c_int, [_vp, _fp, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int64]),
+    ("fdcm_mesh_view_lines_cam", C.c_int, [_vp, _fp, _fp, C.c_int64, C.POINTER(MeshCamera), C.POINTER(MeshLineParams),
+                                           C.POINTER(C.POINTER(C.c_float)), _i64p]),
+    ("fdcm_mesh_view_items_cam", C.c_int, [_vp, _fp, _fp, C.POINTER(MeshCamera), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.c_int64]),
     ("fdcm_selftest_atanf", C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint64]),
     ("fdcm_orientation_bins_mode", C.c_int, []),
     ("fdcm_selftest_sweep_ranges", C.c_int, [C.c_int]),

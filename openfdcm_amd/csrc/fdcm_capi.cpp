@@ -1891,18 +1891,21 @@ static void check_view(const fdcm_mesh* mesh, const float* views, int64_t n_view
     for (int64_t i = 0; i < 9 * n_views; ++i)
         if (!std::isfinite(views[i])) throw std::string("view " + std::to_string(i / 9) + " has an entry that is not finite");
 }
+static void check_line_params(const fdcm_mesh_line_params* params) {
+    require(params != nullptr, "params is null");
+    require(std::isfinite(params->depth_tol) && params->depth_tol >= 0.f, "depth_tol must be finite and >= 0");
+    require(std::isfinite(params->min_length) && params->min_length >= 0.f, "min_length must be finite and >= 0");
+    require(params->visibility == FDCM_MESH_VIS_ITEMS || params->visibility == FDCM_MESH_VIS_EXACT,
+            "visibility must be FDCM_MESH_VIS_ITEMS or FDCM_MESH_VIS_EXACT");
+    require(params->join_tolerance < 0.f || std::isfinite(params->join_tolerance), "join_tolerance must be negative (off) or finite");
+}
 int fdcm_mesh_view_lines_ex(const fdcm_mesh* mesh, const float* views, int64_t n_views, float scale, const fdcm_mesh_line_params* params,
                             float** lines_out, int64_t* offsets_out) {
     return guarded([&] {
         require(lines_out != nullptr, "lines_out is null");
         require(offsets_out != nullptr, "offsets_out is null");
         check_view(mesh, views, n_views, scale);
-        require(params != nullptr, "params is null");
-        require(std::isfinite(params->depth_tol) && params->depth_tol >= 0.f, "depth_tol must be finite and >= 0");
-        require(std::isfinite(params->min_length) && params->min_length >= 0.f, "min_length must be finite and >= 0");
-        require(params->visibility == FDCM_MESH_VIS_ITEMS || params->visibility == FDCM_MESH_VIS_EXACT,
-                "visibility must be FDCM_MESH_VIS_ITEMS or FDCM_MESH_VIS_EXACT");
-        require(params->join_tolerance < 0.f || std::isfinite(params->join_tolerance), "join_tolerance must be negative (off) or finite");
+        check_line_params(params);
         *lines_out = nullptr;
         offsets_out[0] = 0;
         if (n_views > 0) mesh_view_lines(g_device, mesh, views, n_views, scale, *params, lines_out, offsets_out);
@@ -1920,6 +1923,43 @@ int fdcm_mesh_view_items(const fdcm_mesh* mesh, const float* view, float scale, 
         check_view(mesh, view, 1, scale);
         require(capacity >= 0, "capacity must be >= 0");
         mesh_view_items(g_device, mesh, view, scale, box_out, keys_out, capacity);
+    });
+}
+// the pinhole calls: the camera and the positions (check_view's scale is the focal length: both are finite and > 0)
+static void check_camera(const fdcm_mesh* mesh, const float* views, const float* positions, int64_t n_views, const fdcm_mesh_camera* camera) {
+    require(camera != nullptr, "camera is null");
+    require(std::isfinite(camera->focal) && camera->focal > 0.f, "focal must be finite and > 0");
+    require(std::isfinite(camera->near) && camera->near > 0.f, "near must be finite and > 0");
+    check_view(mesh, views, n_views, camera->focal);
+    require(positions != nullptr || n_views == 0, "positions is null");
+    for (int64_t v = 0; v < n_views; ++v) {
+        const float* t = positions + 3 * v;
+        if (!std::isfinite(t[0]) || !std::isfinite(t[1]) || !std::isfinite(t[2]))
+            throw std::string("position " + std::to_string(v) + " has an entry that is not finite");
+        if (!(-t[2] > 0.f)) throw std::string("position " + std::to_string(v) + " is not in front of the camera (-t.z must be > 0)");
+    }
+}
+int fdcm_mesh_view_lines_cam(const fdcm_mesh* mesh, const float* views, const float* positions, int64_t n_views, const fdcm_mesh_camera* camera,
+                             const fdcm_mesh_line_params* params, float** lines_out, int64_t* offsets_out) {
+    return guarded([&] {
+        require(lines_out != nullptr, "lines_out is null");
+        require(offsets_out != nullptr, "offsets_out is null");
+        check_camera(mesh, views, positions, n_views, camera);
+        check_line_params(params);
+        *lines_out = nullptr;
+        offsets_out[0] = 0;
+        if (n_views > 0) mesh_view_lines_cam(g_device, mesh, views, positions, n_views, *camera, *params, lines_out, offsets_out);
+    });
+}
+int fdcm_mesh_view_items_cam(const fdcm_mesh* mesh, const float* view, const float* position, const fdcm_mesh_camera* camera, int32_t* box_out,
+                             uint64_t* keys_out, int64_t capacity) {
+    return guarded([&] {
+        require(box_out != nullptr, "box_out is null");
+        require(view != nullptr, "view is null");
+        require(position != nullptr, "position is null");
+        check_camera(mesh, view, position, 1, camera);
+        require(capacity >= 0, "capacity must be >= 0");
+        mesh_view_items_cam(g_device, mesh, view, position, *camera, box_out, keys_out, capacity);
     });
 }
 

@@ -356,6 +356,11 @@ fdcm_mesh* mesh_create(const float* vertices, int64_t V, const int32_t* faces, i
 void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t n_views, float scale, const fdcm_mesh_line_params& p,
                      float** lines_out, int64_t* offsets_out);
 void mesh_view_items(int device, const fdcm_mesh* m, const float* view, float scale, int32_t* box_out, uint64_t* keys_out, int64_t capacity);
+// the same two through a pinhole camera ("Templates from a mesh: pinhole views"): positions, 3 floats per view, beside the views
+void mesh_view_lines_cam(int device, const fdcm_mesh* m, const float* views, const float* positions, int64_t n_views, const fdcm_mesh_camera& cam,
+                         const fdcm_mesh_line_params& p, float** lines_out, int64_t* offsets_out);
+void mesh_view_items_cam(int device, const fdcm_mesh* m, const float* view, const float* position, const fdcm_mesh_camera& cam, int32_t* box_out,
+                         uint64_t* keys_out, int64_t capacity);
 // implemented in fdcm_build.hip
 void ensure_stream(fdcm_featuremap* fm);  // the handle's stream and timing events, made on first use (on fm's device)
 BuildLayout build_layout(const BuildPlan& plan, int distance, int stop_after);  // from the plan's shape and counts

@@ -25,7 +25,9 @@
 //   k_mesh_starts      a lane per view: where its lines begin among the run's (the host reads these alone)
 //   k_mesh_chains<1>   the same walk, the lines written
 // Nothing stores a projection: every kernel projects the vertices it reads with mesh_project, the one statement of the view, so
-// the passes agree to the bit and a part of the views costs its item buffers, counts and list alone.
+// the passes agree to the bit and a part of the views costs its item buffers, counts and list alone.  The projection is a type
+// parameter of those kernels: MeshOrtho, or MeshPinhole ("Templates from a mesh: pinhole views"), whose depth coordinate is
+// Z = 1 / depth, so that nothing but the projection and the depth-tolerance compare differs between the two.
 // Bounds: a face's box lies in its view's box (both are floors of the same projected values), and every access of the item
 // buffer tests the pixel against the view's box all the same; a list entry is below the part's views times F, the list's size;
 // counts and sums are indexed by (view, block) below the grid's size; a line's position is below the total the host read back.
@@ -51,12 +53,62 @@ static constexpr float kMeshMaxCoord = 1073741824.f;  // 2^30
 struct MeshView { int32_t x0, y0, w, h; long long off; };  // the view's box and where its item buffer begins in the part's (keys)
 struct MeshPoint { float X, Y, Z; };
 
-__device__ __forceinline__ MeshPoint mesh_project(const float* __restrict__ R, float scale, const float* __restrict__ v) {
+// The projection is a type parameter of every kernel that projects: the orthographic one is the block "Templates from a mesh",
+// the pinhole one "Templates from a mesh: pinhole views".  A projection travels in a kernel's arguments where `scale` did (so
+// MeshOrtho's argument blocks are the ones a float gave); `at` is what one view adds to its matrix R, `from` the projection of
+// a part or a run that begins at view v0, and the depth-tolerance compares are the projection's too: `limit` once per sample, then
+// `visible` (the item buffer's rule: false for a NaN) or `hidden` (the exact rule: false for a NaN).
+struct MeshOrtho {
+    float scale;
+    struct View { float scale; };
+    __device__ __forceinline__ View at(int) const { return View{scale}; }
+    __device__ __forceinline__ bool admits(const float* __restrict__, const View&, const float* __restrict__) const { return true; }
+    MeshOrtho from(int64_t) const { return *this; }
+    static __device__ __forceinline__ float limit(float tol, float sz) { return sz + tol; }
+    static __device__ __forceinline__ bool visible(float limit, float, float zf) { return limit >= zf; }
+    static __device__ __forceinline__ bool hidden(float limit, float, float zf) { return zf > limit; }
+};
+struct MeshPinhole {
+    float focal, near;
+    const float* positions;  // 3 per view, beside the views
+    struct View { float tx, ty, tz, focal, ox, oy; };
+    __device__ __forceinline__ View at(int view) const {
+        const float* t = positions + 3 * (size_t)view;
+        View w{t[0], t[1], t[2], focal, 0.f, 0.f};
+        const float zo = 1.0f / (-w.tz);
+        w.ox = (focal * w.tx) * zo;
+        w.oy = (focal * w.ty) * zo;
+        return w;
+    }
+    // the vertex is at depth d >= near (false for a NaN): the one test k_mesh_boxes adds, every other pass sees admitted views only
+    __device__ __forceinline__ bool admits(const float* __restrict__ R, const View& w, const float* __restrict__ v) const {
+        const float d = -(((R[6] * v[0] + R[7] * v[1]) + R[8] * v[2]) + w.tz);
+        return d >= near;
+    }
+    MeshPinhole from(int64_t v0) const { return MeshPinhole{focal, near, positions + 3 * (size_t)v0}; }
+    static __device__ __forceinline__ float limit(float tol, float sz) { return tol * sz; }
+    static __device__ __forceinline__ bool visible(float limit, float sz, float zf) { return limit * zf >= zf - sz; }
+    static __device__ __forceinline__ bool hidden(float limit, float sz, float zf) { return zf - sz > limit * zf; }
+};
+
+__device__ __forceinline__ MeshPoint mesh_project(const float* __restrict__ R, const MeshOrtho::View& w, const float* __restrict__ v) {
     const float x = v[0], y = v[1], z = v[2];
     MeshPoint p;
-    p.X = scale * ((R[0] * x + R[1] * y) + R[2] * z);
-    p.Y = scale * ((R[3] * x + R[4] * y) + R[5] * z);
+    p.X = w.scale * ((R[0] * x + R[1] * y) + R[2] * z);
+    p.Y = w.scale * ((R[3] * x + R[4] * y) + R[5] * z);
     p.Z = (R[6] * x + R[7] * y) + R[8] * z;
+    return p;
+}
+// Z = 1 / depth: larger is nearer, as above, and linear in X and Y across a face and along an edge
+__device__ __forceinline__ MeshPoint mesh_project(const float* __restrict__ R, const MeshPinhole::View& w, const float* __restrict__ v) {
+    const float x = v[0], y = v[1], z = v[2];
+    const float px = ((R[0] * x + R[1] * y) + R[2] * z) + w.tx;
+    const float py = ((R[3] * x + R[4] * y) + R[5] * z) + w.ty;
+    const float pz = ((R[6] * x + R[7] * y) + R[8] * z) + w.tz;
+    MeshPoint p;
+    p.Z = 1.0f / (-pz);
+    p.X = (w.focal * px) * p.Z - w.ox;
+    p.Y = (w.focal * py) * p.Z - w.oy;
     return p;
 }
 __device__ __forceinline__ float mesh_orient(float ax, float ay, float bx, float by, float cx, float cy) {
@@ -78,12 +130,13 @@ struct MeshFace {
         return a > 0.f ? (e0 >= 0.f && e1 >= 0.f && e2 >= 0.f) : (a < 0.f && e0 <= 0.f && e1 <= 0.f && e2 <= 0.f);
     }
 };
-__device__ __forceinline__ MeshFace mesh_face(const float* __restrict__ R, float scale, const float* __restrict__ verts,
+template <class View>
+__device__ __forceinline__ MeshFace mesh_face(const float* __restrict__ R, const View& w, const float* __restrict__ verts,
                                               const int32_t* __restrict__ faces, int f) {
     MeshFace t;
-    t.A = mesh_project(R, scale, verts + 3 * (size_t)faces[3 * (size_t)f]);
-    t.B = mesh_project(R, scale, verts + 3 * (size_t)faces[3 * (size_t)f + 1]);
-    t.C = mesh_project(R, scale, verts + 3 * (size_t)faces[3 * (size_t)f + 2]);
+    t.A = mesh_project(R, w, verts + 3 * (size_t)faces[3 * (size_t)f]);
+    t.B = mesh_project(R, w, verts + 3 * (size_t)faces[3 * (size_t)f + 1]);
+    t.C = mesh_project(R, w, verts + 3 * (size_t)faces[3 * (size_t)f + 2]);
     t.a = mesh_orient(t.A.X, t.A.Y, t.B.X, t.B.Y, t.C.X, t.C.Y);
     return t;
 }
@@ -105,14 +158,18 @@ __device__ __forceinline__ void mesh_shade(const MeshFace& t, int f, const MeshV
 
 // ------------------------------------------------------------------------------------------ projection pass
 // boxes: 4 ints per view, x0 y0 x1 y1, from (INT_MAX, INT_MAX, INT_MIN, INT_MIN).  A coordinate that is not below 2^30 in
-// magnitude (a NaN too) makes the box span everything, which the host refuses like any box above 4096.
+// magnitude (a NaN too) makes the box span everything, which the host refuses like any box above 4096; so does a vertex the
+// projection does not admit (the pinhole's: one nearer than `near`).
+template <class Proj>
 __global__ void __launch_bounds__(256) k_mesh_boxes(const float* __restrict__ verts, int V, int nbV, const float* __restrict__ views,
-                                                    float scale, int32_t* boxes) {
+                                                    Proj pj, int32_t* boxes) {
     const int view = blockIdx.x / nbV, v = (blockIdx.x % nbV) * 256 + threadIdx.x;
     int x0 = INT32_MAX, y0 = INT32_MAX, x1 = INT32_MIN, y1 = INT32_MIN;
     if (v < V) {
-        const MeshPoint p = mesh_project(views + 9 * (size_t)view, scale, verts + 3 * (size_t)v);
-        if (fabsf(p.X) < kMeshMaxCoord && fabsf(p.Y) < kMeshMaxCoord) {
+        const float* R = views + 9 * (size_t)view;
+        const typename Proj::View w = pj.at(view);
+        const MeshPoint p = mesh_project(R, w, verts + 3 * (size_t)v);
+        if (pj.admits(R, w, verts + 3 * (size_t)v) && fabsf(p.X) < kMeshMaxCoord && fabsf(p.Y) < kMeshMaxCoord) {
             x0 = x1 = (int)floorf(p.X);
             y0 = y1 = (int)floorf(p.Y);
         } else {
@@ -132,12 +189,13 @@ __global__ void __launch_bounds__(256) k_mesh_boxes(const float* __restrict__ ve
 
 // ------------------------------------------------------------------------------------------ raster pass
 // views, descs: the part's.  list: its count in the first 8 bytes, then (view in the part, face) pairs.
+template <class Proj>
 __global__ void __launch_bounds__(256) k_mesh_raster(const float* __restrict__ verts, const int32_t* __restrict__ faces, int F, int nbF,
-                                                     const float* __restrict__ views, float scale, const MeshView* __restrict__ descs,
+                                                     const float* __restrict__ views, Proj pj, const MeshView* __restrict__ descs,
                                                      unsigned long long* __restrict__ items, unsigned long long* list) {
     const int view = blockIdx.x / nbF, f = (blockIdx.x % nbF) * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
     if (f >= F) return;
-    const MeshFace t = mesh_face(views + 9 * (size_t)view, scale, verts, faces, f);
+    const MeshFace t = mesh_face(views + 9 * (size_t)view, pj.at(view), verts, faces, f);
     if (!t.solid()) return;
     const MeshBox b = mesh_face_box(t);
     const int tx = ((b.i1 - b.i0) >> 2) + 1, ty = ((b.j1 - b.j0) >> 2) + 1;  // (a view's box spans 4096 at most: 1024 x 1024 tiles)
@@ -155,14 +213,15 @@ __global__ void __launch_bounds__(256) k_mesh_raster(const float* __restrict__ v
         if (i <= b.i1 && j <= b.j1) mesh_shade(t, f, d, items, i, j);
     }
 }
+template <class Proj>
 __global__ void __launch_bounds__(256) k_mesh_raster_big(const float* __restrict__ verts, const int32_t* __restrict__ faces,
-                                                         const float* __restrict__ views, float scale, const MeshView* __restrict__ descs,
+                                                         const float* __restrict__ views, Proj pj, const MeshView* __restrict__ descs,
                                                          unsigned long long* __restrict__ items, const unsigned long long* __restrict__ list) {
     const long long units = (long long)list[0] * kBigSlices;
     const int2* entries = reinterpret_cast<const int2*>(list + 1);
     for (long long u = blockIdx.x; u < units; u += gridDim.x) {
         const int2 en = entries[u / kBigSlices];
-        const MeshFace t = mesh_face(views + 9 * (size_t)en.x, scale, verts, faces, en.y);
+        const MeshFace t = mesh_face(views + 9 * (size_t)en.x, pj.at(en.x), verts, faces, en.y);
         const MeshBox b = mesh_face_box(t);
         const MeshView d = descs[en.x];
         const int tx = ((b.i1 - b.i0) >> 4) + 1, ty = ((b.j1 - b.j0) >> 4) + 1;
@@ -190,14 +249,14 @@ __device__ __host__ __forceinline__ int mesh_tiles_across(int w) { return (w + 7
 // PASS 0: boxes and totals of all views, nothing else is read.  PASS 1, 2: views, boxes and descs are the part's.
 // Bounds: a tile index is clamped into the view's own tiles, so it is below the part's number of tiles; a list position is
 // tested against n_pairs (it is below it: the fill pass repeats the count pass's loop).
-template <int PASS>
+template <int PASS, class Proj>
 __global__ void __launch_bounds__(256) k_mesh_tiles(const float* __restrict__ verts, const int32_t* __restrict__ faces, int F, int nbF,
-                                                    const float* __restrict__ views, float scale, const int32_t* __restrict__ boxes,
+                                                    const float* __restrict__ views, Proj pj, const int32_t* __restrict__ boxes,
                                                     const MeshView* __restrict__ descs, MeshTiles T, unsigned long long* totals) {
     const int view = blockIdx.x / nbF, f = (blockIdx.x % nbF) * 256 + threadIdx.x;
     long long mine = 0;
     if (f < F) {
-        const MeshFace t = mesh_face(views + 9 * (size_t)view, scale, verts, faces, f);
+        const MeshFace t = mesh_face(views + 9 * (size_t)view, pj.at(view), verts, faces, f);
         const int32_t* vb = boxes + 4 * (size_t)view;
         const int w = vb[2] - vb[0] + 1, h = vb[3] - vb[1] + 1;
         if (t.solid()) {
@@ -260,6 +319,7 @@ __device__ __forceinline__ int mesh_block_scan(int v, int tid, int* sw, int& tot
     }
     return before + incl - v;
 }
+template <class Proj>
 struct MeshEdgeArgs {
     const float* verts;
     const int32_t* faces;
@@ -267,7 +327,8 @@ struct MeshEdgeArgs {
     const uint8_t* sharp;
     int E, nbE;
     const float* views;     // the part's
-    float scale, depth_tol, min_length;
+    Proj proj;
+    float depth_tol, min_length;
     const MeshView* descs;
     const unsigned long long* items;
     int* counts;            // per (view, block, thread)
@@ -280,21 +341,22 @@ struct MeshEdgeArgs {
     int2* meta;             // (edge << 2 | k0 == 0 | (k1 == n) << 1, the view's index in the writing run), beside out
 };
 // Exact visibility: whether some face of the sample's tile hides sample k of n of edge ed at (sx, sy, sz)
-__device__ __forceinline__ bool mesh_hidden(const MeshEdgeArgs& g, const float* __restrict__ R, const MeshView& d, const int4& ed, int k, int n,
-                                            float sx, float sy, float sz) {
+template <class Proj>
+__device__ __forceinline__ bool mesh_hidden(const MeshEdgeArgs<Proj>& g, const float* __restrict__ R, const typename Proj::View& w,
+                                            const MeshView& d, const int4& ed, int k, int n, float sx, float sy, float sz) {
     const unsigned ui = (unsigned)((int)floorf(sx) - d.x0), uj = (unsigned)((int)floorf(sy) - d.y0);
     if (ui >= (unsigned)d.w || uj >= (unsigned)d.h) return false;  // (beyond every face's X or Y range)
     const long long tile = d.off + (long long)(uj >> 3) * mesh_tiles_across(d.w) + (ui >> 3);
     const int* list = g.tiles.pairs + (g.tiles.sums[tile >> 8] + g.tiles.start[tile]);
     const int nf = g.tiles.count[tile];
-    const float limit = sz + g.depth_tol;
+    const float limit = Proj::limit(g.depth_tol, sz);
     for (int q = 0; q < nf; ++q) {
         const int f = list[q];
         if (f == ed.z || f == ed.w) continue;
         const int p0 = g.faces[3 * (size_t)f], p1 = g.faces[3 * (size_t)f + 1], p2 = g.faces[3 * (size_t)f + 2];
         if (k == 0 && (p0 == ed.x || p1 == ed.x || p2 == ed.x)) continue;
         if (k == n && (p0 == ed.y || p1 == ed.y || p2 == ed.y)) continue;
-        const MeshFace t = mesh_face(R, g.scale, g.verts, g.faces, f);
+        const MeshFace t = mesh_face(R, w, g.verts, g.faces, f);
         if (!t.solid()) continue;
         if (!(sx >= fminf(fminf(t.A.X, t.B.X), t.C.X) && sx <= fmaxf(fmaxf(t.A.X, t.B.X), t.C.X))) continue;
         if (!(sy >= fminf(fminf(t.A.Y, t.B.Y), t.C.Y) && sy <= fmaxf(fmaxf(t.A.Y, t.B.Y), t.C.Y))) continue;
@@ -302,7 +364,7 @@ __device__ __forceinline__ bool mesh_hidden(const MeshEdgeArgs& g, const float* 
                     e2 = mesh_orient(t.A.X, t.A.Y, t.B.X, t.B.Y, sx, sy);
         if (!((e0 >= 0.f && e1 >= 0.f && e2 >= 0.f) || (e0 <= 0.f && e1 <= 0.f && e2 <= 0.f))) continue;
         const float zf = ((e0 * t.A.Z + e1 * t.B.Z) + e2 * t.C.Z) / t.a;
-        if (zf > limit) return true;  // (false for a NaN)
+        if (Proj::hidden(limit, sz, zf)) return true;  // (false for a NaN)
     }
     return false;
 }
@@ -315,14 +377,14 @@ __device__ __forceinline__ int mesh_opposite(const int32_t* __restrict__ faces, 
 }
 // the lines of edge e in the view: counted, and with WRITE stored from out[at] on; EXACT: the visibility rule.  One body for
 // both passes and both rules, so the count and the writing pass cannot disagree.
-template <bool WRITE, bool EXACT>
-__device__ __forceinline__ int mesh_walk(const MeshEdgeArgs& g, const float* __restrict__ R, const MeshView& d, int view_in_run, int e,
-                                         long long at) {
+template <bool WRITE, bool EXACT, class Proj>
+__device__ __forceinline__ int mesh_walk(const MeshEdgeArgs<Proj>& g, const float* __restrict__ R, const typename Proj::View& w,
+                                         const MeshView& d, int view_in_run, int e, long long at) {
     const int4 ed = g.edges[e];
-    const MeshPoint A = mesh_project(R, g.scale, g.verts + 3 * (size_t)ed.x), B = mesh_project(R, g.scale, g.verts + 3 * (size_t)ed.y);
+    const MeshPoint A = mesh_project(R, w, g.verts + 3 * (size_t)ed.x), B = mesh_project(R, w, g.verts + 3 * (size_t)ed.y);
     if (!g.sharp[e]) {
-        const MeshPoint c0 = mesh_project(R, g.scale, g.verts + 3 * (size_t)mesh_opposite(g.faces, ed.z, ed.x, ed.y));
-        const MeshPoint c1 = mesh_project(R, g.scale, g.verts + 3 * (size_t)mesh_opposite(g.faces, ed.w, ed.x, ed.y));
+        const MeshPoint c0 = mesh_project(R, w, g.verts + 3 * (size_t)mesh_opposite(g.faces, ed.z, ed.x, ed.y));
+        const MeshPoint c1 = mesh_project(R, w, g.verts + 3 * (size_t)mesh_opposite(g.faces, ed.w, ed.x, ed.y));
         const float o0 = mesh_orient(A.X, A.Y, B.X, B.Y, c0.X, c0.Y), o1 = mesh_orient(A.X, A.Y, B.X, B.Y, c1.X, c1.Y);
         if ((o0 > 0.f && o1 < 0.f) || (o0 < 0.f && o1 > 0.f)) return 0;
     }
@@ -352,15 +414,15 @@ __device__ __forceinline__ int mesh_walk(const MeshEdgeArgs& g, const float* __r
         const unsigned ui = (unsigned)((int)floorf(sx) - d.x0), uj = (unsigned)((int)floorf(sy) - d.y0);
         bool vis = true;
         if (EXACT) {
-            vis = !mesh_hidden(g, R, d, ed, k, n, sx, sy, sz);
+            vis = !mesh_hidden(g, R, w, d, ed, k, n, sx, sy, sz);
         } else if (ui < (unsigned)d.w && uj < (unsigned)d.h) {
             const unsigned long long key = g.items[d.off + (long long)uj * d.w + ui];
             const int f = (int)(unsigned)key;
             if (key != 0 && f != ed.z && f != ed.w) {
-                const MeshFace occ = mesh_face(R, g.scale, g.verts, g.faces, f);
+                const MeshFace occ = mesh_face(R, w, g.verts, g.faces, f);
                 float zf;
                 (void)occ.depth(sx, sy, zf);
-                vis = sz + g.depth_tol >= zf;
+                vis = Proj::visible(Proj::limit(g.depth_tol, sz), sz, zf);
             }
         }
         if (vis) {
@@ -373,22 +435,22 @@ __device__ __forceinline__ int mesh_walk(const MeshEdgeArgs& g, const float* __r
     if (open) close();
     return count;
 }
-template <bool WRITE, bool EXACT>
-__global__ void __launch_bounds__(256) k_mesh_edges(MeshEdgeArgs g) {
+template <bool WRITE, bool EXACT, class Proj>
+__global__ void __launch_bounds__(256) k_mesh_edges(MeshEdgeArgs<Proj> g) {
     __shared__ int sw[4];
     const int block = (WRITE ? g.block0 : 0) + (int)blockIdx.x;
     const int view = block / g.nbE, e = (block % g.nbE) * 256 + threadIdx.x;
     const size_t slot = (size_t)block * 256 + threadIdx.x;
     int total;
     if (!WRITE) {
-        const int c = e < g.E ? mesh_walk<false, EXACT>(g, g.views + 9 * (size_t)view, g.descs[view], 0, e, 0) : 0;
+        const int c = e < g.E ? mesh_walk<false, EXACT>(g, g.views + 9 * (size_t)view, g.proj.at(view), g.descs[view], 0, e, 0) : 0;
         g.counts[slot] = c;
         mesh_block_scan(c, threadIdx.x, sw, total);
         if (threadIdx.x == 0) g.sums[block] = total;
     } else {
         const int c = g.counts[slot];
         const long long at = g.sums[block] - g.out0 + mesh_block_scan(c, threadIdx.x, sw, total);
-        if (c) mesh_walk<true, EXACT>(g, g.views + 9 * (size_t)view, g.descs[view], view - g.block0 / g.nbE, e, at);
+        if (c) mesh_walk<true, EXACT>(g, g.views + 9 * (size_t)view, g.proj.at(view), g.descs[view], view - g.block0 / g.nbE, e, at);
     }
 }
 // sums[0 .. nb) -> their exclusive prefix sums in place, sums[nb] = the total (a block's sum is below 2^20: 256 edges of at most
@@ -414,11 +476,13 @@ __global__ void __launch_bounds__(256) k_mesh_scan(long long* sums, int nb) {
 // within a view is the definition's lower index.  An end is (line << 1 | end), end 0 the start (k0), 1 the finish (k1).
 // links: 3 words per (view of the run, vertex): the number of ends there and the first two of them.
 static constexpr int kMeshJoinSpan = 256;  // the most segments one joined line replaces
+template <class Proj>
 struct MeshJoinArgs {
     const float* verts;
     const int4* edges;
     const float* views;     // the run's
-    float scale, tol2, min_length;
+    Proj proj;
+    float tol2, min_length;
     const float4* pre;
     const int2* meta;
     int* links;
@@ -427,14 +491,16 @@ struct MeshJoinArgs {
     long long* sums;        // per 256 lines; scanned before the writing pass
     float4* out;
 };
-__device__ __forceinline__ int mesh_end_vertex(const MeshJoinArgs& g, int i, int end) {  // -1: the end lies inside its edge
+template <class Args>
+__device__ __forceinline__ int mesh_end_vertex(const Args& g, int i, int end) {  // -1: the end lies inside its edge
     const int m = g.meta[i].x;
     if (!((m >> end) & 1)) return -1;
     const int4 ed = g.edges[m >> 2];
     return end ? ed.y : ed.x;
 }
 // the end linked to end `end` of line i, if there is one
-__device__ __forceinline__ bool mesh_linked(const MeshJoinArgs& g, int i, int end, int& j, int& ej) {
+template <class Args>
+__device__ __forceinline__ bool mesh_linked(const Args& g, int i, int end, int& j, int& ej) {
     const int v = mesh_end_vertex(g, i, end);
     if (v < 0) return false;
     const int* l = g.links + 3 * ((size_t)g.meta[i].y * g.V + v);
@@ -443,16 +509,18 @@ __device__ __forceinline__ bool mesh_linked(const MeshJoinArgs& g, int i, int en
     j = s >> 1; ej = s & 1;
     return true;
 }
-__device__ __forceinline__ float2 mesh_end_point(const MeshJoinArgs& g, int i, int end) {
+template <class Args>
+__device__ __forceinline__ float2 mesh_end_point(const Args& g, int i, int end) {
     const int v = mesh_end_vertex(g, i, end);
     if (v >= 0) {
-        const MeshPoint p = mesh_project(g.views + 9 * (size_t)g.meta[i].y, g.scale, g.verts + 3 * (size_t)v);
+        const MeshPoint p = mesh_project(g.views + 9 * (size_t)g.meta[i].y, g.proj.at(g.meta[i].y), g.verts + 3 * (size_t)v);
         return make_float2(p.X, p.Y);
     }
     const float4 l = g.pre[i];
     return end ? make_float2(l.z, l.w) : make_float2(l.x, l.y);
 }
-__global__ void __launch_bounds__(256) k_mesh_links(MeshJoinArgs g) {
+template <class Proj>
+__global__ void __launch_bounds__(256) k_mesh_links(MeshJoinArgs<Proj> g) {
     const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
     if (u >= 2ll * g.L) return;
     const int i = (int)(u >> 1), end = (int)(u & 1);
@@ -464,7 +532,8 @@ __global__ void __launch_bounds__(256) k_mesh_links(MeshJoinArgs g) {
 }
 // Whether line i starts a chain, and the end the chain enters it at.  Every walk follows links, which pair ends two by two, so
 // it ends at a free end or where it began; the step limit L only keeps a damaged table from hanging the lane.
-__device__ __forceinline__ bool mesh_chain_start(const MeshJoinArgs& g, int i, int& enter) {
+template <class Args>
+__device__ __forceinline__ bool mesh_chain_start(const Args& g, int i, int& enter) {
     int j, ej;
     const bool linked0 = mesh_linked(g, i, 0, j, ej), linked1 = mesh_linked(g, i, 1, j, ej);
     if (!linked0 || !linked1) {  // an end line of a path: it starts it when the line at the other free end has no lower index
@@ -485,7 +554,8 @@ __device__ __forceinline__ bool mesh_chain_start(const MeshJoinArgs& g, int i, i
 // A chain point: an end of a line.  P_0 is the end the chain enters its first line at; every later point is the far end of
 // the next line.
 struct MeshChainAt { int line, end; bool first; };
-__device__ __forceinline__ bool mesh_chain_next(const MeshJoinArgs& g, int i0, int enter0, MeshChainAt& p) {
+template <class Args>
+__device__ __forceinline__ bool mesh_chain_next(const Args& g, int i0, int enter0, MeshChainAt& p) {
     if (p.first) { p.end = 1 - p.end; p.first = false; return true; }
     int j, ej;
     if (!mesh_linked(g, p.line, p.end, j, ej) || (j == i0 && ej == enter0)) return false;  // a free end, or the cycle is closed
@@ -493,8 +563,8 @@ __device__ __forceinline__ bool mesh_chain_next(const MeshJoinArgs& g, int i0, i
     return true;
 }
 // the greedy simplification of the chain that starts with line i0: its lines counted, and with WRITE stored from out[at] on
-template <bool WRITE>
-__device__ __forceinline__ int mesh_chain_lines(const MeshJoinArgs& g, int i0, int enter0, long long at) {
+template <bool WRITE, class Args>
+__device__ __forceinline__ int mesh_chain_lines(const Args& g, int i0, int enter0, long long at) {
     int count = 0;
     auto emit = [&](float2 p, float2 q) {
         const float ddx = q.x - p.x, ddy = q.y - p.y;
@@ -536,8 +606,8 @@ __device__ __forceinline__ int mesh_chain_lines(const MeshJoinArgs& g, int i0, i
     emit(Pa, Pc);
     return count;
 }
-template <bool WRITE>
-__global__ void __launch_bounds__(256) k_mesh_chains(MeshJoinArgs g) {
+template <bool WRITE, class Proj>
+__global__ void __launch_bounds__(256) k_mesh_chains(MeshJoinArgs<Proj> g) {
     __shared__ int sw[4];
     const int i = (int)blockIdx.x * 256 + threadIdx.x;  // (counts holds 256 words per block)
     int total, enter;
@@ -631,11 +701,13 @@ size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 // What a call holds on the device, in PixelScratch's members: keys -- the views, the mesh's tables and the part's view
 // records; comps -- the boxes; pixels -- the part's item buffers; parent -- its list of large faces; counts -- its per-edge
 // counts and block sums; out -- its lines.
+// The pinhole's positions, where it has them, lie behind the view records in keys.
+template <class Proj>
 struct MeshDevice {
     PixelScratch s;
     const fdcm_mesh* m;
     int64_t n_views;
-    float scale;
+    Proj proj;                   // of view 0 on: a part or a run takes proj.from(its first view)
     const float *views, *verts;
     const int32_t* faces;
     const int4* edges;
@@ -650,13 +722,19 @@ struct MeshDevice {
     int nbF256() const { return (int)((m->F + 255) / 256); }
 
     // uploads the mesh and the views, runs the projection pass and refuses the views it must
-    MeshDevice(const fdcm_mesh* mesh, const float* host_views, int64_t n, float sc, bool exact_ = false, bool join_ = false)
-        : m(mesh), n_views(n), scale(sc), exact(exact_), join(join_) {
+    MeshDevice(const fdcm_mesh* mesh, const float* host_views, const float* host_positions, int64_t n, Proj pj, bool exact_ = false,
+               bool join_ = false)
+        : m(mesh), n_views(n), proj(pj), exact(exact_), join(join_) {
         const size_t o_views = 0, o_verts = align16((size_t)n * 36), o_faces = align16(o_verts + (size_t)m->V * 12),
                      o_edges = align16(o_faces + (size_t)m->F * 12), o_sharp = o_edges + (size_t)m->E * 16,
-                     o_descs = align16(o_sharp + (size_t)m->E), bytes = o_descs + (size_t)n * sizeof(MeshView);
+                     o_descs = align16(o_sharp + (size_t)m->E), o_positions = align16(o_descs + (size_t)n * sizeof(MeshView)),
+                     bytes = host_positions ? o_positions + (size_t)n * 12 : o_descs + (size_t)n * sizeof(MeshView);
         s.take(s.keys, bytes, FDCM_FILL_PIXEL_KEYS);
         char* base = (char*)s.keys.p;
+        if constexpr (std::is_same<Proj, MeshPinhole>::value) {
+            FDCM_HIP(hipMemcpy(base + o_positions, host_positions, (size_t)n * 12, hipMemcpyHostToDevice));
+            proj.positions = (const float*)(base + o_positions);
+        }
         FDCM_HIP(hipMemcpy(base + o_views, host_views, (size_t)n * 36, hipMemcpyHostToDevice));
         FDCM_HIP(hipMemcpy(base + o_verts, m->vertices.data(), (size_t)m->V * 12, hipMemcpyHostToDevice));
         FDCM_HIP(hipMemcpy(base + o_faces, m->faces.data(), (size_t)m->F * 12, hipMemcpyHostToDevice));
@@ -669,19 +747,21 @@ struct MeshDevice {
         s.take(s.comps, boxes.size() * 4 + (exact ? (size_t)n * 8 : 0), FDCM_FILL_PIXEL_COMPS);  // (exact: the views' pair totals behind)
         FDCM_HIP(hipMemcpy(s.comps.p, boxes.data(), boxes.size() * 4, hipMemcpyHostToDevice));
         const int nbV = (int)((m->V + 255) / 256);  // (at most 2^14 blocks a view and 2^16 views: one grid)
-        hipLaunchKernelGGL(k_mesh_boxes, dim3((unsigned)(nbV * n)), dim3(256), 0, nullptr, verts, (int)m->V, nbV, views, scale, s.comps.as<int32_t>());
+        hipLaunchKernelGGL(k_mesh_boxes<Proj>, dim3((unsigned)(nbV * n)), dim3(256), 0, nullptr, verts, (int)m->V, nbV, views, proj,
+                           s.comps.as<int32_t>());
         FDCM_HIP(hipGetLastError());
         FDCM_HIP(hipMemcpy(boxes.data(), s.comps.p, boxes.size() * 4, hipMemcpyDeviceToHost));
         for (int64_t v = 0; v < n; ++v) {
             const int64_t w = (int64_t)boxes[4 * v + 2] - boxes[4 * v] + 1, h = (int64_t)boxes[4 * v + 3] - boxes[4 * v + 1] + 1;
             if (w > kMeshMaxSpan || h > kMeshMaxSpan)
-                throw std::string("view " + std::to_string(v) + " spans more than 4096 pixels on a side (or a coordinate is not below 2^30)");
+                throw std::string("view " + std::to_string(v) + " spans more than 4096 pixels on a side (or a coordinate is not below 2^30" +
+                                  (std::is_same<Proj, MeshPinhole>::value ? ", or a vertex is nearer than `near`)" : ")"));
         }
         if (!exact) return;
         // the (face, tile) pairs of every view: what its lists take
         unsigned long long* totals = reinterpret_cast<unsigned long long*>(s.comps.as<int32_t>() + boxes.size());
         FDCM_HIP(hipMemsetAsync(totals, 0, (size_t)n * 8, nullptr));
-        hipLaunchKernelGGL(k_mesh_tiles<0>, dim3((unsigned)(nbF256() * n)), dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF256(), views, scale,
+        hipLaunchKernelGGL((k_mesh_tiles<0, Proj>), dim3((unsigned)(nbF256() * n)), dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF256(), views, proj,
                            (const int32_t*)s.comps.as<int32_t>(), (const MeshView*)nullptr, MeshTiles{}, totals);
         FDCM_HIP(hipGetLastError());
         pairs.resize((size_t)n);
@@ -723,9 +803,10 @@ struct MeshDevice {
         FDCM_HIP(hipMemsetAsync(s.pixels.p, 0, total * 8, nullptr));
         FDCM_HIP(hipMemsetAsync(s.parent.p, 0, 8, nullptr));
         const float* pv = views + 9 * (size_t)v0;
-        hipLaunchKernelGGL(k_mesh_raster, dim3((unsigned)(P * nbF())), dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF(), pv, scale,
+        const Proj pp = proj.from(v0);
+        hipLaunchKernelGGL(k_mesh_raster<Proj>, dim3((unsigned)(P * nbF())), dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF(), pv, pp,
                            (const MeshView*)descs, s.pixels.as<unsigned long long>(), s.parent.as<unsigned long long>());
-        hipLaunchKernelGGL(k_mesh_raster_big, dim3(kBigGrid), dim3(256), 0, nullptr, verts, faces, pv, scale, (const MeshView*)descs,
+        hipLaunchKernelGGL(k_mesh_raster_big<Proj>, dim3(kBigGrid), dim3(256), 0, nullptr, verts, faces, pv, pp, (const MeshView*)descs,
                            s.pixels.as<unsigned long long>(), (const unsigned long long*)s.parent.as<unsigned long long>());
         FDCM_HIP(hipGetLastError());
         return total;
@@ -753,11 +834,12 @@ struct MeshDevice {
         const float* pv = views + 9 * (size_t)v0;
         const int32_t* pb = s.comps.as<int32_t>() + 4 * (size_t)v0;
         const dim3 grid((unsigned)(P * nbF256()));
-        hipLaunchKernelGGL(k_mesh_tiles<1>, grid, dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF256(), pv, scale, pb, (const MeshView*)descs, tiles,
+        const Proj pp = proj.from(v0);
+        hipLaunchKernelGGL((k_mesh_tiles<1, Proj>), grid, dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF256(), pv, pp, pb, (const MeshView*)descs, tiles,
                            (unsigned long long*)nullptr);
         hipLaunchKernelGGL(k_mesh_tile_starts, dim3((unsigned)nbT), dim3(256), 0, nullptr, tiles, (long long)T);
         hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(256), 0, nullptr, tiles.sums, (int)nbT);
-        hipLaunchKernelGGL(k_mesh_tiles<2>, grid, dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF256(), pv, scale, pb, (const MeshView*)descs, tiles,
+        hipLaunchKernelGGL((k_mesh_tiles<2, Proj>), grid, dim3(256), 0, nullptr, verts, faces, (int)m->F, nbF256(), pv, pp, pb, (const MeshView*)descs, tiles,
                            (unsigned long long*)nullptr);
         FDCM_HIP(hipGetLastError());
     }
@@ -791,18 +873,20 @@ struct JoinRun {
         bytes = o_links + (size_t)views * (size_t)V * 12;
     }
 };
-void join_run(MeshDevice& dev, const JoinRun& r, const float* run_views, long long lines, std::vector<long long>& starts, float tol, float min_length) {
+template <class Proj>
+void join_run(MeshDevice<Proj>& dev, const JoinRun& r, const float* run_views, const Proj& run_proj, long long lines, std::vector<long long>& starts,
+              float tol, float min_length) {
     char* base = (char*)dev.s.labels.p;
     const size_t views = starts.size() - 1;
-    MeshJoinArgs j;
-    j.verts = dev.verts; j.edges = dev.edges; j.views = run_views; j.scale = dev.scale; j.tol2 = tol * tol; j.min_length = min_length;
+    MeshJoinArgs<Proj> j;
+    j.verts = dev.verts; j.edges = dev.edges; j.views = run_views; j.proj = run_proj; j.tol2 = tol * tol; j.min_length = min_length;
     j.pre = (const float4*)base; j.meta = (const int2*)(base + r.o_meta); j.links = (int*)(base + r.o_links); j.V = (int)dev.m->V; j.L = (int)lines;
     j.counts = (int*)(base + r.o_counts); j.sums = (long long*)(base + r.o_sums); j.out = nullptr;
     long long* d_starts = (long long*)(base + r.o_starts);
     FDCM_HIP(hipMemsetAsync(j.links, 0, views * (size_t)dev.m->V * 12, nullptr));
     FDCM_HIP(hipMemcpy(d_starts, starts.data(), starts.size() * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_mesh_links, dim3((unsigned)((2 * lines + 255) / 256)), dim3(256), 0, nullptr, j);
-    hipLaunchKernelGGL(k_mesh_chains<false>, dim3((unsigned)r.nbL), dim3(256), 0, nullptr, j);
+    hipLaunchKernelGGL(k_mesh_links<Proj>, dim3((unsigned)((2 * lines + 255) / 256)), dim3(256), 0, nullptr, j);
+    hipLaunchKernelGGL((k_mesh_chains<false, Proj>), dim3((unsigned)r.nbL), dim3(256), 0, nullptr, j);
     hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(256), 0, nullptr, j.sums, r.nbL);
     hipLaunchKernelGGL(k_mesh_starts, dim3((unsigned)((starts.size() + 255) / 256)), dim3(256), 0, nullptr, (const int*)j.counts, (const long long*)j.sums,
                        d_starts, (int)starts.size());
@@ -811,24 +895,26 @@ void join_run(MeshDevice& dev, const JoinRun& r, const float* run_views, long lo
     const long long joined = starts.back();
     if (joined == 0) return;
     dev.s.take(dev.s.out, (size_t)joined * 16, FDCM_FILL_PIXEL_OUT);
-    j.out = dev.s.out.as<float4>();
-    hipLaunchKernelGGL(k_mesh_chains<true>, dim3((unsigned)r.nbL), dim3(256), 0, nullptr, j);
+    j.out = dev.s.out.template as<float4>();
+    hipLaunchKernelGGL((k_mesh_chains<true, Proj>), dim3((unsigned)r.nbL), dim3(256), 0, nullptr, j);
     FDCM_HIP(hipGetLastError());
 }
-void launch_edges(const MeshEdgeArgs& g, bool write, bool exact, int blocks) {
+template <class Proj>
+void launch_edges(const MeshEdgeArgs<Proj>& g, bool write, bool exact, int blocks) {
     const dim3 grid((unsigned)blocks), wg(256);
-    if (write && exact) hipLaunchKernelGGL((k_mesh_edges<true, true>), grid, wg, 0, nullptr, g);
-    else if (write) hipLaunchKernelGGL((k_mesh_edges<true, false>), grid, wg, 0, nullptr, g);
-    else if (exact) hipLaunchKernelGGL((k_mesh_edges<false, true>), grid, wg, 0, nullptr, g);
-    else hipLaunchKernelGGL((k_mesh_edges<false, false>), grid, wg, 0, nullptr, g);
+    if (write && exact) hipLaunchKernelGGL((k_mesh_edges<true, true, Proj>), grid, wg, 0, nullptr, g);
+    else if (write) hipLaunchKernelGGL((k_mesh_edges<true, false, Proj>), grid, wg, 0, nullptr, g);
+    else if (exact) hipLaunchKernelGGL((k_mesh_edges<false, true, Proj>), grid, wg, 0, nullptr, g);
+    else hipLaunchKernelGGL((k_mesh_edges<false, false, Proj>), grid, wg, 0, nullptr, g);
 }
-}  // namespace
 
-void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t n_views, float scale, const fdcm_mesh_line_params& p,
-                     float** lines_out, int64_t* offsets_out) {
+// the driver of both projections: parts, writing runs, join passes
+template <class Proj>
+void view_lines(int device, const fdcm_mesh* m, const float* views, const float* positions, int64_t n_views, Proj pj, const fdcm_mesh_line_params& p,
+                float** lines_out, int64_t* offsets_out) {
     FDCM_HIP(hipSetDevice(device));
     const bool exact = p.visibility == FDCM_MESH_VIS_EXACT, join = p.join_tolerance >= 0.f;
-    MeshDevice dev(m, views, n_views, scale, exact, join);
+    MeshDevice<Proj> dev(m, views, positions, n_views, pj, exact, join);
     HostLines host;
     std::vector<int64_t> offsets((size_t)n_views + 1, 0);
     std::vector<long long> view_at, starts;
@@ -839,12 +925,12 @@ void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t
         if (exact) dev.bin(v0, P); else dev.raster(v0, P);
         const int nb = (int)(P * nbE);
         dev.s.take(dev.s.counts, (size_t)nb * 256 * 4 + ((size_t)nb + 1) * 8, FDCM_FILL_PIXEL_COUNTS);
-        MeshEdgeArgs g;
+        MeshEdgeArgs<Proj> g;
         g.verts = dev.verts; g.faces = dev.faces; g.edges = dev.edges; g.sharp = dev.sharp; g.E = (int)m->E; g.nbE = nbE;
-        g.views = dev.views + 9 * (size_t)v0; g.scale = scale; g.depth_tol = p.depth_tol; g.min_length = p.min_length;
-        g.descs = dev.descs; g.items = exact ? nullptr : dev.s.pixels.as<unsigned long long>(); g.tiles = dev.tiles;
+        g.views = dev.views + 9 * (size_t)v0; g.proj = dev.proj.from(v0); g.depth_tol = p.depth_tol; g.min_length = p.min_length;
+        g.descs = dev.descs; g.items = exact ? nullptr : dev.s.pixels.template as<unsigned long long>(); g.tiles = dev.tiles;
         g.join = join ? 1 : 0; g.meta = nullptr;
-        g.sums = dev.s.counts.as<long long>(); g.counts = (int*)(g.sums + nb + 1); g.out = nullptr; g.block0 = 0; g.out0 = 0;
+        g.sums = dev.s.counts.template as<long long>(); g.counts = (int*)(g.sums + nb + 1); g.out = nullptr; g.block0 = 0; g.out0 = 0;
         launch_edges(g, false, exact, nb);
         hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(256), 0, nullptr, g.sums, nb);
         FDCM_HIP(hipGetLastError());
@@ -874,11 +960,11 @@ void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t
                 if (lines > 0) {
                     const JoinRun r(lines, b - a, m->V);
                     dev.s.take(dev.s.labels, r.bytes, FDCM_FILL_PIXEL_LABELS);
-                    g.out = dev.s.labels.as<float4>(); g.meta = (int2*)((char*)dev.s.labels.p + r.o_meta);
+                    g.out = dev.s.labels.template as<float4>(); g.meta = (int2*)((char*)dev.s.labels.p + r.o_meta);
                     g.block0 = (int)(a * nbE); g.out0 = view_at[(size_t)a];
                     launch_edges(g, true, exact, (int)((b - a) * nbE));
                     FDCM_HIP(hipGetLastError());
-                    join_run(dev, r, g.views + 9 * (size_t)a, lines, starts, p.join_tolerance, p.min_length);
+                    join_run(dev, r, g.views + 9 * (size_t)a, g.proj.from(a), lines, starts, p.join_tolerance, p.min_length);
                 }
                 const long long joined = starts.back();
                 if (done + joined >= ((int64_t)1 << 31)) throw std::string("the views give 2^31 lines or more");
@@ -890,7 +976,7 @@ void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t
                 done += joined;
             } else if (lines > 0) {
                 dev.s.take(dev.s.out, (size_t)lines * 16, FDCM_FILL_PIXEL_OUT);
-                g.out = dev.s.out.as<float4>(); g.block0 = (int)(a * nbE); g.out0 = view_at[(size_t)a];
+                g.out = dev.s.out.template as<float4>(); g.block0 = (int)(a * nbE); g.out0 = view_at[(size_t)a];
                 launch_edges(g, true, exact, (int)((b - a) * nbE));
                 FDCM_HIP(hipGetLastError());
                 FDCM_HIP(hipMemcpy(host.p + 4 * (size_t)(done + view_at[(size_t)a]), dev.s.out.p, (size_t)lines * 16, hipMemcpyDeviceToHost));
@@ -904,16 +990,34 @@ void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t
     std::copy(offsets.begin(), offsets.end(), offsets_out);
     if (done > 0) { *lines_out = host.p; host.p = nullptr; }
 }
-
-void mesh_view_items(int device, const fdcm_mesh* m, const float* view, float scale, int32_t* box_out, uint64_t* keys_out, int64_t capacity) {
+template <class Proj>
+void view_items(int device, const fdcm_mesh* m, const float* view, const float* position, Proj pj, int32_t* box_out, uint64_t* keys_out,
+                int64_t capacity) {
     FDCM_HIP(hipSetDevice(device));
-    MeshDevice dev(m, view, 1, scale);
+    MeshDevice<Proj> dev(m, view, position, 1, pj);
     std::copy(dev.boxes.begin(), dev.boxes.end(), box_out);
     if (!keys_out) return;
     if ((int64_t)dev.view_items(0) > capacity)
         throw std::string("keys_out holds " + std::to_string(capacity) + " keys, the view's box has " + std::to_string(dev.view_items(0)));
     const size_t total = dev.raster(0, 1);
     FDCM_HIP(hipMemcpy(keys_out, dev.s.pixels.p, total * 8, hipMemcpyDeviceToHost));
+}
+}  // namespace
+
+void mesh_view_lines(int device, const fdcm_mesh* m, const float* views, int64_t n_views, float scale, const fdcm_mesh_line_params& p,
+                     float** lines_out, int64_t* offsets_out) {
+    view_lines(device, m, views, nullptr, n_views, MeshOrtho{scale}, p, lines_out, offsets_out);
+}
+void mesh_view_items(int device, const fdcm_mesh* m, const float* view, float scale, int32_t* box_out, uint64_t* keys_out, int64_t capacity) {
+    view_items(device, m, view, nullptr, MeshOrtho{scale}, box_out, keys_out, capacity);
+}
+void mesh_view_lines_cam(int device, const fdcm_mesh* m, const float* views, const float* positions, int64_t n_views, const fdcm_mesh_camera& cam,
+                         const fdcm_mesh_line_params& p, float** lines_out, int64_t* offsets_out) {
+    view_lines(device, m, views, positions, n_views, MeshPinhole{cam.focal, cam.near, nullptr}, p, lines_out, offsets_out);
+}
+void mesh_view_items_cam(int device, const fdcm_mesh* m, const float* view, const float* position, const fdcm_mesh_camera& cam, int32_t* box_out,
+                         uint64_t* keys_out, int64_t capacity) {
+    view_items(device, m, view, position, MeshPinhole{cam.focal, cam.near, nullptr}, box_out, keys_out, capacity);
 }
 
 }  // namespace fdcm

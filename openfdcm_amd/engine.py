@@ -1230,6 +1230,11 @@ class Mesh:
         d = self.vertices.astype(np.float64).max(axis=0) - self.vertices.astype(np.float64).min(axis=0)
         return np.float32(1e-4 * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))
 
+    def default_near(self):
+        """float32(1e-3 * the diagonal of the vertices' bounding box): the pinhole calls' near distance."""
+        d = self.vertices.astype(np.float64).max(axis=0) - self.vertices.astype(np.float64).min(axis=0)
+        return np.float32(1e-3 * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))
+
     def close(self):
         if self._h:
             capi.lib().fdcm_mesh_free(self._h)
@@ -1254,17 +1259,45 @@ def _views(views):
 MESH_VISIBILITY = {"items": capi.MESH_VIS_ITEMS, "exact": capi.MESH_VIS_EXACT}
 
 
-def mesh_view_lines(mesh, views, scale, depth_tolerance=None, min_length=2.0, visibility="items", join_tolerance=None):
+def _camera(mesh, n_views, scale, focal, positions, near):
+    """None for the orthographic call; else (fdcm_mesh_camera, positions (n_views, 3) float32) of the pinhole one.  Exactly one of
+    scale and focal is given."""
+    if (scale is None) == (focal is None):
+        raise ValueError("exactly one of scale (orthographic) and focal (pinhole) must be given")
+    if focal is None:
+        if positions is not None or near is not None:
+            raise ValueError("positions and near belong to the pinhole call: give focal, not scale")
+        return None
+    if positions is None:
+        raise ValueError("a pinhole call needs positions (view_positions makes them)")
+    t = np.ascontiguousarray(positions, dtype=np.float32)
+    if t.shape == (3,):
+        t = np.ascontiguousarray(np.broadcast_to(t, (n_views, 3)))
+    if t.shape != (n_views, 3):
+        raise ValueError(f"positions must be (3,) or ({n_views}, 3), got {t.shape}")
+    if near is None:
+        near = mesh.default_near()
+    return capi.MeshCamera(float(focal), float(near)), t
+
+
+def mesh_view_lines(mesh, views, scale=None, depth_tolerance=None, min_length=2.0, visibility="items", join_tolerance=None, *,
+                    focal=None, positions=None, near=None):
     """fdcm_mesh_view_lines_ex as it is: ((N, 4) float32 line records of all views, int64 offsets of n_views + 1).  visibility:
-    "items" or "exact" (an integer goes to the library as it is); join_tolerance: pixels, None for no joining."""
+    "items" or "exact" (an integer goes to the library as it is); join_tolerance: pixels, None for no joining.  With focal=
+    (and positions=, near=) in place of scale: fdcm_mesh_view_lines_cam, the pinhole views."""
     r = _views(views)
+    cam = _camera(mesh, r.shape[0], scale, focal, positions, near)
     tol = mesh.default_depth_tolerance() if depth_tolerance is None else depth_tolerance
     offsets = np.zeros(r.shape[0] + 1, dtype=np.int64)
     out = C.POINTER(C.c_float)()
     params = capi.MeshLineParams(float(tol), float(min_length), int(MESH_VISIBILITY.get(visibility, visibility)),
                                  -1.0 if join_tolerance is None else float(join_tolerance))
-    capi.check(capi.lib().fdcm_mesh_view_lines_ex(mesh._h, capi.fptr(r), r.shape[0], float(scale), C.byref(params),
-                                                  C.byref(out), offsets.ctypes.data_as(C.POINTER(C.c_int64))))
+    if cam is None:
+        capi.check(capi.lib().fdcm_mesh_view_lines_ex(mesh._h, capi.fptr(r), r.shape[0], float(scale), C.byref(params),
+                                                      C.byref(out), offsets.ctypes.data_as(C.POINTER(C.c_int64))))
+    else:
+        capi.check(capi.lib().fdcm_mesh_view_lines_cam(mesh._h, capi.fptr(r), capi.fptr(cam[1]), r.shape[0], C.byref(cam[0]),
+                                                       C.byref(params), C.byref(out), offsets.ctypes.data_as(C.POINTER(C.c_int64))))
     n = int(offsets[-1])
     try:
         rec = np.ctypeslib.as_array(out, shape=(n, 4)).copy() if n else np.zeros((0, 4), dtype=np.float32)
@@ -1274,31 +1307,59 @@ def mesh_view_lines(mesh, views, scale, depth_tolerance=None, min_length=2.0, vi
     return rec, offsets
 
 
-def templates_from_mesh(mesh, views, scale, depth_tolerance=None, min_length=2.0, visibility="items", join_tolerance=None):
+def templates_from_mesh(mesh, views, scale=None, depth_tolerance=None, min_length=2.0, visibility="items", join_tolerance=None, *,
+                        focal=None, positions=None, near=None):
     """The line template of every view of a mesh, computed on the GPU (include/fdcm.h, "Templates from a mesh"): a list of (4, N)
     float32 arrays, template t being view t, with the projection of the mesh origin at (0, 0).  views: (n, 3, 3) rotations
     (view_rotations makes them); scale: pixels per mesh unit; depth_tolerance: mesh units, None for 1e-4 of the bounding box's
-    diagonal; min_length: the shortest line kept, in pixels.  Orthographic.  For a smooth, tessellated part take
-    visibility="exact" (every face is tested at the sample itself, not the one that owns its pixel) and a join_tolerance in
-    pixels, such as 0.5 (the contour's runs are chained at shared vertices and simplified before min_length applies): the
-    defaults keep only fragments of such an outline."""
-    rec, offsets = mesh_view_lines(mesh, views, scale, depth_tolerance, min_length, visibility, join_tolerance)
+    diagonal; min_length: the shortest line kept, in pixels.  For a smooth, tessellated part take visibility="exact" (every
+    face is tested at the sample itself, not the one that owns its pixel) and a join_tolerance in pixels, such as 0.5 (the
+    contour's runs are chained at shared vertices and simplified before min_length applies): the defaults keep only
+    fragments of such an outline.
+    Orthographic with scale=; a pinhole camera with focal= in its place (exactly one of the two): focal in pixels, positions
+    (n, 3) or (3,), where the mesh origin lies in the camera's frame for each view -- the camera at the origin looks down -Z,
+    so positions[:, 2] < 0, and view_positions(n, distance) makes the on-axis ones -- and near in mesh units, None for 1e-3
+    of the bounding box's diagonal: a view with a vertex nearer than that is refused ("Templates from a mesh: pinhole
+    views")."""
+    rec, offsets = mesh_view_lines(mesh, views, scale, depth_tolerance, min_length, visibility, join_tolerance, focal=focal,
+                                   positions=positions, near=near)
     return [np.ascontiguousarray(rec[offsets[i]:offsets[i + 1]].T) for i in range(len(offsets) - 1)]
 
 
-def mesh_view_items(mesh, view, scale):
-    """Test hook (fdcm_mesh_view_items): one view's pixel box (x0, y0, x1, y1) and its item buffer, (rows, columns) uint64."""
+def mesh_view_items(mesh, view, scale=None, *, focal=None, positions=None, near=None):
+    """Test hook (fdcm_mesh_view_items, or with focal= fdcm_mesh_view_items_cam): one view's pixel box (x0, y0, x1, y1) and its
+    item buffer, (rows, columns) uint64."""
     r = _views(view)
     if r.shape[0] != 1:
         raise ValueError("one view")
+    cam = _camera(mesh, 1, scale, focal, positions, near)
     box = np.zeros(4, dtype=np.int32)
     i32 = C.POINTER(C.c_int32)
-    capi.check(capi.lib().fdcm_mesh_view_items(mesh._h, capi.fptr(r), float(scale), box.ctypes.data_as(i32), None, 0))
+
+    def call(keys, capacity):
+        if cam is None:
+            capi.check(capi.lib().fdcm_mesh_view_items(mesh._h, capi.fptr(r), float(scale), box.ctypes.data_as(i32), keys, capacity))
+        else:
+            capi.check(capi.lib().fdcm_mesh_view_items_cam(mesh._h, capi.fptr(r), capi.fptr(cam[1]), C.byref(cam[0]),
+                                                           box.ctypes.data_as(i32), keys, capacity))
+    call(None, 0)
     w, h = int(box[2]) - int(box[0]) + 1, int(box[3]) - int(box[1]) + 1
     keys = np.empty((h, w), dtype=np.uint64)
-    capi.check(capi.lib().fdcm_mesh_view_items(mesh._h, capi.fptr(r), float(scale), box.ctypes.data_as(i32),
-                                               keys.ctypes.data_as(C.POINTER(C.c_uint64)), keys.size))
+    call(keys.ctypes.data_as(C.POINTER(C.c_uint64)), keys.size)
     return tuple(int(b) for b in box), keys
+
+
+def view_positions(n, distance):
+    """n positions (0, 0, -distance), (n, 3) float32: the mesh origin on the optical axis of a pinhole camera, `distance` mesh
+    units in front of it."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    if not (np.isfinite(distance) and distance > 0):
+        raise ValueError("distance must be finite and > 0")
+    t = np.zeros((n, 3), dtype=np.float32)
+    t[:, 2] = -np.float32(distance)
+    return t
 
 
 def view_rotations(n, hemisphere=True):
@@ -1338,6 +1399,41 @@ def record_rotations(records, views):
     rz = np.zeros((len(rec), 3, 3), dtype=np.float64)
     rz[:, 0, 0], rz[:, 0, 1], rz[:, 1, 0], rz[:, 1, 1], rz[:, 2, 2] = tr[:, 0], -tr[:, 3], tr[:, 3], tr[:, 0], 1.0
     return rz @ v[idx], tr[:, [2, 5]].copy()
+
+
+def record_camera_poses(records, views, positions, focal, principal=(0.0, 0.0)):
+    """The pose of the object in the camera's frame per match record of pinhole templates, pure numpy float64: ((n, 3, 3)
+    rotations R_obj, (n, 3) translations T_obj), a mesh point v lying at R_obj v + T_obj in front of a camera that looks down
+    -Z with focal length `focal` (pixels) and the principal point `principal` (image pixels).  With Rz from the record's
+    (c, s) = (transform[0], transform[3]), (x, y) = (transform[2], transform[5]), t_v = positions[tmpl_idx], d0 = -t_v.z,
+    O_v = focal (t_v.x, t_v.y) / d0 and delta = (x, y) - principal - Rz O_v:
+        R_obj = Rz . views[tmpl_idx],    T_obj = Rz t_v + (delta.x d0 / focal, delta.y d0 / focal, 0).
+    Where delta = 0 this is exact: a rotation about the optical axis commutes with the projection, so the mesh under the pose
+    projects onto the record's transform of the template.  Otherwise it is first order: the object is moved parallel to the
+    image plane, which moves the image of a point at depth d by delta d0 / d, not by delta, so the image is the moved template
+    up to delta (d0 - d) / d -- small where the object is shallow against its distance.  In either case the mesh origin
+    projects exactly to (x, y)."""
+    from .matchlist import records_of
+    rec = records_of(records)
+    v = np.asarray(views, dtype=np.float64).reshape(-1, 3, 3)
+    t = np.asarray(positions, dtype=np.float64)
+    t = np.broadcast_to(t, (len(v), 3)) if t.shape == (3,) else t.reshape(-1, 3)
+    if len(t) != len(v):
+        raise ValueError("positions must be (3,) or one per view")
+    idx = rec["tmpl_idx"].astype(np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= len(v)):
+        raise ValueError("a record's tmpl_idx is outside the views")
+    focal = float(focal)
+    tr = rec["transform"].astype(np.float64).reshape(-1, 6)
+    rz = np.zeros((len(rec), 3, 3), dtype=np.float64)
+    rz[:, 0, 0], rz[:, 0, 1], rz[:, 1, 0], rz[:, 1, 1], rz[:, 2, 2] = tr[:, 0], -tr[:, 3], tr[:, 3], tr[:, 0], 1.0
+    tv = t[idx]
+    d0 = -tv[:, 2]
+    o = focal * tv[:, :2] / d0[:, None]
+    delta = tr[:, [2, 5]] - np.asarray(principal, dtype=np.float64) - np.einsum("nij,nj->ni", rz[:, :2, :2], o)
+    T = np.einsum("nij,nj->ni", rz, tv)
+    T[:, :2] += delta * (d0 / focal)[:, None]
+    return rz @ v[idx], T
 
 
 def search_raw(fm, templates, scene, max_tmpl_lines, max_scene_lines, optimizer=capi.BATCH_OPTIMIZE, batch_size=10,

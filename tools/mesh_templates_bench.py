@@ -2,11 +2,18 @@
 faces hide faces), 1000 hemisphere views at a scale that makes it about 300 pixels wide.
 
     python tools/mesh_templates_bench.py [--views 1000] [--referee-views 3] [--out profiles/mesh_templates_bench.json]
+    python tools/mesh_templates_bench.py --distance 5 [--focal F] [--parent DIR]     the pinhole views beside the orthographic ones
 
 Two fresh processes, one after another, each: a warm-up call, then the median wall time of 5 blocking templates_from_mesh calls
 (upload, all passes, download).  The first process also times the numpy referee (tests/mesh_ref.py, the only statement of the
 templates that existed before) on the first views and compares: the tool fails unless they agree byte for byte.  Prints one
-JSON line and writes it to --out."""
+JSON line and writes it to --out.
+
+--distance D (in diagonals of the mesh's bounding box; --focal in pixels, by default SCALE times the distance, which keeps the
+size on the image): "Templates from a mesh: pinhole views".  Fresh processes in turn, twice over: with --parent DIR (another
+checkout of this project, built) that checkout's default call, then this one's default call and, in each of the modes {items,
+exact} x {no joining, 0.5}, the orthographic and the pinhole call.  The first process compares the pinhole lines of the first
+--referee-views views with the referee (tests/mesh_cam_ref.py).  Writes profiles/mesh_camera_bench.json."""
 import argparse
 import json
 import os
@@ -16,7 +23,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+PACKAGE = os.path.abspath(sys.argv[sys.argv.index("--package") + 1]) if "--package" in sys.argv else ROOT   # a child's checkout
+sys.path.insert(0, PACKAGE)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 SCALE, MIN_LENGTH, CALLS = 110.0, 2.0, 5
 
@@ -61,6 +69,88 @@ def child_mode(n_views, referee_views, visibility, join):
     return 0 if out.get("referee_equal", True) else 1
 
 
+def _median_ms(call):
+    call()      # warm-up
+    times = []
+    for _ in range(CALLS):
+        t0 = time.perf_counter()
+        call()
+        times.append(time.perf_counter() - t0)
+    return {"median_ms": 1e3 * statistics.median(times), "min_ms": 1e3 * min(times), "max_ms": 1e3 * max(times)}
+
+
+def child_default(n_views):
+    """The default call alone, with whatever checkout --package names: what the parent commit has too."""
+    from openfdcm_amd import engine
+    v, f = bumpy_sphere()
+    mesh = engine.Mesh(v, f)
+    views = engine.view_rotations(n_views)
+    out = {"package": "this" if PACKAGE == ROOT else "parent", "default": _median_ms(lambda: engine.templates_from_mesh(mesh, views, SCALE, None, MIN_LENGTH))}
+    out["default"]["lines"] = int(engine.mesh_view_lines(mesh, views, SCALE, None, MIN_LENGTH)[1][-1])
+    print("mesh_templates_bench_child " + json.dumps(out), flush=True)
+    return 0
+
+
+def child_camera(n_views, referee_views, distance, focal):
+    import numpy as np
+    import mesh_cam_ref as CR
+    import mesh_ref as MR
+    from openfdcm_amd import engine
+    v, f = bumpy_sphere()
+    mesh = engine.Mesh(v, f)
+    views = engine.view_rotations(n_views)
+    d = v.astype(np.float64).max(axis=0) - v.astype(np.float64).min(axis=0)
+    dist = distance * float(np.sqrt(d @ d))
+    focal = SCALE * dist if focal is None else focal
+    pos = engine.view_positions(n_views, dist)
+    out = {"package": "this", "views": n_views, "faces": int(len(f)), "scale": SCALE, "focal": focal, "distance": dist,
+           "default": _median_ms(lambda: engine.templates_from_mesh(mesh, views, SCALE, None, MIN_LENGTH)), "modes": {}}
+    for visibility in ("items", "exact"):
+        for join in (None, 0.5):
+            o = _median_ms(lambda: engine.templates_from_mesh(mesh, views, SCALE, None, MIN_LENGTH, visibility, join))
+            c = _median_ms(lambda: engine.templates_from_mesh(mesh, views, None, None, MIN_LENGTH, visibility, join, focal=focal, positions=pos))
+            rec, offsets = engine.mesh_view_lines(mesh, views, None, None, MIN_LENGTH, visibility, join, focal=focal, positions=pos)
+            c["lines"] = int(len(rec))
+            c["width_px"] = float(max(rec[:, [0, 2]].max() - rec[:, [0, 2]].min(), rec[:, [1, 3]].max() - rec[:, [1, 3]].min()))
+            o["lines"] = int(engine.mesh_view_lines(mesh, views, SCALE, None, MIN_LENGTH, visibility, join)[1][-1])
+            out["modes"]["%s,join=%s" % (visibility, join)] = {"orthographic": o, "pinhole": c}
+            if referee_views and visibility == "items" and join is None:
+                ref = MR.Mesh(v, f, float(np.cos(np.deg2rad(30))))
+                want = [CR.view_lines(ref, views[i], pos[i], np.float32(focal), mesh.default_near(), mesh.default_depth_tolerance(), MIN_LENGTH)
+                        for i in range(referee_views)]
+                out["referee_views"] = referee_views
+                out["referee_equal"] = bool(np.concatenate(want).tobytes() == rec[:offsets[referee_views]].tobytes())
+    print("mesh_templates_bench_child " + json.dumps(out), flush=True)
+    return 0 if out.get("referee_equal", True) else 1
+
+
+def main_camera(a):
+    """Processes in turn, one after another; nothing is started after a failure."""
+    runs = []
+    for i in range(2):
+        for package in ([a.parent] if a.parent else []) + [ROOT]:
+            cmd = [sys.executable, os.path.abspath(__file__), "--views", str(a.views), "--child", str(i), "--package", package]
+            if package == ROOT:
+                cmd += ["--referee-views", str(a.referee_views), "--distance", str(a.distance)] + (["--focal", str(a.focal)] if a.focal else [])
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+            lines = [l for l in p.stdout.splitlines() if l.startswith("mesh_templates_bench_child ")]
+            if p.returncode != 0 or not lines:
+                sys.stderr.write(p.stdout + p.stderr)
+                print(json.dumps({"error": "a process failed or disagrees with the referee"}))
+                return 1
+            runs.append(json.loads(lines[-1].split(" ", 1)[1]))
+    mine = [r for r in runs if "modes" in r]
+    result = {"bench": "mesh_camera", "processes": runs, "referee_equal": mine[0].get("referee_equal"),
+              "default_median_ms": [r["default"]["median_ms"] for r in mine],
+              "parent_default_median_ms": [r["default"]["median_ms"] for r in runs if "modes" not in r],
+              "median_ms": {k: {p: [r["modes"][k][p]["median_ms"] for r in mine] for p in ("orthographic", "pinhole")} for k in mine[0]["modes"]}}
+    print(json.dumps(result))
+    with open(a.out, "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+    return 0
+
+
 def child(n_views, referee_views):
     import numpy as np
     import mesh_ref as MR
@@ -100,7 +190,19 @@ def main():
     ap.add_argument("--child", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--visibility", choices=("items", "exact"), default=None, help="time this mode beside the default mode")
     ap.add_argument("--join", type=float, default=None, help="the joining tolerance in pixels of the mode timed")
+    ap.add_argument("--distance", type=float, default=None, help="pinhole views: the camera's distance in bounding-box diagonals")
+    ap.add_argument("--focal", type=float, default=None, help="pinhole views: the focal length in pixels (default: SCALE times the distance)")
+    ap.add_argument("--parent", default=None, help="pinhole views: a built checkout whose default call is timed in turn")
+    ap.add_argument("--package", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.distance is not None or a.package is not None:
+        if a.out == ap.get_default("out"):
+            a.out = os.path.join(ROOT, "profiles", "mesh_camera_bench.json")
+        if a.child >= 0 and a.distance is None:
+            return child_default(a.views)
+        if a.child >= 0:
+            return child_camera(a.views, a.referee_views if a.child == 0 else 0, a.distance, a.focal)
+        return main_camera(a)
     mode = a.visibility is not None or a.join is not None
     if mode and a.out == ap.get_default("out"):
         a.out = os.path.join(ROOT, "profiles", "mesh_exact_join_bench.json")
